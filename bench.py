@@ -41,6 +41,11 @@ milliseconds of load to reach its sustained clocks (tools/clock_ramp.py), and a 
 process's first kernel would time that ramp.  The line says so (`leg_order`).  The render contexts run with the library's
 default `timing` = off (no HIP event pair around every render): the timed region is measured with events of its own.
 
+--dump-outputs DIR (N = 1): after the timed steps, the planes the last timed step handed its caller are written as
+DIR/<name>.npy (rgba.npy for a render and for colorize, rgb.npy for the exports; float32), so that two builds can be
+compared output for output: the inputs are fixed by the arguments.  Planes larger than 64 MB in all are written as the
+same seeded sample of 2^20 pixel positions, with their flat indices in DIR/pixel_index.npy.
+
 Rank 0 prints ONE JSON line.  Besides the contract's keys it carries
   roofline       the metric's own roofline ("achieved HBM GB/s vs peak"): algorithmic bytes
                  16 B/pixel (RGBA f32, write-once) / average kernel time measured with HIP events
@@ -228,6 +233,45 @@ def pmc_valu_busy(workload_name: str):
         return None
 
 
+DUMP_BUDGET_BYTES = 64 << 20    # --dump-outputs: at most this much in all
+DUMP_SAMPLE_PIXELS = 1 << 20    # pixels kept when the whole planes would exceed the budget
+DUMP_SEED = 0
+
+
+def dump_outputs(out_dir: str, planes: dict) -> dict:
+    """--dump-outputs: write the planes the timed path handed its caller in its last step as out_dir/<name>.npy.
+    `planes`: name -> device tensor of shape (H, W) or (H, W, C), all of one frame.  Floating planes keep their dtype,
+    integer ones are written as float32 (exact for 8- and 16-bit channels).  If the whole planes exceed DUMP_BUDGET_BYTES,
+    the same fixed, seeded sample of DUMP_SAMPLE_PIXELS pixel positions is taken from every plane ((N, C) arrays) and its
+    flat row-major indices are written beside them as pixel_index.npy (float64)."""
+    import numpy as np
+    import torch
+    first = next(iter(planes.values()))
+    H, W = first.shape[:2]
+
+    def as_float(t):
+        return t if t.dtype in (torch.float32, torch.float64) else t.float()
+
+    total = sum(p.numel() * (8 if p.dtype == torch.float64 else 4) for p in planes.values())
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    idx = None
+    if total > DUMP_BUDGET_BYTES:
+        rng = np.random.default_rng(DUMP_SEED)
+        idx = np.sort(rng.choice(H * W, size=min(DUMP_SAMPLE_PIXELS, H * W), replace=False))
+        np.save(os.path.join(out_dir, "pixel_index.npy"), idx.astype(np.float64))
+        written["pixel_index"] = list(idx.shape)
+        idx_dev = torch.from_numpy(idx).to(first.device)
+    for name, p in planes.items():
+        if idx is not None:
+            p = p.reshape(H * W, -1).index_select(0, idx_dev)
+        a = as_float(p).cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name] = list(a.shape)
+    return {"dir": out_dir, "arrays": written, "sampled": idx is not None,
+            "sample": f"{len(idx)} of {H * W} pixels, seed {DUMP_SEED}" if idx is not None else None}
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -270,7 +314,15 @@ def parse_args(argv=None):
                     help="N > 1, no GPU: gloo ranks run the launcher, the rendezvous and the exchange of --mode on CPU tensors "
                          "filled with a stand-in pattern instead of rendered planes (tests/test_dist_cpu.py drives the "
                          "launcher path with it); the printed value is NOT a measurement")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N = 1: after the timed steps, write the planes of the last timed step as DIR/<name>.npy "
+                         "(float32/float64, at most 64 MB: a fixed, seeded pixel sample of larger planes)")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and (args.gpus != 1 or args.host != "torch" or args.cpu_rehearsal):
+        ap.error("--dump-outputs is for the single-GPU paths (--gpus 1, --host torch)")
+    return args
 
 
 def launch_ranks(args, argv) -> int:
@@ -408,6 +460,7 @@ def kernel_workload(args, w) -> None:
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     kernel_ms = ev0.elapsed_time(ev1) / args.steps
+    dumped = dump_outputs(args.dump_outputs, {"rgba" if kind == "colorize" else "rgb": out}) if args.dump_outputs else None
     verified_against = "the synchronous entry point"
     if kind == "colorize":                      # the recoloured plane IS the rendered one
         verified = bool(torch.equal(out, rgba))
@@ -444,6 +497,8 @@ def kernel_workload(args, w) -> None:
         dtc = time.perf_counter() - t1
         line["cpu_baseline"] = {"value": round(rows * W / dtc / 1e6, 3), "unit": "Mpixels/s", "cores": 1, "kind": "port",
                                 "sample": f"{rows} rows of the same plane, oracle (single thread), {dtc:.2f} s"}
+    if dumped is not None:
+        line["dump_outputs"] = dumped
     print(json.dumps(line), flush=True)
     r.close()
 
@@ -724,6 +779,8 @@ def main() -> None:
         barrier()
         dt = time.perf_counter() - t0
         kernel_ms = ev0.elapsed_time(ev1) / args.steps
+        # outside the timed region, before any later leg reuses the plane: what the last timed step handed its caller
+        dumped = dump_outputs(args.dump_outputs, {"rgba": rgba}) if args.dump_outputs else None
         if check is not None:
             cyc_identical = bool(torch.equal(check, rgba))
             del check
@@ -978,6 +1035,8 @@ def main() -> None:
                                             "the headline value above runs one frame at a time"}
             if not args.no_cpu_baseline:
                 out["cpu_baseline"] = cpu_baseline(w)
+            if dumped is not None:
+                out["dump_outputs"] = dumped
         else:
             # one launch = this rank's 1/N share of a frame (nu payload: 8 or 4 B/pixel; colour payload: 16);
             # duration = the library's event pair around the last launch of each render context on rank 0

@@ -195,6 +195,44 @@ def test_bench_launcher_does_not_touch_torch_or_the_gpu_before_spawning():
     assert seg.index("HSA_ENABLE_IPC_MODE_LEGACY") < seg.index("launch_ranks(") < seg.index("import torch")
 
 
+def test_bench_dump_outputs_whole_planes_and_seeded_sample(tmp_path, monkeypatch):
+    """bench.dump_outputs: planes within the budget are written whole (integer channels as float32); above it every plane
+    gives the same seeded pixel sample, the same from call to call, with its flat indices beside it."""
+    import bench
+    H, W = 24, 40
+    rgba = torch.rand((H, W, 4), generator=torch.Generator().manual_seed(1))
+    rgb8 = (torch.arange(H * W * 3) % 256).to(torch.uint8).reshape(H, W, 3)
+    info = bench.dump_outputs(str(tmp_path / "whole"), {"rgba": rgba, "rgb": rgb8})
+    assert not info["sampled"]
+    assert np.array_equal(np.load(tmp_path / "whole" / "rgba.npy"), rgba.numpy())
+    got8 = np.load(tmp_path / "whole" / "rgb.npy")
+    assert got8.dtype == np.float32 and np.array_equal(got8, rgb8.numpy().astype(np.float32))
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 1000)
+    monkeypatch.setattr(bench, "DUMP_SAMPLE_PIXELS", 50)
+    runs = []
+    for k in range(2):
+        d = tmp_path / f"sample{k}"
+        info = bench.dump_outputs(str(d), {"rgba": rgba, "rgb": rgb8})
+        assert info["sampled"] and info["arrays"] == {"pixel_index": [50], "rgba": [50, 4], "rgb": [50, 3]}
+        idx = np.load(d / "pixel_index.npy")
+        assert idx.dtype == np.float64 and len(set(idx.tolist())) == 50 and np.all(np.diff(idx) > 0)
+        i = idx.astype(np.int64)
+        assert np.array_equal(np.load(d / "rgba.npy"), rgba.numpy().reshape(H * W, 4)[i])
+        assert np.array_equal(np.load(d / "rgb.npy"), rgb8.numpy().reshape(H * W, 3)[i].astype(np.float32))
+        runs.append(idx)
+    assert np.array_equal(runs[0], runs[1])
+
+
+def test_bench_refuses_steps_and_dumps_it_cannot_honour():
+    """--steps K is the number of timed steps: fewer than one is refused; --dump-outputs is refused on the N > 1 and
+    --host node paths; all before anything is launched."""
+    for flags in (["--steps", "0"], ["--warmup", "-1"], ["--gpus", "2", "--dump-outputs", "x"],
+                  ["--host", "node", "--dump-outputs", "x"]):
+        out = _bench(*flags)
+        assert out.returncode == 2 and not out.stdout.strip(), flags
+        assert ("--steps" in out.stderr) or ("--dump-outputs" in out.stderr), out.stderr
+
+
 def test_bench_node_host_refuses_what_it_cannot_do(fr):
     """`bench.py --host node` is ONE process driving all devices through the C ABI: under torch.distributed.run (WORLD_SIZE set)
     it refuses instead of starting one node per rank, and without a GPU it says so (no CPU path); both before any rank is

@@ -1697,6 +1697,45 @@ def test_bench_node_host_and_default_lines(fr):
     assert d["n_gpus"] == 1 and "roofline" in d and "roofline_valu" in d and d["roofline"]["kernel_ms"] > 0
 
 
+@pytest.mark.parametrize("workload", ["c1", "c2"])
+def test_bench_dump_outputs_is_the_rendered_frame(fr, tmp_path, workload):
+    """bench.py --dump-outputs DIR: after K timed steps DIR/rgba.npy holds the colour plane of the last step -- the whole
+    plane for C1 (4 MB), for C2 (256 MB) the seeded 2^20-pixel sample beside its indices -- bitwise equal to a direct
+    render of the same frame; the line reports K steps and their ms_per_step."""
+    import json
+    import subprocess
+    import sys
+    import torch
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    import bench
+    out_dir = str(tmp_path / "dump")
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", workload, "--steps", "3", "--warmup", "1",
+                          "--no-cpu-baseline", "--no-periodicity", "--dump-outputs", out_dir],
+                         capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["dump_outputs"]["dir"] == out_dir
+    w = bench.WORKLOADS[workload]
+    W, H = w["W"], w["H"]
+    want = torch.empty((H, W, 4), dtype=torch.float32, device="cuda")
+    with fr.Renderer(0) as r:
+        r.render(fr.FractalState(**w["state"]), W, H, fractal_type=fr.FractalType[w["fractal"]],
+                 precision=fr.Precision[w["precision"]], rgba=want)
+    want = want.cpu().numpy()
+    got = np.load(os.path.join(out_dir, "rgba.npy"))
+    assert got.dtype == np.float32
+    if workload == "c1":
+        assert not d["dump_outputs"]["sampled"] and sorted(os.listdir(out_dir)) == ["rgba.npy"]
+        assert np.array_equal(got, want)
+    else:
+        idx = np.load(os.path.join(out_dir, "pixel_index.npy"))
+        assert d["dump_outputs"]["sampled"] and idx.dtype == np.float64 and idx.shape == (1 << 20,)
+        assert sum(os.path.getsize(os.path.join(out_dir, f)) for f in os.listdir(out_dir)) <= 64 << 20
+        assert np.array_equal(got, want.reshape(H * W, 4)[idx.astype(np.int64)])
+
+
 @pytest.mark.parametrize("n,slots,lanes", [(1, 2, 2), (4, 3, 2), (8, 8, 4)])
 def test_node_frames_in_flight_device_planes(fr, renderer, n, slots, lanes):
     """fr_node_submit / fr_node_wait_frame with device planes: 12 different frames, up to `slots` in flight on `lanes` render

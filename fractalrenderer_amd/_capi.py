@@ -55,6 +55,10 @@ class fr_params(C.Structure):
     ]
 
 
+class fr_phoenix_params(C.Structure):
+    _fields_ = [("phoenix_p", C.c_float), ("phoenix_r", C.c_float), ("use_julia_set", C.c_int32), ("reserved", C.c_int32)]
+
+
 class fr_output(C.Structure):
     _fields_ = [("rgba", C.c_void_p), ("nu", C.c_void_p), ("iter", C.c_void_p), ("memory", C.c_int32), ("layout", C.c_int32)]
 
@@ -96,6 +100,12 @@ SIGNATURES = {
     "fr_params_reset": (C.c_int, [_P(fr_params)]),
     "fr_params_validate": (C.c_int, [_P(fr_params), C.c_uint32, C.c_uint32]),
     "fr_pack_push_constants": (C.c_int, [_P(fr_params), _P(C.c_float)]),
+    "fr_phoenix_params_default": (C.c_int, [_P(fr_phoenix_params)]),
+    "fr_pack_push_constants_phoenix": (C.c_int, [_P(fr_params), _P(fr_phoenix_params), _P(C.c_float)]),
+    "fr_render_phoenix": (C.c_int, [C.c_void_p, _P(fr_params), _P(fr_phoenix_params), C.c_uint32, C.c_uint32, _P(fr_shard),
+                                    _P(fr_output)]),
+    "fr_render_phoenix_async": (C.c_int, [C.c_void_p, _P(fr_params), _P(fr_phoenix_params), C.c_uint32, C.c_uint32,
+                                          _P(fr_shard), _P(fr_output), C.c_void_p]),
     "fr_ctx_create": (C.c_int, [C.c_int, _P(C.c_void_p)]),
     "fr_ctx_destroy": (None, [C.c_void_p]),
     "fr_shard_rows": (C.c_uint32, [_P(fr_shard), C.c_uint32]),

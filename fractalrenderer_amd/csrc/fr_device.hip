@@ -16,6 +16,7 @@
 #include <string.h>
 
 #include "fr_kernels.hip.h"
+#include "fr_phoenix.hip.h"
 #include "fr_tuning.h"
 
 using namespace fr;
@@ -104,6 +105,7 @@ struct fr_ctx {
     struct DivCheck { bool valid, julia, f64, ok; uint32_t W, H; };
     DivCheck div_cache[8];      /* exact_division_ok() results */
     uint32_t div_next;
+    int phoenix_wg_per_cu[2];   /* resident workgroups per CU of phoenix_kernel<float> / <double> (0 = not asked yet) */
 };
 
 #define FR_HIP_TRY(expr)                                                               \
@@ -646,6 +648,85 @@ static int enqueue_deep_zoom(fr_ctx* c, const fr_params* p, uint32_t W, uint32_t
     hipLaunchKernelGGL((deep_zoom_kernel<3>), dim3(grid), dim3(kBlockThreads), 0, stream, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fr_set_error(FR_ERR_HIP, "deep-zoom kernel launch failed: %s", hipGetErrorString(e));
+    if (c->timing) FR_HIP_TRY(hipEventRecord(c->ev_end, stream));
+    c->have_timing = c->timing;
+    c->have_render = true;
+    c->last_stream = stream;
+    ++c->render_seq;                             /* its first launch forwarded the previous render's verdict (Feedback) */
+    c->last_pool_closing = -1;
+    return FR_OK;
+}
+
+/* ---- Phoenix (fr_phoenix.hip.h) -----------------------------------------------------------------------------------
+ * One pass, no lane pool: a persistent grid of exactly the resident set over the 8x8 sub-tiles of the WaveQueue, the run
+ * lengths and shard counts of an unstaged tile pass (plan_tile_queue: short runs; waves of launches of moderate cost
+ * stop at their home shard + a neighbour, with 64 shards on large frames; long ones steal from every shard). */
+static int enqueue_phoenix(fr_ctx* c, const fr_params* p, const fr_phoenix_params* ph, uint32_t W, uint32_t H,
+                           const fr_shard* shard, float* rgba, void* nu, int32_t* iter, hipStream_t stream, bool out_frame)
+{
+    const int ov = check_overflow(c);            /* of an earlier asynchronous render nobody has asked about */
+    if (ov != FR_OK) return ov;
+    fr_shard norm = shard ? *shard : fr_shard{0u, 1u, H};
+    if (norm.nparts == 0) norm.nparts = 1;
+    if (norm.rows_per_strip == 0) norm.rows_per_strip = (norm.nparts == 1) ? H : 1;
+    if (norm.part >= norm.nparts)
+        return fr_set_error(FR_ERR_INVALID_ARG, "shard part %u >= nparts %u", norm.part, norm.nparts);
+    const uint32_t rows_local = fr_shard_rows(&norm, H);
+    if (rows_local == 0) return FR_OK;
+    const bool f64 = p->precision == FR_PRECISION_F64;
+
+    PhoenixArgs a;
+    memset(&a, 0, sizeof(a));
+    a.center_x = p->center_x; a.center_y = p->center_y; a.zoom = p->zoom;
+    a.julia_cx = p->julia_c_real; a.julia_cy = p->julia_c_imag;
+    a.center_x_f = (float)p->center_x; a.center_y_f = (float)p->center_y; a.zoom_f = (float)p->zoom;   /* data1, data2.xy */
+    a.julia_cx_f = (float)p->julia_c_real; a.julia_cy_f = (float)p->julia_c_imag;
+    a.p = ph->phoenix_p; a.r = ph->phoenix_r;
+    a.stripe_density = p->stripe_density;
+    a.brightness = p->color_brightness; a.saturation = p->color_saturation; a.contrast = p->color_contrast;
+    a.max_iter = p->max_iterations; a.aa = p->antialiasing_samples; a.use_julia = ph->use_julia_set;
+    a.flags = p->flags;
+    a.W = (int32_t)W; a.H = (int32_t)H; a.rows_local = (int32_t)rows_local;
+    a.part = (int32_t)norm.part; a.nparts = (int32_t)norm.nparts; a.rows_per_strip = (int32_t)norm.rows_per_strip;
+    a.out_frame = out_frame ? 1 : 0;
+    a.rgba = reinterpret_cast<float4*>(rgba); a.nu = nu; a.iter = iter;
+
+    int& wg = c->phoenix_wg_per_cu[f64 ? 1 : 0];
+    if (wg == 0) {
+        int nb = 0;
+        const hipError_t e = f64 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, phoenix_kernel<double>, kBlockThreads, 0)
+                                 : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, phoenix_kernel<float>, kBlockThreads, 0);
+        if (e != hipSuccess) return fr_set_error(FR_ERR_HIP, "phoenix occupancy query failed: %s", hipGetErrorString(e));
+        wg = nb < 1 ? 1 : nb;
+    }
+    QueueArgs& q = a.q;
+    q.heads = stage_heads(c, 0);
+    q.nsx = (W + 7) / 8;
+    q.nsx_shift = -1;
+    q.n_items = q.nsx * ((rows_local + 7) / 8);
+    q.n_blk = (q.n_items + kShardBlock - 1) / kShardBlock;
+    uint32_t grid = (uint32_t)c->compute_units * (c->tune_wg_per_cu ? c->tune_wg_per_cu : (uint32_t)wg);
+    const uint32_t max_grid = (q.n_items + 7) / 8;           /* a wave takes at least 2 sub-tiles per dequeue */
+    if (grid > max_grid) grid = max_grid < 1 ? 1 : max_grid;
+    const int aa1 = p->antialiasing_samples > 1 ? p->antialiasing_samples : 1;
+    const bool limited = (long long)p->max_iterations * aa1 * aa1 < 768 && grid >= 64u;
+    uint32_t ns = (limited && grid >= 256u && q.n_blk >= 4u * (uint32_t)kMaxShards) ? (uint32_t)kMaxShards : (uint32_t)kShards;
+    if (c->tune_shards) ns = c->tune_shards;
+    q.ns_log2 = ns == (uint32_t)kMaxShards ? 6u : 3u;
+    q.run_shift = ceil_log2(16u * ((grid * 4u + ns - 1) / ns));
+    q.run_min = 2; q.run_max = 8;
+    uint32_t probes = limited ? (ns == (uint32_t)kMaxShards ? 2u : 1u) : 0u;
+    if (grid < ns) probes = 0;
+    q.flags = probes << kQueueProbeShift;
+    c->last_grid = grid;
+    c->last_stages = 1;
+
+    FR_HIP_TRY(clear_control_block(c, stream, 1));
+    if (c->timing) FR_HIP_TRY(hipEventRecord(c->ev_begin, stream));
+    if (f64) hipLaunchKernelGGL(phoenix_kernel<double>, dim3(grid), dim3(kBlockThreads), 0, stream, a);
+    else hipLaunchKernelGGL(phoenix_kernel<float>, dim3(grid), dim3(kBlockThreads), 0, stream, a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fr_set_error(FR_ERR_HIP, "phoenix kernel launch failed: %s", hipGetErrorString(e));
     if (c->timing) FR_HIP_TRY(hipEventRecord(c->ev_end, stream));
     c->have_timing = c->timing;
     c->have_render = true;
@@ -1345,6 +1426,72 @@ extern "C" int fr_render_shard(fr_ctx* c, const fr_params* p, uint32_t W, uint32
 extern "C" int fr_render(fr_ctx* c, const fr_params* p, uint32_t W, uint32_t H, const fr_output* out)
 {
     return fr_render_shard(c, p, W, H, nullptr, out);
+}
+
+static int check_phoenix(fr_ctx* c, const fr_params* p, const fr_phoenix_params* ph, uint32_t W, uint32_t H,
+                         const fr_shard* shard, const fr_output* out)
+{
+    if (!c) return fr_set_error(FR_ERR_INVALID_ARG, "ctx is NULL");
+    if (!p || !ph || !out) return fr_set_error(FR_ERR_INVALID_ARG, "params/phoenix params/out is NULL");
+    int st = fr_phoenix_validate(p, ph, W, H);
+    if (st != FR_OK) return st;
+    if (out->layout != FR_LAYOUT_PACKED && out->layout != FR_LAYOUT_FRAME)
+        return fr_set_error(FR_ERR_INVALID_ARG, "unknown fr_output.layout %d", out->layout);
+    if (out->layout == FR_LAYOUT_FRAME && out->memory != FR_MEM_DEVICE)
+        return fr_set_error(FR_ERR_INVALID_ARG, "FR_LAYOUT_FRAME needs FR_MEM_DEVICE planes");
+    return check_planes(shard, H, out);
+}
+
+extern "C" int fr_render_phoenix_async(fr_ctx* c, const fr_params* p, const fr_phoenix_params* ph, uint32_t W, uint32_t H,
+                                       const fr_shard* shard, const fr_output* out, void* hip_stream)
+{
+    int st = check_phoenix(c, p, ph, W, H, shard, out);
+    if (st <= 0) return st;
+    if (out->memory != FR_MEM_DEVICE)
+        return fr_set_error(FR_ERR_INVALID_ARG, "fr_render_phoenix_async needs FR_MEM_DEVICE outputs");
+    FR_HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    st = enqueue_phoenix(c, p, ph, W, H, shard, out->rgba, out->nu, out->iter, s, out->layout == FR_LAYOUT_FRAME);
+    if (st == FR_OK) c->render_on_user_stream = s != c->stream;
+    return st;
+}
+
+extern "C" int fr_render_phoenix(fr_ctx* c, const fr_params* p, const fr_phoenix_params* ph, uint32_t W, uint32_t H,
+                                 const fr_shard* shard, const fr_output* out)
+{
+    int st = check_phoenix(c, p, ph, W, H, shard, out);
+    if (st <= 0) return st;
+    FR_HIP_TRY(hipSetDevice(c->device));
+    if (out->memory == FR_MEM_DEVICE) {
+        st = enqueue_phoenix(c, p, ph, W, H, shard, out->rgba, out->nu, out->iter, c->stream, out->layout == FR_LAYOUT_FRAME);
+        if (st != FR_OK) return st;
+        c->render_on_user_stream = false;
+        FR_HIP_TRY(hipStreamSynchronize(c->stream));
+        return check_overflow(c);
+    }
+    if (out->memory != FR_MEM_HOST)
+        return fr_set_error(FR_ERR_INVALID_ARG, "unknown fr_output.memory %d", out->memory);
+    /* host planes: staged through the context's device scratch, as fr_render_shard does */
+    const size_t npx = (size_t)fr_shard_rows(shard, H) * W;
+    const size_t nu_bytes = p->precision == FR_PRECISION_F64 ? 8 : 4;
+    const size_t off_nu = npx * 16, off_iter = off_nu + npx * 8, need = off_iter + npx * 4;
+    if (need > c->scratch_bytes) {
+        if (c->scratch) { (void)hipFree(c->scratch); c->scratch = nullptr; c->scratch_bytes = 0; }
+        FR_HIP_TRY(hipMalloc(&c->scratch, need));
+        c->scratch_bytes = need;
+    }
+    char* base = (char*)c->scratch;
+    float* d_rgba = out->rgba ? (float*)base : nullptr;
+    void* d_nu = out->nu ? (void*)(base + off_nu) : nullptr;
+    int32_t* d_iter = out->iter ? (int32_t*)(base + off_iter) : nullptr;
+    st = enqueue_phoenix(c, p, ph, W, H, shard, d_rgba, d_nu, d_iter, c->stream, false);
+    if (st != FR_OK) return st;
+    c->render_on_user_stream = false;
+    if (out->rgba) FR_HIP_TRY(hipMemcpyAsync(out->rgba, d_rgba, npx * 16, hipMemcpyDeviceToHost, c->stream));
+    if (out->nu) FR_HIP_TRY(hipMemcpyAsync(out->nu, d_nu, npx * nu_bytes, hipMemcpyDeviceToHost, c->stream));
+    if (out->iter) FR_HIP_TRY(hipMemcpyAsync(out->iter, d_iter, npx * 4, hipMemcpyDeviceToHost, c->stream));
+    FR_HIP_TRY(hipStreamSynchronize(c->stream));
+    return check_overflow(c);
 }
 
 /* ---- 8-bit export ------------------------------------------------------------------------------ */

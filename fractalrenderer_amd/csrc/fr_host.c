@@ -157,6 +157,71 @@ int fr_pack_push_constants(const fr_params* p, float out[20])
     }
 }
 
+/* ---- Phoenix ------------------------------------------------------------------------------------ */
+
+/* src/fractal_state.h:82-84 */
+int fr_phoenix_params_default(fr_phoenix_params* ph)
+{
+    if (!ph) return fr_set_error(FR_ERR_INVALID_ARG, "phoenix params is NULL");
+    ph->phoenix_p = 0.0f;
+    ph->phoenix_r = -0.5f;
+    ph->use_julia_set = 0;
+    ph->reserved = 0;
+    return FR_OK;
+}
+
+/* fr_params_validate's rules for the fields shaders/phoenix.comp reads; bailout, color_offset, interior style, trap,
+ * stripe_enabled and use_perturbation are not read and not checked */
+int fr_phoenix_validate(const fr_params* p, const fr_phoenix_params* ph, uint32_t width, uint32_t height)
+{
+    if (!p || !ph) return fr_set_error(FR_ERR_INVALID_ARG, "params/phoenix params is NULL");
+    if (width != 0 || height != 0) {
+        if (width == 0 || height == 0)
+            return fr_set_error(FR_ERR_INVALID_ARG, "width and height must be > 0 (got %ux%u)", width, height);
+        if ((uint64_t)width * (uint64_t)height >= (1ull << 31))
+            return fr_set_error(FR_ERR_INVALID_ARG, "frame %ux%u has 2^31 pixels or more", width, height);
+    }
+    if (p->fractal_type != FR_FRACTAL_PHOENIX)
+        return fr_set_error(FR_ERR_INVALID_ARG, "fr_render_phoenix needs fractal_type FR_FRACTAL_PHOENIX (got %d)", p->fractal_type);
+    if (p->precision != FR_PRECISION_F32 && p->precision != FR_PRECISION_F64)
+        return fr_set_error(FR_ERR_INVALID_ARG, "unknown precision %d", p->precision);
+    if (p->max_iterations < 1 || p->max_iterations > (1 << 24))
+        return fr_set_error(FR_ERR_INVALID_ARG, "max_iterations %d outside [1, 2^24]", p->max_iterations);
+    if (!isfinite(p->zoom) || p->zoom == 0.0)
+        return fr_set_error(FR_ERR_INVALID_ARG, "zoom must be finite and non-zero");
+    if (!isfinite(p->center_x) || !isfinite(p->center_y))
+        return fr_set_error(FR_ERR_INVALID_ARG, "centre must be finite");
+    if (!isfinite(p->julia_c_real) || !isfinite(p->julia_c_imag))
+        return fr_set_error(FR_ERR_INVALID_ARG, "julia c must be finite");
+    if (p->antialiasing_samples < 0 || p->antialiasing_samples > 16)
+        return fr_set_error(FR_ERR_INVALID_ARG, "antialiasing_samples %d outside [0, 16]", p->antialiasing_samples);
+    if (!isfinite(ph->phoenix_p) || !isfinite(ph->phoenix_r))
+        return fr_set_error(FR_ERR_INVALID_ARG, "phoenix p and r must be finite");
+    if (ph->use_julia_set != 0 && ph->use_julia_set != 1)
+        return fr_set_error(FR_ERR_INVALID_ARG, "use_julia_set must be 0 or 1 (got %d)", ph->use_julia_set);
+    if (ph->reserved != 0)
+        return fr_set_error(FR_ERR_INVALID_ARG, "fr_phoenix_params.reserved must be 0");
+    return FR_OK;
+}
+
+/* ComputeEffect::update_from_state, Phoenix case, src/compute_effect_manager.h:201-224 */
+int fr_pack_push_constants_phoenix(const fr_params* p, const fr_phoenix_params* ph, float out[20])
+{
+    if (!out) return fr_set_error(FR_ERR_INVALID_ARG, "out is NULL");
+    const int st = fr_phoenix_validate(p, ph, 0u, 0u);
+    if (st != FR_OK) return st;
+    for (int i = 0; i < 20; ++i) out[i] = 0.0f;
+    out[0] = (float)p->center_x;  out[1] = (float)p->center_y;                 /* data1, :203-208 */
+    out[2] = (float)p->zoom;      out[3] = (float)p->max_iterations;
+    out[4] = (float)p->julia_c_real;  out[5] = (float)p->julia_c_imag;         /* data2, :211-216 */
+    out[6] = ph->phoenix_p;       out[7] = ph->phoenix_r;
+    out[8] = (float)p->antialiasing_samples;  out[9] = p->color_scale;         /* data3, :219-224 */
+    out[10] = p->color_brightness;  out[11] = p->color_saturation;
+    out[12] = p->color_contrast;  out[13] = (float)p->palette_mode;            /* data4 */
+    out[14] = p->stripe_density;  out[15] = ph->use_julia_set ? 1.0f : 0.0f;
+    return FR_OK;                                                              /* data5 = 0 */
+}
+
 /* reference_iterations of a Deep_Zoom render: the trimmed length of the fp64 orbit at the centre,
  * or 0 when perturbation is off (compute_reference_orbit returns early, src/deep_zoom_system.cpp:364) */
 int32_t fr_deep_zoom_reference_length(const fr_params* p)

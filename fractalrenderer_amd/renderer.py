@@ -18,7 +18,7 @@ from typing import Optional
 import numpy as np
 
 from . import _capi
-from .state import FractalState, FractalType, Precision
+from .state import FractalState, FractalType, PhoenixParams, Precision
 
 
 @dataclass(frozen=True)
@@ -190,6 +190,27 @@ class Renderer:
         else:
             _capi.check(self._lib.fr_render_shard_async(self._ctx, C.byref(p), width, height, shp,
                                                         C.byref(out), C.c_void_p(stream or 0)))
+
+    def render_phoenix(self, state: FractalState, width: int, height: int, phoenix: Optional[PhoenixParams] = None, *,
+                       precision: Precision = Precision.F32, post_chain: bool = False,
+                       rgba=None, nu=None, iter=None, shard: Optional[Shard] = None,
+                       stream: Optional[int] = None, sync: bool = True) -> None:
+        """fr_render_phoenix / fr_render_phoenix_async: a frame of shaders/phoenix.comp.  `phoenix` carries FractalState's
+        phoenix_p, phoenix_r and use_julia_set (default: the reference's initialisers, the "Classic Phoenix" preset).
+        Planes, shard, stream and sync as for render(); precision defaults to F32, what the shader computes in."""
+        p = state.to_params(FractalType.Phoenix, precision, post_chain)
+        ph = (phoenix or PhoenixParams()).to_c()
+        rows = shard.rows(height) if shard else height
+        out = self._output(precision, rows, width, rgba, nu, iter)
+        sh = shard.to_c() if shard else None
+        shp = C.byref(sh) if sh is not None else None
+        if sync:
+            if stream is not None:
+                raise ValueError("stream is only meaningful with sync=False")
+            _capi.check(self._lib.fr_render_phoenix(self._ctx, C.byref(p), C.byref(ph), width, height, shp, C.byref(out)))
+        else:
+            _capi.check(self._lib.fr_render_phoenix_async(self._ctx, C.byref(p), C.byref(ph), width, height, shp,
+                                                          C.byref(out), C.c_void_p(stream or 0)))
 
     def dispatch(self, fractal_type: FractalType, state: FractalState, extent: tuple, **kw) -> None:
         """Name-for-name mirror of ComputeEffectManager::dispatch (type, state, extent);

@@ -16,7 +16,9 @@ from . import _capi
 
 class FractalType(enum.IntEnum):
     """src/fractal_state.h:6-14.  Mandelbrot and JuliaSet are the hot path; BurningShip and Deep_Zoom are
-    its variants (section 8 f1/f4); Mandelbulb and Phoenix are rejected with FR_ERR_UNSUPPORTED."""
+    its variants (section 8 f1/f4).  Phoenix renders through Renderer.render_phoenix (fr_render_phoenix: its p, r and
+    Julia-mode flag travel in PhoenixParams, which fr_params has no room for); Renderer.render and the other fr_params
+    entry points reject it with FR_ERR_UNSUPPORTED, as they reject Mandelbulb."""
     Mandelbrot = 0
     JuliaSet = 1
     BurningShip = 2
@@ -113,4 +115,33 @@ def pack_push_constants(state: FractalState, fractal_type: FractalType) -> np.nd
     out = (_capi.C.c_float * 20)()
     p = state.to_params(fractal_type)
     _capi.check(_capi.lib().fr_pack_push_constants(_capi.C.byref(p), out))
+    return np.array(out[:], dtype=np.float32)
+
+
+@dataclass
+class PhoenixParams:
+    """FractalState's Phoenix fields, src/fractal_state.h:82-84 (fr_phoenix_params).  p and r are float in the reference."""
+    phoenix_p: float = 0.0                      # :82  damping
+    phoenix_r: float = -0.5                     # :83  feedback / memory
+    use_julia_set: bool = False                 # :84  C = julia_c for every pixel (which still starts from z = 0)
+
+    def to_c(self) -> _capi.fr_phoenix_params:
+        return _capi.fr_phoenix_params(_F32(self.phoenix_p), _F32(self.phoenix_r), int(self.use_julia_set), 0)
+
+
+# the preset buttons of UIManager::draw_phoenix_controls, src/ui_manager.cpp:1405-1409: name -> PhoenixParams
+PHOENIX_PRESETS = {
+    "Classic Phoenix": PhoenixParams(_F32(0.0), _F32(-0.5)),
+    "Swirl": PhoenixParams(_F32(0.2), _F32(-0.3)),
+    "Tendrils": PhoenixParams(_F32(-0.1), _F32(-0.8)),
+    "Chaos": PhoenixParams(_F32(0.3), _F32(-0.6)),
+}
+
+
+def pack_push_constants_phoenix(state: FractalState, phoenix: PhoenixParams = None) -> np.ndarray:
+    """ComputeEffect::update_from_state, Phoenix case (src/compute_effect_manager.h:201-224): 20 float32."""
+    out = (_capi.C.c_float * 20)()
+    p = state.to_params(FractalType.Phoenix)
+    ph = (phoenix or PhoenixParams()).to_c()
+    _capi.check(_capi.lib().fr_pack_push_constants_phoenix(_capi.C.byref(p), _capi.C.byref(ph), out))
     return np.array(out[:], dtype=np.float32)

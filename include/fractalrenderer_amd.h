@@ -44,7 +44,9 @@ typedef enum fr_status {
 /* FractalType, src/fractal_state.h:6-14 (same numeric values).  Mandelbrot and JuliaSet are the
  * hot path; BurningShip (shaders/burning_ship.comp) is the same loop with z = abs(z) before the
  * square; Deep_Zoom is the reference's perturbation shader (shaders/test_deep_zoom.comp), restated
- * with its fp32 float-float arithmetic; Mandelbulb and Phoenix return FR_ERR_UNSUPPORTED. */
+ * with its fp32 float-float arithmetic.  Phoenix (shaders/phoenix.comp) needs three fields fr_params
+ * has no room for: fr_render and the other fr_params entry points return FR_ERR_UNSUPPORTED for it, and
+ * fr_render_phoenix (below) renders it.  Mandelbulb (a 3-D ray marcher) returns FR_ERR_UNSUPPORTED. */
 typedef enum fr_fractal_type {
     FR_FRACTAL_MANDELBROT   = 0,
     FR_FRACTAL_JULIA        = 1,
@@ -233,6 +235,8 @@ float fr_ctx_last_kernel_ms(fr_ctx* ctx);
 
 /* Options by name; value 0 restores the automatic choice (made per launch from the frame geometry).  None of them can
  * change a pixel (tests/test_gpu_parity.py::test_tuning_variants_are_bit_identical).
+ * Phoenix frames (fr_render_phoenix) accept every option; "periodicity" and "staging" have no effect on them (one pass, no
+ * lane pool, no cycle closing), "shards" and "timing" apply as for the other frames.
  *   "periodicity"   -1 = off, 0 = automatic (ON), 1 = on, N > 1 = on with a first snapshot window of N iterations.
  *                   Cycle closing: the kernels keep, per lane, the orbit state at the wave's last snapshot; a lane whose
  *                   state returns to it is on a cycle, can never escape, and is retired as interior at once instead of
@@ -281,6 +285,54 @@ int fr_ctx_compute_units(fr_ctx* ctx);
 /* Waits for everything this context has enqueued on its OWN stream (fr_render_shard_async with a NULL stream, the
  * exports, fr_colorize_async with a NULL stream) and returns fr_ctx_check()'s verdict. */
 int fr_ctx_synchronize(fr_ctx* ctx);
+
+/* ---- Phoenix (shaders/phoenix.comp) ----------------------------------------------------------------------------------
+ * z' = z^2 + C + r * z_prev + p * z from z = z_prev = 0, update then test |z|^2 > 4 (a fixed bailout), smooth count
+ * i + 1 - log2(log2|z|), colour pow(smooth / max_iter, 0.8) through the ultra_fire palette (always: the shader's
+ * get_palette_color ignores palette_mode, :34-43) with the flow stripes of stripe_density (on when density > 0.01,
+ * whatever stripe_enabled says), in-shader aa x aa supersampling.  The viewport map is Julia's (:106-110).  C is the
+ * pixel's c, or julia_c in Julia mode -- which still starts from z = 0, so EVERY pixel of a Julia-mode frame has the
+ * same colour (as in the reference).  fr_params cannot express a Phoenix frame (FractalState's phoenix_p, phoenix_r and
+ * use_julia_set, src/fractal_state.h:82-84, have no field there): these entry points take them in fr_phoenix_params
+ * and p->fractal_type must be FR_FRACTAL_PHOENIX.  fr_render, fr_params_validate, fr_pack_push_constants keep
+ * answering FR_ERR_UNSUPPORTED for Phoenix. */
+#define FR_HAS_PHOENIX 1
+
+typedef struct fr_phoenix_params {
+    float   phoenix_p;             /* src/fractal_state.h:82  default  0.0   (damping)         */
+    float   phoenix_r;             /*                   :83   default -0.5   (feedback/memory) */
+    int32_t use_julia_set;         /*                   :84   default  0 (bool)               */
+    int32_t reserved;              /* must be 0 */
+} fr_phoenix_params;               /* 16 bytes */
+
+/* FractalState's initialisers for the three fields: (0, -0.5, 0), reserved 0. */
+int fr_phoenix_params_default(fr_phoenix_params* ph);
+
+/* ComputeEffect::update_from_state's Phoenix case, src/compute_effect_manager.h:201-224, as 20 floats bit for bit:
+ * data1 (cx, cy, zoom, max_iter), data2 (julia_c, p, r), data3 (aa, color_scale, brightness, saturation),
+ * data4 (contrast, palette, stripe_density, use_julia ? 1 : 0), data5 = 0.  stripe_density is packed whatever
+ * stripe_enabled says.  Validates as fr_render_phoenix does (no frame size). */
+int fr_pack_push_constants_phoenix(const fr_params* p, const fr_phoenix_params* ph, float out[20]);
+
+/* A Phoenix frame (or one part of a row-strip sharding of it: shard NULL = the whole frame) into `out`, synchronously.
+ * Validation: fr_params_validate's rules for the fields Phoenix reads, fractal_type == FR_FRACTAL_PHOENIX, p and r
+ * finite, use_julia_set 0 or 1, reserved 0; otherwise FR_ERR_INVALID_ARG.  What Phoenix does not read (bailout,
+ * color_offset, interior_style, the orbit trap, stripe_enabled, use_perturbation) is ignored.
+ * Planes as for fr_render (precision, FR_MEM_HOST / FR_MEM_DEVICE, FR_LAYOUT_FRAME, FR_FLAG_POST_CHAIN -- the post chain
+ * with Phoenix's floors: brightness, contrast >= 0.1, saturation >= 0, :160-162): nu = smooth_iter of sample (0,0)
+ * (max_iterations for interior samples), iter = the loop index i of that sample (max_iterations for interior), rgba = the
+ * linear colour before enhance_color.  A sample whose smooth count is negative (a first-step escape far outside the set)
+ * makes the shader's pow() NaN; every palette comparison then fails and it takes the last knot, as in the shader.
+ * FR_PRECISION_F64: map, orbit and smooth count in double; t = smooth / max_iter divided in double, narrowed, and the
+ * colour stage after it in float, as the shader. */
+int fr_render_phoenix(fr_ctx* ctx, const fr_params* p, const fr_phoenix_params* ph, uint32_t width, uint32_t height,
+                      const fr_shard* shard, const fr_output* out);
+
+/* Asynchronous form, the fr_render_shard_async contract: device planes only, enqueued on hip_stream (NULL = the
+ * context's stream), launch-only in steady state (no allocation, no host synchronisation); errors the device reports
+ * later surface through fr_ctx_check.  "timing", fr_ctx_last_kernel_ms and fr_ctx_last_grid cover it. */
+int fr_render_phoenix_async(fr_ctx* ctx, const fr_params* p, const fr_phoenix_params* ph, uint32_t width, uint32_t height,
+                            const fr_shard* shard, const fr_output* out, void* hip_stream);
 
 /* ---- frames over the GPUs of a node (BASELINE.json north_star: "tiled across the 8 GPUs of one node as disjoint row
  * bands with a final RCCL gather over xGMI") -----------------------------------------------------------------------------

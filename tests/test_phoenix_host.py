@@ -1,0 +1,237 @@
+"""Phoenix (fr_render_phoenix): the parts that need no GPU -- ABI layout, defaults, push-constant packing, validation,
+the numpy restatement against the executed shader, and the kernels' register budget."""
+import ctypes as C
+import json
+import os
+import re
+import shutil
+import struct
+import subprocess
+
+import numpy as np
+import pytest
+
+import phoenix_ref
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+FIXTURE = os.path.join(ROOT, "tests", "golden", "phoenix_spv_frames.npz")
+
+
+@pytest.fixture(scope="module")
+def phx():
+    """the executed-shader fixture: {name: (W, H, params, rgba, iter | None, smooth | None)}"""
+    z = np.load(FIXTURE)
+    meta = json.loads(str(z["__meta__"]))
+    out = {}
+    for name, c in meta["cases"].items():
+        it = z[name + "/iter"] if name + "/iter" in z else None
+        sm = z[name + "/smooth"] if name + "/smooth" in z else None
+        out[name] = (c["W"], c["H"], c["params"], z[name + "/rgba"], it, sm)
+    return out
+
+
+def ref_kwargs(p):
+    keys = ("center_x", "center_y", "zoom", "max_iterations", "julia_c_real", "julia_c_imag", "phoenix_p", "phoenix_r",
+            "use_julia_set", "aa", "stripe_density", "color_brightness", "color_saturation", "color_contrast")
+    return {k: p[k] for k in keys}
+
+
+def params_of(fr, p, precision=0):
+    """(fr_params, fr_phoenix_params) of a fixture case"""
+    st = fr.FractalState(center_x=p["center_x"], center_y=p["center_y"], zoom=p["zoom"], max_iterations=p["max_iterations"],
+                         julia_c_real=p["julia_c_real"], julia_c_imag=p["julia_c_imag"], antialiasing_samples=p["aa"],
+                         palette_mode=p["palette_mode"], color_scale=p["color_scale"], stripe_density=p["stripe_density"],
+                         color_brightness=p["color_brightness"], color_saturation=p["color_saturation"],
+                         color_contrast=p["color_contrast"])
+    ph = fr.PhoenixParams(p["phoenix_p"], p["phoenix_r"], bool(p["use_julia_set"]))
+    return st, ph
+
+
+# ---- ABI -----------------------------------------------------------------------------------------------------------
+def test_phoenix_params_layout_matches_the_header(fr, tmp_path):
+    gcc = shutil.which("gcc")
+    if not gcc:
+        pytest.skip("gcc not available")
+    mirror = fr._capi.fr_phoenix_params
+    lines = ['printf("sizeof %zu\\n", sizeof(fr_phoenix_params));']
+    for fname, _ in mirror._fields_:
+        lines.append(f'printf("{fname} %zu\\n", offsetof(fr_phoenix_params, {fname}));')
+    src = tmp_path / "layout.c"
+    src.write_text("#include <stddef.h>\n#include <stdio.h>\n#include \"fractalrenderer_amd.h\"\n"
+                   "#if !defined(FR_HAS_PHOENIX) || FR_HAS_PHOENIX != 1\n#error FR_HAS_PHOENIX\n#endif\n"
+                   "int main(void) {\n" + "\n".join(lines) + "\nreturn 0; }\n")
+    exe = tmp_path / "layout"
+    subprocess.run([gcc, "-std=c11", "-I" + os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
+    got = dict(line.split() for line in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split("\n") if line)
+    assert int(got["sizeof"]) == C.sizeof(mirror) == 16
+    for fname, _ in mirror._fields_:
+        assert int(got[fname]) == getattr(mirror, fname).offset, fname
+    assert C.sizeof(fr._capi.fr_params) == 112
+
+
+def test_phoenix_params_default(fr):
+    ph = fr._capi.fr_phoenix_params(9.0, 9.0, 7, 7)
+    assert fr.lib().fr_phoenix_params_default(C.byref(ph)) == 0
+    assert (ph.phoenix_p, ph.phoenix_r, ph.use_julia_set, ph.reserved) == (0.0, -0.5, 0, 0)
+    d = fr.PhoenixParams()
+    assert (d.phoenix_p, d.phoenix_r, d.use_julia_set) == (0.0, -0.5, False)
+    assert fr.lib().fr_phoenix_params_default(None) == fr._capi.FR_ERR_INVALID_ARG
+
+
+def _reference_layout(p):
+    """src/compute_effect_manager.h:201-224 as little-endian float32 bytes"""
+    f = [p["center_x"], p["center_y"], p["zoom"], p["max_iterations"], p["julia_c_real"], p["julia_c_imag"],
+         p["phoenix_p"], p["phoenix_r"], p["aa"], p["color_scale"], p["color_brightness"], p["color_saturation"],
+         p["color_contrast"], p["palette_mode"], p["stripe_density"], 1.0 if p["use_julia_set"] else 0.0, 0, 0, 0, 0]
+    return struct.pack("<20f", *f)
+
+
+@pytest.mark.parametrize("which", ["default", "custom"])
+def test_pack_push_constants_phoenix_is_the_reference_layout(fr, which):
+    if which == "default":
+        p = dict(center_x=-0.5, center_y=0.0, zoom=3.0, max_iterations=256, julia_c_real=float(np.float32(-0.7)),
+                 julia_c_imag=float(np.float32(0.27015)), phoenix_p=0.0, phoenix_r=-0.5, use_julia_set=0, aa=1,
+                 color_scale=1.0, color_brightness=1.0, color_saturation=1.0, color_contrast=1.0, palette_mode=0,
+                 stripe_density=10.0)
+        st, ph = fr.FractalState(), fr.PhoenixParams()
+    else:
+        p = dict(center_x=0.123456789012, center_y=-1.25e-3, zoom=0.0371, max_iterations=777, julia_c_real=0.31,
+                 julia_c_imag=-0.42, phoenix_p=0.3, phoenix_r=-0.6, use_julia_set=1, aa=3, color_scale=1.7,
+                 color_brightness=1.2, color_saturation=0.8, color_contrast=1.1, palette_mode=5, stripe_density=6.5)
+        st = fr.FractalState(center_x=p["center_x"], center_y=p["center_y"], zoom=p["zoom"], max_iterations=777,
+                             julia_c_real=0.31, julia_c_imag=-0.42, antialiasing_samples=3, color_scale=1.7,
+                             color_brightness=1.2, color_saturation=0.8, color_contrast=1.1, palette_mode=5,
+                             stripe_density=6.5, stripe_enabled=False, bailout=9.0, color_offset=0.4)
+        ph = fr.PhoenixParams(0.3, -0.6, True)
+    py = fr.pack_push_constants_phoenix(st, ph)
+    assert py.tobytes() == _reference_layout(p)
+    out = (C.c_float * 20)()
+    cp, cph = st.to_params(fr.FractalType.Phoenix), ph.to_c()
+    assert fr.lib().fr_pack_push_constants_phoenix(C.byref(cp), C.byref(cph), out) == 0
+    assert bytes(out) == _reference_layout(p)
+
+
+# ---- validation ----------------------------------------------------------------------------------------------------
+def _validate(fr, st, ph):
+    out = (C.c_float * 20)()
+    return fr.lib().fr_pack_push_constants_phoenix(C.byref(st), C.byref(ph), out)
+
+
+def test_phoenix_validation_rules(fr):
+    L, E = fr.lib(), fr._capi
+    base = fr.FractalState().to_params(fr.FractalType.Phoenix)
+    ph0 = fr.PhoenixParams().to_c()
+    assert _validate(fr, base, ph0) == E.FR_OK
+
+    def bad_params(**kw):
+        p = fr.FractalState().to_params(fr.FractalType.Phoenix)
+        for k, v in kw.items():
+            setattr(p, k, v)
+        return p
+
+    for kw in (dict(fractal_type=0), dict(fractal_type=1), dict(fractal_type=3), dict(fractal_type=5), dict(fractal_type=9),
+               dict(precision=2), dict(max_iterations=0), dict(max_iterations=(1 << 24) + 1), dict(zoom=0.0),
+               dict(zoom=float("inf")), dict(center_x=float("nan")), dict(julia_c_imag=float("inf")),
+               dict(antialiasing_samples=17), dict(antialiasing_samples=-1)):
+        assert _validate(fr, bad_params(**kw), ph0) == E.FR_ERR_INVALID_ARG, kw
+    for ph in (E.fr_phoenix_params(float("nan"), -0.5, 0, 0), E.fr_phoenix_params(0.0, float("inf"), 0, 0),
+               E.fr_phoenix_params(0.0, -0.5, 2, 0), E.fr_phoenix_params(0.0, -0.5, -1, 0),
+               E.fr_phoenix_params(0.0, -0.5, 0, 1)):
+        assert _validate(fr, base, ph) == E.FR_ERR_INVALID_ARG
+    # what Phoenix does not read is not checked
+    ignored = bad_params(bailout=float("nan"), color_offset=float("inf"), interior_style=99, orbit_trap_enabled=5,
+                         stripe_enabled=7, use_perturbation=3)
+    assert _validate(fr, ignored, ph0) == E.FR_OK
+    # frame size (render entry points): no context needed to reach the checks that come first
+    o = E.fr_output()
+    for w, h in ((0, 8), (8, 0), (1 << 16, 1 << 15)):
+        assert L.fr_render_phoenix(None, C.byref(base), C.byref(ph0), w, h, None, C.byref(o)) == E.FR_ERR_INVALID_ARG
+    assert L.fr_render_phoenix_async(None, C.byref(base), C.byref(ph0), 8, 8, None, C.byref(o), None) == E.FR_ERR_INVALID_ARG
+
+
+def test_old_entry_points_still_refuse_phoenix(fr):
+    L, E = fr.lib(), fr._capi
+    p = fr.FractalState().to_params(fr.FractalType.Phoenix)
+    assert L.fr_params_validate(C.byref(p), 64, 64) == E.FR_ERR_UNSUPPORTED
+    assert L.fr_pack_push_constants(C.byref(p), (C.c_float * 20)()) == E.FR_ERR_UNSUPPORTED
+    maj, mnr = C.c_int(), C.c_int()
+    L.fr_version(C.byref(maj), C.byref(mnr))
+    assert (maj.value, mnr.value) == (1, 1)
+
+
+# ---- the restatement against the executed shader -------------------------------------------------------------------
+def test_fixture_covers_the_issue_cases(phx):
+    assert json.loads(str(np.load(FIXTURE)["__meta__"]))["sha256"]["phoenix.comp.spv"]
+    ps = [c[2] for c in phx.values()]
+    assert {(p["phoenix_p"], p["phoenix_r"]) for p in ps} >= {(0.0, -0.5), (0.2, -0.3), (-0.1, -0.8), (0.3, -0.6)}
+    assert {p["stripe_density"] for p in ps} >= {10.0, 0.005, 0.0}
+    assert any(p["use_julia_set"] for p in ps) and {2, 3} <= {p["aa"] for p in ps}
+    assert any(p["palette_mode"] != 0 for p in ps) and {1, 2} <= {p["max_iterations"] for p in ps}
+    assert any(c[0] != c[1] for c in phx.values())
+    assert any(c[5] is not None and np.nanmin(c[5]) < 0 for c in phx.values()), "no case with smooth < 0"
+    assert any(c[4] is not None and (c[4] == c[2]["max_iterations"]).mean() > 0.5 for c in phx.values()), "no interior-heavy case"
+
+
+def test_restatement_fp32_matches_the_executed_shader(phx):
+    for name, (W, H, p, rgba, it, sm) in phx.items():
+        r_it, r_sm, r_rgb = phoenix_ref.render(W, H, post=True, **ref_kwargs(p))
+        assert not np.isnan(r_rgb).any() and not np.isnan(rgba).any(), name
+        if it is not None:
+            assert np.array_equal(r_it, it), name
+            ulp = np.spacing(np.maximum(np.abs(sm), 1.0).astype(np.float32))
+            assert np.all(np.abs(r_sm.astype(np.float64) - sm) <= 4 * ulp + 4e-6), name
+        assert np.abs(r_rgb - rgba[..., :3]).max() <= 5e-6, (name, float(np.abs(r_rgb - rgba[..., :3]).max()))
+        assert np.all(rgba[..., 3] == 1.0)
+
+
+def test_restatement_fp64_is_the_same_algorithm_at_wider_precision(phx):
+    """the bar of test_spv_golden.py::test_fp64_restatement_is_the_same_algorithm_at_wider_precision"""
+    agree, total, medians = 0, 0, []
+    for name, (W, H, p, rgba, it, sm) in phx.items():
+        if it is None:
+            continue
+        f_it, _, f_rgb = phoenix_ref.render(W, H, post=True, f64=True, **ref_kwargs(p))
+        same = f_it == it
+        assert same.mean() >= 0.85, name
+        d = np.abs(f_rgb - rgba[..., :3]).max(axis=2)[same]
+        medians.append(float(np.median(d)))
+        agree += int(same.sum())
+        total += same.size
+    assert agree / total >= 0.98
+    assert max(medians) <= 1e-4 and float(np.median(medians)) <= 2e-6
+
+
+def test_julia_mode_frames_are_flat(phx):
+    for name, (W, H, p, rgba, it, sm) in phx.items():
+        if p["use_julia_set"]:
+            assert np.all(rgba == rgba[0, 0]), name
+
+
+# ---- kernels -------------------------------------------------------------------------------------------------------
+def test_phoenix_kernels_keep_their_register_budget(fr):
+    """phoenix_kernel<float> / <double> compile for gfx950 with no scratch and at the occupancy the launcher's resident grid
+    was measured with (enqueue_phoenix asks the runtime; this pins what it gets)."""
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("hipcc not available")
+    csrc = os.path.join(ROOT, "fractalrenderer_amd", "csrc")
+    out = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
+                          "-I" + os.path.join(ROOT, "include"), "-I" + csrc, "-c", os.path.join(csrc, "fr_device.hip"),
+                          "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True)
+    assert out.returncode == 0, out.stderr[-2000:]
+    usage, cur = {}, None
+    for line in out.stderr.splitlines():
+        m = re.search(r"Function Name: (\S+)", line)
+        if m:
+            cur = usage.setdefault(m.group(1), {})
+            continue
+        m = re.search(r"remark:\s+(VGPRs|VGPRs Spill|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]): (\d+)", line)
+        if m and cur is not None:
+            cur[m.group(1)] = int(m.group(2))
+    budget = {"_ZN2fr14phoenix_kernelIdEEvNS_11PhoenixArgsE": (112, 4),    # fp64: 110 VGPRs
+              "_ZN2fr14phoenix_kernelIfEEvNS_11PhoenixArgsE": (88, 5)}     # fp32: 82 VGPRs
+    for name, (max_vgpr, min_occ) in budget.items():
+        u = usage.get(name)
+        assert u, name
+        assert u["ScratchSize [bytes/lane]"] == 0 and u.get("VGPRs Spill", 0) == 0, (name, u)
+        assert u["VGPRs"] <= max_vgpr and u["Occupancy [waves/SIMD]"] >= min_occ, (name, u)

@@ -578,6 +578,31 @@ static hipError_t order_after_last_render(fr_ctx* c, hipStream_t s)
     return hipStreamWaitEvent(s, c->ev_order, 0);
 }
 
+static QueueArgs plan_tile_queue(const fr_ctx* c, uint32_t W, uint32_t rows_local, int shape, bool bounded, bool moderate,
+                                 uint32_t wg_per_cu, uint32_t* grid_out);
+
+/* the caller's shard with its defaults filled in, and the rows it owns (0: nothing to do) */
+static int normalise_shard(const fr_shard* shard, uint32_t H, fr_shard* norm, uint32_t* rows_local)
+{
+    *norm = fr_shard_normalise(shard, H);
+    if (norm->part >= norm->nparts)
+        return fr_set_error(FR_ERR_INVALID_ARG, "shard part %u >= nparts %u", norm->part, norm->nparts);
+    *rows_local = fr_shard_rows(norm, H);
+    return FR_OK;
+}
+
+/* behind the last launch of a render: its end event, and where and in how many stages it went */
+static int finish_render(fr_ctx* c, hipStream_t stream, int nstages)
+{
+    if (c->timing) FR_HIP_TRY(hipEventRecord(c->ev_end, stream));
+    c->have_timing = c->timing;
+    c->have_render = true;
+    c->last_stream = stream;
+    c->last_stages = nstages;
+    ++c->render_seq;                             /* its first launch forwarded the previous render's verdict (Feedback) */
+    return FR_OK;
+}
+
 /* Deep_Zoom: what VulkanEngine::prepare_deep_zoom_rendering + dispatch do per frame
  * (src/vk_engine.cpp:215-251, src/compute_effect_manager.h:236-324): recompute the fp64 reference orbit
  * at the view centre on the host (single point, sequential), narrow it to float pairs
@@ -629,50 +654,33 @@ static int enqueue_deep_zoom(fr_ctx* c, const fr_params* p, uint32_t W, uint32_t
     a.orbit = reinterpret_cast<const float2*>(c->orbit_dev);
     a.rgba = reinterpret_cast<float4*>(rgba); a.nu = (float*)nu; a.iter = iter;
 
-    QueueArgs& q = a.q;
-    q.heads = stage_heads(c, 0);
-    q.nsx = (W + 7) / 8;
-    q.nsx_shift = -1;
-    q.n_items = q.nsx * ((rows_local + 7) / 8);
-    q.n_blk = (q.n_items + kShardBlock - 1) / kShardBlock;
-    uint32_t grid = (uint32_t)c->compute_units * 8u;
-    const uint32_t max_grid = (q.n_items + 7) / 8;           /* a wave takes at least 2 sub-tiles per dequeue */
-    if (grid > max_grid) grid = max_grid < 1 ? 1 : max_grid;
-    q.run_shift = ceil_log2(16u * ((grid * 4u + kShards - 1) / kShards));
-    q.run_min = 2; q.run_max = 8; q.flags = 0; q.ns_log2 = 3;
+    uint32_t grid = 0;
+    a.q = plan_tile_queue(c, W, rows_local, 3, false, false, 8u, &grid);
+    a.q.heads = stage_heads(c, 0);
     c->last_grid = grid;
-    c->last_stages = 1;
+    c->last_pool_closing = -1;
 
     FR_HIP_TRY(clear_control_block(c, stream, 1));
     if (c->timing) FR_HIP_TRY(hipEventRecord(c->ev_begin, stream));
     hipLaunchKernelGGL((deep_zoom_kernel<3>), dim3(grid), dim3(kBlockThreads), 0, stream, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fr_set_error(FR_ERR_HIP, "deep-zoom kernel launch failed: %s", hipGetErrorString(e));
-    if (c->timing) FR_HIP_TRY(hipEventRecord(c->ev_end, stream));
-    c->have_timing = c->timing;
-    c->have_render = true;
-    c->last_stream = stream;
-    ++c->render_seq;                             /* its first launch forwarded the previous render's verdict (Feedback) */
-    c->last_pool_closing = -1;
-    return FR_OK;
+    return finish_render(c, stream, 1);
 }
 
 /* ---- Phoenix (fr_phoenix.hip.h) -----------------------------------------------------------------------------------
- * One pass, no lane pool: a persistent grid of exactly the resident set over the 8x8 sub-tiles of the WaveQueue, the run
- * lengths and shard counts of an unstaged tile pass (plan_tile_queue: short runs; waves of launches of moderate cost
- * stop at their home shard + a neighbour, with 64 shards on large frames; long ones steal from every shard). */
+ * One pass, no lane pool: a persistent grid of exactly the resident set over the 8x8 sub-tiles of the WaveQueue, planned
+ * as an unstaged tile pass (plan_tile_queue: short runs; waves of launches of moderate cost stop at their home shard + a
+ * neighbour, with 64 shards on large frames; long ones steal from every shard). */
 static int enqueue_phoenix(fr_ctx* c, const fr_params* p, const fr_phoenix_params* ph, uint32_t W, uint32_t H,
                            const fr_shard* shard, float* rgba, void* nu, int32_t* iter, hipStream_t stream, bool out_frame)
 {
     const int ov = check_overflow(c);            /* of an earlier asynchronous render nobody has asked about */
     if (ov != FR_OK) return ov;
-    fr_shard norm = shard ? *shard : fr_shard{0u, 1u, H};
-    if (norm.nparts == 0) norm.nparts = 1;
-    if (norm.rows_per_strip == 0) norm.rows_per_strip = (norm.nparts == 1) ? H : 1;
-    if (norm.part >= norm.nparts)
-        return fr_set_error(FR_ERR_INVALID_ARG, "shard part %u >= nparts %u", norm.part, norm.nparts);
-    const uint32_t rows_local = fr_shard_rows(&norm, H);
-    if (rows_local == 0) return FR_OK;
+    fr_shard norm;
+    uint32_t rows_local = 0;
+    const int sh = normalise_shard(shard, H, &norm, &rows_local);
+    if (sh != FR_OK || rows_local == 0) return sh;
     const bool f64 = p->precision == FR_PRECISION_F64;
 
     PhoenixArgs a;
@@ -699,27 +707,12 @@ static int enqueue_phoenix(fr_ctx* c, const fr_params* p, const fr_phoenix_param
         if (e != hipSuccess) return fr_set_error(FR_ERR_HIP, "phoenix occupancy query failed: %s", hipGetErrorString(e));
         wg = nb < 1 ? 1 : nb;
     }
-    QueueArgs& q = a.q;
-    q.heads = stage_heads(c, 0);
-    q.nsx = (W + 7) / 8;
-    q.nsx_shift = -1;
-    q.n_items = q.nsx * ((rows_local + 7) / 8);
-    q.n_blk = (q.n_items + kShardBlock - 1) / kShardBlock;
-    uint32_t grid = (uint32_t)c->compute_units * (c->tune_wg_per_cu ? c->tune_wg_per_cu : (uint32_t)wg);
-    const uint32_t max_grid = (q.n_items + 7) / 8;           /* a wave takes at least 2 sub-tiles per dequeue */
-    if (grid > max_grid) grid = max_grid < 1 ? 1 : max_grid;
     const int aa1 = p->antialiasing_samples > 1 ? p->antialiasing_samples : 1;
-    const bool limited = (long long)p->max_iterations * aa1 * aa1 < 768 && grid >= 64u;
-    uint32_t ns = (limited && grid >= 256u && q.n_blk >= 4u * (uint32_t)kMaxShards) ? (uint32_t)kMaxShards : (uint32_t)kShards;
-    if (c->tune_shards) ns = c->tune_shards;
-    q.ns_log2 = ns == (uint32_t)kMaxShards ? 6u : 3u;
-    q.run_shift = ceil_log2(16u * ((grid * 4u + ns - 1) / ns));
-    q.run_min = 2; q.run_max = 8;
-    uint32_t probes = limited ? (ns == (uint32_t)kMaxShards ? 2u : 1u) : 0u;
-    if (grid < ns) probes = 0;
-    q.flags = probes << kQueueProbeShift;
+    uint32_t grid = 0;
+    a.q = plan_tile_queue(c, W, rows_local, 3, false, (long long)p->max_iterations * aa1 * aa1 < 768, (uint32_t)wg, &grid);
+    a.q.heads = stage_heads(c, 0);
     c->last_grid = grid;
-    c->last_stages = 1;
+    c->last_pool_closing = -1;
 
     FR_HIP_TRY(clear_control_block(c, stream, 1));
     if (c->timing) FR_HIP_TRY(hipEventRecord(c->ev_begin, stream));
@@ -727,13 +720,7 @@ static int enqueue_phoenix(fr_ctx* c, const fr_params* p, const fr_phoenix_param
     else hipLaunchKernelGGL(phoenix_kernel<float>, dim3(grid), dim3(kBlockThreads), 0, stream, a);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fr_set_error(FR_ERR_HIP, "phoenix kernel launch failed: %s", hipGetErrorString(e));
-    if (c->timing) FR_HIP_TRY(hipEventRecord(c->ev_end, stream));
-    c->have_timing = c->timing;
-    c->have_render = true;
-    c->last_stream = stream;
-    ++c->render_seq;                             /* its first launch forwarded the previous render's verdict (Feedback) */
-    c->last_pool_closing = -1;
-    return FR_OK;
+    return finish_render(c, stream, 1);
 }
 
 /* the parameter part of the kernel argument block (everything that does not depend on the frame geometry) */
@@ -777,9 +764,11 @@ static bool needs_effects(const fr_params* p)
 /* ---- geometry of the tile pass ----------------------------------------------------------------------
  * Sub-tiles of 64 pixels (2^shape wide) in blocks of 16 dealt round by round to the 8 or 64 shards, a shard's place
  * rotating with the round (WaveQueue::block_of; blocks >= n_blk are skipped by the kernels); a persistent grid of
- * exactly the resident set; run lengths and probe limit of the queue. */
+ * exactly the resident set (wg_per_cu workgroups per CU unless "workgroups_per_cu" says otherwise); run lengths and
+ * probe limit of the queue.  The Deep_Zoom and Phoenix kernels take the same queue as an unbounded pass on 8x8 sub-tiles.
+ * (The caller sets heads.) */
 static QueueArgs plan_tile_queue(const fr_ctx* c, uint32_t W, uint32_t rows_local, int shape, bool bounded, bool moderate,
-                                 bool six_fit, uint32_t* grid_out, uint32_t* waves_per_shard_out)
+                                 uint32_t wg_per_cu, uint32_t* grid_out)
 {
     const uint32_t fpw = 1u << shape, fph = 64u >> shape;
     QueueArgs tq;
@@ -792,13 +781,7 @@ static QueueArgs plan_tile_queue(const fr_ctx* c, uint32_t W, uint32_t rows_loca
     tq.n_items = tq.nsx * nsy;
     tq.n_blk = (tq.n_items + kShardBlock - 1) / kShardBlock;
 
-    /* The fp64 tile kernel holds 5 workgroups of 256 threads per CU (the per-wave timeline of the diag buffer
-     * shows workgroups beyond the resident set only start when resident ones exit, and find the queue dry):
-     * launch exactly the resident set.  Measured 5 vs 4: C2 +1.9 %, C3 +5.6 %, C5 +1.7 %; 6-8 (the one-sample
-     * kernel fits 7 at 69 VGPRs) within 1 %. */
-    /* the staged lean tile kernel in fp32 (52 VGPRs, 8.5 KB of LDS) holds 6: C3 -1.4 % */
-    const uint32_t wg_per_cu = c->tune_wg_per_cu ? c->tune_wg_per_cu : (six_fit ? 6u : 5u);
-    uint32_t grid = (uint32_t)c->compute_units * wg_per_cu;
+    uint32_t grid = (uint32_t)c->compute_units * (c->tune_wg_per_cu ? c->tune_wg_per_cu : wg_per_cu);
     /* never more waves than the shortest runs can feed: a wave takes at least run_min sub-tiles per dequeue (4 when
      * bounded, 2 otherwise), and waves that find nothing still cost their launch and their exit probes -- at 512^2
      * a grid of one wave per sub-tile left 3 of 4 waves without work: 0.083 ms per frame against 0.048 ms */
@@ -848,7 +831,6 @@ static QueueArgs plan_tile_queue(const fr_ctx* c, uint32_t W, uint32_t rows_loca
     if (grid < ns) probes = 0;
     tq.flags |= probes << kQueueProbeShift;
     *grid_out = grid;
-    *waves_per_shard_out = waves_per_shard;
     return tq;
 }
 
@@ -950,15 +932,10 @@ static int enqueue_render(fr_ctx* c, const fr_params* p, uint32_t W, uint32_t H,
         const int ov = check_overflow(c);          /* of an earlier asynchronous render nobody has asked about */
         if (ov != FR_OK) return ov;
     }
-    fr_shard whole = {0u, 1u, H};
-    const fr_shard* sh = shard ? shard : &whole;
-    fr_shard norm = *sh;
-    if (norm.nparts == 0) norm.nparts = 1;
-    if (norm.rows_per_strip == 0) norm.rows_per_strip = (norm.nparts == 1) ? H : 1;
-    if (norm.part >= norm.nparts)
-        return fr_set_error(FR_ERR_INVALID_ARG, "shard part %u >= nparts %u", norm.part, norm.nparts);
-    const uint32_t rows_local = fr_shard_rows(&norm, H);
-    if (rows_local == 0) return FR_OK;           /* this part owns no rows */
+    fr_shard norm;
+    uint32_t rows_local = 0;
+    const int sh = normalise_shard(shard, H, &norm, &rows_local);
+    if (sh != FR_OK || rows_local == 0) return sh;           /* (rows_local 0: this part owns no rows) */
     if (p->fractal_type == FR_FRACTAL_DEEP_ZOOM)
         return enqueue_deep_zoom(c, p, W, H, &norm, rows_local, rgba, nu, iter, stream, reserve_only, out_frame);
 
@@ -1081,11 +1058,16 @@ static int enqueue_render(fr_ctx* c, const fr_params* p, uint32_t W, uint32_t H,
     /* items of moderate cost (an unstaged pass below the staging threshold): short runs as for unbounded items, but
      * the waves stop at their home shard -- the blocks of 16 sub-tiles dealt round-robin keep the shards level */
     const bool moderate = !staged && !effects && (long long)max_iter * aa1 * aa1 < 768;
-    uint32_t grid = 0, waves_per_shard = 0;
-    /* (fp32 only: the fp64 instantiation's 82 VGPRs leave room for 5 waves per SIMD) */
+    /* The fp64 tile kernel holds 5 workgroups of 256 threads per CU (the per-wave timeline of the diag buffer
+     * shows workgroups beyond the resident set only start when resident ones exit, and find the queue dry):
+     * launch exactly the resident set.  Measured 5 vs 4: C2 +1.9 %, C3 +5.6 %, C5 +1.7 %; 6-8 (the one-sample
+     * kernel fits 7 at 69 VGPRs) within 1 %. */
+    /* the staged lean tile kernel in fp32 (52 VGPRs, 8.5 KB of LDS) holds 6: C3 -1.4 %
+     * (fp32 only: the fp64 instantiation's 82 VGPRs leave room for 5 waves per SIMD) */
     const bool lean_staged = !f64 && staged && !effects && p->antialiasing_samples <= 1 && shape == 3 && c->tune_tile_kernel != 1u &&
                              (norm.nparts == 1 || norm.rows_per_strip % 8u == 0u);
-    const QueueArgs tq = plan_tile_queue(c, W, rows_local, shape, bounded, moderate, lean_staged, &grid, &waves_per_shard);
+    uint32_t grid = 0;
+    const QueueArgs tq = plan_tile_queue(c, W, rows_local, shape, bounded, moderate, lean_staged ? 6u : 5u, &grid);
     auto clamp_shift = [&](int v) { v += c->tune_shift_bias; return (uint32_t)(v < 0 ? 0 : (v > 31 ? 31 : v)); };
     c->last_grid = grid;
 
@@ -1247,13 +1229,7 @@ static int enqueue_render(fr_ctx* c, const fr_params* p, uint32_t W, uint32_t H,
                 return launch_stream_pool<decltype(t), decltype(f)::value>(dim3(sgrid), stream, a); });
         if (e != hipSuccess) return fr_set_error(FR_ERR_HIP, "lane-pool kernel launch failed: %s", hipGetErrorString(e));
     }
-    if (c->timing) FR_HIP_TRY(hipEventRecord(c->ev_end, stream));
-    c->have_timing = c->timing;
-    c->have_render = true;
-    c->last_stream = stream;
-    c->last_stages = nstage;
-    ++c->render_seq;
-    return FR_OK;
+    return finish_render(c, stream, nstage);
 }
 
 static int enqueue_ssaa_staged(fr_ctx* c, const fr_params* p, uint32_t W, uint32_t H, const fr_shard* norm, uint32_t rows_local,
@@ -1300,12 +1276,26 @@ static int enqueue_ssaa_staged(fr_ctx* c, const fr_params* p, uint32_t W, uint32
     return FR_OK;
 }
 
+/* ---- render entry points --------------------------------------------------------------------------------------------
+ * fr_render_shard(_async) and fr_render_phoenix(_async): their parameter checks, then render_sync / render_async with the
+ * enqueue step as enqueue(shard, rgba, nu, iter, stream, out_frame) */
 static int check_common(fr_ctx* c, const fr_params* p, uint32_t W, uint32_t H, const fr_output* out)
 {
     if (!c) return fr_set_error(FR_ERR_INVALID_ARG, "ctx is NULL");
     if (!p || !out) return fr_set_error(FR_ERR_INVALID_ARG, "params/out is NULL");
-    int st = fr_params_validate(p, W, H);
-    if (st != FR_OK) return st;
+    return fr_params_validate(p, W, H);
+}
+
+static int check_phoenix(fr_ctx* c, const fr_params* p, const fr_phoenix_params* ph, uint32_t W, uint32_t H,
+                         const fr_output* out)
+{
+    if (!c) return fr_set_error(FR_ERR_INVALID_ARG, "ctx is NULL");
+    if (!p || !ph || !out) return fr_set_error(FR_ERR_INVALID_ARG, "params/phoenix params/out is NULL");
+    return fr_phoenix_validate(p, ph, W, H);
+}
+
+static int check_layout(const fr_output* out)
+{
     if (out->layout != FR_LAYOUT_PACKED && out->layout != FR_LAYOUT_FRAME)
         return fr_set_error(FR_ERR_INVALID_ARG, "unknown fr_output.layout %d", out->layout);
     if (out->layout == FR_LAYOUT_FRAME && out->memory != FR_MEM_DEVICE)
@@ -1324,20 +1314,73 @@ static int check_planes(const fr_shard* shard, uint32_t H, const fr_output* out)
     return 1;
 }
 
-extern "C" int fr_render_shard_async(fr_ctx* c, const fr_params* p, uint32_t W, uint32_t H,
-                                     const fr_shard* shard, const fr_output* out, void* hip_stream)
+/* device planes only, on the caller's stream (NULL: the context's); returns once the render is enqueued */
+template <class Enqueue>
+static int render_async(const char* entry, fr_ctx* c, uint32_t H, const fr_shard* shard, const fr_output* out, void* hip_stream,
+                        Enqueue&& enqueue)
 {
-    int st = check_common(c, p, W, H, out);
+    int st = check_layout(out);
     if (st != FR_OK) return st;
     if (out->memory != FR_MEM_DEVICE)
-        return fr_set_error(FR_ERR_INVALID_ARG, "fr_render_shard_async needs FR_MEM_DEVICE outputs");
+        return fr_set_error(FR_ERR_INVALID_ARG, "%s needs FR_MEM_DEVICE outputs", entry);
     st = check_planes(shard, H, out);
     if (st <= 0) return st;
     FR_HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    st = enqueue_render(c, p, W, H, shard, out->rgba, out->nu, out->iter, s, false, out->layout == FR_LAYOUT_FRAME);
+    st = enqueue(shard, out->rgba, out->nu, out->iter, s, out->layout == FR_LAYOUT_FRAME);
     if (st == FR_OK) c->render_on_user_stream = s != c->stream;
     return st;
+}
+
+/* on the context's stream, waited for: device planes are written in place, host planes are staged through device scratch
+ * owned by the context (PCIe-inclusive path) */
+template <class Enqueue>
+static int render_sync(fr_ctx* c, const fr_params* p, uint32_t W, uint32_t H, const fr_shard* shard, const fr_output* out,
+                       Enqueue&& enqueue)
+{
+    int st = check_layout(out);
+    if (st != FR_OK) return st;
+    st = check_planes(shard, H, out);
+    if (st <= 0) return st;
+    FR_HIP_TRY(hipSetDevice(c->device));
+    const bool host = out->memory == FR_MEM_HOST;
+    if (!host && out->memory != FR_MEM_DEVICE)
+        return fr_set_error(FR_ERR_INVALID_ARG, "unknown fr_output.memory %d", out->memory);
+    float* rgba = out->rgba; void* nu = out->nu; int32_t* iter = out->iter;
+    const size_t npx = (size_t)fr_shard_rows(shard, H) * W;
+    const size_t nu_bytes = (p->precision == FR_PRECISION_F64 && p->fractal_type != FR_FRACTAL_DEEP_ZOOM) ? 8 : 4;
+    if (host) {
+        const size_t off_nu = npx * 16, off_iter = off_nu + npx * 8, need = off_iter + npx * 4;
+        if (need > c->scratch_bytes) {
+            if (c->scratch) { (void)hipFree(c->scratch); c->scratch = nullptr; c->scratch_bytes = 0; }
+            FR_HIP_TRY(hipMalloc(&c->scratch, need));
+            c->scratch_bytes = need;
+        }
+        char* base = (char*)c->scratch;
+        rgba = out->rgba ? (float*)base : nullptr;
+        nu = out->nu ? (void*)(base + off_nu) : nullptr;
+        iter = out->iter ? (int32_t*)(base + off_iter) : nullptr;
+    }
+    st = enqueue(shard, rgba, nu, iter, c->stream, out->layout == FR_LAYOUT_FRAME);   /* (host planes are packed) */
+    if (st != FR_OK) return st;
+    c->render_on_user_stream = false;
+    if (host) {
+        if (out->rgba) FR_HIP_TRY(hipMemcpyAsync(out->rgba, rgba, npx * 16, hipMemcpyDeviceToHost, c->stream));
+        if (out->nu) FR_HIP_TRY(hipMemcpyAsync(out->nu, nu, npx * nu_bytes, hipMemcpyDeviceToHost, c->stream));
+        if (out->iter) FR_HIP_TRY(hipMemcpyAsync(out->iter, iter, npx * 4, hipMemcpyDeviceToHost, c->stream));
+    }
+    FR_HIP_TRY(hipStreamSynchronize(c->stream));
+    return check_overflow(c);
+}
+
+extern "C" int fr_render_shard_async(fr_ctx* c, const fr_params* p, uint32_t W, uint32_t H,
+                                     const fr_shard* shard, const fr_output* out, void* hip_stream)
+{
+    const int st = check_common(c, p, W, H, out);
+    if (st != FR_OK) return st;
+    return render_async("fr_render_shard_async", c, H, shard, out, hip_stream,
+                        [&](auto sh, auto rgba, auto nu, auto iter, auto s, bool out_frame) {
+                            return enqueue_render(c, p, W, H, sh, rgba, nu, iter, s, false, out_frame); });
 }
 
 extern "C" int fr_ctx_reserve(fr_ctx* c, const fr_params* p, uint32_t W, uint32_t H, const fr_shard* shard)
@@ -1378,49 +1421,10 @@ extern "C" int fr_ctx_device(const fr_ctx* c) { return c ? c->device : -1; }
 extern "C" int fr_render_shard(fr_ctx* c, const fr_params* p, uint32_t W, uint32_t H,
                                const fr_shard* shard, const fr_output* out)
 {
-    int st = check_common(c, p, W, H, out);
+    const int st = check_common(c, p, W, H, out);
     if (st != FR_OK) return st;
-    st = check_planes(shard, H, out);
-    if (st <= 0) return st;
-    FR_HIP_TRY(hipSetDevice(c->device));
-
-    if (out->memory == FR_MEM_DEVICE) {
-        st = enqueue_render(c, p, W, H, shard, out->rgba, out->nu, out->iter, c->stream, false, out->layout == FR_LAYOUT_FRAME);
-        if (st != FR_OK) return st;
-        c->render_on_user_stream = false;
-        FR_HIP_TRY(hipStreamSynchronize(c->stream));
-        return check_overflow(c);
-    }
-    if (out->memory != FR_MEM_HOST)
-        return fr_set_error(FR_ERR_INVALID_ARG, "unknown fr_output.memory %d", out->memory);
-
-    /* host outputs: stage through device scratch owned by the context (PCIe-inclusive path) */
-    fr_shard whole = {0u, 1u, H};
-    const fr_shard* sh = shard ? shard : &whole;
-    fr_shard norm = *sh;
-    if (norm.nparts == 0) norm.nparts = 1;
-    if (norm.rows_per_strip == 0) norm.rows_per_strip = (norm.nparts == 1) ? H : 1;
-    const size_t npx = (size_t)fr_shard_rows(&norm, H) * W;
-    if (npx == 0) return FR_OK;
-    const size_t nu_bytes = (p->precision == FR_PRECISION_F64 && p->fractal_type != FR_FRACTAL_DEEP_ZOOM) ? 8 : 4;
-    const size_t off_nu = npx * 16, off_iter = off_nu + npx * 8, need = off_iter + npx * 4;
-    if (need > c->scratch_bytes) {
-        if (c->scratch) { (void)hipFree(c->scratch); c->scratch = nullptr; c->scratch_bytes = 0; }
-        FR_HIP_TRY(hipMalloc(&c->scratch, need));
-        c->scratch_bytes = need;
-    }
-    char* base = (char*)c->scratch;
-    float* d_rgba = out->rgba ? (float*)base : nullptr;
-    void* d_nu = out->nu ? (void*)(base + off_nu) : nullptr;
-    int32_t* d_iter = out->iter ? (int32_t*)(base + off_iter) : nullptr;
-    st = enqueue_render(c, p, W, H, &norm, d_rgba, d_nu, d_iter, c->stream);
-    if (st != FR_OK) return st;
-    c->render_on_user_stream = false;
-    if (out->rgba) FR_HIP_TRY(hipMemcpyAsync(out->rgba, d_rgba, npx * 16, hipMemcpyDeviceToHost, c->stream));
-    if (out->nu) FR_HIP_TRY(hipMemcpyAsync(out->nu, d_nu, npx * nu_bytes, hipMemcpyDeviceToHost, c->stream));
-    if (out->iter) FR_HIP_TRY(hipMemcpyAsync(out->iter, d_iter, npx * 4, hipMemcpyDeviceToHost, c->stream));
-    FR_HIP_TRY(hipStreamSynchronize(c->stream));
-    return check_overflow(c);
+    return render_sync(c, p, W, H, shard, out, [&](auto sh, auto rgba, auto nu, auto iter, auto s, bool out_frame) {
+        return enqueue_render(c, p, W, H, sh, rgba, nu, iter, s, false, out_frame); });
 }
 
 extern "C" int fr_render(fr_ctx* c, const fr_params* p, uint32_t W, uint32_t H, const fr_output* out)
@@ -1428,70 +1432,23 @@ extern "C" int fr_render(fr_ctx* c, const fr_params* p, uint32_t W, uint32_t H, 
     return fr_render_shard(c, p, W, H, nullptr, out);
 }
 
-static int check_phoenix(fr_ctx* c, const fr_params* p, const fr_phoenix_params* ph, uint32_t W, uint32_t H,
-                         const fr_shard* shard, const fr_output* out)
-{
-    if (!c) return fr_set_error(FR_ERR_INVALID_ARG, "ctx is NULL");
-    if (!p || !ph || !out) return fr_set_error(FR_ERR_INVALID_ARG, "params/phoenix params/out is NULL");
-    int st = fr_phoenix_validate(p, ph, W, H);
-    if (st != FR_OK) return st;
-    if (out->layout != FR_LAYOUT_PACKED && out->layout != FR_LAYOUT_FRAME)
-        return fr_set_error(FR_ERR_INVALID_ARG, "unknown fr_output.layout %d", out->layout);
-    if (out->layout == FR_LAYOUT_FRAME && out->memory != FR_MEM_DEVICE)
-        return fr_set_error(FR_ERR_INVALID_ARG, "FR_LAYOUT_FRAME needs FR_MEM_DEVICE planes");
-    return check_planes(shard, H, out);
-}
-
 extern "C" int fr_render_phoenix_async(fr_ctx* c, const fr_params* p, const fr_phoenix_params* ph, uint32_t W, uint32_t H,
                                        const fr_shard* shard, const fr_output* out, void* hip_stream)
 {
-    int st = check_phoenix(c, p, ph, W, H, shard, out);
-    if (st <= 0) return st;
-    if (out->memory != FR_MEM_DEVICE)
-        return fr_set_error(FR_ERR_INVALID_ARG, "fr_render_phoenix_async needs FR_MEM_DEVICE outputs");
-    FR_HIP_TRY(hipSetDevice(c->device));
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    st = enqueue_phoenix(c, p, ph, W, H, shard, out->rgba, out->nu, out->iter, s, out->layout == FR_LAYOUT_FRAME);
-    if (st == FR_OK) c->render_on_user_stream = s != c->stream;
-    return st;
+    const int st = check_phoenix(c, p, ph, W, H, out);
+    if (st != FR_OK) return st;
+    return render_async("fr_render_phoenix_async", c, H, shard, out, hip_stream,
+                        [&](auto sh, auto rgba, auto nu, auto iter, auto s, bool out_frame) {
+                            return enqueue_phoenix(c, p, ph, W, H, sh, rgba, nu, iter, s, out_frame); });
 }
 
 extern "C" int fr_render_phoenix(fr_ctx* c, const fr_params* p, const fr_phoenix_params* ph, uint32_t W, uint32_t H,
                                  const fr_shard* shard, const fr_output* out)
 {
-    int st = check_phoenix(c, p, ph, W, H, shard, out);
-    if (st <= 0) return st;
-    FR_HIP_TRY(hipSetDevice(c->device));
-    if (out->memory == FR_MEM_DEVICE) {
-        st = enqueue_phoenix(c, p, ph, W, H, shard, out->rgba, out->nu, out->iter, c->stream, out->layout == FR_LAYOUT_FRAME);
-        if (st != FR_OK) return st;
-        c->render_on_user_stream = false;
-        FR_HIP_TRY(hipStreamSynchronize(c->stream));
-        return check_overflow(c);
-    }
-    if (out->memory != FR_MEM_HOST)
-        return fr_set_error(FR_ERR_INVALID_ARG, "unknown fr_output.memory %d", out->memory);
-    /* host planes: staged through the context's device scratch, as fr_render_shard does */
-    const size_t npx = (size_t)fr_shard_rows(shard, H) * W;
-    const size_t nu_bytes = p->precision == FR_PRECISION_F64 ? 8 : 4;
-    const size_t off_nu = npx * 16, off_iter = off_nu + npx * 8, need = off_iter + npx * 4;
-    if (need > c->scratch_bytes) {
-        if (c->scratch) { (void)hipFree(c->scratch); c->scratch = nullptr; c->scratch_bytes = 0; }
-        FR_HIP_TRY(hipMalloc(&c->scratch, need));
-        c->scratch_bytes = need;
-    }
-    char* base = (char*)c->scratch;
-    float* d_rgba = out->rgba ? (float*)base : nullptr;
-    void* d_nu = out->nu ? (void*)(base + off_nu) : nullptr;
-    int32_t* d_iter = out->iter ? (int32_t*)(base + off_iter) : nullptr;
-    st = enqueue_phoenix(c, p, ph, W, H, shard, d_rgba, d_nu, d_iter, c->stream, false);
+    const int st = check_phoenix(c, p, ph, W, H, out);
     if (st != FR_OK) return st;
-    c->render_on_user_stream = false;
-    if (out->rgba) FR_HIP_TRY(hipMemcpyAsync(out->rgba, d_rgba, npx * 16, hipMemcpyDeviceToHost, c->stream));
-    if (out->nu) FR_HIP_TRY(hipMemcpyAsync(out->nu, d_nu, npx * nu_bytes, hipMemcpyDeviceToHost, c->stream));
-    if (out->iter) FR_HIP_TRY(hipMemcpyAsync(out->iter, d_iter, npx * 4, hipMemcpyDeviceToHost, c->stream));
-    FR_HIP_TRY(hipStreamSynchronize(c->stream));
-    return check_overflow(c);
+    return render_sync(c, p, W, H, shard, out, [&](auto sh, auto rgba, auto nu, auto iter, auto s, bool out_frame) {
+        return enqueue_phoenix(c, p, ph, W, H, sh, rgba, nu, iter, s, out_frame); });
 }
 
 /* ---- 8-bit export ------------------------------------------------------------------------------ */

@@ -79,19 +79,19 @@ int fr_params_reset(fr_params* p)
     return FR_OK;
 }
 
-int fr_params_validate(const fr_params* p, uint32_t width, uint32_t height)
+/* ---- validation: the rules fr_params_validate and fr_phoenix_validate share, in the order both report them ---- */
+static int check_frame(uint32_t width, uint32_t height)
 {
-    if (!p) return fr_set_error(FR_ERR_INVALID_ARG, "params is NULL");
     if (width == 0 || height == 0)
         return fr_set_error(FR_ERR_INVALID_ARG, "width and height must be > 0 (got %ux%u)", width, height);
     if ((uint64_t)width * (uint64_t)height >= (1ull << 31))
         return fr_set_error(FR_ERR_INVALID_ARG, "frame %ux%u has 2^31 pixels or more", width, height);
-    if (p->fractal_type < 0 || p->fractal_type > FR_FRACTAL_DEEP_ZOOM)
-        return fr_set_error(FR_ERR_INVALID_ARG, "unknown fractal_type %d", p->fractal_type);
-    if (p->fractal_type == FR_FRACTAL_MANDELBULB || p->fractal_type == FR_FRACTAL_PHOENIX)
-        return fr_set_error(FR_ERR_UNSUPPORTED,
-                            "fractal_type %d is outside the hot path (Mandelbrot, JuliaSet, BurningShip and Deep_Zoom only)",
-                            p->fractal_type);
+    return FR_OK;
+}
+
+/* precision, iteration count and the viewport */
+static int check_view(const fr_params* p)
+{
     if (p->precision != FR_PRECISION_F32 && p->precision != FR_PRECISION_F64)
         return fr_set_error(FR_ERR_INVALID_ARG, "unknown precision %d", p->precision);
     if (p->max_iterations < 1 || p->max_iterations > (1 << 24))
@@ -102,11 +102,31 @@ int fr_params_validate(const fr_params* p, uint32_t width, uint32_t height)
         return fr_set_error(FR_ERR_INVALID_ARG, "centre must be finite");
     if (!isfinite(p->julia_c_real) || !isfinite(p->julia_c_imag))
         return fr_set_error(FR_ERR_INVALID_ARG, "julia c must be finite");
-    if (!isfinite(p->bailout) || !(p->bailout > 0.0f))
-        return fr_set_error(FR_ERR_INVALID_ARG, "bailout must be finite and > 0");
+    return FR_OK;
+}
+
+static int check_samples(const fr_params* p)
+{
     if (p->antialiasing_samples < 0 || p->antialiasing_samples > 16)
         return fr_set_error(FR_ERR_INVALID_ARG, "antialiasing_samples %d outside [0, 16]", p->antialiasing_samples);
     return FR_OK;
+}
+
+int fr_params_validate(const fr_params* p, uint32_t width, uint32_t height)
+{
+    if (!p) return fr_set_error(FR_ERR_INVALID_ARG, "params is NULL");
+    int st = check_frame(width, height);
+    if (st != FR_OK) return st;
+    if (p->fractal_type < 0 || p->fractal_type > FR_FRACTAL_DEEP_ZOOM)
+        return fr_set_error(FR_ERR_INVALID_ARG, "unknown fractal_type %d", p->fractal_type);
+    if (p->fractal_type == FR_FRACTAL_MANDELBULB || p->fractal_type == FR_FRACTAL_PHOENIX)
+        return fr_set_error(FR_ERR_UNSUPPORTED,
+                            "fractal_type %d is outside the hot path (Mandelbrot, JuliaSet, BurningShip and Deep_Zoom only)",
+                            p->fractal_type);
+    if ((st = check_view(p)) != FR_OK) return st;
+    if (!isfinite(p->bailout) || !(p->bailout > 0.0f))
+        return fr_set_error(FR_ERR_INVALID_ARG, "bailout must be finite and > 0");
+    return check_samples(p);
 }
 
 /* ComputeEffect::update_from_state, src/compute_effect_manager.h:84-113 / :115-140 */
@@ -175,26 +195,11 @@ int fr_phoenix_params_default(fr_phoenix_params* ph)
 int fr_phoenix_validate(const fr_params* p, const fr_phoenix_params* ph, uint32_t width, uint32_t height)
 {
     if (!p || !ph) return fr_set_error(FR_ERR_INVALID_ARG, "params/phoenix params is NULL");
-    if (width != 0 || height != 0) {
-        if (width == 0 || height == 0)
-            return fr_set_error(FR_ERR_INVALID_ARG, "width and height must be > 0 (got %ux%u)", width, height);
-        if ((uint64_t)width * (uint64_t)height >= (1ull << 31))
-            return fr_set_error(FR_ERR_INVALID_ARG, "frame %ux%u has 2^31 pixels or more", width, height);
-    }
+    int st = (width != 0 || height != 0) ? check_frame(width, height) : FR_OK;
+    if (st != FR_OK) return st;
     if (p->fractal_type != FR_FRACTAL_PHOENIX)
         return fr_set_error(FR_ERR_INVALID_ARG, "fr_render_phoenix needs fractal_type FR_FRACTAL_PHOENIX (got %d)", p->fractal_type);
-    if (p->precision != FR_PRECISION_F32 && p->precision != FR_PRECISION_F64)
-        return fr_set_error(FR_ERR_INVALID_ARG, "unknown precision %d", p->precision);
-    if (p->max_iterations < 1 || p->max_iterations > (1 << 24))
-        return fr_set_error(FR_ERR_INVALID_ARG, "max_iterations %d outside [1, 2^24]", p->max_iterations);
-    if (!isfinite(p->zoom) || p->zoom == 0.0)
-        return fr_set_error(FR_ERR_INVALID_ARG, "zoom must be finite and non-zero");
-    if (!isfinite(p->center_x) || !isfinite(p->center_y))
-        return fr_set_error(FR_ERR_INVALID_ARG, "centre must be finite");
-    if (!isfinite(p->julia_c_real) || !isfinite(p->julia_c_imag))
-        return fr_set_error(FR_ERR_INVALID_ARG, "julia c must be finite");
-    if (p->antialiasing_samples < 0 || p->antialiasing_samples > 16)
-        return fr_set_error(FR_ERR_INVALID_ARG, "antialiasing_samples %d outside [0, 16]", p->antialiasing_samples);
+    if ((st = check_view(p)) != FR_OK || (st = check_samples(p)) != FR_OK) return st;
     if (!isfinite(ph->phoenix_p) || !isfinite(ph->phoenix_r))
         return fr_set_error(FR_ERR_INVALID_ARG, "phoenix p and r must be finite");
     if (ph->use_julia_set != 0 && ph->use_julia_set != 1)
@@ -239,18 +244,18 @@ int32_t fr_deep_zoom_reference_length(const fr_params* p)
 }
 
 /* ---- row strips -------------------------------------------------------------------------------- */
-static void shard_normalise(const fr_shard* s, uint32_t height, uint32_t* part, uint32_t* nparts, uint32_t* R)
+fr_shard fr_shard_normalise(const fr_shard* s, uint32_t height)
 {
-    *nparts = (s && s->nparts) ? s->nparts : 1u;
-    *part = s ? s->part : 0u;
-    *R = (s && s->rows_per_strip) ? s->rows_per_strip : (*nparts == 1u ? height : 1u);
-    if (*R == 0) *R = 1;
+    const uint32_t nparts = (s && s->nparts) ? s->nparts : 1u;
+    const uint32_t R = (s && s->rows_per_strip) ? s->rows_per_strip : (nparts == 1u ? height : 1u);
+    const fr_shard n = {s ? s->part : 0u, nparts, R ? R : 1u};
+    return n;
 }
 
 uint32_t fr_shard_rows(const fr_shard* s, uint32_t height)
 {
-    uint32_t part, nparts, R;
-    shard_normalise(s, height, &part, &nparts, &R);
+    const fr_shard n = fr_shard_normalise(s, height);
+    const uint32_t part = n.part, nparts = n.nparts, R = n.rows_per_strip;
     if (part >= nparts || height == 0) return 0;
     const uint32_t nstrips = (height + R - 1) / R;                 /* last strip may be short */
     if (part >= nstrips) return 0;
@@ -263,11 +268,10 @@ uint32_t fr_shard_rows(const fr_shard* s, uint32_t height)
 
 uint32_t fr_shard_global_row(const fr_shard* s, uint32_t height, uint32_t local_row)
 {
-    uint32_t part, nparts, R;
-    shard_normalise(s, height, &part, &nparts, &R);
+    const fr_shard n = fr_shard_normalise(s, height);
     if (local_row >= fr_shard_rows(s, height)) return UINT32_MAX;
-    const uint32_t strip = local_row / R;
-    return (strip * nparts + part) * R + (local_row - strip * R);
+    const uint32_t strip = local_row / n.rows_per_strip;
+    return (strip * n.nparts + n.part) * n.rows_per_strip + (local_row - strip * n.rows_per_strip);
 }
 
 /* ---- palette knot tables ------------------------------------------------------------------------ */

@@ -20,6 +20,9 @@ int fr_set_error(int status, const char* fmt, ...)
     ;
 
 int32_t fr_deep_zoom_reference_length(const fr_params* p);
+/* a shard with its defaults filled in (fr_host.c): NULL = the whole frame, nparts 0 = one part, rows_per_strip 0 = the whole
+ * frame for one part and single rows for several */
+fr_shard fr_shard_normalise(const fr_shard* s, uint32_t height);
 /* the validation of fr_render_phoenix (fr_host.c); width == height == 0 skips the frame-size rules */
 int fr_phoenix_validate(const fr_params* p, const fr_phoenix_params* ph, uint32_t width, uint32_t height);
 

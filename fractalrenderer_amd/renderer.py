@@ -180,16 +180,8 @@ class Renderer:
         if rows == 0:
             _capi.check(self._lib.fr_params_validate(C.byref(p), width, height))
             return                                   # this part owns no rows of the frame
-        out = self._output(precision, rows, width, rgba, nu, iter)
-        sh = shard.to_c() if shard else None
-        shp = C.byref(sh) if sh is not None else None
-        if sync:
-            if stream is not None:
-                raise ValueError("stream is only meaningful with sync=False")
-            _capi.check(self._lib.fr_render_shard(self._ctx, C.byref(p), width, height, shp, C.byref(out)))
-        else:
-            _capi.check(self._lib.fr_render_shard_async(self._ctx, C.byref(p), width, height, shp,
-                                                        C.byref(out), C.c_void_p(stream or 0)))
+        self._render_call(self._lib.fr_render_shard, self._lib.fr_render_shard_async, (C.byref(p),), width, height,
+                          precision, rows, rgba, nu, iter, shard, stream, sync)
 
     def render_phoenix(self, state: FractalState, width: int, height: int, phoenix: Optional[PhoenixParams] = None, *,
                        precision: Precision = Precision.F32, post_chain: bool = False,
@@ -201,16 +193,22 @@ class Renderer:
         p = state.to_params(FractalType.Phoenix, precision, post_chain)
         ph = (phoenix or PhoenixParams()).to_c()
         rows = shard.rows(height) if shard else height
-        out = self._output(precision, rows, width, rgba, nu, iter)
+        self._render_call(self._lib.fr_render_phoenix, self._lib.fr_render_phoenix_async, (C.byref(p), C.byref(ph)), width,
+                          height, precision, rows, rgba, nu, iter, shard, stream, sync)
+
+    def _render_call(self, fn_sync, fn_async, params: tuple, width: int, height: int, precision: Precision, rows: int,
+                     rgba, nu, it, shard: Optional[Shard], stream: Optional[int], sync: bool) -> None:
+        """the planes, the shard and the sync / async entry of render() and render_phoenix(); params: the entry's
+        arguments between the context and the frame size"""
+        out = self._output(precision, rows, width, rgba, nu, it)
         sh = shard.to_c() if shard else None
         shp = C.byref(sh) if sh is not None else None
         if sync:
             if stream is not None:
                 raise ValueError("stream is only meaningful with sync=False")
-            _capi.check(self._lib.fr_render_phoenix(self._ctx, C.byref(p), C.byref(ph), width, height, shp, C.byref(out)))
+            _capi.check(fn_sync(self._ctx, *params, width, height, shp, C.byref(out)))
         else:
-            _capi.check(self._lib.fr_render_phoenix_async(self._ctx, C.byref(p), C.byref(ph), width, height, shp,
-                                                          C.byref(out), C.c_void_p(stream or 0)))
+            _capi.check(fn_async(self._ctx, *params, width, height, shp, C.byref(out), C.c_void_p(stream or 0)))
 
     def dispatch(self, fractal_type: FractalType, state: FractalState, extent: tuple, **kw) -> None:
         """Name-for-name mirror of ComputeEffectManager::dispatch (type, state, extent);

@@ -126,6 +126,20 @@ def test_shards_reassemble_the_frame(fr, renderer, f64):
             for k in range(3):
                 assert packed[k].tobytes() == whole[k].tobytes(), (nparts, R, k)
                 assert frame[k].cpu().numpy().tobytes() == whole[k].tobytes(), (nparts, R, k)
+    # a part that owns no rows: the synchronous entries have nothing to do; the asynchronous ones refuse host planes
+    # before they look at the shard, for Phoenix as for the escape-time kernels
+    E, L = fr._capi, fr.lib()
+    none = fr.Shard(2, 3, 64)
+    assert none.rows(H) == 0
+    empty = none.to_c()
+    host = E.fr_output(packed[0].ctypes.data, packed[1].ctypes.data, packed[2].ctypes.data, E.FR_MEM_HOST, E.FR_LAYOUT_PACKED)
+    p, cph = st.to_params(fr.FractalType.Phoenix, prec), ph.to_c()
+    q = st.to_params(fr.FractalType.Mandelbrot, prec)
+    assert L.fr_render_phoenix(renderer._ctx, C.byref(p), C.byref(cph), W, H, C.byref(empty), C.byref(host)) == E.FR_OK
+    assert L.fr_render_shard(renderer._ctx, C.byref(q), W, H, C.byref(empty), C.byref(host)) == E.FR_OK
+    assert L.fr_render_phoenix_async(renderer._ctx, C.byref(p), C.byref(cph), W, H, C.byref(empty), C.byref(host),
+                                     None) == E.FR_ERR_INVALID_ARG
+    assert L.fr_render_shard_async(renderer._ctx, C.byref(q), W, H, C.byref(empty), C.byref(host), None) == E.FR_ERR_INVALID_ARG
 
 
 def test_async_back_to_back_on_a_torch_stream(fr, renderer):

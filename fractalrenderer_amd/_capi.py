@@ -59,6 +59,11 @@ class fr_phoenix_params(C.Structure):
     _fields_ = [("phoenix_p", C.c_float), ("phoenix_r", C.c_float), ("use_julia_set", C.c_int32), ("reserved", C.c_int32)]
 
 
+class fr_mandelbulb_params(C.Structure):
+    _fields_ = [("camera_distance", C.c_float), ("rotation_y", C.c_float), ("fov", C.c_float), ("mandelbulb_power", C.c_float),
+                ("rotation_speed", C.c_float), ("time", C.c_float), ("reserved", C.c_int32 * 2)]
+
+
 class fr_output(C.Structure):
     _fields_ = [("rgba", C.c_void_p), ("nu", C.c_void_p), ("iter", C.c_void_p), ("memory", C.c_int32), ("layout", C.c_int32)]
 
@@ -106,6 +111,12 @@ SIGNATURES = {
                                     _P(fr_output)]),
     "fr_render_phoenix_async": (C.c_int, [C.c_void_p, _P(fr_params), _P(fr_phoenix_params), C.c_uint32, C.c_uint32,
                                           _P(fr_shard), _P(fr_output), C.c_void_p]),
+    "fr_mandelbulb_params_default": (C.c_int, [_P(fr_mandelbulb_params)]),
+    "fr_pack_push_constants_mandelbulb": (C.c_int, [_P(fr_params), _P(fr_mandelbulb_params), _P(C.c_float)]),
+    "fr_render_mandelbulb": (C.c_int, [C.c_void_p, _P(fr_params), _P(fr_mandelbulb_params), C.c_uint32, C.c_uint32,
+                                       _P(fr_shard), _P(fr_output)]),
+    "fr_render_mandelbulb_async": (C.c_int, [C.c_void_p, _P(fr_params), _P(fr_mandelbulb_params), C.c_uint32, C.c_uint32,
+                                             _P(fr_shard), _P(fr_output), C.c_void_p]),
     "fr_ctx_create": (C.c_int, [C.c_int, _P(C.c_void_p)]),
     "fr_ctx_destroy": (None, [C.c_void_p]),
     "fr_shard_rows": (C.c_uint32, [_P(fr_shard), C.c_uint32]),
@@ -184,7 +195,8 @@ INTERNAL_SIGNATURES = {
 PUBLIC_OPTIONS = ("periodicity", "staging", "shards", "tile_kernel", "timing", "diag_buffer", "diag_stride")
 TUNING_NAMES = ("workgroups_per_cu", "run_max", "run_min", "shift_bias", "stage_first", "pool_refill_at", "stream_run_max",
                 "stream_run_min", "stream_workgroups_per_cu", "probes", "stream_probes", "regions", "stream_rotate",
-                "tile_pixels", "tile_exit", "tile_exit_from", "prepare", "pool_items_per_wg", "subtile_shape", "debug_region_blocks", "debug_prologue_epoch", "ssaa", "ssaa_band_samples", "stripes")
+                "tile_pixels", "tile_exit", "tile_exit_from", "prepare", "pool_items_per_wg", "subtile_shape", "debug_region_blocks", "debug_prologue_epoch", "ssaa", "ssaa_band_samples", "stripes",
+                "mandelbulb_split")
 
 
 class FractalRendererError(RuntimeError):

@@ -17,6 +17,7 @@
 
 #include "fr_kernels.hip.h"
 #include "fr_phoenix.hip.h"
+#include "fr_mandelbulb.hip.h"
 #include "fr_tuning.h"
 
 using namespace fr;
@@ -106,6 +107,8 @@ struct fr_ctx {
     DivCheck div_cache[8];      /* exact_division_ok() results */
     uint32_t div_next;
     int phoenix_wg_per_cu[2];   /* resident workgroups per CU of phoenix_kernel<float> / <double> (0 = not asked yet) */
+    int mandelbulb_wg_per_cu[2];  /* ... of mandelbulb_kernel<false> / <true> (0 = not asked yet) */
+    uint32_t tune_mandelbulb_split;  /* 0 = automatic (march / shade split), 1 = shade at the hit, inside the march loop */
 };
 
 #define FR_HIP_TRY(expr)                                                               \
@@ -308,6 +311,9 @@ extern "C" int fr_ctx_set_tuning(fr_ctx* c, const char* name, int64_t value)
     } else if (!strcmp(name, "pool_items_per_wg")) {
         if (value < 0 || value > 4096) return fr_set_error(FR_ERR_INVALID_ARG, "pool_items_per_wg must be in [0,4096]");
         c->tune_pool_items_per_wg = (uint32_t)value;
+    } else if (!strcmp(name, "mandelbulb_split")) {
+        if (value < 0 || value > 1) return fr_set_error(FR_ERR_INVALID_ARG, "mandelbulb_split must be 0 (automatic: march / shade split) or 1 (shade inside the march loop)");
+        c->tune_mandelbulb_split = (uint32_t)value;
     } else if (!strcmp(name, "debug_region_blocks")) {
         c->debug_region_blocks = (uint32_t)value;     /* tests only (overflow reporting); 0 = the real capacity */
     } else {
@@ -720,6 +726,68 @@ static int enqueue_phoenix(fr_ctx* c, const fr_params* p, const fr_phoenix_param
     else hipLaunchKernelGGL(phoenix_kernel<float>, dim3(grid), dim3(kBlockThreads), 0, stream, a);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fr_set_error(FR_ERR_HIP, "phoenix kernel launch failed: %s", hipGetErrorString(e));
+    return finish_render(c, stream, 1);
+}
+
+/* ---- Mandelbulb (fr_mandelbulb.hip.h) -----------------------------------------------------------------------------
+ * One pass, no lane pool, as Phoenix: a persistent grid of exactly the resident set (occupancy query, cached) over the
+ * 8x8 sub-tiles of the WaveQueue, planned as an unstaged tile pass with unlimited stealing (ray lengths vary too much
+ * across a frame for a wave to stop at its home shard).  main's clamps (:177-190) are applied here. */
+static int enqueue_mandelbulb(fr_ctx* c, const fr_params* p, const fr_mandelbulb_params* mb, uint32_t W, uint32_t H,
+                              const fr_shard* shard, float* rgba, void* nu, int32_t* iter, hipStream_t stream, bool out_frame)
+{
+    const int ov = check_overflow(c);            /* of an earlier asynchronous render nobody has asked about */
+    if (ov != FR_OK) return ov;
+    fr_shard norm;
+    uint32_t rows_local = 0;
+    const int sh = normalise_shard(shard, H, &norm, &rows_local);
+    if (sh != FR_OK || rows_local == 0) return sh;
+    auto fmax_ = [](float x, float y) { return x < y ? y : x; };              /* GLSL max, FMax's operand order */
+    auto fclamp = [&](float x, float lo, float hi) { const float m = fmax_(x, lo); return hi < m ? hi : m; };
+
+    MandelbulbArgs a;
+    memset(&a, 0, sizeof(a));
+    a.camera_distance = fmax_(mb->camera_distance, 0.1f);                     /* :177 */
+    a.rotation_y = mb->rotation_y;
+    a.power = fclamp(mb->mandelbulb_power, 2.0f, 16.0f);                      /* :179 */
+    a.max_iter = p->max_iterations < 1 ? 1 : (p->max_iterations > 1024 ? 1024 : p->max_iterations);   /* :180 */
+    a.color_offset = p->color_offset;
+    a.color_scale = fmax_(p->color_scale, 0.1f);                              /* :182 */
+    a.palette_mode = p->palette_mode < 0 ? 0 : (p->palette_mode > 5 ? 5 : p->palette_mode);          /* :183 */
+    a.time = mb->time;
+    a.fov = fclamp(mb->fov, 0.1f, 3.0f);                                      /* :185 */
+    a.aa = p->antialiasing_samples > 1 ? p->antialiasing_samples : 1;        /* :186 */
+    a.brightness = fmax_(p->color_brightness, 0.1f);                          /* :187-190 */
+    a.rotation_speed = mb->rotation_speed != 0.0f ? mb->rotation_speed : 0.3f;
+    a.saturation = fmax_(p->color_saturation, 0.0f);
+    a.contrast = fmax_(p->color_contrast, 0.1f);
+    a.flags = p->flags;
+    a.W = (int32_t)W; a.H = (int32_t)H; a.rows_local = (int32_t)rows_local;
+    a.part = (int32_t)norm.part; a.nparts = (int32_t)norm.nparts; a.rows_per_strip = (int32_t)norm.rows_per_strip;
+    a.out_frame = out_frame ? 1 : 0;
+    a.rgba = reinterpret_cast<float4*>(rgba); a.nu = (float*)nu; a.iter = iter;
+
+    const bool split = c->tune_mandelbulb_split != 1u;
+    int& wg = c->mandelbulb_wg_per_cu[split ? 1 : 0];
+    if (wg == 0) {
+        int nb = 0;
+        const hipError_t e = split ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, mandelbulb_kernel<true>, kBlockThreads, 0)
+                                   : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, mandelbulb_kernel<false>, kBlockThreads, 0);
+        if (e != hipSuccess) return fr_set_error(FR_ERR_HIP, "mandelbulb occupancy query failed: %s", hipGetErrorString(e));
+        wg = nb < 1 ? 1 : nb;
+    }
+    uint32_t grid = 0;
+    a.q = plan_tile_queue(c, W, rows_local, 3, false, false, (uint32_t)wg, &grid);
+    a.q.heads = stage_heads(c, 0);
+    c->last_grid = grid;
+    c->last_pool_closing = -1;
+
+    FR_HIP_TRY(clear_control_block(c, stream, 1));
+    if (c->timing) FR_HIP_TRY(hipEventRecord(c->ev_begin, stream));
+    if (split) hipLaunchKernelGGL(mandelbulb_kernel<true>, dim3(grid), dim3(kBlockThreads), 0, stream, a);
+    else hipLaunchKernelGGL(mandelbulb_kernel<false>, dim3(grid), dim3(kBlockThreads), 0, stream, a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fr_set_error(FR_ERR_HIP, "mandelbulb kernel launch failed: %s", hipGetErrorString(e));
     return finish_render(c, stream, 1);
 }
 
@@ -1277,7 +1345,7 @@ static int enqueue_ssaa_staged(fr_ctx* c, const fr_params* p, uint32_t W, uint32
 }
 
 /* ---- render entry points --------------------------------------------------------------------------------------------
- * fr_render_shard(_async) and fr_render_phoenix(_async): their parameter checks, then render_sync / render_async with the
+ * fr_render_shard(_async), fr_render_phoenix(_async) and fr_render_mandelbulb(_async): their parameter checks, then render_sync / render_async with the
  * enqueue step as enqueue(shard, rgba, nu, iter, stream, out_frame) */
 static int check_common(fr_ctx* c, const fr_params* p, uint32_t W, uint32_t H, const fr_output* out)
 {
@@ -1292,6 +1360,14 @@ static int check_phoenix(fr_ctx* c, const fr_params* p, const fr_phoenix_params*
     if (!c) return fr_set_error(FR_ERR_INVALID_ARG, "ctx is NULL");
     if (!p || !ph || !out) return fr_set_error(FR_ERR_INVALID_ARG, "params/phoenix params/out is NULL");
     return fr_phoenix_validate(p, ph, W, H);
+}
+
+static int check_mandelbulb(fr_ctx* c, const fr_params* p, const fr_mandelbulb_params* mb, uint32_t W, uint32_t H,
+                            const fr_output* out)
+{
+    if (!c) return fr_set_error(FR_ERR_INVALID_ARG, "ctx is NULL");
+    if (!p || !mb || !out) return fr_set_error(FR_ERR_INVALID_ARG, "params/mandelbulb params/out is NULL");
+    return fr_mandelbulb_validate(p, mb, W, H);
 }
 
 static int check_layout(const fr_output* out)
@@ -1449,6 +1525,25 @@ extern "C" int fr_render_phoenix(fr_ctx* c, const fr_params* p, const fr_phoenix
     if (st != FR_OK) return st;
     return render_sync(c, p, W, H, shard, out, [&](auto sh, auto rgba, auto nu, auto iter, auto s, bool out_frame) {
         return enqueue_phoenix(c, p, ph, W, H, sh, rgba, nu, iter, s, out_frame); });
+}
+
+extern "C" int fr_render_mandelbulb_async(fr_ctx* c, const fr_params* p, const fr_mandelbulb_params* mb, uint32_t W,
+                                          uint32_t H, const fr_shard* shard, const fr_output* out, void* hip_stream)
+{
+    const int st = check_mandelbulb(c, p, mb, W, H, out);
+    if (st != FR_OK) return st;
+    return render_async("fr_render_mandelbulb_async", c, H, shard, out, hip_stream,
+                        [&](auto sh, auto rgba, auto nu, auto iter, auto s, bool out_frame) {
+                            return enqueue_mandelbulb(c, p, mb, W, H, sh, rgba, nu, iter, s, out_frame); });
+}
+
+extern "C" int fr_render_mandelbulb(fr_ctx* c, const fr_params* p, const fr_mandelbulb_params* mb, uint32_t W, uint32_t H,
+                                    const fr_shard* shard, const fr_output* out)
+{
+    const int st = check_mandelbulb(c, p, mb, W, H, out);
+    if (st != FR_OK) return st;
+    return render_sync(c, p, W, H, shard, out, [&](auto sh, auto rgba, auto nu, auto iter, auto s, bool out_frame) {
+        return enqueue_mandelbulb(c, p, mb, W, H, sh, rgba, nu, iter, s, out_frame); });
 }
 
 /* ---- 8-bit export ------------------------------------------------------------------------------ */

@@ -227,6 +227,66 @@ int fr_pack_push_constants_phoenix(const fr_params* p, const fr_phoenix_params* 
     return FR_OK;                                                              /* data5 = 0 */
 }
 
+/* ---- Mandelbulb ------------------------------------------------------------------------------------ */
+
+/* src/fractal_state.h:24-26,33,68; the frame time is the caller's (ImGui::GetTime(), src/vk_engine.cpp:336) */
+int fr_mandelbulb_params_default(fr_mandelbulb_params* mb)
+{
+    if (!mb) return fr_set_error(FR_ERR_INVALID_ARG, "mandelbulb params is NULL");
+    mb->camera_distance = 3.0f;
+    mb->rotation_y = 0.0f;
+    mb->fov = 1.0f;
+    mb->mandelbulb_power = 8.0f;
+    mb->rotation_speed = 0.5f;
+    mb->time = 0.0f;
+    mb->reserved[0] = mb->reserved[1] = 0;
+    return FR_OK;
+}
+
+/* fr_params_validate's rules for the fields shaders/mandelbulb.comp reads; centre, zoom, bailout, julia_c, interior
+ * style, trap, stripes and use_perturbation are not read and not checked */
+int fr_mandelbulb_validate(const fr_params* p, const fr_mandelbulb_params* mb, uint32_t width, uint32_t height)
+{
+    if (!p || !mb) return fr_set_error(FR_ERR_INVALID_ARG, "params/mandelbulb params is NULL");
+    int st = (width != 0 || height != 0) ? check_frame(width, height) : FR_OK;
+    if (st != FR_OK) return st;
+    if (p->fractal_type != FR_FRACTAL_MANDELBULB)
+        return fr_set_error(FR_ERR_INVALID_ARG, "fr_render_mandelbulb needs fractal_type FR_FRACTAL_MANDELBULB (got %d)",
+                            p->fractal_type);
+    if (p->precision == FR_PRECISION_F64)
+        return fr_set_error(FR_ERR_UNSUPPORTED, "Mandelbulb renders in FR_PRECISION_F32 only (the shader is fp32)");
+    if (p->precision != FR_PRECISION_F32)
+        return fr_set_error(FR_ERR_INVALID_ARG, "unknown precision %d", p->precision);
+    if (p->max_iterations < 1 || p->max_iterations > (1 << 24))
+        return fr_set_error(FR_ERR_INVALID_ARG, "max_iterations %d outside [1, 2^24]", p->max_iterations);
+    if ((st = check_samples(p)) != FR_OK) return st;
+    if (!isfinite(mb->camera_distance) || !isfinite(mb->rotation_y) || !isfinite(mb->fov) ||
+        !isfinite(mb->mandelbulb_power) || !isfinite(mb->rotation_speed) || !isfinite(mb->time))
+        return fr_set_error(FR_ERR_INVALID_ARG, "mandelbulb camera_distance, rotation_y, fov, power, rotation_speed and "
+                            "time must be finite");
+    if (mb->reserved[0] != 0 || mb->reserved[1] != 0)
+        return fr_set_error(FR_ERR_INVALID_ARG, "fr_mandelbulb_params.reserved must be 0");
+    return FR_OK;
+}
+
+/* ComputeEffect::update_from_state, Mandelbulb case, src/compute_effect_manager.h:173-199 */
+int fr_pack_push_constants_mandelbulb(const fr_params* p, const fr_mandelbulb_params* mb, float out[20])
+{
+    if (!out) return fr_set_error(FR_ERR_INVALID_ARG, "out is NULL");
+    const int st = fr_mandelbulb_validate(p, mb, 0u, 0u);
+    if (st != FR_OK) return st;
+    for (int i = 0; i < 20; ++i) out[i] = 0.0f;
+    out[0] = mb->camera_distance;  out[1] = mb->rotation_y;                   /* data1, :174-179 */
+    out[2] = mb->mandelbulb_power; out[3] = (float)p->max_iterations;
+    out[4] = p->color_offset;      out[5] = p->color_scale;                   /* data2, :180-185 */
+    out[7] = (float)p->palette_mode;
+    out[8] = mb->time;             out[9] = mb->fov;                          /* data3, :186-191 */
+    out[10] = (float)p->antialiasing_samples;  out[11] = p->color_brightness;
+    out[12] = mb->rotation_speed;  out[13] = p->color_saturation;             /* data4, :192-197 */
+    out[14] = p->color_contrast;
+    return FR_OK;                                                             /* data5 = 0, :198 */
+}
+
 /* reference_iterations of a Deep_Zoom render: the trimmed length of the fp64 orbit at the centre,
  * or 0 when perturbation is off (compute_reference_orbit returns early, src/deep_zoom_system.cpp:364) */
 int32_t fr_deep_zoom_reference_length(const fr_params* p)

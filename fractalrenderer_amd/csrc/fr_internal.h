@@ -25,6 +25,8 @@ int32_t fr_deep_zoom_reference_length(const fr_params* p);
 fr_shard fr_shard_normalise(const fr_shard* s, uint32_t height);
 /* the validation of fr_render_phoenix (fr_host.c); width == height == 0 skips the frame-size rules */
 int fr_phoenix_validate(const fr_params* p, const fr_phoenix_params* ph, uint32_t width, uint32_t height);
+/* the validation of fr_render_mandelbulb (fr_host.c); width == height == 0 skips the frame-size rules */
+int fr_mandelbulb_validate(const fr_params* p, const fr_mandelbulb_params* mb, uint32_t width, uint32_t height);
 
 /* the context's own stream (hipStream_t) and device ordinal: fr_node.cpp orders RCCL transfers behind the renders */
 void* fr_ctx_stream_handle(fr_ctx* ctx);

@@ -36,6 +36,8 @@
  *   "stripes"            the Mandelbrot shader's effects (stripe shading, orbit trap, trap-coloured interior): 0 = automatic (lean tile
  *                        pass + lane pool in their code-3 instantiations), 1 = the effects variant of the general tile kernel (tests
  *                        compare the two bitwise)
+ *   "mandelbulb_split"   Mandelbulb: 0 = automatic (the wave marches until no lane is marching, then the lanes that hit shade
+ *                        together), 1 = each lane shades at its hit, inside the march loop (tests compare the two bitwise)
  *   "ssaa_band_samples"  staged SSAA of a whole frame: sample grids larger than this go through the scratch in bands of whole
  *                        sub-tile rows (0 = automatic: 2^29 samples; tests set it small to band small frames)
  *   "debug_prologue_epoch" tests only: sets the context's prologue epoch (28 bits), to walk it across its wrap

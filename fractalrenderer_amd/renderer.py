@@ -18,7 +18,7 @@ from typing import Optional
 import numpy as np
 
 from . import _capi
-from .state import FractalState, FractalType, PhoenixParams, Precision
+from .state import FractalState, FractalType, MandelbulbParams, PhoenixParams, Precision
 
 
 @dataclass(frozen=True)
@@ -196,9 +196,23 @@ class Renderer:
         self._render_call(self._lib.fr_render_phoenix, self._lib.fr_render_phoenix_async, (C.byref(p), C.byref(ph)), width,
                           height, precision, rows, rgba, nu, iter, shard, stream, sync)
 
+    def render_mandelbulb(self, state: FractalState, width: int, height: int, mandelbulb: Optional[MandelbulbParams] = None,
+                          *, post_chain: bool = False, rgba=None, nu=None, iter=None, shard: Optional[Shard] = None,
+                          stream: Optional[int] = None, sync: bool = True) -> None:
+        """fr_render_mandelbulb / fr_render_mandelbulb_async: a frame of shaders/mandelbulb.comp, in fp32 (the only
+        precision).  `mandelbulb` carries the camera, the power and the frame time (default: FractalState's initialisers,
+        time 0).  rgba: the linear colour (NaN where the shader's is, see the header) or, with post_chain, the shader's
+        output; nu (float32): sample (0,0)'s ray parameter t where its march stopped; iter: its hit step, -1 for a miss.
+        Planes, shard, stream and sync as for render()."""
+        p = state.to_params(FractalType.Mandelbulb, Precision.F32, post_chain)
+        mb = (mandelbulb or MandelbulbParams()).to_c()
+        rows = shard.rows(height) if shard else height
+        self._render_call(self._lib.fr_render_mandelbulb, self._lib.fr_render_mandelbulb_async, (C.byref(p), C.byref(mb)),
+                          width, height, Precision.F32, rows, rgba, nu, iter, shard, stream, sync)
+
     def _render_call(self, fn_sync, fn_async, params: tuple, width: int, height: int, precision: Precision, rows: int,
                      rgba, nu, it, shard: Optional[Shard], stream: Optional[int], sync: bool) -> None:
-        """the planes, the shard and the sync / async entry of render() and render_phoenix(); params: the entry's
+        """the planes, the shard and the sync / async entry of render(), render_phoenix() and render_mandelbulb(); params: the entry's
         arguments between the context and the frame size"""
         out = self._output(precision, rows, width, rgba, nu, it)
         sh = shard.to_c() if shard else None

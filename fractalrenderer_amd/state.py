@@ -18,7 +18,8 @@ class FractalType(enum.IntEnum):
     """src/fractal_state.h:6-14.  Mandelbrot and JuliaSet are the hot path; BurningShip and Deep_Zoom are
     its variants (section 8 f1/f4).  Phoenix renders through Renderer.render_phoenix (fr_render_phoenix: its p, r and
     Julia-mode flag travel in PhoenixParams, which fr_params has no room for); Renderer.render and the other fr_params
-    entry points reject it with FR_ERR_UNSUPPORTED, as they reject Mandelbulb."""
+    entry points reject it with FR_ERR_UNSUPPORTED, as they reject Mandelbulb, which renders through
+    Renderer.render_mandelbulb (fr_render_mandelbulb, with MandelbulbParams)."""
     Mandelbrot = 0
     JuliaSet = 1
     BurningShip = 2
@@ -144,4 +145,42 @@ def pack_push_constants_phoenix(state: FractalState, phoenix: PhoenixParams = No
     p = state.to_params(FractalType.Phoenix)
     ph = (phoenix or PhoenixParams()).to_c()
     _capi.check(_capi.lib().fr_pack_push_constants_phoenix(_capi.C.byref(p), _capi.C.byref(ph), out))
+    return np.array(out[:], dtype=np.float32)
+
+
+@dataclass
+class MandelbulbParams:
+    """FractalState's 3-D fields, src/fractal_state.h:24-26,33,68, and the frame time (fr_mandelbulb_params).  The
+    shader animates with `time` (ImGui::GetTime(), src/vk_engine.cpp:336): the caller supplies it."""
+    camera_distance: float = 3.0                # :24
+    rotation_y: float = 0.0                     # :25  radians
+    fov: float = 1.0                            # :26
+    mandelbulb_power: float = 8.0               # :33
+    rotation_speed: float = 0.5                 # :68  (0 means 0.3 in the shader)
+    time: float = 0.0                           # seconds
+
+    def to_c(self) -> _capi.fr_mandelbulb_params:
+        return _capi.fr_mandelbulb_params(_F32(self.camera_distance), _F32(self.rotation_y), _F32(self.fov),
+                                          _F32(self.mandelbulb_power), _F32(self.rotation_speed), _F32(self.time))
+
+
+# UIManager's Mandelbulb buttons: the power presets (src/ui_manager.cpp:1319-1324) and the views (:1476-1480) as
+# name -> MandelbulbParams (the other fields keep their defaults)
+MANDELBULB_PRESETS = {
+    "Classic (8)": MandelbulbParams(mandelbulb_power=8.0),
+    "Smooth (4)": MandelbulbParams(mandelbulb_power=4.0),
+    "Spiky (12)": MandelbulbParams(mandelbulb_power=12.0),
+    "Extreme (16)": MandelbulbParams(mandelbulb_power=16.0),
+    "Front View": MandelbulbParams(camera_distance=3.0, rotation_y=0.0, mandelbulb_power=8.0),
+    "Side View": MandelbulbParams(camera_distance=3.0, rotation_y=_F32(1.5708), mandelbulb_power=8.0),
+    "Close-up Detail": MandelbulbParams(camera_distance=1.5, rotation_y=_F32(0.785), mandelbulb_power=8.0),
+}
+
+
+def pack_push_constants_mandelbulb(state: FractalState, mandelbulb: MandelbulbParams = None) -> np.ndarray:
+    """ComputeEffect::update_from_state, Mandelbulb case (src/compute_effect_manager.h:173-199): 20 float32."""
+    out = (_capi.C.c_float * 20)()
+    p = state.to_params(FractalType.Mandelbulb, Precision.F32)
+    mb = (mandelbulb or MandelbulbParams()).to_c()
+    _capi.check(_capi.lib().fr_pack_push_constants_mandelbulb(_capi.C.byref(p), _capi.C.byref(mb), out))
     return np.array(out[:], dtype=np.float32)

@@ -46,7 +46,8 @@ typedef enum fr_status {
  * square; Deep_Zoom is the reference's perturbation shader (shaders/test_deep_zoom.comp), restated
  * with its fp32 float-float arithmetic.  Phoenix (shaders/phoenix.comp) needs three fields fr_params
  * has no room for: fr_render and the other fr_params entry points return FR_ERR_UNSUPPORTED for it, and
- * fr_render_phoenix (below) renders it.  Mandelbulb (a 3-D ray marcher) returns FR_ERR_UNSUPPORTED. */
+ * fr_render_phoenix (below) renders it.  Mandelbulb (shaders/mandelbulb.comp, a 3-D ray marcher) likewise returns
+ * FR_ERR_UNSUPPORTED there and renders through fr_render_mandelbulb (below). */
 typedef enum fr_fractal_type {
     FR_FRACTAL_MANDELBROT   = 0,
     FR_FRACTAL_JULIA        = 1,
@@ -333,6 +334,63 @@ int fr_render_phoenix(fr_ctx* ctx, const fr_params* p, const fr_phoenix_params* 
  * later surface through fr_ctx_check.  "timing", fr_ctx_last_kernel_ms and fr_ctx_last_grid cover it. */
 int fr_render_phoenix_async(fr_ctx* ctx, const fr_params* p, const fr_phoenix_params* ph, uint32_t width, uint32_t height,
                             const fr_shard* shard, const fr_output* out, void* hip_stream);
+
+/* ---- Mandelbulb (shaders/mandelbulb.comp) ---------------------------------------------------------------------------
+ * A ray marcher, one ray per sample, all in fp32 as the shader: the camera orbits the origin at camera_distance (times
+ * 1 + 0.3 sin(0.5 time)), turned by rotation_y + rotation_speed * time about the y axis (rotation_speed 0 means 0.3, :188);
+ * the power is mandelbulb_power + 0.5 sin(0.7 time).  Up to 200 steps of t += max(0.5 d, 0.0005) on the distance
+ * estimator of the power-n bulb (escape radius 2, max_iterations clamped to [1, 1024]); a hit (d < max(1e-4, 1e-3 t))
+ * is shaded with a 4-call normal, diffuse / specular / rim / glow, this shader's six palettes, 8 ambient-occlusion
+ * samples and distance fog; a miss takes the sky gradient.  aa x aa samples per pixel, averaged.
+ * fr_params cannot express a Mandelbulb frame (camera_distance, rotation_y, fov, mandelbulb_power, rotation_speed and
+ * the frame time have no field there): these entry points take them in fr_mandelbulb_params and p->fractal_type must
+ * be FR_FRACTAL_MANDELBULB.  fr_render, fr_params_validate and fr_pack_push_constants keep answering
+ * FR_ERR_UNSUPPORTED for Mandelbulb.
+ *
+ * NaN policy.  The shader colours a hit with log(log(length(pos))), which is NaN wherever the hit point lies inside the
+ * unit sphere (much of the power-8 surface).  The linear plane (rgba without FR_FLAG_POST_CHAIN) carries that NaN as
+ * the shader computes it; one NaN sample makes its pixel's average NaN.  The post-chained plane follows the IEEE
+ * maxNum / minNum semantics of GPU clamp(): enhance_color's clamp maps NaN to 0, so the pixel is black, finite, which
+ * is what the reference shows on a GPU. */
+#define FR_HAS_MANDELBULB 1
+
+typedef struct fr_mandelbulb_params {
+    float   camera_distance;       /* src/fractal_state.h:24  default 3.0                          */
+    float   rotation_y;            /*                   :25   default 0.0 (radians)                */
+    float   fov;                   /*                   :26   default 1.0                          */
+    float   mandelbulb_power;      /*                   :33   default 8.0                          */
+    float   rotation_speed;        /*                   :68   default 0.5                          */
+    float   time;                  /* the frame time in seconds (ImGui::GetTime(), src/vk_engine.cpp:336); default 0 */
+    int32_t reserved[2];           /* must be 0 */
+} fr_mandelbulb_params;            /* 32 bytes */
+
+/* FractalState's initialisers for the five 3-D fields, time 0, reserved 0. */
+int fr_mandelbulb_params_default(fr_mandelbulb_params* mb);
+
+/* ComputeEffect::update_from_state's Mandelbulb case, src/compute_effect_manager.h:173-199, as 20 floats bit for bit:
+ * data1 (camera_distance, rotation_y, power, max_iter), data2 (color_offset, color_scale, 0, palette_mode),
+ * data3 (time, fov, aa, brightness), data4 (rotation_speed, saturation, contrast, 0), data5 = 0.  Validates as
+ * fr_render_mandelbulb does (no frame size). */
+int fr_pack_push_constants_mandelbulb(const fr_params* p, const fr_mandelbulb_params* mb, float out[20]);
+
+/* A Mandelbulb frame (or one part of a row-strip sharding of it: shard NULL = the whole frame) into `out`, synchronously.
+ * Validation: fr_params_validate's rules for the fields Mandelbulb reads (max_iterations in [1, 2^24], clamped to 1024
+ * as the shader does; antialiasing_samples in [0, 16]), fractal_type == FR_FRACTAL_MANDELBULB, every float of `mb`
+ * finite, reserved 0; otherwise FR_ERR_INVALID_ARG.  FR_PRECISION_F64 answers FR_ERR_UNSUPPORTED (the shader is fp32).
+ * What Mandelbulb does not read (centre, zoom, bailout, julia_c, interior style, the orbit trap, stripes,
+ * use_perturbation) is ignored.
+ * Planes (FR_MEM_HOST / FR_MEM_DEVICE, FR_LAYOUT_FRAME): rgba = the averaged linear colour (FR_FLAG_POST_CHAIN: the
+ * shader's enhance_color -> aces_tonemap -> pow(1/2.2) with its floors: brightness, contrast >= 0.1, saturation >= 0);
+ * iter = the ray-march step index of sample (0,0)'s hit, -1 for a ray that hits nothing; nu (float) = sample (0,0)'s
+ * ray parameter t where its march stopped (a depth plane).  See the NaN policy above. */
+int fr_render_mandelbulb(fr_ctx* ctx, const fr_params* p, const fr_mandelbulb_params* mb, uint32_t width, uint32_t height,
+                         const fr_shard* shard, const fr_output* out);
+
+/* Asynchronous form, the fr_render_shard_async contract: device planes only, enqueued on hip_stream (NULL = the
+ * context's stream), launch-only in steady state; errors the device reports later surface through fr_ctx_check.
+ * "timing", fr_ctx_last_kernel_ms and fr_ctx_last_grid cover it. */
+int fr_render_mandelbulb_async(fr_ctx* ctx, const fr_params* p, const fr_mandelbulb_params* mb, uint32_t width,
+                               uint32_t height, const fr_shard* shard, const fr_output* out, void* hip_stream);
 
 /* ---- frames over the GPUs of a node (BASELINE.json north_star: "tiled across the 8 GPUs of one node as disjoint row
  * bands with a final RCCL gather over xGMI") -----------------------------------------------------------------------------

@@ -8,7 +8,8 @@ from . import _capi
 from ._capi import FractalRendererError, lib
 from .state import (FractalState, FractalType, Precision, Preset, MANDELBROT_PRESETS,
                     SEAHORSE_DEEP, pack_push_constants, PhoenixParams, PHOENIX_PRESETS, pack_push_constants_phoenix,
-                    MandelbulbParams, MANDELBULB_PRESETS, pack_push_constants_mandelbulb)
+                    MandelbulbParams, MANDELBULB_PRESETS, pack_push_constants_mandelbulb, DeepView, deep_frac_bits,
+                    deep_reference_orbit)
 from .renderer import (Renderer, Node, Shard, write_png, write_raw_rgb24, frame_path, export8_thresholds, rccl_selftest,
                        mapped_runtimes)
 from .animation import (AnimationSystem, AnimationRenderer, InterpolationType, Keyframe, DeepZoomPath, ZoomKeyframe)
@@ -18,7 +19,8 @@ lib()  # no silent fallback: a missing/incomplete library is an import error
 __all__ = [
     "FractalRendererError", "lib", "FractalState", "FractalType", "Precision", "Preset",
     "MANDELBROT_PRESETS", "SEAHORSE_DEEP", "pack_push_constants", "PhoenixParams", "PHOENIX_PRESETS",
-    "pack_push_constants_phoenix", "MandelbulbParams", "MANDELBULB_PRESETS", "pack_push_constants_mandelbulb", "Renderer", "Node", "Shard",
+    "pack_push_constants_phoenix", "MandelbulbParams", "MANDELBULB_PRESETS", "pack_push_constants_mandelbulb", "DeepView",
+    "deep_frac_bits", "deep_reference_orbit", "Renderer", "Node", "Shard",
     "write_png", "write_raw_rgb24", "frame_path", "export8_thresholds", "rccl_selftest", "mapped_runtimes",
     "AnimationSystem", "AnimationRenderer", "InterpolationType", "Keyframe", "DeepZoomPath", "ZoomKeyframe",
 ]

@@ -64,6 +64,10 @@ class fr_mandelbulb_params(C.Structure):
                 ("rotation_speed", C.c_float), ("time", C.c_float), ("reserved", C.c_int32 * 2)]
 
 
+class fr_deep_view(C.Structure):
+    _fields_ = [("center_x", C.c_char_p), ("center_y", C.c_char_p), ("frac_bits", C.c_int32), ("reserved", C.c_int32)]
+
+
 class fr_output(C.Structure):
     _fields_ = [("rgba", C.c_void_p), ("nu", C.c_void_p), ("iter", C.c_void_p), ("memory", C.c_int32), ("layout", C.c_int32)]
 
@@ -117,6 +121,13 @@ SIGNATURES = {
                                        _P(fr_shard), _P(fr_output)]),
     "fr_render_mandelbulb_async": (C.c_int, [C.c_void_p, _P(fr_params), _P(fr_mandelbulb_params), C.c_uint32, C.c_uint32,
                                              _P(fr_shard), _P(fr_output), C.c_void_p]),
+    "fr_deep_view_default": (C.c_int, [_P(fr_deep_view)]),
+    "fr_deep_frac_bits": (C.c_int, [C.c_double]),
+    "fr_deep_reference_orbit": (C.c_int, [_P(fr_deep_view), C.c_double, C.c_int32, C.c_float, C.c_void_p, _P(C.c_int32)]),
+    "fr_render_deep": (C.c_int, [C.c_void_p, _P(fr_params), _P(fr_deep_view), C.c_uint32, C.c_uint32, _P(fr_shard),
+                                 _P(fr_output)]),
+    "fr_render_deep_async": (C.c_int, [C.c_void_p, _P(fr_params), _P(fr_deep_view), C.c_uint32, C.c_uint32, _P(fr_shard),
+                                       _P(fr_output), C.c_void_p]),
     "fr_ctx_create": (C.c_int, [C.c_int, _P(C.c_void_p)]),
     "fr_ctx_destroy": (None, [C.c_void_p]),
     "fr_shard_rows": (C.c_uint32, [_P(fr_shard), C.c_uint32]),
@@ -191,6 +202,7 @@ INTERNAL_SIGNATURES = {
     "fr_node_set_tuning": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int64]),
     "fr_node_rccl_usable": (C.c_int, [C.c_void_p]),
     "fr_node_mapped_runtimes": (C.c_int, [C.c_char_p, C.c_size_t]),
+    "fr_deep_parse_fixed": (C.c_int, [C.c_char_p, C.c_int32, _P(C.c_uint64), C.c_int32]),   # fr_internal.h: tests
 }
 PUBLIC_OPTIONS = ("periodicity", "staging", "shards", "tile_kernel", "timing", "diag_buffer", "diag_stride")
 TUNING_NAMES = ("workgroups_per_cu", "run_max", "run_min", "shift_bias", "stage_first", "pool_refill_at", "stream_run_max",

@@ -1,0 +1,458 @@
+/*
+ * fr_deep.c -- host side of the deep Mandelbrot views (fr_render_deep, include/fractalrenderer_amd.h): the decimal
+ * parser, the fixed-point reference orbit and the validation of a deep view.  Plain C11 with unsigned __int128 products.
+ *
+ * Fixed point: a value v is the integer X = v 2^F in L = ceil(F / 64) + 1 limbs of 64 bits, little-endian two's
+ * complement -- F fraction bits and at least 64 integer bits.  Centres are limited to |c| < 2^32, so an orbit point that
+ * has not escaped (|Z|^2 <= bailout^2 <= 2^32) is below 2^16, the escaping one below 2^33, and the squares of the escape
+ * test (< 2^(2F + 66)) fit in the 2L limbs of a product.
+ */
+#include "fr_internal.h"
+
+#include <math.h>
+#include <stdlib.h>
+#include <string.h>
+
+enum {
+    kMaxChars = 4096,                          /* longest centre string */
+    kMaxFracBits = 4096,
+    kMaxLimbs = kMaxFracBits / 64 + 1,         /* L at F = 4096 */
+    /* the parser's working integer: up to 4096 decimal digits (13607 bits) shifted left by F (4096) */
+    kWorkLimbs = 280
+};
+
+typedef struct { int F, L; } fx_fmt;
+
+/* ---- multi-limb magnitudes ---------------------------------------------------------------------------------------- */
+static int top_limb(const uint64_t* a, int n)             /* index of the highest non-zero limb, -1 for zero */
+{
+    for (int i = n - 1; i >= 0; --i)
+        if (a[i]) return i;
+    return -1;
+}
+
+static void shl_bits(uint64_t* a, int n, int s)           /* a <<= s in n limbs (bits shifted out are lost) */
+{
+    const int w = s / 64, b = s % 64;
+    for (int i = n - 1; i >= 0; --i) {
+        uint64_t v = 0;
+        if (i - w >= 0) {
+            v = a[i - w] << b;
+            if (b && i - w - 1 >= 0) v |= a[i - w - 1] >> (64 - b);
+        }
+        a[i] = v;
+    }
+}
+
+/* r = a >> s (r has rn limbs, a has an limbs); returns 1 when a bit shifted out was set */
+static int shr_bits(uint64_t* r, int rn, const uint64_t* a, int an, int s)
+{
+    const int w = s / 64, b = s % 64;
+    int lost = 0;
+    for (int i = 0; i < w && i < an; ++i) lost |= a[i] != 0;
+    if (b && w < an) lost |= (a[w] & ((1ull << b) - 1)) != 0;
+    for (int i = 0; i < rn; ++i) {
+        uint64_t v = 0;
+        if (i + w < an) {
+            v = a[i + w] >> b;
+            if (b && i + w + 1 < an) v |= a[i + w + 1] << (64 - b);
+        }
+        r[i] = v;
+    }
+    return lost;
+}
+
+static int bit_of(const uint64_t* a, int n, long k)      /* bit k of a, 0 outside */
+{
+    if (k < 0 || k >= 64L * n) return 0;
+    return (int)((a[k / 64] >> (k % 64)) & 1u);
+}
+
+static int any_below(const uint64_t* a, int n, long k)    /* some bit below bit k of a is set */
+{
+    for (long i = 0; i < n && 64 * i < k; ++i) {
+        const long lo = 64 * i;
+        const uint64_t m = k - lo >= 64 ? ~0ull : ((1ull << (k - lo)) - 1);
+        if (a[i] & m) return 1;
+    }
+    return 0;
+}
+
+static void add_one(uint64_t* a, int n)
+{
+    for (int i = 0; i < n; ++i)
+        if (++a[i] != 0) return;
+}
+
+static void negate(uint64_t* a, int n)                    /* two's complement */
+{
+    for (int i = 0; i < n; ++i) a[i] = ~a[i];
+    add_one(a, n);
+}
+
+static int is_negative(const uint64_t* a, int n) { return (int)(a[n - 1] >> 63); }
+
+/* r = a + b (n limbs, modular) */
+static void add_n(uint64_t* r, const uint64_t* a, const uint64_t* b, int n)
+{
+    unsigned __int128 c = 0;
+    for (int i = 0; i < n; ++i) {
+        c += (unsigned __int128)a[i] + b[i];
+        r[i] = (uint64_t)c;
+        c >>= 64;
+    }
+}
+
+/* r = a - b (n limbs, modular) */
+static void sub_n(uint64_t* r, const uint64_t* a, const uint64_t* b, int n)
+{
+    uint64_t borrow = 0;
+    for (int i = 0; i < n; ++i) {
+        const uint64_t ai = a[i], bi = b[i];
+        const uint64_t d = ai - bi - borrow;
+        borrow = (ai < bi) || (ai - bi < borrow);
+        r[i] = d;
+    }
+}
+
+static int cmp_n(const uint64_t* a, const uint64_t* b, int n)   /* unsigned compare */
+{
+    for (int i = n - 1; i >= 0; --i)
+        if (a[i] != b[i]) return a[i] < b[i] ? -1 : 1;
+    return 0;
+}
+
+/* r[0 .. 2n) = a * b, magnitudes of n limbs */
+static void mul_mag(uint64_t* r, const uint64_t* a, const uint64_t* b, int n)
+{
+    memset(r, 0, sizeof(uint64_t) * 2 * (size_t)n);
+    const int ta = top_limb(a, n), tb = top_limb(b, n);
+    for (int i = 0; i <= ta; ++i) {
+        unsigned __int128 c = 0;
+        const uint64_t ai = a[i];
+        if (!ai) continue;
+        for (int j = 0; j <= tb; ++j) {
+            c += (unsigned __int128)ai * b[j] + r[i + j];
+            r[i + j] = (uint64_t)c;
+            c >>= 64;
+        }
+        for (int k = i + tb + 1; c; ++k) {
+            c += r[k];
+            r[k] = (uint64_t)c;
+            c >>= 64;
+        }
+    }
+}
+
+static uint64_t mul_small(uint64_t* a, int n, uint64_t m)      /* a *= m; returns the carry out */
+{
+    unsigned __int128 c = 0;
+    for (int i = 0; i < n; ++i) {
+        c += (unsigned __int128)a[i] * m;
+        a[i] = (uint64_t)c;
+        c >>= 64;
+    }
+    return (uint64_t)c;
+}
+
+static void add_small(uint64_t* a, int n, uint64_t v)          /* a += v */
+{
+    for (int i = 0; i < n && v; ++i) {
+        a[i] += v;
+        v = a[i] < v;
+    }
+}
+
+static uint64_t div_small(uint64_t* a, int n, uint64_t d)      /* a /= d (floor); returns the remainder */
+{
+    unsigned __int128 rem = 0;
+    for (int i = n - 1; i >= 0; --i) {
+        const unsigned __int128 cur = (rem << 64) | a[i];
+        a[i] = (uint64_t)(cur / d);
+        rem = cur % d;
+    }
+    return (uint64_t)rem;
+}
+
+/* ---- decimal parser -------------------------------------------------------------------------------------------------
+ * [+-]digits[.digits][(e|E)[+-]digits] -> round_half_even(value 2^F) in fmt.L limbs.  The digits are built into one big
+ * integer D (value = D 10^net), shifted left by F, then multiplied by 10 (net > 0) or divided by 10 once per digit of
+ * the negative exponent; the last division's remainder and a sticky bit of the earlier ones round to nearest, ties to
+ * even.  Returns 0, or -1 for a malformed string, -2 for |value| >= 2^32. */
+static int parse_fixed(const char* s, fx_fmt fmt, uint64_t* out)
+{
+    size_t len = 0;
+    while (len <= (size_t)kMaxChars && s[len]) ++len;
+    if (len == 0 || len > (size_t)kMaxChars) return -1;
+    size_t i = 0;
+    int neg = 0;
+    if (s[i] == '+' || s[i] == '-') neg = s[i++] == '-';
+    uint64_t A[kWorkLimbs];
+    memset(A, 0, sizeof A);
+    long ndig = 0, nfrac = 0;
+    for (; s[i] >= '0' && s[i] <= '9'; ++i, ++ndig) {
+        mul_small(A, kWorkLimbs, 10);
+        add_small(A, kWorkLimbs, (uint64_t)(s[i] - '0'));
+    }
+    if (ndig == 0) return -1;
+    if (s[i] == '.') {
+        ++i;
+        for (; s[i] >= '0' && s[i] <= '9'; ++i, ++nfrac) {
+            mul_small(A, kWorkLimbs, 10);
+            add_small(A, kWorkLimbs, (uint64_t)(s[i] - '0'));
+        }
+        if (nfrac == 0) return -1;
+    }
+    long ex = 0;
+    if (s[i] == 'e' || s[i] == 'E') {
+        ++i;
+        int eneg = 0;
+        if (s[i] == '+' || s[i] == '-') eneg = s[i++] == '-';
+        long nex = 0;
+        for (; s[i] >= '0' && s[i] <= '9'; ++i, ++nex)
+            if (ex < 1000000) ex = ex * 10 + (s[i] - '0');      /* saturates: anything past it is 0 or too large */
+        if (nex == 0) return -1;
+        if (eneg) ex = -ex;
+    }
+    if (s[i] != '\0') return -1;
+
+    memset(out, 0, sizeof(uint64_t) * (size_t)fmt.L);
+    if (top_limb(A, kWorkLimbs) < 0) return 0;                   /* zero, whatever its sign */
+    const long net = ex - nfrac;
+    if (net >= 0) {
+        if (net > 10) return -2;                                 /* D >= 1: >= 1e11 > 2^32 */
+        for (long k = 0; k < net; ++k) mul_small(A, kWorkLimbs, 10);
+        if (top_limb(A, kWorkLimbs) > 0 || A[0] >= (1ull << 32)) return -2;
+        shl_bits(A, kWorkLimbs, fmt.F);
+    } else {
+        const long k = -net;
+        /* D < 10^4096 and 2^F <= 2^4096 < 10^1234: past 10^5331 the value is below 1/2 and rounds to 0 */
+        if (k > 5400) return 0;
+        shl_bits(A, kWorkLimbs, fmt.F);
+        int n = top_limb(A, kWorkLimbs) + 1, sticky = 0;
+        for (long d = 0; d + 1 < k; ++d) {
+            sticky |= div_small(A, n, 10) != 0;
+            while (n > 1 && A[n - 1] == 0) --n;
+        }
+        const uint64_t r = div_small(A, n, 10);                 /* the last digit decides the rounding */
+        if (r > 5 || (r == 5 && (sticky || (A[0] & 1u)))) add_one(A, kWorkLimbs);
+    }
+    const long lim = (long)fmt.F + 32;                           /* |X| < 2^(F + 32) */
+    for (int j = 0; j < kWorkLimbs; ++j) {
+        const long lo = 64L * j;
+        if (lo + 64 <= lim) continue;
+        const uint64_t m = lo >= lim ? ~0ull : ~((1ull << (lim - lo)) - 1);
+        if (A[j] & m) return -2;
+    }
+    memcpy(out, A, sizeof(uint64_t) * (size_t)fmt.L);
+    if (neg) negate(out, fmt.L);
+    return 0;
+}
+
+/* ---- fixed point -> double --------------------------------------------------------------------------------------------
+ * X 2^-F rounded to nearest, ties to even, subnormals included (what float(Fraction(X, 2**F)) is): the top p bits of |X|,
+ * p = 53 or fewer where the result is subnormal, the next bit and a sticky bit below it. */
+static double fixed_to_double(const uint64_t* x, fx_fmt fmt)
+{
+    uint64_t m[kMaxLimbs];
+    memcpy(m, x, sizeof(uint64_t) * (size_t)fmt.L);
+    const int neg = is_negative(m, fmt.L);
+    if (neg) negate(m, fmt.L);
+    const int t = top_limb(m, fmt.L);
+    if (t < 0) return 0.0;
+    const long b = 64L * t + 63 - __builtin_clzll(m[t]);        /* highest set bit */
+    const long e = b - fmt.F;                                     /* 2^e <= |v| < 2^(e+1) */
+    long p = 53;
+    if (e < -1022) p = 53 - (-1022 - e);
+    const long shift = b + 1 - p;                                 /* bits below the kept ones */
+    double r;
+    if (shift <= 0) {
+        r = ldexp((double)m[0], -fmt.F);                          /* b < p <= 53: exact */
+    } else {
+        uint64_t v = 0;
+        for (long k = 0; k < 64 && k < p; ++k) v |= (uint64_t)bit_of(m, fmt.L, shift + k) << k;
+        const int half = bit_of(m, fmt.L, shift - 1), sticky = any_below(m, fmt.L, shift - 1);
+        if (half && (sticky || (v & 1u))) ++v;
+        r = ldexp((double)v, (int)(shift - fmt.F));
+    }
+    return neg ? -r : r;
+}
+
+/* ---- the reference orbit ------------------------------------------------------------------------------------------------ */
+
+/* floor(sign * P / 2^s) into r (L limbs, two's complement); P a 2L-limb magnitude */
+static void floor_shift(uint64_t* r, const uint64_t* P, int s, int negative, fx_fmt fmt)
+{
+    const int lost = shr_bits(r, fmt.L, P, 2 * fmt.L, s);
+    if (negative) {
+        if (lost) add_one(r, fmt.L);
+        negate(r, fmt.L);
+    }
+}
+
+static int orbit_loop(const uint64_t* cr, const uint64_t* ci, fx_fmt fmt, int32_t max_iter, float bailout, double* out_xy,
+                      int32_t* out_len)
+{
+    const int L = fmt.L, L2 = 2 * fmt.L;
+    uint64_t zr[kMaxLimbs], zi[kMaxLimbs], ar[kMaxLimbs], ai[kMaxLimbs], t0[kMaxLimbs], t1[kMaxLimbs];
+    uint64_t sr[2 * kMaxLimbs + 1], si[2 * kMaxLimbs + 1], pr[2 * kMaxLimbs], ssum[2 * kMaxLimbs + 1], T[2 * kMaxLimbs + 1];
+    memset(zr, 0, sizeof zr); memset(zi, 0, sizeof zi);
+    memset(sr, 0, sizeof sr); memset(si, 0, sizeof si);
+    /* T = floor(bailout^2 2^(2F)): |Z|^2 2^(2F) = Zr^2 + Zi^2 is an integer, so "> bailout^2" is "> T" exactly */
+    memset(T, 0, sizeof T);
+    const double b2 = (double)bailout * (double)bailout;          /* exact: a float squared */
+    int ex = 0;
+    const double mant = frexp(b2, &ex);
+    const uint64_t mi = (uint64_t)ldexp(mant, 53);
+    const long ts = (long)ex - 53 + 2L * fmt.F;
+    T[0] = mi;
+    if (ts >= 0) shl_bits(T, L2 + 1, (int)ts);
+    else T[0] = -ts >= 64 ? 0 : mi >> -ts;
+
+    out_xy[0] = 0.0; out_xy[1] = 0.0;
+    int32_t n = 0;
+    for (;; ++n) {
+        if (n == max_iter) break;
+        /* magnitudes of Zr, Zi */
+        memcpy(ar, zr, sizeof(uint64_t) * (size_t)L);
+        memcpy(ai, zi, sizeof(uint64_t) * (size_t)L);
+        const int nr = is_negative(ar, L), ni = is_negative(ai, L);
+        if (nr) negate(ar, L);
+        if (ni) negate(ai, L);
+        mul_mag(sr, ar, ar, L);
+        mul_mag(si, ai, ai, L);
+        sr[L2] = si[L2] = 0;
+        add_n(ssum, sr, si, L2 + 1);
+        if (cmp_n(ssum, T, L2 + 1) > 0) break;                     /* |Z_n|^2 > bailout^2 */
+        mul_mag(pr, ar, ai, L);
+        /* Re = floor(Zr^2 / 2^F) - floor(Zi^2 / 2^F) + Cr,  Im = floor(2 Zr Zi / 2^F) + Ci */
+        floor_shift(t0, sr, fmt.F, 0, fmt);
+        floor_shift(t1, si, fmt.F, 0, fmt);
+        sub_n(zr, t0, t1, L);
+        add_n(zr, zr, cr, L);
+        floor_shift(t0, pr, fmt.F - 1, nr != ni, fmt);
+        add_n(zi, t0, ci, L);
+        out_xy[2 * (n + 1)] = fixed_to_double(zr, fmt);
+        out_xy[2 * (n + 1) + 1] = fixed_to_double(zi, fmt);
+    }
+    *out_len = n + 1;
+    return FR_OK;
+}
+
+/* ---- public entry points ------------------------------------------------------------------------------------------------ */
+
+int fr_deep_view_default(fr_deep_view* v)
+{
+    if (!v) return fr_set_error(FR_ERR_INVALID_ARG, "deep view is NULL");
+    v->center_x = "-0.5";
+    v->center_y = "0";
+    v->frac_bits = 0;
+    v->reserved = 0;
+    return FR_OK;
+}
+
+int fr_deep_frac_bits(double zoom)
+{
+    if (!isfinite(zoom) || !(zoom > 0.0))
+        return fr_set_error(FR_ERR_INVALID_ARG, "fr_deep_frac_bits: zoom must be finite and > 0");
+    double want = 64.0 + (double)(int)(-log10(zoom) * 3.32) + 64.0;   /* src/deep_zoom_system.cpp:209-260 */
+    if (want < 128.0) want = 128.0;
+    if (want > (double)kMaxFracBits) want = kMaxFracBits;
+    const int bits = (int)want;
+    return (bits + 63) / 64 * 64;
+}
+
+/* the view's F (automatic or given), or < 0 after setting the error */
+static int view_frac_bits(const fr_deep_view* v, double zoom)
+{
+    if (!v) return fr_set_error(FR_ERR_INVALID_ARG, "deep view is NULL");
+    if (v->reserved != 0) return fr_set_error(FR_ERR_INVALID_ARG, "fr_deep_view.reserved must be 0");
+    if (v->frac_bits != 0 && (v->frac_bits < 128 || v->frac_bits > kMaxFracBits))
+        return fr_set_error(FR_ERR_INVALID_ARG, "frac_bits %d outside {0} U [128, 4096]", v->frac_bits);
+    if (!v->center_x || !v->center_y) return fr_set_error(FR_ERR_INVALID_ARG, "deep view centre string is NULL");
+    return v->frac_bits ? v->frac_bits : fr_deep_frac_bits(zoom);
+}
+
+static int check_zoom(double zoom)
+{
+    if (!isfinite(zoom) || !(zoom >= 1e-290) || !(zoom <= 1e3))
+        return fr_set_error(FR_ERR_INVALID_ARG, "deep zoom %g outside [1e-290, 1e3]", zoom);
+    return FR_OK;
+}
+
+static int check_bailout(float bailout)
+{
+    if (!isfinite(bailout) || !(bailout > 0.0f) || !(bailout <= 65536.0f))
+        return fr_set_error(FR_ERR_INVALID_ARG, "deep bailout must be finite, > 0 and <= 2^16");
+    return FR_OK;
+}
+
+/* both centre strings in fixed point; FR_OK or FR_ERR_INVALID_ARG */
+static int parse_centre(const fr_deep_view* v, fx_fmt fmt, uint64_t* cr, uint64_t* ci)
+{
+    const char* which[2] = {"center_x", "center_y"};
+    const char* str[2] = {v->center_x, v->center_y};
+    uint64_t* dst[2] = {cr, ci};
+    for (int k = 0; k < 2; ++k) {
+        const int st = parse_fixed(str[k], fmt, dst[k]);
+        if (st == -1)
+            return fr_set_error(FR_ERR_INVALID_ARG, "deep view %s is not [+-]digits[.digits][(e|E)[+-]digits] of at most 4096 "
+                                "characters", which[k]);
+        if (st == -2) return fr_set_error(FR_ERR_INVALID_ARG, "deep view %s: |centre| must be < 2^32", which[k]);
+    }
+    return FR_OK;
+}
+
+int fr_deep_validate(const fr_params* p, const fr_deep_view* v, uint32_t width, uint32_t height)
+{
+    if (!p || !v) return fr_set_error(FR_ERR_INVALID_ARG, "params/deep view is NULL");
+    if (p->fractal_type != FR_FRACTAL_MANDELBROT)
+        return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deep renders FR_FRACTAL_MANDELBROT only (got %d)", p->fractal_type);
+    if (p->precision != FR_PRECISION_F64)
+        return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deep needs FR_PRECISION_F64 (got %d)", p->precision);
+    fr_params q = *p;                                            /* the double centre is not read */
+    q.center_x = 0.0; q.center_y = 0.0;
+    int st = fr_params_validate(&q, width, height);
+    if (st != FR_OK) return st;
+    if ((st = check_zoom(p->zoom)) != FR_OK || (st = check_bailout(p->bailout)) != FR_OK) return st;
+    if (p->orbit_trap_enabled || p->stripe_enabled || p->interior_style == 2)
+        return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deep: the orbit trap, stripes and interior_style 2 need the whole "
+                            "orbit and are not available");
+    const int F = view_frac_bits(v, p->zoom);
+    if (F < 0) return F;
+    uint64_t cr[kMaxLimbs], ci[kMaxLimbs];
+    const fx_fmt fmt = {F, (F + 63) / 64 + 1};
+    return parse_centre(v, fmt, cr, ci);
+}
+
+int fr_deep_parse_fixed(const char* s, int32_t frac_bits, uint64_t* out, int32_t nlimbs)
+{
+    if (!s || !out) return fr_set_error(FR_ERR_INVALID_ARG, "fr_deep_parse_fixed: NULL argument");
+    if (frac_bits < 128 || frac_bits > kMaxFracBits)
+        return fr_set_error(FR_ERR_INVALID_ARG, "frac_bits %d outside [128, 4096]", frac_bits);
+    const fx_fmt fmt = {frac_bits, (frac_bits + 63) / 64 + 1};
+    if (nlimbs < fmt.L) return fr_set_error(FR_ERR_INVALID_ARG, "fr_deep_parse_fixed: %d limbs, %d needed", nlimbs, fmt.L);
+    uint64_t x[kMaxLimbs];
+    const fr_deep_view v = {s, "0", frac_bits, 0};
+    uint64_t unused[kMaxLimbs];
+    const int st = parse_centre(&v, fmt, x, unused);
+    if (st != FR_OK) return st;
+    memcpy(out, x, sizeof(uint64_t) * (size_t)fmt.L);
+    return fmt.L;
+}
+
+int fr_deep_reference_orbit(const fr_deep_view* v, double zoom, int32_t max_iter, float bailout, double* out_xy,
+                            int32_t* out_len)
+{
+    if (!out_xy || !out_len) return fr_set_error(FR_ERR_INVALID_ARG, "fr_deep_reference_orbit: out is NULL");
+    if (max_iter < 1 || max_iter > (1 << 24))
+        return fr_set_error(FR_ERR_INVALID_ARG, "max_iterations %d outside [1, 2^24]", max_iter);
+    int st;
+    if ((st = check_zoom(zoom)) != FR_OK || (st = check_bailout(bailout)) != FR_OK) return st;
+    const int F = view_frac_bits(v, zoom);
+    if (F < 0) return F;
+    const fx_fmt fmt = {F, (F + 63) / 64 + 1};
+    uint64_t cr[kMaxLimbs], ci[kMaxLimbs];
+    if ((st = parse_centre(v, fmt, cr, ci)) != FR_OK) return st;
+    return orbit_loop(cr, ci, fmt, max_iter, bailout, out_xy, out_len);
+}

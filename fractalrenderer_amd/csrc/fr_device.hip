@@ -18,6 +18,7 @@
 #include "fr_kernels.hip.h"
 #include "fr_phoenix.hip.h"
 #include "fr_mandelbulb.hip.h"
+#include "fr_deep.hip.h"
 #include "fr_tuning.h"
 
 using namespace fr;
@@ -109,6 +110,17 @@ struct fr_ctx {
     int phoenix_wg_per_cu[2];   /* resident workgroups per CU of phoenix_kernel<float> / <double> (0 = not asked yet) */
     int mandelbulb_wg_per_cu[2];  /* ... of mandelbulb_kernel<false> / <true> (0 = not asked yet) */
     uint32_t tune_mandelbulb_split;  /* 0 = automatic (march / shade split), 1 = shade at the hit, inside the march loop */
+    /* deep views (fr_render_deep): the most recent reference orbit, on the device, and what it was computed for */
+    double* deep_orbit_host;    /* pinned upload buffer, deep_orbit_cap points */
+    double2* deep_orbit_dev;    /* Z_0 .. Z_N */
+    size_t deep_orbit_cap;
+    int32_t deep_len;           /* N + 1 */
+    bool deep_valid;            /* the key below describes deep_orbit_dev */
+    char* deep_key_x;           /* centre strings (malloc'd copies) */
+    char* deep_key_y;
+    int32_t deep_key_bits, deep_key_iter;
+    float deep_key_bailout;
+    int deep_wg_per_cu;         /* resident workgroups per CU of deep_kernel (0 = not asked yet) */
 };
 
 #define FR_HIP_TRY(expr)                                                               \
@@ -190,6 +202,10 @@ extern "C" void fr_ctx_destroy(fr_ctx* c)
     if (c->frame_buf) (void)hipFree(c->frame_buf);
     if (c->orbit_host) (void)hipHostFree(c->orbit_host);
     if (c->orbit_dev) (void)hipFree(c->orbit_dev);
+    if (c->deep_orbit_host) (void)hipHostFree(c->deep_orbit_host);
+    if (c->deep_orbit_dev) (void)hipFree(c->deep_orbit_dev);
+    free(c->deep_key_x);
+    free(c->deep_key_y);
     if (c->ev_begin) (void)hipEventDestroy(c->ev_begin);
     if (c->ev_end) (void)hipEventDestroy(c->ev_end);
     if (c->ev_order) (void)hipEventDestroy(c->ev_order);
@@ -791,6 +807,109 @@ static int enqueue_mandelbulb(fr_ctx* c, const fr_params* p, const fr_mandelbulb
     return finish_render(c, stream, 1);
 }
 
+/* ---- deep views (fr_deep.hip.h) -------------------------------------------------------------------------------------
+ * The reference orbit of the view (fr_deep.c, on the host) unless the context holds it already, then one pass as Phoenix:
+ * a persistent grid of exactly the resident set (occupancy query, cached) over the 8x8 sub-tiles of the WaveQueue,
+ * planned as an unstaged tile pass with unlimited stealing. */
+static char* copy_string(const char* s)
+{
+    const size_t n = strlen(s) + 1;
+    char* d = (char*)malloc(n);
+    if (d) memcpy(d, s, n);
+    return d;
+}
+
+static int deep_orbit_for(fr_ctx* c, const fr_params* p, const fr_deep_view* v, hipStream_t stream)
+{
+    const int32_t bits = v->frac_bits ? v->frac_bits : fr_deep_frac_bits(p->zoom);
+    const int32_t max_iter = p->max_iterations;
+    if (c->deep_valid && c->deep_key_bits == bits && c->deep_key_iter == max_iter &&
+        memcmp(&c->deep_key_bailout, &p->bailout, sizeof(float)) == 0 && strcmp(c->deep_key_x, v->center_x) == 0 &&
+        strcmp(c->deep_key_y, v->center_y) == 0)
+        return FR_OK;
+    /* the pinned buffer may still feed an earlier upload, the device orbit an earlier render (on this stream, the
+     * context's own or the stream of the previous render) */
+    FR_HIP_TRY(hipStreamSynchronize(stream));
+    FR_HIP_TRY(hipStreamSynchronize(c->stream));
+    if (c->have_render && c->last_stream != stream) FR_HIP_TRY(hipStreamSynchronize(c->last_stream));
+    c->deep_valid = false;
+    const size_t need = (size_t)max_iter + 1;
+    if (need > c->deep_orbit_cap) {
+        if (c->deep_orbit_host) { (void)hipHostFree(c->deep_orbit_host); c->deep_orbit_host = nullptr; }
+        if (c->deep_orbit_dev) { (void)hipFree(c->deep_orbit_dev); c->deep_orbit_dev = nullptr; }
+        c->deep_orbit_cap = 0;
+        FR_HIP_TRY(hipHostMalloc((void**)&c->deep_orbit_host, need * 2 * sizeof(double)));
+        FR_HIP_TRY(hipMalloc((void**)&c->deep_orbit_dev, need * sizeof(double2)));
+        c->deep_orbit_cap = need;
+    }
+    int32_t len = 0;
+    const int st = fr_deep_reference_orbit(v, p->zoom, max_iter, p->bailout, c->deep_orbit_host, &len);
+    if (st != FR_OK) return st;
+    FR_HIP_TRY(hipMemcpyAsync(c->deep_orbit_dev, c->deep_orbit_host, (size_t)len * sizeof(double2), hipMemcpyHostToDevice,
+                              stream));
+    FR_HIP_TRY(hipStreamSynchronize(stream));     /* a later render of this view may go to another stream */
+    free(c->deep_key_x); free(c->deep_key_y);
+    c->deep_key_x = copy_string(v->center_x);
+    c->deep_key_y = copy_string(v->center_y);
+    if (!c->deep_key_x || !c->deep_key_y) return fr_set_error(FR_ERR_NOMEM, "out of host memory");
+    c->deep_key_bits = bits; c->deep_key_iter = max_iter; c->deep_key_bailout = p->bailout;
+    c->deep_len = len;
+    c->deep_valid = true;
+    return FR_OK;
+}
+
+static int enqueue_deep(fr_ctx* c, const fr_params* p, const fr_deep_view* v, uint32_t W, uint32_t H, const fr_shard* shard,
+                        float* rgba, void* nu, int32_t* iter, hipStream_t stream, bool out_frame)
+{
+    const int ov = check_overflow(c);            /* of an earlier asynchronous render nobody has asked about */
+    if (ov != FR_OK) return ov;
+    fr_shard norm;
+    uint32_t rows_local = 0;
+    const int sh = normalise_shard(shard, H, &norm, &rows_local);
+    if (sh != FR_OK || rows_local == 0) return sh;
+    const int os = deep_orbit_for(c, p, v, stream);
+    if (os != FR_OK) return os;
+
+    DeepArgs a;
+    memset(&a, 0, sizeof(a));
+    a.orbit = c->deep_orbit_dev; a.n_ref = c->deep_len - 1;
+    a.max_iter = p->max_iterations; a.aa = p->antialiasing_samples;
+    a.zoom = p->zoom;
+    a.B2 = (double)p->bailout * (double)p->bailout;
+    a.W = (int32_t)W; a.H = (int32_t)H; a.rows_local = (int32_t)rows_local;
+    a.part = (int32_t)norm.part; a.nparts = (int32_t)norm.nparts; a.rows_per_strip = (int32_t)norm.rows_per_strip;
+    a.out_frame = out_frame ? 1 : 0;
+    a.flags = p->flags;
+    a.interior_style = p->interior_style;
+    a.lib_log = !(p->bailout > 1.0f);            /* as fill_params */
+    a.inv_max_iter = 1.0 / (double)p->max_iterations;
+    a.inv_log2_bailout = 1.0 / log2((double)p->bailout);
+    a.color_scale_d = (double)p->color_scale; a.color_offset_d = (double)p->color_offset;
+    a.brightness = p->color_brightness; a.saturation = p->color_saturation; a.contrast = p->color_contrast;
+    fr_palette_table_build(0, p->palette_mode, &a.pal);
+    a.log2_tab = c->log2_tab;
+    a.rgba = reinterpret_cast<float4*>(rgba); a.nu = (double*)nu; a.iter = iter;
+
+    if (c->deep_wg_per_cu == 0) {
+        int nb = 0;
+        const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, deep_kernel, kBlockThreads, 0);
+        if (e != hipSuccess) return fr_set_error(FR_ERR_HIP, "deep occupancy query failed: %s", hipGetErrorString(e));
+        c->deep_wg_per_cu = nb < 1 ? 1 : nb;
+    }
+    uint32_t grid = 0;
+    a.q = plan_tile_queue(c, W, rows_local, 3, false, false, (uint32_t)c->deep_wg_per_cu, &grid);
+    a.q.heads = stage_heads(c, 0);
+    c->last_grid = grid;
+    c->last_pool_closing = -1;
+
+    FR_HIP_TRY(clear_control_block(c, stream, 1));
+    if (c->timing) FR_HIP_TRY(hipEventRecord(c->ev_begin, stream));
+    hipLaunchKernelGGL(deep_kernel, dim3(grid), dim3(kBlockThreads), 0, stream, a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fr_set_error(FR_ERR_HIP, "deep kernel launch failed: %s", hipGetErrorString(e));
+    return finish_render(c, stream, 1);
+}
+
 /* the parameter part of the kernel argument block (everything that does not depend on the frame geometry) */
 static void fill_params(LaunchArgs& a, const fr_params* p)
 {
@@ -1345,7 +1464,7 @@ static int enqueue_ssaa_staged(fr_ctx* c, const fr_params* p, uint32_t W, uint32
 }
 
 /* ---- render entry points --------------------------------------------------------------------------------------------
- * fr_render_shard(_async), fr_render_phoenix(_async) and fr_render_mandelbulb(_async): their parameter checks, then render_sync / render_async with the
+ * fr_render_shard(_async), fr_render_phoenix(_async), fr_render_mandelbulb(_async) and fr_render_deep(_async): their parameter checks, then render_sync / render_async with the
  * enqueue step as enqueue(shard, rgba, nu, iter, stream, out_frame) */
 static int check_common(fr_ctx* c, const fr_params* p, uint32_t W, uint32_t H, const fr_output* out)
 {
@@ -1544,6 +1663,32 @@ extern "C" int fr_render_mandelbulb(fr_ctx* c, const fr_params* p, const fr_mand
     if (st != FR_OK) return st;
     return render_sync(c, p, W, H, shard, out, [&](auto sh, auto rgba, auto nu, auto iter, auto s, bool out_frame) {
         return enqueue_mandelbulb(c, p, mb, W, H, sh, rgba, nu, iter, s, out_frame); });
+}
+
+static int check_deep(fr_ctx* c, const fr_params* p, const fr_deep_view* v, uint32_t W, uint32_t H, const fr_output* out)
+{
+    if (!c) return fr_set_error(FR_ERR_INVALID_ARG, "ctx is NULL");
+    if (!p || !v || !out) return fr_set_error(FR_ERR_INVALID_ARG, "params/deep view/out is NULL");
+    return fr_deep_validate(p, v, W, H);
+}
+
+extern "C" int fr_render_deep_async(fr_ctx* c, const fr_params* p, const fr_deep_view* v, uint32_t W, uint32_t H,
+                                    const fr_shard* shard, const fr_output* out, void* hip_stream)
+{
+    const int st = check_deep(c, p, v, W, H, out);
+    if (st != FR_OK) return st;
+    return render_async("fr_render_deep_async", c, H, shard, out, hip_stream,
+                        [&](auto sh, auto rgba, auto nu, auto iter, auto s, bool out_frame) {
+                            return enqueue_deep(c, p, v, W, H, sh, rgba, nu, iter, s, out_frame); });
+}
+
+extern "C" int fr_render_deep(fr_ctx* c, const fr_params* p, const fr_deep_view* v, uint32_t W, uint32_t H,
+                              const fr_shard* shard, const fr_output* out)
+{
+    const int st = check_deep(c, p, v, W, H, out);
+    if (st != FR_OK) return st;
+    return render_sync(c, p, W, H, shard, out, [&](auto sh, auto rgba, auto nu, auto iter, auto s, bool out_frame) {
+        return enqueue_deep(c, p, v, W, H, sh, rgba, nu, iter, s, out_frame); });
 }
 
 /* ---- 8-bit export ------------------------------------------------------------------------------ */

@@ -27,6 +27,11 @@ fr_shard fr_shard_normalise(const fr_shard* s, uint32_t height);
 int fr_phoenix_validate(const fr_params* p, const fr_phoenix_params* ph, uint32_t width, uint32_t height);
 /* the validation of fr_render_mandelbulb (fr_host.c); width == height == 0 skips the frame-size rules */
 int fr_mandelbulb_validate(const fr_params* p, const fr_mandelbulb_params* mb, uint32_t width, uint32_t height);
+/* the validation of fr_render_deep (fr_deep.c), the centre strings parsed included */
+int fr_deep_validate(const fr_params* p, const fr_deep_view* v, uint32_t width, uint32_t height);
+/* tests: a centre string in the fixed point of the reference orbit (fr_deep.c): ceil(frac_bits / 64) + 1 little-endian
+ * two's-complement limbs into out[0 .. nlimbs); returns that number of limbs or an error */
+int fr_deep_parse_fixed(const char* s, int32_t frac_bits, uint64_t* out, int32_t nlimbs);
 
 /* the context's own stream (hipStream_t) and device ordinal: fr_node.cpp orders RCCL transfers behind the renders */
 void* fr_ctx_stream_handle(fr_ctx* ctx);

@@ -18,7 +18,7 @@ from typing import Optional
 import numpy as np
 
 from . import _capi
-from .state import FractalState, FractalType, MandelbulbParams, PhoenixParams, Precision
+from .state import DeepView, FractalState, FractalType, MandelbulbParams, PhoenixParams, Precision
 
 
 @dataclass(frozen=True)
@@ -210,9 +210,24 @@ class Renderer:
         self._render_call(self._lib.fr_render_mandelbulb, self._lib.fr_render_mandelbulb_async, (C.byref(p), C.byref(mb)),
                           width, height, Precision.F32, rows, rgba, nu, iter, shard, stream, sync)
 
+    def render_deep(self, state: FractalState, width: int, height: int, view: Optional[DeepView] = None, *,
+                    post_chain: bool = False, rgba=None, nu=None, iter=None, shard: Optional[Shard] = None,
+                    stream: Optional[int] = None, sync: bool = True) -> None:
+        """fr_render_deep / fr_render_deep_async: a Mandelbrot view deeper than double precision, by perturbation around one
+        reference orbit computed on the host.  `view` carries the centre as decimal strings (default: "-0.5", "0"); the
+        zoom and every other field come from `state` (its double centre is not read).  Always fp64: nu is float64.
+        Planes, shard, stream and sync as for render().  A new view computes its orbit on the host first, also with
+        sync=False; a render of the view the context holds is launch-only."""
+        p = state.to_params(FractalType.Mandelbrot, Precision.F64, post_chain)
+        v = (view or DeepView()).to_c()
+        rows = shard.rows(height) if shard else height
+        self._render_call(self._lib.fr_render_deep, self._lib.fr_render_deep_async, (C.byref(p), C.byref(v)), width, height,
+                          Precision.F64, rows, rgba, nu, iter, shard, stream, sync)
+
     def _render_call(self, fn_sync, fn_async, params: tuple, width: int, height: int, precision: Precision, rows: int,
                      rgba, nu, it, shard: Optional[Shard], stream: Optional[int], sync: bool) -> None:
-        """the planes, the shard and the sync / async entry of render(), render_phoenix() and render_mandelbulb(); params: the entry's
+        """the planes, the shard and the sync / async entry of render(), render_phoenix(), render_mandelbulb() and render_deep();
+        params: the entry's
         arguments between the context and the frame size"""
         out = self._output(precision, rows, width, rgba, nu, it)
         sh = shard.to_c() if shard else None

@@ -184,3 +184,34 @@ def pack_push_constants_mandelbulb(state: FractalState, mandelbulb: MandelbulbPa
     mb = (mandelbulb or MandelbulbParams()).to_c()
     _capi.check(_capi.lib().fr_pack_push_constants_mandelbulb(_capi.C.byref(p), _capi.C.byref(mb), out))
     return np.array(out[:], dtype=np.float32)
+
+
+@dataclass(frozen=True)
+class DeepView:
+    """The centre of a view deeper than double precision (fr_deep_view): decimal strings, [+-]digits[.digits][(e|E)[+-]digits]
+    of at most 4096 characters, or Decimals (written out with str()).  frac_bits: fraction bits of the host's fixed-point
+    reference orbit, 0 = automatic (deep_frac_bits(zoom)).  The zoom is FractalState.zoom; its centre is not read."""
+    center_x: object = "-0.5"
+    center_y: object = "0"
+    frac_bits: int = 0
+
+    def to_c(self) -> _capi.fr_deep_view:
+        return _capi.fr_deep_view(str(self.center_x).encode("ascii"), str(self.center_y).encode("ascii"),
+                                  int(self.frac_bits), 0)
+
+
+def deep_frac_bits(zoom: float) -> int:
+    """fr_deep_frac_bits: the automatic fraction bits of a deep view at this zoom."""
+    n = int(_capi.lib().fr_deep_frac_bits(float(zoom)))
+    _capi.check(min(n, 0))
+    return n
+
+
+def deep_reference_orbit(view: DeepView, zoom: float, max_iterations: int, bailout: float = 4.0) -> np.ndarray:
+    """fr_deep_reference_orbit: Z_0 .. Z_N of the view as an (N + 1, 2) float64 array (host only)."""
+    buf = np.empty((int(max_iterations) + 1, 2), np.float64)
+    n = _capi.C.c_int32()
+    v = view.to_c()
+    _capi.check(_capi.lib().fr_deep_reference_orbit(_capi.C.byref(v), float(zoom), int(max_iterations), _F32(bailout),
+                                                    buf.ctypes.data, _capi.C.byref(n)))
+    return buf[:n.value].copy()

@@ -392,6 +392,76 @@ int fr_render_mandelbulb(fr_ctx* ctx, const fr_params* p, const fr_mandelbulb_pa
 int fr_render_mandelbulb_async(fr_ctx* ctx, const fr_params* p, const fr_mandelbulb_params* mb, uint32_t width,
                                uint32_t height, const fr_shard* shard, const fr_output* out, void* hip_stream);
 
+/* ---- Mandelbrot views deeper than double precision ------------------------------------------------------------------
+ * fr_params holds its centre as double, so no other path can show a view whose pixel spacing is below one ulp of the
+ * centre (about 1e-13 of height near |c| ~ 1): neighbouring pixels collapse onto one c.  These entry points take the
+ * centre as decimal strings and render by perturbation around ONE reference orbit:
+ *   - the reference Z_n at the exact centre C is computed on the host in fixed point with frac_bits fraction bits
+ *     (below) and stored as doubles;
+ *   - every sample iterates its fp64 delta dz from it, dc being its offset from the centre, and is REBASED to the start
+ *     of the orbit (dz = z, m = 0) whenever |z| < |dz| or the orbit ends (Zhuoran's rebasing): no glitch detection and
+ *     no second reference are needed.
+ * Deltas are fp64, so the zoom reaches 1e-290.
+ *
+ * The view: centre_x / centre_y are decimal strings, [+-]digits[.digits][(e|E)[+-]digits], at most 4096 characters,
+ * |centre| < 2^32; p->center_x and p->center_y are ignored.  The zoom is p->zoom (the view height, as everywhere), finite
+ * and in [1e-290, 1e3].  p->fractal_type must be FR_FRACTAL_MANDELBROT and p->precision FR_PRECISION_F64, and the orbit
+ * trap, stripes and interior_style 2 are not available (they need the whole orbit): otherwise FR_ERR_UNSUPPORTED.  The
+ * other fields follow fr_params_validate's rules; bailout must also be <= 2^16.  A malformed string, reserved != 0 or
+ * frac_bits outside {0} U [128, 4096] is FR_ERR_INVALID_ARG.
+ *
+ * Reference orbit: each centre string becomes a signed fixed-point number with F = frac_bits fraction bits and at least 64
+ * integer bits, rounded to nearest, ties to even.  From Z_0 = 0, Z_{n+1} = Z_n^2 + C with
+ *   Re = floor(Zr Zr / 2^F) - floor(Zi Zi / 2^F) + Cr,   Im = floor(2 Zr Zi / 2^F) + Ci
+ * (floor: the arithmetic shift of two's complement), up to the first N with |Z_N|^2 > bailout^2 (compared exactly) or
+ * N = max_iterations.  Z_0 .. Z_N are stored as doubles, rounded to nearest.
+ *
+ * Per sample (x, y) and sub-sample (sx, sy) -- shaders/mandelbrot.comp:219-230's order, sy outer:
+ *   dc = (((x + sx/aa) - 0.5 W) / H * zoom, ((y + sy/aa) - 0.5 H) / H * zoom), dz = 0, m = 0; then for i = 0 .. max_iter-1:
+ *   t = (Z_m + Z_m) + dz;  dz' = (t.x dz.x - t.y dz.y, t.x dz.y + t.y dz.x) + dc;  m += 1;  z = Z_m + dz';  r2 = |z|^2
+ *   r2 > bailout^2: escaped at i;  else if r2 < |dz'|^2 or m == N: dz = z, m = 0 (rebase);  else dz = dz'
+ * each operation one fp64 rounding as written (no contraction).  The planes are those of fr_render's fp64 Mandelbrot path
+ * for the same (i, r2): nu (double) = smooth count of sample (0,0), iter = its i (max_iterations for interior), rgba =
+ * palette / interior_style 0-1 / aa average / FR_FLAG_POST_CHAIN exactly as there. */
+#define FR_HAS_DEEP 1
+
+typedef struct fr_deep_view {
+    const char* center_x;          /* decimal string (see above) */
+    const char* center_y;
+    int32_t     frac_bits;         /* fraction bits F of the reference orbit; 0 = automatic (fr_deep_frac_bits(zoom)) */
+    int32_t     reserved;          /* must be 0 */
+} fr_deep_view;                    /* 24 bytes on LP64 */
+
+/* "-0.5", "0", 0, 0: FractalState's centre (src/fractal_state.h:18-19). */
+int fr_deep_view_default(fr_deep_view* v);
+
+/* The automatic fraction bits: 64 + (int)(-log10(zoom) * 3.32) + 64 (the reference's calculate_required_precision_bits,
+ * src/deep_zoom_system.cpp:209-260), clamped to [128, 4096], rounded up to a multiple of 64.  zoom must be finite and > 0
+ * (FR_ERR_INVALID_ARG otherwise). */
+int fr_deep_frac_bits(double zoom);
+
+/* The reference orbit of a view, on the host (for callers and tests): out_xy receives Z_0 .. Z_N as (re, im) doubles,
+ * 2 (max_iter + 1) doubles at most; *out_len = N + 1.  Validates the view, zoom (for the automatic F), max_iter and
+ * bailout as fr_render_deep does.  Takes about 3 L^2 64x64-bit products per iteration, L = ceil(F / 64) + 1 limbs. */
+int fr_deep_reference_orbit(const fr_deep_view* v, double zoom, int32_t max_iter, float bailout, double* out_xy,
+                            int32_t* out_len);
+
+/* A deep view (or one part of a row-strip sharding of it: shard NULL = the whole frame) into `out`, synchronously.
+ * Planes as for fr_render: FR_MEM_HOST / FR_MEM_DEVICE, FR_LAYOUT_FRAME.  Options: "shards" and "timing" apply,
+ * "periodicity" and "staging" are accepted and have no effect; fr_ctx_last_kernel_ms and fr_ctx_last_grid cover it.
+ * Orbit cache: the context keeps the most recent reference orbit on the device, keyed by (centre strings, F,
+ * max_iterations, bailout); a render of another view computes its orbit on the host first. */
+int fr_render_deep(fr_ctx* ctx, const fr_params* p, const fr_deep_view* view, uint32_t width, uint32_t height,
+                   const fr_shard* shard, const fr_output* out);
+
+/* Asynchronous form, the fr_render_shard_async contract: device planes only, enqueued on hip_stream (NULL = the
+ * context's stream); errors the device reports later surface through fr_ctx_check.  A render of the view whose orbit
+ * the context holds is launch-only.  A render of a NEW view computes its reference orbit on the host (the calling thread,
+ * see fr_deep_reference_orbit for the cost) and waits for hip_stream -- and for the stream of the context's previous
+ * render -- before it reuses its pinned upload buffer and the device orbit: never launch-only. */
+int fr_render_deep_async(fr_ctx* ctx, const fr_params* p, const fr_deep_view* view, uint32_t width, uint32_t height,
+                         const fr_shard* shard, const fr_output* out, void* hip_stream);
+
 /* ---- frames over the GPUs of a node (BASELINE.json north_star: "tiled across the 8 GPUs of one node as disjoint row
  * bands with a final RCCL gather over xGMI") -----------------------------------------------------------------------------
  * New design, no reference counterpart: the reference renders on the one GPU it picked (src/vk_engine.cpp:608).  What it

@@ -5,12 +5,12 @@ fractalrenderer_amd/csrc/).  This package is the thin host-side mirror of the re
 interface for that path.  Importing it loads the library and fails loudly if it is absent.
 """
 from . import _capi
-from ._capi import FractalRendererError, lib
+from ._capi import FR_FLAG_DEEP_BLA, FractalRendererError, lib
 from .state import (FractalState, FractalType, Precision, Preset, MANDELBROT_PRESETS,
                     SEAHORSE_DEEP, pack_push_constants, PhoenixParams, PHOENIX_PRESETS, pack_push_constants_phoenix,
                     MandelbulbParams, MANDELBULB_PRESETS, pack_push_constants_mandelbulb, DeepView, deep_frac_bits,
                     deep_reference_orbit)
-from .renderer import (Renderer, Node, Shard, write_png, write_raw_rgb24, frame_path, export8_thresholds, rccl_selftest,
+from .renderer import (Renderer, DeepSteps, Node, Shard, write_png, write_raw_rgb24, frame_path, export8_thresholds, rccl_selftest,
                        mapped_runtimes)
 from .animation import (AnimationSystem, AnimationRenderer, InterpolationType, Keyframe, DeepZoomPath, ZoomKeyframe)
 
@@ -20,7 +20,7 @@ __all__ = [
     "FractalRendererError", "lib", "FractalState", "FractalType", "Precision", "Preset",
     "MANDELBROT_PRESETS", "SEAHORSE_DEEP", "pack_push_constants", "PhoenixParams", "PHOENIX_PRESETS",
     "pack_push_constants_phoenix", "MandelbulbParams", "MANDELBULB_PRESETS", "pack_push_constants_mandelbulb", "DeepView",
-    "deep_frac_bits", "deep_reference_orbit", "Renderer", "Node", "Shard",
+    "deep_frac_bits", "deep_reference_orbit", "FR_FLAG_DEEP_BLA", "DeepSteps", "Renderer", "Node", "Shard",
     "write_png", "write_raw_rgb24", "frame_path", "export8_thresholds", "rccl_selftest", "mapped_runtimes",
     "AnimationSystem", "AnimationRenderer", "InterpolationType", "Keyframe", "DeepZoomPath", "ZoomKeyframe",
 ]

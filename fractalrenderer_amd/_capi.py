@@ -37,6 +37,7 @@ FR_PRECISION_F32 = 0
 FR_PRECISION_F64 = 1
 
 FR_FLAG_POST_CHAIN = 0x1
+FR_FLAG_DEEP_BLA = 0x2
 
 
 class fr_params(C.Structure):
@@ -128,6 +129,7 @@ SIGNATURES = {
                                  _P(fr_output)]),
     "fr_render_deep_async": (C.c_int, [C.c_void_p, _P(fr_params), _P(fr_deep_view), C.c_uint32, C.c_uint32, _P(fr_shard),
                                        _P(fr_output), C.c_void_p]),
+    "fr_ctx_last_deep_steps": (C.c_int, [C.c_void_p, _P(C.c_uint64)]),
     "fr_ctx_create": (C.c_int, [C.c_int, _P(C.c_void_p)]),
     "fr_ctx_destroy": (None, [C.c_void_p]),
     "fr_shard_rows": (C.c_uint32, [_P(fr_shard), C.c_uint32]),
@@ -203,6 +205,7 @@ INTERNAL_SIGNATURES = {
     "fr_node_rccl_usable": (C.c_int, [C.c_void_p]),
     "fr_node_mapped_runtimes": (C.c_int, [C.c_char_p, C.c_size_t]),
     "fr_deep_parse_fixed": (C.c_int, [C.c_char_p, C.c_int32, _P(C.c_uint64), C.c_int32]),   # fr_internal.h: tests
+    "fr_deep_bla_table": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),        # fr_internal.h: tests
 }
 PUBLIC_OPTIONS = ("periodicity", "staging", "shards", "tile_kernel", "timing", "diag_buffer", "diag_stride")
 TUNING_NAMES = ("workgroups_per_cu", "run_max", "run_min", "shift_bias", "stage_first", "pool_refill_at", "stream_run_max",

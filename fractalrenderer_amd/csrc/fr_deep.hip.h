@@ -17,6 +17,12 @@
  *     wave has rebased, all 64 lanes read the same orbit point; after that they gather from different m;
  *   - smooth count, palette, interior style and the post chain are those of the fp64 Mandelbrot path: shade() and
  *     post_chain() of fr_kernels.hip.h on (i, r2).
+ *
+ * Bilinear approximation (FR_FLAG_DEEP_BLA; the semantics are in the header): deep_bla_level_kernel builds the table from the
+ * device orbit, one launch per level, and deep_kernel<DeepBlaArgs> runs deep_orbit_bla as its per-sample loop.  The
+ * table stores, level after level (level k from entry offset bla_offset(N - 1, k)), the radius r of every entry in an
+ * array of doubles of its own and (A, B) in an array of double2 pairs: a probe gathers 8 bytes, only the chosen level's
+ * 32 bytes of (A, B) are loaded.
  */
 #pragma once
 #include "fr_kernels.hip.h"
@@ -43,6 +49,69 @@ struct DeepArgs {
     int32_t* iter;
     QueueArgs q;
 };
+
+/* The BLA table of the cached orbit (deep_kernel<DeepBlaArgs> only) */
+struct BlaTable {
+    const double* r;                     /* r of every entry, level 1 first */
+    const double2* ab;                   /* A, B of every entry: ab[2 e], ab[2 e + 1] */
+    int32_t levels;                      /* K = floor(log2(N - 1)), 0 = no table */
+    unsigned long long* steps;           /* plain steps, BLA steps, updates skipped: one atomic add each per wave */
+};
+
+struct DeepBlaArgs {
+    DeepArgs d;
+    BlaTable t;
+};
+
+/* Entries before level k (>= 1) of a table over n1 = N - 1 single steps: sum_{i=1}^{k-1} (n1 >> i).  With
+ * S(x) = sum_{i>=1} (x >> i) = x - popcount(x) that is S(n1) - S(n1 >> (k - 1)). */
+__device__ __forceinline__ uint32_t bla_offset(const uint32_t n1, const int k)
+{
+    const uint32_t t = n1 >> (k - 1);
+    return (n1 - (uint32_t)__popc(n1)) - (t - (uint32_t)__popc(t));
+}
+
+/* |w| as the header writes it: sqrt(w.x*w.x + w.y*w.y).  On gfx950 sqrt(double) is LLVM's expansion of llvm.sqrt.f64:
+ * scaling of small arguments, v_rsq_f64, two Newton-Raphson refinements of the root and half-reciprocal root, and a final
+ * correction from the fma residual x - s*s -- the correctly rounded OCML sequence (tests/test_deep_bla_gpu.py compares
+ * every radius of device-built tables with numpy's bit for bit). */
+__device__ __forceinline__ double bla_abs(const double x, const double y) { return sqrt(x * x + y * y); }
+
+/* Level k of the table: entry j merges x (level k - 1, entry 2j) and y (level k - 1, entry 2j + 1); level 0 is the single
+ * step at m = 1 + i (A = 2 Z_m, B = 1, r = 2^-53 |Z_m|), computed from the orbit and never stored. */
+__global__ void __launch_bounds__(kBlockThreads)
+deep_bla_level_kernel(const double2* __restrict__ orbit, const int32_t n_ref, const int32_t k, const double dcmax,
+                      double* __restrict__ r, double2* __restrict__ ab)
+{
+    const uint32_t n1 = (uint32_t)(n_ref - 1);
+    const uint32_t cnt = n1 >> k;
+    const uint32_t off = bla_offset(n1, k);
+    const uint32_t offp = k > 1 ? bla_offset(n1, k - 1) : 0u;
+    for (uint32_t j = blockIdx.x * kBlockThreads + threadIdx.x; j < cnt; j += gridDim.x * kBlockThreads) {
+        double2 ax, bx, ay, by;
+        double rx, ry;
+        if (k == 1) {
+            const double2 zx = orbit[1 + 2 * j], zy = orbit[2 + 2 * j];
+            ax = make_double2(zx.x + zx.x, zx.y + zx.y); bx = make_double2(1.0, 0.0); rx = 0x1p-53 * bla_abs(zx.x, zx.y);
+            ay = make_double2(zy.x + zy.x, zy.y + zy.y); by = make_double2(1.0, 0.0); ry = 0x1p-53 * bla_abs(zy.x, zy.y);
+        } else {
+            const uint32_t ex = offp + 2 * j, ey = ex + 1;
+            ax = ab[2 * ex]; bx = ab[2 * ex + 1]; rx = r[ex];
+            ay = ab[2 * ey]; by = ab[2 * ey + 1]; ry = r[ey];
+        }
+        const double2 a = make_double2(ay.x * ax.x - ay.y * ax.y, ay.x * ax.y + ay.y * ax.x);
+        const double2 b = make_double2((ay.x * bx.x - ay.y * bx.y) + by.x, (ay.x * bx.y + ay.y * bx.x) + by.y);
+        const double t = (ry - bla_abs(bx.x, bx.y) * dcmax) / bla_abs(ax.x, ax.y);
+        double rr = t > 0.0 ? t : 0.0;                           /* NaN: 0 */
+        rr = rr < rx ? rr : rx;
+        if (!(__builtin_isfinite(a.x) && __builtin_isfinite(a.y) && __builtin_isfinite(b.x) && __builtin_isfinite(b.y)))
+            rr = 0.0;
+        const uint32_t e = off + j;
+        r[e] = rr;
+        ab[2 * e] = a;
+        ab[2 * e + 1] = b;
+    }
+}
 
 /* The wave's 64 samples, one per lane.  live = false: a lane without a sample (outside the frame).  esc = the loop index
  * of the escaping update (max_iter if none), r2 = |z|^2 there. */
@@ -80,9 +149,101 @@ __device__ __forceinline__ void deep_orbit(const DeepArgs& A, const double dcx, 
     }
 }
 
-__global__ void __launch_bounds__(kBlockThreads)
-deep_kernel(const DeepArgs A)
+/* deep_orbit with BLA: u replaces the loop index.  A lane at m >= 1 probes the levels top down from
+ * min(ctz(m - 1), K, floor(log2(N - m)), floor(log2(max_iter - u))) and takes the first k with |dz|^2 < r^2.  No level's
+ * r exceeds the single step's 2^-53 |Z_m| (r only ever shrinks in the merge), so a lane with
+ * |dz|^2 2^104 >= |Z_m|^2 (a bound above 2^-106 |Z_m|^2 with room for every rounding) cannot pass a probe and gathers
+ * nothing.  A BLA lane loads Z_m and Z_{m+1} at its new m (the Z_{m+2} prefetch is for the plain step); BLA and plain
+ * lanes of a wave take their steps in the same trip.  nplain / nbla: the steps this sample took. */
+__device__ __forceinline__ void deep_orbit_bla(const DeepArgs& A, const BlaTable& T, const double dcx, const double dcy,
+                                               const double2 z1, bool live, int& esc, double& er2, uint32_t& nplain,
+                                               uint32_t& nbla)
 {
+    const double2* __restrict__ orbit = A.orbit;
+    const double* __restrict__ tr = T.r;
+    const int N = A.n_ref, max_iter = A.max_iter, K = T.levels;
+    const uint32_t n1 = (uint32_t)(N - 1);
+    const double B2 = A.B2;
+    double dzx = 0.0, dzy = 0.0;
+    double Zx = 0.0, Zy = 0.0;                                   /* Z_m */
+    double Znx = z1.x, Zny = z1.y;                               /* Z_{m+1} */
+    int m = 0, u = 0;
+    esc = max_iter;
+    er2 = 0.0;
+    nplain = 0u; nbla = 0u;
+    for (;;) {
+        if (__builtin_amdgcn_ballot_w64(live) == 0ull) break;
+        if (!live) continue;
+        const double2 Znn = orbit[m + 2 <= N ? m + 2 : N];      /* Z_{m+2}, for a plain step */
+        const double dz2 = dzx * dzx + dzy * dzy;
+        int k = 0;
+        uint32_t e = 0u;
+        if (m >= 1 && dz2 * 0x1p104 < Zx * Zx + Zy * Zy) {
+            const uint32_t mm = (uint32_t)(m - 1);
+            int kk = mm ? __builtin_ctz(mm) : K;
+            kk = kk < K ? kk : K;
+            const int kn = 31 - __builtin_clz((uint32_t)(N - m));
+            const int ki = 31 - __builtin_clz((uint32_t)(max_iter - u));
+            kk = kk < kn ? kk : kn;
+            kk = kk < ki ? kk : ki;
+            for (; kk >= 1; --kk) {
+                const uint32_t ek = bla_offset(n1, kk) + (mm >> kk);
+                const double r = tr[ek];
+                if (dz2 < r * r) { k = kk; e = ek; break; }
+            }
+        }
+        double nx, ny, Zmx, Zmy;
+        int step;
+        if (k > 0) {
+            const double2 a = T.ab[2 * e], b = T.ab[2 * e + 1];
+            nx = (a.x * dzx - a.y * dzy) + (b.x * dcx - b.y * dcy);
+            ny = (a.x * dzy + a.y * dzx) + (b.x * dcy + b.y * dcx);
+            step = 1 << k;
+            ++nbla;
+            m += step;
+            const double2 Zm = orbit[m];
+            Zmx = Zm.x; Zmy = Zm.y;
+        } else {
+            const double tx = (Zx + Zx) + dzx, ty = (Zy + Zy) + dzy;
+            nx = (tx * dzx - ty * dzy) + dcx;
+            ny = (tx * dzy + ty * dzx) + dcy;
+            step = 1;
+            ++nplain;
+            m += 1;
+            Zmx = Znx; Zmy = Zny;
+        }
+        u += step;
+        const double zx = Zmx + nx, zy = Zmy + ny;
+        const double r2 = zx * zx + zy * zy;
+        if (r2 > B2) {
+            esc = u - 1; er2 = r2; live = false;                 /* the last update the step covered */
+        } else if (r2 < nx * nx + ny * ny || m == N) {           /* rebase */
+            dzx = zx; dzy = zy; m = 0;
+            Zx = 0.0; Zy = 0.0; Znx = z1.x; Zny = z1.y;
+        } else {
+            dzx = nx; dzy = ny;
+            Zx = Zmx; Zy = Zmy;
+            if (k > 0) {                                          /* m < N here */
+                const double2 Zn = orbit[m + 1];
+                Znx = Zn.x; Zny = Zn.y;
+            } else {
+                Znx = Znn.x; Zny = Znn.y;
+            }
+        }
+        if (u >= max_iter) live = false;                          /* esc stays max_iter */
+    }
+}
+
+__device__ __forceinline__ const DeepArgs& deep_args(const DeepArgs& A) { return A; }
+__device__ __forceinline__ const DeepArgs& deep_args(const DeepBlaArgs& A) { return A.d; }
+
+/* deep_kernel<DeepArgs>: the plain step; deep_kernel<DeepBlaArgs>: with BLA (deep_orbit_bla, the step counts) */
+template <class ARGS>
+__global__ void __launch_bounds__(kBlockThreads)
+deep_kernel(const ARGS AA)
+{
+    constexpr bool BLA = std::is_same<ARGS, DeepBlaArgs>::value;
+    const DeepArgs& A = deep_args(AA);
     __shared__ LdsBlock S;
     __shared__ double2 log2_lds[kLog2Entries];
     if (threadIdx.x == 0) S.pal = A.pal;
@@ -105,6 +266,7 @@ deep_kernel(const DeepArgs A)
     const bool want_rgb = A.rgba != nullptr;
     const bool want_nu = want_rgb || A.nu != nullptr;
 
+    unsigned long long n_plain = 0ull, n_bla = 0ull, n_upd = 0ull;   /* BLA: this lane's steps and updates */
     WaveQueue q;
     q.init(A.q.heads, A.q.n_blk, (uint32_t)kShardBlock, A.q.run_shift, A.q.run_min, A.q.run_max, lane, A.q.ns_log2);
     q.set_probes(A.q.flags);
@@ -136,7 +298,16 @@ deep_kernel(const DeepArgs A)
                 const double dcy = ((pys - 0.5 * resy) / resy) * zoom;
                 int esc;
                 double r2;
-                deep_orbit(A, inside ? dcx : 0.0, inside ? dcy : 0.0, z1, inside, esc, r2);
+                if constexpr (BLA) {
+                    uint32_t np, nb;
+                    deep_orbit_bla(A, AA.t, inside ? dcx : 0.0, inside ? dcy : 0.0, z1, inside, esc, r2, np, nb);
+                    if (inside) {
+                        n_plain += np; n_bla += nb;
+                        n_upd += (unsigned long long)(esc < A.max_iter ? esc + 1 : A.max_iter);
+                    }
+                } else {
+                    deep_orbit(A, inside ? dcx : 0.0, inside ? dcy : 0.0, z1, inside, esc, r2);
+                }
                 double nu;
                 float rgb[3];
                 shade<double, 0>(A, S, lg, esc, r2, want_nu, want_rgb, nu, rgb);
@@ -153,6 +324,13 @@ deep_kernel(const DeepArgs A)
             if (A.rgba) A.rgba[o] = make_float4(acc[0], acc[1], acc[2], 1.0f);
             if (A.nu) A.nu[o] = nu0;
             if (A.iter) A.iter[o] = it0;
+        }
+    }
+    if constexpr (BLA) {                                          /* updates skipped = updates - plain steps */
+        unsigned long long v[3] = {n_plain, n_bla, n_upd - n_plain};
+        for (int c = 0; c < 3; ++c) {
+            for (int o = kWave / 2; o > 0; o >>= 1) v[c] += __shfl_xor(v[c], o, kWave);
+            if (lane == 0) atomicAdd(AA.t.steps + c, v[c]);
         }
     }
 }

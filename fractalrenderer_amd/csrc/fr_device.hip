@@ -120,7 +120,20 @@ struct fr_ctx {
     char* deep_key_y;
     int32_t deep_key_bits, deep_key_iter;
     float deep_key_bailout;
-    int deep_wg_per_cu;         /* resident workgroups per CU of deep_kernel (0 = not asked yet) */
+    int deep_wg_per_cu;         /* resident workgroups per CU of deep_kernel<DeepArgs> (0 = not asked yet) */
+    uint64_t deep_gen;          /* bumped whenever deep_orbit_dev receives another orbit */
+    /* BLA (FR_FLAG_DEEP_BLA): the table of the cached orbit, and the step counts of the most recent BLA render */
+    double* bla_r;              /* r of every entry (bla_cap) */
+    double2* bla_ab;            /* A, B of every entry (2 bla_cap) */
+    size_t bla_cap;             /* entries */
+    bool bla_valid;             /* the key below describes the table */
+    uint64_t bla_key_gen, bla_key_dcmax;   /* deep_gen of its orbit, bits of dcmax */
+    unsigned long long* bla_steps_dev;     /* the kernel's three counters */
+    unsigned long long* bla_steps_host;    /* pinned: their copy behind the most recent BLA render */
+    bool have_bla_steps;
+    hipEvent_t ev_bla;          /* recorded behind every BLA render (not while capturing): table rebuilds wait for it */
+    bool ev_bla_valid;
+    int deep_bla_wg_per_cu;     /* resident workgroups per CU of deep_kernel<DeepBlaArgs> (0 = not asked yet) */
 };
 
 #define FR_HIP_TRY(expr)                                                               \
@@ -168,6 +181,7 @@ extern "C" int fr_ctx_create(int device_ordinal, fr_ctx** out)
         (e2 = hipEventCreate(&c->ev_begin)) != hipSuccess ||
         (e2 = hipEventCreate(&c->ev_end)) != hipSuccess ||
         (e2 = hipEventCreateWithFlags(&c->ev_order, hipEventDisableTiming)) != hipSuccess ||
+        (e2 = hipEventCreateWithFlags(&c->ev_bla, hipEventDisableTiming)) != hipSuccess ||
         (e2 = hipMalloc((void**)&c->d_ctrl, (kCtrlWords + (size_t)(kFeedbackShards + 2) * kShardStrideWords) * sizeof(uint32_t))) != hipSuccess ||
         (e2 = hipMemset(c->d_ctrl, 0, (kCtrlWords + (size_t)(kFeedbackShards + 2) * kShardStrideWords) * sizeof(uint32_t))) != hipSuccess ||
         (e2 = hipHostMalloc((void**)&c->overflow_host, 64, hipHostMallocMapped)) != hipSuccess ||
@@ -206,6 +220,11 @@ extern "C" void fr_ctx_destroy(fr_ctx* c)
     if (c->deep_orbit_dev) (void)hipFree(c->deep_orbit_dev);
     free(c->deep_key_x);
     free(c->deep_key_y);
+    if (c->bla_r) (void)hipFree(c->bla_r);
+    if (c->bla_ab) (void)hipFree(c->bla_ab);
+    if (c->bla_steps_dev) (void)hipFree(c->bla_steps_dev);
+    if (c->bla_steps_host) (void)hipHostFree(c->bla_steps_host);
+    if (c->ev_bla) (void)hipEventDestroy(c->ev_bla);
     if (c->ev_begin) (void)hipEventDestroy(c->ev_begin);
     if (c->ev_end) (void)hipEventDestroy(c->ev_end);
     if (c->ev_order) (void)hipEventDestroy(c->ev_order);
@@ -832,7 +851,9 @@ static int deep_orbit_for(fr_ctx* c, const fr_params* p, const fr_deep_view* v, 
     FR_HIP_TRY(hipStreamSynchronize(stream));
     FR_HIP_TRY(hipStreamSynchronize(c->stream));
     if (c->have_render && c->last_stream != stream) FR_HIP_TRY(hipStreamSynchronize(c->last_stream));
+    if (c->ev_bla_valid) FR_HIP_TRY(hipEventSynchronize(c->ev_bla));      /* the last BLA render, wherever it went */
     c->deep_valid = false;
+    ++c->deep_gen;
     const size_t need = (size_t)max_iter + 1;
     if (need > c->deep_orbit_cap) {
         if (c->deep_orbit_host) { (void)hipHostFree(c->deep_orbit_host); c->deep_orbit_host = nullptr; }
@@ -855,6 +876,102 @@ static int deep_orbit_for(fr_ctx* c, const fr_params* p, const fr_deep_view* v, 
     c->deep_key_bits = bits; c->deep_key_iter = max_iter; c->deep_key_bailout = p->bailout;
     c->deep_len = len;
     c->deep_valid = true;
+    return FR_OK;
+}
+
+/* BLA: the table of the cached orbit for this frame's dcmax (the whole frame's W, H and zoom), built on `stream` unless
+ * the context holds it.  A rebuild overwrites the buffer in place behind the last BLA render (ev_bla: it may have gone to
+ * another stream); growing it frees the old one, so that waits on the host first. */
+static int deep_bla_table_for(fr_ctx* c, const fr_params* p, uint32_t W, uint32_t H, hipStream_t stream, int* levels)
+{
+    const int32_t N = c->deep_len - 1;
+    const int K = N > 1 ? 31 - __builtin_clz((uint32_t)(N - 1)) : 0;   /* floor(log2(N - 1)) */
+    *levels = K;
+    if (K == 0) return FR_OK;
+    const double a = (double)W / (double)H;
+    const double dcmax = (1.0000001 * (0.5 * p->zoom)) * sqrt(a * a + 1.0);
+    uint64_t dbits;
+    memcpy(&dbits, &dcmax, sizeof(dbits));
+    if (c->bla_valid && c->bla_key_gen == c->deep_gen && c->bla_key_dcmax == dbits) return FR_OK;
+    c->bla_valid = false;
+    const uint32_t n1 = (uint32_t)(N - 1);
+    const size_t need = (size_t)(n1 - (uint32_t)__builtin_popcount(n1));     /* sum over k >= 1 of (N - 1) >> k */
+    if (need > c->bla_cap) {
+        FR_HIP_TRY(hipStreamSynchronize(stream));
+        FR_HIP_TRY(hipStreamSynchronize(c->stream));
+        if (c->ev_bla_valid) FR_HIP_TRY(hipEventSynchronize(c->ev_bla));
+        if (c->bla_r) { (void)hipFree(c->bla_r); c->bla_r = nullptr; }
+        if (c->bla_ab) { (void)hipFree(c->bla_ab); c->bla_ab = nullptr; }
+        c->bla_cap = 0;
+        FR_HIP_TRY(hipMalloc((void**)&c->bla_r, need * sizeof(double)));
+        FR_HIP_TRY(hipMalloc((void**)&c->bla_ab, need * 2 * sizeof(double2)));
+        c->bla_cap = need;
+    } else if (c->ev_bla_valid) {
+        FR_HIP_TRY(hipStreamWaitEvent(stream, c->ev_bla, 0));
+    }
+    for (int k = 1; k <= K; ++k) {
+        const uint32_t cnt = n1 >> k;
+        uint32_t grid = (cnt + kBlockThreads - 1) / kBlockThreads;
+        const uint32_t cap = (uint32_t)c->compute_units * 8u;
+        if (grid > cap) grid = cap;
+        hipLaunchKernelGGL(deep_bla_level_kernel, dim3(grid), dim3(kBlockThreads), 0, stream, c->deep_orbit_dev, N, k, dcmax,
+                           c->bla_r, c->bla_ab);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return fr_set_error(FR_ERR_HIP, "BLA table launch failed: %s", hipGetErrorString(e));
+    }
+    c->bla_key_gen = c->deep_gen;
+    c->bla_key_dcmax = dbits;
+    c->bla_valid = true;
+    return FR_OK;
+}
+
+/* FR_FLAG_DEEP_BLA: the table, then deep_kernel<DeepBlaArgs> on the same queue plan as deep_kernel (its own occupancy), its
+ * counters cleared in front of it and copied to pinned memory behind it */
+static int enqueue_deep_bla(fr_ctx* c, const fr_params* p, uint32_t W, uint32_t H, uint32_t rows_local, const DeepArgs& d,
+                            hipStream_t stream)
+{
+    DeepBlaArgs a;
+    memset(&a, 0, sizeof(a));
+    a.d = d;
+    int levels = 0;
+    const int ts = deep_bla_table_for(c, p, W, H, stream, &levels);
+    if (ts != FR_OK) return ts;
+    a.t.r = c->bla_r; a.t.ab = c->bla_ab; a.t.levels = levels;
+    if (!c->bla_steps_dev) {
+        FR_HIP_TRY(hipMalloc((void**)&c->bla_steps_dev, 3 * sizeof(unsigned long long)));
+        FR_HIP_TRY(hipHostMalloc((void**)&c->bla_steps_host, 3 * sizeof(unsigned long long)));
+    }
+    a.t.steps = c->bla_steps_dev;
+    if (c->deep_bla_wg_per_cu == 0) {
+        int nb = 0;
+        const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, deep_kernel<DeepBlaArgs>, kBlockThreads, 0);
+        if (e != hipSuccess) return fr_set_error(FR_ERR_HIP, "deep BLA occupancy query failed: %s", hipGetErrorString(e));
+        c->deep_bla_wg_per_cu = nb < 1 ? 1 : nb;
+    }
+    uint32_t grid = 0;
+    a.d.q = plan_tile_queue(c, W, rows_local, 3, false, false, (uint32_t)c->deep_bla_wg_per_cu, &grid);
+    a.d.q.heads = stage_heads(c, 0);
+    c->last_grid = grid;
+    c->last_pool_closing = -1;
+
+    FR_HIP_TRY(hipMemsetAsync(c->bla_steps_dev, 0, 3 * sizeof(unsigned long long), stream));
+    FR_HIP_TRY(clear_control_block(c, stream, 1));
+    if (c->timing) FR_HIP_TRY(hipEventRecord(c->ev_begin, stream));
+    hipLaunchKernelGGL(deep_kernel<DeepBlaArgs>, dim3(grid), dim3(kBlockThreads), 0, stream, a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fr_set_error(FR_ERR_HIP, "deep BLA kernel launch failed: %s", hipGetErrorString(e));
+    const int st = finish_render(c, stream, 1);
+    if (st != FR_OK) return st;
+    FR_HIP_TRY(hipMemcpyAsync(c->bla_steps_host, c->bla_steps_dev, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                              stream));
+    c->have_bla_steps = true;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusActive; }
+    c->ev_bla_valid = false;
+    if (cap == hipStreamCaptureStatusNone) {
+        FR_HIP_TRY(hipEventRecord(c->ev_bla, stream));
+        c->ev_bla_valid = true;
+    }
     return FR_OK;
 }
 
@@ -890,9 +1007,10 @@ static int enqueue_deep(fr_ctx* c, const fr_params* p, const fr_deep_view* v, ui
     a.log2_tab = c->log2_tab;
     a.rgba = reinterpret_cast<float4*>(rgba); a.nu = (double*)nu; a.iter = iter;
 
+    if (p->flags & FR_FLAG_DEEP_BLA) return enqueue_deep_bla(c, p, W, H, rows_local, a, stream);
     if (c->deep_wg_per_cu == 0) {
         int nb = 0;
-        const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, deep_kernel, kBlockThreads, 0);
+        const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, deep_kernel<DeepArgs>, kBlockThreads, 0);
         if (e != hipSuccess) return fr_set_error(FR_ERR_HIP, "deep occupancy query failed: %s", hipGetErrorString(e));
         c->deep_wg_per_cu = nb < 1 ? 1 : nb;
     }
@@ -904,7 +1022,7 @@ static int enqueue_deep(fr_ctx* c, const fr_params* p, const fr_deep_view* v, ui
 
     FR_HIP_TRY(clear_control_block(c, stream, 1));
     if (c->timing) FR_HIP_TRY(hipEventRecord(c->ev_begin, stream));
-    hipLaunchKernelGGL(deep_kernel, dim3(grid), dim3(kBlockThreads), 0, stream, a);
+    hipLaunchKernelGGL(deep_kernel<DeepArgs>, dim3(grid), dim3(kBlockThreads), 0, stream, a);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fr_set_error(FR_ERR_HIP, "deep kernel launch failed: %s", hipGetErrorString(e));
     return finish_render(c, stream, 1);
@@ -1591,6 +1709,30 @@ extern "C" int fr_ctx_reserve(fr_ctx* c, const fr_params* p, uint32_t W, uint32_
     FR_HIP_TRY(hipStreamSynchronize(c->stream));
     if (c->render_on_user_stream && c->have_render) FR_HIP_TRY(hipStreamSynchronize(c->last_stream));
     return enqueue_render(c, p, W, H, shard, nullptr, nullptr, nullptr, c->stream, true);
+}
+
+extern "C" int fr_ctx_last_deep_steps(fr_ctx* c, uint64_t out[3])
+{
+    if (!c || !out) return fr_set_error(FR_ERR_INVALID_ARG, "ctx/out is NULL");
+    if (!c->have_bla_steps)
+        return fr_set_error(FR_ERR_UNSUPPORTED, "no fr_render_deep call with FR_FLAG_DEEP_BLA on this context yet");
+    for (int i = 0; i < 3; ++i) out[i] = (uint64_t)c->bla_steps_host[i];
+    return FR_OK;
+}
+
+extern "C" int64_t fr_deep_bla_table(fr_ctx* c, double* r, double* ab, int64_t n)
+{
+    if (!c) return fr_set_error(FR_ERR_INVALID_ARG, "ctx is NULL");
+    if (!c->bla_valid) return 0;
+    const int32_t N = c->deep_len - 1;
+    const uint32_t n1 = (uint32_t)(N - 1);
+    const int64_t have = (int64_t)(n1 - (uint32_t)__builtin_popcount(n1));
+    if (n > have) n = have;
+    FR_HIP_TRY(hipSetDevice(c->device));
+    FR_HIP_TRY(hipDeviceSynchronize());
+    if (n > 0 && r) FR_HIP_TRY(hipMemcpy(r, c->bla_r, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+    if (n > 0 && ab) FR_HIP_TRY(hipMemcpy(ab, c->bla_ab, (size_t)n * 2 * sizeof(double2), hipMemcpyDeviceToHost));
+    return have;
 }
 
 extern "C" int fr_ctx_check(fr_ctx* c)

@@ -32,6 +32,9 @@ int fr_deep_validate(const fr_params* p, const fr_deep_view* v, uint32_t width, 
 /* tests: a centre string in the fixed point of the reference orbit (fr_deep.c): ceil(frac_bits / 64) + 1 little-endian
  * two's-complement limbs into out[0 .. nlimbs); returns that number of limbs or an error */
 int fr_deep_parse_fixed(const char* s, int32_t frac_bits, uint64_t* out, int32_t nlimbs);
+/* tests: the context's BLA table (fr_device.hip), copied to the host after a sync of the context's stream: r[0 .. n) and
+ * ab[0 .. 4n) (A.x, A.y, B.x, B.y per entry), level after level.  Returns the entries it holds, 0 for none. */
+int64_t fr_deep_bla_table(fr_ctx* ctx, double* r, double* ab, int64_t n);
 
 /* the context's own stream (hipStream_t) and device ordinal: fr_node.cpp orders RCCL transfers behind the renders */
 void* fr_ctx_stream_handle(fr_ctx* ctx);

@@ -13,12 +13,19 @@ from __future__ import annotations
 import ctypes as C
 import os
 from dataclasses import dataclass
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import numpy as np
 
 from . import _capi
 from .state import DeepView, FractalState, FractalType, MandelbulbParams, PhoenixParams, Precision
+
+
+class DeepSteps(NamedTuple):
+    """fr_ctx_last_deep_steps: the steps of a deep render with BLA"""
+    plain: int          # plain perturbation steps
+    bla: int            # BLA steps
+    skipped: int        # updates the BLA steps stood for (sum of 2^k)
 
 
 @dataclass(frozen=True)
@@ -117,6 +124,13 @@ class Renderer:
     def last_stages(self) -> int:
         return _capi.check(self._lib.fr_ctx_last_grid(self._ctx)) >> 16
 
+    def last_deep_steps(self) -> DeepSteps:
+        """fr_ctx_last_deep_steps: (plain steps, BLA steps, updates skipped) of the most recent render_deep(bla=True) on
+        this context, over every sub-sample of its pixels (after the caller's own sync for sync=False)."""
+        out = (C.c_uint64 * 3)()
+        _capi.check(self._lib.fr_ctx_last_deep_steps(self._ctx, out))
+        return DeepSteps(int(out[0]), int(out[1]), int(out[2]))
+
     def last_kernel_ms(self) -> float:
         return float(self._lib.fr_ctx_last_kernel_ms(self._ctx))
 
@@ -212,13 +226,16 @@ class Renderer:
 
     def render_deep(self, state: FractalState, width: int, height: int, view: Optional[DeepView] = None, *,
                     post_chain: bool = False, rgba=None, nu=None, iter=None, shard: Optional[Shard] = None,
-                    stream: Optional[int] = None, sync: bool = True) -> None:
+                    stream: Optional[int] = None, sync: bool = True, bla: bool = False) -> None:
         """fr_render_deep / fr_render_deep_async: a Mandelbrot view deeper than double precision, by perturbation around one
         reference orbit computed on the host.  `view` carries the centre as decimal strings (default: "-0.5", "0"); the
         zoom and every other field come from `state` (its double centre is not read).  Always fp64: nu is float64.
         Planes, shard, stream and sync as for render().  A new view computes its orbit on the host first, also with
-        sync=False; a render of the view the context holds is launch-only."""
+        sync=False; a render of the view the context holds is launch-only.  bla=True sets FR_FLAG_DEEP_BLA: iteration
+        skipping by bilinear approximation (the header's rules; last_deep_steps() reports what it skipped)."""
         p = state.to_params(FractalType.Mandelbrot, Precision.F64, post_chain)
+        if bla:
+            p.flags |= _capi.FR_FLAG_DEEP_BLA
         v = (view or DeepView()).to_c()
         rows = shard.rows(height) if shard else height
         self._render_call(self._lib.fr_render_deep, self._lib.fr_render_deep_async, (C.byref(p), C.byref(v)), width, height,

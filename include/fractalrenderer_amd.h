@@ -69,6 +69,8 @@ typedef enum fr_precision {
 #define FR_FLAG_POST_CHAIN   0x1u  /* apply enhance_color -> aces_tonemap -> pow(1/2.2)
                                       (shaders/mandelbrot.comp:233-235, shaders/julia.comp:330-337);
                                       default is the LINEAR colour, before that chain */
+#define FR_FLAG_DEEP_BLA     0x2u  /* fr_render_deep(_async) only: skip iterations by bilinear approximation (see there);
+                                      every other entry point ignores it */
 
 /*
  * fr_params -- the hot-path fields of FractalState (src/fractal_state.h:16-91),
@@ -424,6 +426,7 @@ int fr_render_mandelbulb_async(fr_ctx* ctx, const fr_params* p, const fr_mandelb
  * for the same (i, r2): nu (double) = smooth count of sample (0,0), iter = its i (max_iterations for interior), rgba =
  * palette / interior_style 0-1 / aa average / FR_FLAG_POST_CHAIN exactly as there. */
 #define FR_HAS_DEEP 1
+#define FR_HAS_DEEP_BLA 1         /* FR_FLAG_DEEP_BLA and fr_ctx_last_deep_steps (below fr_render_deep_async) */
 
 typedef struct fr_deep_view {
     const char* center_x;          /* decimal string (see above) */
@@ -461,6 +464,46 @@ int fr_render_deep(fr_ctx* ctx, const fr_params* p, const fr_deep_view* view, ui
  * render -- before it reuses its pinned upload buffer and the device orbit: never launch-only. */
 int fr_render_deep_async(fr_ctx* ctx, const fr_params* p, const fr_deep_view* view, uint32_t width, uint32_t height,
                          const fr_shard* shard, const fr_output* out, void* hip_stream);
+
+/* Bilinear approximation (BLA): iteration skipping for deep views, opt-in per call with FR_FLAG_DEEP_BLA in p->flags.
+ * Only fr_render_deep and fr_render_deep_async read the flag; without it every byte they write is as above.  Near a deep
+ * centre most iterations are the linear part of the step, dz' = 2 Z_m dz + dz^2 + dc with |dz| far below |Z_m|; BLA
+ * replaces 2^k of them with ONE step dz' = A dz + B dc while |dz| is below a validity radius r.  (A, B, r) come from a
+ * table built on the device from the cached reference orbit Z_0 .. Z_N.
+ *
+ * Notation: |w| = sqrt(w.x*w.x + w.y*w.y); complex products are written out as in the step above; every operation is one
+ * fp64 rounding (no contraction).  sqrt is correctly rounded (on gfx950: the OCML expansion of llvm.sqrt.f64, rsq plus
+ * Newton-Raphson with a final fma residual correction).
+ *   - Constants: eps = 2^-53;  dcmax = (1.0000001 * (0.5 * zoom)) * sqrt((W/H)*(W/H) + 1), W/H and zoom of the WHOLE
+ *     frame (never of a shard's rows), so a shard's planes equal the matching rows of the whole frame, byte for byte.
+ *   - Single step at m >= 1 (never stored): A = (Z_m + Z_m), B = (1, 0), r = eps * |Z_m|.
+ *   - Table: levels k = 1 .. K, K = floor(log2(N - 1)) (N <= 2: no table).  Entry j of level k covers the 2^k steps
+ *     from m = 1 + j 2^k and exists iff m + 2^k <= N.  It merges x (level k-1 at m) and y (level k-1 at m + 2^(k-1)):
+ *       A = A_y*A_x,  B = A_y*B_x + B_y,  t = (r_y - |B_x|*dcmax) / |A_x|,  r = (t > 0 ? t : 0) (NaN: 0),
+ *       r = (r < r_x ? r : r_x),  and r = 0 if A or B is not finite.
+ *     So r never exceeds r_x: validity is monotone in k.
+ *   - Stepping: u (the update index) replaces the loop index i.  At each trip of a sample with m >= 1, take the largest
+ *     k >= 1 with (m-1) mod 2^k == 0, m + 2^k <= N, u + 2^k <= max_iterations and dz.x*dz.x + dz.y*dz.y < r*r; then
+ *       dz' = ((A.x dz.x - A.y dz.y) + (B.x dc.x - B.y dc.y), (A.x dz.y + A.y dz.x) + (B.x dc.y + B.y dc.x)),
+ *       m += 2^k, u += 2^k, z = Z_m + dz', r2 = |z|^2 (as the plain step writes it);
+ *     r2 > bailout^2: escaped at u - 1 (the last update the step covered); else the rebase rule of the plain step
+ *     (r2 < |dz'|^2 or m == N).  If no k qualifies, or m == 0, the plain step above, unchanged: it escapes at u and then
+ *     u += 1.  The planes follow from (escape index, r2) exactly as without the flag.
+ * Where it differs from the plain step: a single step drops dz^2 only where |dz| / (2 |Z_m|) < 2^-54, below one rounding of
+ * the kept term; merged steps differ from single ones by rounding order only.  Escapes between the first and the last
+ * update of a BLA step are not looked for.
+ *
+ * Cost: the table has (N - 1) - popcount(N - 1) < N entries of 40 bytes (r 8, A and B 32), on the device, per context,
+ * grown like the orbit buffer (about 0.67 GB at N = 2^24; an allocation failure is FR_ERR_HIP).  It is cached, keyed by the
+ * orbit and the bits of dcmax: a zoom change at a fixed centre rebuilds it (K small launches on the render's stream, no
+ * host work and no upload), a new view computes its orbit first as above.  A rebuild is ordered behind the context's
+ * previous BLA render, whatever stream it went to. */
+
+/* The step counts of the context's most recent fr_render_deep(_async) call made with FR_FLAG_DEEP_BLA, over every
+ * sub-sample of its in-frame pixels: out[0] plain steps, out[1] BLA steps, out[2] updates skipped (the sum of 2^k over
+ * the BLA steps).  A synchronous call has them on return, an asynchronous one once its stream has completed.
+ * FR_ERR_UNSUPPORTED if there is no such call. */
+int fr_ctx_last_deep_steps(fr_ctx* ctx, uint64_t out[3]);
 
 /* ---- frames over the GPUs of a node (BASELINE.json north_star: "tiled across the 8 GPUs of one node as disjoint row
  * bands with a final RCCL gather over xGMI") -----------------------------------------------------------------------------

@@ -69,6 +69,11 @@ class fr_deep_view(C.Structure):
     _fields_ = [("center_x", C.c_char_p), ("center_y", C.c_char_p), ("frac_bits", C.c_int32), ("reserved", C.c_int32)]
 
 
+class fr_deepx_view(C.Structure):
+    _fields_ = [("center_x", C.c_char_p), ("center_y", C.c_char_p), ("zoom", C.c_char_p), ("frac_bits", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 class fr_output(C.Structure):
     _fields_ = [("rgba", C.c_void_p), ("nu", C.c_void_p), ("iter", C.c_void_p), ("memory", C.c_int32), ("layout", C.c_int32)]
 
@@ -130,6 +135,14 @@ SIGNATURES = {
     "fr_render_deep_async": (C.c_int, [C.c_void_p, _P(fr_params), _P(fr_deep_view), C.c_uint32, C.c_uint32, _P(fr_shard),
                                        _P(fr_output), C.c_void_p]),
     "fr_ctx_last_deep_steps": (C.c_int, [C.c_void_p, _P(C.c_uint64)]),
+    "fr_deepx_view_default": (C.c_int, [_P(fr_deepx_view)]),
+    "fr_deepx_zoom": (C.c_int, [C.c_char_p, _P(C.c_double), _P(C.c_int32)]),
+    "fr_deepx_frac_bits": (C.c_int, [C.c_char_p]),
+    "fr_deepx_reference_orbit": (C.c_int, [_P(fr_deepx_view), C.c_int32, C.c_float, C.c_void_p, C.c_void_p, _P(C.c_int32)]),
+    "fr_render_deepx": (C.c_int, [C.c_void_p, _P(fr_params), _P(fr_deepx_view), C.c_uint32, C.c_uint32, _P(fr_shard),
+                                  _P(fr_output)]),
+    "fr_render_deepx_async": (C.c_int, [C.c_void_p, _P(fr_params), _P(fr_deepx_view), C.c_uint32, C.c_uint32, _P(fr_shard),
+                                        _P(fr_output), C.c_void_p]),
     "fr_ctx_create": (C.c_int, [C.c_int, _P(C.c_void_p)]),
     "fr_ctx_destroy": (None, [C.c_void_p]),
     "fr_shard_rows": (C.c_uint32, [_P(fr_shard), C.c_uint32]),

@@ -6,6 +6,11 @@
  * complement -- F fraction bits and at least 64 integer bits.  Centres are limited to |c| < 2^32, so an orbit point that
  * has not escaped (|Z|^2 <= bailout^2 <= 2^32) is below 2^16, the escaping one below 2^33, and the squares of the escape
  * test (< 2^(2F + 66)) fit in the 2L limbs of a product.
+ *
+ * Extended views (fr_render_deepx): the zoom string becomes (zm, ze) through the same parser (its truncated integer, the
+ * inexact flag of its divisions, one rounding to 53 bits), and the orbit is stored as doubles plus a side array of
+ * exponents -- 0 for every point a normal double holds, so those points are the doubles of fr_deep_reference_orbit and the
+ * kernel's plain mode loads 16 bytes per point; only a point below 2^-1022 carries mantissas and a non-zero exponent.
  */
 #include "fr_internal.h"
 
@@ -179,7 +184,10 @@ static uint64_t div_small(uint64_t* a, int n, uint64_t d)      /* a /= d (floor)
  * integer D (value = D 10^net), shifted left by F, then multiplied by 10 (net > 0) or divided by 10 once per digit of
  * the negative exponent; the last division's remainder and a sticky bit of the earlier ones round to nearest, ties to
  * even.  Returns 0, or -1 for a malformed string, -2 for |value| >= 2^32. */
-static int parse_fixed(const char* s, fx_fmt fmt, uint64_t* out)
+/* The scan and the scaling of both parsers: A = floor(|value| 2^F) in kWorkLimbs limbs, *neg the sign, *rem the remainder
+ * of the last division by 10 and *sticky whether an earlier one left any (both 0 when no division took place).  Returns 0;
+ * 1 for a value that is zero or far below 2^-F (A is not set); -1 for a malformed string; -2 for |value| >= 2^32. */
+static int parse_scaled(const char* s, int F, uint64_t* A, int* neg_out, uint64_t* rem, int* sticky_out)
 {
     size_t len = 0;
     while (len <= (size_t)kMaxChars && s[len]) ++len;
@@ -187,8 +195,7 @@ static int parse_fixed(const char* s, fx_fmt fmt, uint64_t* out)
     size_t i = 0;
     int neg = 0;
     if (s[i] == '+' || s[i] == '-') neg = s[i++] == '-';
-    uint64_t A[kWorkLimbs];
-    memset(A, 0, sizeof A);
+    memset(A, 0, sizeof(uint64_t) * kWorkLimbs);
     long ndig = 0, nfrac = 0;
     for (; s[i] >= '0' && s[i] <= '9'; ++i, ++ndig) {
         mul_small(A, kWorkLimbs, 10);
@@ -216,27 +223,40 @@ static int parse_fixed(const char* s, fx_fmt fmt, uint64_t* out)
     }
     if (s[i] != '\0') return -1;
 
-    memset(out, 0, sizeof(uint64_t) * (size_t)fmt.L);
-    if (top_limb(A, kWorkLimbs) < 0) return 0;                   /* zero, whatever its sign */
+    *neg_out = neg; *rem = 0; *sticky_out = 0;
+    if (top_limb(A, kWorkLimbs) < 0) return 1;                   /* zero, whatever its sign */
     const long net = ex - nfrac;
     if (net >= 0) {
         if (net > 10) return -2;                                 /* D >= 1: >= 1e11 > 2^32 */
         for (long k = 0; k < net; ++k) mul_small(A, kWorkLimbs, 10);
         if (top_limb(A, kWorkLimbs) > 0 || A[0] >= (1ull << 32)) return -2;
-        shl_bits(A, kWorkLimbs, fmt.F);
+        shl_bits(A, kWorkLimbs, F);
     } else {
         const long k = -net;
         /* D < 10^4096 and 2^F <= 2^4096 < 10^1234: past 10^5331 the value is below 1/2 and rounds to 0 */
-        if (k > 5400) return 0;
-        shl_bits(A, kWorkLimbs, fmt.F);
+        if (k > 5400) return 1;
+        shl_bits(A, kWorkLimbs, F);
         int n = top_limb(A, kWorkLimbs) + 1, sticky = 0;
         for (long d = 0; d + 1 < k; ++d) {
             sticky |= div_small(A, n, 10) != 0;
             while (n > 1 && A[n - 1] == 0) --n;
         }
-        const uint64_t r = div_small(A, n, 10);                 /* the last digit decides the rounding */
-        if (r > 5 || (r == 5 && (sticky || (A[0] & 1u)))) add_one(A, kWorkLimbs);
+        *rem = div_small(A, n, 10);
+        *sticky_out = sticky;
     }
+    return 0;
+}
+
+static int parse_fixed(const char* s, fx_fmt fmt, uint64_t* out)
+{
+    uint64_t A[kWorkLimbs];
+    int neg = 0, sticky = 0;
+    uint64_t r = 0;
+    const int st = parse_scaled(s, fmt.F, A, &neg, &r, &sticky);
+    if (st == -1) return -1;
+    memset(out, 0, sizeof(uint64_t) * (size_t)fmt.L);
+    if (st != 0) return st == 1 ? 0 : st;
+    if (r > 5 || (r == 5 && (sticky || (A[0] & 1u)))) add_one(A, kWorkLimbs);   /* the last digit decides the rounding */
     const long lim = (long)fmt.F + 32;                           /* |X| < 2^(F + 32) */
     for (int j = 0; j < kWorkLimbs; ++j) {
         const long lo = 64L * j;
@@ -290,8 +310,34 @@ static void floor_shift(uint64_t* r, const uint64_t* P, int s, int negative, fx_
     }
 }
 
+/* Extended storage of one orbit point (fr_deepx_reference_orbit): (mx, my) 2^e.  A point whose larger component is a
+ * normal double keeps e = 0 and the doubles fixed_to_double gives; a smaller one gets e = the exponent that puts its larger
+ * mantissa into [0.5, 1), each mantissa rounded once from the fixed-point value; zero gets FR_DEEPX_ZERO_EXP. */
+static void store_extended(const uint64_t* zr, const uint64_t* zi, fx_fmt fmt, double* mxy, int32_t* e)
+{
+    long top = -1;
+    const uint64_t* z[2] = {zr, zi};
+    for (int k = 0; k < 2; ++k) {
+        uint64_t m[kMaxLimbs];
+        memcpy(m, z[k], sizeof(uint64_t) * (size_t)fmt.L);
+        if (is_negative(m, fmt.L)) negate(m, fmt.L);
+        const int t = top_limb(m, fmt.L);
+        if (t < 0) continue;
+        const long b = 64L * t + 63 - __builtin_clzll(m[t]);
+        if (b > top) top = b;
+    }
+    if (top < 0) { mxy[0] = 0.0; mxy[1] = 0.0; *e = FR_DEEPX_ZERO_EXP; return; }
+    const long b = top - fmt.F;                                   /* 2^b <= larger component < 2^(b + 1) */
+    fx_fmt f = fmt;
+    *e = 0;
+    if (b < -1022) { *e = (int32_t)(b + 1); f.F = fmt.F + (int)(b + 1); }
+    mxy[0] = fixed_to_double(zr, f);
+    mxy[1] = fixed_to_double(zi, f);
+}
+
+/* out_exp NULL: Z_n as doubles; else the extended storage */
 static int orbit_loop(const uint64_t* cr, const uint64_t* ci, fx_fmt fmt, int32_t max_iter, float bailout, double* out_xy,
-                      int32_t* out_len)
+                      int32_t* out_exp, int32_t* out_len)
 {
     const int L = fmt.L, L2 = 2 * fmt.L;
     uint64_t zr[kMaxLimbs], zi[kMaxLimbs], ar[kMaxLimbs], ai[kMaxLimbs], t0[kMaxLimbs], t1[kMaxLimbs];
@@ -310,6 +356,7 @@ static int orbit_loop(const uint64_t* cr, const uint64_t* ci, fx_fmt fmt, int32_
     else T[0] = -ts >= 64 ? 0 : mi >> -ts;
 
     out_xy[0] = 0.0; out_xy[1] = 0.0;
+    if (out_exp) out_exp[0] = FR_DEEPX_ZERO_EXP;
     int32_t n = 0;
     for (;; ++n) {
         if (n == max_iter) break;
@@ -332,8 +379,12 @@ static int orbit_loop(const uint64_t* cr, const uint64_t* ci, fx_fmt fmt, int32_
         add_n(zr, zr, cr, L);
         floor_shift(t0, pr, fmt.F - 1, nr != ni, fmt);
         add_n(zi, t0, ci, L);
-        out_xy[2 * (n + 1)] = fixed_to_double(zr, fmt);
-        out_xy[2 * (n + 1) + 1] = fixed_to_double(zi, fmt);
+        if (out_exp) {
+            store_extended(zr, zi, fmt, out_xy + 2 * (n + 1), out_exp + n + 1);
+        } else {
+            out_xy[2 * (n + 1)] = fixed_to_double(zr, fmt);
+            out_xy[2 * (n + 1) + 1] = fixed_to_double(zi, fmt);
+        }
     }
     *out_len = n + 1;
     return FR_OK;
@@ -454,5 +505,133 @@ int fr_deep_reference_orbit(const fr_deep_view* v, double zoom, int32_t max_iter
     const fx_fmt fmt = {F, (F + 63) / 64 + 1};
     uint64_t cr[kMaxLimbs], ci[kMaxLimbs];
     if ((st = parse_centre(v, fmt, cr, ci)) != FR_OK) return st;
-    return orbit_loop(cr, ci, fmt, max_iter, bailout, out_xy, out_len);
+    return orbit_loop(cr, ci, fmt, max_iter, bailout, out_xy, NULL, out_len);
+}
+
+/* ---- extended-exponent views (fr_render_deepx) ------------------------------------------------------------------------------
+ * The zoom is a decimal string: parsed like a centre into floor(value 2^kZoomBits) with the inexact flag of the divisions,
+ * its top 53 bits rounded to nearest, ties to even -- one rounding from the decimal value. */
+enum { kZoomBits = 3520 };                    /* 1e-1000 2^3520 is about 2^198: far more than 54 bits */
+
+static int zoom_pair(const char* s, double* zm, int32_t* ze)
+{
+    if (!s) return fr_set_error(FR_ERR_INVALID_ARG, "deep zoom string is NULL");
+    uint64_t A[kWorkLimbs];
+    int neg = 0, sticky = 0;
+    uint64_t rem = 0;
+    const int st = parse_scaled(s, kZoomBits, A, &neg, &rem, &sticky);
+    if (st == -1)
+        return fr_set_error(FR_ERR_INVALID_ARG, "deep zoom is not [+-]digits[.digits][(e|E)[+-]digits] of at most 4096 characters");
+    const int t = st == 0 ? top_limb(A, kWorkLimbs) : -1;
+    const long b = t < 0 ? -1 : 64L * t + 63 - __builtin_clzll(A[t]);
+    if (st != 0 || neg || b < 64) return fr_set_error(FR_ERR_INVALID_ARG, "deep zoom outside [1e-1000, 1e3]");
+    uint64_t v = 0;
+    for (int k = 0; k < 53; ++k) v |= (uint64_t)bit_of(A, kWorkLimbs, b - 52 + k) << k;
+    const int half = bit_of(A, kWorkLimbs, b - 53);
+    const int below = any_below(A, kWorkLimbs, b - 53) || rem != 0 || sticky;
+    if (half && (below || (v & 1u))) ++v;
+    long e = b - kZoomBits;
+    if (v == (1ull << 53)) { v >>= 1; ++e; }
+    const double m = ldexp((double)v, -52);
+    /* the range, on the rounded pair: 1e-1000 = 1.0511037747648835 2^-3322, 1e3 = 1.953125 2^9 */
+    if (e < -3322 || (e == -3322 && m < 1.0511037747648835) || e > 9 || (e == 9 && m > 1.953125))
+        return fr_set_error(FR_ERR_INVALID_ARG, "deep zoom outside [1e-1000, 1e3]");
+    *zm = m;
+    *ze = (int32_t)e;
+    return FR_OK;
+}
+
+int fr_deepx_zoom(const char* zoom, double* mant, int32_t* exp2)
+{
+    if (!mant || !exp2) return fr_set_error(FR_ERR_INVALID_ARG, "fr_deepx_zoom: out is NULL");
+    return zoom_pair(zoom, mant, exp2);
+}
+
+static int frac_bits_of_pair(double zm, int32_t ze)
+{
+    if (ze >= -1000) {
+        const double z = ldexp(zm, ze);                          /* exact: a normal double */
+        if (z >= 1e-290) return fr_deep_frac_bits(z);
+    }
+    double want = 64.0 + (double)(int)(-(log10(zm) + (double)ze * log10(2.0)) * 3.32) + 64.0;
+    if (want < 128.0) want = 128.0;
+    if (want > (double)kMaxFracBits) want = kMaxFracBits;
+    const int bits = (int)want;
+    return (bits + 63) / 64 * 64;
+}
+
+int fr_deepx_frac_bits(const char* zoom)
+{
+    double zm;
+    int32_t ze;
+    const int st = zoom_pair(zoom, &zm, &ze);
+    return st != FR_OK ? st : frac_bits_of_pair(zm, ze);
+}
+
+int fr_deepx_view_default(fr_deepx_view* v)
+{
+    if (!v) return fr_set_error(FR_ERR_INVALID_ARG, "deep view is NULL");
+    v->center_x = "-0.5";
+    v->center_y = "0";
+    v->zoom = "3";
+    v->frac_bits = 0;
+    v->reserved = 0;
+    return FR_OK;
+}
+
+int fr_deepx_resolve(const fr_deepx_view* v, double* zm, int32_t* ze, int32_t* frac_bits)
+{
+    if (!v) return fr_set_error(FR_ERR_INVALID_ARG, "deep view is NULL");
+    if (v->reserved != 0) return fr_set_error(FR_ERR_INVALID_ARG, "fr_deepx_view.reserved must be 0");
+    if (v->frac_bits != 0 && (v->frac_bits < 128 || v->frac_bits > kMaxFracBits))
+        return fr_set_error(FR_ERR_INVALID_ARG, "frac_bits %d outside {0} U [128, 4096]", v->frac_bits);
+    if (!v->center_x || !v->center_y) return fr_set_error(FR_ERR_INVALID_ARG, "deep view centre string is NULL");
+    const int st = zoom_pair(v->zoom, zm, ze);
+    if (st != FR_OK) return st;
+    *frac_bits = v->frac_bits ? v->frac_bits : frac_bits_of_pair(*zm, *ze);
+    return FR_OK;
+}
+
+int fr_deepx_validate(const fr_params* p, const fr_deepx_view* v, uint32_t width, uint32_t height)
+{
+    if (!p || !v) return fr_set_error(FR_ERR_INVALID_ARG, "params/deep view is NULL");
+    if (p->fractal_type != FR_FRACTAL_MANDELBROT)
+        return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deepx renders FR_FRACTAL_MANDELBROT only (got %d)", p->fractal_type);
+    if (p->precision != FR_PRECISION_F64)
+        return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deepx needs FR_PRECISION_F64 (got %d)", p->precision);
+    fr_params q = *p;                                            /* the double centre and zoom are not read */
+    q.center_x = 0.0; q.center_y = 0.0; q.zoom = 1.0;
+    int st = fr_params_validate(&q, width, height);
+    if (st != FR_OK) return st;
+    if ((st = check_bailout(p->bailout)) != FR_OK) return st;
+    if (p->orbit_trap_enabled || p->stripe_enabled || p->interior_style == 2)
+        return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deepx: the orbit trap, stripes and interior_style 2 need the whole "
+                            "orbit and are not available");
+    if (p->flags & FR_FLAG_DEEP_BLA)
+        return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deepx: FR_FLAG_DEEP_BLA is not available (the table is fp64)");
+    double zm;
+    int32_t ze, F;
+    if ((st = fr_deepx_resolve(v, &zm, &ze, &F)) != FR_OK) return st;
+    uint64_t cr[kMaxLimbs], ci[kMaxLimbs];
+    const fx_fmt fmt = {F, (F + 63) / 64 + 1};
+    const fr_deep_view c = {v->center_x, v->center_y, F, 0};
+    return parse_centre(&c, fmt, cr, ci);
+}
+
+int fr_deepx_reference_orbit(const fr_deepx_view* v, int32_t max_iter, float bailout, double* out_mant_xy, int32_t* out_exp2,
+                             int32_t* out_len)
+{
+    if (!out_mant_xy || !out_exp2 || !out_len) return fr_set_error(FR_ERR_INVALID_ARG, "fr_deepx_reference_orbit: out is NULL");
+    if (max_iter < 1 || max_iter > (1 << 24))
+        return fr_set_error(FR_ERR_INVALID_ARG, "max_iterations %d outside [1, 2^24]", max_iter);
+    int st;
+    if ((st = check_bailout(bailout)) != FR_OK) return st;
+    double zm;
+    int32_t ze, F;
+    if ((st = fr_deepx_resolve(v, &zm, &ze, &F)) != FR_OK) return st;
+    const fx_fmt fmt = {F, (F + 63) / 64 + 1};
+    uint64_t cr[kMaxLimbs], ci[kMaxLimbs];
+    const fr_deep_view c = {v->center_x, v->center_y, F, 0};
+    if ((st = parse_centre(&c, fmt, cr, ci)) != FR_OK) return st;
+    return orbit_loop(cr, ci, fmt, max_iter, bailout, out_mant_xy, out_exp2, out_len);
 }

@@ -23,6 +23,13 @@
  * table stores, level after level (level k from entry offset bla_offset(N - 1, k)), the radius r of every entry in an
  * array of doubles of its own and (A, B) in an array of double2 pairs: a probe gathers 8 bytes, only the chosen level's
  * 32 bytes of (A, B) are loaded.
+ *
+ * Extended-exponent deltas (fr_render_deepx; the arithmetic is in the header): deep_kernel<DeepXArgs> runs deep_orbit_x as
+ * its per-sample loop.  A lane is in one of two modes.  Plain: deep_orbit's step on the plain doubles of the orbit.
+ * Extended (max(|dz.x|, |dz.y|) < 2^-400): dz is two double mantissas and one int32 exponent, the orbit points come from
+ * the mantissa and exponent arrays, alignment is v_ldexp_f64, and the one normalisation per step takes its exponent with
+ * v_frexp_exp_i32_f64 off max(|x|, |y|); the mode test is an integer compare.  Z_m and Z_{m+1} stay in registers in the
+ * lane's mode and Z_{m+2} is fetched one step ahead from that mode's arrays; a lane that changes mode reloads both.
  */
 #pragma once
 #include "fr_kernels.hip.h"
@@ -234,15 +241,148 @@ __device__ __forceinline__ void deep_orbit_bla(const DeepArgs& A, const BlaTable
     }
 }
 
+/* fr_render_deepx: d.orbit holds the plain doubles P_n, d.zoom is not read */
+struct DeepXArgs {
+    DeepArgs d;
+    const double2* mant;                 /* (mx, my) of Z_0 .. Z_N */
+    const int32_t* exp2;                 /* e of Z_0 .. Z_N */
+    double zm;                           /* zoom = zm 2^ze */
+    int32_t ze;
+};
+
+constexpr int kXZero = FR_DEEPX_ZERO_EXP;
+constexpr int kXThr = -400;              /* extended while the normalised dz.e <= kXThr */
+
+/* norm(x, y, e) of the header */
+__device__ __forceinline__ void x_norm(double& x, double& y, int& e)
+{
+    const double mx = fmax(fabs(x), fabs(y));
+    const int k = __builtin_amdgcn_frexp_exp(mx);
+    x = __builtin_ldexp(x, -k);
+    y = __builtin_ldexp(y, -k);
+    e = mx == 0.0 ? kXZero : e + k;
+}
+
+/* deep_orbit in two modes (the header's EXTENDED and PLAIN steps).  (cx, cy, ec) = dc, normalised. */
+__device__ __forceinline__ void deep_orbit_x(const DeepXArgs& AA, const double cx, const double cy, const int ec, bool live,
+                                             int& esc, double& er2)
+{
+    const DeepArgs& A = AA.d;
+    const double2* __restrict__ orbit = A.orbit;
+    const double2* __restrict__ mant = AA.mant;
+    const int32_t* __restrict__ exp2 = AA.exp2;
+    const int N = A.n_ref, max_iter = A.max_iter;
+    const double B2 = A.B2;
+    /* the plain mode's dc: a component below 2^-1022 is 0 */
+    const double cpx = (cx != 0.0 && __builtin_amdgcn_frexp_exp(cx) + ec > -1022) ? __builtin_ldexp(cx, ec) : 0.0;
+    const double cpy = (cy != 0.0 && __builtin_amdgcn_frexp_exp(cy) + ec > -1022) ? __builtin_ldexp(cy, ec) : 0.0;
+    double dzx = 0.0, dzy = 0.0;                                 /* plain: dz; extended: its mantissas */
+    int ed = kXZero;
+    bool ext = true;
+    double Zx = 0.0, Zy = 0.0;                                   /* Z_m, in the lane's mode */
+    int eZ = kXZero;
+    const double2 z1 = mant[1];
+    double Znx = z1.x, Zny = z1.y;                               /* Z_{m+1} */
+    int eZn = exp2[1];
+    int m = 0;
+    esc = max_iter;
+    er2 = 0.0;
+    for (int i = 0; i < max_iter; ++i) {
+        if (__builtin_amdgcn_ballot_w64(live) == 0ull) break;
+        if (!live) continue;
+        const int mn = m + 2 <= N ? m + 2 : N;                   /* Z_{m+2}, for the next step (m + 1 < N) */
+        double ax, ay;                                           /* the next dz */
+        int ea = 0;
+        bool reb;
+        if (ext) {
+            const double2 Znn = mant[mn];
+            const int eZnn = exp2[mn];
+            const int et = eZ + 1 > ed ? eZ + 1 : ed;
+            const double tx = __builtin_ldexp(Zx, eZ + 1 - et) + __builtin_ldexp(dzx, ed - et);
+            const double ty = __builtin_ldexp(Zy, eZ + 1 - et) + __builtin_ldexp(dzy, ed - et);
+            const double px = tx * dzx - ty * dzy;
+            const double py = tx * dzy + ty * dzx;
+            const int ep = et + ed;
+            const int en = ep > ec ? ep : ec;
+            const double nx = __builtin_ldexp(px, ep - en) + __builtin_ldexp(cx, ec - en);
+            const double ny = __builtin_ldexp(py, ep - en) + __builtin_ldexp(cy, ec - en);
+            ++m;
+            const int ez = eZn > en ? eZn : en;
+            const double zx = __builtin_ldexp(Znx, eZn - ez) + __builtin_ldexp(nx, en - ez);
+            const double zy = __builtin_ldexp(Zny, eZn - ez) + __builtin_ldexp(ny, en - ez);
+            const double r2 = zx * zx + zy * zy;
+            const double r2d = __builtin_ldexp(r2, 2 * ez);
+            if (r2d > B2) {
+                esc = i; er2 = r2d; live = false;
+                continue;
+            }
+            reb = r2 < __builtin_ldexp(nx * nx + ny * ny, 2 * (en - ez)) || m == N;
+            ax = reb ? zx : nx; ay = reb ? zy : ny; ea = reb ? ez : en;
+            x_norm(ax, ay, ea);
+            if (reb) m = 0;
+            if (ea <= kXThr) {                                    /* stays extended */
+                dzx = ax; dzy = ay; ed = ea;
+                if (reb) {
+                    Zx = 0.0; Zy = 0.0; eZ = kXZero; Znx = z1.x; Zny = z1.y; eZn = exp2[1];
+                } else {
+                    Zx = Znx; Zy = Zny; eZ = eZn; Znx = Znn.x; Zny = Znn.y; eZn = eZnn;
+                }
+                continue;
+            }
+            dzx = __builtin_ldexp(ax, ea); dzy = __builtin_ldexp(ay, ea);
+            ext = false;
+        } else {
+            const double2 Znn = orbit[mn];
+            const double tx = (Zx + Zx) + dzx, ty = (Zy + Zy) + dzy;
+            const double nx = (tx * dzx - ty * dzy) + cpx;
+            const double ny = (tx * dzy + ty * dzx) + cpy;
+            ++m;
+            const double zx = Znx + nx, zy = Zny + ny;
+            const double r2 = zx * zx + zy * zy;
+            if (r2 > B2) {
+                esc = i; er2 = r2; live = false;
+                continue;
+            }
+            reb = r2 < nx * nx + ny * ny || m == N;
+            ax = reb ? zx : nx; ay = reb ? zy : ny;
+            if (reb) m = 0;
+            if (!(fmax(fabs(ax), fabs(ay)) < 0x1p-400)) {         /* stays plain */
+                dzx = ax; dzy = ay;
+                if (reb) {
+                    const double2 p1 = orbit[1];
+                    Zx = 0.0; Zy = 0.0; Znx = p1.x; Zny = p1.y;
+                } else {
+                    Zx = Znx; Zy = Zny; Znx = Znn.x; Zny = Znn.y;
+                }
+                continue;
+            }
+            x_norm(ax, ay, ea);
+            dzx = ax; dzy = ay; ed = ea;
+            ext = true;
+        }
+        /* the lane changed its mode: Z_m and Z_{m+1} (m < N here) from the new mode's arrays */
+        if (ext) {
+            const double2 a = mant[m], b = mant[m + 1];
+            Zx = a.x; Zy = a.y; eZ = exp2[m]; Znx = b.x; Zny = b.y; eZn = exp2[m + 1];
+        } else {
+            const double2 a = orbit[m], b = orbit[m + 1];
+            Zx = a.x; Zy = a.y; Znx = b.x; Zny = b.y;
+        }
+    }
+}
+
 __device__ __forceinline__ const DeepArgs& deep_args(const DeepArgs& A) { return A; }
+__device__ __forceinline__ const DeepArgs& deep_args(const DeepXArgs& A) { return A.d; }
 __device__ __forceinline__ const DeepArgs& deep_args(const DeepBlaArgs& A) { return A.d; }
 
-/* deep_kernel<DeepArgs>: the plain step; deep_kernel<DeepBlaArgs>: with BLA (deep_orbit_bla, the step counts) */
+/* deep_kernel<DeepArgs>: the plain step; deep_kernel<DeepBlaArgs>: with BLA (deep_orbit_bla, the step counts);
+ * deep_kernel<DeepXArgs>: extended-exponent deltas (deep_orbit_x) */
 template <class ARGS>
 __global__ void __launch_bounds__(kBlockThreads)
 deep_kernel(const ARGS AA)
 {
     constexpr bool BLA = std::is_same<ARGS, DeepBlaArgs>::value;
+    constexpr bool X = std::is_same<ARGS, DeepXArgs>::value;
     const DeepArgs& A = deep_args(AA);
     __shared__ LdsBlock S;
     __shared__ double2 log2_lds[kLog2Entries];
@@ -298,7 +438,13 @@ deep_kernel(const ARGS AA)
                 const double dcy = ((pys - 0.5 * resy) / resy) * zoom;
                 int esc;
                 double r2;
-                if constexpr (BLA) {
+                if constexpr (X) {
+                    double cx = ((pxs - 0.5 * resx) / resy) * AA.zm, cy = ((pys - 0.5 * resy) / resy) * AA.zm;
+                    int ec = AA.ze;
+                    if (!inside) { cx = 0.0; cy = 0.0; }
+                    x_norm(cx, cy, ec);
+                    deep_orbit_x(AA, cx, cy, ec, inside, esc, r2);
+                } else if constexpr (BLA) {
                     uint32_t np, nb;
                     deep_orbit_bla(A, AA.t, inside ? dcx : 0.0, inside ? dcy : 0.0, z1, inside, esc, r2, np, nb);
                     if (inside) {

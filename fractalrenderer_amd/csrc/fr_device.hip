@@ -134,6 +134,18 @@ struct fr_ctx {
     hipEvent_t ev_bla;          /* recorded behind every BLA render (not while capturing): table rebuilds wait for it */
     bool ev_bla_valid;
     int deep_bla_wg_per_cu;     /* resident workgroups per CU of deep_kernel<DeepBlaArgs> (0 = not asked yet) */
+    /* extended views (fr_render_deepx): their own orbit cache, in the extended storage.  One pinned and one device block
+     * of deepx_cap points each: the plain doubles, the mantissa pairs, the exponents, in this order. */
+    char* deepx_host;
+    char* deepx_dev;
+    size_t deepx_cap;
+    int32_t deepx_len;          /* N + 1 */
+    bool deepx_valid;           /* the key below describes deepx_dev */
+    char* deepx_key_x;
+    char* deepx_key_y;
+    int32_t deepx_key_bits, deepx_key_iter;
+    float deepx_key_bailout;
+    int deepx_wg_per_cu;        /* resident workgroups per CU of deep_kernel<DeepXArgs> (0 = not asked yet) */
 };
 
 #define FR_HIP_TRY(expr)                                                               \
@@ -220,6 +232,10 @@ extern "C" void fr_ctx_destroy(fr_ctx* c)
     if (c->deep_orbit_dev) (void)hipFree(c->deep_orbit_dev);
     free(c->deep_key_x);
     free(c->deep_key_y);
+    if (c->deepx_host) (void)hipHostFree(c->deepx_host);
+    if (c->deepx_dev) (void)hipFree(c->deepx_dev);
+    free(c->deepx_key_x);
+    free(c->deepx_key_y);
     if (c->bla_r) (void)hipFree(c->bla_r);
     if (c->bla_ab) (void)hipFree(c->bla_ab);
     if (c->bla_steps_dev) (void)hipFree(c->bla_steps_dev);
@@ -1028,6 +1044,115 @@ static int enqueue_deep(fr_ctx* c, const fr_params* p, const fr_deep_view* v, ui
     return finish_render(c, stream, 1);
 }
 
+/* ---- extended views (fr_render_deepx) -------------------------------------------------------------------------------
+ * enqueue_deep with the orbit in the extended storage: the mantissa pairs and exponents of fr_deepx_reference_orbit, and
+ * the plain doubles ldexp(mantissa, exponent) formed here on the host, in one upload. */
+static int deepx_orbit_for(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, int32_t bits, hipStream_t stream)
+{
+    const int32_t max_iter = p->max_iterations;
+    if (c->deepx_valid && c->deepx_key_bits == bits && c->deepx_key_iter == max_iter &&
+        memcmp(&c->deepx_key_bailout, &p->bailout, sizeof(float)) == 0 && strcmp(c->deepx_key_x, v->center_x) == 0 &&
+        strcmp(c->deepx_key_y, v->center_y) == 0)
+        return FR_OK;
+    /* as deep_orbit_for: the pinned block may still feed an upload, the device block an earlier render */
+    FR_HIP_TRY(hipStreamSynchronize(stream));
+    FR_HIP_TRY(hipStreamSynchronize(c->stream));
+    if (c->have_render && c->last_stream != stream) FR_HIP_TRY(hipStreamSynchronize(c->last_stream));
+    c->deepx_valid = false;
+    const size_t need = (size_t)max_iter + 1;
+    const size_t point_bytes = 2 * sizeof(double2) + sizeof(int32_t);
+    if (need > c->deepx_cap) {
+        if (c->deepx_host) { (void)hipHostFree(c->deepx_host); c->deepx_host = nullptr; }
+        if (c->deepx_dev) { (void)hipFree(c->deepx_dev); c->deepx_dev = nullptr; }
+        c->deepx_cap = 0;
+        FR_HIP_TRY(hipHostMalloc((void**)&c->deepx_host, need * point_bytes));
+        FR_HIP_TRY(hipMalloc((void**)&c->deepx_dev, need * point_bytes));
+        c->deepx_cap = need;
+    }
+    const size_t cap = c->deepx_cap;
+    double* plain = (double*)c->deepx_host;
+    double* mant = plain + 2 * cap;
+    int32_t* exp2 = (int32_t*)(mant + 2 * cap);
+    int32_t len = 0;
+    fr_deepx_view w = *v;
+    w.frac_bits = bits;
+    const int st = fr_deepx_reference_orbit(&w, max_iter, p->bailout, mant, exp2, &len);
+    if (st != FR_OK) return st;
+    for (int32_t n = 0; n < len; ++n) {
+        plain[2 * n] = ldexp(mant[2 * n], exp2[n]);
+        plain[2 * n + 1] = ldexp(mant[2 * n + 1], exp2[n]);
+    }
+    FR_HIP_TRY(hipMemcpyAsync(c->deepx_dev, c->deepx_host, cap * point_bytes, hipMemcpyHostToDevice, stream));
+    FR_HIP_TRY(hipStreamSynchronize(stream));     /* a later render of this view may go to another stream */
+    free(c->deepx_key_x); free(c->deepx_key_y);
+    c->deepx_key_x = copy_string(v->center_x);
+    c->deepx_key_y = copy_string(v->center_y);
+    if (!c->deepx_key_x || !c->deepx_key_y) return fr_set_error(FR_ERR_NOMEM, "out of host memory");
+    c->deepx_key_bits = bits; c->deepx_key_iter = max_iter; c->deepx_key_bailout = p->bailout;
+    c->deepx_len = len;
+    c->deepx_valid = true;
+    return FR_OK;
+}
+
+static int enqueue_deepx(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, uint32_t W, uint32_t H, const fr_shard* shard,
+                         float* rgba, void* nu, int32_t* iter, hipStream_t stream, bool out_frame)
+{
+    const int ov = check_overflow(c);            /* of an earlier asynchronous render nobody has asked about */
+    if (ov != FR_OK) return ov;
+    fr_shard norm;
+    uint32_t rows_local = 0;
+    const int sh = normalise_shard(shard, H, &norm, &rows_local);
+    if (sh != FR_OK || rows_local == 0) return sh;
+    DeepXArgs x;
+    memset(&x, 0, sizeof(x));
+    int32_t bits = 0;
+    const int rs = fr_deepx_resolve(v, &x.zm, &x.ze, &bits);
+    if (rs != FR_OK) return rs;
+    const int os = deepx_orbit_for(c, p, v, bits, stream);
+    if (os != FR_OK) return os;
+
+    DeepArgs& a = x.d;
+    const size_t cap = c->deepx_cap;
+    a.orbit = reinterpret_cast<const double2*>(c->deepx_dev);
+    x.mant = a.orbit + cap;
+    x.exp2 = reinterpret_cast<const int32_t*>(x.mant + cap);
+    a.n_ref = c->deepx_len - 1;
+    a.max_iter = p->max_iterations; a.aa = p->antialiasing_samples;
+    a.B2 = (double)p->bailout * (double)p->bailout;
+    a.W = (int32_t)W; a.H = (int32_t)H; a.rows_local = (int32_t)rows_local;
+    a.part = (int32_t)norm.part; a.nparts = (int32_t)norm.nparts; a.rows_per_strip = (int32_t)norm.rows_per_strip;
+    a.out_frame = out_frame ? 1 : 0;
+    a.flags = p->flags;
+    a.interior_style = p->interior_style;
+    a.lib_log = !(p->bailout > 1.0f);            /* as fill_params */
+    a.inv_max_iter = 1.0 / (double)p->max_iterations;
+    a.inv_log2_bailout = 1.0 / log2((double)p->bailout);
+    a.color_scale_d = (double)p->color_scale; a.color_offset_d = (double)p->color_offset;
+    a.brightness = p->color_brightness; a.saturation = p->color_saturation; a.contrast = p->color_contrast;
+    fr_palette_table_build(0, p->palette_mode, &a.pal);
+    a.log2_tab = c->log2_tab;
+    a.rgba = reinterpret_cast<float4*>(rgba); a.nu = (double*)nu; a.iter = iter;
+
+    if (c->deepx_wg_per_cu == 0) {
+        int nb = 0;
+        const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, deep_kernel<DeepXArgs>, kBlockThreads, 0);
+        if (e != hipSuccess) return fr_set_error(FR_ERR_HIP, "deepx occupancy query failed: %s", hipGetErrorString(e));
+        c->deepx_wg_per_cu = nb < 1 ? 1 : nb;
+    }
+    uint32_t grid = 0;
+    a.q = plan_tile_queue(c, W, rows_local, 3, false, false, (uint32_t)c->deepx_wg_per_cu, &grid);
+    a.q.heads = stage_heads(c, 0);
+    c->last_grid = grid;
+    c->last_pool_closing = -1;
+
+    FR_HIP_TRY(clear_control_block(c, stream, 1));
+    if (c->timing) FR_HIP_TRY(hipEventRecord(c->ev_begin, stream));
+    hipLaunchKernelGGL(deep_kernel<DeepXArgs>, dim3(grid), dim3(kBlockThreads), 0, stream, x);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fr_set_error(FR_ERR_HIP, "deepx kernel launch failed: %s", hipGetErrorString(e));
+    return finish_render(c, stream, 1);
+}
+
 /* the parameter part of the kernel argument block (everything that does not depend on the frame geometry) */
 static void fill_params(LaunchArgs& a, const fr_params* p)
 {
@@ -1831,6 +1956,32 @@ extern "C" int fr_render_deep(fr_ctx* c, const fr_params* p, const fr_deep_view*
     if (st != FR_OK) return st;
     return render_sync(c, p, W, H, shard, out, [&](auto sh, auto rgba, auto nu, auto iter, auto s, bool out_frame) {
         return enqueue_deep(c, p, v, W, H, sh, rgba, nu, iter, s, out_frame); });
+}
+
+static int check_deepx(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, uint32_t W, uint32_t H, const fr_output* out)
+{
+    if (!c) return fr_set_error(FR_ERR_INVALID_ARG, "ctx is NULL");
+    if (!p || !v || !out) return fr_set_error(FR_ERR_INVALID_ARG, "params/deep view/out is NULL");
+    return fr_deepx_validate(p, v, W, H);
+}
+
+extern "C" int fr_render_deepx_async(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, uint32_t W, uint32_t H,
+                                     const fr_shard* shard, const fr_output* out, void* hip_stream)
+{
+    const int st = check_deepx(c, p, v, W, H, out);
+    if (st != FR_OK) return st;
+    return render_async("fr_render_deepx_async", c, H, shard, out, hip_stream,
+                        [&](auto sh, auto rgba, auto nu, auto iter, auto s, bool out_frame) {
+                            return enqueue_deepx(c, p, v, W, H, sh, rgba, nu, iter, s, out_frame); });
+}
+
+extern "C" int fr_render_deepx(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, uint32_t W, uint32_t H,
+                               const fr_shard* shard, const fr_output* out)
+{
+    const int st = check_deepx(c, p, v, W, H, out);
+    if (st != FR_OK) return st;
+    return render_sync(c, p, W, H, shard, out, [&](auto sh, auto rgba, auto nu, auto iter, auto s, bool out_frame) {
+        return enqueue_deepx(c, p, v, W, H, sh, rgba, nu, iter, s, out_frame); });
 }
 
 /* ---- 8-bit export ------------------------------------------------------------------------------ */

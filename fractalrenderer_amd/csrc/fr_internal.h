@@ -29,6 +29,9 @@ int fr_phoenix_validate(const fr_params* p, const fr_phoenix_params* ph, uint32_
 int fr_mandelbulb_validate(const fr_params* p, const fr_mandelbulb_params* mb, uint32_t width, uint32_t height);
 /* the validation of fr_render_deep (fr_deep.c), the centre strings parsed included */
 int fr_deep_validate(const fr_params* p, const fr_deep_view* v, uint32_t width, uint32_t height);
+/* the validation of fr_render_deepx (fr_deep.c), and its view resolved: the zoom pair and the fraction bits */
+int fr_deepx_validate(const fr_params* p, const fr_deepx_view* v, uint32_t width, uint32_t height);
+int fr_deepx_resolve(const fr_deepx_view* v, double* zm, int32_t* ze, int32_t* frac_bits);
 /* tests: a centre string in the fixed point of the reference orbit (fr_deep.c): ceil(frac_bits / 64) + 1 little-endian
  * two's-complement limbs into out[0 .. nlimbs); returns that number of limbs or an error */
 int fr_deep_parse_fixed(const char* s, int32_t frac_bits, uint64_t* out, int32_t nlimbs);

@@ -232,12 +232,19 @@ class Renderer:
         zoom and every other field come from `state` (its double centre is not read).  Always fp64: nu is float64.
         Planes, shard, stream and sync as for render().  A new view computes its orbit on the host first, also with
         sync=False; a render of the view the context holds is launch-only.  bla=True sets FR_FLAG_DEEP_BLA: iteration
-        skipping by bilinear approximation (the header's rules; last_deep_steps() reports what it skipped)."""
+        skipping by bilinear approximation (the header's rules; last_deep_steps() reports what it skipped).
+        A view with a zoom string (DeepView(..., zoom="1e-400")) goes to fr_render_deepx / fr_render_deepx_async:
+        extended-exponent deltas, zooms down to 1e-1000, state.zoom not read, no BLA."""
         p = state.to_params(FractalType.Mandelbrot, Precision.F64, post_chain)
         if bla:
             p.flags |= _capi.FR_FLAG_DEEP_BLA
-        v = (view or DeepView()).to_c()
         rows = shard.rows(height) if shard else height
+        if view is not None and view.zoom is not None:
+            vx = view.to_cx()
+            self._render_call(self._lib.fr_render_deepx, self._lib.fr_render_deepx_async, (C.byref(p), C.byref(vx)), width,
+                              height, Precision.F64, rows, rgba, nu, iter, shard, stream, sync)
+            return
+        v = (view or DeepView()).to_c()
         self._render_call(self._lib.fr_render_deep, self._lib.fr_render_deep_async, (C.byref(p), C.byref(v)), width, height,
                           Precision.F64, rows, rgba, nu, iter, shard, stream, sync)
 

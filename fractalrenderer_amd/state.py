@@ -190,14 +190,21 @@ def pack_push_constants_mandelbulb(state: FractalState, mandelbulb: MandelbulbPa
 class DeepView:
     """The centre of a view deeper than double precision (fr_deep_view): decimal strings, [+-]digits[.digits][(e|E)[+-]digits]
     of at most 4096 characters, or Decimals (written out with str()).  frac_bits: fraction bits of the host's fixed-point
-    reference orbit, 0 = automatic (deep_frac_bits(zoom)).  The zoom is FractalState.zoom; its centre is not read."""
+    reference orbit, 0 = automatic (deep_frac_bits(zoom)).  The zoom is FractalState.zoom; its centre is not read.
+    zoom: None, or the view height as a decimal string (or Decimal) in [1e-1000, 1e3] -- then the view is an fr_deepx_view,
+    rendered with extended-exponent deltas (fr_render_deepx), and FractalState.zoom is not read either."""
     center_x: object = "-0.5"
     center_y: object = "0"
     frac_bits: int = 0
+    zoom: object = None
 
     def to_c(self) -> _capi.fr_deep_view:
         return _capi.fr_deep_view(str(self.center_x).encode("ascii"), str(self.center_y).encode("ascii"),
                                   int(self.frac_bits), 0)
+
+    def to_cx(self) -> _capi.fr_deepx_view:
+        return _capi.fr_deepx_view(str(self.center_x).encode("ascii"), str(self.center_y).encode("ascii"),
+                                   str(self.zoom).encode("ascii"), int(self.frac_bits), 0)
 
 
 def deep_frac_bits(zoom: float) -> int:
@@ -215,3 +222,29 @@ def deep_reference_orbit(view: DeepView, zoom: float, max_iterations: int, bailo
     _capi.check(_capi.lib().fr_deep_reference_orbit(_capi.C.byref(v), float(zoom), int(max_iterations), _F32(bailout),
                                                     buf.ctypes.data, _capi.C.byref(n)))
     return buf[:n.value].copy()
+
+
+def deepx_zoom(zoom) -> tuple:
+    """fr_deepx_zoom: a decimal zoom string as (zm, ze), zoom = zm 2^ze, zm in [1, 2) correctly rounded."""
+    zm, ze = _capi.C.c_double(), _capi.C.c_int32()
+    _capi.check(_capi.lib().fr_deepx_zoom(str(zoom).encode("ascii"), _capi.C.byref(zm), _capi.C.byref(ze)))
+    return zm.value, ze.value
+
+
+def deepx_frac_bits(zoom) -> int:
+    """fr_deepx_frac_bits: the automatic fraction bits of an extended view at this zoom (a decimal string)."""
+    n = int(_capi.lib().fr_deepx_frac_bits(str(zoom).encode("ascii")))
+    _capi.check(min(n, 0))
+    return n
+
+
+def deepx_reference_orbit(view: DeepView, max_iterations: int, bailout: float = 4.0) -> tuple:
+    """fr_deepx_reference_orbit: Z_0 .. Z_N of an extended view (view.zoom set) as ((N + 1, 2) float64 mantissas,
+    (N + 1,) int32 exponents): point n is mantissas[n] * 2^exponents[n] (host only)."""
+    mant = np.empty((int(max_iterations) + 1, 2), np.float64)
+    exp2 = np.empty(int(max_iterations) + 1, np.int32)
+    n = _capi.C.c_int32()
+    v = view.to_cx()
+    _capi.check(_capi.lib().fr_deepx_reference_orbit(_capi.C.byref(v), int(max_iterations), _F32(bailout), mant.ctypes.data,
+                                                     exp2.ctypes.data, _capi.C.byref(n)))
+    return mant[:n.value].copy(), exp2[:n.value].copy()

@@ -403,7 +403,8 @@ int fr_render_mandelbulb_async(fr_ctx* ctx, const fr_params* p, const fr_mandelb
  *   - every sample iterates its fp64 delta dz from it, dc being its offset from the centre, and is REBASED to the start
  *     of the orbit (dz = z, m = 0) whenever |z| < |dz| or the orbit ends (Zhuoran's rebasing): no glitch detection and
  *     no second reference are needed.
- * Deltas are fp64, so the zoom reaches 1e-290.
+ * Deltas are fp64, so the zoom reaches 1e-290; fr_render_deepx (below, FR_HAS_DEEPX) carries them with an extended exponent
+ * and reaches 1e-1000.
  *
  * The view: centre_x / centre_y are decimal strings, [+-]digits[.digits][(e|E)[+-]digits], at most 4096 characters,
  * |centre| < 2^32; p->center_x and p->center_y are ignored.  The zoom is p->zoom (the view height, as everywhere), finite
@@ -504,6 +505,93 @@ int fr_render_deep_async(fr_ctx* ctx, const fr_params* p, const fr_deep_view* vi
  * the BLA steps).  A synchronous call has them on return, an asynchronous one once its stream has completed.
  * FR_ERR_UNSUPPORTED if there is no such call. */
 int fr_ctx_last_deep_steps(fr_ctx* ctx, uint64_t out[3]);
+
+/* ---- deep views below 1e-290: extended-exponent deltas ----------------------------------------------------------------
+ * fr_render_deep stops where a double can no longer hold the zoom, a sample's dc and dz, or an orbit point that passes
+ * close to 0.  These entry points take the ZOOM as a decimal string too and carry every delta as two double mantissas
+ * with one shared int32 binary exponent while it is small; nothing about fr_render_deep changes.
+ *
+ * The view: centre strings as fr_deep_view; zoom = the view height as a decimal string of the same grammar, read as
+ * zm 2^ze, zm a double in [1, 2) holding the decimal value correctly rounded to 53 significant bits (ties to even), ze an
+ * int32 (fr_deepx_zoom returns the pair).  1e-1000 <= zoom <= 1e3, compared on the rounded pair.  p->zoom, p->center_x and
+ * p->center_y are ignored.  FR_ERR_UNSUPPORTED as for fr_render_deep, and for FR_FLAG_DEEP_BLA (out of scope, below);
+ * FR_ERR_INVALID_ARG for a malformed or out-of-range zoom, and otherwise as there.
+ *
+ * Reference orbit: Z_0 .. Z_N exactly as for fr_render_deep (same recurrence, same escape test, F = frac_bits or
+ * fr_deepx_frac_bits(zoom)); what differs is the storage.  Point n is (mx, my) 2^e: two doubles and one int32, in two
+ * arrays (mantissa pairs, exponents).  A point whose larger component is at least 2^-1022 has e = 0 and (mx, my) = the
+ * doubles of fr_deep_reference_orbit; a smaller one has e = floor(log2(larger component)) + 1, so that its larger mantissa
+ * lies in [0.5, 1), each mantissa rounded once to nearest from the fixed-point value; (0, 0) has e = FR_DEEPX_ZERO_EXP.  The
+ * device also keeps P_n = (ldexp(mx, e), ldexp(my, e)) as plain doubles (rounded to nearest; for e = 0 the same doubles):
+ * the plain mode below loads 16 bytes per point as fr_render_deep does, the extended mode 20.
+ *
+ * Extended numbers: X = (x, y, e) stands for (x, y) 2^e, x and y doubles.  Every mantissa operation below is one IEEE
+ * fp64 operation, rounded to nearest (no contraction; gradual underflow of a mantissa as IEEE has it), every exponent
+ * operation is exact int32 arithmetic, ldexp(x, n) = x 2^n rounded to nearest (exact unless the result is subnormal).
+ *   norm(x, y, e):  k = frexp exponent of max(|x|, |y|) (that maximum in [2^(k-1), 2^k); 0 for 0);
+ *                   (ldexp(x, -k), ldexp(y, -k), e + k), and e = FR_DEEPX_ZERO_EXP when x = y = 0.
+ *   A (+) B:        e = max(A.e, B.e);  (ldexp(A.x, A.e - e) + ldexp(B.x, B.e - e), same in y, e)   -- not normalised
+ * Per sample: fx = ((x + sx/aa) - 0.5 W) / H, fy = ((y + sy/aa) - 0.5 H) / H as fr_render_deep forms them;
+ *   dc = norm(fx * zm, fy * zm, ze): one rounding per component, then an exact exponent (for a zoom that is a normal double
+ *   this is the dc of fr_render_deep, bit for bit);  dcp (the plain mode's dc) = (ldexp(dc.x, dc.e), ldexp(dc.y, dc.e)) with
+ *   a component whose value is below 2^-1022 taken as 0;  dz = (0, 0, FR_DEEPX_ZERO_EXP), m = 0, mode = extended.
+ * Then for i = 0 .. max_iter-1 one step in the sample's mode.
+ *   EXTENDED (dz an extended number, normalised; Z_m, Z_{m+1} in the extended storage):
+ *     t = (Z_m.x, Z_m.y, Z_m.e + 1) (+) dz;
+ *     p = (t.x dz.x - t.y dz.y, t.x dz.y + t.y dz.x, t.e + dz.e);   n = p (+) dc;   m += 1;   z = Z_m (+) n;
+ *     r2 = z.x z.x + z.y z.y;   escaped at i if ldexp(r2, 2 z.e) > bailout^2 (that double is the sample's r2);
+ *     else rebase if r2 < ldexp(n.x n.x + n.y n.y, 2 (n.e - z.e)) or m == N   (z.e >= n.e always);
+ *     dz = norm(rebase ? z : n), m = 0 on a rebase.
+ *     If now dz.e > -400 -- max(|dz.x|, |dz.y|) 2^dz.e >= 2^-400 -- the sample turns PLAIN with
+ *     dz = (ldexp(dz.x, dz.e), ldexp(dz.y, dz.e)).
+ *   PLAIN (dz two doubles): the step of fr_render_deep, operation for operation, on P_m, P_{m+1} and dcp.  If afterwards
+ *     max(|dz.x|, |dz.y|) < 2^-400 the sample turns EXTENDED with dz = norm(dz.x, dz.y, 0).
+ * The threshold 2^-400: the plain step multiplies two deltas (at m = 0, t = dz), so its products stay above 2^-802, far
+ * inside the normal range, and nothing a double would flush enters a plain step; a component of dc below 2^-1022 is below
+ * 2^-220 of those products, far under half an ulp of the dz' it is added to, so taking it as 0 loses nothing; an orbit
+ * point below 2^-1022 read as P_m is likewise below half an ulp of the dz of at least 2^-401 it meets.  An extended step on
+ * operands that a double holds performs the same roundings as the plain step (the exponents only carry the scale), so a
+ * view whose dc is at least 2^-400 -- every zoom down to about 1e-117 -- leaves the extended mode on its first step and
+ * gets the bytes of fr_render_deep.  Planes, shards, layouts, memory kinds, options, fr_ctx_last_kernel_ms / _grid and
+ * the asynchronous form's rules are those of fr_render_deep; the context keeps the most recent extended orbit on the device
+ * next to (and independent of) fr_render_deep's, keyed by (centre strings, F, max_iterations, bailout).
+ *
+ * Out of scope: BLA for extended views (A grows like 1 / zoom: the table and deep_bla_level_kernel need extended
+ * exponents too), fr_node, .franim and zoom paths for deep views, and depths beyond 1e-1000 (the 4096-bit cap of F). */
+#define FR_HAS_DEEPX 1
+#define FR_DEEPX_ZERO_EXP (-(1 << 28))   /* the exponent of a zero in the extended storage */
+
+typedef struct fr_deepx_view {
+    const char* center_x;          /* as fr_deep_view */
+    const char* center_y;
+    const char* zoom;              /* the view height as a decimal string, same grammar as the centre, > 0 */
+    int32_t     frac_bits;         /* 0 = automatic (fr_deepx_frac_bits(zoom)) */
+    int32_t     reserved;          /* must be 0 */
+} fr_deepx_view;                   /* 32 bytes on LP64 */
+
+/* "-0.5", "0", "3", 0, 0 */
+int fr_deepx_view_default(fr_deepx_view* v);
+
+/* The zoom string as *mant 2^*exp2, *mant in [1, 2) (above).  FR_ERR_INVALID_ARG for a malformed string or a value
+ * outside [1e-1000, 1e3]. */
+int fr_deepx_zoom(const char* zoom, double* mant, int32_t* exp2);
+
+/* The automatic fraction bits: fr_deep_frac_bits((double)zoom) for a zoom that is a double >= 1e-290, else the same rule on
+ * -log10(zoom) = -(log10(zm) + ze * log10(2)): 3456 at 1e-1000.  < 0: the error of fr_deepx_zoom. */
+int fr_deepx_frac_bits(const char* zoom);
+
+/* The reference orbit in the extended storage, on the host: out_mant_xy receives 2 (max_iter + 1) doubles at most,
+ * out_exp2 max_iter + 1 exponents; *out_len = N + 1.  Cost as fr_deep_reference_orbit. */
+int fr_deepx_reference_orbit(const fr_deepx_view* v, int32_t max_iter, float bailout, double* out_mant_xy, int32_t* out_exp2,
+                             int32_t* out_len);
+
+/* fr_render_deep's contract (planes, memory kinds, FR_LAYOUT_FRAME, shards, options, the orbit cache) for an extended view */
+int fr_render_deepx(fr_ctx* ctx, const fr_params* p, const fr_deepx_view* view, uint32_t width, uint32_t height,
+                    const fr_shard* shard, const fr_output* out);
+
+/* fr_render_deep_async's contract: a render of a new view computes its orbit on the host first and is never launch-only */
+int fr_render_deepx_async(fr_ctx* ctx, const fr_params* p, const fr_deepx_view* view, uint32_t width, uint32_t height,
+                          const fr_shard* shard, const fr_output* out, void* hip_stream);
 
 /* ---- frames over the GPUs of a node (BASELINE.json north_star: "tiled across the 8 GPUs of one node as disjoint row
  * bands with a final RCCL gather over xGMI") -----------------------------------------------------------------------------

@@ -43,7 +43,7 @@ struct DeepArgs {
     int32_t n_ref;                       /* N >= 1 */
     int32_t max_iter, aa;
     double zoom, B2;
-    int32_t W, H, rows_local, part, nparts, rows_per_strip, out_frame;
+    TileGeom g;
     uint32_t flags;
     /* colour stage (fill_params's values for the same fr_params) */
     int32_t interior_style, lib_log;
@@ -398,8 +398,7 @@ deep_kernel(const ARGS AA)
     const LogTab<double> lg{log2_lds};
 
     const uint32_t lane = threadIdx.x & (kWave - 1);
-    const int lx = (int)(lane & 7u), ly = (int)(lane >> 3);
-    const int W = A.W, H = A.H;
+    const int W = A.g.W, H = A.g.H;
     const int aa = A.aa > 1 ? A.aa : 1;
     const double resx = (double)W, resy = (double)H, zoom = A.zoom;
     const double2 z1 = A.orbit[1];
@@ -407,71 +406,52 @@ deep_kernel(const ARGS AA)
     const bool want_nu = want_rgb || A.nu != nullptr;
 
     unsigned long long n_plain = 0ull, n_bla = 0ull, n_upd = 0ull;   /* BLA: this lane's steps and updates */
-    WaveQueue q;
-    q.init(A.q.heads, A.q.n_blk, (uint32_t)kShardBlock, A.q.run_shift, A.q.run_min, A.q.run_max, lane, A.q.ns_log2);
-    q.set_probes(A.q.flags);
-    uint32_t begin, count, cur_shard;
-    while (q.next(begin, count, cur_shard)) {
-        for (uint32_t j = begin; j < begin + count; ++j) {
-            const uint32_t blk = WaveQueue::block_of(j / kShardBlock, cur_shard, A.q.ns_log2);
-            if (blk >= A.q.n_blk) continue;
-            const uint32_t sid = blk * kShardBlock + (j % kShardBlock);
-            if (sid >= A.q.n_items) continue;
-            const uint32_t sty = sid / A.q.nsx, stx = sid - sty * A.q.nsx;
-            const int px = (int)stx * 8 + lx;
-            const int lrow = (int)sty * 8 + ly;
-            const bool inside = px < W && lrow < A.rows_local;
-            int py = lrow;
-            if (A.nparts != 1) {
-                const int strip = lrow / A.rows_per_strip;
-                py = (strip * A.nparts + A.part) * A.rows_per_strip + (lrow - strip * A.rows_per_strip);
-            }
-            float acc[3] = {0.0f, 0.0f, 0.0f};
-            double nu0 = 0.0;
-            int it0 = 0;
-            const int nsamp = aa * aa;
-            for (int s = 0; s < nsamp; ++s) {
-                const int sy = s / aa, sx = s - sy * aa;                                   /* mandelbrot.comp:219-230 */
-                const double pxs = (double)px + (double)sx / (double)aa;
-                const double pys = (double)py + (double)sy / (double)aa;
-                const double dcx = ((pxs - 0.5 * resx) / resy) * zoom;                     /* :149-151, less the centre */
-                const double dcy = ((pys - 0.5 * resy) / resy) * zoom;
-                int esc;
-                double r2;
-                if constexpr (X) {
-                    double cx = ((pxs - 0.5 * resx) / resy) * AA.zm, cy = ((pys - 0.5 * resy) / resy) * AA.zm;
-                    int ec = AA.ze;
-                    if (!inside) { cx = 0.0; cy = 0.0; }
-                    x_norm(cx, cy, ec);
-                    deep_orbit_x(AA, cx, cy, ec, inside, esc, r2);
-                } else if constexpr (BLA) {
-                    uint32_t np, nb;
-                    deep_orbit_bla(A, AA.t, inside ? dcx : 0.0, inside ? dcy : 0.0, z1, inside, esc, r2, np, nb);
-                    if (inside) {
-                        n_plain += np; n_bla += nb;
-                        n_upd += (unsigned long long)(esc < A.max_iter ? esc + 1 : A.max_iter);
-                    }
-                } else {
-                    deep_orbit(A, inside ? dcx : 0.0, inside ? dcy : 0.0, z1, inside, esc, r2);
+    walk_subtiles<3, true>(A.q, A.g, lane, [&](const int px, const int py, const int lrow, const bool inside) {
+        float acc[3] = {0.0f, 0.0f, 0.0f};
+        double nu0 = 0.0;
+        int it0 = 0;
+        const int nsamp = aa * aa;
+        for (int s = 0; s < nsamp; ++s) {
+            const int sy = s / aa, sx = s - sy * aa;                                   /* mandelbrot.comp:219-230 */
+            const double pxs = (double)px + (double)sx / (double)aa;
+            const double pys = (double)py + (double)sy / (double)aa;
+            const double dcx = ((pxs - 0.5 * resx) / resy) * zoom;                     /* :149-151, less the centre */
+            const double dcy = ((pys - 0.5 * resy) / resy) * zoom;
+            int esc;
+            double r2;
+            if constexpr (X) {
+                double cx = ((pxs - 0.5 * resx) / resy) * AA.zm, cy = ((pys - 0.5 * resy) / resy) * AA.zm;
+                int ec = AA.ze;
+                if (!inside) { cx = 0.0; cy = 0.0; }
+                x_norm(cx, cy, ec);
+                deep_orbit_x(AA, cx, cy, ec, inside, esc, r2);
+            } else if constexpr (BLA) {
+                uint32_t np, nb;
+                deep_orbit_bla(A, AA.t, inside ? dcx : 0.0, inside ? dcy : 0.0, z1, inside, esc, r2, np, nb);
+                if (inside) {
+                    n_plain += np; n_bla += nb;
+                    n_upd += (unsigned long long)(esc < A.max_iter ? esc + 1 : A.max_iter);
                 }
-                double nu;
-                float rgb[3];
-                shade<double, 0>(A, S, lg, esc, r2, want_nu, want_rgb, nu, rgb);
-                if (s == 0) { nu0 = nu; it0 = esc; }
-                acc[0] += rgb[0]; acc[1] += rgb[1]; acc[2] += rgb[2];
+            } else {
+                deep_orbit(A, inside ? dcx : 0.0, inside ? dcy : 0.0, z1, inside, esc, r2);
             }
-            if (aa > 1) {
-                const float n = (float)(aa * aa);
-                acc[0] /= n; acc[1] /= n; acc[2] /= n;
-            }
-            if (want_rgb && (A.flags & FR_FLAG_POST_CHAIN)) post_chain(acc, A.brightness, A.saturation, A.contrast, false);
-            if (!inside) continue;
-            const size_t o = (size_t)(A.out_frame ? py : lrow) * (size_t)W + (size_t)px;
-            if (A.rgba) A.rgba[o] = make_float4(acc[0], acc[1], acc[2], 1.0f);
-            if (A.nu) A.nu[o] = nu0;
-            if (A.iter) A.iter[o] = it0;
+            double nu;
+            float rgb[3];
+            shade<double, 0>(A, S, lg, esc, r2, want_nu, want_rgb, nu, rgb);
+            if (s == 0) { nu0 = nu; it0 = esc; }
+            acc[0] += rgb[0]; acc[1] += rgb[1]; acc[2] += rgb[2];
         }
-    }
+        if (aa > 1) {
+            const float n = (float)(aa * aa);
+            acc[0] /= n; acc[1] /= n; acc[2] /= n;
+        }
+        if (want_rgb && (A.flags & FR_FLAG_POST_CHAIN)) post_chain(acc, A.brightness, A.saturation, A.contrast, false);
+        if (!inside) return;
+        const size_t o = plane_index(A.g, px, py, lrow);
+        if (A.rgba) A.rgba[o] = make_float4(acc[0], acc[1], acc[2], 1.0f);
+        if (A.nu) A.nu[o] = nu0;
+        if (A.iter) A.iter[o] = it0;
+    });
     if constexpr (BLA) {                                          /* updates skipped = updates - plain steps */
         unsigned long long v[3] = {n_plain, n_bla, n_upd - n_plain};
         for (int c = 0; c < 3; ++c) {

@@ -30,6 +30,15 @@ static constexpr size_t kReadyWord = kCtrlWords + (size_t)(kFeedbackShards + 1) 
 static constexpr size_t kFeedbackWord = kCtrlWords;            /* behind the stages: Feedback::dev_flag (kFeedbackShards words, 128 B apart) */
 static constexpr uint32_t kProbeEvery = 16;                     /* frames between two looks of a view that closed nothing */
 
+/* what a cached reference orbit was computed for (orbit_key_matches / orbit_key_store) */
+struct OrbitKey {
+    bool valid;                 /* the key describes the orbit on the device */
+    char* x;                    /* centre strings (malloc'd copies) */
+    char* y;
+    int32_t bits, max_iter;
+    float bailout;              /* compared by its bits */
+};
+
 struct fr_ctx {
     int device;
     int compute_units;
@@ -115,11 +124,7 @@ struct fr_ctx {
     double2* deep_orbit_dev;    /* Z_0 .. Z_N */
     size_t deep_orbit_cap;
     int32_t deep_len;           /* N + 1 */
-    bool deep_valid;            /* the key below describes deep_orbit_dev */
-    char* deep_key_x;           /* centre strings (malloc'd copies) */
-    char* deep_key_y;
-    int32_t deep_key_bits, deep_key_iter;
-    float deep_key_bailout;
+    OrbitKey deep_key;          /* of deep_orbit_dev */
     int deep_wg_per_cu;         /* resident workgroups per CU of deep_kernel<DeepArgs> (0 = not asked yet) */
     uint64_t deep_gen;          /* bumped whenever deep_orbit_dev receives another orbit */
     /* BLA (FR_FLAG_DEEP_BLA): the table of the cached orbit, and the step counts of the most recent BLA render */
@@ -140,11 +145,7 @@ struct fr_ctx {
     char* deepx_dev;
     size_t deepx_cap;
     int32_t deepx_len;          /* N + 1 */
-    bool deepx_valid;           /* the key below describes deepx_dev */
-    char* deepx_key_x;
-    char* deepx_key_y;
-    int32_t deepx_key_bits, deepx_key_iter;
-    float deepx_key_bailout;
+    OrbitKey deepx_key;         /* of deepx_dev */
     int deepx_wg_per_cu;        /* resident workgroups per CU of deep_kernel<DeepXArgs> (0 = not asked yet) */
 };
 
@@ -230,12 +231,12 @@ extern "C" void fr_ctx_destroy(fr_ctx* c)
     if (c->orbit_dev) (void)hipFree(c->orbit_dev);
     if (c->deep_orbit_host) (void)hipHostFree(c->deep_orbit_host);
     if (c->deep_orbit_dev) (void)hipFree(c->deep_orbit_dev);
-    free(c->deep_key_x);
-    free(c->deep_key_y);
+    free(c->deep_key.x);
+    free(c->deep_key.y);
     if (c->deepx_host) (void)hipHostFree(c->deepx_host);
     if (c->deepx_dev) (void)hipFree(c->deepx_dev);
-    free(c->deepx_key_x);
-    free(c->deepx_key_y);
+    free(c->deepx_key.x);
+    free(c->deepx_key.y);
     if (c->bla_r) (void)hipFree(c->bla_r);
     if (c->bla_ab) (void)hipFree(c->bla_ab);
     if (c->bla_steps_dev) (void)hipFree(c->bla_steps_dev);
@@ -660,6 +661,56 @@ static int finish_render(fr_ctx* c, hipStream_t stream, int nstages)
     return FR_OK;
 }
 
+/* the geometry part of a one-pass kernel's argument block (TileGeom, fr_kernels.hip.h) */
+static TileGeom tile_geom(uint32_t W, uint32_t H, uint32_t rows_local, const fr_shard* norm, bool out_frame)
+{
+    TileGeom g;
+    g.W = (int32_t)W; g.H = (int32_t)H; g.rows_local = (int32_t)rows_local;
+    g.part = (int32_t)norm->part; g.nparts = (int32_t)norm->nparts; g.rows_per_strip = (int32_t)norm->rows_per_strip;
+    g.out_frame = out_frame ? 1 : 0;
+    return g;
+}
+
+/* What an entry path that takes a caller's shard does first (enqueue_render has its own, with reserve_only).
+ * FR_OK with *rows_local == 0: this part owns no rows, nothing to do. */
+static int begin_shard(fr_ctx* c, const fr_shard* shard, uint32_t H, fr_shard* norm, uint32_t* rows_local)
+{
+    const int ov = check_overflow(c);            /* of an earlier asynchronous render nobody has asked about */
+    if (ov != FR_OK) return ov;
+    return normalise_shard(shard, H, norm, rows_local);
+}
+
+/* ---- one-pass kernels (Deep_Zoom, Phoenix, Mandelbulb, the deep views) ----------------------------------------------
+ * From "the argument block is filled" to "the render is finished".  One pass, no lane pool: a persistent grid of exactly
+ * the resident set over the 8x8 sub-tiles of the WaveQueue (walk_subtiles), planned as an unstaged tile pass
+ * (plan_tile_queue: short runs; waves of `moderate` launches stop at their home shard + a neighbour, with 64 shards on
+ * large frames; the others steal from every shard).  The resident set is wg_per_cu workgroups per CU: the caller's cache
+ * word of `kernel`, 0 = not asked yet -- then the occupancy query answers, once per context and kernel.
+ * g and q are the geometry and queue members of a. */
+template <class ARGS>
+static int launch_one_pass(fr_ctx* c, hipStream_t stream, const char* name, void (*kernel)(ARGS), ARGS& a, const TileGeom& g,
+                           QueueArgs& q, int& wg_per_cu, bool moderate)
+{
+    if (wg_per_cu == 0) {
+        int nb = 0;
+        const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, kBlockThreads, 0);
+        if (e != hipSuccess) return fr_set_error(FR_ERR_HIP, "%s occupancy query failed: %s", name, hipGetErrorString(e));
+        wg_per_cu = nb < 1 ? 1 : nb;
+    }
+    uint32_t grid = 0;
+    q = plan_tile_queue(c, (uint32_t)g.W, (uint32_t)g.rows_local, 3, false, moderate, (uint32_t)wg_per_cu, &grid);
+    q.heads = stage_heads(c, 0);
+    c->last_grid = grid;
+    c->last_pool_closing = -1;
+
+    FR_HIP_TRY(clear_control_block(c, stream, 1));
+    if (c->timing) FR_HIP_TRY(hipEventRecord(c->ev_begin, stream));
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlockThreads), 0, stream, a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fr_set_error(FR_ERR_HIP, "%s launch failed: %s", name, hipGetErrorString(e));
+    return finish_render(c, stream, 1);
+}
+
 /* Deep_Zoom: what VulkanEngine::prepare_deep_zoom_rendering + dispatch do per frame
  * (src/vk_engine.cpp:215-251, src/compute_effect_manager.h:236-324): recompute the fp64 reference orbit
  * at the view centre on the host (single point, sequential), narrow it to float pairs
@@ -705,38 +756,21 @@ static int enqueue_deep_zoom(fr_ctx* c, const fr_params* p, uint32_t W, uint32_t
     a.zoom_hi = (float)p->zoom;   a.zoom_lo = (float)(p->zoom - (double)a.zoom_hi);
     a.bailout = p->bailout; a.color_offset = p->color_offset; a.color_scale = p->color_scale;
     a.palette_mode = p->palette_mode; a.max_iter = max_iter; a.ref_iter = ref_iter;
-    a.W = (int32_t)W; a.H = (int32_t)H; a.rows_local = (int32_t)rows_local;
-    a.part = (int32_t)norm->part; a.nparts = (int32_t)norm->nparts; a.rows_per_strip = (int32_t)norm->rows_per_strip;
-    a.out_frame = out_frame ? 1 : 0;
+    a.g = tile_geom(W, H, rows_local, norm, out_frame);
     a.orbit = reinterpret_cast<const float2*>(c->orbit_dev);
     a.rgba = reinterpret_cast<float4*>(rgba); a.nu = (float*)nu; a.iter = iter;
 
-    uint32_t grid = 0;
-    a.q = plan_tile_queue(c, W, rows_local, 3, false, false, 8u, &grid);
-    a.q.heads = stage_heads(c, 0);
-    c->last_grid = grid;
-    c->last_pool_closing = -1;
-
-    FR_HIP_TRY(clear_control_block(c, stream, 1));
-    if (c->timing) FR_HIP_TRY(hipEventRecord(c->ev_begin, stream));
-    hipLaunchKernelGGL((deep_zoom_kernel<3>), dim3(grid), dim3(kBlockThreads), 0, stream, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fr_set_error(FR_ERR_HIP, "deep-zoom kernel launch failed: %s", hipGetErrorString(e));
-    return finish_render(c, stream, 1);
+    int wg = 8;                                  /* a fixed 8 workgroups per CU: nothing is asked */
+    return launch_one_pass(c, stream, "deep_zoom_kernel", deep_zoom_kernel<3>, a, a.g, a.q, wg, false);
 }
 
-/* ---- Phoenix (fr_phoenix.hip.h) -----------------------------------------------------------------------------------
- * One pass, no lane pool: a persistent grid of exactly the resident set over the 8x8 sub-tiles of the WaveQueue, planned
- * as an unstaged tile pass (plan_tile_queue: short runs; waves of launches of moderate cost stop at their home shard + a
- * neighbour, with 64 shards on large frames; long ones steal from every shard). */
+/* ---- Phoenix (fr_phoenix.hip.h): one pass (launch_one_pass) ---------------------------------------------------------- */
 static int enqueue_phoenix(fr_ctx* c, const fr_params* p, const fr_phoenix_params* ph, uint32_t W, uint32_t H,
                            const fr_shard* shard, float* rgba, void* nu, int32_t* iter, hipStream_t stream, bool out_frame)
 {
-    const int ov = check_overflow(c);            /* of an earlier asynchronous render nobody has asked about */
-    if (ov != FR_OK) return ov;
     fr_shard norm;
     uint32_t rows_local = 0;
-    const int sh = normalise_shard(shard, H, &norm, &rows_local);
+    const int sh = begin_shard(c, shard, H, &norm, &rows_local);
     if (sh != FR_OK || rows_local == 0) return sh;
     const bool f64 = p->precision == FR_PRECISION_F64;
 
@@ -751,47 +785,26 @@ static int enqueue_phoenix(fr_ctx* c, const fr_params* p, const fr_phoenix_param
     a.brightness = p->color_brightness; a.saturation = p->color_saturation; a.contrast = p->color_contrast;
     a.max_iter = p->max_iterations; a.aa = p->antialiasing_samples; a.use_julia = ph->use_julia_set;
     a.flags = p->flags;
-    a.W = (int32_t)W; a.H = (int32_t)H; a.rows_local = (int32_t)rows_local;
-    a.part = (int32_t)norm.part; a.nparts = (int32_t)norm.nparts; a.rows_per_strip = (int32_t)norm.rows_per_strip;
-    a.out_frame = out_frame ? 1 : 0;
+    a.g = tile_geom(W, H, rows_local, &norm, out_frame);
     a.rgba = reinterpret_cast<float4*>(rgba); a.nu = nu; a.iter = iter;
 
-    int& wg = c->phoenix_wg_per_cu[f64 ? 1 : 0];
-    if (wg == 0) {
-        int nb = 0;
-        const hipError_t e = f64 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, phoenix_kernel<double>, kBlockThreads, 0)
-                                 : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, phoenix_kernel<float>, kBlockThreads, 0);
-        if (e != hipSuccess) return fr_set_error(FR_ERR_HIP, "phoenix occupancy query failed: %s", hipGetErrorString(e));
-        wg = nb < 1 ? 1 : nb;
-    }
+    /* launches of moderate cost stop at their home shard + a neighbour; long ones steal from every shard */
     const int aa1 = p->antialiasing_samples > 1 ? p->antialiasing_samples : 1;
-    uint32_t grid = 0;
-    a.q = plan_tile_queue(c, W, rows_local, 3, false, (long long)p->max_iterations * aa1 * aa1 < 768, (uint32_t)wg, &grid);
-    a.q.heads = stage_heads(c, 0);
-    c->last_grid = grid;
-    c->last_pool_closing = -1;
-
-    FR_HIP_TRY(clear_control_block(c, stream, 1));
-    if (c->timing) FR_HIP_TRY(hipEventRecord(c->ev_begin, stream));
-    if (f64) hipLaunchKernelGGL(phoenix_kernel<double>, dim3(grid), dim3(kBlockThreads), 0, stream, a);
-    else hipLaunchKernelGGL(phoenix_kernel<float>, dim3(grid), dim3(kBlockThreads), 0, stream, a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fr_set_error(FR_ERR_HIP, "phoenix kernel launch failed: %s", hipGetErrorString(e));
-    return finish_render(c, stream, 1);
+    const bool moderate = (long long)p->max_iterations * aa1 * aa1 < 768;
+    return launch_one_pass(c, stream, f64 ? "phoenix_kernel<double>" : "phoenix_kernel<float>",
+                           f64 ? phoenix_kernel<double> : phoenix_kernel<float>, a, a.g, a.q, c->phoenix_wg_per_cu[f64 ? 1 : 0],
+                           moderate);
 }
 
 /* ---- Mandelbulb (fr_mandelbulb.hip.h) -----------------------------------------------------------------------------
- * One pass, no lane pool, as Phoenix: a persistent grid of exactly the resident set (occupancy query, cached) over the
- * 8x8 sub-tiles of the WaveQueue, planned as an unstaged tile pass with unlimited stealing (ray lengths vary too much
- * across a frame for a wave to stop at its home shard).  main's clamps (:177-190) are applied here. */
+ * One pass (launch_one_pass) with unlimited stealing: ray lengths vary too much across a frame for a wave to stop at its
+ * home shard.  main's clamps (:177-190) are applied here. */
 static int enqueue_mandelbulb(fr_ctx* c, const fr_params* p, const fr_mandelbulb_params* mb, uint32_t W, uint32_t H,
                               const fr_shard* shard, float* rgba, void* nu, int32_t* iter, hipStream_t stream, bool out_frame)
 {
-    const int ov = check_overflow(c);            /* of an earlier asynchronous render nobody has asked about */
-    if (ov != FR_OK) return ov;
     fr_shard norm;
     uint32_t rows_local = 0;
-    const int sh = normalise_shard(shard, H, &norm, &rows_local);
+    const int sh = begin_shard(c, shard, H, &norm, &rows_local);
     if (sh != FR_OK || rows_local == 0) return sh;
     auto fmax_ = [](float x, float y) { return x < y ? y : x; };              /* GLSL max, FMax's operand order */
     auto fclamp = [&](float x, float lo, float hi) { const float m = fmax_(x, lo); return hi < m ? hi : m; };
@@ -813,39 +826,18 @@ static int enqueue_mandelbulb(fr_ctx* c, const fr_params* p, const fr_mandelbulb
     a.saturation = fmax_(p->color_saturation, 0.0f);
     a.contrast = fmax_(p->color_contrast, 0.1f);
     a.flags = p->flags;
-    a.W = (int32_t)W; a.H = (int32_t)H; a.rows_local = (int32_t)rows_local;
-    a.part = (int32_t)norm.part; a.nparts = (int32_t)norm.nparts; a.rows_per_strip = (int32_t)norm.rows_per_strip;
-    a.out_frame = out_frame ? 1 : 0;
+    a.g = tile_geom(W, H, rows_local, &norm, out_frame);
     a.rgba = reinterpret_cast<float4*>(rgba); a.nu = (float*)nu; a.iter = iter;
 
     const bool split = c->tune_mandelbulb_split != 1u;
-    int& wg = c->mandelbulb_wg_per_cu[split ? 1 : 0];
-    if (wg == 0) {
-        int nb = 0;
-        const hipError_t e = split ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, mandelbulb_kernel<true>, kBlockThreads, 0)
-                                   : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, mandelbulb_kernel<false>, kBlockThreads, 0);
-        if (e != hipSuccess) return fr_set_error(FR_ERR_HIP, "mandelbulb occupancy query failed: %s", hipGetErrorString(e));
-        wg = nb < 1 ? 1 : nb;
-    }
-    uint32_t grid = 0;
-    a.q = plan_tile_queue(c, W, rows_local, 3, false, false, (uint32_t)wg, &grid);
-    a.q.heads = stage_heads(c, 0);
-    c->last_grid = grid;
-    c->last_pool_closing = -1;
-
-    FR_HIP_TRY(clear_control_block(c, stream, 1));
-    if (c->timing) FR_HIP_TRY(hipEventRecord(c->ev_begin, stream));
-    if (split) hipLaunchKernelGGL(mandelbulb_kernel<true>, dim3(grid), dim3(kBlockThreads), 0, stream, a);
-    else hipLaunchKernelGGL(mandelbulb_kernel<false>, dim3(grid), dim3(kBlockThreads), 0, stream, a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fr_set_error(FR_ERR_HIP, "mandelbulb kernel launch failed: %s", hipGetErrorString(e));
-    return finish_render(c, stream, 1);
+    return launch_one_pass(c, stream, split ? "mandelbulb_kernel<true>" : "mandelbulb_kernel<false>",
+                           split ? mandelbulb_kernel<true> : mandelbulb_kernel<false>, a, a.g, a.q,
+                           c->mandelbulb_wg_per_cu[split ? 1 : 0], false);
 }
 
 /* ---- deep views (fr_deep.hip.h) -------------------------------------------------------------------------------------
- * The reference orbit of the view (fr_deep.c, on the host) unless the context holds it already, then one pass as Phoenix:
- * a persistent grid of exactly the resident set (occupancy query, cached) over the 8x8 sub-tiles of the WaveQueue,
- * planned as an unstaged tile pass with unlimited stealing. */
+ * The reference orbit of the view (fr_deep.c, on the host) unless the context holds it already, then one pass
+ * (launch_one_pass) with unlimited stealing. */
 static char* copy_string(const char* s)
 {
     const size_t n = strlen(s) + 1;
@@ -854,21 +846,36 @@ static char* copy_string(const char* s)
     return d;
 }
 
+static bool orbit_key_matches(const OrbitKey& k, const char* x, const char* y, int32_t bits, int32_t max_iter, float bailout)
+{
+    return k.valid && k.bits == bits && k.max_iter == max_iter && memcmp(&k.bailout, &bailout, sizeof(float)) == 0 &&
+           strcmp(k.x, x) == 0 && strcmp(k.y, y) == 0;
+}
+
+/* the key of the orbit that has just arrived on the device: valid once both strings are copied */
+static int orbit_key_store(OrbitKey& k, const char* x, const char* y, int32_t bits, int32_t max_iter, float bailout)
+{
+    free(k.x); free(k.y);
+    k.x = copy_string(x);
+    k.y = copy_string(y);
+    if (!k.x || !k.y) return fr_set_error(FR_ERR_NOMEM, "out of host memory");
+    k.bits = bits; k.max_iter = max_iter; k.bailout = bailout;
+    k.valid = true;
+    return FR_OK;
+}
+
 static int deep_orbit_for(fr_ctx* c, const fr_params* p, const fr_deep_view* v, hipStream_t stream)
 {
     const int32_t bits = v->frac_bits ? v->frac_bits : fr_deep_frac_bits(p->zoom);
     const int32_t max_iter = p->max_iterations;
-    if (c->deep_valid && c->deep_key_bits == bits && c->deep_key_iter == max_iter &&
-        memcmp(&c->deep_key_bailout, &p->bailout, sizeof(float)) == 0 && strcmp(c->deep_key_x, v->center_x) == 0 &&
-        strcmp(c->deep_key_y, v->center_y) == 0)
-        return FR_OK;
+    if (orbit_key_matches(c->deep_key, v->center_x, v->center_y, bits, max_iter, p->bailout)) return FR_OK;
     /* the pinned buffer may still feed an earlier upload, the device orbit an earlier render (on this stream, the
      * context's own or the stream of the previous render) */
     FR_HIP_TRY(hipStreamSynchronize(stream));
     FR_HIP_TRY(hipStreamSynchronize(c->stream));
     if (c->have_render && c->last_stream != stream) FR_HIP_TRY(hipStreamSynchronize(c->last_stream));
     if (c->ev_bla_valid) FR_HIP_TRY(hipEventSynchronize(c->ev_bla));      /* the last BLA render, wherever it went */
-    c->deep_valid = false;
+    c->deep_key.valid = false;
     ++c->deep_gen;
     const size_t need = (size_t)max_iter + 1;
     if (need > c->deep_orbit_cap) {
@@ -885,14 +892,9 @@ static int deep_orbit_for(fr_ctx* c, const fr_params* p, const fr_deep_view* v, 
     FR_HIP_TRY(hipMemcpyAsync(c->deep_orbit_dev, c->deep_orbit_host, (size_t)len * sizeof(double2), hipMemcpyHostToDevice,
                               stream));
     FR_HIP_TRY(hipStreamSynchronize(stream));     /* a later render of this view may go to another stream */
-    free(c->deep_key_x); free(c->deep_key_y);
-    c->deep_key_x = copy_string(v->center_x);
-    c->deep_key_y = copy_string(v->center_y);
-    if (!c->deep_key_x || !c->deep_key_y) return fr_set_error(FR_ERR_NOMEM, "out of host memory");
-    c->deep_key_bits = bits; c->deep_key_iter = max_iter; c->deep_key_bailout = p->bailout;
-    c->deep_len = len;
-    c->deep_valid = true;
-    return FR_OK;
+    const int ks = orbit_key_store(c->deep_key, v->center_x, v->center_y, bits, max_iter, p->bailout);
+    if (ks == FR_OK) c->deep_len = len;
+    return ks;
 }
 
 /* BLA: the table of the cached orbit for this frame's dcmax (the whole frame's W, H and zoom), built on `stream` unless
@@ -943,14 +945,13 @@ static int deep_bla_table_for(fr_ctx* c, const fr_params* p, uint32_t W, uint32_
 
 /* FR_FLAG_DEEP_BLA: the table, then deep_kernel<DeepBlaArgs> on the same queue plan as deep_kernel (its own occupancy), its
  * counters cleared in front of it and copied to pinned memory behind it */
-static int enqueue_deep_bla(fr_ctx* c, const fr_params* p, uint32_t W, uint32_t H, uint32_t rows_local, const DeepArgs& d,
-                            hipStream_t stream)
+static int enqueue_deep_bla(fr_ctx* c, const fr_params* p, const DeepArgs& d, hipStream_t stream)
 {
     DeepBlaArgs a;
     memset(&a, 0, sizeof(a));
     a.d = d;
     int levels = 0;
-    const int ts = deep_bla_table_for(c, p, W, H, stream, &levels);
+    const int ts = deep_bla_table_for(c, p, (uint32_t)d.g.W, (uint32_t)d.g.H, stream, &levels);
     if (ts != FR_OK) return ts;
     a.t.r = c->bla_r; a.t.ab = c->bla_ab; a.t.levels = levels;
     if (!c->bla_steps_dev) {
@@ -958,25 +959,9 @@ static int enqueue_deep_bla(fr_ctx* c, const fr_params* p, uint32_t W, uint32_t 
         FR_HIP_TRY(hipHostMalloc((void**)&c->bla_steps_host, 3 * sizeof(unsigned long long)));
     }
     a.t.steps = c->bla_steps_dev;
-    if (c->deep_bla_wg_per_cu == 0) {
-        int nb = 0;
-        const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, deep_kernel<DeepBlaArgs>, kBlockThreads, 0);
-        if (e != hipSuccess) return fr_set_error(FR_ERR_HIP, "deep BLA occupancy query failed: %s", hipGetErrorString(e));
-        c->deep_bla_wg_per_cu = nb < 1 ? 1 : nb;
-    }
-    uint32_t grid = 0;
-    a.d.q = plan_tile_queue(c, W, rows_local, 3, false, false, (uint32_t)c->deep_bla_wg_per_cu, &grid);
-    a.d.q.heads = stage_heads(c, 0);
-    c->last_grid = grid;
-    c->last_pool_closing = -1;
-
     FR_HIP_TRY(hipMemsetAsync(c->bla_steps_dev, 0, 3 * sizeof(unsigned long long), stream));
-    FR_HIP_TRY(clear_control_block(c, stream, 1));
-    if (c->timing) FR_HIP_TRY(hipEventRecord(c->ev_begin, stream));
-    hipLaunchKernelGGL(deep_kernel<DeepBlaArgs>, dim3(grid), dim3(kBlockThreads), 0, stream, a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fr_set_error(FR_ERR_HIP, "deep BLA kernel launch failed: %s", hipGetErrorString(e));
-    const int st = finish_render(c, stream, 1);
+    const int st = launch_one_pass(c, stream, "deep_kernel<DeepBlaArgs>", deep_kernel<DeepBlaArgs>, a, a.d.g, a.d.q,
+                                   c->deep_bla_wg_per_cu, false);
     if (st != FR_OK) return st;
     FR_HIP_TRY(hipMemcpyAsync(c->bla_steps_host, c->bla_steps_dev, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost,
                               stream));
@@ -991,27 +976,13 @@ static int enqueue_deep_bla(fr_ctx* c, const fr_params* p, uint32_t W, uint32_t 
     return FR_OK;
 }
 
-static int enqueue_deep(fr_ctx* c, const fr_params* p, const fr_deep_view* v, uint32_t W, uint32_t H, const fr_shard* shard,
-                        float* rgba, void* nu, int32_t* iter, hipStream_t stream, bool out_frame)
+/* everything of DeepArgs that enqueue_deep and enqueue_deepx fill alike: zoom and the orbit stay with the caller */
+static void fill_deep_args(DeepArgs& a, const fr_ctx* c, const fr_params* p, const TileGeom& g, float* rgba, void* nu,
+                           int32_t* iter)
 {
-    const int ov = check_overflow(c);            /* of an earlier asynchronous render nobody has asked about */
-    if (ov != FR_OK) return ov;
-    fr_shard norm;
-    uint32_t rows_local = 0;
-    const int sh = normalise_shard(shard, H, &norm, &rows_local);
-    if (sh != FR_OK || rows_local == 0) return sh;
-    const int os = deep_orbit_for(c, p, v, stream);
-    if (os != FR_OK) return os;
-
-    DeepArgs a;
-    memset(&a, 0, sizeof(a));
-    a.orbit = c->deep_orbit_dev; a.n_ref = c->deep_len - 1;
     a.max_iter = p->max_iterations; a.aa = p->antialiasing_samples;
-    a.zoom = p->zoom;
     a.B2 = (double)p->bailout * (double)p->bailout;
-    a.W = (int32_t)W; a.H = (int32_t)H; a.rows_local = (int32_t)rows_local;
-    a.part = (int32_t)norm.part; a.nparts = (int32_t)norm.nparts; a.rows_per_strip = (int32_t)norm.rows_per_strip;
-    a.out_frame = out_frame ? 1 : 0;
+    a.g = g;
     a.flags = p->flags;
     a.interior_style = p->interior_style;
     a.lib_log = !(p->bailout > 1.0f);            /* as fill_params */
@@ -1022,26 +993,26 @@ static int enqueue_deep(fr_ctx* c, const fr_params* p, const fr_deep_view* v, ui
     fr_palette_table_build(0, p->palette_mode, &a.pal);
     a.log2_tab = c->log2_tab;
     a.rgba = reinterpret_cast<float4*>(rgba); a.nu = (double*)nu; a.iter = iter;
+}
 
-    if (p->flags & FR_FLAG_DEEP_BLA) return enqueue_deep_bla(c, p, W, H, rows_local, a, stream);
-    if (c->deep_wg_per_cu == 0) {
-        int nb = 0;
-        const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, deep_kernel<DeepArgs>, kBlockThreads, 0);
-        if (e != hipSuccess) return fr_set_error(FR_ERR_HIP, "deep occupancy query failed: %s", hipGetErrorString(e));
-        c->deep_wg_per_cu = nb < 1 ? 1 : nb;
-    }
-    uint32_t grid = 0;
-    a.q = plan_tile_queue(c, W, rows_local, 3, false, false, (uint32_t)c->deep_wg_per_cu, &grid);
-    a.q.heads = stage_heads(c, 0);
-    c->last_grid = grid;
-    c->last_pool_closing = -1;
+static int enqueue_deep(fr_ctx* c, const fr_params* p, const fr_deep_view* v, uint32_t W, uint32_t H, const fr_shard* shard,
+                        float* rgba, void* nu, int32_t* iter, hipStream_t stream, bool out_frame)
+{
+    fr_shard norm;
+    uint32_t rows_local = 0;
+    const int sh = begin_shard(c, shard, H, &norm, &rows_local);
+    if (sh != FR_OK || rows_local == 0) return sh;
+    const int os = deep_orbit_for(c, p, v, stream);
+    if (os != FR_OK) return os;
 
-    FR_HIP_TRY(clear_control_block(c, stream, 1));
-    if (c->timing) FR_HIP_TRY(hipEventRecord(c->ev_begin, stream));
-    hipLaunchKernelGGL(deep_kernel<DeepArgs>, dim3(grid), dim3(kBlockThreads), 0, stream, a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fr_set_error(FR_ERR_HIP, "deep kernel launch failed: %s", hipGetErrorString(e));
-    return finish_render(c, stream, 1);
+    DeepArgs a;
+    memset(&a, 0, sizeof(a));
+    a.orbit = c->deep_orbit_dev; a.n_ref = c->deep_len - 1;
+    a.zoom = p->zoom;
+    fill_deep_args(a, c, p, tile_geom(W, H, rows_local, &norm, out_frame), rgba, nu, iter);
+
+    if (p->flags & FR_FLAG_DEEP_BLA) return enqueue_deep_bla(c, p, a, stream);
+    return launch_one_pass(c, stream, "deep_kernel<DeepArgs>", deep_kernel<DeepArgs>, a, a.g, a.q, c->deep_wg_per_cu, false);
 }
 
 /* ---- extended views (fr_render_deepx) -------------------------------------------------------------------------------
@@ -1050,15 +1021,12 @@ static int enqueue_deep(fr_ctx* c, const fr_params* p, const fr_deep_view* v, ui
 static int deepx_orbit_for(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, int32_t bits, hipStream_t stream)
 {
     const int32_t max_iter = p->max_iterations;
-    if (c->deepx_valid && c->deepx_key_bits == bits && c->deepx_key_iter == max_iter &&
-        memcmp(&c->deepx_key_bailout, &p->bailout, sizeof(float)) == 0 && strcmp(c->deepx_key_x, v->center_x) == 0 &&
-        strcmp(c->deepx_key_y, v->center_y) == 0)
-        return FR_OK;
+    if (orbit_key_matches(c->deepx_key, v->center_x, v->center_y, bits, max_iter, p->bailout)) return FR_OK;
     /* as deep_orbit_for: the pinned block may still feed an upload, the device block an earlier render */
     FR_HIP_TRY(hipStreamSynchronize(stream));
     FR_HIP_TRY(hipStreamSynchronize(c->stream));
     if (c->have_render && c->last_stream != stream) FR_HIP_TRY(hipStreamSynchronize(c->last_stream));
-    c->deepx_valid = false;
+    c->deepx_key.valid = false;
     const size_t need = (size_t)max_iter + 1;
     const size_t point_bytes = 2 * sizeof(double2) + sizeof(int32_t);
     if (need > c->deepx_cap) {
@@ -1084,24 +1052,17 @@ static int deepx_orbit_for(fr_ctx* c, const fr_params* p, const fr_deepx_view* v
     }
     FR_HIP_TRY(hipMemcpyAsync(c->deepx_dev, c->deepx_host, cap * point_bytes, hipMemcpyHostToDevice, stream));
     FR_HIP_TRY(hipStreamSynchronize(stream));     /* a later render of this view may go to another stream */
-    free(c->deepx_key_x); free(c->deepx_key_y);
-    c->deepx_key_x = copy_string(v->center_x);
-    c->deepx_key_y = copy_string(v->center_y);
-    if (!c->deepx_key_x || !c->deepx_key_y) return fr_set_error(FR_ERR_NOMEM, "out of host memory");
-    c->deepx_key_bits = bits; c->deepx_key_iter = max_iter; c->deepx_key_bailout = p->bailout;
-    c->deepx_len = len;
-    c->deepx_valid = true;
-    return FR_OK;
+    const int ks = orbit_key_store(c->deepx_key, v->center_x, v->center_y, bits, max_iter, p->bailout);
+    if (ks == FR_OK) c->deepx_len = len;
+    return ks;
 }
 
 static int enqueue_deepx(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, uint32_t W, uint32_t H, const fr_shard* shard,
                          float* rgba, void* nu, int32_t* iter, hipStream_t stream, bool out_frame)
 {
-    const int ov = check_overflow(c);            /* of an earlier asynchronous render nobody has asked about */
-    if (ov != FR_OK) return ov;
     fr_shard norm;
     uint32_t rows_local = 0;
-    const int sh = normalise_shard(shard, H, &norm, &rows_local);
+    const int sh = begin_shard(c, shard, H, &norm, &rows_local);
     if (sh != FR_OK || rows_local == 0) return sh;
     DeepXArgs x;
     memset(&x, 0, sizeof(x));
@@ -1117,40 +1078,9 @@ static int enqueue_deepx(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, 
     x.mant = a.orbit + cap;
     x.exp2 = reinterpret_cast<const int32_t*>(x.mant + cap);
     a.n_ref = c->deepx_len - 1;
-    a.max_iter = p->max_iterations; a.aa = p->antialiasing_samples;
-    a.B2 = (double)p->bailout * (double)p->bailout;
-    a.W = (int32_t)W; a.H = (int32_t)H; a.rows_local = (int32_t)rows_local;
-    a.part = (int32_t)norm.part; a.nparts = (int32_t)norm.nparts; a.rows_per_strip = (int32_t)norm.rows_per_strip;
-    a.out_frame = out_frame ? 1 : 0;
-    a.flags = p->flags;
-    a.interior_style = p->interior_style;
-    a.lib_log = !(p->bailout > 1.0f);            /* as fill_params */
-    a.inv_max_iter = 1.0 / (double)p->max_iterations;
-    a.inv_log2_bailout = 1.0 / log2((double)p->bailout);
-    a.color_scale_d = (double)p->color_scale; a.color_offset_d = (double)p->color_offset;
-    a.brightness = p->color_brightness; a.saturation = p->color_saturation; a.contrast = p->color_contrast;
-    fr_palette_table_build(0, p->palette_mode, &a.pal);
-    a.log2_tab = c->log2_tab;
-    a.rgba = reinterpret_cast<float4*>(rgba); a.nu = (double*)nu; a.iter = iter;
+    fill_deep_args(a, c, p, tile_geom(W, H, rows_local, &norm, out_frame), rgba, nu, iter);
 
-    if (c->deepx_wg_per_cu == 0) {
-        int nb = 0;
-        const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, deep_kernel<DeepXArgs>, kBlockThreads, 0);
-        if (e != hipSuccess) return fr_set_error(FR_ERR_HIP, "deepx occupancy query failed: %s", hipGetErrorString(e));
-        c->deepx_wg_per_cu = nb < 1 ? 1 : nb;
-    }
-    uint32_t grid = 0;
-    a.q = plan_tile_queue(c, W, rows_local, 3, false, false, (uint32_t)c->deepx_wg_per_cu, &grid);
-    a.q.heads = stage_heads(c, 0);
-    c->last_grid = grid;
-    c->last_pool_closing = -1;
-
-    FR_HIP_TRY(clear_control_block(c, stream, 1));
-    if (c->timing) FR_HIP_TRY(hipEventRecord(c->ev_begin, stream));
-    hipLaunchKernelGGL(deep_kernel<DeepXArgs>, dim3(grid), dim3(kBlockThreads), 0, stream, x);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fr_set_error(FR_ERR_HIP, "deepx kernel launch failed: %s", hipGetErrorString(e));
-    return finish_render(c, stream, 1);
+    return launch_one_pass(c, stream, "deep_kernel<DeepXArgs>", deep_kernel<DeepXArgs>, x, a.g, a.q, c->deepx_wg_per_cu, false);
 }
 
 /* the parameter part of the kernel argument block (everything that does not depend on the frame geometry) */
@@ -1707,8 +1637,9 @@ static int enqueue_ssaa_staged(fr_ctx* c, const fr_params* p, uint32_t W, uint32
 }
 
 /* ---- render entry points --------------------------------------------------------------------------------------------
- * fr_render_shard(_async), fr_render_phoenix(_async), fr_render_mandelbulb(_async) and fr_render_deep(_async): their parameter checks, then render_sync / render_async with the
- * enqueue step as enqueue(shard, rgba, nu, iter, stream, out_frame) */
+ * fr_render_shard, fr_render_phoenix, fr_render_mandelbulb, fr_render_deep and fr_render_deepx, each with its _async form:
+ * their parameter checks, then render_sync / render_async with the enqueue step as
+ * enqueue(shard, rgba, nu, iter, stream, out_frame) */
 static int check_common(fr_ctx* c, const fr_params* p, uint32_t W, uint32_t H, const fr_output* out)
 {
     if (!c) return fr_set_error(FR_ERR_INVALID_ARG, "ctx is NULL");

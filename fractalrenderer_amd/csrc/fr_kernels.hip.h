@@ -757,6 +757,56 @@ struct WaveQueue {
     }
 };
 
+/* ---- one-pass kernels: the sub-tile walk -------------------------------------------------------
+ * Where the rows of a render live (tile_geom() on the host fills it): the part renders rows_local rows of a W x H frame;
+ * with nparts > 1 they are strips of rows_per_strip rows dealt round-robin to the parts. */
+struct TileGeom {
+    int32_t W, H;                /* whole frame */
+    int32_t rows_local;          /* rows this part renders */
+    int32_t part, nparts, rows_per_strip;
+    int32_t out_frame;           /* as LaunchArgs::out_frame */
+};
+
+/* index of pixel (px, frame row py = local row lrow) in the output planes */
+__device__ __forceinline__ size_t plane_index(const TileGeom& G, const int px, const int py, const int lrow)
+{
+    return (size_t)(G.out_frame ? py : lrow) * (size_t)G.W + (size_t)px;
+}
+
+/* Pulls runs of sub-tiles (2^FPW_LOG2 pixels wide, one pixel per lane) from the sharded queue until it is dry and calls
+ * body(px, py, lrow, inside) for each: px the lane's column, lrow its row among the part's rows, py its row of the frame.
+ * EVERY lane reaches the body, `inside` the frame or not: the bodies' sample loops vote across the wave.  PROBES: the
+ * launch's probe limit applies (set_probes). */
+template <int FPW_LOG2, bool PROBES, class Body>
+__device__ __forceinline__ void walk_subtiles(const QueueArgs& Q, const TileGeom& G, const uint32_t lane, Body&& body)
+{
+    constexpr int FPW = 1 << FPW_LOG2;
+    constexpr int FPH = kWave / FPW;
+    const int lx = (int)(lane & (FPW - 1)), ly = (int)(lane >> FPW_LOG2);
+    WaveQueue q;
+    q.init(Q.heads, Q.n_blk, (uint32_t)kShardBlock, Q.run_shift, Q.run_min, Q.run_max, lane, Q.ns_log2);
+    if (PROBES) q.set_probes(Q.flags);
+    uint32_t begin, count, cur_shard;
+    while (q.next(begin, count, cur_shard)) {
+        for (uint32_t j = begin; j < begin + count; ++j) {
+            const uint32_t blk = WaveQueue::block_of(j / kShardBlock, cur_shard, Q.ns_log2);
+            if (blk >= Q.n_blk) continue;
+            const uint32_t sid = blk * kShardBlock + (j % kShardBlock);
+            if (sid >= Q.n_items) continue;
+            const uint32_t sty = sid / Q.nsx, stx = sid - sty * Q.nsx;
+            const int px = (int)stx * FPW + lx;
+            const int lrow = (int)sty * FPH + ly;
+            const bool inside = px < G.W && lrow < G.rows_local;
+            int py = lrow;
+            if (G.nparts != 1) {
+                const int strip = lrow / G.rows_per_strip;
+                py = (strip * G.nparts + G.part) * G.rows_per_strip + (lrow - strip * G.rows_per_strip);
+            }
+            body(px, py, lrow, inside);
+        }
+    }
+}
+
 /* ---- survivor ring ---------------------------------------------------------------------------
  * A wave's unfinished samples are appended to a ring in LDS (wave-private: DS operations of one
  * wave execute in order, no barrier needed); whenever 64 are queued, lane l takes record head+l
@@ -2686,7 +2736,7 @@ struct DeepZoomArgs {
     float cx_hi, cx_lo, cy_hi, cy_lo, zoom_hi, zoom_lo;
     float bailout, color_offset, color_scale;
     int32_t palette_mode, max_iter, ref_iter;
-    int32_t W, H, rows_local, part, nparts, rows_per_strip, out_frame;
+    TileGeom g;
     const float2* orbit;
     float4* rgba;
     float* nu;
@@ -2744,11 +2794,8 @@ template <int FPW_LOG2>
 __global__ void __launch_bounds__(kBlockThreads)
 deep_zoom_kernel(const DeepZoomArgs A)
 {
-    constexpr int FPW = 1 << FPW_LOG2;
-    constexpr int FPH = kWave / FPW;
     const uint32_t lane = threadIdx.x & (kWave - 1);
-    const int lx = (int)(lane & (FPW - 1)), ly = (int)(lane >> FPW_LOG2);
-    const int W = A.W, H = A.H, max_iter = A.max_iter, ref_iter = A.ref_iter;
+    const int W = A.g.W, H = A.g.H, max_iter = A.max_iter, ref_iter = A.ref_iter;
     const float bailout = fmaxf(2.0f, A.bailout);                   /* :114 */
     const float bailout_sq = bailout * bailout;
     const FF center_x = {A.cx_hi, A.cx_lo}, center_y = {A.cy_hi, A.cy_lo}, zoom = {A.zoom_hi, A.zoom_lo};
@@ -2756,89 +2803,72 @@ deep_zoom_kernel(const DeepZoomArgs A)
     const FF pixel_size = dd_mul_sf(zoom, 4.0f / (float)H);          /* :128 */
     const int n_ref = max_iter < ref_iter ? max_iter : ref_iter;
 
-    WaveQueue q;
-    q.init(A.q.heads, A.q.n_blk, (uint32_t)kShardBlock, A.q.run_shift, A.q.run_min, A.q.run_max, lane, A.q.ns_log2);
-    uint32_t begin, count, cur_shard;
-    while (q.next(begin, count, cur_shard)) {
-        for (uint32_t j = begin; j < begin + count; ++j) {
-            const uint32_t blk = WaveQueue::block_of(j / kShardBlock, cur_shard, A.q.ns_log2);
-            if (blk >= A.q.n_blk) continue;
-            const uint32_t sid = blk * kShardBlock + (j % kShardBlock);
-            if (sid >= A.q.n_items) continue;
-            const uint32_t sty = sid / A.q.nsx, stx = sid - sty * A.q.nsx;
-            const int px = (int)stx * FPW + lx;
-            const int lrow = (int)sty * FPH + ly;
-            const bool inside = px < W && lrow < A.rows_local;
-            int py = lrow;
-            if (A.nparts != 1) {
-                const int strip = lrow / A.rows_per_strip;
-                py = (strip * A.nparts + A.part) * A.rows_per_strip + (lrow - strip * A.rows_per_strip);
-            }
-            const float uvx = (float)px / (float)W, uvy = (float)py / (float)H;          /* :118 */
-            const float offset_x = (uvx - 0.5f) * aspect;                               /* :131-132 */
-            const float offset_y = (uvy - 0.5f);
-            const FF dc_x = dd_mul_sf(pixel_size, offset_x), dc_y = dd_mul_sf(pixel_size, offset_y);   /* :135-136 */
-            const FF c_x_dd = dd_add_dd(center_x, dc_x), c_y_dd = dd_add_dd(center_y, dc_y);          /* :139-140 */
-            const float delta_x = dc_x.hi + dc_x.lo, delta_y = dc_y.hi + dc_y.lo;                      /* :143 */
-            const float c_fx = c_x_dd.hi + c_x_dd.lo, c_fy = c_y_dd.hi + c_y_dd.lo;
+    /* no probe limit: this kernel has always probed every shard */
+    walk_subtiles<FPW_LOG2, false>(A.q, A.g, lane, [&](const int px, const int py, const int lrow, const bool inside) {
+        const float uvx = (float)px / (float)W, uvy = (float)py / (float)H;          /* :118 */
+        const float offset_x = (uvx - 0.5f) * aspect;                               /* :131-132 */
+        const float offset_y = (uvy - 0.5f);
+        const FF dc_x = dd_mul_sf(pixel_size, offset_x), dc_y = dd_mul_sf(pixel_size, offset_y);   /* :135-136 */
+        const FF c_x_dd = dd_add_dd(center_x, dc_x), c_y_dd = dd_add_dd(center_y, dc_y);          /* :139-140 */
+        const float delta_x = dc_x.hi + dc_x.lo, delta_y = dc_y.hi + dc_y.lo;                      /* :143 */
+        const float c_fx = c_x_dd.hi + c_x_dd.lo, c_fy = c_y_dd.hi + c_y_dd.lo;
 
-            float dzx = 0.0f, dzy = 0.0f;
-            bool live = inside;
-            int esc_i = max_iter;
-            float ezx = 0.0f, ezy = 0.0f;
-            /* perturbed iteration against the reference orbit, :153-173 */
-            auto perturb = [&](const float2 zr, const int i) {
-                const float mx = zr.x * dzx - zr.y * dzy, my = zr.x * dzy + zr.y * dzx;
-                const float t1x = mx * 2.0f, t1y = my * 2.0f;
-                const float t2x = dzx * dzx - dzy * dzy, t2y = 2.0f * dzx * dzy;
-                const float ndx = t1x + t2x + delta_x, ndy = t1y + t2y + delta_y;
-                if (live) {
-                    dzx = ndx; dzy = ndy;
-                    const float zfx = zr.x + dzx, zfy = zr.y + dzy;
-                    if (zfx * zfx + zfy * zfy > bailout_sq) { live = false; esc_i = i; ezx = zfx; ezy = zfy; }
-                }
-            };
-            /* four reference points per scalar load and per "anybody still alive" test: the orbit comes through
-             * the scalar cache (wave-uniform index), whose latency would otherwise sit in every update */
-            int i = 0;
-            for (; i + 4 <= n_ref; i += 4) {
-                if (__builtin_amdgcn_ballot_w64(live) == 0ull) break;
-                const float2 z0 = A.orbit[i], z1 = A.orbit[i + 1], z2 = A.orbit[i + 2], z3 = A.orbit[i + 3];
-                perturb(z0, i); perturb(z1, i + 1); perturb(z2, i + 2); perturb(z3, i + 3);
+        float dzx = 0.0f, dzy = 0.0f;
+        bool live = inside;
+        int esc_i = max_iter;
+        float ezx = 0.0f, ezy = 0.0f;
+        /* perturbed iteration against the reference orbit, :153-173 */
+        auto perturb = [&](const float2 zr, const int i) {
+            const float mx = zr.x * dzx - zr.y * dzy, my = zr.x * dzy + zr.y * dzx;
+            const float t1x = mx * 2.0f, t1y = my * 2.0f;
+            const float t2x = dzx * dzx - dzy * dzy, t2y = 2.0f * dzx * dzy;
+            const float ndx = t1x + t2x + delta_x, ndy = t1y + t2y + delta_y;
+            if (live) {
+                dzx = ndx; dzy = ndy;
+                const float zfx = zr.x + dzx, zfy = zr.y + dzy;
+                if (zfx * zfx + zfy * zfy > bailout_sq) { live = false; esc_i = i; ezx = zfx; ezy = zfy; }
             }
-            if (__builtin_amdgcn_ballot_w64(live) != 0ull)
-                for (; i < n_ref; ++i) perturb(A.orbit[i], i);
-            /* continue in plain fp32 for the remaining iterations, :181-203 */
-            float zx, zy;
-            if (ref_iter > 0) { const float2 zl = A.orbit[ref_iter - 1]; zx = zl.x + dzx; zy = zl.y + dzy; }
-            else { zx = c_fx; zy = c_fy; }
-            auto plain = [&](const int k) {
-                const float z2x = zx * zx - zy * zy, z2y = 2.0f * zx * zy;
-                const float nx = z2x + c_fx, ny = z2y + c_fy;
-                if (live) {
-                    zx = nx; zy = ny;
-                    if (zx * zx + zy * zy > bailout_sq) { live = false; esc_i = k; ezx = zx; ezy = zy; }
-                }
-            };
-            int k = n_ref;
-            for (; k + 4 <= max_iter; k += 4) {
-                if (__builtin_amdgcn_ballot_w64(live) == 0ull) break;
-                plain(k); plain(k + 1); plain(k + 2); plain(k + 3);
-            }
-            if (__builtin_amdgcn_ballot_w64(live) != 0ull)
-                for (; k < max_iter; ++k) plain(k);
-            if (inside) {
-                float rgb[3] = {0.0f, 0.0f, 0.0f};
-                float smooth = (float)max_iter;
-                if (esc_i < max_iter && !((float)esc_i >= (float)max_iter - 0.5f))      /* :76 */
-                    deep_zoom_color(A, (float)esc_i, ezx, ezy, rgb, smooth);
-                const size_t o = (size_t)(A.out_frame ? py : lrow) * (size_t)W + (size_t)px;
-                if (A.rgba) A.rgba[o] = make_float4(rgb[0], rgb[1], rgb[2], 1.0f);
-                if (A.nu) A.nu[o] = smooth;
-                if (A.iter) A.iter[o] = esc_i;
-            }
+        };
+        /* four reference points per scalar load and per "anybody still alive" test: the orbit comes through
+         * the scalar cache (wave-uniform index), whose latency would otherwise sit in every update */
+        int i = 0;
+        for (; i + 4 <= n_ref; i += 4) {
+            if (__builtin_amdgcn_ballot_w64(live) == 0ull) break;
+            const float2 z0 = A.orbit[i], z1 = A.orbit[i + 1], z2 = A.orbit[i + 2], z3 = A.orbit[i + 3];
+            perturb(z0, i); perturb(z1, i + 1); perturb(z2, i + 2); perturb(z3, i + 3);
         }
-    }
+        if (__builtin_amdgcn_ballot_w64(live) != 0ull)
+            for (; i < n_ref; ++i) perturb(A.orbit[i], i);
+        /* continue in plain fp32 for the remaining iterations, :181-203 */
+        float zx, zy;
+        if (ref_iter > 0) { const float2 zl = A.orbit[ref_iter - 1]; zx = zl.x + dzx; zy = zl.y + dzy; }
+        else { zx = c_fx; zy = c_fy; }
+        auto plain = [&](const int k) {
+            const float z2x = zx * zx - zy * zy, z2y = 2.0f * zx * zy;
+            const float nx = z2x + c_fx, ny = z2y + c_fy;
+            if (live) {
+                zx = nx; zy = ny;
+                if (zx * zx + zy * zy > bailout_sq) { live = false; esc_i = k; ezx = zx; ezy = zy; }
+            }
+        };
+        int k = n_ref;
+        for (; k + 4 <= max_iter; k += 4) {
+            if (__builtin_amdgcn_ballot_w64(live) == 0ull) break;
+            plain(k); plain(k + 1); plain(k + 2); plain(k + 3);
+        }
+        if (__builtin_amdgcn_ballot_w64(live) != 0ull)
+            for (; k < max_iter; ++k) plain(k);
+        if (inside) {
+            float rgb[3] = {0.0f, 0.0f, 0.0f};
+            float smooth = (float)max_iter;
+            if (esc_i < max_iter && !((float)esc_i >= (float)max_iter - 0.5f))      /* :76 */
+                deep_zoom_color(A, (float)esc_i, ezx, ezy, rgb, smooth);
+            const size_t o = plane_index(A.g, px, py, lrow);
+            if (A.rgba) A.rgba[o] = make_float4(rgb[0], rgb[1], rgb[2], 1.0f);
+            if (A.nu) A.nu[o] = smooth;
+            if (A.iter) A.iter[o] = esc_i;
+        }
+    });
 }
 
 /* ---- exports: RGBA f32 -> packed RGB8 / RGB16, flipped (src/vk_engine.cpp:1344-1371, :2054-2073) ---------------------

@@ -31,7 +31,7 @@ struct MandelbulbArgs {
     float brightness, saturation, contrast;
     int32_t max_iter, palette_mode, aa;
     uint32_t flags;
-    int32_t W, H, rows_local, part, nparts, rows_per_strip, out_frame;
+    TileGeom g;
     float4* rgba;
     float* nu;
     int32_t* iter;
@@ -250,8 +250,7 @@ __global__ void __launch_bounds__(kBlockThreads)
 mandelbulb_kernel(const MandelbulbArgs A)
 {
     const uint32_t lane = threadIdx.x & (kWave - 1);
-    const int lx = (int)(lane & 7u), ly = (int)(lane >> 3);
-    const int W = A.W, H = A.H, max_iter = A.max_iter, aa = A.aa;
+    const int W = A.g.W, H = A.g.H, max_iter = A.max_iter, aa = A.aa;
 
     /* the camera, :192-209 (wave-uniform) */
     const float rotation = A.rotation_y + A.rotation_speed * A.time;
@@ -277,79 +276,60 @@ mandelbulb_kernel(const MandelbulbArgs A)
     const float mix_w = 0.3f + 0.3f * sinf(A.time * 0.5f);
     const float faa = (float)aa, half_w = (float)W * 0.5f, half_h = (float)H * 0.5f, fh = (float)H;
 
-    WaveQueue q;
-    q.init(A.q.heads, A.q.n_blk, (uint32_t)kShardBlock, A.q.run_shift, A.q.run_min, A.q.run_max, lane, A.q.ns_log2);
-    q.set_probes(A.q.flags);
-    uint32_t begin, count, cur_shard;
-    while (q.next(begin, count, cur_shard)) {
-        for (uint32_t j = begin; j < begin + count; ++j) {
-            const uint32_t blk = WaveQueue::block_of(j / kShardBlock, cur_shard, A.q.ns_log2);
-            if (blk >= A.q.n_blk) continue;
-            const uint32_t sid = blk * kShardBlock + (j % kShardBlock);
-            if (sid >= A.q.n_items) continue;
-            const uint32_t sty = sid / A.q.nsx, stx = sid - sty * A.q.nsx;
-            const int px = (int)stx * 8 + lx;
-            const int lrow = (int)sty * 8 + ly;
-            const bool inside = px < W && lrow < A.rows_local;
-            int py = lrow;
-            if (A.nparts != 1) {
-                const int strip = lrow / A.rows_per_strip;
-                py = (strip * A.nparts + A.part) * A.rows_per_strip + (lrow - strip * A.rows_per_strip);
-            }
-            float acc[3] = {0.0f, 0.0f, 0.0f};
-            float t0 = 0.0f;
-            int step0 = -1;
-            for (int sy = 0; sy < aa; ++sy) {
-                for (int sx = 0; sx < aa; ++sx) {
-                    const float ux = (((float)px + (float)sx / faa) - half_w) / fh;     /* :203-205 */
-                    const float uy = (((float)py + (float)sy / faa) - half_h) / fh;
-                    float rdx = (fwx + (rtx * ux) * A.fov) + (upx * uy) * A.fov;           /* :209 */
-                    float rdy = (fwy + (rty * ux) * A.fov) + (upy * uy) * A.fov;
-                    float rdz = (fwz + (rtz * ux) * A.fov) + (upz * uy) * A.fov;
-                    {
-                        const float l = sqrtf((rdx * rdx + rdy * rdy) + rdz * rdz);
-                        rdx = rdx / l; rdy = rdy / l; rdz = rdz / l;
-                    }
-                    /* raymarch, :133-167 */
-                    float t = 0.001f, d = 0.0f, escape_iter = 0.0f, pxh = 0.0f, pyh = 0.0f, pzh = 0.0f;
-                    float rgb[3];
-                    int step = -1;
-                    bool marching = inside;
-                    bool hit = false;
-                    for (int i = 0; i < kMbMaxSteps; ++i) {
-                        if (__builtin_amdgcn_ballot_w64(marching) == 0ull) break;
-                        if (!marching) continue;
-                        pxh = rdx * t + rox; pyh = rdy * t + roy; pzh = rdz * t + roz;
-                        d = mb_de(pxh, pyh, pzh, power, max_iter, escape_iter);
-                        if (isnan(d) || isinf(d)) { marching = false; continue; }
-                        const float threshold = mb_max(0.0001f, 0.001f * t);
-                        if (d < threshold) {
-                            marching = false; hit = true; step = i;
-                            if (!kSplit)
-                                mb_shade(A, power, max_iter, pxh, pyh, pzh, rdx, rdy, rdz, t, d, escape_iter, mix_w, rgb);
-                            continue;
-                        }
-                        if (t > kMbMaxDist || d > kMbMaxDist) { marching = false; continue; }
-                        t = t + mb_max(d * 0.5f, 0.0005f);
-                    }
-                    if (kSplit && hit) mb_shade(A, power, max_iter, pxh, pyh, pzh, rdx, rdy, rdz, t, d, escape_iter, mix_w, rgb);
-                    if (!hit) mb_sky(rdy, rgb);
-                    if (sx == 0 && sy == 0) { t0 = t; step0 = step; }
-                    acc[0] = acc[0] + rgb[0]; acc[1] = acc[1] + rgb[1]; acc[2] = acc[2] + rgb[2];   /* :211 */
+    walk_subtiles<3, true>(A.q, A.g, lane, [&](const int px, const int py, const int lrow, const bool inside) {
+        float acc[3] = {0.0f, 0.0f, 0.0f};
+        float t0 = 0.0f;
+        int step0 = -1;
+        for (int sy = 0; sy < aa; ++sy) {
+            for (int sx = 0; sx < aa; ++sx) {
+                const float ux = (((float)px + (float)sx / faa) - half_w) / fh;     /* :203-205 */
+                const float uy = (((float)py + (float)sy / faa) - half_h) / fh;
+                float rdx = (fwx + (rtx * ux) * A.fov) + (upx * uy) * A.fov;           /* :209 */
+                float rdy = (fwy + (rty * ux) * A.fov) + (upy * uy) * A.fov;
+                float rdz = (fwz + (rtz * ux) * A.fov) + (upz * uy) * A.fov;
+                {
+                    const float l = sqrtf((rdx * rdx + rdy * rdy) + rdz * rdz);
+                    rdx = rdx / l; rdy = rdy / l; rdz = rdz / l;
                 }
+                /* raymarch, :133-167 */
+                float t = 0.001f, d = 0.0f, escape_iter = 0.0f, pxh = 0.0f, pyh = 0.0f, pzh = 0.0f;
+                float rgb[3];
+                int step = -1;
+                bool marching = inside;
+                bool hit = false;
+                for (int i = 0; i < kMbMaxSteps; ++i) {
+                    if (__builtin_amdgcn_ballot_w64(marching) == 0ull) break;
+                    if (!marching) continue;
+                    pxh = rdx * t + rox; pyh = rdy * t + roy; pzh = rdz * t + roz;
+                    d = mb_de(pxh, pyh, pzh, power, max_iter, escape_iter);
+                    if (isnan(d) || isinf(d)) { marching = false; continue; }
+                    const float threshold = mb_max(0.0001f, 0.001f * t);
+                    if (d < threshold) {
+                        marching = false; hit = true; step = i;
+                        if (!kSplit)
+                            mb_shade(A, power, max_iter, pxh, pyh, pzh, rdx, rdy, rdz, t, d, escape_iter, mix_w, rgb);
+                        continue;
+                    }
+                    if (t > kMbMaxDist || d > kMbMaxDist) { marching = false; continue; }
+                    t = t + mb_max(d * 0.5f, 0.0005f);
+                }
+                if (kSplit && hit) mb_shade(A, power, max_iter, pxh, pyh, pzh, rdx, rdy, rdz, t, d, escape_iter, mix_w, rgb);
+                if (!hit) mb_sky(rdy, rgb);
+                if (sx == 0 && sy == 0) { t0 = t; step0 = step; }
+                acc[0] = acc[0] + rgb[0]; acc[1] = acc[1] + rgb[1]; acc[2] = acc[2] + rgb[2];   /* :211 */
             }
-            if (!inside) continue;
-            const size_t o = (size_t)(A.out_frame ? py : lrow) * (size_t)W + (size_t)px;
-            if (A.rgba) {
-                const float n = (float)(aa * aa);
-                float rgb[3] = {acc[0] / n, acc[1] / n, acc[2] / n};                     /* :215 */
-                if (A.flags & FR_FLAG_POST_CHAIN) mb_post_chain(rgb, A.brightness, A.saturation, A.contrast);
-                A.rgba[o] = make_float4(rgb[0], rgb[1], rgb[2], 1.0f);
-            }
-            if (A.nu) A.nu[o] = t0;
-            if (A.iter) A.iter[o] = step0;
         }
-    }
+        if (!inside) return;
+        const size_t o = plane_index(A.g, px, py, lrow);
+        if (A.rgba) {
+            const float n = (float)(aa * aa);
+            float rgb[3] = {acc[0] / n, acc[1] / n, acc[2] / n};                     /* :215 */
+            if (A.flags & FR_FLAG_POST_CHAIN) mb_post_chain(rgb, A.brightness, A.saturation, A.contrast);
+            A.rgba[o] = make_float4(rgb[0], rgb[1], rgb[2], 1.0f);
+        }
+        if (A.nu) A.nu[o] = t0;
+        if (A.iter) A.iter[o] = step0;
+    });
 }
 
 }  // namespace fr

@@ -32,7 +32,7 @@ struct PhoenixArgs {
     float brightness, saturation, contrast;
     int32_t max_iter, aa, use_julia;
     uint32_t flags;
-    int32_t W, H, rows_local, part, nparts, rows_per_strip, out_frame;
+    TileGeom g;
     float4* rgba;
     void* nu;
     int32_t* iter;
@@ -150,8 +150,7 @@ __global__ void __launch_bounds__(kBlockThreads)
 phoenix_kernel(const PhoenixArgs A)
 {
     const uint32_t lane = threadIdx.x & (kWave - 1);
-    const int lx = (int)(lane & 7u), ly = (int)(lane >> 3);
-    const int W = A.W, H = A.H, max_iter = A.max_iter;
+    const int W = A.g.W, H = A.g.H, max_iter = A.max_iter;
     const int aa = A.aa > 1 ? A.aa : 1;                                     /* max(int(data3.x), 1), :91 */
     constexpr bool f64 = std::is_same<T, double>::value;
     const T p = (T)A.p, r = (T)A.r;
@@ -163,61 +162,42 @@ phoenix_kernel(const PhoenixArgs A)
     const T sample_offset = ((T)1 / sizex) / (T)aa;                         /* :93-94 */
     const T centre_off = sample_offset * (T)(aa - 1) * (T)0.5;              /* :103, second term */
 
-    WaveQueue q;
-    q.init(A.q.heads, A.q.n_blk, (uint32_t)kShardBlock, A.q.run_shift, A.q.run_min, A.q.run_max, lane, A.q.ns_log2);
-    q.set_probes(A.q.flags);
-    uint32_t begin, count, cur_shard;
-    while (q.next(begin, count, cur_shard)) {
-        for (uint32_t j = begin; j < begin + count; ++j) {
-            const uint32_t blk = WaveQueue::block_of(j / kShardBlock, cur_shard, A.q.ns_log2);
-            if (blk >= A.q.n_blk) continue;
-            const uint32_t sid = blk * kShardBlock + (j % kShardBlock);
-            if (sid >= A.q.n_items) continue;
-            const uint32_t sty = sid / A.q.nsx, stx = sid - sty * A.q.nsx;
-            const int px = (int)stx * 8 + lx;
-            const int lrow = (int)sty * 8 + ly;
-            const bool inside = px < W && lrow < A.rows_local;
-            int py = lrow;
-            if (A.nparts != 1) {
-                const int strip = lrow / A.rows_per_strip;
-                py = (strip * A.nparts + A.part) * A.rows_per_strip + (lrow - strip * A.rows_per_strip);
-            }
-            const T base_u = (T)px / sizex, base_v = (T)py / sizey;        /* :157 */
-            float acc[3] = {0.0f, 0.0f, 0.0f};
-            T nu0 = (T)0;
-            int it0 = 0;
-            for (int sx = 0; sx < aa; ++sx) {
-                for (int sy = 0; sy < aa; ++sy) {
-                    const T ox = (T)sx * sample_offset - centre_off, oy = (T)sy * sample_offset - centre_off;   /* :103 */
-                    const T u = base_u + ox / sizex, v = base_v + oy / sizey;                               /* :104 */
-                    T cx = ctr_x + ((u - (T)0.5) * zoom) * aspect;                                          /* :107-110 */
-                    T cy = ctr_y + (v - (T)0.5) * zoom;
-                    if (A.use_julia) { cx = jcx; cy = jcy; }                                                /* :64-65 */
-                    int esc;
-                    T ezx, ezy;
-                    phoenix_orbit<T>(cx, cy, p, r, max_iter, inside, esc, ezx, ezy);
-                    const T smooth = phoenix_smooth<T>(esc, ezx, ezy, max_iter);
-                    if (sx == 0 && sy == 0) { nu0 = smooth; it0 = esc; }
-                    if (A.rgba) {
-                        float rgb[3];
-                        phoenix_colour((float)(smooth / (T)max_iter), (float)smooth, (float)ezx, (float)ezy,
-                                       A.stripe_density, rgb);
-                        acc[0] = acc[0] + rgb[0]; acc[1] = acc[1] + rgb[1]; acc[2] = acc[2] + rgb[2];   /* :142 */
-                    }
+    walk_subtiles<3, true>(A.q, A.g, lane, [&](const int px, const int py, const int lrow, const bool inside) {
+        const T base_u = (T)px / sizex, base_v = (T)py / sizey;        /* :157 */
+        float acc[3] = {0.0f, 0.0f, 0.0f};
+        T nu0 = (T)0;
+        int it0 = 0;
+        for (int sx = 0; sx < aa; ++sx) {
+            for (int sy = 0; sy < aa; ++sy) {
+                const T ox = (T)sx * sample_offset - centre_off, oy = (T)sy * sample_offset - centre_off;   /* :103 */
+                const T u = base_u + ox / sizex, v = base_v + oy / sizey;                               /* :104 */
+                T cx = ctr_x + ((u - (T)0.5) * zoom) * aspect;                                          /* :107-110 */
+                T cy = ctr_y + (v - (T)0.5) * zoom;
+                if (A.use_julia) { cx = jcx; cy = jcy; }                                                /* :64-65 */
+                int esc;
+                T ezx, ezy;
+                phoenix_orbit<T>(cx, cy, p, r, max_iter, inside, esc, ezx, ezy);
+                const T smooth = phoenix_smooth<T>(esc, ezx, ezy, max_iter);
+                if (sx == 0 && sy == 0) { nu0 = smooth; it0 = esc; }
+                if (A.rgba) {
+                    float rgb[3];
+                    phoenix_colour((float)(smooth / (T)max_iter), (float)smooth, (float)ezx, (float)ezy,
+                                   A.stripe_density, rgb);
+                    acc[0] = acc[0] + rgb[0]; acc[1] = acc[1] + rgb[1]; acc[2] = acc[2] + rgb[2];   /* :142 */
                 }
             }
-            if (!inside) continue;
-            const size_t o = (size_t)(A.out_frame ? py : lrow) * (size_t)W + (size_t)px;
-            if (A.rgba) {
-                const float n = (float)(aa * aa);
-                float rgb[3] = {acc[0] / n, acc[1] / n, acc[2] / n};                                      /* :146 */
-                if (A.flags & FR_FLAG_POST_CHAIN) post_chain(rgb, A.brightness, A.saturation, A.contrast, true);
-                A.rgba[o] = make_float4(rgb[0], rgb[1], rgb[2], 1.0f);
-            }
-            if (A.nu) static_cast<T*>(A.nu)[o] = nu0;
-            if (A.iter) A.iter[o] = it0;
         }
-    }
+        if (!inside) return;
+        const size_t o = plane_index(A.g, px, py, lrow);
+        if (A.rgba) {
+            const float n = (float)(aa * aa);
+            float rgb[3] = {acc[0] / n, acc[1] / n, acc[2] / n};                                      /* :146 */
+            if (A.flags & FR_FLAG_POST_CHAIN) post_chain(rgb, A.brightness, A.saturation, A.contrast, true);
+            A.rgba[o] = make_float4(rgb[0], rgb[1], rgb[2], 1.0f);
+        }
+        if (A.nu) static_cast<T*>(A.nu)[o] = nu0;
+        if (A.iter) A.iter[o] = it0;
+    });
 }
 
 }  // namespace fr

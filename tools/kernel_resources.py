@@ -25,5 +25,5 @@ print(f"{'kernel':84s} {'VGPR':>5s} {'SGPR':>5s} {'sSpill':>6s} {'vSpill':>6s} {
 for name in sorted(usage):
     if any(w in name for w in want):
         u = usage[name]
-        print(f"{name[:84]:84s} {u.get('VGPRs',0):5d} {u.get('SGPRs',0):5d} {u.get('SGPRs Spill',0):6d} {u.get('VGPRs Spill',0):6d} "
+        print(f"{name[:84]:84s} {u.get('VGPRs',0):5d} {u.get('TotalSGPRs',0):5d} {u.get('SGPRs Spill',0):6d} {u.get('VGPRs Spill',0):6d} "
               f"{u.get('ScratchSize [bytes/lane]',0):7d} {u.get('Occupancy [waves/SIMD]',0):4d} {u.get('LDS Size [bytes/block]',0):6d}")

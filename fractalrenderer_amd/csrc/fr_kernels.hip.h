@@ -318,6 +318,12 @@ __device__ __forceinline__ LogTab<T> stage_log2(double2* lds, const LaunchArgs& 
  * pixel).  An empty volatile asm cannot be speculated, so the branch stays a branch. */
 __device__ __forceinline__ void cold_path() { asm volatile("" ::: "memory"); }
 
+/* rank of this lane among the lanes set in a ballot mask */
+__device__ __forceinline__ uint32_t lane_rank(const uint64_t mask)
+{
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+}
+
 /* Correctly rounded a/b from y = RN(1/b) without a divide (Markstein): q = RN(a*y),
  * r = a - b*q exactly (fma), q' = RN(q + r*y).  The host enables this only after checking, for
  * every column and row coordinate of the frame, that q' equals the IEEE quotient. */
@@ -598,9 +604,16 @@ clear_words_kernel(uint32_t* __restrict__ p, const uint32_t n, const Feedback fb
 #ifdef FR_STAMP_TESTED   /* -DFR_STAMP -DFR_STAMP_TESTED: the slots count updates instead of cycles -- 0: updates a lane-pool wave ran
                           * TESTED, 2: updates of its dirty unchecked stretches (FR_CLOCK_GHZ=0.001 tools/stamps.py prints counts) */
 #define FR_STAMP_END(k) do {} while (0)
+#define FR_STAMP_TIMED(k, call) (call)
+#define FR_STAMP_COUNT(k, n) do { st_acc[k] += (n); } while (0)
 #else
 #define FR_STAMP_END(k) do { st_acc[k] += __builtin_amdgcn_s_memtime() - st_t; } while (0)
+/* the value of `call`, the cycles it took added to slot k */
+#define FR_STAMP_TIMED(k, call) ({ const uint64_t st0_ = __builtin_amdgcn_s_memtime(); const auto r_ = (call); \
+        st_acc[k] += __builtin_amdgcn_s_memtime() - st0_; r_; })
+#define FR_STAMP_COUNT(k, n) do { (void)(n); } while (0)
 #endif
+#define FR_STAMP_SET(k, v) do { st_acc[k] = (v); } while (0)
 #define FR_STAMP_WRITE(A, lane) do { if ((A).diag && (lane) == 0) { uint64_t* d_ = (A).diag + (size_t)(blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6)) * 8 + 4; \
         d_[0] = st_acc[0]; d_[1] = st_acc[1]; d_[2] = st_acc[2]; d_[3] = st_acc[3]; } } while (0)
 constexpr int kDiagWords = 8;
@@ -608,6 +621,9 @@ constexpr int kDiagWords = 8;
 #define FR_STAMP_DECL
 #define FR_STAMP_BEGIN() do {} while (0)
 #define FR_STAMP_END(k) do {} while (0)
+#define FR_STAMP_TIMED(k, call) (call)
+#define FR_STAMP_COUNT(k, n) do { (void)(n); } while (0)
+#define FR_STAMP_SET(k, v) do {} while (0)
 #define FR_STAMP_WRITE(A, lane) do {} while (0)
 constexpr int kDiagWords = 4;
 #endif
@@ -880,7 +896,7 @@ struct RingWriter {
         if (m == 0ull) return;
         const uint32_t n = (uint32_t)__builtin_popcountll(m);
         if (keep) {
-            const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+            const uint32_t rank = lane_rank(m);
             const uint32_t slot = (tail + rank) & (kRingSlots - 1);
             ring->pix[slot] = pixel;
             ring->it[slot] = done;
@@ -925,6 +941,8 @@ struct RingWriter {
 template <typename T>
 struct Orbit {
     T X, Yd, cx, cyd, x2, y2d;
+    /* park at the fixed point z = 0 of c = 0: never "escapes" again */
+    __device__ __forceinline__ void park() { X = T(0); Yd = T(0); cx = T(0); cyd = T(0); x2 = T(0); y2d = T(0); }
 };
 
 /* ABS (Burning Ship, shaders/burning_ship.comp:241-245): z = abs(z) before the square only changes
@@ -1002,7 +1020,7 @@ __device__ __forceinline__ void escape_run(Orbit<T>& o, const T B2, const int i0
         const bool hit = o.X == refX && o.Yd == refYd;       /* finished lanes sit at 0 == 0: masked by `done` */
         const uint64_t hm = __builtin_amdgcn_ballot_w64(hit) & ~done;
         if (hm != 0ull) {
-            if (hit) { o.X = T(0); o.Yd = T(0); o.cx = T(0); o.cyd = T(0); o.x2 = T(0); o.y2d = T(0); }
+            if (hit) o.park();
             done |= hm;
             snap_closed += (uint32_t)__builtin_popcountll(hm);
         }
@@ -1043,8 +1061,7 @@ __device__ __forceinline__ void escape_run(Orbit<T>& o, const T B2, const int i0
                 if (e) {
                     esc_i = i;
                     esc_r2 = T(0.25) * r2x4;
-                    /* park at the fixed point z = 0 of c = 0: never "escapes" again */
-                    o.X = T(0); o.Yd = T(0); o.cx = T(0); o.cyd = T(0); o.x2 = T(0); o.y2d = T(0);
+                    o.park();
                 }
                 done |= em;
                 if (done == ~0ull) end = i;      /* single-exit loop: everybody finished -> this was the last update */
@@ -1179,12 +1196,13 @@ template <int FRACTAL> struct Form {
     static constexpr bool per_sample_c = FRACTAL != 1;
 };
 
-__device__ __forceinline__ void diag_write(const LaunchArgs& A, uint32_t lane, uint64_t t0, uint32_t items, uint32_t claims)
+/* dry: when the wave found its queue dry, in ticks since t0 (the lane pool; packed above the dequeue count) */
+__device__ __forceinline__ void diag_write(const LaunchArgs& A, uint32_t lane, uint64_t t0, uint32_t items, uint32_t claims, uint32_t dry = 0u)
 {
     if (A.diag && lane == 0) {      /* diagnostics: per-wave timeline (100 MHz ticks) and work counts */
         const uint32_t wave_id = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
         uint64_t* d = A.diag + (size_t)wave_id * kDiagWords;
-        d[0] = t0; d[1] = __builtin_amdgcn_s_memrealtime(); d[2] = items; d[3] = claims;
+        d[0] = t0; d[1] = __builtin_amdgcn_s_memrealtime(); d[2] = items; d[3] = (uint64_t)claims | ((uint64_t)dry << 32);
     }
 }
 
@@ -1456,9 +1474,7 @@ tile_kernel(const LaunchArgs A)
     }
     if (staged) writer.finish();
     diag_write(A, (uint32_t)lane, diag_t0, diag_items, diag_claims);
-#ifdef FR_STAMP
-    st_acc[1] = writer.st_block;
-#endif
+    FR_STAMP_SET(1, writer.st_block);
     FR_STAMP_WRITE(A, lane);
 }
 
@@ -1922,7 +1938,7 @@ struct LeanWriter {
         const uint64_t m = __builtin_amdgcn_ballot_w64(keep);
         if (m == 0ull) return;
         if (keep) {
-            const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+            const uint32_t rank = lane_rank(m);
             const uint32_t slot = (tail + rank) & (kRingSlots - 1);
             ring->pix[slot] = pixel;
             ring->it[slot] = done;
@@ -2134,9 +2150,7 @@ tile_lean_kernel(const LaunchArgs A)
             d[0] = diag_t0; d[1] = __builtin_amdgcn_s_memrealtime(); d[2] = diag_items; d[3] = diag_claims;
         }
     }
-#ifdef FR_STAMP
-    st_acc[1] = writer.st_block;
-#endif
+    FR_STAMP_SET(1, writer.st_block);
     FR_STAMP_WRITE(A, lane);
 }
 
@@ -2173,9 +2187,22 @@ struct DeferRing {
     uint32_t pix[kDeferSlots];
     int32_t i0[kDeferSlots];             /* index of the stretch's first update in the sample's own count */
     T f[NF][kDeferSlots];                /* X, Yd (, cx, cyd) at the stretch's start */
+
+    /* the lanes of `badm` (this lane: `bad`) queue their sample from entry `tail` on: pixel, index i0 of the stretch's first
+     * update, z at the stretch's start and the lane's c.  Returns how many entries that made */
+    __device__ __forceinline__ uint32_t push(const uint32_t tail, const uint64_t badm, const bool bad, const uint32_t pixel,
+                                             const int at, const T sX, const T sYd, const Orbit<T>& o)
+    {
+        if (bad) {
+            const uint32_t slot = (tail + lane_rank(badm)) & (uint32_t)(kDeferSlots - 1);
+            pix[slot] = pixel; i0[slot] = at;
+            f[0][slot] = sX; f[1][slot] = sYd;
+            if constexpr (NF == 4) { f[2][slot] = o.cx; f[3][slot] = o.cyd; }
+        }
+        return (uint32_t)__builtin_popcountll(badm);
+    }
 };
 
-template <typename T>
 __device__ __forceinline__ uint32_t wave_min_u32(uint32_t v)
 {
 #pragma unroll
@@ -2185,6 +2212,109 @@ __device__ __forceinline__ uint32_t wave_min_u32(uint32_t v)
     }
     return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
 }
+
+/* colour stage of one finished sample and its stores.  eX, eYd: the sample's z after its last update (STRIPES) */
+template <typename T, int FRACTAL>
+__device__ __forceinline__ void shade_and_store(const LdsBlock& S, const LogTab<T>& lg, const uint32_t pix, const int it, const T r2,
+                                                const T eX, const T eYd, const bool want_nu, const bool want_rgb)
+{
+    constexpr int FR = FRACTAL == 3 ? 0 : FRACTAL;
+    T nu;
+    float rgb[3];
+    if constexpr (FRACTAL == 3) shade_stripes<T>(*kargs(), S, it, eX, T(0.5) * eYd, nu, rgb);
+    else shade<T, FR>(*kargs(), S, lg, it, r2, want_nu, want_rgb, nu, rgb);
+    KArgs K = kargs();
+    if (want_rgb && (K->flags & FR_FLAG_POST_CHAIN))
+        post_chain(rgb, S.brightness, S.saturation, S.contrast, FR != 0);
+    if (K->rgba) K->rgba[pix] = make_float4(rgb[0], rgb[1], rgb[2], 1.0f);
+    if (K->nu) reinterpret_cast<T*>(K->nu)[pix] = nu;
+    if (K->iter) K->iter[pix] = it;
+}
+
+/* diagnostic build (-DFR_STAMP): the records must have arrived before the clock is read: touch them */
+template <typename T>
+__device__ __forceinline__ void stamp_await_records(const Orbit<T>& o)
+{
+#ifdef FR_STAMP
+    const T touch = o.X + o.Yd + o.cx + o.cyd;
+    asm volatile("" :: "v"(touch));
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#endif
+}
+
+/* diagnostic build (-DFR_WATCHDOG_DUMP, tools/watchdog_probe.py): the first wave whose watchdog fires leaves its bookkeeping
+ * in diag[0..14] and two words per lane in diag[16..79] and diag[80..143] */
+__device__ __forceinline__ void watchdog_dump(const LaunchArgs& A, const uint32_t lane, const uint64_t (&head)[15],
+                                              const uint64_t lane_sample, const uint64_t lane_flags)
+{
+#ifdef FR_WATCHDOG_DUMP
+    if (A.diag) {
+        uint64_t first = 1;
+        if (lane == 0) first = atomicAdd((unsigned long long*)&A.diag[15], 1ull);
+        first = __builtin_amdgcn_readfirstlane((int)first);
+        if (first == 0) {
+            if (lane == 0) for (int k = 0; k < 15; ++k) A.diag[k] = head[k];
+            A.diag[16 + lane] = lane_sample; A.diag[80 + lane] = lane_flags;
+        }
+    }
+#endif
+}
+
+/* what one lane of the pool holds: its sample, and the result it waits to have shaded and stored */
+template <typename T, int FRACTAL>
+struct PoolLane {
+    static constexpr int NF = RecFields<FRACTAL>::n;
+    uint32_t pixel;                      /* kInvalidPixel: lane is free */
+    uint32_t fin;                        /* 1: finished, waiting to be shaded and stored (a VGPR flag, not a
+                                          * lane mask: a divergent bool carried through the iteration loops costs
+                                          * mask-merging scalar instructions in every iteration) */
+    Orbit<T> o;
+    uint32_t deadline;
+    int esc_i;
+    T esc_r2;
+    T esc_X, esc_Yd;                     /* STRIPES: z after the lane's last update (escape, or its max_iter-th) */
+
+    __device__ __forceinline__ void init()
+    {
+        pixel = kInvalidPixel; fin = 0u; deadline = 0u; esc_i = 0; esc_r2 = T(0); esc_X = T(0); esc_Yd = T(0);
+        o.X = o.Yd = o.cx = o.cyd = o.x2 = o.y2d = T(0);
+    }
+    __device__ __forceinline__ bool idle() const { return pixel == kInvalidPixel; }
+    __device__ __forceinline__ bool running() const { return pixel != kInvalidPixel && fin == 0u; }
+    /* the sample's own count of the update the wave runs at clock `wclock`, for a sample of `span` updates in all */
+    __device__ __forceinline__ int index_at(const uint32_t wclock, const uint32_t span) const { return (int)(wclock - (deadline - span)); }
+    /* KEEP_Z (STRIPES, at the deadline): z after exactly max_iter updates */
+    template <bool KEEP_Z = false>
+    __device__ __forceinline__ void finish_interior(const int max_iter)
+    {
+        if constexpr (KEEP_Z) { esc_X = o.X; esc_Yd = o.Yd; }
+        esc_i = max_iter; esc_r2 = T(0); fin = 1u; o.park();
+    }
+    __device__ __forceinline__ void finish_escaped(const int idx, const T r2x4)
+    {
+        if constexpr (FRACTAL == 3) { esc_X = o.X; esc_Yd = o.Yd; }
+        esc_i = idx; esc_r2 = T(0.25) * r2x4; fin = 1u; o.park();
+    }
+    /* refill: record l of block j of region `shard` of the survivor stream (an empty slot of the block leaves the lane
+     * idle).  Returns whether the lane has a sample now */
+    __device__ __forceinline__ bool load_record(const LdsBlock& S, const uint32_t shard, const uint32_t j, const uint32_t l,
+                                                const uint32_t wclock, const int max_iter)
+    {
+        KArgs K = kargs();
+        const uint8_t* b = K->in.base + ((size_t)shard * K->in.region_blocks + j) * RingWriter<T, NF>::kBlockBytes;
+        const T* fields = reinterpret_cast<const T*>(b + RingWriter<T, NF>::kHeaderBytes);
+        const uint32_t pix = reinterpret_cast<const uint32_t*>(b)[l];
+        if (pix == kInvalidPixel) return false;
+        pixel = pix;
+        const uint32_t done = reinterpret_cast<const uint32_t*>(b)[64 + l];
+        o.X = fields[l]; o.Yd = fields[64 + l];
+        if constexpr (Form<FRACTAL>::per_sample_c) { o.cx = fields[128 + l]; o.cyd = fields[192 + l]; }
+        else { o.cx = (T)S.julia_cx; o.cyd = T(2) * (T)S.julia_cy; }
+        o.x2 = o.X * o.X; o.y2d = o.Yd * o.Yd;
+        deadline = wclock + ((uint32_t)max_iter - done);
+        return true;
+    }
+};
 
 /* Lanes are refilled with survivor records of the tile pass (A.in) and run the remaining iterations [A.i0, max_iter).
  * (A fresh-pixel form of this kernel -- lanes refilled straight from the pixel index, no tile pass -- was the first lane
@@ -2198,7 +2328,6 @@ __global__ void __launch_bounds__(kBlockThreads)
 pool_kernel(const LaunchArgs A)
 {
     constexpr int NF = RecFields<FRACTAL>::n;
-    constexpr size_t kBlockBytes = RingWriter<T, NF>::kBlockBytes;
     constexpr bool STRIPES = FRACTAL == 3;                /* Mandelbrot + stripe shading (shade_stripes): a finished lane keeps the
                                                            * z of its last update, and no lane runs past its deadline */
     constexpr int FR = STRIPES ? 0 : FRACTAL;
@@ -2233,17 +2362,9 @@ pool_kernel(const LaunchArgs A)
     uint32_t diag_items = 0, diag_claims = 0, diag_dry = 0;
     if (A.diag) diag_t0 = __builtin_amdgcn_s_memrealtime();
 
-    /* per-lane state */
-    uint32_t pixel = kInvalidPixel;      /* kInvalidPixel: lane is free */
-    uint32_t fin = 0;                    /* 1: finished, waiting to be shaded and stored (a VGPR flag, not a
-                                          * lane mask: a divergent bool carried through the iteration loops costs
-                                          * mask-merging scalar instructions in every iteration) */
-    Orbit<T> o;
-    o.X = o.Yd = o.cx = o.cyd = o.x2 = o.y2d = T(0);
-    uint32_t deadline = 0;
-    int esc_i = 0;
-    T esc_r2 = T(0);
-    T esc_X = T(0), esc_Yd = T(0);       /* STRIPES: z after the lane's last update (escape, or its max_iter-th) */
+    PoolLane<T, FRACTAL> L;
+    L.init();
+    Orbit<T>& o = L.o;
     /* PERIOD: the lane's own state at the last snapshot (NaN: none since its refill) and "it came back to it" */
     T refX = __builtin_nan(""), refYd = __builtin_nan("");
     uint32_t cyc = 0;
@@ -2300,26 +2421,13 @@ pool_kernel(const LaunchArgs A)
                 pending &= ~__builtin_amdgcn_ballot_w64(e);
                 ++k;
             } while (pending != 0ull && k < (uint32_t)max_iter);
-#ifdef FR_STAMP_TESTED
-            st_acc[3] += k;              /* diagnostic: updates of deferred replays */
-#endif
+            FR_STAMP_COUNT(3, k);        /* diagnostic: updates of deferred replays */
             if (have) {
                 /* an escape at or past the sample's last update is no escape: it ran its max_iter updates */
                 const int idx = ri0 + (int)ek;
                 const bool esc = !open && idx < max_iter;
-                const int r_it = esc ? idx : max_iter;
-                const T r_r2 = esc ? T(0.25) * er : T(0);
-                T nu;
-                float rgb[3];
                 /* (STRIPES: a stretch never crosses a deadline, so a deferred lane did escape before its max_iter-th update) */
-                if constexpr (STRIPES) shade_stripes<T>(*kargs(), S, r_it, eX, T(0.5) * eYd, nu, rgb);
-                else shade<T, FR>(*kargs(), S, lg, r_it, r_r2, want_nu, want_rgb, nu, rgb);
-                KArgs K = kargs();
-                if (want_rgb && (K->flags & FR_FLAG_POST_CHAIN))
-                    post_chain(rgb, S.brightness, S.saturation, S.contrast, FR != 0);
-                if (K->rgba) K->rgba[rpix] = make_float4(rgb[0], rgb[1], rgb[2], 1.0f);
-                if (K->nu) reinterpret_cast<T*>(K->nu)[rpix] = nu;
-                if (K->iter) K->iter[rpix] = r_it;
+                shade_and_store<T, FRACTAL>(S, lg, rpix, esc ? idx : max_iter, esc ? T(0.25) * er : T(0), eX, eYd, want_nu, want_rgb);
             }
             dhead += count;
             __builtin_amdgcn_wave_barrier();
@@ -2327,48 +2435,30 @@ pool_kernel(const LaunchArgs A)
         if (finishing) break;
         /* ---- retire: shade and store the finished lanes ---- */
         FR_STAMP_BEGIN();
-        const uint64_t finm = __builtin_amdgcn_ballot_w64(fin != 0u);
+        const uint64_t finm = __builtin_amdgcn_ballot_w64(L.fin != 0u);
         if (finm != 0ull) {
             if (PERIOD && ever_closed) {
                 /* lifetime of (the first of) the lanes retired now: its deadline was set to refill clock + remaining updates.
                  * (Read with the lane's number, in uniform control flow: a readfirstlane inside the divergent block below
                  * left the wave running on with the retiring lanes' EXEC mask -- the rest of the loop saw 17 lanes.) */
-                const uint32_t life = (uint32_t)__builtin_amdgcn_readlane((int)(wclock - (deadline - ((uint32_t)max_iter - (uint32_t)A.i0))),
+                const uint32_t life = (uint32_t)__builtin_amdgcn_readlane(L.index_at(wclock, (uint32_t)max_iter - (uint32_t)A.i0),
                                                                           (int)__builtin_ctzll(finm));
                 life_avg = life_avg == 0u ? life : (3u * life_avg + life) >> 2;
             }
-            if (fin != 0u) {
-                T nu;
-                float rgb[3];
-                if constexpr (STRIPES) shade_stripes<T>(*kargs(), S, esc_i, esc_X, T(0.5) * esc_Yd, nu, rgb);
-                else shade<T, FR>(*kargs(), S, lg, esc_i, esc_r2, want_nu, want_rgb, nu, rgb);
-                KArgs K = kargs();
-                if (want_rgb && (K->flags & FR_FLAG_POST_CHAIN))
-                    post_chain(rgb, S.brightness, S.saturation, S.contrast, FR != 0);
-                if (K->rgba) K->rgba[pixel] = make_float4(rgb[0], rgb[1], rgb[2], 1.0f);
-                if (K->nu) reinterpret_cast<T*>(K->nu)[pixel] = nu;
-                if (K->iter) K->iter[pixel] = esc_i;
-                pixel = kInvalidPixel;
-                fin = 0u;
+            if (L.fin != 0u) {
+                shade_and_store<T, FRACTAL>(S, lg, L.pixel, L.esc_i, L.esc_r2, L.esc_X, L.esc_Yd, want_nu, want_rgb);
+                L.pixel = kInvalidPixel;
+                L.fin = 0u;
             }
         }
         FR_STAMP_END(3);
         /* ---- refill the free lanes from the reserve ---- */
         FR_STAMP_BEGIN();
         for (;;) {
-            const uint64_t freem = __builtin_amdgcn_ballot_w64(pixel == kInvalidPixel);
+            const uint64_t freem = __builtin_amdgcn_ballot_w64(L.idle());
             if (freem == 0ull || dry) break;
             if (res_next == res_count * 64u) {
-#ifdef FR_STAMP
-                const uint64_t stq = __builtin_amdgcn_s_memtime();
-                const bool got_q = q.next<true>(lane, res_begin, res_count, res_shard);
-#ifndef FR_STAMP_TESTED
-                st_acc[0] += __builtin_amdgcn_s_memtime() - stq;
-#endif
-                if (!got_q) {
-#else
-                if (!q.next<true>(lane, res_begin, res_count, res_shard)) {
-#endif
+                if (!FR_STAMP_TIMED(0, q.next<true>(lane, res_begin, res_count, res_shard))) {
                     dry = true;
                     /* diagnostics: when this wave found the queue dry, in 100 MHz ticks since its start (bits 32..) */
                     diag_dry = A.diag ? (uint32_t)(__builtin_amdgcn_s_memrealtime() - diag_t0) : 0u;
@@ -2381,43 +2471,20 @@ pool_kernel(const LaunchArgs A)
             const uint32_t nfree = (uint32_t)__builtin_popcountll(freem);
             const uint32_t avail = res_count * 64u - res_next;
             const uint32_t n = nfree < avail ? nfree : avail;
-            if (pixel == kInvalidPixel) {
-                const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(freem >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)freem, 0u));
+            if (L.idle()) {
+                const uint32_t rank = lane_rank(freem);
                 if (rank < n) {
                     const uint32_t t = res_next + rank;
-                    const uint32_t j = res_begin + (t >> 6), l = t & 63u;
-                    {
-                        /* record l of block j of region res_shard */
-                        KArgs K = kargs();
-                        const uint8_t* b = K->in.base + ((size_t)res_shard * K->in.region_blocks + j) * kBlockBytes;
-                        const T* fields = reinterpret_cast<const T*>(b + RingWriter<T, NF>::kHeaderBytes);
-                        const uint32_t pix = reinterpret_cast<const uint32_t*>(b)[l];
-                        if (pix != kInvalidPixel) {
-                            pixel = pix;
-                            const uint32_t done = reinterpret_cast<const uint32_t*>(b)[64 + l];
-                            o.X = fields[l];
-                            o.Yd = fields[64 + l];
-                            if constexpr (Form<FRACTAL>::per_sample_c) { o.cx = fields[128 + l]; o.cyd = fields[192 + l]; }
-                            else { o.cx = (T)S.julia_cx; o.cyd = T(2) * (T)S.julia_cy; }
-                            o.x2 = o.X * o.X;
-                            o.y2d = o.Yd * o.Yd;
-                            deadline = wclock + ((uint32_t)max_iter - done);
-                            if constexpr (PERIOD) { refX = __builtin_nan(""); refYd = refX; cyc = 0u; }
-                        }
+                    if (L.load_record(S, res_shard, res_begin + (t >> 6), t & 63u, wclock, max_iter)) {
+                        if constexpr (PERIOD) { refX = __builtin_nan(""); refYd = refX; cyc = 0u; }
                     }
                 }
             }
             res_next += n;
         }
-#ifdef FR_STAMP
-        {   /* the records must have arrived before the clock is read: touch them */
-            const T touch = o.X + o.Yd + o.cx + o.cyd;
-            asm volatile("" :: "v"(touch));
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-#endif
+        stamp_await_records(o);
         FR_STAMP_END(2);
-        const uint64_t active = __builtin_amdgcn_ballot_w64(pixel != kInvalidPixel);
+        const uint64_t active = __builtin_amdgcn_ballot_w64(!L.idle());
         if (active == 0ull) { finishing = true; continue; }  /* queue dry and every lane retired: flush the ring, leave */
         const uint32_t nactive = (uint32_t)__builtin_popcountll(active);
         /* a wave that can no longer refill is on the critical path of the launch: give it issue priority */
@@ -2452,16 +2519,12 @@ pool_kernel(const LaunchArgs A)
         uint32_t newly = 0;
         /* lanes whose deadline is reached are interior; then find the next earliest deadline */
         auto reach_deadline = [&](bool at_or_past) {
-            const bool running = pixel != kInvalidPixel && fin == 0u;
-            const bool hit = running && (at_or_past ? (int32_t)(wclock - deadline) >= 0 : deadline == wclock);
-            if (hit) {
-                esc_i = max_iter; esc_r2 = T(0); fin = 1u;
-                if constexpr (STRIPES) { esc_X = o.X; esc_Yd = o.Yd; }          /* z after exactly max_iter updates */
-                o.X = T(0); o.Yd = T(0); o.cx = T(0); o.cyd = T(0); o.x2 = T(0); o.y2d = T(0);
-            }
+            const bool running = L.running();
+            const bool hit = running && (at_or_past ? (int32_t)(wclock - L.deadline) >= 0 : L.deadline == wclock);
+            if (hit) L.template finish_interior<STRIPES>(max_iter);
             const uint32_t nhit = (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(hit));
             newly += nhit;
-            const uint32_t rel = wave_min_u32<T>((running && !hit) ? deadline - wclock : 0xFFFFFFFFu);
+            const uint32_t rel = wave_min_u32((running && !hit) ? L.deadline - wclock : 0xFFFFFFFFu);
             have_running = rel != 0xFFFFFFFFu;
             next_deadline = wclock + (have_running ? rel : (uint32_t)max_iter);
         };
@@ -2484,13 +2547,10 @@ pool_kernel(const LaunchArgs A)
          * the stride is forgotten and learned again.  Any equality is a proof, whatever the stride: only WHEN a cycle
          * is seen changes, never a pixel. */
         auto close_cycles = [&](const uint32_t hit_off) {
-            const bool running = pixel != kInvalidPixel && fin == 0u;
+            const bool running = L.running();
             const bool hit = running && cyc != 0u;
             if (__builtin_amdgcn_ballot_w64(hit) != 0ull) {
-                if (hit) {
-                    esc_i = max_iter; esc_r2 = T(0); fin = 1u; cyc = 0u;
-                    o.X = T(0); o.Yd = T(0); o.cx = T(0); o.cyd = T(0); o.x2 = T(0); o.y2d = T(0);
-                }
+                if (hit) { L.finish_interior(max_iter); cyc = 0u; }
                 const uint32_t nhit = (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(hit));
                 newly += nhit;
                 snap_closed += nhit;
@@ -2560,36 +2620,22 @@ pool_kernel(const LaunchArgs A)
         while (newly < goal) {
             if ((int32_t)(wclock - watchdog) > 0) {
                 if (lane == 0 && A.out.overflow) __hip_atomic_store(A.out.overflow, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-#ifdef FR_WATCHDOG_DUMP
-                if (A.diag) {
-                    uint64_t first = 1;
-                    if (lane == 0) first = atomicAdd((unsigned long long*)&A.diag[15], 1ull);
-                    first = __builtin_amdgcn_readfirstlane((int)first);
-                    if (first == 0) {
-                        if (lane == 0) {
-                            A.diag[0] = wclock; A.diag[1] = next_deadline; A.diag[2] = have_running; A.diag[3] = goal; A.diag[4] = newly;
-                            A.diag[5] = nactive; A.diag[6] = stride; A.diag[7] = fast; A.diag[8] = watchdog; A.diag[9] = snap_window;
-                            A.diag[10] = next_snap; A.diag[11] = dry; A.diag[12] = life_avg; A.diag[13] = refill_at; A.diag[14] = (uint64_t)max_iter | ((uint64_t)A.i0 << 32);
-                        }
-                        A.diag[16 + lane] = ((uint64_t)pixel << 32) | (uint64_t)(uint32_t)(deadline - wclock);
-                        A.diag[80 + lane] = ((uint64_t)fin << 32) | (uint64_t)cyc;
-                    }
-                }
-#endif
-                if (pixel != kInvalidPixel && fin == 0u) {
-                    esc_i = max_iter; esc_r2 = T(0); fin = 1u;
-                    o.X = T(0); o.Yd = T(0); o.cx = T(0); o.cyd = T(0); o.x2 = T(0); o.y2d = T(0);
-                }
+                watchdog_dump(A, lane,
+                              {wclock, next_deadline, have_running, goal, newly, nactive, stride, fast, watchdog, snap_window, next_snap,
+                               dry, life_avg, refill_at, (uint64_t)max_iter | ((uint64_t)A.i0 << 32)},
+                              ((uint64_t)L.pixel << 32) | (uint64_t)(uint32_t)(L.deadline - wclock), ((uint64_t)L.fin << 32) | (uint64_t)cyc);
+                if (L.running()) L.finish_interior(max_iter);
                 break;
             }
-            if (fast) {
-                if constexpr (STRIPES) {
-                    /* where the z of a sample that never escapes is read (striped interior, style 0) no stretch may cross a
-                     * deadline: that z must be the one after exactly max_iter updates.  Within the longest stretch (64 updates)
-                     * of the earliest deadline the wave runs tested blocks, which stop at it */
-                    if (A.stripe_enabled && A.interior_style == 0 &&
-                        (uint32_t)(next_deadline - wclock) < 4u * (uint32_t)kFastBlock) goto tested_stretch;
-                }
+            bool unchecked = fast;
+            if constexpr (STRIPES) {
+                /* where the z of a sample that never escapes is read (striped interior, style 0) no stretch may cross a
+                 * deadline: that z must be the one after exactly max_iter updates.  Within the longest stretch (64 updates)
+                 * of the earliest deadline the wave runs tested blocks, which stop at it */
+                unchecked = fast && !(A.stripe_enabled && A.interior_style == 0 &&
+                                      (uint32_t)(next_deadline - wclock) < 4u * (uint32_t)kFastBlock);
+            }
+            if (unchecked) {
                 const T sX = o.X, sYd = o.Yd;
                 /* after 2 (6) clean stretches in a row the wave runs 2 (4) blocks per snapshot / test (a half, a
                  * quarter of that overhead on the long interior runs that dominate deep views); a dirty one resets it */
@@ -2632,26 +2678,14 @@ pool_kernel(const LaunchArgs A)
                 if (badm != 0ull) {
                     /* dirty stretch: the escaped lanes' stretch-start states go to the ring (located 64 at a time, see
                      * DeferRing), the lanes are free; everybody else's progress counts and the wave stays unchecked */
-                    if (bad) {
-                        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(badm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)badm, 0u));
-                        const uint32_t slot = (dtail + rank) & (uint32_t)(kDeferSlots - 1);
-                        D.pix[slot] = pixel;
-                        D.i0[slot] = (int)(wclock - (deadline - (uint32_t)max_iter));
-                        D.f[0][slot] = sX;
-                        D.f[1][slot] = sYd;
-                        if constexpr (Form<FRACTAL>::per_sample_c) { D.f[2][slot] = o.cx; D.f[3][slot] = o.cyd; }
-                        pixel = kInvalidPixel;
-                        o.X = T(0); o.Yd = T(0); o.cx = T(0); o.cyd = T(0); o.x2 = T(0); o.y2d = T(0);
-                    }
-                    const uint32_t nbad = (uint32_t)__builtin_popcountll(badm);
+                    const uint32_t nbad = D.push(dtail, badm, bad, L.pixel, L.index_at(wclock, (uint32_t)max_iter), sX, sYd, o);
+                    if (bad) { L.pixel = kInvalidPixel; o.park(); }
                     dtail += nbad;
                     newly += nbad;
                     streak = 0;
                     ring_full = dtail - dhead >= 64u;
                     __builtin_amdgcn_wave_barrier();
-#ifdef FR_STAMP_TESTED
-                    st_acc[2] += len;        /* diagnostic: updates of dirty unchecked stretches */
-#endif
+                    FR_STAMP_COUNT(2, len);  /* diagnostic: updates of dirty unchecked stretches */
                 } else {
                     ++streak;
                 }
@@ -2667,7 +2701,6 @@ pool_kernel(const LaunchArgs A)
                 if (ring_full) break;        /* 64 deferred escapes queued: replay them (top of the loop) before more arrive */
                 continue;
             }
-        tested_stretch:
             /* tested stretch: up to the next deadline, at most one block.  The loop carries a countdown and
              * one vector-compare branch; goal and deadline are only looked at where they can change (on an
              * escape event / after the stretch).  On escape-dense views such as the C3 Julia dust the scalar
@@ -2684,30 +2717,20 @@ pool_kernel(const LaunchArgs A)
                 const uint64_t em = __builtin_amdgcn_ballot_w64(e);
                 ++k;
                 if (em != 0ull) {
-                    if (e) {
-                        esc_i = (int)(wclock + k - 1u - (deadline - (uint32_t)max_iter));
-                        esc_r2 = T(0.25) * r2x4;
-                        fin = 1u;
-                        if constexpr (STRIPES) { esc_X = o.X; esc_Yd = o.Yd; }
-                        o.X = T(0); o.Yd = T(0); o.cx = T(0); o.cyd = T(0); o.x2 = T(0); o.y2d = T(0);
-                    }
+                    if (e) L.finish_escaped(L.index_at(wclock + k - 1u, (uint32_t)max_iter), r2x4);
                     newly += (uint32_t)__builtin_popcountll(em);
                     escaped = true;
                     if (newly >= goal) n = k;        /* single-exit loop: goal reached -> this was the last update */
                 }
             }
             wclock += k;
-#ifdef FR_STAMP_TESTED
-            st_acc[0] += k;              /* diagnostic: updates this wave ran TESTED */
-#endif
+            FR_STAMP_COUNT(0, k);        /* diagnostic: updates this wave ran TESTED */
             clean = escaped ? 0u : clean + k;
             if (wclock == next_deadline) reach_deadline(false);
             /* back to unchecked blocks after a block's worth of updates without an escape */
             if (clean >= (uint32_t)kFastBlock) { fast = fast_ok; clean = 0; }
         }
-#ifdef FR_STAMP
-        st_acc[1] = wclock;          /* pool: updates this wave has run (x 64 lanes = the lane-updates it paid for) */
-#endif
+        FR_STAMP_SET(1, wclock);     /* pool: updates this wave has run (x 64 lanes = the lane-updates it paid for) */
     }
     if constexpr (PERIOD) {
         if (lane == 0 && A.closed_flag) {
@@ -2718,12 +2741,7 @@ pool_kernel(const LaunchArgs A)
         if (blockIdx.x == 0 && threadIdx.x == 0 && A.closed_flag)        /* "this render's pool looked" */
             __hip_atomic_store(A.closed_flag + kFeedbackShards * kShardStrideWords, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    if (A.diag && lane == 0) {      /* as diag_write, with the dry time packed above the dequeue count */
-        const uint32_t wave_id = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
-        uint64_t* d = A.diag + (size_t)wave_id * kDiagWords;
-        d[0] = diag_t0; d[1] = __builtin_amdgcn_s_memrealtime(); d[2] = diag_items;
-        d[3] = (uint64_t)diag_claims | ((uint64_t)diag_dry << 32);
-    }
+    diag_write(A, lane, diag_t0, diag_items, diag_claims, diag_dry);
     FR_STAMP_WRITE(A, lane);
 }
 

@@ -214,6 +214,9 @@ INTERNAL_SIGNATURES = {
     "fr_export8_thresholds_host_powf": (None, [_P(C.c_float)]),
     "fr_node_rccl_selftest": (C.c_int, [C.c_int, C.c_size_t, _P(C.c_int)]),
     "fr_ctx_last_pool_closing": (C.c_int, [C.c_void_p]),
+    "fr_plan_describe": (C.c_int, [_P(fr_params), C.c_uint32, C.c_uint32, _P(fr_shard), C.c_int, _P(C.c_char_p),
+                                   _P(C.c_int64), C.c_int, _P(C.c_int64), C.c_int]),
+    "fr_plan_fields": (C.c_char_p, []),
     "fr_node_set_tuning": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int64]),
     "fr_node_rccl_usable": (C.c_int, [C.c_void_p]),
     "fr_node_mapped_runtimes": (C.c_int, [C.c_char_p, C.c_size_t]),
@@ -288,3 +291,17 @@ def check(status: int) -> int:
     if status < 0:
         raise FractalRendererError(status, lib().fr_last_error().decode("utf-8", "replace"))
     return status
+
+
+def plan_describe(params: fr_params, width: int, height: int, shard: "fr_shard | None" = None, compute_units: int = 256,
+                  tunings=()) -> dict:
+    """The schedule fr_render_shard would choose (fr_tuning.h: fr_plan_describe), as {field: int}.  Needs no GPU.
+    tunings: (name, value) pairs of fr_ctx_set_tuning / the scheduling names of fr_ctx_set_option."""
+    L = lib()
+    fields = L.fr_plan_fields().decode().split()
+    names = (C.c_char_p * max(len(tunings), 1))(*[n.encode() for n, _ in tunings])
+    values = (C.c_int64 * max(len(tunings), 1))(*[int(v) for _, v in tunings])
+    out = (C.c_int64 * len(fields))()
+    check(L.fr_plan_describe(C.byref(params), width, height, C.byref(shard) if shard is not None else None, compute_units,
+                             names, values, len(tunings), out, len(fields)))
+    return dict(zip(fields, out))

@@ -20,6 +20,7 @@
 #include "fr_mandelbulb.hip.h"
 #include "fr_deep.hip.h"
 #include "fr_tuning.h"
+#include "fr_plan.h"
 
 using namespace fr;
 
@@ -59,45 +60,19 @@ struct fr_ctx {
     size_t orbit_cap;           /* capacity in scalars (2 per orbit point) */
     void* stream_buf;           /* survivor stream (tile pass -> lane pool) */
     size_t stream_bytes;
-    uint32_t tune_pool_refill;  /* lane pool: idle lanes that trigger a refill (0 = 24) */
-    int32_t tune_periodicity;   /* cycle closing: -1 off, 0 automatic (on, first window 128), else the first snapshot window in iterations */
-    uint32_t tune_staging;      /* 0 = automatic, 1 = single pass, 3 = tile pass + lane-pool pass whatever max_iter is */
-    uint32_t tune_stage_first;  /* iteration budget b0 of the tile pass (0 = automatic) */
-    uint32_t tune_stream_run_max, tune_stream_run_min, tune_stream_wg_per_cu;
+    Tuning tune;                /* fr_ctx_set_tuning and the scheduling names of fr_ctx_set_option (fr_plan.h) */
     size_t diag_stride;         /* words between the diag regions of consecutive stages */
     int last_stages;
-    uint32_t tune_wg_per_cu;    /* 0 = automatic */
-    uint32_t tune_run_max;      /* 0 = automatic */
-    uint32_t tune_run_min;      /* 0 = automatic */
-    int tune_shift_bias;        /* added to the guided-run shift */
-    uint32_t tune_probes;       /* tile pass: shards a wave probes before exiting (0 = automatic) */
-    uint32_t tune_stream_probes;/* same for the stream / lane-pool passes */
-    uint32_t tune_stream_rotate;/* 0 automatic, 1 regions by XCD, 2 writers rotate over the regions */
     uint64_t* diag;             /* optional device buffer for per-wave timelines */
     uint32_t last_grid;
-    uint32_t tune_shape;        /* 0 = automatic, else FPW_LOG2 (3, 4, 6) */
     void* scratch;              /* device staging for FR_MEM_HOST outputs */
     size_t scratch_bytes;
-    uint32_t debug_region_blocks; /* tests only: cap the capacity of a survivor-stream region, to provoke an overflow */
     double2* log2_tab;          /* device copy of the log2 table of the fp64 smooth-count epilogue (log2_tab()) */
     float* export8_thr;         /* device: 256 x {t[b], t[b + 1]}, the byte thresholds of the 8-bit export (fr_export8_thresholds) */
     void* coord_buf;            /* lean tile pass: W + H coordinates of the frame being rendered (prepare_kernel) */
     size_t coord_bytes;
-    uint32_t tune_tile_kernel;  /* 0 = automatic (the lean tile kernel where it applies), 1 = the general tile_kernel */
-    uint32_t tune_stripes;      /* the Mandelbrot shader's effects (stripes, orbit trap, trap-coloured interior): 0 = automatic (lean tile
-                                   pass + lane pool, kernel code FRACTAL = 3), 1 = the effects variant of the general tile kernel */
-    uint32_t tune_ssaa_band;    /* staged SSAA: samples per band of a whole frame whose sample grid is larger (0 = automatic: 2^29) */
-    uint32_t tune_ssaa;         /* SSAA: 0 = automatic, 1 = the sample loop of the general tile kernel, 2 = staged (sample grid
-                                 * through tile pass + lane pool, then ssaa_reduce_kernel) wherever it applies */
     void* ssaa_buf;             /* staged SSAA: the sample planes (colour [+ nu] [+ iter]), grow-only */
     size_t ssaa_bytes;
-    uint32_t tune_shards;       /* 0 = automatic, 8 or 64: queue shards / stream regions of a render */
-    uint32_t tune_regions;      /* 0 = automatic (= shards), 8 or 64: regions of the survivor streams */
-    uint32_t tune_tile_pixels;  /* lean tile kernel: sub-tiles (pixels per lane) per trip, 0 = automatic (2), 1 or 2 */
-    uint32_t tune_tile_exit;    /* lean tile pass, staged: occupancy exit -- 0 = automatic, 1 = off, else the per-record cost of the
-                                   lane pool in updates that the exit rule assumes (escape_run_lean) */
-    uint32_t tune_tile_exit_from; /* ... and the updates a trip runs before it may leave (0 = automatic) */
-    uint32_t tune_pool_items_per_wg; /* lane pool grid: at most one workgroup per this many sub-tiles of the frame (0 = 32) */
     uint32_t* overflow_host;    /* pinned, device-mapped word: a survivor stream ran out of blocks (see StreamRef::overflow) */
     uint32_t* overflow_dev;     /* the same word as the kernels address it */
     bool render_on_user_stream; /* the most recent render was enqueued on a caller's stream: ev_end orders the context's
@@ -105,8 +80,6 @@ struct fr_ctx {
     /* automatic cycle closing of the lane pool (pool_wants_cycle_closing) */
     uint32_t render_seq;        /* renders enqueued on this context */
     uint32_t prologue_epoch;    /* lean tile passes launched with the in-kernel prologue (lean_prologue): 28 bits */
-    uint32_t tune_prepare;      /* 0 = automatic (the tile pass prepares its own control block and tables, except on a capturing
-                                   stream), 1 = prepare_kernel in a launch of its own */
     uint64_t probe_key;         /* what the context renders (fractal, precision, max_iter, geometry, coarse view) */
     int probe_mode;             /* 0 LOOK: every render's pool looks; 1 SKIP: none does, skip_left to go; 2 WAIT: one look is in
                                  * flight (render probe_seq), nobody else looks until its verdict is back */
@@ -118,7 +91,6 @@ struct fr_ctx {
     uint32_t div_next;
     int phoenix_wg_per_cu[2];   /* resident workgroups per CU of phoenix_kernel<float> / <double> (0 = not asked yet) */
     int mandelbulb_wg_per_cu[2];  /* ... of mandelbulb_kernel<false> / <true> (0 = not asked yet) */
-    uint32_t tune_mandelbulb_split;  /* 0 = automatic (march / shade split), 1 = shade at the hit, inside the march loop */
     /* deep views (fr_render_deep): the most recent reference orbit, on the device, and what it was computed for */
     double* deep_orbit_host;    /* pinned upload buffer, deep_orbit_cap points */
     double2* deep_orbit_dev;    /* Z_0 .. Z_N */
@@ -259,21 +231,9 @@ extern "C" int fr_ctx_compute_units(fr_ctx* c)
 extern "C" int fr_ctx_set_option(fr_ctx* c, const char* name, int64_t value)
 {
     if (!c || !name) return fr_set_error(FR_ERR_INVALID_ARG, "ctx/name is NULL");
-    if (!strcmp(name, "periodicity")) {
-        if (value < -1 || value > (1 << 20)) return fr_set_error(FR_ERR_INVALID_ARG, "periodicity must be -1 (off), 0 (automatic: on), 1 (on) or a first snapshot window in iterations");
-        c->tune_periodicity = value <= 0 ? (int32_t)value : (value == 1 ? 128 : (int32_t)((value + 15) / 16 * 16));
-    } else if (!strcmp(name, "staging")) {
-        /* 2 (block stream passes) and 4 (fused launch) were measured dead ends and left the library in 1.0: accepted,
-         * they select the automatic schedule */
-        if (value < 0 || value > 4) return fr_set_error(FR_ERR_INVALID_ARG, "staging must be 0 (automatic), 1 (single pass) or 3 (tile pass + lane-pool pass)");
-        c->tune_staging = (value == 2 || value == 4) ? 0u : (uint32_t)value;
-    } else if (!strcmp(name, "shards")) {
-        if (value != 0 && value != 8 && value != 64) return fr_set_error(FR_ERR_INVALID_ARG, "shards must be 0 (automatic), 8 or 64");
-        c->tune_shards = (uint32_t)value;
-    } else if (!strcmp(name, "tile_kernel")) {
-        if (value < 0 || value > 1) return fr_set_error(FR_ERR_INVALID_ARG, "tile_kernel must be 0 (automatic: lean where it applies) or 1 (general)");
-        c->tune_tile_kernel = (uint32_t)value;
-    } else if (!strcmp(name, "timing")) {
+    const int st = option_set(c->tune, name, value);
+    if (st != kNotMine) return st;               /* periodicity, staging, shards, tile_kernel */
+    if (!strcmp(name, "timing")) {
         if (value < 0 || value > 1) return fr_set_error(FR_ERR_INVALID_ARG, "timing must be 0 (off) or 1 (an event pair around every render: fr_ctx_last_kernel_ms)");
         c->timing = value != 0;
         if (!c->timing) c->have_timing = false;
@@ -296,82 +256,12 @@ extern "C" int fr_ctx_set_option(fr_ctx* c, const char* name, int64_t value)
 extern "C" int fr_ctx_set_tuning(fr_ctx* c, const char* name, int64_t value)
 {
     if (!c || !name) return fr_set_error(FR_ERR_INVALID_ARG, "ctx/name is NULL");
-    if (!strcmp(name, "workgroups_per_cu")) {
-        if (value < 0 || value > 16) return fr_set_error(FR_ERR_INVALID_ARG, "workgroups_per_cu must be in [0,16]");
-        c->tune_wg_per_cu = (uint32_t)value;
-    } else if (!strcmp(name, "run_max")) {
-        if (value < 0 || value > 1024) return fr_set_error(FR_ERR_INVALID_ARG, "run_max must be in [0,1024]");
-        c->tune_run_max = (uint32_t)value;
-    } else if (!strcmp(name, "run_min")) {
-        if (value < 0 || value > 1024) return fr_set_error(FR_ERR_INVALID_ARG, "run_min must be in [0,1024]");
-        c->tune_run_min = (uint32_t)value;
-    } else if (!strcmp(name, "shift_bias")) {
-        if (value < -16 || value > 16) return fr_set_error(FR_ERR_INVALID_ARG, "shift_bias must be in [-16,16]");
-        c->tune_shift_bias = (int)value;
-    } else if (!strcmp(name, "subtile_shape")) {
-        if (value != 0 && value != 3 && value != 4 && value != 6)
-            return fr_set_error(FR_ERR_INVALID_ARG, "subtile_shape must be 0, 3 (8x8), 4 (16x4) or 6 (64x1)");
-        c->tune_shape = (uint32_t)value;
-    } else if (!strcmp(name, "pool_refill_at")) {
-        if (value < 0 || value > 64) return fr_set_error(FR_ERR_INVALID_ARG, "pool_refill_at must be in [0,64]");
-        c->tune_pool_refill = (uint32_t)value;
-    } else if (!strcmp(name, "stage_first")) {
-        if (value < 0 || value > (1 << 24)) return fr_set_error(FR_ERR_INVALID_ARG, "stage_first out of range");
-        c->tune_stage_first = (uint32_t)value;
-    } else if (!strcmp(name, "stream_run_max")) {
-        if (value < 0 || value > 1024) return fr_set_error(FR_ERR_INVALID_ARG, "stream_run_max must be in [0,1024]");
-        c->tune_stream_run_max = (uint32_t)value;
-    } else if (!strcmp(name, "stream_run_min")) {
-        if (value < 0 || value > 1024) return fr_set_error(FR_ERR_INVALID_ARG, "stream_run_min must be in [0,1024]");
-        c->tune_stream_run_min = (uint32_t)value;
-    } else if (!strcmp(name, "stream_workgroups_per_cu")) {
-        if (value < 0 || value > 8) return fr_set_error(FR_ERR_INVALID_ARG, "stream_workgroups_per_cu must be in [0,8]");
-        c->tune_stream_wg_per_cu = (uint32_t)value;
-    } else if (!strcmp(name, "probes")) {
-        c->tune_probes = (uint32_t)value & 0xFu;
-    } else if (!strcmp(name, "stream_probes")) {
-        c->tune_stream_probes = (uint32_t)value & 0xFu;
-    } else if (!strcmp(name, "stream_rotate")) {
-        c->tune_stream_rotate = (uint32_t)value;
-    } else if (!strcmp(name, "regions")) {
-        if (value != 0 && value != 8 && value != 64) return fr_set_error(FR_ERR_INVALID_ARG, "regions must be 0 (automatic), 8 or 64");
-        c->tune_regions = (uint32_t)value;
-    } else if (!strcmp(name, "tile_pixels")) {
-        if (value < 0 || value > 2) return fr_set_error(FR_ERR_INVALID_ARG, "tile_pixels must be 0 (automatic), 1 or 2");
-        c->tune_tile_pixels = (uint32_t)value;
-    } else if (!strcmp(name, "prepare")) {
-        if (value < 0 || value > 1) return fr_set_error(FR_ERR_INVALID_ARG, "prepare must be 0 (automatic: inside the lean tile pass) or 1 (a launch of its own)");
-        c->tune_prepare = (uint32_t)value;
-    } else if (!strcmp(name, "debug_prologue_epoch")) {
+    if (!strcmp(name, "debug_prologue_epoch")) {
         if (value < 0 || value > 0x0FFFFFFF) return fr_set_error(FR_ERR_INVALID_ARG, "debug_prologue_epoch: 28 bits");
         c->prologue_epoch = (uint32_t)value;          /* tests only: the epoch of the next in-kernel prologue is this + 1 */
-    } else if (!strcmp(name, "tile_exit")) {
-        if (value < 0 || value > 4096) return fr_set_error(FR_ERR_INVALID_ARG, "tile_exit must be 0 (automatic), 1 (off) or a cost in updates up to 4096");
-        c->tune_tile_exit = (uint32_t)value;
-    } else if (!strcmp(name, "tile_exit_from")) {
-        if (value < 0 || value > (1 << 24)) return fr_set_error(FR_ERR_INVALID_ARG, "tile_exit_from out of range");
-        c->tune_tile_exit_from = (uint32_t)value;
-    } else if (!strcmp(name, "ssaa")) {
-        if (value < 0 || value > 2) return fr_set_error(FR_ERR_INVALID_ARG, "ssaa must be 0 (automatic), 1 (sample loop of the general tile kernel) or 2 (staged)");
-        c->tune_ssaa = (uint32_t)value;
-    } else if (!strcmp(name, "stripes")) {
-        if (value < 0 || value > 1) return fr_set_error(FR_ERR_INVALID_ARG, "stripes must be 0 (automatic) or 1 (Mandelbrot effects by the effects variant of the general tile kernel)");
-        c->tune_stripes = (uint32_t)value;
-    } else if (!strcmp(name, "ssaa_band_samples")) {
-        if (value < 0 || value > (1ll << 30)) return fr_set_error(FR_ERR_INVALID_ARG, "ssaa_band_samples must be 0 (automatic: 2^29) or up to 2^30");
-        c->tune_ssaa_band = (uint32_t)value;
-    } else if (!strcmp(name, "pool_items_per_wg")) {
-        if (value < 0 || value > 4096) return fr_set_error(FR_ERR_INVALID_ARG, "pool_items_per_wg must be in [0,4096]");
-        c->tune_pool_items_per_wg = (uint32_t)value;
-    } else if (!strcmp(name, "mandelbulb_split")) {
-        if (value < 0 || value > 1) return fr_set_error(FR_ERR_INVALID_ARG, "mandelbulb_split must be 0 (automatic: march / shade split) or 1 (shade inside the march loop)");
-        c->tune_mandelbulb_split = (uint32_t)value;
-    } else if (!strcmp(name, "debug_region_blocks")) {
-        c->debug_region_blocks = (uint32_t)value;     /* tests only (overflow reporting); 0 = the real capacity */
-    } else {
-        return fr_set_error(FR_ERR_INVALID_ARG, "unknown tuning name '%s'", name);
     }
-    return FR_OK;
+    const int st = strcmp(name, "debug_prologue_epoch") ? tuning_set(c->tune, name, value) : FR_OK;
+    return st == kNotMine ? fr_set_error(FR_ERR_INVALID_ARG, "unknown tuning name '%s'", name) : st;
 }
 
 /* workgroups of 256 threads per launch of the most recent render; bits 16.. = number of stages */
@@ -520,13 +410,6 @@ static hipError_t by_variant(int fractal, bool f64, Fn&& fn)
     }
 }
 
-static uint32_t ceil_log2(uint32_t v)
-{
-    uint32_t b = 0;
-    while ((1u << b) < v && b < 31) ++b;
-    return b;
-}
-
 /* control block in device memory, zeroed by ONE memset per render:
  *   words [s * kStageWords, + kMaxShards * 32): the (8 or 64) queue heads of stage s, 128 B apart
  *   the next kMaxShards * 32 words: the (8 or 64) region counters of the survivor stream written by stage s */
@@ -542,15 +425,6 @@ static int check_overflow(fr_ctx* c)
     return fr_set_error(FR_ERR_INTERNAL, "a kernel reported an internal error (a survivor stream overflowed, or a lane-pool wave "
                                          "gave up on a stretch that would not end): the frame of the last render on this context "
                                          "is incomplete, please report the parameters");
-}
-
-/* Cycle closing ("periodicity"): on unless switched off.  Where it takes effect: the lane-pool pass (PERIOD
- * instantiation), the tile kernel when it runs samples to max_iter with 8x8 sub-tiles -- a one-pass frame (PERIOD
- * instantiation) and SSAA (always compiled in).  Where it does not: the effects variants, one-pass frames with 16x4 /
- * 64x1 sub-tiles and Deep_Zoom -- those iterate every sample to max_iter, as the reference does. */
-static uint32_t period_window(const fr_ctx* c)
-{
-    return c->tune_periodicity < 0 ? 0u : (c->tune_periodicity == 0 ? 128u : (uint32_t)c->tune_periodicity);
 }
 
 /* what the first launch of a render forwards from the previous one (see Feedback) */
@@ -572,7 +446,7 @@ static Feedback feedback_of(fr_ctx* c)
  * device: until then the pool keeps looking.  A view whose pools close cycles always looks.  Nothing a pixel depends on. */
 static bool pool_wants_cycle_closing(fr_ctx* c, const fr_params* p, uint32_t W, uint32_t rows)
 {
-    if (c->tune_periodicity != 0) return c->tune_periodicity > 0;          /* explicit: on (any window) or off */
+    if (c->tune.periodicity != 0) return c->tune.periodicity > 0;          /* explicit: on (any window) or off */
     uint64_t key = 1469598103934665603ull;
     /* ... and WHERE it looks, coarsely: the octave of the zoom, the centre in units of that octave's view height, the Julia
      * constant to 1/64 -- a sequence that leaves a dust for an interior-heavy view (or pans by a view, or zooms by 2x) starts
@@ -636,9 +510,6 @@ static hipError_t order_after_last_render(fr_ctx* c, hipStream_t s)
     return hipStreamWaitEvent(s, c->ev_order, 0);
 }
 
-static QueueArgs plan_tile_queue(const fr_ctx* c, uint32_t W, uint32_t rows_local, int shape, bool bounded, bool moderate,
-                                 uint32_t wg_per_cu, uint32_t* grid_out);
-
 /* the caller's shard with its defaults filled in, and the rows it owns (0: nothing to do) */
 static int normalise_shard(const fr_shard* shard, uint32_t H, fr_shard* norm, uint32_t* rows_local)
 {
@@ -698,7 +569,7 @@ static int launch_one_pass(fr_ctx* c, hipStream_t stream, const char* name, void
         wg_per_cu = nb < 1 ? 1 : nb;
     }
     uint32_t grid = 0;
-    q = plan_tile_queue(c, (uint32_t)g.W, (uint32_t)g.rows_local, 3, false, moderate, (uint32_t)wg_per_cu, &grid);
+    q = plan_tile_queue(c->tune, c->compute_units, (uint32_t)g.W, (uint32_t)g.rows_local, 3, false, moderate, (uint32_t)wg_per_cu, &grid);
     q.heads = stage_heads(c, 0);
     c->last_grid = grid;
     c->last_pool_closing = -1;
@@ -829,7 +700,7 @@ static int enqueue_mandelbulb(fr_ctx* c, const fr_params* p, const fr_mandelbulb
     a.g = tile_geom(W, H, rows_local, &norm, out_frame);
     a.rgba = reinterpret_cast<float4*>(rgba); a.nu = (float*)nu; a.iter = iter;
 
-    const bool split = c->tune_mandelbulb_split != 1u;
+    const bool split = c->tune.mandelbulb_split != 1u;
     return launch_one_pass(c, stream, split ? "mandelbulb_kernel<true>" : "mandelbulb_kernel<false>",
                            split ? mandelbulb_kernel<true> : mandelbulb_kernel<false>, a, a.g, a.q,
                            c->mandelbulb_wg_per_cu[split ? 1 : 0], false);
@@ -1110,180 +981,179 @@ static void fill_params(LaunchArgs& a, const fr_params* p)
     a.lib_log = !(p->bailout > 1.0f);        /* log2_pos() needs positive arguments: |z|^2 > 1 */
 }
 
-/* colourings that need more of the orbit than (escape index, |z|^2): the as-written effects loops */
-static bool needs_effects(const fr_params* p)
+/* the grow-only device buffers of the context (growing happens on the first render of a larger geometry, not capturable) */
+static int grow_device(void** buf, size_t* cap, size_t need)
 {
-    switch (p->fractal_type) {
-    case FR_FRACTAL_MANDELBROT:   return p->orbit_trap_enabled || p->stripe_enabled || p->interior_style == 2;
-    case FR_FRACTAL_BURNING_SHIP: return p->orbit_trap_enabled || (p->stripe_enabled && p->interior_style == 2) ||
-                                         p->interior_style == 3;
-    default: return false;
-    }
-}
-
-/* ---- geometry of the tile pass ----------------------------------------------------------------------
- * Sub-tiles of 64 pixels (2^shape wide) in blocks of 16 dealt round by round to the 8 or 64 shards, a shard's place
- * rotating with the round (WaveQueue::block_of; blocks >= n_blk are skipped by the kernels); a persistent grid of
- * exactly the resident set (wg_per_cu workgroups per CU unless "workgroups_per_cu" says otherwise); run lengths and
- * probe limit of the queue.  The Deep_Zoom and Phoenix kernels take the same queue as an unbounded pass on 8x8 sub-tiles.
- * (The caller sets heads.) */
-static QueueArgs plan_tile_queue(const fr_ctx* c, uint32_t W, uint32_t rows_local, int shape, bool bounded, bool moderate,
-                                 uint32_t wg_per_cu, uint32_t* grid_out)
-{
-    const uint32_t fpw = 1u << shape, fph = 64u >> shape;
-    QueueArgs tq;
-    memset(&tq, 0, sizeof(tq));
-    tq.nsx = (W + fpw - 1) / fpw;
-    tq.nsx_shift = -1;
-    for (int b = 0; b < 31; ++b)
-        if (tq.nsx == (1u << b)) tq.nsx_shift = b;
-    const uint32_t nsy = (rows_local + fph - 1) / fph;
-    tq.n_items = tq.nsx * nsy;
-    tq.n_blk = (tq.n_items + kShardBlock - 1) / kShardBlock;
-
-    uint32_t grid = (uint32_t)c->compute_units * (c->tune_wg_per_cu ? c->tune_wg_per_cu : wg_per_cu);
-    /* never more waves than the shortest runs can feed: a wave takes at least run_min sub-tiles per dequeue (4 when
-     * bounded, 2 otherwise), and waves that find nothing still cost their launch and their exit probes -- at 512^2
-     * a grid of one wave per sub-tile left 3 of 4 waves without work: 0.083 ms per frame against 0.048 ms */
-    const uint32_t per_wave = c->tune_run_min ? c->tune_run_min : (bounded ? 4u : 2u);
-    const uint32_t max_grid = (tq.n_items + 4u * per_wave - 1u) / (4u * per_wave);
-    if (grid > max_grid) grid = max_grid < 1 ? 1 : max_grid;
-    /* Shards: 64 (8 per XCD) where waves stop at their home shard(s) and the frame has work for them -- 64 queue heads
-     * (and 64 block counters of the survivor stream) instead of 8 take the same claims at 8x the rate (kMaxShards);
-     * launches with unlimited stealing keep 8: a wave probes every shard before it exits. */
-    const bool limited = (bounded || moderate) && grid >= 64u;
-    /* (from 4 blocks per shard and 256 workgroups: a 512^2 frame -- 256 blocks -- measured -6 % with 64 shards, end of round 4;
-     * the rule had asked for 8 blocks per shard and 512 workgroups) */
-    uint32_t ns = (limited && grid >= 256u && tq.n_blk >= 4u * (uint32_t)kMaxShards) ? (uint32_t)kMaxShards : (uint32_t)kShards;
-    if (c->tune_shards) ns = c->tune_shards;
-    tq.ns_log2 = ns == (uint32_t)kMaxShards ? 6u : 3u;
-    const uint32_t waves_per_shard = (grid * 4u + ns - 1) / ns;
-    auto clamp_shift = [&](int v) { v += c->tune_shift_bias; return (uint32_t)(v < 0 ? 0 : (v > 31 ? 31 : v)); };
-    /* Run length of a dequeue = clamp(remaining >> run_shift, run_min, run_max).
-     *  - unbounded items (single pass, measured on C2, profiles/r01_sweep_c2.txt): sub-tile cost varies 100x,
-     *    so long runs leave a tail of waves holding several max_iter sub-tiles while single sub-tile claims
-     *    saturate the queue words (~88 dequeues/us each: a 0.44 ms floor): short runs of 2..8;
-     *  - bounded items (staged tile pass: at most b0 iterations each): long runs are safe and hide the
-     *    dequeue latency that dominates cheap sub-tiles. */
-    if (bounded) {
-        /* 64 shards: runs a quarter as long again (remaining / (8 waves' worth)) -- with waves that stop at their home
-         * shards the last runs of a shard are its tail, and at 80 waves per shard a run of 16 sub-tiles inside the set is
-         * 20 us on a chip that is otherwise done: C2 tile pass 114 -> 105 us, C3 125 -> 112 us, C5 1639 -> 1593 us
-         * (a view where every sub-tile costs the same pays for the extra claims: 76 -> 85 us) */
-        tq.run_shift = clamp_shift((int)ceil_log2(2u * waves_per_shard) + (ns == (uint32_t)kMaxShards ? 2 : 0));
-        tq.run_max = c->tune_run_max ? c->tune_run_max : 32u;
-        tq.run_min = c->tune_run_min ? c->tune_run_min : 4u;
-    } else {
-        tq.run_shift = clamp_shift((int)ceil_log2(16u * waves_per_shard));
-        tq.run_max = c->tune_run_max ? c->tune_run_max : 8u;
-        tq.run_min = c->tune_run_min ? c->tune_run_min : 2u;
-    }
-    if (tq.run_min > tq.run_max) tq.run_min = tq.run_max;
-    tq.flags = 0u;
-    /* Bounded items are dealt evenly to the shards, so a wave whose home shard is dry exits instead of
-     * probing the other 7 (measured: the exit storm of 4096 waves x 8 serialized atomics costs 31 us of the
-     * 260 us tile pass of C2 and 36 of the 74 us of a 1/8 shard, profiles/r01_probe_limit.txt).  Unbounded
-     * passes keep full stealing; so do grids with fewer workgroups than shards. */
-    /* Passes whose items are long (SSAA: aa^2 samples to max_iter per pixel; effects; a forced single pass) keep full
-     * stealing: with home + one neighbour the C5 view at 2x2 samples takes 9.96 ms instead of 8.12 ms. */
-    /* 64 shards: home + the next one of the same XCD (80 waves per shard: a second look evens out the ends) */
-    uint32_t probes = c->tune_probes ? c->tune_probes : (limited ? (ns == (uint32_t)kMaxShards ? 2u : 1u) : 0u);
-    if (grid < ns) probes = 0;
-    tq.flags |= probes << kQueueProbeShift;
-    *grid_out = grid;
-    return tq;
-}
-
-/* ---- stage schedule ----------------------------------------------------------------------------------
- * Two passes -- the tile pass runs [0, b0), the lane pool [b0, max_iter) -- or one.  Not staged: SSAA (samples of a pixel
- * must meet again to be averaged), the effects variants (accumulators along the whole orbit), short max_iter.  Returns
- * the number of passes; bounds[k] = upper iteration bound of pass k.  (Block stream passes with x4 budgets and a fused
- * one-launch schedule were built and measured slower everywhere: DESIGN.md section 7.) */
-static int staging_threshold(const fr_params* p, size_t npx)
-{
-    const bool big = npx > ((size_t)1 << 23);
-    if (p->fractal_type == FR_FRACTAL_JULIA) return npx <= ((size_t)1 << 20) ? 512 : 256;   /* (small frames: 256^2 ... 1024x768 at 256, the
-                                                                                              * dust 55 -> 36 us in one pass, a filled set 50 -> 23) */
-    /* Small frames (end of round 4, profiles/r04_small_frame_staging.txt): the second launch and the lane pool's ramp and
-     * run-out are ~45-60 us whatever the frame, which a frame of half a megapixel does not win back before max_iter 1024-2048
-     * (256^2 at 512, fp64: 74 -> 49 us in one pass; 512^2 at 1024, fp32: 92 -> 72; but the Seahorse view at 2048: 129 against
-     * 168-190 in one pass): up to 2^19 pixels fp32 stages from 1536, fp64 from 1024 -- from 1536 up to 2^18 pixels; a Julia set from 512 up to 2^20 pixels. */
-    if (npx <= ((size_t)1 << 19)) return p->precision == FR_PRECISION_F64 ? (npx <= ((size_t)1 << 18) ? 1536 : 1024) : 1536;
-    return p->precision == FR_PRECISION_F64 ? (big ? 384 : 512) : (big ? 512 : 768);
-}
-
-static int plan_stages(const fr_ctx* c, const fr_params* p, bool effects, size_t npx, bool pool_runs_everything, int bounds[kMaxStages])
-{
-    const int max_iter = p->max_iterations;
-    int nstage = 0;
-    const bool allow = !effects && p->antialiasing_samples <= 1 && c->tune_staging != 1u;
-    /* tile-pass budget: ~max_iter/28 rounded to the unchecked block, within [32, 192] (measured best:
-     * 32 at max_iter 1024, 64 at 2048, 128-192 at 4096, flat at 16384) */
-    int auto_first = ((max_iter / 28 + kFastBlock / 2) / kFastBlock) * kFastBlock;
-    auto_first = auto_first < 32 ? 32 : (auto_first > 192 ? 192 : auto_first);
-    /* fp64 frames of 2^24 pixels and more whose lane pool runs every survivor to max_iter (cycle closing off, or skipped
-     * because it closed nothing lately): ~max_iter/11 within [96, 192].  Round 3's sweeps with the lean tile kernel
-     * (profiles/r03_b0_and_pool_tuning.txt): C2 (4096^2, 1024) 96 against 32: -1.8 %, C5 (8192^2, 4096) 192 against 144:
-     * -0.5 %; a 1080p frame at 1024 keeps 32 (96: +8 %), the fp32 Julia dust its 80 (96-128 within noise, 256: +8 %).
-     * A pool that closes cycles makes a survivor cheap, and the long tile pass only costs: C2 with cycle closing
-     * 0.517 ms at 32, 0.583 ms at 96. */
-    if (pool_runs_everything && p->precision == FR_PRECISION_F64 && npx >= ((size_t)1 << 24)) {
-        int big = ((max_iter / 11 + kFastBlock / 2) / kFastBlock) * kFastBlock;
-        big = big < 96 ? 96 : (big > 192 ? 192 : big);
-        if (big > auto_first) auto_first = big;
-    }
-    const int first = c->tune_stage_first ? (int)c->tune_stage_first : auto_first;
-    /* The second pass pays off where orbits are long.  Rounds 1-3: below max_iter ~768 (~384 on frames above 4K) ONE pass
-     * whose waves stop at their home shard was faster -- 1080p at max_iter 256: 0.061 ms against 0.109 ms -- and above it
-     * the two passes won by up to 35 % (profiles/r01_staging_crossover.txt).  Round 4's lane pool (deferred escapes) moved
-     * the crossover down where escapes are spread out (profiles/r04_staging_crossover.txt, 168 cells): a Julia set wins
-     * with two passes from max_iter 256 (-5 to -12 %; 384: -15 to -30 %; 512: -23 to -36 %), an fp64 Mandelbrot view
-     * from 512 at every size up to 4K (-6 to -13 %; 384 on frames above 2^23 pixels as before: the default view loses 5-9 %
-     * there, the Seahorse view wins 15-28 %), an fp32 one stays at 768 (512 above 2^23 pixels, where 384 lost 7-11 %).
-     * An explicit "staging" or "stage_first" stages whenever there is room for two budgets. */
-    const int auto_min = staging_threshold(p, npx);
-    const bool forced = c->tune_staging != 0 || c->tune_stage_first != 0;
-    if (allow && (forced ? max_iter >= 2 * first : max_iter >= auto_min)) {
-        int b = first - first % kFastBlock;                      /* the budget is a multiple of the unchecked block */
-        if (b < kFastBlock) b = kFastBlock;
-        if (b < max_iter) bounds[nstage++] = b;
-    }
-    bounds[nstage++] = max_iter;
-    return nstage;
-}
-
-/* Survivor stream: blocks of 64 records {pixel u32, iterations done u32, nfields x T}.  Worst case: every
- * sample survives (npx/64 full blocks) + one partial block per writer wave; the regions of the stream hold
- * 1.5x that, so a region that fills up can spill into its neighbours.  Grow-only (happens on the first
- * render of a larger geometry, not capturable). */
-static int reserve_stream(fr_ctx* c, size_t npx, size_t nfields, bool f64, uint32_t writer_workgroups, uint32_t nregions,
-                          uint32_t* region_blocks)
-{
-    const size_t block_bytes = 2 * 64 * 4 + nfields * 64 * (f64 ? 8 : 4);
-    const uint32_t worst_blocks = (uint32_t)((npx + 63) / 64) + writer_workgroups * 4u + 16u;
-    *region_blocks = (worst_blocks * 3u / 2u + nregions - 1) / nregions + 1u;
-    const size_t need = (size_t)*region_blocks * nregions * block_bytes;
-    if (need <= c->stream_bytes) return FR_OK;
-    if (c->stream_buf) { (void)hipFree(c->stream_buf); c->stream_buf = nullptr; }
-    c->stream_bytes = 0;
-    FR_HIP_TRY(hipMalloc(&c->stream_buf, need));
-    c->stream_bytes = need;
+    if (need <= *cap) return FR_OK;
+    if (*buf) { (void)hipFree(*buf); *buf = nullptr; }
+    *cap = 0;
+    FR_HIP_TRY(hipMalloc(buf, need));
+    *cap = need;
     return FR_OK;
 }
 
-/* reserve_only: do everything a render of this geometry would do BEFORE its first launch -- grow the survivor streams,
- * the Deep_Zoom orbit buffers, fill the exact-division cache -- and stop (fr_ctx_reserve). */
+/* ---- the render of a Mandelbrot / Julia / Burning Ship frame ---------------------------------------------------------
+ * enqueue_render: plan (plan_render, fr_plan.h: every decision, no HIP call), route, fill_geometry, the two grow_device calls,
+ * begin_frame, launch_tile_pass, launch_pool_pass, finish_render.
+ * reserve_only: do everything a render of this geometry would do BEFORE its first launch -- grow the survivor streams,
+ * the Deep_Zoom orbit buffers, fill the exact-division cache -- and stop (fr_ctx_reserve).
+ * ssaa_of > 1: this IS the sample grid of a supersampled res_w x res_h frame (enqueue_ssaa_staged): lean kernels only, the
+ * coordinate tables hold the samples' coordinates */
 static int enqueue_ssaa_staged(fr_ctx* c, const fr_params* p, uint32_t W, uint32_t H, const fr_shard* norm, uint32_t rows_local,
                                float* rgba, void* nu, int32_t* iter, hipStream_t stream, bool reserve_only, bool out_frame);
-static int staging_threshold(const fr_params* p, size_t npx);
 
-/* occupancy exit of the lean tile pass (escape_run_lean): what a record costs the lane pool, in updates, and the updates a
- * trip runs before it may leave */
-constexpr uint32_t kTileExitCost = 48u;
-constexpr uint32_t kTileExitFrom = 32u;
+/* staged SSAA of a whole frame band by band (plan_route): each band is the one strip of "part b of nbands", rendered
+ * straight into the caller's planes, one after the other on the stream */
+static int enqueue_ssaa_banded(fr_ctx* c, const fr_params* p, uint32_t W, uint32_t H, const RenderPlan& plan, float* rgba,
+                               void* nu, int32_t* iter, hipStream_t stream, bool reserve_only)
+{
+    const bool timed = c->timing;
+    if (timed && !reserve_only) FR_HIP_TRY(hipEventRecord(c->ev_begin, stream));
+    c->timing = false;                                                   /* one event pair around all bands */
+    int st = FR_OK;
+    for (uint32_t b = 0; b < plan.nbands && st == FR_OK; ++b) {
+        const fr_shard band = {b, plan.nbands, plan.band_rows};
+        st = enqueue_ssaa_staged(c, p, W, H, &band, fr_shard_rows(&band, H), rgba, nu, iter, stream, reserve_only, true);
+        if (reserve_only) break;                                         /* the first band is the largest */
+    }
+    c->timing = timed;
+    if (st == FR_OK && timed && !reserve_only) {
+        FR_HIP_TRY(hipEventRecord(c->ev_end, stream));
+        c->have_timing = true;
+    }
+    return st;
+}
 
-/* ssaa_of > 1: this IS the sample grid of a supersampled res_w x res_h frame (enqueue_ssaa_staged): lean kernels only, the
- * coordinate tables hold the samples' coordinates */
+/* the geometry part of the kernel argument block, and what the host prepares for the viewport map */
+static void fill_geometry(LaunchArgs& a, fr_ctx* c, const fr_params* p, uint32_t W, uint32_t H, const fr_shard& norm,
+                          uint32_t rows_local, bool out_frame, int ssaa_of, uint32_t res_w, uint32_t res_h)
+{
+    const bool f64 = p->precision == FR_PRECISION_F64;
+    a.ssaa = ssaa_of > 1 ? ssaa_of : 0;
+    a.res_w = (int32_t)res_w; a.res_h = (int32_t)res_h;
+    a.W = (int32_t)W; a.H = (int32_t)H; a.rows_local = (int32_t)rows_local;
+    a.part = (int32_t)norm.part; a.nparts = (int32_t)norm.nparts; a.rows_per_strip = (int32_t)norm.rows_per_strip;
+    a.out_frame = out_frame ? 1 : 0;
+    a.log2_tab = c->log2_tab;
+
+    /* escape is absorbing (see escape_run): bailout^2 in [4.5, 1e12], and for Julia |c| <= bailout;
+     * Mandelbrot lanes with |c| > bailout retire at i = 0 inside the first, tested block */
+    const double B2 = f64 ? (double)p->bailout * (double)p->bailout : (double)(p->bailout * p->bailout);
+    const double c2 = a.julia_cx * a.julia_cx + a.julia_cy * a.julia_cy;
+    a.fast_ok = (B2 >= 4.5 && B2 <= 1e12 && (p->fractal_type != FR_FRACTAL_JULIA || c2 <= B2)) ? 1 : 0;
+    /* 4 bailout^2 as the kernels form it: B * B in the kernel's precision, times 4 (exact) */
+    const float b2f = p->bailout * p->bailout;
+    a.b2x4_d = 4.0 * ((double)p->bailout * (double)p->bailout);
+    a.b2x4_f = 4.0f * b2f;
+
+    /* host-prepared reciprocals; the divide-free viewport map is enabled only when verified exact */
+    a.inv_w_d = 1.0 / (double)W;  a.inv_h_d = 1.0 / (double)H;
+    a.inv_w_f = 1.0f / (float)W;  a.inv_h_f = 1.0f / (float)H;
+    a.aspect_d = (double)W / (double)H;
+    a.aspect_f = (float)W / (float)H;
+    /* (the uv viewport map of julia.comp:325 / burning_ship.comp:393 has its own quotients) */
+    a.exact_div_ok = exact_division_ok(c, W, H, p->fractal_type != FR_FRACTAL_MANDELBROT, f64) ? 1 : 0;
+}
+
+/* In front of the tile pass: the begin event, then a zeroed control block (and, for the lean kernels, their coordinate
+ * tables) by one of three means. */
+static int begin_frame(fr_ctx* c, const RenderPlan& plan, int nstages, const fr_params* p, LaunchArgs& a, hipStream_t stream)
+{
+    const uint32_t ctrl_words = (uint32_t)((size_t)nstages * kStageWords);
+    /* the frame's device time (fr_ctx_last_kernel_ms) includes the small launch that prepares it */
+    if (c->timing) FR_HIP_TRY(hipEventRecord(c->ev_begin, stream));
+    if (!plan.lean()) { FR_HIP_TRY(clear_control_block(c, stream, nstages)); return FR_OK; }
+    a.xs = c->coord_buf;
+    a.yds = (uint8_t*)c->coord_buf + (size_t)a.W * (plan.f64 ? sizeof(double) : sizeof(float));
+    /* the lean tile pass prepares its own control block and coordinate tables (lean_prologue: its first workgroups, the others
+     * wait on a word keyed by a per-context epoch) -- except on a capturing stream: a replayed launch would carry a stale epoch */
+    bool in_kernel_prologue = false;
+    if (c->tune.prepare != 1u) {
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(stream, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusActive; }
+        in_kernel_prologue = cap == hipStreamCaptureStatusNone;
+    }
+    if (!in_kernel_prologue) {
+        const hipError_t ep = by_variant(p->fractal_type, plan.f64, [&](auto t, auto f) {
+            return launch_prepare<decltype(t), decltype(f)::value>(stream, a, c->d_ctrl, ctrl_words, feedback_of(c)); });
+        if (ep != hipSuccess) return fr_set_error(FR_ERR_HIP, "prepare kernel launch failed: %s", hipGetErrorString(ep));
+        return FR_OK;
+    }
+    if (c->prologue_epoch >= 0x0FFFFFF0u) {                 /* 28 bits: start over behind a cleared word */
+        FR_HIP_TRY(hipMemsetAsync(c->d_ctrl + kReadyWord, 0, sizeof(uint32_t), stream));
+        c->prologue_epoch = 0;
+    }
+    const Feedback fb = feedback_of(c);
+    a.pro_ready = c->d_ctrl + kReadyWord;
+    a.pro_epoch = ++c->prologue_epoch << 4;
+    a.pro_ctrl = c->d_ctrl;
+    a.pro_ctrl_words = ctrl_words;
+    a.pro_fb_flag = fb.dev_flag; a.pro_fb_host = fb.host_word; a.pro_prev_seq = fb.prev_seq;
+    uint32_t n = 8;
+    while (n > plan.grid) n >>= 1;
+    a.pro_n = n ? n : 1u;
+    return FR_OK;
+}
+
+/* the tile pass: [0, b0) of a staged render, whose survivors go to the stream; else the whole render */
+static int launch_tile_pass(fr_ctx* c, const RenderPlan& plan, const fr_params* p, LaunchArgs& a, bool pool_looks, hipStream_t stream)
+{
+    const int fractal = p->fractal_type;                      /* 0 Mandelbrot, 1 Julia, 2 Burning Ship */
+    const dim3 grid(plan.grid);
+    a.q = plan.tq;
+    a.q.heads = stage_heads(c, 0);
+    a.i1 = plan.b0[pool_looks];                                /* (from i0 = 0) */
+    a.exit_cost = plan.exit_cost;
+    a.exit_from = plan.exit_from[pool_looks];
+    a.out.overflow = c->overflow_dev;                           /* (the prologue's timeout reports through it too) */
+    if (plan.staged()) {
+        a.out.base = (uint8_t*)c->stream_buf;
+        a.out.n_blocks = stage_counter(c, 0);
+        a.out.region_blocks = plan.region_blocks;
+        a.out.rotate = plan.rotate_regions;
+        a.out.nregions = plan.nregions;
+    }
+    a.diag = c->diag;
+    a.period_window = plan.tile_period_window;
+    const hipError_t e =
+        plan.family == kGeneralEffects ? by_variant(fractal, plan.f64, [&](auto t, auto f) {
+            constexpr int F = decltype(f)::value == 1 ? 0 : decltype(f)::value;      /* Julia has no effects variant */
+            return launch_tile<decltype(t), F, true>(plan.shape, grid, stream, a); })
+        : plan.stripes() ? (plan.f64 ? launch_tile_lean_stripes<double>(grid, stream, a) : launch_tile_lean_stripes<float>(grid, stream, a))
+        : plan.lean() ? by_variant(fractal, plan.f64, [&](auto t, auto f) {
+            return launch_tile_lean<decltype(t), decltype(f)::value>(plan.tile_pixels, grid, stream, a); })
+        : by_variant(fractal, plan.f64, [&](auto t, auto f) {      /* kGeneral, kGeneralSampleLoop: launch_tile looks at a.aa */
+            return launch_tile<decltype(t), decltype(f)::value, false>(plan.shape, grid, stream, a); });
+    if (e != hipSuccess) return fr_set_error(FR_ERR_HIP, "tile kernel launch failed: %s", hipGetErrorString(e));
+    return FR_OK;
+}
+
+/* the lane-pool pass: the survivors, to max_iter */
+static int launch_pool_pass(fr_ctx* c, const RenderPlan& plan, const fr_params* p, LaunchArgs& a, bool pool_looks, hipStream_t stream)
+{
+    const dim3 sgrid(plan.sgrid);
+    a.i0 = plan.b0[pool_looks];
+    a.i1 = p->max_iterations;
+    a.pro_ready = nullptr;
+    a.in = a.out;                                           /* what the tile pass wrote */
+    a.in.n_blocks = stage_counter(c, 0);
+    memset(&a.out, 0, sizeof(a.out));                       /* the pool pass runs everything out ... */
+    a.out.overflow = c->overflow_dev;                       /* ... and reports a stretch loop that will not end */
+    a.q = plan.pq;
+    a.q.heads = stage_heads(c, 1);
+    a.diag = c->diag ? c->diag + c->diag_stride : nullptr;
+    a.pool_refill_at = plan.pool_refill_at;
+    a.period_window = pool_looks ? period_window(c->tune) : 0u;
+    c->last_pool_closing = a.period_window != 0u;
+    a.closed_flag = c->d_ctrl + kFeedbackWord;
+    const hipError_t e =
+        plan.stripes() ? (plan.f64 ? launch_pool_stripes<double>(sgrid, stream, a) : launch_pool_stripes<float>(sgrid, stream, a))
+                       : by_variant(p->fractal_type, plan.f64, [&](auto t, auto f) {
+                             return launch_stream_pool<decltype(t), decltype(f)::value>(sgrid, stream, a); });
+    if (e != hipSuccess) return fr_set_error(FR_ERR_HIP, "lane-pool kernel launch failed: %s", hipGetErrorString(e));
+    return FR_OK;
+}
+
 static int enqueue_render(fr_ctx* c, const fr_params* p, uint32_t W, uint32_t H, const fr_shard* shard,
                           float* rgba, void* nu, int32_t* iter, hipStream_t stream, bool reserve_only = false,
                           bool out_frame = false, int ssaa_of = 0, uint32_t res_w = 0, uint32_t res_h = 0)
@@ -1296,326 +1166,56 @@ static int enqueue_render(fr_ctx* c, const fr_params* p, uint32_t W, uint32_t H,
     uint32_t rows_local = 0;
     const int sh = normalise_shard(shard, H, &norm, &rows_local);
     if (sh != FR_OK || rows_local == 0) return sh;           /* (rows_local 0: this part owns no rows) */
-    if (p->fractal_type == FR_FRACTAL_DEEP_ZOOM)
+    const RenderPlan plan = plan_render(c->tune, c->compute_units, p, W, H, norm, rows_local, ssaa_of, out_frame);
+    if (plan.route == kRouteDeepZoom)
         return enqueue_deep_zoom(c, p, W, H, &norm, rows_local, rgba, nu, iter, stream, reserve_only, out_frame);
-
-    const int fractal = p->fractal_type;                      /* 0 Mandelbrot, 1 Julia, 2 Burning Ship */
-    const bool julia = fractal == FR_FRACTAL_JULIA;
-    const bool uv_map = fractal != FR_FRACTAL_MANDELBROT;     /* julia.comp:325 / burning_ship.comp:393 viewport map */
-    const bool f64 = p->precision == FR_PRECISION_F64;
-    /* The Mandelbrot shader's effects need nothing along the orbit: stripe shading reads the z of the sample's last update, and
-     * the orbit trap's minimum is the constant 0 (see shade_stripes: the first update makes z = c, and distToC is part of
-     * the minimum).  Such frames take the lean tile pass and the lane pool in their code-3 instantiations instead of the
-     * effects variant's lockstep run to max_iter with four running minima -- 8x8 sub-tiles, two per trip.  (Burning Ship's
-     * trap and stripe sums are real accumulators: the effects variant keeps them.) */
-    const bool m_effects = fractal == FR_FRACTAL_MANDELBROT && needs_effects(p) &&
-                              c->tune_stripes != 1u && c->tune_tile_kernel != 1u && (c->tune_shape == 0u || c->tune_shape == 3u) &&
-                              c->tune_tile_pixels != 1u;
-    const bool m_effects_lean = m_effects && p->antialiasing_samples <= 1 && (norm.nparts == 1 || norm.rows_per_strip % 8u == 0u);
-    const bool effects = needs_effects(p) && !m_effects_lean;
-    const int max_iter = p->max_iterations;
-
-    /* SSAA.  The sample loop of the general tile kernel runs a pixel's aa x aa samples one after the other, each to max_iter
-     * in lockstep with the 63 other pixels of its sub-tile: no compaction, no lane pool -- on escape-dense views a sample
-     * costs 1.6-1.8x what a pixel of the same view costs without SSAA (profiles/r04_ssaa_staged.txt).  Staged: the sample
-     * grid is a frame of W aa x H aa "pixels" whose coordinates are the samples' (prepare_kernel writes them into the lean
-     * kernels' tables), rendered through tile pass + lane pool into scratch planes, and ssaa_reduce_kernel averages.  Same
-     * arithmetic per sample, same summation order: bit-identical planes.  Applies where the lean kernels do (no effects,
-     * 8x8 sub-tiles, strips of whole sub-tile rows in sample space) and the sample grid is a legal frame (< 2^31 samples). */
-    if (ssaa_of <= 1 && p->antialiasing_samples > 1 && (!needs_effects(p) || m_effects) && c->tune_ssaa != 1u) {   /* (striped sample
-                                                                  grids too: their samples take the stripe instantiations) */
-        const uint32_t aa = (uint32_t)p->antialiasing_samples;
-        const uint64_t nsamples = (uint64_t)W * aa * (uint64_t)H * aa;
-        const bool lean_ok = c->tune_tile_kernel != 1u && (c->tune_shape == 0u || c->tune_shape == 3u) &&
-                             (norm.nparts == 1 || (norm.rows_per_strip * aa) % 8u == 0u);
-        /* (measured: -32 to -61 % on every view and size but the C2 frame with cycle closing off, +-2 %; also where the sample
-         * grid takes ONE pass -- 1080p at max_iter 256: -38 % -- because the lean kernel beats the general one.  The sample
-         * planes and the survivor stream of the sample grid are context scratch: 16 B + up to 60 B per sample; above 2^29
-         * samples -- 8192^2 at aa 3 -- the sample loop stays.) */
-        const uint64_t band_cap = c->tune_ssaa_band ? c->tune_ssaa_band : (1ull << 29);
-        const bool fits = nsamples <= band_cap || (c->tune_ssaa == 2u && !c->tune_ssaa_band);
-        if (lean_ok && fits && nsamples < (1ull << 31) && (uint64_t)norm.rows_per_strip * aa <= 0xFFFFFFFFull)
-            return enqueue_ssaa_staged(c, p, W, H, &norm, rows_local, rgba, nu, iter, stream, reserve_only, out_frame);
-        /* A WHOLE frame whose sample grid is larger (a print export: 8192^2 at aa 3 is 6e8 samples, 46 GB of sample planes and
-         * survivor stream) goes through the same scratch band by band: contiguous bands of whole sub-tile rows, each rendered as
-         * the one strip of "part b of B" straight into the caller's planes (FR_LAYOUT_FRAME addressing), one after the other on
-         * the stream.  Same samples, same sums: bit-identical (test_staged_ssaa_is_bit_identical_to_the_sample_loop).  Row-strip shards keep the sample
-         * loop above the cap: a band of a shard is not a shard. */
-        if (lean_ok && !fits && norm.nparts == 1 && !out_frame && (uint64_t)W * aa * 8u * aa <= band_cap) {
-            const uint64_t per_row = (uint64_t)W * aa * aa;                     /* samples per pixel row */
-            uint32_t band_rows = (uint32_t)(band_cap / per_row) & ~7u;           /* whole sub-tile rows, >= 8 by the test above */
-            if (band_rows > H) band_rows = (H + 7u) & ~7u;
-            const uint32_t nbands = (H + band_rows - 1u) / band_rows;
-            const bool timed = c->timing;
-            if (timed && !reserve_only) FR_HIP_TRY(hipEventRecord(c->ev_begin, stream));
-            c->timing = false;                                                   /* one event pair around all bands */
-            int st = FR_OK;
-            for (uint32_t b = 0; b < nbands && st == FR_OK; ++b) {
-                const fr_shard band = {b, nbands, band_rows};
-                st = enqueue_ssaa_staged(c, p, W, H, &band, fr_shard_rows(&band, H), rgba, nu, iter, stream, reserve_only, true);
-                if (reserve_only) break;                                         /* the first band is the largest */
-            }
-            c->timing = timed;
-            if (st == FR_OK && timed && !reserve_only) {
-                FR_HIP_TRY(hipEventRecord(c->ev_end, stream));
-                c->have_timing = true;
-            }
-            return st;
-        }
-    }
+    if (plan.route == kRouteSsaaStaged)
+        return enqueue_ssaa_staged(c, p, W, H, &norm, rows_local, rgba, nu, iter, stream, reserve_only, out_frame);
+    if (plan.route == kRouteSsaaBanded) return enqueue_ssaa_banded(c, p, W, H, plan, rgba, nu, iter, stream, reserve_only);
+    if (ssaa_of > 1 && !plan.lean()) return fr_set_error(FR_ERR_INTERNAL, "staged SSAA reached a render the lean tile kernel does not serve");
 
     LaunchArgs a;
     fill_params(a, p);
-    a.ssaa = ssaa_of > 1 ? ssaa_of : 0;
-    a.res_w = (int32_t)res_w; a.res_h = (int32_t)res_h;
-    a.W = (int32_t)W; a.H = (int32_t)H;
-    a.rows_local = (int32_t)rows_local;
-    a.part = (int32_t)norm.part; a.nparts = (int32_t)norm.nparts; a.rows_per_strip = (int32_t)norm.rows_per_strip;
-    a.out_frame = out_frame ? 1 : 0;
-    a.rgba = reinterpret_cast<float4*>(rgba);
-    a.nu = nu; a.iter = iter;
-    a.log2_tab = c->log2_tab;
+    fill_geometry(a, c, p, W, H, norm, rows_local, out_frame, ssaa_of, res_w, res_h);
+    a.rgba = reinterpret_cast<float4*>(rgba); a.nu = nu; a.iter = iter;
+    c->last_grid = plan.grid; c->last_pool_closing = -1;
+    int st = grow_device(&c->stream_buf, &c->stream_bytes, plan.stream_bytes);      /* the context scratch the plan needs */
+    if (st == FR_OK) st = grow_device(&c->coord_buf, &c->coord_bytes, plan.coord_bytes);
+    if (st != FR_OK || reserve_only) return st;
 
-    /* escape is absorbing (see escape_run): bailout^2 in [4.5, 1e12], and for Julia |c| <= bailout;
-     * Mandelbrot lanes with |c| > bailout retire at i = 0 inside the first, tested block */
-    {
-        const double B2 = f64 ? (double)p->bailout * (double)p->bailout
-                              : (double)(p->bailout * p->bailout);
-        const double c2 = a.julia_cx * a.julia_cx + a.julia_cy * a.julia_cy;
-        a.fast_ok = (B2 >= 4.5 && B2 <= 1e12 && (!julia || c2 <= B2)) ? 1 : 0;
-        /* 4 bailout^2 as the kernels form it: B * B in the kernel's precision, times 4 (exact) */
-        const float b2f = p->bailout * p->bailout;
-        a.b2x4_d = 4.0 * ((double)p->bailout * (double)p->bailout);
-        a.b2x4_f = 4.0f * b2f;
-    }
-
-    /* host-prepared reciprocals; the divide-free viewport map is enabled only when verified exact */
-    a.inv_w_d = 1.0 / (double)W;  a.inv_h_d = 1.0 / (double)H;
-    a.inv_w_f = 1.0f / (float)W;  a.inv_h_f = 1.0f / (float)H;
-    a.aspect_d = (double)W / (double)H;
-    a.aspect_f = (float)W / (float)H;
-    a.exact_div_ok = exact_division_ok(c, W, H, uv_map, f64) ? 1 : 0;
-
-    int bounds[kMaxStages];
-    int nstage = plan_stages(c, p, effects, (size_t)rows_local * W, false, bounds);
-    const bool staged = nstage > 1;
-    c->last_pool_closing = -1;
     /* does this render's lane pool look for cycles?  (fr_ctx_reserve sizes for the pool that looks: the shorter tile pass
      * leaves more survivors.) */
-    const bool pool_looks = staged && !m_effects_lean &&           /* (a closed cycle has no z after max_iter updates) */
-                            (reserve_only ? c->tune_periodicity >= 0 : pool_wants_cycle_closing(c, p, W, rows_local));
-    if (staged && !pool_looks) nstage = plan_stages(c, p, effects, (size_t)rows_local * W, true, bounds);   /* (still two passes) */
-    /* survivor-stream writers move to the next region after every block: the regions come out equally
-     * long with the same mix of blocks, so the reading pass is balanced with little stealing (measured,
-     * profiles/r01_region_rotation.txt: C2 0.883 -> 0.831 ms, C3 0.598 -> 0.539 ms; regions by XCD = 1) */
-    const uint32_t rotate_regions = c->tune_stream_rotate == 1u ? 0u : 1u;
-    const int shape = c->tune_shape ? (int)c->tune_shape : 3;
-
-    /* bounded, cheap items: the staged tile pass, and an unstaged pass whose samples run at most 128 updates
-     * (measured at max_iter <= 32: 0.31 ms with short runs -- the queue words saturate -- 0.17 ms with long) */
-    const int aa1 = p->antialiasing_samples > 1 ? p->antialiasing_samples : 1;
-    const bool bounded = staged || (!effects && (long long)max_iter * aa1 * aa1 <= 128);
-    /* items of moderate cost (an unstaged pass below the staging threshold): short runs as for unbounded items, but
-     * the waves stop at their home shard -- the blocks of 16 sub-tiles dealt round-robin keep the shards level */
-    const bool moderate = !staged && !effects && (long long)max_iter * aa1 * aa1 < 768;
-    /* The fp64 tile kernel holds 5 workgroups of 256 threads per CU (the per-wave timeline of the diag buffer
-     * shows workgroups beyond the resident set only start when resident ones exit, and find the queue dry):
-     * launch exactly the resident set.  Measured 5 vs 4: C2 +1.9 %, C3 +5.6 %, C5 +1.7 %; 6-8 (the one-sample
-     * kernel fits 7 at 69 VGPRs) within 1 %. */
-    /* the staged lean tile kernel in fp32 (52 VGPRs, 8.5 KB of LDS) holds 6: C3 -1.4 %
-     * (fp32 only: the fp64 instantiation's 82 VGPRs leave room for 5 waves per SIMD) */
-    const bool lean_staged = !f64 && staged && !effects && p->antialiasing_samples <= 1 && shape == 3 && c->tune_tile_kernel != 1u &&
-                             (norm.nparts == 1 || norm.rows_per_strip % 8u == 0u);
-    uint32_t grid = 0;
-    const QueueArgs tq = plan_tile_queue(c, W, rows_local, shape, bounded, moderate, lean_staged ? 6u : 5u, &grid);
-    auto clamp_shift = [&](int v) { v += c->tune_shift_bias; return (uint32_t)(v < 0 ? 0 : (v > 31 ? 31 : v)); };
-    c->last_grid = grid;
-
-    /* ---- survivor streams in context scratch ------------------------------------------------------------ */
-    /* the pool / stream kernels hold 6 workgroups per CU; their blocks are latency bound (dequeue -> record
-     * loads -> iterate -> scattered stores), so run all of them */
-    uint32_t sgrid = (uint32_t)c->compute_units * (c->tune_stream_wg_per_cu ? c->tune_stream_wg_per_cu : 6u);
-    {   /* small frames: at most one wave per 8 sub-tiles of the frame (every survivor block holds 64 records, and
-         * a frame rarely leaves more than a quarter of its pixels alive after the tile pass: ~2 blocks per wave;
-         * 1080p at max_iter 1024: 0.144 ms with 6 workgroups per CU, 0.128 ms with the 4 this cap gives) */
-        const uint32_t per_wg = c->tune_pool_items_per_wg ? c->tune_pool_items_per_wg : 32u;
-        const uint32_t cap = (tq.n_items + per_wg - 1u) / per_wg;
-        if (sgrid > cap) sgrid = cap < 1u ? 1u : cap;
-    }
-    /* the survivor streams have as many regions as the tile queue has shards ("regions" overrides) */
-    const uint32_t nregions = c->tune_regions ? c->tune_regions : (1u << tq.ns_log2);
-    const uint32_t nregions_log2 = nregions == (uint32_t)kMaxShards ? 6u : 3u;
-    uint32_t region_blocks = 0;
-    if (staged) {
-        const int st = reserve_stream(c, (size_t)rows_local * W, julia ? 2 : 4, f64, grid > sgrid ? grid : sgrid, nregions,
-                                      &region_blocks);
-        if (st != FR_OK) return st;
-        if (c->debug_region_blocks && c->debug_region_blocks < region_blocks) region_blocks = c->debug_region_blocks;
-    }
-    /* the lean tile kernel: every one-sample render without effects on 8x8 sub-tiles whose row strips (if sharded) are
-     * whole sub-tile rows; "tile_kernel" = 1 keeps the general kernel (tests compare the two bitwise) */
-    const bool lean = !effects && p->antialiasing_samples <= 1 && shape == 3 && c->tune_tile_kernel != 1u &&
-                      (norm.nparts == 1 || norm.rows_per_strip % 8u == 0u);
-    if (ssaa_of > 1 && !lean) return fr_set_error(FR_ERR_INTERNAL, "staged SSAA reached a render the lean tile kernel does not serve");
-    if (lean) {
-        const size_t need = ((size_t)W + H) * sizeof(double);
-        if (need > c->coord_bytes) {
-            if (c->coord_buf) { (void)hipFree(c->coord_buf); c->coord_buf = nullptr; }
-            c->coord_bytes = 0;
-            FR_HIP_TRY(hipMalloc(&c->coord_buf, need));
-            c->coord_bytes = need;
-        }
-        a.xs = c->coord_buf;
-        a.yds = (uint8_t*)c->coord_buf + (size_t)W * (f64 ? sizeof(double) : sizeof(float));
-    }
-    if (reserve_only) return FR_OK;
-
-    /* the frame's device time (fr_ctx_last_kernel_ms) includes the small launch that prepares it */
-    if (c->timing) FR_HIP_TRY(hipEventRecord(c->ev_begin, stream));
-    /* the lean tile pass prepares its own control block and coordinate tables (lean_prologue: its first workgroups, the others
-     * wait on a word keyed by a per-context epoch) -- except on a capturing stream: a replayed launch would carry a stale epoch */
-    bool in_kernel_prologue = false;
-    if (lean && c->tune_prepare != 1u) {
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(stream, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusActive; }
-        in_kernel_prologue = cap == hipStreamCaptureStatusNone;
-    }
-    if (in_kernel_prologue) {
-        if (c->prologue_epoch >= 0x0FFFFFF0u) {                 /* 28 bits: start over behind a cleared word */
-            FR_HIP_TRY(hipMemsetAsync(c->d_ctrl + kReadyWord, 0, sizeof(uint32_t), stream));
-            c->prologue_epoch = 0;
-        }
-        const Feedback fb = feedback_of(c);
-        a.pro_ready = c->d_ctrl + kReadyWord;
-        a.pro_epoch = ++c->prologue_epoch << 4;
-        a.pro_ctrl = c->d_ctrl;
-        a.pro_ctrl_words = (uint32_t)((size_t)nstage * kStageWords);
-        a.pro_fb_flag = fb.dev_flag; a.pro_fb_host = fb.host_word; a.pro_prev_seq = fb.prev_seq;
-        uint32_t n = 8;
-        while (n > grid) n >>= 1;
-        a.pro_n = n ? n : 1u;
-    } else if (lean) {
-        hipError_t ep = by_variant(fractal, f64, [&](auto t, auto f) {
-            return launch_prepare<decltype(t), decltype(f)::value>(stream, a, c->d_ctrl, (uint32_t)((size_t)nstage * kStageWords), feedback_of(c)); });
-        if (ep != hipSuccess) return fr_set_error(FR_ERR_HIP, "prepare kernel launch failed: %s", hipGetErrorString(ep));
-    } else {
-        FR_HIP_TRY(clear_control_block(c, stream, nstage));
-    }
-
-    /* ---- tile pass ---------------------------------------------------------------------------------- */
-    a.q = tq;
-    a.q.heads = stage_heads(c, 0);
-    a.i0 = 0;
-    a.i1 = bounds[0];
-    a.exit_from = 0;
-    a.exit_cost = 0u;
-    if (staged && lean && c->tune_tile_exit != 1u) {
-        a.exit_cost = c->tune_tile_exit ? c->tune_tile_exit : kTileExitCost;
-        /* not in the first half of the budget (C5, b0 192: 4.22 -> 4.09 ms leaving from 64, 4.06 from 96; C2, b0 96: +-0.3 %
-         * whatever the rule -- profiles/r04_tile_occupancy_exit.txt) */
-        const uint32_t half = ((uint32_t)bounds[0] / 2u + 15u) / 16u * 16u;
-        a.exit_from = (int32_t)(c->tune_tile_exit_from ? c->tune_tile_exit_from : (half > kTileExitFrom ? half : kTileExitFrom));
-    }
-    a.out.overflow = c->overflow_dev;                           /* (the prologue's timeout reports through it too) */
-    if (staged) {
-        a.out.base = (uint8_t*)c->stream_buf;
-        a.out.n_blocks = stage_counter(c, 0);
-        a.out.region_blocks = region_blocks;
-        a.out.rotate = rotate_regions;
-        a.out.nregions = nregions;
-        a.out.overflow = c->overflow_dev;
-    }
-    a.diag = c->diag;
-    hipError_t e;
-    if (effects) {
-        e = by_variant(fractal, f64, [&](auto t, auto f) {
-            constexpr int F = decltype(f)::value == 1 ? 0 : decltype(f)::value;      /* Julia has no effects variant */
-            return launch_tile<decltype(t), F, true>(shape, dim3(grid), stream, a); });
-    } else {
-        /* a pass that runs its samples to max_iter closes cycles in escape_run: SSAA (any shape; always compiled in) and
-         * the one-sample kernel with 8x8 sub-tiles (its PERIOD instantiation, launch_tile) */
-        a.period_window = !staged && !m_effects_lean ? period_window(c) : 0u;   /* a staged tile pass hands its survivors on */
-        if (lean && m_effects_lean)
-            e = f64 ? launch_tile_lean_stripes<double>(dim3(grid), stream, a) : launch_tile_lean_stripes<float>(dim3(grid), stream, a);
-        else if (lean)
-            e = by_variant(fractal, f64, [&](auto t, auto f) {
-                return launch_tile_lean<decltype(t), decltype(f)::value>(c->tune_tile_pixels == 1u ? 1 : 2, dim3(grid), stream, a); });
-        else
-            e = by_variant(fractal, f64, [&](auto t, auto f) {
-                return launch_tile<decltype(t), decltype(f)::value, false>(shape, dim3(grid), stream, a); });
-    }
-    if (e != hipSuccess) return fr_set_error(FR_ERR_HIP, "tile kernel launch failed: %s", hipGetErrorString(e));
-
-    /* ---- lane-pool pass: the survivors, to max_iter ------------------------------------------------------ */
-    if (staged) {
-        a.i0 = bounds[0];
-        a.i1 = max_iter;
-        a.pro_ready = nullptr;
-        a.in = a.out;                                           /* what the tile pass wrote */
-        a.in.n_blocks = stage_counter(c, 0);
-        memset(&a.out, 0, sizeof(a.out));                       /* the pool pass runs everything out ... */
-        a.out.overflow = c->overflow_dev;                       /* ... and reports a stretch loop that will not end */
-        memset(&a.q, 0, sizeof(a.q));
-        a.q.heads = stage_heads(c, 1);
-        a.q.ns_log2 = nregions_log2;                            /* region r of the input stream is shard r of this queue */
-        const uint32_t swps = (sgrid * 4u + nregions - 1) / nregions;
-        a.q.run_shift = clamp_shift((int)ceil_log2(2u * swps));
-        /* a lane-pool wave holds its claimed blocks as a private reserve and only stalls for a dequeue
-         * once per reserve, so claim little and never ahead: what a wave has reserved when the queue
-         * runs dry is exactly the tail of the pass (measured: 1-3 block runs + one run prefetched left
-         * a 315 us drain on C2; a block of 64 interior records is ~60 us of work at 5 waves/SIMD).
-         * ONE block per claim since round 3 (runs of 1-2 before): C2 -3.1 %, 1080p/1024 -0.9 %, C3 / C5 / C4 within
-         * +-1 % (profiles/r03_b0_and_pool_tuning.txt) */
-        a.q.run_min = c->tune_stream_run_min ? c->tune_stream_run_min : 1u;
-        a.q.run_max = c->tune_stream_run_max ? c->tune_stream_run_max : 1u;
-        if (a.q.run_min > a.q.run_max) a.q.run_min = a.q.run_max;
-        {
-            uint32_t probes = c->tune_stream_probes ? c->tune_stream_probes : (rotate_regions ? 4u : 0u);
-            if (sgrid < 64u || sgrid < nregions) probes = 0;
-            a.q.flags = probes << kQueueProbeShift;
-        }
-        a.diag = c->diag ? c->diag + c->diag_stride : nullptr;
-        /* finished lanes wait until this many are idle: 24 in fp32, 16 in fp64 (where a retire + refill round is cheaper
-         * relative to an update: C5 -1.5 %, 1080p/1024 -1.8 %, C2 / C4 unchanged; the fp32 dust +1.5 % with 16) */
-        a.pool_refill_at = c->tune_pool_refill ? c->tune_pool_refill : (f64 ? 16u : 24u);
-        if (a.pool_refill_at > 64u) a.pool_refill_at = 64u;
-        a.period_window = pool_looks ? period_window(c) : 0u;
-        c->last_pool_closing = a.period_window != 0u;
-        a.closed_flag = c->d_ctrl + kFeedbackWord;
-        if (m_effects_lean)
-            e = f64 ? launch_pool_stripes<double>(dim3(sgrid), stream, a) : launch_pool_stripes<float>(dim3(sgrid), stream, a);
-        else
-            e = by_variant(fractal, f64, [&](auto t, auto f) {
-                return launch_stream_pool<decltype(t), decltype(f)::value>(dim3(sgrid), stream, a); });
-        if (e != hipSuccess) return fr_set_error(FR_ERR_HIP, "lane-pool kernel launch failed: %s", hipGetErrorString(e));
-    }
-    return finish_render(c, stream, nstage);
+    const bool pool_looks = plan.pool_may_look && pool_wants_cycle_closing(c, p, W, rows_local);
+    const int nstages = plan.staged() && !pool_looks ? plan.nstages_all : plan.nstages;   /* (2 either way but for a forced schedule
+                                                     with max_iter < 2 b0 of the pool that runs everything: 1, though both passes run) */
+    if ((st = begin_frame(c, plan, nstages, p, a, stream)) != FR_OK) return st;
+    if ((st = launch_tile_pass(c, plan, p, a, pool_looks, stream)) != FR_OK) return st;
+    if (plan.staged() && (st = launch_pool_pass(c, plan, p, a, pool_looks, stream)) != FR_OK) return st;
+    return finish_render(c, stream, nstages);
 }
 
+/* staged SSAA: the sample grid as a render of its own into context scratch, then the average */
 static int enqueue_ssaa_staged(fr_ctx* c, const fr_params* p, uint32_t W, uint32_t H, const fr_shard* norm, uint32_t rows_local,
                                float* rgba, void* nu, int32_t* iter, hipStream_t stream, bool reserve_only, bool out_frame)
 {
     const uint32_t aa = (uint32_t)p->antialiasing_samples;
     const uint32_t Ws = W * aa, Hs = H * aa;
+    fr_params q = *p;
+    q.antialiasing_samples = 1;
+    q.flags &= ~FR_FLAG_POST_CHAIN;                            /* the post chain follows the average */
+    const fr_shard sh = {norm->part, norm->nparts, norm->rows_per_strip * aa};
     const size_t nsamp = (size_t)rows_local * aa * Ws;
     const bool f64 = p->precision == FR_PRECISION_F64;
     const size_t nu_elt = f64 ? 8 : 4;
     /* sample planes: colour, then nu, then iter -- only those the caller's planes need */
     const size_t off_nu = rgba ? nsamp * 16 : 0, off_iter = off_nu + (nu ? nsamp * nu_elt : 0), need = off_iter + (iter ? nsamp * 4 : 0);
-    if (need > c->ssaa_bytes) {
-        if (c->ssaa_buf) { (void)hipFree(c->ssaa_buf); c->ssaa_buf = nullptr; c->ssaa_bytes = 0; }
-        FR_HIP_TRY(hipMalloc(&c->ssaa_buf, need));
-        c->ssaa_bytes = need;
-    }
+    int st = grow_device(&c->ssaa_buf, &c->ssaa_bytes, need);
+    if (st != FR_OK) return st;
     char* base = (char*)c->ssaa_buf;
     float* s_rgba = rgba ? (float*)base : nullptr;
     void* s_nu = nu ? (void*)(base + off_nu) : nullptr;
     int32_t* s_iter = iter ? (int32_t*)(base + off_iter) : nullptr;
-    fr_params q = *p;
-    q.antialiasing_samples = 1;
-    q.flags &= ~FR_FLAG_POST_CHAIN;                            /* the post chain follows the average */
-    const fr_shard sh = {norm->part, norm->nparts, norm->rows_per_strip * aa};
-    int st = enqueue_render(c, &q, Ws, Hs, &sh, s_rgba, s_nu, s_iter, stream, reserve_only, false, (int)aa, W, H);
+    st = enqueue_render(c, &q, Ws, Hs, &sh, s_rgba, s_nu, s_iter, stream, reserve_only, false, (int)aa, W, H);
     if (st != FR_OK || reserve_only) return st;
     SsaaArgs r;
     r.s_rgba = reinterpret_cast<const float4*>(s_rgba); r.s_nu = s_nu; r.s_iter = s_iter;
@@ -1720,11 +1320,8 @@ static int render_sync(fr_ctx* c, const fr_params* p, uint32_t W, uint32_t H, co
     const size_t nu_bytes = (p->precision == FR_PRECISION_F64 && p->fractal_type != FR_FRACTAL_DEEP_ZOOM) ? 8 : 4;
     if (host) {
         const size_t off_nu = npx * 16, off_iter = off_nu + npx * 8, need = off_iter + npx * 4;
-        if (need > c->scratch_bytes) {
-            if (c->scratch) { (void)hipFree(c->scratch); c->scratch = nullptr; c->scratch_bytes = 0; }
-            FR_HIP_TRY(hipMalloc(&c->scratch, need));
-            c->scratch_bytes = need;
-        }
+        const int gs = grow_device(&c->scratch, &c->scratch_bytes, need);
+        if (gs != FR_OK) return gs;
         char* base = (char*)c->scratch;
         rgba = out->rgba ? (float*)base : nullptr;
         nu = out->nu ? (void*)(base + off_nu) : nullptr;
@@ -1765,6 +1362,66 @@ extern "C" int fr_ctx_reserve(fr_ctx* c, const fr_params* p, uint32_t W, uint32_
     FR_HIP_TRY(hipStreamSynchronize(c->stream));
     if (c->render_on_user_stream && c->have_render) FR_HIP_TRY(hipStreamSynchronize(c->last_stream));
     return enqueue_render(c, p, W, H, shard, nullptr, nullptr, nullptr, c->stream, true);
+}
+
+/* ---- fr_plan_describe (fr_tuning.h): the plan of a render as a flat record of integers, with no context and no device.
+ * Of a staged or banded SSAA render the record holds the route and, from "W" on, the plan of the sample-grid render
+ * (of the first band, which is the largest).  A part that owns no rows: all zero. */
+static const char kPlanFields[] =
+    "route nbands band_rows W H rows_local rows_per_strip family shape tile_pixels nstages nstages_all wg_per_cu grid sgrid nregions "
+    "rotate_regions bounded moderate exit_cost exit_from_look exit_from_all pool_refill_at tile_period_window pool_may_look "
+    "b0_look b0_all region_blocks stream_bytes coord_bytes tq_nsx tq_nsx_shift tq_n_items tq_n_blk tq_ns_log2 tq_run_shift "
+    "tq_run_min tq_run_max tq_flags pq_ns_log2 pq_run_shift pq_run_min pq_run_max pq_flags";
+constexpr int kPlanFieldCount = 44;
+
+extern "C" const char* fr_plan_fields(void) { return kPlanFields; }
+
+extern "C" int fr_plan_describe(const fr_params* p, uint32_t W, uint32_t H, const fr_shard* shard, int compute_units,
+                                const char* const* names, const int64_t* values, int n_tunings, int64_t* out, int n_out)
+{
+    if (!p || !out || (n_tunings > 0 && (!names || !values))) return fr_set_error(FR_ERR_INVALID_ARG, "fr_plan_describe: NULL argument");
+    if (n_out != kPlanFieldCount) return fr_set_error(FR_ERR_INVALID_ARG, "fr_plan_describe: the record has %d fields", kPlanFieldCount);
+    Tuning tune;
+    memset(&tune, 0, sizeof(tune));
+    for (int i = 0; i < n_tunings; ++i) {
+        int st = tuning_set(tune, names[i], values[i]);
+        if (st == kNotMine) st = option_set(tune, names[i], values[i]);
+        if (st == kNotMine) return fr_set_error(FR_ERR_INVALID_ARG, "unknown tuning name '%s'", names[i]);
+        if (st != FR_OK) return st;
+    }
+    memset(out, 0, sizeof(int64_t) * kPlanFieldCount);
+    fr_shard norm;
+    uint32_t rows_local = 0;
+    const int sh = normalise_shard(shard, H, &norm, &rows_local);
+    if (sh != FR_OK || rows_local == 0) return sh;
+    RenderPlan r = plan_render(tune, compute_units, p, W, H, norm, rows_local, 0);
+    const int route = r.route;
+    const uint32_t nbands = r.nbands, band_rows = r.band_rows;
+    fr_params q = *p;
+    if (route == kRouteSsaaStaged || route == kRouteSsaaBanded) {
+        const fr_shard band = {0, nbands, band_rows};
+        if (route == kRouteSsaaBanded) { norm = band; rows_local = fr_shard_rows(&band, H); }
+        const uint32_t aa = (uint32_t)p->antialiasing_samples;      /* the sample grid, as enqueue_ssaa_staged makes it */
+        const fr_shard grid_shard = {norm.part, norm.nparts, norm.rows_per_strip * aa};
+        q.antialiasing_samples = 1;
+        W *= aa; H *= aa;
+        const int gs = normalise_shard(&grid_shard, H, &norm, &rows_local);
+        if (gs != FR_OK) return gs;
+        r = plan_render(tune, compute_units, &q, W, H, norm, rows_local, p->antialiasing_samples);
+        if (!r.lean()) return fr_set_error(FR_ERR_INTERNAL, "staged SSAA reached a render the lean tile kernel does not serve");
+    }
+    int64_t* o = out;
+    *o++ = route; *o++ = nbands; *o++ = band_rows;
+    if (route == kRouteDeepZoom) return FR_OK;
+    const int64_t rest[] = {W, H, rows_local, norm.rows_per_strip, r.family, r.shape, r.tile_pixels, r.nstages, r.nstages_all, r.wg_per_cu, r.grid,
+                            r.sgrid, r.nregions, r.rotate_regions, r.bounded, r.moderate, r.exit_cost, r.exit_from[1], r.exit_from[0],
+                            r.pool_refill_at, r.tile_period_window, r.pool_may_look, r.b0[1], r.b0[0], r.region_blocks,
+                            (int64_t)r.stream_bytes, (int64_t)r.coord_bytes, r.tq.nsx, r.tq.nsx_shift, r.tq.n_items, r.tq.n_blk,
+                            r.tq.ns_log2, r.tq.run_shift, r.tq.run_min, r.tq.run_max, r.tq.flags, r.pq.ns_log2, r.pq.run_shift,
+                            r.pq.run_min, r.pq.run_max, r.pq.flags};
+    static_assert(sizeof(rest) / sizeof(rest[0]) == kPlanFieldCount - 3, "one value per name of kPlanFields");
+    memcpy(o, rest, sizeof(rest));
+    return FR_OK;
 }
 
 extern "C" int fr_ctx_last_deep_steps(fr_ctx* c, uint64_t out[3])
@@ -2009,11 +1666,8 @@ static int export_sync(fr_ctx* c, const float* rgba, uint32_t W, uint32_t H, OUT
     OUT* d_out = out;
     if (memory == FR_MEM_HOST) {
         const size_t need = npx * 16 + npx * 3 * sizeof(OUT);
-        if (need > c->scratch_bytes) {
-            if (c->scratch) { (void)hipFree(c->scratch); c->scratch = nullptr; c->scratch_bytes = 0; }
-            FR_HIP_TRY(hipMalloc(&c->scratch, need));
-            c->scratch_bytes = need;
-        }
+        const int gs = grow_device(&c->scratch, &c->scratch_bytes, need);
+        if (gs != FR_OK) return gs;
         FR_HIP_TRY(hipMemcpyAsync(c->scratch, rgba, npx * 16, hipMemcpyHostToDevice, c->stream));
         d_in = reinterpret_cast<const float4*>(c->scratch);
         d_out = reinterpret_cast<OUT*>((uint8_t*)c->scratch + npx * 16);
@@ -2079,11 +1733,8 @@ extern "C" int fr_render_frame_png(fr_ctx* c, const fr_params* p, uint32_t W, ui
     FR_HIP_TRY(hipSetDevice(c->device));
     const size_t npx = (size_t)W * H;
     const size_t need = npx * 16 + npx * 3;
-    if (need > c->frame_bytes) {
-        if (c->frame_buf) { (void)hipFree(c->frame_buf); c->frame_buf = nullptr; c->frame_bytes = 0; }
-        FR_HIP_TRY(hipMalloc(&c->frame_buf, need));
-        c->frame_bytes = need;
-    }
+    const int gs = grow_device(&c->frame_buf, &c->frame_bytes, need);
+    if (gs != FR_OK) return gs;
     fr_params q = *p;
     if (q.fractal_type != FR_FRACTAL_DEEP_ZOOM) q.flags |= FR_FLAG_POST_CHAIN;   /* the storage image holds the post-chained colour;
                                                                                      the deep-zoom shader has no post chain */

@@ -60,6 +60,21 @@ int fr_ctx_set_tuning(fr_ctx* ctx, const char* name, int64_t value);
  * render had no lane pool */
 int fr_ctx_last_pool_closing(const fr_ctx* ctx);
 
+/* The schedule of a render as a flat record of integers (fr_plan.h: plan_render), decided from the request, a compute-unit
+ * count and tunings alone: no context, no device.  names / values: n_tunings fr_ctx_set_tuning names (and the scheduling
+ * names of fr_ctx_set_option: "periodicity", "staging", "shards", "tile_kernel") applied in order to the automatic
+ * choices.  out receives one value per name of fr_plan_fields() (space separated; n_out = their number).  Of a staged or
+ * banded SSAA render the record holds the route and the plan of the sample-grid render (of the first band).  The request
+ * is one with FR_LAYOUT_PACKED planes: a whole frame in FR_LAYOUT_FRAME planes is never banded (it takes the sample loop).
+ *   route   0 this part owns no rows, 1 direct, 2 Deep_Zoom, 3 staged SSAA, 4 staged SSAA in nbands bands of band_rows rows
+ *   family  0 general tile kernel, 1 its effects variant, 2 its sample loop, 3 lean, 4 lean stripes
+ *   nstages_all  what the stage schedule answers for a pool that runs every survivor out: the stages whose control words
+ *           such a render clears (the render itself is nstages passes)
+ *   b0_look / b0_all, exit_from_look / exit_from_all: for a lane pool that looks for cycles / runs every survivor out */
+int fr_plan_describe(const fr_params* params, uint32_t width, uint32_t height, const fr_shard* shard, int compute_units,
+                     const char* const* names, const int64_t* values, int n_tunings, int64_t* out, int n_out);
+const char* fr_plan_fields(void);
+
 /* RCCL leg of fr_node on ONE device (fr_node.cpp): plugin load, one-rank communicator, a grouped ncclSend / ncclRecv of
  * `bytes` bytes to itself on a stream, compared on the host.  *rccl_version receives ncclGetVersion(). */
 int fr_node_rccl_selftest(int device, size_t bytes, int* rccl_version);

@@ -51,6 +51,10 @@ CASES = {
     "interior": (40, 30, dict(max_iterations=128, center_x=0.0, center_y=0.0, zoom=0.6)),
     "post": (32, 24, dict(max_iterations=64, color_brightness=1.2, color_saturation=0.8, color_contrast=1.1)),
     "post_floors": (32, 24, dict(max_iterations=64, color_brightness=0.02, color_saturation=-1.0, color_contrast=0.0)),
+    # one full block of 16 updates (two) and a tail of one: escapes at i = 16 (7 samples) and at i = 32 (4 samples; the
+    # centre of tail_17 has only 2 of them at this size, so tail_33 sits 1.1 pixels left and half a pixel up)
+    "tail_17": (24, 16, dict(max_iterations=17, center_x=-0.45, center_y=0.55, zoom=0.4)),
+    "tail_33": (24, 16, dict(max_iterations=33, center_x=-0.4775, center_y=0.5375, zoom=0.4)),
 }
 
 DEFAULTS = dict(center_x=-0.5, center_y=0.0, zoom=3.0, max_iterations=256, julia_c_real=JC[0], julia_c_imag=JC[1],

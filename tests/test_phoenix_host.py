@@ -11,6 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import phoenix_cases
 import phoenix_ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -170,6 +171,11 @@ def test_fixture_covers_the_issue_cases(phx):
     assert any(c[0] != c[1] for c in phx.values())
     assert any(c[5] is not None and np.nanmin(c[5]) < 0 for c in phx.values()), "no case with smooth < 0"
     assert any(c[4] is not None and (c[4] == c[2]["max_iterations"]).mean() > 0.5 for c in phx.values()), "no interior-heavy case"
+    # full blocks of 16 updates followed by a tail, with escapes the executed shader put INTO the tail
+    assert {17, 33} <= {p["max_iterations"] for p in ps}
+    for max_iter in (17, 33):
+        tails = [phoenix_cases.tail_escapes(c[4], max_iter) for c in phx.values() if c[2]["max_iterations"] == max_iter]
+        assert tails and min(tails) >= 4, (max_iter, tails)
 
 
 def test_restatement_fp32_matches_the_executed_shader(phx):
@@ -199,6 +205,44 @@ def test_restatement_fp64_is_the_same_algorithm_at_wider_precision(phx):
         total += same.size
     assert agree / total >= 0.98
     assert max(medians) <= 1e-4 and float(np.median(medians)) <= 2e-6
+
+
+def test_orbit_cases_can_fail():
+    """What makes test_phoenix_orbit_gpu.py meaningful, shown on the restatement alone: the boundary cases have escapes in
+    every full block and in the tail (a loop that is off by one there changes an escape index) next to orbits that never
+    leave; the re-entry cases hold orbits that come back inside their block; and no case needs more of the colour exception
+    (_few: max(2, 0.1 %) of the frame, 2 on these frames) than its own reference can justify."""
+    for group, cases in phoenix_cases.GROUPS.items():
+        for name, case in cases.items():
+            max_iter = case[2]["max_iterations"]
+            it, sm, rgb = phoenix_cases.reference(case)
+            what = (group, name)
+            if group == "boundary":
+                if max_iter % 16:
+                    assert phoenix_cases.tail_escapes(it, max_iter) >= 4, what
+                else:
+                    assert phoenix_cases.tail_escapes(it, max_iter) == 0, what
+                blocks = phoenix_cases.block_escapes(it, max_iter)
+                assert len(blocks) == max_iter // 16 and all(n >= 4 for n in blocks), (what, blocks)
+                assert int((it == max_iter).sum()) >= 100, what
+            if group == "reentry":
+                assert phoenix_cases.reentries(case) >= 16, what
+            if group == "interior":
+                assert (it == max_iter).mean() > 0.5, what
+            assert phoenix_cases.near_wrap(case) <= 2, (what, phoenix_cases.near_wrap(case))
+            assert not np.isnan(rgb).any() and not (sm < 0).any(), what
+    # a tail that stops one update early shows only in samples that escape in the LAST update: every max_iter with a tail has
+    # them under at least one of the two parameter sets, in either precision (Classic has none at max_iter 47)
+    for max_iter in (15, 17, 31, 33, 47, 49, 63):
+        for f64 in (False, True):
+            last = [phoenix_cases.last_update_escapes(phoenix_cases.reference(c)[0], max_iter)
+                    for c in phoenix_cases.BOUNDARY.values() if (c[2]["max_iterations"], c[2]["f64"]) == (max_iter, f64)]
+            assert len(last) == 2 and max(last) >= 1, (max_iter, f64, last)
+    # the cases the GPU file is parametrised over
+    assert {c[2]["max_iterations"] for c in phoenix_cases.BOUNDARY.values()} == {15, 16, 17, 31, 32, 33, 47, 48, 49, 63}
+    assert {(c[0], c[1]) for c in phoenix_cases.RAGGED.values()} == {(9, 9), (65, 7), (1, 1)}
+    for group, cases in phoenix_cases.GROUPS.items():
+        assert {c[2]["f64"] for c in cases.values()} == ({True} if group in ("colour_f64", "julia_f64") else {False, True})
 
 
 def test_julia_mode_frames_are_flat(phx):

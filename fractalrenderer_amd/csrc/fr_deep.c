@@ -608,7 +608,8 @@ int fr_deepx_validate(const fr_params* p, const fr_deepx_view* v, uint32_t width
         return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deepx: the orbit trap, stripes and interior_style 2 need the whole "
                             "orbit and are not available");
     if (p->flags & FR_FLAG_DEEP_BLA)
-        return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deepx: FR_FLAG_DEEP_BLA is not available (the table is fp64)");
+        return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deepx: FR_FLAG_DEEP_BLA is not available (its table is fp64): the flag of "
+                            "extended views is FR_FLAG_DEEPX_BLA");
     double zm;
     int32_t ze, F;
     if ((st = fr_deepx_resolve(v, &zm, &ze, &F)) != FR_OK) return st;

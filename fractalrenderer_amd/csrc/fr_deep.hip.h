@@ -30,6 +30,12 @@
  * the mantissa and exponent arrays, alignment is v_ldexp_f64, and the one normalisation per step takes its exponent with
  * v_frexp_exp_i32_f64 off max(|x|, |y|); the mode test is an integer compare.  Z_m and Z_{m+1} stay in registers in the
  * lane's mode and Z_{m+2} is fetched one step ahead from that mode's arrays; a lane that changes mode reloads both.
+ *
+ * BLA for extended views (FR_FLAG_DEEPX_BLA; the semantics are in the header): deepx_bla_level_kernel builds a table whose
+ * (A, B, r) carry int32 exponents from the extended orbit arrays, one launch per level, and deep_kernel<DeepXBlaArgs> runs
+ * deep_orbit_x_bla: deep_orbit_x whose lanes, in either mode, probe the table as deep_orbit_bla does and take a BLA step in
+ * extended arithmetic.  A probe gathers 8 bytes (r as a float mantissa and an int32 exponent); the chosen level's A and B
+ * are 32 bytes of mantissas and 8 bytes of exponents in arrays of their own.
  */
 #pragma once
 #include "fr_kernels.hip.h"
@@ -371,18 +377,303 @@ __device__ __forceinline__ void deep_orbit_x(const DeepXArgs& AA, const double c
     }
 }
 
+/* ---- BLA for extended views (FR_FLAG_DEEPX_BLA; the semantics are in the header) -----------------------------------------
+ * The table of the extended orbit: per entry the radius r as 8 bytes (XRad: the top 24 bits of its mantissa as a float and
+ * its int32 exponent -- what a probe gathers), and apart from it (A, B) as two double2 of normalised mantissas with their
+ * two exponents in an int2, loaded for the chosen level only.  Levels and offsets are those of the fp64 table. */
+struct XRad {
+    float v;                             /* mantissa in [0.5, 1), 0 for r = 0 */
+    int32_t e;                           /* FR_DEEPX_ZERO_EXP for r = 0 */
+};
+
+struct BlaXTable {
+    const XRad* r;                       /* r of every entry, level 1 first */
+    const double2* ab;                   /* mantissas of A, B: ab[2 e], ab[2 e + 1] */
+    const int2* abe;                     /* (A.e, B.e) */
+    int32_t levels;                      /* K = floor(log2(N - 1)), 0 = no table */
+    unsigned long long* steps;           /* single steps, BLA steps, updates skipped: one atomic add each per wave */
+};
+
+struct DeepXBlaArgs {
+    DeepXArgs x;
+    BlaXTable t;
+};
+
+constexpr int kXBlaExpLim = 1 << 27;     /* an entry whose A.e or B.e leaves [-2^27, 2^27] is void */
+
+/* an extended real normalised: v into [0.5, 1), zero gets FR_DEEPX_ZERO_EXP */
+__device__ __forceinline__ void x_norm1(double& v, int& e)
+{
+    const int k = __builtin_amdgcn_frexp_exp(v);
+    e = v == 0.0 ? kXZero : e + k;
+    v = __builtin_ldexp(v, -k);
+}
+
+/* the top 24 bits of a mantissa in [0.5, 1) (toward zero): exactly a float */
+__device__ __forceinline__ double x_trunc24(const double v)
+{
+    return __longlong_as_double(__double_as_longlong(v) & ~((1ll << 29) - 1));
+}
+
+/* Level k of the extended table.  Level 0 is the single step at m = 1 + i (A = norm(Z_m.x, Z_m.y, Z_m.e + 1), B = norm(1, 0, 0),
+ * r = 2^-53 |Z_m|), computed from the orbit and never stored. */
+__global__ void __launch_bounds__(kBlockThreads)
+deepx_bla_level_kernel(const double2* __restrict__ mant, const int32_t* __restrict__ exp2, const int32_t n_ref, const int32_t k,
+                       const double dcv, const int32_t dce, XRad* __restrict__ r, double2* __restrict__ ab,
+                       int2* __restrict__ abe)
+{
+    const uint32_t n1 = (uint32_t)(n_ref - 1);
+    const uint32_t cnt = n1 >> k;
+    const uint32_t off = bla_offset(n1, k);
+    const uint32_t offp = k > 1 ? bla_offset(n1, k - 1) : 0u;
+    for (uint32_t j = blockIdx.x * kBlockThreads + threadIdx.x; j < cnt; j += gridDim.x * kBlockThreads) {
+        double2 A[2], B[2];                                      /* x, y */
+        int eA[2], eB[2], eR[2];
+        double R[2];
+        if (k == 1) {
+            for (int s = 0; s < 2; ++s) {
+                const double2 z = mant[1 + s + 2 * j];
+                const int ez = exp2[1 + s + 2 * j];
+                A[s] = z; eA[s] = ez + 1;
+                x_norm(A[s].x, A[s].y, eA[s]);
+                B[s] = make_double2(0.5, 0.0); eB[s] = 1;
+                double nx = z.x, ny = z.y;
+                int ne = ez;
+                x_norm(nx, ny, ne);
+                R[s] = bla_abs(nx, ny); eR[s] = ne;
+                x_norm1(R[s], eR[s]);
+                if (R[s] != 0.0) eR[s] -= 53;
+            }
+        } else {
+            for (int s = 0; s < 2; ++s) {
+                const uint32_t e = offp + 2 * j + s;
+                const int2 ee = abe[e];
+                const XRad rr = r[e];
+                A[s] = ab[2 * e]; B[s] = ab[2 * e + 1]; eA[s] = ee.x; eB[s] = ee.y;
+                R[s] = (double)rr.v; eR[s] = rr.e;
+            }
+        }
+        double2 a = make_double2(A[1].x * A[0].x - A[1].y * A[0].y, A[1].x * A[0].y + A[1].y * A[0].x);
+        int ea = eA[1] + eA[0];
+        x_norm(a.x, a.y, ea);
+        const double px = A[1].x * B[0].x - A[1].y * B[0].y, py = A[1].x * B[0].y + A[1].y * B[0].x;
+        const int e1 = eA[1] + eB[0];
+        int eb = e1 > eB[1] ? e1 : eB[1];
+        double2 b = make_double2(__builtin_ldexp(px, e1 - eb) + __builtin_ldexp(B[1].x, eB[1] - eb),
+                                 __builtin_ldexp(py, e1 - eb) + __builtin_ldexp(B[1].y, eB[1] - eb));
+        x_norm(b.x, b.y, eb);
+        double bv = bla_abs(B[0].x, B[0].y), av = bla_abs(A[0].x, A[0].y);
+        int be = eB[0], ae = eA[0];
+        x_norm1(bv, be);
+        x_norm1(av, ae);
+        const double pv = bv * dcv;
+        const int pe = be + dce;
+        const int et = eR[1] > pe ? eR[1] : pe;
+        const double t = (__builtin_ldexp(R[1], eR[1] - et) - __builtin_ldexp(pv, pe - et)) / av;
+        double rv = (t > 0.0 && __builtin_isfinite(t)) ? t : 0.0;    /* NaN: 0 */
+        int re = et - ae;
+        x_norm1(rv, re);
+        if (!(re < eR[0] || (re == eR[0] && rv < R[0]))) { rv = R[0]; re = eR[0]; }
+        const int la = ea < 0 ? -ea : ea, lb = eb < 0 ? -eb : eb;
+        if (la > kXBlaExpLim || lb > kXBlaExpLim) {
+            rv = 0.0; re = kXZero;
+            a = make_double2(0.0, 0.0); ea = kXZero;
+            b = make_double2(0.0, 0.0); eb = kXZero;
+        }
+        const uint32_t e = off + j;
+        XRad out;
+        out.v = (float)x_trunc24(rv); out.e = re;
+        r[e] = out;
+        ab[2 * e] = a;
+        ab[2 * e + 1] = b;
+        abe[e] = make_int2(ea, eb);
+    }
+}
+
+/* deep_orbit_x with BLA: u replaces the loop index.  A lane at m >= 1, in either mode, probes the levels top down as
+ * deep_orbit_bla does, on its dz as a normalised extended number (a plain lane forms norm(dz.x, dz.y, 0)), and takes the
+ * first k with |dz|^2 < r^2; the step is then taken in extended arithmetic whatever the lane's mode, and the lane reloads
+ * Z_m, Z_{m+1} in the mode the step leaves it in.  No level's r exceeds 2^-53 |Z_m| < 2^(E - 52.5), E the exponent of Z_m's
+ * larger component normalised, and |dz| >= 2^(dz.e - 1): a lane with dz.e + 51 >= E cannot pass a probe and gathers nothing
+ * (E from the lane's own copy of Z_m: for a point below 2^-1022 the plain double's exponent is never below the true one).
+ * BLA lanes and single-step lanes of a wave take their steps in the same trip.  nsingle / nbla: the steps this sample took. */
+__device__ __forceinline__ void deep_orbit_x_bla(const DeepXArgs& AA, const BlaXTable& T, const double cx, const double cy,
+                                                 const int ec, bool live, int& esc, double& er2, uint32_t& nsingle,
+                                                 uint32_t& nbla)
+{
+    const DeepArgs& A = AA.d;
+    const double2* __restrict__ orbit = A.orbit;
+    const double2* __restrict__ mant = AA.mant;
+    const int32_t* __restrict__ exp2 = AA.exp2;
+    const XRad* __restrict__ tr = T.r;
+    const int N = A.n_ref, max_iter = A.max_iter, K = T.levels;
+    const uint32_t n1 = (uint32_t)(N - 1);
+    const double B2 = A.B2;
+    const double cpx = (cx != 0.0 && __builtin_amdgcn_frexp_exp(cx) + ec > -1022) ? __builtin_ldexp(cx, ec) : 0.0;
+    const double cpy = (cy != 0.0 && __builtin_amdgcn_frexp_exp(cy) + ec > -1022) ? __builtin_ldexp(cy, ec) : 0.0;
+    double dzx = 0.0, dzy = 0.0;                                 /* plain: dz; extended: its mantissas */
+    int ed = kXZero;
+    bool ext = true;
+    double Zx = 0.0, Zy = 0.0;                                   /* Z_m, in the lane's mode */
+    int eZ = kXZero;
+    const double2 z1 = mant[1];
+    const int e1 = exp2[1];
+    double Znx = z1.x, Zny = z1.y;                               /* Z_{m+1} */
+    int eZn = e1;
+    int m = 0, u = 0;
+    esc = max_iter;
+    er2 = 0.0;
+    nsingle = 0u; nbla = 0u;
+    for (;;) {
+        if (__builtin_amdgcn_ballot_w64(live) == 0ull) break;
+        if (!live) continue;
+        const int mn = m + 2 <= N ? m + 2 : N;                   /* Z_{m+2}, for the single step after this one */
+        int k = 0;
+        uint32_t e = 0u;
+        double qx = dzx, qy = dzy;                               /* dz, extended and normalised */
+        int qe = ed;
+        if (m >= 1) {
+            if (!ext) { qe = 0; x_norm(qx, qy, qe); }
+            const int eZm = (ext ? eZ : 0) + __builtin_amdgcn_frexp_exp(fmax(fabs(Zx), fabs(Zy)));
+            if (qe + 51 < eZm) {
+                const double dz2 = qx * qx + qy * qy;
+                const uint32_t mm = (uint32_t)(m - 1);
+                int kk = mm ? __builtin_ctz(mm) : K;
+                kk = kk < K ? kk : K;
+                const int kn = 31 - __builtin_clz((uint32_t)(N - m));
+                const int ki = 31 - __builtin_clz((uint32_t)(max_iter - u));
+                kk = kk < kn ? kk : kn;
+                kk = kk < ki ? kk : ki;
+                for (; kk >= 1; --kk) {
+                    const uint32_t ek = bla_offset(n1, kk) + (mm >> kk);
+                    const XRad r = tr[ek];
+                    const double rv = (double)r.v;
+                    if (dz2 < __builtin_ldexp(rv * rv, 2 * (r.e - qe))) { k = kk; e = ek; break; }
+                }
+            }
+        }
+        double ax, ay;                                           /* the next dz */
+        int ea = 0;
+        bool reb;
+        if (k > 0 || ext) {
+            double nx, ny, Wx, Wy;                               /* n and Z at the new m */
+            int en, eW, eZnn = 0;
+            double2 Znn = make_double2(0.0, 0.0);
+            if (k > 0) {
+                const double2 a = T.ab[2 * e], b = T.ab[2 * e + 1];
+                const int2 ee = T.abe[e];
+                const double px = a.x * qx - a.y * qy, py = a.x * qy + a.y * qx;
+                const double sx = b.x * cx - b.y * cy, sy = b.x * cy + b.y * cx;
+                const int ep = ee.x + qe, es = ee.y + ec;
+                en = ep > es ? ep : es;
+                nx = __builtin_ldexp(px, ep - en) + __builtin_ldexp(sx, es - en);
+                ny = __builtin_ldexp(py, ep - en) + __builtin_ldexp(sy, es - en);
+                m += 1 << k;
+                u += 1 << k;
+                ++nbla;
+                const double2 Wm = mant[m];
+                Wx = Wm.x; Wy = Wm.y; eW = exp2[m];
+            } else {
+                Znn = mant[mn];
+                eZnn = exp2[mn];
+                const int et = eZ + 1 > ed ? eZ + 1 : ed;
+                const double tx = __builtin_ldexp(Zx, eZ + 1 - et) + __builtin_ldexp(dzx, ed - et);
+                const double ty = __builtin_ldexp(Zy, eZ + 1 - et) + __builtin_ldexp(dzy, ed - et);
+                const double px = tx * dzx - ty * dzy;
+                const double py = tx * dzy + ty * dzx;
+                const int ep = et + ed;
+                en = ep > ec ? ep : ec;
+                nx = __builtin_ldexp(px, ep - en) + __builtin_ldexp(cx, ec - en);
+                ny = __builtin_ldexp(py, ep - en) + __builtin_ldexp(cy, ec - en);
+                ++m;
+                ++u;
+                ++nsingle;
+                Wx = Znx; Wy = Zny; eW = eZn;
+            }
+            const int ez = eW > en ? eW : en;
+            const double zx = __builtin_ldexp(Wx, eW - ez) + __builtin_ldexp(nx, en - ez);
+            const double zy = __builtin_ldexp(Wy, eW - ez) + __builtin_ldexp(ny, en - ez);
+            const double r2 = zx * zx + zy * zy;
+            const double r2d = __builtin_ldexp(r2, 2 * ez);
+            if (r2d > B2) {
+                esc = u - 1; er2 = r2d; live = false;             /* the last update the step covered */
+                continue;
+            }
+            reb = r2 < __builtin_ldexp(nx * nx + ny * ny, 2 * (en - ez)) || m == N;
+            ax = reb ? zx : nx; ay = reb ? zy : ny; ea = reb ? ez : en;
+            x_norm(ax, ay, ea);
+            if (reb) m = 0;
+            if (ea <= kXThr) {                                    /* extended from here */
+                dzx = ax; dzy = ay; ed = ea;
+                ext = true;
+                if (reb) {
+                    Zx = 0.0; Zy = 0.0; eZ = kXZero; Znx = z1.x; Zny = z1.y; eZn = e1;
+                } else if (k == 0) {
+                    Zx = Znx; Zy = Zny; eZ = eZn; Znx = Znn.x; Zny = Znn.y; eZn = eZnn;
+                } else {                                          /* m < N here */
+                    const double2 b = mant[m + 1];
+                    Zx = Wx; Zy = Wy; eZ = eW; Znx = b.x; Zny = b.y; eZn = exp2[m + 1];
+                }
+            } else {                                              /* plain from here (m < N) */
+                const double2 a = orbit[m], b = orbit[m + 1];
+                dzx = __builtin_ldexp(ax, ea); dzy = __builtin_ldexp(ay, ea);
+                ext = false;
+                Zx = a.x; Zy = a.y; Znx = b.x; Zny = b.y;
+            }
+        } else {
+            const double2 Znn = orbit[mn];
+            const double tx = (Zx + Zx) + dzx, ty = (Zy + Zy) + dzy;
+            const double nx = (tx * dzx - ty * dzy) + cpx;
+            const double ny = (tx * dzy + ty * dzx) + cpy;
+            ++m;
+            ++u;
+            ++nsingle;
+            const double zx = Znx + nx, zy = Zny + ny;
+            const double r2 = zx * zx + zy * zy;
+            if (r2 > B2) {
+                esc = u - 1; er2 = r2; live = false;
+                continue;
+            }
+            reb = r2 < nx * nx + ny * ny || m == N;
+            ax = reb ? zx : nx; ay = reb ? zy : ny;
+            if (reb) m = 0;
+            if (!(fmax(fabs(ax), fabs(ay)) < 0x1p-400)) {         /* stays plain */
+                dzx = ax; dzy = ay;
+                if (reb) {
+                    const double2 p1 = orbit[1];
+                    Zx = 0.0; Zy = 0.0; Znx = p1.x; Zny = p1.y;
+                } else {
+                    Zx = Znx; Zy = Zny; Znx = Znn.x; Zny = Znn.y;
+                }
+            } else {                                              /* turns extended (m < N) */
+                const double2 a = mant[m], b = mant[m + 1];
+                x_norm(ax, ay, ea);
+                dzx = ax; dzy = ay; ed = ea;
+                ext = true;
+                Zx = a.x; Zy = a.y; eZ = exp2[m]; Znx = b.x; Zny = b.y; eZn = exp2[m + 1];
+            }
+        }
+        if (u >= max_iter) live = false;                          /* esc stays max_iter */
+    }
+}
+
 __device__ __forceinline__ const DeepArgs& deep_args(const DeepArgs& A) { return A; }
 __device__ __forceinline__ const DeepArgs& deep_args(const DeepXArgs& A) { return A.d; }
 __device__ __forceinline__ const DeepArgs& deep_args(const DeepBlaArgs& A) { return A.d; }
+__device__ __forceinline__ const DeepArgs& deep_args(const DeepXBlaArgs& A) { return A.x.d; }
+__device__ __forceinline__ const DeepXArgs& deepx_args(const DeepXArgs& A) { return A; }
+__device__ __forceinline__ const DeepXArgs& deepx_args(const DeepXBlaArgs& A) { return A.x; }
 
 /* deep_kernel<DeepArgs>: the plain step; deep_kernel<DeepBlaArgs>: with BLA (deep_orbit_bla, the step counts);
- * deep_kernel<DeepXArgs>: extended-exponent deltas (deep_orbit_x) */
+ * deep_kernel<DeepXArgs>: extended-exponent deltas (deep_orbit_x); deep_kernel<DeepXBlaArgs>: those with BLA
+ * (deep_orbit_x_bla, the step counts) */
 template <class ARGS>
 __global__ void __launch_bounds__(kBlockThreads)
 deep_kernel(const ARGS AA)
 {
-    constexpr bool BLA = std::is_same<ARGS, DeepBlaArgs>::value;
-    constexpr bool X = std::is_same<ARGS, DeepXArgs>::value;
+    constexpr bool XBLA = std::is_same<ARGS, DeepXBlaArgs>::value;
+    constexpr bool BLA = std::is_same<ARGS, DeepBlaArgs>::value || XBLA;
+    constexpr bool X = std::is_same<ARGS, DeepXArgs>::value || XBLA;
     const DeepArgs& A = deep_args(AA);
     __shared__ LdsBlock S;
     __shared__ double2 log2_lds[kLog2Entries];
@@ -420,11 +711,21 @@ deep_kernel(const ARGS AA)
             int esc;
             double r2;
             if constexpr (X) {
-                double cx = ((pxs - 0.5 * resx) / resy) * AA.zm, cy = ((pys - 0.5 * resy) / resy) * AA.zm;
-                int ec = AA.ze;
+                const DeepXArgs& XA = deepx_args(AA);
+                double cx = ((pxs - 0.5 * resx) / resy) * XA.zm, cy = ((pys - 0.5 * resy) / resy) * XA.zm;
+                int ec = XA.ze;
                 if (!inside) { cx = 0.0; cy = 0.0; }
                 x_norm(cx, cy, ec);
-                deep_orbit_x(AA, cx, cy, ec, inside, esc, r2);
+                if constexpr (XBLA) {
+                    uint32_t np, nb;
+                    deep_orbit_x_bla(XA, AA.t, cx, cy, ec, inside, esc, r2, np, nb);
+                    if (inside) {
+                        n_plain += np; n_bla += nb;
+                        n_upd += (unsigned long long)(esc < A.max_iter ? esc + 1 : A.max_iter);
+                    }
+                } else {
+                    deep_orbit_x(XA, cx, cy, ec, inside, esc, r2);
+                }
             } else if constexpr (BLA) {
                 uint32_t np, nb;
                 deep_orbit_bla(A, AA.t, inside ? dcx : 0.0, inside ? dcy : 0.0, z1, inside, esc, r2, np, nb);

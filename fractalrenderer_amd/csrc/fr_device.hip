@@ -119,6 +119,22 @@ struct fr_ctx {
     int32_t deepx_len;          /* N + 1 */
     OrbitKey deepx_key;         /* of deepx_dev */
     int deepx_wg_per_cu;        /* resident workgroups per CU of deep_kernel<DeepXArgs> (0 = not asked yet) */
+    uint64_t deepx_gen;         /* bumped whenever deepx_dev receives another orbit */
+    /* BLA for extended views (FR_FLAG_DEEPX_BLA): the table of the cached extended orbit and the step counts of the most
+     * recent such render -- the deepx path's own, nothing of it is shared with the fp64 table above */
+    XRad* xbla_r;               /* r of every entry (xbla_cap) */
+    double2* xbla_ab;           /* mantissas of A, B of every entry (2 xbla_cap) */
+    int2* xbla_abe;             /* their exponents (xbla_cap) */
+    size_t xbla_cap;            /* entries */
+    bool xbla_valid;            /* the key below describes the table */
+    uint64_t xbla_key_gen, xbla_key_dcv;   /* deepx_gen of its orbit, bits of dcmax's mantissa */
+    int32_t xbla_key_dce;                  /* dcmax's exponent */
+    unsigned long long* xbla_steps_dev;    /* the kernel's three counters */
+    unsigned long long* xbla_steps_host;   /* pinned: their copy behind the most recent render with the flag */
+    bool have_xbla_steps;
+    hipEvent_t ev_xbla;         /* recorded behind every render with the flag (not while capturing): rebuilds wait for it */
+    bool ev_xbla_valid;
+    int deepx_bla_wg_per_cu;    /* resident workgroups per CU of deep_kernel<DeepXBlaArgs> (0 = not asked yet) */
 };
 
 #define FR_HIP_TRY(expr)                                                               \
@@ -167,6 +183,7 @@ extern "C" int fr_ctx_create(int device_ordinal, fr_ctx** out)
         (e2 = hipEventCreate(&c->ev_end)) != hipSuccess ||
         (e2 = hipEventCreateWithFlags(&c->ev_order, hipEventDisableTiming)) != hipSuccess ||
         (e2 = hipEventCreateWithFlags(&c->ev_bla, hipEventDisableTiming)) != hipSuccess ||
+        (e2 = hipEventCreateWithFlags(&c->ev_xbla, hipEventDisableTiming)) != hipSuccess ||
         (e2 = hipMalloc((void**)&c->d_ctrl, (kCtrlWords + (size_t)(kFeedbackShards + 2) * kShardStrideWords) * sizeof(uint32_t))) != hipSuccess ||
         (e2 = hipMemset(c->d_ctrl, 0, (kCtrlWords + (size_t)(kFeedbackShards + 2) * kShardStrideWords) * sizeof(uint32_t))) != hipSuccess ||
         (e2 = hipHostMalloc((void**)&c->overflow_host, 64, hipHostMallocMapped)) != hipSuccess ||
@@ -214,6 +231,12 @@ extern "C" void fr_ctx_destroy(fr_ctx* c)
     if (c->bla_steps_dev) (void)hipFree(c->bla_steps_dev);
     if (c->bla_steps_host) (void)hipHostFree(c->bla_steps_host);
     if (c->ev_bla) (void)hipEventDestroy(c->ev_bla);
+    if (c->xbla_r) (void)hipFree(c->xbla_r);
+    if (c->xbla_ab) (void)hipFree(c->xbla_ab);
+    if (c->xbla_abe) (void)hipFree(c->xbla_abe);
+    if (c->xbla_steps_dev) (void)hipFree(c->xbla_steps_dev);
+    if (c->xbla_steps_host) (void)hipHostFree(c->xbla_steps_host);
+    if (c->ev_xbla) (void)hipEventDestroy(c->ev_xbla);
     if (c->ev_begin) (void)hipEventDestroy(c->ev_begin);
     if (c->ev_end) (void)hipEventDestroy(c->ev_end);
     if (c->ev_order) (void)hipEventDestroy(c->ev_order);
@@ -897,7 +920,9 @@ static int deepx_orbit_for(fr_ctx* c, const fr_params* p, const fr_deepx_view* v
     FR_HIP_TRY(hipStreamSynchronize(stream));
     FR_HIP_TRY(hipStreamSynchronize(c->stream));
     if (c->have_render && c->last_stream != stream) FR_HIP_TRY(hipStreamSynchronize(c->last_stream));
+    if (c->ev_xbla_valid) FR_HIP_TRY(hipEventSynchronize(c->ev_xbla));    /* the last render with BLA, wherever it went */
     c->deepx_key.valid = false;
+    ++c->deepx_gen;
     const size_t need = (size_t)max_iter + 1;
     const size_t point_bytes = 2 * sizeof(double2) + sizeof(int32_t);
     if (need > c->deepx_cap) {
@@ -928,6 +953,90 @@ static int deepx_orbit_for(fr_ctx* c, const fr_params* p, const fr_deepx_view* v
     return ks;
 }
 
+/* FR_FLAG_DEEPX_BLA: the table of the cached extended orbit for this frame's dcmax (the whole frame's W, H and the zoom
+ * pair), built on `stream` unless the context holds it -- deep_bla_table_for's rules on the deepx path's own buffers and
+ * event. */
+static int deepx_bla_table_for(fr_ctx* c, const DeepXArgs& x, hipStream_t stream, int* levels)
+{
+    const int32_t N = c->deepx_len - 1;
+    const int K = N > 1 ? 31 - __builtin_clz((uint32_t)(N - 1)) : 0;   /* floor(log2(N - 1)) */
+    *levels = K;
+    if (K == 0) return FR_OK;
+    const double a = (double)x.d.g.W / (double)x.d.g.H;
+    int de = 0;
+    const double dv = frexp((1.0000001 * (0.5 * x.zm)) * sqrt(a * a + 1.0), &de);   /* normalised: dv in [0.5, 1) */
+    const int32_t dce = x.ze + de;
+    uint64_t dbits;
+    memcpy(&dbits, &dv, sizeof(dbits));
+    if (c->xbla_valid && c->xbla_key_gen == c->deepx_gen && c->xbla_key_dcv == dbits && c->xbla_key_dce == dce) return FR_OK;
+    c->xbla_valid = false;
+    const uint32_t n1 = (uint32_t)(N - 1);
+    const size_t need = (size_t)(n1 - (uint32_t)__builtin_popcount(n1));     /* sum over k >= 1 of (N - 1) >> k */
+    if (need > c->xbla_cap) {
+        FR_HIP_TRY(hipStreamSynchronize(stream));
+        FR_HIP_TRY(hipStreamSynchronize(c->stream));
+        if (c->ev_xbla_valid) FR_HIP_TRY(hipEventSynchronize(c->ev_xbla));
+        if (c->xbla_r) { (void)hipFree(c->xbla_r); c->xbla_r = nullptr; }
+        if (c->xbla_ab) { (void)hipFree(c->xbla_ab); c->xbla_ab = nullptr; }
+        if (c->xbla_abe) { (void)hipFree(c->xbla_abe); c->xbla_abe = nullptr; }
+        c->xbla_cap = 0;
+        FR_HIP_TRY(hipMalloc((void**)&c->xbla_r, need * sizeof(XRad)));
+        FR_HIP_TRY(hipMalloc((void**)&c->xbla_ab, need * 2 * sizeof(double2)));
+        FR_HIP_TRY(hipMalloc((void**)&c->xbla_abe, need * sizeof(int2)));
+        c->xbla_cap = need;
+    } else if (c->ev_xbla_valid) {
+        FR_HIP_TRY(hipStreamWaitEvent(stream, c->ev_xbla, 0));
+    }
+    for (int k = 1; k <= K; ++k) {
+        const uint32_t cnt = n1 >> k;
+        uint32_t grid = (cnt + kBlockThreads - 1) / kBlockThreads;
+        const uint32_t cap = (uint32_t)c->compute_units * 8u;
+        if (grid > cap) grid = cap;
+        hipLaunchKernelGGL(deepx_bla_level_kernel, dim3(grid), dim3(kBlockThreads), 0, stream, x.mant, x.exp2, N, k, dv, dce,
+                           c->xbla_r, c->xbla_ab, c->xbla_abe);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return fr_set_error(FR_ERR_HIP, "extended BLA table launch failed: %s", hipGetErrorString(e));
+    }
+    c->xbla_key_gen = c->deepx_gen;
+    c->xbla_key_dcv = dbits;
+    c->xbla_key_dce = dce;
+    c->xbla_valid = true;
+    return FR_OK;
+}
+
+/* the table, then deep_kernel<DeepXBlaArgs> on the queue plan of deep_kernel<DeepXArgs> (its own occupancy), its counters
+ * cleared in front of it and copied to pinned memory behind it */
+static int enqueue_deepx_bla(fr_ctx* c, const DeepXArgs& x, hipStream_t stream)
+{
+    DeepXBlaArgs a;
+    memset(&a, 0, sizeof(a));
+    a.x = x;
+    int levels = 0;
+    const int ts = deepx_bla_table_for(c, x, stream, &levels);
+    if (ts != FR_OK) return ts;
+    a.t.r = c->xbla_r; a.t.ab = c->xbla_ab; a.t.abe = c->xbla_abe; a.t.levels = levels;
+    if (!c->xbla_steps_dev) {
+        FR_HIP_TRY(hipMalloc((void**)&c->xbla_steps_dev, 3 * sizeof(unsigned long long)));
+        FR_HIP_TRY(hipHostMalloc((void**)&c->xbla_steps_host, 3 * sizeof(unsigned long long)));
+    }
+    a.t.steps = c->xbla_steps_dev;
+    FR_HIP_TRY(hipMemsetAsync(c->xbla_steps_dev, 0, 3 * sizeof(unsigned long long), stream));
+    const int st = launch_one_pass(c, stream, "deep_kernel<DeepXBlaArgs>", deep_kernel<DeepXBlaArgs>, a, a.x.d.g, a.x.d.q,
+                                   c->deepx_bla_wg_per_cu, false);
+    if (st != FR_OK) return st;
+    FR_HIP_TRY(hipMemcpyAsync(c->xbla_steps_host, c->xbla_steps_dev, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                              stream));
+    c->have_xbla_steps = true;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusActive; }
+    c->ev_xbla_valid = false;
+    if (cap == hipStreamCaptureStatusNone) {
+        FR_HIP_TRY(hipEventRecord(c->ev_xbla, stream));
+        c->ev_xbla_valid = true;
+    }
+    return FR_OK;
+}
+
 static int enqueue_deepx(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, uint32_t W, uint32_t H, const fr_shard* shard,
                          float* rgba, void* nu, int32_t* iter, hipStream_t stream, bool out_frame)
 {
@@ -951,6 +1060,7 @@ static int enqueue_deepx(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, 
     a.n_ref = c->deepx_len - 1;
     fill_deep_args(a, c, p, tile_geom(W, H, rows_local, &norm, out_frame), rgba, nu, iter);
 
+    if (p->flags & FR_FLAG_DEEPX_BLA) return enqueue_deepx_bla(c, x, stream);
     return launch_one_pass(c, stream, "deep_kernel<DeepXArgs>", deep_kernel<DeepXArgs>, x, a.g, a.q, c->deepx_wg_per_cu, false);
 }
 
@@ -1445,6 +1555,31 @@ extern "C" int64_t fr_deep_bla_table(fr_ctx* c, double* r, double* ab, int64_t n
     FR_HIP_TRY(hipDeviceSynchronize());
     if (n > 0 && r) FR_HIP_TRY(hipMemcpy(r, c->bla_r, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
     if (n > 0 && ab) FR_HIP_TRY(hipMemcpy(ab, c->bla_ab, (size_t)n * 2 * sizeof(double2), hipMemcpyDeviceToHost));
+    return have;
+}
+
+extern "C" int fr_ctx_last_deepx_steps(fr_ctx* c, uint64_t out[3])
+{
+    if (!c || !out) return fr_set_error(FR_ERR_INVALID_ARG, "ctx/out is NULL");
+    if (!c->have_xbla_steps)
+        return fr_set_error(FR_ERR_UNSUPPORTED, "no fr_render_deepx call with FR_FLAG_DEEPX_BLA on this context yet");
+    for (int i = 0; i < 3; ++i) out[i] = (uint64_t)c->xbla_steps_host[i];
+    return FR_OK;
+}
+
+extern "C" int64_t fr_deepx_bla_table(fr_ctx* c, void* r, double* ab, int32_t* ab_exp, int64_t n)
+{
+    if (!c) return fr_set_error(FR_ERR_INVALID_ARG, "ctx is NULL");
+    if (!c->xbla_valid) return 0;
+    const int32_t N = c->deepx_len - 1;
+    const uint32_t n1 = (uint32_t)(N - 1);
+    const int64_t have = (int64_t)(n1 - (uint32_t)__builtin_popcount(n1));
+    if (n > have) n = have;
+    FR_HIP_TRY(hipSetDevice(c->device));
+    FR_HIP_TRY(hipDeviceSynchronize());
+    if (n > 0 && r) FR_HIP_TRY(hipMemcpy(r, c->xbla_r, (size_t)n * sizeof(XRad), hipMemcpyDeviceToHost));
+    if (n > 0 && ab) FR_HIP_TRY(hipMemcpy(ab, c->xbla_ab, (size_t)n * 2 * sizeof(double2), hipMemcpyDeviceToHost));
+    if (n > 0 && ab_exp) FR_HIP_TRY(hipMemcpy(ab_exp, c->xbla_abe, (size_t)n * sizeof(int2), hipMemcpyDeviceToHost));
     return have;
 }
 

@@ -38,6 +38,10 @@ int fr_deep_parse_fixed(const char* s, int32_t frac_bits, uint64_t* out, int32_t
 /* tests: the context's BLA table (fr_device.hip), copied to the host after a sync of the context's stream: r[0 .. n) and
  * ab[0 .. 4n) (A.x, A.y, B.x, B.y per entry), level after level.  Returns the entries it holds, 0 for none. */
 int64_t fr_deep_bla_table(fr_ctx* ctx, double* r, double* ab, int64_t n);
+/* tests: the extended BLA table of the context (FR_FLAG_DEEPX_BLA), level 1 first: r receives n entries of 8 bytes (the
+ * mantissa as a float, the int32 exponent), ab 4 n doubles (the mantissas of A, B), ab_exp 2 n int32 (their exponents);
+ * NULL skips a part.  Returns the number of entries the table has (0: none). */
+int64_t fr_deepx_bla_table(fr_ctx* ctx, void* r, double* ab, int32_t* ab_exp, int64_t n);
 
 /* the context's own stream (hipStream_t) and device ordinal: fr_node.cpp orders RCCL transfers behind the renders */
 void* fr_ctx_stream_handle(fr_ctx* ctx);

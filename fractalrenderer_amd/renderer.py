@@ -131,6 +131,13 @@ class Renderer:
         _capi.check(self._lib.fr_ctx_last_deep_steps(self._ctx, out))
         return DeepSteps(int(out[0]), int(out[1]), int(out[2]))
 
+    def last_deepx_steps(self) -> DeepSteps:
+        """fr_ctx_last_deepx_steps: (single steps of both modes, BLA steps, updates skipped) of the most recent
+        render_deep(xbla=True) on this context, as last_deep_steps()."""
+        out = (C.c_uint64 * 3)()
+        _capi.check(self._lib.fr_ctx_last_deepx_steps(self._ctx, out))
+        return DeepSteps(int(out[0]), int(out[1]), int(out[2]))
+
     def last_kernel_ms(self) -> float:
         return float(self._lib.fr_ctx_last_kernel_ms(self._ctx))
 
@@ -226,7 +233,7 @@ class Renderer:
 
     def render_deep(self, state: FractalState, width: int, height: int, view: Optional[DeepView] = None, *,
                     post_chain: bool = False, rgba=None, nu=None, iter=None, shard: Optional[Shard] = None,
-                    stream: Optional[int] = None, sync: bool = True, bla: bool = False) -> None:
+                    stream: Optional[int] = None, sync: bool = True, bla: bool = False, xbla: bool = False) -> None:
         """fr_render_deep / fr_render_deep_async: a Mandelbrot view deeper than double precision, by perturbation around one
         reference orbit computed on the host.  `view` carries the centre as decimal strings (default: "-0.5", "0"); the
         zoom and every other field come from `state` (its double centre is not read).  Always fp64: nu is float64.
@@ -234,10 +241,17 @@ class Renderer:
         sync=False; a render of the view the context holds is launch-only.  bla=True sets FR_FLAG_DEEP_BLA: iteration
         skipping by bilinear approximation (the header's rules; last_deep_steps() reports what it skipped).
         A view with a zoom string (DeepView(..., zoom="1e-400")) goes to fr_render_deepx / fr_render_deepx_async:
-        extended-exponent deltas, zooms down to 1e-1000, state.zoom not read, no BLA."""
+        extended-exponent deltas, zooms down to 1e-1000, state.zoom not read.  bla=True raises there (its table is fp64);
+        xbla=True sets FR_FLAG_DEEPX_BLA, BLA in the extended arithmetic (last_deepx_steps() reports what it skipped), and
+        is a ValueError for a view without a zoom string."""
+        if xbla and (view is None or view.zoom is None):
+            raise ValueError("xbla=True needs a view with a zoom string (DeepView(..., zoom=\"1e-400\")); bla=True is the "
+                             "flag of views without one")
         p = state.to_params(FractalType.Mandelbrot, Precision.F64, post_chain)
         if bla:
             p.flags |= _capi.FR_FLAG_DEEP_BLA
+        if xbla:
+            p.flags |= _capi.FR_FLAG_DEEPX_BLA
         rows = shard.rows(height) if shard else height
         if view is not None and view.zoom is not None:
             vx = view.to_cx()

@@ -71,6 +71,8 @@ typedef enum fr_precision {
                                       default is the LINEAR colour, before that chain */
 #define FR_FLAG_DEEP_BLA     0x2u  /* fr_render_deep(_async) only: skip iterations by bilinear approximation (see there);
                                       every other entry point ignores it */
+#define FR_FLAG_DEEPX_BLA    0x4u  /* fr_render_deepx(_async) only: the same for extended views (see there); every other
+                                      entry point ignores it, fr_render_deep included */
 
 /*
  * fr_params -- the hot-path fields of FractalState (src/fractal_state.h:16-91),
@@ -514,7 +516,8 @@ int fr_ctx_last_deep_steps(fr_ctx* ctx, uint64_t out[3]);
  * The view: centre strings as fr_deep_view; zoom = the view height as a decimal string of the same grammar, read as
  * zm 2^ze, zm a double in [1, 2) holding the decimal value correctly rounded to 53 significant bits (ties to even), ze an
  * int32 (fr_deepx_zoom returns the pair).  1e-1000 <= zoom <= 1e3, compared on the rounded pair.  p->zoom, p->center_x and
- * p->center_y are ignored.  FR_ERR_UNSUPPORTED as for fr_render_deep, and for FR_FLAG_DEEP_BLA (out of scope, below);
+ * p->center_y are ignored.  FR_ERR_UNSUPPORTED as for fr_render_deep, and for FR_FLAG_DEEP_BLA (the fp64 table; the
+ * extended views' own flag is FR_FLAG_DEEPX_BLA, below), with or without FR_FLAG_DEEPX_BLA;
  * FR_ERR_INVALID_ARG for a malformed or out-of-range zoom, and otherwise as there.
  *
  * Reference orbit: Z_0 .. Z_N exactly as for fr_render_deep (same recurrence, same escape test, F = frac_bits or
@@ -556,9 +559,9 @@ int fr_ctx_last_deep_steps(fr_ctx* ctx, uint64_t out[3]);
  * the asynchronous form's rules are those of fr_render_deep; the context keeps the most recent extended orbit on the device
  * next to (and independent of) fr_render_deep's, keyed by (centre strings, F, max_iterations, bailout).
  *
- * Out of scope: BLA for extended views (A grows like 1 / zoom: the table and deep_bla_level_kernel need extended
- * exponents too), fr_node, .franim and zoom paths for deep views, and depths beyond 1e-1000 (the 4096-bit cap of F). */
+ * Out of scope: fr_node, .franim and zoom paths for deep views, and depths beyond 1e-1000 (the 4096-bit cap of F). */
 #define FR_HAS_DEEPX 1
+#define FR_HAS_DEEPX_BLA 1        /* FR_FLAG_DEEPX_BLA and fr_ctx_last_deepx_steps (below fr_render_deepx_async) */
 #define FR_DEEPX_ZERO_EXP (-(1 << 28))   /* the exponent of a zero in the extended storage */
 
 typedef struct fr_deepx_view {
@@ -592,6 +595,53 @@ int fr_render_deepx(fr_ctx* ctx, const fr_params* p, const fr_deepx_view* view, 
 /* fr_render_deep_async's contract: a render of a new view computes its orbit on the host first and is never launch-only */
 int fr_render_deepx_async(fr_ctx* ctx, const fr_params* p, const fr_deepx_view* view, uint32_t width, uint32_t height,
                           const fr_shard* shard, const fr_output* out, void* hip_stream);
+
+/* Bilinear approximation for extended views, opt-in per call with FR_FLAG_DEEPX_BLA in p->flags.  Only fr_render_deepx and
+ * fr_render_deepx_async read the flag; without it every byte they write is as above.  It is FR_FLAG_DEEP_BLA's scheme with
+ * the table and the BLA step carried in the extended arithmetic of this section (A grows like 1 / zoom, far beyond a
+ * double), taken by samples in either mode.  (A, B, r) come from a table built on the device from the cached extended orbit.
+ *
+ * Notation: extended complex (x, y, e), norm and (+) as above.  An extended real (v, e) stands for v 2^e; normalised it has
+ * v in [0.5, 1) (k = frexp exponent of v; (ldexp(v, -k), e + k)), and zero has e = FR_DEEPX_ZERO_EXP.  P (x) Q is the complex
+ * mantissa product written out as in the plain step, (P.x Q.x - P.y Q.y, P.x Q.y + P.y Q.x), each operation one rounding,
+ * with the exponent P.e + Q.e, not normalised unless said.  |w| of a normalised extended complex is
+ * (sqrt(w.x*w.x + w.y*w.y), w.e), then normalised; sqrt is correctly rounded as for FR_FLAG_DEEP_BLA.
+ *   - Constants: eps = 2^-53;  dcmax = the extended real ((1.0000001 * (0.5 * zm)) * sqrt((W/H)*(W/H) + 1), ze), normalised,
+ *     W/H of the WHOLE frame (never of a shard's rows).
+ *   - Single step at m >= 1 (never stored): A = norm(Z_m.x, Z_m.y, Z_m.e + 1) from the extended storage, B = norm(1, 0, 0),
+ *     r = eps * |norm(Z_m)|, the multiplication by 2^-53 going to the exponent (r = 0 stays the zero).
+ *   - Table: levels, entry indexing and the existence rule are exactly those of FR_FLAG_DEEP_BLA.  Merging x then y:
+ *       A = norm(A_y (x) A_x),   B = norm((A_y (x) B_x) (+) B_y),
+ *       t = (r_y (-) |B_x| dcmax) (/) |A_x|:  |B_x| dcmax = (|B_x|.v dcmax.v, |B_x|.e + dcmax.e);  (-) aligns both to the larger
+ *         exponent e with ldexp and subtracts once;  (/) is one division of the mantissas with the exponent e - |A_x|.e;
+ *       r = norm(t) if t's mantissa is > 0 and finite, else the zero (NaN: zero);  then r = r_x unless r < r_x, compared on
+ *       the normalised (exponent, mantissa);
+ *       if the exponent of A or of B lies outside [-2^27, 2^27] the entry is void: r, A and B are all stored as zero (this
+ *       replaces the fp64 table's "not finite" rule; zeroing A and B too keeps every int32 exponent sum of the levels above
+ *       in range, and r of every level above a void entry is 0 by the two rules before);
+ *       last, the STORED r keeps the top 24 bits of its mantissa, the rest cleared (toward zero: a float holds it exactly),
+ *       so that r is 8 bytes, a float and an int32; the merges of the next level and the probes read that stored value.  The
+ *       single step's r is not stored and not cut.  A radius is a bound: cutting it can only refuse a step.
+ *   - Stepping: u replaces the loop index as for FR_FLAG_DEEP_BLA, and the level choice is the one there: the largest
+ *     k >= 1 with (m-1) mod 2^k == 0, m + 2^k <= N and u + 2^k <= max_iterations whose probe passes.  The probe is on dz as a
+ *     normalised extended number -- a sample in the PLAIN mode uses norm(dz.x, dz.y, 0) --:
+ *       dz.x*dz.x + dz.y*dz.y < ldexp(r.v*r.v, 2 (r.e - dz.e))      (r.v*r.v is exact: 24 bits squared).
+ *     A BLA step is always taken in extended arithmetic, on that dz and the extended dc (never dcp):
+ *       n = (A (x) dz) (+) (B (x) dc);   m += 2^k;   u += 2^k;   z = Z_m (+) n  (Z_m from the extended storage);
+ *     then the escape test, the rebase rule, norm and the mode rule of the EXTENDED step, unchanged: escaped at u - 1 if
+ *     ldexp(r2, 2 z.e) > bailout^2; dz = norm(rebase ? z : n); a result with dz.e > -400 turns the sample PLAIN.
+ *     If no level qualifies, or m == 0, the sample takes the step of its mode above, operation for operation: it escapes at
+ *     u and then u += 1.
+ * Cost: (N - 1) - popcount(N - 1) entries of 48 bytes (r 8, the mantissas of A and B 32, their exponents 8), cached per
+ * context next to the extended orbit, keyed by that orbit and the bits of dcmax (mantissa and exponent), grown like the orbit
+ * buffer.  A zoom change at a fixed centre rebuilds it (K small launches on the render's stream, ordered behind the context's
+ * previous render with the flag, whatever stream that went to); a cached view is launch-only.  The table belongs to this
+ * path alone: it is not shared with, and does not invalidate, FR_FLAG_DEEP_BLA's. */
+
+/* fr_ctx_last_deep_steps' contract for the context's most recent fr_render_deepx(_async) call made with FR_FLAG_DEEPX_BLA:
+ * out[0] single steps (plain and extended), out[1] BLA steps, out[2] updates skipped.  FR_ERR_UNSUPPORTED if there is no
+ * such call.  fr_ctx_last_deep_steps does not report these calls. */
+int fr_ctx_last_deepx_steps(fr_ctx* ctx, uint64_t out[3]);
 
 /* ---- frames over the GPUs of a node (BASELINE.json north_star: "tiled across the 8 GPUs of one node as disjoint row
  * bands with a final RCCL gather over xGMI") -----------------------------------------------------------------------------

@@ -135,6 +135,12 @@ SIGNATURES = {
                                  _P(fr_output)]),
     "fr_render_deep_async": (C.c_int, [C.c_void_p, _P(fr_params), _P(fr_deep_view), C.c_uint32, C.c_uint32, _P(fr_shard),
                                        _P(fr_output), C.c_void_p]),
+    "fr_deep_ship_reference_orbit": (C.c_int, [_P(fr_deep_view), C.c_double, C.c_int32, C.c_float, C.c_void_p,
+                                               _P(C.c_int32)]),
+    "fr_render_deep_ship": (C.c_int, [C.c_void_p, _P(fr_params), _P(fr_deep_view), C.c_uint32, C.c_uint32, _P(fr_shard),
+                                      _P(fr_output)]),
+    "fr_render_deep_ship_async": (C.c_int, [C.c_void_p, _P(fr_params), _P(fr_deep_view), C.c_uint32, C.c_uint32, _P(fr_shard),
+                                            _P(fr_output), C.c_void_p]),
     "fr_ctx_last_deep_steps": (C.c_int, [C.c_void_p, _P(C.c_uint64)]),
     "fr_ctx_last_deepx_steps": (C.c_int, [C.c_void_p, _P(C.c_uint64)]),
     "fr_deepx_view_default": (C.c_int, [_P(fr_deepx_view)]),
@@ -226,6 +232,7 @@ INTERNAL_SIGNATURES = {
     "fr_deep_bla_table": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),        # fr_internal.h: tests
     "fr_deepx_bla_table": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),   # fr_internal.h: tests
     "fr_deepx_validate": (C.c_int, [_P(fr_params), _P(fr_deepx_view), C.c_uint32, C.c_uint32]),        # fr_internal.h: tests
+    "fr_deep_ship_validate": (C.c_int, [_P(fr_params), _P(fr_deep_view), C.c_uint32, C.c_uint32]),     # fr_internal.h: tests
 }
 PUBLIC_OPTIONS = ("periodicity", "staging", "shards", "tile_kernel", "timing", "diag_buffer", "diag_stride")
 TUNING_NAMES = ("workgroups_per_cu", "run_max", "run_min", "shift_bias", "stage_first", "pool_refill_at", "stream_run_max",

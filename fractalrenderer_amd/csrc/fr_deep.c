@@ -11,6 +11,9 @@
  * inexact flag of its divisions, one rounding to 53 bits), and the orbit is stored as doubles plus a side array of
  * exponents -- 0 for every point a normal double holds, so those points are the doubles of fr_deep_reference_orbit and the
  * kernel's plain mode loads 16 bytes per point; only a point below 2^-1022 carries mantissas and a non-zero exponent.
+ *
+ * Deep Burning Ship views (fr_render_deep_ship): the same loop with Im = floor(2 |Zr| |Zi| / 2^F) + Ci (orbit_formula), and
+ * fr_deep_validate's rules for FR_FRACTAL_BURNING_SHIP (fr_deep_ship_validate).
  */
 #include "fr_internal.h"
 
@@ -335,9 +338,13 @@ static void store_extended(const uint64_t* zr, const uint64_t* zi, fx_fmt fmt, d
     mxy[1] = fixed_to_double(zi, f);
 }
 
+/* The recurrence: kOrbitMandelbrot Z^2 + C; kOrbitShip (|Zr| + i |Zi|)^2 + C, whose imaginary product is never negative
+ * (fr_render_deep_ship). */
+typedef enum { kOrbitMandelbrot = 0, kOrbitShip = 1 } orbit_formula;
+
 /* out_exp NULL: Z_n as doubles; else the extended storage */
-static int orbit_loop(const uint64_t* cr, const uint64_t* ci, fx_fmt fmt, int32_t max_iter, float bailout, double* out_xy,
-                      int32_t* out_exp, int32_t* out_len)
+static int orbit_loop(const uint64_t* cr, const uint64_t* ci, fx_fmt fmt, orbit_formula formula, int32_t max_iter,
+                      float bailout, double* out_xy, int32_t* out_exp, int32_t* out_len)
 {
     const int L = fmt.L, L2 = 2 * fmt.L;
     uint64_t zr[kMaxLimbs], zi[kMaxLimbs], ar[kMaxLimbs], ai[kMaxLimbs], t0[kMaxLimbs], t1[kMaxLimbs];
@@ -372,12 +379,12 @@ static int orbit_loop(const uint64_t* cr, const uint64_t* ci, fx_fmt fmt, int32_
         add_n(ssum, sr, si, L2 + 1);
         if (cmp_n(ssum, T, L2 + 1) > 0) break;                     /* |Z_n|^2 > bailout^2 */
         mul_mag(pr, ar, ai, L);
-        /* Re = floor(Zr^2 / 2^F) - floor(Zi^2 / 2^F) + Cr,  Im = floor(2 Zr Zi / 2^F) + Ci */
+        /* Re = floor(Zr^2 / 2^F) - floor(Zi^2 / 2^F) + Cr,  Im = floor(2 Zr Zi / 2^F) + Ci (the ship: 2 |Zr| |Zi|) */
         floor_shift(t0, sr, fmt.F, 0, fmt);
         floor_shift(t1, si, fmt.F, 0, fmt);
         sub_n(zr, t0, t1, L);
         add_n(zr, zr, cr, L);
-        floor_shift(t0, pr, fmt.F - 1, nr != ni, fmt);
+        floor_shift(t0, pr, fmt.F - 1, formula == kOrbitShip ? 0 : nr != ni, fmt);
         add_n(zi, t0, ci, L);
         if (out_exp) {
             store_extended(zr, zi, fmt, out_xy + 2 * (n + 1), out_exp + n + 1);
@@ -492,10 +499,10 @@ int fr_deep_parse_fixed(const char* s, int32_t frac_bits, uint64_t* out, int32_t
     return fmt.L;
 }
 
-int fr_deep_reference_orbit(const fr_deep_view* v, double zoom, int32_t max_iter, float bailout, double* out_xy,
-                            int32_t* out_len)
+static int reference_orbit(const char* who, orbit_formula formula, const fr_deep_view* v, double zoom, int32_t max_iter,
+                           float bailout, double* out_xy, int32_t* out_len)
 {
-    if (!out_xy || !out_len) return fr_set_error(FR_ERR_INVALID_ARG, "fr_deep_reference_orbit: out is NULL");
+    if (!out_xy || !out_len) return fr_set_error(FR_ERR_INVALID_ARG, "%s: out is NULL", who);
     if (max_iter < 1 || max_iter > (1 << 24))
         return fr_set_error(FR_ERR_INVALID_ARG, "max_iterations %d outside [1, 2^24]", max_iter);
     int st;
@@ -505,7 +512,46 @@ int fr_deep_reference_orbit(const fr_deep_view* v, double zoom, int32_t max_iter
     const fx_fmt fmt = {F, (F + 63) / 64 + 1};
     uint64_t cr[kMaxLimbs], ci[kMaxLimbs];
     if ((st = parse_centre(v, fmt, cr, ci)) != FR_OK) return st;
-    return orbit_loop(cr, ci, fmt, max_iter, bailout, out_xy, NULL, out_len);
+    return orbit_loop(cr, ci, fmt, formula, max_iter, bailout, out_xy, NULL, out_len);
+}
+
+int fr_deep_reference_orbit(const fr_deep_view* v, double zoom, int32_t max_iter, float bailout, double* out_xy,
+                            int32_t* out_len)
+{
+    return reference_orbit("fr_deep_reference_orbit", kOrbitMandelbrot, v, zoom, max_iter, bailout, out_xy, out_len);
+}
+
+/* ---- deep Burning Ship views (fr_render_deep_ship) ----------------------------------------------------------------------- */
+int fr_deep_ship_reference_orbit(const fr_deep_view* v, double zoom, int32_t max_iter, float bailout, double* out_xy,
+                                 int32_t* out_len)
+{
+    return reference_orbit("fr_deep_ship_reference_orbit", kOrbitShip, v, zoom, max_iter, bailout, out_xy, out_len);
+}
+
+int fr_deep_ship_validate(const fr_params* p, const fr_deep_view* v, uint32_t width, uint32_t height)
+{
+    if (!p || !v) return fr_set_error(FR_ERR_INVALID_ARG, "params/deep view is NULL");
+    if (p->fractal_type != FR_FRACTAL_BURNING_SHIP)
+        return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deep_ship renders FR_FRACTAL_BURNING_SHIP only (got %d)",
+                            p->fractal_type);
+    if (p->precision != FR_PRECISION_F64)
+        return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deep_ship needs FR_PRECISION_F64 (got %d)", p->precision);
+    fr_params q = *p;                                            /* the double centre is not read */
+    q.center_x = 0.0; q.center_y = 0.0;
+    int st = fr_params_validate(&q, width, height);
+    if (st != FR_OK) return st;
+    if ((st = check_zoom(p->zoom)) != FR_OK || (st = check_bailout(p->bailout)) != FR_OK) return st;
+    if (p->orbit_trap_enabled || (p->stripe_enabled && p->interior_style == 2) || p->interior_style == 3)
+        return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deep_ship: the orbit trap, stripes with interior_style 2 and "
+                            "interior_style 3 need the whole orbit and are not available");
+    if (p->flags & (FR_FLAG_DEEP_BLA | FR_FLAG_DEEPX_BLA))
+        return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deep_ship: bilinear approximation is not available for the Burning "
+                            "Ship (FR_FLAG_DEEP_BLA / FR_FLAG_DEEPX_BLA)");
+    const int F = view_frac_bits(v, p->zoom);
+    if (F < 0) return F;
+    uint64_t cr[kMaxLimbs], ci[kMaxLimbs];
+    const fx_fmt fmt = {F, (F + 63) / 64 + 1};
+    return parse_centre(v, fmt, cr, ci);
 }
 
 /* ---- extended-exponent views (fr_render_deepx) ------------------------------------------------------------------------------
@@ -634,5 +680,5 @@ int fr_deepx_reference_orbit(const fr_deepx_view* v, int32_t max_iter, float bai
     uint64_t cr[kMaxLimbs], ci[kMaxLimbs];
     const fr_deep_view c = {v->center_x, v->center_y, F, 0};
     if ((st = parse_centre(&c, fmt, cr, ci)) != FR_OK) return st;
-    return orbit_loop(cr, ci, fmt, max_iter, bailout, out_mant_xy, out_exp2, out_len);
+    return orbit_loop(cr, ci, fmt, kOrbitMandelbrot, max_iter, bailout, out_mant_xy, out_exp2, out_len);
 }

@@ -36,6 +36,12 @@
  * deep_orbit_x_bla: deep_orbit_x whose lanes, in either mode, probe the table as deep_orbit_bla does and take a BLA step in
  * extended arithmetic.  A probe gathers 8 bytes (r as a float mantissa and an int32 exponent); the chosen level's A and B
  * are 32 bytes of mantissas and 8 bytes of exponents in arrays of their own.
+ *
+ * Deep Burning Ship views (fr_render_deep_ship; the step is in the header): deep_kernel<DeepShipArgs> runs deep_orbit_ship as
+ * its per-sample loop -- deep_orbit on (|Z_m|, fold(Z_m, dz)), the fold a pair of compares and selects, with deep_orbit's
+ * registers and prefetch.  The orbit is the ship's own (fr_deep.c), dc is the Burning Ship shader's viewport map less the
+ * centre (sx outer), and the colour stage is that of the fp64 Burning Ship path: shade<double, 2>, interior samples
+ * black, the post chain with the Julia / Burning Ship floors.
  */
 #pragma once
 #include "fr_kernels.hip.h"
@@ -147,6 +153,61 @@ __device__ __forceinline__ void deep_orbit(const DeepArgs& A, const double dcx, 
         const double tx = (Zx + Zx) + dzx, ty = (Zy + Zy) + dzy;
         const double nx = (tx * dzx - ty * dzy) + dcx;
         const double ny = (tx * dzy + ty * dzx) + dcy;
+        ++m;
+        const double zx = Znx + nx, zy = Zny + ny;
+        const double r2 = zx * zx + zy * zy;
+        if (r2 > B2) {
+            esc = i; er2 = r2; live = false;
+        } else if (r2 < nx * nx + ny * ny || m == N) {           /* rebase */
+            dzx = zx; dzy = zy; m = 0;
+            Zx = 0.0; Zy = 0.0; Znx = z1.x; Zny = z1.y;
+        } else {
+            dzx = nx; dzy = ny;
+            Zx = Znx; Zy = Zny; Znx = Znn.x; Zny = Znn.y;
+        }
+    }
+}
+
+/* fr_render_deep_ship: d.orbit holds the Burning Ship orbit of the centre */
+struct DeepShipArgs {
+    DeepArgs d;
+    double log_bailout;                  /* log(bailout), for shade<double, 2> at bailout <= 1 (LaunchArgs::log_bailout) */
+};
+
+/* |X + a| - |X| without the cancelling sum: the signs of X and of w = X + a (exact: an IEEE sum is zero only when it is
+ * exactly zero) pick a, -a or +-(2X + a).  X2 = X + X.  Compares and selects, no branch. */
+__device__ __forceinline__ double ship_fold(const double X, const double X2, const double a)
+{
+    const double w = X + a, d = X2 + a;
+    const double up = w >= 0.0 ? a : -d;
+    const double dn = w > 0.0 ? d : -a;
+    return X >= 0.0 ? up : dn;
+}
+
+/* deep_orbit for z <- (|x| + i |y|)^2 + c: the same step on U = (|Z_m.x|, |Z_m.y|) and f = (fold(Z_m.x, dz.x),
+ * fold(Z_m.y, dz.y)); z = Z_{m+1} + dz' with the signed orbit point, escape and rebase as there (Z_0 = 0: at m = 0 the
+ * step is (|dz.x| + i |dz.y|)^2 + dc). */
+__device__ __forceinline__ void deep_orbit_ship(const DeepArgs& A, const double dcx, const double dcy, const double2 z1,
+                                                bool live, int& esc, double& er2)
+{
+    const double2* __restrict__ orbit = A.orbit;
+    const int N = A.n_ref, max_iter = A.max_iter;
+    const double B2 = A.B2;
+    double dzx = 0.0, dzy = 0.0;
+    double Zx = 0.0, Zy = 0.0;                                   /* Z_m */
+    double Znx = z1.x, Zny = z1.y;                               /* Z_{m+1} */
+    int m = 0;
+    esc = max_iter;
+    er2 = 0.0;
+    for (int i = 0; i < max_iter; ++i) {
+        if (__builtin_amdgcn_ballot_w64(live) == 0ull) break;
+        if (!live) continue;
+        const double2 Znn = orbit[m + 2 <= N ? m + 2 : N];      /* Z_{m+2}, for the next step (m + 1 < N) */
+        const double X2 = Zx + Zx, Y2 = Zy + Zy;
+        const double fx = ship_fold(Zx, X2, dzx), fy = ship_fold(Zy, Y2, dzy);
+        const double tx = fabs(X2) + fx, ty = fabs(Y2) + fy;     /* |X| + |X| = |X + X| */
+        const double nx = (tx * fx - ty * fy) + dcx;
+        const double ny = (tx * fy + ty * fx) + dcy;
         ++m;
         const double zx = Znx + nx, zy = Zny + ny;
         const double r2 = zx * zx + zy * zy;
@@ -661,12 +722,14 @@ __device__ __forceinline__ const DeepArgs& deep_args(const DeepArgs& A) { return
 __device__ __forceinline__ const DeepArgs& deep_args(const DeepXArgs& A) { return A.d; }
 __device__ __forceinline__ const DeepArgs& deep_args(const DeepBlaArgs& A) { return A.d; }
 __device__ __forceinline__ const DeepArgs& deep_args(const DeepXBlaArgs& A) { return A.x.d; }
+__device__ __forceinline__ const DeepArgs& deep_args(const DeepShipArgs& A) { return A.d; }
 __device__ __forceinline__ const DeepXArgs& deepx_args(const DeepXArgs& A) { return A; }
 __device__ __forceinline__ const DeepXArgs& deepx_args(const DeepXBlaArgs& A) { return A.x; }
 
 /* deep_kernel<DeepArgs>: the plain step; deep_kernel<DeepBlaArgs>: with BLA (deep_orbit_bla, the step counts);
  * deep_kernel<DeepXArgs>: extended-exponent deltas (deep_orbit_x); deep_kernel<DeepXBlaArgs>: those with BLA
- * (deep_orbit_x_bla, the step counts) */
+ * (deep_orbit_x_bla, the step counts); deep_kernel<DeepShipArgs>: the Burning Ship (deep_orbit_ship, its viewport map and
+ * colour stage) */
 template <class ARGS>
 __global__ void __launch_bounds__(kBlockThreads)
 deep_kernel(const ARGS AA)
@@ -674,15 +737,20 @@ deep_kernel(const ARGS AA)
     constexpr bool XBLA = std::is_same<ARGS, DeepXBlaArgs>::value;
     constexpr bool BLA = std::is_same<ARGS, DeepBlaArgs>::value || XBLA;
     constexpr bool X = std::is_same<ARGS, DeepXArgs>::value || XBLA;
+    constexpr bool SHIP = std::is_same<ARGS, DeepShipArgs>::value;
+    constexpr int FRACTAL = SHIP ? 2 : 0;                         /* the colour stage: shade() / colour_of() */
     const DeepArgs& A = deep_args(AA);
     __shared__ LdsBlock S;
     __shared__ double2 log2_lds[kLog2Entries];
     if (threadIdx.x == 0) S.pal = A.pal;
+    if constexpr (SHIP) {
+        if (threadIdx.x == 0) S.log_bailout = AA.log_bailout;
+    }
     reinterpret_cast<double*>(log2_lds)[threadIdx.x] = reinterpret_cast<const double*>(A.log2_tab)[threadIdx.x];
     __syncthreads();
     if (threadIdx.x == 0) {                                       /* the colour of interior samples, once per workgroup */
         float rgb[3] = {0.0f, 0.0f, 0.0f};
-        colour_of<double, 0>(A, S, (double)A.max_iter, true, rgb);
+        colour_of<double, FRACTAL>(A, S, (double)A.max_iter, true, rgb);
         S.interior_rgb[0] = rgb[0]; S.interior_rgb[1] = rgb[1]; S.interior_rgb[2] = rgb[2];
     }
     __syncthreads();
@@ -710,7 +778,20 @@ deep_kernel(const ARGS AA)
             const double dcy = ((pys - 0.5 * resy) / resy) * zoom;
             int esc;
             double r2;
-            if constexpr (X) {
+            if constexpr (SHIP) {                                 /* the map of tile_kernel's Burning Ship path, less the centre */
+                const int ux = s / aa, uy = s - ux * aa;          /* burning_ship.comp:337-344: sx outer */
+                double uvx = (double)px / resx, uvy = (double)py / resy;
+                if (aa > 1) {
+                    const double pixel_size = 1.0 / resx;
+                    const double sample_offset = pixel_size / (double)aa;
+                    const double centre = sample_offset * (double)(aa - 1) * 0.5;
+                    uvx = uvx + ((double)ux * sample_offset - centre) / resx;
+                    uvy = uvy + ((double)uy * sample_offset - centre) / resy;
+                }
+                const double sdx = (uvx - 0.5) * zoom * (resx / resy);
+                const double sdy = (uvy - 0.5) * zoom;
+                deep_orbit_ship(A, inside ? sdx : 0.0, inside ? sdy : 0.0, z1, inside, esc, r2);
+            } else if constexpr (X) {
                 const DeepXArgs& XA = deepx_args(AA);
                 double cx = ((pxs - 0.5 * resx) / resy) * XA.zm, cy = ((pys - 0.5 * resy) / resy) * XA.zm;
                 int ec = XA.ze;
@@ -738,7 +819,7 @@ deep_kernel(const ARGS AA)
             }
             double nu;
             float rgb[3];
-            shade<double, 0>(A, S, lg, esc, r2, want_nu, want_rgb, nu, rgb);
+            shade<double, FRACTAL>(A, S, lg, esc, r2, want_nu, want_rgb, nu, rgb);
             if (s == 0) { nu0 = nu; it0 = esc; }
             acc[0] += rgb[0]; acc[1] += rgb[1]; acc[2] += rgb[2];
         }
@@ -746,7 +827,7 @@ deep_kernel(const ARGS AA)
             const float n = (float)(aa * aa);
             acc[0] /= n; acc[1] /= n; acc[2] /= n;
         }
-        if (want_rgb && (A.flags & FR_FLAG_POST_CHAIN)) post_chain(acc, A.brightness, A.saturation, A.contrast, false);
+        if (want_rgb && (A.flags & FR_FLAG_POST_CHAIN)) post_chain(acc, A.brightness, A.saturation, A.contrast, SHIP);
         if (!inside) return;
         const size_t o = plane_index(A.g, px, py, lrow);
         if (A.rgba) A.rgba[o] = make_float4(acc[0], acc[1], acc[2], 1.0f);

@@ -135,6 +135,14 @@ struct fr_ctx {
     hipEvent_t ev_xbla;         /* recorded behind every render with the flag (not while capturing): rebuilds wait for it */
     bool ev_xbla_valid;
     int deepx_bla_wg_per_cu;    /* resident workgroups per CU of deep_kernel<DeepXBlaArgs> (0 = not asked yet) */
+    /* deep Burning Ship views (fr_render_deep_ship): their own orbit cache, as fr_render_deep's */
+    double* ship_orbit_host;    /* pinned upload buffer, ship_orbit_cap points */
+    double2* ship_orbit_dev;    /* Z_0 .. Z_N of the ship's recurrence */
+    size_t ship_orbit_cap;
+    int32_t ship_len;           /* N + 1 */
+    OrbitKey ship_key;          /* of ship_orbit_dev */
+    int ship_wg_per_cu;         /* resident workgroups per CU of deep_kernel<DeepShipArgs> (0 = not asked yet) */
+    uint64_t ship_gen;          /* bumped whenever ship_orbit_dev receives another orbit */
 };
 
 #define FR_HIP_TRY(expr)                                                               \
@@ -226,6 +234,10 @@ extern "C" void fr_ctx_destroy(fr_ctx* c)
     if (c->deepx_dev) (void)hipFree(c->deepx_dev);
     free(c->deepx_key.x);
     free(c->deepx_key.y);
+    if (c->ship_orbit_host) (void)hipHostFree(c->ship_orbit_host);
+    if (c->ship_orbit_dev) (void)hipFree(c->ship_orbit_dev);
+    free(c->ship_key.x);
+    free(c->ship_key.y);
     if (c->bla_r) (void)hipFree(c->bla_r);
     if (c->bla_ab) (void)hipFree(c->bla_ab);
     if (c->bla_steps_dev) (void)hipFree(c->bla_steps_dev);
@@ -758,37 +770,62 @@ static int orbit_key_store(OrbitKey& k, const char* x, const char* y, int32_t bi
     return FR_OK;
 }
 
-static int deep_orbit_for(fr_ctx* c, const fr_params* p, const fr_deep_view* v, hipStream_t stream)
+/* One cache slot of plain-double orbits (fr_render_deep's, fr_render_deep_ship's): the buffers, what they hold, and the host
+ * function that computes the orbit */
+struct OrbitSlot {
+    double*& host;
+    double2*& dev;
+    size_t& cap;
+    int32_t& len;
+    OrbitKey& key;
+    uint64_t& gen;
+    int (*compute)(const fr_deep_view*, double, int32_t, float, double*, int32_t*);
+};
+
+static int orbit_slot_fill(fr_ctx* c, const OrbitSlot& o, const fr_params* p, const fr_deep_view* v, hipStream_t stream)
 {
     const int32_t bits = v->frac_bits ? v->frac_bits : fr_deep_frac_bits(p->zoom);
     const int32_t max_iter = p->max_iterations;
-    if (orbit_key_matches(c->deep_key, v->center_x, v->center_y, bits, max_iter, p->bailout)) return FR_OK;
+    if (orbit_key_matches(o.key, v->center_x, v->center_y, bits, max_iter, p->bailout)) return FR_OK;
     /* the pinned buffer may still feed an earlier upload, the device orbit an earlier render (on this stream, the
      * context's own or the stream of the previous render) */
     FR_HIP_TRY(hipStreamSynchronize(stream));
     FR_HIP_TRY(hipStreamSynchronize(c->stream));
     if (c->have_render && c->last_stream != stream) FR_HIP_TRY(hipStreamSynchronize(c->last_stream));
     if (c->ev_bla_valid) FR_HIP_TRY(hipEventSynchronize(c->ev_bla));      /* the last BLA render, wherever it went */
-    c->deep_key.valid = false;
-    ++c->deep_gen;
+    o.key.valid = false;
+    ++o.gen;
     const size_t need = (size_t)max_iter + 1;
-    if (need > c->deep_orbit_cap) {
-        if (c->deep_orbit_host) { (void)hipHostFree(c->deep_orbit_host); c->deep_orbit_host = nullptr; }
-        if (c->deep_orbit_dev) { (void)hipFree(c->deep_orbit_dev); c->deep_orbit_dev = nullptr; }
-        c->deep_orbit_cap = 0;
-        FR_HIP_TRY(hipHostMalloc((void**)&c->deep_orbit_host, need * 2 * sizeof(double)));
-        FR_HIP_TRY(hipMalloc((void**)&c->deep_orbit_dev, need * sizeof(double2)));
-        c->deep_orbit_cap = need;
+    if (need > o.cap) {
+        if (o.host) { (void)hipHostFree(o.host); o.host = nullptr; }
+        if (o.dev) { (void)hipFree(o.dev); o.dev = nullptr; }
+        o.cap = 0;
+        FR_HIP_TRY(hipHostMalloc((void**)&o.host, need * 2 * sizeof(double)));
+        FR_HIP_TRY(hipMalloc((void**)&o.dev, need * sizeof(double2)));
+        o.cap = need;
     }
     int32_t len = 0;
-    const int st = fr_deep_reference_orbit(v, p->zoom, max_iter, p->bailout, c->deep_orbit_host, &len);
+    const int st = o.compute(v, p->zoom, max_iter, p->bailout, o.host, &len);
     if (st != FR_OK) return st;
-    FR_HIP_TRY(hipMemcpyAsync(c->deep_orbit_dev, c->deep_orbit_host, (size_t)len * sizeof(double2), hipMemcpyHostToDevice,
-                              stream));
+    FR_HIP_TRY(hipMemcpyAsync(o.dev, o.host, (size_t)len * sizeof(double2), hipMemcpyHostToDevice, stream));
     FR_HIP_TRY(hipStreamSynchronize(stream));     /* a later render of this view may go to another stream */
-    const int ks = orbit_key_store(c->deep_key, v->center_x, v->center_y, bits, max_iter, p->bailout);
-    if (ks == FR_OK) c->deep_len = len;
+    const int ks = orbit_key_store(o.key, v->center_x, v->center_y, bits, max_iter, p->bailout);
+    if (ks == FR_OK) o.len = len;
     return ks;
+}
+
+static int deep_orbit_for(fr_ctx* c, const fr_params* p, const fr_deep_view* v, hipStream_t stream)
+{
+    const OrbitSlot o = {c->deep_orbit_host, c->deep_orbit_dev, c->deep_orbit_cap, c->deep_len, c->deep_key, c->deep_gen,
+                         fr_deep_reference_orbit};
+    return orbit_slot_fill(c, o, p, v, stream);
+}
+
+static int ship_orbit_for(fr_ctx* c, const fr_params* p, const fr_deep_view* v, hipStream_t stream)
+{
+    const OrbitSlot o = {c->ship_orbit_host, c->ship_orbit_dev, c->ship_orbit_cap, c->ship_len, c->ship_key, c->ship_gen,
+                         fr_deep_ship_reference_orbit};
+    return orbit_slot_fill(c, o, p, v, stream);
 }
 
 /* BLA: the table of the cached orbit for this frame's dcmax (the whole frame's W, H and zoom), built on `stream` unless
@@ -884,7 +921,7 @@ static void fill_deep_args(DeepArgs& a, const fr_ctx* c, const fr_params* p, con
     a.inv_log2_bailout = 1.0 / log2((double)p->bailout);
     a.color_scale_d = (double)p->color_scale; a.color_offset_d = (double)p->color_offset;
     a.brightness = p->color_brightness; a.saturation = p->color_saturation; a.contrast = p->color_contrast;
-    fr_palette_table_build(0, p->palette_mode, &a.pal);
+    fr_palette_table_build(p->fractal_type != FR_FRACTAL_MANDELBROT ? 1 : 0, p->palette_mode, &a.pal);   /* as fill_params */
     a.log2_tab = c->log2_tab;
     a.rgba = reinterpret_cast<float4*>(rgba); a.nu = (double*)nu; a.iter = iter;
 }
@@ -907,6 +944,29 @@ static int enqueue_deep(fr_ctx* c, const fr_params* p, const fr_deep_view* v, ui
 
     if (p->flags & FR_FLAG_DEEP_BLA) return enqueue_deep_bla(c, p, a, stream);
     return launch_one_pass(c, stream, "deep_kernel<DeepArgs>", deep_kernel<DeepArgs>, a, a.g, a.q, c->deep_wg_per_cu, false);
+}
+
+/* ---- deep Burning Ship views (fr_render_deep_ship) --------------------------------------------------------------------
+ * enqueue_deep on the ship's own orbit slot and deep_kernel<DeepShipArgs> */
+static int enqueue_deep_ship(fr_ctx* c, const fr_params* p, const fr_deep_view* v, uint32_t W, uint32_t H,
+                             const fr_shard* shard, float* rgba, void* nu, int32_t* iter, hipStream_t stream, bool out_frame)
+{
+    fr_shard norm;
+    uint32_t rows_local = 0;
+    const int sh = begin_shard(c, shard, H, &norm, &rows_local);
+    if (sh != FR_OK || rows_local == 0) return sh;
+    const int os = ship_orbit_for(c, p, v, stream);
+    if (os != FR_OK) return os;
+
+    DeepShipArgs s;
+    memset(&s, 0, sizeof(s));
+    DeepArgs& a = s.d;
+    a.orbit = c->ship_orbit_dev; a.n_ref = c->ship_len - 1;
+    a.zoom = p->zoom;
+    fill_deep_args(a, c, p, tile_geom(W, H, rows_local, &norm, out_frame), rgba, nu, iter);
+    s.log_bailout = log((double)p->bailout);     /* as fill_params */
+    return launch_one_pass(c, stream, "deep_kernel<DeepShipArgs>", deep_kernel<DeepShipArgs>, s, a.g, a.q, c->ship_wg_per_cu,
+                           false);
 }
 
 /* ---- extended views (fr_render_deepx) -------------------------------------------------------------------------------
@@ -1347,7 +1407,8 @@ static int enqueue_ssaa_staged(fr_ctx* c, const fr_params* p, uint32_t W, uint32
 }
 
 /* ---- render entry points --------------------------------------------------------------------------------------------
- * fr_render_shard, fr_render_phoenix, fr_render_mandelbulb, fr_render_deep and fr_render_deepx, each with its _async form:
+ * fr_render_shard, fr_render_phoenix, fr_render_mandelbulb, fr_render_deep, fr_render_deep_ship and fr_render_deepx, each with
+ * its _async form:
  * their parameter checks, then render_sync / render_async with the enqueue step as
  * enqueue(shard, rgba, nu, iter, stream, out_frame) */
 static int check_common(fr_ctx* c, const fr_params* p, uint32_t W, uint32_t H, const fr_output* out)
@@ -1679,6 +1740,32 @@ extern "C" int fr_render_deep(fr_ctx* c, const fr_params* p, const fr_deep_view*
     if (st != FR_OK) return st;
     return render_sync(c, p, W, H, shard, out, [&](auto sh, auto rgba, auto nu, auto iter, auto s, bool out_frame) {
         return enqueue_deep(c, p, v, W, H, sh, rgba, nu, iter, s, out_frame); });
+}
+
+static int check_deep_ship(fr_ctx* c, const fr_params* p, const fr_deep_view* v, uint32_t W, uint32_t H, const fr_output* out)
+{
+    if (!c) return fr_set_error(FR_ERR_INVALID_ARG, "ctx is NULL");
+    if (!p || !v || !out) return fr_set_error(FR_ERR_INVALID_ARG, "params/deep view/out is NULL");
+    return fr_deep_ship_validate(p, v, W, H);
+}
+
+extern "C" int fr_render_deep_ship_async(fr_ctx* c, const fr_params* p, const fr_deep_view* v, uint32_t W, uint32_t H,
+                                         const fr_shard* shard, const fr_output* out, void* hip_stream)
+{
+    const int st = check_deep_ship(c, p, v, W, H, out);
+    if (st != FR_OK) return st;
+    return render_async("fr_render_deep_ship_async", c, H, shard, out, hip_stream,
+                        [&](auto sh, auto rgba, auto nu, auto iter, auto s, bool out_frame) {
+                            return enqueue_deep_ship(c, p, v, W, H, sh, rgba, nu, iter, s, out_frame); });
+}
+
+extern "C" int fr_render_deep_ship(fr_ctx* c, const fr_params* p, const fr_deep_view* v, uint32_t W, uint32_t H,
+                                   const fr_shard* shard, const fr_output* out)
+{
+    const int st = check_deep_ship(c, p, v, W, H, out);
+    if (st != FR_OK) return st;
+    return render_sync(c, p, W, H, shard, out, [&](auto sh, auto rgba, auto nu, auto iter, auto s, bool out_frame) {
+        return enqueue_deep_ship(c, p, v, W, H, sh, rgba, nu, iter, s, out_frame); });
 }
 
 static int check_deepx(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, uint32_t W, uint32_t H, const fr_output* out)

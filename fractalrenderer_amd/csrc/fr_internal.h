@@ -29,6 +29,8 @@ int fr_phoenix_validate(const fr_params* p, const fr_phoenix_params* ph, uint32_
 int fr_mandelbulb_validate(const fr_params* p, const fr_mandelbulb_params* mb, uint32_t width, uint32_t height);
 /* the validation of fr_render_deep (fr_deep.c), the centre strings parsed included */
 int fr_deep_validate(const fr_params* p, const fr_deep_view* v, uint32_t width, uint32_t height);
+/* the validation of fr_render_deep_ship (fr_deep.c): fr_deep_validate's rules for FR_FRACTAL_BURNING_SHIP */
+int fr_deep_ship_validate(const fr_params* p, const fr_deep_view* v, uint32_t width, uint32_t height);
 /* the validation of fr_render_deepx (fr_deep.c), and its view resolved: the zoom pair and the fraction bits */
 int fr_deepx_validate(const fr_params* p, const fr_deepx_view* v, uint32_t width, uint32_t height);
 int fr_deepx_resolve(const fr_deepx_view* v, double* zm, int32_t* ze, int32_t* frac_bits);

@@ -262,9 +262,26 @@ class Renderer:
         self._render_call(self._lib.fr_render_deep, self._lib.fr_render_deep_async, (C.byref(p), C.byref(v)), width, height,
                           Precision.F64, rows, rgba, nu, iter, shard, stream, sync)
 
+    def render_deep_ship(self, state: FractalState, width: int, height: int, view: Optional[DeepView] = None, *,
+                         post_chain: bool = False, rgba=None, nu=None, iter=None, shard: Optional[Shard] = None,
+                         stream: Optional[int] = None, sync: bool = True) -> None:
+        """fr_render_deep_ship / fr_render_deep_ship_async: a Burning Ship view deeper than double precision, by perturbation
+        around one reference orbit of the ship's recurrence computed on the host.  `view` carries the centre as decimal
+        strings (a view with a zoom string is a ValueError: extended exponents are Mandelbrot's); the zoom, in
+        [1e-290, 1e3], and every other field come from `state` (its double centre is not read).  Always fp64: nu is float64.
+        Planes, shard, stream and sync as for render_deep(); the context keeps the ship's orbit next to render_deep's."""
+        if view is not None and view.zoom is not None:
+            raise ValueError("render_deep_ship takes the zoom from the state: extended views (a zoom string) are Mandelbrot only")
+        p = state.to_params(FractalType.BurningShip, Precision.F64, post_chain)
+        v = (view or DeepView()).to_c()
+        rows = shard.rows(height) if shard else height
+        self._render_call(self._lib.fr_render_deep_ship, self._lib.fr_render_deep_ship_async, (C.byref(p), C.byref(v)), width,
+                          height, Precision.F64, rows, rgba, nu, iter, shard, stream, sync)
+
     def _render_call(self, fn_sync, fn_async, params: tuple, width: int, height: int, precision: Precision, rows: int,
                      rgba, nu, it, shard: Optional[Shard], stream: Optional[int], sync: bool) -> None:
-        """the planes, the shard and the sync / async entry of render(), render_phoenix(), render_mandelbulb() and render_deep();
+        """the planes, the shard and the sync / async entry of render(), render_phoenix(), render_mandelbulb(), render_deep() and
+        render_deep_ship();
         params: the entry's
         arguments between the context and the frame size"""
         out = self._output(precision, rows, width, rgba, nu, it)

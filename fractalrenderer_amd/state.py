@@ -224,6 +224,16 @@ def deep_reference_orbit(view: DeepView, zoom: float, max_iterations: int, bailo
     return buf[:n.value].copy()
 
 
+def deep_ship_reference_orbit(view: DeepView, zoom: float, max_iterations: int, bailout: float = 4.0) -> np.ndarray:
+    """fr_deep_ship_reference_orbit: Z_0 .. Z_N of the Burning Ship recurrence at the view's centre, as deep_reference_orbit."""
+    buf = np.empty((int(max_iterations) + 1, 2), np.float64)
+    n = _capi.C.c_int32()
+    v = view.to_c()
+    _capi.check(_capi.lib().fr_deep_ship_reference_orbit(_capi.C.byref(v), float(zoom), int(max_iterations), _F32(bailout),
+                                                         buf.ctypes.data, _capi.C.byref(n)))
+    return buf[:n.value].copy()
+
+
 def deepx_zoom(zoom) -> tuple:
     """fr_deepx_zoom: a decimal zoom string as (zm, ze), zoom = zm 2^ze, zm in [1, 2) correctly rounded."""
     zm, ze = _capi.C.c_double(), _capi.C.c_int32()

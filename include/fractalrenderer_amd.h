@@ -508,6 +508,59 @@ int fr_render_deep_async(fr_ctx* ctx, const fr_params* p, const fr_deep_view* vi
  * FR_ERR_UNSUPPORTED if there is no such call. */
 int fr_ctx_last_deep_steps(fr_ctx* ctx, uint64_t out[3]);
 
+/* ---- Burning Ship views deeper than double precision ----------------------------------------------------------------------
+ * fr_render_deep for z <- (|x| + i |y|)^2 + c: the same perturbation around one reference orbit with rebasing, the same view
+ * (fr_deep_view, p->zoom in [1e-290, 1e3], p->center_x / p->center_y ignored), planes, shards and asynchronous rules.  The
+ * mini-ships along the needle near -1.75 lie far below double precision; this is the path that shows them.
+ *
+ * p->fractal_type must be FR_FRACTAL_BURNING_SHIP and p->precision FR_PRECISION_F64.  FR_ERR_UNSUPPORTED also where the ship
+ * needs the whole orbit -- orbit_trap_enabled, stripe_enabled with interior_style 2, interior_style 3 -- and for
+ * FR_FLAG_DEEP_BLA or FR_FLAG_DEEPX_BLA.  The other fields follow fr_params_validate's rules; bailout must be <= 2^16.
+ * fr_render_deep keeps rejecting FR_FRACTAL_BURNING_SHIP.
+ *
+ * Reference orbit: fr_render_deep's fixed point and escape test, with
+ *   Re = floor(Zr Zr / 2^F) - floor(Zi Zi / 2^F) + Cr,   Im = floor(2 |Zr| |Zi| / 2^F) + Ci
+ * (|Zr|^2 = Zr^2, so Re is unchanged).  Z_0 .. Z_N are stored as doubles, SIGNED.
+ *
+ * The fold: for an orbit coordinate X and a delta a, |X + a| - |X| without forming |X + a| from a cancelling sum --
+ *   fold(X, a):  w = X + a;  d = (X + X) + a;     X >= 0 ?  (w >= 0 ? a : -d)  :  (w > 0 ? d : -a)
+ * The sign of w is exact: an IEEE sum is zero only when it is exactly zero.
+ *
+ * Per sample (x, y) and sub-sample s = 0 .. aa*aa-1 with sx = s / aa (OUTER), sy = s % aa -- shaders/burning_ship.comp:393,
+ * :322-325, :337-344, the map fr_render's fp64 Burning Ship path applies, less the centre:
+ *   uvx = x / W;  uvy = y / H;   aa > 1:  pixel_size = 1 / W;  sample_offset = pixel_size / aa;
+ *       centre = sample_offset * (aa - 1) * 0.5;  uvx = uvx + (sx * sample_offset - centre) / W;
+ *       uvy = uvy + (sy * sample_offset - centre) / H
+ *   dc = ((uvx - 0.5) * zoom * aspect, (uvy - 0.5) * zoom),  aspect = (double)W / (double)H of the WHOLE frame
+ * (not Mandelbrot's map).  dz = 0, m = 0; then for i = 0 .. max_iter-1, with Z_m = (X, Y), dz = (a, b),
+ * U = (|X|, |Y|), f = (fold(X, a), fold(Y, b)):
+ *   t = (U + U) + f;  dz' = (t.x f.x - t.y f.y, t.x f.y + t.y f.x) + dc;  m += 1;  z = Z_m + dz';  r2 = |z|^2
+ *   r2 > bailout^2: escaped at i;  else if r2 < |dz'|^2 or m == N: dz = z, m = 0 (rebase);  else dz = dz'
+ * each operation one fp64 rounding as written (no contraction).  Z_0 = 0 keeps the rebase valid: at m = 0 the step is
+ * (|a| + i |b|)^2 + dc.  The planes are those of fr_render's fp64 Burning Ship path for the same (i, r2): nu (double) =
+ * i + 1 - log2(log2(r2) / log2(bailout)) of sample s = 0 (max_iterations for interior), iter = its i, rgba = palette,
+ * interior samples black (burning_ship.comp:259-283 without effects), aa average, FR_FLAG_POST_CHAIN with the Julia /
+ * Burning Ship floors.  A shard's planes equal the matching rows of the whole frame, byte for byte.
+ *
+ * The context keeps the most recent ship orbit on the device in a slot of its own, keyed as fr_render_deep's: a ship render
+ * never evicts the Mandelbrot orbit, nor the reverse.
+ *
+ * Out of scope: BLA for the ship (its linear map is a real 2x2 matrix with fold conditions), extended exponents below
+ * 1e-290, fr_node and .franim. */
+#define FR_HAS_DEEP_SHIP 1
+
+/* fr_deep_reference_orbit for the ship's recurrence: same arguments, validation and cost */
+int fr_deep_ship_reference_orbit(const fr_deep_view* v, double zoom, int32_t max_iter, float bailout, double* out_xy,
+                                 int32_t* out_len);
+
+/* fr_render_deep's contract (planes, memory kinds, FR_LAYOUT_FRAME, shards, options, fr_ctx_last_kernel_ms / _grid) */
+int fr_render_deep_ship(fr_ctx* ctx, const fr_params* p, const fr_deep_view* view, uint32_t width, uint32_t height,
+                        const fr_shard* shard, const fr_output* out);
+
+/* fr_render_deep_async's contract: a render of a new view computes its orbit on the host first and is never launch-only */
+int fr_render_deep_ship_async(fr_ctx* ctx, const fr_params* p, const fr_deep_view* view, uint32_t width, uint32_t height,
+                              const fr_shard* shard, const fr_output* out, void* hip_stream);
+
 /* ---- deep views below 1e-290: extended-exponent deltas ----------------------------------------------------------------
  * fr_render_deep stops where a double can no longer hold the zoom, a sample's dc and dz, or an orbit point that passes
  * close to 0.  These entry points take the ZOOM as a decimal string too and carry every delta as two double mantissas

@@ -106,12 +106,19 @@ def perturb(orbit: np.ndarray, dcx: np.ndarray, dcy: np.ndarray, max_iter: int, 
     return it.reshape(shape), r2out.reshape(shape), rebases
 
 
-def smooth(it: np.ndarray, r2: np.ndarray, max_iter: int) -> np.ndarray:
-    """nu of the fp64 Mandelbrot path: i + 1 - log2(log2|z|) for an escaped sample, max_iter otherwise"""
+def smooth(it: np.ndarray, r2: np.ndarray, max_iter: int, bailout: float = 4.0) -> np.ndarray:
+    """nu of the fp64 Mandelbrot path: i + 1 - log2(log2|z|) for an escaped sample, max_iter otherwise.  At bailout <= 1
+    the kernel takes the shader's form as written, through the library log: log_zn = log(r2) / 2,
+    nu = i + 1 - log(log_zn / ln 2) / ln 2 -- NaN where log_zn < 0 (r2 < 1), +inf where r2 == 1."""
     nu = np.full(it.shape, float(max_iter))
     e = it < max_iter
     with np.errstate(all="ignore"):
-        nu[e] = (it[e] + 1.0) - np.log2(0.5 * np.log2(r2[e]))
+        if np.float32(bailout) > np.float32(1.0):
+            nu[e] = (it[e] + 1.0) - np.log2(0.5 * np.log2(r2[e]))
+        else:
+            ln2 = np.log(np.float64(2.0))
+            log_zn = np.log(r2[e]) / np.float64(2.0)
+            nu[e] = (it[e].astype(np.float64) + 1.0) - np.log(log_zn / ln2) / ln2
     return nu
 
 

@@ -115,12 +115,18 @@ def perturb(orbit: np.ndarray, dcx: np.ndarray, dcy: np.ndarray, max_iter: int, 
 
 
 def smooth(it: np.ndarray, r2: np.ndarray, max_iter: int, bailout: float = 4.0) -> np.ndarray:
-    """nu of the fp64 Burning Ship path: i + 1 - log2(log2(r2) / log2(bailout)) for an escaped sample, max_iter otherwise"""
+    """nu of the fp64 Burning Ship path: i + 1 - log2(log2(r2) / log2(bailout)) for an escaped sample, max_iter otherwise.
+    At bailout <= 1 the kernel takes the shader's form as written, through the library log:
+    nu = i + 1 - log(log(r2) / log(bailout)) / ln 2 -- NaN where the quotient is negative, -inf at bailout == 1."""
     nu = np.full(it.shape, float(max_iter))
     e = it < max_iter
-    inv = np.float64(1.0) / np.log2(np.float64(np.float32(bailout)))
+    b = np.float64(np.float32(bailout))
     with np.errstate(all="ignore"):
-        nu[e] = (it[e] + 1.0) - np.log2(np.log2(r2[e]) * inv)
+        if np.float32(bailout) > np.float32(1.0):
+            inv = np.float64(1.0) / np.log2(b)
+            nu[e] = (it[e] + 1.0) - np.log2(np.log2(r2[e]) * inv)
+        else:
+            nu[e] = (it[e].astype(np.float64) + 1.0) - np.log(np.log(r2[e]) / np.log(b)) / np.log(np.float64(2.0))
     return nu
 
 

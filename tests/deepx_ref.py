@@ -143,7 +143,7 @@ def perturb_x(mant, exp2, dc, max_iter: int, bailout: float = 4.0, stats=None):
     ed = np.full(n, X_ZERO, np.int64)
     ext = np.ones(n, bool)
     m = np.zeros(n, np.int64)
-    n_ext = n_plain = to_plain = to_ext = 0
+    n_ext = n_plain = to_plain = to_ext = n_reb = 0
     with np.errstate(all="ignore"):
         for i in range(max_iter):
             if idx.size == 0:
@@ -176,6 +176,7 @@ def perturb_x(mant, exp2, dc, max_iter: int, bailout: float = 4.0, stats=None):
                 es = r2d > B2
                 n2 = nx * nx + ny * ny
                 reb = ~es & ((r2 < _ld(n2, 2 * (en - ez))) | (mm == N))
+                n_reb += int(reb.sum())
                 ax, ay, ea = _norm(np.where(reb, zx, nx), np.where(reb, zy, ny), np.where(reb, ez, en))
                 stay = ea <= X_THR
                 to_plain += int((~stay & ~es).sum())
@@ -201,6 +202,7 @@ def perturb_x(mant, exp2, dc, max_iter: int, bailout: float = 4.0, stats=None):
                 r2 = zx * zx + zy * zy
                 es = r2 > B2
                 reb = ~es & ((r2 < nx * nx + ny * ny) | (mm == N))
+                n_reb += int(reb.sum())
                 ax = np.where(reb, zx, nx)
                 ay = np.where(reb, zy, ny)
                 small = np.maximum(np.abs(ax), np.abs(ay)) < _THR
@@ -220,7 +222,8 @@ def perturb_x(mant, exp2, dc, max_iter: int, bailout: float = 4.0, stats=None):
                 idx, dx, dy, ed, ext, m = idx[k], dx[k], dy[k], ed[k], ext[k], m[k]
                 cx, cy, ec, cpx, cpy = cx[k], cy[k], ec[k], cpx[k], cpy[k]
     if stats is not None:
-        for key, v in (("ext_steps", n_ext), ("plain_steps", n_plain), ("to_plain", to_plain), ("to_ext", to_ext)):
+        for key, v in (("ext_steps", n_ext), ("plain_steps", n_plain), ("to_plain", to_plain), ("to_ext", to_ext),
+                       ("rebases", n_reb)):
             stats[key] = stats.get(key, 0) + v
     return it, r2out
 

@@ -73,6 +73,7 @@ CASES = {
     "ship_small_bailout_f64": (OracleParams(fractal=2, center_x=-0.5, center_y=-0.5, zoom=3.5, max_iterations=200,
                                             bailout=1.5), 64, 48),
     # Deep_Zoom: the reference's perturbation shader (shaders/test_deep_zoom.comp), fp32 float-float
+    # (the loop-structure cases -- group tails, phase joins, palettes -- are in deepzoom_cases.py)
     "deepzoom_seahorse": (OracleParams(fractal=5, precision=0, center_x=SEAHORSE[0], center_y=SEAHORSE[1], zoom=1e-6,
                                        max_iterations=2000, use_perturbation=1), 72, 40),
     "deepzoom_wide_escaping_reference": (OracleParams(fractal=5, precision=0, center_x=-0.75, center_y=0.1, zoom=100.0,

@@ -2635,6 +2635,53 @@ pool_kernel(const LaunchArgs A)
                 unchecked = fast && !(A.stripe_enabled && A.interior_style == 0 &&
                                       (uint32_t)(next_deadline - wclock) < 4u * (uint32_t)kFastBlock);
             }
+            if constexpr (!PERIOD && !STRIPES) {
+                if (unchecked) {
+                    /* CLEAN RUN.  The stretch loop around this one also holds the dirty path, reach_deadline and the tested
+                     * stretch, which rewrite every field of the lane, so the register allocator keeps two homes for the
+                     * whole lane state and copies between them on every trip: 25 moves around the 96-384 fp64 instructions
+                     * of a stretch.  A clean stretch that reaches no deadline changes the orbit and
+                     * three wave-uniform scalars and nothing else, so a run of them is a loop of its own, which nothing
+                     * that touches the lane is part of.  Same stretches, same lengths, same order of updates as the general
+                     * form below: `newly` does not change on a clean stretch short of a deadline (so `newly < goal` holds),
+                     * `fast` does not change here at all, and the watchdog is looked at before every stretch. */
+                    T sX, sYd;
+                    uint32_t len;
+                    bool bad;
+                    uint64_t badm;
+                    for (;;) {
+                        sX = o.X; sYd = o.Yd;
+                        const uint32_t reps = streak >= 6u ? 4u : (streak >= 2u ? 2u : 1u);
+                        len = reps * (uint32_t)kFastBlock;
+                        for (uint32_t rep = 0; rep < reps; ++rep) {
+#pragma unroll
+                            for (int k = 0; k < kFastBlock; ++k) orbit_step<T, Form<FRACTAL>::abs_step>(o);
+                        }
+                        bad = !(orbit_r2x4(o) <= B2x4);
+                        badm = __builtin_amdgcn_ballot_w64(bad);
+                        if (badm != 0ull) break;                     /* dirty: handled below, once */
+                        ++streak;
+                        wclock += len;
+                        if ((int32_t)(wclock - next_deadline) >= 0 || (int32_t)(wclock - watchdog) > 0) break;
+                    }
+                    bool ring_full = false;
+                    if (badm != 0ull) {
+                        /* dirty stretch: as in the general form below */
+                        const uint32_t nbad = D.push(dtail, badm, bad, L.pixel, L.index_at(wclock, (uint32_t)max_iter), sX, sYd, o);
+                        if (bad) { L.pixel = kInvalidPixel; o.park(); }
+                        dtail += nbad;
+                        newly += nbad;
+                        streak = 0;
+                        ring_full = dtail - dhead >= 64u;
+                        __builtin_amdgcn_wave_barrier();
+                        FR_STAMP_COUNT(2, len);  /* diagnostic: updates of dirty unchecked stretches */
+                        wclock += len;
+                    }
+                    if ((int32_t)(wclock - next_deadline) >= 0) reach_deadline(true);
+                    if (ring_full) break;
+                    continue;
+                }
+            }
             if (unchecked) {
                 const T sX = o.X, sYd = o.Yd;
                 /* after 2 (6) clean stretches in a row the wave runs 2 (4) blocks per snapshot / test (a half, a

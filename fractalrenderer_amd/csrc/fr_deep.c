@@ -545,8 +545,8 @@ int fr_deep_ship_validate(const fr_params* p, const fr_deep_view* v, uint32_t wi
         return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deep_ship: the orbit trap, stripes with interior_style 2 and "
                             "interior_style 3 need the whole orbit and are not available");
     if (p->flags & (FR_FLAG_DEEP_BLA | FR_FLAG_DEEPX_BLA))
-        return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deep_ship: bilinear approximation is not available for the Burning "
-                            "Ship (FR_FLAG_DEEP_BLA / FR_FLAG_DEEPX_BLA)");
+        return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deep_ship: FR_FLAG_DEEP_BLA / FR_FLAG_DEEPX_BLA are not available (their "
+                            "tables are Mandelbrot's): the flag of the ship is FR_FLAG_DEEP_SHIP_BLA");
     const int F = view_frac_bits(v, p->zoom);
     if (F < 0) return F;
     uint64_t cr[kMaxLimbs], ci[kMaxLimbs];

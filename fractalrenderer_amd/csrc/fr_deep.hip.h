@@ -42,6 +42,12 @@
  * registers and prefetch.  The orbit is the ship's own (fr_deep.c), dc is the Burning Ship shader's viewport map less the
  * centre (sx outer), and the colour stage is that of the fp64 Burning Ship path: shade<double, 2>, interior samples
  * black, the post chain with the Julia / Burning Ship floors.
+ *
+ * BLA for the ship (FR_FLAG_DEEP_SHIP_BLA; the semantics are in the header): while no fold flips a sign the ship's step less
+ * its square term is a real 2x2 map, 2 |Z_m| times a rotation or reflection.  deep_ship_bla_level_kernel builds the table
+ * from the ship's device orbit, one launch per level -- r in an array of doubles of its own, the eight doubles of (A, B) as
+ * four double2 per entry -- and deep_kernel<DeepShipBlaArgs> runs deep_orbit_ship_bla: deep_orbit_ship whose lanes probe
+ * the table as deep_orbit_bla does.  A probe gathers 8 bytes, only the chosen level's 64 bytes of (A, B) are loaded.
  */
 #pragma once
 #include "fr_kernels.hip.h"
@@ -281,6 +287,170 @@ __device__ __forceinline__ void deep_orbit_bla(const DeepArgs& A, const BlaTable
             const double tx = (Zx + Zx) + dzx, ty = (Zy + Zy) + dzy;
             nx = (tx * dzx - ty * dzy) + dcx;
             ny = (tx * dzy + ty * dzx) + dcy;
+            step = 1;
+            ++nplain;
+            m += 1;
+            Zmx = Znx; Zmy = Zny;
+        }
+        u += step;
+        const double zx = Zmx + nx, zy = Zmy + ny;
+        const double r2 = zx * zx + zy * zy;
+        if (r2 > B2) {
+            esc = u - 1; er2 = r2; live = false;                 /* the last update the step covered */
+        } else if (r2 < nx * nx + ny * ny || m == N) {           /* rebase */
+            dzx = zx; dzy = zy; m = 0;
+            Zx = 0.0; Zy = 0.0; Znx = z1.x; Zny = z1.y;
+        } else {
+            dzx = nx; dzy = ny;
+            Zx = Zmx; Zy = Zmy;
+            if (k > 0) {                                          /* m < N here */
+                const double2 Zn = orbit[m + 1];
+                Znx = Zn.x; Zny = Zn.y;
+            } else {
+                Znx = Znn.x; Zny = Znn.y;
+            }
+        }
+        if (u >= max_iter) live = false;                          /* esc stays max_iter */
+    }
+}
+
+/* ---- BLA for the ship (FR_FLAG_DEEP_SHIP_BLA; the semantics are in the header) --------------------------------------------
+ * The table of the ship's cached orbit: levels and offsets are those of the Mandelbrot table, an entry is r and the real
+ * matrices A = (a11, a12, a21, a22), B = (b11, b12, b21, b22). */
+struct ShipBlaTable {
+    const double* r;                     /* r of every entry, level 1 first */
+    const double2* ab;                   /* ab[4 e .. 4 e + 3] = (a11, a12), (a21, a22), (b11, b12), (b21, b22) */
+    int32_t levels;                      /* K = floor(log2(N - 1)), 0 = no table */
+    unsigned long long* steps;           /* plain steps, BLA steps, updates skipped: one atomic add each per wave */
+};
+
+struct DeepShipBlaArgs {
+    DeepShipArgs s;
+    ShipBlaTable t;
+};
+
+/* one entry while it is being merged: the rows of A and of B, and r */
+struct ShipLin {
+    double2 a1, a2, b1, b2;
+    double r;
+};
+
+/* The single step at orbit point Z = (X, Y): A = [[2X, -2Y], [2|Y| sgn X, 2|X| sgn Y]], B = 1, r = 2^-53 |Z| capped by |X|
+ * and |Y| (the fold conditions: below them no fold flips a sign). */
+__device__ __forceinline__ ShipLin ship_single(const double2 Z)
+{
+    const double ax = fabs(Z.x), ay = fabs(Z.y);
+    const double sx = Z.x >= 0.0 ? 1.0 : -1.0, sy = Z.y >= 0.0 ? 1.0 : -1.0;
+    ShipLin s;
+    s.a1 = make_double2(Z.x + Z.x, -(Z.y + Z.y));
+    s.a2 = make_double2((ay + ay) * sx, (ax + ax) * sy);
+    s.b1 = make_double2(1.0, 0.0);
+    s.b2 = make_double2(0.0, 1.0);
+    double r = 0x1p-53 * bla_abs(Z.x, Z.y);
+    r = r < ax ? r : ax;
+    r = r < ay ? r : ay;
+    s.r = r;
+    return s;
+}
+
+/* Level k of the ship's table: deep_bla_level_kernel with the real 2x2 products.  |A_x| is the length of A_x's first column
+ * (A_x is a scaled orthogonal matrix: its operator norm), |B_x| the Frobenius norm. */
+__global__ void __launch_bounds__(kBlockThreads)
+deep_ship_bla_level_kernel(const double2* __restrict__ orbit, const int32_t n_ref, const int32_t k, const double dcmax,
+                           double* __restrict__ r, double2* __restrict__ ab)
+{
+    const uint32_t n1 = (uint32_t)(n_ref - 1);
+    const uint32_t cnt = n1 >> k;
+    const uint32_t off = bla_offset(n1, k);
+    const uint32_t offp = k > 1 ? bla_offset(n1, k - 1) : 0u;
+    for (uint32_t j = blockIdx.x * kBlockThreads + threadIdx.x; j < cnt; j += gridDim.x * kBlockThreads) {
+        ShipLin x, y;
+        if (k == 1) {
+            x = ship_single(orbit[1 + 2 * j]);
+            y = ship_single(orbit[2 + 2 * j]);
+        } else {
+            const uint32_t ex = offp + 2 * j, ey = ex + 1;
+            x.a1 = ab[4 * ex]; x.a2 = ab[4 * ex + 1]; x.b1 = ab[4 * ex + 2]; x.b2 = ab[4 * ex + 3]; x.r = r[ex];
+            y.a1 = ab[4 * ey]; y.a2 = ab[4 * ey + 1]; y.b1 = ab[4 * ey + 2]; y.b2 = ab[4 * ey + 3]; y.r = r[ey];
+        }
+        const double2 a1 = make_double2(y.a1.x * x.a1.x + y.a1.y * x.a2.x, y.a1.x * x.a1.y + y.a1.y * x.a2.y);
+        const double2 a2 = make_double2(y.a2.x * x.a1.x + y.a2.y * x.a2.x, y.a2.x * x.a1.y + y.a2.y * x.a2.y);
+        const double2 b1 = make_double2((y.a1.x * x.b1.x + y.a1.y * x.b2.x) + y.b1.x, (y.a1.x * x.b1.y + y.a1.y * x.b2.y) + y.b1.y);
+        const double2 b2 = make_double2((y.a2.x * x.b1.x + y.a2.y * x.b2.x) + y.b2.x, (y.a2.x * x.b1.y + y.a2.y * x.b2.y) + y.b2.y);
+        const double nb = sqrt((x.b1.x * x.b1.x + x.b1.y * x.b1.y) + (x.b2.x * x.b2.x + x.b2.y * x.b2.y));
+        const double t = (y.r - nb * dcmax) / bla_abs(x.a1.x, x.a2.x);
+        double rr = t > 0.0 ? t : 0.0;                           /* NaN: 0 */
+        rr = rr < x.r ? rr : x.r;
+        if (!(__builtin_isfinite(a1.x) && __builtin_isfinite(a1.y) && __builtin_isfinite(a2.x) && __builtin_isfinite(a2.y) &&
+              __builtin_isfinite(b1.x) && __builtin_isfinite(b1.y) && __builtin_isfinite(b2.x) && __builtin_isfinite(b2.y)))
+            rr = 0.0;
+        const uint32_t e = off + j;
+        r[e] = rr;
+        ab[4 * e] = a1;
+        ab[4 * e + 1] = a2;
+        ab[4 * e + 2] = b1;
+        ab[4 * e + 3] = b2;
+    }
+}
+
+/* deep_orbit_ship with BLA: u replaces the loop index, the probe is deep_orbit_bla's (no level's r exceeds the single step's
+ * 2^-53 |Z_m|, so the same pre-filter holds).  The BLA branch loads the entry's eight doubles and Z_m, Z_{m+1} at its new
+ * m; the plain branch is deep_orbit_ship's step with its Z_{m+2} prefetch. */
+__device__ __forceinline__ void deep_orbit_ship_bla(const DeepArgs& A, const ShipBlaTable& T, const double dcx,
+                                                    const double dcy, const double2 z1, bool live, int& esc, double& er2,
+                                                    uint32_t& nplain, uint32_t& nbla)
+{
+    const double2* __restrict__ orbit = A.orbit;
+    const double* __restrict__ tr = T.r;
+    const double2* __restrict__ tab = T.ab;
+    const int N = A.n_ref, max_iter = A.max_iter, K = T.levels;
+    const uint32_t n1 = (uint32_t)(N - 1);
+    const double B2 = A.B2;
+    double dzx = 0.0, dzy = 0.0;
+    double Zx = 0.0, Zy = 0.0;                                   /* Z_m */
+    double Znx = z1.x, Zny = z1.y;                               /* Z_{m+1} */
+    int m = 0, u = 0;
+    esc = max_iter;
+    er2 = 0.0;
+    nplain = 0u; nbla = 0u;
+    for (;;) {
+        if (__builtin_amdgcn_ballot_w64(live) == 0ull) break;
+        if (!live) continue;
+        const double2 Znn = orbit[m + 2 <= N ? m + 2 : N];      /* Z_{m+2}, for a plain step */
+        const double dz2 = dzx * dzx + dzy * dzy;
+        int k = 0;
+        uint32_t e = 0u;
+        if (m >= 1 && dz2 * 0x1p104 < Zx * Zx + Zy * Zy) {
+            const uint32_t mm = (uint32_t)(m - 1);
+            int kk = mm ? __builtin_ctz(mm) : K;
+            kk = kk < K ? kk : K;
+            const int kn = 31 - __builtin_clz((uint32_t)(N - m));
+            const int ki = 31 - __builtin_clz((uint32_t)(max_iter - u));
+            kk = kk < kn ? kk : kn;
+            kk = kk < ki ? kk : ki;
+            for (; kk >= 1; --kk) {
+                const uint32_t ek = bla_offset(n1, kk) + (mm >> kk);
+                const double r = tr[ek];
+                if (dz2 < r * r) { k = kk; e = ek; break; }
+            }
+        }
+        double nx, ny, Zmx, Zmy;
+        int step;
+        if (k > 0) {
+            const double2 a1 = tab[4 * e], a2 = tab[4 * e + 1], b1 = tab[4 * e + 2], b2 = tab[4 * e + 3];
+            nx = (a1.x * dzx + a1.y * dzy) + (b1.x * dcx + b1.y * dcy);
+            ny = (a2.x * dzx + a2.y * dzy) + (b2.x * dcx + b2.y * dcy);
+            step = 1 << k;
+            ++nbla;
+            m += step;
+            const double2 Zm = orbit[m];
+            Zmx = Zm.x; Zmy = Zm.y;
+        } else {
+            const double X2 = Zx + Zx, Y2 = Zy + Zy;
+            const double fx = ship_fold(Zx, X2, dzx), fy = ship_fold(Zy, Y2, dzy);
+            const double tx = fabs(X2) + fx, ty = fabs(Y2) + fy;     /* |X| + |X| = |X + X| */
+            nx = (tx * fx - ty * fy) + dcx;
+            ny = (tx * fy + ty * fx) + dcy;
             step = 1;
             ++nplain;
             m += 1;
@@ -723,28 +893,32 @@ __device__ __forceinline__ const DeepArgs& deep_args(const DeepXArgs& A) { retur
 __device__ __forceinline__ const DeepArgs& deep_args(const DeepBlaArgs& A) { return A.d; }
 __device__ __forceinline__ const DeepArgs& deep_args(const DeepXBlaArgs& A) { return A.x.d; }
 __device__ __forceinline__ const DeepArgs& deep_args(const DeepShipArgs& A) { return A.d; }
+__device__ __forceinline__ const DeepArgs& deep_args(const DeepShipBlaArgs& A) { return A.s.d; }
 __device__ __forceinline__ const DeepXArgs& deepx_args(const DeepXArgs& A) { return A; }
 __device__ __forceinline__ const DeepXArgs& deepx_args(const DeepXBlaArgs& A) { return A.x; }
+__device__ __forceinline__ const DeepShipArgs& ship_args(const DeepShipArgs& A) { return A; }
+__device__ __forceinline__ const DeepShipArgs& ship_args(const DeepShipBlaArgs& A) { return A.s; }
 
 /* deep_kernel<DeepArgs>: the plain step; deep_kernel<DeepBlaArgs>: with BLA (deep_orbit_bla, the step counts);
  * deep_kernel<DeepXArgs>: extended-exponent deltas (deep_orbit_x); deep_kernel<DeepXBlaArgs>: those with BLA
  * (deep_orbit_x_bla, the step counts); deep_kernel<DeepShipArgs>: the Burning Ship (deep_orbit_ship, its viewport map and
- * colour stage) */
+ * colour stage); deep_kernel<DeepShipBlaArgs>: the ship with BLA (deep_orbit_ship_bla, the step counts) */
 template <class ARGS>
 __global__ void __launch_bounds__(kBlockThreads)
 deep_kernel(const ARGS AA)
 {
     constexpr bool XBLA = std::is_same<ARGS, DeepXBlaArgs>::value;
-    constexpr bool BLA = std::is_same<ARGS, DeepBlaArgs>::value || XBLA;
+    constexpr bool SHIPBLA = std::is_same<ARGS, DeepShipBlaArgs>::value;
+    constexpr bool BLA = std::is_same<ARGS, DeepBlaArgs>::value || XBLA || SHIPBLA;
     constexpr bool X = std::is_same<ARGS, DeepXArgs>::value || XBLA;
-    constexpr bool SHIP = std::is_same<ARGS, DeepShipArgs>::value;
+    constexpr bool SHIP = std::is_same<ARGS, DeepShipArgs>::value || SHIPBLA;
     constexpr int FRACTAL = SHIP ? 2 : 0;                         /* the colour stage: shade() / colour_of() */
     const DeepArgs& A = deep_args(AA);
     __shared__ LdsBlock S;
     __shared__ double2 log2_lds[kLog2Entries];
     if (threadIdx.x == 0) S.pal = A.pal;
     if constexpr (SHIP) {
-        if (threadIdx.x == 0) S.log_bailout = AA.log_bailout;
+        if (threadIdx.x == 0) S.log_bailout = ship_args(AA).log_bailout;
     }
     reinterpret_cast<double*>(log2_lds)[threadIdx.x] = reinterpret_cast<const double*>(A.log2_tab)[threadIdx.x];
     __syncthreads();
@@ -790,7 +964,16 @@ deep_kernel(const ARGS AA)
                 }
                 const double sdx = (uvx - 0.5) * zoom * (resx / resy);
                 const double sdy = (uvy - 0.5) * zoom;
-                deep_orbit_ship(A, inside ? sdx : 0.0, inside ? sdy : 0.0, z1, inside, esc, r2);
+                if constexpr (SHIPBLA) {
+                    uint32_t np, nb;
+                    deep_orbit_ship_bla(A, AA.t, inside ? sdx : 0.0, inside ? sdy : 0.0, z1, inside, esc, r2, np, nb);
+                    if (inside) {
+                        n_plain += np; n_bla += nb;
+                        n_upd += (unsigned long long)(esc < A.max_iter ? esc + 1 : A.max_iter);
+                    }
+                } else {
+                    deep_orbit_ship(A, inside ? sdx : 0.0, inside ? sdy : 0.0, z1, inside, esc, r2);
+                }
             } else if constexpr (X) {
                 const DeepXArgs& XA = deepx_args(AA);
                 double cx = ((pxs - 0.5 * resx) / resy) * XA.zm, cy = ((pys - 0.5 * resy) / resy) * XA.zm;

@@ -143,6 +143,19 @@ struct fr_ctx {
     OrbitKey ship_key;          /* of ship_orbit_dev */
     int ship_wg_per_cu;         /* resident workgroups per CU of deep_kernel<DeepShipArgs> (0 = not asked yet) */
     uint64_t ship_gen;          /* bumped whenever ship_orbit_dev receives another orbit */
+    /* BLA for the ship (FR_FLAG_DEEP_SHIP_BLA): the table of the cached ship orbit and the step counts of the most recent
+     * such render -- the ship path's own, nothing of it is shared with the Mandelbrot tables above */
+    double* ship_bla_r;         /* r of every entry (ship_bla_cap) */
+    double2* ship_bla_ab;       /* the rows of A and of B of every entry (4 ship_bla_cap) */
+    size_t ship_bla_cap;        /* entries */
+    bool ship_bla_valid;        /* the key below describes the table */
+    uint64_t ship_bla_key_gen, ship_bla_key_dcmax;   /* ship_gen of its orbit, bits of dcmax */
+    unsigned long long* ship_bla_steps_dev;    /* the kernel's three counters */
+    unsigned long long* ship_bla_steps_host;   /* pinned: their copy behind the most recent render with the flag */
+    bool have_ship_bla_steps;
+    hipEvent_t ev_ship_bla;     /* recorded behind every render with the flag (not while capturing): rebuilds wait for it */
+    bool ev_ship_bla_valid;
+    int ship_bla_wg_per_cu;     /* resident workgroups per CU of deep_kernel<DeepShipBlaArgs> (0 = not asked yet) */
 };
 
 #define FR_HIP_TRY(expr)                                                               \
@@ -192,6 +205,7 @@ extern "C" int fr_ctx_create(int device_ordinal, fr_ctx** out)
         (e2 = hipEventCreateWithFlags(&c->ev_order, hipEventDisableTiming)) != hipSuccess ||
         (e2 = hipEventCreateWithFlags(&c->ev_bla, hipEventDisableTiming)) != hipSuccess ||
         (e2 = hipEventCreateWithFlags(&c->ev_xbla, hipEventDisableTiming)) != hipSuccess ||
+        (e2 = hipEventCreateWithFlags(&c->ev_ship_bla, hipEventDisableTiming)) != hipSuccess ||
         (e2 = hipMalloc((void**)&c->d_ctrl, (kCtrlWords + (size_t)(kFeedbackShards + 2) * kShardStrideWords) * sizeof(uint32_t))) != hipSuccess ||
         (e2 = hipMemset(c->d_ctrl, 0, (kCtrlWords + (size_t)(kFeedbackShards + 2) * kShardStrideWords) * sizeof(uint32_t))) != hipSuccess ||
         (e2 = hipHostMalloc((void**)&c->overflow_host, 64, hipHostMallocMapped)) != hipSuccess ||
@@ -249,6 +263,11 @@ extern "C" void fr_ctx_destroy(fr_ctx* c)
     if (c->xbla_steps_dev) (void)hipFree(c->xbla_steps_dev);
     if (c->xbla_steps_host) (void)hipHostFree(c->xbla_steps_host);
     if (c->ev_xbla) (void)hipEventDestroy(c->ev_xbla);
+    if (c->ship_bla_r) (void)hipFree(c->ship_bla_r);
+    if (c->ship_bla_ab) (void)hipFree(c->ship_bla_ab);
+    if (c->ship_bla_steps_dev) (void)hipFree(c->ship_bla_steps_dev);
+    if (c->ship_bla_steps_host) (void)hipHostFree(c->ship_bla_steps_host);
+    if (c->ev_ship_bla) (void)hipEventDestroy(c->ev_ship_bla);
     if (c->ev_begin) (void)hipEventDestroy(c->ev_begin);
     if (c->ev_end) (void)hipEventDestroy(c->ev_end);
     if (c->ev_order) (void)hipEventDestroy(c->ev_order);
@@ -770,8 +789,8 @@ static int orbit_key_store(OrbitKey& k, const char* x, const char* y, int32_t bi
     return FR_OK;
 }
 
-/* One cache slot of plain-double orbits (fr_render_deep's, fr_render_deep_ship's): the buffers, what they hold, and the host
- * function that computes the orbit */
+/* One cache slot of plain-double orbits (fr_render_deep's, fr_render_deep_ship's): the buffers, what they hold, the host
+ * function that computes the orbit, and the event behind the slot's most recent BLA render */
 struct OrbitSlot {
     double*& host;
     double2*& dev;
@@ -780,6 +799,8 @@ struct OrbitSlot {
     OrbitKey& key;
     uint64_t& gen;
     int (*compute)(const fr_deep_view*, double, int32_t, float, double*, int32_t*);
+    hipEvent_t ev_bla;
+    const bool& ev_bla_valid;
 };
 
 static int orbit_slot_fill(fr_ctx* c, const OrbitSlot& o, const fr_params* p, const fr_deep_view* v, hipStream_t stream)
@@ -792,7 +813,7 @@ static int orbit_slot_fill(fr_ctx* c, const OrbitSlot& o, const fr_params* p, co
     FR_HIP_TRY(hipStreamSynchronize(stream));
     FR_HIP_TRY(hipStreamSynchronize(c->stream));
     if (c->have_render && c->last_stream != stream) FR_HIP_TRY(hipStreamSynchronize(c->last_stream));
-    if (c->ev_bla_valid) FR_HIP_TRY(hipEventSynchronize(c->ev_bla));      /* the last BLA render, wherever it went */
+    if (o.ev_bla_valid) FR_HIP_TRY(hipEventSynchronize(o.ev_bla));        /* the slot's last BLA render, wherever it went */
     o.key.valid = false;
     ++o.gen;
     const size_t need = (size_t)max_iter + 1;
@@ -817,14 +838,14 @@ static int orbit_slot_fill(fr_ctx* c, const OrbitSlot& o, const fr_params* p, co
 static int deep_orbit_for(fr_ctx* c, const fr_params* p, const fr_deep_view* v, hipStream_t stream)
 {
     const OrbitSlot o = {c->deep_orbit_host, c->deep_orbit_dev, c->deep_orbit_cap, c->deep_len, c->deep_key, c->deep_gen,
-                         fr_deep_reference_orbit};
+                         fr_deep_reference_orbit, c->ev_bla, c->ev_bla_valid};
     return orbit_slot_fill(c, o, p, v, stream);
 }
 
 static int ship_orbit_for(fr_ctx* c, const fr_params* p, const fr_deep_view* v, hipStream_t stream)
 {
     const OrbitSlot o = {c->ship_orbit_host, c->ship_orbit_dev, c->ship_orbit_cap, c->ship_len, c->ship_key, c->ship_gen,
-                         fr_deep_ship_reference_orbit};
+                         fr_deep_ship_reference_orbit, c->ev_ship_bla, c->ev_ship_bla_valid};
     return orbit_slot_fill(c, o, p, v, stream);
 }
 
@@ -947,7 +968,90 @@ static int enqueue_deep(fr_ctx* c, const fr_params* p, const fr_deep_view* v, ui
 }
 
 /* ---- deep Burning Ship views (fr_render_deep_ship) --------------------------------------------------------------------
- * enqueue_deep on the ship's own orbit slot and deep_kernel<DeepShipArgs> */
+ * FR_FLAG_DEEP_SHIP_BLA: the table of the cached ship orbit for this frame's dcmax (the whole frame's W, H and zoom; the
+ * ship's own bound, see the header), built on `stream` unless the context holds it -- deep_bla_table_for's rules on the ship
+ * path's own buffers and event. */
+static int ship_bla_table_for(fr_ctx* c, const fr_params* p, uint32_t W, uint32_t H, hipStream_t stream, int* levels)
+{
+    const int32_t N = c->ship_len - 1;
+    const int K = N > 1 ? 31 - __builtin_clz((uint32_t)(N - 1)) : 0;   /* floor(log2(N - 1)) */
+    *levels = K;
+    if (K == 0) return FR_OK;
+    const double w = (double)W, h = (double)H;
+    const double a = w / h;
+    const double hx = 0.5 + 0.5 / (w * w);
+    const double hy = 0.5 + 0.5 / (w * h);
+    const double ex = hx * a;
+    const double dcmax = (1.0000001 * p->zoom) * sqrt(ex * ex + hy * hy);
+    uint64_t dbits;
+    memcpy(&dbits, &dcmax, sizeof(dbits));
+    if (c->ship_bla_valid && c->ship_bla_key_gen == c->ship_gen && c->ship_bla_key_dcmax == dbits) return FR_OK;
+    c->ship_bla_valid = false;
+    const uint32_t n1 = (uint32_t)(N - 1);
+    const size_t need = (size_t)(n1 - (uint32_t)__builtin_popcount(n1));     /* sum over k >= 1 of (N - 1) >> k */
+    if (need > c->ship_bla_cap) {
+        FR_HIP_TRY(hipStreamSynchronize(stream));
+        FR_HIP_TRY(hipStreamSynchronize(c->stream));
+        if (c->ev_ship_bla_valid) FR_HIP_TRY(hipEventSynchronize(c->ev_ship_bla));
+        if (c->ship_bla_r) { (void)hipFree(c->ship_bla_r); c->ship_bla_r = nullptr; }
+        if (c->ship_bla_ab) { (void)hipFree(c->ship_bla_ab); c->ship_bla_ab = nullptr; }
+        c->ship_bla_cap = 0;
+        FR_HIP_TRY(hipMalloc((void**)&c->ship_bla_r, need * sizeof(double)));
+        FR_HIP_TRY(hipMalloc((void**)&c->ship_bla_ab, need * 4 * sizeof(double2)));
+        c->ship_bla_cap = need;
+    } else if (c->ev_ship_bla_valid) {
+        FR_HIP_TRY(hipStreamWaitEvent(stream, c->ev_ship_bla, 0));
+    }
+    for (int k = 1; k <= K; ++k) {
+        const uint32_t cnt = n1 >> k;
+        uint32_t grid = (cnt + kBlockThreads - 1) / kBlockThreads;
+        const uint32_t cap = (uint32_t)c->compute_units * 8u;
+        if (grid > cap) grid = cap;
+        hipLaunchKernelGGL(deep_ship_bla_level_kernel, dim3(grid), dim3(kBlockThreads), 0, stream, c->ship_orbit_dev, N, k,
+                           dcmax, c->ship_bla_r, c->ship_bla_ab);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return fr_set_error(FR_ERR_HIP, "ship BLA table launch failed: %s", hipGetErrorString(e));
+    }
+    c->ship_bla_key_gen = c->ship_gen;
+    c->ship_bla_key_dcmax = dbits;
+    c->ship_bla_valid = true;
+    return FR_OK;
+}
+
+/* enqueue_deep_bla for the ship: the table, then deep_kernel<DeepShipBlaArgs> on deep_kernel<DeepShipArgs>'s queue plan (its
+ * own occupancy), its counters cleared in front of it and copied to pinned memory behind it */
+static int enqueue_deep_ship_bla(fr_ctx* c, const fr_params* p, const DeepShipArgs& s, hipStream_t stream)
+{
+    DeepShipBlaArgs a;
+    memset(&a, 0, sizeof(a));
+    a.s = s;
+    int levels = 0;
+    const int ts = ship_bla_table_for(c, p, (uint32_t)s.d.g.W, (uint32_t)s.d.g.H, stream, &levels);
+    if (ts != FR_OK) return ts;
+    a.t.r = c->ship_bla_r; a.t.ab = c->ship_bla_ab; a.t.levels = levels;
+    if (!c->ship_bla_steps_dev) {
+        FR_HIP_TRY(hipMalloc((void**)&c->ship_bla_steps_dev, 3 * sizeof(unsigned long long)));
+        FR_HIP_TRY(hipHostMalloc((void**)&c->ship_bla_steps_host, 3 * sizeof(unsigned long long)));
+    }
+    a.t.steps = c->ship_bla_steps_dev;
+    FR_HIP_TRY(hipMemsetAsync(c->ship_bla_steps_dev, 0, 3 * sizeof(unsigned long long), stream));
+    const int st = launch_one_pass(c, stream, "deep_kernel<DeepShipBlaArgs>", deep_kernel<DeepShipBlaArgs>, a, a.s.d.g, a.s.d.q,
+                                   c->ship_bla_wg_per_cu, false);
+    if (st != FR_OK) return st;
+    FR_HIP_TRY(hipMemcpyAsync(c->ship_bla_steps_host, c->ship_bla_steps_dev, 3 * sizeof(unsigned long long),
+                              hipMemcpyDeviceToHost, stream));
+    c->have_ship_bla_steps = true;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusActive; }
+    c->ev_ship_bla_valid = false;
+    if (cap == hipStreamCaptureStatusNone) {
+        FR_HIP_TRY(hipEventRecord(c->ev_ship_bla, stream));
+        c->ev_ship_bla_valid = true;
+    }
+    return FR_OK;
+}
+
+/* enqueue_deep on the ship's own orbit slot and deep_kernel<DeepShipArgs> */
 static int enqueue_deep_ship(fr_ctx* c, const fr_params* p, const fr_deep_view* v, uint32_t W, uint32_t H,
                              const fr_shard* shard, float* rgba, void* nu, int32_t* iter, hipStream_t stream, bool out_frame)
 {
@@ -965,6 +1069,7 @@ static int enqueue_deep_ship(fr_ctx* c, const fr_params* p, const fr_deep_view* 
     a.zoom = p->zoom;
     fill_deep_args(a, c, p, tile_geom(W, H, rows_local, &norm, out_frame), rgba, nu, iter);
     s.log_bailout = log((double)p->bailout);     /* as fill_params */
+    if (p->flags & FR_FLAG_DEEP_SHIP_BLA) return enqueue_deep_ship_bla(c, p, s, stream);
     return launch_one_pass(c, stream, "deep_kernel<DeepShipArgs>", deep_kernel<DeepShipArgs>, s, a.g, a.q, c->ship_wg_per_cu,
                            false);
 }
@@ -1616,6 +1721,30 @@ extern "C" int64_t fr_deep_bla_table(fr_ctx* c, double* r, double* ab, int64_t n
     FR_HIP_TRY(hipDeviceSynchronize());
     if (n > 0 && r) FR_HIP_TRY(hipMemcpy(r, c->bla_r, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
     if (n > 0 && ab) FR_HIP_TRY(hipMemcpy(ab, c->bla_ab, (size_t)n * 2 * sizeof(double2), hipMemcpyDeviceToHost));
+    return have;
+}
+
+extern "C" int fr_ctx_last_deep_ship_steps(fr_ctx* c, uint64_t out[3])
+{
+    if (!c || !out) return fr_set_error(FR_ERR_INVALID_ARG, "ctx/out is NULL");
+    if (!c->have_ship_bla_steps)
+        return fr_set_error(FR_ERR_UNSUPPORTED, "no fr_render_deep_ship call with FR_FLAG_DEEP_SHIP_BLA on this context yet");
+    for (int i = 0; i < 3; ++i) out[i] = (uint64_t)c->ship_bla_steps_host[i];
+    return FR_OK;
+}
+
+extern "C" int64_t fr_deep_ship_bla_table(fr_ctx* c, double* r, double* ab, int64_t n)
+{
+    if (!c) return fr_set_error(FR_ERR_INVALID_ARG, "ctx is NULL");
+    if (!c->ship_bla_valid) return 0;
+    const int32_t N = c->ship_len - 1;
+    const uint32_t n1 = (uint32_t)(N - 1);
+    const int64_t have = (int64_t)(n1 - (uint32_t)__builtin_popcount(n1));
+    if (n > have) n = have;
+    FR_HIP_TRY(hipSetDevice(c->device));
+    FR_HIP_TRY(hipDeviceSynchronize());
+    if (n > 0 && r) FR_HIP_TRY(hipMemcpy(r, c->ship_bla_r, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+    if (n > 0 && ab) FR_HIP_TRY(hipMemcpy(ab, c->ship_bla_ab, (size_t)n * 4 * sizeof(double2), hipMemcpyDeviceToHost));
     return have;
 }
 

@@ -44,6 +44,9 @@ int64_t fr_deep_bla_table(fr_ctx* ctx, double* r, double* ab, int64_t n);
  * mantissa as a float, the int32 exponent), ab 4 n doubles (the mantissas of A, B), ab_exp 2 n int32 (their exponents);
  * NULL skips a part.  Returns the number of entries the table has (0: none). */
 int64_t fr_deepx_bla_table(fr_ctx* ctx, void* r, double* ab, int32_t* ab_exp, int64_t n);
+/* tests: the ship's BLA table of the context (FR_FLAG_DEEP_SHIP_BLA), as fr_deep_bla_table: r[0 .. n) and ab[0 .. 8n)
+ * (a11, a12, a21, a22, b11, b12, b21, b22 per entry), level after level.  Returns the entries it holds, 0 for none. */
+int64_t fr_deep_ship_bla_table(fr_ctx* ctx, double* r, double* ab, int64_t n);
 
 /* the context's own stream (hipStream_t) and device ordinal: fr_node.cpp orders RCCL transfers behind the renders */
 void* fr_ctx_stream_handle(fr_ctx* ctx);

@@ -138,6 +138,13 @@ class Renderer:
         _capi.check(self._lib.fr_ctx_last_deepx_steps(self._ctx, out))
         return DeepSteps(int(out[0]), int(out[1]), int(out[2]))
 
+    def last_deep_ship_steps(self) -> DeepSteps:
+        """fr_ctx_last_deep_ship_steps: (plain steps, BLA steps, updates skipped) of the most recent
+        render_deep_ship(bla=True) on this context, as last_deep_steps()."""
+        out = (C.c_uint64 * 3)()
+        _capi.check(self._lib.fr_ctx_last_deep_ship_steps(self._ctx, out))
+        return DeepSteps(int(out[0]), int(out[1]), int(out[2]))
+
     def last_kernel_ms(self) -> float:
         return float(self._lib.fr_ctx_last_kernel_ms(self._ctx))
 
@@ -264,15 +271,19 @@ class Renderer:
 
     def render_deep_ship(self, state: FractalState, width: int, height: int, view: Optional[DeepView] = None, *,
                          post_chain: bool = False, rgba=None, nu=None, iter=None, shard: Optional[Shard] = None,
-                         stream: Optional[int] = None, sync: bool = True) -> None:
+                         stream: Optional[int] = None, sync: bool = True, bla: bool = False) -> None:
         """fr_render_deep_ship / fr_render_deep_ship_async: a Burning Ship view deeper than double precision, by perturbation
         around one reference orbit of the ship's recurrence computed on the host.  `view` carries the centre as decimal
         strings (a view with a zoom string is a ValueError: extended exponents are Mandelbrot's); the zoom, in
         [1e-290, 1e3], and every other field come from `state` (its double centre is not read).  Always fp64: nu is float64.
-        Planes, shard, stream and sync as for render_deep(); the context keeps the ship's orbit next to render_deep's."""
+        Planes, shard, stream and sync as for render_deep(); the context keeps the ship's orbit next to render_deep's.
+        bla=True sets FR_FLAG_DEEP_SHIP_BLA: iteration skipping by bilinear approximation with the ship's real 2x2 maps (the
+        header's rules; last_deep_ship_steps() reports what it skipped)."""
         if view is not None and view.zoom is not None:
             raise ValueError("render_deep_ship takes the zoom from the state: extended views (a zoom string) are Mandelbrot only")
         p = state.to_params(FractalType.BurningShip, Precision.F64, post_chain)
+        if bla:
+            p.flags |= _capi.FR_FLAG_DEEP_SHIP_BLA
         v = (view or DeepView()).to_c()
         rows = shard.rows(height) if shard else height
         self._render_call(self._lib.fr_render_deep_ship, self._lib.fr_render_deep_ship_async, (C.byref(p), C.byref(v)), width,

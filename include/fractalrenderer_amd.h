@@ -73,6 +73,8 @@ typedef enum fr_precision {
                                       every other entry point ignores it */
 #define FR_FLAG_DEEPX_BLA    0x4u  /* fr_render_deepx(_async) only: the same for extended views (see there); every other
                                       entry point ignores it, fr_render_deep included */
+#define FR_FLAG_DEEP_SHIP_BLA 0x8u /* fr_render_deep_ship and its _async form only: the same for deep Burning Ship views
+                                      (see there); every other entry point ignores it */
 
 /*
  * fr_params -- the hot-path fields of FractalState (src/fractal_state.h:16-91),
@@ -515,7 +517,8 @@ int fr_ctx_last_deep_steps(fr_ctx* ctx, uint64_t out[3]);
  *
  * p->fractal_type must be FR_FRACTAL_BURNING_SHIP and p->precision FR_PRECISION_F64.  FR_ERR_UNSUPPORTED also where the ship
  * needs the whole orbit -- orbit_trap_enabled, stripe_enabled with interior_style 2, interior_style 3 -- and for
- * FR_FLAG_DEEP_BLA or FR_FLAG_DEEPX_BLA.  The other fields follow fr_params_validate's rules; bailout must be <= 2^16.
+ * FR_FLAG_DEEP_BLA or FR_FLAG_DEEPX_BLA (the ship's own flag is FR_FLAG_DEEP_SHIP_BLA, below).  The other fields follow
+ * fr_params_validate's rules; bailout must be <= 2^16.
  * fr_render_deep keeps rejecting FR_FRACTAL_BURNING_SHIP.
  *
  * Reference orbit: fr_render_deep's fixed point and escape test, with
@@ -545,9 +548,9 @@ int fr_ctx_last_deep_steps(fr_ctx* ctx, uint64_t out[3]);
  * The context keeps the most recent ship orbit on the device in a slot of its own, keyed as fr_render_deep's: a ship render
  * never evicts the Mandelbrot orbit, nor the reverse.
  *
- * Out of scope: BLA for the ship (its linear map is a real 2x2 matrix with fold conditions), extended exponents below
- * 1e-290, fr_node and .franim. */
+ * Out of scope: extended exponents below 1e-290, fr_node and .franim. */
 #define FR_HAS_DEEP_SHIP 1
+#define FR_HAS_DEEP_SHIP_BLA 1    /* FR_FLAG_DEEP_SHIP_BLA and fr_ctx_last_deep_ship_steps (below fr_render_deep_ship_async) */
 
 /* fr_deep_reference_orbit for the ship's recurrence: same arguments, validation and cost */
 int fr_deep_ship_reference_orbit(const fr_deep_view* v, double zoom, int32_t max_iter, float bailout, double* out_xy,
@@ -560,6 +563,61 @@ int fr_render_deep_ship(fr_ctx* ctx, const fr_params* p, const fr_deep_view* vie
 /* fr_render_deep_async's contract: a render of a new view computes its orbit on the host first and is never launch-only */
 int fr_render_deep_ship_async(fr_ctx* ctx, const fr_params* p, const fr_deep_view* view, uint32_t width, uint32_t height,
                               const fr_shard* shard, const fr_output* out, void* hip_stream);
+
+/* Bilinear approximation for the ship, opt-in per call with FR_FLAG_DEEP_SHIP_BLA in p->flags.  Only fr_render_deep_ship and
+ * fr_render_deep_ship_async read the flag; without it every byte they write is as above.  Take an orbit point Z_m = (X, Y)
+ * and a delta dz = (a, b) with |a| < |X| and |b| < |Y|: no fold flips a sign, fold(X, a) = sgn(X) a, fold(Y, b) = sgn(Y) b,
+ * and the ship's step less its square term is the REAL linear map dz' = A dz + dc with
+ *   A = [[2X, -2Y], [2|Y| sgn X, 2|X| sgn Y]].
+ * The columns of A are orthogonal and both have length 2 |Z_m|: A is 2 |Z_m| times a rotation or reflection, and so is every
+ * product of such matrices.  The validity argument of FR_FLAG_DEEP_BLA therefore carries over with |A| read as a column
+ * length; the only new conditions are the two fold conditions, which cap the single step's radius.
+ *
+ * Notation: matrices are (m11, m12, m21, m22), row by row; sgn(v) = (v >= 0 ? 1 : -1); every operation is one fp64 rounding
+ * (no contraction); sqrt is correctly rounded (as for FR_FLAG_DEEP_BLA).
+ *   - Constants: eps = 2^-53.  With a = (double)W / (double)H of the WHOLE frame (never of a shard's rows):
+ *       hx = 0.5 + 0.5 / (W*W);  hy = 0.5 + 0.5 / (W*H);  ex = hx * a;  dcmax = (1.0000001 * zoom) * sqrt(ex*ex + hy*hy)
+ *     (W*W and W*H as products of doubles).  Not FR_FLAG_DEEP_BLA's dcmax: with aa > 1 the ship shader's sub-sample offsets
+ *     reach (aa-1)/(2 aa W^2) outside [0, 1) in uvx and (aa-1)/(2 aa W H) in uvy, more than the 1e-7 margin on small frames.
+ *   - Single step at m >= 1 (never stored), Z_m = (X, Y), sx = sgn(X), sy = sgn(Y):
+ *       A = (X + X, -(Y + Y), (|Y| + |Y|) * sx, (|X| + |X|) * sy),  B = (1, 0, 0, 1),
+ *       r = eps * sqrt(X*X + Y*Y);  r = (r < |X| ? r : |X|);  r = (r < |Y| ? r : |Y|)
+ *     The last two are the fold conditions.  An orbit on the real axis (centre_y "0") has Y = 0 throughout: r = 0, and it
+ *     takes no BLA step.
+ *   - Table: the levels, the entry coverage and the entry count (N - 1) - popcount(N - 1) of FR_FLAG_DEEP_BLA.  Entry j of
+ *     level k merges x (level k-1 at m) and y (level k-1 at m + 2^(k-1)):
+ *       A = A_y A_x, the real 2x2 product, each element p*q + s*t (a11 = y.a11*x.a11 + y.a12*x.a21, ...);
+ *       B = A_y B_x + B_y, each element (p*q + s*t) + y.b (b11 = (y.a11*x.b11 + y.a12*x.b21) + y.b11, ...);
+ *       |A_x| = sqrt(x.a11*x.a11 + x.a21*x.a21), the first column: A_x is a scaled orthogonal matrix, so its operator norm;
+ *       |B_x| = sqrt((x.b11*x.b11 + x.b12*x.b12) + (x.b21*x.b21 + x.b22*x.b22)), the Frobenius norm;
+ *       t = (r_y - |B_x| * dcmax) / |A_x|,  r = (t > 0 ? t : 0) (NaN: 0),  r = (r < r_x ? r : r_x),
+ *       and r = 0 if any of the eight elements is not finite.
+ *   - Stepping: FR_FLAG_DEEP_BLA's, u replacing the loop index.  At m >= 1 take the largest k >= 1 with
+ *     (m-1) mod 2^k == 0, m + 2^k <= N, u + 2^k <= max_iterations and dz.x*dz.x + dz.y*dz.y < r*r; then
+ *       dz' = ((a11 dz.x + a12 dz.y) + (b11 dc.x + b12 dc.y), (a21 dz.x + a22 dz.y) + (b21 dc.x + b22 dc.y)),
+ *       m += 2^k, u += 2^k, z = Z_m + dz', r2 = |z|^2;
+ *     r2 > bailout^2: escaped at u - 1; else the rebase rule of the plain step.  If no k qualifies, or m == 0, the ship's
+ *     plain step above, operation for operation: it escapes at u and then u += 1.  The planes follow from (escape index,
+ *     r2) exactly as without the flag.  No level's r exceeds eps |Z_m|.
+ * Escapes between the first and the last update of a BLA step are not looked for.
+ *
+ * What it skips (the numpy restatement, 256 x 192, aa 1): on a view at 1e-30 whose reference escapes (N = 197) 42.8 % of the
+ * updates, 1.70x fewer loop trips, iter equal to the unflagged path's on every pixel; on a view at 1e-100 (N = 590) 75.3 %,
+ * 3.94x fewer trips, iter different on 23 of 49152 pixels.  Shallow views (|dc| far above every radius) take no BLA step.
+ * Measured on one MI355X at 4096^2 (profiles/deep_ship_bla_time.txt, flagged and unflagged interleaved in one session):
+ * 4.67 ms against 5.48 ms on the first view (1.17x) and 6.87 ms against 17.24 ms on the second (2.51x); a flagged loop trip
+ * costs about 1.5 plain ones (the level probe, the 64-byte gather, 4 waves per SIMD for 5).
+ *
+ * Cost: 72 bytes per entry (r 8, A and B 64), on the device, per context, in buffers of the ship path's own, grown like the
+ * orbit buffer and keyed by the ship's orbit and the bits of dcmax: a zoom change at a fixed centre rebuilds the table (K
+ * small launches on the render's stream, no host work), a new view computes its orbit first.  A rebuild, and the upload of
+ * a new ship orbit, are ordered behind the context's previous render with the flag, whatever stream it went to.  The
+ * Mandelbrot tables, their counts and fr_ctx_last_deep_steps are untouched by ship renders, and the reverse. */
+
+/* fr_ctx_last_deep_steps' contract for the context's most recent fr_render_deep_ship / fr_render_deep_ship_async call made with
+ * FR_FLAG_DEEP_SHIP_BLA: out[0] plain steps, out[1] BLA steps, out[2] updates skipped.  FR_ERR_UNSUPPORTED if there is no such
+ * call. */
+int fr_ctx_last_deep_ship_steps(fr_ctx* ctx, uint64_t out[3]);
 
 /* ---- deep views below 1e-290: extended-exponent deltas ----------------------------------------------------------------
  * fr_render_deep stops where a double can no longer hold the zoom, a sample's dc and dz, or an orbit point that passes

@@ -12,7 +12,8 @@ from .state import (FractalState, FractalType, Precision, Preset, MANDELBROT_PRE
                     deep_reference_orbit, deep_ship_reference_orbit, deepx_zoom, deepx_frac_bits, deepx_reference_orbit)
 from .renderer import (Renderer, DeepSteps, Node, Shard, write_png, write_raw_rgb24, frame_path, export8_thresholds, rccl_selftest,
                        mapped_runtimes)
-from .animation import (AnimationSystem, AnimationRenderer, InterpolationType, Keyframe, DeepZoomPath, ZoomKeyframe)
+from .animation import (AnimationSystem, AnimationRenderer, InterpolationType, Keyframe, DeepZoomPath, ZoomKeyframe,
+                        DeepZoomSequence, DeepSequenceFrame)
 
 lib()  # no silent fallback: a missing/incomplete library is an import error
 
@@ -23,4 +24,5 @@ __all__ = [
     "deep_frac_bits", "deep_reference_orbit", "deep_ship_reference_orbit", "deepx_zoom", "deepx_frac_bits", "deepx_reference_orbit", "FR_FLAG_DEEP_BLA", "FR_FLAG_DEEPX_BLA", "FR_FLAG_DEEP_SHIP_BLA", "DeepSteps", "Renderer", "Node", "Shard",
     "write_png", "write_raw_rgb24", "frame_path", "export8_thresholds", "rccl_selftest", "mapped_runtimes",
     "AnimationSystem", "AnimationRenderer", "InterpolationType", "Keyframe", "DeepZoomPath", "ZoomKeyframe",
+    "DeepZoomSequence", "DeepSequenceFrame",
 ]

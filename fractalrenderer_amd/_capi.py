@@ -76,6 +76,16 @@ class fr_deepx_view(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class fr_deep_sequence_desc(C.Structure):
+    _fields_ = [("center_x", C.c_char_p), ("center_y", C.c_char_p), ("zoom_first", C.c_char_p), ("zoom_last", C.c_char_p),
+                ("frames", C.c_int32), ("frac_bits", C.c_int32), ("mode", C.c_int32), ("reserved", C.c_int32)]
+
+
+class fr_deep_sequence_frame(C.Structure):
+    _fields_ = [("zoom_mant", C.c_double), ("zoom_exp2", C.c_int32), ("frac_bits", C.c_int32), ("keyframe", C.c_int32),
+                ("resampled", C.c_int32), ("u", C.c_double)]
+
+
 class fr_output(C.Structure):
     _fields_ = [("rgba", C.c_void_p), ("nu", C.c_void_p), ("iter", C.c_void_p), ("memory", C.c_int32), ("layout", C.c_int32)]
 
@@ -153,6 +163,13 @@ SIGNATURES = {
                                   _P(fr_output)]),
     "fr_render_deepx_async": (C.c_int, [C.c_void_p, _P(fr_params), _P(fr_deepx_view), C.c_uint32, C.c_uint32, _P(fr_shard),
                                         _P(fr_output), C.c_void_p]),
+    "fr_deep_sequence_plan": (C.c_int, [_P(fr_deep_sequence_desc), C.c_int32, _P(fr_deep_sequence_frame)]),
+    "fr_deep_sequence_create": (C.c_int, [C.c_void_p, _P(fr_params), _P(fr_deep_sequence_desc), C.c_uint32, C.c_uint32,
+                                          _P(C.c_void_p)]),
+    "fr_deep_sequence_destroy": (None, [C.c_void_p]),
+    "fr_deep_sequence_render": (C.c_int, [C.c_void_p, C.c_int32, _P(fr_output)]),
+    "fr_deep_sequence_render_png": (C.c_int, [C.c_void_p, C.c_int32, C.c_char_p]),
+    "fr_deep_sequence_stats": (C.c_int, [C.c_void_p, _P(C.c_uint64)]),
     "fr_ctx_create": (C.c_int, [C.c_int, _P(C.c_void_p)]),
     "fr_ctx_destroy": (None, [C.c_void_p]),
     "fr_shard_rows": (C.c_uint32, [_P(fr_shard), C.c_uint32]),
@@ -236,6 +253,7 @@ INTERNAL_SIGNATURES = {
     "fr_deep_ship_bla_table": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),   # fr_internal.h: tests
     "fr_deepx_validate": (C.c_int, [_P(fr_params), _P(fr_deepx_view), C.c_uint32, C.c_uint32]),        # fr_internal.h: tests
     "fr_deep_ship_validate": (C.c_int, [_P(fr_params), _P(fr_deep_view), C.c_uint32, C.c_uint32]),     # fr_internal.h: tests
+    "fr_deepseq_resolve": (C.c_int, [_P(fr_params), _P(fr_deep_sequence_desc), C.c_uint32, C.c_uint32, C.c_void_p]),   # fr_internal.h: tests
 }
 PUBLIC_OPTIONS = ("periodicity", "staging", "shards", "tile_kernel", "timing", "diag_buffer", "diag_stride")
 TUNING_NAMES = ("workgroups_per_cu", "run_max", "run_min", "shift_bias", "stage_first", "pool_refill_at", "stream_run_max",

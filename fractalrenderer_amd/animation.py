@@ -12,10 +12,10 @@ import ctypes as C
 import enum
 import os
 from dataclasses import dataclass
-from typing import Callable, List, Optional
+from typing import Callable, List, NamedTuple, Optional
 
 from . import _capi
-from .renderer import frame_path
+from .renderer import Renderer, frame_path
 from .state import FractalState, FractalType, Precision
 
 
@@ -224,3 +224,87 @@ class DeepZoomPath:
         self.state.center_x, self.state.center_y, self.state.zoom = p.center_x, p.center_y, p.zoom
         self.zoom_animating, self.zoom_progress = bool(anim.value), float(prog.value)
         return bool(dirty.value)
+
+
+class DeepSequenceFrame(NamedTuple):
+    """fr_deep_sequence_frame: what one frame of a DeepZoomSequence is"""
+    zoom_mant: float        # the frame's view height is zoom_mant 2^zoom_exp2, zoom_mant in [1, 2)
+    zoom_exp2: int
+    frac_bits: int          # the sequence's F
+    keyframe: int           # k = floor(-log2(zoom / zoom_first)); may be negative
+    resampled: bool         # keyframes=True and the frame is not a keyframe itself
+    u: float                # 1.0 on a keyframe, else in (0.5, 1): the frame's height over keyframe k's
+
+
+class DeepZoomSequence:
+    """fr_deep_sequence: a zoom into one deep centre, frame after frame, around one reference orbit.  The zoom runs from
+    zoom_first to zoom_last (decimal strings, fr_deepx_view's range) in equal steps of log(zoom) over `frames` frames.
+    keyframes=False renders every frame exactly (fr_render_deepx's kernels); keyframes=True renders one keyframe per octave
+    and resamples the frames in between from their two neighbouring keyframes on the GPU (rgba only).  xbla sets
+    FR_FLAG_DEEPX_BLA for every exact render; post_chain as for Renderer.render_deep.  The renderer must outlive the
+    sequence; the rules are in include/fractalrenderer_amd.h."""
+
+    def __init__(self, renderer: Renderer, state: FractalState, cx, cy, zoom_first, zoom_last, frames: int, width: int,
+                 height: int, *, keyframes: bool = False, frac_bits: int = 0, xbla: bool = False, post_chain: bool = False):
+        self._lib = _capi.lib()
+        self._h = None
+        self.renderer, self.frames, self.width, self.height = renderer, int(frames), int(width), int(height)
+        self._desc = _capi.fr_deep_sequence_desc(str(cx).encode("ascii"), str(cy).encode("ascii"),
+                                                 str(zoom_first).encode("ascii"), str(zoom_last).encode("ascii"),
+                                                 int(frames), int(frac_bits), 1 if keyframes else 0, 0)
+        p = state.to_params(FractalType.Mandelbrot, Precision.F64, post_chain)
+        if xbla:
+            p.flags |= _capi.FR_FLAG_DEEPX_BLA
+        h = C.c_void_p()
+        _capi.check(self._lib.fr_deep_sequence_create(renderer._ctx, C.byref(p), C.byref(self._desc), self.width, self.height,
+                                                      C.byref(h)))
+        self._h = h
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            self._lib.fr_deep_sequence_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def plan(self, frame: int) -> DeepSequenceFrame:
+        """fr_deep_sequence_plan: host arithmetic only"""
+        f = _capi.fr_deep_sequence_frame()
+        _capi.check(self._lib.fr_deep_sequence_plan(C.byref(self._desc), int(frame), C.byref(f)))
+        return DeepSequenceFrame(f.zoom_mant, f.zoom_exp2, f.frac_bits, f.keyframe, bool(f.resampled), f.u)
+
+    def render(self, frame: int, *, rgba=None, nu=None, iter=None) -> None:
+        """fr_deep_sequence_render: the frame into the given planes, Renderer.render_deep's conventions (numpy arrays or torch
+        CUDA tensors; nu is float64); a resampled frame has an rgba plane only.  Returns when the planes are written."""
+        out = Renderer._output(None, Precision.F64, self.height, self.width, rgba, nu, iter)
+        _capi.check(self._lib.fr_deep_sequence_render(self._h, int(frame), C.byref(out)))
+
+    def render_png(self, frame: int, path: str) -> None:
+        """fr_deep_sequence_render_png: the post-chained frame through the 8-bit export into a PNG"""
+        _capi.check(self._lib.fr_deep_sequence_render_png(self._h, int(frame), os.fsencode(path)))
+
+    def render_to_folder(self, folder: str, on_frame: Optional[Callable[[int, int], object]] = None) -> int:
+        """Every frame as frame_%06d.png (fr_frame_path) in `folder`, in order.  on_frame(frame, frames) is called behind
+        each file; a truthy return cancels the run.  Returns the number of files written."""
+        os.makedirs(folder, exist_ok=True)
+        for f in range(self.frames):
+            self.render_png(f, frame_path(folder, f))
+            if on_frame is not None and on_frame(f, self.frames):
+                return f + 1
+        return self.frames
+
+    def stats(self) -> tuple:
+        """fr_deep_sequence_stats: (exact renders enqueued, frames resampled, reference orbits computed)"""
+        out = (C.c_uint64 * 3)()
+        _capi.check(self._lib.fr_deep_sequence_stats(self._h, out))
+        return int(out[0]), int(out[1]), int(out[2])

@@ -606,6 +606,8 @@ static int frac_bits_of_pair(double zm, int32_t ze)
     return (bits + 63) / 64 * 64;
 }
 
+int fr_deepx_frac_bits_pair(double zm, int32_t ze) { return frac_bits_of_pair(zm, ze); }
+
 int fr_deepx_frac_bits(const char* zoom)
 {
     double zm;
@@ -638,9 +640,9 @@ int fr_deepx_resolve(const fr_deepx_view* v, double* zm, int32_t* ze, int32_t* f
     return FR_OK;
 }
 
-int fr_deepx_validate(const fr_params* p, const fr_deepx_view* v, uint32_t width, uint32_t height)
+int fr_deepx_validate_params(const fr_params* p, uint32_t width, uint32_t height)
 {
-    if (!p || !v) return fr_set_error(FR_ERR_INVALID_ARG, "params/deep view is NULL");
+    if (!p) return fr_set_error(FR_ERR_INVALID_ARG, "params/deep view is NULL");
     if (p->fractal_type != FR_FRACTAL_MANDELBROT)
         return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deepx renders FR_FRACTAL_MANDELBROT only (got %d)", p->fractal_type);
     if (p->precision != FR_PRECISION_F64)
@@ -656,13 +658,26 @@ int fr_deepx_validate(const fr_params* p, const fr_deepx_view* v, uint32_t width
     if (p->flags & FR_FLAG_DEEP_BLA)
         return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deepx: FR_FLAG_DEEP_BLA is not available (its table is fp64): the flag of "
                             "extended views is FR_FLAG_DEEPX_BLA");
+    return FR_OK;
+}
+
+int fr_deepx_check_centre(const char* center_x, const char* center_y, int32_t frac_bits)
+{
+    uint64_t cr[kMaxLimbs], ci[kMaxLimbs];
+    const fx_fmt fmt = {frac_bits, (frac_bits + 63) / 64 + 1};
+    const fr_deep_view c = {center_x, center_y, frac_bits, 0};
+    return parse_centre(&c, fmt, cr, ci);
+}
+
+int fr_deepx_validate(const fr_params* p, const fr_deepx_view* v, uint32_t width, uint32_t height)
+{
+    if (!p || !v) return fr_set_error(FR_ERR_INVALID_ARG, "params/deep view is NULL");
+    int st = fr_deepx_validate_params(p, width, height);
+    if (st != FR_OK) return st;
     double zm;
     int32_t ze, F;
     if ((st = fr_deepx_resolve(v, &zm, &ze, &F)) != FR_OK) return st;
-    uint64_t cr[kMaxLimbs], ci[kMaxLimbs];
-    const fx_fmt fmt = {F, (F + 63) / 64 + 1};
-    const fr_deep_view c = {v->center_x, v->center_y, F, 0};
-    return parse_centre(&c, fmt, cr, ci);
+    return fr_deepx_check_centre(v->center_x, v->center_y, F);
 }
 
 int fr_deepx_reference_orbit(const fr_deepx_view* v, int32_t max_iter, float bailout, double* out_mant_xy, int32_t* out_exp2,

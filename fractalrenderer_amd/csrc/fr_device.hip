@@ -19,6 +19,7 @@
 #include "fr_phoenix.hip.h"
 #include "fr_mandelbulb.hip.h"
 #include "fr_deep.hip.h"
+#include "fr_deepseq.hip.h"
 #include "fr_tuning.h"
 #include "fr_plan.h"
 
@@ -1202,8 +1203,11 @@ static int enqueue_deepx_bla(fr_ctx* c, const DeepXArgs& x, hipStream_t stream)
     return FR_OK;
 }
 
-static int enqueue_deepx(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, uint32_t W, uint32_t H, const fr_shard* shard,
-                         float* rgba, void* nu, int32_t* iter, hipStream_t stream, bool out_frame)
+/* the extended view already resolved: v gives the centre strings (and a zoom string the orbit does not depend on), the
+ * zoom is (zm, ze) and the orbit's fraction bits are `bits` -- what fr_render_deepx and the frames of a fr_deep_sequence share */
+static int enqueue_deepx_at(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, double zm, int32_t ze, int32_t bits, uint32_t W,
+                            uint32_t H, const fr_shard* shard, float* rgba, void* nu, int32_t* iter, hipStream_t stream,
+                            bool out_frame)
 {
     fr_shard norm;
     uint32_t rows_local = 0;
@@ -1211,9 +1215,8 @@ static int enqueue_deepx(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, 
     if (sh != FR_OK || rows_local == 0) return sh;
     DeepXArgs x;
     memset(&x, 0, sizeof(x));
-    int32_t bits = 0;
-    const int rs = fr_deepx_resolve(v, &x.zm, &x.ze, &bits);
-    if (rs != FR_OK) return rs;
+    x.zm = zm;
+    x.ze = ze;
     const int os = deepx_orbit_for(c, p, v, bits, stream);
     if (os != FR_OK) return os;
 
@@ -1227,6 +1230,123 @@ static int enqueue_deepx(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, 
 
     if (p->flags & FR_FLAG_DEEPX_BLA) return enqueue_deepx_bla(c, x, stream);
     return launch_one_pass(c, stream, "deep_kernel<DeepXArgs>", deep_kernel<DeepXArgs>, x, a.g, a.q, c->deepx_wg_per_cu, false);
+}
+
+static int enqueue_deepx(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, uint32_t W, uint32_t H, const fr_shard* shard,
+                         float* rgba, void* nu, int32_t* iter, hipStream_t stream, bool out_frame)
+{
+    double zm = 0.0;
+    int32_t ze = 0, bits = 0;
+    const int rs = fr_deepx_resolve(v, &zm, &ze, &bits);
+    if (rs != FR_OK) return rs;
+    return enqueue_deepx_at(c, p, v, zm, ze, bits, W, H, shard, rgba, nu, iter, stream, out_frame);
+}
+
+/* ---- deep zoom sequences (fr_deep_sequence; the rules are in the header, the host planning in fr_deepseq.c) ---------------
+ * Every exact render is enqueue_deepx_at around the sequence's one orbit key.  Mode 1 keeps two device rgba planes: each
+ * holds one keyframe, tagged with its index and with the post-chain flag it was rendered with (fr_deep_sequence_render_png
+ * forces the flag), and the least recently needed one makes room. */
+struct fr_deep_sequence {
+    fr_ctx* c;
+    fr_params p;
+    fr_deepseq_walk w;
+    char* str[3];               /* copies of center_x, center_y, zoom_first */
+    fr_deepx_view view;         /* the centre (the orbit key); its zoom string only has to be a valid one */
+    uint32_t W, H;
+    float* key[2];              /* mode 1: the keyframe planes */
+    int32_t key_id[2];
+    bool key_valid[2], key_post[2];
+    uint64_t key_used[2], clock;
+    uint64_t n_exact, n_resampled, n_orbits;
+};
+
+static int seq_exact(fr_deep_sequence* q, const fr_params* p, double zm, int32_t ze, float* rgba, void* nu, int32_t* iter,
+                     hipStream_t s)
+{
+    const int st = enqueue_deepx_at(q->c, p, &q->view, zm, ze, q->w.frac_bits, q->W, q->H, nullptr, rgba, nu, iter, s, false);
+    if (st == FR_OK) ++q->n_exact;
+    return st;
+}
+
+/* keyframe j in one of the two planes, rendered unless it is there -- into a free plane, else the less recently needed one,
+ * but never the plane that holds keyframe *other (the frame's second one); nu / iter of it, if asked for, come from that
+ * render or from one of their own */
+static int seq_keyframe(fr_deep_sequence* q, const fr_params* p, int32_t j, const int32_t* other, void* nu, int32_t* iter,
+                        hipStream_t s, int* slot_out)
+{
+    const bool post = (p->flags & FR_FLAG_POST_CHAIN) != 0;
+    int slot = -1, kept = -1;
+    for (int i = 0; i < 2; ++i) {
+        if (!q->key_valid[i] || q->key_post[i] != post) continue;
+        if (q->key_id[i] == j) slot = i;
+        else if (other && q->key_id[i] == *other) kept = i;
+    }
+    if (slot >= 0) {
+        if (nu || iter) {
+            const int st = seq_exact(q, p, q->w.zm0, q->w.ze0 - j, nullptr, nu, iter, s);
+            if (st != FR_OK) return st;
+        }
+    } else {
+        slot = kept >= 0 ? 1 - kept : (!q->key_valid[0] ? 0 : (!q->key_valid[1] ? 1 : (q->key_used[0] <= q->key_used[1] ? 0 : 1)));
+        q->key_valid[slot] = false;
+        const int st = seq_exact(q, p, q->w.zm0, q->w.ze0 - j, q->key[slot], nu, iter, s);
+        if (st != FR_OK) return st;
+        q->key_id[slot] = j;
+        q->key_post[slot] = post;
+        q->key_valid[slot] = true;
+    }
+    q->key_used[slot] = ++q->clock;
+    *slot_out = slot;
+    return FR_OK;
+}
+
+static int seq_enqueue_frame(fr_deep_sequence* q, const fr_params* p, const fr_deep_sequence_frame& f, float* rgba, void* nu,
+                             int32_t* iter, hipStream_t s)
+{
+    const size_t npx = (size_t)q->W * q->H;
+    if (q->w.mode == 0 || (!f.resampled && !(f.zoom_mant == q->w.zm0 && f.zoom_exp2 == q->w.ze0 - f.keyframe)))
+        return seq_exact(q, p, f.zoom_mant, f.zoom_exp2, rgba, nu, iter, s);
+    int s0 = -1, s1 = -1;
+    const int32_t k0 = f.keyframe, k1 = f.keyframe + 1;
+    int st = seq_keyframe(q, p, k0, f.resampled ? &k1 : nullptr, nu, iter, s, &s0);
+    if (st != FR_OK) return st;
+    if (!f.resampled) {
+        if (rgba) FR_HIP_TRY(hipMemcpyAsync(rgba, q->key[s0], npx * 16, hipMemcpyDeviceToDevice, s));
+        return FR_OK;
+    }
+    st = seq_keyframe(q, p, k1, &k0, nullptr, nullptr, s, &s1);
+    if (st != FR_OK) return st;
+    ResampleArgs a;
+    a.key0 = reinterpret_cast<const float4*>(q->key[s0]);
+    a.key1 = reinterpret_cast<const float4*>(q->key[s1]);
+    a.out = reinterpret_cast<float4*>(rgba);
+    a.W = (int32_t)q->W; a.H = (int32_t)q->H;
+    a.u = f.u;
+    const uint32_t grid = (uint32_t)((npx + kBlockThreads - 1) / kBlockThreads);
+    hipLaunchKernelGGL(deep_resample_kernel, dim3(grid), dim3(kBlockThreads), 0, s, a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fr_set_error(FR_ERR_HIP, "deep_resample_kernel launch failed: %s", hipGetErrorString(e));
+    ++q->n_resampled;
+    return FR_OK;
+}
+
+/* one frame on `s`: one event pair around all of its launches (fr_ctx_last_kernel_ms is the frame's device time), and the
+ * orbits the context computed for it counted */
+static int seq_enqueue(fr_deep_sequence* q, const fr_params* p, const fr_deep_sequence_frame& f, float* rgba, void* nu,
+                       int32_t* iter, hipStream_t s)
+{
+    fr_ctx* c = q->c;
+    const uint64_t gen0 = c->deepx_gen;
+    const bool timed = c->timing;
+    if (timed) FR_HIP_TRY(hipEventRecord(c->ev_begin, s));
+    c->timing = false;
+    const int st = seq_enqueue_frame(q, p, f, rgba, nu, iter, s);
+    c->timing = timed;
+    q->n_orbits += c->deepx_gen - gen0;
+    if (st != FR_OK) return st;
+    if (timed) FR_HIP_TRY(hipEventRecord(c->ev_end, s));
+    c->have_timing = timed;
+    return FR_OK;
 }
 
 /* the parameter part of the kernel argument block (everything that does not depend on the frame geometry) */
@@ -2074,6 +2194,27 @@ extern "C" int fr_export_rgb16_async(fr_ctx* c, const float* rgba, uint32_t W, u
     return export_async<uint16_t>(c, rgba, W, H, rgb16, through_half, hip_stream, "fr_export_rgb16_async");
 }
 
+/* behind the render of a frame into frame_buf on the context's stream: fp16 round + 8-bit export + flip on the device, the
+ * 3 B/pixel readback, PNG */
+static int frame_png_tail(fr_ctx* c, uint32_t W, uint32_t H, const char* path)
+{
+    const size_t npx = (size_t)W * H;
+    float* d_rgba = (float*)c->frame_buf;
+    uint8_t* d_rgb8 = (uint8_t*)c->frame_buf + npx * 16;
+    c->render_on_user_stream = false;
+    hipError_t e = launch_export(c, reinterpret_cast<const float4*>(d_rgba), d_rgb8, W, H, 1, c->stream);
+    if (e != hipSuccess) return fr_set_error(FR_ERR_HIP, "export launch failed: %s", hipGetErrorString(e));
+    uint8_t* host = (uint8_t*)malloc(npx * 3);
+    if (!host) return fr_set_error(FR_ERR_NOMEM, "out of host memory");
+    hipError_t ce = hipMemcpyAsync(host, d_rgb8, npx * 3, hipMemcpyDeviceToHost, c->stream);
+    if (ce == hipSuccess) ce = hipStreamSynchronize(c->stream);
+    if (ce != hipSuccess) { free(host); return fr_set_error(FR_ERR_HIP, "readback failed: %s", hipGetErrorString(ce)); }
+    int st = check_overflow(c);
+    if (st == FR_OK) st = fr_write_png(path, W, H, 8, host, nullptr, 0, 0);
+    free(host);
+    return st;
+}
+
 /* RenderFrameCallback body: src/vk_engine.cpp:1181-1418 (render -> readback -> CPU tonemap/flip -> PNG),
  * with everything up to the 3 B/pixel readback on the GPU. */
 extern "C" int fr_render_frame_png(fr_ctx* c, const fr_params* p, uint32_t W, uint32_t H, const char* path)
@@ -2090,19 +2231,91 @@ extern "C" int fr_render_frame_png(fr_ctx* c, const fr_params* p, uint32_t W, ui
     if (q.fractal_type != FR_FRACTAL_DEEP_ZOOM) q.flags |= FR_FLAG_POST_CHAIN;   /* the storage image holds the post-chained colour;
                                                                                      the deep-zoom shader has no post chain */
     float* d_rgba = (float*)c->frame_buf;
-    uint8_t* d_rgb8 = (uint8_t*)c->frame_buf + npx * 16;
     st = enqueue_render(c, &q, W, H, nullptr, d_rgba, nullptr, nullptr, c->stream);
     if (st != FR_OK) return st;
-    c->render_on_user_stream = false;
-    hipError_t e = launch_export(c, reinterpret_cast<const float4*>(d_rgba), d_rgb8, W, H, 1, c->stream);
-    if (e != hipSuccess) return fr_set_error(FR_ERR_HIP, "export launch failed: %s", hipGetErrorString(e));
-    uint8_t* host = (uint8_t*)malloc(npx * 3);
-    if (!host) return fr_set_error(FR_ERR_NOMEM, "out of host memory");
-    hipError_t ce = hipMemcpyAsync(host, d_rgb8, npx * 3, hipMemcpyDeviceToHost, c->stream);
-    if (ce == hipSuccess) ce = hipStreamSynchronize(c->stream);
-    if (ce != hipSuccess) { free(host); return fr_set_error(FR_ERR_HIP, "readback failed: %s", hipGetErrorString(ce)); }
-    st = check_overflow(c);
-    if (st == FR_OK) st = fr_write_png(path, W, H, 8, host, nullptr, 0, 0);
-    free(host);
-    return st;
+    return frame_png_tail(c, W, H, path);
+}
+
+/* ---- deep zoom sequences: the entry points (the enqueue side is next to enqueue_deepx) ------------------------------------ */
+extern "C" int fr_deep_sequence_create(fr_ctx* c, const fr_params* p, const fr_deep_sequence_desc* d, uint32_t W, uint32_t H,
+                                       fr_deep_sequence** out)
+{
+    if (!out) return fr_set_error(FR_ERR_INVALID_ARG, "fr_deep_sequence_create: out is NULL");
+    *out = nullptr;
+    if (!c) return fr_set_error(FR_ERR_INVALID_ARG, "ctx is NULL");
+    if (!p || !d) return fr_set_error(FR_ERR_INVALID_ARG, "params/deep sequence descriptor is NULL");
+    fr_deepseq_walk w;
+    const int st = fr_deepseq_resolve(p, d, W, H, &w);
+    if (st != FR_OK) return st;
+    if ((uint64_t)W * H >= (1ull << 31)) return fr_set_error(FR_ERR_INVALID_ARG, "a deep sequence frame has fewer than 2^31 pixels");
+    fr_deep_sequence* q = (fr_deep_sequence*)calloc(1, sizeof(fr_deep_sequence));
+    if (!q) return fr_set_error(FR_ERR_NOMEM, "out of host memory");
+    q->c = c; q->p = *p; q->w = w; q->W = W; q->H = H;
+    const char* src[3] = {d->center_x, d->center_y, d->zoom_first};
+    for (int i = 0; i < 3; ++i)
+        if (!(q->str[i] = strdup(src[i]))) { fr_deep_sequence_destroy(q); return fr_set_error(FR_ERR_NOMEM, "out of host memory"); }
+    q->view.center_x = q->str[0]; q->view.center_y = q->str[1]; q->view.zoom = q->str[2];
+    q->view.frac_bits = w.frac_bits; q->view.reserved = 0;
+    if (w.mode == 1) {
+        hipError_t e = hipSetDevice(c->device);
+        for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipMalloc((void**)&q->key[i], (size_t)W * H * 16);
+        if (e != hipSuccess) {
+            fr_deep_sequence_destroy(q);
+            return fr_set_error(FR_ERR_HIP, "deep sequence keyframe planes: %s", hipGetErrorString(e));
+        }
+    }
+    *out = q;
+    return FR_OK;
+}
+
+extern "C" void fr_deep_sequence_destroy(fr_deep_sequence* q)
+{
+    if (!q) return;
+    if (q->key[0] || q->key[1]) {
+        (void)hipSetDevice(q->c->device);
+        (void)hipStreamSynchronize(q->c->stream);
+        for (int i = 0; i < 2; ++i)
+            if (q->key[i]) (void)hipFree(q->key[i]);
+    }
+    for (int i = 0; i < 3; ++i) free(q->str[i]);
+    free(q);
+}
+
+extern "C" int fr_deep_sequence_render(fr_deep_sequence* q, int32_t frame, const fr_output* out)
+{
+    if (!q || !out) return fr_set_error(FR_ERR_INVALID_ARG, "fr_deep_sequence_render: sequence/out is NULL");
+    if (frame < 0 || frame >= q->w.frames) return fr_set_error(FR_ERR_INVALID_ARG, "frame %d outside [0, %d)", frame, q->w.frames);
+    if (out->layout != FR_LAYOUT_PACKED) return fr_set_error(FR_ERR_INVALID_ARG, "a deep sequence writes FR_LAYOUT_PACKED whole frames");
+    fr_deep_sequence_frame f;
+    fr_deepseq_frame(&q->w, frame, &f);
+    if (f.resampled && (out->nu || out->iter))
+        return fr_set_error(FR_ERR_UNSUPPORTED, "frame %d is resampled from keyframes %d and %d: it has an rgba plane only", frame,
+                            f.keyframe, f.keyframe + 1);
+    return render_sync(q->c, &q->p, q->W, q->H, nullptr, out, [&](auto, auto rgba, auto nu, auto iter, auto s, bool) {
+        return seq_enqueue(q, &q->p, f, rgba, nu, iter, s); });
+}
+
+extern "C" int fr_deep_sequence_render_png(fr_deep_sequence* q, int32_t frame, const char* path)
+{
+    if (!q || !path) return fr_set_error(FR_ERR_INVALID_ARG, "fr_deep_sequence_render_png: NULL argument");
+    if (frame < 0 || frame >= q->w.frames) return fr_set_error(FR_ERR_INVALID_ARG, "frame %d outside [0, %d)", frame, q->w.frames);
+    fr_ctx* c = q->c;
+    FR_HIP_TRY(hipSetDevice(c->device));
+    const size_t npx = (size_t)q->W * q->H;
+    const int gs = grow_device(&c->frame_buf, &c->frame_bytes, npx * 16 + npx * 3);
+    if (gs != FR_OK) return gs;
+    fr_params p = q->p;
+    p.flags |= FR_FLAG_POST_CHAIN;
+    fr_deep_sequence_frame f;
+    fr_deepseq_frame(&q->w, frame, &f);
+    const int st = seq_enqueue(q, &p, f, (float*)c->frame_buf, nullptr, nullptr, c->stream);
+    if (st != FR_OK) return st;
+    return frame_png_tail(c, q->W, q->H, path);
+}
+
+extern "C" int fr_deep_sequence_stats(const fr_deep_sequence* q, uint64_t out[3])
+{
+    if (!q || !out) return fr_set_error(FR_ERR_INVALID_ARG, "fr_deep_sequence_stats: sequence/out is NULL");
+    out[0] = q->n_exact; out[1] = q->n_resampled; out[2] = q->n_orbits;
+    return FR_OK;
 }

@@ -34,6 +34,21 @@ int fr_deep_ship_validate(const fr_params* p, const fr_deep_view* v, uint32_t wi
 /* the validation of fr_render_deepx (fr_deep.c), and its view resolved: the zoom pair and the fraction bits */
 int fr_deepx_validate(const fr_params* p, const fr_deepx_view* v, uint32_t width, uint32_t height);
 int fr_deepx_resolve(const fr_deepx_view* v, double* zm, int32_t* ze, int32_t* frac_bits);
+/* the parts of fr_deepx_validate that a caller with a resolved view shares (fr_deepseq.c): the rules for p, the centre
+ * strings parsed at frac_bits, and fr_deepx_frac_bits' rule on a zoom pair */
+int fr_deepx_validate_params(const fr_params* p, uint32_t width, uint32_t height);
+int fr_deepx_check_centre(const char* center_x, const char* center_y, int32_t frac_bits);
+int fr_deepx_frac_bits_pair(double zm, int32_t ze);
+
+/* fr_deep_sequence (fr_deepseq.c): a descriptor resolved -- the two zoom pairs, D = log2(last / first), the one F -- and
+ * what frame f is.  fr_deepseq_resolve performs every check of the descriptor; p may be NULL (fr_deep_sequence_plan has
+ * none), width == height == 0 skips the frame-size rules as fr_params_validate does. */
+typedef struct fr_deepseq_walk {
+    double  zm0, zm1, D;
+    int32_t ze0, ze1, frames, frac_bits, mode;
+} fr_deepseq_walk;
+int  fr_deepseq_resolve(const fr_params* p, const fr_deep_sequence_desc* d, uint32_t width, uint32_t height, fr_deepseq_walk* w);
+void fr_deepseq_frame(const fr_deepseq_walk* w, int32_t frame, fr_deep_sequence_frame* out);
 /* tests: a centre string in the fixed point of the reference orbit (fr_deep.c): ceil(frac_bits / 64) + 1 little-endian
  * two's-complement limbs into out[0 .. nlimbs); returns that number of limbs or an error */
 int fr_deep_parse_fixed(const char* s, int32_t frac_bits, uint64_t* out, int32_t nlimbs);

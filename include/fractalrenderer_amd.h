@@ -408,7 +408,7 @@ int fr_render_mandelbulb_async(fr_ctx* ctx, const fr_params* p, const fr_mandelb
  *     of the orbit (dz = z, m = 0) whenever |z| < |dz| or the orbit ends (Zhuoran's rebasing): no glitch detection and
  *     no second reference are needed.
  * Deltas are fp64, so the zoom reaches 1e-290; fr_render_deepx (below, FR_HAS_DEEPX) carries them with an extended exponent
- * and reaches 1e-1000.
+ * and reaches 1e-1000, and fr_deep_sequence (below it, FR_HAS_DEEP_SEQUENCE) walks a zoom into one centre through such views.
  *
  * The view: centre_x / centre_y are decimal strings, [+-]digits[.digits][(e|E)[+-]digits], at most 4096 characters,
  * |centre| < 2^32; p->center_x and p->center_y are ignored.  The zoom is p->zoom (the view height, as everywhere), finite
@@ -548,7 +548,7 @@ int fr_ctx_last_deep_steps(fr_ctx* ctx, uint64_t out[3]);
  * The context keeps the most recent ship orbit on the device in a slot of its own, keyed as fr_render_deep's: a ship render
  * never evicts the Mandelbrot orbit, nor the reverse.
  *
- * Out of scope: extended exponents below 1e-290, fr_node and .franim. */
+ * Out of scope: extended exponents below 1e-290, fr_node and .franim, and zoom sequences (fr_deep_sequence is Mandelbrot's). */
 #define FR_HAS_DEEP_SHIP 1
 #define FR_HAS_DEEP_SHIP_BLA 1    /* FR_FLAG_DEEP_SHIP_BLA and fr_ctx_last_deep_ship_steps (below fr_render_deep_ship_async) */
 
@@ -670,7 +670,8 @@ int fr_ctx_last_deep_ship_steps(fr_ctx* ctx, uint64_t out[3]);
  * the asynchronous form's rules are those of fr_render_deep; the context keeps the most recent extended orbit on the device
  * next to (and independent of) fr_render_deep's, keyed by (centre strings, F, max_iterations, bailout).
  *
- * Out of scope: fr_node, .franim and zoom paths for deep views, and depths beyond 1e-1000 (the 4096-bit cap of F). */
+ * Out of scope: fr_node and .franim for deep views, and depths beyond 1e-1000 (the 4096-bit cap of F).  A zoom into one
+ * centre, frame after frame, is fr_deep_sequence (below, FR_HAS_DEEP_SEQUENCE); fr_zoom_path stays a double. */
 #define FR_HAS_DEEPX 1
 #define FR_HAS_DEEPX_BLA 1        /* FR_FLAG_DEEPX_BLA and fr_ctx_last_deepx_steps (below fr_render_deepx_async) */
 #define FR_DEEPX_ZERO_EXP (-(1 << 28))   /* the exponent of a zero in the extended storage */
@@ -753,6 +754,95 @@ int fr_render_deepx_async(fr_ctx* ctx, const fr_params* p, const fr_deepx_view* 
  * out[0] single steps (plain and extended), out[1] BLA steps, out[2] updates skipped.  FR_ERR_UNSUPPORTED if there is no
  * such call.  fr_ctx_last_deep_steps does not report these calls. */
 int fr_ctx_last_deepx_steps(fr_ctx* ctx, uint64_t out[3]);
+
+/* ---- deep zoom sequences: one centre, one orbit, frame after frame ---------------------------------------------------------
+ * A zoom into one centre as an object: the zoom walked in log space over the whole range of fr_render_deepx, every frame
+ * and keyframe rendered around ONE reference orbit, and -- in mode 1 -- only one keyframe per octave rendered exactly, the
+ * frames in between resampled on the device from the two neighbouring keyframes.  Nothing about fr_render_deepx changes.
+ *
+ * Zoom of frame f.  (zm0, ze0), (zm1, ze1) = the fr_deepx_zoom pairs of zoom_first and zoom_last;
+ *   D = (double)(ze1 - ze0) + (log2(zm1) - log2(zm0)), each operation one fp64 rounding, log2 and exp2 the host's libm.
+ *   Frame 0 has the first pair exactly (L = 0), frame frames-1 the last pair exactly (L = D).  Any other frame:
+ *   L = (D * f) / (frames - 1), q = floor(L), r = L - q, m = zm0 * exp2(r); if m >= 2 then m = m / 2, q = q + 1; the pair is
+ *   (m, ze0 + q).  Two equal mantissas make D an exact integer, and every frame with integral L lies exactly on
+ *   zoom_first 2^L: its decimal string exists and fr_render_deepx renders the same view.
+ *   s = -L, k = floor(s) (fr_deep_sequence_frame.keyframe).  The frame is on the keyframe grid iff s == k; then u = 1, else
+ *   u = exp2(-(s - k)), in (0.5, 1): the frame's height over keyframe k's.  Keyframe j is the view at (zm0, ze0 - j), for a
+ *   zoom-out sequence too, where j goes negative.
+ * F and the orbit.  frac_bits = 0: F = fr_deepx_frac_bits' rule applied to HALF the smaller of the two zooms (the pair
+ *   (zm, ze - 1) of the smaller), in both modes; else F = frac_bits as for fr_deepx_view.  Every frame and keyframe of a
+ *   sequence is an extended view with this one F, p's max_iterations and bailout: they all hit the context's extended-orbit
+ *   cache under one key, and the orbit is computed once (until another fr_render_deepx view on the context displaces it).
+ * Validation.  p: fr_render_deepx's rules, FR_FLAG_DEEPX_BLA included -- every exact render honours the flag.  The zoom
+ *   strings: fr_deepx_zoom's rules.  Centre strings and frac_bits as for fr_deepx_view.  frames < 2, a mode outside {0, 1}
+ *   or reserved != 0: FR_ERR_INVALID_ARG.  Mode 1: every keyframe the plan needs (k of every frame, k + 1 of every frame
+ *   off the grid) must lie in [1e-1000, 1e3], compared on the pair as there: FR_ERR_INVALID_ARG.  fr_deep_sequence_plan
+ *   performs the descriptor's checks with no device (and no p); a frame outside [0, frames) is FR_ERR_INVALID_ARG.
+ * Mode 0.  Frame f is fr_render_deepx's render at the planned pair: all three planes, FR_MEM_HOST / FR_MEM_DEVICE,
+ *   FR_LAYOUT_PACKED whole frames.  A frame whose pair is that of a decimal string gets the bytes of fr_render_deepx with
+ *   that string and frac_bits = F.
+ * Mode 1.  A frame on the grid is its keyframe, rendered exactly: the bytes of mode 0, all three planes.  Any other frame
+ *   (fr_deep_sequence_frame.resampled = 1) is resampled from keyframes k and k + 1, rgba only: asking for nu or iter is
+ *   FR_ERR_UNSUPPORTED.  The sequence owns two device rgba planes that hold the two most recently needed keyframes, rendered
+ *   with p's flags (with FR_FLAG_POST_CHAIN the resampled colour is post-chained colour), so a monotone walk over the
+ *   frames renders each keyframe once.  (A last frame whose mantissa differs from zm0 while D still came out integral is
+ *   rendered at its own pair and not kept as a keyframe.)  fr_ctx_last_kernel_ms after a sequence call is the device time of
+ *   everything that call enqueued: the keyframes it had to render and the resampling.
+ * Resampling, per pixel (x, y): coordinates fp64, colour fp32, every operation one rounding, no contraction.
+ *   dx = x - 0.5 W, dy = y - 0.5 H, u2 = u + u;  qx = 0.5 W + dx*u2, qy = 0.5 H + dy*u2.
+ *   If 0 <= qx <= W-1 and 0 <= qy <= H-1 read keyframe k + 1 at (qx, qy), else keyframe k at (0.5 W + dx*u, 0.5 H + dy*u).
+ *   At the read point (sx, sy): x0 = floor(sx) clamped to [0, W-1], x1 = min(x0 + 1, W-1), wx = (float)(sx - x0),
+ *   cx = 1.0f - wx; the same for y.  Per colour channel, v00 = (x0, y0), v01 = (x1, y0), v10 = (x0, y1), v11 = (x1, y1):
+ *   top = v00*cx + v01*wx, bot = v10*cx + v11*wx, out = top*cy + bot*wy.  Alpha is 1.
+ * Calls are synchronous, frames may be asked for in any order, and a sequence is used from one thread at a time, like its
+ * context, which must outlive it.  W * H < 2^31.
+ *
+ * Out of scope: Burning Ship sequences; a max_iterations that varies per frame (it would change the BLA table's N and the
+ * colour scale between keyframes); shards, fr_node and .franim files; asynchronous forms; a moving centre. */
+#define FR_HAS_DEEP_SEQUENCE 1
+
+typedef struct fr_deep_sequence fr_deep_sequence;
+
+typedef struct fr_deep_sequence_desc {
+    const char* center_x;      /* as fr_deep_view */
+    const char* center_y;
+    const char* zoom_first;    /* view height of frame 0, fr_deepx_view's grammar and range */
+    const char* zoom_last;     /* view height of frame frames-1 */
+    int32_t     frames;        /* >= 2 */
+    int32_t     frac_bits;     /* 0 = automatic (above), else as fr_deepx_view */
+    int32_t     mode;          /* 0 = every frame rendered exactly; 1 = octave keyframes + resampling */
+    int32_t     reserved;      /* must be 0 */
+} fr_deep_sequence_desc;       /* 48 bytes on LP64 */
+
+typedef struct fr_deep_sequence_frame {   /* what frame f is: host arithmetic only */
+    double  zoom_mant;         /* in [1, 2) */
+    int32_t zoom_exp2;
+    int32_t frac_bits;         /* the sequence's F */
+    int32_t keyframe;          /* k (above); may be negative */
+    int32_t resampled;         /* 1: mode 1 and the frame is not a keyframe itself */
+    double  u;                 /* 1.0 on a keyframe, else in (0.5, 1) */
+} fr_deep_sequence_frame;      /* 32 bytes */
+
+/* Frame `frame` of the sequence `desc` describes; no device is touched. */
+int fr_deep_sequence_plan(const fr_deep_sequence_desc* desc, int32_t frame, fr_deep_sequence_frame* out);
+
+/* A sequence of width x height frames on ctx.  p, the strings and desc are copied.  Mode 1 allocates its two keyframe
+ * planes (32 width height bytes) here. */
+int fr_deep_sequence_create(fr_ctx* ctx, const fr_params* p, const fr_deep_sequence_desc* desc, uint32_t width, uint32_t height,
+                            fr_deep_sequence** out);
+void fr_deep_sequence_destroy(fr_deep_sequence* seq);
+
+/* Frame `frame` into out's planes (rules above); returns when they are written. */
+int fr_deep_sequence_render(fr_deep_sequence* seq, int32_t frame, const fr_output* out);
+
+/* The frame with FR_FLAG_POST_CHAIN forced, then fr_render_frame_png's tail: fp16 round, 8-bit export, flip, PNG.  (A
+ * keyframe plane remembers the flag it was rendered with: a mode-1 sequence created without the flag that alternates between
+ * this call and fr_deep_sequence_render renders its keyframes again at every change.) */
+int fr_deep_sequence_render_png(fr_deep_sequence* seq, int32_t frame, const char* path);
+
+/* out[0] exact renders enqueued (mode-0 frames and keyframes), out[1] frames produced by resampling, out[2] reference
+ * orbits computed during this sequence's calls. */
+int fr_deep_sequence_stats(const fr_deep_sequence* seq, uint64_t out[3]);
 
 /* ---- frames over the GPUs of a node (BASELINE.json north_star: "tiled across the 8 GPUs of one node as disjoint row
  * bands with a final RCCL gather over xGMI") -----------------------------------------------------------------------------

@@ -163,6 +163,13 @@ SIGNATURES = {
                                   _P(fr_output)]),
     "fr_render_deepx_async": (C.c_int, [C.c_void_p, _P(fr_params), _P(fr_deepx_view), C.c_uint32, C.c_uint32, _P(fr_shard),
                                         _P(fr_output), C.c_void_p]),
+    "fr_deepx_ship_reference_orbit": (C.c_int, [_P(fr_deepx_view), C.c_int32, C.c_float, C.c_void_p, C.c_void_p, _P(C.c_int32)]),
+    "fr_render_deepx_ship": (C.c_int, [C.c_void_p, _P(fr_params), _P(fr_deepx_view), C.c_uint32, C.c_uint32, _P(fr_shard),
+                                       _P(fr_output)]),
+    "fr_render_deepx_ship_async": (C.c_int, [C.c_void_p, _P(fr_params), _P(fr_deepx_view), C.c_uint32, C.c_uint32, _P(fr_shard),
+                                             _P(fr_output), C.c_void_p]),
+    "fr_deep_ship_sequence_create": (C.c_int, [C.c_void_p, _P(fr_params), _P(fr_deep_sequence_desc), C.c_uint32, C.c_uint32,
+                                               _P(C.c_void_p)]),
     "fr_deep_sequence_plan": (C.c_int, [_P(fr_deep_sequence_desc), C.c_int32, _P(fr_deep_sequence_frame)]),
     "fr_deep_sequence_create": (C.c_int, [C.c_void_p, _P(fr_params), _P(fr_deep_sequence_desc), C.c_uint32, C.c_uint32,
                                           _P(C.c_void_p)]),
@@ -252,6 +259,7 @@ INTERNAL_SIGNATURES = {
     "fr_deepx_bla_table": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),   # fr_internal.h: tests
     "fr_deep_ship_bla_table": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),   # fr_internal.h: tests
     "fr_deepx_validate": (C.c_int, [_P(fr_params), _P(fr_deepx_view), C.c_uint32, C.c_uint32]),        # fr_internal.h: tests
+    "fr_deepx_ship_validate": (C.c_int, [_P(fr_params), _P(fr_deepx_view), C.c_uint32, C.c_uint32]),   # fr_internal.h: tests
     "fr_deep_ship_validate": (C.c_int, [_P(fr_params), _P(fr_deep_view), C.c_uint32, C.c_uint32]),     # fr_internal.h: tests
     "fr_deepseq_resolve": (C.c_int, [_P(fr_params), _P(fr_deep_sequence_desc), C.c_uint32, C.c_uint32, C.c_void_p]),   # fr_internal.h: tests
 }

@@ -241,23 +241,31 @@ class DeepZoomSequence:
     zoom_first to zoom_last (decimal strings, fr_deepx_view's range) in equal steps of log(zoom) over `frames` frames.
     keyframes=False renders every frame exactly (fr_render_deepx's kernels); keyframes=True renders one keyframe per octave
     and resamples the frames in between from their two neighbouring keyframes on the GPU (rgba only).  xbla sets
-    FR_FLAG_DEEPX_BLA for every exact render; post_chain as for Renderer.render_deep.  The renderer must outlive the
-    sequence; the rules are in include/fractalrenderer_amd.h."""
+    FR_FLAG_DEEPX_BLA for every exact render; post_chain as for Renderer.render_deep.  formula="ship" walks into a Burning
+    Ship centre instead (fr_deep_ship_sequence_create: every exact render is fr_render_deepx_ship's; xbla=True is a ValueError
+    there, extended ship views have no BLA).  The renderer must outlive the sequence; the rules are in
+    include/fractalrenderer_amd.h."""
 
     def __init__(self, renderer: Renderer, state: FractalState, cx, cy, zoom_first, zoom_last, frames: int, width: int,
-                 height: int, *, keyframes: bool = False, frac_bits: int = 0, xbla: bool = False, post_chain: bool = False):
+                 height: int, *, keyframes: bool = False, frac_bits: int = 0, xbla: bool = False, post_chain: bool = False,
+                 formula: str = "mandelbrot"):
+        if formula not in ("mandelbrot", "ship"):
+            raise ValueError(f"formula {formula!r} is neither \"mandelbrot\" nor \"ship\"")
+        ship = formula == "ship"
+        if ship and xbla:
+            raise ValueError("xbla=True is not available with formula=\"ship\": extended Burning Ship views have no BLA")
         self._lib = _capi.lib()
         self._h = None
         self.renderer, self.frames, self.width, self.height = renderer, int(frames), int(width), int(height)
         self._desc = _capi.fr_deep_sequence_desc(str(cx).encode("ascii"), str(cy).encode("ascii"),
                                                  str(zoom_first).encode("ascii"), str(zoom_last).encode("ascii"),
                                                  int(frames), int(frac_bits), 1 if keyframes else 0, 0)
-        p = state.to_params(FractalType.Mandelbrot, Precision.F64, post_chain)
+        p = state.to_params(FractalType.BurningShip if ship else FractalType.Mandelbrot, Precision.F64, post_chain)
         if xbla:
             p.flags |= _capi.FR_FLAG_DEEPX_BLA
         h = C.c_void_p()
-        _capi.check(self._lib.fr_deep_sequence_create(renderer._ctx, C.byref(p), C.byref(self._desc), self.width, self.height,
-                                                      C.byref(h)))
+        create = self._lib.fr_deep_ship_sequence_create if ship else self._lib.fr_deep_sequence_create
+        _capi.check(create(renderer._ctx, C.byref(p), C.byref(self._desc), self.width, self.height, C.byref(h)))
         self._h = h
 
     def close(self) -> None:

@@ -14,6 +14,9 @@
  *
  * Deep Burning Ship views (fr_render_deep_ship): the same loop with Im = floor(2 |Zr| |Zi| / 2^F) + Ci (orbit_formula), and
  * fr_deep_validate's rules for FR_FRACTAL_BURNING_SHIP (fr_deep_ship_validate).
+ *
+ * Extended Burning Ship views (fr_render_deepx_ship): the ship's recurrence through the extended storage, and the ship's
+ * rules with the zoom taken from the view's string (fr_deepx_ship_validate).
  */
 #include "fr_internal.h"
 
@@ -680,10 +683,10 @@ int fr_deepx_validate(const fr_params* p, const fr_deepx_view* v, uint32_t width
     return fr_deepx_check_centre(v->center_x, v->center_y, F);
 }
 
-int fr_deepx_reference_orbit(const fr_deepx_view* v, int32_t max_iter, float bailout, double* out_mant_xy, int32_t* out_exp2,
-                             int32_t* out_len)
+static int reference_orbit_x(const char* who, orbit_formula formula, const fr_deepx_view* v, int32_t max_iter, float bailout,
+                             double* out_mant_xy, int32_t* out_exp2, int32_t* out_len)
 {
-    if (!out_mant_xy || !out_exp2 || !out_len) return fr_set_error(FR_ERR_INVALID_ARG, "fr_deepx_reference_orbit: out is NULL");
+    if (!out_mant_xy || !out_exp2 || !out_len) return fr_set_error(FR_ERR_INVALID_ARG, "%s: out is NULL", who);
     if (max_iter < 1 || max_iter > (1 << 24))
         return fr_set_error(FR_ERR_INVALID_ARG, "max_iterations %d outside [1, 2^24]", max_iter);
     int st;
@@ -695,5 +698,51 @@ int fr_deepx_reference_orbit(const fr_deepx_view* v, int32_t max_iter, float bai
     uint64_t cr[kMaxLimbs], ci[kMaxLimbs];
     const fr_deep_view c = {v->center_x, v->center_y, F, 0};
     if ((st = parse_centre(&c, fmt, cr, ci)) != FR_OK) return st;
-    return orbit_loop(cr, ci, fmt, kOrbitMandelbrot, max_iter, bailout, out_mant_xy, out_exp2, out_len);
+    return orbit_loop(cr, ci, fmt, formula, max_iter, bailout, out_mant_xy, out_exp2, out_len);
+}
+
+int fr_deepx_reference_orbit(const fr_deepx_view* v, int32_t max_iter, float bailout, double* out_mant_xy, int32_t* out_exp2,
+                             int32_t* out_len)
+{
+    return reference_orbit_x("fr_deepx_reference_orbit", kOrbitMandelbrot, v, max_iter, bailout, out_mant_xy, out_exp2, out_len);
+}
+
+/* ---- extended Burning Ship views (fr_render_deepx_ship) ---------------------------------------------------------------------- */
+int fr_deepx_ship_reference_orbit(const fr_deepx_view* v, int32_t max_iter, float bailout, double* out_mant_xy,
+                                  int32_t* out_exp2, int32_t* out_len)
+{
+    return reference_orbit_x("fr_deepx_ship_reference_orbit", kOrbitShip, v, max_iter, bailout, out_mant_xy, out_exp2, out_len);
+}
+
+int fr_deepx_ship_validate_params(const fr_params* p, uint32_t width, uint32_t height)
+{
+    if (!p) return fr_set_error(FR_ERR_INVALID_ARG, "params/deep view is NULL");
+    if (p->fractal_type != FR_FRACTAL_BURNING_SHIP)
+        return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deepx_ship renders FR_FRACTAL_BURNING_SHIP only (got %d)",
+                            p->fractal_type);
+    if (p->precision != FR_PRECISION_F64)
+        return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deepx_ship needs FR_PRECISION_F64 (got %d)", p->precision);
+    fr_params q = *p;                                            /* the double centre and zoom are not read */
+    q.center_x = 0.0; q.center_y = 0.0; q.zoom = 1.0;
+    int st = fr_params_validate(&q, width, height);
+    if (st != FR_OK) return st;
+    if ((st = check_bailout(p->bailout)) != FR_OK) return st;
+    if (p->orbit_trap_enabled || (p->stripe_enabled && p->interior_style == 2) || p->interior_style == 3)
+        return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deepx_ship: the orbit trap, stripes with interior_style 2 and "
+                            "interior_style 3 need the whole orbit and are not available");
+    if (p->flags & (FR_FLAG_DEEP_BLA | FR_FLAG_DEEPX_BLA | FR_FLAG_DEEP_SHIP_BLA))
+        return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deepx_ship: FR_FLAG_DEEP_BLA / FR_FLAG_DEEPX_BLA / FR_FLAG_DEEP_SHIP_BLA "
+                            "are not available (extended Burning Ship views have no BLA table)");
+    return FR_OK;
+}
+
+int fr_deepx_ship_validate(const fr_params* p, const fr_deepx_view* v, uint32_t width, uint32_t height)
+{
+    if (!p || !v) return fr_set_error(FR_ERR_INVALID_ARG, "params/deep view is NULL");
+    int st = fr_deepx_ship_validate_params(p, width, height);
+    if (st != FR_OK) return st;
+    double zm;
+    int32_t ze, F;
+    if ((st = fr_deepx_resolve(v, &zm, &ze, &F)) != FR_OK) return st;
+    return fr_deepx_check_centre(v->center_x, v->center_y, F);
 }

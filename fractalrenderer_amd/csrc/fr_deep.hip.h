@@ -48,6 +48,12 @@
  * from the ship's device orbit, one launch per level -- r in an array of doubles of its own, the eight doubles of (A, B) as
  * four double2 per entry -- and deep_kernel<DeepShipBlaArgs> runs deep_orbit_ship_bla: deep_orbit_ship whose lanes probe
  * the table as deep_orbit_bla does.  A probe gathers 8 bytes, only the chosen level's 64 bytes of (A, B) are loaded.
+ *
+ * Extended Burning Ship views (fr_render_deepx_ship; the step is in the header): deep_kernel<DeepShipXArgs> runs
+ * deep_orbit_ship_x -- deep_orbit_x's two modes, registers, prefetch and mode changes around the ship's step.  The plain mode
+ * is deep_orbit_ship's step; the extended mode takes the fold in the delta's frame (ship_fold_x: the orbit coordinate brought
+ * to the delta's exponent by v_ldexp_f64, the same compares and selects), so a coordinate far below its partner, or exactly 0
+ * on the real axis, still folds the delta it meets.  The viewport map and the colour stage are the ship's.
  */
 #pragma once
 #include "fr_kernels.hip.h"
@@ -608,6 +614,137 @@ __device__ __forceinline__ void deep_orbit_x(const DeepXArgs& AA, const double c
     }
 }
 
+/* fr_render_deepx_ship: x.d.orbit holds the plain doubles P_n of the ship's orbit, x.mant / x.exp2 its extended storage */
+struct DeepShipXArgs {
+    DeepXArgs x;
+    double log_bailout;                  /* as DeepShipArgs */
+};
+
+/* fold_x of the header: ship_fold on an orbit mantissa X at exponent eZ and a delta mantissa a at exponent ed, s = eZ - ed,
+ * taken in the delta's frame -- the result is a mantissa at ed.  X far above the delta: the ldexp may give +-inf, w has X's
+ * sign, the select returns +-a and drops the infinite d.  X far below: Xs is 0 or a subnormal, below half an ulp of a. */
+__device__ __forceinline__ double ship_fold_x(const double X, const int s, const double a)
+{
+    const double Xs = __builtin_ldexp(X, s), X2s = __builtin_ldexp(X, s + 1);
+    const double w = Xs + a, d = X2s + a;
+    const double up = w >= 0.0 ? a : -d;
+    const double dn = w > 0.0 ? d : -a;
+    return X >= 0.0 ? up : dn;
+}
+
+/* deep_orbit_x for z <- (|x| + i |y|)^2 + c (the header's EXTENDED and PLAIN steps of fr_render_deepx_ship): the extended
+ * step on U = (|Z_m.x|, |Z_m.y|, Z_m.e + 1) and f = (fold_x, fold_x, dz.e), the plain step deep_orbit_ship's; z = Z_{m+1} (+) n
+ * with the signed orbit point, escape, rebase, norm and the mode rule as in deep_orbit_x.  (cx, cy, ec) = dc, normalised. */
+__device__ __forceinline__ void deep_orbit_ship_x(const DeepXArgs& AA, const double cx, const double cy, const int ec,
+                                                  bool live, int& esc, double& er2)
+{
+    const DeepArgs& A = AA.d;
+    const double2* __restrict__ orbit = A.orbit;
+    const double2* __restrict__ mant = AA.mant;
+    const int32_t* __restrict__ exp2 = AA.exp2;
+    const int N = A.n_ref, max_iter = A.max_iter;
+    const double B2 = A.B2;
+    /* the plain mode's dc: a component below 2^-1022 is 0 */
+    const double cpx = (cx != 0.0 && __builtin_amdgcn_frexp_exp(cx) + ec > -1022) ? __builtin_ldexp(cx, ec) : 0.0;
+    const double cpy = (cy != 0.0 && __builtin_amdgcn_frexp_exp(cy) + ec > -1022) ? __builtin_ldexp(cy, ec) : 0.0;
+    double dzx = 0.0, dzy = 0.0;                                 /* plain: dz; extended: its mantissas */
+    int ed = kXZero;
+    bool ext = true;
+    double Zx = 0.0, Zy = 0.0;                                   /* Z_m, in the lane's mode */
+    int eZ = kXZero;
+    const double2 z1 = mant[1];
+    double Znx = z1.x, Zny = z1.y;                               /* Z_{m+1} */
+    int eZn = exp2[1];
+    int m = 0;
+    esc = max_iter;
+    er2 = 0.0;
+    for (int i = 0; i < max_iter; ++i) {
+        if (__builtin_amdgcn_ballot_w64(live) == 0ull) break;
+        if (!live) continue;
+        const int mn = m + 2 <= N ? m + 2 : N;                   /* Z_{m+2}, for the next step (m + 1 < N) */
+        double ax, ay;                                           /* the next dz */
+        int ea = 0;
+        bool reb;
+        if (ext) {
+            const double2 Znn = mant[mn];
+            const int eZnn = exp2[mn];
+            const double fx = ship_fold_x(Zx, eZ - ed, dzx), fy = ship_fold_x(Zy, eZ - ed, dzy);
+            const int et = eZ + 1 > ed ? eZ + 1 : ed;
+            const double tx = __builtin_ldexp(fabs(Zx), eZ + 1 - et) + __builtin_ldexp(fx, ed - et);
+            const double ty = __builtin_ldexp(fabs(Zy), eZ + 1 - et) + __builtin_ldexp(fy, ed - et);
+            const double px = tx * fx - ty * fy;
+            const double py = tx * fy + ty * fx;
+            const int ep = et + ed;
+            const int en = ep > ec ? ep : ec;
+            const double nx = __builtin_ldexp(px, ep - en) + __builtin_ldexp(cx, ec - en);
+            const double ny = __builtin_ldexp(py, ep - en) + __builtin_ldexp(cy, ec - en);
+            ++m;
+            const int ez = eZn > en ? eZn : en;
+            const double zx = __builtin_ldexp(Znx, eZn - ez) + __builtin_ldexp(nx, en - ez);
+            const double zy = __builtin_ldexp(Zny, eZn - ez) + __builtin_ldexp(ny, en - ez);
+            const double r2 = zx * zx + zy * zy;
+            const double r2d = __builtin_ldexp(r2, 2 * ez);
+            if (r2d > B2) {
+                esc = i; er2 = r2d; live = false;
+                continue;
+            }
+            reb = r2 < __builtin_ldexp(nx * nx + ny * ny, 2 * (en - ez)) || m == N;
+            ax = reb ? zx : nx; ay = reb ? zy : ny; ea = reb ? ez : en;
+            x_norm(ax, ay, ea);
+            if (reb) m = 0;
+            if (ea <= kXThr) {                                    /* stays extended */
+                dzx = ax; dzy = ay; ed = ea;
+                if (reb) {
+                    Zx = 0.0; Zy = 0.0; eZ = kXZero; Znx = z1.x; Zny = z1.y; eZn = exp2[1];
+                } else {
+                    Zx = Znx; Zy = Zny; eZ = eZn; Znx = Znn.x; Zny = Znn.y; eZn = eZnn;
+                }
+                continue;
+            }
+            dzx = __builtin_ldexp(ax, ea); dzy = __builtin_ldexp(ay, ea);
+            ext = false;
+        } else {
+            const double2 Znn = orbit[mn];
+            const double X2 = Zx + Zx, Y2 = Zy + Zy;
+            const double fx = ship_fold(Zx, X2, dzx), fy = ship_fold(Zy, Y2, dzy);
+            const double tx = fabs(X2) + fx, ty = fabs(Y2) + fy;     /* |X| + |X| = |X + X| */
+            const double nx = (tx * fx - ty * fy) + cpx;
+            const double ny = (tx * fy + ty * fx) + cpy;
+            ++m;
+            const double zx = Znx + nx, zy = Zny + ny;
+            const double r2 = zx * zx + zy * zy;
+            if (r2 > B2) {
+                esc = i; er2 = r2; live = false;
+                continue;
+            }
+            reb = r2 < nx * nx + ny * ny || m == N;
+            ax = reb ? zx : nx; ay = reb ? zy : ny;
+            if (reb) m = 0;
+            if (!(fmax(fabs(ax), fabs(ay)) < 0x1p-400)) {         /* stays plain */
+                dzx = ax; dzy = ay;
+                if (reb) {
+                    const double2 p1 = orbit[1];
+                    Zx = 0.0; Zy = 0.0; Znx = p1.x; Zny = p1.y;
+                } else {
+                    Zx = Znx; Zy = Zny; Znx = Znn.x; Zny = Znn.y;
+                }
+                continue;
+            }
+            x_norm(ax, ay, ea);
+            dzx = ax; dzy = ay; ed = ea;
+            ext = true;
+        }
+        /* the lane changed its mode: Z_m and Z_{m+1} (m < N here) from the new mode's arrays */
+        if (ext) {
+            const double2 a = mant[m], b = mant[m + 1];
+            Zx = a.x; Zy = a.y; eZ = exp2[m]; Znx = b.x; Zny = b.y; eZn = exp2[m + 1];
+        } else {
+            const double2 a = orbit[m], b = orbit[m + 1];
+            Zx = a.x; Zy = a.y; Znx = b.x; Zny = b.y;
+        }
+    }
+}
+
 /* ---- BLA for extended views (FR_FLAG_DEEPX_BLA; the semantics are in the header) -----------------------------------------
  * The table of the extended orbit: per entry the radius r as 8 bytes (XRad: the top 24 bits of its mantissa as a float and
  * its int32 exponent -- what a probe gathers), and apart from it (A, B) as two double2 of normalised mantissas with their
@@ -894,15 +1031,18 @@ __device__ __forceinline__ const DeepArgs& deep_args(const DeepBlaArgs& A) { ret
 __device__ __forceinline__ const DeepArgs& deep_args(const DeepXBlaArgs& A) { return A.x.d; }
 __device__ __forceinline__ const DeepArgs& deep_args(const DeepShipArgs& A) { return A.d; }
 __device__ __forceinline__ const DeepArgs& deep_args(const DeepShipBlaArgs& A) { return A.s.d; }
+__device__ __forceinline__ const DeepArgs& deep_args(const DeepShipXArgs& A) { return A.x.d; }
 __device__ __forceinline__ const DeepXArgs& deepx_args(const DeepXArgs& A) { return A; }
 __device__ __forceinline__ const DeepXArgs& deepx_args(const DeepXBlaArgs& A) { return A.x; }
-__device__ __forceinline__ const DeepShipArgs& ship_args(const DeepShipArgs& A) { return A; }
-__device__ __forceinline__ const DeepShipArgs& ship_args(const DeepShipBlaArgs& A) { return A.s; }
+__device__ __forceinline__ double ship_log_bailout(const DeepShipArgs& A) { return A.log_bailout; }
+__device__ __forceinline__ double ship_log_bailout(const DeepShipBlaArgs& A) { return A.s.log_bailout; }
+__device__ __forceinline__ double ship_log_bailout(const DeepShipXArgs& A) { return A.log_bailout; }
 
 /* deep_kernel<DeepArgs>: the plain step; deep_kernel<DeepBlaArgs>: with BLA (deep_orbit_bla, the step counts);
  * deep_kernel<DeepXArgs>: extended-exponent deltas (deep_orbit_x); deep_kernel<DeepXBlaArgs>: those with BLA
  * (deep_orbit_x_bla, the step counts); deep_kernel<DeepShipArgs>: the Burning Ship (deep_orbit_ship, its viewport map and
- * colour stage); deep_kernel<DeepShipBlaArgs>: the ship with BLA (deep_orbit_ship_bla, the step counts) */
+ * colour stage); deep_kernel<DeepShipBlaArgs>: the ship with BLA (deep_orbit_ship_bla, the step counts);
+ * deep_kernel<DeepShipXArgs>: the ship with extended-exponent deltas (deep_orbit_ship_x, the ship's map and colour stage) */
 template <class ARGS>
 __global__ void __launch_bounds__(kBlockThreads)
 deep_kernel(const ARGS AA)
@@ -911,14 +1051,15 @@ deep_kernel(const ARGS AA)
     constexpr bool SHIPBLA = std::is_same<ARGS, DeepShipBlaArgs>::value;
     constexpr bool BLA = std::is_same<ARGS, DeepBlaArgs>::value || XBLA || SHIPBLA;
     constexpr bool X = std::is_same<ARGS, DeepXArgs>::value || XBLA;
-    constexpr bool SHIP = std::is_same<ARGS, DeepShipArgs>::value || SHIPBLA;
+    constexpr bool SHIPX = std::is_same<ARGS, DeepShipXArgs>::value;
+    constexpr bool SHIP = std::is_same<ARGS, DeepShipArgs>::value || SHIPBLA || SHIPX;
     constexpr int FRACTAL = SHIP ? 2 : 0;                         /* the colour stage: shade() / colour_of() */
     const DeepArgs& A = deep_args(AA);
     __shared__ LdsBlock S;
     __shared__ double2 log2_lds[kLog2Entries];
     if (threadIdx.x == 0) S.pal = A.pal;
     if constexpr (SHIP) {
-        if (threadIdx.x == 0) S.log_bailout = ship_args(AA).log_bailout;
+        if (threadIdx.x == 0) S.log_bailout = ship_log_bailout(AA);
     }
     reinterpret_cast<double*>(log2_lds)[threadIdx.x] = reinterpret_cast<const double*>(A.log2_tab)[threadIdx.x];
     __syncthreads();
@@ -962,9 +1103,16 @@ deep_kernel(const ARGS AA)
                     uvx = uvx + ((double)ux * sample_offset - centre) / resx;
                     uvy = uvy + ((double)uy * sample_offset - centre) / resy;
                 }
-                const double sdx = (uvx - 0.5) * zoom * (resx / resy);
-                const double sdy = (uvy - 0.5) * zoom;
-                if constexpr (SHIPBLA) {
+                double zs = zoom;                                 /* extended: the zoom's mantissa, its exponent goes to dc.e */
+                if constexpr (SHIPX) zs = AA.x.zm;
+                const double sdx = (uvx - 0.5) * zs * (resx / resy);
+                const double sdy = (uvy - 0.5) * zs;
+                if constexpr (SHIPX) {
+                    double cx = inside ? sdx : 0.0, cy = inside ? sdy : 0.0;
+                    int ec = AA.x.ze;
+                    x_norm(cx, cy, ec);
+                    deep_orbit_ship_x(AA.x, cx, cy, ec, inside, esc, r2);
+                } else if constexpr (SHIPBLA) {
                     uint32_t np, nb;
                     deep_orbit_ship_bla(A, AA.t, inside ? sdx : 0.0, inside ? sdy : 0.0, z1, inside, esc, r2, np, nb);
                     if (inside) {

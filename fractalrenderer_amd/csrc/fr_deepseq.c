@@ -50,9 +50,16 @@ void fr_deepseq_frame(const fr_deepseq_walk* w, int32_t f, fr_deep_sequence_fram
 
 int fr_deepseq_resolve(const fr_params* p, const fr_deep_sequence_desc* d, uint32_t width, uint32_t height, fr_deepseq_walk* w)
 {
+    return fr_deepseq_resolve_formula(p, d, width, height, 0, w);
+}
+
+int fr_deepseq_resolve_formula(const fr_params* p, const fr_deep_sequence_desc* d, uint32_t width, uint32_t height, int ship,
+                               fr_deepseq_walk* w)
+{
     if (!d || !w) return fr_set_error(FR_ERR_INVALID_ARG, "deep sequence descriptor is NULL");
     int st;
-    if (p && (st = fr_deepx_validate_params(p, width, height)) != FR_OK) return st;
+    if (p && (st = ship ? fr_deepx_ship_validate_params(p, width, height) : fr_deepx_validate_params(p, width, height)) != FR_OK)
+        return st;
     if (d->reserved != 0) return fr_set_error(FR_ERR_INVALID_ARG, "fr_deep_sequence_desc.reserved must be 0");
     if (d->frames < 2) return fr_set_error(FR_ERR_INVALID_ARG, "a deep sequence has at least 2 frames (got %d)", d->frames);
     if (d->mode != 0 && d->mode != 1) return fr_set_error(FR_ERR_INVALID_ARG, "fr_deep_sequence_desc.mode %d outside {0, 1}", d->mode);

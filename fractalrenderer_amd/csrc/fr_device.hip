@@ -157,6 +157,14 @@ struct fr_ctx {
     hipEvent_t ev_ship_bla;     /* recorded behind every render with the flag (not while capturing): rebuilds wait for it */
     bool ev_ship_bla_valid;
     int ship_bla_wg_per_cu;     /* resident workgroups per CU of deep_kernel<DeepShipBlaArgs> (0 = not asked yet) */
+    /* extended Burning Ship views (fr_render_deepx_ship): their own orbit cache, laid out as deepx_host / deepx_dev */
+    char* shipx_host;
+    char* shipx_dev;
+    size_t shipx_cap;
+    int32_t shipx_len;          /* N + 1 */
+    OrbitKey shipx_key;         /* of shipx_dev */
+    int shipx_wg_per_cu;        /* resident workgroups per CU of deep_kernel<DeepShipXArgs> (0 = not asked yet) */
+    uint64_t shipx_gen;         /* bumped whenever shipx_dev receives another orbit */
 };
 
 #define FR_HIP_TRY(expr)                                                               \
@@ -249,6 +257,10 @@ extern "C" void fr_ctx_destroy(fr_ctx* c)
     if (c->deepx_dev) (void)hipFree(c->deepx_dev);
     free(c->deepx_key.x);
     free(c->deepx_key.y);
+    if (c->shipx_host) (void)hipHostFree(c->shipx_host);
+    if (c->shipx_dev) (void)hipFree(c->shipx_dev);
+    free(c->shipx_key.x);
+    free(c->shipx_key.y);
     if (c->ship_orbit_host) (void)hipHostFree(c->ship_orbit_host);
     if (c->ship_orbit_dev) (void)hipFree(c->ship_orbit_dev);
     free(c->ship_key.x);
@@ -1075,48 +1087,80 @@ static int enqueue_deep_ship(fr_ctx* c, const fr_params* p, const fr_deep_view* 
                            false);
 }
 
-/* ---- extended views (fr_render_deepx) -------------------------------------------------------------------------------
- * enqueue_deep with the orbit in the extended storage: the mantissa pairs and exponents of fr_deepx_reference_orbit, and
- * the plain doubles ldexp(mantissa, exponent) formed here on the host, in one upload. */
-static int deepx_orbit_for(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, int32_t bits, hipStream_t stream)
+/* ---- extended views (fr_render_deepx, fr_render_deepx_ship) -----------------------------------------------------------
+ * enqueue_deep with the orbit in the extended storage: the mantissa pairs and exponents of the formula's reference orbit,
+ * and the plain doubles ldexp(mantissa, exponent) formed here on the host, in one upload.
+ *
+ * One cache slot of extended orbits (OrbitSlot's counterpart): one pinned and one device block of cap points each, what they
+ * hold, the host function that computes the orbit, and the event behind the slot's most recent BLA render (none: no BLA) */
+struct XOrbitSlot {
+    char*& host;
+    char*& dev;
+    size_t& cap;
+    int32_t& len;
+    OrbitKey& key;
+    uint64_t& gen;
+    int (*compute)(const fr_deepx_view*, int32_t, float, double*, int32_t*, int32_t*);
+    hipEvent_t ev_bla;
+    const bool& ev_bla_valid;
+};
+
+static const bool kNoBlaEvent = false;
+
+static int xorbit_slot_fill(fr_ctx* c, const XOrbitSlot& o, const fr_params* p, const fr_deepx_view* v, int32_t bits,
+                            hipStream_t stream)
 {
     const int32_t max_iter = p->max_iterations;
-    if (orbit_key_matches(c->deepx_key, v->center_x, v->center_y, bits, max_iter, p->bailout)) return FR_OK;
-    /* as deep_orbit_for: the pinned block may still feed an upload, the device block an earlier render */
+    if (orbit_key_matches(o.key, v->center_x, v->center_y, bits, max_iter, p->bailout)) return FR_OK;
+    /* as orbit_slot_fill: the pinned block may still feed an upload, the device block an earlier render */
     FR_HIP_TRY(hipStreamSynchronize(stream));
     FR_HIP_TRY(hipStreamSynchronize(c->stream));
     if (c->have_render && c->last_stream != stream) FR_HIP_TRY(hipStreamSynchronize(c->last_stream));
-    if (c->ev_xbla_valid) FR_HIP_TRY(hipEventSynchronize(c->ev_xbla));    /* the last render with BLA, wherever it went */
-    c->deepx_key.valid = false;
-    ++c->deepx_gen;
+    if (o.ev_bla_valid) FR_HIP_TRY(hipEventSynchronize(o.ev_bla));        /* the slot's last BLA render, wherever it went */
+    o.key.valid = false;
+    ++o.gen;
     const size_t need = (size_t)max_iter + 1;
     const size_t point_bytes = 2 * sizeof(double2) + sizeof(int32_t);
-    if (need > c->deepx_cap) {
-        if (c->deepx_host) { (void)hipHostFree(c->deepx_host); c->deepx_host = nullptr; }
-        if (c->deepx_dev) { (void)hipFree(c->deepx_dev); c->deepx_dev = nullptr; }
-        c->deepx_cap = 0;
-        FR_HIP_TRY(hipHostMalloc((void**)&c->deepx_host, need * point_bytes));
-        FR_HIP_TRY(hipMalloc((void**)&c->deepx_dev, need * point_bytes));
-        c->deepx_cap = need;
+    if (need > o.cap) {
+        if (o.host) { (void)hipHostFree(o.host); o.host = nullptr; }
+        if (o.dev) { (void)hipFree(o.dev); o.dev = nullptr; }
+        o.cap = 0;
+        FR_HIP_TRY(hipHostMalloc((void**)&o.host, need * point_bytes));
+        FR_HIP_TRY(hipMalloc((void**)&o.dev, need * point_bytes));
+        o.cap = need;
     }
-    const size_t cap = c->deepx_cap;
-    double* plain = (double*)c->deepx_host;
+    const size_t cap = o.cap;
+    double* plain = (double*)o.host;
     double* mant = plain + 2 * cap;
     int32_t* exp2 = (int32_t*)(mant + 2 * cap);
     int32_t len = 0;
     fr_deepx_view w = *v;
     w.frac_bits = bits;
-    const int st = fr_deepx_reference_orbit(&w, max_iter, p->bailout, mant, exp2, &len);
+    const int st = o.compute(&w, max_iter, p->bailout, mant, exp2, &len);
     if (st != FR_OK) return st;
     for (int32_t n = 0; n < len; ++n) {
         plain[2 * n] = ldexp(mant[2 * n], exp2[n]);
         plain[2 * n + 1] = ldexp(mant[2 * n + 1], exp2[n]);
     }
-    FR_HIP_TRY(hipMemcpyAsync(c->deepx_dev, c->deepx_host, cap * point_bytes, hipMemcpyHostToDevice, stream));
+    FR_HIP_TRY(hipMemcpyAsync(o.dev, o.host, cap * point_bytes, hipMemcpyHostToDevice, stream));
     FR_HIP_TRY(hipStreamSynchronize(stream));     /* a later render of this view may go to another stream */
-    const int ks = orbit_key_store(c->deepx_key, v->center_x, v->center_y, bits, max_iter, p->bailout);
-    if (ks == FR_OK) c->deepx_len = len;
+    const int ks = orbit_key_store(o.key, v->center_x, v->center_y, bits, max_iter, p->bailout);
+    if (ks == FR_OK) o.len = len;
     return ks;
+}
+
+static int deepx_orbit_for(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, int32_t bits, hipStream_t stream)
+{
+    const XOrbitSlot o = {c->deepx_host, c->deepx_dev, c->deepx_cap, c->deepx_len, c->deepx_key, c->deepx_gen,
+                          fr_deepx_reference_orbit, c->ev_xbla, c->ev_xbla_valid};
+    return xorbit_slot_fill(c, o, p, v, bits, stream);
+}
+
+static int shipx_orbit_for(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, int32_t bits, hipStream_t stream)
+{
+    const XOrbitSlot o = {c->shipx_host, c->shipx_dev, c->shipx_cap, c->shipx_len, c->shipx_key, c->shipx_gen,
+                          fr_deepx_ship_reference_orbit, nullptr, kNoBlaEvent};
+    return xorbit_slot_fill(c, o, p, v, bits, stream);
 }
 
 /* FR_FLAG_DEEPX_BLA: the table of the cached extended orbit for this frame's dcmax (the whole frame's W, H and the zoom
@@ -1242,13 +1286,55 @@ static int enqueue_deepx(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, 
     return enqueue_deepx_at(c, p, v, zm, ze, bits, W, H, shard, rgba, nu, iter, stream, out_frame);
 }
 
+/* ---- extended Burning Ship views (fr_render_deepx_ship) ------------------------------------------------------------------
+ * enqueue_deepx_at on the extended ship slot and deep_kernel<DeepShipXArgs>: what fr_render_deepx_ship and the frames of a ship
+ * sequence share */
+static int enqueue_deepx_ship_at(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, double zm, int32_t ze, int32_t bits,
+                                 uint32_t W, uint32_t H, const fr_shard* shard, float* rgba, void* nu, int32_t* iter,
+                                 hipStream_t stream, bool out_frame)
+{
+    fr_shard norm;
+    uint32_t rows_local = 0;
+    const int sh = begin_shard(c, shard, H, &norm, &rows_local);
+    if (sh != FR_OK || rows_local == 0) return sh;
+    DeepShipXArgs s;
+    memset(&s, 0, sizeof(s));
+    s.x.zm = zm;
+    s.x.ze = ze;
+    const int os = shipx_orbit_for(c, p, v, bits, stream);
+    if (os != FR_OK) return os;
+
+    DeepArgs& a = s.x.d;
+    const size_t cap = c->shipx_cap;
+    a.orbit = reinterpret_cast<const double2*>(c->shipx_dev);
+    s.x.mant = a.orbit + cap;
+    s.x.exp2 = reinterpret_cast<const int32_t*>(s.x.mant + cap);
+    a.n_ref = c->shipx_len - 1;
+    fill_deep_args(a, c, p, tile_geom(W, H, rows_local, &norm, out_frame), rgba, nu, iter);
+    s.log_bailout = log((double)p->bailout);     /* as fill_params */
+    return launch_one_pass(c, stream, "deep_kernel<DeepShipXArgs>", deep_kernel<DeepShipXArgs>, s, a.g, a.q, c->shipx_wg_per_cu,
+                           false);
+}
+
+static int enqueue_deepx_ship(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, uint32_t W, uint32_t H,
+                              const fr_shard* shard, float* rgba, void* nu, int32_t* iter, hipStream_t stream, bool out_frame)
+{
+    double zm = 0.0;
+    int32_t ze = 0, bits = 0;
+    const int rs = fr_deepx_resolve(v, &zm, &ze, &bits);
+    if (rs != FR_OK) return rs;
+    return enqueue_deepx_ship_at(c, p, v, zm, ze, bits, W, H, shard, rgba, nu, iter, stream, out_frame);
+}
+
 /* ---- deep zoom sequences (fr_deep_sequence; the rules are in the header, the host planning in fr_deepseq.c) ---------------
- * Every exact render is enqueue_deepx_at around the sequence's one orbit key.  Mode 1 keeps two device rgba planes: each
- * holds one keyframe, tagged with its index and with the post-chain flag it was rendered with (fr_deep_sequence_render_png
+ * Every exact render is enqueue_deepx_at -- enqueue_deepx_ship_at for a ship sequence -- around the sequence's one orbit
+ * key.  Mode 1 keeps two device rgba planes: each holds one keyframe, tagged with its index and with the post-chain flag it
+ * was rendered with (fr_deep_sequence_render_png
  * forces the flag), and the least recently needed one makes room. */
 struct fr_deep_sequence {
     fr_ctx* c;
     fr_params p;
+    bool ship;                  /* the formula: fr_deep_ship_sequence_create's sequences render through fr_render_deepx_ship's path */
     fr_deepseq_walk w;
     char* str[3];               /* copies of center_x, center_y, zoom_first */
     fr_deepx_view view;         /* the centre (the orbit key); its zoom string only has to be a valid one */
@@ -1263,7 +1349,9 @@ struct fr_deep_sequence {
 static int seq_exact(fr_deep_sequence* q, const fr_params* p, double zm, int32_t ze, float* rgba, void* nu, int32_t* iter,
                      hipStream_t s)
 {
-    const int st = enqueue_deepx_at(q->c, p, &q->view, zm, ze, q->w.frac_bits, q->W, q->H, nullptr, rgba, nu, iter, s, false);
+    const int st = q->ship
+        ? enqueue_deepx_ship_at(q->c, p, &q->view, zm, ze, q->w.frac_bits, q->W, q->H, nullptr, rgba, nu, iter, s, false)
+        : enqueue_deepx_at(q->c, p, &q->view, zm, ze, q->w.frac_bits, q->W, q->H, nullptr, rgba, nu, iter, s, false);
     if (st == FR_OK) ++q->n_exact;
     return st;
 }
@@ -1336,13 +1424,14 @@ static int seq_enqueue(fr_deep_sequence* q, const fr_params* p, const fr_deep_se
                        int32_t* iter, hipStream_t s)
 {
     fr_ctx* c = q->c;
-    const uint64_t gen0 = c->deepx_gen;
+    const uint64_t& gen = q->ship ? c->shipx_gen : c->deepx_gen;
+    const uint64_t gen0 = gen;
     const bool timed = c->timing;
     if (timed) FR_HIP_TRY(hipEventRecord(c->ev_begin, s));
     c->timing = false;
     const int st = seq_enqueue_frame(q, p, f, rgba, nu, iter, s);
     c->timing = timed;
-    q->n_orbits += c->deepx_gen - gen0;
+    q->n_orbits += gen - gen0;
     if (st != FR_OK) return st;
     if (timed) FR_HIP_TRY(hipEventRecord(c->ev_end, s));
     c->have_timing = timed;
@@ -1632,8 +1721,8 @@ static int enqueue_ssaa_staged(fr_ctx* c, const fr_params* p, uint32_t W, uint32
 }
 
 /* ---- render entry points --------------------------------------------------------------------------------------------
- * fr_render_shard, fr_render_phoenix, fr_render_mandelbulb, fr_render_deep, fr_render_deep_ship and fr_render_deepx, each with
- * its _async form:
+ * fr_render_shard, fr_render_phoenix, fr_render_mandelbulb, fr_render_deep, fr_render_deep_ship, fr_render_deepx and
+ * fr_render_deepx_ship, each with its _async form:
  * their parameter checks, then render_sync / render_async with the enqueue step as
  * enqueue(shard, rgba, nu, iter, stream, out_frame) */
 static int check_common(fr_ctx* c, const fr_params* p, uint32_t W, uint32_t H, const fr_output* out)
@@ -2043,6 +2132,32 @@ extern "C" int fr_render_deepx(fr_ctx* c, const fr_params* p, const fr_deepx_vie
         return enqueue_deepx(c, p, v, W, H, sh, rgba, nu, iter, s, out_frame); });
 }
 
+static int check_deepx_ship(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, uint32_t W, uint32_t H, const fr_output* out)
+{
+    if (!c) return fr_set_error(FR_ERR_INVALID_ARG, "ctx is NULL");
+    if (!p || !v || !out) return fr_set_error(FR_ERR_INVALID_ARG, "params/deep view/out is NULL");
+    return fr_deepx_ship_validate(p, v, W, H);
+}
+
+extern "C" int fr_render_deepx_ship_async(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, uint32_t W, uint32_t H,
+                                          const fr_shard* shard, const fr_output* out, void* hip_stream)
+{
+    const int st = check_deepx_ship(c, p, v, W, H, out);
+    if (st != FR_OK) return st;
+    return render_async("fr_render_deepx_ship_async", c, H, shard, out, hip_stream,
+                        [&](auto sh, auto rgba, auto nu, auto iter, auto s, bool out_frame) {
+                            return enqueue_deepx_ship(c, p, v, W, H, sh, rgba, nu, iter, s, out_frame); });
+}
+
+extern "C" int fr_render_deepx_ship(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, uint32_t W, uint32_t H,
+                                    const fr_shard* shard, const fr_output* out)
+{
+    const int st = check_deepx_ship(c, p, v, W, H, out);
+    if (st != FR_OK) return st;
+    return render_sync(c, p, W, H, shard, out, [&](auto sh, auto rgba, auto nu, auto iter, auto s, bool out_frame) {
+        return enqueue_deepx_ship(c, p, v, W, H, sh, rgba, nu, iter, s, out_frame); });
+}
+
 /* ---- 8-bit export ------------------------------------------------------------------------------ */
 /* 1 when a frame's colour plane is a function of its smooth-count plane alone (fr_colorize_async) */
 extern "C" int fr_colorize_supported(const fr_params* p)
@@ -2237,20 +2352,20 @@ extern "C" int fr_render_frame_png(fr_ctx* c, const fr_params* p, uint32_t W, ui
 }
 
 /* ---- deep zoom sequences: the entry points (the enqueue side is next to enqueue_deepx) ------------------------------------ */
-extern "C" int fr_deep_sequence_create(fr_ctx* c, const fr_params* p, const fr_deep_sequence_desc* d, uint32_t W, uint32_t H,
-                                       fr_deep_sequence** out)
+static int deep_sequence_create(const char* who, bool ship, fr_ctx* c, const fr_params* p, const fr_deep_sequence_desc* d,
+                                uint32_t W, uint32_t H, fr_deep_sequence** out)
 {
-    if (!out) return fr_set_error(FR_ERR_INVALID_ARG, "fr_deep_sequence_create: out is NULL");
+    if (!out) return fr_set_error(FR_ERR_INVALID_ARG, "%s: out is NULL", who);
     *out = nullptr;
     if (!c) return fr_set_error(FR_ERR_INVALID_ARG, "ctx is NULL");
     if (!p || !d) return fr_set_error(FR_ERR_INVALID_ARG, "params/deep sequence descriptor is NULL");
     fr_deepseq_walk w;
-    const int st = fr_deepseq_resolve(p, d, W, H, &w);
+    const int st = fr_deepseq_resolve_formula(p, d, W, H, ship ? 1 : 0, &w);
     if (st != FR_OK) return st;
     if ((uint64_t)W * H >= (1ull << 31)) return fr_set_error(FR_ERR_INVALID_ARG, "a deep sequence frame has fewer than 2^31 pixels");
     fr_deep_sequence* q = (fr_deep_sequence*)calloc(1, sizeof(fr_deep_sequence));
     if (!q) return fr_set_error(FR_ERR_NOMEM, "out of host memory");
-    q->c = c; q->p = *p; q->w = w; q->W = W; q->H = H;
+    q->c = c; q->p = *p; q->ship = ship; q->w = w; q->W = W; q->H = H;
     const char* src[3] = {d->center_x, d->center_y, d->zoom_first};
     for (int i = 0; i < 3; ++i)
         if (!(q->str[i] = strdup(src[i]))) { fr_deep_sequence_destroy(q); return fr_set_error(FR_ERR_NOMEM, "out of host memory"); }
@@ -2266,6 +2381,18 @@ extern "C" int fr_deep_sequence_create(fr_ctx* c, const fr_params* p, const fr_d
     }
     *out = q;
     return FR_OK;
+}
+
+extern "C" int fr_deep_sequence_create(fr_ctx* c, const fr_params* p, const fr_deep_sequence_desc* d, uint32_t W, uint32_t H,
+                                       fr_deep_sequence** out)
+{
+    return deep_sequence_create("fr_deep_sequence_create", false, c, p, d, W, H, out);
+}
+
+extern "C" int fr_deep_ship_sequence_create(fr_ctx* c, const fr_params* p, const fr_deep_sequence_desc* d, uint32_t W, uint32_t H,
+                                            fr_deep_sequence** out)
+{
+    return deep_sequence_create("fr_deep_ship_sequence_create", true, c, p, d, W, H, out);
 }
 
 extern "C" void fr_deep_sequence_destroy(fr_deep_sequence* q)

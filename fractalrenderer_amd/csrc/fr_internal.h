@@ -39,6 +39,10 @@ int fr_deepx_resolve(const fr_deepx_view* v, double* zm, int32_t* ze, int32_t* f
 int fr_deepx_validate_params(const fr_params* p, uint32_t width, uint32_t height);
 int fr_deepx_check_centre(const char* center_x, const char* center_y, int32_t frac_bits);
 int fr_deepx_frac_bits_pair(double zm, int32_t ze);
+/* the validation of fr_render_deepx_ship (fr_deep.c): fr_deep_ship_validate's rules with the zoom from the view's string and
+ * no BLA flag; _params is the part a caller with a resolved view shares */
+int fr_deepx_ship_validate(const fr_params* p, const fr_deepx_view* v, uint32_t width, uint32_t height);
+int fr_deepx_ship_validate_params(const fr_params* p, uint32_t width, uint32_t height);
 
 /* fr_deep_sequence (fr_deepseq.c): a descriptor resolved -- the two zoom pairs, D = log2(last / first), the one F -- and
  * what frame f is.  fr_deepseq_resolve performs every check of the descriptor; p may be NULL (fr_deep_sequence_plan has
@@ -48,6 +52,9 @@ typedef struct fr_deepseq_walk {
     int32_t ze0, ze1, frames, frac_bits, mode;
 } fr_deepseq_walk;
 int  fr_deepseq_resolve(const fr_params* p, const fr_deep_sequence_desc* d, uint32_t width, uint32_t height, fr_deepseq_walk* w);
+/* fr_deepseq_resolve with p checked by the formula's rules: ship = 0 fr_render_deepx's, 1 fr_render_deepx_ship's */
+int  fr_deepseq_resolve_formula(const fr_params* p, const fr_deep_sequence_desc* d, uint32_t width, uint32_t height, int ship,
+                                fr_deepseq_walk* w);
 void fr_deepseq_frame(const fr_deepseq_walk* w, int32_t frame, fr_deep_sequence_frame* out);
 /* tests: a centre string in the fixed point of the reference orbit (fr_deep.c): ceil(frac_bits / 64) + 1 little-endian
  * two's-complement limbs into out[0 .. nlimbs); returns that number of limbs or an error */

@@ -274,7 +274,7 @@ class Renderer:
                          stream: Optional[int] = None, sync: bool = True, bla: bool = False) -> None:
         """fr_render_deep_ship / fr_render_deep_ship_async: a Burning Ship view deeper than double precision, by perturbation
         around one reference orbit of the ship's recurrence computed on the host.  `view` carries the centre as decimal
-        strings (a view with a zoom string is a ValueError: extended exponents are Mandelbrot's); the zoom, in
+        strings (a view with a zoom string is a ValueError: it goes to render_deepx_ship()); the zoom, in
         [1e-290, 1e3], and every other field come from `state` (its double centre is not read).  Always fp64: nu is float64.
         Planes, shard, stream and sync as for render_deep(); the context keeps the ship's orbit next to render_deep's.
         bla=True sets FR_FLAG_DEEP_SHIP_BLA: iteration skipping by bilinear approximation with the ship's real 2x2 maps (the
@@ -289,10 +289,27 @@ class Renderer:
         self._render_call(self._lib.fr_render_deep_ship, self._lib.fr_render_deep_ship_async, (C.byref(p), C.byref(v)), width,
                           height, Precision.F64, rows, rgba, nu, iter, shard, stream, sync)
 
+    def render_deepx_ship(self, state: FractalState, width: int, height: int, view: DeepView, *, post_chain: bool = False,
+                          rgba=None, nu=None, iter=None, shard: Optional[Shard] = None, stream: Optional[int] = None,
+                          sync: bool = True) -> None:
+        """fr_render_deepx_ship / fr_render_deepx_ship_async: a Burning Ship view with extended-exponent deltas, zooms down to
+        1e-1000.  `view` carries the centre and the zoom as decimal strings (DeepView(..., zoom="1e-400")); a view without a
+        zoom string is a ValueError (render_deep_ship() takes those).  state.zoom and its double centre are not read; every
+        other field comes from `state`.  Planes, shard, stream and sync as for render_deep_ship(); the context keeps this
+        path's orbit in a slot of its own.  There is no BLA for extended ship views."""
+        if view is None or view.zoom is None:
+            raise ValueError("render_deepx_ship needs a view with a zoom string (DeepView(..., zoom=\"1e-400\")); "
+                             "render_deep_ship renders views without one")
+        p = state.to_params(FractalType.BurningShip, Precision.F64, post_chain)
+        vx = view.to_cx()
+        rows = shard.rows(height) if shard else height
+        self._render_call(self._lib.fr_render_deepx_ship, self._lib.fr_render_deepx_ship_async, (C.byref(p), C.byref(vx)), width,
+                          height, Precision.F64, rows, rgba, nu, iter, shard, stream, sync)
+
     def _render_call(self, fn_sync, fn_async, params: tuple, width: int, height: int, precision: Precision, rows: int,
                      rgba, nu, it, shard: Optional[Shard], stream: Optional[int], sync: bool) -> None:
-        """the planes, the shard and the sync / async entry of render(), render_phoenix(), render_mandelbulb(), render_deep() and
-        render_deep_ship();
+        """the planes, the shard and the sync / async entry of render(), render_phoenix(), render_mandelbulb(), render_deep(),
+        render_deep_ship() and render_deepx_ship();
         params: the entry's
         arguments between the context and the frame size"""
         out = self._output(precision, rows, width, rgba, nu, it)

@@ -192,7 +192,7 @@ class DeepView:
     of at most 4096 characters, or Decimals (written out with str()).  frac_bits: fraction bits of the host's fixed-point
     reference orbit, 0 = automatic (deep_frac_bits(zoom)).  The zoom is FractalState.zoom; its centre is not read.
     zoom: None, or the view height as a decimal string (or Decimal) in [1e-1000, 1e3] -- then the view is an fr_deepx_view,
-    rendered with extended-exponent deltas (fr_render_deepx), and FractalState.zoom is not read either."""
+    rendered with extended-exponent deltas (fr_render_deepx, fr_render_deepx_ship), and FractalState.zoom is not read either."""
     center_x: object = "-0.5"
     center_y: object = "0"
     frac_bits: int = 0
@@ -257,4 +257,15 @@ def deepx_reference_orbit(view: DeepView, max_iterations: int, bailout: float = 
     v = view.to_cx()
     _capi.check(_capi.lib().fr_deepx_reference_orbit(_capi.C.byref(v), int(max_iterations), _F32(bailout), mant.ctypes.data,
                                                      exp2.ctypes.data, _capi.C.byref(n)))
+    return mant[:n.value].copy(), exp2[:n.value].copy()
+
+
+def deepx_ship_reference_orbit(view: DeepView, max_iterations: int, bailout: float = 4.0) -> tuple:
+    """fr_deepx_ship_reference_orbit: deepx_reference_orbit for the Burning Ship recurrence (points signed)."""
+    mant = np.empty((int(max_iterations) + 1, 2), np.float64)
+    exp2 = np.empty(int(max_iterations) + 1, np.int32)
+    n = _capi.C.c_int32()
+    v = view.to_cx()
+    _capi.check(_capi.lib().fr_deepx_ship_reference_orbit(_capi.C.byref(v), int(max_iterations), _F32(bailout), mant.ctypes.data,
+                                                          exp2.ctypes.data, _capi.C.byref(n)))
     return mant[:n.value].copy(), exp2[:n.value].copy()

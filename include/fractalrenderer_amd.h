@@ -548,7 +548,8 @@ int fr_ctx_last_deep_steps(fr_ctx* ctx, uint64_t out[3]);
  * The context keeps the most recent ship orbit on the device in a slot of its own, keyed as fr_render_deep's: a ship render
  * never evicts the Mandelbrot orbit, nor the reverse.
  *
- * Out of scope: extended exponents below 1e-290, fr_node and .franim, and zoom sequences (fr_deep_sequence is Mandelbrot's). */
+ * Out of scope: fr_node and .franim.  Extended exponents below 1e-290 are fr_render_deepx_ship (below, FR_HAS_DEEPX_SHIP), zoom
+ * sequences fr_deep_ship_sequence_create (FR_HAS_DEEP_SHIP_SEQUENCE). */
 #define FR_HAS_DEEP_SHIP 1
 #define FR_HAS_DEEP_SHIP_BLA 1    /* FR_FLAG_DEEP_SHIP_BLA and fr_ctx_last_deep_ship_steps (below fr_render_deep_ship_async) */
 
@@ -797,7 +798,8 @@ int fr_ctx_last_deepx_steps(fr_ctx* ctx, uint64_t out[3]);
  * Calls are synchronous, frames may be asked for in any order, and a sequence is used from one thread at a time, like its
  * context, which must outlive it.  W * H < 2^31.
  *
- * Out of scope: Burning Ship sequences; a max_iterations that varies per frame (it would change the BLA table's N and the
+ * Burning Ship sequences are fr_deep_ship_sequence_create (below, FR_HAS_DEEP_SHIP_SEQUENCE).
+ * Out of scope: a max_iterations that varies per frame (it would change the BLA table's N and the
  * colour scale between keyframes); shards, fr_node and .franim files; asynchronous forms; a moving centre. */
 #define FR_HAS_DEEP_SEQUENCE 1
 
@@ -843,6 +845,74 @@ int fr_deep_sequence_render_png(fr_deep_sequence* seq, int32_t frame, const char
 /* out[0] exact renders enqueued (mode-0 frames and keyframes), out[1] frames produced by resampling, out[2] reference
  * orbits computed during this sequence's calls. */
 int fr_deep_sequence_stats(const fr_deep_sequence* seq, uint64_t out[3]);
+
+/* ---- Burning Ship views below 1e-290: the ship's step with extended-exponent deltas ------------------------------------------
+ * fr_render_deep_ship for a view that a double cannot hold, as fr_render_deepx is for fr_render_deep.  Everything of the
+ * fr_render_deepx section is reused unchanged: extended numbers, norm, (+), the -400 mode rule, FR_DEEPX_ZERO_EXP; the view
+ * fr_deepx_view, fr_deepx_zoom, fr_deepx_frac_bits; the storage of an orbit point, (mx, my) 2^e plus the plain doubles P_n.
+ *
+ * Validation: fr_render_deep_ship's rules with the zoom taken from the view's string, 1e-1000 <= zoom <= 1e3; p->zoom and the
+ * double centre are ignored.  FR_FLAG_DEEP_BLA, FR_FLAG_DEEPX_BLA and FR_FLAG_DEEP_SHIP_BLA are FR_ERR_UNSUPPORTED here: BLA for
+ * extended ship views is out of scope.
+ *
+ * Orbit: the recurrence of fr_deep_ship_reference_orbit (points SIGNED) in the storage of fr_deepx_reference_orbit.  The
+ * exponent of a point is shared by its two coordinates and belongs to the larger one: a coordinate more than 2^1074 below its
+ * partner is stored as 0.
+ *
+ * dc: the ship's viewport map of fr_render_deep_ship -- uvx, uvy with the sx-outer sub-sample offsets -- then
+ *   dc = norm(((uvx - 0.5) * zm) * aspect, (uvy - 0.5) * zm, ze),  aspect = (double)W / (double)H of the WHOLE frame;
+ * dcp follows from dc as for fr_render_deepx.  dz = (0, 0, FR_DEEPX_ZERO_EXP), m = 0, mode = extended.
+ *
+ * EXTENDED step, Z_m = (X, Y, eZ) from the extended storage, dz = (a, b, ed) normalised.  The fold is taken IN THE DELTA'S
+ * FRAME, the orbit coordinate brought to the delta's exponent:
+ *   fold_x(X, eZ, a, ed):  Xs = ldexp(X, eZ - ed);  X2s = ldexp(X, eZ + 1 - ed);  w = Xs + a;  d = X2s + a;
+ *                          X >= 0 ? (w >= 0 ? a : -d) : (w > 0 ? d : -a)             -- a mantissa at exponent ed
+ *   f = (fold_x(X, eZ, a, ed), fold_x(Y, eZ, b, ed), ed)
+ *   t = (|X|, |Y|, eZ + 1) (+) f;   p = (t.x f.x - t.y f.y, t.x f.y + t.y f.x, t.e + ed);   n = p (+) dc;   m += 1;
+ *   z = Z_m (+) n
+ * and then the escape test, the rebase rule, norm and the mode rule of fr_render_deepx's EXTENDED step, unchanged.  For an
+ * orbit coordinate far above the delta the ldexp may give +-inf: w then has the sign of X, the fold returns +-a and the
+ * infinite d is discarded by the select.  For one far below the delta it gives 0 or a subnormal: that coordinate is below
+ * half an ulp of a.  (Aligning the fold to max(eZ + 1, ed) instead would be wrong: the orbit's exponent belongs to the larger
+ * coordinate, and a centre on the real axis has Y = 0 beside X near 2 -- its flipped d = 2Y + b would underflow to nothing.)
+ *
+ * PLAIN step: fr_render_deep_ship's step, operation for operation, on P_m, P_{m+1} and dcp; the mode switches are those of
+ * fr_render_deepx.
+ *
+ * On operands that a double holds the extended step performs the plain step's roundings (the exponents only carry the
+ * scale), so a view whose dc is at least 2^-400 -- every zoom down to about 1e-117 -- leaves the extended mode on its first
+ * step and gets the bytes of fr_render_deep_ship.
+ *
+ * Planes, colour stage, shards, layouts, memory kinds, options and fr_ctx_last_kernel_ms / _grid are those of
+ * fr_render_deep_ship.  The context keeps the most recent extended ship orbit on the device in a slot of its own, keyed as
+ * fr_render_deepx's: none of the four deep paths evicts another's orbit.
+ *
+ * Sequences (FR_HAS_DEEP_SHIP_SEQUENCE): fr_deep_ship_sequence_create makes a fr_deep_sequence whose exact renders are
+ * fr_render_deepx_ship's; the descriptor, the walk, F, mode 1's keyframe planes and the resampling are fr_deep_sequence's,
+ * and so are _plan, _render, _render_png, _stats and _destroy.  (At aa 1 the ship's map is ((x - 0.5 W) / H) zoom too, so the
+ * resampling geometry holds.)  p follows fr_render_deepx_ship's rules: p->fractal_type must be FR_FRACTAL_BURNING_SHIP, and
+ * fr_deep_sequence_create keeps rejecting it.
+ *
+ * Out of scope: BLA for extended ship views; fr_node and .franim; depths beyond 1e-1000; per-coordinate exponents in the
+ * orbit storage. */
+#define FR_HAS_DEEPX_SHIP 1
+#define FR_HAS_DEEP_SHIP_SEQUENCE 1
+
+/* fr_deepx_reference_orbit for the ship's recurrence: same arguments, validation and cost */
+int fr_deepx_ship_reference_orbit(const fr_deepx_view* v, int32_t max_iter, float bailout, double* out_mant_xy, int32_t* out_exp2,
+                                  int32_t* out_len);
+
+/* fr_render_deep_ship's contract (planes, memory kinds, FR_LAYOUT_FRAME, shards, options, the orbit cache) for an extended view */
+int fr_render_deepx_ship(fr_ctx* ctx, const fr_params* p, const fr_deepx_view* view, uint32_t width, uint32_t height,
+                         const fr_shard* shard, const fr_output* out);
+
+/* fr_render_deep_async's contract: a render of a new view computes its orbit on the host first and is never launch-only */
+int fr_render_deepx_ship_async(fr_ctx* ctx, const fr_params* p, const fr_deepx_view* view, uint32_t width, uint32_t height,
+                               const fr_shard* shard, const fr_output* out, void* hip_stream);
+
+/* fr_deep_sequence_create for a Burning Ship sequence (above); the object is used and destroyed as any fr_deep_sequence */
+int fr_deep_ship_sequence_create(fr_ctx* ctx, const fr_params* p, const fr_deep_sequence_desc* desc, uint32_t width,
+                                 uint32_t height, fr_deep_sequence** out);
 
 /* ---- frames over the GPUs of a node (BASELINE.json north_star: "tiled across the 8 GPUs of one node as disjoint row
  * bands with a final RCCL gather over xGMI") -----------------------------------------------------------------------------

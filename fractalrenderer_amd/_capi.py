@@ -40,6 +40,7 @@ FR_FLAG_POST_CHAIN = 0x1
 FR_FLAG_DEEP_BLA = 0x2
 FR_FLAG_DEEPX_BLA = 0x4
 FR_FLAG_DEEP_SHIP_BLA = 0x8
+FR_FLAG_DEEPX_SHIP_BLA = 0x10
 
 
 class fr_params(C.Structure):
@@ -155,6 +156,7 @@ SIGNATURES = {
     "fr_ctx_last_deep_steps": (C.c_int, [C.c_void_p, _P(C.c_uint64)]),
     "fr_ctx_last_deepx_steps": (C.c_int, [C.c_void_p, _P(C.c_uint64)]),
     "fr_ctx_last_deep_ship_steps": (C.c_int, [C.c_void_p, _P(C.c_uint64)]),
+    "fr_ctx_last_deepx_ship_steps": (C.c_int, [C.c_void_p, _P(C.c_uint64)]),
     "fr_deepx_view_default": (C.c_int, [_P(fr_deepx_view)]),
     "fr_deepx_zoom": (C.c_int, [C.c_char_p, _P(C.c_double), _P(C.c_int32)]),
     "fr_deepx_frac_bits": (C.c_int, [C.c_char_p]),
@@ -257,6 +259,7 @@ INTERNAL_SIGNATURES = {
     "fr_deep_parse_fixed": (C.c_int, [C.c_char_p, C.c_int32, _P(C.c_uint64), C.c_int32]),   # fr_internal.h: tests
     "fr_deep_bla_table": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),        # fr_internal.h: tests
     "fr_deepx_bla_table": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),   # fr_internal.h: tests
+    "fr_deepx_ship_bla_table": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),   # fr_internal.h: tests
     "fr_deep_ship_bla_table": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),   # fr_internal.h: tests
     "fr_deepx_validate": (C.c_int, [_P(fr_params), _P(fr_deepx_view), C.c_uint32, C.c_uint32]),        # fr_internal.h: tests
     "fr_deepx_ship_validate": (C.c_int, [_P(fr_params), _P(fr_deepx_view), C.c_uint32, C.c_uint32]),   # fr_internal.h: tests

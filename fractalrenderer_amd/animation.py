@@ -242,18 +242,21 @@ class DeepZoomSequence:
     keyframes=False renders every frame exactly (fr_render_deepx's kernels); keyframes=True renders one keyframe per octave
     and resamples the frames in between from their two neighbouring keyframes on the GPU (rgba only).  xbla sets
     FR_FLAG_DEEPX_BLA for every exact render; post_chain as for Renderer.render_deep.  formula="ship" walks into a Burning
-    Ship centre instead (fr_deep_ship_sequence_create: every exact render is fr_render_deepx_ship's; xbla=True is a ValueError
-    there, extended ship views have no BLA).  The renderer must outlive the sequence; the rules are in
-    include/fractalrenderer_amd.h."""
+    Ship centre instead (fr_deep_ship_sequence_create: every exact render is fr_render_deepx_ship's; bla=True sets
+    FR_FLAG_DEEPX_SHIP_BLA for each of them, and xbla=True is a ValueError there, as bla=True is for the Mandelbrot formula).
+    The renderer must outlive the sequence; the rules are in include/fractalrenderer_amd.h."""
 
     def __init__(self, renderer: Renderer, state: FractalState, cx, cy, zoom_first, zoom_last, frames: int, width: int,
                  height: int, *, keyframes: bool = False, frac_bits: int = 0, xbla: bool = False, post_chain: bool = False,
-                 formula: str = "mandelbrot"):
+                 formula: str = "mandelbrot", bla: bool = False):
         if formula not in ("mandelbrot", "ship"):
             raise ValueError(f"formula {formula!r} is neither \"mandelbrot\" nor \"ship\"")
         ship = formula == "ship"
         if ship and xbla:
-            raise ValueError("xbla=True is not available with formula=\"ship\": extended Burning Ship views have no BLA")
+            raise ValueError("xbla=True is not available with formula=\"ship\": the flag of extended Burning Ship views is "
+                             "bla=True")
+        if bla and not ship:
+            raise ValueError("bla=True is the Burning Ship formula's flag: the Mandelbrot formula takes xbla=True")
         self._lib = _capi.lib()
         self._h = None
         self.renderer, self.frames, self.width, self.height = renderer, int(frames), int(width), int(height)
@@ -263,6 +266,8 @@ class DeepZoomSequence:
         p = state.to_params(FractalType.BurningShip if ship else FractalType.Mandelbrot, Precision.F64, post_chain)
         if xbla:
             p.flags |= _capi.FR_FLAG_DEEPX_BLA
+        if bla:
+            p.flags |= _capi.FR_FLAG_DEEPX_SHIP_BLA
         h = C.c_void_p()
         create = self._lib.fr_deep_ship_sequence_create if ship else self._lib.fr_deep_sequence_create
         _capi.check(create(renderer._ctx, C.byref(p), C.byref(self._desc), self.width, self.height, C.byref(h)))

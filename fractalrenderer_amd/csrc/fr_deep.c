@@ -732,7 +732,8 @@ int fr_deepx_ship_validate_params(const fr_params* p, uint32_t width, uint32_t h
                             "interior_style 3 need the whole orbit and are not available");
     if (p->flags & (FR_FLAG_DEEP_BLA | FR_FLAG_DEEPX_BLA | FR_FLAG_DEEP_SHIP_BLA))
         return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deepx_ship: FR_FLAG_DEEP_BLA / FR_FLAG_DEEPX_BLA / FR_FLAG_DEEP_SHIP_BLA "
-                            "are not available (extended Burning Ship views have no BLA table)");
+                            "are not available (their tables belong to the other deep paths): the flag of extended Burning "
+                            "Ship views is FR_FLAG_DEEPX_SHIP_BLA");
     return FR_OK;
 }
 

@@ -54,6 +54,13 @@
  * is deep_orbit_ship's step; the extended mode takes the fold in the delta's frame (ship_fold_x: the orbit coordinate brought
  * to the delta's exponent by v_ldexp_f64, the same compares and selects), so a coordinate far below its partner, or exactly 0
  * on the real axis, still folds the delta it meets.  The viewport map and the colour stage are the ship's.
+ *
+ * BLA for extended ship views (FR_FLAG_DEEPX_SHIP_BLA; the semantics are in the header): the ship's real 2x2 maps carried as
+ * four mantissas with one shared int32 exponent.  deepx_ship_bla_level_kernel builds the table from the ship's extended
+ * orbit, one launch per level -- r as an XRad in an array of its own, the eight mantissas of (A, B) as four double2 and their
+ * two exponents as an int2 per entry -- and deep_kernel<DeepShipXBlaArgs> runs deep_orbit_ship_x_bla: deep_orbit_ship_x whose
+ * lanes, in either mode, probe the table as deep_orbit_x_bla does and take a BLA step in extended arithmetic.  A probe
+ * gathers 8 bytes; the chosen level's 72 bytes of (A, B) are loaded inside the taken-step branch only.
  */
 #pragma once
 #include "fr_kernels.hip.h"
@@ -1025,6 +1032,316 @@ __device__ __forceinline__ void deep_orbit_x_bla(const DeepXArgs& AA, const BlaX
     }
 }
 
+/* ---- BLA for extended ship views (FR_FLAG_DEEPX_SHIP_BLA; the semantics are in the header) ---------------------------------
+ * The table of the ship's extended orbit: per entry the radius as an XRad (what a probe gathers), and apart from it the real
+ * matrices A and B as four double2 of mantissas -- (a11, a12), (a21, a22), (b11, b12), (b21, b22), each matrix normalised on
+ * its largest element -- with their two shared exponents in an int2, loaded for the chosen level only.  Levels and offsets
+ * are those of the fp64 table. */
+struct ShipXBlaTable {
+    const XRad* r;                       /* r of every entry, level 1 first */
+    const double2* ab;                   /* ab[4 e .. 4 e + 3]: the rows of A and of B, mantissas */
+    const int2* abe;                     /* (A.e, B.e) */
+    int32_t levels;                      /* K = floor(log2(N - 1)), 0 = no table */
+    unsigned long long* steps;           /* single steps, BLA steps, updates skipped: one atomic add each per wave */
+};
+
+struct DeepShipXBlaArgs {
+    DeepShipXArgs s;
+    ShipXBlaTable t;
+};
+
+/* norm4 of the header: a matrix's four mantissas normalised on the largest of them */
+__device__ __forceinline__ void x_norm4(double2& r1, double2& r2, int& e)
+{
+    const double mx = fmax(fmax(fabs(r1.x), fabs(r1.y)), fmax(fabs(r2.x), fabs(r2.y)));
+    const int k = __builtin_amdgcn_frexp_exp(mx);
+    r1.x = __builtin_ldexp(r1.x, -k); r1.y = __builtin_ldexp(r1.y, -k);
+    r2.x = __builtin_ldexp(r2.x, -k); r2.y = __builtin_ldexp(r2.y, -k);
+    e = mx == 0.0 ? kXZero : e + k;
+}
+
+/* one entry while it is being merged: the rows of A and of B with their exponents, and r */
+struct ShipXLin {
+    double2 a1, a2, b1, b2;
+    int ea, eb;
+    double rv;
+    int re;
+};
+
+/* (v, e) < (w, f) on normalised extended reals; the zero's exponent FR_DEEPX_ZERO_EXP is below every other */
+__device__ __forceinline__ bool x_less(const double v, const int e, const double w, const int f)
+{
+    return e < f || (e == f && v < w);
+}
+
+/* The single step at the extended orbit point Z = (X, Y) 2^eZ: ship_single with the doubling in A's exponent, r = 2^-53 |norm(Z)|
+ * capped by |X| and |Y| as extended reals (a coordinate stored as 0 gives r = 0). */
+__device__ __forceinline__ ShipXLin shipx_single(const double2 Z, const int eZ)
+{
+    const double ax = fabs(Z.x), ay = fabs(Z.y);
+    const double sx = Z.x >= 0.0 ? 1.0 : -1.0, sy = Z.y >= 0.0 ? 1.0 : -1.0;
+    ShipXLin s;
+    s.a1 = make_double2(Z.x, -Z.y);
+    s.a2 = make_double2(ay * sx, ax * sy);
+    s.ea = eZ + 1;
+    x_norm4(s.a1, s.a2, s.ea);
+    s.b1 = make_double2(0.5, 0.0);
+    s.b2 = make_double2(0.0, 0.5);
+    s.eb = 1;
+    double nx = Z.x, ny = Z.y;
+    int ne = eZ;
+    x_norm(nx, ny, ne);
+    double rv = bla_abs(nx, ny);
+    int re = ne;
+    x_norm1(rv, re);
+    if (rv != 0.0) re -= 53;
+    double cv = ax;
+    int ce = eZ;
+    x_norm1(cv, ce);
+    if (!x_less(rv, re, cv, ce)) { rv = cv; re = ce; }
+    cv = ay; ce = eZ;
+    x_norm1(cv, ce);
+    if (!x_less(rv, re, cv, ce)) { rv = cv; re = ce; }
+    s.rv = rv; s.re = re;
+    return s;
+}
+
+/* Level k of the extended ship table: deep_ship_bla_level_kernel's products and norms in deepx_bla_level_kernel's arithmetic
+ * (t, the r < r_x rule, the void rule and the 24-bit cut of the stored radius are that kernel's). */
+__global__ void __launch_bounds__(kBlockThreads)
+deepx_ship_bla_level_kernel(const double2* __restrict__ mant, const int32_t* __restrict__ exp2, const int32_t n_ref,
+                            const int32_t k, const double dcv, const int32_t dce, XRad* __restrict__ r,
+                            double2* __restrict__ ab, int2* __restrict__ abe)
+{
+    const uint32_t n1 = (uint32_t)(n_ref - 1);
+    const uint32_t cnt = n1 >> k;
+    const uint32_t off = bla_offset(n1, k);
+    const uint32_t offp = k > 1 ? bla_offset(n1, k - 1) : 0u;
+    for (uint32_t j = blockIdx.x * kBlockThreads + threadIdx.x; j < cnt; j += gridDim.x * kBlockThreads) {
+        ShipXLin x, y;
+        if (k == 1) {
+            x = shipx_single(mant[1 + 2 * j], exp2[1 + 2 * j]);
+            y = shipx_single(mant[2 + 2 * j], exp2[2 + 2 * j]);
+        } else {
+            const uint32_t ex = offp + 2 * j, ey = ex + 1;
+            const int2 eex = abe[ex], eey = abe[ey];
+            const XRad rx = r[ex], ry = r[ey];
+            x.a1 = ab[4 * ex]; x.a2 = ab[4 * ex + 1]; x.b1 = ab[4 * ex + 2]; x.b2 = ab[4 * ex + 3];
+            x.ea = eex.x; x.eb = eex.y; x.rv = (double)rx.v; x.re = rx.e;
+            y.a1 = ab[4 * ey]; y.a2 = ab[4 * ey + 1]; y.b1 = ab[4 * ey + 2]; y.b2 = ab[4 * ey + 3];
+            y.ea = eey.x; y.eb = eey.y; y.rv = (double)ry.v; y.re = ry.e;
+        }
+        double2 a1 = make_double2(y.a1.x * x.a1.x + y.a1.y * x.a2.x, y.a1.x * x.a1.y + y.a1.y * x.a2.y);
+        double2 a2 = make_double2(y.a2.x * x.a1.x + y.a2.y * x.a2.x, y.a2.x * x.a1.y + y.a2.y * x.a2.y);
+        int ea = y.ea + x.ea;
+        x_norm4(a1, a2, ea);
+        const double2 p1 = make_double2(y.a1.x * x.b1.x + y.a1.y * x.b2.x, y.a1.x * x.b1.y + y.a1.y * x.b2.y);
+        const double2 p2 = make_double2(y.a2.x * x.b1.x + y.a2.y * x.b2.x, y.a2.x * x.b1.y + y.a2.y * x.b2.y);
+        const int e1 = y.ea + x.eb;
+        int eb = e1 > y.eb ? e1 : y.eb;
+        double2 b1 = make_double2(__builtin_ldexp(p1.x, e1 - eb) + __builtin_ldexp(y.b1.x, y.eb - eb),
+                                  __builtin_ldexp(p1.y, e1 - eb) + __builtin_ldexp(y.b1.y, y.eb - eb));
+        double2 b2 = make_double2(__builtin_ldexp(p2.x, e1 - eb) + __builtin_ldexp(y.b2.x, y.eb - eb),
+                                  __builtin_ldexp(p2.y, e1 - eb) + __builtin_ldexp(y.b2.y, y.eb - eb));
+        x_norm4(b1, b2, eb);
+        double bv = sqrt((x.b1.x * x.b1.x + x.b1.y * x.b1.y) + (x.b2.x * x.b2.x + x.b2.y * x.b2.y));
+        double av = bla_abs(x.a1.x, x.a2.x);
+        int be = x.eb, ae = x.ea;
+        x_norm1(bv, be);
+        x_norm1(av, ae);
+        const double pv = bv * dcv;
+        const int pe = be + dce;
+        const int et = y.re > pe ? y.re : pe;
+        const double t = (__builtin_ldexp(y.rv, y.re - et) - __builtin_ldexp(pv, pe - et)) / av;
+        double rv = (t > 0.0 && __builtin_isfinite(t)) ? t : 0.0;    /* NaN: 0 */
+        int re = et - ae;
+        x_norm1(rv, re);
+        if (!x_less(rv, re, x.rv, x.re)) { rv = x.rv; re = x.re; }
+        const int la = ea < 0 ? -ea : ea, lb = eb < 0 ? -eb : eb;
+        if (la > kXBlaExpLim || lb > kXBlaExpLim) {
+            rv = 0.0; re = kXZero;
+            a1 = make_double2(0.0, 0.0); a2 = a1; ea = kXZero;
+            b1 = a1; b2 = a1; eb = kXZero;
+        }
+        const uint32_t e = off + j;
+        XRad out;
+        out.v = (float)x_trunc24(rv); out.e = re;
+        r[e] = out;
+        ab[4 * e] = a1;
+        ab[4 * e + 1] = a2;
+        ab[4 * e + 2] = b1;
+        ab[4 * e + 3] = b2;
+        abe[e] = make_int2(ea, eb);
+    }
+}
+
+/* deep_orbit_ship_x with BLA: deep_orbit_x_bla's loop -- u for the loop index, its probe on the 8-byte radius with the
+ * pre-filter dz.e + 51 < E (no level's r exceeds the single step's 2^-53 |Z_m|: the fold caps only lower it), its reload of
+ * Z_m, Z_{m+1} in the mode a step leaves the lane in -- around the ship's steps: the BLA step is the real 2x2 map in extended
+ * arithmetic, its nine loads inside the taken branch; the single steps are deep_orbit_ship_x's, operation for operation. */
+__device__ __forceinline__ void deep_orbit_ship_x_bla(const DeepXArgs& AA, const ShipXBlaTable& T, const double cx,
+                                                      const double cy, const int ec, bool live, int& esc, double& er2,
+                                                      uint32_t& nsingle, uint32_t& nbla)
+{
+    const DeepArgs& A = AA.d;
+    const double2* __restrict__ orbit = A.orbit;
+    const double2* __restrict__ mant = AA.mant;
+    const int32_t* __restrict__ exp2 = AA.exp2;
+    const XRad* __restrict__ tr = T.r;
+    const int N = A.n_ref, max_iter = A.max_iter, K = T.levels;
+    const uint32_t n1 = (uint32_t)(N - 1);
+    const double B2 = A.B2;
+    const double cpx = (cx != 0.0 && __builtin_amdgcn_frexp_exp(cx) + ec > -1022) ? __builtin_ldexp(cx, ec) : 0.0;
+    const double cpy = (cy != 0.0 && __builtin_amdgcn_frexp_exp(cy) + ec > -1022) ? __builtin_ldexp(cy, ec) : 0.0;
+    double dzx = 0.0, dzy = 0.0;                                 /* plain: dz; extended: its mantissas */
+    int ed = kXZero;
+    bool ext = true;
+    double Zx = 0.0, Zy = 0.0;                                   /* Z_m, in the lane's mode */
+    int eZ = kXZero;
+    const double2 z1 = mant[1];
+    const int e1 = exp2[1];
+    double Znx = z1.x, Zny = z1.y;                               /* Z_{m+1} */
+    int eZn = e1;
+    int m = 0, u = 0;
+    esc = max_iter;
+    er2 = 0.0;
+    nsingle = 0u; nbla = 0u;
+    for (;;) {
+        if (__builtin_amdgcn_ballot_w64(live) == 0ull) break;
+        if (!live) continue;
+        const int mn = m + 2 <= N ? m + 2 : N;                   /* Z_{m+2}, for the single step after this one */
+        int k = 0;
+        uint32_t e = 0u;
+        double qx = dzx, qy = dzy;                               /* dz, extended and normalised */
+        int qe = ed;
+        if (m >= 1) {
+            if (!ext) { qe = 0; x_norm(qx, qy, qe); }
+            const int eZm = (ext ? eZ : 0) + __builtin_amdgcn_frexp_exp(fmax(fabs(Zx), fabs(Zy)));
+            if (qe + 51 < eZm) {
+                const double dz2 = qx * qx + qy * qy;
+                const uint32_t mm = (uint32_t)(m - 1);
+                int kk = mm ? __builtin_ctz(mm) : K;
+                kk = kk < K ? kk : K;
+                const int kn = 31 - __builtin_clz((uint32_t)(N - m));
+                const int ki = 31 - __builtin_clz((uint32_t)(max_iter - u));
+                kk = kk < kn ? kk : kn;
+                kk = kk < ki ? kk : ki;
+                for (; kk >= 1; --kk) {
+                    const uint32_t ek = bla_offset(n1, kk) + (mm >> kk);
+                    const XRad r = tr[ek];
+                    const double rv = (double)r.v;
+                    if (dz2 < __builtin_ldexp(rv * rv, 2 * (r.e - qe))) { k = kk; e = ek; break; }
+                }
+            }
+        }
+        double ax, ay;                                           /* the next dz */
+        int ea = 0;
+        bool reb;
+        if (k > 0 || ext) {
+            double nx, ny, Wx, Wy;                               /* n and Z at the new m */
+            int en, eW, eZnn = 0;
+            double2 Znn = make_double2(0.0, 0.0);
+            if (k > 0) {
+                const double2 a1 = T.ab[4 * e], a2 = T.ab[4 * e + 1], b1 = T.ab[4 * e + 2], b2 = T.ab[4 * e + 3];
+                const int2 ee = T.abe[e];
+                const double px = a1.x * qx + a1.y * qy, py = a2.x * qx + a2.y * qy;
+                const double sx = b1.x * cx + b1.y * cy, sy = b2.x * cx + b2.y * cy;
+                const int ep = ee.x + qe, es = ee.y + ec;
+                en = ep > es ? ep : es;
+                nx = __builtin_ldexp(px, ep - en) + __builtin_ldexp(sx, es - en);
+                ny = __builtin_ldexp(py, ep - en) + __builtin_ldexp(sy, es - en);
+                m += 1 << k;
+                u += 1 << k;
+                ++nbla;
+                const double2 Wm = mant[m];
+                Wx = Wm.x; Wy = Wm.y; eW = exp2[m];
+            } else {
+                Znn = mant[mn];
+                eZnn = exp2[mn];
+                const double fx = ship_fold_x(Zx, eZ - ed, dzx), fy = ship_fold_x(Zy, eZ - ed, dzy);
+                const int et = eZ + 1 > ed ? eZ + 1 : ed;
+                const double tx = __builtin_ldexp(fabs(Zx), eZ + 1 - et) + __builtin_ldexp(fx, ed - et);
+                const double ty = __builtin_ldexp(fabs(Zy), eZ + 1 - et) + __builtin_ldexp(fy, ed - et);
+                const double px = tx * fx - ty * fy;
+                const double py = tx * fy + ty * fx;
+                const int ep = et + ed;
+                en = ep > ec ? ep : ec;
+                nx = __builtin_ldexp(px, ep - en) + __builtin_ldexp(cx, ec - en);
+                ny = __builtin_ldexp(py, ep - en) + __builtin_ldexp(cy, ec - en);
+                ++m;
+                ++u;
+                ++nsingle;
+                Wx = Znx; Wy = Zny; eW = eZn;
+            }
+            const int ez = eW > en ? eW : en;
+            const double zx = __builtin_ldexp(Wx, eW - ez) + __builtin_ldexp(nx, en - ez);
+            const double zy = __builtin_ldexp(Wy, eW - ez) + __builtin_ldexp(ny, en - ez);
+            const double r2 = zx * zx + zy * zy;
+            const double r2d = __builtin_ldexp(r2, 2 * ez);
+            if (r2d > B2) {
+                esc = u - 1; er2 = r2d; live = false;             /* the last update the step covered */
+                continue;
+            }
+            reb = r2 < __builtin_ldexp(nx * nx + ny * ny, 2 * (en - ez)) || m == N;
+            ax = reb ? zx : nx; ay = reb ? zy : ny; ea = reb ? ez : en;
+            x_norm(ax, ay, ea);
+            if (reb) m = 0;
+            if (ea <= kXThr) {                                    /* extended from here */
+                dzx = ax; dzy = ay; ed = ea;
+                ext = true;
+                if (reb) {
+                    Zx = 0.0; Zy = 0.0; eZ = kXZero; Znx = z1.x; Zny = z1.y; eZn = e1;
+                } else if (k == 0) {
+                    Zx = Znx; Zy = Zny; eZ = eZn; Znx = Znn.x; Zny = Znn.y; eZn = eZnn;
+                } else {                                          /* m < N here */
+                    const double2 b = mant[m + 1];
+                    Zx = Wx; Zy = Wy; eZ = eW; Znx = b.x; Zny = b.y; eZn = exp2[m + 1];
+                }
+            } else {                                              /* plain from here (m < N) */
+                const double2 a = orbit[m], b = orbit[m + 1];
+                dzx = __builtin_ldexp(ax, ea); dzy = __builtin_ldexp(ay, ea);
+                ext = false;
+                Zx = a.x; Zy = a.y; Znx = b.x; Zny = b.y;
+            }
+        } else {
+            const double2 Znn = orbit[mn];
+            const double X2 = Zx + Zx, Y2 = Zy + Zy;
+            const double fx = ship_fold(Zx, X2, dzx), fy = ship_fold(Zy, Y2, dzy);
+            const double tx = fabs(X2) + fx, ty = fabs(Y2) + fy;     /* |X| + |X| = |X + X| */
+            const double nx = (tx * fx - ty * fy) + cpx;
+            const double ny = (tx * fy + ty * fx) + cpy;
+            ++m;
+            ++u;
+            ++nsingle;
+            const double zx = Znx + nx, zy = Zny + ny;
+            const double r2 = zx * zx + zy * zy;
+            if (r2 > B2) {
+                esc = u - 1; er2 = r2; live = false;
+                continue;
+            }
+            reb = r2 < nx * nx + ny * ny || m == N;
+            ax = reb ? zx : nx; ay = reb ? zy : ny;
+            if (reb) m = 0;
+            if (!(fmax(fabs(ax), fabs(ay)) < 0x1p-400)) {         /* stays plain */
+                dzx = ax; dzy = ay;
+                if (reb) {
+                    const double2 p1 = orbit[1];
+                    Zx = 0.0; Zy = 0.0; Znx = p1.x; Zny = p1.y;
+                } else {
+                    Zx = Znx; Zy = Zny; Znx = Znn.x; Zny = Znn.y;
+                }
+            } else {                                              /* turns extended (m < N) */
+                const double2 a = mant[m], b = mant[m + 1];
+                x_norm(ax, ay, ea);
+                dzx = ax; dzy = ay; ed = ea;
+                ext = true;
+                Zx = a.x; Zy = a.y; eZ = exp2[m]; Znx = b.x; Zny = b.y; eZn = exp2[m + 1];
+            }
+        }
+        if (u >= max_iter) live = false;                          /* esc stays max_iter */
+    }
+}
+
 __device__ __forceinline__ const DeepArgs& deep_args(const DeepArgs& A) { return A; }
 __device__ __forceinline__ const DeepArgs& deep_args(const DeepXArgs& A) { return A.d; }
 __device__ __forceinline__ const DeepArgs& deep_args(const DeepBlaArgs& A) { return A.d; }
@@ -1032,26 +1349,32 @@ __device__ __forceinline__ const DeepArgs& deep_args(const DeepXBlaArgs& A) { re
 __device__ __forceinline__ const DeepArgs& deep_args(const DeepShipArgs& A) { return A.d; }
 __device__ __forceinline__ const DeepArgs& deep_args(const DeepShipBlaArgs& A) { return A.s.d; }
 __device__ __forceinline__ const DeepArgs& deep_args(const DeepShipXArgs& A) { return A.x.d; }
+__device__ __forceinline__ const DeepArgs& deep_args(const DeepShipXBlaArgs& A) { return A.s.x.d; }
 __device__ __forceinline__ const DeepXArgs& deepx_args(const DeepXArgs& A) { return A; }
 __device__ __forceinline__ const DeepXArgs& deepx_args(const DeepXBlaArgs& A) { return A.x; }
+__device__ __forceinline__ const DeepXArgs& deepx_args(const DeepShipXArgs& A) { return A.x; }
+__device__ __forceinline__ const DeepXArgs& deepx_args(const DeepShipXBlaArgs& A) { return A.s.x; }
 __device__ __forceinline__ double ship_log_bailout(const DeepShipArgs& A) { return A.log_bailout; }
 __device__ __forceinline__ double ship_log_bailout(const DeepShipBlaArgs& A) { return A.s.log_bailout; }
 __device__ __forceinline__ double ship_log_bailout(const DeepShipXArgs& A) { return A.log_bailout; }
+__device__ __forceinline__ double ship_log_bailout(const DeepShipXBlaArgs& A) { return A.s.log_bailout; }
 
 /* deep_kernel<DeepArgs>: the plain step; deep_kernel<DeepBlaArgs>: with BLA (deep_orbit_bla, the step counts);
  * deep_kernel<DeepXArgs>: extended-exponent deltas (deep_orbit_x); deep_kernel<DeepXBlaArgs>: those with BLA
  * (deep_orbit_x_bla, the step counts); deep_kernel<DeepShipArgs>: the Burning Ship (deep_orbit_ship, its viewport map and
  * colour stage); deep_kernel<DeepShipBlaArgs>: the ship with BLA (deep_orbit_ship_bla, the step counts);
- * deep_kernel<DeepShipXArgs>: the ship with extended-exponent deltas (deep_orbit_ship_x, the ship's map and colour stage) */
+ * deep_kernel<DeepShipXArgs>: the ship with extended-exponent deltas (deep_orbit_ship_x, the ship's map and colour stage);
+ * deep_kernel<DeepShipXBlaArgs>: those with BLA (deep_orbit_ship_x_bla, the step counts) */
 template <class ARGS>
 __global__ void __launch_bounds__(kBlockThreads)
 deep_kernel(const ARGS AA)
 {
     constexpr bool XBLA = std::is_same<ARGS, DeepXBlaArgs>::value;
     constexpr bool SHIPBLA = std::is_same<ARGS, DeepShipBlaArgs>::value;
-    constexpr bool BLA = std::is_same<ARGS, DeepBlaArgs>::value || XBLA || SHIPBLA;
+    constexpr bool SHIPXBLA = std::is_same<ARGS, DeepShipXBlaArgs>::value;
+    constexpr bool BLA = std::is_same<ARGS, DeepBlaArgs>::value || XBLA || SHIPBLA || SHIPXBLA;
     constexpr bool X = std::is_same<ARGS, DeepXArgs>::value || XBLA;
-    constexpr bool SHIPX = std::is_same<ARGS, DeepShipXArgs>::value;
+    constexpr bool SHIPX = std::is_same<ARGS, DeepShipXArgs>::value || SHIPXBLA;
     constexpr bool SHIP = std::is_same<ARGS, DeepShipArgs>::value || SHIPBLA || SHIPX;
     constexpr int FRACTAL = SHIP ? 2 : 0;                         /* the colour stage: shade() / colour_of() */
     const DeepArgs& A = deep_args(AA);
@@ -1104,14 +1427,23 @@ deep_kernel(const ARGS AA)
                     uvy = uvy + ((double)uy * sample_offset - centre) / resy;
                 }
                 double zs = zoom;                                 /* extended: the zoom's mantissa, its exponent goes to dc.e */
-                if constexpr (SHIPX) zs = AA.x.zm;
+                if constexpr (SHIPX) zs = deepx_args(AA).zm;
                 const double sdx = (uvx - 0.5) * zs * (resx / resy);
                 const double sdy = (uvy - 0.5) * zs;
                 if constexpr (SHIPX) {
                     double cx = inside ? sdx : 0.0, cy = inside ? sdy : 0.0;
-                    int ec = AA.x.ze;
+                    int ec = deepx_args(AA).ze;
                     x_norm(cx, cy, ec);
-                    deep_orbit_ship_x(AA.x, cx, cy, ec, inside, esc, r2);
+                    if constexpr (SHIPXBLA) {
+                        uint32_t np, nb;
+                        deep_orbit_ship_x_bla(deepx_args(AA), AA.t, cx, cy, ec, inside, esc, r2, np, nb);
+                        if (inside) {
+                            n_plain += np; n_bla += nb;
+                            n_upd += (unsigned long long)(esc < A.max_iter ? esc + 1 : A.max_iter);
+                        }
+                    } else {
+                        deep_orbit_ship_x(deepx_args(AA), cx, cy, ec, inside, esc, r2);
+                    }
                 } else if constexpr (SHIPBLA) {
                     uint32_t np, nb;
                     deep_orbit_ship_bla(A, AA.t, inside ? sdx : 0.0, inside ? sdy : 0.0, z1, inside, esc, r2, np, nb);

@@ -165,6 +165,21 @@ struct fr_ctx {
     OrbitKey shipx_key;         /* of shipx_dev */
     int shipx_wg_per_cu;        /* resident workgroups per CU of deep_kernel<DeepShipXArgs> (0 = not asked yet) */
     uint64_t shipx_gen;         /* bumped whenever shipx_dev receives another orbit */
+    /* BLA for extended ship views (FR_FLAG_DEEPX_SHIP_BLA): the table of the cached extended ship orbit and the step counts of
+     * the most recent such render -- this path's own, nothing of it is shared with the three tables above */
+    XRad* shipx_bla_r;          /* r of every entry (shipx_bla_cap) */
+    double2* shipx_bla_ab;      /* the mantissa rows of A and of B of every entry (4 shipx_bla_cap) */
+    int2* shipx_bla_abe;        /* their exponents (shipx_bla_cap) */
+    size_t shipx_bla_cap;       /* entries */
+    bool shipx_bla_valid;       /* the key below describes the table */
+    uint64_t shipx_bla_key_gen, shipx_bla_key_dcv;   /* shipx_gen of its orbit, bits of dcmax's mantissa */
+    int32_t shipx_bla_key_dce;                       /* dcmax's exponent */
+    unsigned long long* shipx_bla_steps_dev;    /* the kernel's three counters */
+    unsigned long long* shipx_bla_steps_host;   /* pinned: their copy behind the most recent render with the flag */
+    bool have_shipx_bla_steps;
+    hipEvent_t ev_shipx_bla;    /* recorded behind every render with the flag (not while capturing): rebuilds wait for it */
+    bool ev_shipx_bla_valid;
+    int shipx_bla_wg_per_cu;    /* resident workgroups per CU of deep_kernel<DeepShipXBlaArgs> (0 = not asked yet) */
 };
 
 #define FR_HIP_TRY(expr)                                                               \
@@ -215,6 +230,7 @@ extern "C" int fr_ctx_create(int device_ordinal, fr_ctx** out)
         (e2 = hipEventCreateWithFlags(&c->ev_bla, hipEventDisableTiming)) != hipSuccess ||
         (e2 = hipEventCreateWithFlags(&c->ev_xbla, hipEventDisableTiming)) != hipSuccess ||
         (e2 = hipEventCreateWithFlags(&c->ev_ship_bla, hipEventDisableTiming)) != hipSuccess ||
+        (e2 = hipEventCreateWithFlags(&c->ev_shipx_bla, hipEventDisableTiming)) != hipSuccess ||
         (e2 = hipMalloc((void**)&c->d_ctrl, (kCtrlWords + (size_t)(kFeedbackShards + 2) * kShardStrideWords) * sizeof(uint32_t))) != hipSuccess ||
         (e2 = hipMemset(c->d_ctrl, 0, (kCtrlWords + (size_t)(kFeedbackShards + 2) * kShardStrideWords) * sizeof(uint32_t))) != hipSuccess ||
         (e2 = hipHostMalloc((void**)&c->overflow_host, 64, hipHostMallocMapped)) != hipSuccess ||
@@ -281,6 +297,12 @@ extern "C" void fr_ctx_destroy(fr_ctx* c)
     if (c->ship_bla_steps_dev) (void)hipFree(c->ship_bla_steps_dev);
     if (c->ship_bla_steps_host) (void)hipHostFree(c->ship_bla_steps_host);
     if (c->ev_ship_bla) (void)hipEventDestroy(c->ev_ship_bla);
+    if (c->shipx_bla_r) (void)hipFree(c->shipx_bla_r);
+    if (c->shipx_bla_ab) (void)hipFree(c->shipx_bla_ab);
+    if (c->shipx_bla_abe) (void)hipFree(c->shipx_bla_abe);
+    if (c->shipx_bla_steps_dev) (void)hipFree(c->shipx_bla_steps_dev);
+    if (c->shipx_bla_steps_host) (void)hipHostFree(c->shipx_bla_steps_host);
+    if (c->ev_shipx_bla) (void)hipEventDestroy(c->ev_shipx_bla);
     if (c->ev_begin) (void)hipEventDestroy(c->ev_begin);
     if (c->ev_end) (void)hipEventDestroy(c->ev_end);
     if (c->ev_order) (void)hipEventDestroy(c->ev_order);
@@ -1092,7 +1114,7 @@ static int enqueue_deep_ship(fr_ctx* c, const fr_params* p, const fr_deep_view* 
  * and the plain doubles ldexp(mantissa, exponent) formed here on the host, in one upload.
  *
  * One cache slot of extended orbits (OrbitSlot's counterpart): one pinned and one device block of cap points each, what they
- * hold, the host function that computes the orbit, and the event behind the slot's most recent BLA render (none: no BLA) */
+ * hold, the host function that computes the orbit, and the event behind the slot's most recent BLA render */
 struct XOrbitSlot {
     char*& host;
     char*& dev;
@@ -1104,8 +1126,6 @@ struct XOrbitSlot {
     hipEvent_t ev_bla;
     const bool& ev_bla_valid;
 };
-
-static const bool kNoBlaEvent = false;
 
 static int xorbit_slot_fill(fr_ctx* c, const XOrbitSlot& o, const fr_params* p, const fr_deepx_view* v, int32_t bits,
                             hipStream_t stream)
@@ -1159,7 +1179,7 @@ static int deepx_orbit_for(fr_ctx* c, const fr_params* p, const fr_deepx_view* v
 static int shipx_orbit_for(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, int32_t bits, hipStream_t stream)
 {
     const XOrbitSlot o = {c->shipx_host, c->shipx_dev, c->shipx_cap, c->shipx_len, c->shipx_key, c->shipx_gen,
-                          fr_deepx_ship_reference_orbit, nullptr, kNoBlaEvent};
+                          fr_deepx_ship_reference_orbit, c->ev_shipx_bla, c->ev_shipx_bla_valid};
     return xorbit_slot_fill(c, o, p, v, bits, stream);
 }
 
@@ -1287,7 +1307,97 @@ static int enqueue_deepx(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, 
 }
 
 /* ---- extended Burning Ship views (fr_render_deepx_ship) ------------------------------------------------------------------
- * enqueue_deepx_at on the extended ship slot and deep_kernel<DeepShipXArgs>: what fr_render_deepx_ship and the frames of a ship
+ * FR_FLAG_DEEPX_SHIP_BLA: the table of the cached extended ship orbit for this frame's dcmax (the ship's bound on the whole
+ * frame's W, H, as an extended real with the zoom pair), built on `stream` unless the context holds it -- deepx_bla_table_for's
+ * rules on this path's own buffers and event. */
+static int deepx_ship_bla_table_for(fr_ctx* c, const DeepXArgs& x, hipStream_t stream, int* levels)
+{
+    const int32_t N = c->shipx_len - 1;
+    const int K = N > 1 ? 31 - __builtin_clz((uint32_t)(N - 1)) : 0;   /* floor(log2(N - 1)) */
+    *levels = K;
+    if (K == 0) return FR_OK;
+    const double w = (double)x.d.g.W, h = (double)x.d.g.H;
+    const double a = w / h;
+    const double hx = 0.5 + 0.5 / (w * w);
+    const double hy = 0.5 + 0.5 / (w * h);
+    const double ex = hx * a;
+    int de = 0;
+    const double dv = frexp((1.0000001 * x.zm) * sqrt(ex * ex + hy * hy), &de);   /* normalised: dv in [0.5, 1) */
+    const int32_t dce = x.ze + de;
+    uint64_t dbits;
+    memcpy(&dbits, &dv, sizeof(dbits));
+    if (c->shipx_bla_valid && c->shipx_bla_key_gen == c->shipx_gen && c->shipx_bla_key_dcv == dbits &&
+        c->shipx_bla_key_dce == dce)
+        return FR_OK;
+    c->shipx_bla_valid = false;
+    const uint32_t n1 = (uint32_t)(N - 1);
+    const size_t need = (size_t)(n1 - (uint32_t)__builtin_popcount(n1));     /* sum over k >= 1 of (N - 1) >> k */
+    if (need > c->shipx_bla_cap) {
+        FR_HIP_TRY(hipStreamSynchronize(stream));
+        FR_HIP_TRY(hipStreamSynchronize(c->stream));
+        if (c->ev_shipx_bla_valid) FR_HIP_TRY(hipEventSynchronize(c->ev_shipx_bla));
+        if (c->shipx_bla_r) { (void)hipFree(c->shipx_bla_r); c->shipx_bla_r = nullptr; }
+        if (c->shipx_bla_ab) { (void)hipFree(c->shipx_bla_ab); c->shipx_bla_ab = nullptr; }
+        if (c->shipx_bla_abe) { (void)hipFree(c->shipx_bla_abe); c->shipx_bla_abe = nullptr; }
+        c->shipx_bla_cap = 0;
+        FR_HIP_TRY(hipMalloc((void**)&c->shipx_bla_r, need * sizeof(XRad)));
+        FR_HIP_TRY(hipMalloc((void**)&c->shipx_bla_ab, need * 4 * sizeof(double2)));
+        FR_HIP_TRY(hipMalloc((void**)&c->shipx_bla_abe, need * sizeof(int2)));
+        c->shipx_bla_cap = need;
+    } else if (c->ev_shipx_bla_valid) {
+        FR_HIP_TRY(hipStreamWaitEvent(stream, c->ev_shipx_bla, 0));
+    }
+    for (int k = 1; k <= K; ++k) {
+        const uint32_t cnt = n1 >> k;
+        uint32_t grid = (cnt + kBlockThreads - 1) / kBlockThreads;
+        const uint32_t cap = (uint32_t)c->compute_units * 8u;
+        if (grid > cap) grid = cap;
+        hipLaunchKernelGGL(deepx_ship_bla_level_kernel, dim3(grid), dim3(kBlockThreads), 0, stream, x.mant, x.exp2, N, k, dv, dce,
+                           c->shipx_bla_r, c->shipx_bla_ab, c->shipx_bla_abe);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return fr_set_error(FR_ERR_HIP, "extended ship BLA table launch failed: %s", hipGetErrorString(e));
+    }
+    c->shipx_bla_key_gen = c->shipx_gen;
+    c->shipx_bla_key_dcv = dbits;
+    c->shipx_bla_key_dce = dce;
+    c->shipx_bla_valid = true;
+    return FR_OK;
+}
+
+/* the table, then deep_kernel<DeepShipXBlaArgs> on the queue plan of deep_kernel<DeepShipXArgs> (its own occupancy), its
+ * counters cleared in front of it and copied to pinned memory behind it */
+static int enqueue_deepx_ship_bla(fr_ctx* c, const DeepShipXArgs& s, hipStream_t stream)
+{
+    DeepShipXBlaArgs a;
+    memset(&a, 0, sizeof(a));
+    a.s = s;
+    int levels = 0;
+    const int ts = deepx_ship_bla_table_for(c, s.x, stream, &levels);
+    if (ts != FR_OK) return ts;
+    a.t.r = c->shipx_bla_r; a.t.ab = c->shipx_bla_ab; a.t.abe = c->shipx_bla_abe; a.t.levels = levels;
+    if (!c->shipx_bla_steps_dev) {
+        FR_HIP_TRY(hipMalloc((void**)&c->shipx_bla_steps_dev, 3 * sizeof(unsigned long long)));
+        FR_HIP_TRY(hipHostMalloc((void**)&c->shipx_bla_steps_host, 3 * sizeof(unsigned long long)));
+    }
+    a.t.steps = c->shipx_bla_steps_dev;
+    FR_HIP_TRY(hipMemsetAsync(c->shipx_bla_steps_dev, 0, 3 * sizeof(unsigned long long), stream));
+    const int st = launch_one_pass(c, stream, "deep_kernel<DeepShipXBlaArgs>", deep_kernel<DeepShipXBlaArgs>, a, a.s.x.d.g,
+                                   a.s.x.d.q, c->shipx_bla_wg_per_cu, false);
+    if (st != FR_OK) return st;
+    FR_HIP_TRY(hipMemcpyAsync(c->shipx_bla_steps_host, c->shipx_bla_steps_dev, 3 * sizeof(unsigned long long),
+                              hipMemcpyDeviceToHost, stream));
+    c->have_shipx_bla_steps = true;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusActive; }
+    c->ev_shipx_bla_valid = false;
+    if (cap == hipStreamCaptureStatusNone) {
+        FR_HIP_TRY(hipEventRecord(c->ev_shipx_bla, stream));
+        c->ev_shipx_bla_valid = true;
+    }
+    return FR_OK;
+}
+
+/* enqueue_deepx_at on the extended ship slot and deep_kernel<DeepShipXArgs>: what fr_render_deepx_ship and the frames of a ship
  * sequence share */
 static int enqueue_deepx_ship_at(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, double zm, int32_t ze, int32_t bits,
                                  uint32_t W, uint32_t H, const fr_shard* shard, float* rgba, void* nu, int32_t* iter,
@@ -1312,6 +1422,7 @@ static int enqueue_deepx_ship_at(fr_ctx* c, const fr_params* p, const fr_deepx_v
     a.n_ref = c->shipx_len - 1;
     fill_deep_args(a, c, p, tile_geom(W, H, rows_local, &norm, out_frame), rgba, nu, iter);
     s.log_bailout = log((double)p->bailout);     /* as fill_params */
+    if (p->flags & FR_FLAG_DEEPX_SHIP_BLA) return enqueue_deepx_ship_bla(c, s, stream);
     return launch_one_pass(c, stream, "deep_kernel<DeepShipXArgs>", deep_kernel<DeepShipXArgs>, s, a.g, a.q, c->shipx_wg_per_cu,
                            false);
 }
@@ -1979,6 +2090,31 @@ extern "C" int64_t fr_deepx_bla_table(fr_ctx* c, void* r, double* ab, int32_t* a
     if (n > 0 && r) FR_HIP_TRY(hipMemcpy(r, c->xbla_r, (size_t)n * sizeof(XRad), hipMemcpyDeviceToHost));
     if (n > 0 && ab) FR_HIP_TRY(hipMemcpy(ab, c->xbla_ab, (size_t)n * 2 * sizeof(double2), hipMemcpyDeviceToHost));
     if (n > 0 && ab_exp) FR_HIP_TRY(hipMemcpy(ab_exp, c->xbla_abe, (size_t)n * sizeof(int2), hipMemcpyDeviceToHost));
+    return have;
+}
+
+extern "C" int fr_ctx_last_deepx_ship_steps(fr_ctx* c, uint64_t out[3])
+{
+    if (!c || !out) return fr_set_error(FR_ERR_INVALID_ARG, "ctx/out is NULL");
+    if (!c->have_shipx_bla_steps)
+        return fr_set_error(FR_ERR_UNSUPPORTED, "no fr_render_deepx_ship call with FR_FLAG_DEEPX_SHIP_BLA on this context yet");
+    for (int i = 0; i < 3; ++i) out[i] = (uint64_t)c->shipx_bla_steps_host[i];
+    return FR_OK;
+}
+
+extern "C" int64_t fr_deepx_ship_bla_table(fr_ctx* c, void* r, double* ab, int32_t* ab_exp, int64_t n)
+{
+    if (!c) return fr_set_error(FR_ERR_INVALID_ARG, "ctx is NULL");
+    if (!c->shipx_bla_valid) return 0;
+    const int32_t N = c->shipx_len - 1;
+    const uint32_t n1 = (uint32_t)(N - 1);
+    const int64_t have = (int64_t)(n1 - (uint32_t)__builtin_popcount(n1));
+    if (n > have) n = have;
+    FR_HIP_TRY(hipSetDevice(c->device));
+    FR_HIP_TRY(hipDeviceSynchronize());
+    if (n > 0 && r) FR_HIP_TRY(hipMemcpy(r, c->shipx_bla_r, (size_t)n * sizeof(XRad), hipMemcpyDeviceToHost));
+    if (n > 0 && ab) FR_HIP_TRY(hipMemcpy(ab, c->shipx_bla_ab, (size_t)n * 4 * sizeof(double2), hipMemcpyDeviceToHost));
+    if (n > 0 && ab_exp) FR_HIP_TRY(hipMemcpy(ab_exp, c->shipx_bla_abe, (size_t)n * sizeof(int2), hipMemcpyDeviceToHost));
     return have;
 }
 

@@ -40,7 +40,7 @@ int fr_deepx_validate_params(const fr_params* p, uint32_t width, uint32_t height
 int fr_deepx_check_centre(const char* center_x, const char* center_y, int32_t frac_bits);
 int fr_deepx_frac_bits_pair(double zm, int32_t ze);
 /* the validation of fr_render_deepx_ship (fr_deep.c): fr_deep_ship_validate's rules with the zoom from the view's string and
- * no BLA flag; _params is the part a caller with a resolved view shares */
+ * no BLA flag but the path's own, FR_FLAG_DEEPX_SHIP_BLA; _params is the part a caller with a resolved view shares */
 int fr_deepx_ship_validate(const fr_params* p, const fr_deepx_view* v, uint32_t width, uint32_t height);
 int fr_deepx_ship_validate_params(const fr_params* p, uint32_t width, uint32_t height);
 
@@ -69,6 +69,10 @@ int64_t fr_deepx_bla_table(fr_ctx* ctx, void* r, double* ab, int32_t* ab_exp, in
 /* tests: the ship's BLA table of the context (FR_FLAG_DEEP_SHIP_BLA), as fr_deep_bla_table: r[0 .. n) and ab[0 .. 8n)
  * (a11, a12, a21, a22, b11, b12, b21, b22 per entry), level after level.  Returns the entries it holds, 0 for none. */
 int64_t fr_deep_ship_bla_table(fr_ctx* ctx, double* r, double* ab, int64_t n);
+/* tests: the extended ship BLA table of the context (FR_FLAG_DEEPX_SHIP_BLA), as fr_deepx_bla_table: r receives n entries of 8
+ * bytes, ab 8 n doubles (the mantissas a11, a12, a21, a22, b11, b12, b21, b22 per entry), ab_exp 2 n int32 (A.e, B.e);
+ * NULL skips a part.  Returns the number of entries the table has (0: none). */
+int64_t fr_deepx_ship_bla_table(fr_ctx* ctx, void* r, double* ab, int32_t* ab_exp, int64_t n);
 
 /* the context's own stream (hipStream_t) and device ordinal: fr_node.cpp orders RCCL transfers behind the renders */
 void* fr_ctx_stream_handle(fr_ctx* ctx);

@@ -145,6 +145,13 @@ class Renderer:
         _capi.check(self._lib.fr_ctx_last_deep_ship_steps(self._ctx, out))
         return DeepSteps(int(out[0]), int(out[1]), int(out[2]))
 
+    def last_deepx_ship_steps(self) -> DeepSteps:
+        """fr_ctx_last_deepx_ship_steps: (single steps of both modes, BLA steps, updates skipped) of the most recent
+        render_deepx_ship(bla=True) or ship-sequence render with bla=True on this context, as last_deep_steps()."""
+        out = (C.c_uint64 * 3)()
+        _capi.check(self._lib.fr_ctx_last_deepx_ship_steps(self._ctx, out))
+        return DeepSteps(int(out[0]), int(out[1]), int(out[2]))
+
     def last_kernel_ms(self) -> float:
         return float(self._lib.fr_ctx_last_kernel_ms(self._ctx))
 
@@ -291,16 +298,19 @@ class Renderer:
 
     def render_deepx_ship(self, state: FractalState, width: int, height: int, view: DeepView, *, post_chain: bool = False,
                           rgba=None, nu=None, iter=None, shard: Optional[Shard] = None, stream: Optional[int] = None,
-                          sync: bool = True) -> None:
+                          sync: bool = True, bla: bool = False) -> None:
         """fr_render_deepx_ship / fr_render_deepx_ship_async: a Burning Ship view with extended-exponent deltas, zooms down to
         1e-1000.  `view` carries the centre and the zoom as decimal strings (DeepView(..., zoom="1e-400")); a view without a
         zoom string is a ValueError (render_deep_ship() takes those).  state.zoom and its double centre are not read; every
         other field comes from `state`.  Planes, shard, stream and sync as for render_deep_ship(); the context keeps this
-        path's orbit in a slot of its own.  There is no BLA for extended ship views."""
+        path's orbit in a slot of its own.  bla=True sets FR_FLAG_DEEPX_SHIP_BLA: iteration skipping with the ship's 2x2 maps in
+        extended arithmetic (the header's rules; last_deepx_ship_steps() reports what it skipped)."""
         if view is None or view.zoom is None:
             raise ValueError("render_deepx_ship needs a view with a zoom string (DeepView(..., zoom=\"1e-400\")); "
                              "render_deep_ship renders views without one")
         p = state.to_params(FractalType.BurningShip, Precision.F64, post_chain)
+        if bla:
+            p.flags |= _capi.FR_FLAG_DEEPX_SHIP_BLA
         vx = view.to_cx()
         rows = shard.rows(height) if shard else height
         self._render_call(self._lib.fr_render_deepx_ship, self._lib.fr_render_deepx_ship_async, (C.byref(p), C.byref(vx)), width,

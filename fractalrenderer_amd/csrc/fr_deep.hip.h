@@ -1,66 +1,49 @@
 /*
- * fr_deep.hip.h -- Mandelbrot views deeper than double precision on gfx950 (fr_render_deep): perturbation around one
- * reference orbit with rebasing.
+ * fr_deep.hip.h -- views deeper than double precision on gfx950: perturbation around one reference orbit with rebasing, for
+ * the Mandelbrot set (fr_render_deep, fr_render_deepx) and the Burning Ship (fr_render_deep_ship, fr_render_deepx_ship).
  *
  * The reference orbit Z_0 .. Z_N (fr_deep.c: fixed point on the host, stored as doubles) sits in HBM; every sample
- * iterates its fp64 delta dz = z - Z_m from it, dc being its offset from the centre:
+ * iterates its delta dz = z - Z_m from it, dc being its offset from the centre.  The Mandelbrot step:
  *   t = (Z_m + Z_m) + dz;  dz' = (t.x dz.x - t.y dz.y, t.x dz.y + t.y dz.x) + dc;  m += 1;  z = Z_m + dz';  r2 = |z|^2
  *   r2 > B2: escaped at this loop index;  r2 < |dz'|^2 or m == N: rebase, dz = z, m = 0;  else dz = dz'
  * one rounding per operation as written (the file is built with -ffp-contract=off).  The rebase restarts the sample on the
  * orbit's start whenever its delta has outgrown the orbit (|z| < |dz|) or the orbit ends, so one reference serves every
- * sample and no glitch can form.  How it runs (as the Phoenix kernel):
- *   - a persistent grid of the resident set pulls runs of 8x8 sub-tiles from the sharded WaveQueue with unlimited
- *     stealing (deep views have very uneven iteration counts);
- *   - one lane per sample; the aa x aa samples of a pixel run one after the other in the lane (mandelbrot.comp:219-230);
- *   - dz, dc, m and the loop index stay in registers.  Z_m and Z_{m+1} are in registers too, and Z_{m+2} is loaded one
- *     step ahead; Z_1 is loaded once, so a rebase (Z_m = Z_0 = 0, Z_{m+1} = Z_1) waits for no load.  While no lane of a
- *     wave has rebased, all 64 lanes read the same orbit point; after that they gather from different m;
- *   - smooth count, palette, interior style and the post chain are those of the fp64 Mandelbrot path: shade() and
+ * sample and no glitch can form.
+ *
+ * The shape of the file:
+ *   - two formula policies, MandelFormula and ShipFormula, hold everything that differs between the two recurrences and
+ *     nothing else: the linear part of the plain step (t, f) and of the extended step (U, f), the BLA step in fp64 and in
+ *     extended arithmetic with the loads of its own entry, the viewport map of a sample, the colour stage's index, and for
+ *     the table build the single step, the merge products, the two norms and the load and store of an entry.  The ship's
+ *     step is the Mandelbrot step on U = (|Z_m.x|, |Z_m.y|) and f = (fold(Z_m.x, dz.x), fold(Z_m.y, dz.y)), the fold a pair
+ *     of compares and selects; its BLA step is a real 2x2 map where Mandelbrot's is a complex product.
+ *   - four per-sample loops, each templated on the formula: deep_orbit (fp64 deltas), deep_orbit_bla (those with BLA),
+ *     deep_orbit_x (extended-exponent deltas, fr_render_deepx*), deep_orbit_x_bla (those with BLA).  The BLA loops count the
+ *     updates u a sample has covered, the others the loop index.  In all of them dz, dc, m and the count stay in registers;
+ *     Z_m and Z_{m+1} are in registers too and Z_{m+2} is loaded one step ahead; Z_1 is loaded once, so a rebase
+ *     (Z_m = Z_0 = 0, Z_{m+1} = Z_1) waits for no load.  While no lane of a wave has rebased, all 64 lanes read the same
+ *     orbit point; after that they gather from different m.
+ *   - extended-exponent deltas (the arithmetic is in the header): a lane is in one of two modes.  Plain: the fp64 step on
+ *     the plain doubles of the orbit.  Extended (max(|dz.x|, |dz.y|) < 2^-400): dz is two double mantissas and one int32
+ *     exponent, the orbit points come from the mantissa and exponent arrays, alignment is v_ldexp_f64, and the one
+ *     normalisation per step takes its exponent with v_frexp_exp_i32_f64 off max(|x|, |y|); the mode test is an integer
+ *     compare.  A lane that changes mode reloads Z_m and Z_{m+1} from the new mode's arrays.  The ship's extended step
+ *     takes the fold in the delta's frame (ship_fold_x).
+ *   - two level probes, bla_probe on the fp64 table and bla_probe_x on the extended one, each used by its BLA loop for both
+ *     formulas: top down from bla_top_level, the first level whose radius admits |dz|, behind a pre-filter that lets a lane
+ *     which cannot pass gather nothing.  A probe gathers 8 bytes; the chosen level's (A, B) are loaded inside the
+ *     taken-step branch only.
+ *   - two table builds, bla_level (fp64) and bla_level_x (extended), one launch per level: entry j of level k merges entries
+ *     2j and 2j + 1 of level k - 1, level 0 being the single steps, computed from the orbit and never stored.  The four
+ *     __global__ level kernels are these two with a formula.  The table stores, level after level (level k from entry
+ *     offset bla_offset(N - 1, k)), the radius r of every entry in an array of its own -- a double, or an XRad -- and
+ *     (A, B) as F::kAbPerEntry double2 per entry (2: complex A, B; 4: the rows of the ship's real matrices), the extended
+ *     tables with their two exponents in an int2.
+ *   - deep_kernel<ARGS>, one kernel body for the eight argument blocks: a persistent grid of the resident set pulls runs of
+ *     8x8 sub-tiles from the sharded WaveQueue with unlimited stealing (deep views have very uneven iteration counts); one
+ *     lane per sample, the aa x aa samples of a pixel one after the other in the lane; dc through the formula's viewport
+ *     map, one dispatch on (extended, BLA) to the loop, then the colour stage of the formula's fp64 path: shade() and
  *     post_chain() of fr_kernels.hip.h on (i, r2).
- *
- * Bilinear approximation (FR_FLAG_DEEP_BLA; the semantics are in the header): deep_bla_level_kernel builds the table from the
- * device orbit, one launch per level, and deep_kernel<DeepBlaArgs> runs deep_orbit_bla as its per-sample loop.  The
- * table stores, level after level (level k from entry offset bla_offset(N - 1, k)), the radius r of every entry in an
- * array of doubles of its own and (A, B) in an array of double2 pairs: a probe gathers 8 bytes, only the chosen level's
- * 32 bytes of (A, B) are loaded.
- *
- * Extended-exponent deltas (fr_render_deepx; the arithmetic is in the header): deep_kernel<DeepXArgs> runs deep_orbit_x as
- * its per-sample loop.  A lane is in one of two modes.  Plain: deep_orbit's step on the plain doubles of the orbit.
- * Extended (max(|dz.x|, |dz.y|) < 2^-400): dz is two double mantissas and one int32 exponent, the orbit points come from
- * the mantissa and exponent arrays, alignment is v_ldexp_f64, and the one normalisation per step takes its exponent with
- * v_frexp_exp_i32_f64 off max(|x|, |y|); the mode test is an integer compare.  Z_m and Z_{m+1} stay in registers in the
- * lane's mode and Z_{m+2} is fetched one step ahead from that mode's arrays; a lane that changes mode reloads both.
- *
- * BLA for extended views (FR_FLAG_DEEPX_BLA; the semantics are in the header): deepx_bla_level_kernel builds a table whose
- * (A, B, r) carry int32 exponents from the extended orbit arrays, one launch per level, and deep_kernel<DeepXBlaArgs> runs
- * deep_orbit_x_bla: deep_orbit_x whose lanes, in either mode, probe the table as deep_orbit_bla does and take a BLA step in
- * extended arithmetic.  A probe gathers 8 bytes (r as a float mantissa and an int32 exponent); the chosen level's A and B
- * are 32 bytes of mantissas and 8 bytes of exponents in arrays of their own.
- *
- * Deep Burning Ship views (fr_render_deep_ship; the step is in the header): deep_kernel<DeepShipArgs> runs deep_orbit_ship as
- * its per-sample loop -- deep_orbit on (|Z_m|, fold(Z_m, dz)), the fold a pair of compares and selects, with deep_orbit's
- * registers and prefetch.  The orbit is the ship's own (fr_deep.c), dc is the Burning Ship shader's viewport map less the
- * centre (sx outer), and the colour stage is that of the fp64 Burning Ship path: shade<double, 2>, interior samples
- * black, the post chain with the Julia / Burning Ship floors.
- *
- * BLA for the ship (FR_FLAG_DEEP_SHIP_BLA; the semantics are in the header): while no fold flips a sign the ship's step less
- * its square term is a real 2x2 map, 2 |Z_m| times a rotation or reflection.  deep_ship_bla_level_kernel builds the table
- * from the ship's device orbit, one launch per level -- r in an array of doubles of its own, the eight doubles of (A, B) as
- * four double2 per entry -- and deep_kernel<DeepShipBlaArgs> runs deep_orbit_ship_bla: deep_orbit_ship whose lanes probe
- * the table as deep_orbit_bla does.  A probe gathers 8 bytes, only the chosen level's 64 bytes of (A, B) are loaded.
- *
- * Extended Burning Ship views (fr_render_deepx_ship; the step is in the header): deep_kernel<DeepShipXArgs> runs
- * deep_orbit_ship_x -- deep_orbit_x's two modes, registers, prefetch and mode changes around the ship's step.  The plain mode
- * is deep_orbit_ship's step; the extended mode takes the fold in the delta's frame (ship_fold_x: the orbit coordinate brought
- * to the delta's exponent by v_ldexp_f64, the same compares and selects), so a coordinate far below its partner, or exactly 0
- * on the real axis, still folds the delta it meets.  The viewport map and the colour stage are the ship's.
- *
- * BLA for extended ship views (FR_FLAG_DEEPX_SHIP_BLA; the semantics are in the header): the ship's real 2x2 maps carried as
- * four mantissas with one shared int32 exponent.  deepx_ship_bla_level_kernel builds the table from the ship's extended
- * orbit, one launch per level -- r as an XRad in an array of its own, the eight mantissas of (A, B) as four double2 and their
- * two exponents as an int2 per entry -- and deep_kernel<DeepShipXBlaArgs> runs deep_orbit_ship_x_bla: deep_orbit_ship_x whose
- * lanes, in either mode, probe the table as deep_orbit_x_bla does and take a BLA step in extended arithmetic.  A probe
- * gathers 8 bytes; the chosen level's 72 bytes of (A, B) are loaded inside the taken-step branch only.
  */
 #pragma once
 #include "fr_kernels.hip.h"
@@ -88,12 +71,29 @@ struct DeepArgs {
     QueueArgs q;
 };
 
-/* The BLA table of the cached orbit (deep_kernel<DeepBlaArgs> only) */
+/* The fp64 BLA table of a cached orbit (FR_FLAG_DEEP_BLA, FR_FLAG_DEEP_SHIP_BLA) */
 struct BlaTable {
     const double* r;                     /* r of every entry, level 1 first */
-    const double2* ab;                   /* A, B of every entry: ab[2 e], ab[2 e + 1] */
+    const double2* ab;                   /* (A, B) of every entry: ab[n e .. n e + n - 1], n = F::kAbPerEntry */
     int32_t levels;                      /* K = floor(log2(N - 1)), 0 = no table */
     unsigned long long* steps;           /* plain steps, BLA steps, updates skipped: one atomic add each per wave */
+};
+
+/* The radius of an extended table's entry: the top 24 bits of its mantissa as a float and its int32 exponent -- the 8 bytes
+ * a probe gathers */
+struct XRad {
+    float v;                             /* mantissa in [0.5, 1), 0 for r = 0 */
+    int32_t e;                           /* FR_DEEPX_ZERO_EXP for r = 0 */
+};
+
+/* The extended BLA table of a cached extended orbit (FR_FLAG_DEEPX_BLA, FR_FLAG_DEEPX_SHIP_BLA): BlaTable with normalised
+ * mantissas in ab and the exponents apart */
+struct BlaXTable {
+    const XRad* r;                       /* r of every entry, level 1 first */
+    const double2* ab;                   /* mantissas of (A, B), laid out as BlaTable::ab */
+    const int2* abe;                     /* (A.e, B.e) */
+    int32_t levels;                      /* K = floor(log2(N - 1)), 0 = no table */
+    unsigned long long* steps;           /* single steps, BLA steps, updates skipped: one atomic add each per wave */
 };
 
 struct DeepBlaArgs {
@@ -101,12 +101,91 @@ struct DeepBlaArgs {
     BlaTable t;
 };
 
-/* Entries before level k (>= 1) of a table over n1 = N - 1 single steps: sum_{i=1}^{k-1} (n1 >> i).  With
- * S(x) = sum_{i>=1} (x >> i) = x - popcount(x) that is S(n1) - S(n1 >> (k - 1)). */
-__device__ __forceinline__ uint32_t bla_offset(const uint32_t n1, const int k)
+/* fr_render_deep_ship: d.orbit holds the Burning Ship orbit of the centre */
+struct DeepShipArgs {
+    DeepArgs d;
+    double log_bailout;                  /* log(bailout), for shade<double, 2> at bailout <= 1 (LaunchArgs::log_bailout) */
+};
+
+struct DeepShipBlaArgs {
+    DeepShipArgs s;
+    BlaTable t;
+};
+
+/* fr_render_deepx: d.orbit holds the plain doubles P_n, d.zoom is not read */
+struct DeepXArgs {
+    DeepArgs d;
+    const double2* mant;                 /* (mx, my) of Z_0 .. Z_N */
+    const int32_t* exp2;                 /* e of Z_0 .. Z_N */
+    double zm;                           /* zoom = zm 2^ze */
+    int32_t ze;
+};
+
+struct DeepXBlaArgs {
+    DeepXArgs x;
+    BlaXTable t;
+};
+
+/* fr_render_deepx_ship: x.d.orbit holds the plain doubles P_n of the ship's orbit, x.mant / x.exp2 its extended storage */
+struct DeepShipXArgs {
+    DeepXArgs x;
+    double log_bailout;                  /* as DeepShipArgs */
+};
+
+struct DeepShipXBlaArgs {
+    DeepShipXArgs s;
+    BlaXTable t;
+};
+
+constexpr int kXZero = FR_DEEPX_ZERO_EXP;
+constexpr int kXThr = -400;              /* extended while the normalised dz.e <= kXThr */
+constexpr int kXBlaExpLim = 1 << 27;     /* an entry whose A.e or B.e leaves [-2^27, 2^27] is void */
+
+/* ---- extended reals ----------------------------------------------------------------------------------------------------
+ * norm(x, y, e) of the header */
+__device__ __forceinline__ void x_norm(double& x, double& y, int& e)
 {
-    const uint32_t t = n1 >> (k - 1);
-    return (n1 - (uint32_t)__popc(n1)) - (t - (uint32_t)__popc(t));
+    const double mx = fmax(fabs(x), fabs(y));
+    const int k = __builtin_amdgcn_frexp_exp(mx);
+    x = __builtin_ldexp(x, -k);
+    y = __builtin_ldexp(y, -k);
+    e = mx == 0.0 ? kXZero : e + k;
+}
+
+/* an extended real normalised: v into [0.5, 1), zero gets FR_DEEPX_ZERO_EXP */
+__device__ __forceinline__ void x_norm1(double& v, int& e)
+{
+    const int k = __builtin_amdgcn_frexp_exp(v);
+    e = v == 0.0 ? kXZero : e + k;
+    v = __builtin_ldexp(v, -k);
+}
+
+/* norm4 of the header: a matrix's four mantissas normalised on the largest of them */
+__device__ __forceinline__ void x_norm4(double2& r1, double2& r2, int& e)
+{
+    const double mx = fmax(fmax(fabs(r1.x), fabs(r1.y)), fmax(fabs(r2.x), fabs(r2.y)));
+    const int k = __builtin_amdgcn_frexp_exp(mx);
+    r1.x = __builtin_ldexp(r1.x, -k); r1.y = __builtin_ldexp(r1.y, -k);
+    r2.x = __builtin_ldexp(r2.x, -k); r2.y = __builtin_ldexp(r2.y, -k);
+    e = mx == 0.0 ? kXZero : e + k;
+}
+
+/* (v, e) < (w, f) on normalised extended reals; the zero's exponent FR_DEEPX_ZERO_EXP is below every other */
+__device__ __forceinline__ bool x_less(const double v, const int e, const double w, const int f)
+{
+    return e < f || (e == f && v < w);
+}
+
+/* the top 24 bits of a mantissa in [0.5, 1) (toward zero): exactly a float */
+__device__ __forceinline__ double x_trunc24(const double v)
+{
+    return __longlong_as_double(__double_as_longlong(v) & ~((1ll << 29) - 1));
+}
+
+/* a component of the normalised dc = (cx, cy, ec) as the plain mode's double: below 2^-1022 it is 0 */
+__device__ __forceinline__ double x_plain(const double c, const int ec)
+{
+    return (c != 0.0 && __builtin_amdgcn_frexp_exp(c) + ec > -1022) ? __builtin_ldexp(c, ec) : 0.0;
 }
 
 /* |w| as the header writes it: sqrt(w.x*w.x + w.y*w.y).  On gfx950 sqrt(double) is LLVM's expansion of llvm.sqrt.f64:
@@ -115,44 +194,505 @@ __device__ __forceinline__ uint32_t bla_offset(const uint32_t n1, const int k)
  * every radius of device-built tables with numpy's bit for bit). */
 __device__ __forceinline__ double bla_abs(const double x, const double y) { return sqrt(x * x + y * y); }
 
-/* Level k of the table: entry j merges x (level k - 1, entry 2j) and y (level k - 1, entry 2j + 1); level 0 is the single
- * step at m = 1 + i (A = 2 Z_m, B = 1, r = 2^-53 |Z_m|), computed from the orbit and never stored. */
-__global__ void __launch_bounds__(kBlockThreads)
-deep_bla_level_kernel(const double2* __restrict__ orbit, const int32_t n_ref, const int32_t k, const double dcmax,
-                      double* __restrict__ r, double2* __restrict__ ab)
+/* |X + a| - |X| without the cancelling sum: the signs of X and of w = X + a (exact: an IEEE sum is zero only when it is
+ * exactly zero) pick a, -a or +-(2X + a).  X2 = X + X.  Compares and selects, no branch. */
+__device__ __forceinline__ double ship_fold(const double X, const double X2, const double a)
 {
+    const double w = X + a, d = X2 + a;
+    const double up = w >= 0.0 ? a : -d;
+    const double dn = w > 0.0 ? d : -a;
+    return X >= 0.0 ? up : dn;
+}
+
+/* fold_x of the header: ship_fold on an orbit mantissa X at exponent eZ and a delta mantissa a at exponent ed, s = eZ - ed,
+ * taken in the delta's frame -- the result is a mantissa at ed.  X far above the delta: the ldexp may give +-inf, w has X's
+ * sign, the select returns +-a and drops the infinite d.  X far below: Xs is 0 or a subnormal, below half an ulp of a. */
+__device__ __forceinline__ double ship_fold_x(const double X, const int s, const double a)
+{
+    const double Xs = __builtin_ldexp(X, s), X2s = __builtin_ldexp(X, s + 1);
+    const double w = Xs + a, d = X2s + a;
+    const double up = w >= 0.0 ? a : -d;
+    const double dn = w > 0.0 ? d : -a;
+    return X >= 0.0 ? up : dn;
+}
+
+/* ---- the formula policies ------------------------------------------------------------------------------------------------
+ * What a policy hands to the shared code, all by value (small structs in registers). */
+struct StepLin { double tx, ty, fx, fy; };          /* the plain step: dz' = t * f + dc, a complex product */
+struct StepLinX { double ux, uy, fx, fy; };         /* the extended step: t = (U, Z_m.e + 1) (+) (f, dz.e), dz' = t * f (+) dc */
+struct BlaStepX { double px, py, sx, sy; int ea, eb; };   /* a BLA step's A dz and B dc as mantissas, and (A.e, B.e) */
+
+/* an entry of a table while it is being merged: F::kAbPerEntry / 2 double2 each of A and of B, and r */
+template <int ROWS>
+struct BlaLin {
+    double2 a[ROWS], b[ROWS];
+    double r;
+};
+template <int ROWS>
+struct BlaLinX {
+    double2 a[ROWS], b[ROWS];
+    int ea, eb;
+    double rv;
+    int re;
+};
+
+/* z <- z^2 + c */
+struct MandelFormula {
+    static constexpr int kFractal = 0;                /* the colour stage: shade() / colour_of() */
+    static constexpr bool kLogBailoutLds = false;
+    static constexpr int kAbPerEntry = 2;             /* complex A, B */
+    using Lin = BlaLin<1>;
+    using LinX = BlaLinX<1>;
+
+    static __device__ __forceinline__ StepLin lin(const double Zx, const double Zy, const double dzx, const double dzy)
+    {
+        return {(Zx + Zx) + dzx, (Zy + Zy) + dzy, dzx, dzy};
+    }
+    static __device__ __forceinline__ StepLinX lin_x(const double Zx, const double Zy, const int eZ, const double dzx,
+                                                     const double dzy, const int ed)
+    {
+        return {Zx, Zy, dzx, dzy};
+    }
+    /* dz' = A dz + B dc, complex products */
+    static __device__ __forceinline__ double2 bla(const BlaTable& T, const uint32_t e, const double dzx,
+                                                  const double dzy, const double dcx, const double dcy)
+    {
+        const double2 a = T.ab[2 * e], b = T.ab[2 * e + 1];
+        return make_double2((a.x * dzx - a.y * dzy) + (b.x * dcx - b.y * dcy), (a.x * dzy + a.y * dzx) + (b.x * dcy + b.y * dcx));
+    }
+    static __device__ __forceinline__ BlaStepX bla_x(const BlaXTable& T, const uint32_t e, const double qx, const double qy,
+                                                     const double cx, const double cy)
+    {
+        const double2 a = T.ab[2 * e], b = T.ab[2 * e + 1];
+        const int2 ee = T.abe[e];
+        return {a.x * qx - a.y * qy, a.x * qy + a.y * qx, b.x * cx - b.y * cy, b.x * cy + b.y * cx, ee.x, ee.y};
+    }
+    /* mandelbrot.comp:219-230 (sy outer) and :149-151, less the centre; zs = the zoom or its mantissa */
+    static __device__ __forceinline__ double2 dc(const int px, const int py, const int s, const int aa, const double resx,
+                                                 const double resy, const double zs)
+    {
+        const int sy = s / aa, sx = s - sy * aa;
+        const double pxs = (double)px + (double)sx / (double)aa;
+        const double pys = (double)py + (double)sy / (double)aa;
+        return make_double2(((pxs - 0.5 * resx) / resy) * zs, ((pys - 0.5 * resy) / resy) * zs);
+    }
+
+    /* the table build.  The single step at Z_m: A = 2 Z_m, B = 1, r = 2^-53 |Z_m| */
+    static __device__ __forceinline__ Lin single(const double2 Z)
+    {
+        Lin s;
+        s.a[0] = make_double2(Z.x + Z.x, Z.y + Z.y);
+        s.b[0] = make_double2(1.0, 0.0);
+        s.r = 0x1p-53 * bla_abs(Z.x, Z.y);
+        return s;
+    }
+    /* A = norm(Z_m.x, Z_m.y, Z_m.e + 1), B = norm(1, 0, 0), r = 2^-53 |Z_m| */
+    static __device__ __forceinline__ LinX single_x(const double2 Z, const int eZ)
+    {
+        LinX s;
+        s.a[0] = Z; s.ea = eZ + 1;
+        x_norm(s.a[0].x, s.a[0].y, s.ea);
+        s.b[0] = make_double2(0.5, 0.0); s.eb = 1;
+        double nx = Z.x, ny = Z.y;
+        int ne = eZ;
+        x_norm(nx, ny, ne);
+        s.rv = bla_abs(nx, ny); s.re = ne;
+        x_norm1(s.rv, s.re);
+        if (s.rv != 0.0) s.re -= 53;
+        return s;
+    }
+    /* A_y A_x and A_y B_x (the caller adds B_y) */
+    template <class L>
+    static __device__ __forceinline__ void mul_a(const L& y, const L& x, double2* a)
+    {
+        a[0] = make_double2(y.a[0].x * x.a[0].x - y.a[0].y * x.a[0].y, y.a[0].x * x.a[0].y + y.a[0].y * x.a[0].x);
+    }
+    template <class L>
+    static __device__ __forceinline__ void mul_b(const L& y, const L& x, double2* p)
+    {
+        p[0] = make_double2(y.a[0].x * x.b[0].x - y.a[0].y * x.b[0].y, y.a[0].x * x.b[0].y + y.a[0].y * x.b[0].x);
+    }
+    template <class L>
+    static __device__ __forceinline__ double norm_a(const L& x) { return bla_abs(x.a[0].x, x.a[0].y); }
+    template <class L>
+    static __device__ __forceinline__ double norm_b(const L& x) { return bla_abs(x.b[0].x, x.b[0].y); }
+    static __device__ __forceinline__ void norm_rows(double2* m, int& e) { x_norm(m[0].x, m[0].y, e); }
+};
+
+/* z <- (|x| + i |y|)^2 + c */
+struct ShipFormula {
+    static constexpr int kFractal = 2;
+    static constexpr bool kLogBailoutLds = true;      /* shade<double, 2> at bailout <= 1 */
+    static constexpr int kAbPerEntry = 4;             /* the rows (a11, a12), (a21, a22), (b11, b12), (b21, b22) */
+    using Lin = BlaLin<2>;
+    using LinX = BlaLinX<2>;
+
+    static __device__ __forceinline__ StepLin lin(const double Zx, const double Zy, const double dzx, const double dzy)
+    {
+        const double X2 = Zx + Zx, Y2 = Zy + Zy;
+        const double fx = ship_fold(Zx, X2, dzx), fy = ship_fold(Zy, Y2, dzy);
+        return {fabs(X2) + fx, fabs(Y2) + fy, fx, fy};       /* |X| + |X| = |X + X| */
+    }
+    static __device__ __forceinline__ StepLinX lin_x(const double Zx, const double Zy, const int eZ, const double dzx,
+                                                     const double dzy, const int ed)
+    {
+        const double fx = ship_fold_x(Zx, eZ - ed, dzx), fy = ship_fold_x(Zy, eZ - ed, dzy);
+        return {fabs(Zx), fabs(Zy), fx, fy};
+    }
+    /* dz' = A dz + B dc, real 2x2 maps: valid while no fold flips a sign, which the radius guarantees */
+    static __device__ __forceinline__ double2 bla(const BlaTable& T, const uint32_t e, const double dzx,
+                                                  const double dzy, const double dcx, const double dcy)
+    {
+        const double2 a1 = T.ab[4 * e], a2 = T.ab[4 * e + 1], b1 = T.ab[4 * e + 2], b2 = T.ab[4 * e + 3];
+        return make_double2((a1.x * dzx + a1.y * dzy) + (b1.x * dcx + b1.y * dcy), (a2.x * dzx + a2.y * dzy) + (b2.x * dcx + b2.y * dcy));
+    }
+    static __device__ __forceinline__ BlaStepX bla_x(const BlaXTable& T, const uint32_t e, const double qx, const double qy,
+                                                     const double cx, const double cy)
+    {
+        const double2 a1 = T.ab[4 * e], a2 = T.ab[4 * e + 1], b1 = T.ab[4 * e + 2], b2 = T.ab[4 * e + 3];
+        const int2 ee = T.abe[e];
+        return {a1.x * qx + a1.y * qy, a2.x * qx + a2.y * qy, b1.x * cx + b1.y * cy, b2.x * cx + b2.y * cy, ee.x, ee.y};
+    }
+    /* the map of tile_kernel's Burning Ship path, less the centre (burning_ship.comp:337-344: sx outer) */
+    static __device__ __forceinline__ double2 dc(const int px, const int py, const int s, const int aa, const double resx,
+                                                 const double resy, const double zs)
+    {
+        const int ux = s / aa, uy = s - ux * aa;
+        double uvx = (double)px / resx, uvy = (double)py / resy;
+        if (aa > 1) {
+            const double pixel_size = 1.0 / resx;
+            const double sample_offset = pixel_size / (double)aa;
+            const double centre = sample_offset * (double)(aa - 1) * 0.5;
+            uvx = uvx + ((double)ux * sample_offset - centre) / resx;
+            uvy = uvy + ((double)uy * sample_offset - centre) / resy;
+        }
+        return make_double2((uvx - 0.5) * zs * (resx / resy), (uvy - 0.5) * zs);
+    }
+
+    /* the table build.  The single step at Z = (X, Y): A = [[2X, -2Y], [2|Y| sgn X, 2|X| sgn Y]], B = 1, r = 2^-53 |Z| capped
+     * by |X| and |Y| (the fold conditions: below them no fold flips a sign) */
+    static __device__ __forceinline__ Lin single(const double2 Z)
+    {
+        const double ax = fabs(Z.x), ay = fabs(Z.y);
+        const double sx = Z.x >= 0.0 ? 1.0 : -1.0, sy = Z.y >= 0.0 ? 1.0 : -1.0;
+        Lin s;
+        s.a[0] = make_double2(Z.x + Z.x, -(Z.y + Z.y));
+        s.a[1] = make_double2((ay + ay) * sx, (ax + ax) * sy);
+        s.b[0] = make_double2(1.0, 0.0);
+        s.b[1] = make_double2(0.0, 1.0);
+        double r = 0x1p-53 * bla_abs(Z.x, Z.y);
+        r = r < ax ? r : ax;
+        r = r < ay ? r : ay;
+        s.r = r;
+        return s;
+    }
+    /* single() with the doubling in A's exponent, r = 2^-53 |norm(Z)| capped by |X| and |Y| as extended reals (a coordinate
+     * stored as 0 gives r = 0) */
+    static __device__ __forceinline__ LinX single_x(const double2 Z, const int eZ)
+    {
+        const double ax = fabs(Z.x), ay = fabs(Z.y);
+        const double sx = Z.x >= 0.0 ? 1.0 : -1.0, sy = Z.y >= 0.0 ? 1.0 : -1.0;
+        LinX s;
+        s.a[0] = make_double2(Z.x, -Z.y);
+        s.a[1] = make_double2(ay * sx, ax * sy);
+        s.ea = eZ + 1;
+        x_norm4(s.a[0], s.a[1], s.ea);
+        s.b[0] = make_double2(0.5, 0.0);
+        s.b[1] = make_double2(0.0, 0.5);
+        s.eb = 1;
+        double nx = Z.x, ny = Z.y;
+        int ne = eZ;
+        x_norm(nx, ny, ne);
+        double rv = bla_abs(nx, ny);
+        int re = ne;
+        x_norm1(rv, re);
+        if (rv != 0.0) re -= 53;
+        double cv = ax;
+        int ce = eZ;
+        x_norm1(cv, ce);
+        if (!x_less(rv, re, cv, ce)) { rv = cv; re = ce; }
+        cv = ay; ce = eZ;
+        x_norm1(cv, ce);
+        if (!x_less(rv, re, cv, ce)) { rv = cv; re = ce; }
+        s.rv = rv; s.re = re;
+        return s;
+    }
+    /* A_y A_x and A_y B_x (the caller adds B_y), real 2x2 products */
+    template <class L>
+    static __device__ __forceinline__ void mul_a(const L& y, const L& x, double2* a)
+    {
+        a[0] = make_double2(y.a[0].x * x.a[0].x + y.a[0].y * x.a[1].x, y.a[0].x * x.a[0].y + y.a[0].y * x.a[1].y);
+        a[1] = make_double2(y.a[1].x * x.a[0].x + y.a[1].y * x.a[1].x, y.a[1].x * x.a[0].y + y.a[1].y * x.a[1].y);
+    }
+    template <class L>
+    static __device__ __forceinline__ void mul_b(const L& y, const L& x, double2* p)
+    {
+        p[0] = make_double2(y.a[0].x * x.b[0].x + y.a[0].y * x.b[1].x, y.a[0].x * x.b[0].y + y.a[0].y * x.b[1].y);
+        p[1] = make_double2(y.a[1].x * x.b[0].x + y.a[1].y * x.b[1].x, y.a[1].x * x.b[0].y + y.a[1].y * x.b[1].y);
+    }
+    /* |A_x| is the length of A_x's first column (A_x is a scaled orthogonal matrix: its operator norm), |B_x| the Frobenius
+     * norm */
+    template <class L>
+    static __device__ __forceinline__ double norm_a(const L& x) { return bla_abs(x.a[0].x, x.a[1].x); }
+    template <class L>
+    static __device__ __forceinline__ double norm_b(const L& x)
+    {
+        return sqrt((x.b[0].x * x.b[0].x + x.b[0].y * x.b[0].y) + (x.b[1].x * x.b[1].x + x.b[1].y * x.b[1].y));
+    }
+    static __device__ __forceinline__ void norm_rows(double2* m, int& e) { x_norm4(m[0], m[1], e); }
+};
+
+/* ---- the steps ---------------------------------------------------------------------------------------------------------
+ * The plain step: dz' from (Z_m, dz, dc) */
+template <class F>
+__device__ __forceinline__ double2 deep_step(const double Zx, const double Zy, const double dzx, const double dzy,
+                                             const double dcx, const double dcy)
+{
+    const StepLin l = F::lin(Zx, Zy, dzx, dzy);
+    return make_double2((l.tx * l.fx - l.ty * l.fy) + dcx, (l.tx * l.fy + l.ty * l.fx) + dcy);
+}
+
+/* The extended step (the header's EXTENDED step): dz' = (n.x, n.y, en), not normalised */
+template <class F>
+__device__ __forceinline__ double2 deep_step_x(const double Zx, const double Zy, const int eZ, const double dzx,
+                                               const double dzy, const int ed, const double cx, const double cy, const int ec,
+                                               int& en)
+{
+    const StepLinX l = F::lin_x(Zx, Zy, eZ, dzx, dzy, ed);
+    const int et = eZ + 1 > ed ? eZ + 1 : ed;
+    const double tx = __builtin_ldexp(l.ux, eZ + 1 - et) + __builtin_ldexp(l.fx, ed - et);
+    const double ty = __builtin_ldexp(l.uy, eZ + 1 - et) + __builtin_ldexp(l.fy, ed - et);
+    const double px = tx * l.fx - ty * l.fy;
+    const double py = tx * l.fy + ty * l.fx;
+    const int ep = et + ed;
+    en = ep > ec ? ep : ec;
+    return make_double2(__builtin_ldexp(px, ep - en) + __builtin_ldexp(cx, ec - en),
+                        __builtin_ldexp(py, ep - en) + __builtin_ldexp(cy, ec - en));
+}
+
+/* ---- the tables --------------------------------------------------------------------------------------------------------
+ * Entries before level k (>= 1) of a table over n1 = N - 1 single steps: sum_{i=1}^{k-1} (n1 >> i).  With
+ * S(x) = sum_{i>=1} (x >> i) = x - popcount(x) that is S(n1) - S(n1 >> (k - 1)). */
+__device__ __forceinline__ uint32_t bla_offset(const uint32_t n1, const int k)
+{
+    const uint32_t t = n1 >> (k - 1);
+    return (n1 - (uint32_t)__popc(n1)) - (t - (uint32_t)__popc(t));
+}
+
+/* Level k of an fp64 table: entry j merges x (level k - 1, entry 2j) and y (level k - 1, entry 2j + 1); level 0 is the single
+ * step at m = 1 + i, computed from the orbit and never stored.  A = A_y A_x, B = A_y B_x + B_y,
+ * r = min(r_x, max(0, (r_y - |B_x| dcmax) / |A_x|)), 0 when an element is not finite. */
+template <class F>
+__device__ __forceinline__ void bla_level(const double2* __restrict__ orbit, const int32_t n_ref, const int32_t k,
+                                          const double dcmax, double* __restrict__ r, double2* __restrict__ ab)
+{
+    constexpr int R = F::kAbPerEntry / 2;
     const uint32_t n1 = (uint32_t)(n_ref - 1);
     const uint32_t cnt = n1 >> k;
     const uint32_t off = bla_offset(n1, k);
     const uint32_t offp = k > 1 ? bla_offset(n1, k - 1) : 0u;
     for (uint32_t j = blockIdx.x * kBlockThreads + threadIdx.x; j < cnt; j += gridDim.x * kBlockThreads) {
-        double2 ax, bx, ay, by;
-        double rx, ry;
+        typename F::Lin x, y;
         if (k == 1) {
-            const double2 zx = orbit[1 + 2 * j], zy = orbit[2 + 2 * j];
-            ax = make_double2(zx.x + zx.x, zx.y + zx.y); bx = make_double2(1.0, 0.0); rx = 0x1p-53 * bla_abs(zx.x, zx.y);
-            ay = make_double2(zy.x + zy.x, zy.y + zy.y); by = make_double2(1.0, 0.0); ry = 0x1p-53 * bla_abs(zy.x, zy.y);
+            x = F::single(orbit[1 + 2 * j]);
+            y = F::single(orbit[2 + 2 * j]);
         } else {
             const uint32_t ex = offp + 2 * j, ey = ex + 1;
-            ax = ab[2 * ex]; bx = ab[2 * ex + 1]; rx = r[ex];
-            ay = ab[2 * ey]; by = ab[2 * ey + 1]; ry = r[ey];
+            for (int i = 0; i < R; ++i) { x.a[i] = ab[2 * R * ex + i]; x.b[i] = ab[2 * R * ex + R + i]; }
+            x.r = r[ex];
+            for (int i = 0; i < R; ++i) { y.a[i] = ab[2 * R * ey + i]; y.b[i] = ab[2 * R * ey + R + i]; }
+            y.r = r[ey];
         }
-        const double2 a = make_double2(ay.x * ax.x - ay.y * ax.y, ay.x * ax.y + ay.y * ax.x);
-        const double2 b = make_double2((ay.x * bx.x - ay.y * bx.y) + by.x, (ay.x * bx.y + ay.y * bx.x) + by.y);
-        const double t = (ry - bla_abs(bx.x, bx.y) * dcmax) / bla_abs(ax.x, ax.y);
+        double2 a[R], b[R];
+        F::mul_a(y, x, a);
+        F::mul_b(y, x, b);
+        bool finite = true;
+        for (int i = 0; i < R; ++i) {
+            b[i] = make_double2(b[i].x + y.b[i].x, b[i].y + y.b[i].y);
+            finite = finite && __builtin_isfinite(a[i].x) && __builtin_isfinite(a[i].y) && __builtin_isfinite(b[i].x) &&
+                     __builtin_isfinite(b[i].y);
+        }
+        const double t = (y.r - F::norm_b(x) * dcmax) / F::norm_a(x);
         double rr = t > 0.0 ? t : 0.0;                           /* NaN: 0 */
-        rr = rr < rx ? rr : rx;
-        if (!(__builtin_isfinite(a.x) && __builtin_isfinite(a.y) && __builtin_isfinite(b.x) && __builtin_isfinite(b.y)))
-            rr = 0.0;
+        rr = rr < x.r ? rr : x.r;
+        if (!finite) rr = 0.0;
         const uint32_t e = off + j;
         r[e] = rr;
-        ab[2 * e] = a;
-        ab[2 * e + 1] = b;
+        for (int i = 0; i < R; ++i) { ab[2 * R * e + i] = a[i]; ab[2 * R * e + R + i] = b[i]; }
     }
 }
 
-/* The wave's 64 samples, one per lane.  live = false: a lane without a sample (outside the frame).  esc = the loop index
- * of the escaping update (max_iter if none), r2 = |z|^2 there. */
+/* Level k of an extended table: bla_level with (A, B, r) carrying int32 exponents, from the extended orbit arrays.  An entry
+ * whose A.e or B.e leaves [-2^27, 2^27] is void (all zero); the stored radius is cut to 24 bits. */
+template <class F>
+__device__ __forceinline__ void bla_level_x(const double2* __restrict__ mant, const int32_t* __restrict__ exp2,
+                                            const int32_t n_ref, const int32_t k, const double dcv, const int32_t dce,
+                                            XRad* __restrict__ r, double2* __restrict__ ab, int2* __restrict__ abe)
+{
+    constexpr int R = F::kAbPerEntry / 2;
+    const uint32_t n1 = (uint32_t)(n_ref - 1);
+    const uint32_t cnt = n1 >> k;
+    const uint32_t off = bla_offset(n1, k);
+    const uint32_t offp = k > 1 ? bla_offset(n1, k - 1) : 0u;
+    for (uint32_t j = blockIdx.x * kBlockThreads + threadIdx.x; j < cnt; j += gridDim.x * kBlockThreads) {
+        typename F::LinX x, y;
+        if (k == 1) {
+            x = F::single_x(mant[1 + 2 * j], exp2[1 + 2 * j]);
+            y = F::single_x(mant[2 + 2 * j], exp2[2 + 2 * j]);
+        } else {
+            const uint32_t ex = offp + 2 * j, ey = ex + 1;
+            const int2 eex = abe[ex], eey = abe[ey];
+            const XRad rx = r[ex], ry = r[ey];
+            for (int i = 0; i < R; ++i) { x.a[i] = ab[2 * R * ex + i]; x.b[i] = ab[2 * R * ex + R + i]; }
+            x.ea = eex.x; x.eb = eex.y; x.rv = (double)rx.v; x.re = rx.e;
+            for (int i = 0; i < R; ++i) { y.a[i] = ab[2 * R * ey + i]; y.b[i] = ab[2 * R * ey + R + i]; }
+            y.ea = eey.x; y.eb = eey.y; y.rv = (double)ry.v; y.re = ry.e;
+        }
+        double2 a[R], p[R], b[R];
+        F::mul_a(y, x, a);
+        int ea = y.ea + x.ea;
+        F::norm_rows(a, ea);
+        F::mul_b(y, x, p);
+        const int e1 = y.ea + x.eb;
+        int eb = e1 > y.eb ? e1 : y.eb;
+        for (int i = 0; i < R; ++i)
+            b[i] = make_double2(__builtin_ldexp(p[i].x, e1 - eb) + __builtin_ldexp(y.b[i].x, y.eb - eb),
+                                __builtin_ldexp(p[i].y, e1 - eb) + __builtin_ldexp(y.b[i].y, y.eb - eb));
+        F::norm_rows(b, eb);
+        double bv = F::norm_b(x), av = F::norm_a(x);
+        int be = x.eb, ae = x.ea;
+        x_norm1(bv, be);
+        x_norm1(av, ae);
+        const double pv = bv * dcv;
+        const int pe = be + dce;
+        const int et = y.re > pe ? y.re : pe;
+        const double t = (__builtin_ldexp(y.rv, y.re - et) - __builtin_ldexp(pv, pe - et)) / av;
+        double rv = (t > 0.0 && __builtin_isfinite(t)) ? t : 0.0;    /* NaN: 0 */
+        int re = et - ae;
+        x_norm1(rv, re);
+        if (!x_less(rv, re, x.rv, x.re)) { rv = x.rv; re = x.re; }
+        const int la = ea < 0 ? -ea : ea, lb = eb < 0 ? -eb : eb;
+        if (la > kXBlaExpLim || lb > kXBlaExpLim) {
+            rv = 0.0; re = kXZero;
+            for (int i = 0; i < R; ++i) { a[i] = make_double2(0.0, 0.0); b[i] = make_double2(0.0, 0.0); }
+            ea = kXZero; eb = kXZero;
+        }
+        const uint32_t e = off + j;
+        XRad out;
+        out.v = (float)x_trunc24(rv); out.e = re;
+        r[e] = out;
+        for (int i = 0; i < R; ++i) { ab[2 * R * e + i] = a[i]; ab[2 * R * e + R + i] = b[i]; }
+        abe[e] = make_int2(ea, eb);
+    }
+}
+
+__global__ void __launch_bounds__(kBlockThreads)
+deep_bla_level_kernel(const double2* __restrict__ orbit, const int32_t n_ref, const int32_t k, const double dcmax,
+                      double* __restrict__ r, double2* __restrict__ ab)
+{
+    bla_level<MandelFormula>(orbit, n_ref, k, dcmax, r, ab);
+}
+
+__global__ void __launch_bounds__(kBlockThreads)
+deep_ship_bla_level_kernel(const double2* __restrict__ orbit, const int32_t n_ref, const int32_t k, const double dcmax,
+                           double* __restrict__ r, double2* __restrict__ ab)
+{
+    bla_level<ShipFormula>(orbit, n_ref, k, dcmax, r, ab);
+}
+
+__global__ void __launch_bounds__(kBlockThreads)
+deepx_bla_level_kernel(const double2* __restrict__ mant, const int32_t* __restrict__ exp2, const int32_t n_ref, const int32_t k,
+                       const double dcv, const int32_t dce, XRad* __restrict__ r, double2* __restrict__ ab,
+                       int2* __restrict__ abe)
+{
+    bla_level_x<MandelFormula>(mant, exp2, n_ref, k, dcv, dce, r, ab, abe);
+}
+
+__global__ void __launch_bounds__(kBlockThreads)
+deepx_ship_bla_level_kernel(const double2* __restrict__ mant, const int32_t* __restrict__ exp2, const int32_t n_ref,
+                            const int32_t k, const double dcv, const int32_t dce, XRad* __restrict__ r,
+                            double2* __restrict__ ab, int2* __restrict__ abe)
+{
+    bla_level_x<ShipFormula>(mant, exp2, n_ref, k, dcv, dce, r, ab, abe);
+}
+
+/* ---- the level probes --------------------------------------------------------------------------------------------------
+ * The level a lane at m >= 1 with u updates behind it probes first: min(ctz(m - 1), K, floor(log2(N - m)),
+ * floor(log2(max_iter - u))) */
+__device__ __forceinline__ int bla_top_level(const uint32_t mm, const int K, const int N, const int m, const int max_iter,
+                                             const int u)
+{
+    int kk = mm ? __builtin_ctz(mm) : K;
+    kk = kk < K ? kk : K;
+    const int kn = 31 - __builtin_clz((uint32_t)(N - m));
+    const int ki = 31 - __builtin_clz((uint32_t)(max_iter - u));
+    kk = kk < kn ? kk : kn;
+    kk = kk < ki ? kk : ki;
+    return kk;
+}
+
+struct BlaHit {
+    int k;                               /* the level taken, 0 = none */
+    uint32_t e;                          /* its entry */
+};
+
+/* The fp64 probe: the levels top down, the first k with |dz|^2 < r^2.  No level's r exceeds the single step's 2^-53 |Z_m| (r
+ * only ever shrinks in the merge, the ship's fold caps only lower it), so a lane with |dz|^2 2^104 >= |Z_m|^2 (a bound above
+ * 2^-106 |Z_m|^2 with room for every rounding) cannot pass a probe and gathers nothing. */
+__device__ __forceinline__ BlaHit bla_probe(const double* tr, const uint32_t n1, const int K, const int N,
+                                            const int max_iter, const int m, const int u, const double dz2, const double Zx,
+                                            const double Zy)
+{
+    BlaHit h = {0, 0u};
+    if (m >= 1 && dz2 * 0x1p104 < Zx * Zx + Zy * Zy) {
+        const uint32_t mm = (uint32_t)(m - 1);
+        for (int kk = bla_top_level(mm, K, N, m, max_iter, u); kk >= 1; --kk) {
+            const uint32_t ek = bla_offset(n1, kk) + (mm >> kk);
+            const double r = tr[ek];
+            if (dz2 < r * r) { h.k = kk; h.e = ek; break; }
+        }
+    }
+    return h;
+}
+
+struct BlaHitX {
+    int k;
+    uint32_t e;
+    double qx, qy;                       /* dz, extended and normalised */
+    int qe;
+};
+
+/* The extended probe, for a lane in either mode: on its dz as a normalised extended number (a plain lane forms
+ * norm(dz.x, dz.y, 0)).  No level's r exceeds 2^-53 |Z_m| < 2^(E - 52.5), E the exponent of Z_m's larger component normalised,
+ * and |dz| >= 2^(dz.e - 1): a lane with dz.e + 51 >= E cannot pass a probe and gathers nothing (E from the lane's own copy of
+ * Z_m: for a point below 2^-1022 the plain double's exponent is never below the true one). */
+__device__ __forceinline__ BlaHitX bla_probe_x(const XRad* tr, const uint32_t n1, const int K, const int N,
+                                               const int max_iter, const int m, const int u, const bool ext, const double dzx,
+                                               const double dzy, const int ed, const double Zx, const double Zy, const int eZ)
+{
+    BlaHitX h = {0, 0u, dzx, dzy, ed};
+    if (m >= 1) {
+        if (!ext) { h.qe = 0; x_norm(h.qx, h.qy, h.qe); }
+        const int eZm = (ext ? eZ : 0) + __builtin_amdgcn_frexp_exp(fmax(fabs(Zx), fabs(Zy)));
+        if (h.qe + 51 < eZm) {
+            const double dz2 = h.qx * h.qx + h.qy * h.qy;
+            const uint32_t mm = (uint32_t)(m - 1);
+            for (int kk = bla_top_level(mm, K, N, m, max_iter, u); kk >= 1; --kk) {
+                const uint32_t ek = bla_offset(n1, kk) + (mm >> kk);
+                const XRad r = tr[ek];
+                const double rv = (double)r.v;
+                if (dz2 < __builtin_ldexp(rv * rv, 2 * (r.e - h.qe))) { h.k = kk; h.e = ek; break; }
+            }
+        }
+    }
+    return h;
+}
+
+/* ---- the per-sample loops ----------------------------------------------------------------------------------------------
+ * The wave's 64 samples, one per lane.  live = false: a lane without a sample (outside the frame).  esc = the loop index
+ * of the escaping update (max_iter if none), r2 = |z|^2 there.  z = Z_{m+1} + dz' with the signed orbit point for either
+ * formula (Z_0 = 0: at m = 0 the ship's step is (|dz.x| + i |dz.y|)^2 + dc). */
+template <class F>
 __device__ __forceinline__ void deep_orbit(const DeepArgs& A, const double dcx, const double dcy, const double2 z1,
                                            bool live, int& esc, double& er2)
 {
@@ -169,9 +709,8 @@ __device__ __forceinline__ void deep_orbit(const DeepArgs& A, const double dcx, 
         if (__builtin_amdgcn_ballot_w64(live) == 0ull) break;
         if (!live) continue;
         const double2 Znn = orbit[m + 2 <= N ? m + 2 : N];      /* Z_{m+2}, for the next step (m + 1 < N) */
-        const double tx = (Zx + Zx) + dzx, ty = (Zy + Zy) + dzy;
-        const double nx = (tx * dzx - ty * dzy) + dcx;
-        const double ny = (tx * dzy + ty * dzx) + dcy;
+        const double2 n = deep_step<F>(Zx, Zy, dzx, dzy, dcx, dcy);
+        const double nx = n.x, ny = n.y;
         ++m;
         const double zx = Znx + nx, zy = Zny + ny;
         const double r2 = zx * zx + zy * zy;
@@ -187,67 +726,10 @@ __device__ __forceinline__ void deep_orbit(const DeepArgs& A, const double dcx, 
     }
 }
 
-/* fr_render_deep_ship: d.orbit holds the Burning Ship orbit of the centre */
-struct DeepShipArgs {
-    DeepArgs d;
-    double log_bailout;                  /* log(bailout), for shade<double, 2> at bailout <= 1 (LaunchArgs::log_bailout) */
-};
-
-/* |X + a| - |X| without the cancelling sum: the signs of X and of w = X + a (exact: an IEEE sum is zero only when it is
- * exactly zero) pick a, -a or +-(2X + a).  X2 = X + X.  Compares and selects, no branch. */
-__device__ __forceinline__ double ship_fold(const double X, const double X2, const double a)
-{
-    const double w = X + a, d = X2 + a;
-    const double up = w >= 0.0 ? a : -d;
-    const double dn = w > 0.0 ? d : -a;
-    return X >= 0.0 ? up : dn;
-}
-
-/* deep_orbit for z <- (|x| + i |y|)^2 + c: the same step on U = (|Z_m.x|, |Z_m.y|) and f = (fold(Z_m.x, dz.x),
- * fold(Z_m.y, dz.y)); z = Z_{m+1} + dz' with the signed orbit point, escape and rebase as there (Z_0 = 0: at m = 0 the
- * step is (|dz.x| + i |dz.y|)^2 + dc). */
-__device__ __forceinline__ void deep_orbit_ship(const DeepArgs& A, const double dcx, const double dcy, const double2 z1,
-                                                bool live, int& esc, double& er2)
-{
-    const double2* __restrict__ orbit = A.orbit;
-    const int N = A.n_ref, max_iter = A.max_iter;
-    const double B2 = A.B2;
-    double dzx = 0.0, dzy = 0.0;
-    double Zx = 0.0, Zy = 0.0;                                   /* Z_m */
-    double Znx = z1.x, Zny = z1.y;                               /* Z_{m+1} */
-    int m = 0;
-    esc = max_iter;
-    er2 = 0.0;
-    for (int i = 0; i < max_iter; ++i) {
-        if (__builtin_amdgcn_ballot_w64(live) == 0ull) break;
-        if (!live) continue;
-        const double2 Znn = orbit[m + 2 <= N ? m + 2 : N];      /* Z_{m+2}, for the next step (m + 1 < N) */
-        const double X2 = Zx + Zx, Y2 = Zy + Zy;
-        const double fx = ship_fold(Zx, X2, dzx), fy = ship_fold(Zy, Y2, dzy);
-        const double tx = fabs(X2) + fx, ty = fabs(Y2) + fy;     /* |X| + |X| = |X + X| */
-        const double nx = (tx * fx - ty * fy) + dcx;
-        const double ny = (tx * fy + ty * fx) + dcy;
-        ++m;
-        const double zx = Znx + nx, zy = Zny + ny;
-        const double r2 = zx * zx + zy * zy;
-        if (r2 > B2) {
-            esc = i; er2 = r2; live = false;
-        } else if (r2 < nx * nx + ny * ny || m == N) {           /* rebase */
-            dzx = zx; dzy = zy; m = 0;
-            Zx = 0.0; Zy = 0.0; Znx = z1.x; Zny = z1.y;
-        } else {
-            dzx = nx; dzy = ny;
-            Zx = Znx; Zy = Zny; Znx = Znn.x; Zny = Znn.y;
-        }
-    }
-}
-
-/* deep_orbit with BLA: u replaces the loop index.  A lane at m >= 1 probes the levels top down from
- * min(ctz(m - 1), K, floor(log2(N - m)), floor(log2(max_iter - u))) and takes the first k with |dz|^2 < r^2.  No level's
- * r exceeds the single step's 2^-53 |Z_m| (r only ever shrinks in the merge), so a lane with
- * |dz|^2 2^104 >= |Z_m|^2 (a bound above 2^-106 |Z_m|^2 with room for every rounding) cannot pass a probe and gathers
- * nothing.  A BLA lane loads Z_m and Z_{m+1} at its new m (the Z_{m+2} prefetch is for the plain step); BLA and plain
+/* deep_orbit with BLA: u replaces the loop index.  A lane probes the table (bla_probe) and takes the level it finds, else
+ * the plain step.  A BLA lane loads Z_m and Z_{m+1} at its new m (the Z_{m+2} prefetch is for the plain step); BLA and plain
  * lanes of a wave take their steps in the same trip.  nplain / nbla: the steps this sample took. */
+template <class F>
 __device__ __forceinline__ void deep_orbit_bla(const DeepArgs& A, const BlaTable& T, const double dcx, const double dcy,
                                                const double2 z1, bool live, int& esc, double& er2, uint32_t& nplain,
                                                uint32_t& nbla)
@@ -269,43 +751,27 @@ __device__ __forceinline__ void deep_orbit_bla(const DeepArgs& A, const BlaTable
         if (!live) continue;
         const double2 Znn = orbit[m + 2 <= N ? m + 2 : N];      /* Z_{m+2}, for a plain step */
         const double dz2 = dzx * dzx + dzy * dzy;
-        int k = 0;
-        uint32_t e = 0u;
-        if (m >= 1 && dz2 * 0x1p104 < Zx * Zx + Zy * Zy) {
-            const uint32_t mm = (uint32_t)(m - 1);
-            int kk = mm ? __builtin_ctz(mm) : K;
-            kk = kk < K ? kk : K;
-            const int kn = 31 - __builtin_clz((uint32_t)(N - m));
-            const int ki = 31 - __builtin_clz((uint32_t)(max_iter - u));
-            kk = kk < kn ? kk : kn;
-            kk = kk < ki ? kk : ki;
-            for (; kk >= 1; --kk) {
-                const uint32_t ek = bla_offset(n1, kk) + (mm >> kk);
-                const double r = tr[ek];
-                if (dz2 < r * r) { k = kk; e = ek; break; }
-            }
-        }
-        double nx, ny, Zmx, Zmy;
+        const BlaHit h = bla_probe(tr, n1, K, N, max_iter, m, u, dz2, Zx, Zy);
+        const int k = h.k;
+        double2 n;
+        double Zmx, Zmy;
         int step;
         if (k > 0) {
-            const double2 a = T.ab[2 * e], b = T.ab[2 * e + 1];
-            nx = (a.x * dzx - a.y * dzy) + (b.x * dcx - b.y * dcy);
-            ny = (a.x * dzy + a.y * dzx) + (b.x * dcy + b.y * dcx);
+            n = F::bla(T, h.e, dzx, dzy, dcx, dcy);
             step = 1 << k;
             ++nbla;
             m += step;
             const double2 Zm = orbit[m];
             Zmx = Zm.x; Zmy = Zm.y;
         } else {
-            const double tx = (Zx + Zx) + dzx, ty = (Zy + Zy) + dzy;
-            nx = (tx * dzx - ty * dzy) + dcx;
-            ny = (tx * dzy + ty * dzx) + dcy;
+            n = deep_step<F>(Zx, Zy, dzx, dzy, dcx, dcy);
             step = 1;
             ++nplain;
             m += 1;
             Zmx = Znx; Zmy = Zny;
         }
         u += step;
+        const double nx = n.x, ny = n.y;
         const double zx = Zmx + nx, zy = Zmy + ny;
         const double r2 = zx * zx + zy * zy;
         if (r2 > B2) {
@@ -327,193 +793,9 @@ __device__ __forceinline__ void deep_orbit_bla(const DeepArgs& A, const BlaTable
     }
 }
 
-/* ---- BLA for the ship (FR_FLAG_DEEP_SHIP_BLA; the semantics are in the header) --------------------------------------------
- * The table of the ship's cached orbit: levels and offsets are those of the Mandelbrot table, an entry is r and the real
- * matrices A = (a11, a12, a21, a22), B = (b11, b12, b21, b22). */
-struct ShipBlaTable {
-    const double* r;                     /* r of every entry, level 1 first */
-    const double2* ab;                   /* ab[4 e .. 4 e + 3] = (a11, a12), (a21, a22), (b11, b12), (b21, b22) */
-    int32_t levels;                      /* K = floor(log2(N - 1)), 0 = no table */
-    unsigned long long* steps;           /* plain steps, BLA steps, updates skipped: one atomic add each per wave */
-};
-
-struct DeepShipBlaArgs {
-    DeepShipArgs s;
-    ShipBlaTable t;
-};
-
-/* one entry while it is being merged: the rows of A and of B, and r */
-struct ShipLin {
-    double2 a1, a2, b1, b2;
-    double r;
-};
-
-/* The single step at orbit point Z = (X, Y): A = [[2X, -2Y], [2|Y| sgn X, 2|X| sgn Y]], B = 1, r = 2^-53 |Z| capped by |X|
- * and |Y| (the fold conditions: below them no fold flips a sign). */
-__device__ __forceinline__ ShipLin ship_single(const double2 Z)
-{
-    const double ax = fabs(Z.x), ay = fabs(Z.y);
-    const double sx = Z.x >= 0.0 ? 1.0 : -1.0, sy = Z.y >= 0.0 ? 1.0 : -1.0;
-    ShipLin s;
-    s.a1 = make_double2(Z.x + Z.x, -(Z.y + Z.y));
-    s.a2 = make_double2((ay + ay) * sx, (ax + ax) * sy);
-    s.b1 = make_double2(1.0, 0.0);
-    s.b2 = make_double2(0.0, 1.0);
-    double r = 0x1p-53 * bla_abs(Z.x, Z.y);
-    r = r < ax ? r : ax;
-    r = r < ay ? r : ay;
-    s.r = r;
-    return s;
-}
-
-/* Level k of the ship's table: deep_bla_level_kernel with the real 2x2 products.  |A_x| is the length of A_x's first column
- * (A_x is a scaled orthogonal matrix: its operator norm), |B_x| the Frobenius norm. */
-__global__ void __launch_bounds__(kBlockThreads)
-deep_ship_bla_level_kernel(const double2* __restrict__ orbit, const int32_t n_ref, const int32_t k, const double dcmax,
-                           double* __restrict__ r, double2* __restrict__ ab)
-{
-    const uint32_t n1 = (uint32_t)(n_ref - 1);
-    const uint32_t cnt = n1 >> k;
-    const uint32_t off = bla_offset(n1, k);
-    const uint32_t offp = k > 1 ? bla_offset(n1, k - 1) : 0u;
-    for (uint32_t j = blockIdx.x * kBlockThreads + threadIdx.x; j < cnt; j += gridDim.x * kBlockThreads) {
-        ShipLin x, y;
-        if (k == 1) {
-            x = ship_single(orbit[1 + 2 * j]);
-            y = ship_single(orbit[2 + 2 * j]);
-        } else {
-            const uint32_t ex = offp + 2 * j, ey = ex + 1;
-            x.a1 = ab[4 * ex]; x.a2 = ab[4 * ex + 1]; x.b1 = ab[4 * ex + 2]; x.b2 = ab[4 * ex + 3]; x.r = r[ex];
-            y.a1 = ab[4 * ey]; y.a2 = ab[4 * ey + 1]; y.b1 = ab[4 * ey + 2]; y.b2 = ab[4 * ey + 3]; y.r = r[ey];
-        }
-        const double2 a1 = make_double2(y.a1.x * x.a1.x + y.a1.y * x.a2.x, y.a1.x * x.a1.y + y.a1.y * x.a2.y);
-        const double2 a2 = make_double2(y.a2.x * x.a1.x + y.a2.y * x.a2.x, y.a2.x * x.a1.y + y.a2.y * x.a2.y);
-        const double2 b1 = make_double2((y.a1.x * x.b1.x + y.a1.y * x.b2.x) + y.b1.x, (y.a1.x * x.b1.y + y.a1.y * x.b2.y) + y.b1.y);
-        const double2 b2 = make_double2((y.a2.x * x.b1.x + y.a2.y * x.b2.x) + y.b2.x, (y.a2.x * x.b1.y + y.a2.y * x.b2.y) + y.b2.y);
-        const double nb = sqrt((x.b1.x * x.b1.x + x.b1.y * x.b1.y) + (x.b2.x * x.b2.x + x.b2.y * x.b2.y));
-        const double t = (y.r - nb * dcmax) / bla_abs(x.a1.x, x.a2.x);
-        double rr = t > 0.0 ? t : 0.0;                           /* NaN: 0 */
-        rr = rr < x.r ? rr : x.r;
-        if (!(__builtin_isfinite(a1.x) && __builtin_isfinite(a1.y) && __builtin_isfinite(a2.x) && __builtin_isfinite(a2.y) &&
-              __builtin_isfinite(b1.x) && __builtin_isfinite(b1.y) && __builtin_isfinite(b2.x) && __builtin_isfinite(b2.y)))
-            rr = 0.0;
-        const uint32_t e = off + j;
-        r[e] = rr;
-        ab[4 * e] = a1;
-        ab[4 * e + 1] = a2;
-        ab[4 * e + 2] = b1;
-        ab[4 * e + 3] = b2;
-    }
-}
-
-/* deep_orbit_ship with BLA: u replaces the loop index, the probe is deep_orbit_bla's (no level's r exceeds the single step's
- * 2^-53 |Z_m|, so the same pre-filter holds).  The BLA branch loads the entry's eight doubles and Z_m, Z_{m+1} at its new
- * m; the plain branch is deep_orbit_ship's step with its Z_{m+2} prefetch. */
-__device__ __forceinline__ void deep_orbit_ship_bla(const DeepArgs& A, const ShipBlaTable& T, const double dcx,
-                                                    const double dcy, const double2 z1, bool live, int& esc, double& er2,
-                                                    uint32_t& nplain, uint32_t& nbla)
-{
-    const double2* __restrict__ orbit = A.orbit;
-    const double* __restrict__ tr = T.r;
-    const double2* __restrict__ tab = T.ab;
-    const int N = A.n_ref, max_iter = A.max_iter, K = T.levels;
-    const uint32_t n1 = (uint32_t)(N - 1);
-    const double B2 = A.B2;
-    double dzx = 0.0, dzy = 0.0;
-    double Zx = 0.0, Zy = 0.0;                                   /* Z_m */
-    double Znx = z1.x, Zny = z1.y;                               /* Z_{m+1} */
-    int m = 0, u = 0;
-    esc = max_iter;
-    er2 = 0.0;
-    nplain = 0u; nbla = 0u;
-    for (;;) {
-        if (__builtin_amdgcn_ballot_w64(live) == 0ull) break;
-        if (!live) continue;
-        const double2 Znn = orbit[m + 2 <= N ? m + 2 : N];      /* Z_{m+2}, for a plain step */
-        const double dz2 = dzx * dzx + dzy * dzy;
-        int k = 0;
-        uint32_t e = 0u;
-        if (m >= 1 && dz2 * 0x1p104 < Zx * Zx + Zy * Zy) {
-            const uint32_t mm = (uint32_t)(m - 1);
-            int kk = mm ? __builtin_ctz(mm) : K;
-            kk = kk < K ? kk : K;
-            const int kn = 31 - __builtin_clz((uint32_t)(N - m));
-            const int ki = 31 - __builtin_clz((uint32_t)(max_iter - u));
-            kk = kk < kn ? kk : kn;
-            kk = kk < ki ? kk : ki;
-            for (; kk >= 1; --kk) {
-                const uint32_t ek = bla_offset(n1, kk) + (mm >> kk);
-                const double r = tr[ek];
-                if (dz2 < r * r) { k = kk; e = ek; break; }
-            }
-        }
-        double nx, ny, Zmx, Zmy;
-        int step;
-        if (k > 0) {
-            const double2 a1 = tab[4 * e], a2 = tab[4 * e + 1], b1 = tab[4 * e + 2], b2 = tab[4 * e + 3];
-            nx = (a1.x * dzx + a1.y * dzy) + (b1.x * dcx + b1.y * dcy);
-            ny = (a2.x * dzx + a2.y * dzy) + (b2.x * dcx + b2.y * dcy);
-            step = 1 << k;
-            ++nbla;
-            m += step;
-            const double2 Zm = orbit[m];
-            Zmx = Zm.x; Zmy = Zm.y;
-        } else {
-            const double X2 = Zx + Zx, Y2 = Zy + Zy;
-            const double fx = ship_fold(Zx, X2, dzx), fy = ship_fold(Zy, Y2, dzy);
-            const double tx = fabs(X2) + fx, ty = fabs(Y2) + fy;     /* |X| + |X| = |X + X| */
-            nx = (tx * fx - ty * fy) + dcx;
-            ny = (tx * fy + ty * fx) + dcy;
-            step = 1;
-            ++nplain;
-            m += 1;
-            Zmx = Znx; Zmy = Zny;
-        }
-        u += step;
-        const double zx = Zmx + nx, zy = Zmy + ny;
-        const double r2 = zx * zx + zy * zy;
-        if (r2 > B2) {
-            esc = u - 1; er2 = r2; live = false;                 /* the last update the step covered */
-        } else if (r2 < nx * nx + ny * ny || m == N) {           /* rebase */
-            dzx = zx; dzy = zy; m = 0;
-            Zx = 0.0; Zy = 0.0; Znx = z1.x; Zny = z1.y;
-        } else {
-            dzx = nx; dzy = ny;
-            Zx = Zmx; Zy = Zmy;
-            if (k > 0) {                                          /* m < N here */
-                const double2 Zn = orbit[m + 1];
-                Znx = Zn.x; Zny = Zn.y;
-            } else {
-                Znx = Znn.x; Zny = Znn.y;
-            }
-        }
-        if (u >= max_iter) live = false;                          /* esc stays max_iter */
-    }
-}
-
-/* fr_render_deepx: d.orbit holds the plain doubles P_n, d.zoom is not read */
-struct DeepXArgs {
-    DeepArgs d;
-    const double2* mant;                 /* (mx, my) of Z_0 .. Z_N */
-    const int32_t* exp2;                 /* e of Z_0 .. Z_N */
-    double zm;                           /* zoom = zm 2^ze */
-    int32_t ze;
-};
-
-constexpr int kXZero = FR_DEEPX_ZERO_EXP;
-constexpr int kXThr = -400;              /* extended while the normalised dz.e <= kXThr */
-
-/* norm(x, y, e) of the header */
-__device__ __forceinline__ void x_norm(double& x, double& y, int& e)
-{
-    const double mx = fmax(fabs(x), fabs(y));
-    const int k = __builtin_amdgcn_frexp_exp(mx);
-    x = __builtin_ldexp(x, -k);
-    y = __builtin_ldexp(y, -k);
-    e = mx == 0.0 ? kXZero : e + k;
-}
-
-/* deep_orbit in two modes (the header's EXTENDED and PLAIN steps).  (cx, cy, ec) = dc, normalised. */
+/* deep_orbit in two modes (the header's EXTENDED and PLAIN steps).  (cx, cy, ec) = dc, normalised.  z = Z_{m+1} (+) n with the
+ * signed orbit point; escape, rebase, norm and the mode rule are the same for either formula. */
+template <class F>
 __device__ __forceinline__ void deep_orbit_x(const DeepXArgs& AA, const double cx, const double cy, const int ec, bool live,
                                              int& esc, double& er2)
 {
@@ -523,9 +805,7 @@ __device__ __forceinline__ void deep_orbit_x(const DeepXArgs& AA, const double c
     const int32_t* __restrict__ exp2 = AA.exp2;
     const int N = A.n_ref, max_iter = A.max_iter;
     const double B2 = A.B2;
-    /* the plain mode's dc: a component below 2^-1022 is 0 */
-    const double cpx = (cx != 0.0 && __builtin_amdgcn_frexp_exp(cx) + ec > -1022) ? __builtin_ldexp(cx, ec) : 0.0;
-    const double cpy = (cy != 0.0 && __builtin_amdgcn_frexp_exp(cy) + ec > -1022) ? __builtin_ldexp(cy, ec) : 0.0;
+    const double cpx = x_plain(cx, ec), cpy = x_plain(cy, ec);   /* the plain mode's dc */
     double dzx = 0.0, dzy = 0.0;                                 /* plain: dz; extended: its mantissas */
     int ed = kXZero;
     bool ext = true;
@@ -547,15 +827,9 @@ __device__ __forceinline__ void deep_orbit_x(const DeepXArgs& AA, const double c
         if (ext) {
             const double2 Znn = mant[mn];
             const int eZnn = exp2[mn];
-            const int et = eZ + 1 > ed ? eZ + 1 : ed;
-            const double tx = __builtin_ldexp(Zx, eZ + 1 - et) + __builtin_ldexp(dzx, ed - et);
-            const double ty = __builtin_ldexp(Zy, eZ + 1 - et) + __builtin_ldexp(dzy, ed - et);
-            const double px = tx * dzx - ty * dzy;
-            const double py = tx * dzy + ty * dzx;
-            const int ep = et + ed;
-            const int en = ep > ec ? ep : ec;
-            const double nx = __builtin_ldexp(px, ep - en) + __builtin_ldexp(cx, ec - en);
-            const double ny = __builtin_ldexp(py, ep - en) + __builtin_ldexp(cy, ec - en);
+            int en;
+            const double2 n = deep_step_x<F>(Zx, Zy, eZ, dzx, dzy, ed, cx, cy, ec, en);
+            const double nx = n.x, ny = n.y;
             ++m;
             const int ez = eZn > en ? eZn : en;
             const double zx = __builtin_ldexp(Znx, eZn - ez) + __builtin_ldexp(nx, en - ez);
@@ -583,9 +857,8 @@ __device__ __forceinline__ void deep_orbit_x(const DeepXArgs& AA, const double c
             ext = false;
         } else {
             const double2 Znn = orbit[mn];
-            const double tx = (Zx + Zx) + dzx, ty = (Zy + Zy) + dzy;
-            const double nx = (tx * dzx - ty * dzy) + cpx;
-            const double ny = (tx * dzy + ty * dzx) + cpy;
+            const double2 n = deep_step<F>(Zx, Zy, dzx, dzy, cpx, cpy);
+            const double nx = n.x, ny = n.y;
             ++m;
             const double zx = Znx + nx, zy = Zny + ny;
             const double r2 = zx * zx + zy * zy;
@@ -621,257 +894,11 @@ __device__ __forceinline__ void deep_orbit_x(const DeepXArgs& AA, const double c
     }
 }
 
-/* fr_render_deepx_ship: x.d.orbit holds the plain doubles P_n of the ship's orbit, x.mant / x.exp2 its extended storage */
-struct DeepShipXArgs {
-    DeepXArgs x;
-    double log_bailout;                  /* as DeepShipArgs */
-};
-
-/* fold_x of the header: ship_fold on an orbit mantissa X at exponent eZ and a delta mantissa a at exponent ed, s = eZ - ed,
- * taken in the delta's frame -- the result is a mantissa at ed.  X far above the delta: the ldexp may give +-inf, w has X's
- * sign, the select returns +-a and drops the infinite d.  X far below: Xs is 0 or a subnormal, below half an ulp of a. */
-__device__ __forceinline__ double ship_fold_x(const double X, const int s, const double a)
-{
-    const double Xs = __builtin_ldexp(X, s), X2s = __builtin_ldexp(X, s + 1);
-    const double w = Xs + a, d = X2s + a;
-    const double up = w >= 0.0 ? a : -d;
-    const double dn = w > 0.0 ? d : -a;
-    return X >= 0.0 ? up : dn;
-}
-
-/* deep_orbit_x for z <- (|x| + i |y|)^2 + c (the header's EXTENDED and PLAIN steps of fr_render_deepx_ship): the extended
- * step on U = (|Z_m.x|, |Z_m.y|, Z_m.e + 1) and f = (fold_x, fold_x, dz.e), the plain step deep_orbit_ship's; z = Z_{m+1} (+) n
- * with the signed orbit point, escape, rebase, norm and the mode rule as in deep_orbit_x.  (cx, cy, ec) = dc, normalised. */
-__device__ __forceinline__ void deep_orbit_ship_x(const DeepXArgs& AA, const double cx, const double cy, const int ec,
-                                                  bool live, int& esc, double& er2)
-{
-    const DeepArgs& A = AA.d;
-    const double2* __restrict__ orbit = A.orbit;
-    const double2* __restrict__ mant = AA.mant;
-    const int32_t* __restrict__ exp2 = AA.exp2;
-    const int N = A.n_ref, max_iter = A.max_iter;
-    const double B2 = A.B2;
-    /* the plain mode's dc: a component below 2^-1022 is 0 */
-    const double cpx = (cx != 0.0 && __builtin_amdgcn_frexp_exp(cx) + ec > -1022) ? __builtin_ldexp(cx, ec) : 0.0;
-    const double cpy = (cy != 0.0 && __builtin_amdgcn_frexp_exp(cy) + ec > -1022) ? __builtin_ldexp(cy, ec) : 0.0;
-    double dzx = 0.0, dzy = 0.0;                                 /* plain: dz; extended: its mantissas */
-    int ed = kXZero;
-    bool ext = true;
-    double Zx = 0.0, Zy = 0.0;                                   /* Z_m, in the lane's mode */
-    int eZ = kXZero;
-    const double2 z1 = mant[1];
-    double Znx = z1.x, Zny = z1.y;                               /* Z_{m+1} */
-    int eZn = exp2[1];
-    int m = 0;
-    esc = max_iter;
-    er2 = 0.0;
-    for (int i = 0; i < max_iter; ++i) {
-        if (__builtin_amdgcn_ballot_w64(live) == 0ull) break;
-        if (!live) continue;
-        const int mn = m + 2 <= N ? m + 2 : N;                   /* Z_{m+2}, for the next step (m + 1 < N) */
-        double ax, ay;                                           /* the next dz */
-        int ea = 0;
-        bool reb;
-        if (ext) {
-            const double2 Znn = mant[mn];
-            const int eZnn = exp2[mn];
-            const double fx = ship_fold_x(Zx, eZ - ed, dzx), fy = ship_fold_x(Zy, eZ - ed, dzy);
-            const int et = eZ + 1 > ed ? eZ + 1 : ed;
-            const double tx = __builtin_ldexp(fabs(Zx), eZ + 1 - et) + __builtin_ldexp(fx, ed - et);
-            const double ty = __builtin_ldexp(fabs(Zy), eZ + 1 - et) + __builtin_ldexp(fy, ed - et);
-            const double px = tx * fx - ty * fy;
-            const double py = tx * fy + ty * fx;
-            const int ep = et + ed;
-            const int en = ep > ec ? ep : ec;
-            const double nx = __builtin_ldexp(px, ep - en) + __builtin_ldexp(cx, ec - en);
-            const double ny = __builtin_ldexp(py, ep - en) + __builtin_ldexp(cy, ec - en);
-            ++m;
-            const int ez = eZn > en ? eZn : en;
-            const double zx = __builtin_ldexp(Znx, eZn - ez) + __builtin_ldexp(nx, en - ez);
-            const double zy = __builtin_ldexp(Zny, eZn - ez) + __builtin_ldexp(ny, en - ez);
-            const double r2 = zx * zx + zy * zy;
-            const double r2d = __builtin_ldexp(r2, 2 * ez);
-            if (r2d > B2) {
-                esc = i; er2 = r2d; live = false;
-                continue;
-            }
-            reb = r2 < __builtin_ldexp(nx * nx + ny * ny, 2 * (en - ez)) || m == N;
-            ax = reb ? zx : nx; ay = reb ? zy : ny; ea = reb ? ez : en;
-            x_norm(ax, ay, ea);
-            if (reb) m = 0;
-            if (ea <= kXThr) {                                    /* stays extended */
-                dzx = ax; dzy = ay; ed = ea;
-                if (reb) {
-                    Zx = 0.0; Zy = 0.0; eZ = kXZero; Znx = z1.x; Zny = z1.y; eZn = exp2[1];
-                } else {
-                    Zx = Znx; Zy = Zny; eZ = eZn; Znx = Znn.x; Zny = Znn.y; eZn = eZnn;
-                }
-                continue;
-            }
-            dzx = __builtin_ldexp(ax, ea); dzy = __builtin_ldexp(ay, ea);
-            ext = false;
-        } else {
-            const double2 Znn = orbit[mn];
-            const double X2 = Zx + Zx, Y2 = Zy + Zy;
-            const double fx = ship_fold(Zx, X2, dzx), fy = ship_fold(Zy, Y2, dzy);
-            const double tx = fabs(X2) + fx, ty = fabs(Y2) + fy;     /* |X| + |X| = |X + X| */
-            const double nx = (tx * fx - ty * fy) + cpx;
-            const double ny = (tx * fy + ty * fx) + cpy;
-            ++m;
-            const double zx = Znx + nx, zy = Zny + ny;
-            const double r2 = zx * zx + zy * zy;
-            if (r2 > B2) {
-                esc = i; er2 = r2; live = false;
-                continue;
-            }
-            reb = r2 < nx * nx + ny * ny || m == N;
-            ax = reb ? zx : nx; ay = reb ? zy : ny;
-            if (reb) m = 0;
-            if (!(fmax(fabs(ax), fabs(ay)) < 0x1p-400)) {         /* stays plain */
-                dzx = ax; dzy = ay;
-                if (reb) {
-                    const double2 p1 = orbit[1];
-                    Zx = 0.0; Zy = 0.0; Znx = p1.x; Zny = p1.y;
-                } else {
-                    Zx = Znx; Zy = Zny; Znx = Znn.x; Zny = Znn.y;
-                }
-                continue;
-            }
-            x_norm(ax, ay, ea);
-            dzx = ax; dzy = ay; ed = ea;
-            ext = true;
-        }
-        /* the lane changed its mode: Z_m and Z_{m+1} (m < N here) from the new mode's arrays */
-        if (ext) {
-            const double2 a = mant[m], b = mant[m + 1];
-            Zx = a.x; Zy = a.y; eZ = exp2[m]; Znx = b.x; Zny = b.y; eZn = exp2[m + 1];
-        } else {
-            const double2 a = orbit[m], b = orbit[m + 1];
-            Zx = a.x; Zy = a.y; Znx = b.x; Zny = b.y;
-        }
-    }
-}
-
-/* ---- BLA for extended views (FR_FLAG_DEEPX_BLA; the semantics are in the header) -----------------------------------------
- * The table of the extended orbit: per entry the radius r as 8 bytes (XRad: the top 24 bits of its mantissa as a float and
- * its int32 exponent -- what a probe gathers), and apart from it (A, B) as two double2 of normalised mantissas with their
- * two exponents in an int2, loaded for the chosen level only.  Levels and offsets are those of the fp64 table. */
-struct XRad {
-    float v;                             /* mantissa in [0.5, 1), 0 for r = 0 */
-    int32_t e;                           /* FR_DEEPX_ZERO_EXP for r = 0 */
-};
-
-struct BlaXTable {
-    const XRad* r;                       /* r of every entry, level 1 first */
-    const double2* ab;                   /* mantissas of A, B: ab[2 e], ab[2 e + 1] */
-    const int2* abe;                     /* (A.e, B.e) */
-    int32_t levels;                      /* K = floor(log2(N - 1)), 0 = no table */
-    unsigned long long* steps;           /* single steps, BLA steps, updates skipped: one atomic add each per wave */
-};
-
-struct DeepXBlaArgs {
-    DeepXArgs x;
-    BlaXTable t;
-};
-
-constexpr int kXBlaExpLim = 1 << 27;     /* an entry whose A.e or B.e leaves [-2^27, 2^27] is void */
-
-/* an extended real normalised: v into [0.5, 1), zero gets FR_DEEPX_ZERO_EXP */
-__device__ __forceinline__ void x_norm1(double& v, int& e)
-{
-    const int k = __builtin_amdgcn_frexp_exp(v);
-    e = v == 0.0 ? kXZero : e + k;
-    v = __builtin_ldexp(v, -k);
-}
-
-/* the top 24 bits of a mantissa in [0.5, 1) (toward zero): exactly a float */
-__device__ __forceinline__ double x_trunc24(const double v)
-{
-    return __longlong_as_double(__double_as_longlong(v) & ~((1ll << 29) - 1));
-}
-
-/* Level k of the extended table.  Level 0 is the single step at m = 1 + i (A = norm(Z_m.x, Z_m.y, Z_m.e + 1), B = norm(1, 0, 0),
- * r = 2^-53 |Z_m|), computed from the orbit and never stored. */
-__global__ void __launch_bounds__(kBlockThreads)
-deepx_bla_level_kernel(const double2* __restrict__ mant, const int32_t* __restrict__ exp2, const int32_t n_ref, const int32_t k,
-                       const double dcv, const int32_t dce, XRad* __restrict__ r, double2* __restrict__ ab,
-                       int2* __restrict__ abe)
-{
-    const uint32_t n1 = (uint32_t)(n_ref - 1);
-    const uint32_t cnt = n1 >> k;
-    const uint32_t off = bla_offset(n1, k);
-    const uint32_t offp = k > 1 ? bla_offset(n1, k - 1) : 0u;
-    for (uint32_t j = blockIdx.x * kBlockThreads + threadIdx.x; j < cnt; j += gridDim.x * kBlockThreads) {
-        double2 A[2], B[2];                                      /* x, y */
-        int eA[2], eB[2], eR[2];
-        double R[2];
-        if (k == 1) {
-            for (int s = 0; s < 2; ++s) {
-                const double2 z = mant[1 + s + 2 * j];
-                const int ez = exp2[1 + s + 2 * j];
-                A[s] = z; eA[s] = ez + 1;
-                x_norm(A[s].x, A[s].y, eA[s]);
-                B[s] = make_double2(0.5, 0.0); eB[s] = 1;
-                double nx = z.x, ny = z.y;
-                int ne = ez;
-                x_norm(nx, ny, ne);
-                R[s] = bla_abs(nx, ny); eR[s] = ne;
-                x_norm1(R[s], eR[s]);
-                if (R[s] != 0.0) eR[s] -= 53;
-            }
-        } else {
-            for (int s = 0; s < 2; ++s) {
-                const uint32_t e = offp + 2 * j + s;
-                const int2 ee = abe[e];
-                const XRad rr = r[e];
-                A[s] = ab[2 * e]; B[s] = ab[2 * e + 1]; eA[s] = ee.x; eB[s] = ee.y;
-                R[s] = (double)rr.v; eR[s] = rr.e;
-            }
-        }
-        double2 a = make_double2(A[1].x * A[0].x - A[1].y * A[0].y, A[1].x * A[0].y + A[1].y * A[0].x);
-        int ea = eA[1] + eA[0];
-        x_norm(a.x, a.y, ea);
-        const double px = A[1].x * B[0].x - A[1].y * B[0].y, py = A[1].x * B[0].y + A[1].y * B[0].x;
-        const int e1 = eA[1] + eB[0];
-        int eb = e1 > eB[1] ? e1 : eB[1];
-        double2 b = make_double2(__builtin_ldexp(px, e1 - eb) + __builtin_ldexp(B[1].x, eB[1] - eb),
-                                 __builtin_ldexp(py, e1 - eb) + __builtin_ldexp(B[1].y, eB[1] - eb));
-        x_norm(b.x, b.y, eb);
-        double bv = bla_abs(B[0].x, B[0].y), av = bla_abs(A[0].x, A[0].y);
-        int be = eB[0], ae = eA[0];
-        x_norm1(bv, be);
-        x_norm1(av, ae);
-        const double pv = bv * dcv;
-        const int pe = be + dce;
-        const int et = eR[1] > pe ? eR[1] : pe;
-        const double t = (__builtin_ldexp(R[1], eR[1] - et) - __builtin_ldexp(pv, pe - et)) / av;
-        double rv = (t > 0.0 && __builtin_isfinite(t)) ? t : 0.0;    /* NaN: 0 */
-        int re = et - ae;
-        x_norm1(rv, re);
-        if (!(re < eR[0] || (re == eR[0] && rv < R[0]))) { rv = R[0]; re = eR[0]; }
-        const int la = ea < 0 ? -ea : ea, lb = eb < 0 ? -eb : eb;
-        if (la > kXBlaExpLim || lb > kXBlaExpLim) {
-            rv = 0.0; re = kXZero;
-            a = make_double2(0.0, 0.0); ea = kXZero;
-            b = make_double2(0.0, 0.0); eb = kXZero;
-        }
-        const uint32_t e = off + j;
-        XRad out;
-        out.v = (float)x_trunc24(rv); out.e = re;
-        r[e] = out;
-        ab[2 * e] = a;
-        ab[2 * e + 1] = b;
-        abe[e] = make_int2(ea, eb);
-    }
-}
-
-/* deep_orbit_x with BLA: u replaces the loop index.  A lane at m >= 1, in either mode, probes the levels top down as
- * deep_orbit_bla does, on its dz as a normalised extended number (a plain lane forms norm(dz.x, dz.y, 0)), and takes the
- * first k with |dz|^2 < r^2; the step is then taken in extended arithmetic whatever the lane's mode, and the lane reloads
- * Z_m, Z_{m+1} in the mode the step leaves it in.  No level's r exceeds 2^-53 |Z_m| < 2^(E - 52.5), E the exponent of Z_m's
- * larger component normalised, and |dz| >= 2^(dz.e - 1): a lane with dz.e + 51 >= E cannot pass a probe and gathers nothing
- * (E from the lane's own copy of Z_m: for a point below 2^-1022 the plain double's exponent is never below the true one).
- * BLA lanes and single-step lanes of a wave take their steps in the same trip.  nsingle / nbla: the steps this sample took. */
+/* deep_orbit_x with BLA: u replaces the loop index.  A lane, in either mode, probes the table (bla_probe_x); a BLA step is
+ * taken in extended arithmetic whatever the lane's mode, its loads inside the taken branch, and the lane reloads Z_m, Z_{m+1}
+ * in the mode the step leaves it in.  The single steps are deep_orbit_x's, operation for operation.  BLA lanes and
+ * single-step lanes of a wave take their steps in the same trip.  nsingle / nbla: the steps this sample took. */
+template <class F>
 __device__ __forceinline__ void deep_orbit_x_bla(const DeepXArgs& AA, const BlaXTable& T, const double cx, const double cy,
                                                  const int ec, bool live, int& esc, double& er2, uint32_t& nsingle,
                                                  uint32_t& nbla)
@@ -884,8 +911,7 @@ __device__ __forceinline__ void deep_orbit_x_bla(const DeepXArgs& AA, const BlaX
     const int N = A.n_ref, max_iter = A.max_iter, K = T.levels;
     const uint32_t n1 = (uint32_t)(N - 1);
     const double B2 = A.B2;
-    const double cpx = (cx != 0.0 && __builtin_amdgcn_frexp_exp(cx) + ec > -1022) ? __builtin_ldexp(cx, ec) : 0.0;
-    const double cpy = (cy != 0.0 && __builtin_amdgcn_frexp_exp(cy) + ec > -1022) ? __builtin_ldexp(cy, ec) : 0.0;
+    const double cpx = x_plain(cx, ec), cpy = x_plain(cy, ec);   /* the plain mode's dc */
     double dzx = 0.0, dzy = 0.0;                                 /* plain: dz; extended: its mantissas */
     int ed = kXZero;
     bool ext = true;
@@ -903,30 +929,8 @@ __device__ __forceinline__ void deep_orbit_x_bla(const DeepXArgs& AA, const BlaX
         if (__builtin_amdgcn_ballot_w64(live) == 0ull) break;
         if (!live) continue;
         const int mn = m + 2 <= N ? m + 2 : N;                   /* Z_{m+2}, for the single step after this one */
-        int k = 0;
-        uint32_t e = 0u;
-        double qx = dzx, qy = dzy;                               /* dz, extended and normalised */
-        int qe = ed;
-        if (m >= 1) {
-            if (!ext) { qe = 0; x_norm(qx, qy, qe); }
-            const int eZm = (ext ? eZ : 0) + __builtin_amdgcn_frexp_exp(fmax(fabs(Zx), fabs(Zy)));
-            if (qe + 51 < eZm) {
-                const double dz2 = qx * qx + qy * qy;
-                const uint32_t mm = (uint32_t)(m - 1);
-                int kk = mm ? __builtin_ctz(mm) : K;
-                kk = kk < K ? kk : K;
-                const int kn = 31 - __builtin_clz((uint32_t)(N - m));
-                const int ki = 31 - __builtin_clz((uint32_t)(max_iter - u));
-                kk = kk < kn ? kk : kn;
-                kk = kk < ki ? kk : ki;
-                for (; kk >= 1; --kk) {
-                    const uint32_t ek = bla_offset(n1, kk) + (mm >> kk);
-                    const XRad r = tr[ek];
-                    const double rv = (double)r.v;
-                    if (dz2 < __builtin_ldexp(rv * rv, 2 * (r.e - qe))) { k = kk; e = ek; break; }
-                }
-            }
-        }
+        const BlaHitX h = bla_probe_x(tr, n1, K, N, max_iter, m, u, ext, dzx, dzy, ed, Zx, Zy, eZ);
+        const int k = h.k;
         double ax, ay;                                           /* the next dz */
         int ea = 0;
         bool reb;
@@ -935,14 +939,11 @@ __device__ __forceinline__ void deep_orbit_x_bla(const DeepXArgs& AA, const BlaX
             int en, eW, eZnn = 0;
             double2 Znn = make_double2(0.0, 0.0);
             if (k > 0) {
-                const double2 a = T.ab[2 * e], b = T.ab[2 * e + 1];
-                const int2 ee = T.abe[e];
-                const double px = a.x * qx - a.y * qy, py = a.x * qy + a.y * qx;
-                const double sx = b.x * cx - b.y * cy, sy = b.x * cy + b.y * cx;
-                const int ep = ee.x + qe, es = ee.y + ec;
+                const BlaStepX s = F::bla_x(T, h.e, h.qx, h.qy, cx, cy);
+                const int ep = s.ea + h.qe, es = s.eb + ec;
                 en = ep > es ? ep : es;
-                nx = __builtin_ldexp(px, ep - en) + __builtin_ldexp(sx, es - en);
-                ny = __builtin_ldexp(py, ep - en) + __builtin_ldexp(sy, es - en);
+                nx = __builtin_ldexp(s.px, ep - en) + __builtin_ldexp(s.sx, es - en);
+                ny = __builtin_ldexp(s.py, ep - en) + __builtin_ldexp(s.sy, es - en);
                 m += 1 << k;
                 u += 1 << k;
                 ++nbla;
@@ -951,15 +952,8 @@ __device__ __forceinline__ void deep_orbit_x_bla(const DeepXArgs& AA, const BlaX
             } else {
                 Znn = mant[mn];
                 eZnn = exp2[mn];
-                const int et = eZ + 1 > ed ? eZ + 1 : ed;
-                const double tx = __builtin_ldexp(Zx, eZ + 1 - et) + __builtin_ldexp(dzx, ed - et);
-                const double ty = __builtin_ldexp(Zy, eZ + 1 - et) + __builtin_ldexp(dzy, ed - et);
-                const double px = tx * dzx - ty * dzy;
-                const double py = tx * dzy + ty * dzx;
-                const int ep = et + ed;
-                en = ep > ec ? ep : ec;
-                nx = __builtin_ldexp(px, ep - en) + __builtin_ldexp(cx, ec - en);
-                ny = __builtin_ldexp(py, ep - en) + __builtin_ldexp(cy, ec - en);
+                const double2 n = deep_step_x<F>(Zx, Zy, eZ, dzx, dzy, ed, cx, cy, ec, en);
+                nx = n.x; ny = n.y;
                 ++m;
                 ++u;
                 ++nsingle;
@@ -997,9 +991,8 @@ __device__ __forceinline__ void deep_orbit_x_bla(const DeepXArgs& AA, const BlaX
             }
         } else {
             const double2 Znn = orbit[mn];
-            const double tx = (Zx + Zx) + dzx, ty = (Zy + Zy) + dzy;
-            const double nx = (tx * dzx - ty * dzy) + cpx;
-            const double ny = (tx * dzy + ty * dzx) + cpy;
+            const double2 n = deep_step<F>(Zx, Zy, dzx, dzy, cpx, cpy);
+            const double nx = n.x, ny = n.y;
             ++m;
             ++u;
             ++nsingle;
@@ -1032,356 +1025,43 @@ __device__ __forceinline__ void deep_orbit_x_bla(const DeepXArgs& AA, const BlaX
     }
 }
 
-/* ---- BLA for extended ship views (FR_FLAG_DEEPX_SHIP_BLA; the semantics are in the header) ---------------------------------
- * The table of the ship's extended orbit: per entry the radius as an XRad (what a probe gathers), and apart from it the real
- * matrices A and B as four double2 of mantissas -- (a11, a12), (a21, a22), (b11, b12), (b21, b22), each matrix normalised on
- * its largest element -- with their two shared exponents in an int2, loaded for the chosen level only.  Levels and offsets
- * are those of the fp64 table. */
-struct ShipXBlaTable {
-    const XRad* r;                       /* r of every entry, level 1 first */
-    const double2* ab;                   /* ab[4 e .. 4 e + 3]: the rows of A and of B, mantissas */
-    const int2* abe;                     /* (A.e, B.e) */
-    int32_t levels;                      /* K = floor(log2(N - 1)), 0 = no table */
-    unsigned long long* steps;           /* single steps, BLA steps, updates skipped: one atomic add each per wave */
-};
-
-struct DeepShipXBlaArgs {
-    DeepShipXArgs s;
-    ShipXBlaTable t;
-};
-
-/* norm4 of the header: a matrix's four mantissas normalised on the largest of them */
-__device__ __forceinline__ void x_norm4(double2& r1, double2& r2, int& e)
-{
-    const double mx = fmax(fmax(fabs(r1.x), fabs(r1.y)), fmax(fabs(r2.x), fabs(r2.y)));
-    const int k = __builtin_amdgcn_frexp_exp(mx);
-    r1.x = __builtin_ldexp(r1.x, -k); r1.y = __builtin_ldexp(r1.y, -k);
-    r2.x = __builtin_ldexp(r2.x, -k); r2.y = __builtin_ldexp(r2.y, -k);
-    e = mx == 0.0 ? kXZero : e + k;
-}
-
-/* one entry while it is being merged: the rows of A and of B with their exponents, and r */
-struct ShipXLin {
-    double2 a1, a2, b1, b2;
-    int ea, eb;
-    double rv;
-    int re;
-};
-
-/* (v, e) < (w, f) on normalised extended reals; the zero's exponent FR_DEEPX_ZERO_EXP is below every other */
-__device__ __forceinline__ bool x_less(const double v, const int e, const double w, const int f)
-{
-    return e < f || (e == f && v < w);
-}
-
-/* The single step at the extended orbit point Z = (X, Y) 2^eZ: ship_single with the doubling in A's exponent, r = 2^-53 |norm(Z)|
- * capped by |X| and |Y| as extended reals (a coordinate stored as 0 gives r = 0). */
-__device__ __forceinline__ ShipXLin shipx_single(const double2 Z, const int eZ)
-{
-    const double ax = fabs(Z.x), ay = fabs(Z.y);
-    const double sx = Z.x >= 0.0 ? 1.0 : -1.0, sy = Z.y >= 0.0 ? 1.0 : -1.0;
-    ShipXLin s;
-    s.a1 = make_double2(Z.x, -Z.y);
-    s.a2 = make_double2(ay * sx, ax * sy);
-    s.ea = eZ + 1;
-    x_norm4(s.a1, s.a2, s.ea);
-    s.b1 = make_double2(0.5, 0.0);
-    s.b2 = make_double2(0.0, 0.5);
-    s.eb = 1;
-    double nx = Z.x, ny = Z.y;
-    int ne = eZ;
-    x_norm(nx, ny, ne);
-    double rv = bla_abs(nx, ny);
-    int re = ne;
-    x_norm1(rv, re);
-    if (rv != 0.0) re -= 53;
-    double cv = ax;
-    int ce = eZ;
-    x_norm1(cv, ce);
-    if (!x_less(rv, re, cv, ce)) { rv = cv; re = ce; }
-    cv = ay; ce = eZ;
-    x_norm1(cv, ce);
-    if (!x_less(rv, re, cv, ce)) { rv = cv; re = ce; }
-    s.rv = rv; s.re = re;
-    return s;
-}
-
-/* Level k of the extended ship table: deep_ship_bla_level_kernel's products and norms in deepx_bla_level_kernel's arithmetic
- * (t, the r < r_x rule, the void rule and the 24-bit cut of the stored radius are that kernel's). */
-__global__ void __launch_bounds__(kBlockThreads)
-deepx_ship_bla_level_kernel(const double2* __restrict__ mant, const int32_t* __restrict__ exp2, const int32_t n_ref,
-                            const int32_t k, const double dcv, const int32_t dce, XRad* __restrict__ r,
-                            double2* __restrict__ ab, int2* __restrict__ abe)
-{
-    const uint32_t n1 = (uint32_t)(n_ref - 1);
-    const uint32_t cnt = n1 >> k;
-    const uint32_t off = bla_offset(n1, k);
-    const uint32_t offp = k > 1 ? bla_offset(n1, k - 1) : 0u;
-    for (uint32_t j = blockIdx.x * kBlockThreads + threadIdx.x; j < cnt; j += gridDim.x * kBlockThreads) {
-        ShipXLin x, y;
-        if (k == 1) {
-            x = shipx_single(mant[1 + 2 * j], exp2[1 + 2 * j]);
-            y = shipx_single(mant[2 + 2 * j], exp2[2 + 2 * j]);
-        } else {
-            const uint32_t ex = offp + 2 * j, ey = ex + 1;
-            const int2 eex = abe[ex], eey = abe[ey];
-            const XRad rx = r[ex], ry = r[ey];
-            x.a1 = ab[4 * ex]; x.a2 = ab[4 * ex + 1]; x.b1 = ab[4 * ex + 2]; x.b2 = ab[4 * ex + 3];
-            x.ea = eex.x; x.eb = eex.y; x.rv = (double)rx.v; x.re = rx.e;
-            y.a1 = ab[4 * ey]; y.a2 = ab[4 * ey + 1]; y.b1 = ab[4 * ey + 2]; y.b2 = ab[4 * ey + 3];
-            y.ea = eey.x; y.eb = eey.y; y.rv = (double)ry.v; y.re = ry.e;
-        }
-        double2 a1 = make_double2(y.a1.x * x.a1.x + y.a1.y * x.a2.x, y.a1.x * x.a1.y + y.a1.y * x.a2.y);
-        double2 a2 = make_double2(y.a2.x * x.a1.x + y.a2.y * x.a2.x, y.a2.x * x.a1.y + y.a2.y * x.a2.y);
-        int ea = y.ea + x.ea;
-        x_norm4(a1, a2, ea);
-        const double2 p1 = make_double2(y.a1.x * x.b1.x + y.a1.y * x.b2.x, y.a1.x * x.b1.y + y.a1.y * x.b2.y);
-        const double2 p2 = make_double2(y.a2.x * x.b1.x + y.a2.y * x.b2.x, y.a2.x * x.b1.y + y.a2.y * x.b2.y);
-        const int e1 = y.ea + x.eb;
-        int eb = e1 > y.eb ? e1 : y.eb;
-        double2 b1 = make_double2(__builtin_ldexp(p1.x, e1 - eb) + __builtin_ldexp(y.b1.x, y.eb - eb),
-                                  __builtin_ldexp(p1.y, e1 - eb) + __builtin_ldexp(y.b1.y, y.eb - eb));
-        double2 b2 = make_double2(__builtin_ldexp(p2.x, e1 - eb) + __builtin_ldexp(y.b2.x, y.eb - eb),
-                                  __builtin_ldexp(p2.y, e1 - eb) + __builtin_ldexp(y.b2.y, y.eb - eb));
-        x_norm4(b1, b2, eb);
-        double bv = sqrt((x.b1.x * x.b1.x + x.b1.y * x.b1.y) + (x.b2.x * x.b2.x + x.b2.y * x.b2.y));
-        double av = bla_abs(x.a1.x, x.a2.x);
-        int be = x.eb, ae = x.ea;
-        x_norm1(bv, be);
-        x_norm1(av, ae);
-        const double pv = bv * dcv;
-        const int pe = be + dce;
-        const int et = y.re > pe ? y.re : pe;
-        const double t = (__builtin_ldexp(y.rv, y.re - et) - __builtin_ldexp(pv, pe - et)) / av;
-        double rv = (t > 0.0 && __builtin_isfinite(t)) ? t : 0.0;    /* NaN: 0 */
-        int re = et - ae;
-        x_norm1(rv, re);
-        if (!x_less(rv, re, x.rv, x.re)) { rv = x.rv; re = x.re; }
-        const int la = ea < 0 ? -ea : ea, lb = eb < 0 ? -eb : eb;
-        if (la > kXBlaExpLim || lb > kXBlaExpLim) {
-            rv = 0.0; re = kXZero;
-            a1 = make_double2(0.0, 0.0); a2 = a1; ea = kXZero;
-            b1 = a1; b2 = a1; eb = kXZero;
-        }
-        const uint32_t e = off + j;
-        XRad out;
-        out.v = (float)x_trunc24(rv); out.e = re;
-        r[e] = out;
-        ab[4 * e] = a1;
-        ab[4 * e + 1] = a2;
-        ab[4 * e + 2] = b1;
-        ab[4 * e + 3] = b2;
-        abe[e] = make_int2(ea, eb);
-    }
-}
-
-/* deep_orbit_ship_x with BLA: deep_orbit_x_bla's loop -- u for the loop index, its probe on the 8-byte radius with the
- * pre-filter dz.e + 51 < E (no level's r exceeds the single step's 2^-53 |Z_m|: the fold caps only lower it), its reload of
- * Z_m, Z_{m+1} in the mode a step leaves the lane in -- around the ship's steps: the BLA step is the real 2x2 map in extended
- * arithmetic, its nine loads inside the taken branch; the single steps are deep_orbit_ship_x's, operation for operation. */
-__device__ __forceinline__ void deep_orbit_ship_x_bla(const DeepXArgs& AA, const ShipXBlaTable& T, const double cx,
-                                                      const double cy, const int ec, bool live, int& esc, double& er2,
-                                                      uint32_t& nsingle, uint32_t& nbla)
-{
-    const DeepArgs& A = AA.d;
-    const double2* __restrict__ orbit = A.orbit;
-    const double2* __restrict__ mant = AA.mant;
-    const int32_t* __restrict__ exp2 = AA.exp2;
-    const XRad* __restrict__ tr = T.r;
-    const int N = A.n_ref, max_iter = A.max_iter, K = T.levels;
-    const uint32_t n1 = (uint32_t)(N - 1);
-    const double B2 = A.B2;
-    const double cpx = (cx != 0.0 && __builtin_amdgcn_frexp_exp(cx) + ec > -1022) ? __builtin_ldexp(cx, ec) : 0.0;
-    const double cpy = (cy != 0.0 && __builtin_amdgcn_frexp_exp(cy) + ec > -1022) ? __builtin_ldexp(cy, ec) : 0.0;
-    double dzx = 0.0, dzy = 0.0;                                 /* plain: dz; extended: its mantissas */
-    int ed = kXZero;
-    bool ext = true;
-    double Zx = 0.0, Zy = 0.0;                                   /* Z_m, in the lane's mode */
-    int eZ = kXZero;
-    const double2 z1 = mant[1];
-    const int e1 = exp2[1];
-    double Znx = z1.x, Zny = z1.y;                               /* Z_{m+1} */
-    int eZn = e1;
-    int m = 0, u = 0;
-    esc = max_iter;
-    er2 = 0.0;
-    nsingle = 0u; nbla = 0u;
-    for (;;) {
-        if (__builtin_amdgcn_ballot_w64(live) == 0ull) break;
-        if (!live) continue;
-        const int mn = m + 2 <= N ? m + 2 : N;                   /* Z_{m+2}, for the single step after this one */
-        int k = 0;
-        uint32_t e = 0u;
-        double qx = dzx, qy = dzy;                               /* dz, extended and normalised */
-        int qe = ed;
-        if (m >= 1) {
-            if (!ext) { qe = 0; x_norm(qx, qy, qe); }
-            const int eZm = (ext ? eZ : 0) + __builtin_amdgcn_frexp_exp(fmax(fabs(Zx), fabs(Zy)));
-            if (qe + 51 < eZm) {
-                const double dz2 = qx * qx + qy * qy;
-                const uint32_t mm = (uint32_t)(m - 1);
-                int kk = mm ? __builtin_ctz(mm) : K;
-                kk = kk < K ? kk : K;
-                const int kn = 31 - __builtin_clz((uint32_t)(N - m));
-                const int ki = 31 - __builtin_clz((uint32_t)(max_iter - u));
-                kk = kk < kn ? kk : kn;
-                kk = kk < ki ? kk : ki;
-                for (; kk >= 1; --kk) {
-                    const uint32_t ek = bla_offset(n1, kk) + (mm >> kk);
-                    const XRad r = tr[ek];
-                    const double rv = (double)r.v;
-                    if (dz2 < __builtin_ldexp(rv * rv, 2 * (r.e - qe))) { k = kk; e = ek; break; }
-                }
-            }
-        }
-        double ax, ay;                                           /* the next dz */
-        int ea = 0;
-        bool reb;
-        if (k > 0 || ext) {
-            double nx, ny, Wx, Wy;                               /* n and Z at the new m */
-            int en, eW, eZnn = 0;
-            double2 Znn = make_double2(0.0, 0.0);
-            if (k > 0) {
-                const double2 a1 = T.ab[4 * e], a2 = T.ab[4 * e + 1], b1 = T.ab[4 * e + 2], b2 = T.ab[4 * e + 3];
-                const int2 ee = T.abe[e];
-                const double px = a1.x * qx + a1.y * qy, py = a2.x * qx + a2.y * qy;
-                const double sx = b1.x * cx + b1.y * cy, sy = b2.x * cx + b2.y * cy;
-                const int ep = ee.x + qe, es = ee.y + ec;
-                en = ep > es ? ep : es;
-                nx = __builtin_ldexp(px, ep - en) + __builtin_ldexp(sx, es - en);
-                ny = __builtin_ldexp(py, ep - en) + __builtin_ldexp(sy, es - en);
-                m += 1 << k;
-                u += 1 << k;
-                ++nbla;
-                const double2 Wm = mant[m];
-                Wx = Wm.x; Wy = Wm.y; eW = exp2[m];
-            } else {
-                Znn = mant[mn];
-                eZnn = exp2[mn];
-                const double fx = ship_fold_x(Zx, eZ - ed, dzx), fy = ship_fold_x(Zy, eZ - ed, dzy);
-                const int et = eZ + 1 > ed ? eZ + 1 : ed;
-                const double tx = __builtin_ldexp(fabs(Zx), eZ + 1 - et) + __builtin_ldexp(fx, ed - et);
-                const double ty = __builtin_ldexp(fabs(Zy), eZ + 1 - et) + __builtin_ldexp(fy, ed - et);
-                const double px = tx * fx - ty * fy;
-                const double py = tx * fy + ty * fx;
-                const int ep = et + ed;
-                en = ep > ec ? ep : ec;
-                nx = __builtin_ldexp(px, ep - en) + __builtin_ldexp(cx, ec - en);
-                ny = __builtin_ldexp(py, ep - en) + __builtin_ldexp(cy, ec - en);
-                ++m;
-                ++u;
-                ++nsingle;
-                Wx = Znx; Wy = Zny; eW = eZn;
-            }
-            const int ez = eW > en ? eW : en;
-            const double zx = __builtin_ldexp(Wx, eW - ez) + __builtin_ldexp(nx, en - ez);
-            const double zy = __builtin_ldexp(Wy, eW - ez) + __builtin_ldexp(ny, en - ez);
-            const double r2 = zx * zx + zy * zy;
-            const double r2d = __builtin_ldexp(r2, 2 * ez);
-            if (r2d > B2) {
-                esc = u - 1; er2 = r2d; live = false;             /* the last update the step covered */
-                continue;
-            }
-            reb = r2 < __builtin_ldexp(nx * nx + ny * ny, 2 * (en - ez)) || m == N;
-            ax = reb ? zx : nx; ay = reb ? zy : ny; ea = reb ? ez : en;
-            x_norm(ax, ay, ea);
-            if (reb) m = 0;
-            if (ea <= kXThr) {                                    /* extended from here */
-                dzx = ax; dzy = ay; ed = ea;
-                ext = true;
-                if (reb) {
-                    Zx = 0.0; Zy = 0.0; eZ = kXZero; Znx = z1.x; Zny = z1.y; eZn = e1;
-                } else if (k == 0) {
-                    Zx = Znx; Zy = Zny; eZ = eZn; Znx = Znn.x; Zny = Znn.y; eZn = eZnn;
-                } else {                                          /* m < N here */
-                    const double2 b = mant[m + 1];
-                    Zx = Wx; Zy = Wy; eZ = eW; Znx = b.x; Zny = b.y; eZn = exp2[m + 1];
-                }
-            } else {                                              /* plain from here (m < N) */
-                const double2 a = orbit[m], b = orbit[m + 1];
-                dzx = __builtin_ldexp(ax, ea); dzy = __builtin_ldexp(ay, ea);
-                ext = false;
-                Zx = a.x; Zy = a.y; Znx = b.x; Zny = b.y;
-            }
-        } else {
-            const double2 Znn = orbit[mn];
-            const double X2 = Zx + Zx, Y2 = Zy + Zy;
-            const double fx = ship_fold(Zx, X2, dzx), fy = ship_fold(Zy, Y2, dzy);
-            const double tx = fabs(X2) + fx, ty = fabs(Y2) + fy;     /* |X| + |X| = |X + X| */
-            const double nx = (tx * fx - ty * fy) + cpx;
-            const double ny = (tx * fy + ty * fx) + cpy;
-            ++m;
-            ++u;
-            ++nsingle;
-            const double zx = Znx + nx, zy = Zny + ny;
-            const double r2 = zx * zx + zy * zy;
-            if (r2 > B2) {
-                esc = u - 1; er2 = r2; live = false;
-                continue;
-            }
-            reb = r2 < nx * nx + ny * ny || m == N;
-            ax = reb ? zx : nx; ay = reb ? zy : ny;
-            if (reb) m = 0;
-            if (!(fmax(fabs(ax), fabs(ay)) < 0x1p-400)) {         /* stays plain */
-                dzx = ax; dzy = ay;
-                if (reb) {
-                    const double2 p1 = orbit[1];
-                    Zx = 0.0; Zy = 0.0; Znx = p1.x; Zny = p1.y;
-                } else {
-                    Zx = Znx; Zy = Zny; Znx = Znn.x; Zny = Znn.y;
-                }
-            } else {                                              /* turns extended (m < N) */
-                const double2 a = mant[m], b = mant[m + 1];
-                x_norm(ax, ay, ea);
-                dzx = ax; dzy = ay; ed = ea;
-                ext = true;
-                Zx = a.x; Zy = a.y; eZ = exp2[m]; Znx = b.x; Zny = b.y; eZn = exp2[m + 1];
-            }
-        }
-        if (u >= max_iter) live = false;                          /* esc stays max_iter */
-    }
-}
-
-__device__ __forceinline__ const DeepArgs& deep_args(const DeepArgs& A) { return A; }
-__device__ __forceinline__ const DeepArgs& deep_args(const DeepXArgs& A) { return A.d; }
-__device__ __forceinline__ const DeepArgs& deep_args(const DeepBlaArgs& A) { return A.d; }
-__device__ __forceinline__ const DeepArgs& deep_args(const DeepXBlaArgs& A) { return A.x.d; }
-__device__ __forceinline__ const DeepArgs& deep_args(const DeepShipArgs& A) { return A.d; }
-__device__ __forceinline__ const DeepArgs& deep_args(const DeepShipBlaArgs& A) { return A.s.d; }
-__device__ __forceinline__ const DeepArgs& deep_args(const DeepShipXArgs& A) { return A.x.d; }
-__device__ __forceinline__ const DeepArgs& deep_args(const DeepShipXBlaArgs& A) { return A.s.x.d; }
-__device__ __forceinline__ const DeepXArgs& deepx_args(const DeepXArgs& A) { return A; }
-__device__ __forceinline__ const DeepXArgs& deepx_args(const DeepXBlaArgs& A) { return A.x; }
-__device__ __forceinline__ const DeepXArgs& deepx_args(const DeepShipXArgs& A) { return A.x; }
-__device__ __forceinline__ const DeepXArgs& deepx_args(const DeepShipXBlaArgs& A) { return A.s.x; }
+/* ---- the kernel --------------------------------------------------------------------------------------------------------
+ * What an argument block is made of */
+__host__ __device__ __forceinline__ const DeepArgs& deep_args(const DeepArgs& A) { return A; }
+__host__ __device__ __forceinline__ const DeepArgs& deep_args(const DeepXArgs& A) { return A.d; }
+__host__ __device__ __forceinline__ const DeepArgs& deep_args(const DeepBlaArgs& A) { return A.d; }
+__host__ __device__ __forceinline__ const DeepArgs& deep_args(const DeepXBlaArgs& A) { return A.x.d; }
+__host__ __device__ __forceinline__ const DeepArgs& deep_args(const DeepShipArgs& A) { return A.d; }
+__host__ __device__ __forceinline__ const DeepArgs& deep_args(const DeepShipBlaArgs& A) { return A.s.d; }
+__host__ __device__ __forceinline__ const DeepArgs& deep_args(const DeepShipXArgs& A) { return A.x.d; }
+__host__ __device__ __forceinline__ const DeepArgs& deep_args(const DeepShipXBlaArgs& A) { return A.s.x.d; }
+__host__ __device__ __forceinline__ const DeepXArgs& deepx_args(const DeepXArgs& A) { return A; }
+__host__ __device__ __forceinline__ const DeepXArgs& deepx_args(const DeepXBlaArgs& A) { return A.x; }
+__host__ __device__ __forceinline__ const DeepXArgs& deepx_args(const DeepShipXArgs& A) { return A.x; }
+__host__ __device__ __forceinline__ const DeepXArgs& deepx_args(const DeepShipXBlaArgs& A) { return A.s.x; }
 __device__ __forceinline__ double ship_log_bailout(const DeepShipArgs& A) { return A.log_bailout; }
 __device__ __forceinline__ double ship_log_bailout(const DeepShipBlaArgs& A) { return A.s.log_bailout; }
 __device__ __forceinline__ double ship_log_bailout(const DeepShipXArgs& A) { return A.log_bailout; }
 __device__ __forceinline__ double ship_log_bailout(const DeepShipXBlaArgs& A) { return A.s.log_bailout; }
 
-/* deep_kernel<DeepArgs>: the plain step; deep_kernel<DeepBlaArgs>: with BLA (deep_orbit_bla, the step counts);
- * deep_kernel<DeepXArgs>: extended-exponent deltas (deep_orbit_x); deep_kernel<DeepXBlaArgs>: those with BLA
- * (deep_orbit_x_bla, the step counts); deep_kernel<DeepShipArgs>: the Burning Ship (deep_orbit_ship, its viewport map and
- * colour stage); deep_kernel<DeepShipBlaArgs>: the ship with BLA (deep_orbit_ship_bla, the step counts);
- * deep_kernel<DeepShipXArgs>: the ship with extended-exponent deltas (deep_orbit_ship_x, the ship's map and colour stage);
- * deep_kernel<DeepShipXBlaArgs>: those with BLA (deep_orbit_ship_x_bla, the step counts) */
+template <class T, class... U>
+constexpr bool is_any_of = (std::is_same<T, U>::value || ...);
+
+/* ARGS names the loop: Deep[Ship][X][Bla]Args = the formula, extended-exponent deltas, BLA (with the step counts) */
 template <class ARGS>
 __global__ void __launch_bounds__(kBlockThreads)
 deep_kernel(const ARGS AA)
 {
-    constexpr bool XBLA = std::is_same<ARGS, DeepXBlaArgs>::value;
-    constexpr bool SHIPBLA = std::is_same<ARGS, DeepShipBlaArgs>::value;
-    constexpr bool SHIPXBLA = std::is_same<ARGS, DeepShipXBlaArgs>::value;
-    constexpr bool BLA = std::is_same<ARGS, DeepBlaArgs>::value || XBLA || SHIPBLA || SHIPXBLA;
-    constexpr bool X = std::is_same<ARGS, DeepXArgs>::value || XBLA;
-    constexpr bool SHIPX = std::is_same<ARGS, DeepShipXArgs>::value || SHIPXBLA;
-    constexpr bool SHIP = std::is_same<ARGS, DeepShipArgs>::value || SHIPBLA || SHIPX;
-    constexpr int FRACTAL = SHIP ? 2 : 0;                         /* the colour stage: shade() / colour_of() */
+    constexpr bool BLA = is_any_of<ARGS, DeepBlaArgs, DeepXBlaArgs, DeepShipBlaArgs, DeepShipXBlaArgs>;
+    constexpr bool X = is_any_of<ARGS, DeepXArgs, DeepXBlaArgs, DeepShipXArgs, DeepShipXBlaArgs>;
+    constexpr bool SHIP = is_any_of<ARGS, DeepShipArgs, DeepShipBlaArgs, DeepShipXArgs, DeepShipXBlaArgs>;
+    using F = std::conditional_t<SHIP, ShipFormula, MandelFormula>;
+    constexpr int FRACTAL = F::kFractal;
     const DeepArgs& A = deep_args(AA);
     __shared__ LdsBlock S;
     __shared__ double2 log2_lds[kLog2Entries];
     if (threadIdx.x == 0) S.pal = A.pal;
-    if constexpr (SHIP) {
+    if constexpr (F::kLogBailoutLds) {
         if (threadIdx.x == 0) S.log_bailout = ship_log_bailout(AA);
     }
     reinterpret_cast<double*>(log2_lds)[threadIdx.x] = reinterpret_cast<const double*>(A.log2_tab)[threadIdx.x];
@@ -1397,7 +1077,9 @@ deep_kernel(const ARGS AA)
     const uint32_t lane = threadIdx.x & (kWave - 1);
     const int W = A.g.W, H = A.g.H;
     const int aa = A.aa > 1 ? A.aa : 1;
-    const double resx = (double)W, resy = (double)H, zoom = A.zoom;
+    const double resx = (double)W, resy = (double)H;
+    double zs = A.zoom;                                           /* extended: the zoom's mantissa, its exponent goes to dc.e */
+    if constexpr (X) zs = deepx_args(AA).zm;
     const double2 z1 = A.orbit[1];
     const bool want_rgb = A.rgba != nullptr;
     const bool want_nu = want_rgb || A.nu != nullptr;
@@ -1409,76 +1091,23 @@ deep_kernel(const ARGS AA)
         int it0 = 0;
         const int nsamp = aa * aa;
         for (int s = 0; s < nsamp; ++s) {
-            const int sy = s / aa, sx = s - sy * aa;                                   /* mandelbrot.comp:219-230 */
-            const double pxs = (double)px + (double)sx / (double)aa;
-            const double pys = (double)py + (double)sy / (double)aa;
-            const double dcx = ((pxs - 0.5 * resx) / resy) * zoom;                     /* :149-151, less the centre */
-            const double dcy = ((pys - 0.5 * resy) / resy) * zoom;
             int esc;
             double r2;
-            if constexpr (SHIP) {                                 /* the map of tile_kernel's Burning Ship path, less the centre */
-                const int ux = s / aa, uy = s - ux * aa;          /* burning_ship.comp:337-344: sx outer */
-                double uvx = (double)px / resx, uvy = (double)py / resy;
-                if (aa > 1) {
-                    const double pixel_size = 1.0 / resx;
-                    const double sample_offset = pixel_size / (double)aa;
-                    const double centre = sample_offset * (double)(aa - 1) * 0.5;
-                    uvx = uvx + ((double)ux * sample_offset - centre) / resx;
-                    uvy = uvy + ((double)uy * sample_offset - centre) / resy;
-                }
-                double zs = zoom;                                 /* extended: the zoom's mantissa, its exponent goes to dc.e */
-                if constexpr (SHIPX) zs = deepx_args(AA).zm;
-                const double sdx = (uvx - 0.5) * zs * (resx / resy);
-                const double sdy = (uvy - 0.5) * zs;
-                if constexpr (SHIPX) {
-                    double cx = inside ? sdx : 0.0, cy = inside ? sdy : 0.0;
-                    int ec = deepx_args(AA).ze;
-                    x_norm(cx, cy, ec);
-                    if constexpr (SHIPXBLA) {
-                        uint32_t np, nb;
-                        deep_orbit_ship_x_bla(deepx_args(AA), AA.t, cx, cy, ec, inside, esc, r2, np, nb);
-                        if (inside) {
-                            n_plain += np; n_bla += nb;
-                            n_upd += (unsigned long long)(esc < A.max_iter ? esc + 1 : A.max_iter);
-                        }
-                    } else {
-                        deep_orbit_ship_x(deepx_args(AA), cx, cy, ec, inside, esc, r2);
-                    }
-                } else if constexpr (SHIPBLA) {
-                    uint32_t np, nb;
-                    deep_orbit_ship_bla(A, AA.t, inside ? sdx : 0.0, inside ? sdy : 0.0, z1, inside, esc, r2, np, nb);
-                    if (inside) {
-                        n_plain += np; n_bla += nb;
-                        n_upd += (unsigned long long)(esc < A.max_iter ? esc + 1 : A.max_iter);
-                    }
-                } else {
-                    deep_orbit_ship(A, inside ? sdx : 0.0, inside ? sdy : 0.0, z1, inside, esc, r2);
-                }
-            } else if constexpr (X) {
-                const DeepXArgs& XA = deepx_args(AA);
-                double cx = ((pxs - 0.5 * resx) / resy) * XA.zm, cy = ((pys - 0.5 * resy) / resy) * XA.zm;
-                int ec = XA.ze;
-                if (!inside) { cx = 0.0; cy = 0.0; }
+            const double2 dc = F::dc(px, py, s, aa, resx, resy, zs);
+            double cx = inside ? dc.x : 0.0, cy = inside ? dc.y : 0.0;
+            uint32_t np = 0u, nb = 0u;
+            if constexpr (X) {
+                int ec = deepx_args(AA).ze;
                 x_norm(cx, cy, ec);
-                if constexpr (XBLA) {
-                    uint32_t np, nb;
-                    deep_orbit_x_bla(XA, AA.t, cx, cy, ec, inside, esc, r2, np, nb);
-                    if (inside) {
-                        n_plain += np; n_bla += nb;
-                        n_upd += (unsigned long long)(esc < A.max_iter ? esc + 1 : A.max_iter);
-                    }
-                } else {
-                    deep_orbit_x(XA, cx, cy, ec, inside, esc, r2);
-                }
-            } else if constexpr (BLA) {
-                uint32_t np, nb;
-                deep_orbit_bla(A, AA.t, inside ? dcx : 0.0, inside ? dcy : 0.0, z1, inside, esc, r2, np, nb);
-                if (inside) {
-                    n_plain += np; n_bla += nb;
-                    n_upd += (unsigned long long)(esc < A.max_iter ? esc + 1 : A.max_iter);
-                }
+                if constexpr (BLA) deep_orbit_x_bla<F>(deepx_args(AA), AA.t, cx, cy, ec, inside, esc, r2, np, nb);
+                else deep_orbit_x<F>(deepx_args(AA), cx, cy, ec, inside, esc, r2);
             } else {
-                deep_orbit(A, inside ? dcx : 0.0, inside ? dcy : 0.0, z1, inside, esc, r2);
+                if constexpr (BLA) deep_orbit_bla<F>(A, AA.t, cx, cy, z1, inside, esc, r2, np, nb);
+                else deep_orbit<F>(A, cx, cy, z1, inside, esc, r2);
+            }
+            if (BLA && inside) {
+                n_plain += np; n_bla += nb;
+                n_upd += (unsigned long long)(esc < A.max_iter ? esc + 1 : A.max_iter);
             }
             double nu;
             float rgb[3];

@@ -41,6 +41,36 @@ struct OrbitKey {
     float bailout;              /* compared by its bits */
 };
 
+enum { kMandel = 0, kShip = 1 };    /* the formula of a deep view: the index of its cache slots */
+
+/* One cache slot of reference orbits of deep views: the buffers and what they hold */
+struct DeepOrbit {
+    char* host;                 /* pinned upload buffer, cap points */
+    char* dev;
+    size_t cap;
+    int32_t len;                /* N + 1 */
+    OrbitKey key;               /* of dev */
+    uint64_t gen;               /* bumped whenever dev receives another orbit */
+    int wg_per_cu;              /* resident workgroups per CU of the slot's unflagged deep_kernel (0 = not asked yet) */
+};
+
+/* One BLA table of a cached orbit, and the step counts of the most recent render with its flag */
+struct BlaSlot {
+    void* r;                    /* r of every entry (cap): doubles, or XRad in an extended table */
+    double2* ab;                /* (A, B) of every entry (the formula's kAbPerEntry times cap); extended: their mantissas */
+    int2* abe;                  /* extended: their exponents (cap) */
+    size_t cap;                 /* entries */
+    bool valid;                 /* the key below describes the table */
+    uint64_t key_gen, key_dcv;  /* gen of its orbit; bits of dcmax, extended: of dcmax's mantissa */
+    int32_t key_dce;            /* extended: dcmax's exponent */
+    unsigned long long* steps_dev;     /* the kernel's three counters */
+    unsigned long long* steps_host;    /* pinned: their copy behind the most recent render with the flag */
+    bool have_steps;
+    hipEvent_t ev;              /* recorded behind every render with the flag (not while capturing): rebuilds wait for it */
+    bool ev_valid;
+    int wg_per_cu;              /* resident workgroups per CU of the slot's flagged deep_kernel (0 = not asked yet) */
+};
+
 struct fr_ctx {
     int device;
     int compute_units;
@@ -92,94 +122,14 @@ struct fr_ctx {
     uint32_t div_next;
     int phoenix_wg_per_cu[2];   /* resident workgroups per CU of phoenix_kernel<float> / <double> (0 = not asked yet) */
     int mandelbulb_wg_per_cu[2];  /* ... of mandelbulb_kernel<false> / <true> (0 = not asked yet) */
-    /* deep views (fr_render_deep): the most recent reference orbit, on the device, and what it was computed for */
-    double* deep_orbit_host;    /* pinned upload buffer, deep_orbit_cap points */
-    double2* deep_orbit_dev;    /* Z_0 .. Z_N */
-    size_t deep_orbit_cap;
-    int32_t deep_len;           /* N + 1 */
-    OrbitKey deep_key;          /* of deep_orbit_dev */
-    int deep_wg_per_cu;         /* resident workgroups per CU of deep_kernel<DeepArgs> (0 = not asked yet) */
-    uint64_t deep_gen;          /* bumped whenever deep_orbit_dev receives another orbit */
-    /* BLA (FR_FLAG_DEEP_BLA): the table of the cached orbit, and the step counts of the most recent BLA render */
-    double* bla_r;              /* r of every entry (bla_cap) */
-    double2* bla_ab;            /* A, B of every entry (2 bla_cap) */
-    size_t bla_cap;             /* entries */
-    bool bla_valid;             /* the key below describes the table */
-    uint64_t bla_key_gen, bla_key_dcmax;   /* deep_gen of its orbit, bits of dcmax */
-    unsigned long long* bla_steps_dev;     /* the kernel's three counters */
-    unsigned long long* bla_steps_host;    /* pinned: their copy behind the most recent BLA render */
-    bool have_bla_steps;
-    hipEvent_t ev_bla;          /* recorded behind every BLA render (not while capturing): table rebuilds wait for it */
-    bool ev_bla_valid;
-    int deep_bla_wg_per_cu;     /* resident workgroups per CU of deep_kernel<DeepBlaArgs> (0 = not asked yet) */
-    /* extended views (fr_render_deepx): their own orbit cache, in the extended storage.  One pinned and one device block
-     * of deepx_cap points each: the plain doubles, the mantissa pairs, the exponents, in this order. */
-    char* deepx_host;
-    char* deepx_dev;
-    size_t deepx_cap;
-    int32_t deepx_len;          /* N + 1 */
-    OrbitKey deepx_key;         /* of deepx_dev */
-    int deepx_wg_per_cu;        /* resident workgroups per CU of deep_kernel<DeepXArgs> (0 = not asked yet) */
-    uint64_t deepx_gen;         /* bumped whenever deepx_dev receives another orbit */
-    /* BLA for extended views (FR_FLAG_DEEPX_BLA): the table of the cached extended orbit and the step counts of the most
-     * recent such render -- the deepx path's own, nothing of it is shared with the fp64 table above */
-    XRad* xbla_r;               /* r of every entry (xbla_cap) */
-    double2* xbla_ab;           /* mantissas of A, B of every entry (2 xbla_cap) */
-    int2* xbla_abe;             /* their exponents (xbla_cap) */
-    size_t xbla_cap;            /* entries */
-    bool xbla_valid;            /* the key below describes the table */
-    uint64_t xbla_key_gen, xbla_key_dcv;   /* deepx_gen of its orbit, bits of dcmax's mantissa */
-    int32_t xbla_key_dce;                  /* dcmax's exponent */
-    unsigned long long* xbla_steps_dev;    /* the kernel's three counters */
-    unsigned long long* xbla_steps_host;   /* pinned: their copy behind the most recent render with the flag */
-    bool have_xbla_steps;
-    hipEvent_t ev_xbla;         /* recorded behind every render with the flag (not while capturing): rebuilds wait for it */
-    bool ev_xbla_valid;
-    int deepx_bla_wg_per_cu;    /* resident workgroups per CU of deep_kernel<DeepXBlaArgs> (0 = not asked yet) */
-    /* deep Burning Ship views (fr_render_deep_ship): their own orbit cache, as fr_render_deep's */
-    double* ship_orbit_host;    /* pinned upload buffer, ship_orbit_cap points */
-    double2* ship_orbit_dev;    /* Z_0 .. Z_N of the ship's recurrence */
-    size_t ship_orbit_cap;
-    int32_t ship_len;           /* N + 1 */
-    OrbitKey ship_key;          /* of ship_orbit_dev */
-    int ship_wg_per_cu;         /* resident workgroups per CU of deep_kernel<DeepShipArgs> (0 = not asked yet) */
-    uint64_t ship_gen;          /* bumped whenever ship_orbit_dev receives another orbit */
-    /* BLA for the ship (FR_FLAG_DEEP_SHIP_BLA): the table of the cached ship orbit and the step counts of the most recent
-     * such render -- the ship path's own, nothing of it is shared with the Mandelbrot tables above */
-    double* ship_bla_r;         /* r of every entry (ship_bla_cap) */
-    double2* ship_bla_ab;       /* the rows of A and of B of every entry (4 ship_bla_cap) */
-    size_t ship_bla_cap;        /* entries */
-    bool ship_bla_valid;        /* the key below describes the table */
-    uint64_t ship_bla_key_gen, ship_bla_key_dcmax;   /* ship_gen of its orbit, bits of dcmax */
-    unsigned long long* ship_bla_steps_dev;    /* the kernel's three counters */
-    unsigned long long* ship_bla_steps_host;   /* pinned: their copy behind the most recent render with the flag */
-    bool have_ship_bla_steps;
-    hipEvent_t ev_ship_bla;     /* recorded behind every render with the flag (not while capturing): rebuilds wait for it */
-    bool ev_ship_bla_valid;
-    int ship_bla_wg_per_cu;     /* resident workgroups per CU of deep_kernel<DeepShipBlaArgs> (0 = not asked yet) */
-    /* extended Burning Ship views (fr_render_deepx_ship): their own orbit cache, laid out as deepx_host / deepx_dev */
-    char* shipx_host;
-    char* shipx_dev;
-    size_t shipx_cap;
-    int32_t shipx_len;          /* N + 1 */
-    OrbitKey shipx_key;         /* of shipx_dev */
-    int shipx_wg_per_cu;        /* resident workgroups per CU of deep_kernel<DeepShipXArgs> (0 = not asked yet) */
-    uint64_t shipx_gen;         /* bumped whenever shipx_dev receives another orbit */
-    /* BLA for extended ship views (FR_FLAG_DEEPX_SHIP_BLA): the table of the cached extended ship orbit and the step counts of
-     * the most recent such render -- this path's own, nothing of it is shared with the three tables above */
-    XRad* shipx_bla_r;          /* r of every entry (shipx_bla_cap) */
-    double2* shipx_bla_ab;      /* the mantissa rows of A and of B of every entry (4 shipx_bla_cap) */
-    int2* shipx_bla_abe;        /* their exponents (shipx_bla_cap) */
-    size_t shipx_bla_cap;       /* entries */
-    bool shipx_bla_valid;       /* the key below describes the table */
-    uint64_t shipx_bla_key_gen, shipx_bla_key_dcv;   /* shipx_gen of its orbit, bits of dcmax's mantissa */
-    int32_t shipx_bla_key_dce;                       /* dcmax's exponent */
-    unsigned long long* shipx_bla_steps_dev;    /* the kernel's three counters */
-    unsigned long long* shipx_bla_steps_host;   /* pinned: their copy behind the most recent render with the flag */
-    bool have_shipx_bla_steps;
-    hipEvent_t ev_shipx_bla;    /* recorded behind every render with the flag (not while capturing): rebuilds wait for it */
-    bool ev_shipx_bla_valid;
-    int shipx_bla_wg_per_cu;    /* resident workgroups per CU of deep_kernel<DeepShipXBlaArgs> (0 = not asked yet) */
+    /* deep views, per formula (kMandel, kShip): the most recent reference orbit and its BLA table, for the fp64 views
+     * (fr_render_deep, fr_render_deep_ship) and for the extended ones (fr_render_deepx, fr_render_deepx_ship).  The four
+     * paths share nothing. */
+    DeepOrbit deep[2];          /* plain doubles Z_0 .. Z_N: 2 cap doubles pinned, cap double2 on the device */
+    DeepOrbit deepx[2];         /* the extended storage.  One pinned and one device block of cap points each: the plain
+                                 * doubles, the mantissa pairs, the exponents, in this order. */
+    BlaSlot bla[2];             /* FR_FLAG_DEEP_BLA, FR_FLAG_DEEP_SHIP_BLA: the tables of deep[] */
+    BlaSlot blax[2];            /* FR_FLAG_DEEPX_BLA, FR_FLAG_DEEPX_SHIP_BLA: the tables of deepx[] */
 };
 
 #define FR_HIP_TRY(expr)                                                               \
@@ -227,10 +177,10 @@ extern "C" int fr_ctx_create(int device_ordinal, fr_ctx** out)
         (e2 = hipEventCreate(&c->ev_begin)) != hipSuccess ||
         (e2 = hipEventCreate(&c->ev_end)) != hipSuccess ||
         (e2 = hipEventCreateWithFlags(&c->ev_order, hipEventDisableTiming)) != hipSuccess ||
-        (e2 = hipEventCreateWithFlags(&c->ev_bla, hipEventDisableTiming)) != hipSuccess ||
-        (e2 = hipEventCreateWithFlags(&c->ev_xbla, hipEventDisableTiming)) != hipSuccess ||
-        (e2 = hipEventCreateWithFlags(&c->ev_ship_bla, hipEventDisableTiming)) != hipSuccess ||
-        (e2 = hipEventCreateWithFlags(&c->ev_shipx_bla, hipEventDisableTiming)) != hipSuccess ||
+        (e2 = hipEventCreateWithFlags(&c->bla[kMandel].ev, hipEventDisableTiming)) != hipSuccess ||
+        (e2 = hipEventCreateWithFlags(&c->bla[kShip].ev, hipEventDisableTiming)) != hipSuccess ||
+        (e2 = hipEventCreateWithFlags(&c->blax[kMandel].ev, hipEventDisableTiming)) != hipSuccess ||
+        (e2 = hipEventCreateWithFlags(&c->blax[kShip].ev, hipEventDisableTiming)) != hipSuccess ||
         (e2 = hipMalloc((void**)&c->d_ctrl, (kCtrlWords + (size_t)(kFeedbackShards + 2) * kShardStrideWords) * sizeof(uint32_t))) != hipSuccess ||
         (e2 = hipMemset(c->d_ctrl, 0, (kCtrlWords + (size_t)(kFeedbackShards + 2) * kShardStrideWords) * sizeof(uint32_t))) != hipSuccess ||
         (e2 = hipHostMalloc((void**)&c->overflow_host, 64, hipHostMallocMapped)) != hipSuccess ||
@@ -265,44 +215,20 @@ extern "C" void fr_ctx_destroy(fr_ctx* c)
     if (c->frame_buf) (void)hipFree(c->frame_buf);
     if (c->orbit_host) (void)hipHostFree(c->orbit_host);
     if (c->orbit_dev) (void)hipFree(c->orbit_dev);
-    if (c->deep_orbit_host) (void)hipHostFree(c->deep_orbit_host);
-    if (c->deep_orbit_dev) (void)hipFree(c->deep_orbit_dev);
-    free(c->deep_key.x);
-    free(c->deep_key.y);
-    if (c->deepx_host) (void)hipHostFree(c->deepx_host);
-    if (c->deepx_dev) (void)hipFree(c->deepx_dev);
-    free(c->deepx_key.x);
-    free(c->deepx_key.y);
-    if (c->shipx_host) (void)hipHostFree(c->shipx_host);
-    if (c->shipx_dev) (void)hipFree(c->shipx_dev);
-    free(c->shipx_key.x);
-    free(c->shipx_key.y);
-    if (c->ship_orbit_host) (void)hipHostFree(c->ship_orbit_host);
-    if (c->ship_orbit_dev) (void)hipFree(c->ship_orbit_dev);
-    free(c->ship_key.x);
-    free(c->ship_key.y);
-    if (c->bla_r) (void)hipFree(c->bla_r);
-    if (c->bla_ab) (void)hipFree(c->bla_ab);
-    if (c->bla_steps_dev) (void)hipFree(c->bla_steps_dev);
-    if (c->bla_steps_host) (void)hipHostFree(c->bla_steps_host);
-    if (c->ev_bla) (void)hipEventDestroy(c->ev_bla);
-    if (c->xbla_r) (void)hipFree(c->xbla_r);
-    if (c->xbla_ab) (void)hipFree(c->xbla_ab);
-    if (c->xbla_abe) (void)hipFree(c->xbla_abe);
-    if (c->xbla_steps_dev) (void)hipFree(c->xbla_steps_dev);
-    if (c->xbla_steps_host) (void)hipHostFree(c->xbla_steps_host);
-    if (c->ev_xbla) (void)hipEventDestroy(c->ev_xbla);
-    if (c->ship_bla_r) (void)hipFree(c->ship_bla_r);
-    if (c->ship_bla_ab) (void)hipFree(c->ship_bla_ab);
-    if (c->ship_bla_steps_dev) (void)hipFree(c->ship_bla_steps_dev);
-    if (c->ship_bla_steps_host) (void)hipHostFree(c->ship_bla_steps_host);
-    if (c->ev_ship_bla) (void)hipEventDestroy(c->ev_ship_bla);
-    if (c->shipx_bla_r) (void)hipFree(c->shipx_bla_r);
-    if (c->shipx_bla_ab) (void)hipFree(c->shipx_bla_ab);
-    if (c->shipx_bla_abe) (void)hipFree(c->shipx_bla_abe);
-    if (c->shipx_bla_steps_dev) (void)hipFree(c->shipx_bla_steps_dev);
-    if (c->shipx_bla_steps_host) (void)hipHostFree(c->shipx_bla_steps_host);
-    if (c->ev_shipx_bla) (void)hipEventDestroy(c->ev_shipx_bla);
+    for (DeepOrbit* o : {&c->deep[kMandel], &c->deep[kShip], &c->deepx[kMandel], &c->deepx[kShip]}) {
+        if (o->host) (void)hipHostFree(o->host);
+        if (o->dev) (void)hipFree(o->dev);
+        free(o->key.x);
+        free(o->key.y);
+    }
+    for (BlaSlot* t : {&c->bla[kMandel], &c->bla[kShip], &c->blax[kMandel], &c->blax[kShip]}) {
+        if (t->r) (void)hipFree(t->r);
+        if (t->ab) (void)hipFree(t->ab);
+        if (t->abe) (void)hipFree(t->abe);
+        if (t->steps_dev) (void)hipFree(t->steps_dev);
+        if (t->steps_host) (void)hipHostFree(t->steps_host);
+        if (t->ev) (void)hipEventDestroy(t->ev);
+    }
     if (c->ev_begin) (void)hipEventDestroy(c->ev_begin);
     if (c->ev_end) (void)hipEventDestroy(c->ev_end);
     if (c->ev_order) (void)hipEventDestroy(c->ev_order);
@@ -824,22 +750,12 @@ static int orbit_key_store(OrbitKey& k, const char* x, const char* y, int32_t bi
     return FR_OK;
 }
 
-/* One cache slot of plain-double orbits (fr_render_deep's, fr_render_deep_ship's): the buffers, what they hold, the host
- * function that computes the orbit, and the event behind the slot's most recent BLA render */
-struct OrbitSlot {
-    double*& host;
-    double2*& dev;
-    size_t& cap;
-    int32_t& len;
-    OrbitKey& key;
-    uint64_t& gen;
-    int (*compute)(const fr_deep_view*, double, int32_t, float, double*, int32_t*);
-    hipEvent_t ev_bla;
-    const bool& ev_bla_valid;
-};
-
-static int orbit_slot_fill(fr_ctx* c, const OrbitSlot& o, const fr_params* p, const fr_deep_view* v, hipStream_t stream)
+/* fp64 views: the plain-double orbit of the view in the formula's cache slot (fr_render_deep's, fr_render_deep_ship's) unless
+ * the slot holds it already */
+static int orbit_slot_fill(fr_ctx* c, int f, const fr_params* p, const fr_deep_view* v, hipStream_t stream)
 {
+    DeepOrbit& o = c->deep[f];
+    const BlaSlot& t = c->bla[f];
     const int32_t bits = v->frac_bits ? v->frac_bits : fr_deep_frac_bits(p->zoom);
     const int32_t max_iter = p->max_iterations;
     if (orbit_key_matches(o.key, v->center_x, v->center_y, bits, max_iter, p->bailout)) return FR_OK;
@@ -848,7 +764,7 @@ static int orbit_slot_fill(fr_ctx* c, const OrbitSlot& o, const fr_params* p, co
     FR_HIP_TRY(hipStreamSynchronize(stream));
     FR_HIP_TRY(hipStreamSynchronize(c->stream));
     if (c->have_render && c->last_stream != stream) FR_HIP_TRY(hipStreamSynchronize(c->last_stream));
-    if (o.ev_bla_valid) FR_HIP_TRY(hipEventSynchronize(o.ev_bla));        /* the slot's last BLA render, wherever it went */
+    if (t.ev_valid) FR_HIP_TRY(hipEventSynchronize(t.ev));                /* the slot's last BLA render, wherever it went */
     o.key.valid = false;
     ++o.gen;
     const size_t need = (size_t)max_iter + 1;
@@ -861,7 +777,8 @@ static int orbit_slot_fill(fr_ctx* c, const OrbitSlot& o, const fr_params* p, co
         o.cap = need;
     }
     int32_t len = 0;
-    const int st = o.compute(v, p->zoom, max_iter, p->bailout, o.host, &len);
+    const int st = (f == kShip ? fr_deep_ship_reference_orbit : fr_deep_reference_orbit)(v, p->zoom, max_iter, p->bailout,
+                                                                                         (double*)o.host, &len);
     if (st != FR_OK) return st;
     FR_HIP_TRY(hipMemcpyAsync(o.dev, o.host, (size_t)len * sizeof(double2), hipMemcpyHostToDevice, stream));
     FR_HIP_TRY(hipStreamSynchronize(stream));     /* a later render of this view may go to another stream */
@@ -870,100 +787,134 @@ static int orbit_slot_fill(fr_ctx* c, const OrbitSlot& o, const fr_params* p, co
     return ks;
 }
 
-static int deep_orbit_for(fr_ctx* c, const fr_params* p, const fr_deep_view* v, hipStream_t stream)
+/* The frame's dcmax (the whole frame's W, H; each formula's own bound, see the header); zs = the zoom or its mantissa */
+static double bla_dcmax(int f, double zs, double w, double h)
 {
-    const OrbitSlot o = {c->deep_orbit_host, c->deep_orbit_dev, c->deep_orbit_cap, c->deep_len, c->deep_key, c->deep_gen,
-                         fr_deep_reference_orbit, c->ev_bla, c->ev_bla_valid};
-    return orbit_slot_fill(c, o, p, v, stream);
+    const double a = w / h;
+    if (f == kMandel) return (1.0000001 * (0.5 * zs)) * sqrt(a * a + 1.0);
+    const double hx = 0.5 + 0.5 / (w * w);
+    const double hy = 0.5 + 0.5 / (w * h);
+    const double ex = hx * a;
+    return (1.0000001 * zs) * sqrt(ex * ex + hy * hy);
 }
 
-static int ship_orbit_for(fr_ctx* c, const fr_params* p, const fr_deep_view* v, hipStream_t stream)
+/* BLA: the table of the formula's cached orbit -- the extended one with x, the view's extended block -- for this frame's
+ * dcmax, built on `stream` unless the slot holds it.  A rebuild overwrites the buffers in place behind the slot's last BLA
+ * render (its event: the render may have gone to another stream); growing them frees the old ones, so that waits on the host
+ * first. */
+static int bla_table_for(fr_ctx* c, int f, const DeepArgs& d, const DeepXArgs* x, hipStream_t stream, int* levels)
 {
-    const OrbitSlot o = {c->ship_orbit_host, c->ship_orbit_dev, c->ship_orbit_cap, c->ship_len, c->ship_key, c->ship_gen,
-                         fr_deep_ship_reference_orbit, c->ev_ship_bla, c->ev_ship_bla_valid};
-    return orbit_slot_fill(c, o, p, v, stream);
-}
-
-/* BLA: the table of the cached orbit for this frame's dcmax (the whole frame's W, H and zoom), built on `stream` unless
- * the context holds it.  A rebuild overwrites the buffer in place behind the last BLA render (ev_bla: it may have gone to
- * another stream); growing it frees the old one, so that waits on the host first. */
-static int deep_bla_table_for(fr_ctx* c, const fr_params* p, uint32_t W, uint32_t H, hipStream_t stream, int* levels)
-{
-    const int32_t N = c->deep_len - 1;
+    BlaSlot& t = (x ? c->blax : c->bla)[f];
+    const DeepOrbit& o = (x ? c->deepx : c->deep)[f];
+    const int32_t N = o.len - 1;
     const int K = N > 1 ? 31 - __builtin_clz((uint32_t)(N - 1)) : 0;   /* floor(log2(N - 1)) */
     *levels = K;
     if (K == 0) return FR_OK;
-    const double a = (double)W / (double)H;
-    const double dcmax = (1.0000001 * (0.5 * p->zoom)) * sqrt(a * a + 1.0);
+    double dcv = bla_dcmax(f, x ? x->zm : d.zoom, (double)d.g.W, (double)d.g.H);
+    int32_t dce = 0;
+    if (x) {                                     /* as an extended real with the zoom pair, normalised: dcv in [0.5, 1) */
+        int de = 0;
+        dcv = frexp(dcv, &de);
+        dce = x->ze + de;
+    }
     uint64_t dbits;
-    memcpy(&dbits, &dcmax, sizeof(dbits));
-    if (c->bla_valid && c->bla_key_gen == c->deep_gen && c->bla_key_dcmax == dbits) return FR_OK;
-    c->bla_valid = false;
+    memcpy(&dbits, &dcv, sizeof(dbits));
+    if (t.valid && t.key_gen == o.gen && t.key_dcv == dbits && t.key_dce == dce) return FR_OK;
+    t.valid = false;
     const uint32_t n1 = (uint32_t)(N - 1);
     const size_t need = (size_t)(n1 - (uint32_t)__builtin_popcount(n1));     /* sum over k >= 1 of (N - 1) >> k */
-    if (need > c->bla_cap) {
+    if (need > t.cap) {
         FR_HIP_TRY(hipStreamSynchronize(stream));
         FR_HIP_TRY(hipStreamSynchronize(c->stream));
-        if (c->ev_bla_valid) FR_HIP_TRY(hipEventSynchronize(c->ev_bla));
-        if (c->bla_r) { (void)hipFree(c->bla_r); c->bla_r = nullptr; }
-        if (c->bla_ab) { (void)hipFree(c->bla_ab); c->bla_ab = nullptr; }
-        c->bla_cap = 0;
-        FR_HIP_TRY(hipMalloc((void**)&c->bla_r, need * sizeof(double)));
-        FR_HIP_TRY(hipMalloc((void**)&c->bla_ab, need * 2 * sizeof(double2)));
-        c->bla_cap = need;
-    } else if (c->ev_bla_valid) {
-        FR_HIP_TRY(hipStreamWaitEvent(stream, c->ev_bla, 0));
+        if (t.ev_valid) FR_HIP_TRY(hipEventSynchronize(t.ev));
+        if (t.r) { (void)hipFree(t.r); t.r = nullptr; }
+        if (t.ab) { (void)hipFree(t.ab); t.ab = nullptr; }
+        if (t.abe) { (void)hipFree(t.abe); t.abe = nullptr; }
+        t.cap = 0;
+        const size_t nab = f == kShip ? ShipFormula::kAbPerEntry : MandelFormula::kAbPerEntry;
+        FR_HIP_TRY(hipMalloc(&t.r, need * (x ? sizeof(XRad) : sizeof(double))));
+        FR_HIP_TRY(hipMalloc((void**)&t.ab, need * nab * sizeof(double2)));
+        if (x) FR_HIP_TRY(hipMalloc((void**)&t.abe, need * sizeof(int2)));
+        t.cap = need;
+    } else if (t.ev_valid) {
+        FR_HIP_TRY(hipStreamWaitEvent(stream, t.ev, 0));
     }
     for (int k = 1; k <= K; ++k) {
         const uint32_t cnt = n1 >> k;
         uint32_t grid = (cnt + kBlockThreads - 1) / kBlockThreads;
         const uint32_t cap = (uint32_t)c->compute_units * 8u;
         if (grid > cap) grid = cap;
-        hipLaunchKernelGGL(deep_bla_level_kernel, dim3(grid), dim3(kBlockThreads), 0, stream, c->deep_orbit_dev, N, k, dcmax,
-                           c->bla_r, c->bla_ab);
+        if (x)
+            hipLaunchKernelGGL(f == kShip ? deepx_ship_bla_level_kernel : deepx_bla_level_kernel, dim3(grid), dim3(kBlockThreads),
+                               0, stream, x->mant, x->exp2, N, k, dcv, dce, (XRad*)t.r, t.ab, t.abe);
+        else
+            hipLaunchKernelGGL(f == kShip ? deep_ship_bla_level_kernel : deep_bla_level_kernel, dim3(grid), dim3(kBlockThreads), 0,
+                               stream, d.orbit, N, k, dcv, (double*)t.r, t.ab);
         const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fr_set_error(FR_ERR_HIP, "BLA table launch failed: %s", hipGetErrorString(e));
+        if (e != hipSuccess)
+            return fr_set_error(FR_ERR_HIP, "%s%sBLA table launch failed: %s", x ? "extended " : "", f == kShip ? "ship " : "",
+                                hipGetErrorString(e));
     }
-    c->bla_key_gen = c->deep_gen;
-    c->bla_key_dcmax = dbits;
-    c->bla_valid = true;
+    t.key_gen = o.gen;
+    t.key_dcv = dbits;
+    t.key_dce = dce;
+    t.valid = true;
     return FR_OK;
 }
 
-/* FR_FLAG_DEEP_BLA: the table, then deep_kernel<DeepBlaArgs> on the same queue plan as deep_kernel (its own occupancy), its
- * counters cleared in front of it and copied to pinned memory behind it */
-static int enqueue_deep_bla(fr_ctx* c, const fr_params* p, const DeepArgs& d, hipStream_t stream)
+static void bla_table_args(BlaTable& a, const BlaSlot& t) { a.r = (const double*)t.r; a.ab = t.ab; }
+static void bla_table_args(BlaXTable& a, const BlaSlot& t) { a.r = (const XRad*)t.r; a.ab = t.ab; a.abe = t.abe; }
+
+template <class ARGS>
+static DeepArgs& deep_of(ARGS& a) { return const_cast<DeepArgs&>(deep_args(a)); }
+
+/* One pass of a deep view, `base` being the argument block of its unflagged kernel: deep_kernel<BASE> at the occupancy cached in
+ * wg_per_cu, or with `bla` the table, then deep_kernel<BLA> (BLA = {BASE, the table}) on the same queue plan at its slot's own
+ * occupancy, its counters cleared in front of it and copied to pinned memory behind it.  The slot's event is recorded behind
+ * every such render unless the stream is capturing: table rebuilds and orbit uploads wait for it. */
+template <class BLA, class BASE>
+static int launch_deep(fr_ctx* c, hipStream_t stream, const char* name, const char* bla_name, BASE& base, bool bla, int& wg_per_cu)
 {
-    DeepBlaArgs a;
-    memset(&a, 0, sizeof(a));
-    a.d = d;
-    int levels = 0;
-    const int ts = deep_bla_table_for(c, p, (uint32_t)d.g.W, (uint32_t)d.g.H, stream, &levels);
-    if (ts != FR_OK) return ts;
-    a.t.r = c->bla_r; a.t.ab = c->bla_ab; a.t.levels = levels;
-    if (!c->bla_steps_dev) {
-        FR_HIP_TRY(hipMalloc((void**)&c->bla_steps_dev, 3 * sizeof(unsigned long long)));
-        FR_HIP_TRY(hipHostMalloc((void**)&c->bla_steps_host, 3 * sizeof(unsigned long long)));
+    if (!bla) {
+        DeepArgs& d = deep_of(base);
+        return launch_one_pass(c, stream, name, deep_kernel<BASE>, base, d.g, d.q, wg_per_cu, false);
     }
-    a.t.steps = c->bla_steps_dev;
-    FR_HIP_TRY(hipMemsetAsync(c->bla_steps_dev, 0, 3 * sizeof(unsigned long long), stream));
-    const int st = launch_one_pass(c, stream, "deep_kernel<DeepBlaArgs>", deep_kernel<DeepBlaArgs>, a, a.d.g, a.d.q,
-                                   c->deep_bla_wg_per_cu, false);
+    constexpr int f = is_any_of<BASE, DeepShipArgs, DeepShipXArgs> ? kShip : kMandel;
+    constexpr bool ext = is_any_of<BASE, DeepXArgs, DeepShipXArgs>;
+    BLA a;
+    memset(&a, 0, sizeof(a));
+    auto& [b, tab] = a;
+    b = base;
+    DeepArgs& d = deep_of(a);
+    const DeepXArgs* x = nullptr;
+    if constexpr (ext) x = &deepx_args(a);
+    BlaSlot& t = (ext ? c->blax : c->bla)[f];
+    int levels = 0;
+    const int ts = bla_table_for(c, f, d, x, stream, &levels);
+    if (ts != FR_OK) return ts;
+    bla_table_args(tab, t);
+    tab.levels = levels;
+    if (!t.steps_dev) {
+        FR_HIP_TRY(hipMalloc((void**)&t.steps_dev, 3 * sizeof(unsigned long long)));
+        FR_HIP_TRY(hipHostMalloc((void**)&t.steps_host, 3 * sizeof(unsigned long long)));
+    }
+    tab.steps = t.steps_dev;
+    FR_HIP_TRY(hipMemsetAsync(t.steps_dev, 0, 3 * sizeof(unsigned long long), stream));
+    const int st = launch_one_pass(c, stream, bla_name, deep_kernel<BLA>, a, d.g, d.q, t.wg_per_cu, false);
     if (st != FR_OK) return st;
-    FR_HIP_TRY(hipMemcpyAsync(c->bla_steps_host, c->bla_steps_dev, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost,
-                              stream));
-    c->have_bla_steps = true;
+    FR_HIP_TRY(hipMemcpyAsync(t.steps_host, t.steps_dev, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+    t.have_steps = true;
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(stream, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusActive; }
-    c->ev_bla_valid = false;
+    t.ev_valid = false;
     if (cap == hipStreamCaptureStatusNone) {
-        FR_HIP_TRY(hipEventRecord(c->ev_bla, stream));
-        c->ev_bla_valid = true;
+        FR_HIP_TRY(hipEventRecord(t.ev, stream));
+        t.ev_valid = true;
     }
     return FR_OK;
 }
 
-/* everything of DeepArgs that enqueue_deep and enqueue_deepx fill alike: zoom and the orbit stay with the caller */
+/* everything of DeepArgs that enqueue_deep and enqueue_deepx_at fill alike: zoom and the orbit stay with the caller */
 static void fill_deep_args(DeepArgs& a, const fr_ctx* c, const fr_params* p, const TileGeom& g, float* rgba, void* nu,
                            int32_t* iter)
 {
@@ -982,161 +933,47 @@ static void fill_deep_args(DeepArgs& a, const fr_ctx* c, const fr_params* p, con
     a.rgba = reinterpret_cast<float4*>(rgba); a.nu = (double*)nu; a.iter = iter;
 }
 
-static int enqueue_deep(fr_ctx* c, const fr_params* p, const fr_deep_view* v, uint32_t W, uint32_t H, const fr_shard* shard,
+/* fr_render_deep (f = kMandel), fr_render_deep_ship (f = kShip) */
+static int enqueue_deep(fr_ctx* c, int f, const fr_params* p, const fr_deep_view* v, uint32_t W, uint32_t H, const fr_shard* shard,
                         float* rgba, void* nu, int32_t* iter, hipStream_t stream, bool out_frame)
 {
     fr_shard norm;
     uint32_t rows_local = 0;
     const int sh = begin_shard(c, shard, H, &norm, &rows_local);
     if (sh != FR_OK || rows_local == 0) return sh;
-    const int os = deep_orbit_for(c, p, v, stream);
+    const int os = orbit_slot_fill(c, f, p, v, stream);
     if (os != FR_OK) return os;
 
-    DeepArgs a;
-    memset(&a, 0, sizeof(a));
-    a.orbit = c->deep_orbit_dev; a.n_ref = c->deep_len - 1;
-    a.zoom = p->zoom;
-    fill_deep_args(a, c, p, tile_geom(W, H, rows_local, &norm, out_frame), rgba, nu, iter);
-
-    if (p->flags & FR_FLAG_DEEP_BLA) return enqueue_deep_bla(c, p, a, stream);
-    return launch_one_pass(c, stream, "deep_kernel<DeepArgs>", deep_kernel<DeepArgs>, a, a.g, a.q, c->deep_wg_per_cu, false);
-}
-
-/* ---- deep Burning Ship views (fr_render_deep_ship) --------------------------------------------------------------------
- * FR_FLAG_DEEP_SHIP_BLA: the table of the cached ship orbit for this frame's dcmax (the whole frame's W, H and zoom; the
- * ship's own bound, see the header), built on `stream` unless the context holds it -- deep_bla_table_for's rules on the ship
- * path's own buffers and event. */
-static int ship_bla_table_for(fr_ctx* c, const fr_params* p, uint32_t W, uint32_t H, hipStream_t stream, int* levels)
-{
-    const int32_t N = c->ship_len - 1;
-    const int K = N > 1 ? 31 - __builtin_clz((uint32_t)(N - 1)) : 0;   /* floor(log2(N - 1)) */
-    *levels = K;
-    if (K == 0) return FR_OK;
-    const double w = (double)W, h = (double)H;
-    const double a = w / h;
-    const double hx = 0.5 + 0.5 / (w * w);
-    const double hy = 0.5 + 0.5 / (w * h);
-    const double ex = hx * a;
-    const double dcmax = (1.0000001 * p->zoom) * sqrt(ex * ex + hy * hy);
-    uint64_t dbits;
-    memcpy(&dbits, &dcmax, sizeof(dbits));
-    if (c->ship_bla_valid && c->ship_bla_key_gen == c->ship_gen && c->ship_bla_key_dcmax == dbits) return FR_OK;
-    c->ship_bla_valid = false;
-    const uint32_t n1 = (uint32_t)(N - 1);
-    const size_t need = (size_t)(n1 - (uint32_t)__builtin_popcount(n1));     /* sum over k >= 1 of (N - 1) >> k */
-    if (need > c->ship_bla_cap) {
-        FR_HIP_TRY(hipStreamSynchronize(stream));
-        FR_HIP_TRY(hipStreamSynchronize(c->stream));
-        if (c->ev_ship_bla_valid) FR_HIP_TRY(hipEventSynchronize(c->ev_ship_bla));
-        if (c->ship_bla_r) { (void)hipFree(c->ship_bla_r); c->ship_bla_r = nullptr; }
-        if (c->ship_bla_ab) { (void)hipFree(c->ship_bla_ab); c->ship_bla_ab = nullptr; }
-        c->ship_bla_cap = 0;
-        FR_HIP_TRY(hipMalloc((void**)&c->ship_bla_r, need * sizeof(double)));
-        FR_HIP_TRY(hipMalloc((void**)&c->ship_bla_ab, need * 4 * sizeof(double2)));
-        c->ship_bla_cap = need;
-    } else if (c->ev_ship_bla_valid) {
-        FR_HIP_TRY(hipStreamWaitEvent(stream, c->ev_ship_bla, 0));
-    }
-    for (int k = 1; k <= K; ++k) {
-        const uint32_t cnt = n1 >> k;
-        uint32_t grid = (cnt + kBlockThreads - 1) / kBlockThreads;
-        const uint32_t cap = (uint32_t)c->compute_units * 8u;
-        if (grid > cap) grid = cap;
-        hipLaunchKernelGGL(deep_ship_bla_level_kernel, dim3(grid), dim3(kBlockThreads), 0, stream, c->ship_orbit_dev, N, k,
-                           dcmax, c->ship_bla_r, c->ship_bla_ab);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fr_set_error(FR_ERR_HIP, "ship BLA table launch failed: %s", hipGetErrorString(e));
-    }
-    c->ship_bla_key_gen = c->ship_gen;
-    c->ship_bla_key_dcmax = dbits;
-    c->ship_bla_valid = true;
-    return FR_OK;
-}
-
-/* enqueue_deep_bla for the ship: the table, then deep_kernel<DeepShipBlaArgs> on deep_kernel<DeepShipArgs>'s queue plan (its
- * own occupancy), its counters cleared in front of it and copied to pinned memory behind it */
-static int enqueue_deep_ship_bla(fr_ctx* c, const fr_params* p, const DeepShipArgs& s, hipStream_t stream)
-{
-    DeepShipBlaArgs a;
-    memset(&a, 0, sizeof(a));
-    a.s = s;
-    int levels = 0;
-    const int ts = ship_bla_table_for(c, p, (uint32_t)s.d.g.W, (uint32_t)s.d.g.H, stream, &levels);
-    if (ts != FR_OK) return ts;
-    a.t.r = c->ship_bla_r; a.t.ab = c->ship_bla_ab; a.t.levels = levels;
-    if (!c->ship_bla_steps_dev) {
-        FR_HIP_TRY(hipMalloc((void**)&c->ship_bla_steps_dev, 3 * sizeof(unsigned long long)));
-        FR_HIP_TRY(hipHostMalloc((void**)&c->ship_bla_steps_host, 3 * sizeof(unsigned long long)));
-    }
-    a.t.steps = c->ship_bla_steps_dev;
-    FR_HIP_TRY(hipMemsetAsync(c->ship_bla_steps_dev, 0, 3 * sizeof(unsigned long long), stream));
-    const int st = launch_one_pass(c, stream, "deep_kernel<DeepShipBlaArgs>", deep_kernel<DeepShipBlaArgs>, a, a.s.d.g, a.s.d.q,
-                                   c->ship_bla_wg_per_cu, false);
-    if (st != FR_OK) return st;
-    FR_HIP_TRY(hipMemcpyAsync(c->ship_bla_steps_host, c->ship_bla_steps_dev, 3 * sizeof(unsigned long long),
-                              hipMemcpyDeviceToHost, stream));
-    c->have_ship_bla_steps = true;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(stream, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusActive; }
-    c->ev_ship_bla_valid = false;
-    if (cap == hipStreamCaptureStatusNone) {
-        FR_HIP_TRY(hipEventRecord(c->ev_ship_bla, stream));
-        c->ev_ship_bla_valid = true;
-    }
-    return FR_OK;
-}
-
-/* enqueue_deep on the ship's own orbit slot and deep_kernel<DeepShipArgs> */
-static int enqueue_deep_ship(fr_ctx* c, const fr_params* p, const fr_deep_view* v, uint32_t W, uint32_t H,
-                             const fr_shard* shard, float* rgba, void* nu, int32_t* iter, hipStream_t stream, bool out_frame)
-{
-    fr_shard norm;
-    uint32_t rows_local = 0;
-    const int sh = begin_shard(c, shard, H, &norm, &rows_local);
-    if (sh != FR_OK || rows_local == 0) return sh;
-    const int os = ship_orbit_for(c, p, v, stream);
-    if (os != FR_OK) return os;
-
+    DeepOrbit& o = c->deep[f];
     DeepShipArgs s;
     memset(&s, 0, sizeof(s));
     DeepArgs& a = s.d;
-    a.orbit = c->ship_orbit_dev; a.n_ref = c->ship_len - 1;
+    a.orbit = reinterpret_cast<const double2*>(o.dev); a.n_ref = o.len - 1;
     a.zoom = p->zoom;
     fill_deep_args(a, c, p, tile_geom(W, H, rows_local, &norm, out_frame), rgba, nu, iter);
     s.log_bailout = log((double)p->bailout);     /* as fill_params */
-    if (p->flags & FR_FLAG_DEEP_SHIP_BLA) return enqueue_deep_ship_bla(c, p, s, stream);
-    return launch_one_pass(c, stream, "deep_kernel<DeepShipArgs>", deep_kernel<DeepShipArgs>, s, a.g, a.q, c->ship_wg_per_cu,
-                           false);
+    if (f == kShip)
+        return launch_deep<DeepShipBlaArgs>(c, stream, "deep_kernel<DeepShipArgs>", "deep_kernel<DeepShipBlaArgs>", s,
+                                            (p->flags & FR_FLAG_DEEP_SHIP_BLA) != 0, o.wg_per_cu);
+    return launch_deep<DeepBlaArgs>(c, stream, "deep_kernel<DeepArgs>", "deep_kernel<DeepBlaArgs>", a,
+                                    (p->flags & FR_FLAG_DEEP_BLA) != 0, o.wg_per_cu);
 }
 
 /* ---- extended views (fr_render_deepx, fr_render_deepx_ship) -----------------------------------------------------------
  * enqueue_deep with the orbit in the extended storage: the mantissa pairs and exponents of the formula's reference orbit,
- * and the plain doubles ldexp(mantissa, exponent) formed here on the host, in one upload.
- *
- * One cache slot of extended orbits (OrbitSlot's counterpart): one pinned and one device block of cap points each, what they
- * hold, the host function that computes the orbit, and the event behind the slot's most recent BLA render */
-struct XOrbitSlot {
-    char*& host;
-    char*& dev;
-    size_t& cap;
-    int32_t& len;
-    OrbitKey& key;
-    uint64_t& gen;
-    int (*compute)(const fr_deepx_view*, int32_t, float, double*, int32_t*, int32_t*);
-    hipEvent_t ev_bla;
-    const bool& ev_bla_valid;
-};
-
-static int xorbit_slot_fill(fr_ctx* c, const XOrbitSlot& o, const fr_params* p, const fr_deepx_view* v, int32_t bits,
-                            hipStream_t stream)
+ * and the plain doubles ldexp(mantissa, exponent) formed here on the host, in one upload into the formula's extended cache
+ * slot (orbit_slot_fill's counterpart). */
+static int xorbit_slot_fill(fr_ctx* c, int f, const fr_params* p, const fr_deepx_view* v, int32_t bits, hipStream_t stream)
 {
+    DeepOrbit& o = c->deepx[f];
+    const BlaSlot& t = c->blax[f];
     const int32_t max_iter = p->max_iterations;
     if (orbit_key_matches(o.key, v->center_x, v->center_y, bits, max_iter, p->bailout)) return FR_OK;
     /* as orbit_slot_fill: the pinned block may still feed an upload, the device block an earlier render */
     FR_HIP_TRY(hipStreamSynchronize(stream));
     FR_HIP_TRY(hipStreamSynchronize(c->stream));
     if (c->have_render && c->last_stream != stream) FR_HIP_TRY(hipStreamSynchronize(c->last_stream));
-    if (o.ev_bla_valid) FR_HIP_TRY(hipEventSynchronize(o.ev_bla));        /* the slot's last BLA render, wherever it went */
+    if (t.ev_valid) FR_HIP_TRY(hipEventSynchronize(t.ev));                /* the slot's last BLA render, wherever it went */
     o.key.valid = false;
     ++o.gen;
     const size_t need = (size_t)max_iter + 1;
@@ -1156,7 +993,8 @@ static int xorbit_slot_fill(fr_ctx* c, const XOrbitSlot& o, const fr_params* p, 
     int32_t len = 0;
     fr_deepx_view w = *v;
     w.frac_bits = bits;
-    const int st = o.compute(&w, max_iter, p->bailout, mant, exp2, &len);
+    const int st = (f == kShip ? fr_deepx_ship_reference_orbit : fr_deepx_reference_orbit)(&w, max_iter, p->bailout, mant, exp2,
+                                                                                           &len);
     if (st != FR_OK) return st;
     for (int32_t n = 0; n < len; ++n) {
         plain[2 * n] = ldexp(mant[2 * n], exp2[n]);
@@ -1169,239 +1007,12 @@ static int xorbit_slot_fill(fr_ctx* c, const XOrbitSlot& o, const fr_params* p, 
     return ks;
 }
 
-static int deepx_orbit_for(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, int32_t bits, hipStream_t stream)
-{
-    const XOrbitSlot o = {c->deepx_host, c->deepx_dev, c->deepx_cap, c->deepx_len, c->deepx_key, c->deepx_gen,
-                          fr_deepx_reference_orbit, c->ev_xbla, c->ev_xbla_valid};
-    return xorbit_slot_fill(c, o, p, v, bits, stream);
-}
-
-static int shipx_orbit_for(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, int32_t bits, hipStream_t stream)
-{
-    const XOrbitSlot o = {c->shipx_host, c->shipx_dev, c->shipx_cap, c->shipx_len, c->shipx_key, c->shipx_gen,
-                          fr_deepx_ship_reference_orbit, c->ev_shipx_bla, c->ev_shipx_bla_valid};
-    return xorbit_slot_fill(c, o, p, v, bits, stream);
-}
-
-/* FR_FLAG_DEEPX_BLA: the table of the cached extended orbit for this frame's dcmax (the whole frame's W, H and the zoom
- * pair), built on `stream` unless the context holds it -- deep_bla_table_for's rules on the deepx path's own buffers and
- * event. */
-static int deepx_bla_table_for(fr_ctx* c, const DeepXArgs& x, hipStream_t stream, int* levels)
-{
-    const int32_t N = c->deepx_len - 1;
-    const int K = N > 1 ? 31 - __builtin_clz((uint32_t)(N - 1)) : 0;   /* floor(log2(N - 1)) */
-    *levels = K;
-    if (K == 0) return FR_OK;
-    const double a = (double)x.d.g.W / (double)x.d.g.H;
-    int de = 0;
-    const double dv = frexp((1.0000001 * (0.5 * x.zm)) * sqrt(a * a + 1.0), &de);   /* normalised: dv in [0.5, 1) */
-    const int32_t dce = x.ze + de;
-    uint64_t dbits;
-    memcpy(&dbits, &dv, sizeof(dbits));
-    if (c->xbla_valid && c->xbla_key_gen == c->deepx_gen && c->xbla_key_dcv == dbits && c->xbla_key_dce == dce) return FR_OK;
-    c->xbla_valid = false;
-    const uint32_t n1 = (uint32_t)(N - 1);
-    const size_t need = (size_t)(n1 - (uint32_t)__builtin_popcount(n1));     /* sum over k >= 1 of (N - 1) >> k */
-    if (need > c->xbla_cap) {
-        FR_HIP_TRY(hipStreamSynchronize(stream));
-        FR_HIP_TRY(hipStreamSynchronize(c->stream));
-        if (c->ev_xbla_valid) FR_HIP_TRY(hipEventSynchronize(c->ev_xbla));
-        if (c->xbla_r) { (void)hipFree(c->xbla_r); c->xbla_r = nullptr; }
-        if (c->xbla_ab) { (void)hipFree(c->xbla_ab); c->xbla_ab = nullptr; }
-        if (c->xbla_abe) { (void)hipFree(c->xbla_abe); c->xbla_abe = nullptr; }
-        c->xbla_cap = 0;
-        FR_HIP_TRY(hipMalloc((void**)&c->xbla_r, need * sizeof(XRad)));
-        FR_HIP_TRY(hipMalloc((void**)&c->xbla_ab, need * 2 * sizeof(double2)));
-        FR_HIP_TRY(hipMalloc((void**)&c->xbla_abe, need * sizeof(int2)));
-        c->xbla_cap = need;
-    } else if (c->ev_xbla_valid) {
-        FR_HIP_TRY(hipStreamWaitEvent(stream, c->ev_xbla, 0));
-    }
-    for (int k = 1; k <= K; ++k) {
-        const uint32_t cnt = n1 >> k;
-        uint32_t grid = (cnt + kBlockThreads - 1) / kBlockThreads;
-        const uint32_t cap = (uint32_t)c->compute_units * 8u;
-        if (grid > cap) grid = cap;
-        hipLaunchKernelGGL(deepx_bla_level_kernel, dim3(grid), dim3(kBlockThreads), 0, stream, x.mant, x.exp2, N, k, dv, dce,
-                           c->xbla_r, c->xbla_ab, c->xbla_abe);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fr_set_error(FR_ERR_HIP, "extended BLA table launch failed: %s", hipGetErrorString(e));
-    }
-    c->xbla_key_gen = c->deepx_gen;
-    c->xbla_key_dcv = dbits;
-    c->xbla_key_dce = dce;
-    c->xbla_valid = true;
-    return FR_OK;
-}
-
-/* the table, then deep_kernel<DeepXBlaArgs> on the queue plan of deep_kernel<DeepXArgs> (its own occupancy), its counters
- * cleared in front of it and copied to pinned memory behind it */
-static int enqueue_deepx_bla(fr_ctx* c, const DeepXArgs& x, hipStream_t stream)
-{
-    DeepXBlaArgs a;
-    memset(&a, 0, sizeof(a));
-    a.x = x;
-    int levels = 0;
-    const int ts = deepx_bla_table_for(c, x, stream, &levels);
-    if (ts != FR_OK) return ts;
-    a.t.r = c->xbla_r; a.t.ab = c->xbla_ab; a.t.abe = c->xbla_abe; a.t.levels = levels;
-    if (!c->xbla_steps_dev) {
-        FR_HIP_TRY(hipMalloc((void**)&c->xbla_steps_dev, 3 * sizeof(unsigned long long)));
-        FR_HIP_TRY(hipHostMalloc((void**)&c->xbla_steps_host, 3 * sizeof(unsigned long long)));
-    }
-    a.t.steps = c->xbla_steps_dev;
-    FR_HIP_TRY(hipMemsetAsync(c->xbla_steps_dev, 0, 3 * sizeof(unsigned long long), stream));
-    const int st = launch_one_pass(c, stream, "deep_kernel<DeepXBlaArgs>", deep_kernel<DeepXBlaArgs>, a, a.x.d.g, a.x.d.q,
-                                   c->deepx_bla_wg_per_cu, false);
-    if (st != FR_OK) return st;
-    FR_HIP_TRY(hipMemcpyAsync(c->xbla_steps_host, c->xbla_steps_dev, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost,
-                              stream));
-    c->have_xbla_steps = true;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(stream, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusActive; }
-    c->ev_xbla_valid = false;
-    if (cap == hipStreamCaptureStatusNone) {
-        FR_HIP_TRY(hipEventRecord(c->ev_xbla, stream));
-        c->ev_xbla_valid = true;
-    }
-    return FR_OK;
-}
-
 /* the extended view already resolved: v gives the centre strings (and a zoom string the orbit does not depend on), the
- * zoom is (zm, ze) and the orbit's fraction bits are `bits` -- what fr_render_deepx and the frames of a fr_deep_sequence share */
-static int enqueue_deepx_at(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, double zm, int32_t ze, int32_t bits, uint32_t W,
-                            uint32_t H, const fr_shard* shard, float* rgba, void* nu, int32_t* iter, hipStream_t stream,
-                            bool out_frame)
-{
-    fr_shard norm;
-    uint32_t rows_local = 0;
-    const int sh = begin_shard(c, shard, H, &norm, &rows_local);
-    if (sh != FR_OK || rows_local == 0) return sh;
-    DeepXArgs x;
-    memset(&x, 0, sizeof(x));
-    x.zm = zm;
-    x.ze = ze;
-    const int os = deepx_orbit_for(c, p, v, bits, stream);
-    if (os != FR_OK) return os;
-
-    DeepArgs& a = x.d;
-    const size_t cap = c->deepx_cap;
-    a.orbit = reinterpret_cast<const double2*>(c->deepx_dev);
-    x.mant = a.orbit + cap;
-    x.exp2 = reinterpret_cast<const int32_t*>(x.mant + cap);
-    a.n_ref = c->deepx_len - 1;
-    fill_deep_args(a, c, p, tile_geom(W, H, rows_local, &norm, out_frame), rgba, nu, iter);
-
-    if (p->flags & FR_FLAG_DEEPX_BLA) return enqueue_deepx_bla(c, x, stream);
-    return launch_one_pass(c, stream, "deep_kernel<DeepXArgs>", deep_kernel<DeepXArgs>, x, a.g, a.q, c->deepx_wg_per_cu, false);
-}
-
-static int enqueue_deepx(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, uint32_t W, uint32_t H, const fr_shard* shard,
-                         float* rgba, void* nu, int32_t* iter, hipStream_t stream, bool out_frame)
-{
-    double zm = 0.0;
-    int32_t ze = 0, bits = 0;
-    const int rs = fr_deepx_resolve(v, &zm, &ze, &bits);
-    if (rs != FR_OK) return rs;
-    return enqueue_deepx_at(c, p, v, zm, ze, bits, W, H, shard, rgba, nu, iter, stream, out_frame);
-}
-
-/* ---- extended Burning Ship views (fr_render_deepx_ship) ------------------------------------------------------------------
- * FR_FLAG_DEEPX_SHIP_BLA: the table of the cached extended ship orbit for this frame's dcmax (the ship's bound on the whole
- * frame's W, H, as an extended real with the zoom pair), built on `stream` unless the context holds it -- deepx_bla_table_for's
- * rules on this path's own buffers and event. */
-static int deepx_ship_bla_table_for(fr_ctx* c, const DeepXArgs& x, hipStream_t stream, int* levels)
-{
-    const int32_t N = c->shipx_len - 1;
-    const int K = N > 1 ? 31 - __builtin_clz((uint32_t)(N - 1)) : 0;   /* floor(log2(N - 1)) */
-    *levels = K;
-    if (K == 0) return FR_OK;
-    const double w = (double)x.d.g.W, h = (double)x.d.g.H;
-    const double a = w / h;
-    const double hx = 0.5 + 0.5 / (w * w);
-    const double hy = 0.5 + 0.5 / (w * h);
-    const double ex = hx * a;
-    int de = 0;
-    const double dv = frexp((1.0000001 * x.zm) * sqrt(ex * ex + hy * hy), &de);   /* normalised: dv in [0.5, 1) */
-    const int32_t dce = x.ze + de;
-    uint64_t dbits;
-    memcpy(&dbits, &dv, sizeof(dbits));
-    if (c->shipx_bla_valid && c->shipx_bla_key_gen == c->shipx_gen && c->shipx_bla_key_dcv == dbits &&
-        c->shipx_bla_key_dce == dce)
-        return FR_OK;
-    c->shipx_bla_valid = false;
-    const uint32_t n1 = (uint32_t)(N - 1);
-    const size_t need = (size_t)(n1 - (uint32_t)__builtin_popcount(n1));     /* sum over k >= 1 of (N - 1) >> k */
-    if (need > c->shipx_bla_cap) {
-        FR_HIP_TRY(hipStreamSynchronize(stream));
-        FR_HIP_TRY(hipStreamSynchronize(c->stream));
-        if (c->ev_shipx_bla_valid) FR_HIP_TRY(hipEventSynchronize(c->ev_shipx_bla));
-        if (c->shipx_bla_r) { (void)hipFree(c->shipx_bla_r); c->shipx_bla_r = nullptr; }
-        if (c->shipx_bla_ab) { (void)hipFree(c->shipx_bla_ab); c->shipx_bla_ab = nullptr; }
-        if (c->shipx_bla_abe) { (void)hipFree(c->shipx_bla_abe); c->shipx_bla_abe = nullptr; }
-        c->shipx_bla_cap = 0;
-        FR_HIP_TRY(hipMalloc((void**)&c->shipx_bla_r, need * sizeof(XRad)));
-        FR_HIP_TRY(hipMalloc((void**)&c->shipx_bla_ab, need * 4 * sizeof(double2)));
-        FR_HIP_TRY(hipMalloc((void**)&c->shipx_bla_abe, need * sizeof(int2)));
-        c->shipx_bla_cap = need;
-    } else if (c->ev_shipx_bla_valid) {
-        FR_HIP_TRY(hipStreamWaitEvent(stream, c->ev_shipx_bla, 0));
-    }
-    for (int k = 1; k <= K; ++k) {
-        const uint32_t cnt = n1 >> k;
-        uint32_t grid = (cnt + kBlockThreads - 1) / kBlockThreads;
-        const uint32_t cap = (uint32_t)c->compute_units * 8u;
-        if (grid > cap) grid = cap;
-        hipLaunchKernelGGL(deepx_ship_bla_level_kernel, dim3(grid), dim3(kBlockThreads), 0, stream, x.mant, x.exp2, N, k, dv, dce,
-                           c->shipx_bla_r, c->shipx_bla_ab, c->shipx_bla_abe);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fr_set_error(FR_ERR_HIP, "extended ship BLA table launch failed: %s", hipGetErrorString(e));
-    }
-    c->shipx_bla_key_gen = c->shipx_gen;
-    c->shipx_bla_key_dcv = dbits;
-    c->shipx_bla_key_dce = dce;
-    c->shipx_bla_valid = true;
-    return FR_OK;
-}
-
-/* the table, then deep_kernel<DeepShipXBlaArgs> on the queue plan of deep_kernel<DeepShipXArgs> (its own occupancy), its
- * counters cleared in front of it and copied to pinned memory behind it */
-static int enqueue_deepx_ship_bla(fr_ctx* c, const DeepShipXArgs& s, hipStream_t stream)
-{
-    DeepShipXBlaArgs a;
-    memset(&a, 0, sizeof(a));
-    a.s = s;
-    int levels = 0;
-    const int ts = deepx_ship_bla_table_for(c, s.x, stream, &levels);
-    if (ts != FR_OK) return ts;
-    a.t.r = c->shipx_bla_r; a.t.ab = c->shipx_bla_ab; a.t.abe = c->shipx_bla_abe; a.t.levels = levels;
-    if (!c->shipx_bla_steps_dev) {
-        FR_HIP_TRY(hipMalloc((void**)&c->shipx_bla_steps_dev, 3 * sizeof(unsigned long long)));
-        FR_HIP_TRY(hipHostMalloc((void**)&c->shipx_bla_steps_host, 3 * sizeof(unsigned long long)));
-    }
-    a.t.steps = c->shipx_bla_steps_dev;
-    FR_HIP_TRY(hipMemsetAsync(c->shipx_bla_steps_dev, 0, 3 * sizeof(unsigned long long), stream));
-    const int st = launch_one_pass(c, stream, "deep_kernel<DeepShipXBlaArgs>", deep_kernel<DeepShipXBlaArgs>, a, a.s.x.d.g,
-                                   a.s.x.d.q, c->shipx_bla_wg_per_cu, false);
-    if (st != FR_OK) return st;
-    FR_HIP_TRY(hipMemcpyAsync(c->shipx_bla_steps_host, c->shipx_bla_steps_dev, 3 * sizeof(unsigned long long),
-                              hipMemcpyDeviceToHost, stream));
-    c->have_shipx_bla_steps = true;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(stream, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusActive; }
-    c->ev_shipx_bla_valid = false;
-    if (cap == hipStreamCaptureStatusNone) {
-        FR_HIP_TRY(hipEventRecord(c->ev_shipx_bla, stream));
-        c->ev_shipx_bla_valid = true;
-    }
-    return FR_OK;
-}
-
-/* enqueue_deepx_at on the extended ship slot and deep_kernel<DeepShipXArgs>: what fr_render_deepx_ship and the frames of a ship
- * sequence share */
-static int enqueue_deepx_ship_at(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, double zm, int32_t ze, int32_t bits,
-                                 uint32_t W, uint32_t H, const fr_shard* shard, float* rgba, void* nu, int32_t* iter,
-                                 hipStream_t stream, bool out_frame)
+ * zoom is (zm, ze) and the orbit's fraction bits are `bits` -- what fr_render_deepx / fr_render_deepx_ship and the frames of a
+ * fr_deep_sequence of the formula share */
+static int enqueue_deepx_at(fr_ctx* c, int f, const fr_params* p, const fr_deepx_view* v, double zm, int32_t ze, int32_t bits,
+                            uint32_t W, uint32_t H, const fr_shard* shard, float* rgba, void* nu, int32_t* iter,
+                            hipStream_t stream, bool out_frame)
 {
     fr_shard norm;
     uint32_t rows_local = 0;
@@ -1409,37 +1020,39 @@ static int enqueue_deepx_ship_at(fr_ctx* c, const fr_params* p, const fr_deepx_v
     if (sh != FR_OK || rows_local == 0) return sh;
     DeepShipXArgs s;
     memset(&s, 0, sizeof(s));
-    s.x.zm = zm;
-    s.x.ze = ze;
-    const int os = shipx_orbit_for(c, p, v, bits, stream);
+    DeepXArgs& x = s.x;
+    x.zm = zm;
+    x.ze = ze;
+    const int os = xorbit_slot_fill(c, f, p, v, bits, stream);
     if (os != FR_OK) return os;
 
-    DeepArgs& a = s.x.d;
-    const size_t cap = c->shipx_cap;
-    a.orbit = reinterpret_cast<const double2*>(c->shipx_dev);
-    s.x.mant = a.orbit + cap;
-    s.x.exp2 = reinterpret_cast<const int32_t*>(s.x.mant + cap);
-    a.n_ref = c->shipx_len - 1;
+    DeepOrbit& o = c->deepx[f];
+    DeepArgs& a = x.d;
+    a.orbit = reinterpret_cast<const double2*>(o.dev);
+    x.mant = a.orbit + o.cap;
+    x.exp2 = reinterpret_cast<const int32_t*>(x.mant + o.cap);
+    a.n_ref = o.len - 1;
     fill_deep_args(a, c, p, tile_geom(W, H, rows_local, &norm, out_frame), rgba, nu, iter);
     s.log_bailout = log((double)p->bailout);     /* as fill_params */
-    if (p->flags & FR_FLAG_DEEPX_SHIP_BLA) return enqueue_deepx_ship_bla(c, s, stream);
-    return launch_one_pass(c, stream, "deep_kernel<DeepShipXArgs>", deep_kernel<DeepShipXArgs>, s, a.g, a.q, c->shipx_wg_per_cu,
-                           false);
+    if (f == kShip)
+        return launch_deep<DeepShipXBlaArgs>(c, stream, "deep_kernel<DeepShipXArgs>", "deep_kernel<DeepShipXBlaArgs>", s,
+                                             (p->flags & FR_FLAG_DEEPX_SHIP_BLA) != 0, o.wg_per_cu);
+    return launch_deep<DeepXBlaArgs>(c, stream, "deep_kernel<DeepXArgs>", "deep_kernel<DeepXBlaArgs>", x,
+                                     (p->flags & FR_FLAG_DEEPX_BLA) != 0, o.wg_per_cu);
 }
 
-static int enqueue_deepx_ship(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, uint32_t W, uint32_t H,
-                              const fr_shard* shard, float* rgba, void* nu, int32_t* iter, hipStream_t stream, bool out_frame)
+static int enqueue_deepx(fr_ctx* c, int f, const fr_params* p, const fr_deepx_view* v, uint32_t W, uint32_t H,
+                         const fr_shard* shard, float* rgba, void* nu, int32_t* iter, hipStream_t stream, bool out_frame)
 {
     double zm = 0.0;
     int32_t ze = 0, bits = 0;
     const int rs = fr_deepx_resolve(v, &zm, &ze, &bits);
     if (rs != FR_OK) return rs;
-    return enqueue_deepx_ship_at(c, p, v, zm, ze, bits, W, H, shard, rgba, nu, iter, stream, out_frame);
+    return enqueue_deepx_at(c, f, p, v, zm, ze, bits, W, H, shard, rgba, nu, iter, stream, out_frame);
 }
 
 /* ---- deep zoom sequences (fr_deep_sequence; the rules are in the header, the host planning in fr_deepseq.c) ---------------
- * Every exact render is enqueue_deepx_at -- enqueue_deepx_ship_at for a ship sequence -- around the sequence's one orbit
- * key.  Mode 1 keeps two device rgba planes: each holds one keyframe, tagged with its index and with the post-chain flag it
+ * Every exact render is enqueue_deepx_at with the sequence's formula, around the sequence's one orbit key. Mode 1 keeps two device rgba planes: each holds one keyframe, tagged with its index and with the post-chain flag it
  * was rendered with (fr_deep_sequence_render_png
  * forces the flag), and the least recently needed one makes room. */
 struct fr_deep_sequence {
@@ -1460,9 +1073,8 @@ struct fr_deep_sequence {
 static int seq_exact(fr_deep_sequence* q, const fr_params* p, double zm, int32_t ze, float* rgba, void* nu, int32_t* iter,
                      hipStream_t s)
 {
-    const int st = q->ship
-        ? enqueue_deepx_ship_at(q->c, p, &q->view, zm, ze, q->w.frac_bits, q->W, q->H, nullptr, rgba, nu, iter, s, false)
-        : enqueue_deepx_at(q->c, p, &q->view, zm, ze, q->w.frac_bits, q->W, q->H, nullptr, rgba, nu, iter, s, false);
+    const int st = enqueue_deepx_at(q->c, q->ship ? kShip : kMandel, p, &q->view, zm, ze, q->w.frac_bits, q->W, q->H, nullptr,
+                                    rgba, nu, iter, s, false);
     if (st == FR_OK) ++q->n_exact;
     return st;
 }
@@ -1535,7 +1147,7 @@ static int seq_enqueue(fr_deep_sequence* q, const fr_params* p, const fr_deep_se
                        int32_t* iter, hipStream_t s)
 {
     fr_ctx* c = q->c;
-    const uint64_t& gen = q->ship ? c->shipx_gen : c->deepx_gen;
+    const uint64_t& gen = c->deepx[q->ship ? kShip : kMandel].gen;
     const uint64_t gen0 = gen;
     const bool timed = c->timing;
     if (timed) FR_HIP_TRY(hipEventRecord(c->ev_begin, s));
@@ -2020,102 +1632,73 @@ extern "C" int fr_plan_describe(const fr_params* p, uint32_t W, uint32_t H, cons
     return FR_OK;
 }
 
-extern "C" int fr_ctx_last_deep_steps(fr_ctx* c, uint64_t out[3])
+/* the step counts behind a slot's most recent render; `what` names the call and flag that fill them */
+static int last_bla_steps(fr_ctx* c, bool ext, int f, const char* what, uint64_t out[3])
 {
     if (!c || !out) return fr_set_error(FR_ERR_INVALID_ARG, "ctx/out is NULL");
-    if (!c->have_bla_steps)
-        return fr_set_error(FR_ERR_UNSUPPORTED, "no fr_render_deep call with FR_FLAG_DEEP_BLA on this context yet");
-    for (int i = 0; i < 3; ++i) out[i] = (uint64_t)c->bla_steps_host[i];
+    const BlaSlot& t = (ext ? c->blax : c->bla)[f];
+    if (!t.have_steps) return fr_set_error(FR_ERR_UNSUPPORTED, "no %s on this context yet", what);
+    for (int i = 0; i < 3; ++i) out[i] = (uint64_t)t.steps_host[i];
     return FR_OK;
 }
 
-extern "C" int64_t fr_deep_bla_table(fr_ctx* c, double* r, double* ab, int64_t n)
+/* tests: the first n entries of a slot's table, as the device holds them; returns the entries the table has */
+static int64_t read_bla_table(fr_ctx* c, bool ext, int f, void* r, double* ab, int32_t* ab_exp, int64_t n)
 {
     if (!c) return fr_set_error(FR_ERR_INVALID_ARG, "ctx is NULL");
-    if (!c->bla_valid) return 0;
-    const int32_t N = c->deep_len - 1;
+    const BlaSlot& t = (ext ? c->blax : c->bla)[f];
+    if (!t.valid) return 0;
+    const int32_t N = (ext ? c->deepx : c->deep)[f].len - 1;
     const uint32_t n1 = (uint32_t)(N - 1);
     const int64_t have = (int64_t)(n1 - (uint32_t)__builtin_popcount(n1));
     if (n > have) n = have;
+    const size_t nab = f == kShip ? ShipFormula::kAbPerEntry : MandelFormula::kAbPerEntry;
     FR_HIP_TRY(hipSetDevice(c->device));
     FR_HIP_TRY(hipDeviceSynchronize());
-    if (n > 0 && r) FR_HIP_TRY(hipMemcpy(r, c->bla_r, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
-    if (n > 0 && ab) FR_HIP_TRY(hipMemcpy(ab, c->bla_ab, (size_t)n * 2 * sizeof(double2), hipMemcpyDeviceToHost));
+    if (n > 0 && r) FR_HIP_TRY(hipMemcpy(r, t.r, (size_t)n * (ext ? sizeof(XRad) : sizeof(double)), hipMemcpyDeviceToHost));
+    if (n > 0 && ab) FR_HIP_TRY(hipMemcpy(ab, t.ab, (size_t)n * nab * sizeof(double2), hipMemcpyDeviceToHost));
+    if (n > 0 && ext && ab_exp) FR_HIP_TRY(hipMemcpy(ab_exp, t.abe, (size_t)n * sizeof(int2), hipMemcpyDeviceToHost));
     return have;
+}
+
+extern "C" int fr_ctx_last_deep_steps(fr_ctx* c, uint64_t out[3])
+{
+    return last_bla_steps(c, false, kMandel, "fr_render_deep call with FR_FLAG_DEEP_BLA", out);
 }
 
 extern "C" int fr_ctx_last_deep_ship_steps(fr_ctx* c, uint64_t out[3])
 {
-    if (!c || !out) return fr_set_error(FR_ERR_INVALID_ARG, "ctx/out is NULL");
-    if (!c->have_ship_bla_steps)
-        return fr_set_error(FR_ERR_UNSUPPORTED, "no fr_render_deep_ship call with FR_FLAG_DEEP_SHIP_BLA on this context yet");
-    for (int i = 0; i < 3; ++i) out[i] = (uint64_t)c->ship_bla_steps_host[i];
-    return FR_OK;
-}
-
-extern "C" int64_t fr_deep_ship_bla_table(fr_ctx* c, double* r, double* ab, int64_t n)
-{
-    if (!c) return fr_set_error(FR_ERR_INVALID_ARG, "ctx is NULL");
-    if (!c->ship_bla_valid) return 0;
-    const int32_t N = c->ship_len - 1;
-    const uint32_t n1 = (uint32_t)(N - 1);
-    const int64_t have = (int64_t)(n1 - (uint32_t)__builtin_popcount(n1));
-    if (n > have) n = have;
-    FR_HIP_TRY(hipSetDevice(c->device));
-    FR_HIP_TRY(hipDeviceSynchronize());
-    if (n > 0 && r) FR_HIP_TRY(hipMemcpy(r, c->ship_bla_r, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
-    if (n > 0 && ab) FR_HIP_TRY(hipMemcpy(ab, c->ship_bla_ab, (size_t)n * 4 * sizeof(double2), hipMemcpyDeviceToHost));
-    return have;
+    return last_bla_steps(c, false, kShip, "fr_render_deep_ship call with FR_FLAG_DEEP_SHIP_BLA", out);
 }
 
 extern "C" int fr_ctx_last_deepx_steps(fr_ctx* c, uint64_t out[3])
 {
-    if (!c || !out) return fr_set_error(FR_ERR_INVALID_ARG, "ctx/out is NULL");
-    if (!c->have_xbla_steps)
-        return fr_set_error(FR_ERR_UNSUPPORTED, "no fr_render_deepx call with FR_FLAG_DEEPX_BLA on this context yet");
-    for (int i = 0; i < 3; ++i) out[i] = (uint64_t)c->xbla_steps_host[i];
-    return FR_OK;
-}
-
-extern "C" int64_t fr_deepx_bla_table(fr_ctx* c, void* r, double* ab, int32_t* ab_exp, int64_t n)
-{
-    if (!c) return fr_set_error(FR_ERR_INVALID_ARG, "ctx is NULL");
-    if (!c->xbla_valid) return 0;
-    const int32_t N = c->deepx_len - 1;
-    const uint32_t n1 = (uint32_t)(N - 1);
-    const int64_t have = (int64_t)(n1 - (uint32_t)__builtin_popcount(n1));
-    if (n > have) n = have;
-    FR_HIP_TRY(hipSetDevice(c->device));
-    FR_HIP_TRY(hipDeviceSynchronize());
-    if (n > 0 && r) FR_HIP_TRY(hipMemcpy(r, c->xbla_r, (size_t)n * sizeof(XRad), hipMemcpyDeviceToHost));
-    if (n > 0 && ab) FR_HIP_TRY(hipMemcpy(ab, c->xbla_ab, (size_t)n * 2 * sizeof(double2), hipMemcpyDeviceToHost));
-    if (n > 0 && ab_exp) FR_HIP_TRY(hipMemcpy(ab_exp, c->xbla_abe, (size_t)n * sizeof(int2), hipMemcpyDeviceToHost));
-    return have;
+    return last_bla_steps(c, true, kMandel, "fr_render_deepx call with FR_FLAG_DEEPX_BLA", out);
 }
 
 extern "C" int fr_ctx_last_deepx_ship_steps(fr_ctx* c, uint64_t out[3])
 {
-    if (!c || !out) return fr_set_error(FR_ERR_INVALID_ARG, "ctx/out is NULL");
-    if (!c->have_shipx_bla_steps)
-        return fr_set_error(FR_ERR_UNSUPPORTED, "no fr_render_deepx_ship call with FR_FLAG_DEEPX_SHIP_BLA on this context yet");
-    for (int i = 0; i < 3; ++i) out[i] = (uint64_t)c->shipx_bla_steps_host[i];
-    return FR_OK;
+    return last_bla_steps(c, true, kShip, "fr_render_deepx_ship call with FR_FLAG_DEEPX_SHIP_BLA", out);
+}
+
+extern "C" int64_t fr_deep_bla_table(fr_ctx* c, double* r, double* ab, int64_t n)
+{
+    return read_bla_table(c, false, kMandel, r, ab, nullptr, n);
+}
+
+extern "C" int64_t fr_deep_ship_bla_table(fr_ctx* c, double* r, double* ab, int64_t n)
+{
+    return read_bla_table(c, false, kShip, r, ab, nullptr, n);
+}
+
+extern "C" int64_t fr_deepx_bla_table(fr_ctx* c, void* r, double* ab, int32_t* ab_exp, int64_t n)
+{
+    return read_bla_table(c, true, kMandel, r, ab, ab_exp, n);
 }
 
 extern "C" int64_t fr_deepx_ship_bla_table(fr_ctx* c, void* r, double* ab, int32_t* ab_exp, int64_t n)
 {
-    if (!c) return fr_set_error(FR_ERR_INVALID_ARG, "ctx is NULL");
-    if (!c->shipx_bla_valid) return 0;
-    const int32_t N = c->shipx_len - 1;
-    const uint32_t n1 = (uint32_t)(N - 1);
-    const int64_t have = (int64_t)(n1 - (uint32_t)__builtin_popcount(n1));
-    if (n > have) n = have;
-    FR_HIP_TRY(hipSetDevice(c->device));
-    FR_HIP_TRY(hipDeviceSynchronize());
-    if (n > 0 && r) FR_HIP_TRY(hipMemcpy(r, c->shipx_bla_r, (size_t)n * sizeof(XRad), hipMemcpyDeviceToHost));
-    if (n > 0 && ab) FR_HIP_TRY(hipMemcpy(ab, c->shipx_bla_ab, (size_t)n * 4 * sizeof(double2), hipMemcpyDeviceToHost));
-    if (n > 0 && ab_exp) FR_HIP_TRY(hipMemcpy(ab_exp, c->shipx_bla_abe, (size_t)n * sizeof(int2), hipMemcpyDeviceToHost));
-    return have;
+    return read_bla_table(c, true, kShip, r, ab, ab_exp, n);
 }
 
 extern "C" int fr_ctx_check(fr_ctx* c)
@@ -2204,7 +1787,7 @@ extern "C" int fr_render_deep_async(fr_ctx* c, const fr_params* p, const fr_deep
     if (st != FR_OK) return st;
     return render_async("fr_render_deep_async", c, H, shard, out, hip_stream,
                         [&](auto sh, auto rgba, auto nu, auto iter, auto s, bool out_frame) {
-                            return enqueue_deep(c, p, v, W, H, sh, rgba, nu, iter, s, out_frame); });
+                            return enqueue_deep(c, kMandel, p, v, W, H, sh, rgba, nu, iter, s, out_frame); });
 }
 
 extern "C" int fr_render_deep(fr_ctx* c, const fr_params* p, const fr_deep_view* v, uint32_t W, uint32_t H,
@@ -2213,7 +1796,7 @@ extern "C" int fr_render_deep(fr_ctx* c, const fr_params* p, const fr_deep_view*
     const int st = check_deep(c, p, v, W, H, out);
     if (st != FR_OK) return st;
     return render_sync(c, p, W, H, shard, out, [&](auto sh, auto rgba, auto nu, auto iter, auto s, bool out_frame) {
-        return enqueue_deep(c, p, v, W, H, sh, rgba, nu, iter, s, out_frame); });
+        return enqueue_deep(c, kMandel, p, v, W, H, sh, rgba, nu, iter, s, out_frame); });
 }
 
 static int check_deep_ship(fr_ctx* c, const fr_params* p, const fr_deep_view* v, uint32_t W, uint32_t H, const fr_output* out)
@@ -2230,7 +1813,7 @@ extern "C" int fr_render_deep_ship_async(fr_ctx* c, const fr_params* p, const fr
     if (st != FR_OK) return st;
     return render_async("fr_render_deep_ship_async", c, H, shard, out, hip_stream,
                         [&](auto sh, auto rgba, auto nu, auto iter, auto s, bool out_frame) {
-                            return enqueue_deep_ship(c, p, v, W, H, sh, rgba, nu, iter, s, out_frame); });
+                            return enqueue_deep(c, kShip, p, v, W, H, sh, rgba, nu, iter, s, out_frame); });
 }
 
 extern "C" int fr_render_deep_ship(fr_ctx* c, const fr_params* p, const fr_deep_view* v, uint32_t W, uint32_t H,
@@ -2239,7 +1822,7 @@ extern "C" int fr_render_deep_ship(fr_ctx* c, const fr_params* p, const fr_deep_
     const int st = check_deep_ship(c, p, v, W, H, out);
     if (st != FR_OK) return st;
     return render_sync(c, p, W, H, shard, out, [&](auto sh, auto rgba, auto nu, auto iter, auto s, bool out_frame) {
-        return enqueue_deep_ship(c, p, v, W, H, sh, rgba, nu, iter, s, out_frame); });
+        return enqueue_deep(c, kShip, p, v, W, H, sh, rgba, nu, iter, s, out_frame); });
 }
 
 static int check_deepx(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, uint32_t W, uint32_t H, const fr_output* out)
@@ -2256,7 +1839,7 @@ extern "C" int fr_render_deepx_async(fr_ctx* c, const fr_params* p, const fr_dee
     if (st != FR_OK) return st;
     return render_async("fr_render_deepx_async", c, H, shard, out, hip_stream,
                         [&](auto sh, auto rgba, auto nu, auto iter, auto s, bool out_frame) {
-                            return enqueue_deepx(c, p, v, W, H, sh, rgba, nu, iter, s, out_frame); });
+                            return enqueue_deepx(c, kMandel, p, v, W, H, sh, rgba, nu, iter, s, out_frame); });
 }
 
 extern "C" int fr_render_deepx(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, uint32_t W, uint32_t H,
@@ -2265,7 +1848,7 @@ extern "C" int fr_render_deepx(fr_ctx* c, const fr_params* p, const fr_deepx_vie
     const int st = check_deepx(c, p, v, W, H, out);
     if (st != FR_OK) return st;
     return render_sync(c, p, W, H, shard, out, [&](auto sh, auto rgba, auto nu, auto iter, auto s, bool out_frame) {
-        return enqueue_deepx(c, p, v, W, H, sh, rgba, nu, iter, s, out_frame); });
+        return enqueue_deepx(c, kMandel, p, v, W, H, sh, rgba, nu, iter, s, out_frame); });
 }
 
 static int check_deepx_ship(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, uint32_t W, uint32_t H, const fr_output* out)
@@ -2282,7 +1865,7 @@ extern "C" int fr_render_deepx_ship_async(fr_ctx* c, const fr_params* p, const f
     if (st != FR_OK) return st;
     return render_async("fr_render_deepx_ship_async", c, H, shard, out, hip_stream,
                         [&](auto sh, auto rgba, auto nu, auto iter, auto s, bool out_frame) {
-                            return enqueue_deepx_ship(c, p, v, W, H, sh, rgba, nu, iter, s, out_frame); });
+                            return enqueue_deepx(c, kShip, p, v, W, H, sh, rgba, nu, iter, s, out_frame); });
 }
 
 extern "C" int fr_render_deepx_ship(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, uint32_t W, uint32_t H,
@@ -2291,7 +1874,7 @@ extern "C" int fr_render_deepx_ship(fr_ctx* c, const fr_params* p, const fr_deep
     const int st = check_deepx_ship(c, p, v, W, H, out);
     if (st != FR_OK) return st;
     return render_sync(c, p, W, H, shard, out, [&](auto sh, auto rgba, auto nu, auto iter, auto s, bool out_frame) {
-        return enqueue_deepx_ship(c, p, v, W, H, sh, rgba, nu, iter, s, out_frame); });
+        return enqueue_deepx(c, kShip, p, v, W, H, sh, rgba, nu, iter, s, out_frame); });
 }
 
 /* ---- 8-bit export ------------------------------------------------------------------------------ */

@@ -1,9 +1,11 @@
 """The parameter cases of test_deep_cases_gpu.py as data, and the CPU predicates that say what each of them can see.
 
-The deep-view kernels (deep_kernel<DeepArgs / DeepBlaArgs / DeepXArgs / DeepXBlaArgs / DeepShipArgs>, fr_deep.hip.h) are
-tested elsewhere on many views and always with the FractalState defaults.  Here the views are few and the parameters
-vary: everything fr_deep_validate, fr_deepx_validate and fr_deep_ship_validate accept and fill_deep_args (fr_device.hip)
-turns into kernel arguments by hand.
+The deep-view kernels (fr_deep.hip.h: the eight instantiations deep_kernel<Deep[Ship][X][Bla]Args> -- DeepArgs, DeepBlaArgs,
+DeepXArgs, DeepXBlaArgs, DeepShipArgs, DeepShipBlaArgs, DeepShipXArgs, DeepShipXBlaArgs) are tested elsewhere on many
+views and always with the FractalState defaults.  Here the views are few and the parameters vary: everything
+fr_deep_validate, fr_deepx_validate and fr_deep_ship_validate accept and fill_deep_args (fr_device.hip) turns into kernel
+arguments by hand.  The cases run the five paths below (the first five of the eight kernels); the other three ship kernels
+read the same argument block through the same colour stage.
 
 A case is Case(path, view, params, W, H):
   path    deep | deep_bla | deepx | deepx_bla | ship

@@ -17,6 +17,9 @@
  *
  * Extended Burning Ship views (fr_render_deepx_ship): the ship's recurrence through the extended storage, and the ship's
  * rules with the zoom taken from the view's string (fr_deepx_ship_validate).
+ *
+ * Deep Julia views (fr_render_deep_julia, fr_render_deepx_julia): Mandelbrot's recurrence with c from a pair of doubles, twice --
+ * from the view's centre (orbit_loop's start point) and from 0 -- in either storage, and the two validators.
  */
 #include "fr_internal.h"
 
@@ -345,17 +348,11 @@ static void store_extended(const uint64_t* zr, const uint64_t* zi, fx_fmt fmt, d
  * (fr_render_deep_ship). */
 typedef enum { kOrbitMandelbrot = 0, kOrbitShip = 1 } orbit_formula;
 
-/* out_exp NULL: Z_n as doubles; else the extended storage */
-static int orbit_loop(const uint64_t* cr, const uint64_t* ci, fx_fmt fmt, orbit_formula formula, int32_t max_iter,
-                      float bailout, double* out_xy, int32_t* out_exp, int32_t* out_len)
+/* T = floor(bailout^2 2^(2F)) in 2L + 1 limbs: |Z|^2 2^(2F) = Zr^2 + Zi^2 is an integer, so "> bailout^2" is "> T" exactly */
+static void bailout_threshold(uint64_t* T, fx_fmt fmt, float bailout)
 {
-    const int L = fmt.L, L2 = 2 * fmt.L;
-    uint64_t zr[kMaxLimbs], zi[kMaxLimbs], ar[kMaxLimbs], ai[kMaxLimbs], t0[kMaxLimbs], t1[kMaxLimbs];
-    uint64_t sr[2 * kMaxLimbs + 1], si[2 * kMaxLimbs + 1], pr[2 * kMaxLimbs], ssum[2 * kMaxLimbs + 1], T[2 * kMaxLimbs + 1];
-    memset(zr, 0, sizeof zr); memset(zi, 0, sizeof zi);
-    memset(sr, 0, sizeof sr); memset(si, 0, sizeof si);
-    /* T = floor(bailout^2 2^(2F)): |Z|^2 2^(2F) = Zr^2 + Zi^2 is an integer, so "> bailout^2" is "> T" exactly */
-    memset(T, 0, sizeof T);
+    const int L2 = 2 * fmt.L;
+    memset(T, 0, sizeof(uint64_t) * (size_t)(L2 + 1));
     const double b2 = (double)bailout * (double)bailout;          /* exact: a float squared */
     int ex = 0;
     const double mant = frexp(b2, &ex);
@@ -364,9 +361,33 @@ static int orbit_loop(const uint64_t* cr, const uint64_t* ci, fx_fmt fmt, orbit_
     T[0] = mi;
     if (ts >= 0) shl_bits(T, L2 + 1, (int)ts);
     else T[0] = -ts >= 64 ? 0 : mi >> -ts;
+}
+
+/* out_exp NULL: Z_n as doubles; else the extended storage.  (sr0, si0) the orbit's first point, NULL for 0 (the Julia views'
+ * primary orbit starts at the view's centre, fr_render_deep_julia). */
+static int orbit_loop(const uint64_t* cr, const uint64_t* ci, const uint64_t* sr0, const uint64_t* si0, fx_fmt fmt,
+                      orbit_formula formula, int32_t max_iter, float bailout, double* out_xy, int32_t* out_exp,
+                      int32_t* out_len)
+{
+    const int L = fmt.L, L2 = 2 * fmt.L;
+    uint64_t zr[kMaxLimbs], zi[kMaxLimbs], ar[kMaxLimbs], ai[kMaxLimbs], t0[kMaxLimbs], t1[kMaxLimbs];
+    uint64_t sr[2 * kMaxLimbs + 1], si[2 * kMaxLimbs + 1], pr[2 * kMaxLimbs], ssum[2 * kMaxLimbs + 1], T[2 * kMaxLimbs + 1];
+    memset(zr, 0, sizeof zr); memset(zi, 0, sizeof zi);
+    memset(sr, 0, sizeof sr); memset(si, 0, sizeof si);
+    bailout_threshold(T, fmt, bailout);
 
     out_xy[0] = 0.0; out_xy[1] = 0.0;
     if (out_exp) out_exp[0] = FR_DEEPX_ZERO_EXP;
+    if (sr0 && si0) {
+        memcpy(zr, sr0, sizeof(uint64_t) * (size_t)L);
+        memcpy(zi, si0, sizeof(uint64_t) * (size_t)L);
+        if (out_exp) {
+            store_extended(zr, zi, fmt, out_xy, out_exp);
+        } else {
+            out_xy[0] = fixed_to_double(zr, fmt);
+            out_xy[1] = fixed_to_double(zi, fmt);
+        }
+    }
     int32_t n = 0;
     for (;; ++n) {
         if (n == max_iter) break;
@@ -515,7 +536,7 @@ static int reference_orbit(const char* who, orbit_formula formula, const fr_deep
     const fx_fmt fmt = {F, (F + 63) / 64 + 1};
     uint64_t cr[kMaxLimbs], ci[kMaxLimbs];
     if ((st = parse_centre(v, fmt, cr, ci)) != FR_OK) return st;
-    return orbit_loop(cr, ci, fmt, formula, max_iter, bailout, out_xy, NULL, out_len);
+    return orbit_loop(cr, ci, NULL, NULL, fmt, formula, max_iter, bailout, out_xy, NULL, out_len);
 }
 
 int fr_deep_reference_orbit(const fr_deep_view* v, double zoom, int32_t max_iter, float bailout, double* out_xy,
@@ -698,7 +719,7 @@ static int reference_orbit_x(const char* who, orbit_formula formula, const fr_de
     uint64_t cr[kMaxLimbs], ci[kMaxLimbs];
     const fr_deep_view c = {v->center_x, v->center_y, F, 0};
     if ((st = parse_centre(&c, fmt, cr, ci)) != FR_OK) return st;
-    return orbit_loop(cr, ci, fmt, formula, max_iter, bailout, out_mant_xy, out_exp2, out_len);
+    return orbit_loop(cr, ci, NULL, NULL, fmt, formula, max_iter, bailout, out_mant_xy, out_exp2, out_len);
 }
 
 int fr_deepx_reference_orbit(const fr_deepx_view* v, int32_t max_iter, float bailout, double* out_mant_xy, int32_t* out_exp2,
@@ -746,4 +767,153 @@ int fr_deepx_ship_validate(const fr_params* p, const fr_deepx_view* v, uint32_t 
     int32_t ze, F;
     if ((st = fr_deepx_resolve(v, &zm, &ze, &F)) != FR_OK) return st;
     return fr_deepx_check_centre(v->center_x, v->center_y, F);
+}
+
+/* ---- deep Julia views (fr_render_deep_julia, fr_render_deepx_julia) -----------------------------------------------------------
+ * c is a pair of doubles: round_half_even(c 2^F), exact wherever F holds the double's last bit (every c but a tiny one). */
+static void double_to_fixed(double c, fx_fmt fmt, uint64_t* out)
+{
+    memset(out, 0, sizeof(uint64_t) * (size_t)fmt.L);
+    if (c == 0.0) return;
+    int ex = 0;
+    const double mant = frexp(fabs(c), &ex);
+    const uint64_t mi = (uint64_t)ldexp(mant, 53);               /* |c| = mi 2^(ex - 53) */
+    const long s = (long)ex - 53 + fmt.F;
+    if (s >= 0) {
+        out[0] = mi;
+        shl_bits(out, fmt.L, (int)s);                            /* |c| < 2^32: below 2^(F + 32) */
+    } else if (-s < 64) {
+        const int k = (int)-s;
+        const uint64_t q = mi >> k, rem = mi & ((1ull << k) - 1), half = 1ull << (k - 1);
+        out[0] = q + (rem > half || (rem == half && (q & 1u)));
+    }                                                            /* else below 2^-11 of a unit: 0 */
+    if (c < 0.0) negate(out, fmt.L);
+}
+
+static int check_julia_c(double c_re, double c_im)
+{
+    if (!isfinite(c_re) || !isfinite(c_im) || !(fabs(c_re) < 4294967296.0) || !(fabs(c_im) < 4294967296.0))
+        return fr_set_error(FR_ERR_INVALID_ARG, "deep Julia views need a finite c with |c_re|, |c_im| < 2^32");
+    return FR_OK;
+}
+
+/* the centre rule of the Julia views: |P_0|^2 <= bailout^2, compared exactly */
+static int check_julia_centre(const uint64_t* cr, const uint64_t* ci, fx_fmt fmt, float bailout)
+{
+    const int L = fmt.L, L2 = 2 * fmt.L;
+    uint64_t ar[kMaxLimbs], ai[kMaxLimbs];
+    uint64_t sr[2 * kMaxLimbs + 1], si[2 * kMaxLimbs + 1], ssum[2 * kMaxLimbs + 1], T[2 * kMaxLimbs + 1];
+    memcpy(ar, cr, sizeof(uint64_t) * (size_t)L);
+    memcpy(ai, ci, sizeof(uint64_t) * (size_t)L);
+    if (is_negative(ar, L)) negate(ar, L);
+    if (is_negative(ai, L)) negate(ai, L);
+    mul_mag(sr, ar, ar, L);
+    mul_mag(si, ai, ai, L);
+    sr[L2] = si[L2] = 0;
+    add_n(ssum, sr, si, L2 + 1);
+    bailout_threshold(T, fmt, bailout);
+    if (cmp_n(ssum, T, L2 + 1) > 0)
+        return fr_set_error(FR_ERR_INVALID_ARG, "deep Julia view: the centre lies outside the bailout radius (|centre|^2 > bailout^2)");
+    return FR_OK;
+}
+
+/* P (from the centre) and Q (from 0) of z <- z^2 + c in one storage; the centre already parsed */
+static int julia_orbits(const uint64_t* zr, const uint64_t* zi, double c_re, double c_im, fx_fmt fmt, int32_t max_iter,
+                        float bailout, double* p_xy, int32_t* p_exp, int32_t* p_len, double* q_xy, int32_t* q_exp,
+                        int32_t* q_len)
+{
+    int st;
+    if ((st = check_julia_centre(zr, zi, fmt, bailout)) != FR_OK) return st;
+    uint64_t cr[kMaxLimbs], ci[kMaxLimbs];
+    double_to_fixed(c_re, fmt, cr);
+    double_to_fixed(c_im, fmt, ci);
+    if ((st = orbit_loop(cr, ci, zr, zi, fmt, kOrbitMandelbrot, max_iter, bailout, p_xy, p_exp, p_len)) != FR_OK) return st;
+    return orbit_loop(cr, ci, NULL, NULL, fmt, kOrbitMandelbrot, max_iter, bailout, q_xy, q_exp, q_len);
+}
+
+int fr_deep_julia_reference_orbits(const fr_deep_view* v, double c_re, double c_im, double zoom, int32_t max_iter, float bailout,
+                                   double* out_p_xy, int32_t* out_p_len, double* out_q_xy, int32_t* out_q_len)
+{
+    if (!out_p_xy || !out_p_len || !out_q_xy || !out_q_len)
+        return fr_set_error(FR_ERR_INVALID_ARG, "fr_deep_julia_reference_orbits: out is NULL");
+    if (max_iter < 1 || max_iter > (1 << 24))
+        return fr_set_error(FR_ERR_INVALID_ARG, "max_iterations %d outside [1, 2^24]", max_iter);
+    int st;
+    if ((st = check_zoom(zoom)) != FR_OK || (st = check_bailout(bailout)) != FR_OK || (st = check_julia_c(c_re, c_im)) != FR_OK)
+        return st;
+    const int F = view_frac_bits(v, zoom);
+    if (F < 0) return F;
+    const fx_fmt fmt = {F, (F + 63) / 64 + 1};
+    uint64_t zr[kMaxLimbs], zi[kMaxLimbs];
+    if ((st = parse_centre(v, fmt, zr, zi)) != FR_OK) return st;
+    return julia_orbits(zr, zi, c_re, c_im, fmt, max_iter, bailout, out_p_xy, NULL, out_p_len, out_q_xy, NULL, out_q_len);
+}
+
+int fr_deepx_julia_reference_orbits(const fr_deepx_view* v, double c_re, double c_im, int32_t max_iter, float bailout,
+                                    double* out_p_mant_xy, int32_t* out_p_exp2, int32_t* out_p_len, double* out_q_mant_xy,
+                                    int32_t* out_q_exp2, int32_t* out_q_len)
+{
+    if (!out_p_mant_xy || !out_p_exp2 || !out_p_len || !out_q_mant_xy || !out_q_exp2 || !out_q_len)
+        return fr_set_error(FR_ERR_INVALID_ARG, "fr_deepx_julia_reference_orbits: out is NULL");
+    if (max_iter < 1 || max_iter > (1 << 24))
+        return fr_set_error(FR_ERR_INVALID_ARG, "max_iterations %d outside [1, 2^24]", max_iter);
+    int st;
+    if ((st = check_bailout(bailout)) != FR_OK || (st = check_julia_c(c_re, c_im)) != FR_OK) return st;
+    double zm;
+    int32_t ze, F;
+    if ((st = fr_deepx_resolve(v, &zm, &ze, &F)) != FR_OK) return st;
+    const fx_fmt fmt = {F, (F + 63) / 64 + 1};
+    uint64_t zr[kMaxLimbs], zi[kMaxLimbs];
+    const fr_deep_view c = {v->center_x, v->center_y, F, 0};
+    if ((st = parse_centre(&c, fmt, zr, zi)) != FR_OK) return st;
+    return julia_orbits(zr, zi, c_re, c_im, fmt, max_iter, bailout, out_p_mant_xy, out_p_exp2, out_p_len, out_q_mant_xy,
+                        out_q_exp2, out_q_len);
+}
+
+/* what both validators ask of p; `zoomed`: the zoom is p's (fr_render_deep_julia), else the view's string */
+static int julia_validate_params(const char* who, const fr_params* p, uint32_t width, uint32_t height, int zoomed)
+{
+    if (p->fractal_type != FR_FRACTAL_JULIA)
+        return fr_set_error(FR_ERR_UNSUPPORTED, "%s renders FR_FRACTAL_JULIA only (got %d)", who, p->fractal_type);
+    if (p->precision != FR_PRECISION_F64)
+        return fr_set_error(FR_ERR_UNSUPPORTED, "%s needs FR_PRECISION_F64 (got %d)", who, p->precision);
+    fr_params q = *p;                                            /* the double centre (and the extended form's zoom) is not read */
+    q.center_x = 0.0; q.center_y = 0.0;
+    if (!zoomed) q.zoom = 1.0;
+    int st = fr_params_validate(&q, width, height);
+    if (st != FR_OK) return st;
+    if (zoomed && (st = check_zoom(p->zoom)) != FR_OK) return st;
+    if ((st = check_bailout(p->bailout)) != FR_OK || (st = check_julia_c(p->julia_c_real, p->julia_c_imag)) != FR_OK) return st;
+    if (p->flags & (FR_FLAG_DEEP_BLA | FR_FLAG_DEEPX_BLA | FR_FLAG_DEEP_SHIP_BLA | FR_FLAG_DEEPX_SHIP_BLA))
+        return fr_set_error(FR_ERR_UNSUPPORTED, "%s: the BLA flags are not available (their tables belong to the Mandelbrot and "
+                            "Burning Ship paths)", who);
+    return FR_OK;
+}
+
+int fr_deep_julia_validate(const fr_params* p, const fr_deep_view* v, uint32_t width, uint32_t height)
+{
+    if (!p || !v) return fr_set_error(FR_ERR_INVALID_ARG, "params/deep view is NULL");
+    int st = julia_validate_params("fr_render_deep_julia", p, width, height, 1);
+    if (st != FR_OK) return st;
+    const int F = view_frac_bits(v, p->zoom);
+    if (F < 0) return F;
+    uint64_t zr[kMaxLimbs], zi[kMaxLimbs];
+    const fx_fmt fmt = {F, (F + 63) / 64 + 1};
+    if ((st = parse_centre(v, fmt, zr, zi)) != FR_OK) return st;
+    return check_julia_centre(zr, zi, fmt, p->bailout);
+}
+
+int fr_deepx_julia_validate(const fr_params* p, const fr_deepx_view* v, uint32_t width, uint32_t height)
+{
+    if (!p || !v) return fr_set_error(FR_ERR_INVALID_ARG, "params/deep view is NULL");
+    int st = julia_validate_params("fr_render_deepx_julia", p, width, height, 0);
+    if (st != FR_OK) return st;
+    double zm;
+    int32_t ze, F;
+    if ((st = fr_deepx_resolve(v, &zm, &ze, &F)) != FR_OK) return st;
+    uint64_t zr[kMaxLimbs], zi[kMaxLimbs];
+    const fx_fmt fmt = {F, (F + 63) / 64 + 1};
+    const fr_deep_view c = {v->center_x, v->center_y, F, 0};
+    if ((st = parse_centre(&c, fmt, zr, zi)) != FR_OK) return st;
+    return check_julia_centre(zr, zi, fmt, p->bailout);
 }

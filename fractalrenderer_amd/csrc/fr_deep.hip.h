@@ -1,6 +1,7 @@
 /*
  * fr_deep.hip.h -- views deeper than double precision on gfx950: perturbation around one reference orbit with rebasing, for
- * the Mandelbrot set (fr_render_deep, fr_render_deepx) and the Burning Ship (fr_render_deep_ship, fr_render_deepx_ship).
+ * the Mandelbrot set (fr_render_deep, fr_render_deepx), the Burning Ship (fr_render_deep_ship, fr_render_deepx_ship) and, around
+ * two orbits, Julia sets (fr_render_deep_julia, fr_render_deepx_julia).
  *
  * The reference orbit Z_0 .. Z_N (fr_deep.c: fixed point on the host, stored as doubles) sits in HBM; every sample
  * iterates its delta dz = z - Z_m from it, dc being its offset from the centre.  The Mandelbrot step:
@@ -17,6 +18,10 @@
  *     the table build the single step, the merge products, the two norms and the load and store of an entry.  The ship's
  *     step is the Mandelbrot step on U = (|Z_m.x|, |Z_m.y|) and f = (fold(Z_m.x, dz.x), fold(Z_m.y, dz.y)), the fold a pair
  *     of compares and selects; its BLA step is a real 2x2 map where Mandelbrot's is a complex product.
+ *   - a third policy, JuliaFormula, without BLA: Mandelbrot's linear part, the ship's viewport map, no dc term (the sample's
+ *     offset is its first delta) and kTwoOrbits -- a lane starts on the orbit P of the view's centre, stored behind the
+ *     critical orbit Q in the same buffers, and its first rebase moves it onto Q (Q_0 = 0 keeps the rebase exact) for good.  A
+ *     lane carries its orbit's base and N; the extended loop flushes a delta whose exponent runs below -2^27 to zero.
  *   - four per-sample loops, each templated on the formula: deep_orbit (fp64 deltas), deep_orbit_bla (those with BLA),
  *     deep_orbit_x (extended-exponent deltas, fr_render_deepx*), deep_orbit_x_bla (those with BLA).  The BLA loops count the
  *     updates u a sample has covered, the others the loop index.  In all of them dz, dc, m and the count stay in registers;
@@ -39,7 +44,7 @@
  *     offset bla_offset(N - 1, k)), the radius r of every entry in an array of its own -- a double, or an XRad -- and
  *     (A, B) as F::kAbPerEntry double2 per entry (2: complex A, B; 4: the rows of the ship's real matrices), the extended
  *     tables with their two exponents in an int2.
- *   - deep_kernel<ARGS>, one kernel body for the eight argument blocks: a persistent grid of the resident set pulls runs of
+ *   - deep_kernel<ARGS>, one kernel body for the ten argument blocks: a persistent grid of the resident set pulls runs of
  *     8x8 sub-tiles from the sharded WaveQueue with unlimited stealing (deep views have very uneven iteration counts); one
  *     lane per sample, the aa x aa samples of a pixel one after the other in the lane; dc through the formula's viewport
  *     map, one dispatch on (extended, BLA) to the loop, then the colour stage of the formula's fp64 path: shade() and
@@ -137,9 +142,31 @@ struct DeepShipXBlaArgs {
     BlaXTable t;
 };
 
+/* A Julia view's second orbit: d.orbit / d.n_ref (and x.mant, x.exp2) are Q, the critical orbit a rebase lands on, so
+ * z1 = Q_1; P, the orbit of the centre every sample starts on, sits p_off points behind Q in the same buffers */
+struct JuliaStart {
+    int32_t p_off;
+    int32_t n_p;                         /* N_P >= 1 */
+};
+
+/* fr_render_deep_julia */
+struct DeepJuliaArgs {
+    DeepArgs d;
+    double log_bailout;                  /* as DeepShipArgs */
+    JuliaStart j;
+};
+
+/* fr_render_deepx_julia */
+struct DeepJuliaXArgs {
+    DeepXArgs x;
+    double log_bailout;
+    JuliaStart j;
+};
+
 constexpr int kXZero = FR_DEEPX_ZERO_EXP;
 constexpr int kXThr = -400;              /* extended while the normalised dz.e <= kXThr */
 constexpr int kXBlaExpLim = 1 << 27;     /* an entry whose A.e or B.e leaves [-2^27, 2^27] is void */
+constexpr int kXFlushExp = -(1 << 27);   /* Julia: a normalised dz with e below this becomes the zero (the header's FLUSH) */
 
 /* ---- extended reals ----------------------------------------------------------------------------------------------------
  * norm(x, y, e) of the header */
@@ -240,6 +267,7 @@ struct BlaLinX {
 struct MandelFormula {
     static constexpr int kFractal = 0;                /* the colour stage: shade() / colour_of() */
     static constexpr bool kLogBailoutLds = false;
+    static constexpr bool kTwoOrbits = false;         /* one orbit from 0, a dc term in every step */
     static constexpr int kAbPerEntry = 2;             /* complex A, B */
     using Lin = BlaLin<1>;
     using LinX = BlaLinX<1>;
@@ -323,6 +351,7 @@ struct MandelFormula {
 struct ShipFormula {
     static constexpr int kFractal = 2;
     static constexpr bool kLogBailoutLds = true;      /* shade<double, 2> at bailout <= 1 */
+    static constexpr bool kTwoOrbits = false;
     static constexpr int kAbPerEntry = 4;             /* the rows (a11, a12), (a21, a22), (b11, b12), (b21, b22) */
     using Lin = BlaLin<2>;
     using LinX = BlaLinX<2>;
@@ -442,6 +471,31 @@ struct ShipFormula {
     static __device__ __forceinline__ void norm_rows(double2* m, int& e) { x_norm4(m[0], m[1], e); }
 };
 
+/* z <- z^2 + c with c fixed and the sample's offset in z_0 (Julia): Mandelbrot's linear part, the ship's viewport map (the
+ * two shaders share it), no dc term, and two orbits -- a sample starts with dz = its offset on the orbit of the centre and
+ * rebases onto the critical orbit.  No BLA. */
+struct JuliaFormula {
+    static constexpr int kFractal = 1;
+    static constexpr bool kLogBailoutLds = true;      /* shade<double, 1> at bailout <= 1 */
+    static constexpr bool kTwoOrbits = true;
+
+    static __device__ __forceinline__ StepLin lin(const double Zx, const double Zy, const double dzx, const double dzy)
+    {
+        return MandelFormula::lin(Zx, Zy, dzx, dzy);
+    }
+    static __device__ __forceinline__ StepLinX lin_x(const double Zx, const double Zy, const int eZ, const double dzx,
+                                                     const double dzy, const int ed)
+    {
+        return MandelFormula::lin_x(Zx, Zy, eZ, dzx, dzy, ed);
+    }
+    /* julia.comp:221-225, :253-264, less the centre: the sample's first delta */
+    static __device__ __forceinline__ double2 dc(const int px, const int py, const int s, const int aa, const double resx,
+                                                 const double resy, const double zs)
+    {
+        return ShipFormula::dc(px, py, s, aa, resx, resy, zs);
+    }
+};
+
 /* ---- the steps ---------------------------------------------------------------------------------------------------------
  * The plain step: dz' from (Z_m, dz, dc) */
 template <class F>
@@ -449,7 +503,8 @@ __device__ __forceinline__ double2 deep_step(const double Zx, const double Zy, c
                                              const double dcx, const double dcy)
 {
     const StepLin l = F::lin(Zx, Zy, dzx, dzy);
-    return make_double2((l.tx * l.fx - l.ty * l.fy) + dcx, (l.tx * l.fy + l.ty * l.fx) + dcy);
+    if constexpr (F::kTwoOrbits) return make_double2(l.tx * l.fx - l.ty * l.fy, l.tx * l.fy + l.ty * l.fx);
+    else return make_double2((l.tx * l.fx - l.ty * l.fy) + dcx, (l.tx * l.fy + l.ty * l.fx) + dcy);
 }
 
 /* The extended step (the header's EXTENDED step): dz' = (n.x, n.y, en), not normalised */
@@ -465,9 +520,14 @@ __device__ __forceinline__ double2 deep_step_x(const double Zx, const double Zy,
     const double px = tx * l.fx - ty * l.fy;
     const double py = tx * l.fy + ty * l.fx;
     const int ep = et + ed;
-    en = ep > ec ? ep : ec;
-    return make_double2(__builtin_ldexp(px, ep - en) + __builtin_ldexp(cx, ec - en),
-                        __builtin_ldexp(py, ep - en) + __builtin_ldexp(cy, ec - en));
+    if constexpr (F::kTwoOrbits) {                                /* n = p */
+        en = ep;
+        return make_double2(px, py);
+    } else {
+        en = ep > ec ? ep : ec;
+        return make_double2(__builtin_ldexp(px, ep - en) + __builtin_ldexp(cx, ec - en),
+                            __builtin_ldexp(py, ep - en) + __builtin_ldexp(cy, ec - en));
+    }
 }
 
 /* ---- the tables --------------------------------------------------------------------------------------------------------
@@ -693,22 +753,30 @@ __device__ __forceinline__ BlaHitX bla_probe_x(const XRad* tr, const uint32_t n1
  * of the escaping update (max_iter if none), r2 = |z|^2 there.  z = Z_{m+1} + dz' with the signed orbit point for either
  * formula (Z_0 = 0: at m = 0 the ship's step is (|dz.x| + i |dz.y|)^2 + dc). */
 template <class F>
-__device__ __forceinline__ void deep_orbit(const DeepArgs& A, const double dcx, const double dcy, const double2 z1,
-                                           bool live, int& esc, double& er2)
+__device__ __forceinline__ void deep_orbit(const DeepArgs& A, const JuliaStart J, const double dcx, const double dcy,
+                                           const double2 z1, bool live, int& esc, double& er2)
 {
     const double2* __restrict__ orbit = A.orbit;
-    const int N = A.n_ref, max_iter = A.max_iter;
+    const int max_iter = A.max_iter;
+    int N = A.n_ref;                                             /* of the lane's orbit: Julia's lanes start on P */
+    int base = 0;                                                /* where that orbit starts in `orbit` */
     const double B2 = A.B2;
     double dzx = 0.0, dzy = 0.0;
     double Zx = 0.0, Zy = 0.0;                                   /* Z_m */
     double Znx = z1.x, Zny = z1.y;                               /* Z_{m+1} */
+    if constexpr (F::kTwoOrbits) {                               /* dz = the sample's offset, on P: one point for all lanes */
+        base = J.p_off; N = J.n_p;
+        const double2 p0 = orbit[base], p1 = orbit[base + 1];
+        dzx = dcx; dzy = dcy;
+        Zx = p0.x; Zy = p0.y; Znx = p1.x; Zny = p1.y;
+    }
     int m = 0;
     esc = max_iter;
     er2 = 0.0;
     for (int i = 0; i < max_iter; ++i) {
         if (__builtin_amdgcn_ballot_w64(live) == 0ull) break;
         if (!live) continue;
-        const double2 Znn = orbit[m + 2 <= N ? m + 2 : N];      /* Z_{m+2}, for the next step (m + 1 < N) */
+        const double2 Znn = orbit[base + (m + 2 <= N ? m + 2 : N)];   /* Z_{m+2}, for the next step (m + 1 < N) */
         const double2 n = deep_step<F>(Zx, Zy, dzx, dzy, dcx, dcy);
         const double nx = n.x, ny = n.y;
         ++m;
@@ -719,6 +787,7 @@ __device__ __forceinline__ void deep_orbit(const DeepArgs& A, const double dcx, 
         } else if (r2 < nx * nx + ny * ny || m == N) {           /* rebase */
             dzx = zx; dzy = zy; m = 0;
             Zx = 0.0; Zy = 0.0; Znx = z1.x; Zny = z1.y;
+            if constexpr (F::kTwoOrbits) { base = 0; N = A.n_ref; }   /* onto Q, for good */
         } else {
             dzx = nx; dzy = ny;
             Zx = Znx; Zy = Zny; Znx = Znn.x; Zny = Znn.y;
@@ -796,14 +865,16 @@ __device__ __forceinline__ void deep_orbit_bla(const DeepArgs& A, const BlaTable
 /* deep_orbit in two modes (the header's EXTENDED and PLAIN steps).  (cx, cy, ec) = dc, normalised.  z = Z_{m+1} (+) n with the
  * signed orbit point; escape, rebase, norm and the mode rule are the same for either formula. */
 template <class F>
-__device__ __forceinline__ void deep_orbit_x(const DeepXArgs& AA, const double cx, const double cy, const int ec, bool live,
-                                             int& esc, double& er2)
+__device__ __forceinline__ void deep_orbit_x(const DeepXArgs& AA, const JuliaStart J, const double cx, const double cy,
+                                             const int ec, bool live, int& esc, double& er2)
 {
     const DeepArgs& A = AA.d;
     const double2* __restrict__ orbit = A.orbit;
     const double2* __restrict__ mant = AA.mant;
     const int32_t* __restrict__ exp2 = AA.exp2;
-    const int N = A.n_ref, max_iter = A.max_iter;
+    const int max_iter = A.max_iter;
+    int N = A.n_ref;                                             /* of the lane's orbit, which starts at `base` in the arrays */
+    int base = 0;
     const double B2 = A.B2;
     const double cpx = x_plain(cx, ec), cpy = x_plain(cy, ec);   /* the plain mode's dc */
     double dzx = 0.0, dzy = 0.0;                                 /* plain: dz; extended: its mantissas */
@@ -814,13 +885,26 @@ __device__ __forceinline__ void deep_orbit_x(const DeepXArgs& AA, const double c
     const double2 z1 = mant[1];
     double Znx = z1.x, Zny = z1.y;                               /* Z_{m+1} */
     int eZn = exp2[1];
+    if constexpr (F::kTwoOrbits) {                               /* dz = the sample's offset (cx, cy, ec), on P, in its mode */
+        base = J.p_off; N = J.n_p;
+        ext = ec <= kXThr;
+        if (ext) {
+            const double2 a = mant[base], b = mant[base + 1];
+            dzx = cx; dzy = cy; ed = ec;
+            Zx = a.x; Zy = a.y; eZ = exp2[base]; Znx = b.x; Zny = b.y; eZn = exp2[base + 1];
+        } else {
+            const double2 a = orbit[base], b = orbit[base + 1];
+            dzx = __builtin_ldexp(cx, ec); dzy = __builtin_ldexp(cy, ec);
+            Zx = a.x; Zy = a.y; Znx = b.x; Zny = b.y;
+        }
+    }
     int m = 0;
     esc = max_iter;
     er2 = 0.0;
     for (int i = 0; i < max_iter; ++i) {
         if (__builtin_amdgcn_ballot_w64(live) == 0ull) break;
         if (!live) continue;
-        const int mn = m + 2 <= N ? m + 2 : N;                   /* Z_{m+2}, for the next step (m + 1 < N) */
+        const int mn = base + (m + 2 <= N ? m + 2 : N);          /* Z_{m+2}, for the next step (m + 1 < N) */
         double ax, ay;                                           /* the next dz */
         int ea = 0;
         bool reb;
@@ -843,6 +927,10 @@ __device__ __forceinline__ void deep_orbit_x(const DeepXArgs& AA, const double c
             reb = r2 < __builtin_ldexp(nx * nx + ny * ny, 2 * (en - ez)) || m == N;
             ax = reb ? zx : nx; ay = reb ? zy : ny; ea = reb ? ez : en;
             x_norm(ax, ay, ea);
+            if constexpr (F::kTwoOrbits) {
+                if (ea < kXFlushExp) { ax = 0.0; ay = 0.0; ea = kXZero; }   /* FLUSH */
+                if (reb) { base = 0; N = A.n_ref; }               /* onto Q, for good */
+            }
             if (reb) m = 0;
             if (ea <= kXThr) {                                    /* stays extended */
                 dzx = ax; dzy = ay; ed = ea;
@@ -869,6 +957,9 @@ __device__ __forceinline__ void deep_orbit_x(const DeepXArgs& AA, const double c
             reb = r2 < nx * nx + ny * ny || m == N;
             ax = reb ? zx : nx; ay = reb ? zy : ny;
             if (reb) m = 0;
+            if constexpr (F::kTwoOrbits) {
+                if (reb) { base = 0; N = A.n_ref; }
+            }
             if (!(fmax(fabs(ax), fabs(ay)) < 0x1p-400)) {         /* stays plain */
                 dzx = ax; dzy = ay;
                 if (reb) {
@@ -885,10 +976,10 @@ __device__ __forceinline__ void deep_orbit_x(const DeepXArgs& AA, const double c
         }
         /* the lane changed its mode: Z_m and Z_{m+1} (m < N here) from the new mode's arrays */
         if (ext) {
-            const double2 a = mant[m], b = mant[m + 1];
-            Zx = a.x; Zy = a.y; eZ = exp2[m]; Znx = b.x; Zny = b.y; eZn = exp2[m + 1];
+            const double2 a = mant[base + m], b = mant[base + m + 1];
+            Zx = a.x; Zy = a.y; eZ = exp2[base + m]; Znx = b.x; Zny = b.y; eZn = exp2[base + m + 1];
         } else {
-            const double2 a = orbit[m], b = orbit[m + 1];
+            const double2 a = orbit[base + m], b = orbit[base + m + 1];
             Zx = a.x; Zy = a.y; Znx = b.x; Zny = b.y;
         }
     }
@@ -1035,6 +1126,9 @@ __host__ __device__ __forceinline__ const DeepArgs& deep_args(const DeepShipArgs
 __host__ __device__ __forceinline__ const DeepArgs& deep_args(const DeepShipBlaArgs& A) { return A.s.d; }
 __host__ __device__ __forceinline__ const DeepArgs& deep_args(const DeepShipXArgs& A) { return A.x.d; }
 __host__ __device__ __forceinline__ const DeepArgs& deep_args(const DeepShipXBlaArgs& A) { return A.s.x.d; }
+__host__ __device__ __forceinline__ const DeepArgs& deep_args(const DeepJuliaArgs& A) { return A.d; }
+__host__ __device__ __forceinline__ const DeepArgs& deep_args(const DeepJuliaXArgs& A) { return A.x.d; }
+__host__ __device__ __forceinline__ const DeepXArgs& deepx_args(const DeepJuliaXArgs& A) { return A.x; }
 __host__ __device__ __forceinline__ const DeepXArgs& deepx_args(const DeepXArgs& A) { return A; }
 __host__ __device__ __forceinline__ const DeepXArgs& deepx_args(const DeepXBlaArgs& A) { return A.x; }
 __host__ __device__ __forceinline__ const DeepXArgs& deepx_args(const DeepShipXArgs& A) { return A.x; }
@@ -1043,19 +1137,29 @@ __device__ __forceinline__ double ship_log_bailout(const DeepShipArgs& A) { retu
 __device__ __forceinline__ double ship_log_bailout(const DeepShipBlaArgs& A) { return A.s.log_bailout; }
 __device__ __forceinline__ double ship_log_bailout(const DeepShipXArgs& A) { return A.log_bailout; }
 __device__ __forceinline__ double ship_log_bailout(const DeepShipXBlaArgs& A) { return A.s.log_bailout; }
+__device__ __forceinline__ double ship_log_bailout(const DeepJuliaArgs& A) { return A.log_bailout; }
+__device__ __forceinline__ double ship_log_bailout(const DeepJuliaXArgs& A) { return A.log_bailout; }
+/* where a sample starts: a Julia view's P; nothing for the formulas with one orbit */
+template <class ARGS>
+__device__ __forceinline__ JuliaStart julia_start(const ARGS& A)
+{
+    if constexpr (std::is_same<ARGS, DeepJuliaArgs>::value || std::is_same<ARGS, DeepJuliaXArgs>::value) return A.j;
+    else return JuliaStart{0, 0};
+}
 
 template <class T, class... U>
 constexpr bool is_any_of = (std::is_same<T, U>::value || ...);
 
-/* ARGS names the loop: Deep[Ship][X][Bla]Args = the formula, extended-exponent deltas, BLA (with the step counts) */
+/* ARGS names the loop: Deep[Ship|Julia][X][Bla]Args = the formula, extended-exponent deltas, BLA (with the step counts) */
 template <class ARGS>
 __global__ void __launch_bounds__(kBlockThreads)
 deep_kernel(const ARGS AA)
 {
     constexpr bool BLA = is_any_of<ARGS, DeepBlaArgs, DeepXBlaArgs, DeepShipBlaArgs, DeepShipXBlaArgs>;
-    constexpr bool X = is_any_of<ARGS, DeepXArgs, DeepXBlaArgs, DeepShipXArgs, DeepShipXBlaArgs>;
+    constexpr bool X = is_any_of<ARGS, DeepXArgs, DeepXBlaArgs, DeepShipXArgs, DeepShipXBlaArgs, DeepJuliaXArgs>;
     constexpr bool SHIP = is_any_of<ARGS, DeepShipArgs, DeepShipBlaArgs, DeepShipXArgs, DeepShipXBlaArgs>;
-    using F = std::conditional_t<SHIP, ShipFormula, MandelFormula>;
+    constexpr bool JULIA = is_any_of<ARGS, DeepJuliaArgs, DeepJuliaXArgs>;
+    using F = std::conditional_t<JULIA, JuliaFormula, std::conditional_t<SHIP, ShipFormula, MandelFormula>>;
     constexpr int FRACTAL = F::kFractal;
     const DeepArgs& A = deep_args(AA);
     __shared__ LdsBlock S;
@@ -1100,10 +1204,10 @@ deep_kernel(const ARGS AA)
                 int ec = deepx_args(AA).ze;
                 x_norm(cx, cy, ec);
                 if constexpr (BLA) deep_orbit_x_bla<F>(deepx_args(AA), AA.t, cx, cy, ec, inside, esc, r2, np, nb);
-                else deep_orbit_x<F>(deepx_args(AA), cx, cy, ec, inside, esc, r2);
+                else deep_orbit_x<F>(deepx_args(AA), julia_start(AA), cx, cy, ec, inside, esc, r2);
             } else {
                 if constexpr (BLA) deep_orbit_bla<F>(A, AA.t, cx, cy, z1, inside, esc, r2, np, nb);
-                else deep_orbit<F>(A, cx, cy, z1, inside, esc, r2);
+                else deep_orbit<F>(A, julia_start(AA), cx, cy, z1, inside, esc, r2);
             }
             if (BLA && inside) {
                 n_plain += np; n_bla += nb;
@@ -1119,7 +1223,7 @@ deep_kernel(const ARGS AA)
             const float n = (float)(aa * aa);
             acc[0] /= n; acc[1] /= n; acc[2] /= n;
         }
-        if (want_rgb && (A.flags & FR_FLAG_POST_CHAIN)) post_chain(acc, A.brightness, A.saturation, A.contrast, SHIP);
+        if (want_rgb && (A.flags & FR_FLAG_POST_CHAIN)) post_chain(acc, A.brightness, A.saturation, A.contrast, FRACTAL != 0);
         if (!inside) return;
         const size_t o = plane_index(A.g, px, py, lrow);
         if (A.rgba) A.rgba[o] = make_float4(acc[0], acc[1], acc[2], 1.0f);

@@ -39,16 +39,19 @@ struct OrbitKey {
     char* y;
     int32_t bits, max_iter;
     float bailout;              /* compared by its bits */
+    uint64_t c_bits[2];         /* Julia: the bits of c (0 in the other formulas' slots) */
 };
 
-enum { kMandel = 0, kShip = 1 };    /* the formula of a deep view: the index of its cache slots */
+/* the formula of a deep view: the index of its cache slots (kJulia has orbit slots only: no BLA) */
+enum { kMandel = 0, kShip = 1, kJulia = 2 };
 
 /* One cache slot of reference orbits of deep views: the buffers and what they hold */
 struct DeepOrbit {
     char* host;                 /* pinned upload buffer, cap points */
     char* dev;
     size_t cap;
-    int32_t len;                /* N + 1 */
+    int32_t len;                /* N + 1 (a Julia slot: of Q, at point 0; P lies cap / 2 points behind it) */
+    int32_t len_p;              /* a Julia slot: N_P + 1 */
     OrbitKey key;               /* of dev */
     uint64_t gen;               /* bumped whenever dev receives another orbit */
     int wg_per_cu;              /* resident workgroups per CU of the slot's unflagged deep_kernel (0 = not asked yet) */
@@ -122,11 +125,12 @@ struct fr_ctx {
     uint32_t div_next;
     int phoenix_wg_per_cu[2];   /* resident workgroups per CU of phoenix_kernel<float> / <double> (0 = not asked yet) */
     int mandelbulb_wg_per_cu[2];  /* ... of mandelbulb_kernel<false> / <true> (0 = not asked yet) */
-    /* deep views, per formula (kMandel, kShip): the most recent reference orbit and its BLA table, for the fp64 views
-     * (fr_render_deep, fr_render_deep_ship) and for the extended ones (fr_render_deepx, fr_render_deepx_ship).  The four
-     * paths share nothing. */
-    DeepOrbit deep[2];          /* plain doubles Z_0 .. Z_N: 2 cap doubles pinned, cap double2 on the device */
-    DeepOrbit deepx[2];         /* the extended storage.  One pinned and one device block of cap points each: the plain
+    /* deep views, per formula (kMandel, kShip, kJulia): the most recent reference orbit and its BLA table, for the fp64 views
+     * (fr_render_deep, fr_render_deep_ship, fr_render_deep_julia) and for the extended ones (fr_render_deepx,
+     * fr_render_deepx_ship, fr_render_deepx_julia).  The six paths share nothing.  A Julia slot holds two orbits: Q in the first
+     * half of every array, P in the second. */
+    DeepOrbit deep[3];          /* plain doubles Z_0 .. Z_N: 2 cap doubles pinned, cap double2 on the device */
+    DeepOrbit deepx[3];         /* the extended storage.  One pinned and one device block of cap points each: the plain
                                  * doubles, the mantissa pairs, the exponents, in this order. */
     BlaSlot bla[2];             /* FR_FLAG_DEEP_BLA, FR_FLAG_DEEP_SHIP_BLA: the tables of deep[] */
     BlaSlot blax[2];            /* FR_FLAG_DEEPX_BLA, FR_FLAG_DEEPX_SHIP_BLA: the tables of deepx[] */
@@ -215,7 +219,8 @@ extern "C" void fr_ctx_destroy(fr_ctx* c)
     if (c->frame_buf) (void)hipFree(c->frame_buf);
     if (c->orbit_host) (void)hipHostFree(c->orbit_host);
     if (c->orbit_dev) (void)hipFree(c->orbit_dev);
-    for (DeepOrbit* o : {&c->deep[kMandel], &c->deep[kShip], &c->deepx[kMandel], &c->deepx[kShip]}) {
+    for (DeepOrbit* o : {&c->deep[kMandel], &c->deep[kShip], &c->deep[kJulia], &c->deepx[kMandel], &c->deepx[kShip],
+                         &c->deepx[kJulia]}) {
         if (o->host) (void)hipHostFree(o->host);
         if (o->dev) (void)hipFree(o->dev);
         free(o->key.x);
@@ -750,6 +755,28 @@ static int orbit_key_store(OrbitKey& k, const char* x, const char* y, int32_t bi
     return FR_OK;
 }
 
+/* A slot about to receive another orbit: everything that may still read its pinned or its device block has finished (an earlier
+ * upload or render on this stream, the context's own or the stream of the previous render; with `t` the slot's last BLA
+ * render, wherever it went), its key is void, and both blocks hold `need` points of `point_bytes` */
+static int orbit_slot_prepare(fr_ctx* c, DeepOrbit& o, const BlaSlot* t, hipStream_t stream, size_t need, size_t point_bytes)
+{
+    FR_HIP_TRY(hipStreamSynchronize(stream));
+    FR_HIP_TRY(hipStreamSynchronize(c->stream));
+    if (c->have_render && c->last_stream != stream) FR_HIP_TRY(hipStreamSynchronize(c->last_stream));
+    if (t && t->ev_valid) FR_HIP_TRY(hipEventSynchronize(t->ev));
+    o.key.valid = false;
+    ++o.gen;
+    if (need > o.cap) {
+        if (o.host) { (void)hipHostFree(o.host); o.host = nullptr; }
+        if (o.dev) { (void)hipFree(o.dev); o.dev = nullptr; }
+        o.cap = 0;
+        FR_HIP_TRY(hipHostMalloc((void**)&o.host, need * point_bytes));
+        FR_HIP_TRY(hipMalloc((void**)&o.dev, need * point_bytes));
+        o.cap = need;
+    }
+    return FR_OK;
+}
+
 /* fp64 views: the plain-double orbit of the view in the formula's cache slot (fr_render_deep's, fr_render_deep_ship's) unless
  * the slot holds it already */
 static int orbit_slot_fill(fr_ctx* c, int f, const fr_params* p, const fr_deep_view* v, hipStream_t stream)
@@ -759,23 +786,8 @@ static int orbit_slot_fill(fr_ctx* c, int f, const fr_params* p, const fr_deep_v
     const int32_t bits = v->frac_bits ? v->frac_bits : fr_deep_frac_bits(p->zoom);
     const int32_t max_iter = p->max_iterations;
     if (orbit_key_matches(o.key, v->center_x, v->center_y, bits, max_iter, p->bailout)) return FR_OK;
-    /* the pinned buffer may still feed an earlier upload, the device orbit an earlier render (on this stream, the
-     * context's own or the stream of the previous render) */
-    FR_HIP_TRY(hipStreamSynchronize(stream));
-    FR_HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->have_render && c->last_stream != stream) FR_HIP_TRY(hipStreamSynchronize(c->last_stream));
-    if (t.ev_valid) FR_HIP_TRY(hipEventSynchronize(t.ev));                /* the slot's last BLA render, wherever it went */
-    o.key.valid = false;
-    ++o.gen;
-    const size_t need = (size_t)max_iter + 1;
-    if (need > o.cap) {
-        if (o.host) { (void)hipHostFree(o.host); o.host = nullptr; }
-        if (o.dev) { (void)hipFree(o.dev); o.dev = nullptr; }
-        o.cap = 0;
-        FR_HIP_TRY(hipHostMalloc((void**)&o.host, need * 2 * sizeof(double)));
-        FR_HIP_TRY(hipMalloc((void**)&o.dev, need * sizeof(double2)));
-        o.cap = need;
-    }
+    const int ps = orbit_slot_prepare(c, o, &t, stream, (size_t)max_iter + 1, sizeof(double2));
+    if (ps != FR_OK) return ps;
     int32_t len = 0;
     const int st = (f == kShip ? fr_deep_ship_reference_orbit : fr_deep_reference_orbit)(v, p->zoom, max_iter, p->bailout,
                                                                                          (double*)o.host, &len);
@@ -969,23 +981,9 @@ static int xorbit_slot_fill(fr_ctx* c, int f, const fr_params* p, const fr_deepx
     const BlaSlot& t = c->blax[f];
     const int32_t max_iter = p->max_iterations;
     if (orbit_key_matches(o.key, v->center_x, v->center_y, bits, max_iter, p->bailout)) return FR_OK;
-    /* as orbit_slot_fill: the pinned block may still feed an upload, the device block an earlier render */
-    FR_HIP_TRY(hipStreamSynchronize(stream));
-    FR_HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->have_render && c->last_stream != stream) FR_HIP_TRY(hipStreamSynchronize(c->last_stream));
-    if (t.ev_valid) FR_HIP_TRY(hipEventSynchronize(t.ev));                /* the slot's last BLA render, wherever it went */
-    o.key.valid = false;
-    ++o.gen;
-    const size_t need = (size_t)max_iter + 1;
     const size_t point_bytes = 2 * sizeof(double2) + sizeof(int32_t);
-    if (need > o.cap) {
-        if (o.host) { (void)hipHostFree(o.host); o.host = nullptr; }
-        if (o.dev) { (void)hipFree(o.dev); o.dev = nullptr; }
-        o.cap = 0;
-        FR_HIP_TRY(hipHostMalloc((void**)&o.host, need * point_bytes));
-        FR_HIP_TRY(hipMalloc((void**)&o.dev, need * point_bytes));
-        o.cap = need;
-    }
+    const int ps = orbit_slot_prepare(c, o, &t, stream, (size_t)max_iter + 1, point_bytes);
+    if (ps != FR_OK) return ps;
     const size_t cap = o.cap;
     double* plain = (double*)o.host;
     double* mant = plain + 2 * cap;
@@ -1049,6 +1047,119 @@ static int enqueue_deepx(fr_ctx* c, int f, const fr_params* p, const fr_deepx_vi
     const int rs = fr_deepx_resolve(v, &zm, &ze, &bits);
     if (rs != FR_OK) return rs;
     return enqueue_deepx_at(c, f, p, v, zm, ze, bits, W, H, shard, rgba, nu, iter, stream, out_frame);
+}
+
+/* ---- Julia views (fr_render_deep_julia, fr_render_deepx_julia) ---------------------------------------------------------
+ * Two orbits per slot (the header's P and Q), keyed by the bits of c as well; no BLA, so nothing but an earlier render can
+ * still read the slot.  ext: the extended storage, `zoom` then being the view's zoom string. */
+static int julia_slot_fill(fr_ctx* c, bool ext, const fr_params* p, const char* cx, const char* cy, const char* zoom,
+                           int32_t bits, hipStream_t stream)
+{
+    DeepOrbit& o = (ext ? c->deepx : c->deep)[kJulia];
+    const int32_t max_iter = p->max_iterations;
+    uint64_t cb[2];
+    memcpy(&cb[0], &p->julia_c_real, sizeof(uint64_t));
+    memcpy(&cb[1], &p->julia_c_imag, sizeof(uint64_t));
+    if (orbit_key_matches(o.key, cx, cy, bits, max_iter, p->bailout) && o.key.c_bits[0] == cb[0] && o.key.c_bits[1] == cb[1])
+        return FR_OK;
+    const size_t point_bytes = ext ? 2 * sizeof(double2) + sizeof(int32_t) : sizeof(double2);
+    const int ps = orbit_slot_prepare(c, o, nullptr, stream, 2 * ((size_t)max_iter + 1), point_bytes);   /* an even capacity */
+    if (ps != FR_OK) return ps;
+    const size_t cap = o.cap, half = cap / 2;
+    double* plain = (double*)o.host;
+    int32_t len_p = 0, len_q = 0;
+    int st;
+    if (ext) {
+        double* mant = plain + 2 * cap;
+        int32_t* exp2 = (int32_t*)(mant + 2 * cap);
+        const fr_deepx_view w = {cx, cy, zoom, bits, 0};
+        st = fr_deepx_julia_reference_orbits(&w, p->julia_c_real, p->julia_c_imag, max_iter, p->bailout, mant + 2 * half,
+                                             exp2 + half, &len_p, mant, exp2, &len_q);
+        if (st != FR_OK) return st;
+        for (const size_t b : {(size_t)0, half}) {
+            const int32_t len = b ? len_p : len_q;
+            for (int32_t n = 0; n < len; ++n) {
+                plain[2 * (b + n)] = ldexp(mant[2 * (b + n)], exp2[b + n]);
+                plain[2 * (b + n) + 1] = ldexp(mant[2 * (b + n) + 1], exp2[b + n]);
+            }
+        }
+    } else {
+        const fr_deep_view w = {cx, cy, bits, 0};
+        st = fr_deep_julia_reference_orbits(&w, p->julia_c_real, p->julia_c_imag, p->zoom, max_iter, p->bailout, plain + 2 * half,
+                                            &len_p, plain, &len_q);
+        if (st != FR_OK) return st;
+    }
+    /* what the host wrote, nothing else: per array, Q's points at 0 and P's at `half` */
+    for (const size_t b : {(size_t)0, half}) {
+        const size_t len = (size_t)(b ? len_p : len_q);
+        FR_HIP_TRY(hipMemcpyAsync(o.dev + b * sizeof(double2), o.host + b * sizeof(double2), len * sizeof(double2),
+                                  hipMemcpyHostToDevice, stream));
+        if (ext) {
+            const size_t mo = (cap + b) * sizeof(double2), eo = 2 * cap * sizeof(double2) + b * sizeof(int32_t);
+            FR_HIP_TRY(hipMemcpyAsync(o.dev + mo, o.host + mo, len * sizeof(double2), hipMemcpyHostToDevice, stream));
+            FR_HIP_TRY(hipMemcpyAsync(o.dev + eo, o.host + eo, len * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+        }
+    }
+    FR_HIP_TRY(hipStreamSynchronize(stream));     /* a later render of this view may go to another stream */
+    const int ks = orbit_key_store(o.key, cx, cy, bits, max_iter, p->bailout);
+    if (ks != FR_OK) return ks;
+    o.key.c_bits[0] = cb[0]; o.key.c_bits[1] = cb[1];
+    o.len = len_q; o.len_p = len_p;
+    return FR_OK;
+}
+
+static int enqueue_deep_julia(fr_ctx* c, const fr_params* p, const fr_deep_view* v, uint32_t W, uint32_t H, const fr_shard* shard,
+                              float* rgba, void* nu, int32_t* iter, hipStream_t stream, bool out_frame)
+{
+    fr_shard norm;
+    uint32_t rows_local = 0;
+    const int sh = begin_shard(c, shard, H, &norm, &rows_local);
+    if (sh != FR_OK || rows_local == 0) return sh;
+    const int32_t bits = v->frac_bits ? v->frac_bits : fr_deep_frac_bits(p->zoom);
+    const int os = julia_slot_fill(c, false, p, v->center_x, v->center_y, nullptr, bits, stream);
+    if (os != FR_OK) return os;
+
+    DeepOrbit& o = c->deep[kJulia];
+    DeepJuliaArgs j;
+    memset(&j, 0, sizeof(j));
+    DeepArgs& a = j.d;
+    a.orbit = reinterpret_cast<const double2*>(o.dev); a.n_ref = o.len - 1;
+    a.zoom = p->zoom;
+    j.j.p_off = (int32_t)(o.cap / 2); j.j.n_p = o.len_p - 1;
+    fill_deep_args(a, c, p, tile_geom(W, H, rows_local, &norm, out_frame), rgba, nu, iter);
+    j.log_bailout = log((double)p->bailout);     /* as fill_params */
+    return launch_one_pass(c, stream, "deep_kernel<DeepJuliaArgs>", deep_kernel<DeepJuliaArgs>, j, a.g, a.q, o.wg_per_cu, false);
+}
+
+static int enqueue_deepx_julia(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, uint32_t W, uint32_t H,
+                               const fr_shard* shard, float* rgba, void* nu, int32_t* iter, hipStream_t stream, bool out_frame)
+{
+    double zm = 0.0;
+    int32_t ze = 0, bits = 0;
+    const int rs = fr_deepx_resolve(v, &zm, &ze, &bits);
+    if (rs != FR_OK) return rs;
+    fr_shard norm;
+    uint32_t rows_local = 0;
+    const int sh = begin_shard(c, shard, H, &norm, &rows_local);
+    if (sh != FR_OK || rows_local == 0) return sh;
+    const int os = julia_slot_fill(c, true, p, v->center_x, v->center_y, v->zoom, bits, stream);
+    if (os != FR_OK) return os;
+
+    DeepOrbit& o = c->deepx[kJulia];
+    DeepJuliaXArgs j;
+    memset(&j, 0, sizeof(j));
+    DeepXArgs& x = j.x;
+    x.zm = zm;
+    x.ze = ze;
+    DeepArgs& a = x.d;
+    a.orbit = reinterpret_cast<const double2*>(o.dev);
+    x.mant = a.orbit + o.cap;
+    x.exp2 = reinterpret_cast<const int32_t*>(x.mant + o.cap);
+    a.n_ref = o.len - 1;
+    j.j.p_off = (int32_t)(o.cap / 2); j.j.n_p = o.len_p - 1;
+    fill_deep_args(a, c, p, tile_geom(W, H, rows_local, &norm, out_frame), rgba, nu, iter);
+    j.log_bailout = log((double)p->bailout);     /* as fill_params */
+    return launch_one_pass(c, stream, "deep_kernel<DeepJuliaXArgs>", deep_kernel<DeepJuliaXArgs>, j, a.g, a.q, o.wg_per_cu, false);
 }
 
 /* ---- deep zoom sequences (fr_deep_sequence; the rules are in the header, the host planning in fr_deepseq.c) ---------------
@@ -1875,6 +1986,58 @@ extern "C" int fr_render_deepx_ship(fr_ctx* c, const fr_params* p, const fr_deep
     if (st != FR_OK) return st;
     return render_sync(c, p, W, H, shard, out, [&](auto sh, auto rgba, auto nu, auto iter, auto s, bool out_frame) {
         return enqueue_deepx(c, kShip, p, v, W, H, sh, rgba, nu, iter, s, out_frame); });
+}
+
+static int check_deep_julia(fr_ctx* c, const fr_params* p, const fr_deep_view* v, uint32_t W, uint32_t H, const fr_output* out)
+{
+    if (!c) return fr_set_error(FR_ERR_INVALID_ARG, "ctx is NULL");
+    if (!p || !v || !out) return fr_set_error(FR_ERR_INVALID_ARG, "params/deep view/out is NULL");
+    return fr_deep_julia_validate(p, v, W, H);
+}
+
+extern "C" int fr_render_deep_julia_async(fr_ctx* c, const fr_params* p, const fr_deep_view* v, uint32_t W, uint32_t H,
+                                          const fr_shard* shard, const fr_output* out, void* hip_stream)
+{
+    const int st = check_deep_julia(c, p, v, W, H, out);
+    if (st != FR_OK) return st;
+    return render_async("fr_render_deep_julia_async", c, H, shard, out, hip_stream,
+                        [&](auto sh, auto rgba, auto nu, auto iter, auto s, bool out_frame) {
+                            return enqueue_deep_julia(c, p, v, W, H, sh, rgba, nu, iter, s, out_frame); });
+}
+
+extern "C" int fr_render_deep_julia(fr_ctx* c, const fr_params* p, const fr_deep_view* v, uint32_t W, uint32_t H,
+                                    const fr_shard* shard, const fr_output* out)
+{
+    const int st = check_deep_julia(c, p, v, W, H, out);
+    if (st != FR_OK) return st;
+    return render_sync(c, p, W, H, shard, out, [&](auto sh, auto rgba, auto nu, auto iter, auto s, bool out_frame) {
+        return enqueue_deep_julia(c, p, v, W, H, sh, rgba, nu, iter, s, out_frame); });
+}
+
+static int check_deepx_julia(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, uint32_t W, uint32_t H, const fr_output* out)
+{
+    if (!c) return fr_set_error(FR_ERR_INVALID_ARG, "ctx is NULL");
+    if (!p || !v || !out) return fr_set_error(FR_ERR_INVALID_ARG, "params/deep view/out is NULL");
+    return fr_deepx_julia_validate(p, v, W, H);
+}
+
+extern "C" int fr_render_deepx_julia_async(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, uint32_t W, uint32_t H,
+                                           const fr_shard* shard, const fr_output* out, void* hip_stream)
+{
+    const int st = check_deepx_julia(c, p, v, W, H, out);
+    if (st != FR_OK) return st;
+    return render_async("fr_render_deepx_julia_async", c, H, shard, out, hip_stream,
+                        [&](auto sh, auto rgba, auto nu, auto iter, auto s, bool out_frame) {
+                            return enqueue_deepx_julia(c, p, v, W, H, sh, rgba, nu, iter, s, out_frame); });
+}
+
+extern "C" int fr_render_deepx_julia(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, uint32_t W, uint32_t H,
+                                     const fr_shard* shard, const fr_output* out)
+{
+    const int st = check_deepx_julia(c, p, v, W, H, out);
+    if (st != FR_OK) return st;
+    return render_sync(c, p, W, H, shard, out, [&](auto sh, auto rgba, auto nu, auto iter, auto s, bool out_frame) {
+        return enqueue_deepx_julia(c, p, v, W, H, sh, rgba, nu, iter, s, out_frame); });
 }
 
 /* ---- 8-bit export ------------------------------------------------------------------------------ */

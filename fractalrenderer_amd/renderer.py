@@ -316,10 +316,31 @@ class Renderer:
         self._render_call(self._lib.fr_render_deepx_ship, self._lib.fr_render_deepx_ship_async, (C.byref(p), C.byref(vx)), width,
                           height, Precision.F64, rows, rgba, nu, iter, shard, stream, sync)
 
+    def render_deep_julia(self, state: FractalState, width: int, height: int, view: Optional[DeepView] = None, *,
+                          post_chain: bool = False, rgba=None, nu=None, iter=None, shard: Optional[Shard] = None,
+                          stream: Optional[int] = None, sync: bool = True) -> None:
+        """fr_render_deep_julia / fr_render_deep_julia_async: a Julia set view deeper than double precision, by perturbation
+        around two reference orbits computed on the host (the orbit of the centre, and the critical orbit samples rebase
+        onto).  c = (state.julia_c_real, state.julia_c_imag); `view` carries the centre as decimal strings (default "0",
+        "0"), the zoom and every other field come from `state` (its double centre is not read).  A view with a zoom string
+        (DeepView(..., zoom="1e-400")) goes to fr_render_deepx_julia / fr_render_deepx_julia_async: extended-exponent deltas,
+        zooms down to 1e-1000, state.zoom not read.  Always fp64; planes, shard, stream and sync as for render_deep().
+        There is no BLA for Julia views."""
+        p = state.to_params(FractalType.JuliaSet, Precision.F64, post_chain)
+        rows = shard.rows(height) if shard else height
+        if view is not None and view.zoom is not None:
+            vx = view.to_cx()
+            self._render_call(self._lib.fr_render_deepx_julia, self._lib.fr_render_deepx_julia_async, (C.byref(p), C.byref(vx)),
+                              width, height, Precision.F64, rows, rgba, nu, iter, shard, stream, sync)
+            return
+        v = (view or DeepView("0", "0")).to_c()
+        self._render_call(self._lib.fr_render_deep_julia, self._lib.fr_render_deep_julia_async, (C.byref(p), C.byref(v)), width,
+                          height, Precision.F64, rows, rgba, nu, iter, shard, stream, sync)
+
     def _render_call(self, fn_sync, fn_async, params: tuple, width: int, height: int, precision: Precision, rows: int,
                      rgba, nu, it, shard: Optional[Shard], stream: Optional[int], sync: bool) -> None:
         """the planes, the shard and the sync / async entry of render(), render_phoenix(), render_mandelbulb(), render_deep(),
-        render_deep_ship() and render_deepx_ship();
+        render_deep_ship(), render_deepx_ship() and render_deep_julia();
         params: the entry's
         arguments between the context and the frame size"""
         out = self._output(precision, rows, width, rgba, nu, it)

@@ -269,3 +269,25 @@ def deepx_ship_reference_orbit(view: DeepView, max_iterations: int, bailout: flo
     _capi.check(_capi.lib().fr_deepx_ship_reference_orbit(_capi.C.byref(v), int(max_iterations), _F32(bailout), mant.ctypes.data,
                                                           exp2.ctypes.data, _capi.C.byref(n)))
     return mant[:n.value].copy(), exp2[:n.value].copy()
+
+
+def deep_julia_reference_orbits(view: DeepView, c, max_iterations: int, bailout: float = 4.0, zoom: float = 1.0) -> tuple:
+    """fr_deep_julia_reference_orbits / fr_deepx_julia_reference_orbits: the two orbits of a deep Julia view (host only).
+    c = (c_re, c_im), doubles.  P starts at the view's centre, Q at 0.  A view without a zoom string gives
+    (P, Q) as (N_P + 1, 2) and (N_Q + 1, 2) float64 arrays, F taken from `zoom`; a view with one gives the extended storage,
+    ((P mantissas, P exponents), (Q mantissas, Q exponents)) as deepx_reference_orbit does, and `zoom` is not read."""
+    n = int(max_iterations) + 1
+    np_, nq = _capi.C.c_int32(), _capi.C.c_int32()
+    pm, qm = np.empty((n, 2), np.float64), np.empty((n, 2), np.float64)
+    if view.zoom is None:
+        v = view.to_c()
+        _capi.check(_capi.lib().fr_deep_julia_reference_orbits(_capi.C.byref(v), float(c[0]), float(c[1]), float(zoom),
+                                                               int(max_iterations), _F32(bailout), pm.ctypes.data,
+                                                               _capi.C.byref(np_), qm.ctypes.data, _capi.C.byref(nq)))
+        return pm[:np_.value].copy(), qm[:nq.value].copy()
+    pe, qe = np.empty(n, np.int32), np.empty(n, np.int32)
+    vx = view.to_cx()
+    _capi.check(_capi.lib().fr_deepx_julia_reference_orbits(_capi.C.byref(vx), float(c[0]), float(c[1]), int(max_iterations),
+                                                            _F32(bailout), pm.ctypes.data, pe.ctypes.data, _capi.C.byref(np_),
+                                                            qm.ctypes.data, qe.ctypes.data, _capi.C.byref(nq)))
+    return (pm[:np_.value].copy(), pe[:np_.value].copy()), (qm[:nq.value].copy(), qe[:nq.value].copy())

@@ -974,6 +974,88 @@ int fr_deep_ship_sequence_create(fr_ctx* ctx, const fr_params* p, const fr_deep_
  * FR_ERR_UNSUPPORTED if there is no such call.  The other three counts do not report these calls. */
 int fr_ctx_last_deepx_ship_steps(fr_ctx* ctx, uint64_t out[3]);
 
+/* ---- Julia set views deeper than double precision: perturbation around two reference orbits -----------------------------------
+ * fr_render with FR_FRACTAL_JULIA holds its centre as a double: below a zoom of about 1e-13 neighbouring pixels collapse onto
+ * one z_0.  fr_render_deep_julia takes the centre as decimal strings (fr_deep_view, p->zoom in [1e-290, 1e3]),
+ * fr_render_deepx_julia the zoom as a string too (fr_deepx_view, 1e-1000 .. 1e3).  c = (p->julia_c_real, p->julia_c_imag),
+ * both doubles.  p->center_x, p->center_y and, in the extended form, p->zoom are ignored.
+ *
+ * A Julia view does not fit the loops above as they stand: its reference orbit starts at the view's centre, not at 0; there is
+ * no dc term (c is the same for every sample, the sample's offset is its first delta); and the rebase "dz = z, m = 0" is only
+ * valid on an orbit whose first point is 0.  Hence TWO orbits, both on the host in fr_render_deep's fixed point (the same F
+ * rules, floor shifts and escape test "|Z_n|^2 > bailout^2, compared exactly, tested before the update"), with the
+ * recurrence of Mandelbrot's orbit; c enters the fixed point as the exact value of its doubles, rounded to nearest-even only
+ * where F is too small to hold it:
+ *   P (primary):   P_0 = the centre, P_{n+1} = P_n^2 + c, stored P_0 .. P_{N_P}
+ *   Q (critical):  Q_0 = 0,          Q_{n+1} = Q_n^2 + c, stored Q_0 .. Q_{N_Q}: fr_deep_reference_orbit's orbit at C = c, so
+ *                  Q_1 = c and N_Q >= 1
+ * A centre with |P_0|^2 > bailout^2 (exact compare) is FR_ERR_INVALID_ARG; hence N_P >= 1.  A sample starts on P and moves to
+ * Q at its first rebase, for good; that rebase is exact because Q_0 = 0, which is the whole no-glitch argument of
+ * fr_render_deep, unchanged.
+ *
+ * Per sample, fp64 deltas (fr_render_deep_julia): d0 = fr_render_deep_ship's dc of the pixel and sub-sample -- Julia's viewport
+ * map less the centre (shaders/julia.comp:221-225, :253-264; sx OUTER, aspect of the WHOLE frame; the shader text is the
+ * ship's).  dz = d0, on P, m = 0; then for i = 0 .. max_iter-1, Z the sample's current orbit and N its last index:
+ *   t = (Z_m + Z_m) + dz;  dz' = (t.x dz.x - t.y dz.y, t.x dz.y + t.y dz.x);  m += 1;  z = Z_m + dz';  r2 = |z|^2
+ *   r2 > bailout^2: escaped at i;  else if r2 < |dz'|^2 or m == N: dz = z, m = 0, the orbit becomes Q (rebase);  else dz = dz'
+ * each operation one fp64 rounding as written (no contraction), and no dc term.
+ *
+ * Extended deltas (fr_render_deepx_julia): fr_render_deepx's arithmetic, orbit storage (both orbits) and -400 mode rule,
+ * operation for operation, with these differences.  The first delta is dz = norm(d0's mantissas, ze) -- fr_render_deepx_ship's
+ * dc -- and the mode rule applies to it at once: a sample with dz.e > -400 starts PLAIN with (ldexp(dz.x, dz.e),
+ * ldexp(dz.y, dz.e)).  There is no (+) dc: n = p.  Rebasing follows the two-orbit rule.  FLUSH: without a dc term a delta in a
+ * superattracting basin (c = -1, c = 0, ...) squares itself towards nothing, and its int32 exponent would run away; so after
+ * every norm of dz a result with e < -2^27 becomes the zero (0, 0, FR_DEEPX_ZERO_EXP), and every exponent sum of a step stays
+ * above -2^29.  Such a delta is below 2^(-2^27) of the orbit it follows and cannot change any z.  On operands that a double
+ * holds the extended step does the plain step's roundings, so a view whose d0 is at least 2^-400 gets the bytes of
+ * fr_render_deep_julia.
+ *
+ * Planes: those of fr_render's fp64 Julia path for the same (i, r2): nu (double) = i + 1 - log2(log2(r2) / log2(bailout)) of
+ * sample s = 0 (the as-written library-log form at bailout <= 1; max_iterations for interior), iter = its i,
+ * t = color_offset + nu / max_iter * color_scale, interior black, the aa average in the shader's order, FR_FLAG_POST_CHAIN
+ * with the Julia floors.  Julia has no trap, stripe or interior styles: those fields are ignored, as fr_render ignores them.
+ *
+ * Validation (fr_deep_julia_validate, fr_deepx_julia_validate: no device needed): FR_ERR_UNSUPPORTED if p->fractal_type is not
+ * FR_FRACTAL_JULIA, p->precision not FR_PRECISION_F64, or with any of the four BLA flags; FR_ERR_INVALID_ARG for c not finite
+ * or a component of |c| >= 2^32, bailout > 2^16, the centre rule above, and otherwise as fr_render_deep_ship /
+ * fr_render_deepx_ship.  The other deep entry points keep rejecting FR_FRACTAL_JULIA.
+ *
+ * Argument shape, shards, FR_LAYOUT_FRAME, memory kinds, options, fr_ctx_last_kernel_ms / _grid and the asynchronous rules are
+ * fr_render_deep_ship's and fr_render_deepx_ship's; a render of a new view computes its orbits on the host first and is
+ * never launch-only.  The context keeps the most recent pair of orbits of each of the two paths in slots of their own, keyed
+ * by (centre strings, F, max_iterations, bailout, the bits of c): none of the six deep paths evicts another's orbit.
+ *
+ * Measured on one MI355X at 4096^2 (profiles/deep_julia_time.txt, the cases interleaved in one session, device time): RABBIT30
+ * (1e-30, max_iter 1100) 17.58 ms and DENDRITE100 (1e-100, 1200) 12.31 ms through fr_render_deep_julia, 946 and 970 G
+ * lane-updates/s, next to fr_render_deep's 16.54 ms (830 G/s) on its 1e-100 view; the dendrite at 1e-400 (3000) 95.6 ms through
+ * fr_render_deepx_julia, 496 G/s, next to fr_render_deepx's 111.9 ms (487 G/s) on its 1e-400 view.
+ *
+ * Out of scope: BLA for Julia (one table per orbit, with B = 0); zoom sequences; fr_node and .franim; c as a decimal string. */
+#define FR_HAS_DEEP_JULIA 1
+#define FR_HAS_DEEPX_JULIA 1
+
+/* Both orbits as doubles, on the host: out_p_xy and out_q_xy receive 2 (max_iter + 1) doubles each at most;
+ * *out_p_len = N_P + 1, *out_q_len = N_Q + 1.  Validation and cost as two fr_deep_reference_orbit calls. */
+int fr_deep_julia_reference_orbits(const fr_deep_view* v, double c_re, double c_im, double zoom, int32_t max_iter, float bailout,
+                                   double* out_p_xy, int32_t* out_p_len, double* out_q_xy, int32_t* out_q_len);
+
+/* Both orbits in the extended storage of fr_deepx_reference_orbit */
+int fr_deepx_julia_reference_orbits(const fr_deepx_view* v, double c_re, double c_im, int32_t max_iter, float bailout,
+                                    double* out_p_mant_xy, int32_t* out_p_exp2, int32_t* out_p_len, double* out_q_mant_xy,
+                                    int32_t* out_q_exp2, int32_t* out_q_len);
+
+int fr_deep_julia_validate(const fr_params* p, const fr_deep_view* view, uint32_t width, uint32_t height);
+int fr_deepx_julia_validate(const fr_params* p, const fr_deepx_view* view, uint32_t width, uint32_t height);
+
+int fr_render_deep_julia(fr_ctx* ctx, const fr_params* p, const fr_deep_view* view, uint32_t width, uint32_t height,
+                         const fr_shard* shard, const fr_output* out);
+int fr_render_deep_julia_async(fr_ctx* ctx, const fr_params* p, const fr_deep_view* view, uint32_t width, uint32_t height,
+                               const fr_shard* shard, const fr_output* out, void* hip_stream);
+int fr_render_deepx_julia(fr_ctx* ctx, const fr_params* p, const fr_deepx_view* view, uint32_t width, uint32_t height,
+                          const fr_shard* shard, const fr_output* out);
+int fr_render_deepx_julia_async(fr_ctx* ctx, const fr_params* p, const fr_deepx_view* view, uint32_t width, uint32_t height,
+                                const fr_shard* shard, const fr_output* out, void* hip_stream);
+
 /* ---- frames over the GPUs of a node (BASELINE.json north_star: "tiled across the 8 GPUs of one node as disjoint row
  * bands with a final RCCL gather over xGMI") -----------------------------------------------------------------------------
  * New design, no reference counterpart: the reference renders on the one GPU it picked (src/vk_engine.cpp:608).  What it

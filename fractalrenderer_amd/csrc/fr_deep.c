@@ -485,6 +485,15 @@ static int parse_centre(const fr_deep_view* v, fx_fmt fmt, uint64_t* cr, uint64_
     return FR_OK;
 }
 
+/* the Julia tables belong to fr_render_deep_julia / fr_render_deepx_julia: every other deep entry point refuses their flags */
+static int check_no_julia_bla(const char* who, const fr_params* p)
+{
+    if (p->flags & (FR_FLAG_DEEP_JULIA_BLA | FR_FLAG_DEEPX_JULIA_BLA))
+        return fr_set_error(FR_ERR_UNSUPPORTED, "%s: FR_FLAG_DEEP_JULIA_BLA / FR_FLAG_DEEPX_JULIA_BLA are not available (their "
+                            "tables belong to the Julia paths)", who);
+    return FR_OK;
+}
+
 int fr_deep_validate(const fr_params* p, const fr_deep_view* v, uint32_t width, uint32_t height)
 {
     if (!p || !v) return fr_set_error(FR_ERR_INVALID_ARG, "params/deep view is NULL");
@@ -500,6 +509,7 @@ int fr_deep_validate(const fr_params* p, const fr_deep_view* v, uint32_t width, 
     if (p->orbit_trap_enabled || p->stripe_enabled || p->interior_style == 2)
         return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deep: the orbit trap, stripes and interior_style 2 need the whole "
                             "orbit and are not available");
+    if ((st = check_no_julia_bla("fr_render_deep", p)) != FR_OK) return st;
     const int F = view_frac_bits(v, p->zoom);
     if (F < 0) return F;
     uint64_t cr[kMaxLimbs], ci[kMaxLimbs];
@@ -571,6 +581,7 @@ int fr_deep_ship_validate(const fr_params* p, const fr_deep_view* v, uint32_t wi
     if (p->flags & (FR_FLAG_DEEP_BLA | FR_FLAG_DEEPX_BLA))
         return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deep_ship: FR_FLAG_DEEP_BLA / FR_FLAG_DEEPX_BLA are not available (their "
                             "tables are Mandelbrot's): the flag of the ship is FR_FLAG_DEEP_SHIP_BLA");
+    if ((st = check_no_julia_bla("fr_render_deep_ship", p)) != FR_OK) return st;
     const int F = view_frac_bits(v, p->zoom);
     if (F < 0) return F;
     uint64_t cr[kMaxLimbs], ci[kMaxLimbs];
@@ -682,7 +693,7 @@ int fr_deepx_validate_params(const fr_params* p, uint32_t width, uint32_t height
     if (p->flags & FR_FLAG_DEEP_BLA)
         return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deepx: FR_FLAG_DEEP_BLA is not available (its table is fp64): the flag of "
                             "extended views is FR_FLAG_DEEPX_BLA");
-    return FR_OK;
+    return check_no_julia_bla("fr_render_deepx", p);
 }
 
 int fr_deepx_check_centre(const char* center_x, const char* center_y, int32_t frac_bits)
@@ -755,7 +766,7 @@ int fr_deepx_ship_validate_params(const fr_params* p, uint32_t width, uint32_t h
         return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deepx_ship: FR_FLAG_DEEP_BLA / FR_FLAG_DEEPX_BLA / FR_FLAG_DEEP_SHIP_BLA "
                             "are not available (their tables belong to the other deep paths): the flag of extended Burning "
                             "Ship views is FR_FLAG_DEEPX_SHIP_BLA");
-    return FR_OK;
+    return check_no_julia_bla("fr_render_deepx_ship", p);
 }
 
 int fr_deepx_ship_validate(const fr_params* p, const fr_deepx_view* v, uint32_t width, uint32_t height)
@@ -887,6 +898,10 @@ static int julia_validate_params(const char* who, const fr_params* p, uint32_t w
     if (p->flags & (FR_FLAG_DEEP_BLA | FR_FLAG_DEEPX_BLA | FR_FLAG_DEEP_SHIP_BLA | FR_FLAG_DEEPX_SHIP_BLA))
         return fr_set_error(FR_ERR_UNSUPPORTED, "%s: the BLA flags are not available (their tables belong to the Mandelbrot and "
                             "Burning Ship paths)", who);
+    if (p->flags & (zoomed ? FR_FLAG_DEEPX_JULIA_BLA : FR_FLAG_DEEP_JULIA_BLA))
+        return fr_set_error(FR_ERR_UNSUPPORTED, "%s: %s is not available (its table is %s): the flag of this entry point is %s", who,
+                            zoomed ? "FR_FLAG_DEEPX_JULIA_BLA" : "FR_FLAG_DEEP_JULIA_BLA", zoomed ? "extended" : "fp64",
+                            zoomed ? "FR_FLAG_DEEP_JULIA_BLA" : "FR_FLAG_DEEPX_JULIA_BLA");
     return FR_OK;
 }
 

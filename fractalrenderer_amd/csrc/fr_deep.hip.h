@@ -18,10 +18,12 @@
  *     the table build the single step, the merge products, the two norms and the load and store of an entry.  The ship's
  *     step is the Mandelbrot step on U = (|Z_m.x|, |Z_m.y|) and f = (fold(Z_m.x, dz.x), fold(Z_m.y, dz.y)), the fold a pair
  *     of compares and selects; its BLA step is a real 2x2 map where Mandelbrot's is a complex product.
- *   - a third policy, JuliaFormula, without BLA: Mandelbrot's linear part, the ship's viewport map, no dc term (the sample's
- *     offset is its first delta) and kTwoOrbits -- a lane starts on the orbit P of the view's centre, stored behind the
- *     critical orbit Q in the same buffers, and its first rebase moves it onto Q (Q_0 = 0 keeps the rebase exact) for good.  A
- *     lane carries its orbit's base and N; the extended loop flushes a delta whose exponent runs below -2^27 to zero.
+ *   - a third policy, JuliaFormula: Mandelbrot's linear part, the ship's viewport map, no dc term (the sample's offset is its
+ *     first delta) and kTwoOrbits -- a lane starts on the orbit P of the view's centre, stored behind the critical orbit Q in
+ *     the same buffers, and its first rebase moves it onto Q (Q_0 = 0 keeps the rebase exact) for good.  A lane carries its
+ *     orbit's base and N; the extended loops flush a delta whose exponent runs below -2^27 to zero.  Its BLA is Mandelbrot's
+ *     with kHasB = false: no dc, so an entry is (r, A) and a step one complex product; there is one table per orbit, Q's
+ *     first in the same buffers, and a BLA lane also carries its table's entry base, n1 and K.
  *   - four per-sample loops, each templated on the formula: deep_orbit (fp64 deltas), deep_orbit_bla (those with BLA),
  *     deep_orbit_x (extended-exponent deltas, fr_render_deepx*), deep_orbit_x_bla (those with BLA).  The BLA loops count the
  *     updates u a sample has covered, the others the loop index.  In all of them dz, dc, m and the count stay in registers;
@@ -39,12 +41,12 @@
  *     which cannot pass gather nothing.  A probe gathers 8 bytes; the chosen level's (A, B) are loaded inside the
  *     taken-step branch only.
  *   - two table builds, bla_level (fp64) and bla_level_x (extended), one launch per level: entry j of level k merges entries
- *     2j and 2j + 1 of level k - 1, level 0 being the single steps, computed from the orbit and never stored.  The four
- *     __global__ level kernels are these two with a formula.  The table stores, level after level (level k from entry
+ *     2j and 2j + 1 of level k - 1, level 0 being the single steps, computed from the orbit and never stored.  The six
+ *     __global__ level kernels are these two with a formula (Julia's: one orbit and its part of the buffers per launch).  The table stores, level after level (level k from entry
  *     offset bla_offset(N - 1, k)), the radius r of every entry in an array of its own -- a double, or an XRad -- and
- *     (A, B) as F::kAbPerEntry double2 per entry (2: complex A, B; 4: the rows of the ship's real matrices), the extended
- *     tables with their two exponents in an int2.
- *   - deep_kernel<ARGS>, one kernel body for the ten argument blocks: a persistent grid of the resident set pulls runs of
+ *     (A, B) as F::kAbPerEntry double2 per entry (2: complex A, B; 4: the rows of the ship's real matrices; 1: Julia's A), the
+ *     extended tables with their two exponents in an int2 (Julia: A's in an int32).
+ *   - deep_kernel<ARGS>, one kernel body for the twelve argument blocks: a persistent grid of the resident set pulls runs of
  *     8x8 sub-tiles from the sharded WaveQueue with unlimited stealing (deep views have very uneven iteration counts); one
  *     lane per sample, the aa x aa samples of a pixel one after the other in the lane; dc through the formula's viewport
  *     map, one dispatch on (extended, BLA) to the loop, then the colour stage of the formula's fp64 path: shade() and
@@ -163,6 +165,25 @@ struct DeepJuliaXArgs {
     JuliaStart j;
 };
 
+/* A Julia view's tables (FR_FLAG_DEEP_JULIA_BLA, FR_FLAG_DEEPX_JULIA_BLA): q is the table of Q = d.orbit; P's entries start
+ * base_p entries behind Q's in the same arrays */
+template <class TAB>
+struct JuliaTab {
+    TAB q;
+    int32_t levels_p;                    /* K of P's table, 0 = none */
+    uint32_t base_p;                     /* the entries of Q's table */
+};
+
+struct DeepJuliaBlaArgs {
+    DeepJuliaArgs j;
+    JuliaTab<BlaTable> t;
+};
+
+struct DeepJuliaXBlaArgs {
+    DeepJuliaXArgs j;
+    JuliaTab<BlaXTable> t;
+};
+
 constexpr int kXZero = FR_DEEPX_ZERO_EXP;
 constexpr int kXThr = -400;              /* extended while the normalised dz.e <= kXThr */
 constexpr int kXBlaExpLim = 1 << 27;     /* an entry whose A.e or B.e leaves [-2^27, 2^27] is void */
@@ -268,6 +289,7 @@ struct MandelFormula {
     static constexpr int kFractal = 0;                /* the colour stage: shade() / colour_of() */
     static constexpr bool kLogBailoutLds = false;
     static constexpr bool kTwoOrbits = false;         /* one orbit from 0, a dc term in every step */
+    static constexpr bool kHasB = true;
     static constexpr int kAbPerEntry = 2;             /* complex A, B */
     using Lin = BlaLin<1>;
     using LinX = BlaLinX<1>;
@@ -352,6 +374,7 @@ struct ShipFormula {
     static constexpr int kFractal = 2;
     static constexpr bool kLogBailoutLds = true;      /* shade<double, 2> at bailout <= 1 */
     static constexpr bool kTwoOrbits = false;
+    static constexpr bool kHasB = true;
     static constexpr int kAbPerEntry = 4;             /* the rows (a11, a12), (a21, a22), (b11, b12), (b21, b22) */
     using Lin = BlaLin<2>;
     using LinX = BlaLinX<2>;
@@ -473,11 +496,15 @@ struct ShipFormula {
 
 /* z <- z^2 + c with c fixed and the sample's offset in z_0 (Julia): Mandelbrot's linear part, the ship's viewport map (the
  * two shaders share it), no dc term, and two orbits -- a sample starts with dz = its offset on the orbit of the centre and
- * rebases onto the critical orbit.  No BLA. */
+ * rebases onto the critical orbit.  BLA: Mandelbrot's single step and merge without B, dz' = A dz. */
 struct JuliaFormula {
     static constexpr int kFractal = 1;
     static constexpr bool kLogBailoutLds = true;      /* shade<double, 1> at bailout <= 1 */
     static constexpr bool kTwoOrbits = true;
+    static constexpr bool kHasB = false;              /* no dc term: an entry is (r, A) */
+    static constexpr int kAbPerEntry = 1;             /* complex A */
+    using Lin = BlaLin<1>;                            /* b stays unused */
+    using LinX = BlaLinX<1>;
 
     static __device__ __forceinline__ StepLin lin(const double Zx, const double Zy, const double dzx, const double dzy)
     {
@@ -494,6 +521,28 @@ struct JuliaFormula {
     {
         return ShipFormula::dc(px, py, s, aa, resx, resy, zs);
     }
+    /* dz' = A dz, a complex product */
+    static __device__ __forceinline__ double2 bla(const BlaTable& T, const uint32_t e, const double dzx,
+                                                  const double dzy, const double, const double)
+    {
+        const double2 a = T.ab[e];
+        return make_double2(a.x * dzx - a.y * dzy, a.x * dzy + a.y * dzx);
+    }
+    static __device__ __forceinline__ BlaStepX bla_x(const BlaXTable& T, const uint32_t e, const double qx, const double qy,
+                                                     const double, const double)
+    {
+        const double2 a = T.ab[e];
+        return {a.x * qx - a.y * qy, a.x * qy + a.y * qx, 0.0, 0.0, reinterpret_cast<const int32_t*>(T.abe)[e], 0};
+    }
+
+    /* the table build: Mandelbrot's, B never read */
+    static __device__ __forceinline__ Lin single(const double2 Z) { return MandelFormula::single(Z); }
+    static __device__ __forceinline__ LinX single_x(const double2 Z, const int eZ) { return MandelFormula::single_x(Z, eZ); }
+    template <class L>
+    static __device__ __forceinline__ void mul_a(const L& y, const L& x, double2* a) { MandelFormula::mul_a(y, x, a); }
+    template <class L>
+    static __device__ __forceinline__ double norm_a(const L& x) { return MandelFormula::norm_a(x); }
+    static __device__ __forceinline__ void norm_rows(double2* m, int& e) { MandelFormula::norm_rows(m, e); }
 };
 
 /* ---- the steps ---------------------------------------------------------------------------------------------------------
@@ -541,12 +590,14 @@ __device__ __forceinline__ uint32_t bla_offset(const uint32_t n1, const int k)
 
 /* Level k of an fp64 table: entry j merges x (level k - 1, entry 2j) and y (level k - 1, entry 2j + 1); level 0 is the single
  * step at m = 1 + i, computed from the orbit and never stored.  A = A_y A_x, B = A_y B_x + B_y,
- * r = min(r_x, max(0, (r_y - |B_x| dcmax) / |A_x|)), 0 when an element is not finite. */
+ * r = min(r_x, max(0, (r_y - |B_x| dcmax) / |A_x|)), 0 when an element is not finite.  A formula without B (Julia) has
+ * neither B nor dcmax: r = min(r_x, max(0, r_y / |A_x|)). */
 template <class F>
 __device__ __forceinline__ void bla_level(const double2* __restrict__ orbit, const int32_t n_ref, const int32_t k,
                                           const double dcmax, double* __restrict__ r, double2* __restrict__ ab)
 {
-    constexpr int R = F::kAbPerEntry / 2;
+    constexpr int S = F::kAbPerEntry;                            /* double2 per entry: A's rows, then B's */
+    constexpr int R = F::kHasB ? S / 2 : S;
     const uint32_t n1 = (uint32_t)(n_ref - 1);
     const uint32_t cnt = n1 >> k;
     const uint32_t off = bla_offset(n1, k);
@@ -558,38 +609,56 @@ __device__ __forceinline__ void bla_level(const double2* __restrict__ orbit, con
             y = F::single(orbit[2 + 2 * j]);
         } else {
             const uint32_t ex = offp + 2 * j, ey = ex + 1;
-            for (int i = 0; i < R; ++i) { x.a[i] = ab[2 * R * ex + i]; x.b[i] = ab[2 * R * ex + R + i]; }
+            for (int i = 0; i < R; ++i) {
+                x.a[i] = ab[S * ex + i];
+                if constexpr (F::kHasB) x.b[i] = ab[S * ex + R + i];
+            }
             x.r = r[ex];
-            for (int i = 0; i < R; ++i) { y.a[i] = ab[2 * R * ey + i]; y.b[i] = ab[2 * R * ey + R + i]; }
+            for (int i = 0; i < R; ++i) {
+                y.a[i] = ab[S * ey + i];
+                if constexpr (F::kHasB) y.b[i] = ab[S * ey + R + i];
+            }
             y.r = r[ey];
         }
         double2 a[R], b[R];
         F::mul_a(y, x, a);
-        F::mul_b(y, x, b);
+        if constexpr (F::kHasB) F::mul_b(y, x, b);
         bool finite = true;
         for (int i = 0; i < R; ++i) {
-            b[i] = make_double2(b[i].x + y.b[i].x, b[i].y + y.b[i].y);
-            finite = finite && __builtin_isfinite(a[i].x) && __builtin_isfinite(a[i].y) && __builtin_isfinite(b[i].x) &&
-                     __builtin_isfinite(b[i].y);
+            if constexpr (F::kHasB) {
+                b[i] = make_double2(b[i].x + y.b[i].x, b[i].y + y.b[i].y);
+                finite = finite && __builtin_isfinite(a[i].x) && __builtin_isfinite(a[i].y) && __builtin_isfinite(b[i].x) &&
+                         __builtin_isfinite(b[i].y);
+            } else {
+                finite = finite && __builtin_isfinite(a[i].x) && __builtin_isfinite(a[i].y);
+            }
         }
-        const double t = (y.r - F::norm_b(x) * dcmax) / F::norm_a(x);
+        double t;
+        if constexpr (F::kHasB) t = (y.r - F::norm_b(x) * dcmax) / F::norm_a(x);
+        else t = y.r / F::norm_a(x);
         double rr = t > 0.0 ? t : 0.0;                           /* NaN: 0 */
         rr = rr < x.r ? rr : x.r;
         if (!finite) rr = 0.0;
         const uint32_t e = off + j;
         r[e] = rr;
-        for (int i = 0; i < R; ++i) { ab[2 * R * e + i] = a[i]; ab[2 * R * e + R + i] = b[i]; }
+        for (int i = 0; i < R; ++i) {
+            ab[S * e + i] = a[i];
+            if constexpr (F::kHasB) ab[S * e + R + i] = b[i];
+        }
     }
 }
 
 /* Level k of an extended table: bla_level with (A, B, r) carrying int32 exponents, from the extended orbit arrays.  An entry
- * whose A.e or B.e leaves [-2^27, 2^27] is void (all zero); the stored radius is cut to 24 bits. */
+ * whose A.e or B.e leaves [-2^27, 2^27] is void (all zero); the stored radius is cut to 24 bits.  A formula without B (Julia)
+ * stores A.e alone, an int32 per entry in abe, and has t = r_y (/) |A_x|. */
 template <class F>
 __device__ __forceinline__ void bla_level_x(const double2* __restrict__ mant, const int32_t* __restrict__ exp2,
                                             const int32_t n_ref, const int32_t k, const double dcv, const int32_t dce,
                                             XRad* __restrict__ r, double2* __restrict__ ab, int2* __restrict__ abe)
 {
-    constexpr int R = F::kAbPerEntry / 2;
+    constexpr int S = F::kAbPerEntry;                            /* double2 per entry: A's rows, then B's */
+    constexpr int R = F::kHasB ? S / 2 : S;
+    int32_t* __restrict__ const ae1 = reinterpret_cast<int32_t*>(abe);   /* without B: A.e of every entry */
     const uint32_t n1 = (uint32_t)(n_ref - 1);
     const uint32_t cnt = n1 >> k;
     const uint32_t off = bla_offset(n1, k);
@@ -601,32 +670,49 @@ __device__ __forceinline__ void bla_level_x(const double2* __restrict__ mant, co
             y = F::single_x(mant[2 + 2 * j], exp2[2 + 2 * j]);
         } else {
             const uint32_t ex = offp + 2 * j, ey = ex + 1;
-            const int2 eex = abe[ex], eey = abe[ey];
             const XRad rx = r[ex], ry = r[ey];
-            for (int i = 0; i < R; ++i) { x.a[i] = ab[2 * R * ex + i]; x.b[i] = ab[2 * R * ex + R + i]; }
-            x.ea = eex.x; x.eb = eex.y; x.rv = (double)rx.v; x.re = rx.e;
-            for (int i = 0; i < R; ++i) { y.a[i] = ab[2 * R * ey + i]; y.b[i] = ab[2 * R * ey + R + i]; }
-            y.ea = eey.x; y.eb = eey.y; y.rv = (double)ry.v; y.re = ry.e;
+            if constexpr (F::kHasB) {
+                const int2 eex = abe[ex], eey = abe[ey];
+                for (int i = 0; i < R; ++i) { x.a[i] = ab[S * ex + i]; x.b[i] = ab[S * ex + R + i]; }
+                x.ea = eex.x; x.eb = eex.y;
+                for (int i = 0; i < R; ++i) { y.a[i] = ab[S * ey + i]; y.b[i] = ab[S * ey + R + i]; }
+                y.ea = eey.x; y.eb = eey.y;
+            } else {
+                for (int i = 0; i < R; ++i) { x.a[i] = ab[S * ex + i]; y.a[i] = ab[S * ey + i]; }
+                x.ea = ae1[ex]; y.ea = ae1[ey];
+            }
+            x.rv = (double)rx.v; x.re = rx.e;
+            y.rv = (double)ry.v; y.re = ry.e;
         }
         double2 a[R], p[R], b[R];
         F::mul_a(y, x, a);
         int ea = y.ea + x.ea;
         F::norm_rows(a, ea);
-        F::mul_b(y, x, p);
-        const int e1 = y.ea + x.eb;
-        int eb = e1 > y.eb ? e1 : y.eb;
-        for (int i = 0; i < R; ++i)
-            b[i] = make_double2(__builtin_ldexp(p[i].x, e1 - eb) + __builtin_ldexp(y.b[i].x, y.eb - eb),
-                                __builtin_ldexp(p[i].y, e1 - eb) + __builtin_ldexp(y.b[i].y, y.eb - eb));
-        F::norm_rows(b, eb);
-        double bv = F::norm_b(x), av = F::norm_a(x);
-        int be = x.eb, ae = x.ea;
-        x_norm1(bv, be);
+        int eb = 0;
+        double av = F::norm_a(x);
+        int ae = x.ea;
         x_norm1(av, ae);
-        const double pv = bv * dcv;
-        const int pe = be + dce;
-        const int et = y.re > pe ? y.re : pe;
-        const double t = (__builtin_ldexp(y.rv, y.re - et) - __builtin_ldexp(pv, pe - et)) / av;
+        double t;
+        int et;
+        if constexpr (F::kHasB) {
+            F::mul_b(y, x, p);
+            const int e1 = y.ea + x.eb;
+            eb = e1 > y.eb ? e1 : y.eb;
+            for (int i = 0; i < R; ++i)
+                b[i] = make_double2(__builtin_ldexp(p[i].x, e1 - eb) + __builtin_ldexp(y.b[i].x, y.eb - eb),
+                                    __builtin_ldexp(p[i].y, e1 - eb) + __builtin_ldexp(y.b[i].y, y.eb - eb));
+            F::norm_rows(b, eb);
+            double bv = F::norm_b(x);
+            int be = x.eb;
+            x_norm1(bv, be);
+            const double pv = bv * dcv;
+            const int pe = be + dce;
+            et = y.re > pe ? y.re : pe;
+            t = (__builtin_ldexp(y.rv, y.re - et) - __builtin_ldexp(pv, pe - et)) / av;
+        } else {
+            et = y.re;
+            t = y.rv / av;
+        }
         double rv = (t > 0.0 && __builtin_isfinite(t)) ? t : 0.0;    /* NaN: 0 */
         int re = et - ae;
         x_norm1(rv, re);
@@ -641,8 +727,13 @@ __device__ __forceinline__ void bla_level_x(const double2* __restrict__ mant, co
         XRad out;
         out.v = (float)x_trunc24(rv); out.e = re;
         r[e] = out;
-        for (int i = 0; i < R; ++i) { ab[2 * R * e + i] = a[i]; ab[2 * R * e + R + i] = b[i]; }
-        abe[e] = make_int2(ea, eb);
+        if constexpr (F::kHasB) {
+            for (int i = 0; i < R; ++i) { ab[S * e + i] = a[i]; ab[S * e + R + i] = b[i]; }
+            abe[e] = make_int2(ea, eb);
+        } else {
+            for (int i = 0; i < R; ++i) ab[S * e + i] = a[i];
+            ae1[e] = ea;
+        }
     }
 }
 
@@ -674,6 +765,22 @@ deepx_ship_bla_level_kernel(const double2* __restrict__ mant, const int32_t* __r
                             double2* __restrict__ ab, int2* __restrict__ abe)
 {
     bla_level_x<ShipFormula>(mant, exp2, n_ref, k, dcv, dce, r, ab, abe);
+}
+
+/* Julia: one launch per level and orbit.  orbit / mant / exp2 point at the orbit's point 0 (Q's, or P's behind it), r / ab / ae
+ * at the first entry of that orbit's table */
+__global__ void __launch_bounds__(kBlockThreads)
+deep_julia_bla_level_kernel(const double2* __restrict__ orbit, const int32_t n_ref, const int32_t k, double* __restrict__ r,
+                            double2* __restrict__ ab)
+{
+    bla_level<JuliaFormula>(orbit, n_ref, k, 0.0, r, ab);
+}
+
+__global__ void __launch_bounds__(kBlockThreads)
+deepx_julia_bla_level_kernel(const double2* __restrict__ mant, const int32_t* __restrict__ exp2, const int32_t n_ref,
+                             const int32_t k, XRad* __restrict__ r, double2* __restrict__ ab, int32_t* __restrict__ ae)
+{
+    bla_level_x<JuliaFormula>(mant, exp2, n_ref, k, 0.0, 0, r, ab, reinterpret_cast<int2*>(ae));
 }
 
 /* ---- the level probes --------------------------------------------------------------------------------------------------
@@ -797,20 +904,30 @@ __device__ __forceinline__ void deep_orbit(const DeepArgs& A, const JuliaStart J
 
 /* deep_orbit with BLA: u replaces the loop index.  A lane probes the table (bla_probe) and takes the level it finds, else
  * the plain step.  A BLA lane loads Z_m and Z_{m+1} at its new m (the Z_{m+2} prefetch is for the plain step); BLA and plain
- * lanes of a wave take their steps in the same trip.  nplain / nbla: the steps this sample took. */
+ * lanes of a wave take their steps in the same trip.  nplain / nbla: the steps this sample took.  Two orbits (J, levels_p and
+ * base_p of P's table): the lane's orbit base, N, and its table's entry base, n1 and K are P's until the first rebase. */
 template <class F>
-__device__ __forceinline__ void deep_orbit_bla(const DeepArgs& A, const BlaTable& T, const double dcx, const double dcy,
-                                               const double2 z1, bool live, int& esc, double& er2, uint32_t& nplain,
-                                               uint32_t& nbla)
+__device__ __forceinline__ void deep_orbit_bla(const DeepArgs& A, const BlaTable& T, const JuliaStart J, const int levels_p,
+                                               const uint32_t base_p, const double dcx, const double dcy, const double2 z1,
+                                               bool live, int& esc, double& er2, uint32_t& nplain, uint32_t& nbla)
 {
     const double2* __restrict__ orbit = A.orbit;
     const double* __restrict__ tr = T.r;
-    const int N = A.n_ref, max_iter = A.max_iter, K = T.levels;
-    const uint32_t n1 = (uint32_t)(N - 1);
+    const int max_iter = A.max_iter;
+    int N = A.n_ref, K = T.levels;
+    uint32_t n1 = (uint32_t)(N - 1);
+    int base = 0;                                                /* where the lane's orbit starts in `orbit` */
+    uint32_t tb = 0u;                                            /* ... and its table in tr / T.ab */
     const double B2 = A.B2;
     double dzx = 0.0, dzy = 0.0;
     double Zx = 0.0, Zy = 0.0;                                   /* Z_m */
     double Znx = z1.x, Zny = z1.y;                               /* Z_{m+1} */
+    if constexpr (F::kTwoOrbits) {                               /* dz = the sample's offset, on P: one point for all lanes */
+        base = J.p_off; N = J.n_p; K = levels_p; n1 = (uint32_t)(N - 1); tb = base_p;
+        const double2 p0 = orbit[base], p1 = orbit[base + 1];
+        dzx = dcx; dzy = dcy;
+        Zx = p0.x; Zy = p0.y; Znx = p1.x; Zny = p1.y;
+    }
     int m = 0, u = 0;
     esc = max_iter;
     er2 = 0.0;
@@ -818,19 +935,19 @@ __device__ __forceinline__ void deep_orbit_bla(const DeepArgs& A, const BlaTable
     for (;;) {
         if (__builtin_amdgcn_ballot_w64(live) == 0ull) break;
         if (!live) continue;
-        const double2 Znn = orbit[m + 2 <= N ? m + 2 : N];      /* Z_{m+2}, for a plain step */
+        const double2 Znn = orbit[base + (m + 2 <= N ? m + 2 : N)];   /* Z_{m+2}, for a plain step */
         const double dz2 = dzx * dzx + dzy * dzy;
-        const BlaHit h = bla_probe(tr, n1, K, N, max_iter, m, u, dz2, Zx, Zy);
+        const BlaHit h = bla_probe(tr + tb, n1, K, N, max_iter, m, u, dz2, Zx, Zy);
         const int k = h.k;
         double2 n;
         double Zmx, Zmy;
         int step;
         if (k > 0) {
-            n = F::bla(T, h.e, dzx, dzy, dcx, dcy);
+            n = F::bla(T, tb + h.e, dzx, dzy, dcx, dcy);
             step = 1 << k;
             ++nbla;
             m += step;
-            const double2 Zm = orbit[m];
+            const double2 Zm = orbit[base + m];
             Zmx = Zm.x; Zmy = Zm.y;
         } else {
             n = deep_step<F>(Zx, Zy, dzx, dzy, dcx, dcy);
@@ -848,11 +965,14 @@ __device__ __forceinline__ void deep_orbit_bla(const DeepArgs& A, const BlaTable
         } else if (r2 < nx * nx + ny * ny || m == N) {           /* rebase */
             dzx = zx; dzy = zy; m = 0;
             Zx = 0.0; Zy = 0.0; Znx = z1.x; Zny = z1.y;
+            if constexpr (F::kTwoOrbits) {                        /* onto Q and its table, for good */
+                base = 0; N = A.n_ref; K = T.levels; n1 = (uint32_t)(N - 1); tb = 0u;
+            }
         } else {
             dzx = nx; dzy = ny;
             Zx = Zmx; Zy = Zmy;
             if (k > 0) {                                          /* m < N here */
-                const double2 Zn = orbit[m + 1];
+                const double2 Zn = orbit[base + m + 1];
                 Znx = Zn.x; Zny = Zn.y;
             } else {
                 Znx = Znn.x; Zny = Znn.y;
@@ -988,19 +1108,23 @@ __device__ __forceinline__ void deep_orbit_x(const DeepXArgs& AA, const JuliaSta
 /* deep_orbit_x with BLA: u replaces the loop index.  A lane, in either mode, probes the table (bla_probe_x); a BLA step is
  * taken in extended arithmetic whatever the lane's mode, its loads inside the taken branch, and the lane reloads Z_m, Z_{m+1}
  * in the mode the step leaves it in.  The single steps are deep_orbit_x's, operation for operation.  BLA lanes and
- * single-step lanes of a wave take their steps in the same trip.  nsingle / nbla: the steps this sample took. */
+ * single-step lanes of a wave take their steps in the same trip.  nsingle / nbla: the steps this sample took.  Two orbits: as
+ * deep_orbit_bla, and a BLA step ends with the flush of deep_orbit_x. */
 template <class F>
-__device__ __forceinline__ void deep_orbit_x_bla(const DeepXArgs& AA, const BlaXTable& T, const double cx, const double cy,
-                                                 const int ec, bool live, int& esc, double& er2, uint32_t& nsingle,
-                                                 uint32_t& nbla)
+__device__ __forceinline__ void deep_orbit_x_bla(const DeepXArgs& AA, const BlaXTable& T, const JuliaStart J, const int levels_p,
+                                                 const uint32_t base_p, const double cx, const double cy, const int ec,
+                                                 bool live, int& esc, double& er2, uint32_t& nsingle, uint32_t& nbla)
 {
     const DeepArgs& A = AA.d;
     const double2* __restrict__ orbit = A.orbit;
     const double2* __restrict__ mant = AA.mant;
     const int32_t* __restrict__ exp2 = AA.exp2;
     const XRad* __restrict__ tr = T.r;
-    const int N = A.n_ref, max_iter = A.max_iter, K = T.levels;
-    const uint32_t n1 = (uint32_t)(N - 1);
+    const int max_iter = A.max_iter;
+    int N = A.n_ref, K = T.levels;
+    uint32_t n1 = (uint32_t)(N - 1);
+    int base = 0;                                                /* where the lane's orbit starts in the arrays */
+    uint32_t tb = 0u;                                            /* ... and its table in tr / T.ab / T.abe */
     const double B2 = A.B2;
     const double cpx = x_plain(cx, ec), cpy = x_plain(cy, ec);   /* the plain mode's dc */
     double dzx = 0.0, dzy = 0.0;                                 /* plain: dz; extended: its mantissas */
@@ -1012,6 +1136,19 @@ __device__ __forceinline__ void deep_orbit_x_bla(const DeepXArgs& AA, const BlaX
     const int e1 = exp2[1];
     double Znx = z1.x, Zny = z1.y;                               /* Z_{m+1} */
     int eZn = e1;
+    if constexpr (F::kTwoOrbits) {                               /* dz = the sample's offset (cx, cy, ec), on P, in its mode */
+        base = J.p_off; N = J.n_p; K = levels_p; n1 = (uint32_t)(N - 1); tb = base_p;
+        ext = ec <= kXThr;
+        if (ext) {
+            const double2 a = mant[base], b = mant[base + 1];
+            dzx = cx; dzy = cy; ed = ec;
+            Zx = a.x; Zy = a.y; eZ = exp2[base]; Znx = b.x; Zny = b.y; eZn = exp2[base + 1];
+        } else {
+            const double2 a = orbit[base], b = orbit[base + 1];
+            dzx = __builtin_ldexp(cx, ec); dzy = __builtin_ldexp(cy, ec);
+            Zx = a.x; Zy = a.y; Znx = b.x; Zny = b.y;
+        }
+    }
     int m = 0, u = 0;
     esc = max_iter;
     er2 = 0.0;
@@ -1019,8 +1156,8 @@ __device__ __forceinline__ void deep_orbit_x_bla(const DeepXArgs& AA, const BlaX
     for (;;) {
         if (__builtin_amdgcn_ballot_w64(live) == 0ull) break;
         if (!live) continue;
-        const int mn = m + 2 <= N ? m + 2 : N;                   /* Z_{m+2}, for the single step after this one */
-        const BlaHitX h = bla_probe_x(tr, n1, K, N, max_iter, m, u, ext, dzx, dzy, ed, Zx, Zy, eZ);
+        const int mn = base + (m + 2 <= N ? m + 2 : N);          /* Z_{m+2}, for the single step after this one */
+        const BlaHitX h = bla_probe_x(tr + tb, n1, K, N, max_iter, m, u, ext, dzx, dzy, ed, Zx, Zy, eZ);
         const int k = h.k;
         double ax, ay;                                           /* the next dz */
         int ea = 0;
@@ -1030,16 +1167,22 @@ __device__ __forceinline__ void deep_orbit_x_bla(const DeepXArgs& AA, const BlaX
             int en, eW, eZnn = 0;
             double2 Znn = make_double2(0.0, 0.0);
             if (k > 0) {
-                const BlaStepX s = F::bla_x(T, h.e, h.qx, h.qy, cx, cy);
-                const int ep = s.ea + h.qe, es = s.eb + ec;
-                en = ep > es ? ep : es;
-                nx = __builtin_ldexp(s.px, ep - en) + __builtin_ldexp(s.sx, es - en);
-                ny = __builtin_ldexp(s.py, ep - en) + __builtin_ldexp(s.sy, es - en);
+                const BlaStepX s = F::bla_x(T, tb + h.e, h.qx, h.qy, cx, cy);
+                const int ep = s.ea + h.qe;
+                if constexpr (F::kHasB) {
+                    const int es = s.eb + ec;
+                    en = ep > es ? ep : es;
+                    nx = __builtin_ldexp(s.px, ep - en) + __builtin_ldexp(s.sx, es - en);
+                    ny = __builtin_ldexp(s.py, ep - en) + __builtin_ldexp(s.sy, es - en);
+                } else {                                          /* n = A (x) dz */
+                    en = ep;
+                    nx = s.px; ny = s.py;
+                }
                 m += 1 << k;
                 u += 1 << k;
                 ++nbla;
-                const double2 Wm = mant[m];
-                Wx = Wm.x; Wy = Wm.y; eW = exp2[m];
+                const double2 Wm = mant[base + m];
+                Wx = Wm.x; Wy = Wm.y; eW = exp2[base + m];
             } else {
                 Znn = mant[mn];
                 eZnn = exp2[mn];
@@ -1063,6 +1206,12 @@ __device__ __forceinline__ void deep_orbit_x_bla(const DeepXArgs& AA, const BlaX
             ax = reb ? zx : nx; ay = reb ? zy : ny; ea = reb ? ez : en;
             x_norm(ax, ay, ea);
             if (reb) m = 0;
+            if constexpr (F::kTwoOrbits) {
+                if (ea < kXFlushExp) { ax = 0.0; ay = 0.0; ea = kXZero; }   /* FLUSH */
+                if (reb) {                                        /* onto Q and its table, for good */
+                    base = 0; N = A.n_ref; K = T.levels; n1 = (uint32_t)(N - 1); tb = 0u;
+                }
+            }
             if (ea <= kXThr) {                                    /* extended from here */
                 dzx = ax; dzy = ay; ed = ea;
                 ext = true;
@@ -1071,11 +1220,11 @@ __device__ __forceinline__ void deep_orbit_x_bla(const DeepXArgs& AA, const BlaX
                 } else if (k == 0) {
                     Zx = Znx; Zy = Zny; eZ = eZn; Znx = Znn.x; Zny = Znn.y; eZn = eZnn;
                 } else {                                          /* m < N here */
-                    const double2 b = mant[m + 1];
-                    Zx = Wx; Zy = Wy; eZ = eW; Znx = b.x; Zny = b.y; eZn = exp2[m + 1];
+                    const double2 b = mant[base + m + 1];
+                    Zx = Wx; Zy = Wy; eZ = eW; Znx = b.x; Zny = b.y; eZn = exp2[base + m + 1];
                 }
             } else {                                              /* plain from here (m < N) */
-                const double2 a = orbit[m], b = orbit[m + 1];
+                const double2 a = orbit[base + m], b = orbit[base + m + 1];
                 dzx = __builtin_ldexp(ax, ea); dzy = __builtin_ldexp(ay, ea);
                 ext = false;
                 Zx = a.x; Zy = a.y; Znx = b.x; Zny = b.y;
@@ -1096,6 +1245,9 @@ __device__ __forceinline__ void deep_orbit_x_bla(const DeepXArgs& AA, const BlaX
             reb = r2 < nx * nx + ny * ny || m == N;
             ax = reb ? zx : nx; ay = reb ? zy : ny;
             if (reb) m = 0;
+            if constexpr (F::kTwoOrbits) {
+                if (reb) { base = 0; N = A.n_ref; K = T.levels; n1 = (uint32_t)(N - 1); tb = 0u; }
+            }
             if (!(fmax(fabs(ax), fabs(ay)) < 0x1p-400)) {         /* stays plain */
                 dzx = ax; dzy = ay;
                 if (reb) {
@@ -1105,11 +1257,11 @@ __device__ __forceinline__ void deep_orbit_x_bla(const DeepXArgs& AA, const BlaX
                     Zx = Znx; Zy = Zny; Znx = Znn.x; Zny = Znn.y;
                 }
             } else {                                              /* turns extended (m < N) */
-                const double2 a = mant[m], b = mant[m + 1];
+                const double2 a = mant[base + m], b = mant[base + m + 1];
                 x_norm(ax, ay, ea);
                 dzx = ax; dzy = ay; ed = ea;
                 ext = true;
-                Zx = a.x; Zy = a.y; eZ = exp2[m]; Znx = b.x; Zny = b.y; eZn = exp2[m + 1];
+                Zx = a.x; Zy = a.y; eZ = exp2[base + m]; Znx = b.x; Zny = b.y; eZn = exp2[base + m + 1];
             }
         }
         if (u >= max_iter) live = false;                          /* esc stays max_iter */
@@ -1139,26 +1291,43 @@ __device__ __forceinline__ double ship_log_bailout(const DeepShipXArgs& A) { ret
 __device__ __forceinline__ double ship_log_bailout(const DeepShipXBlaArgs& A) { return A.s.log_bailout; }
 __device__ __forceinline__ double ship_log_bailout(const DeepJuliaArgs& A) { return A.log_bailout; }
 __device__ __forceinline__ double ship_log_bailout(const DeepJuliaXArgs& A) { return A.log_bailout; }
+__host__ __device__ __forceinline__ const DeepArgs& deep_args(const DeepJuliaBlaArgs& A) { return A.j.d; }
+__host__ __device__ __forceinline__ const DeepArgs& deep_args(const DeepJuliaXBlaArgs& A) { return A.j.x.d; }
+__host__ __device__ __forceinline__ const DeepXArgs& deepx_args(const DeepJuliaXBlaArgs& A) { return A.j.x; }
+__device__ __forceinline__ double ship_log_bailout(const DeepJuliaBlaArgs& A) { return A.j.log_bailout; }
+__device__ __forceinline__ double ship_log_bailout(const DeepJuliaXBlaArgs& A) { return A.j.log_bailout; }
+
+template <class T, class... U>
+constexpr bool is_any_of = (std::is_same<T, U>::value || ...);
+
 /* where a sample starts: a Julia view's P; nothing for the formulas with one orbit */
 template <class ARGS>
 __device__ __forceinline__ JuliaStart julia_start(const ARGS& A)
 {
-    if constexpr (std::is_same<ARGS, DeepJuliaArgs>::value || std::is_same<ARGS, DeepJuliaXArgs>::value) return A.j;
+    if constexpr (is_any_of<ARGS, DeepJuliaArgs, DeepJuliaXArgs>) return A.j;
+    else if constexpr (is_any_of<ARGS, DeepJuliaBlaArgs, DeepJuliaXBlaArgs>) return A.j.j;
     else return JuliaStart{0, 0};
 }
 
-template <class T, class... U>
-constexpr bool is_any_of = (std::is_same<T, U>::value || ...);
+/* a table block's table: Q's of a Julia view */
+template <class TAB>
+__host__ __device__ __forceinline__ TAB& q_table(TAB& t) { return t; }
+template <class TAB>
+__host__ __device__ __forceinline__ TAB& q_table(JuliaTab<TAB>& t) { return t.q; }
+template <class TAB>
+__host__ __device__ __forceinline__ const TAB& q_table(const JuliaTab<TAB>& t) { return t.q; }
 
 /* ARGS names the loop: Deep[Ship|Julia][X][Bla]Args = the formula, extended-exponent deltas, BLA (with the step counts) */
 template <class ARGS>
 __global__ void __launch_bounds__(kBlockThreads)
 deep_kernel(const ARGS AA)
 {
-    constexpr bool BLA = is_any_of<ARGS, DeepBlaArgs, DeepXBlaArgs, DeepShipBlaArgs, DeepShipXBlaArgs>;
-    constexpr bool X = is_any_of<ARGS, DeepXArgs, DeepXBlaArgs, DeepShipXArgs, DeepShipXBlaArgs, DeepJuliaXArgs>;
+    constexpr bool BLA = is_any_of<ARGS, DeepBlaArgs, DeepXBlaArgs, DeepShipBlaArgs, DeepShipXBlaArgs, DeepJuliaBlaArgs,
+                                   DeepJuliaXBlaArgs>;
+    constexpr bool X = is_any_of<ARGS, DeepXArgs, DeepXBlaArgs, DeepShipXArgs, DeepShipXBlaArgs, DeepJuliaXArgs,
+                                 DeepJuliaXBlaArgs>;
     constexpr bool SHIP = is_any_of<ARGS, DeepShipArgs, DeepShipBlaArgs, DeepShipXArgs, DeepShipXBlaArgs>;
-    constexpr bool JULIA = is_any_of<ARGS, DeepJuliaArgs, DeepJuliaXArgs>;
+    constexpr bool JULIA = is_any_of<ARGS, DeepJuliaArgs, DeepJuliaXArgs, DeepJuliaBlaArgs, DeepJuliaXBlaArgs>;
     using F = std::conditional_t<JULIA, JuliaFormula, std::conditional_t<SHIP, ShipFormula, MandelFormula>>;
     constexpr int FRACTAL = F::kFractal;
     const DeepArgs& A = deep_args(AA);
@@ -1189,6 +1358,9 @@ deep_kernel(const ARGS AA)
     const bool want_nu = want_rgb || A.nu != nullptr;
 
     unsigned long long n_plain = 0ull, n_bla = 0ull, n_upd = 0ull;   /* BLA: this lane's steps and updates */
+    int levels_p = 0;                                             /* BLA on two orbits: P's table */
+    uint32_t base_p = 0u;
+    if constexpr (BLA && JULIA) { levels_p = AA.t.levels_p; base_p = AA.t.base_p; }
     walk_subtiles<3, true>(A.q, A.g, lane, [&](const int px, const int py, const int lrow, const bool inside) {
         float acc[3] = {0.0f, 0.0f, 0.0f};
         double nu0 = 0.0;
@@ -1203,10 +1375,13 @@ deep_kernel(const ARGS AA)
             if constexpr (X) {
                 int ec = deepx_args(AA).ze;
                 x_norm(cx, cy, ec);
-                if constexpr (BLA) deep_orbit_x_bla<F>(deepx_args(AA), AA.t, cx, cy, ec, inside, esc, r2, np, nb);
+                if constexpr (BLA)
+                    deep_orbit_x_bla<F>(deepx_args(AA), q_table(AA.t), julia_start(AA), levels_p, base_p, cx, cy, ec, inside, esc,
+                                        r2, np, nb);
                 else deep_orbit_x<F>(deepx_args(AA), julia_start(AA), cx, cy, ec, inside, esc, r2);
             } else {
-                if constexpr (BLA) deep_orbit_bla<F>(A, AA.t, cx, cy, z1, inside, esc, r2, np, nb);
+                if constexpr (BLA)
+                    deep_orbit_bla<F>(A, q_table(AA.t), julia_start(AA), levels_p, base_p, cx, cy, z1, inside, esc, r2, np, nb);
                 else deep_orbit<F>(A, julia_start(AA), cx, cy, z1, inside, esc, r2);
             }
             if (BLA && inside) {
@@ -1234,7 +1409,7 @@ deep_kernel(const ARGS AA)
         unsigned long long v[3] = {n_plain, n_bla, n_upd - n_plain};
         for (int c = 0; c < 3; ++c) {
             for (int o = kWave / 2; o > 0; o >>= 1) v[c] += __shfl_xor(v[c], o, kWave);
-            if (lane == 0) atomicAdd(AA.t.steps + c, v[c]);
+            if (lane == 0) atomicAdd(q_table(AA.t).steps + c, v[c]);
         }
     }
 }

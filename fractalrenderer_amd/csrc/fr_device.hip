@@ -42,7 +42,7 @@ struct OrbitKey {
     uint64_t c_bits[2];         /* Julia: the bits of c (0 in the other formulas' slots) */
 };
 
-/* the formula of a deep view: the index of its cache slots (kJulia has orbit slots only: no BLA) */
+/* the formula of a deep view: the index of its cache slots */
 enum { kMandel = 0, kShip = 1, kJulia = 2 };
 
 /* One cache slot of reference orbits of deep views: the buffers and what they hold */
@@ -61,11 +61,12 @@ struct DeepOrbit {
 struct BlaSlot {
     void* r;                    /* r of every entry (cap): doubles, or XRad in an extended table */
     double2* ab;                /* (A, B) of every entry (the formula's kAbPerEntry times cap); extended: their mantissas */
-    int2* abe;                  /* extended: their exponents (cap) */
-    size_t cap;                 /* entries */
+    int2* abe;                  /* extended: their exponents (cap); a Julia slot: A's alone, an int32 per entry */
+    size_t cap;                 /* entries (a Julia slot: of both tables, Q's first) */
     bool valid;                 /* the key below describes the table */
-    uint64_t key_gen, key_dcv;  /* gen of its orbit; bits of dcmax, extended: of dcmax's mantissa */
+    uint64_t key_gen, key_dcv;  /* gen of its orbit; bits of dcmax, extended: of dcmax's mantissa (a Julia slot: 0, no dcmax) */
     int32_t key_dce;            /* extended: dcmax's exponent */
+    uint64_t builds;            /* how often the table has been built (tests: fr_deep_bla_builds) */
     unsigned long long* steps_dev;     /* the kernel's three counters */
     unsigned long long* steps_host;    /* pinned: their copy behind the most recent render with the flag */
     bool have_steps;
@@ -132,8 +133,8 @@ struct fr_ctx {
     DeepOrbit deep[3];          /* plain doubles Z_0 .. Z_N: 2 cap doubles pinned, cap double2 on the device */
     DeepOrbit deepx[3];         /* the extended storage.  One pinned and one device block of cap points each: the plain
                                  * doubles, the mantissa pairs, the exponents, in this order. */
-    BlaSlot bla[2];             /* FR_FLAG_DEEP_BLA, FR_FLAG_DEEP_SHIP_BLA: the tables of deep[] */
-    BlaSlot blax[2];            /* FR_FLAG_DEEPX_BLA, FR_FLAG_DEEPX_SHIP_BLA: the tables of deepx[] */
+    BlaSlot bla[3];             /* FR_FLAG_DEEP_BLA, FR_FLAG_DEEP_SHIP_BLA, FR_FLAG_DEEP_JULIA_BLA: the tables of deep[] */
+    BlaSlot blax[3];            /* FR_FLAG_DEEPX_BLA, FR_FLAG_DEEPX_SHIP_BLA, FR_FLAG_DEEPX_JULIA_BLA: the tables of deepx[] */
 };
 
 #define FR_HIP_TRY(expr)                                                               \
@@ -185,6 +186,8 @@ extern "C" int fr_ctx_create(int device_ordinal, fr_ctx** out)
         (e2 = hipEventCreateWithFlags(&c->bla[kShip].ev, hipEventDisableTiming)) != hipSuccess ||
         (e2 = hipEventCreateWithFlags(&c->blax[kMandel].ev, hipEventDisableTiming)) != hipSuccess ||
         (e2 = hipEventCreateWithFlags(&c->blax[kShip].ev, hipEventDisableTiming)) != hipSuccess ||
+        (e2 = hipEventCreateWithFlags(&c->bla[kJulia].ev, hipEventDisableTiming)) != hipSuccess ||
+        (e2 = hipEventCreateWithFlags(&c->blax[kJulia].ev, hipEventDisableTiming)) != hipSuccess ||
         (e2 = hipMalloc((void**)&c->d_ctrl, (kCtrlWords + (size_t)(kFeedbackShards + 2) * kShardStrideWords) * sizeof(uint32_t))) != hipSuccess ||
         (e2 = hipMemset(c->d_ctrl, 0, (kCtrlWords + (size_t)(kFeedbackShards + 2) * kShardStrideWords) * sizeof(uint32_t))) != hipSuccess ||
         (e2 = hipHostMalloc((void**)&c->overflow_host, 64, hipHostMallocMapped)) != hipSuccess ||
@@ -226,7 +229,7 @@ extern "C" void fr_ctx_destroy(fr_ctx* c)
         free(o->key.x);
         free(o->key.y);
     }
-    for (BlaSlot* t : {&c->bla[kMandel], &c->bla[kShip], &c->blax[kMandel], &c->blax[kShip]}) {
+    for (BlaSlot* t : {&c->bla[kMandel], &c->bla[kShip], &c->bla[kJulia], &c->blax[kMandel], &c->blax[kShip], &c->blax[kJulia]}) {
         if (t->r) (void)hipFree(t->r);
         if (t->ab) (void)hipFree(t->ab);
         if (t->abe) (void)hipFree(t->abe);
@@ -813,28 +816,50 @@ static double bla_dcmax(int f, double zs, double w, double h)
 /* BLA: the table of the formula's cached orbit -- the extended one with x, the view's extended block -- for this frame's
  * dcmax, built on `stream` unless the slot holds it.  A rebuild overwrites the buffers in place behind the slot's last BLA
  * render (its event: the render may have gone to another stream); growing them frees the old ones, so that waits on the host
- * first. */
-static int bla_table_for(fr_ctx* c, int f, const DeepArgs& d, const DeepXArgs* x, hipStream_t stream, int* levels)
+ * first.  A Julia slot (jt) holds two tables, Q's entries first and P's behind them, built from the slot's two orbits; no dcmax
+ * enters them, so their key is the orbit slot's generation alone and a zoom change rebuilds nothing. */
+static int bla_levels(int32_t N) { return N > 1 ? 31 - __builtin_clz((uint32_t)(N - 1)) : 0; }   /* floor(log2(N - 1)) */
+static size_t bla_entries(int32_t N)             /* sum over k >= 1 of (N - 1) >> k */
+{
+    const uint32_t n1 = (uint32_t)(N - 1);
+    return (size_t)(n1 - (uint32_t)__builtin_popcount(n1));
+}
+
+struct JuliaTables { int32_t levels_p; uint32_t base_p; };
+
+static int bla_table_for(fr_ctx* c, int f, const DeepArgs& d, const DeepXArgs* x, hipStream_t stream, int* levels,
+                         JuliaTables* jt)
 {
     BlaSlot& t = (x ? c->blax : c->bla)[f];
     const DeepOrbit& o = (x ? c->deepx : c->deep)[f];
     const int32_t N = o.len - 1;
-    const int K = N > 1 ? 31 - __builtin_clz((uint32_t)(N - 1)) : 0;   /* floor(log2(N - 1)) */
+    const int K = bla_levels(N);
     *levels = K;
-    if (K == 0) return FR_OK;
-    double dcv = bla_dcmax(f, x ? x->zm : d.zoom, (double)d.g.W, (double)d.g.H);
+    const int32_t NP = f == kJulia ? o.len_p - 1 : 1;
+    const int KP = bla_levels(NP);
+    size_t need = bla_entries(N);
+    if (f == kJulia) {
+        jt->levels_p = KP;
+        jt->base_p = (uint32_t)need;
+        need += bla_entries(NP);
+    }
+    if (K == 0 && KP == 0) return FR_OK;
+    double dcv = 0.0;
     int32_t dce = 0;
-    if (x) {                                     /* as an extended real with the zoom pair, normalised: dcv in [0.5, 1) */
-        int de = 0;
-        dcv = frexp(dcv, &de);
-        dce = x->ze + de;
+    if (f != kJulia) {
+        dcv = bla_dcmax(f, x ? x->zm : d.zoom, (double)d.g.W, (double)d.g.H);
+        if (x) {                                 /* as an extended real with the zoom pair, normalised: dcv in [0.5, 1) */
+            int de = 0;
+            dcv = frexp(dcv, &de);
+            dce = x->ze + de;
+        }
     }
     uint64_t dbits;
     memcpy(&dbits, &dcv, sizeof(dbits));
     if (t.valid && t.key_gen == o.gen && t.key_dcv == dbits && t.key_dce == dce) return FR_OK;
     t.valid = false;
     const uint32_t n1 = (uint32_t)(N - 1);
-    const size_t need = (size_t)(n1 - (uint32_t)__builtin_popcount(n1));     /* sum over k >= 1 of (N - 1) >> k */
+    const size_t nab = f == kShip ? ShipFormula::kAbPerEntry : f == kJulia ? JuliaFormula::kAbPerEntry : MandelFormula::kAbPerEntry;
     if (need > t.cap) {
         FR_HIP_TRY(hipStreamSynchronize(stream));
         FR_HIP_TRY(hipStreamSynchronize(c->stream));
@@ -843,19 +868,18 @@ static int bla_table_for(fr_ctx* c, int f, const DeepArgs& d, const DeepXArgs* x
         if (t.ab) { (void)hipFree(t.ab); t.ab = nullptr; }
         if (t.abe) { (void)hipFree(t.abe); t.abe = nullptr; }
         t.cap = 0;
-        const size_t nab = f == kShip ? ShipFormula::kAbPerEntry : MandelFormula::kAbPerEntry;
         FR_HIP_TRY(hipMalloc(&t.r, need * (x ? sizeof(XRad) : sizeof(double))));
         FR_HIP_TRY(hipMalloc((void**)&t.ab, need * nab * sizeof(double2)));
-        if (x) FR_HIP_TRY(hipMalloc((void**)&t.abe, need * sizeof(int2)));
+        if (x) FR_HIP_TRY(hipMalloc((void**)&t.abe, need * (f == kJulia ? sizeof(int32_t) : sizeof(int2))));
         t.cap = need;
     } else if (t.ev_valid) {
         FR_HIP_TRY(hipStreamWaitEvent(stream, t.ev, 0));
     }
-    for (int k = 1; k <= K; ++k) {
+    const uint32_t grid_cap = (uint32_t)c->compute_units * 8u;
+    for (int k = 1; k <= K && f != kJulia; ++k) {
         const uint32_t cnt = n1 >> k;
         uint32_t grid = (cnt + kBlockThreads - 1) / kBlockThreads;
-        const uint32_t cap = (uint32_t)c->compute_units * 8u;
-        if (grid > cap) grid = cap;
+        if (grid > grid_cap) grid = grid_cap;
         if (x)
             hipLaunchKernelGGL(f == kShip ? deepx_ship_bla_level_kernel : deepx_bla_level_kernel, dim3(grid), dim3(kBlockThreads),
                                0, stream, x->mant, x->exp2, N, k, dcv, dce, (XRad*)t.r, t.ab, t.abe);
@@ -867,6 +891,25 @@ static int bla_table_for(fr_ctx* c, int f, const DeepArgs& d, const DeepXArgs* x
             return fr_set_error(FR_ERR_HIP, "%s%sBLA table launch failed: %s", x ? "extended " : "", f == kShip ? "ship " : "",
                                 hipGetErrorString(e));
     }
+    for (int q = 0; q < 2 && f == kJulia; ++q) {                 /* Q's table from the orbit at point 0, then P's behind both */
+        const int32_t No = q ? NP : N;
+        const size_t po = q ? o.cap / 2 : 0, eo = q ? jt->base_p : 0;   /* the orbit's first point, the table's first entry */
+        for (int k = 1; k <= (q ? KP : K); ++k) {
+            const uint32_t cnt = (uint32_t)(No - 1) >> k;
+            uint32_t grid = (cnt + kBlockThreads - 1) / kBlockThreads;
+            if (grid > grid_cap) grid = grid_cap;
+            if (x)
+                hipLaunchKernelGGL(deepx_julia_bla_level_kernel, dim3(grid), dim3(kBlockThreads), 0, stream, x->mant + po,
+                                   x->exp2 + po, No, k, (XRad*)t.r + eo, t.ab + eo * nab, (int32_t*)t.abe + eo);
+            else
+                hipLaunchKernelGGL(deep_julia_bla_level_kernel, dim3(grid), dim3(kBlockThreads), 0, stream, d.orbit + po, No, k,
+                                   (double*)t.r + eo, t.ab + eo * nab);
+            const hipError_t e = hipGetLastError();
+            if (e != hipSuccess)
+                return fr_set_error(FR_ERR_HIP, "%sJulia BLA table launch failed: %s", x ? "extended " : "", hipGetErrorString(e));
+        }
+    }
+    ++t.builds;
     t.key_gen = o.gen;
     t.key_dcv = dbits;
     t.key_dce = dce;
@@ -891,19 +934,22 @@ static int launch_deep(fr_ctx* c, hipStream_t stream, const char* name, const ch
         DeepArgs& d = deep_of(base);
         return launch_one_pass(c, stream, name, deep_kernel<BASE>, base, d.g, d.q, wg_per_cu, false);
     }
-    constexpr int f = is_any_of<BASE, DeepShipArgs, DeepShipXArgs> ? kShip : kMandel;
-    constexpr bool ext = is_any_of<BASE, DeepXArgs, DeepShipXArgs>;
+    constexpr int f = is_any_of<BASE, DeepShipArgs, DeepShipXArgs> ? kShip : is_any_of<BASE, DeepJuliaArgs, DeepJuliaXArgs> ? kJulia : kMandel;
+    constexpr bool ext = is_any_of<BASE, DeepXArgs, DeepShipXArgs, DeepJuliaXArgs>;
     BLA a;
     memset(&a, 0, sizeof(a));
-    auto& [b, tab] = a;
+    auto& [b, tabs] = a;
     b = base;
     DeepArgs& d = deep_of(a);
     const DeepXArgs* x = nullptr;
     if constexpr (ext) x = &deepx_args(a);
     BlaSlot& t = (ext ? c->blax : c->bla)[f];
     int levels = 0;
-    const int ts = bla_table_for(c, f, d, x, stream, &levels);
+    JuliaTables jt = {0, 0u};
+    const int ts = bla_table_for(c, f, d, x, stream, &levels, &jt);
     if (ts != FR_OK) return ts;
+    auto& tab = q_table(tabs);
+    if constexpr (f == kJulia) { tabs.levels_p = jt.levels_p; tabs.base_p = jt.base_p; }
     bla_table_args(tab, t);
     tab.levels = levels;
     if (!t.steps_dev) {
@@ -1050,8 +1096,8 @@ static int enqueue_deepx(fr_ctx* c, int f, const fr_params* p, const fr_deepx_vi
 }
 
 /* ---- Julia views (fr_render_deep_julia, fr_render_deepx_julia) ---------------------------------------------------------
- * Two orbits per slot (the header's P and Q), keyed by the bits of c as well; no BLA, so nothing but an earlier render can
- * still read the slot.  ext: the extended storage, `zoom` then being the view's zoom string. */
+ * Two orbits per slot (the header's P and Q), keyed by the bits of c as well.  ext: the extended storage, `zoom` then being the
+ * view's zoom string. */
 static int julia_slot_fill(fr_ctx* c, bool ext, const fr_params* p, const char* cx, const char* cy, const char* zoom,
                            int32_t bits, hipStream_t stream)
 {
@@ -1063,7 +1109,8 @@ static int julia_slot_fill(fr_ctx* c, bool ext, const fr_params* p, const char* 
     if (orbit_key_matches(o.key, cx, cy, bits, max_iter, p->bailout) && o.key.c_bits[0] == cb[0] && o.key.c_bits[1] == cb[1])
         return FR_OK;
     const size_t point_bytes = ext ? 2 * sizeof(double2) + sizeof(int32_t) : sizeof(double2);
-    const int ps = orbit_slot_prepare(c, o, nullptr, stream, 2 * ((size_t)max_iter + 1), point_bytes);   /* an even capacity */
+    const int ps = orbit_slot_prepare(c, o, &(ext ? c->blax : c->bla)[kJulia], stream, 2 * ((size_t)max_iter + 1),
+                                      point_bytes);              /* an even capacity */
     if (ps != FR_OK) return ps;
     const size_t cap = o.cap, half = cap / 2;
     double* plain = (double*)o.host;
@@ -1128,7 +1175,8 @@ static int enqueue_deep_julia(fr_ctx* c, const fr_params* p, const fr_deep_view*
     j.j.p_off = (int32_t)(o.cap / 2); j.j.n_p = o.len_p - 1;
     fill_deep_args(a, c, p, tile_geom(W, H, rows_local, &norm, out_frame), rgba, nu, iter);
     j.log_bailout = log((double)p->bailout);     /* as fill_params */
-    return launch_one_pass(c, stream, "deep_kernel<DeepJuliaArgs>", deep_kernel<DeepJuliaArgs>, j, a.g, a.q, o.wg_per_cu, false);
+    return launch_deep<DeepJuliaBlaArgs>(c, stream, "deep_kernel<DeepJuliaArgs>", "deep_kernel<DeepJuliaBlaArgs>", j,
+                                         (p->flags & FR_FLAG_DEEP_JULIA_BLA) != 0, o.wg_per_cu);
 }
 
 static int enqueue_deepx_julia(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, uint32_t W, uint32_t H,
@@ -1159,7 +1207,8 @@ static int enqueue_deepx_julia(fr_ctx* c, const fr_params* p, const fr_deepx_vie
     j.j.p_off = (int32_t)(o.cap / 2); j.j.n_p = o.len_p - 1;
     fill_deep_args(a, c, p, tile_geom(W, H, rows_local, &norm, out_frame), rgba, nu, iter);
     j.log_bailout = log((double)p->bailout);     /* as fill_params */
-    return launch_one_pass(c, stream, "deep_kernel<DeepJuliaXArgs>", deep_kernel<DeepJuliaXArgs>, j, a.g, a.q, o.wg_per_cu, false);
+    return launch_deep<DeepJuliaXBlaArgs>(c, stream, "deep_kernel<DeepJuliaXArgs>", "deep_kernel<DeepJuliaXBlaArgs>", j,
+                                          (p->flags & FR_FLAG_DEEPX_JULIA_BLA) != 0, o.wg_per_cu);
 }
 
 /* ---- deep zoom sequences (fr_deep_sequence; the rules are in the header, the host planning in fr_deepseq.c) ---------------
@@ -1759,16 +1808,20 @@ static int64_t read_bla_table(fr_ctx* c, bool ext, int f, void* r, double* ab, i
     if (!c) return fr_set_error(FR_ERR_INVALID_ARG, "ctx is NULL");
     const BlaSlot& t = (ext ? c->blax : c->bla)[f];
     if (!t.valid) return 0;
-    const int32_t N = (ext ? c->deepx : c->deep)[f].len - 1;
-    const uint32_t n1 = (uint32_t)(N - 1);
-    const int64_t have = (int64_t)(n1 - (uint32_t)__builtin_popcount(n1));
+    const DeepOrbit& o = (ext ? c->deepx : c->deep)[f];
+    int64_t have = (int64_t)bla_entries(o.len - 1);
+    if (f == kJulia) {                                            /* Q's entries, then P's; none once the slot's orbits changed */
+        if (t.key_gen != o.gen) return 0;
+        have += (int64_t)bla_entries(o.len_p - 1);
+    }
     if (n > have) n = have;
-    const size_t nab = f == kShip ? ShipFormula::kAbPerEntry : MandelFormula::kAbPerEntry;
+    const size_t nab = f == kShip ? ShipFormula::kAbPerEntry : f == kJulia ? JuliaFormula::kAbPerEntry : MandelFormula::kAbPerEntry;
+    const size_t nexp = f == kJulia ? sizeof(int32_t) : sizeof(int2);
     FR_HIP_TRY(hipSetDevice(c->device));
     FR_HIP_TRY(hipDeviceSynchronize());
     if (n > 0 && r) FR_HIP_TRY(hipMemcpy(r, t.r, (size_t)n * (ext ? sizeof(XRad) : sizeof(double)), hipMemcpyDeviceToHost));
     if (n > 0 && ab) FR_HIP_TRY(hipMemcpy(ab, t.ab, (size_t)n * nab * sizeof(double2), hipMemcpyDeviceToHost));
-    if (n > 0 && ext && ab_exp) FR_HIP_TRY(hipMemcpy(ab_exp, t.abe, (size_t)n * sizeof(int2), hipMemcpyDeviceToHost));
+    if (n > 0 && ext && ab_exp) FR_HIP_TRY(hipMemcpy(ab_exp, t.abe, (size_t)n * nexp, hipMemcpyDeviceToHost));
     return have;
 }
 
@@ -1790,6 +1843,32 @@ extern "C" int fr_ctx_last_deepx_steps(fr_ctx* c, uint64_t out[3])
 extern "C" int fr_ctx_last_deepx_ship_steps(fr_ctx* c, uint64_t out[3])
 {
     return last_bla_steps(c, true, kShip, "fr_render_deepx_ship call with FR_FLAG_DEEPX_SHIP_BLA", out);
+}
+
+extern "C" int64_t fr_deep_bla_builds(fr_ctx* c, int extended, int formula)
+{
+    if (!c || formula < kMandel || formula > kJulia) return fr_set_error(FR_ERR_INVALID_ARG, "ctx is NULL or no such formula");
+    return (int64_t)(extended ? c->blax : c->bla)[formula].builds;
+}
+
+extern "C" int fr_ctx_last_deep_julia_steps(fr_ctx* c, uint64_t out[3])
+{
+    return last_bla_steps(c, false, kJulia, "fr_render_deep_julia call with FR_FLAG_DEEP_JULIA_BLA", out);
+}
+
+extern "C" int fr_ctx_last_deepx_julia_steps(fr_ctx* c, uint64_t out[3])
+{
+    return last_bla_steps(c, true, kJulia, "fr_render_deepx_julia call with FR_FLAG_DEEPX_JULIA_BLA", out);
+}
+
+extern "C" int64_t fr_deep_julia_bla_table(fr_ctx* c, double* r, double* a, int64_t n)
+{
+    return read_bla_table(c, false, kJulia, r, a, nullptr, n);
+}
+
+extern "C" int64_t fr_deepx_julia_bla_table(fr_ctx* c, void* r, double* a, int32_t* a_exp, int64_t n)
+{
+    return read_bla_table(c, true, kJulia, r, a, a_exp, n);
 }
 
 extern "C" int64_t fr_deep_bla_table(fr_ctx* c, double* r, double* ab, int64_t n)

@@ -73,6 +73,9 @@ int64_t fr_deep_ship_bla_table(fr_ctx* ctx, double* r, double* ab, int64_t n);
  * bytes, ab 8 n doubles (the mantissas a11, a12, a21, a22, b11, b12, b21, b22 per entry), ab_exp 2 n int32 (A.e, B.e);
  * NULL skips a part.  Returns the number of entries the table has (0: none). */
 int64_t fr_deepx_ship_bla_table(fr_ctx* ctx, void* r, double* ab, int32_t* ab_exp, int64_t n);
+/* tests: how often the context has built the BLA table of a path: extended 0 / 1, formula 0 Mandelbrot, 1 Burning Ship, 2 Julia
+ * (a cached table serves a render without a build) */
+int64_t fr_deep_bla_builds(fr_ctx* ctx, int extended, int formula);
 
 /* the context's own stream (hipStream_t) and device ordinal: fr_node.cpp orders RCCL transfers behind the renders */
 void* fr_ctx_stream_handle(fr_ctx* ctx);

@@ -152,6 +152,20 @@ class Renderer:
         _capi.check(self._lib.fr_ctx_last_deepx_ship_steps(self._ctx, out))
         return DeepSteps(int(out[0]), int(out[1]), int(out[2]))
 
+    def last_deep_julia_steps(self) -> DeepSteps:
+        """fr_ctx_last_deep_julia_steps: (single steps, BLA steps, updates skipped) of the most recent render_deep_julia(bla=True)
+        of a view without a zoom string on this context, both orbits counted together, as last_deep_steps()."""
+        out = (C.c_uint64 * 3)()
+        _capi.check(self._lib.fr_ctx_last_deep_julia_steps(self._ctx, out))
+        return DeepSteps(int(out[0]), int(out[1]), int(out[2]))
+
+    def last_deepx_julia_steps(self) -> DeepSteps:
+        """fr_ctx_last_deepx_julia_steps: the same for the most recent render_deep_julia(bla=True) of a view with a zoom
+        string (single steps of both modes)."""
+        out = (C.c_uint64 * 3)()
+        _capi.check(self._lib.fr_ctx_last_deepx_julia_steps(self._ctx, out))
+        return DeepSteps(int(out[0]), int(out[1]), int(out[2]))
+
     def last_kernel_ms(self) -> float:
         return float(self._lib.fr_ctx_last_kernel_ms(self._ctx))
 
@@ -318,21 +332,27 @@ class Renderer:
 
     def render_deep_julia(self, state: FractalState, width: int, height: int, view: Optional[DeepView] = None, *,
                           post_chain: bool = False, rgba=None, nu=None, iter=None, shard: Optional[Shard] = None,
-                          stream: Optional[int] = None, sync: bool = True) -> None:
+                          stream: Optional[int] = None, sync: bool = True, bla: bool = False) -> None:
         """fr_render_deep_julia / fr_render_deep_julia_async: a Julia set view deeper than double precision, by perturbation
         around two reference orbits computed on the host (the orbit of the centre, and the critical orbit samples rebase
         onto).  c = (state.julia_c_real, state.julia_c_imag); `view` carries the centre as decimal strings (default "0",
         "0"), the zoom and every other field come from `state` (its double centre is not read).  A view with a zoom string
         (DeepView(..., zoom="1e-400")) goes to fr_render_deepx_julia / fr_render_deepx_julia_async: extended-exponent deltas,
         zooms down to 1e-1000, state.zoom not read.  Always fp64; planes, shard, stream and sync as for render_deep().
-        There is no BLA for Julia views."""
+        bla=True sets the flag that fits the view, FR_FLAG_DEEPX_JULIA_BLA with a zoom string and FR_FLAG_DEEP_JULIA_BLA
+        without: iteration skipping by bilinear approximation on both orbits (the header's rules; last_deepx_julia_steps() /
+        last_deep_julia_steps() report what it skipped)."""
         p = state.to_params(FractalType.JuliaSet, Precision.F64, post_chain)
         rows = shard.rows(height) if shard else height
         if view is not None and view.zoom is not None:
+            if bla:
+                p.flags |= _capi.FR_FLAG_DEEPX_JULIA_BLA
             vx = view.to_cx()
             self._render_call(self._lib.fr_render_deepx_julia, self._lib.fr_render_deepx_julia_async, (C.byref(p), C.byref(vx)),
                               width, height, Precision.F64, rows, rgba, nu, iter, shard, stream, sync)
             return
+        if bla:
+            p.flags |= _capi.FR_FLAG_DEEP_JULIA_BLA
         v = (view or DeepView("0", "0")).to_c()
         self._render_call(self._lib.fr_render_deep_julia, self._lib.fr_render_deep_julia_async, (C.byref(p), C.byref(v)), width,
                           height, Precision.F64, rows, rgba, nu, iter, shard, stream, sync)

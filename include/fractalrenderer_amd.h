@@ -77,6 +77,10 @@ typedef enum fr_precision {
                                       (see there); every other entry point ignores it */
 #define FR_FLAG_DEEPX_SHIP_BLA 0x10u /* fr_render_deepx_ship, its _async form and fr_deep_ship_sequence_create only: the same
                                       for extended Burning Ship views (see there); every other entry point ignores it */
+#define FR_FLAG_DEEP_JULIA_BLA 0x20u /* fr_render_deep_julia and its _async form only: the same for deep Julia views (see
+                                      there); the other deep entry points answer FR_ERR_UNSUPPORTED */
+#define FR_FLAG_DEEPX_JULIA_BLA 0x40u /* fr_render_deepx_julia and its _async form only: the same for extended Julia views (see
+                                      there); the other deep entry points answer FR_ERR_UNSUPPORTED */
 
 /*
  * fr_params -- the hot-path fields of FractalState (src/fractal_state.h:16-91),
@@ -1016,9 +1020,12 @@ int fr_ctx_last_deepx_ship_steps(fr_ctx* ctx, uint64_t out[3]);
  * with the Julia floors.  Julia has no trap, stripe or interior styles: those fields are ignored, as fr_render ignores them.
  *
  * Validation (fr_deep_julia_validate, fr_deepx_julia_validate: no device needed): FR_ERR_UNSUPPORTED if p->fractal_type is not
- * FR_FRACTAL_JULIA, p->precision not FR_PRECISION_F64, or with any of the four BLA flags; FR_ERR_INVALID_ARG for c not finite
- * or a component of |c| >= 2^32, bailout > 2^16, the centre rule above, and otherwise as fr_render_deep_ship /
- * fr_render_deepx_ship.  The other deep entry points keep rejecting FR_FRACTAL_JULIA.
+ * FR_FRACTAL_JULIA, p->precision not FR_PRECISION_F64, or with any of the four BLA flags of the other formulas or with the
+ * other Julia entry point's flag (FR_FLAG_DEEPX_JULIA_BLA in fr_render_deep_julia, FR_FLAG_DEEP_JULIA_BLA in
+ * fr_render_deepx_julia); FR_ERR_INVALID_ARG for c not finite or a component of |c| >= 2^32, bailout > 2^16, the centre rule
+ * above, and otherwise as fr_render_deep_ship / fr_render_deepx_ship.  The other deep entry points keep rejecting
+ * FR_FRACTAL_JULIA, and answer FR_ERR_UNSUPPORTED for the two Julia BLA flags (fr_render_deep, fr_render_deepx,
+ * fr_render_deep_ship, fr_render_deepx_ship and the two sequence creators).
  *
  * Argument shape, shards, FR_LAYOUT_FRAME, memory kinds, options, fr_ctx_last_kernel_ms / _grid and the asynchronous rules are
  * fr_render_deep_ship's and fr_render_deepx_ship's; a render of a new view computes its orbits on the host first and is
@@ -1030,9 +1037,11 @@ int fr_ctx_last_deepx_ship_steps(fr_ctx* ctx, uint64_t out[3]);
  * lane-updates/s, next to fr_render_deep's 16.54 ms (830 G/s) on its 1e-100 view; the dendrite at 1e-400 (3000) 95.6 ms through
  * fr_render_deepx_julia, 496 G/s, next to fr_render_deepx's 111.9 ms (487 G/s) on its 1e-400 view.
  *
- * Out of scope: BLA for Julia (one table per orbit, with B = 0); zoom sequences; fr_node and .franim; c as a decimal string. */
+ * Out of scope: Julia zoom sequences; fr_node and .franim; c as a decimal string. */
 #define FR_HAS_DEEP_JULIA 1
 #define FR_HAS_DEEPX_JULIA 1
+#define FR_HAS_DEEP_JULIA_BLA 1   /* FR_FLAG_DEEP_JULIA_BLA and fr_ctx_last_deep_julia_steps (below the render entry points) */
+#define FR_HAS_DEEPX_JULIA_BLA 1  /* FR_FLAG_DEEPX_JULIA_BLA and fr_ctx_last_deepx_julia_steps */
 
 /* Both orbits as doubles, on the host: out_p_xy and out_q_xy receive 2 (max_iter + 1) doubles each at most;
  * *out_p_len = N_P + 1, *out_q_len = N_Q + 1.  Validation and cost as two fr_deep_reference_orbit calls. */
@@ -1055,6 +1064,66 @@ int fr_render_deepx_julia(fr_ctx* ctx, const fr_params* p, const fr_deepx_view* 
                           const fr_shard* shard, const fr_output* out);
 int fr_render_deepx_julia_async(fr_ctx* ctx, const fr_params* p, const fr_deepx_view* view, uint32_t width, uint32_t height,
                                 const fr_shard* shard, const fr_output* out, void* hip_stream);
+
+/* Bilinear approximation for Julia views, opt-in per call: FR_FLAG_DEEP_JULIA_BLA is read by fr_render_deep_julia(_async) only,
+ * FR_FLAG_DEEPX_JULIA_BLA by fr_render_deepx_julia(_async) only; without its flag every byte an entry point writes is as above.
+ * It is FR_FLAG_DEEP_BLA's scheme with B = 0: a Julia step has no dc term, so a step over 2^k updates is ONE complex product
+ * dz' = A dz, the table holds no B, and no dcmax enters a radius -- the tables do not depend on the frame.
+ *
+ * Notation and rounding are FR_FLAG_DEEP_BLA's: one fp64 rounding per operation, no contraction, |w| = sqrt(w.x*w.x + w.y*w.y)
+ * with sqrt correctly rounded.  eps = 2^-53.
+ *   - Single step at m >= 1 on an orbit Z (never stored): A = Z_m + Z_m, r = eps * |Z_m|.
+ *   - Tables: TWO, one over Q_1 .. Q_{N_Q - 1} and one over P_1 .. P_{N_P - 1}, each with FR_FLAG_DEEP_BLA's levels
+ *     (K = floor(log2(N - 1)); N <= 2: no table for that orbit), entry coverage, existence rule and entry count
+ *     E(N) = (N - 1) - popcount(N - 1).  Either table may be absent while the other exists.  They live in one set of buffers,
+ *     Q's entries first: entries [0, E(N_Q)) are Q's table level after level, [E(N_Q), E(N_Q) + E(N_P)) are P's.  An fp64 entry
+ *     is 24 bytes (r 8, A 16), an extended one 28 (the radius 8, A's mantissas 16, A.e 4).
+ *   - Merge (fp64), x then y:  A = A_y*A_x,  t = r_y / |A_x|,  r = (t > 0 ? t : 0) (NaN: 0),  r = (r < r_x ? r : r_x),  and
+ *     r = 0 if A is not finite.  This is FR_FLAG_DEEP_BLA's merge with B = 0.
+ *   - Extended tables: FR_FLAG_DEEPX_BLA's arithmetic with the B terms removed.  Single step: A = norm(Z_m.x, Z_m.y, Z_m.e + 1),
+ *     r = eps * |norm(Z_m)|.  Merge: A = norm(A_y (x) A_x) with the exponent A_y.e + A_x.e;  t = r_y (/) |A_x| (one division of
+ *     the mantissas, exponent r_y.e - |A_x|.e), r = norm(t) if t's mantissa is > 0 and finite, else the zero;  then r = r_x
+ *     unless r < r_x on (exponent, mantissa).  An entry whose A.e leaves [-2^27, 2^27] is void (r and A stored as zero), and the
+ *     STORED radius is cut to 24 bits, as there.
+ *   - Stepping: FR_FLAG_DEEP_BLA's on the sample's CURRENT orbit Z with its N and that orbit's table.  At m >= 1 take the
+ *     largest k >= 1 with (m-1) mod 2^k == 0, m + 2^k <= N, u + 2^k <= max_iterations and |dz|^2 < r*r; then
+ *       dz' = (A.x dz.x - A.y dz.y, A.x dz.y + A.y dz.x),  m += 2^k,  u += 2^k,  z = Z_m + dz',  r2 = |z|^2;
+ *     r2 > bailout^2: escaped at u - 1; otherwise the two-orbit rebase rule of the plain Julia step (r2 < |dz'|^2 or m == N:
+ *     dz = z, m = 0, and the orbit -- with it the table -- becomes Q's for good).  A sample starts on P with dz = d0, m = 0 and
+ *     takes the plain step there: at m = 0 no BLA is tried, on either orbit.  If no k qualifies the plain step runs unchanged.
+ *   - Extended stepping: a sample in either mode probes on its dz as a normalised extended number (FR_FLAG_DEEPX_BLA's probe); the
+ *     BLA step is dz' = norm(A.mant (x) dz.mant, A.e + dz.e), then the FLUSH (e < -2^27 gives the zero), then the -400 mode
+ *     rule, escape and rebase as above.  Every exponent sum stays above -2^29, as without the flag.
+ * Where it differs from the plain step: as FR_FLAG_DEEP_BLA -- a single step drops dz^2 only where it is below one rounding of
+ * the kept term, merged steps differ by rounding order, and escapes inside a BLA step are not looked for.
+ *
+ * Cost: E(N_Q) + E(N_P) entries on the device, per context and path, grown like the orbit buffers; the two paths' tables are
+ * slots of their own and neither evicts another path's orbit or table.  The tables are keyed by the orbit slot alone: a new c, a
+ * new centre, F, max_iterations or bailout recomputes the orbits and then the tables (K_Q + K_P small launches on the render's
+ * stream, ordered behind the slot's previous render with the flag, whatever stream that went to); a zoom change at the same
+ * key rebuilds nothing and is launch-only.
+ *
+ * Measured on one MI355X at 4096^2 (profiles/deep_julia_bla_time.txt, flagged and unflagged interleaved in one session, device
+ * time): the dendrite at 1e-400 96.36 -> 5.49 ms (17.6x, 95.8 % of the updates skipped), DENDRITE100 12.40 -> 4.30 ms (2.88x),
+ * RABBIT30 17.89 -> 14.46 ms (1.24x: its interior samples leave the linear phase early), a view at 1e-60 centred on a preimage
+ * of 0, whose samples step on both tables, 5.52 -> 2.36 ms in fp64 deltas and 7.93 -> 2.94 ms in extended ones; every pixel of
+ * these frames has the unflagged iter.  Where nothing qualifies the flag costs: c = 0 (every radius over a zero is 0) runs at
+ * 0.53x (fp64) and 0.69x (extended) of the unflagged kernels. */
+
+/* fr_ctx_last_deep_steps' contract for the context's most recent fr_render_deep_julia(_async) call made with
+ * FR_FLAG_DEEP_JULIA_BLA, and for the most recent fr_render_deepx_julia(_async) call made with FR_FLAG_DEEPX_JULIA_BLA:
+ * out[0] single steps, out[1] BLA steps, out[2] updates skipped, over every sub-sample of the in-frame pixels, both orbits
+ * counted together.  FR_ERR_UNSUPPORTED if there is no such call. */
+int fr_ctx_last_deep_julia_steps(fr_ctx* ctx, uint64_t out[3]);
+int fr_ctx_last_deepx_julia_steps(fr_ctx* ctx, uint64_t out[3]);
+
+/* The tables as the device holds them, copied to the host after a device synchronise: the first n entries, Q's table first, then
+ * P's (a caller splits them with E(N_Q), then E(N_P), the lengths from fr_deep_julia_reference_orbits /
+ * fr_deepx_julia_reference_orbits; inside a table level k starts E(N) - E(((N - 1) >> (k - 1)) + 1) entries in).  r: n doubles, or
+ * n 8-byte radii (the mantissa as a float, the int32 exponent); a: 2 n doubles (A.x, A.y; extended: the mantissas); a_exp: n
+ * int32.  NULL skips a part.  Returns the number of entries the context holds (0: no table, or the orbits have changed since). */
+int64_t fr_deep_julia_bla_table(fr_ctx* ctx, double* r, double* a, int64_t n);
+int64_t fr_deepx_julia_bla_table(fr_ctx* ctx, void* r, double* a, int32_t* a_exp, int64_t n);
 
 /* ---- frames over the GPUs of a node (BASELINE.json north_star: "tiled across the 8 GPUs of one node as disjoint row
  * bands with a final RCCL gather over xGMI") -----------------------------------------------------------------------------

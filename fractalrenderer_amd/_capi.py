@@ -74,6 +74,10 @@ class fr_deep_view(C.Structure):
     _fields_ = [("center_x", C.c_char_p), ("center_y", C.c_char_p), ("frac_bits", C.c_int32), ("reserved", C.c_int32)]
 
 
+class fr_deep_de(C.Structure):
+    _fields_ = [("de", C.c_void_p), ("deriv", C.c_void_p), ("shade", C.c_int32), ("edge_px", C.c_float)]
+
+
 class fr_deepx_view(C.Structure):
     _fields_ = [("center_x", C.c_char_p), ("center_y", C.c_char_p), ("zoom", C.c_char_p), ("frac_bits", C.c_int32),
                 ("reserved", C.c_int32)]
@@ -149,6 +153,12 @@ SIGNATURES = {
                                  _P(fr_output)]),
     "fr_render_deep_async": (C.c_int, [C.c_void_p, _P(fr_params), _P(fr_deep_view), C.c_uint32, C.c_uint32, _P(fr_shard),
                                        _P(fr_output), C.c_void_p]),
+    "fr_deep_de_default": (C.c_int, [_P(fr_deep_de)]),
+    "fr_deep_de_validate": (C.c_int, [_P(fr_params), _P(fr_deep_view), _P(fr_deep_de), C.c_uint32, C.c_uint32]),
+    "fr_render_deep_de": (C.c_int, [C.c_void_p, _P(fr_params), _P(fr_deep_view), _P(fr_deep_de), C.c_uint32, C.c_uint32,
+                                    _P(fr_shard), _P(fr_output)]),
+    "fr_render_deep_de_async": (C.c_int, [C.c_void_p, _P(fr_params), _P(fr_deep_view), _P(fr_deep_de), C.c_uint32, C.c_uint32,
+                                          _P(fr_shard), _P(fr_output), C.c_void_p]),
     "fr_deep_ship_reference_orbit": (C.c_int, [_P(fr_deep_view), C.c_double, C.c_int32, C.c_float, C.c_void_p,
                                                _P(C.c_int32)]),
     "fr_render_deep_ship": (C.c_int, [C.c_void_p, _P(fr_params), _P(fr_deep_view), C.c_uint32, C.c_uint32, _P(fr_shard),

@@ -517,6 +517,27 @@ int fr_deep_validate(const fr_params* p, const fr_deep_view* v, uint32_t width, 
     return parse_centre(v, fmt, cr, ci);
 }
 
+int fr_deep_de_default(fr_deep_de* e)
+{
+    if (!e) return fr_set_error(FR_ERR_INVALID_ARG, "fr_deep_de is NULL");
+    e->de = NULL;
+    e->deriv = NULL;
+    e->shade = 0;
+    e->edge_px = 1.8f;                           /* 0.005 c-plane units (mandelbrot_debug.comp:196) at zoom 3.0 on 1080 rows */
+    return FR_OK;
+}
+
+int fr_deep_de_validate(const fr_params* p, const fr_deep_view* v, const fr_deep_de* e, uint32_t width, uint32_t height)
+{
+    if (!e) return fr_set_error(FR_ERR_INVALID_ARG, "fr_deep_de is NULL");
+    const int st = fr_deep_validate(p, v, width, height);
+    if (st != FR_OK) return st;
+    if (e->shade != 0 && e->shade != 1) return fr_set_error(FR_ERR_INVALID_ARG, "fr_deep_de.shade %d is neither 0 nor 1", e->shade);
+    if (e->shade == 1 && (!isfinite(e->edge_px) || !(e->edge_px > 0.0f)))
+        return fr_set_error(FR_ERR_INVALID_ARG, "fr_deep_de.edge_px must be finite and > 0 with shade 1");
+    return FR_OK;
+}
+
 int fr_deep_parse_fixed(const char* s, int32_t frac_bits, uint64_t* out, int32_t nlimbs)
 {
     if (!s || !out) return fr_set_error(FR_ERR_INVALID_ARG, "fr_deep_parse_fixed: NULL argument");

@@ -46,11 +46,16 @@
  *     offset bla_offset(N - 1, k)), the radius r of every entry in an array of its own -- a double, or an XRad -- and
  *     (A, B) as F::kAbPerEntry double2 per entry (2: complex A, B; 4: the rows of the ship's real matrices; 1: Julia's A), the
  *     extended tables with their two exponents in an int2 (Julia: A's in an int32).
- *   - deep_kernel<ARGS>, one kernel body for the twelve argument blocks: a persistent grid of the resident set pulls runs of
+ *   - deep_kernel<ARGS>, one kernel body for the fourteen argument blocks: a persistent grid of the resident set pulls runs of
  *     8x8 sub-tiles from the sharded WaveQueue with unlimited stealing (deep views have very uneven iteration counts); one
  *     lane per sample, the aa x aa samples of a pixel one after the other in the lane; dc through the formula's viewport
  *     map, one dispatch on (extended, BLA) to the loop, then the colour stage of the formula's fp64 path: shade() and
  *     post_chain() of fr_kernels.hip.h on (i, r2).
+ *   - the distance estimate (fr_render_deep_de; DeepDeArgs, DeepDeBlaArgs): a compile-time option DE of deep_orbit and
+ *     deep_orbit_bla for the Mandelbrot formula carries D = dz/dc * s, s = zoom / H one pixel spacing, next to the delta --
+ *     D' = 2 z D + s in a plain step, D' = A D + B s in a BLA step, nothing in a rebase -- and feeds nothing back: (i, r2) and
+ *     the step counts are those of the loops without it.  Four live VGPRs and, per plain update, 11 fp64 operations.  The
+ *     kernel turns (r2, D) of an escaped sample into |z| log|z| / |D| and, on request, the debug shader's distance shading.
  */
 #pragma once
 #include "fr_kernels.hip.h"
@@ -105,6 +110,22 @@ struct BlaXTable {
 
 struct DeepBlaArgs {
     DeepArgs d;
+    BlaTable t;
+};
+
+/* fr_render_deep_de: fr_render_deep with the scaled derivative D = dz/dc * s carried next to the delta */
+struct DeepDeArgs {
+    DeepArgs d;
+    double s;                            /* zoom / H of the whole frame: one pixel spacing */
+    double* de;                          /* distance estimate of sample (0,0), in pixel spacings */
+    double* deriv;                       /* (D.x, D.y) of sample (0,0) at its escaping update: two doubles per pixel, a caller's
+                                          * plane with no more than a double's alignment */
+    int32_t shade;                       /* 1: the debug shader's distance shading on every escaped sub-sample */
+    float edge_px;                       /* ... its smoothstep's upper edge, in pixel spacings */
+};
+
+struct DeepDeBlaArgs {
+    DeepDeArgs e;
     BlaTable t;
 };
 
@@ -264,6 +285,11 @@ __device__ __forceinline__ double ship_fold_x(const double X, const int s, const
     return X >= 0.0 ? up : dn;
 }
 
+/* fr_render_deep_de: D' stays where the step forms it.  Left alone the compiler sinks the whole update behind the trip's
+ * escape and rebase branches (nothing in them reads D) and keeps the old dz and Z_m alive, in eight registers of their own, to
+ * form it there. */
+__device__ __forceinline__ void deep_pin_d(double2& D) { asm volatile("" : "+v"(D.x), "+v"(D.y)); }
+
 /* ---- the formula policies ------------------------------------------------------------------------------------------------
  * What a policy hands to the shared code, all by value (small structs in registers). */
 struct StepLin { double tx, ty, fx, fy; };          /* the plain step: dz' = t * f + dc, a complex product */
@@ -308,6 +334,15 @@ struct MandelFormula {
                                                   const double dzy, const double dcx, const double dcy)
     {
         const double2 a = T.ab[2 * e], b = T.ab[2 * e + 1];
+        return make_double2((a.x * dzx - a.y * dzy) + (b.x * dcx - b.y * dcy), (a.x * dzy + a.y * dzx) + (b.x * dcy + b.y * dcx));
+    }
+    /* bla() with the derivative of the map it applies, from the one load of (A, B): D' = A D + B s */
+    static __device__ __forceinline__ double2 bla_d(const BlaTable& T, const uint32_t e, const double dzx, const double dzy,
+                                                    const double dcx, const double dcy, const double s, double2& D)
+    {
+        const double2 a = T.ab[2 * e], b = T.ab[2 * e + 1];
+        D = make_double2((a.x * D.x - a.y * D.y) + b.x * s, (a.x * D.y + a.y * D.x) + b.y * s);
+        deep_pin_d(D);
         return make_double2((a.x * dzx - a.y * dzy) + (b.x * dcx - b.y * dcy), (a.x * dzy + a.y * dzx) + (b.x * dcy + b.y * dcx));
     }
     static __device__ __forceinline__ BlaStepX bla_x(const BlaXTable& T, const uint32_t e, const double qx, const double qy,
@@ -554,6 +589,18 @@ __device__ __forceinline__ double2 deep_step(const double Zx, const double Zy, c
     const StepLin l = F::lin(Zx, Zy, dzx, dzy);
     if constexpr (F::kTwoOrbits) return make_double2(l.tx * l.fx - l.ty * l.fy, l.tx * l.fy + l.ty * l.fx);
     else return make_double2((l.tx * l.fx - l.ty * l.fy) + dcx, (l.tx * l.fy + l.ty * l.fx) + dcy);
+}
+
+/* The derivative's plain step (fr_render_deep_de), at the sample's point before the update: z = Z_m + dz is the sum the previous
+ * trip's escape test formed (0 at the start, dz itself behind a rebase: Z_0 = 0), formed again here so that it is not live
+ * across the trip; w = z + z; D' = ((w.x D.x - w.y D.y) + s, w.x D.y + w.y D.x) */
+__device__ __forceinline__ void deep_step_d(const double Zx, const double Zy, const double dzx, const double dzy, const double s,
+                                            double2& D)
+{
+    const double zx = Zx + dzx, zy = Zy + dzy;
+    const double wx = zx + zx, wy = zy + zy;
+    D = make_double2((wx * D.x - wy * D.y) + s, wx * D.y + wy * D.x);
+    deep_pin_d(D);
 }
 
 /* The extended step (the header's EXTENDED step): dz' = (n.x, n.y, en), not normalised */
@@ -859,9 +906,10 @@ __device__ __forceinline__ BlaHitX bla_probe_x(const XRad* tr, const uint32_t n1
  * The wave's 64 samples, one per lane.  live = false: a lane without a sample (outside the frame).  esc = the loop index
  * of the escaping update (max_iter if none), r2 = |z|^2 there.  z = Z_{m+1} + dz' with the signed orbit point for either
  * formula (Z_0 = 0: at m = 0 the ship's step is (|dz.x| + i |dz.y|)^2 + dc). */
-template <class F>
+template <class F, bool DE = false>
 __device__ __forceinline__ void deep_orbit(const DeepArgs& A, const JuliaStart J, const double dcx, const double dcy,
-                                           const double2 z1, bool live, int& esc, double& er2)
+                                           const double2 z1, bool live, int& esc, double& er2, const double s = 0.0,
+                                           double2* const Dout = nullptr)
 {
     const double2* __restrict__ orbit = A.orbit;
     const int max_iter = A.max_iter;
@@ -880,10 +928,12 @@ __device__ __forceinline__ void deep_orbit(const DeepArgs& A, const JuliaStart J
     int m = 0;
     esc = max_iter;
     er2 = 0.0;
+    double2 D = make_double2(0.0, 0.0);                          /* DE: dz/dc * s, through the escaping update */
     for (int i = 0; i < max_iter; ++i) {
         if (__builtin_amdgcn_ballot_w64(live) == 0ull) break;
         if (!live) continue;
         const double2 Znn = orbit[base + (m + 2 <= N ? m + 2 : N)];   /* Z_{m+2}, for the next step (m + 1 < N) */
+        if constexpr (DE) deep_step_d(Zx, Zy, dzx, dzy, s, D);
         const double2 n = deep_step<F>(Zx, Zy, dzx, dzy, dcx, dcy);
         const double nx = n.x, ny = n.y;
         ++m;
@@ -900,16 +950,19 @@ __device__ __forceinline__ void deep_orbit(const DeepArgs& A, const JuliaStart J
             Zx = Znx; Zy = Zny; Znx = Znn.x; Zny = Znn.y;
         }
     }
+    if constexpr (DE) *Dout = D;
 }
 
 /* deep_orbit with BLA: u replaces the loop index.  A lane probes the table (bla_probe) and takes the level it finds, else
  * the plain step.  A BLA lane loads Z_m and Z_{m+1} at its new m (the Z_{m+2} prefetch is for the plain step); BLA and plain
  * lanes of a wave take their steps in the same trip.  nplain / nbla: the steps this sample took.  Two orbits (J, levels_p and
- * base_p of P's table): the lane's orbit base, N, and its table's entry base, n1 and K are P's until the first rebase. */
-template <class F>
+ * base_p of P's table): the lane's orbit base, N, and its table's entry base, n1 and K are P's until the first rebase.
+ * DE: a BLA step takes D through the derivative of the linear map it applies, from the (A, B) it loads anyway (F::bla_d). */
+template <class F, bool DE = false>
 __device__ __forceinline__ void deep_orbit_bla(const DeepArgs& A, const BlaTable& T, const JuliaStart J, const int levels_p,
                                                const uint32_t base_p, const double dcx, const double dcy, const double2 z1,
-                                               bool live, int& esc, double& er2, uint32_t& nplain, uint32_t& nbla)
+                                               bool live, int& esc, double& er2, uint32_t& nplain, uint32_t& nbla,
+                                               const double s = 0.0, double2* const Dout = nullptr)
 {
     const double2* __restrict__ orbit = A.orbit;
     const double* __restrict__ tr = T.r;
@@ -932,6 +985,7 @@ __device__ __forceinline__ void deep_orbit_bla(const DeepArgs& A, const BlaTable
     esc = max_iter;
     er2 = 0.0;
     nplain = 0u; nbla = 0u;
+    double2 D = make_double2(0.0, 0.0);                          /* DE: dz/dc * s, through the escaping update */
     for (;;) {
         if (__builtin_amdgcn_ballot_w64(live) == 0ull) break;
         if (!live) continue;
@@ -943,13 +997,15 @@ __device__ __forceinline__ void deep_orbit_bla(const DeepArgs& A, const BlaTable
         double Zmx, Zmy;
         int step;
         if (k > 0) {
-            n = F::bla(T, tb + h.e, dzx, dzy, dcx, dcy);
+            if constexpr (DE) n = F::bla_d(T, tb + h.e, dzx, dzy, dcx, dcy, s, D);
+            else n = F::bla(T, tb + h.e, dzx, dzy, dcx, dcy);
             step = 1 << k;
             ++nbla;
             m += step;
             const double2 Zm = orbit[base + m];
             Zmx = Zm.x; Zmy = Zm.y;
         } else {
+            if constexpr (DE) deep_step_d(Zx, Zy, dzx, dzy, s, D);
             n = deep_step<F>(Zx, Zy, dzx, dzy, dcx, dcy);
             step = 1;
             ++nplain;
@@ -980,6 +1036,7 @@ __device__ __forceinline__ void deep_orbit_bla(const DeepArgs& A, const BlaTable
         }
         if (u >= max_iter) live = false;                          /* esc stays max_iter */
     }
+    if constexpr (DE) *Dout = D;
 }
 
 /* deep_orbit in two modes (the header's EXTENDED and PLAIN steps).  (cx, cy, ec) = dc, normalised.  z = Z_{m+1} (+) n with the
@@ -1274,6 +1331,10 @@ __host__ __device__ __forceinline__ const DeepArgs& deep_args(const DeepArgs& A)
 __host__ __device__ __forceinline__ const DeepArgs& deep_args(const DeepXArgs& A) { return A.d; }
 __host__ __device__ __forceinline__ const DeepArgs& deep_args(const DeepBlaArgs& A) { return A.d; }
 __host__ __device__ __forceinline__ const DeepArgs& deep_args(const DeepXBlaArgs& A) { return A.x.d; }
+__host__ __device__ __forceinline__ const DeepArgs& deep_args(const DeepDeArgs& A) { return A.d; }
+__host__ __device__ __forceinline__ const DeepArgs& deep_args(const DeepDeBlaArgs& A) { return A.e.d; }
+__host__ __device__ __forceinline__ const DeepDeArgs& de_args(const DeepDeArgs& A) { return A; }
+__host__ __device__ __forceinline__ const DeepDeArgs& de_args(const DeepDeBlaArgs& A) { return A.e; }
 __host__ __device__ __forceinline__ const DeepArgs& deep_args(const DeepShipArgs& A) { return A.d; }
 __host__ __device__ __forceinline__ const DeepArgs& deep_args(const DeepShipBlaArgs& A) { return A.s.d; }
 __host__ __device__ __forceinline__ const DeepArgs& deep_args(const DeepShipXArgs& A) { return A.x.d; }
@@ -1317,13 +1378,37 @@ __host__ __device__ __forceinline__ TAB& q_table(JuliaTab<TAB>& t) { return t.q;
 template <class TAB>
 __host__ __device__ __forceinline__ const TAB& q_table(const JuliaTab<TAB>& t) { return t.q; }
 
-/* ARGS names the loop: Deep[Ship|Julia][X][Bla]Args = the formula, extended-exponent deltas, BLA (with the step counts) */
+/* The distance estimate of a sample that escaped with r2 and D (fr_render_deep_de): |z| log|z| / |D|, in pixel spacings since D
+ * carries s.  |D| overflowing gives 0 by the division; NaN (D not finite, 0 / 0) becomes 0.  A function of its own, once per
+ * escaped sample: inlined, the library log's polynomial coefficients are hoisted out of every loop of the kernel into twelve
+ * VGPRs that stay live through the orbit loop (107 and 136 VGPRs, a wave per SIMD less in either kernel, against 94 and 123
+ * this way; it uses 21 itself and no stack). */
+__device__ __attribute__((noinline)) double deep_de_of(const double r2, const double2 D)
+{
+    const double dl = sqrt(D.x * D.x + D.y * D.y);
+    const double zl = sqrt(r2);
+    const double de = (zl * log(zl)) / dl;
+    return de != de ? 0.0 : de;
+}
+
+/* mandelbrot_debug.comp:196-197 on a sample's linear rgb, the smoothstep's edge in pixel spacings; fp32 */
+__device__ __forceinline__ void deep_de_shade(float rgb[3], const double de, const float edge_px)
+{
+    const float x = fminf(fmaxf((float)de / edge_px, 0.0f), 1.0f);
+    const float sm = x * x * (3.0f - 2.0f * x);
+    const float t = (1.0f - sm) * 0.3f;
+    for (int c = 0; c < 3; ++c) rgb[c] = rgb[c] * (1.0f - t) + (rgb[c] * 0.7f) * t;
+}
+
+/* ARGS names the loop: Deep[Ship|Julia][X][Bla]Args = the formula, extended-exponent deltas, BLA (with the step counts);
+ * DeepDe[Bla]Args = Deep[Bla]Args with the derivative and its two planes */
 template <class ARGS>
 __global__ void __launch_bounds__(kBlockThreads)
 deep_kernel(const ARGS AA)
 {
     constexpr bool BLA = is_any_of<ARGS, DeepBlaArgs, DeepXBlaArgs, DeepShipBlaArgs, DeepShipXBlaArgs, DeepJuliaBlaArgs,
-                                   DeepJuliaXBlaArgs>;
+                                   DeepJuliaXBlaArgs, DeepDeBlaArgs>;
+    constexpr bool DE = is_any_of<ARGS, DeepDeArgs, DeepDeBlaArgs>;
     constexpr bool X = is_any_of<ARGS, DeepXArgs, DeepXBlaArgs, DeepShipXArgs, DeepShipXBlaArgs, DeepJuliaXArgs,
                                  DeepJuliaXBlaArgs>;
     constexpr bool SHIP = is_any_of<ARGS, DeepShipArgs, DeepShipBlaArgs, DeepShipXArgs, DeepShipXBlaArgs>;
@@ -1356,6 +1441,9 @@ deep_kernel(const ARGS AA)
     const double2 z1 = A.orbit[1];
     const bool want_rgb = A.rgba != nullptr;
     const bool want_nu = want_rgb || A.nu != nullptr;
+    double de_s = 0.0;                                            /* DE: one pixel spacing, wave-uniform */
+    bool de_shade = false;
+    if constexpr (DE) { de_s = de_args(AA).s; de_shade = want_rgb && de_args(AA).shade != 0; }
 
     unsigned long long n_plain = 0ull, n_bla = 0ull, n_upd = 0ull;   /* BLA: this lane's steps and updates */
     int levels_p = 0;                                             /* BLA on two orbits: P's table */
@@ -1372,7 +1460,12 @@ deep_kernel(const ARGS AA)
             const double2 dc = F::dc(px, py, s, aa, resx, resy, zs);
             double cx = inside ? dc.x : 0.0, cy = inside ? dc.y : 0.0;
             uint32_t np = 0u, nb = 0u;
-            if constexpr (X) {
+            double2 D = make_double2(0.0, 0.0);
+            if constexpr (DE) {
+                if constexpr (BLA)
+                    deep_orbit_bla<F, true>(A, AA.t, julia_start(AA), levels_p, base_p, cx, cy, z1, inside, esc, r2, np, nb, de_s, &D);
+                else deep_orbit<F, true>(A, julia_start(AA), cx, cy, z1, inside, esc, r2, de_s, &D);
+            } else if constexpr (X) {
                 int ec = deepx_args(AA).ze;
                 x_norm(cx, cy, ec);
                 if constexpr (BLA)
@@ -1388,10 +1481,26 @@ deep_kernel(const ARGS AA)
                 n_plain += np; n_bla += nb;
                 n_upd += (unsigned long long)(esc < A.max_iter ? esc + 1 : A.max_iter);
             }
+            /* DE: the planes of sample (0,0) at once and in front of the colour stage, deriv first: nothing of them stays live
+             * through the colour stage or the samples that follow */
+            double de = 0.0;
+            if constexpr (DE) {
+                const bool escaped = esc < A.max_iter;            /* interior: 0 and (0, 0) */
+                const bool first = s == 0 && inside;
+                if (first && de_args(AA).deriv) {
+                    double* const dst = de_args(AA).deriv + 2 * plane_index(A.g, px, py, lrow);
+                    dst[0] = escaped ? D.x : 0.0; dst[1] = escaped ? D.y : 0.0;
+                }
+                if (escaped && (s == 0 || de_shade)) de = deep_de_of(r2, D);
+                if (first && de_args(AA).de) de_args(AA).de[plane_index(A.g, px, py, lrow)] = de;
+            }
             double nu;
             float rgb[3];
             shade<double, FRACTAL>(A, S, lg, esc, r2, want_nu, want_rgb, nu, rgb);
             if (s == 0) { nu0 = nu; it0 = esc; }
+            if constexpr (DE) {
+                if (de_shade && esc < A.max_iter) deep_de_shade(rgb, de, de_args(AA).edge_px);
+            }
             acc[0] += rgb[0]; acc[1] += rgb[1]; acc[2] += rgb[2];
         }
         if (aa > 1) {

@@ -135,6 +135,8 @@ struct fr_ctx {
                                  * doubles, the mantissa pairs, the exponents, in this order. */
     BlaSlot bla[3];             /* FR_FLAG_DEEP_BLA, FR_FLAG_DEEP_SHIP_BLA, FR_FLAG_DEEP_JULIA_BLA: the tables of deep[] */
     BlaSlot blax[3];            /* FR_FLAG_DEEPX_BLA, FR_FLAG_DEEPX_SHIP_BLA, FR_FLAG_DEEPX_JULIA_BLA: the tables of deepx[] */
+    int deep_de_wg_per_cu[2];   /* fr_render_deep_de reads deep[kMandel] and bla[kMandel]; its kernels have their own resident
+                                 * sets: deep_kernel<DeepDeArgs> / <DeepDeBlaArgs> (0 = not asked yet) */
 };
 
 #define FR_HIP_TRY(expr)                                                               \
@@ -926,9 +928,11 @@ static DeepArgs& deep_of(ARGS& a) { return const_cast<DeepArgs&>(deep_args(a)); 
 /* One pass of a deep view, `base` being the argument block of its unflagged kernel: deep_kernel<BASE> at the occupancy cached in
  * wg_per_cu, or with `bla` the table, then deep_kernel<BLA> (BLA = {BASE, the table}) on the same queue plan at its slot's own
  * occupancy, its counters cleared in front of it and copied to pinned memory behind it.  The slot's event is recorded behind
- * every such render unless the stream is capturing: table rebuilds and orbit uploads wait for it. */
+ * every such render unless the stream is capturing: table rebuilds and orbit uploads wait for it.  bla_wg_per_cu: the occupancy
+ * word of a flagged kernel that shares its slot with another (fr_render_deep_de). */
 template <class BLA, class BASE>
-static int launch_deep(fr_ctx* c, hipStream_t stream, const char* name, const char* bla_name, BASE& base, bool bla, int& wg_per_cu)
+static int launch_deep(fr_ctx* c, hipStream_t stream, const char* name, const char* bla_name, BASE& base, bool bla, int& wg_per_cu,
+                       int* bla_wg_per_cu = nullptr)
 {
     if (!bla) {
         DeepArgs& d = deep_of(base);
@@ -958,7 +962,8 @@ static int launch_deep(fr_ctx* c, hipStream_t stream, const char* name, const ch
     }
     tab.steps = t.steps_dev;
     FR_HIP_TRY(hipMemsetAsync(t.steps_dev, 0, 3 * sizeof(unsigned long long), stream));
-    const int st = launch_one_pass(c, stream, bla_name, deep_kernel<BLA>, a, d.g, d.q, t.wg_per_cu, false);
+    const int st = launch_one_pass(c, stream, bla_name, deep_kernel<BLA>, a, d.g, d.q, bla_wg_per_cu ? *bla_wg_per_cu : t.wg_per_cu,
+                                   false);
     if (st != FR_OK) return st;
     FR_HIP_TRY(hipMemcpyAsync(t.steps_host, t.steps_dev, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
     t.have_steps = true;
@@ -1015,6 +1020,32 @@ static int enqueue_deep(fr_ctx* c, int f, const fr_params* p, const fr_deep_view
                                             (p->flags & FR_FLAG_DEEP_SHIP_BLA) != 0, o.wg_per_cu);
     return launch_deep<DeepBlaArgs>(c, stream, "deep_kernel<DeepArgs>", "deep_kernel<DeepBlaArgs>", a,
                                     (p->flags & FR_FLAG_DEEP_BLA) != 0, o.wg_per_cu);
+}
+
+/* fr_render_deep_de: enqueue_deep's Mandelbrot path -- its orbit slot, its table, its step counts -- with the derivative's
+ * argument block around DeepArgs.  s = zoom / H of the whole frame, whatever rows this part owns. */
+static int enqueue_deep_de(fr_ctx* c, const fr_params* p, const fr_deep_view* v, const fr_deep_de* e, uint32_t W, uint32_t H,
+                           const fr_shard* shard, float* rgba, void* nu, int32_t* iter, double* de, double* deriv,
+                           hipStream_t stream, bool out_frame)
+{
+    fr_shard norm;
+    uint32_t rows_local = 0;
+    const int sh = begin_shard(c, shard, H, &norm, &rows_local);
+    if (sh != FR_OK || rows_local == 0) return sh;
+    const int os = orbit_slot_fill(c, kMandel, p, v, stream);
+    if (os != FR_OK) return os;
+
+    DeepOrbit& o = c->deep[kMandel];
+    DeepDeArgs a;
+    memset(&a, 0, sizeof(a));
+    a.d.orbit = reinterpret_cast<const double2*>(o.dev); a.d.n_ref = o.len - 1;
+    a.d.zoom = p->zoom;
+    fill_deep_args(a.d, c, p, tile_geom(W, H, rows_local, &norm, out_frame), rgba, nu, iter);
+    a.s = p->zoom / (double)H;
+    a.de = de; a.deriv = deriv;
+    a.shade = e->shade; a.edge_px = e->edge_px;
+    return launch_deep<DeepDeBlaArgs>(c, stream, "deep_kernel<DeepDeArgs>", "deep_kernel<DeepDeBlaArgs>", a,
+                                      (p->flags & FR_FLAG_DEEP_BLA) != 0, c->deep_de_wg_per_cu[0], &c->deep_de_wg_per_cu[1]);
 }
 
 /* ---- extended views (fr_render_deepx, fr_render_deepx_ship) -----------------------------------------------------------
@@ -1605,7 +1636,7 @@ static int enqueue_ssaa_staged(fr_ctx* c, const fr_params* p, uint32_t W, uint32
 
 /* ---- render entry points --------------------------------------------------------------------------------------------
  * fr_render_shard, fr_render_phoenix, fr_render_mandelbulb, fr_render_deep, fr_render_deep_ship, fr_render_deepx and
- * fr_render_deepx_ship, each with its _async form:
+ * fr_render_deepx_ship, each with its _async form (fr_render_deep_de has two planes more and its own two functions):
  * their parameter checks, then render_sync / render_async with the enqueue step as
  * enqueue(shard, rgba, nu, iter, stream, out_frame) */
 static int check_common(fr_ctx* c, const fr_params* p, uint32_t W, uint32_t H, const fr_output* out)
@@ -1987,6 +2018,82 @@ extern "C" int fr_render_deep(fr_ctx* c, const fr_params* p, const fr_deep_view*
     if (st != FR_OK) return st;
     return render_sync(c, p, W, H, shard, out, [&](auto sh, auto rgba, auto nu, auto iter, auto s, bool out_frame) {
         return enqueue_deep(c, kMandel, p, v, W, H, sh, rgba, nu, iter, s, out_frame); });
+}
+
+/* fr_render_deep_de: render_async / render_sync with five planes -- de and deriv follow out->memory and out->layout as nu
+ * does, and any one plane is enough */
+static int check_deep_de(fr_ctx* c, const fr_params* p, const fr_deep_view* v, const fr_deep_de* e, uint32_t W, uint32_t H,
+                         const fr_output* out)
+{
+    if (!c) return fr_set_error(FR_ERR_INVALID_ARG, "ctx is NULL");
+    if (!p || !v || !e || !out) return fr_set_error(FR_ERR_INVALID_ARG, "params/deep view/de/out is NULL");
+    return fr_deep_de_validate(p, v, e, W, H);
+}
+
+/* 1: this part owns rows and has a plane to write; 0: it owns no rows; < 0: error */
+static int check_planes_de(const fr_shard* shard, uint32_t H, const fr_output* out, const fr_deep_de* e)
+{
+    if (shard && shard->nparts && shard->part >= shard->nparts)
+        return fr_set_error(FR_ERR_INVALID_ARG, "shard part %u >= nparts %u", shard->part, shard->nparts);
+    if (fr_shard_rows(shard, H) == 0) return 0;
+    if (!out->rgba && !out->nu && !out->iter && !e->de && !e->deriv)
+        return fr_set_error(FR_ERR_INVALID_ARG, "fr_render_deep_de: neither fr_output nor fr_deep_de has a plane to write");
+    return 1;
+}
+
+extern "C" int fr_render_deep_de_async(fr_ctx* c, const fr_params* p, const fr_deep_view* v, const fr_deep_de* e, uint32_t W,
+                                       uint32_t H, const fr_shard* shard, const fr_output* out, void* hip_stream)
+{
+    int st = check_deep_de(c, p, v, e, W, H, out);
+    if (st != FR_OK) return st;
+    if ((st = check_layout(out)) != FR_OK) return st;
+    if (out->memory != FR_MEM_DEVICE) return fr_set_error(FR_ERR_INVALID_ARG, "fr_render_deep_de_async needs FR_MEM_DEVICE outputs");
+    st = check_planes_de(shard, H, out, e);
+    if (st <= 0) return st;
+    FR_HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    st = enqueue_deep_de(c, p, v, e, W, H, shard, out->rgba, out->nu, out->iter, e->de, e->deriv, s, out->layout == FR_LAYOUT_FRAME);
+    if (st == FR_OK) c->render_on_user_stream = s != c->stream;
+    return st;
+}
+
+extern "C" int fr_render_deep_de(fr_ctx* c, const fr_params* p, const fr_deep_view* v, const fr_deep_de* e, uint32_t W, uint32_t H,
+                                 const fr_shard* shard, const fr_output* out)
+{
+    int st = check_deep_de(c, p, v, e, W, H, out);
+    if (st != FR_OK) return st;
+    if ((st = check_layout(out)) != FR_OK) return st;
+    st = check_planes_de(shard, H, out, e);
+    if (st <= 0) return st;
+    FR_HIP_TRY(hipSetDevice(c->device));
+    const bool host = out->memory == FR_MEM_HOST;
+    if (!host && out->memory != FR_MEM_DEVICE) return fr_set_error(FR_ERR_INVALID_ARG, "unknown fr_output.memory %d", out->memory);
+    float* rgba = out->rgba; void* nu = out->nu; int32_t* iter = out->iter;
+    double* de = e->de; double* deriv = e->deriv;
+    const size_t npx = (size_t)fr_shard_rows(shard, H) * W;
+    if (host) {                                  /* staged like the other planes: rgba 16, deriv 16, nu 8, de 8, iter 4 bytes */
+        const size_t off_deriv = npx * 16, off_nu = off_deriv + npx * 16, off_de = off_nu + npx * 8, off_iter = off_de + npx * 8;
+        const int gs = grow_device(&c->scratch, &c->scratch_bytes, off_iter + npx * 4);
+        if (gs != FR_OK) return gs;
+        char* base = (char*)c->scratch;
+        rgba = out->rgba ? (float*)base : nullptr;
+        deriv = e->deriv ? (double*)(base + off_deriv) : nullptr;
+        nu = out->nu ? (void*)(base + off_nu) : nullptr;
+        de = e->de ? (double*)(base + off_de) : nullptr;
+        iter = out->iter ? (int32_t*)(base + off_iter) : nullptr;
+    }
+    st = enqueue_deep_de(c, p, v, e, W, H, shard, rgba, nu, iter, de, deriv, c->stream, out->layout == FR_LAYOUT_FRAME);
+    if (st != FR_OK) return st;
+    c->render_on_user_stream = false;
+    if (host) {
+        if (out->rgba) FR_HIP_TRY(hipMemcpyAsync(out->rgba, rgba, npx * 16, hipMemcpyDeviceToHost, c->stream));
+        if (e->deriv) FR_HIP_TRY(hipMemcpyAsync(e->deriv, deriv, npx * 16, hipMemcpyDeviceToHost, c->stream));
+        if (out->nu) FR_HIP_TRY(hipMemcpyAsync(out->nu, nu, npx * 8, hipMemcpyDeviceToHost, c->stream));
+        if (e->de) FR_HIP_TRY(hipMemcpyAsync(e->de, de, npx * 8, hipMemcpyDeviceToHost, c->stream));
+        if (out->iter) FR_HIP_TRY(hipMemcpyAsync(out->iter, iter, npx * 4, hipMemcpyDeviceToHost, c->stream));
+    }
+    FR_HIP_TRY(hipStreamSynchronize(c->stream));
+    return check_overflow(c);
 }
 
 static int check_deep_ship(fr_ctx* c, const fr_params* p, const fr_deep_view* v, uint32_t W, uint32_t H, const fr_output* out)

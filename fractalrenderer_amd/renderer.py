@@ -21,6 +21,9 @@ from . import _capi
 from .state import DeepView, FractalState, FractalType, MandelbulbParams, PhoenixParams, Precision
 
 
+DEEP_DE_EDGE_PX = 1.8     # fr_deep_de_default's edge_px: 0.005 c-plane units at zoom 3.0 on 1080 rows
+
+
 class DeepSteps(NamedTuple):
     """fr_ctx_last_deep_steps: the steps of a deep render with BLA"""
     plain: int          # plain perturbation steps
@@ -289,6 +292,48 @@ class Renderer:
         v = (view or DeepView()).to_c()
         self._render_call(self._lib.fr_render_deep, self._lib.fr_render_deep_async, (C.byref(p), C.byref(v)), width, height,
                           Precision.F64, rows, rgba, nu, iter, shard, stream, sync)
+
+    def render_deep_de(self, state: FractalState, width: int, height: int, view: Optional[DeepView] = None, *,
+                       post_chain: bool = False, rgba=None, nu=None, iter=None, de=None, deriv=None, shade: bool = False,
+                       edge_px: float = DEEP_DE_EDGE_PX, shard: Optional[Shard] = None, stream: Optional[int] = None,
+                       sync: bool = True, bla: bool = False) -> None:
+        """fr_render_deep_de / fr_render_deep_de_async: render_deep() with the derivative dz/dc carried through the
+        perturbation loop and two planes more.  de: rows*W float64, the exterior distance estimate of sample (0,0) in pixel
+        spacings of the whole frame (0 for interior); deriv: rows*W*2 float64, (D.x, D.y) = dz/dc * (zoom / H) at the escaping
+        update.  Any one of the five planes is enough; all of them are host or all device memory.  shade=True applies the
+        debug shader's distance shading to every escaped sub-sample (edge_px: the smoothstep's upper edge in pixel spacings);
+        without it rgba is render_deep()'s.  iter, nu and last_deep_steps() are render_deep()'s, and the context's orbit and
+        BLA table are shared with it.  bla=True sets FR_FLAG_DEEP_BLA.  A view with a zoom string is a ValueError: below
+        1e-290 the derivative needs an exponent of its own."""
+        if view is not None and view.zoom is not None:
+            raise ValueError("render_deep_de takes the zoom from the state: extended views (a zoom string) have no distance estimate")
+        p = state.to_params(FractalType.Mandelbrot, Precision.F64, post_chain)
+        if bla:
+            p.flags |= _capi.FR_FLAG_DEEP_BLA
+        v = (view or DeepView()).to_c()
+        rows = shard.rows(height) if shard else height
+        out = self._output(Precision.F64, rows, width, rgba, nu, iter)
+        e = _capi.fr_deep_de(None, None, 1 if shade else 0, float(edge_px))
+        kinds = set()
+        for name, x, n in (("de", de, rows * width), ("deriv", deriv, rows * width * 2)):
+            ptr, kind = Renderer._ptr(x, "float64", n, name)
+            setattr(e, name, ptr)
+            if kind:
+                kinds.add(kind)
+        if rgba is not None or nu is not None or iter is not None:
+            kinds.add("device" if out.memory == _capi.FR_MEM_DEVICE else "host")
+        if len(kinds) > 1:
+            raise ValueError("output planes must all be host or all be device memory")
+        out.memory = _capi.FR_MEM_DEVICE if kinds == {"device"} else _capi.FR_MEM_HOST
+        sh = shard.to_c() if shard else None
+        shp = C.byref(sh) if sh is not None else None
+        if sync:
+            if stream is not None:
+                raise ValueError("stream is only meaningful with sync=False")
+            _capi.check(self._lib.fr_render_deep_de(self._ctx, C.byref(p), C.byref(v), C.byref(e), width, height, shp, C.byref(out)))
+        else:
+            _capi.check(self._lib.fr_render_deep_de_async(self._ctx, C.byref(p), C.byref(v), C.byref(e), width, height, shp,
+                                                          C.byref(out), C.c_void_p(stream or 0)))
 
     def render_deep_ship(self, state: FractalState, width: int, height: int, view: Optional[DeepView] = None, *,
                          post_chain: bool = False, rgba=None, nu=None, iter=None, shard: Optional[Shard] = None,

@@ -516,6 +516,67 @@ int fr_render_deep_async(fr_ctx* ctx, const fr_params* p, const fr_deep_view* vi
  * FR_ERR_UNSUPPORTED if there is no such call. */
 int fr_ctx_last_deep_steps(fr_ctx* ctx, uint64_t out[3]);
 
+/* ---- distance estimates for deep Mandelbrot views ---------------------------------------------------------------------------
+ * At depth the filaments of the set are far thinner than a pixel and the smooth count of a frame is noise (view C of the tests,
+ * a 1e-50 minibrot neighbourhood: the median escaped pixel lies 0.005 pixel spacings from the set).  fr_render_deep_de is
+ * fr_render_deep with the derivative dz/dc carried through the perturbation loop, its rebases and its BLA steps, and two planes
+ * more: the exterior distance estimate |z| log|z| / |dz/dc| of shaders/mandelbrot_debug.comp:106-148, and the derivative
+ * itself.  Range, view, orbit and flags are fr_render_deep's: Mandelbrot, FR_PRECISION_F64, zoom in [1e-290, 1e3], plain or
+ * with FR_FLAG_DEEP_BLA.  fr_render_deep and every other entry point are untouched.
+ *
+ * The arithmetic (fp64, one rounding per operation as written, no contraction), next to fr_render_deep's step above:
+ *   - s = zoom / H, H the height of the WHOLE frame (never a shard's rows): one pixel spacing.  D = (0, 0) at the start.
+ *     D is dz/dc * s: scaled so that it stays in range down to zoom 1e-290 (s ~ 1e-292, where dz/dc itself reaches 1e292 and
+ *     more before a sample escapes) and so that |D| at escape is about 1 / de with de in pixel spacings.
+ *   - Plain step: D' is formed in every trip, from the sample's point before the update,
+ *       z = Z_m + dz   (the sum the previous trip's escape test formed; (0, 0) at the start; dz itself behind a rebase, Z_0 = 0)
+ *       w = z + z;   D' = ((w.x D.x - w.y D.y) + s,  w.x D.y + w.y D.x)
+ *   - BLA step with the entry (A, B) the sample takes: D' = ((A.x D.x - A.y D.y) + B.x s,  (A.x D.y + A.y D.x) + B.y s),
+ *     the derivative of the linear map dz' = A dz + B dc that the step applies -- exact for that map, whatever the map drops.
+ *   - A rebase leaves D alone: the point does not move.
+ *   - Escape with r2:  zl = sqrt(r2);  dl = sqrt(D.x D.x + D.y D.y);  de = (zl * log(zl)) / dl;  a NaN de becomes 0; an
+ *     overflowing |D| gives 0 by the division.  log is the device library's (within 1 ulp), sqrt is correctly rounded.
+ *   - Interior samples (iter == max_iterations): de = 0, deriv = (0, 0).
+ * D never feeds back: iter, nu, r2 and the three step counts are bit for bit fr_render_deep's for the same parameters.
+ *
+ * Shading (shade == 1), mandelbrot_debug.comp:196-197 with the edge in pixels, in fp32 on every ESCAPED sub-sample's linear rgb,
+ * before the aa average and before FR_FLAG_POST_CHAIN (interior samples are not shaded: the shader returns before them):
+ *   x = clamp((float)de / edge_px, 0, 1);  sm = x*x*(3 - 2x);  t = (1 - sm) * 0.3f;  rgb = rgb*(1 - t) + (rgb*0.7f)*t
+ *
+ * Planes: de->de and de->deriv follow out->memory and out->layout exactly as out->nu does (FR_MEM_HOST stages them like the
+ * other planes).  Of the five planes rgba, nu, iter, de, deriv at least one must be given; rgba is not required.
+ * Shared state: the orbit cache slot, the BLA table with its key, and fr_ctx_last_deep_steps are fr_render_deep's own -- a
+ * call here after fr_render_deep of the same view computes no orbit and builds no table, and the reverse.
+ * Validation: everything fr_render_deep checks; `de` NULL, shade outside {0, 1}, or shade == 1 with edge_px not finite or
+ * <= 0 is FR_ERR_INVALID_ARG.
+ * Cost: four live VGPRs and 11 fp64 operations per plain update on top of the step's 18 (README: measured).
+ * Out of scope: extended views below 1e-290 (s underflows there and D needs an exponent of its own); the Burning Ship, which
+ * needs a real 2x2 Jacobian; Julia sets; fr_deep_sequence; fr_node and .franim; slope or normal lighting -- deriv is what a
+ * caller needs for it. */
+#define FR_HAS_DEEP_DE 1
+
+typedef struct fr_deep_de {
+    double* de;       /* rows*W: distance estimate of sample (0,0), in PIXEL SPACINGS of the whole frame (zoom / H); 0 for
+                       * interior.  NULL to skip */
+    double* deriv;    /* rows*W*2: (D.x, D.y) of sample (0,0) at its escaping update, (0,0) for interior.  NULL to skip */
+    int32_t shade;    /* 0: rgba exactly fr_render_deep's; 1: the debug shader's distance shading on every escaped sub-sample */
+    float   edge_px;  /* shade == 1: the smoothstep's upper edge in pixel spacings, finite > 0 */
+} fr_deep_de;         /* 24 bytes on LP64 */
+
+/* NULL, NULL, 0, 1.8f  (0.005 c-plane units, mandelbrot_debug.comp:196, at zoom 3.0 on 1080 rows) */
+int fr_deep_de_default(fr_deep_de* de);
+
+/* What fr_render_deep_de checks of its arguments, the centre strings parsed included (no context needed). */
+int fr_deep_de_validate(const fr_params* p, const fr_deep_view* view, const fr_deep_de* de, uint32_t width, uint32_t height);
+
+/* fr_render_deep with the distance planes; options, timing and the orbit cache as there. */
+int fr_render_deep_de(fr_ctx* ctx, const fr_params* p, const fr_deep_view* view, const fr_deep_de* de, uint32_t width,
+                      uint32_t height, const fr_shard* shard, const fr_output* out);
+
+/* Asynchronous form: fr_render_deep_async's contract, de->de and de->deriv device planes like the others. */
+int fr_render_deep_de_async(fr_ctx* ctx, const fr_params* p, const fr_deep_view* view, const fr_deep_de* de, uint32_t width,
+                            uint32_t height, const fr_shard* shard, const fr_output* out, void* hip_stream);
+
 /* ---- Burning Ship views deeper than double precision ----------------------------------------------------------------------
  * fr_render_deep for z <- (|x| + i |y|)^2 + c: the same perturbation around one reference orbit with rebasing, the same view
  * (fr_deep_view, p->zoom in [1e-290, 1e3], p->center_x / p->center_y ignored), planes, shards and asynchronous rules.  The

@@ -20,6 +20,9 @@
  *
  * Deep Julia views (fr_render_deep_julia, fr_render_deepx_julia): Mandelbrot's recurrence with c from a pair of doubles, twice --
  * from the view's centre (orbit_loop's start point) and from 0 -- in either storage, and the two validators.
+ *
+ * The six paths share one host side: what their validators ask is a row of kRules read by validate_params, either view struct
+ * goes through resolve_view, and the six reference-orbit entry points start with orbit_request.
  */
 #include "fr_internal.h"
 
@@ -433,6 +436,17 @@ int fr_deep_view_default(fr_deep_view* v)
     return FR_OK;
 }
 
+int fr_deepx_view_default(fr_deepx_view* v)
+{
+    if (!v) return fr_set_error(FR_ERR_INVALID_ARG, "deep view is NULL");
+    v->center_x = "-0.5";
+    v->center_y = "0";
+    v->zoom = "3";
+    v->frac_bits = 0;
+    v->reserved = 0;
+    return FR_OK;
+}
+
 int fr_deep_frac_bits(double zoom)
 {
     if (!isfinite(zoom) || !(zoom > 0.0))
@@ -442,17 +456,6 @@ int fr_deep_frac_bits(double zoom)
     if (want > (double)kMaxFracBits) want = kMaxFracBits;
     const int bits = (int)want;
     return (bits + 63) / 64 * 64;
-}
-
-/* the view's F (automatic or given), or < 0 after setting the error */
-static int view_frac_bits(const fr_deep_view* v, double zoom)
-{
-    if (!v) return fr_set_error(FR_ERR_INVALID_ARG, "deep view is NULL");
-    if (v->reserved != 0) return fr_set_error(FR_ERR_INVALID_ARG, "fr_deep_view.reserved must be 0");
-    if (v->frac_bits != 0 && (v->frac_bits < 128 || v->frac_bits > kMaxFracBits))
-        return fr_set_error(FR_ERR_INVALID_ARG, "frac_bits %d outside {0} U [128, 4096]", v->frac_bits);
-    if (!v->center_x || !v->center_y) return fr_set_error(FR_ERR_INVALID_ARG, "deep view centre string is NULL");
-    return v->frac_bits ? v->frac_bits : fr_deep_frac_bits(zoom);
 }
 
 static int check_zoom(double zoom)
@@ -469,11 +472,18 @@ static int check_bailout(float bailout)
     return FR_OK;
 }
 
+static int check_julia_c(double c_re, double c_im)
+{
+    if (!isfinite(c_re) || !isfinite(c_im) || !(fabs(c_re) < 4294967296.0) || !(fabs(c_im) < 4294967296.0))
+        return fr_set_error(FR_ERR_INVALID_ARG, "deep Julia views need a finite c with |c_re|, |c_im| < 2^32");
+    return FR_OK;
+}
+
 /* both centre strings in fixed point; FR_OK or FR_ERR_INVALID_ARG */
-static int parse_centre(const fr_deep_view* v, fx_fmt fmt, uint64_t* cr, uint64_t* ci)
+static int parse_centre(const char* center_x, const char* center_y, fx_fmt fmt, uint64_t* cr, uint64_t* ci)
 {
     const char* which[2] = {"center_x", "center_y"};
-    const char* str[2] = {v->center_x, v->center_y};
+    const char* str[2] = {center_x, center_y};
     uint64_t* dst[2] = {cr, ci};
     for (int k = 0; k < 2; ++k) {
         const int st = parse_fixed(str[k], fmt, dst[k]);
@@ -485,57 +495,11 @@ static int parse_centre(const fr_deep_view* v, fx_fmt fmt, uint64_t* cr, uint64_
     return FR_OK;
 }
 
-/* the Julia tables belong to fr_render_deep_julia / fr_render_deepx_julia: every other deep entry point refuses their flags */
-static int check_no_julia_bla(const char* who, const fr_params* p)
+int fr_deepx_check_centre(const char* center_x, const char* center_y, int32_t frac_bits)
 {
-    if (p->flags & (FR_FLAG_DEEP_JULIA_BLA | FR_FLAG_DEEPX_JULIA_BLA))
-        return fr_set_error(FR_ERR_UNSUPPORTED, "%s: FR_FLAG_DEEP_JULIA_BLA / FR_FLAG_DEEPX_JULIA_BLA are not available (their "
-                            "tables belong to the Julia paths)", who);
-    return FR_OK;
-}
-
-int fr_deep_validate(const fr_params* p, const fr_deep_view* v, uint32_t width, uint32_t height)
-{
-    if (!p || !v) return fr_set_error(FR_ERR_INVALID_ARG, "params/deep view is NULL");
-    if (p->fractal_type != FR_FRACTAL_MANDELBROT)
-        return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deep renders FR_FRACTAL_MANDELBROT only (got %d)", p->fractal_type);
-    if (p->precision != FR_PRECISION_F64)
-        return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deep needs FR_PRECISION_F64 (got %d)", p->precision);
-    fr_params q = *p;                                            /* the double centre is not read */
-    q.center_x = 0.0; q.center_y = 0.0;
-    int st = fr_params_validate(&q, width, height);
-    if (st != FR_OK) return st;
-    if ((st = check_zoom(p->zoom)) != FR_OK || (st = check_bailout(p->bailout)) != FR_OK) return st;
-    if (p->orbit_trap_enabled || p->stripe_enabled || p->interior_style == 2)
-        return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deep: the orbit trap, stripes and interior_style 2 need the whole "
-                            "orbit and are not available");
-    if ((st = check_no_julia_bla("fr_render_deep", p)) != FR_OK) return st;
-    const int F = view_frac_bits(v, p->zoom);
-    if (F < 0) return F;
     uint64_t cr[kMaxLimbs], ci[kMaxLimbs];
-    const fx_fmt fmt = {F, (F + 63) / 64 + 1};
-    return parse_centre(v, fmt, cr, ci);
-}
-
-int fr_deep_de_default(fr_deep_de* e)
-{
-    if (!e) return fr_set_error(FR_ERR_INVALID_ARG, "fr_deep_de is NULL");
-    e->de = NULL;
-    e->deriv = NULL;
-    e->shade = 0;
-    e->edge_px = 1.8f;                           /* 0.005 c-plane units (mandelbrot_debug.comp:196) at zoom 3.0 on 1080 rows */
-    return FR_OK;
-}
-
-int fr_deep_de_validate(const fr_params* p, const fr_deep_view* v, const fr_deep_de* e, uint32_t width, uint32_t height)
-{
-    if (!e) return fr_set_error(FR_ERR_INVALID_ARG, "fr_deep_de is NULL");
-    const int st = fr_deep_validate(p, v, width, height);
-    if (st != FR_OK) return st;
-    if (e->shade != 0 && e->shade != 1) return fr_set_error(FR_ERR_INVALID_ARG, "fr_deep_de.shade %d is neither 0 nor 1", e->shade);
-    if (e->shade == 1 && (!isfinite(e->edge_px) || !(e->edge_px > 0.0f)))
-        return fr_set_error(FR_ERR_INVALID_ARG, "fr_deep_de.edge_px must be finite and > 0 with shade 1");
-    return FR_OK;
+    const fx_fmt fmt = {frac_bits, (frac_bits + 63) / 64 + 1};
+    return parse_centre(center_x, center_y, fmt, cr, ci);
 }
 
 int fr_deep_parse_fixed(const char* s, int32_t frac_bits, uint64_t* out, int32_t nlimbs)
@@ -545,72 +509,14 @@ int fr_deep_parse_fixed(const char* s, int32_t frac_bits, uint64_t* out, int32_t
         return fr_set_error(FR_ERR_INVALID_ARG, "frac_bits %d outside [128, 4096]", frac_bits);
     const fx_fmt fmt = {frac_bits, (frac_bits + 63) / 64 + 1};
     if (nlimbs < fmt.L) return fr_set_error(FR_ERR_INVALID_ARG, "fr_deep_parse_fixed: %d limbs, %d needed", nlimbs, fmt.L);
-    uint64_t x[kMaxLimbs];
-    const fr_deep_view v = {s, "0", frac_bits, 0};
-    uint64_t unused[kMaxLimbs];
-    const int st = parse_centre(&v, fmt, x, unused);
+    uint64_t x[kMaxLimbs], unused[kMaxLimbs];
+    const int st = parse_centre(s, "0", fmt, x, unused);
     if (st != FR_OK) return st;
     memcpy(out, x, sizeof(uint64_t) * (size_t)fmt.L);
     return fmt.L;
 }
 
-static int reference_orbit(const char* who, orbit_formula formula, const fr_deep_view* v, double zoom, int32_t max_iter,
-                           float bailout, double* out_xy, int32_t* out_len)
-{
-    if (!out_xy || !out_len) return fr_set_error(FR_ERR_INVALID_ARG, "%s: out is NULL", who);
-    if (max_iter < 1 || max_iter > (1 << 24))
-        return fr_set_error(FR_ERR_INVALID_ARG, "max_iterations %d outside [1, 2^24]", max_iter);
-    int st;
-    if ((st = check_zoom(zoom)) != FR_OK || (st = check_bailout(bailout)) != FR_OK) return st;
-    const int F = view_frac_bits(v, zoom);
-    if (F < 0) return F;
-    const fx_fmt fmt = {F, (F + 63) / 64 + 1};
-    uint64_t cr[kMaxLimbs], ci[kMaxLimbs];
-    if ((st = parse_centre(v, fmt, cr, ci)) != FR_OK) return st;
-    return orbit_loop(cr, ci, NULL, NULL, fmt, formula, max_iter, bailout, out_xy, NULL, out_len);
-}
-
-int fr_deep_reference_orbit(const fr_deep_view* v, double zoom, int32_t max_iter, float bailout, double* out_xy,
-                            int32_t* out_len)
-{
-    return reference_orbit("fr_deep_reference_orbit", kOrbitMandelbrot, v, zoom, max_iter, bailout, out_xy, out_len);
-}
-
-/* ---- deep Burning Ship views (fr_render_deep_ship) ----------------------------------------------------------------------- */
-int fr_deep_ship_reference_orbit(const fr_deep_view* v, double zoom, int32_t max_iter, float bailout, double* out_xy,
-                                 int32_t* out_len)
-{
-    return reference_orbit("fr_deep_ship_reference_orbit", kOrbitShip, v, zoom, max_iter, bailout, out_xy, out_len);
-}
-
-int fr_deep_ship_validate(const fr_params* p, const fr_deep_view* v, uint32_t width, uint32_t height)
-{
-    if (!p || !v) return fr_set_error(FR_ERR_INVALID_ARG, "params/deep view is NULL");
-    if (p->fractal_type != FR_FRACTAL_BURNING_SHIP)
-        return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deep_ship renders FR_FRACTAL_BURNING_SHIP only (got %d)",
-                            p->fractal_type);
-    if (p->precision != FR_PRECISION_F64)
-        return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deep_ship needs FR_PRECISION_F64 (got %d)", p->precision);
-    fr_params q = *p;                                            /* the double centre is not read */
-    q.center_x = 0.0; q.center_y = 0.0;
-    int st = fr_params_validate(&q, width, height);
-    if (st != FR_OK) return st;
-    if ((st = check_zoom(p->zoom)) != FR_OK || (st = check_bailout(p->bailout)) != FR_OK) return st;
-    if (p->orbit_trap_enabled || (p->stripe_enabled && p->interior_style == 2) || p->interior_style == 3)
-        return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deep_ship: the orbit trap, stripes with interior_style 2 and "
-                            "interior_style 3 need the whole orbit and are not available");
-    if (p->flags & (FR_FLAG_DEEP_BLA | FR_FLAG_DEEPX_BLA))
-        return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deep_ship: FR_FLAG_DEEP_BLA / FR_FLAG_DEEPX_BLA are not available (their "
-                            "tables are Mandelbrot's): the flag of the ship is FR_FLAG_DEEP_SHIP_BLA");
-    if ((st = check_no_julia_bla("fr_render_deep_ship", p)) != FR_OK) return st;
-    const int F = view_frac_bits(v, p->zoom);
-    if (F < 0) return F;
-    uint64_t cr[kMaxLimbs], ci[kMaxLimbs];
-    const fx_fmt fmt = {F, (F + 63) / 64 + 1};
-    return parse_centre(v, fmt, cr, ci);
-}
-
-/* ---- extended-exponent views (fr_render_deepx) ------------------------------------------------------------------------------
+/* ---- the zoom of an extended view ---------------------------------------------------------------------------------------------
  * The zoom is a decimal string: parsed like a centre into floor(value 2^kZoomBits) with the inexact flag of the divisions,
  * its top 53 bits rounded to nearest, ties to even -- one rounding from the decimal value. */
 enum { kZoomBits = 3520 };                    /* 1e-1000 2^3520 is about 2^198: far more than 54 bits */
@@ -649,7 +555,7 @@ int fr_deepx_zoom(const char* zoom, double* mant, int32_t* exp2)
     return zoom_pair(zoom, mant, exp2);
 }
 
-static int frac_bits_of_pair(double zm, int32_t ze)
+int fr_deepx_frac_bits_pair(double zm, int32_t ze)
 {
     if (ze >= -1000) {
         const double z = ldexp(zm, ze);                          /* exact: a normal double */
@@ -662,170 +568,132 @@ static int frac_bits_of_pair(double zm, int32_t ze)
     return (bits + 63) / 64 * 64;
 }
 
-int fr_deepx_frac_bits_pair(double zm, int32_t ze) { return frac_bits_of_pair(zm, ze); }
-
 int fr_deepx_frac_bits(const char* zoom)
 {
     double zm;
     int32_t ze;
     const int st = zoom_pair(zoom, &zm, &ze);
-    return st != FR_OK ? st : frac_bits_of_pair(zm, ze);
+    return st != FR_OK ? st : fr_deepx_frac_bits_pair(zm, ze);
 }
 
-int fr_deepx_view_default(fr_deepx_view* v)
+/* ---- a view resolved --------------------------------------------------------------------------------------------------------
+ * Either view struct (v: the zoom is the caller's double; x: the view's string) checked in one order -- reserved, frac_bits, the
+ * centre strings, the zoom string -- and turned into the fixed-point format, the zoom pair (v: (zoom, 0)) and, with `centre`,
+ * both centre strings parsed.  Every validator and every reference orbit goes through here. */
+typedef struct {
+    fx_fmt fmt;
+    uint64_t cr[kMaxLimbs], ci[kMaxLimbs];
+    double zm;
+    int32_t ze;
+} deep_resolved;
+
+static int resolve_view(const fr_deep_view* v, const fr_deepx_view* x, double zoom, int centre, deep_resolved* r)
 {
-    if (!v) return fr_set_error(FR_ERR_INVALID_ARG, "deep view is NULL");
-    v->center_x = "-0.5";
-    v->center_y = "0";
-    v->zoom = "3";
-    v->frac_bits = 0;
-    v->reserved = 0;
-    return FR_OK;
+    if (!v && !x) return fr_set_error(FR_ERR_INVALID_ARG, "deep view is NULL");
+    const char* cx = x ? x->center_x : v->center_x;
+    const char* cy = x ? x->center_y : v->center_y;
+    const int32_t bits = x ? x->frac_bits : v->frac_bits;
+    if ((x ? x->reserved : v->reserved) != 0)
+        return fr_set_error(FR_ERR_INVALID_ARG, "%s.reserved must be 0", x ? "fr_deepx_view" : "fr_deep_view");
+    if (bits != 0 && (bits < 128 || bits > kMaxFracBits))
+        return fr_set_error(FR_ERR_INVALID_ARG, "frac_bits %d outside {0} U [128, 4096]", bits);
+    if (!cx || !cy) return fr_set_error(FR_ERR_INVALID_ARG, "deep view centre string is NULL");
+    r->zm = zoom;
+    r->ze = 0;
+    int st;
+    if (x && (st = zoom_pair(x->zoom, &r->zm, &r->ze)) != FR_OK) return st;
+    const int F = bits ? bits : x ? fr_deepx_frac_bits_pair(r->zm, r->ze) : fr_deep_frac_bits(zoom);
+    if (F < 0) return F;
+    r->fmt.F = F;
+    r->fmt.L = (F + 63) / 64 + 1;
+    return centre ? parse_centre(cx, cy, r->fmt, r->cr, r->ci) : FR_OK;
 }
 
 int fr_deepx_resolve(const fr_deepx_view* v, double* zm, int32_t* ze, int32_t* frac_bits)
 {
-    if (!v) return fr_set_error(FR_ERR_INVALID_ARG, "deep view is NULL");
-    if (v->reserved != 0) return fr_set_error(FR_ERR_INVALID_ARG, "fr_deepx_view.reserved must be 0");
-    if (v->frac_bits != 0 && (v->frac_bits < 128 || v->frac_bits > kMaxFracBits))
-        return fr_set_error(FR_ERR_INVALID_ARG, "frac_bits %d outside {0} U [128, 4096]", v->frac_bits);
-    if (!v->center_x || !v->center_y) return fr_set_error(FR_ERR_INVALID_ARG, "deep view centre string is NULL");
-    const int st = zoom_pair(v->zoom, zm, ze);
+    deep_resolved r;
+    const int st = resolve_view(NULL, v, 0.0, 0, &r);
     if (st != FR_OK) return st;
-    *frac_bits = v->frac_bits ? v->frac_bits : frac_bits_of_pair(*zm, *ze);
+    *zm = r.zm;
+    *ze = r.ze;
+    *frac_bits = r.fmt.F;
     return FR_OK;
 }
 
-int fr_deepx_validate_params(const fr_params* p, uint32_t width, uint32_t height)
+/* ---- the rules of the six paths -----------------------------------------------------------------------------------------------
+ * What differs between the validators: one row per (formula, storage).  validate_params checks in this order: the fractal
+ * type, the precision, fr_params_validate (the double centre, and the zoom where the view's string carries it, not read), the
+ * zoom, the bailout, Julia's c, the whole-orbit rule, the foreign BLA flags. */
+typedef enum { kWholeNone = 0, kWholeMandel, kWholeShip } whole_orbit_rule;
+
+typedef struct {
+    const char* who;                 /* the entry point, as the messages name it */
+    int32_t fractal;
+    const char* fractal_name;
+    int zoom_in_params;              /* the zoom is p->zoom; else the view's string */
+    int julia;                       /* c is checked, and the centre has to lie inside the bailout radius */
+    whole_orbit_rule whole;          /* which colourings need the whole orbit: Mandelbrot's list, the ship's, none */
+    struct { uint32_t mask; const char* msg; } foreign[2];   /* BLA flags of other paths, in the order they are refused */
+} deep_rules;
+
+#define JULIA_FLAGS (FR_FLAG_DEEP_JULIA_BLA | FR_FLAG_DEEPX_JULIA_BLA)
+#define JULIA_FLAGS_MSG "FR_FLAG_DEEP_JULIA_BLA / FR_FLAG_DEEPX_JULIA_BLA are not available (their tables belong to the Julia paths)"
+#define OTHER_FLAGS (FR_FLAG_DEEP_BLA | FR_FLAG_DEEPX_BLA | FR_FLAG_DEEP_SHIP_BLA | FR_FLAG_DEEPX_SHIP_BLA)
+#define OTHER_FLAGS_MSG "the BLA flags are not available (their tables belong to the Mandelbrot and Burning Ship paths)"
+
+enum { kDeep, kDeepX, kDeepShip, kDeepXShip, kDeepJulia, kDeepXJulia };
+
+static const deep_rules kRules[6] = {
+    [kDeep] = {"fr_render_deep", FR_FRACTAL_MANDELBROT, "FR_FRACTAL_MANDELBROT", 1, 0, kWholeMandel,
+               {{JULIA_FLAGS, JULIA_FLAGS_MSG}, {0, NULL}}},
+    [kDeepX] = {"fr_render_deepx", FR_FRACTAL_MANDELBROT, "FR_FRACTAL_MANDELBROT", 0, 0, kWholeMandel,
+                {{FR_FLAG_DEEP_BLA, "FR_FLAG_DEEP_BLA is not available (its table is fp64): the flag of extended views is "
+                                    "FR_FLAG_DEEPX_BLA"},
+                 {JULIA_FLAGS, JULIA_FLAGS_MSG}}},
+    [kDeepShip] = {"fr_render_deep_ship", FR_FRACTAL_BURNING_SHIP, "FR_FRACTAL_BURNING_SHIP", 1, 0, kWholeShip,
+                   {{FR_FLAG_DEEP_BLA | FR_FLAG_DEEPX_BLA,
+                     "FR_FLAG_DEEP_BLA / FR_FLAG_DEEPX_BLA are not available (their tables are Mandelbrot's): the flag of the ship "
+                     "is FR_FLAG_DEEP_SHIP_BLA"},
+                    {JULIA_FLAGS, JULIA_FLAGS_MSG}}},
+    [kDeepXShip] = {"fr_render_deepx_ship", FR_FRACTAL_BURNING_SHIP, "FR_FRACTAL_BURNING_SHIP", 0, 0, kWholeShip,
+                    {{FR_FLAG_DEEP_BLA | FR_FLAG_DEEPX_BLA | FR_FLAG_DEEP_SHIP_BLA,
+                      "FR_FLAG_DEEP_BLA / FR_FLAG_DEEPX_BLA / FR_FLAG_DEEP_SHIP_BLA are not available (their tables belong to the "
+                      "other deep paths): the flag of extended Burning Ship views is FR_FLAG_DEEPX_SHIP_BLA"},
+                     {JULIA_FLAGS, JULIA_FLAGS_MSG}}},
+    [kDeepJulia] = {"fr_render_deep_julia", FR_FRACTAL_JULIA, "FR_FRACTAL_JULIA", 1, 1, kWholeNone,
+                    {{OTHER_FLAGS, OTHER_FLAGS_MSG},
+                     {FR_FLAG_DEEPX_JULIA_BLA, "FR_FLAG_DEEPX_JULIA_BLA is not available (its table is extended): the flag of this "
+                                               "entry point is FR_FLAG_DEEP_JULIA_BLA"}}},
+    [kDeepXJulia] = {"fr_render_deepx_julia", FR_FRACTAL_JULIA, "FR_FRACTAL_JULIA", 0, 1, kWholeNone,
+                     {{OTHER_FLAGS, OTHER_FLAGS_MSG},
+                      {FR_FLAG_DEEP_JULIA_BLA, "FR_FLAG_DEEP_JULIA_BLA is not available (its table is fp64): the flag of this entry "
+                                               "point is FR_FLAG_DEEPX_JULIA_BLA"}}},
+};
+
+static int validate_params(const deep_rules* k, const fr_params* p, uint32_t width, uint32_t height)
 {
     if (!p) return fr_set_error(FR_ERR_INVALID_ARG, "params/deep view is NULL");
-    if (p->fractal_type != FR_FRACTAL_MANDELBROT)
-        return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deepx renders FR_FRACTAL_MANDELBROT only (got %d)", p->fractal_type);
+    if (p->fractal_type != k->fractal)
+        return fr_set_error(FR_ERR_UNSUPPORTED, "%s renders %s only (got %d)", k->who, k->fractal_name, p->fractal_type);
     if (p->precision != FR_PRECISION_F64)
-        return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deepx needs FR_PRECISION_F64 (got %d)", p->precision);
-    fr_params q = *p;                                            /* the double centre and zoom are not read */
-    q.center_x = 0.0; q.center_y = 0.0; q.zoom = 1.0;
+        return fr_set_error(FR_ERR_UNSUPPORTED, "%s needs FR_PRECISION_F64 (got %d)", k->who, p->precision);
+    fr_params q = *p;                                            /* the double centre (and a string's zoom) is not read */
+    q.center_x = 0.0; q.center_y = 0.0;
+    if (!k->zoom_in_params) q.zoom = 1.0;
     int st = fr_params_validate(&q, width, height);
     if (st != FR_OK) return st;
+    if (k->zoom_in_params && (st = check_zoom(p->zoom)) != FR_OK) return st;
     if ((st = check_bailout(p->bailout)) != FR_OK) return st;
-    if (p->orbit_trap_enabled || p->stripe_enabled || p->interior_style == 2)
-        return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deepx: the orbit trap, stripes and interior_style 2 need the whole "
-                            "orbit and are not available");
-    if (p->flags & FR_FLAG_DEEP_BLA)
-        return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deepx: FR_FLAG_DEEP_BLA is not available (its table is fp64): the flag of "
-                            "extended views is FR_FLAG_DEEPX_BLA");
-    return check_no_julia_bla("fr_render_deepx", p);
-}
-
-int fr_deepx_check_centre(const char* center_x, const char* center_y, int32_t frac_bits)
-{
-    uint64_t cr[kMaxLimbs], ci[kMaxLimbs];
-    const fx_fmt fmt = {frac_bits, (frac_bits + 63) / 64 + 1};
-    const fr_deep_view c = {center_x, center_y, frac_bits, 0};
-    return parse_centre(&c, fmt, cr, ci);
-}
-
-int fr_deepx_validate(const fr_params* p, const fr_deepx_view* v, uint32_t width, uint32_t height)
-{
-    if (!p || !v) return fr_set_error(FR_ERR_INVALID_ARG, "params/deep view is NULL");
-    int st = fr_deepx_validate_params(p, width, height);
-    if (st != FR_OK) return st;
-    double zm;
-    int32_t ze, F;
-    if ((st = fr_deepx_resolve(v, &zm, &ze, &F)) != FR_OK) return st;
-    return fr_deepx_check_centre(v->center_x, v->center_y, F);
-}
-
-static int reference_orbit_x(const char* who, orbit_formula formula, const fr_deepx_view* v, int32_t max_iter, float bailout,
-                             double* out_mant_xy, int32_t* out_exp2, int32_t* out_len)
-{
-    if (!out_mant_xy || !out_exp2 || !out_len) return fr_set_error(FR_ERR_INVALID_ARG, "%s: out is NULL", who);
-    if (max_iter < 1 || max_iter > (1 << 24))
-        return fr_set_error(FR_ERR_INVALID_ARG, "max_iterations %d outside [1, 2^24]", max_iter);
-    int st;
-    if ((st = check_bailout(bailout)) != FR_OK) return st;
-    double zm;
-    int32_t ze, F;
-    if ((st = fr_deepx_resolve(v, &zm, &ze, &F)) != FR_OK) return st;
-    const fx_fmt fmt = {F, (F + 63) / 64 + 1};
-    uint64_t cr[kMaxLimbs], ci[kMaxLimbs];
-    const fr_deep_view c = {v->center_x, v->center_y, F, 0};
-    if ((st = parse_centre(&c, fmt, cr, ci)) != FR_OK) return st;
-    return orbit_loop(cr, ci, NULL, NULL, fmt, formula, max_iter, bailout, out_mant_xy, out_exp2, out_len);
-}
-
-int fr_deepx_reference_orbit(const fr_deepx_view* v, int32_t max_iter, float bailout, double* out_mant_xy, int32_t* out_exp2,
-                             int32_t* out_len)
-{
-    return reference_orbit_x("fr_deepx_reference_orbit", kOrbitMandelbrot, v, max_iter, bailout, out_mant_xy, out_exp2, out_len);
-}
-
-/* ---- extended Burning Ship views (fr_render_deepx_ship) ---------------------------------------------------------------------- */
-int fr_deepx_ship_reference_orbit(const fr_deepx_view* v, int32_t max_iter, float bailout, double* out_mant_xy,
-                                  int32_t* out_exp2, int32_t* out_len)
-{
-    return reference_orbit_x("fr_deepx_ship_reference_orbit", kOrbitShip, v, max_iter, bailout, out_mant_xy, out_exp2, out_len);
-}
-
-int fr_deepx_ship_validate_params(const fr_params* p, uint32_t width, uint32_t height)
-{
-    if (!p) return fr_set_error(FR_ERR_INVALID_ARG, "params/deep view is NULL");
-    if (p->fractal_type != FR_FRACTAL_BURNING_SHIP)
-        return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deepx_ship renders FR_FRACTAL_BURNING_SHIP only (got %d)",
-                            p->fractal_type);
-    if (p->precision != FR_PRECISION_F64)
-        return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deepx_ship needs FR_PRECISION_F64 (got %d)", p->precision);
-    fr_params q = *p;                                            /* the double centre and zoom are not read */
-    q.center_x = 0.0; q.center_y = 0.0; q.zoom = 1.0;
-    int st = fr_params_validate(&q, width, height);
-    if (st != FR_OK) return st;
-    if ((st = check_bailout(p->bailout)) != FR_OK) return st;
-    if (p->orbit_trap_enabled || (p->stripe_enabled && p->interior_style == 2) || p->interior_style == 3)
-        return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deepx_ship: the orbit trap, stripes with interior_style 2 and "
-                            "interior_style 3 need the whole orbit and are not available");
-    if (p->flags & (FR_FLAG_DEEP_BLA | FR_FLAG_DEEPX_BLA | FR_FLAG_DEEP_SHIP_BLA))
-        return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deepx_ship: FR_FLAG_DEEP_BLA / FR_FLAG_DEEPX_BLA / FR_FLAG_DEEP_SHIP_BLA "
-                            "are not available (their tables belong to the other deep paths): the flag of extended Burning "
-                            "Ship views is FR_FLAG_DEEPX_SHIP_BLA");
-    return check_no_julia_bla("fr_render_deepx_ship", p);
-}
-
-int fr_deepx_ship_validate(const fr_params* p, const fr_deepx_view* v, uint32_t width, uint32_t height)
-{
-    if (!p || !v) return fr_set_error(FR_ERR_INVALID_ARG, "params/deep view is NULL");
-    int st = fr_deepx_ship_validate_params(p, width, height);
-    if (st != FR_OK) return st;
-    double zm;
-    int32_t ze, F;
-    if ((st = fr_deepx_resolve(v, &zm, &ze, &F)) != FR_OK) return st;
-    return fr_deepx_check_centre(v->center_x, v->center_y, F);
-}
-
-/* ---- deep Julia views (fr_render_deep_julia, fr_render_deepx_julia) -----------------------------------------------------------
- * c is a pair of doubles: round_half_even(c 2^F), exact wherever F holds the double's last bit (every c but a tiny one). */
-static void double_to_fixed(double c, fx_fmt fmt, uint64_t* out)
-{
-    memset(out, 0, sizeof(uint64_t) * (size_t)fmt.L);
-    if (c == 0.0) return;
-    int ex = 0;
-    const double mant = frexp(fabs(c), &ex);
-    const uint64_t mi = (uint64_t)ldexp(mant, 53);               /* |c| = mi 2^(ex - 53) */
-    const long s = (long)ex - 53 + fmt.F;
-    if (s >= 0) {
-        out[0] = mi;
-        shl_bits(out, fmt.L, (int)s);                            /* |c| < 2^32: below 2^(F + 32) */
-    } else if (-s < 64) {
-        const int k = (int)-s;
-        const uint64_t q = mi >> k, rem = mi & ((1ull << k) - 1), half = 1ull << (k - 1);
-        out[0] = q + (rem > half || (rem == half && (q & 1u)));
-    }                                                            /* else below 2^-11 of a unit: 0 */
-    if (c < 0.0) negate(out, fmt.L);
-}
-
-static int check_julia_c(double c_re, double c_im)
-{
-    if (!isfinite(c_re) || !isfinite(c_im) || !(fabs(c_re) < 4294967296.0) || !(fabs(c_im) < 4294967296.0))
-        return fr_set_error(FR_ERR_INVALID_ARG, "deep Julia views need a finite c with |c_re|, |c_im| < 2^32");
+    if (k->julia && (st = check_julia_c(p->julia_c_real, p->julia_c_imag)) != FR_OK) return st;
+    if (k->whole == kWholeMandel && (p->orbit_trap_enabled || p->stripe_enabled || p->interior_style == 2))
+        return fr_set_error(FR_ERR_UNSUPPORTED, "%s: the orbit trap, stripes and interior_style 2 need the whole orbit and are "
+                            "not available", k->who);
+    if (k->whole == kWholeShip &&
+        (p->orbit_trap_enabled || (p->stripe_enabled && p->interior_style == 2) || p->interior_style == 3))
+        return fr_set_error(FR_ERR_UNSUPPORTED, "%s: the orbit trap, stripes with interior_style 2 and interior_style 3 need the "
+                            "whole orbit and are not available", k->who);
+    for (int i = 0; i < 2; ++i)
+        if (p->flags & k->foreign[i].mask) return fr_set_error(FR_ERR_UNSUPPORTED, "%s: %s", k->who, k->foreign[i].msg);
     return FR_OK;
 }
 
@@ -849,107 +717,188 @@ static int check_julia_centre(const uint64_t* cr, const uint64_t* ci, fx_fmt fmt
     return FR_OK;
 }
 
-/* P (from the centre) and Q (from 0) of z <- z^2 + c in one storage; the centre already parsed */
-static int julia_orbits(const uint64_t* zr, const uint64_t* zi, double c_re, double c_im, fx_fmt fmt, int32_t max_iter,
-                        float bailout, double* p_xy, int32_t* p_exp, int32_t* p_len, double* q_xy, int32_t* q_exp,
-                        int32_t* q_len)
+/* a validator with its view: the row's rules for p, then the view resolved and its centre parsed (v or x, as resolve_view) */
+static int validate_view(const deep_rules* k, const fr_params* p, const fr_deep_view* v, const fr_deepx_view* x, uint32_t width,
+                         uint32_t height)
+{
+    if (!p || (!v && !x)) return fr_set_error(FR_ERR_INVALID_ARG, "params/deep view is NULL");
+    int st = validate_params(k, p, width, height);
+    if (st != FR_OK) return st;
+    deep_resolved r;
+    if ((st = resolve_view(v, x, p->zoom, 1, &r)) != FR_OK) return st;
+    return k->julia ? check_julia_centre(r.cr, r.ci, r.fmt, p->bailout) : FR_OK;
+}
+
+int fr_deep_validate(const fr_params* p, const fr_deep_view* v, uint32_t width, uint32_t height)
+{
+    return validate_view(&kRules[kDeep], p, v, NULL, width, height);
+}
+
+int fr_deep_ship_validate(const fr_params* p, const fr_deep_view* v, uint32_t width, uint32_t height)
+{
+    return validate_view(&kRules[kDeepShip], p, v, NULL, width, height);
+}
+
+int fr_deepx_validate_params(const fr_params* p, uint32_t width, uint32_t height)
+{
+    return validate_params(&kRules[kDeepX], p, width, height);
+}
+
+int fr_deepx_validate(const fr_params* p, const fr_deepx_view* v, uint32_t width, uint32_t height)
+{
+    return validate_view(&kRules[kDeepX], p, NULL, v, width, height);
+}
+
+int fr_deepx_ship_validate_params(const fr_params* p, uint32_t width, uint32_t height)
+{
+    return validate_params(&kRules[kDeepXShip], p, width, height);
+}
+
+int fr_deepx_ship_validate(const fr_params* p, const fr_deepx_view* v, uint32_t width, uint32_t height)
+{
+    return validate_view(&kRules[kDeepXShip], p, NULL, v, width, height);
+}
+
+int fr_deep_julia_validate(const fr_params* p, const fr_deep_view* v, uint32_t width, uint32_t height)
+{
+    return validate_view(&kRules[kDeepJulia], p, v, NULL, width, height);
+}
+
+int fr_deepx_julia_validate(const fr_params* p, const fr_deepx_view* v, uint32_t width, uint32_t height)
+{
+    return validate_view(&kRules[kDeepXJulia], p, NULL, v, width, height);
+}
+
+int fr_deep_de_default(fr_deep_de* e)
+{
+    if (!e) return fr_set_error(FR_ERR_INVALID_ARG, "fr_deep_de is NULL");
+    e->de = NULL;
+    e->deriv = NULL;
+    e->shade = 0;
+    e->edge_px = 1.8f;                           /* 0.005 c-plane units (mandelbrot_debug.comp:196) at zoom 3.0 on 1080 rows */
+    return FR_OK;
+}
+
+int fr_deep_de_validate(const fr_params* p, const fr_deep_view* v, const fr_deep_de* e, uint32_t width, uint32_t height)
+{
+    if (!e) return fr_set_error(FR_ERR_INVALID_ARG, "fr_deep_de is NULL");
+    const int st = fr_deep_validate(p, v, width, height);
+    if (st != FR_OK) return st;
+    if (e->shade != 0 && e->shade != 1) return fr_set_error(FR_ERR_INVALID_ARG, "fr_deep_de.shade %d is neither 0 nor 1", e->shade);
+    if (e->shade == 1 && (!isfinite(e->edge_px) || !(e->edge_px > 0.0f)))
+        return fr_set_error(FR_ERR_INVALID_ARG, "fr_deep_de.edge_px must be finite and > 0 with shade 1");
+    return FR_OK;
+}
+
+/* ---- the reference orbits -----------------------------------------------------------------------------------------------------
+ * What the six entry points ask before they iterate, in this order: the out pointers (have_out), max_iter, the zoom (the entry's
+ * double; NULL for an extended entry, whose view carries a string), the bailout, Julia's c (julia_c, NULL elsewhere), then
+ * the view resolved with its centre -- v or x, whichever the entry takes; a NULL view is resolve_view's to refuse. */
+static int orbit_request(const char* who, int have_out, const fr_deep_view* v, const fr_deepx_view* x, const double* zoom,
+                         int32_t max_iter, float bailout, const double* julia_c, deep_resolved* r)
+{
+    if (!have_out) return fr_set_error(FR_ERR_INVALID_ARG, "%s: out is NULL", who);
+    if (max_iter < 1 || max_iter > (1 << 24))
+        return fr_set_error(FR_ERR_INVALID_ARG, "max_iterations %d outside [1, 2^24]", max_iter);
+    int st;
+    if (zoom && (st = check_zoom(*zoom)) != FR_OK) return st;
+    if ((st = check_bailout(bailout)) != FR_OK) return st;
+    if (julia_c && (st = check_julia_c(julia_c[0], julia_c[1])) != FR_OK) return st;
+    return resolve_view(v, x, zoom ? *zoom : 0.0, 1, r);
+}
+
+int fr_deep_reference_orbit(const fr_deep_view* v, double zoom, int32_t max_iter, float bailout, double* out_xy,
+                            int32_t* out_len)
+{
+    deep_resolved r;
+    const int st = orbit_request("fr_deep_reference_orbit", out_xy && out_len, v, NULL, &zoom, max_iter, bailout, NULL, &r);
+    if (st != FR_OK) return st;
+    return orbit_loop(r.cr, r.ci, NULL, NULL, r.fmt, kOrbitMandelbrot, max_iter, bailout, out_xy, NULL, out_len);
+}
+
+int fr_deep_ship_reference_orbit(const fr_deep_view* v, double zoom, int32_t max_iter, float bailout, double* out_xy,
+                                 int32_t* out_len)
+{
+    deep_resolved r;
+    const int st = orbit_request("fr_deep_ship_reference_orbit", out_xy && out_len, v, NULL, &zoom, max_iter, bailout, NULL, &r);
+    if (st != FR_OK) return st;
+    return orbit_loop(r.cr, r.ci, NULL, NULL, r.fmt, kOrbitShip, max_iter, bailout, out_xy, NULL, out_len);
+}
+
+int fr_deepx_reference_orbit(const fr_deepx_view* v, int32_t max_iter, float bailout, double* out_mant_xy, int32_t* out_exp2,
+                             int32_t* out_len)
+{
+    deep_resolved r;
+    const int st = orbit_request("fr_deepx_reference_orbit", out_mant_xy && out_exp2 && out_len, NULL, v, NULL, max_iter, bailout,
+                                 NULL, &r);
+    if (st != FR_OK) return st;
+    return orbit_loop(r.cr, r.ci, NULL, NULL, r.fmt, kOrbitMandelbrot, max_iter, bailout, out_mant_xy, out_exp2, out_len);
+}
+
+int fr_deepx_ship_reference_orbit(const fr_deepx_view* v, int32_t max_iter, float bailout, double* out_mant_xy,
+                                  int32_t* out_exp2, int32_t* out_len)
+{
+    deep_resolved r;
+    const int st = orbit_request("fr_deepx_ship_reference_orbit", out_mant_xy && out_exp2 && out_len, NULL, v, NULL, max_iter,
+                                 bailout, NULL, &r);
+    if (st != FR_OK) return st;
+    return orbit_loop(r.cr, r.ci, NULL, NULL, r.fmt, kOrbitShip, max_iter, bailout, out_mant_xy, out_exp2, out_len);
+}
+
+/* ---- deep Julia views (fr_render_deep_julia, fr_render_deepx_julia) -----------------------------------------------------------
+ * c is a pair of doubles: round_half_even(c 2^F), exact wherever F holds the double's last bit (every c but a tiny one). */
+static void double_to_fixed(double c, fx_fmt fmt, uint64_t* out)
+{
+    memset(out, 0, sizeof(uint64_t) * (size_t)fmt.L);
+    if (c == 0.0) return;
+    int ex = 0;
+    const double mant = frexp(fabs(c), &ex);
+    const uint64_t mi = (uint64_t)ldexp(mant, 53);               /* |c| = mi 2^(ex - 53) */
+    const long s = (long)ex - 53 + fmt.F;
+    if (s >= 0) {
+        out[0] = mi;
+        shl_bits(out, fmt.L, (int)s);                            /* |c| < 2^32: below 2^(F + 32) */
+    } else if (-s < 64) {
+        const int k = (int)-s;
+        const uint64_t q = mi >> k, rem = mi & ((1ull << k) - 1), half = 1ull << (k - 1);
+        out[0] = q + (rem > half || (rem == half && (q & 1u)));
+    }                                                            /* else below 2^-11 of a unit: 0 */
+    if (c < 0.0) negate(out, fmt.L);
+}
+
+/* P (from the centre) and Q (from 0) of z <- z^2 + c in one storage; the view resolved, its centre z */
+static int julia_orbits(const deep_resolved* z, const double* c, int32_t max_iter, float bailout, double* p_xy, int32_t* p_exp,
+                        int32_t* p_len, double* q_xy, int32_t* q_exp, int32_t* q_len)
 {
     int st;
-    if ((st = check_julia_centre(zr, zi, fmt, bailout)) != FR_OK) return st;
+    if ((st = check_julia_centre(z->cr, z->ci, z->fmt, bailout)) != FR_OK) return st;
     uint64_t cr[kMaxLimbs], ci[kMaxLimbs];
-    double_to_fixed(c_re, fmt, cr);
-    double_to_fixed(c_im, fmt, ci);
-    if ((st = orbit_loop(cr, ci, zr, zi, fmt, kOrbitMandelbrot, max_iter, bailout, p_xy, p_exp, p_len)) != FR_OK) return st;
-    return orbit_loop(cr, ci, NULL, NULL, fmt, kOrbitMandelbrot, max_iter, bailout, q_xy, q_exp, q_len);
+    double_to_fixed(c[0], z->fmt, cr);
+    double_to_fixed(c[1], z->fmt, ci);
+    if ((st = orbit_loop(cr, ci, z->cr, z->ci, z->fmt, kOrbitMandelbrot, max_iter, bailout, p_xy, p_exp, p_len)) != FR_OK) return st;
+    return orbit_loop(cr, ci, NULL, NULL, z->fmt, kOrbitMandelbrot, max_iter, bailout, q_xy, q_exp, q_len);
 }
 
 int fr_deep_julia_reference_orbits(const fr_deep_view* v, double c_re, double c_im, double zoom, int32_t max_iter, float bailout,
                                    double* out_p_xy, int32_t* out_p_len, double* out_q_xy, int32_t* out_q_len)
 {
-    if (!out_p_xy || !out_p_len || !out_q_xy || !out_q_len)
-        return fr_set_error(FR_ERR_INVALID_ARG, "fr_deep_julia_reference_orbits: out is NULL");
-    if (max_iter < 1 || max_iter > (1 << 24))
-        return fr_set_error(FR_ERR_INVALID_ARG, "max_iterations %d outside [1, 2^24]", max_iter);
-    int st;
-    if ((st = check_zoom(zoom)) != FR_OK || (st = check_bailout(bailout)) != FR_OK || (st = check_julia_c(c_re, c_im)) != FR_OK)
-        return st;
-    const int F = view_frac_bits(v, zoom);
-    if (F < 0) return F;
-    const fx_fmt fmt = {F, (F + 63) / 64 + 1};
-    uint64_t zr[kMaxLimbs], zi[kMaxLimbs];
-    if ((st = parse_centre(v, fmt, zr, zi)) != FR_OK) return st;
-    return julia_orbits(zr, zi, c_re, c_im, fmt, max_iter, bailout, out_p_xy, NULL, out_p_len, out_q_xy, NULL, out_q_len);
+    const double c[2] = {c_re, c_im};
+    deep_resolved r;
+    const int st = orbit_request("fr_deep_julia_reference_orbits", out_p_xy && out_p_len && out_q_xy && out_q_len, v, NULL, &zoom,
+                                 max_iter, bailout, c, &r);
+    if (st != FR_OK) return st;
+    return julia_orbits(&r, c, max_iter, bailout, out_p_xy, NULL, out_p_len, out_q_xy, NULL, out_q_len);
 }
 
 int fr_deepx_julia_reference_orbits(const fr_deepx_view* v, double c_re, double c_im, int32_t max_iter, float bailout,
                                     double* out_p_mant_xy, int32_t* out_p_exp2, int32_t* out_p_len, double* out_q_mant_xy,
                                     int32_t* out_q_exp2, int32_t* out_q_len)
 {
-    if (!out_p_mant_xy || !out_p_exp2 || !out_p_len || !out_q_mant_xy || !out_q_exp2 || !out_q_len)
-        return fr_set_error(FR_ERR_INVALID_ARG, "fr_deepx_julia_reference_orbits: out is NULL");
-    if (max_iter < 1 || max_iter > (1 << 24))
-        return fr_set_error(FR_ERR_INVALID_ARG, "max_iterations %d outside [1, 2^24]", max_iter);
-    int st;
-    if ((st = check_bailout(bailout)) != FR_OK || (st = check_julia_c(c_re, c_im)) != FR_OK) return st;
-    double zm;
-    int32_t ze, F;
-    if ((st = fr_deepx_resolve(v, &zm, &ze, &F)) != FR_OK) return st;
-    const fx_fmt fmt = {F, (F + 63) / 64 + 1};
-    uint64_t zr[kMaxLimbs], zi[kMaxLimbs];
-    const fr_deep_view c = {v->center_x, v->center_y, F, 0};
-    if ((st = parse_centre(&c, fmt, zr, zi)) != FR_OK) return st;
-    return julia_orbits(zr, zi, c_re, c_im, fmt, max_iter, bailout, out_p_mant_xy, out_p_exp2, out_p_len, out_q_mant_xy,
-                        out_q_exp2, out_q_len);
-}
-
-/* what both validators ask of p; `zoomed`: the zoom is p's (fr_render_deep_julia), else the view's string */
-static int julia_validate_params(const char* who, const fr_params* p, uint32_t width, uint32_t height, int zoomed)
-{
-    if (p->fractal_type != FR_FRACTAL_JULIA)
-        return fr_set_error(FR_ERR_UNSUPPORTED, "%s renders FR_FRACTAL_JULIA only (got %d)", who, p->fractal_type);
-    if (p->precision != FR_PRECISION_F64)
-        return fr_set_error(FR_ERR_UNSUPPORTED, "%s needs FR_PRECISION_F64 (got %d)", who, p->precision);
-    fr_params q = *p;                                            /* the double centre (and the extended form's zoom) is not read */
-    q.center_x = 0.0; q.center_y = 0.0;
-    if (!zoomed) q.zoom = 1.0;
-    int st = fr_params_validate(&q, width, height);
+    const double c[2] = {c_re, c_im};
+    deep_resolved r;
+    const int st = orbit_request("fr_deepx_julia_reference_orbits",
+                                 out_p_mant_xy && out_p_exp2 && out_p_len && out_q_mant_xy && out_q_exp2 && out_q_len, NULL, v, NULL,
+                                 max_iter, bailout, c, &r);
     if (st != FR_OK) return st;
-    if (zoomed && (st = check_zoom(p->zoom)) != FR_OK) return st;
-    if ((st = check_bailout(p->bailout)) != FR_OK || (st = check_julia_c(p->julia_c_real, p->julia_c_imag)) != FR_OK) return st;
-    if (p->flags & (FR_FLAG_DEEP_BLA | FR_FLAG_DEEPX_BLA | FR_FLAG_DEEP_SHIP_BLA | FR_FLAG_DEEPX_SHIP_BLA))
-        return fr_set_error(FR_ERR_UNSUPPORTED, "%s: the BLA flags are not available (their tables belong to the Mandelbrot and "
-                            "Burning Ship paths)", who);
-    if (p->flags & (zoomed ? FR_FLAG_DEEPX_JULIA_BLA : FR_FLAG_DEEP_JULIA_BLA))
-        return fr_set_error(FR_ERR_UNSUPPORTED, "%s: %s is not available (its table is %s): the flag of this entry point is %s", who,
-                            zoomed ? "FR_FLAG_DEEPX_JULIA_BLA" : "FR_FLAG_DEEP_JULIA_BLA", zoomed ? "extended" : "fp64",
-                            zoomed ? "FR_FLAG_DEEP_JULIA_BLA" : "FR_FLAG_DEEPX_JULIA_BLA");
-    return FR_OK;
-}
-
-int fr_deep_julia_validate(const fr_params* p, const fr_deep_view* v, uint32_t width, uint32_t height)
-{
-    if (!p || !v) return fr_set_error(FR_ERR_INVALID_ARG, "params/deep view is NULL");
-    int st = julia_validate_params("fr_render_deep_julia", p, width, height, 1);
-    if (st != FR_OK) return st;
-    const int F = view_frac_bits(v, p->zoom);
-    if (F < 0) return F;
-    uint64_t zr[kMaxLimbs], zi[kMaxLimbs];
-    const fx_fmt fmt = {F, (F + 63) / 64 + 1};
-    if ((st = parse_centre(v, fmt, zr, zi)) != FR_OK) return st;
-    return check_julia_centre(zr, zi, fmt, p->bailout);
-}
-
-int fr_deepx_julia_validate(const fr_params* p, const fr_deepx_view* v, uint32_t width, uint32_t height)
-{
-    if (!p || !v) return fr_set_error(FR_ERR_INVALID_ARG, "params/deep view is NULL");
-    int st = julia_validate_params("fr_render_deepx_julia", p, width, height, 0);
-    if (st != FR_OK) return st;
-    double zm;
-    int32_t ze, F;
-    if ((st = fr_deepx_resolve(v, &zm, &ze, &F)) != FR_OK) return st;
-    uint64_t zr[kMaxLimbs], zi[kMaxLimbs];
-    const fx_fmt fmt = {F, (F + 63) / 64 + 1};
-    const fr_deep_view c = {v->center_x, v->center_y, F, 0};
-    if ((st = parse_centre(&c, fmt, zr, zi)) != FR_OK) return st;
-    return check_julia_centre(zr, zi, fmt, p->bailout);
+    return julia_orbits(&r, c, max_iter, bailout, out_p_mant_xy, out_p_exp2, out_p_len, out_q_mant_xy, out_q_exp2, out_q_len);
 }

@@ -54,7 +54,6 @@ struct DeepOrbit {
     int32_t len_p;              /* a Julia slot: N_P + 1 */
     OrbitKey key;               /* of dev */
     uint64_t gen;               /* bumped whenever dev receives another orbit */
-    int wg_per_cu;              /* resident workgroups per CU of the slot's unflagged deep_kernel (0 = not asked yet) */
 };
 
 /* One BLA table of a cached orbit, and the step counts of the most recent render with its flag */
@@ -72,7 +71,15 @@ struct BlaSlot {
     bool have_steps;
     hipEvent_t ev;              /* recorded behind every render with the flag (not while capturing): rebuilds wait for it */
     bool ev_valid;
-    int wg_per_cu;              /* resident workgroups per CU of the slot's flagged deep_kernel (0 = not asked yet) */
+};
+
+/* What the context keeps for one deep path, a (storage, formula) pair: its most recent reference orbit(s), their BLA table, and
+ * the resident workgroups per CU of the deep_kernel instantiations that read them (0 = not asked yet): [0] the path's own pair,
+ * [1] fr_render_deep_de's, which shares the fp64 Mandelbrot slot; [.][0] the unflagged kernel, [.][1] the flagged one */
+struct DeepSlot {
+    DeepOrbit o;
+    BlaSlot t;
+    int wg_per_cu[2][2];
 };
 
 struct fr_ctx {
@@ -126,18 +133,17 @@ struct fr_ctx {
     uint32_t div_next;
     int phoenix_wg_per_cu[2];   /* resident workgroups per CU of phoenix_kernel<float> / <double> (0 = not asked yet) */
     int mandelbulb_wg_per_cu[2];  /* ... of mandelbulb_kernel<false> / <true> (0 = not asked yet) */
-    /* deep views, per formula (kMandel, kShip, kJulia): the most recent reference orbit and its BLA table, for the fp64 views
-     * (fr_render_deep, fr_render_deep_ship, fr_render_deep_julia) and for the extended ones (fr_render_deepx,
-     * fr_render_deepx_ship, fr_render_deepx_julia).  The six paths share nothing.  A Julia slot holds two orbits: Q in the first
-     * half of every array, P in the second. */
-    DeepOrbit deep[3];          /* plain doubles Z_0 .. Z_N: 2 cap doubles pinned, cap double2 on the device */
-    DeepOrbit deepx[3];         /* the extended storage.  One pinned and one device block of cap points each: the plain
-                                 * doubles, the mantissa pairs, the exponents, in this order. */
-    BlaSlot bla[3];             /* FR_FLAG_DEEP_BLA, FR_FLAG_DEEP_SHIP_BLA, FR_FLAG_DEEP_JULIA_BLA: the tables of deep[] */
-    BlaSlot blax[3];            /* FR_FLAG_DEEPX_BLA, FR_FLAG_DEEPX_SHIP_BLA, FR_FLAG_DEEPX_JULIA_BLA: the tables of deepx[] */
-    int deep_de_wg_per_cu[2];   /* fr_render_deep_de reads deep[kMandel] and bla[kMandel]; its kernels have their own resident
-                                 * sets: deep_kernel<DeepDeArgs> / <DeepDeBlaArgs> (0 = not asked yet) */
+    /* deep views: one slot per path, deep[storage][formula] (deep_slot()).  Storage 0, plain doubles Z_0 .. Z_N in one pinned and
+     * one device block of cap double2: fr_render_deep (and fr_render_deep_de), fr_render_deep_ship, fr_render_deep_julia with
+     * the tables of FR_FLAG_DEEP_BLA, FR_FLAG_DEEP_SHIP_BLA, FR_FLAG_DEEP_JULIA_BLA.  Storage 1, the extended storage, one
+     * pinned and one device block of cap points each -- the plain doubles, the mantissa pairs, the exponents, in this order:
+     * fr_render_deepx, fr_render_deepx_ship, fr_render_deepx_julia and the sequences, with the tables of FR_FLAG_DEEPX_BLA,
+     * FR_FLAG_DEEPX_SHIP_BLA, FR_FLAG_DEEPX_JULIA_BLA.  The six paths share nothing.  A Julia slot holds two orbits: Q in the
+     * first half of every array, P in the second. */
+    DeepSlot deep[2][3];
 };
+
+static DeepSlot& deep_slot(fr_ctx* c, bool ext, int f) { return c->deep[ext ? 1 : 0][f]; }
 
 #define FR_HIP_TRY(expr)                                                               \
     do {                                                                               \
@@ -179,17 +185,20 @@ extern "C" int fr_ctx_create(int device_ordinal, fr_ctx** out)
     float t8[257], pairs[512];
     fr_export8_thresholds(t8);
     for (int b = 0; b < 256; ++b) { pairs[2 * b] = t8[b]; pairs[2 * b + 1] = t8[b + 1]; }
+    auto slot_events = [c] {                     /* the event of every deep slot's table (BlaSlot::ev) */
+        for (auto& storage : c->deep)
+            for (DeepSlot& s : storage) {
+                const hipError_t e = hipEventCreateWithFlags(&s.t.ev, hipEventDisableTiming);
+                if (e != hipSuccess) return e;
+            }
+        return hipSuccess;
+    };
     hipError_t e2;
     if ((e2 = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)) != hipSuccess ||
         (e2 = hipEventCreate(&c->ev_begin)) != hipSuccess ||
         (e2 = hipEventCreate(&c->ev_end)) != hipSuccess ||
         (e2 = hipEventCreateWithFlags(&c->ev_order, hipEventDisableTiming)) != hipSuccess ||
-        (e2 = hipEventCreateWithFlags(&c->bla[kMandel].ev, hipEventDisableTiming)) != hipSuccess ||
-        (e2 = hipEventCreateWithFlags(&c->bla[kShip].ev, hipEventDisableTiming)) != hipSuccess ||
-        (e2 = hipEventCreateWithFlags(&c->blax[kMandel].ev, hipEventDisableTiming)) != hipSuccess ||
-        (e2 = hipEventCreateWithFlags(&c->blax[kShip].ev, hipEventDisableTiming)) != hipSuccess ||
-        (e2 = hipEventCreateWithFlags(&c->bla[kJulia].ev, hipEventDisableTiming)) != hipSuccess ||
-        (e2 = hipEventCreateWithFlags(&c->blax[kJulia].ev, hipEventDisableTiming)) != hipSuccess ||
+        (e2 = slot_events()) != hipSuccess ||
         (e2 = hipMalloc((void**)&c->d_ctrl, (kCtrlWords + (size_t)(kFeedbackShards + 2) * kShardStrideWords) * sizeof(uint32_t))) != hipSuccess ||
         (e2 = hipMemset(c->d_ctrl, 0, (kCtrlWords + (size_t)(kFeedbackShards + 2) * kShardStrideWords) * sizeof(uint32_t))) != hipSuccess ||
         (e2 = hipHostMalloc((void**)&c->overflow_host, 64, hipHostMallocMapped)) != hipSuccess ||
@@ -224,21 +233,19 @@ extern "C" void fr_ctx_destroy(fr_ctx* c)
     if (c->frame_buf) (void)hipFree(c->frame_buf);
     if (c->orbit_host) (void)hipHostFree(c->orbit_host);
     if (c->orbit_dev) (void)hipFree(c->orbit_dev);
-    for (DeepOrbit* o : {&c->deep[kMandel], &c->deep[kShip], &c->deep[kJulia], &c->deepx[kMandel], &c->deepx[kShip],
-                         &c->deepx[kJulia]}) {
-        if (o->host) (void)hipHostFree(o->host);
-        if (o->dev) (void)hipFree(o->dev);
-        free(o->key.x);
-        free(o->key.y);
-    }
-    for (BlaSlot* t : {&c->bla[kMandel], &c->bla[kShip], &c->bla[kJulia], &c->blax[kMandel], &c->blax[kShip], &c->blax[kJulia]}) {
-        if (t->r) (void)hipFree(t->r);
-        if (t->ab) (void)hipFree(t->ab);
-        if (t->abe) (void)hipFree(t->abe);
-        if (t->steps_dev) (void)hipFree(t->steps_dev);
-        if (t->steps_host) (void)hipHostFree(t->steps_host);
-        if (t->ev) (void)hipEventDestroy(t->ev);
-    }
+    for (auto& storage : c->deep)
+        for (DeepSlot& s : storage) {
+            if (s.o.host) (void)hipHostFree(s.o.host);
+            if (s.o.dev) (void)hipFree(s.o.dev);
+            free(s.o.key.x);
+            free(s.o.key.y);
+            if (s.t.r) (void)hipFree(s.t.r);
+            if (s.t.ab) (void)hipFree(s.t.ab);
+            if (s.t.abe) (void)hipFree(s.t.abe);
+            if (s.t.steps_dev) (void)hipFree(s.t.steps_dev);
+            if (s.t.steps_host) (void)hipHostFree(s.t.steps_host);
+            if (s.t.ev) (void)hipEventDestroy(s.t.ev);
+        }
     if (c->ev_begin) (void)hipEventDestroy(c->ev_begin);
     if (c->ev_end) (void)hipEventDestroy(c->ev_end);
     if (c->ev_order) (void)hipEventDestroy(c->ev_order);
@@ -782,26 +789,76 @@ static int orbit_slot_prepare(fr_ctx* c, DeepOrbit& o, const BlaSlot* t, hipStre
     return FR_OK;
 }
 
-/* fp64 views: the plain-double orbit of the view in the formula's cache slot (fr_render_deep's, fr_render_deep_ship's) unless
- * the slot holds it already */
-static int orbit_slot_fill(fr_ctx* c, int f, const fr_params* p, const fr_deep_view* v, hipStream_t stream)
+/* what differs per formula on the host: the orbits a slot holds (a Julia slot: Q, then P) and the double2 per table entry */
+static const struct { int orbits; size_t ab_per_entry; } kFormula[3] = {
+    {1, MandelFormula::kAbPerEntry}, {1, ShipFormula::kAbPerEntry}, {2, JuliaFormula::kAbPerEntry}};
+
+/* a view as the enqueue side reads it: the centre strings, the zoom as a pair (an fp64 view: (zoom, 0)) and the fraction bits of
+ * its orbit; zoom: the string of an extended view, which the orbit does not depend on (nullptr: an fp64 view) */
+struct DeepAt {
+    const char *cx, *cy, *zoom;
+    double zm;
+    int32_t ze, bits;
+};
+
+/* The reference orbit(s) of the view in the path's slot unless the slot holds them already (keyed by the centre strings, the
+ * fraction bits, max_iter, the bailout and, in a Julia slot, the bits of c).  One orbit, or Julia's Q at point 0 and P half the
+ * capacity behind it (kFormula); ext: the extended storage, whose plain doubles ldexp(mantissa, exponent) are formed here.
+ * Per array and orbit, what the host wrote is uploaded and nothing else: no kernel reads a point past an orbit's length. */
+static int deep_slot_fill(fr_ctx* c, int f, bool ext, const fr_params* p, const DeepAt& at, hipStream_t stream)
 {
-    DeepOrbit& o = c->deep[f];
-    const BlaSlot& t = c->bla[f];
-    const int32_t bits = v->frac_bits ? v->frac_bits : fr_deep_frac_bits(p->zoom);
+    DeepSlot& s = deep_slot(c, ext, f);
+    DeepOrbit& o = s.o;
     const int32_t max_iter = p->max_iterations;
-    if (orbit_key_matches(o.key, v->center_x, v->center_y, bits, max_iter, p->bailout)) return FR_OK;
-    const int ps = orbit_slot_prepare(c, o, &t, stream, (size_t)max_iter + 1, sizeof(double2));
+    const int norb = kFormula[f].orbits;
+    uint64_t cb[2] = {0, 0};
+    if (f == kJulia) {
+        memcpy(&cb[0], &p->julia_c_real, sizeof(uint64_t));
+        memcpy(&cb[1], &p->julia_c_imag, sizeof(uint64_t));
+    }
+    if (orbit_key_matches(o.key, at.cx, at.cy, at.bits, max_iter, p->bailout) && o.key.c_bits[0] == cb[0] && o.key.c_bits[1] == cb[1])
+        return FR_OK;
+    const size_t point_bytes = ext ? 2 * sizeof(double2) + sizeof(int32_t) : sizeof(double2);
+    const int ps = orbit_slot_prepare(c, o, &s.t, stream, (size_t)norb * ((size_t)max_iter + 1), point_bytes);
     if (ps != FR_OK) return ps;
-    int32_t len = 0;
-    const int st = (f == kShip ? fr_deep_ship_reference_orbit : fr_deep_reference_orbit)(v, p->zoom, max_iter, p->bailout,
-                                                                                         (double*)o.host, &len);
+    const size_t cap = o.cap, second = cap / 2;                  /* a Julia slot's capacity is even */
+    double* plain = (double*)o.host;
+    double* mant = ext ? plain + 2 * cap : nullptr;
+    int32_t* exp2 = ext ? (int32_t*)(mant + 2 * cap) : nullptr;
+    const fr_deep_view v = {at.cx, at.cy, at.bits, 0};
+    const fr_deepx_view x = {at.cx, at.cy, at.zoom, at.bits, 0};
+    int32_t len[2] = {0, 0};                                      /* of the orbit at point 0, of Julia's P */
+    int st;
+    if (f == kJulia)
+        st = ext ? fr_deepx_julia_reference_orbits(&x, p->julia_c_real, p->julia_c_imag, max_iter, p->bailout, mant + 2 * second,
+                                                   exp2 + second, &len[1], mant, exp2, &len[0])
+                 : fr_deep_julia_reference_orbits(&v, p->julia_c_real, p->julia_c_imag, p->zoom, max_iter, p->bailout,
+                                                  plain + 2 * second, &len[1], plain, &len[0]);
+    else if (ext)
+        st = (f == kShip ? fr_deepx_ship_reference_orbit : fr_deepx_reference_orbit)(&x, max_iter, p->bailout, mant, exp2, &len[0]);
+    else
+        st = (f == kShip ? fr_deep_ship_reference_orbit : fr_deep_reference_orbit)(&v, p->zoom, max_iter, p->bailout, plain, &len[0]);
     if (st != FR_OK) return st;
-    FR_HIP_TRY(hipMemcpyAsync(o.dev, o.host, (size_t)len * sizeof(double2), hipMemcpyHostToDevice, stream));
+    for (int q = 0; q < norb; ++q) {
+        const size_t b = q ? second : 0, n = (size_t)len[q];
+        for (size_t i = b; ext && i < b + n; ++i) {
+            plain[2 * i] = ldexp(mant[2 * i], exp2[i]);
+            plain[2 * i + 1] = ldexp(mant[2 * i + 1], exp2[i]);
+        }
+        FR_HIP_TRY(hipMemcpyAsync(o.dev + b * sizeof(double2), o.host + b * sizeof(double2), n * sizeof(double2),
+                                  hipMemcpyHostToDevice, stream));
+        if (ext) {
+            const size_t mo = (cap + b) * sizeof(double2), eo = 2 * cap * sizeof(double2) + b * sizeof(int32_t);
+            FR_HIP_TRY(hipMemcpyAsync(o.dev + mo, o.host + mo, n * sizeof(double2), hipMemcpyHostToDevice, stream));
+            FR_HIP_TRY(hipMemcpyAsync(o.dev + eo, o.host + eo, n * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+        }
+    }
     FR_HIP_TRY(hipStreamSynchronize(stream));     /* a later render of this view may go to another stream */
-    const int ks = orbit_key_store(o.key, v->center_x, v->center_y, bits, max_iter, p->bailout);
-    if (ks == FR_OK) o.len = len;
-    return ks;
+    const int ks = orbit_key_store(o.key, at.cx, at.cy, at.bits, max_iter, p->bailout);
+    if (ks != FR_OK) return ks;
+    o.key.c_bits[0] = cb[0]; o.key.c_bits[1] = cb[1];
+    o.len = len[0]; o.len_p = len[1];
+    return FR_OK;
 }
 
 /* The frame's dcmax (the whole frame's W, H; each formula's own bound, see the header); zs = the zoom or its mantissa */
@@ -815,11 +872,6 @@ static double bla_dcmax(int f, double zs, double w, double h)
     return (1.0000001 * zs) * sqrt(ex * ex + hy * hy);
 }
 
-/* BLA: the table of the formula's cached orbit -- the extended one with x, the view's extended block -- for this frame's
- * dcmax, built on `stream` unless the slot holds it.  A rebuild overwrites the buffers in place behind the slot's last BLA
- * render (its event: the render may have gone to another stream); growing them frees the old ones, so that waits on the host
- * first.  A Julia slot (jt) holds two tables, Q's entries first and P's behind them, built from the slot's two orbits; no dcmax
- * enters them, so their key is the orbit slot's generation alone and a zoom change rebuilds nothing. */
 static int bla_levels(int32_t N) { return N > 1 ? 31 - __builtin_clz((uint32_t)(N - 1)) : 0; }   /* floor(log2(N - 1)) */
 static size_t bla_entries(int32_t N)             /* sum over k >= 1 of (N - 1) >> k */
 {
@@ -829,23 +881,28 @@ static size_t bla_entries(int32_t N)             /* sum over k >= 1 of (N - 1) >
 
 struct JuliaTables { int32_t levels_p; uint32_t base_p; };
 
-static int bla_table_for(fr_ctx* c, int f, const DeepArgs& d, const DeepXArgs* x, hipStream_t stream, int* levels,
+/* BLA: the table of the slot's cached orbit -- the extended one with x, the view's extended block -- for this frame's dcmax,
+ * built on `stream` unless the slot holds it.  A rebuild overwrites the buffers in place behind the slot's last BLA render (its
+ * event: the render may have gone to another stream); growing them frees the old ones, so that waits on the host first.  A
+ * Julia slot (jt) holds two tables, Q's entries first and P's behind them, built from the slot's two orbits; no dcmax enters
+ * them, so their key is the orbit slot's generation alone and a zoom change rebuilds nothing. */
+static int bla_table_for(fr_ctx* c, DeepSlot& s, int f, const DeepArgs& d, const DeepXArgs* x, hipStream_t stream, int* levels,
                          JuliaTables* jt)
 {
-    BlaSlot& t = (x ? c->blax : c->bla)[f];
-    const DeepOrbit& o = (x ? c->deepx : c->deep)[f];
-    const int32_t N = o.len - 1;
-    const int K = bla_levels(N);
-    *levels = K;
-    const int32_t NP = f == kJulia ? o.len_p - 1 : 1;
-    const int KP = bla_levels(NP);
-    size_t need = bla_entries(N);
+    BlaSlot& t = s.t;
+    const DeepOrbit& o = s.o;
+    const int norb = kFormula[f].orbits;
+    /* the slot's orbits as the build walks them: N, the orbit's first point, the first entry of its table */
+    struct { int32_t N; size_t point, entry; } orb[2] = {{o.len - 1, 0, 0}, {f == kJulia ? o.len_p - 1 : 1, o.cap / 2, 0}};
+    orb[1].entry = bla_entries(orb[0].N);
+    *levels = bla_levels(orb[0].N);
+    size_t need = orb[1].entry;
     if (f == kJulia) {
-        jt->levels_p = KP;
+        jt->levels_p = bla_levels(orb[1].N);
         jt->base_p = (uint32_t)need;
-        need += bla_entries(NP);
+        need += bla_entries(orb[1].N);
     }
-    if (K == 0 && KP == 0) return FR_OK;
+    if (bla_levels(orb[0].N) == 0 && bla_levels(orb[1].N) == 0) return FR_OK;
     double dcv = 0.0;
     int32_t dce = 0;
     if (f != kJulia) {
@@ -860,8 +917,7 @@ static int bla_table_for(fr_ctx* c, int f, const DeepArgs& d, const DeepXArgs* x
     memcpy(&dbits, &dcv, sizeof(dbits));
     if (t.valid && t.key_gen == o.gen && t.key_dcv == dbits && t.key_dce == dce) return FR_OK;
     t.valid = false;
-    const uint32_t n1 = (uint32_t)(N - 1);
-    const size_t nab = f == kShip ? ShipFormula::kAbPerEntry : f == kJulia ? JuliaFormula::kAbPerEntry : MandelFormula::kAbPerEntry;
+    const size_t nab = kFormula[f].ab_per_entry;
     if (need > t.cap) {
         FR_HIP_TRY(hipStreamSynchronize(stream));
         FR_HIP_TRY(hipStreamSynchronize(c->stream));
@@ -877,40 +933,34 @@ static int bla_table_for(fr_ctx* c, int f, const DeepArgs& d, const DeepXArgs* x
     } else if (t.ev_valid) {
         FR_HIP_TRY(hipStreamWaitEvent(stream, t.ev, 0));
     }
-    const uint32_t grid_cap = (uint32_t)c->compute_units * 8u;
-    for (int k = 1; k <= K && f != kJulia; ++k) {
-        const uint32_t cnt = n1 >> k;
-        uint32_t grid = (cnt + kBlockThreads - 1) / kBlockThreads;
-        if (grid > grid_cap) grid = grid_cap;
-        if (x)
-            hipLaunchKernelGGL(f == kShip ? deepx_ship_bla_level_kernel : deepx_bla_level_kernel, dim3(grid), dim3(kBlockThreads),
-                               0, stream, x->mant, x->exp2, N, k, dcv, dce, (XRad*)t.r, t.ab, t.abe);
+    /* level k of one orbit's table: each formula's kernel in either storage (Julia's take no dcmax and an int32 exponent plane) */
+    auto launch_level = [&](dim3 grid, int32_t N, int k, size_t po, size_t eo) {
+        const dim3 block(kBlockThreads);
+        if (f == kJulia && x)
+            hipLaunchKernelGGL(deepx_julia_bla_level_kernel, grid, block, 0, stream, x->mant + po, x->exp2 + po, N, k,
+                               (XRad*)t.r + eo, t.ab + eo * nab, (int32_t*)t.abe + eo);
+        else if (f == kJulia)
+            hipLaunchKernelGGL(deep_julia_bla_level_kernel, grid, block, 0, stream, d.orbit + po, N, k, (double*)t.r + eo,
+                               t.ab + eo * nab);
+        else if (x)
+            hipLaunchKernelGGL(f == kShip ? deepx_ship_bla_level_kernel : deepx_bla_level_kernel, grid, block, 0, stream, x->mant,
+                               x->exp2, N, k, dcv, dce, (XRad*)t.r, t.ab, t.abe);
         else
-            hipLaunchKernelGGL(f == kShip ? deep_ship_bla_level_kernel : deep_bla_level_kernel, dim3(grid), dim3(kBlockThreads), 0,
-                               stream, d.orbit, N, k, dcv, (double*)t.r, t.ab);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess)
-            return fr_set_error(FR_ERR_HIP, "%s%sBLA table launch failed: %s", x ? "extended " : "", f == kShip ? "ship " : "",
-                                hipGetErrorString(e));
-    }
-    for (int q = 0; q < 2 && f == kJulia; ++q) {                 /* Q's table from the orbit at point 0, then P's behind both */
-        const int32_t No = q ? NP : N;
-        const size_t po = q ? o.cap / 2 : 0, eo = q ? jt->base_p : 0;   /* the orbit's first point, the table's first entry */
-        for (int k = 1; k <= (q ? KP : K); ++k) {
-            const uint32_t cnt = (uint32_t)(No - 1) >> k;
+            hipLaunchKernelGGL(f == kShip ? deep_ship_bla_level_kernel : deep_bla_level_kernel, grid, block, 0, stream, d.orbit, N, k,
+                               dcv, (double*)t.r, t.ab);
+    };
+    const uint32_t grid_cap = (uint32_t)c->compute_units * 8u;
+    for (int q = 0; q < norb; ++q)
+        for (int k = 1; k <= bla_levels(orb[q].N); ++k) {
+            const uint32_t cnt = (uint32_t)(orb[q].N - 1) >> k;
             uint32_t grid = (cnt + kBlockThreads - 1) / kBlockThreads;
             if (grid > grid_cap) grid = grid_cap;
-            if (x)
-                hipLaunchKernelGGL(deepx_julia_bla_level_kernel, dim3(grid), dim3(kBlockThreads), 0, stream, x->mant + po,
-                                   x->exp2 + po, No, k, (XRad*)t.r + eo, t.ab + eo * nab, (int32_t*)t.abe + eo);
-            else
-                hipLaunchKernelGGL(deep_julia_bla_level_kernel, dim3(grid), dim3(kBlockThreads), 0, stream, d.orbit + po, No, k,
-                                   (double*)t.r + eo, t.ab + eo * nab);
+            launch_level(dim3(grid), orb[q].N, k, orb[q].point, orb[q].entry);
             const hipError_t e = hipGetLastError();
             if (e != hipSuccess)
-                return fr_set_error(FR_ERR_HIP, "%sJulia BLA table launch failed: %s", x ? "extended " : "", hipGetErrorString(e));
+                return fr_set_error(FR_ERR_HIP, "%s%sBLA table launch failed: %s", x ? "extended " : "",
+                                    f == kShip ? "ship " : f == kJulia ? "Julia " : "", hipGetErrorString(e));
         }
-    }
     ++t.builds;
     t.key_gen = o.gen;
     t.key_dcv = dbits;
@@ -925,35 +975,60 @@ static void bla_table_args(BlaXTable& a, const BlaSlot& t) { a.r = (const XRad*)
 template <class ARGS>
 static DeepArgs& deep_of(ARGS& a) { return const_cast<DeepArgs&>(deep_args(a)); }
 
+/* One record per argument block of an unflagged deep_kernel: the path it renders -- formula, storage, de = 1 for the blocks that
+ * carry a derivative -- the block of its flagged kernel (Bla = {the base block, the table}), the flag that selects it, and both
+ * kernels' names in messages.  launch_deep and enqueue_deep_view read everything that differs between the paths from here. */
+template <int F, bool EXT, class BLA, uint32_t FLAG, int DE = 0>
+struct DeepPathOf {
+    static constexpr int f = F, de = DE;
+    static constexpr bool ext = EXT;
+    static constexpr uint32_t flag = FLAG;
+    using Bla = BLA;
+};
+template <class BASE> struct DeepPath;
+template <> struct DeepPath<DeepArgs> : DeepPathOf<kMandel, false, DeepBlaArgs, FR_FLAG_DEEP_BLA> {
+    static constexpr const char *name = "deep_kernel<DeepArgs>", *bla_name = "deep_kernel<DeepBlaArgs>"; };
+template <> struct DeepPath<DeepDeArgs> : DeepPathOf<kMandel, false, DeepDeBlaArgs, FR_FLAG_DEEP_BLA, 1> {
+    static constexpr const char *name = "deep_kernel<DeepDeArgs>", *bla_name = "deep_kernel<DeepDeBlaArgs>"; };
+template <> struct DeepPath<DeepShipArgs> : DeepPathOf<kShip, false, DeepShipBlaArgs, FR_FLAG_DEEP_SHIP_BLA> {
+    static constexpr const char *name = "deep_kernel<DeepShipArgs>", *bla_name = "deep_kernel<DeepShipBlaArgs>"; };
+template <> struct DeepPath<DeepJuliaArgs> : DeepPathOf<kJulia, false, DeepJuliaBlaArgs, FR_FLAG_DEEP_JULIA_BLA> {
+    static constexpr const char *name = "deep_kernel<DeepJuliaArgs>", *bla_name = "deep_kernel<DeepJuliaBlaArgs>"; };
+template <> struct DeepPath<DeepXArgs> : DeepPathOf<kMandel, true, DeepXBlaArgs, FR_FLAG_DEEPX_BLA> {
+    static constexpr const char *name = "deep_kernel<DeepXArgs>", *bla_name = "deep_kernel<DeepXBlaArgs>"; };
+template <> struct DeepPath<DeepShipXArgs> : DeepPathOf<kShip, true, DeepShipXBlaArgs, FR_FLAG_DEEPX_SHIP_BLA> {
+    static constexpr const char *name = "deep_kernel<DeepShipXArgs>", *bla_name = "deep_kernel<DeepShipXBlaArgs>"; };
+template <> struct DeepPath<DeepJuliaXArgs> : DeepPathOf<kJulia, true, DeepJuliaXBlaArgs, FR_FLAG_DEEPX_JULIA_BLA> {
+    static constexpr const char *name = "deep_kernel<DeepJuliaXArgs>", *bla_name = "deep_kernel<DeepJuliaXBlaArgs>"; };
+
 /* One pass of a deep view, `base` being the argument block of its unflagged kernel: deep_kernel<BASE> at the occupancy cached in
- * wg_per_cu, or with `bla` the table, then deep_kernel<BLA> (BLA = {BASE, the table}) on the same queue plan at its slot's own
- * occupancy, its counters cleared in front of it and copied to pinned memory behind it.  The slot's event is recorded behind
- * every such render unless the stream is capturing: table rebuilds and orbit uploads wait for it.  bla_wg_per_cu: the occupancy
- * word of a flagged kernel that shares its slot with another (fr_render_deep_de). */
-template <class BLA, class BASE>
-static int launch_deep(fr_ctx* c, hipStream_t stream, const char* name, const char* bla_name, BASE& base, bool bla, int& wg_per_cu,
-                       int* bla_wg_per_cu = nullptr)
+ * its slot, or with `bla` the table, then the path's flagged kernel on the same queue plan at its own occupancy, its counters
+ * cleared in front of it and copied to pinned memory behind it.  The slot's event is recorded behind every such render unless
+ * the stream is capturing: table rebuilds and orbit uploads wait for it. */
+template <class BASE>
+static int launch_deep(fr_ctx* c, hipStream_t stream, BASE& base, bool bla)
 {
+    using P = DeepPath<BASE>;
+    using BLA = typename P::Bla;
+    DeepSlot& s = deep_slot(c, P::ext, P::f);
     if (!bla) {
         DeepArgs& d = deep_of(base);
-        return launch_one_pass(c, stream, name, deep_kernel<BASE>, base, d.g, d.q, wg_per_cu, false);
+        return launch_one_pass(c, stream, P::name, deep_kernel<BASE>, base, d.g, d.q, s.wg_per_cu[P::de][0], false);
     }
-    constexpr int f = is_any_of<BASE, DeepShipArgs, DeepShipXArgs> ? kShip : is_any_of<BASE, DeepJuliaArgs, DeepJuliaXArgs> ? kJulia : kMandel;
-    constexpr bool ext = is_any_of<BASE, DeepXArgs, DeepShipXArgs, DeepJuliaXArgs>;
     BLA a;
     memset(&a, 0, sizeof(a));
     auto& [b, tabs] = a;
     b = base;
     DeepArgs& d = deep_of(a);
     const DeepXArgs* x = nullptr;
-    if constexpr (ext) x = &deepx_args(a);
-    BlaSlot& t = (ext ? c->blax : c->bla)[f];
+    if constexpr (P::ext) x = &deepx_args(a);
+    BlaSlot& t = s.t;
     int levels = 0;
     JuliaTables jt = {0, 0u};
-    const int ts = bla_table_for(c, f, d, x, stream, &levels, &jt);
+    const int ts = bla_table_for(c, s, P::f, d, x, stream, &levels, &jt);
     if (ts != FR_OK) return ts;
     auto& tab = q_table(tabs);
-    if constexpr (f == kJulia) { tabs.levels_p = jt.levels_p; tabs.base_p = jt.base_p; }
+    if constexpr (P::f == kJulia) { tabs.levels_p = jt.levels_p; tabs.base_p = jt.base_p; }
     bla_table_args(tab, t);
     tab.levels = levels;
     if (!t.steps_dev) {
@@ -962,8 +1037,7 @@ static int launch_deep(fr_ctx* c, hipStream_t stream, const char* name, const ch
     }
     tab.steps = t.steps_dev;
     FR_HIP_TRY(hipMemsetAsync(t.steps_dev, 0, 3 * sizeof(unsigned long long), stream));
-    const int st = launch_one_pass(c, stream, bla_name, deep_kernel<BLA>, a, d.g, d.q, bla_wg_per_cu ? *bla_wg_per_cu : t.wg_per_cu,
-                                   false);
+    const int st = launch_one_pass(c, stream, P::bla_name, deep_kernel<BLA>, a, d.g, d.q, s.wg_per_cu[P::de][1], false);
     if (st != FR_OK) return st;
     FR_HIP_TRY(hipMemcpyAsync(t.steps_host, t.steps_dev, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
     t.have_steps = true;
@@ -977,7 +1051,7 @@ static int launch_deep(fr_ctx* c, hipStream_t stream, const char* name, const ch
     return FR_OK;
 }
 
-/* everything of DeepArgs that enqueue_deep and enqueue_deepx_at fill alike: zoom and the orbit stay with the caller */
+/* everything of DeepArgs that does not depend on the path: the zoom and the orbit stay with enqueue_deep_view */
 static void fill_deep_args(DeepArgs& a, const fr_ctx* c, const fr_params* p, const TileGeom& g, float* rgba, void* nu,
                            int32_t* iter)
 {
@@ -996,250 +1070,53 @@ static void fill_deep_args(DeepArgs& a, const fr_ctx* c, const fr_params* p, con
     a.rgba = reinterpret_cast<float4*>(rgba); a.nu = (double*)nu; a.iter = iter;
 }
 
-/* fr_render_deep (f = kMandel), fr_render_deep_ship (f = kShip) */
-static int enqueue_deep(fr_ctx* c, int f, const fr_params* p, const fr_deep_view* v, uint32_t W, uint32_t H, const fr_shard* shard,
-                        float* rgba, void* nu, int32_t* iter, hipStream_t stream, bool out_frame)
+/* Every deep render, BASE being the argument block of the path's unflagged kernel (DeepPath): the rows of this part, the orbit(s)
+ * in the path's slot, the block filled -- the orbit, in the extended storage its mantissas, exponents and the zoom pair, Julia's
+ * second orbit, log(bailout) where the block has one (as fill_params) -- then `extra` for what only one block carries
+ * (fr_render_deep_de's derivative) and the launch, with the table when p carries the path's flag. */
+template <class BASE, class Extra>
+static int enqueue_deep_view(fr_ctx* c, const fr_params* p, const DeepAt& at, uint32_t W, uint32_t H, const fr_shard* shard,
+                             float* rgba, void* nu, int32_t* iter, hipStream_t stream, bool out_frame, Extra&& extra)
 {
+    using P = DeepPath<BASE>;
     fr_shard norm;
     uint32_t rows_local = 0;
     const int sh = begin_shard(c, shard, H, &norm, &rows_local);
     if (sh != FR_OK || rows_local == 0) return sh;
-    const int os = orbit_slot_fill(c, f, p, v, stream);
+    const int os = deep_slot_fill(c, P::f, P::ext, p, at, stream);
     if (os != FR_OK) return os;
 
-    DeepOrbit& o = c->deep[f];
-    DeepShipArgs s;
-    memset(&s, 0, sizeof(s));
-    DeepArgs& a = s.d;
+    const DeepOrbit& o = deep_slot(c, P::ext, P::f).o;
+    BASE b;
+    memset(&b, 0, sizeof(b));
+    DeepArgs& a = deep_of(b);
     a.orbit = reinterpret_cast<const double2*>(o.dev); a.n_ref = o.len - 1;
-    a.zoom = p->zoom;
-    fill_deep_args(a, c, p, tile_geom(W, H, rows_local, &norm, out_frame), rgba, nu, iter);
-    s.log_bailout = log((double)p->bailout);     /* as fill_params */
-    if (f == kShip)
-        return launch_deep<DeepShipBlaArgs>(c, stream, "deep_kernel<DeepShipArgs>", "deep_kernel<DeepShipBlaArgs>", s,
-                                            (p->flags & FR_FLAG_DEEP_SHIP_BLA) != 0, o.wg_per_cu);
-    return launch_deep<DeepBlaArgs>(c, stream, "deep_kernel<DeepArgs>", "deep_kernel<DeepBlaArgs>", a,
-                                    (p->flags & FR_FLAG_DEEP_BLA) != 0, o.wg_per_cu);
-}
-
-/* fr_render_deep_de: enqueue_deep's Mandelbrot path -- its orbit slot, its table, its step counts -- with the derivative's
- * argument block around DeepArgs.  s = zoom / H of the whole frame, whatever rows this part owns. */
-static int enqueue_deep_de(fr_ctx* c, const fr_params* p, const fr_deep_view* v, const fr_deep_de* e, uint32_t W, uint32_t H,
-                           const fr_shard* shard, float* rgba, void* nu, int32_t* iter, double* de, double* deriv,
-                           hipStream_t stream, bool out_frame)
-{
-    fr_shard norm;
-    uint32_t rows_local = 0;
-    const int sh = begin_shard(c, shard, H, &norm, &rows_local);
-    if (sh != FR_OK || rows_local == 0) return sh;
-    const int os = orbit_slot_fill(c, kMandel, p, v, stream);
-    if (os != FR_OK) return os;
-
-    DeepOrbit& o = c->deep[kMandel];
-    DeepDeArgs a;
-    memset(&a, 0, sizeof(a));
-    a.d.orbit = reinterpret_cast<const double2*>(o.dev); a.d.n_ref = o.len - 1;
-    a.d.zoom = p->zoom;
-    fill_deep_args(a.d, c, p, tile_geom(W, H, rows_local, &norm, out_frame), rgba, nu, iter);
-    a.s = p->zoom / (double)H;
-    a.de = de; a.deriv = deriv;
-    a.shade = e->shade; a.edge_px = e->edge_px;
-    return launch_deep<DeepDeBlaArgs>(c, stream, "deep_kernel<DeepDeArgs>", "deep_kernel<DeepDeBlaArgs>", a,
-                                      (p->flags & FR_FLAG_DEEP_BLA) != 0, c->deep_de_wg_per_cu[0], &c->deep_de_wg_per_cu[1]);
-}
-
-/* ---- extended views (fr_render_deepx, fr_render_deepx_ship) -----------------------------------------------------------
- * enqueue_deep with the orbit in the extended storage: the mantissa pairs and exponents of the formula's reference orbit,
- * and the plain doubles ldexp(mantissa, exponent) formed here on the host, in one upload into the formula's extended cache
- * slot (orbit_slot_fill's counterpart). */
-static int xorbit_slot_fill(fr_ctx* c, int f, const fr_params* p, const fr_deepx_view* v, int32_t bits, hipStream_t stream)
-{
-    DeepOrbit& o = c->deepx[f];
-    const BlaSlot& t = c->blax[f];
-    const int32_t max_iter = p->max_iterations;
-    if (orbit_key_matches(o.key, v->center_x, v->center_y, bits, max_iter, p->bailout)) return FR_OK;
-    const size_t point_bytes = 2 * sizeof(double2) + sizeof(int32_t);
-    const int ps = orbit_slot_prepare(c, o, &t, stream, (size_t)max_iter + 1, point_bytes);
-    if (ps != FR_OK) return ps;
-    const size_t cap = o.cap;
-    double* plain = (double*)o.host;
-    double* mant = plain + 2 * cap;
-    int32_t* exp2 = (int32_t*)(mant + 2 * cap);
-    int32_t len = 0;
-    fr_deepx_view w = *v;
-    w.frac_bits = bits;
-    const int st = (f == kShip ? fr_deepx_ship_reference_orbit : fr_deepx_reference_orbit)(&w, max_iter, p->bailout, mant, exp2,
-                                                                                           &len);
-    if (st != FR_OK) return st;
-    for (int32_t n = 0; n < len; ++n) {
-        plain[2 * n] = ldexp(mant[2 * n], exp2[n]);
-        plain[2 * n + 1] = ldexp(mant[2 * n + 1], exp2[n]);
+    if constexpr (P::ext) {                                      /* (d.zoom is not read) */
+        DeepXArgs& x = const_cast<DeepXArgs&>(deepx_args(b));
+        x.mant = a.orbit + o.cap;
+        x.exp2 = reinterpret_cast<const int32_t*>(x.mant + o.cap);
+        x.zm = at.zm;
+        x.ze = at.ze;
+    } else {
+        a.zoom = p->zoom;
     }
-    FR_HIP_TRY(hipMemcpyAsync(o.dev, o.host, cap * point_bytes, hipMemcpyHostToDevice, stream));
-    FR_HIP_TRY(hipStreamSynchronize(stream));     /* a later render of this view may go to another stream */
-    const int ks = orbit_key_store(o.key, v->center_x, v->center_y, bits, max_iter, p->bailout);
-    if (ks == FR_OK) o.len = len;
-    return ks;
+    if constexpr (P::f == kJulia) { b.j.p_off = (int32_t)(o.cap / 2); b.j.n_p = o.len_p - 1; }
+    fill_deep_args(a, c, p, tile_geom(W, H, rows_local, &norm, out_frame), rgba, nu, iter);
+    if constexpr (P::f != kMandel) b.log_bailout = log((double)p->bailout);
+    extra(b);
+    return launch_deep(c, stream, b, (p->flags & P::flag) != 0);
 }
 
 /* the extended view already resolved: v gives the centre strings (and a zoom string the orbit does not depend on), the
- * zoom is (zm, ze) and the orbit's fraction bits are `bits` -- what fr_render_deepx / fr_render_deepx_ship and the frames of a
- * fr_deep_sequence of the formula share */
+ * zoom is (zm, ze) and the orbit's fraction bits are `bits` -- what the frames of a fr_deep_sequence of the formula ask for */
 static int enqueue_deepx_at(fr_ctx* c, int f, const fr_params* p, const fr_deepx_view* v, double zm, int32_t ze, int32_t bits,
                             uint32_t W, uint32_t H, const fr_shard* shard, float* rgba, void* nu, int32_t* iter,
                             hipStream_t stream, bool out_frame)
 {
-    fr_shard norm;
-    uint32_t rows_local = 0;
-    const int sh = begin_shard(c, shard, H, &norm, &rows_local);
-    if (sh != FR_OK || rows_local == 0) return sh;
-    DeepShipXArgs s;
-    memset(&s, 0, sizeof(s));
-    DeepXArgs& x = s.x;
-    x.zm = zm;
-    x.ze = ze;
-    const int os = xorbit_slot_fill(c, f, p, v, bits, stream);
-    if (os != FR_OK) return os;
-
-    DeepOrbit& o = c->deepx[f];
-    DeepArgs& a = x.d;
-    a.orbit = reinterpret_cast<const double2*>(o.dev);
-    x.mant = a.orbit + o.cap;
-    x.exp2 = reinterpret_cast<const int32_t*>(x.mant + o.cap);
-    a.n_ref = o.len - 1;
-    fill_deep_args(a, c, p, tile_geom(W, H, rows_local, &norm, out_frame), rgba, nu, iter);
-    s.log_bailout = log((double)p->bailout);     /* as fill_params */
+    const DeepAt at = {v->center_x, v->center_y, v->zoom, zm, ze, bits};
     if (f == kShip)
-        return launch_deep<DeepShipXBlaArgs>(c, stream, "deep_kernel<DeepShipXArgs>", "deep_kernel<DeepShipXBlaArgs>", s,
-                                             (p->flags & FR_FLAG_DEEPX_SHIP_BLA) != 0, o.wg_per_cu);
-    return launch_deep<DeepXBlaArgs>(c, stream, "deep_kernel<DeepXArgs>", "deep_kernel<DeepXBlaArgs>", x,
-                                     (p->flags & FR_FLAG_DEEPX_BLA) != 0, o.wg_per_cu);
-}
-
-static int enqueue_deepx(fr_ctx* c, int f, const fr_params* p, const fr_deepx_view* v, uint32_t W, uint32_t H,
-                         const fr_shard* shard, float* rgba, void* nu, int32_t* iter, hipStream_t stream, bool out_frame)
-{
-    double zm = 0.0;
-    int32_t ze = 0, bits = 0;
-    const int rs = fr_deepx_resolve(v, &zm, &ze, &bits);
-    if (rs != FR_OK) return rs;
-    return enqueue_deepx_at(c, f, p, v, zm, ze, bits, W, H, shard, rgba, nu, iter, stream, out_frame);
-}
-
-/* ---- Julia views (fr_render_deep_julia, fr_render_deepx_julia) ---------------------------------------------------------
- * Two orbits per slot (the header's P and Q), keyed by the bits of c as well.  ext: the extended storage, `zoom` then being the
- * view's zoom string. */
-static int julia_slot_fill(fr_ctx* c, bool ext, const fr_params* p, const char* cx, const char* cy, const char* zoom,
-                           int32_t bits, hipStream_t stream)
-{
-    DeepOrbit& o = (ext ? c->deepx : c->deep)[kJulia];
-    const int32_t max_iter = p->max_iterations;
-    uint64_t cb[2];
-    memcpy(&cb[0], &p->julia_c_real, sizeof(uint64_t));
-    memcpy(&cb[1], &p->julia_c_imag, sizeof(uint64_t));
-    if (orbit_key_matches(o.key, cx, cy, bits, max_iter, p->bailout) && o.key.c_bits[0] == cb[0] && o.key.c_bits[1] == cb[1])
-        return FR_OK;
-    const size_t point_bytes = ext ? 2 * sizeof(double2) + sizeof(int32_t) : sizeof(double2);
-    const int ps = orbit_slot_prepare(c, o, &(ext ? c->blax : c->bla)[kJulia], stream, 2 * ((size_t)max_iter + 1),
-                                      point_bytes);              /* an even capacity */
-    if (ps != FR_OK) return ps;
-    const size_t cap = o.cap, half = cap / 2;
-    double* plain = (double*)o.host;
-    int32_t len_p = 0, len_q = 0;
-    int st;
-    if (ext) {
-        double* mant = plain + 2 * cap;
-        int32_t* exp2 = (int32_t*)(mant + 2 * cap);
-        const fr_deepx_view w = {cx, cy, zoom, bits, 0};
-        st = fr_deepx_julia_reference_orbits(&w, p->julia_c_real, p->julia_c_imag, max_iter, p->bailout, mant + 2 * half,
-                                             exp2 + half, &len_p, mant, exp2, &len_q);
-        if (st != FR_OK) return st;
-        for (const size_t b : {(size_t)0, half}) {
-            const int32_t len = b ? len_p : len_q;
-            for (int32_t n = 0; n < len; ++n) {
-                plain[2 * (b + n)] = ldexp(mant[2 * (b + n)], exp2[b + n]);
-                plain[2 * (b + n) + 1] = ldexp(mant[2 * (b + n) + 1], exp2[b + n]);
-            }
-        }
-    } else {
-        const fr_deep_view w = {cx, cy, bits, 0};
-        st = fr_deep_julia_reference_orbits(&w, p->julia_c_real, p->julia_c_imag, p->zoom, max_iter, p->bailout, plain + 2 * half,
-                                            &len_p, plain, &len_q);
-        if (st != FR_OK) return st;
-    }
-    /* what the host wrote, nothing else: per array, Q's points at 0 and P's at `half` */
-    for (const size_t b : {(size_t)0, half}) {
-        const size_t len = (size_t)(b ? len_p : len_q);
-        FR_HIP_TRY(hipMemcpyAsync(o.dev + b * sizeof(double2), o.host + b * sizeof(double2), len * sizeof(double2),
-                                  hipMemcpyHostToDevice, stream));
-        if (ext) {
-            const size_t mo = (cap + b) * sizeof(double2), eo = 2 * cap * sizeof(double2) + b * sizeof(int32_t);
-            FR_HIP_TRY(hipMemcpyAsync(o.dev + mo, o.host + mo, len * sizeof(double2), hipMemcpyHostToDevice, stream));
-            FR_HIP_TRY(hipMemcpyAsync(o.dev + eo, o.host + eo, len * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-        }
-    }
-    FR_HIP_TRY(hipStreamSynchronize(stream));     /* a later render of this view may go to another stream */
-    const int ks = orbit_key_store(o.key, cx, cy, bits, max_iter, p->bailout);
-    if (ks != FR_OK) return ks;
-    o.key.c_bits[0] = cb[0]; o.key.c_bits[1] = cb[1];
-    o.len = len_q; o.len_p = len_p;
-    return FR_OK;
-}
-
-static int enqueue_deep_julia(fr_ctx* c, const fr_params* p, const fr_deep_view* v, uint32_t W, uint32_t H, const fr_shard* shard,
-                              float* rgba, void* nu, int32_t* iter, hipStream_t stream, bool out_frame)
-{
-    fr_shard norm;
-    uint32_t rows_local = 0;
-    const int sh = begin_shard(c, shard, H, &norm, &rows_local);
-    if (sh != FR_OK || rows_local == 0) return sh;
-    const int32_t bits = v->frac_bits ? v->frac_bits : fr_deep_frac_bits(p->zoom);
-    const int os = julia_slot_fill(c, false, p, v->center_x, v->center_y, nullptr, bits, stream);
-    if (os != FR_OK) return os;
-
-    DeepOrbit& o = c->deep[kJulia];
-    DeepJuliaArgs j;
-    memset(&j, 0, sizeof(j));
-    DeepArgs& a = j.d;
-    a.orbit = reinterpret_cast<const double2*>(o.dev); a.n_ref = o.len - 1;
-    a.zoom = p->zoom;
-    j.j.p_off = (int32_t)(o.cap / 2); j.j.n_p = o.len_p - 1;
-    fill_deep_args(a, c, p, tile_geom(W, H, rows_local, &norm, out_frame), rgba, nu, iter);
-    j.log_bailout = log((double)p->bailout);     /* as fill_params */
-    return launch_deep<DeepJuliaBlaArgs>(c, stream, "deep_kernel<DeepJuliaArgs>", "deep_kernel<DeepJuliaBlaArgs>", j,
-                                         (p->flags & FR_FLAG_DEEP_JULIA_BLA) != 0, o.wg_per_cu);
-}
-
-static int enqueue_deepx_julia(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, uint32_t W, uint32_t H,
-                               const fr_shard* shard, float* rgba, void* nu, int32_t* iter, hipStream_t stream, bool out_frame)
-{
-    double zm = 0.0;
-    int32_t ze = 0, bits = 0;
-    const int rs = fr_deepx_resolve(v, &zm, &ze, &bits);
-    if (rs != FR_OK) return rs;
-    fr_shard norm;
-    uint32_t rows_local = 0;
-    const int sh = begin_shard(c, shard, H, &norm, &rows_local);
-    if (sh != FR_OK || rows_local == 0) return sh;
-    const int os = julia_slot_fill(c, true, p, v->center_x, v->center_y, v->zoom, bits, stream);
-    if (os != FR_OK) return os;
-
-    DeepOrbit& o = c->deepx[kJulia];
-    DeepJuliaXArgs j;
-    memset(&j, 0, sizeof(j));
-    DeepXArgs& x = j.x;
-    x.zm = zm;
-    x.ze = ze;
-    DeepArgs& a = x.d;
-    a.orbit = reinterpret_cast<const double2*>(o.dev);
-    x.mant = a.orbit + o.cap;
-    x.exp2 = reinterpret_cast<const int32_t*>(x.mant + o.cap);
-    a.n_ref = o.len - 1;
-    j.j.p_off = (int32_t)(o.cap / 2); j.j.n_p = o.len_p - 1;
-    fill_deep_args(a, c, p, tile_geom(W, H, rows_local, &norm, out_frame), rgba, nu, iter);
-    j.log_bailout = log((double)p->bailout);     /* as fill_params */
-    return launch_deep<DeepJuliaXBlaArgs>(c, stream, "deep_kernel<DeepJuliaXArgs>", "deep_kernel<DeepJuliaXBlaArgs>", j,
-                                          (p->flags & FR_FLAG_DEEPX_JULIA_BLA) != 0, o.wg_per_cu);
+        return enqueue_deep_view<DeepShipXArgs>(c, p, at, W, H, shard, rgba, nu, iter, stream, out_frame, [](auto&) {});
+    return enqueue_deep_view<DeepXArgs>(c, p, at, W, H, shard, rgba, nu, iter, stream, out_frame, [](auto&) {});
 }
 
 /* ---- deep zoom sequences (fr_deep_sequence; the rules are in the header, the host planning in fr_deepseq.c) ---------------
@@ -1338,7 +1215,7 @@ static int seq_enqueue(fr_deep_sequence* q, const fr_params* p, const fr_deep_se
                        int32_t* iter, hipStream_t s)
 {
     fr_ctx* c = q->c;
-    const uint64_t& gen = c->deepx[q->ship ? kShip : kMandel].gen;
+    const uint64_t& gen = deep_slot(c, true, q->ship ? kShip : kMandel).o.gen;
     const uint64_t gen0 = gen;
     const bool timed = c->timing;
     if (timed) FR_HIP_TRY(hipEventRecord(c->ev_begin, s));
@@ -1635,10 +1512,10 @@ static int enqueue_ssaa_staged(fr_ctx* c, const fr_params* p, uint32_t W, uint32
 }
 
 /* ---- render entry points --------------------------------------------------------------------------------------------
- * fr_render_shard, fr_render_phoenix, fr_render_mandelbulb, fr_render_deep, fr_render_deep_ship, fr_render_deepx and
- * fr_render_deepx_ship, each with its _async form (fr_render_deep_de has two planes more and its own two functions):
- * their parameter checks, then render_sync / render_async with the enqueue step as
- * enqueue(shard, rgba, nu, iter, stream, out_frame) */
+ * fr_render_shard, fr_render_phoenix, fr_render_mandelbulb and the seven deep entry points (fr_render_deep, _deep_de,
+ * _deep_ship, _deepx, _deepx_ship, _deep_julia, _deepx_julia; all through deep_entry), each with its _async form: their
+ * parameter checks, then render_sync / render_async with the planes beyond fr_output's three (ExtraPlanes; fr_render_deep_de
+ * alone has any) and the enqueue step as enqueue(shard, rgba, nu, iter, extra planes, stream, out_frame) */
 static int check_common(fr_ctx* c, const fr_params* p, uint32_t W, uint32_t H, const fr_output* out)
 {
     if (!c) return fr_set_error(FR_ERR_INVALID_ARG, "ctx is NULL");
@@ -1671,44 +1548,57 @@ static int check_layout(const fr_output* out)
     return FR_OK;
 }
 
+/* The planes an entry point writes beyond fr_output's three (fr_render_deep_de: deriv, de): where each goes (NULL: not asked
+ * for) and its bytes per pixel, a power of two.  They follow out->memory and out->layout as nu does, any one plane of the
+ * render is enough, and `none` is the message of a render that has none. */
+enum { kMaxExtraPlanes = 2 };
+struct ExtraPlanes {
+    int n = 0;
+    struct { void* dst; size_t bytes; } plane[kMaxExtraPlanes] = {};
+    const char* none = "fr_output has no plane to write";
+};
+
 /* 1: this part owns rows and has a plane to write; 0: it owns no rows (nothing to do); < 0: error */
-static int check_planes(const fr_shard* shard, uint32_t H, const fr_output* out)
+static int check_planes(const fr_shard* shard, uint32_t H, const fr_output* out, const ExtraPlanes& extra)
 {
     if (shard && shard->nparts && shard->part >= shard->nparts)
         return fr_set_error(FR_ERR_INVALID_ARG, "shard part %u >= nparts %u", shard->part, shard->nparts);
     if (fr_shard_rows(shard, H) == 0) return 0;
-    if (!out->rgba && !out->nu && !out->iter)
-        return fr_set_error(FR_ERR_INVALID_ARG, "fr_output has no plane to write");
+    bool any = out->rgba || out->nu || out->iter;
+    for (int i = 0; i < extra.n; ++i) any = any || extra.plane[i].dst;
+    if (!any) return fr_set_error(FR_ERR_INVALID_ARG, "%s", extra.none);
     return 1;
 }
 
 /* device planes only, on the caller's stream (NULL: the context's); returns once the render is enqueued */
 template <class Enqueue>
-static int render_async(const char* entry, fr_ctx* c, uint32_t H, const fr_shard* shard, const fr_output* out, void* hip_stream,
-                        Enqueue&& enqueue)
+static int render_async(const char* entry, fr_ctx* c, uint32_t H, const fr_shard* shard, const fr_output* out,
+                        const ExtraPlanes& extra, void* hip_stream, Enqueue&& enqueue)
 {
     int st = check_layout(out);
     if (st != FR_OK) return st;
     if (out->memory != FR_MEM_DEVICE)
         return fr_set_error(FR_ERR_INVALID_ARG, "%s needs FR_MEM_DEVICE outputs", entry);
-    st = check_planes(shard, H, out);
+    st = check_planes(shard, H, out, extra);
     if (st <= 0) return st;
     FR_HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    st = enqueue(shard, out->rgba, out->nu, out->iter, s, out->layout == FR_LAYOUT_FRAME);
+    void* xp[kMaxExtraPlanes] = {extra.plane[0].dst, extra.plane[1].dst};
+    st = enqueue(shard, out->rgba, out->nu, out->iter, xp, s, out->layout == FR_LAYOUT_FRAME);
     if (st == FR_OK) c->render_on_user_stream = s != c->stream;
     return st;
 }
 
 /* on the context's stream, waited for: device planes are written in place, host planes are staged through device scratch
- * owned by the context (PCIe-inclusive path) */
+ * owned by the context (PCIe-inclusive path): rgba, nu, iter at the offsets they always had, each extra plane behind them at
+ * the next multiple of its element size */
 template <class Enqueue>
 static int render_sync(fr_ctx* c, const fr_params* p, uint32_t W, uint32_t H, const fr_shard* shard, const fr_output* out,
-                       Enqueue&& enqueue)
+                       const ExtraPlanes& extra, Enqueue&& enqueue)
 {
     int st = check_layout(out);
     if (st != FR_OK) return st;
-    st = check_planes(shard, H, out);
+    st = check_planes(shard, H, out, extra);
     if (st <= 0) return st;
     FR_HIP_TRY(hipSetDevice(c->device));
     const bool host = out->memory == FR_MEM_HOST;
@@ -1717,22 +1607,32 @@ static int render_sync(fr_ctx* c, const fr_params* p, uint32_t W, uint32_t H, co
     float* rgba = out->rgba; void* nu = out->nu; int32_t* iter = out->iter;
     const size_t npx = (size_t)fr_shard_rows(shard, H) * W;
     const size_t nu_bytes = (p->precision == FR_PRECISION_F64 && p->fractal_type != FR_FRACTAL_DEEP_ZOOM) ? 8 : 4;
+    void* xp[kMaxExtraPlanes] = {extra.plane[0].dst, extra.plane[1].dst};
     if (host) {
-        const size_t off_nu = npx * 16, off_iter = off_nu + npx * 8, need = off_iter + npx * 4;
+        const size_t off_nu = npx * 16, off_iter = off_nu + npx * 8;
+        size_t need = off_iter + npx * 4, off_x[kMaxExtraPlanes] = {0, 0};
+        for (int i = 0; i < extra.n; ++i) {
+            off_x[i] = (need + extra.plane[i].bytes - 1) / extra.plane[i].bytes * extra.plane[i].bytes;
+            need = off_x[i] + npx * extra.plane[i].bytes;
+        }
         const int gs = grow_device(&c->scratch, &c->scratch_bytes, need);
         if (gs != FR_OK) return gs;
         char* base = (char*)c->scratch;
         rgba = out->rgba ? (float*)base : nullptr;
         nu = out->nu ? (void*)(base + off_nu) : nullptr;
         iter = out->iter ? (int32_t*)(base + off_iter) : nullptr;
+        for (int i = 0; i < extra.n; ++i) xp[i] = extra.plane[i].dst ? base + off_x[i] : nullptr;
     }
-    st = enqueue(shard, rgba, nu, iter, c->stream, out->layout == FR_LAYOUT_FRAME);   /* (host planes are packed) */
+    st = enqueue(shard, rgba, nu, iter, xp, c->stream, out->layout == FR_LAYOUT_FRAME);   /* (host planes are packed) */
     if (st != FR_OK) return st;
     c->render_on_user_stream = false;
     if (host) {
         if (out->rgba) FR_HIP_TRY(hipMemcpyAsync(out->rgba, rgba, npx * 16, hipMemcpyDeviceToHost, c->stream));
         if (out->nu) FR_HIP_TRY(hipMemcpyAsync(out->nu, nu, npx * nu_bytes, hipMemcpyDeviceToHost, c->stream));
         if (out->iter) FR_HIP_TRY(hipMemcpyAsync(out->iter, iter, npx * 4, hipMemcpyDeviceToHost, c->stream));
+        for (int i = 0; i < extra.n; ++i)
+            if (extra.plane[i].dst)
+                FR_HIP_TRY(hipMemcpyAsync(extra.plane[i].dst, xp[i], npx * extra.plane[i].bytes, hipMemcpyDeviceToHost, c->stream));
     }
     FR_HIP_TRY(hipStreamSynchronize(c->stream));
     return check_overflow(c);
@@ -1743,8 +1643,8 @@ extern "C" int fr_render_shard_async(fr_ctx* c, const fr_params* p, uint32_t W, 
 {
     const int st = check_common(c, p, W, H, out);
     if (st != FR_OK) return st;
-    return render_async("fr_render_shard_async", c, H, shard, out, hip_stream,
-                        [&](auto sh, auto rgba, auto nu, auto iter, auto s, bool out_frame) {
+    return render_async("fr_render_shard_async", c, H, shard, out, {}, hip_stream,
+                        [&](auto sh, auto rgba, auto nu, auto iter, auto, auto s, bool out_frame) {
                             return enqueue_render(c, p, W, H, sh, rgba, nu, iter, s, false, out_frame); });
 }
 
@@ -1827,7 +1727,7 @@ extern "C" int fr_plan_describe(const fr_params* p, uint32_t W, uint32_t H, cons
 static int last_bla_steps(fr_ctx* c, bool ext, int f, const char* what, uint64_t out[3])
 {
     if (!c || !out) return fr_set_error(FR_ERR_INVALID_ARG, "ctx/out is NULL");
-    const BlaSlot& t = (ext ? c->blax : c->bla)[f];
+    const BlaSlot& t = deep_slot(c, ext, f).t;
     if (!t.have_steps) return fr_set_error(FR_ERR_UNSUPPORTED, "no %s on this context yet", what);
     for (int i = 0; i < 3; ++i) out[i] = (uint64_t)t.steps_host[i];
     return FR_OK;
@@ -1837,16 +1737,16 @@ static int last_bla_steps(fr_ctx* c, bool ext, int f, const char* what, uint64_t
 static int64_t read_bla_table(fr_ctx* c, bool ext, int f, void* r, double* ab, int32_t* ab_exp, int64_t n)
 {
     if (!c) return fr_set_error(FR_ERR_INVALID_ARG, "ctx is NULL");
-    const BlaSlot& t = (ext ? c->blax : c->bla)[f];
+    const BlaSlot& t = deep_slot(c, ext, f).t;
     if (!t.valid) return 0;
-    const DeepOrbit& o = (ext ? c->deepx : c->deep)[f];
+    const DeepOrbit& o = deep_slot(c, ext, f).o;
     int64_t have = (int64_t)bla_entries(o.len - 1);
     if (f == kJulia) {                                            /* Q's entries, then P's; none once the slot's orbits changed */
         if (t.key_gen != o.gen) return 0;
         have += (int64_t)bla_entries(o.len_p - 1);
     }
     if (n > have) n = have;
-    const size_t nab = f == kShip ? ShipFormula::kAbPerEntry : f == kJulia ? JuliaFormula::kAbPerEntry : MandelFormula::kAbPerEntry;
+    const size_t nab = kFormula[f].ab_per_entry;
     const size_t nexp = f == kJulia ? sizeof(int32_t) : sizeof(int2);
     FR_HIP_TRY(hipSetDevice(c->device));
     FR_HIP_TRY(hipDeviceSynchronize());
@@ -1879,7 +1779,7 @@ extern "C" int fr_ctx_last_deepx_ship_steps(fr_ctx* c, uint64_t out[3])
 extern "C" int64_t fr_deep_bla_builds(fr_ctx* c, int extended, int formula)
 {
     if (!c || formula < kMandel || formula > kJulia) return fr_set_error(FR_ERR_INVALID_ARG, "ctx is NULL or no such formula");
-    return (int64_t)(extended ? c->blax : c->bla)[formula].builds;
+    return (int64_t)deep_slot(c, extended != 0, formula).t.builds;
 }
 
 extern "C" int fr_ctx_last_deep_julia_steps(fr_ctx* c, uint64_t out[3])
@@ -1947,7 +1847,7 @@ extern "C" int fr_render_shard(fr_ctx* c, const fr_params* p, uint32_t W, uint32
 {
     const int st = check_common(c, p, W, H, out);
     if (st != FR_OK) return st;
-    return render_sync(c, p, W, H, shard, out, [&](auto sh, auto rgba, auto nu, auto iter, auto s, bool out_frame) {
+    return render_sync(c, p, W, H, shard, out, {}, [&](auto sh, auto rgba, auto nu, auto iter, auto, auto s, bool out_frame) {
         return enqueue_render(c, p, W, H, sh, rgba, nu, iter, s, false, out_frame); });
 }
 
@@ -1961,8 +1861,8 @@ extern "C" int fr_render_phoenix_async(fr_ctx* c, const fr_params* p, const fr_p
 {
     const int st = check_phoenix(c, p, ph, W, H, out);
     if (st != FR_OK) return st;
-    return render_async("fr_render_phoenix_async", c, H, shard, out, hip_stream,
-                        [&](auto sh, auto rgba, auto nu, auto iter, auto s, bool out_frame) {
+    return render_async("fr_render_phoenix_async", c, H, shard, out, {}, hip_stream,
+                        [&](auto sh, auto rgba, auto nu, auto iter, auto, auto s, bool out_frame) {
                             return enqueue_phoenix(c, p, ph, W, H, sh, rgba, nu, iter, s, out_frame); });
 }
 
@@ -1971,7 +1871,7 @@ extern "C" int fr_render_phoenix(fr_ctx* c, const fr_params* p, const fr_phoenix
 {
     const int st = check_phoenix(c, p, ph, W, H, out);
     if (st != FR_OK) return st;
-    return render_sync(c, p, W, H, shard, out, [&](auto sh, auto rgba, auto nu, auto iter, auto s, bool out_frame) {
+    return render_sync(c, p, W, H, shard, out, {}, [&](auto sh, auto rgba, auto nu, auto iter, auto, auto s, bool out_frame) {
         return enqueue_phoenix(c, p, ph, W, H, sh, rgba, nu, iter, s, out_frame); });
 }
 
@@ -1980,8 +1880,8 @@ extern "C" int fr_render_mandelbulb_async(fr_ctx* c, const fr_params* p, const f
 {
     const int st = check_mandelbulb(c, p, mb, W, H, out);
     if (st != FR_OK) return st;
-    return render_async("fr_render_mandelbulb_async", c, H, shard, out, hip_stream,
-                        [&](auto sh, auto rgba, auto nu, auto iter, auto s, bool out_frame) {
+    return render_async("fr_render_mandelbulb_async", c, H, shard, out, {}, hip_stream,
+                        [&](auto sh, auto rgba, auto nu, auto iter, auto, auto s, bool out_frame) {
                             return enqueue_mandelbulb(c, p, mb, W, H, sh, rgba, nu, iter, s, out_frame); });
 }
 
@@ -1990,240 +1890,145 @@ extern "C" int fr_render_mandelbulb(fr_ctx* c, const fr_params* p, const fr_mand
 {
     const int st = check_mandelbulb(c, p, mb, W, H, out);
     if (st != FR_OK) return st;
-    return render_sync(c, p, W, H, shard, out, [&](auto sh, auto rgba, auto nu, auto iter, auto s, bool out_frame) {
+    return render_sync(c, p, W, H, shard, out, {}, [&](auto sh, auto rgba, auto nu, auto iter, auto, auto s, bool out_frame) {
         return enqueue_mandelbulb(c, p, mb, W, H, sh, rgba, nu, iter, s, out_frame); });
 }
 
-static int check_deep(fr_ctx* c, const fr_params* p, const fr_deep_view* v, uint32_t W, uint32_t H, const fr_output* out)
+/* The fourteen deep entry points: BASE names the path (DeepPath), async_entry the _async form (nullptr: the synchronous one),
+ * validate() runs the path's validator once the pointers are known not to be NULL, and the enqueue step is enqueue_deep_view of
+ * the view read into a DeepAt.  e: fr_render_deep_de's block, whose two planes travel as extra planes into the derivative's
+ * fields; nullptr for every other path. */
+template <class BASE, class VIEW, class Validate>
+static int deep_entry(const char* async_entry, fr_ctx* c, const fr_params* p, const VIEW* v, const fr_deep_de* e, uint32_t W,
+                      uint32_t H, const fr_shard* shard, const fr_output* out, void* hip_stream, Validate&& validate)
 {
+    constexpr bool de = DeepPath<BASE>::de != 0;
     if (!c) return fr_set_error(FR_ERR_INVALID_ARG, "ctx is NULL");
-    if (!p || !v || !out) return fr_set_error(FR_ERR_INVALID_ARG, "params/deep view/out is NULL");
-    return fr_deep_validate(p, v, W, H);
+    if (!p || !v || !out || (de && !e))
+        return fr_set_error(FR_ERR_INVALID_ARG, de ? "params/deep view/de/out is NULL" : "params/deep view/out is NULL");
+    const int st = validate();
+    if (st != FR_OK) return st;
+    ExtraPlanes extra;
+    if constexpr (de)
+        extra = {2, {{e->deriv, 16}, {e->de, 8}}, "fr_render_deep_de: neither fr_output nor fr_deep_de has a plane to write"};
+    auto enqueue = [&](auto sh, auto rgba, auto nu, auto iter, void* const* xp, auto s, bool out_frame) {
+        DeepAt at = {v->center_x, v->center_y, nullptr, p->zoom, 0, v->frac_bits};
+        if constexpr (DeepPath<BASE>::ext) {     /* the zoom is the view's string: resolved here, with the automatic F */
+            at.zoom = v->zoom;
+            const int rs = fr_deepx_resolve(v, &at.zm, &at.ze, &at.bits);
+            if (rs != FR_OK) return rs;
+        } else if (!at.bits) {
+            at.bits = fr_deep_frac_bits(p->zoom);
+        }
+        return enqueue_deep_view<BASE>(c, p, at, W, H, sh, rgba, nu, iter, s, out_frame, [&](BASE& a) {
+            if constexpr (de) {                  /* s = zoom / H of the whole frame, whatever rows this part owns */
+                a.s = p->zoom / (double)H;
+                a.deriv = (double*)xp[0]; a.de = (double*)xp[1];
+                a.shade = e->shade; a.edge_px = e->edge_px;
+            }
+        });
+    };
+    return async_entry ? render_async(async_entry, c, H, shard, out, extra, hip_stream, enqueue)
+                       : render_sync(c, p, W, H, shard, out, extra, enqueue);
 }
 
 extern "C" int fr_render_deep_async(fr_ctx* c, const fr_params* p, const fr_deep_view* v, uint32_t W, uint32_t H,
                                     const fr_shard* shard, const fr_output* out, void* hip_stream)
 {
-    const int st = check_deep(c, p, v, W, H, out);
-    if (st != FR_OK) return st;
-    return render_async("fr_render_deep_async", c, H, shard, out, hip_stream,
-                        [&](auto sh, auto rgba, auto nu, auto iter, auto s, bool out_frame) {
-                            return enqueue_deep(c, kMandel, p, v, W, H, sh, rgba, nu, iter, s, out_frame); });
+    return deep_entry<DeepArgs>("fr_render_deep_async", c, p, v, nullptr, W, H, shard, out, hip_stream,
+                                [&] { return fr_deep_validate(p, v, W, H); });
 }
 
 extern "C" int fr_render_deep(fr_ctx* c, const fr_params* p, const fr_deep_view* v, uint32_t W, uint32_t H,
                               const fr_shard* shard, const fr_output* out)
 {
-    const int st = check_deep(c, p, v, W, H, out);
-    if (st != FR_OK) return st;
-    return render_sync(c, p, W, H, shard, out, [&](auto sh, auto rgba, auto nu, auto iter, auto s, bool out_frame) {
-        return enqueue_deep(c, kMandel, p, v, W, H, sh, rgba, nu, iter, s, out_frame); });
+    return deep_entry<DeepArgs>(nullptr, c, p, v, nullptr, W, H, shard, out, nullptr,
+                                [&] { return fr_deep_validate(p, v, W, H); });
 }
 
-/* fr_render_deep_de: render_async / render_sync with five planes -- de and deriv follow out->memory and out->layout as nu
- * does, and any one plane is enough */
-static int check_deep_de(fr_ctx* c, const fr_params* p, const fr_deep_view* v, const fr_deep_de* e, uint32_t W, uint32_t H,
-                         const fr_output* out)
-{
-    if (!c) return fr_set_error(FR_ERR_INVALID_ARG, "ctx is NULL");
-    if (!p || !v || !e || !out) return fr_set_error(FR_ERR_INVALID_ARG, "params/deep view/de/out is NULL");
-    return fr_deep_de_validate(p, v, e, W, H);
-}
-
-/* 1: this part owns rows and has a plane to write; 0: it owns no rows; < 0: error */
-static int check_planes_de(const fr_shard* shard, uint32_t H, const fr_output* out, const fr_deep_de* e)
-{
-    if (shard && shard->nparts && shard->part >= shard->nparts)
-        return fr_set_error(FR_ERR_INVALID_ARG, "shard part %u >= nparts %u", shard->part, shard->nparts);
-    if (fr_shard_rows(shard, H) == 0) return 0;
-    if (!out->rgba && !out->nu && !out->iter && !e->de && !e->deriv)
-        return fr_set_error(FR_ERR_INVALID_ARG, "fr_render_deep_de: neither fr_output nor fr_deep_de has a plane to write");
-    return 1;
-}
-
+/* fr_render_deep_de: five planes -- de and deriv follow out->memory and out->layout as nu does, and any one plane is enough */
 extern "C" int fr_render_deep_de_async(fr_ctx* c, const fr_params* p, const fr_deep_view* v, const fr_deep_de* e, uint32_t W,
                                        uint32_t H, const fr_shard* shard, const fr_output* out, void* hip_stream)
 {
-    int st = check_deep_de(c, p, v, e, W, H, out);
-    if (st != FR_OK) return st;
-    if ((st = check_layout(out)) != FR_OK) return st;
-    if (out->memory != FR_MEM_DEVICE) return fr_set_error(FR_ERR_INVALID_ARG, "fr_render_deep_de_async needs FR_MEM_DEVICE outputs");
-    st = check_planes_de(shard, H, out, e);
-    if (st <= 0) return st;
-    FR_HIP_TRY(hipSetDevice(c->device));
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    st = enqueue_deep_de(c, p, v, e, W, H, shard, out->rgba, out->nu, out->iter, e->de, e->deriv, s, out->layout == FR_LAYOUT_FRAME);
-    if (st == FR_OK) c->render_on_user_stream = s != c->stream;
-    return st;
+    return deep_entry<DeepDeArgs>("fr_render_deep_de_async", c, p, v, e, W, H, shard, out, hip_stream,
+                                  [&] { return fr_deep_de_validate(p, v, e, W, H); });
 }
 
 extern "C" int fr_render_deep_de(fr_ctx* c, const fr_params* p, const fr_deep_view* v, const fr_deep_de* e, uint32_t W, uint32_t H,
                                  const fr_shard* shard, const fr_output* out)
 {
-    int st = check_deep_de(c, p, v, e, W, H, out);
-    if (st != FR_OK) return st;
-    if ((st = check_layout(out)) != FR_OK) return st;
-    st = check_planes_de(shard, H, out, e);
-    if (st <= 0) return st;
-    FR_HIP_TRY(hipSetDevice(c->device));
-    const bool host = out->memory == FR_MEM_HOST;
-    if (!host && out->memory != FR_MEM_DEVICE) return fr_set_error(FR_ERR_INVALID_ARG, "unknown fr_output.memory %d", out->memory);
-    float* rgba = out->rgba; void* nu = out->nu; int32_t* iter = out->iter;
-    double* de = e->de; double* deriv = e->deriv;
-    const size_t npx = (size_t)fr_shard_rows(shard, H) * W;
-    if (host) {                                  /* staged like the other planes: rgba 16, deriv 16, nu 8, de 8, iter 4 bytes */
-        const size_t off_deriv = npx * 16, off_nu = off_deriv + npx * 16, off_de = off_nu + npx * 8, off_iter = off_de + npx * 8;
-        const int gs = grow_device(&c->scratch, &c->scratch_bytes, off_iter + npx * 4);
-        if (gs != FR_OK) return gs;
-        char* base = (char*)c->scratch;
-        rgba = out->rgba ? (float*)base : nullptr;
-        deriv = e->deriv ? (double*)(base + off_deriv) : nullptr;
-        nu = out->nu ? (void*)(base + off_nu) : nullptr;
-        de = e->de ? (double*)(base + off_de) : nullptr;
-        iter = out->iter ? (int32_t*)(base + off_iter) : nullptr;
-    }
-    st = enqueue_deep_de(c, p, v, e, W, H, shard, rgba, nu, iter, de, deriv, c->stream, out->layout == FR_LAYOUT_FRAME);
-    if (st != FR_OK) return st;
-    c->render_on_user_stream = false;
-    if (host) {
-        if (out->rgba) FR_HIP_TRY(hipMemcpyAsync(out->rgba, rgba, npx * 16, hipMemcpyDeviceToHost, c->stream));
-        if (e->deriv) FR_HIP_TRY(hipMemcpyAsync(e->deriv, deriv, npx * 16, hipMemcpyDeviceToHost, c->stream));
-        if (out->nu) FR_HIP_TRY(hipMemcpyAsync(out->nu, nu, npx * 8, hipMemcpyDeviceToHost, c->stream));
-        if (e->de) FR_HIP_TRY(hipMemcpyAsync(e->de, de, npx * 8, hipMemcpyDeviceToHost, c->stream));
-        if (out->iter) FR_HIP_TRY(hipMemcpyAsync(out->iter, iter, npx * 4, hipMemcpyDeviceToHost, c->stream));
-    }
-    FR_HIP_TRY(hipStreamSynchronize(c->stream));
-    return check_overflow(c);
-}
-
-static int check_deep_ship(fr_ctx* c, const fr_params* p, const fr_deep_view* v, uint32_t W, uint32_t H, const fr_output* out)
-{
-    if (!c) return fr_set_error(FR_ERR_INVALID_ARG, "ctx is NULL");
-    if (!p || !v || !out) return fr_set_error(FR_ERR_INVALID_ARG, "params/deep view/out is NULL");
-    return fr_deep_ship_validate(p, v, W, H);
+    return deep_entry<DeepDeArgs>(nullptr, c, p, v, e, W, H, shard, out, nullptr,
+                                  [&] { return fr_deep_de_validate(p, v, e, W, H); });
 }
 
 extern "C" int fr_render_deep_ship_async(fr_ctx* c, const fr_params* p, const fr_deep_view* v, uint32_t W, uint32_t H,
                                          const fr_shard* shard, const fr_output* out, void* hip_stream)
 {
-    const int st = check_deep_ship(c, p, v, W, H, out);
-    if (st != FR_OK) return st;
-    return render_async("fr_render_deep_ship_async", c, H, shard, out, hip_stream,
-                        [&](auto sh, auto rgba, auto nu, auto iter, auto s, bool out_frame) {
-                            return enqueue_deep(c, kShip, p, v, W, H, sh, rgba, nu, iter, s, out_frame); });
+    return deep_entry<DeepShipArgs>("fr_render_deep_ship_async", c, p, v, nullptr, W, H, shard, out, hip_stream,
+                                    [&] { return fr_deep_ship_validate(p, v, W, H); });
 }
 
 extern "C" int fr_render_deep_ship(fr_ctx* c, const fr_params* p, const fr_deep_view* v, uint32_t W, uint32_t H,
                                    const fr_shard* shard, const fr_output* out)
 {
-    const int st = check_deep_ship(c, p, v, W, H, out);
-    if (st != FR_OK) return st;
-    return render_sync(c, p, W, H, shard, out, [&](auto sh, auto rgba, auto nu, auto iter, auto s, bool out_frame) {
-        return enqueue_deep(c, kShip, p, v, W, H, sh, rgba, nu, iter, s, out_frame); });
-}
-
-static int check_deepx(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, uint32_t W, uint32_t H, const fr_output* out)
-{
-    if (!c) return fr_set_error(FR_ERR_INVALID_ARG, "ctx is NULL");
-    if (!p || !v || !out) return fr_set_error(FR_ERR_INVALID_ARG, "params/deep view/out is NULL");
-    return fr_deepx_validate(p, v, W, H);
+    return deep_entry<DeepShipArgs>(nullptr, c, p, v, nullptr, W, H, shard, out, nullptr,
+                                    [&] { return fr_deep_ship_validate(p, v, W, H); });
 }
 
 extern "C" int fr_render_deepx_async(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, uint32_t W, uint32_t H,
                                      const fr_shard* shard, const fr_output* out, void* hip_stream)
 {
-    const int st = check_deepx(c, p, v, W, H, out);
-    if (st != FR_OK) return st;
-    return render_async("fr_render_deepx_async", c, H, shard, out, hip_stream,
-                        [&](auto sh, auto rgba, auto nu, auto iter, auto s, bool out_frame) {
-                            return enqueue_deepx(c, kMandel, p, v, W, H, sh, rgba, nu, iter, s, out_frame); });
+    return deep_entry<DeepXArgs>("fr_render_deepx_async", c, p, v, nullptr, W, H, shard, out, hip_stream,
+                                 [&] { return fr_deepx_validate(p, v, W, H); });
 }
 
 extern "C" int fr_render_deepx(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, uint32_t W, uint32_t H,
                                const fr_shard* shard, const fr_output* out)
 {
-    const int st = check_deepx(c, p, v, W, H, out);
-    if (st != FR_OK) return st;
-    return render_sync(c, p, W, H, shard, out, [&](auto sh, auto rgba, auto nu, auto iter, auto s, bool out_frame) {
-        return enqueue_deepx(c, kMandel, p, v, W, H, sh, rgba, nu, iter, s, out_frame); });
-}
-
-static int check_deepx_ship(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, uint32_t W, uint32_t H, const fr_output* out)
-{
-    if (!c) return fr_set_error(FR_ERR_INVALID_ARG, "ctx is NULL");
-    if (!p || !v || !out) return fr_set_error(FR_ERR_INVALID_ARG, "params/deep view/out is NULL");
-    return fr_deepx_ship_validate(p, v, W, H);
+    return deep_entry<DeepXArgs>(nullptr, c, p, v, nullptr, W, H, shard, out, nullptr,
+                                 [&] { return fr_deepx_validate(p, v, W, H); });
 }
 
 extern "C" int fr_render_deepx_ship_async(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, uint32_t W, uint32_t H,
                                           const fr_shard* shard, const fr_output* out, void* hip_stream)
 {
-    const int st = check_deepx_ship(c, p, v, W, H, out);
-    if (st != FR_OK) return st;
-    return render_async("fr_render_deepx_ship_async", c, H, shard, out, hip_stream,
-                        [&](auto sh, auto rgba, auto nu, auto iter, auto s, bool out_frame) {
-                            return enqueue_deepx(c, kShip, p, v, W, H, sh, rgba, nu, iter, s, out_frame); });
+    return deep_entry<DeepShipXArgs>("fr_render_deepx_ship_async", c, p, v, nullptr, W, H, shard, out, hip_stream,
+                                     [&] { return fr_deepx_ship_validate(p, v, W, H); });
 }
 
 extern "C" int fr_render_deepx_ship(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, uint32_t W, uint32_t H,
                                     const fr_shard* shard, const fr_output* out)
 {
-    const int st = check_deepx_ship(c, p, v, W, H, out);
-    if (st != FR_OK) return st;
-    return render_sync(c, p, W, H, shard, out, [&](auto sh, auto rgba, auto nu, auto iter, auto s, bool out_frame) {
-        return enqueue_deepx(c, kShip, p, v, W, H, sh, rgba, nu, iter, s, out_frame); });
-}
-
-static int check_deep_julia(fr_ctx* c, const fr_params* p, const fr_deep_view* v, uint32_t W, uint32_t H, const fr_output* out)
-{
-    if (!c) return fr_set_error(FR_ERR_INVALID_ARG, "ctx is NULL");
-    if (!p || !v || !out) return fr_set_error(FR_ERR_INVALID_ARG, "params/deep view/out is NULL");
-    return fr_deep_julia_validate(p, v, W, H);
+    return deep_entry<DeepShipXArgs>(nullptr, c, p, v, nullptr, W, H, shard, out, nullptr,
+                                     [&] { return fr_deepx_ship_validate(p, v, W, H); });
 }
 
 extern "C" int fr_render_deep_julia_async(fr_ctx* c, const fr_params* p, const fr_deep_view* v, uint32_t W, uint32_t H,
                                           const fr_shard* shard, const fr_output* out, void* hip_stream)
 {
-    const int st = check_deep_julia(c, p, v, W, H, out);
-    if (st != FR_OK) return st;
-    return render_async("fr_render_deep_julia_async", c, H, shard, out, hip_stream,
-                        [&](auto sh, auto rgba, auto nu, auto iter, auto s, bool out_frame) {
-                            return enqueue_deep_julia(c, p, v, W, H, sh, rgba, nu, iter, s, out_frame); });
+    return deep_entry<DeepJuliaArgs>("fr_render_deep_julia_async", c, p, v, nullptr, W, H, shard, out, hip_stream,
+                                     [&] { return fr_deep_julia_validate(p, v, W, H); });
 }
 
 extern "C" int fr_render_deep_julia(fr_ctx* c, const fr_params* p, const fr_deep_view* v, uint32_t W, uint32_t H,
                                     const fr_shard* shard, const fr_output* out)
 {
-    const int st = check_deep_julia(c, p, v, W, H, out);
-    if (st != FR_OK) return st;
-    return render_sync(c, p, W, H, shard, out, [&](auto sh, auto rgba, auto nu, auto iter, auto s, bool out_frame) {
-        return enqueue_deep_julia(c, p, v, W, H, sh, rgba, nu, iter, s, out_frame); });
-}
-
-static int check_deepx_julia(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, uint32_t W, uint32_t H, const fr_output* out)
-{
-    if (!c) return fr_set_error(FR_ERR_INVALID_ARG, "ctx is NULL");
-    if (!p || !v || !out) return fr_set_error(FR_ERR_INVALID_ARG, "params/deep view/out is NULL");
-    return fr_deepx_julia_validate(p, v, W, H);
+    return deep_entry<DeepJuliaArgs>(nullptr, c, p, v, nullptr, W, H, shard, out, nullptr,
+                                     [&] { return fr_deep_julia_validate(p, v, W, H); });
 }
 
 extern "C" int fr_render_deepx_julia_async(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, uint32_t W, uint32_t H,
                                            const fr_shard* shard, const fr_output* out, void* hip_stream)
 {
-    const int st = check_deepx_julia(c, p, v, W, H, out);
-    if (st != FR_OK) return st;
-    return render_async("fr_render_deepx_julia_async", c, H, shard, out, hip_stream,
-                        [&](auto sh, auto rgba, auto nu, auto iter, auto s, bool out_frame) {
-                            return enqueue_deepx_julia(c, p, v, W, H, sh, rgba, nu, iter, s, out_frame); });
+    return deep_entry<DeepJuliaXArgs>("fr_render_deepx_julia_async", c, p, v, nullptr, W, H, shard, out, hip_stream,
+                                      [&] { return fr_deepx_julia_validate(p, v, W, H); });
 }
 
 extern "C" int fr_render_deepx_julia(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, uint32_t W, uint32_t H,
                                      const fr_shard* shard, const fr_output* out)
 {
-    const int st = check_deepx_julia(c, p, v, W, H, out);
-    if (st != FR_OK) return st;
-    return render_sync(c, p, W, H, shard, out, [&](auto sh, auto rgba, auto nu, auto iter, auto s, bool out_frame) {
-        return enqueue_deepx_julia(c, p, v, W, H, sh, rgba, nu, iter, s, out_frame); });
+    return deep_entry<DeepJuliaXArgs>(nullptr, c, p, v, nullptr, W, H, shard, out, nullptr,
+                                      [&] { return fr_deepx_julia_validate(p, v, W, H); });
 }
 
 /* ---- 8-bit export ------------------------------------------------------------------------------ */
@@ -2419,7 +2224,7 @@ extern "C" int fr_render_frame_png(fr_ctx* c, const fr_params* p, uint32_t W, ui
     return frame_png_tail(c, W, H, path);
 }
 
-/* ---- deep zoom sequences: the entry points (the enqueue side is next to enqueue_deepx) ------------------------------------ */
+/* ---- deep zoom sequences: the entry points (the enqueue side is next to enqueue_deepx_at) --------------------------------- */
 static int deep_sequence_create(const char* who, bool ship, fr_ctx* c, const fr_params* p, const fr_deep_sequence_desc* d,
                                 uint32_t W, uint32_t H, fr_deep_sequence** out)
 {
@@ -2486,7 +2291,7 @@ extern "C" int fr_deep_sequence_render(fr_deep_sequence* q, int32_t frame, const
     if (f.resampled && (out->nu || out->iter))
         return fr_set_error(FR_ERR_UNSUPPORTED, "frame %d is resampled from keyframes %d and %d: it has an rgba plane only", frame,
                             f.keyframe, f.keyframe + 1);
-    return render_sync(q->c, &q->p, q->W, q->H, nullptr, out, [&](auto, auto rgba, auto nu, auto iter, auto s, bool) {
+    return render_sync(q->c, &q->p, q->W, q->H, nullptr, out, {}, [&](auto, auto rgba, auto nu, auto iter, auto, auto s, bool) {
         return seq_enqueue(q, &q->p, f, rgba, nu, iter, s); });
 }
 

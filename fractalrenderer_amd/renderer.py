@@ -127,47 +127,41 @@ class Renderer:
     def last_stages(self) -> int:
         return _capi.check(self._lib.fr_ctx_last_grid(self._ctx)) >> 16
 
+    def _last_steps(self, symbol: str) -> DeepSteps:
+        """the three counters behind one of the fr_ctx_last_*_steps entry points"""
+        out = (C.c_uint64 * 3)()
+        _capi.check(getattr(self._lib, symbol)(self._ctx, out))
+        return DeepSteps(int(out[0]), int(out[1]), int(out[2]))
+
     def last_deep_steps(self) -> DeepSteps:
         """fr_ctx_last_deep_steps: (plain steps, BLA steps, updates skipped) of the most recent render_deep(bla=True) on
         this context, over every sub-sample of its pixels (after the caller's own sync for sync=False)."""
-        out = (C.c_uint64 * 3)()
-        _capi.check(self._lib.fr_ctx_last_deep_steps(self._ctx, out))
-        return DeepSteps(int(out[0]), int(out[1]), int(out[2]))
+        return self._last_steps("fr_ctx_last_deep_steps")
 
     def last_deepx_steps(self) -> DeepSteps:
         """fr_ctx_last_deepx_steps: (single steps of both modes, BLA steps, updates skipped) of the most recent
         render_deep(xbla=True) on this context, as last_deep_steps()."""
-        out = (C.c_uint64 * 3)()
-        _capi.check(self._lib.fr_ctx_last_deepx_steps(self._ctx, out))
-        return DeepSteps(int(out[0]), int(out[1]), int(out[2]))
+        return self._last_steps("fr_ctx_last_deepx_steps")
 
     def last_deep_ship_steps(self) -> DeepSteps:
         """fr_ctx_last_deep_ship_steps: (plain steps, BLA steps, updates skipped) of the most recent
         render_deep_ship(bla=True) on this context, as last_deep_steps()."""
-        out = (C.c_uint64 * 3)()
-        _capi.check(self._lib.fr_ctx_last_deep_ship_steps(self._ctx, out))
-        return DeepSteps(int(out[0]), int(out[1]), int(out[2]))
+        return self._last_steps("fr_ctx_last_deep_ship_steps")
 
     def last_deepx_ship_steps(self) -> DeepSteps:
         """fr_ctx_last_deepx_ship_steps: (single steps of both modes, BLA steps, updates skipped) of the most recent
         render_deepx_ship(bla=True) or ship-sequence render with bla=True on this context, as last_deep_steps()."""
-        out = (C.c_uint64 * 3)()
-        _capi.check(self._lib.fr_ctx_last_deepx_ship_steps(self._ctx, out))
-        return DeepSteps(int(out[0]), int(out[1]), int(out[2]))
+        return self._last_steps("fr_ctx_last_deepx_ship_steps")
 
     def last_deep_julia_steps(self) -> DeepSteps:
         """fr_ctx_last_deep_julia_steps: (single steps, BLA steps, updates skipped) of the most recent render_deep_julia(bla=True)
         of a view without a zoom string on this context, both orbits counted together, as last_deep_steps()."""
-        out = (C.c_uint64 * 3)()
-        _capi.check(self._lib.fr_ctx_last_deep_julia_steps(self._ctx, out))
-        return DeepSteps(int(out[0]), int(out[1]), int(out[2]))
+        return self._last_steps("fr_ctx_last_deep_julia_steps")
 
     def last_deepx_julia_steps(self) -> DeepSteps:
         """fr_ctx_last_deepx_julia_steps: the same for the most recent render_deep_julia(bla=True) of a view with a zoom
         string (single steps of both modes)."""
-        out = (C.c_uint64 * 3)()
-        _capi.check(self._lib.fr_ctx_last_deepx_julia_steps(self._ctx, out))
-        return DeepSteps(int(out[0]), int(out[1]), int(out[2]))
+        return self._last_steps("fr_ctx_last_deepx_julia_steps")
 
     def last_kernel_ms(self) -> float:
         return float(self._lib.fr_ctx_last_kernel_ms(self._ctx))
@@ -198,15 +192,18 @@ class Renderer:
             raise ValueError(f"{what}: {a.size} elements, expected {nelem}")
         return a.ctypes.data, "host"
 
-    def _output(self, precision: Precision, rows: int, width: int, rgba, nu, it) -> _capi.fr_output:
+    def _output(self, precision: Precision, rows: int, width: int, rgba, nu, it, extra=()) -> _capi.fr_output:
         # (also called with self = None by Node.render: uses nothing of the instance)
+        # extra: planes beyond fr_output's three as (struct, field, array, dtype, elements per pixel); their pointers go into the
+        # struct's field and their memory kind has to be that of the others
         npx = rows * width
         nu_dtype = "float64" if precision == Precision.F64 else "float32"   # Deep_Zoom callers pass Precision.F32
         kinds = set()
         o = _capi.fr_output()
-        for name, x, dt, n in (("rgba", rgba, "float32", npx * 4), ("nu", nu, nu_dtype, npx), ("iter", it, "int32", npx)):
-            p, kind = Renderer._ptr(x, dt, n, name)
-            setattr(o, name, p)
+        planes = [(o, "rgba", rgba, "float32", 4), (o, "nu", nu, nu_dtype, 1), (o, "iter", it, "int32", 1)]
+        for struct, name, x, dt, per_px in planes + list(extra):
+            p, kind = Renderer._ptr(x, dt, npx * per_px, name)
+            setattr(struct, name, p)
             if kind:
                 kinds.add(kind)
         if len(kinds) > 1:
@@ -312,28 +309,11 @@ class Renderer:
             p.flags |= _capi.FR_FLAG_DEEP_BLA
         v = (view or DeepView()).to_c()
         rows = shard.rows(height) if shard else height
-        out = self._output(Precision.F64, rows, width, rgba, nu, iter)
         e = _capi.fr_deep_de(None, None, 1 if shade else 0, float(edge_px))
-        kinds = set()
-        for name, x, n in (("de", de, rows * width), ("deriv", deriv, rows * width * 2)):
-            ptr, kind = Renderer._ptr(x, "float64", n, name)
-            setattr(e, name, ptr)
-            if kind:
-                kinds.add(kind)
-        if rgba is not None or nu is not None or iter is not None:
-            kinds.add("device" if out.memory == _capi.FR_MEM_DEVICE else "host")
-        if len(kinds) > 1:
-            raise ValueError("output planes must all be host or all be device memory")
-        out.memory = _capi.FR_MEM_DEVICE if kinds == {"device"} else _capi.FR_MEM_HOST
-        sh = shard.to_c() if shard else None
-        shp = C.byref(sh) if sh is not None else None
-        if sync:
-            if stream is not None:
-                raise ValueError("stream is only meaningful with sync=False")
-            _capi.check(self._lib.fr_render_deep_de(self._ctx, C.byref(p), C.byref(v), C.byref(e), width, height, shp, C.byref(out)))
-        else:
-            _capi.check(self._lib.fr_render_deep_de_async(self._ctx, C.byref(p), C.byref(v), C.byref(e), width, height, shp,
-                                                          C.byref(out), C.c_void_p(stream or 0)))
+        # (through the class: tests call this method on a stand-in for the renderer that has _lib, _ctx and _output only)
+        Renderer._render_call(self, self._lib.fr_render_deep_de, self._lib.fr_render_deep_de_async,
+                              (C.byref(p), C.byref(v), C.byref(e)), width, height, Precision.F64, rows, rgba, nu, iter, shard,
+                              stream, sync, extra=((e, "de", de, "float64", 1), (e, "deriv", deriv, "float64", 2)))
 
     def render_deep_ship(self, state: FractalState, width: int, height: int, view: Optional[DeepView] = None, *,
                          post_chain: bool = False, rgba=None, nu=None, iter=None, shard: Optional[Shard] = None,
@@ -403,12 +383,11 @@ class Renderer:
                           height, Precision.F64, rows, rgba, nu, iter, shard, stream, sync)
 
     def _render_call(self, fn_sync, fn_async, params: tuple, width: int, height: int, precision: Precision, rows: int,
-                     rgba, nu, it, shard: Optional[Shard], stream: Optional[int], sync: bool) -> None:
+                     rgba, nu, it, shard: Optional[Shard], stream: Optional[int], sync: bool, extra=()) -> None:
         """the planes, the shard and the sync / async entry of render(), render_phoenix(), render_mandelbulb(), render_deep(),
-        render_deep_ship(), render_deepx_ship() and render_deep_julia();
-        params: the entry's
-        arguments between the context and the frame size"""
-        out = self._output(precision, rows, width, rgba, nu, it)
+        render_deep_de(), render_deep_ship(), render_deepx_ship() and render_deep_julia(); params: the entry's arguments between
+        the context and the frame size; extra: the planes it writes beyond rgba, nu and iter (_output)"""
+        out = self._output(precision, rows, width, rgba, nu, it, extra)
         sh = shard.to_c() if shard else None
         shp = C.byref(sh) if sh is not None else None
         if sync:

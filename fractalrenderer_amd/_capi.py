@@ -181,6 +181,11 @@ SIGNATURES = {
                                   _P(fr_output)]),
     "fr_render_deepx_async": (C.c_int, [C.c_void_p, _P(fr_params), _P(fr_deepx_view), C.c_uint32, C.c_uint32, _P(fr_shard),
                                         _P(fr_output), C.c_void_p]),
+    "fr_deepx_de_validate": (C.c_int, [_P(fr_params), _P(fr_deepx_view), _P(fr_deep_de), C.c_uint32, C.c_uint32]),
+    "fr_render_deepx_de": (C.c_int, [C.c_void_p, _P(fr_params), _P(fr_deepx_view), _P(fr_deep_de), C.c_uint32, C.c_uint32,
+                                     _P(fr_shard), _P(fr_output)]),
+    "fr_render_deepx_de_async": (C.c_int, [C.c_void_p, _P(fr_params), _P(fr_deepx_view), _P(fr_deep_de), C.c_uint32, C.c_uint32,
+                                           _P(fr_shard), _P(fr_output), C.c_void_p]),
     "fr_deepx_ship_reference_orbit": (C.c_int, [_P(fr_deepx_view), C.c_int32, C.c_float, C.c_void_p, C.c_void_p, _P(C.c_int32)]),
     "fr_render_deepx_ship": (C.c_int, [C.c_void_p, _P(fr_params), _P(fr_deepx_view), C.c_uint32, C.c_uint32, _P(fr_shard),
                                        _P(fr_output)]),

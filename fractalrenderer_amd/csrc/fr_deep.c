@@ -779,15 +779,31 @@ int fr_deep_de_default(fr_deep_de* e)
     return FR_OK;
 }
 
-int fr_deep_de_validate(const fr_params* p, const fr_deep_view* v, const fr_deep_de* e, uint32_t width, uint32_t height)
+/* the rules of the distance block itself, behind the view's */
+static int check_de_block(const fr_deep_de* e)
 {
-    if (!e) return fr_set_error(FR_ERR_INVALID_ARG, "fr_deep_de is NULL");
-    const int st = fr_deep_validate(p, v, width, height);
-    if (st != FR_OK) return st;
     if (e->shade != 0 && e->shade != 1) return fr_set_error(FR_ERR_INVALID_ARG, "fr_deep_de.shade %d is neither 0 nor 1", e->shade);
     if (e->shade == 1 && (!isfinite(e->edge_px) || !(e->edge_px > 0.0f)))
         return fr_set_error(FR_ERR_INVALID_ARG, "fr_deep_de.edge_px must be finite and > 0 with shade 1");
     return FR_OK;
+}
+
+int fr_deep_de_validate(const fr_params* p, const fr_deep_view* v, const fr_deep_de* e, uint32_t width, uint32_t height)
+{
+    if (!e) return fr_set_error(FR_ERR_INVALID_ARG, "fr_deep_de is NULL");
+    const int st = fr_deep_validate(p, v, width, height);
+    return st != FR_OK ? st : check_de_block(e);
+}
+
+int fr_deepx_de_validate(const fr_params* p, const fr_deepx_view* v, const fr_deep_de* e, uint32_t width, uint32_t height)
+{
+    if (!e) return fr_set_error(FR_ERR_INVALID_ARG, "fr_deep_de is NULL");
+    const int st = fr_deepx_validate(p, v, width, height);
+    if (st != FR_OK) return st;
+    if (p->flags & (FR_FLAG_DEEP_SHIP_BLA | FR_FLAG_DEEPX_SHIP_BLA))     /* (fr_render_deepx does not read them) */
+        return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deepx_de: FR_FLAG_DEEP_SHIP_BLA / FR_FLAG_DEEPX_SHIP_BLA are not "
+                            "available (their tables are the Burning Ship's): the flag of this entry point is FR_FLAG_DEEPX_BLA");
+    return check_de_block(e);
 }
 
 /* ---- the reference orbits -----------------------------------------------------------------------------------------------------

@@ -46,16 +46,21 @@
  *     offset bla_offset(N - 1, k)), the radius r of every entry in an array of its own -- a double, or an XRad -- and
  *     (A, B) as F::kAbPerEntry double2 per entry (2: complex A, B; 4: the rows of the ship's real matrices; 1: Julia's A), the
  *     extended tables with their two exponents in an int2 (Julia: A's in an int32).
- *   - deep_kernel<ARGS>, one kernel body for the fourteen argument blocks: a persistent grid of the resident set pulls runs of
- *     8x8 sub-tiles from the sharded WaveQueue with unlimited stealing (deep views have very uneven iteration counts); one
- *     lane per sample, the aa x aa samples of a pixel one after the other in the lane; dc through the formula's viewport
- *     map, one dispatch on (extended, BLA) to the loop, then the colour stage of the formula's fp64 path: shade() and
- *     post_chain() of fr_kernels.hip.h on (i, r2).
+ *   - deep_kernel<ARGS>, one kernel body (deep_kernel_body) for the sixteen argument blocks: a persistent grid of the resident
+ *     set pulls runs of 8x8 sub-tiles from the sharded WaveQueue with unlimited stealing (deep views have very uneven
+ *     iteration counts); one lane per sample, the aa x aa samples of a pixel one after the other in the lane; dc through the
+ *     formula's viewport map, one dispatch on (extended, BLA) to the loop, then the colour stage of the formula's fp64 path:
+ *     shade() and post_chain() of fr_kernels.hip.h on (i, r2).
  *   - the distance estimate (fr_render_deep_de; DeepDeArgs, DeepDeBlaArgs): a compile-time option DE of deep_orbit and
  *     deep_orbit_bla for the Mandelbrot formula carries D = dz/dc * s, s = zoom / H one pixel spacing, next to the delta --
  *     D' = 2 z D + s in a plain step, D' = A D + B s in a BLA step, nothing in a rebase -- and feeds nothing back: (i, r2) and
  *     the step counts are those of the loops without it.  Four live VGPRs and, per plain update, 11 fp64 operations.  The
  *     kernel turns (r2, D) of an escaped sample into |z| log|z| / |D| and, on request, the debug shader's distance shading.
+ *   - the same below 1e-290 (fr_render_deepx_de; DeepXDeArgs, DeepXDeBlaArgs): the option DE of deep_orbit_x and
+ *     deep_orbit_x_bla for the Mandelbrot formula, with D an extended complex number (XDeriv: two mantissas, one int32 exponent)
+ *     whatever mode the lane's delta is in, normalised after every update; s = (sm, es) stays in SGPRs.  Five live VGPRs.  Its
+ *     two kernels are deepx_de_kernel<ARGS>, a second __global__ template around the one body (deep_kernel_body), so that the
+ *     set of deep_kernel instantiations stays what it was.
  */
 #pragma once
 #include "fr_kernels.hip.h"
@@ -151,6 +156,22 @@ struct DeepXArgs {
 
 struct DeepXBlaArgs {
     DeepXArgs x;
+    BlaXTable t;
+};
+
+/* fr_render_deepx_de: fr_render_deepx with the scaled derivative carried as an extended complex number (D.x, D.y, D.e) */
+struct DeepXDeArgs {
+    DeepXArgs x;
+    double sm;                           /* one pixel spacing zoom / H of the whole frame = sm 2^es, sm in [0.5, 1) */
+    int32_t es;
+    double* de;                          /* as DeepDeArgs */
+    double* deriv;
+    int32_t shade;
+    float edge_px;
+};
+
+struct DeepXDeBlaArgs {
+    DeepXDeArgs e;
     BlaXTable t;
 };
 
@@ -290,6 +311,38 @@ __device__ __forceinline__ double ship_fold_x(const double X, const int s, const
  * form it there. */
 __device__ __forceinline__ void deep_pin_d(double2& D) { asm volatile("" : "+v"(D.x), "+v"(D.y)); }
 
+/* fr_render_deepx_de: D = dz/dc * s as an extended complex number, normalised after every update in either mode of the lane's
+ * delta; the zero has FR_DEEPX_ZERO_EXP */
+struct XDeriv {
+    double x, y;
+    int e;
+};
+
+/* D' = norm(p (+) q) of the header: p at ep the step's linear part applied to D, q at eq its dc term applied to s.  Pinned as
+ * deep_pin_d pins the fp64 D. */
+__device__ __forceinline__ void deepx_d_set(XDeriv& D, const double px, const double py, const int ep, const double qx,
+                                            const double qy, const int eq)
+{
+    const int e = ep > eq ? ep : eq;
+    D.x = __builtin_ldexp(px, ep - e) + __builtin_ldexp(qx, eq - e);
+    D.y = __builtin_ldexp(py, ep - e) + __builtin_ldexp(qy, eq - e);
+    D.e = e;
+    x_norm(D.x, D.y, D.e);
+    asm volatile("" : "+v"(D.x), "+v"(D.y), "+v"(D.e));
+}
+
+/* ... with q = (sm, 0, es), a single step's: nothing is added to the imaginary part */
+__device__ __forceinline__ void deepx_d_set(XDeriv& D, const double px, const double py, const int ep, const double sm,
+                                            const int es)
+{
+    const int e = ep > es ? ep : es;
+    D.x = __builtin_ldexp(px, ep - e) + __builtin_ldexp(sm, es - e);
+    D.y = __builtin_ldexp(py, ep - e);
+    D.e = e;
+    x_norm(D.x, D.y, D.e);
+    asm volatile("" : "+v"(D.x), "+v"(D.y), "+v"(D.e));
+}
+
 /* ---- the formula policies ------------------------------------------------------------------------------------------------
  * What a policy hands to the shared code, all by value (small structs in registers). */
 struct StepLin { double tx, ty, fx, fy; };          /* the plain step: dz' = t * f + dc, a complex product */
@@ -350,6 +403,16 @@ struct MandelFormula {
     {
         const double2 a = T.ab[2 * e], b = T.ab[2 * e + 1];
         const int2 ee = T.abe[e];
+        return {a.x * qx - a.y * qy, a.x * qy + a.y * qx, b.x * cx - b.y * cy, b.x * cy + b.y * cx, ee.x, ee.y};
+    }
+    /* bla_x() with the derivative of the map it applies, from the one load of the entry:
+     * D' = norm((A D, A.e + D.e) (+) (B (sm, 0), B.e + es)) */
+    static __device__ __forceinline__ BlaStepX bla_x_d(const BlaXTable& T, const uint32_t e, const double qx, const double qy,
+                                                       const double cx, const double cy, const double sm, const int es, XDeriv& D)
+    {
+        const double2 a = T.ab[2 * e], b = T.ab[2 * e + 1];
+        const int2 ee = T.abe[e];
+        deepx_d_set(D, a.x * D.x - a.y * D.y, a.x * D.y + a.y * D.x, ee.x + D.e, b.x * sm, b.y * sm, ee.y + es);
         return {a.x * qx - a.y * qy, a.x * qy + a.y * qx, b.x * cx - b.y * cy, b.x * cy + b.y * cx, ee.x, ee.y};
     }
     /* mandelbrot.comp:219-230 (sy outer) and :149-151, less the centre; zs = the zoom or its mantissa */
@@ -624,6 +687,26 @@ __device__ __forceinline__ double2 deep_step_x(const double Zx, const double Zy,
         return make_double2(__builtin_ldexp(px, ep - en) + __builtin_ldexp(cx, ec - en),
                             __builtin_ldexp(py, ep - en) + __builtin_ldexp(cy, ec - en));
     }
+}
+
+/* The derivative's extended step (fr_render_deepx_de), at the sample's point before the update: b = (Z_m, eZ) (+) (dz, ed) at
+ * eb = max(eZ, ed), the doubling of w = 2 b in the exponent; D' = norm((b D, eb + 1 + D.e) (+) (sm, 0, es)) */
+__device__ __forceinline__ void deep_step_xd(const double Zx, const double Zy, const int eZ, const double dzx, const double dzy,
+                                             const int ed, const double sm, const int es, XDeriv& D)
+{
+    const int eb = eZ > ed ? eZ : ed;
+    const double bx = __builtin_ldexp(Zx, eZ - eb) + __builtin_ldexp(dzx, ed - eb);
+    const double by = __builtin_ldexp(Zy, eZ - eb) + __builtin_ldexp(dzy, ed - eb);
+    deepx_d_set(D, bx * D.x - by * D.y, bx * D.y + by * D.x, eb + 1 + D.e, sm, es);
+}
+
+/* ... and its plain step on the extended D: deep_step_d's w = 2 (Z_m + dz) on the plain doubles, the product at D.e */
+__device__ __forceinline__ void deep_step_pd(const double Zx, const double Zy, const double dzx, const double dzy, const double sm,
+                                             const int es, XDeriv& D)
+{
+    const double zx = Zx + dzx, zy = Zy + dzy;
+    const double wx = zx + zx, wy = zy + zy;
+    deepx_d_set(D, wx * D.x - wy * D.y, wx * D.y + wy * D.x, D.e, sm, es);
 }
 
 /* ---- the tables --------------------------------------------------------------------------------------------------------
@@ -1041,9 +1124,10 @@ __device__ __forceinline__ void deep_orbit_bla(const DeepArgs& A, const BlaTable
 
 /* deep_orbit in two modes (the header's EXTENDED and PLAIN steps).  (cx, cy, ec) = dc, normalised.  z = Z_{m+1} (+) n with the
  * signed orbit point; escape, rebase, norm and the mode rule are the same for either formula. */
-template <class F>
+template <class F, bool DE = false>
 __device__ __forceinline__ void deep_orbit_x(const DeepXArgs& AA, const JuliaStart J, const double cx, const double cy,
-                                             const int ec, bool live, int& esc, double& er2)
+                                             const int ec, bool live, int& esc, double& er2, const double sm = 0.0,
+                                             const int es = 0, XDeriv* const Dout = nullptr)
 {
     const DeepArgs& A = AA.d;
     const double2* __restrict__ orbit = A.orbit;
@@ -1078,6 +1162,7 @@ __device__ __forceinline__ void deep_orbit_x(const DeepXArgs& AA, const JuliaSta
     int m = 0;
     esc = max_iter;
     er2 = 0.0;
+    XDeriv D = {0.0, 0.0, kXZero};                               /* DE: dz/dc * s, through the escaping update */
     for (int i = 0; i < max_iter; ++i) {
         if (__builtin_amdgcn_ballot_w64(live) == 0ull) break;
         if (!live) continue;
@@ -1089,6 +1174,7 @@ __device__ __forceinline__ void deep_orbit_x(const DeepXArgs& AA, const JuliaSta
             const double2 Znn = mant[mn];
             const int eZnn = exp2[mn];
             int en;
+            if constexpr (DE) deep_step_xd(Zx, Zy, eZ, dzx, dzy, ed, sm, es, D);
             const double2 n = deep_step_x<F>(Zx, Zy, eZ, dzx, dzy, ed, cx, cy, ec, en);
             const double nx = n.x, ny = n.y;
             ++m;
@@ -1122,6 +1208,7 @@ __device__ __forceinline__ void deep_orbit_x(const DeepXArgs& AA, const JuliaSta
             ext = false;
         } else {
             const double2 Znn = orbit[mn];
+            if constexpr (DE) deep_step_pd(Zx, Zy, dzx, dzy, sm, es, D);
             const double2 n = deep_step<F>(Zx, Zy, dzx, dzy, cpx, cpy);
             const double nx = n.x, ny = n.y;
             ++m;
@@ -1160,6 +1247,7 @@ __device__ __forceinline__ void deep_orbit_x(const DeepXArgs& AA, const JuliaSta
             Zx = a.x; Zy = a.y; Znx = b.x; Zny = b.y;
         }
     }
+    if constexpr (DE) *Dout = D;
 }
 
 /* deep_orbit_x with BLA: u replaces the loop index.  A lane, in either mode, probes the table (bla_probe_x); a BLA step is
@@ -1167,10 +1255,11 @@ __device__ __forceinline__ void deep_orbit_x(const DeepXArgs& AA, const JuliaSta
  * in the mode the step leaves it in.  The single steps are deep_orbit_x's, operation for operation.  BLA lanes and
  * single-step lanes of a wave take their steps in the same trip.  nsingle / nbla: the steps this sample took.  Two orbits: as
  * deep_orbit_bla, and a BLA step ends with the flush of deep_orbit_x. */
-template <class F>
+template <class F, bool DE = false>
 __device__ __forceinline__ void deep_orbit_x_bla(const DeepXArgs& AA, const BlaXTable& T, const JuliaStart J, const int levels_p,
                                                  const uint32_t base_p, const double cx, const double cy, const int ec,
-                                                 bool live, int& esc, double& er2, uint32_t& nsingle, uint32_t& nbla)
+                                                 bool live, int& esc, double& er2, uint32_t& nsingle, uint32_t& nbla,
+                                                 const double sm = 0.0, const int es = 0, XDeriv* const Dout = nullptr)
 {
     const DeepArgs& A = AA.d;
     const double2* __restrict__ orbit = A.orbit;
@@ -1210,6 +1299,7 @@ __device__ __forceinline__ void deep_orbit_x_bla(const DeepXArgs& AA, const BlaX
     esc = max_iter;
     er2 = 0.0;
     nsingle = 0u; nbla = 0u;
+    XDeriv D = {0.0, 0.0, kXZero};                               /* DE: dz/dc * s, through the escaping update */
     for (;;) {
         if (__builtin_amdgcn_ballot_w64(live) == 0ull) break;
         if (!live) continue;
@@ -1224,13 +1314,15 @@ __device__ __forceinline__ void deep_orbit_x_bla(const DeepXArgs& AA, const BlaX
             int en, eW, eZnn = 0;
             double2 Znn = make_double2(0.0, 0.0);
             if (k > 0) {
-                const BlaStepX s = F::bla_x(T, tb + h.e, h.qx, h.qy, cx, cy);
+                BlaStepX s;
+                if constexpr (DE) s = F::bla_x_d(T, tb + h.e, h.qx, h.qy, cx, cy, sm, es, D);
+                else s = F::bla_x(T, tb + h.e, h.qx, h.qy, cx, cy);
                 const int ep = s.ea + h.qe;
                 if constexpr (F::kHasB) {
-                    const int es = s.eb + ec;
-                    en = ep > es ? ep : es;
-                    nx = __builtin_ldexp(s.px, ep - en) + __builtin_ldexp(s.sx, es - en);
-                    ny = __builtin_ldexp(s.py, ep - en) + __builtin_ldexp(s.sy, es - en);
+                    const int eq = s.eb + ec;
+                    en = ep > eq ? ep : eq;
+                    nx = __builtin_ldexp(s.px, ep - en) + __builtin_ldexp(s.sx, eq - en);
+                    ny = __builtin_ldexp(s.py, ep - en) + __builtin_ldexp(s.sy, eq - en);
                 } else {                                          /* n = A (x) dz */
                     en = ep;
                     nx = s.px; ny = s.py;
@@ -1243,6 +1335,7 @@ __device__ __forceinline__ void deep_orbit_x_bla(const DeepXArgs& AA, const BlaX
             } else {
                 Znn = mant[mn];
                 eZnn = exp2[mn];
+                if constexpr (DE) deep_step_xd(Zx, Zy, eZ, dzx, dzy, ed, sm, es, D);
                 const double2 n = deep_step_x<F>(Zx, Zy, eZ, dzx, dzy, ed, cx, cy, ec, en);
                 nx = n.x; ny = n.y;
                 ++m;
@@ -1288,6 +1381,7 @@ __device__ __forceinline__ void deep_orbit_x_bla(const DeepXArgs& AA, const BlaX
             }
         } else {
             const double2 Znn = orbit[mn];
+            if constexpr (DE) deep_step_pd(Zx, Zy, dzx, dzy, sm, es, D);
             const double2 n = deep_step<F>(Zx, Zy, dzx, dzy, cpx, cpy);
             const double nx = n.x, ny = n.y;
             ++m;
@@ -1323,6 +1417,7 @@ __device__ __forceinline__ void deep_orbit_x_bla(const DeepXArgs& AA, const BlaX
         }
         if (u >= max_iter) live = false;                          /* esc stays max_iter */
     }
+    if constexpr (DE) *Dout = D;
 }
 
 /* ---- the kernel --------------------------------------------------------------------------------------------------------
@@ -1335,6 +1430,12 @@ __host__ __device__ __forceinline__ const DeepArgs& deep_args(const DeepDeArgs& 
 __host__ __device__ __forceinline__ const DeepArgs& deep_args(const DeepDeBlaArgs& A) { return A.e.d; }
 __host__ __device__ __forceinline__ const DeepDeArgs& de_args(const DeepDeArgs& A) { return A; }
 __host__ __device__ __forceinline__ const DeepDeArgs& de_args(const DeepDeBlaArgs& A) { return A.e; }
+__host__ __device__ __forceinline__ const DeepArgs& deep_args(const DeepXDeArgs& A) { return A.x.d; }
+__host__ __device__ __forceinline__ const DeepArgs& deep_args(const DeepXDeBlaArgs& A) { return A.e.x.d; }
+__host__ __device__ __forceinline__ const DeepXArgs& deepx_args(const DeepXDeArgs& A) { return A.x; }
+__host__ __device__ __forceinline__ const DeepXArgs& deepx_args(const DeepXDeBlaArgs& A) { return A.e.x; }
+__host__ __device__ __forceinline__ const DeepXDeArgs& de_args(const DeepXDeArgs& A) { return A; }
+__host__ __device__ __forceinline__ const DeepXDeArgs& de_args(const DeepXDeBlaArgs& A) { return A.e; }
 __host__ __device__ __forceinline__ const DeepArgs& deep_args(const DeepShipArgs& A) { return A.d; }
 __host__ __device__ __forceinline__ const DeepArgs& deep_args(const DeepShipBlaArgs& A) { return A.s.d; }
 __host__ __device__ __forceinline__ const DeepArgs& deep_args(const DeepShipXArgs& A) { return A.x.d; }
@@ -1401,16 +1502,17 @@ __device__ __forceinline__ void deep_de_shade(float rgb[3], const double de, con
 }
 
 /* ARGS names the loop: Deep[Ship|Julia][X][Bla]Args = the formula, extended-exponent deltas, BLA (with the step counts);
- * DeepDe[Bla]Args = Deep[Bla]Args with the derivative and its two planes */
+ * DeepDe[Bla]Args = Deep[Bla]Args, DeepXDe[Bla]Args = DeepX[Bla]Args with the derivative and its two planes.  The body of the
+ * two __global__ templates below: deep_kernel for the fourteen blocks without an extended derivative, deepx_de_kernel for the
+ * two with one. */
 template <class ARGS>
-__global__ void __launch_bounds__(kBlockThreads)
-deep_kernel(const ARGS AA)
+__device__ __forceinline__ void deep_kernel_body(const ARGS& AA)
 {
     constexpr bool BLA = is_any_of<ARGS, DeepBlaArgs, DeepXBlaArgs, DeepShipBlaArgs, DeepShipXBlaArgs, DeepJuliaBlaArgs,
-                                   DeepJuliaXBlaArgs, DeepDeBlaArgs>;
-    constexpr bool DE = is_any_of<ARGS, DeepDeArgs, DeepDeBlaArgs>;
+                                   DeepJuliaXBlaArgs, DeepDeBlaArgs, DeepXDeBlaArgs>;
+    constexpr bool DE = is_any_of<ARGS, DeepDeArgs, DeepDeBlaArgs, DeepXDeArgs, DeepXDeBlaArgs>;
     constexpr bool X = is_any_of<ARGS, DeepXArgs, DeepXBlaArgs, DeepShipXArgs, DeepShipXBlaArgs, DeepJuliaXArgs,
-                                 DeepJuliaXBlaArgs>;
+                                 DeepJuliaXBlaArgs, DeepXDeArgs, DeepXDeBlaArgs>;
     constexpr bool SHIP = is_any_of<ARGS, DeepShipArgs, DeepShipBlaArgs, DeepShipXArgs, DeepShipXBlaArgs>;
     constexpr bool JULIA = is_any_of<ARGS, DeepJuliaArgs, DeepJuliaXArgs, DeepJuliaBlaArgs, DeepJuliaXBlaArgs>;
     using F = std::conditional_t<JULIA, JuliaFormula, std::conditional_t<SHIP, ShipFormula, MandelFormula>>;
@@ -1441,9 +1543,14 @@ deep_kernel(const ARGS AA)
     const double2 z1 = A.orbit[1];
     const bool want_rgb = A.rgba != nullptr;
     const bool want_nu = want_rgb || A.nu != nullptr;
-    double de_s = 0.0;                                            /* DE: one pixel spacing, wave-uniform */
+    double de_s = 0.0;                                            /* DE: one pixel spacing, wave-uniform; extended: its mantissa */
+    int de_es = 0;                                                /* ... and exponent */
     bool de_shade = false;
-    if constexpr (DE) { de_s = de_args(AA).s; de_shade = want_rgb && de_args(AA).shade != 0; }
+    if constexpr (DE) {
+        if constexpr (X) { de_s = de_args(AA).sm; de_es = de_args(AA).es; }
+        else de_s = de_args(AA).s;
+        de_shade = want_rgb && de_args(AA).shade != 0;
+    }
 
     unsigned long long n_plain = 0ull, n_bla = 0ull, n_upd = 0ull;   /* BLA: this lane's steps and updates */
     int levels_p = 0;                                             /* BLA on two orbits: P's table */
@@ -1461,7 +1568,19 @@ deep_kernel(const ARGS AA)
             double cx = inside ? dc.x : 0.0, cy = inside ? dc.y : 0.0;
             uint32_t np = 0u, nb = 0u;
             double2 D = make_double2(0.0, 0.0);
-            if constexpr (DE) {
+            /* DE, extended: D = (D.x, D.y) 2^eD.  The loop's XDeriv is unpacked into these two so that the planes and
+             * deep_de_of(r2, D) below are one code path with the fp64 derivative's, the exponent applied behind them */
+            int eD = 0;
+            if constexpr (DE && X) {
+                int ec = deepx_args(AA).ze;
+                x_norm(cx, cy, ec);
+                XDeriv Dx;
+                if constexpr (BLA)
+                    deep_orbit_x_bla<F, true>(deepx_args(AA), AA.t, julia_start(AA), levels_p, base_p, cx, cy, ec, inside, esc, r2,
+                                              np, nb, de_s, de_es, &Dx);
+                else deep_orbit_x<F, true>(deepx_args(AA), julia_start(AA), cx, cy, ec, inside, esc, r2, de_s, de_es, &Dx);
+                D = make_double2(Dx.x, Dx.y); eD = Dx.e;
+            } else if constexpr (DE) {
                 if constexpr (BLA)
                     deep_orbit_bla<F, true>(A, AA.t, julia_start(AA), levels_p, base_p, cx, cy, z1, inside, esc, r2, np, nb, de_s, &D);
                 else deep_orbit<F, true>(A, julia_start(AA), cx, cy, z1, inside, esc, r2, de_s, &D);
@@ -1489,9 +1608,16 @@ deep_kernel(const ARGS AA)
                 const bool first = s == 0 && inside;
                 if (first && de_args(AA).deriv) {
                     double* const dst = de_args(AA).deriv + 2 * plane_index(A.g, px, py, lrow);
-                    dst[0] = escaped ? D.x : 0.0; dst[1] = escaped ? D.y : 0.0;
+                    if constexpr (X) {                            /* saturates outside a double's range */
+                        dst[0] = escaped ? __builtin_ldexp(D.x, eD) : 0.0; dst[1] = escaped ? __builtin_ldexp(D.y, eD) : 0.0;
+                    } else {
+                        dst[0] = escaped ? D.x : 0.0; dst[1] = escaped ? D.y : 0.0;
+                    }
                 }
-                if (escaped && (s == 0 || de_shade)) de = deep_de_of(r2, D);
+                if (escaped && (s == 0 || de_shade)) {
+                    de = deep_de_of(r2, D);                       /* extended: of the mantissas, so |D| cannot overflow */
+                    if constexpr (X) de = __builtin_ldexp(de, -eD);
+                }
                 if (first && de_args(AA).de) de_args(AA).de[plane_index(A.g, px, py, lrow)] = de;
             }
             double nu;
@@ -1521,6 +1647,21 @@ deep_kernel(const ARGS AA)
             if (lane == 0) atomicAdd(q_table(AA.t).steps + c, v[c]);
         }
     }
+}
+
+template <class ARGS>
+__global__ void __launch_bounds__(kBlockThreads)
+deep_kernel(const ARGS AA)
+{
+    deep_kernel_body(AA);
+}
+
+/* fr_render_deepx_de's two kernels (DeepXDeArgs, DeepXDeBlaArgs) */
+template <class ARGS>
+__global__ void __launch_bounds__(kBlockThreads)
+deepx_de_kernel(const ARGS AA)
+{
+    deep_kernel_body(AA);
 }
 
 }  // namespace fr

@@ -75,7 +75,8 @@ struct BlaSlot {
 
 /* What the context keeps for one deep path, a (storage, formula) pair: its most recent reference orbit(s), their BLA table, and
  * the resident workgroups per CU of the deep_kernel instantiations that read them (0 = not asked yet): [0] the path's own pair,
- * [1] fr_render_deep_de's, which shares the fp64 Mandelbrot slot; [.][0] the unflagged kernel, [.][1] the flagged one */
+ * [1] fr_render_deep_de's, which shares the fp64 Mandelbrot slot, and fr_render_deepx_de's, which shares the extended one;
+ * [.][0] the unflagged kernel, [.][1] the flagged one */
 struct DeepSlot {
     DeepOrbit o;
     BlaSlot t;
@@ -975,15 +976,17 @@ static void bla_table_args(BlaXTable& a, const BlaSlot& t) { a.r = (const XRad*)
 template <class ARGS>
 static DeepArgs& deep_of(ARGS& a) { return const_cast<DeepArgs&>(deep_args(a)); }
 
-/* One record per argument block of an unflagged deep_kernel: the path it renders -- formula, storage, de = 1 for the blocks that
- * carry a derivative -- the block of its flagged kernel (Bla = {the base block, the table}), the flag that selects it, and both
- * kernels' names in messages.  launch_deep and enqueue_deep_view read everything that differs between the paths from here. */
+/* One record per argument block of an unflagged deep kernel: the path it renders -- formula, storage, de = 1 for the blocks that
+ * carry a derivative -- the block of its flagged kernel (Bla = {the base block, the table}), the flag that selects it, the
+ * __global__ template of both kernels (deep_kernel unless the record names another) and their names in messages.  launch_deep
+ * and enqueue_deep_view read everything that differs between the paths from here. */
 template <int F, bool EXT, class BLA, uint32_t FLAG, int DE = 0>
 struct DeepPathOf {
     static constexpr int f = F, de = DE;
     static constexpr bool ext = EXT;
     static constexpr uint32_t flag = FLAG;
     using Bla = BLA;
+    template <class ARGS> static auto kernel() -> void (*)(ARGS) { return deep_kernel<ARGS>; }   /* of either block */
 };
 template <class BASE> struct DeepPath;
 template <> struct DeepPath<DeepArgs> : DeepPathOf<kMandel, false, DeepBlaArgs, FR_FLAG_DEEP_BLA> {
@@ -996,15 +999,18 @@ template <> struct DeepPath<DeepJuliaArgs> : DeepPathOf<kJulia, false, DeepJulia
     static constexpr const char *name = "deep_kernel<DeepJuliaArgs>", *bla_name = "deep_kernel<DeepJuliaBlaArgs>"; };
 template <> struct DeepPath<DeepXArgs> : DeepPathOf<kMandel, true, DeepXBlaArgs, FR_FLAG_DEEPX_BLA> {
     static constexpr const char *name = "deep_kernel<DeepXArgs>", *bla_name = "deep_kernel<DeepXBlaArgs>"; };
+template <> struct DeepPath<DeepXDeArgs> : DeepPathOf<kMandel, true, DeepXDeBlaArgs, FR_FLAG_DEEPX_BLA, 1> {
+    static constexpr const char *name = "deepx_de_kernel<DeepXDeArgs>", *bla_name = "deepx_de_kernel<DeepXDeBlaArgs>";
+    template <class ARGS> static auto kernel() -> void (*)(ARGS) { return deepx_de_kernel<ARGS>; } };
 template <> struct DeepPath<DeepShipXArgs> : DeepPathOf<kShip, true, DeepShipXBlaArgs, FR_FLAG_DEEPX_SHIP_BLA> {
     static constexpr const char *name = "deep_kernel<DeepShipXArgs>", *bla_name = "deep_kernel<DeepShipXBlaArgs>"; };
 template <> struct DeepPath<DeepJuliaXArgs> : DeepPathOf<kJulia, true, DeepJuliaXBlaArgs, FR_FLAG_DEEPX_JULIA_BLA> {
     static constexpr const char *name = "deep_kernel<DeepJuliaXArgs>", *bla_name = "deep_kernel<DeepJuliaXBlaArgs>"; };
 
-/* One pass of a deep view, `base` being the argument block of its unflagged kernel: deep_kernel<BASE> at the occupancy cached in
- * its slot, or with `bla` the table, then the path's flagged kernel on the same queue plan at its own occupancy, its counters
- * cleared in front of it and copied to pinned memory behind it.  The slot's event is recorded behind every such render unless
- * the stream is capturing: table rebuilds and orbit uploads wait for it. */
+/* One pass of a deep view, `base` being the argument block of its unflagged kernel: the path's kernel of BASE at the occupancy
+ * cached in its slot, or with `bla` the table, then the path's flagged kernel on the same queue plan at its own occupancy, its
+ * counters cleared in front of it and copied to pinned memory behind it.  The slot's event is recorded behind every such render
+ * unless the stream is capturing: table rebuilds and orbit uploads wait for it. */
 template <class BASE>
 static int launch_deep(fr_ctx* c, hipStream_t stream, BASE& base, bool bla)
 {
@@ -1013,7 +1019,7 @@ static int launch_deep(fr_ctx* c, hipStream_t stream, BASE& base, bool bla)
     DeepSlot& s = deep_slot(c, P::ext, P::f);
     if (!bla) {
         DeepArgs& d = deep_of(base);
-        return launch_one_pass(c, stream, P::name, deep_kernel<BASE>, base, d.g, d.q, s.wg_per_cu[P::de][0], false);
+        return launch_one_pass(c, stream, P::name, P::template kernel<BASE>(), base, d.g, d.q, s.wg_per_cu[P::de][0], false);
     }
     BLA a;
     memset(&a, 0, sizeof(a));
@@ -1037,7 +1043,7 @@ static int launch_deep(fr_ctx* c, hipStream_t stream, BASE& base, bool bla)
     }
     tab.steps = t.steps_dev;
     FR_HIP_TRY(hipMemsetAsync(t.steps_dev, 0, 3 * sizeof(unsigned long long), stream));
-    const int st = launch_one_pass(c, stream, P::bla_name, deep_kernel<BLA>, a, d.g, d.q, s.wg_per_cu[P::de][1], false);
+    const int st = launch_one_pass(c, stream, P::bla_name, P::template kernel<BLA>(), a, d.g, d.q, s.wg_per_cu[P::de][1], false);
     if (st != FR_OK) return st;
     FR_HIP_TRY(hipMemcpyAsync(t.steps_host, t.steps_dev, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
     t.have_steps = true;
@@ -1512,10 +1518,11 @@ static int enqueue_ssaa_staged(fr_ctx* c, const fr_params* p, uint32_t W, uint32
 }
 
 /* ---- render entry points --------------------------------------------------------------------------------------------
- * fr_render_shard, fr_render_phoenix, fr_render_mandelbulb and the seven deep entry points (fr_render_deep, _deep_de,
- * _deep_ship, _deepx, _deepx_ship, _deep_julia, _deepx_julia; all through deep_entry), each with its _async form: their
- * parameter checks, then render_sync / render_async with the planes beyond fr_output's three (ExtraPlanes; fr_render_deep_de
- * alone has any) and the enqueue step as enqueue(shard, rgba, nu, iter, extra planes, stream, out_frame) */
+ * fr_render_shard, fr_render_phoenix, fr_render_mandelbulb and the eight deep entry points (fr_render_deep, _deep_de,
+ * _deep_ship, _deepx, _deepx_de, _deepx_ship, _deep_julia, _deepx_julia; all through deep_entry), each with its _async form:
+ * their parameter checks, then render_sync / render_async with the planes beyond fr_output's three (ExtraPlanes;
+ * fr_render_deep_de and fr_render_deepx_de alone have any) and the enqueue step as enqueue(shard, rgba, nu, iter, extra planes,
+ * stream, out_frame) */
 static int check_common(fr_ctx* c, const fr_params* p, uint32_t W, uint32_t H, const fr_output* out)
 {
     if (!c) return fr_set_error(FR_ERR_INVALID_ARG, "ctx is NULL");
@@ -1894,10 +1901,10 @@ extern "C" int fr_render_mandelbulb(fr_ctx* c, const fr_params* p, const fr_mand
         return enqueue_mandelbulb(c, p, mb, W, H, sh, rgba, nu, iter, s, out_frame); });
 }
 
-/* The fourteen deep entry points: BASE names the path (DeepPath), async_entry the _async form (nullptr: the synchronous one),
+/* The sixteen deep entry points: BASE names the path (DeepPath), async_entry the _async form (nullptr: the synchronous one),
  * validate() runs the path's validator once the pointers are known not to be NULL, and the enqueue step is enqueue_deep_view of
- * the view read into a DeepAt.  e: fr_render_deep_de's block, whose two planes travel as extra planes into the derivative's
- * fields; nullptr for every other path. */
+ * the view read into a DeepAt.  e: the block of fr_render_deep_de and fr_render_deepx_de, whose two planes travel as extra
+ * planes into the derivative's fields; nullptr for every other path. */
 template <class BASE, class VIEW, class Validate>
 static int deep_entry(const char* async_entry, fr_ctx* c, const fr_params* p, const VIEW* v, const fr_deep_de* e, uint32_t W,
                       uint32_t H, const fr_shard* shard, const fr_output* out, void* hip_stream, Validate&& validate)
@@ -1910,7 +1917,9 @@ static int deep_entry(const char* async_entry, fr_ctx* c, const fr_params* p, co
     if (st != FR_OK) return st;
     ExtraPlanes extra;
     if constexpr (de)
-        extra = {2, {{e->deriv, 16}, {e->de, 8}}, "fr_render_deep_de: neither fr_output nor fr_deep_de has a plane to write"};
+        extra = {2, {{e->deriv, 16}, {e->de, 8}},
+                 DeepPath<BASE>::ext ? "fr_render_deepx_de: neither fr_output nor fr_deep_de has a plane to write"
+                                     : "fr_render_deep_de: neither fr_output nor fr_deep_de has a plane to write"};
     auto enqueue = [&](auto sh, auto rgba, auto nu, auto iter, void* const* xp, auto s, bool out_frame) {
         DeepAt at = {v->center_x, v->center_y, nullptr, p->zoom, 0, v->frac_bits};
         if constexpr (DeepPath<BASE>::ext) {     /* the zoom is the view's string: resolved here, with the automatic F */
@@ -1922,7 +1931,13 @@ static int deep_entry(const char* async_entry, fr_ctx* c, const fr_params* p, co
         }
         return enqueue_deep_view<BASE>(c, p, at, W, H, sh, rgba, nu, iter, s, out_frame, [&](BASE& a) {
             if constexpr (de) {                  /* s = zoom / H of the whole frame, whatever rows this part owns */
-                a.s = p->zoom / (double)H;
+                if constexpr (DeepPath<BASE>::ext) {     /* norm1(zm / H, ze) */
+                    int k = 0;
+                    a.sm = frexp(at.zm / (double)H, &k);
+                    a.es = at.ze + k;
+                } else {
+                    a.s = p->zoom / (double)H;
+                }
                 a.deriv = (double*)xp[0]; a.de = (double*)xp[1];
                 a.shade = e->shade; a.edge_px = e->edge_px;
             }
@@ -1987,6 +2002,21 @@ extern "C" int fr_render_deepx(fr_ctx* c, const fr_params* p, const fr_deepx_vie
 {
     return deep_entry<DeepXArgs>(nullptr, c, p, v, nullptr, W, H, shard, out, nullptr,
                                  [&] { return fr_deepx_validate(p, v, W, H); });
+}
+
+/* fr_render_deepx_de: fr_render_deep_de's five planes on fr_render_deepx's path */
+extern "C" int fr_render_deepx_de_async(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, const fr_deep_de* e, uint32_t W,
+                                        uint32_t H, const fr_shard* shard, const fr_output* out, void* hip_stream)
+{
+    return deep_entry<DeepXDeArgs>("fr_render_deepx_de_async", c, p, v, e, W, H, shard, out, hip_stream,
+                                   [&] { return fr_deepx_de_validate(p, v, e, W, H); });
+}
+
+extern "C" int fr_render_deepx_de(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, const fr_deep_de* e, uint32_t W,
+                                  uint32_t H, const fr_shard* shard, const fr_output* out)
+{
+    return deep_entry<DeepXDeArgs>(nullptr, c, p, v, e, W, H, shard, out, nullptr,
+                                   [&] { return fr_deepx_de_validate(p, v, e, W, H); });
 }
 
 extern "C" int fr_render_deepx_ship_async(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, uint32_t W, uint32_t H,

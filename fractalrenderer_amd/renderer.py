@@ -301,9 +301,9 @@ class Renderer:
         debug shader's distance shading to every escaped sub-sample (edge_px: the smoothstep's upper edge in pixel spacings);
         without it rgba is render_deep()'s.  iter, nu and last_deep_steps() are render_deep()'s, and the context's orbit and
         BLA table are shared with it.  bla=True sets FR_FLAG_DEEP_BLA.  A view with a zoom string is a ValueError: below
-        1e-290 the derivative needs an exponent of its own."""
+        1e-290 the derivative needs an exponent of its own, and render_deepx_de() carries one."""
         if view is not None and view.zoom is not None:
-            raise ValueError("render_deep_de takes the zoom from the state: extended views (a zoom string) have no distance estimate")
+            raise ValueError("render_deep_de takes the zoom from the state: extended views (a zoom string) go to render_deepx_de")
         p = state.to_params(FractalType.Mandelbrot, Precision.F64, post_chain)
         if bla:
             p.flags |= _capi.FR_FLAG_DEEP_BLA
@@ -313,6 +313,30 @@ class Renderer:
         # (through the class: tests call this method on a stand-in for the renderer that has _lib, _ctx and _output only)
         Renderer._render_call(self, self._lib.fr_render_deep_de, self._lib.fr_render_deep_de_async,
                               (C.byref(p), C.byref(v), C.byref(e)), width, height, Precision.F64, rows, rgba, nu, iter, shard,
+                              stream, sync, extra=((e, "de", de, "float64", 1), (e, "deriv", deriv, "float64", 2)))
+
+    def render_deepx_de(self, state: FractalState, width: int, height: int, view: DeepView, *, post_chain: bool = False,
+                        rgba=None, nu=None, iter=None, de=None, deriv=None, shade: bool = False,
+                        edge_px: float = DEEP_DE_EDGE_PX, shard: Optional[Shard] = None, stream: Optional[int] = None,
+                        sync: bool = True, bla: bool = False) -> None:
+        """fr_render_deepx_de / fr_render_deepx_de_async: render_deep_de() for a view with a zoom string
+        (DeepView(..., zoom="1e-400")), zooms down to 1e-1000: the derivative is carried with an exponent of its own through
+        both modes of the extended loop.  A view without a zoom string is a ValueError (render_deep_de() takes those).
+        de, deriv, shade and edge_px as for render_deep_de(): de stays finite at any depth, deriv saturates outside a
+        double's range.  iter, nu and rgba without shade are render_deep()'s of the same view, and the context's extended
+        orbit and table are shared with it.  bla=True sets FR_FLAG_DEEPX_BLA (last_deepx_steps() reports what it skipped)."""
+        if view is None or view.zoom is None:
+            raise ValueError("render_deepx_de needs a view with a zoom string (DeepView(..., zoom=\"1e-400\")); "
+                             "render_deep_de renders views without one")
+        p = state.to_params(FractalType.Mandelbrot, Precision.F64, post_chain)
+        if bla:
+            p.flags |= _capi.FR_FLAG_DEEPX_BLA
+        vx = view.to_cx()
+        rows = shard.rows(height) if shard else height
+        e = _capi.fr_deep_de(None, None, 1 if shade else 0, float(edge_px))
+        # (through the class, as render_deep_de)
+        Renderer._render_call(self, self._lib.fr_render_deepx_de, self._lib.fr_render_deepx_de_async,
+                              (C.byref(p), C.byref(vx), C.byref(e)), width, height, Precision.F64, rows, rgba, nu, iter, shard,
                               stream, sync, extra=((e, "de", de, "float64", 1), (e, "deriv", deriv, "float64", 2)))
 
     def render_deep_ship(self, state: FractalState, width: int, height: int, view: Optional[DeepView] = None, *,

@@ -550,7 +550,8 @@ int fr_ctx_last_deep_steps(fr_ctx* ctx, uint64_t out[3]);
  * Validation: everything fr_render_deep checks; `de` NULL, shade outside {0, 1}, or shade == 1 with edge_px not finite or
  * <= 0 is FR_ERR_INVALID_ARG.
  * Cost: four live VGPRs and 11 fp64 operations per plain update on top of the step's 18 (README: measured).
- * Out of scope: extended views below 1e-290 (s underflows there and D needs an exponent of its own); the Burning Ship, which
+ * Extended views below 1e-290, where s underflows and D needs an exponent of its own, are fr_render_deepx_de (below,
+ * FR_HAS_DEEPX_DE).  Out of scope: the Burning Ship, which
  * needs a real 2x2 Jacobian; Julia sets; fr_deep_sequence; fr_node and .franim; slope or normal lighting -- deriv is what a
  * caller needs for it. */
 #define FR_HAS_DEEP_DE 1
@@ -822,6 +823,63 @@ int fr_render_deepx_async(fr_ctx* ctx, const fr_params* p, const fr_deepx_view* 
  * out[0] single steps (plain and extended), out[1] BLA steps, out[2] updates skipped.  FR_ERR_UNSUPPORTED if there is no
  * such call.  fr_ctx_last_deep_steps does not report these calls. */
 int fr_ctx_last_deepx_steps(fr_ctx* ctx, uint64_t out[3]);
+
+/* ---- distance estimates for extended views ------------------------------------------------------------------------------------
+ * fr_render_deep_de (above, FR_HAS_DEEP_DE) for the views of fr_render_deepx: the same two planes more, the distance estimate
+ * of sample (0,0) in pixel spacings and the scaled derivative D = dz/dc * s, down to zoom 1e-1000.  The view is fr_deepx_view,
+ * the distance block fr_deep_de with fr_deep_de_default unchanged; range, precision and flags are fr_render_deepx's:
+ * Mandelbrot, FR_PRECISION_F64, plain or with FR_FLAG_DEEPX_BLA.  Every other entry point is untouched.
+ *
+ * Below 1e-290 s = zoom / H underflows and D, which starts at s and reaches about 1 / de, crosses more than a double's range
+ * on its way.  So D is an extended complex number (D.x, D.y, D.e) for the whole orbit, whatever mode the sample's delta is in,
+ * normalised with norm after every update; the zero has FR_DEEPX_ZERO_EXP.  Notation as above: norm, and
+ * (a, ea) (+) (b, eb) = ldexp(a, ea - e) + ldexp(b, eb - e) at e = max(ea, eb), per component.  Every operation is one fp64
+ * rounding or an exact scaling, no contraction.
+ *   - s = (sm, es) = the extended real (zm / (double)H, ze) normalised, H the height of the WHOLE frame, zm 2^ze the view's
+ *     zoom (fr_deepx_zoom); the division is rounded once.  D = (0, 0, FR_DEEPX_ZERO_EXP) at the start.
+ *   - EXTENDED single step: D' is formed from the sample's point before the update,
+ *       eb = max(Z_m.e, dz.e);   b = ldexp(Z_m, Z_m.e - eb) + ldexp(dz, dz.e - eb), per component;
+ *       P = (b.x D.x - b.y D.y,  b.x D.y + b.y D.x) at the exponent eP = eb + 1 + D.e  (the + 1 is the 2 of w = 2 z);
+ *       e = max(eP, es);   D' = norm(ldexp(P.x, eP - e) + ldexp(sm, es - e),  ldexp(P.y, eP - e),  e)
+ *     -- s is real: nothing is added to the imaginary part, whose zero keeps its sign as in fr_render_deep_de.
+ *   - PLAIN single step: b = Z_m + dz on the plain doubles, w = b + b (the sums of fr_render_deep_de's step),
+ *       P = (w.x D.x - w.y D.y,  w.x D.y + w.y D.x) at eP = D.e;   D' as above.
+ *   - BLA step (FR_FLAG_DEEPX_BLA) with the entry (A, B) the sample takes, in either mode:
+ *       P = A (x) D at eP = A.e + D.e;   Q = (B.x sm, B.y sm) at eQ = B.e + es;   D' = norm(P (+) Q)
+ *     -- the derivative of the linear map the step applies.
+ *   - A rebase and a change of mode leave D alone.
+ *   - Escape with r2 (the plain double both modes produce):  zl = sqrt(r2);  dl = sqrt(D.x D.x + D.y D.y) on the MANTISSAS;
+ *     de = ldexp((zl * log(zl)) / dl, -D.e), a NaN quotient becoming 0 first;  deriv = (ldexp(D.x, D.e), ldexp(D.y, D.e)),
+ *     which saturates to +-inf or 0 outside a double's range -- de does not, being formed from the mantissas.
+ *   - Interior samples: de = 0, deriv = (0, 0).
+ * Scaling by a power of two is exact, so on a view both entry points accept -- the zoom a double's decimal string -- iter,
+ * r2, de and deriv without BLA are bit for bit fr_render_deep_de's while no intermediate of either leaves a double's range.
+ * D never feeds back: iter, nu, rgba without shading and the three step counts are fr_render_deepx's byte for byte.
+ *
+ * Shading and planes: as fr_render_deep_de.  Shared state: the extended orbit slot, the extended BLA table with its key and
+ * fr_ctx_last_deepx_steps are fr_render_deepx's own -- a call here after fr_render_deepx of the same view computes no orbit
+ * and builds no table, and the reverse.
+ * Validation: everything fr_render_deepx checks; every BLA flag but FR_FLAG_DEEPX_BLA is FR_ERR_UNSUPPORTED (the two of the
+ * Burning Ship included, which fr_render_deepx does not read); `de` NULL, shade outside {0, 1}, or shade == 1 with edge_px not
+ * finite or <= 0 is FR_ERR_INVALID_ARG; of the five planes at least one must be given.
+ * Cost: five live VGPRs; per single step a complex product, an alignment and a norm on top of the step (README: measured).
+ * Neither kernel uses scratch or spills a VGPR.  Like every deep kernel they sit at the cap of 106 SGPRs and park scalar kernel
+ * arguments in VGPR lanes: 84 and 87 of them (76 and 78 in fr_render_deepx's kernels; the distance block adds nine scalars),
+ * written once in the prologue and read back per sample around the orbit loop, never inside it (checked on the ISA by
+ * tests/test_deepx_de_host.py).
+ * Out of scope: the Burning Ship, Julia sets, fr_deep_sequence, fr_node and .franim, slope or normal lighting. */
+#define FR_HAS_DEEPX_DE 1
+
+/* What fr_render_deepx_de checks of its arguments, the view's strings parsed included (no context needed). */
+int fr_deepx_de_validate(const fr_params* p, const fr_deepx_view* view, const fr_deep_de* de, uint32_t width, uint32_t height);
+
+/* fr_render_deepx with the distance planes; options, timing and the orbit cache as there. */
+int fr_render_deepx_de(fr_ctx* ctx, const fr_params* p, const fr_deepx_view* view, const fr_deep_de* de, uint32_t width,
+                       uint32_t height, const fr_shard* shard, const fr_output* out);
+
+/* Asynchronous form: fr_render_deepx_async's contract, de->de and de->deriv device planes like the others. */
+int fr_render_deepx_de_async(fr_ctx* ctx, const fr_params* p, const fr_deepx_view* view, const fr_deep_de* de, uint32_t width,
+                             uint32_t height, const fr_shard* shard, const fr_output* out, void* hip_stream);
 
 /* ---- deep zoom sequences: one centre, one orbit, frame after frame ---------------------------------------------------------
  * A zoom into one centre as an object: the zoom walked in log space over the whole range of fr_render_deepx, every frame

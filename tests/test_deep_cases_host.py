@@ -1,7 +1,8 @@
 """The deep parameter cases (tests/deep_cases.py) on the CPU: what each case can see, the restatements against the exact
-integer iteration across the bailout range, and five deliberately wrong builds of fill_deep_args / the orbit cache, emulated
-in numpy with the restatement in place of the kernel -- each must fail at least one case of the table.  No GPU, no product
-library: numpy, Python integers and the CPU oracle's colour stage."""
+integer iteration across the bailout range, and eight deliberately wrong builds of the argument blocks / the orbit cache,
+emulated in numpy with the restatement in place of the kernel -- each must fail at least one case of the table, the last
+three cases that the table of the first five paths did not have.  No GPU, no product library: numpy, Python integers and
+the CPU oracle's colour stage."""
 import functools
 import math
 from fractions import Fraction
@@ -10,6 +11,8 @@ import numpy as np
 import pytest
 
 import deep_cases as dc
+import deep_julia_bla_ref as JB
+import deep_julia_ref as J
 import deep_ref as R
 import deep_ship_ref as S
 import deepx_ref as X
@@ -49,16 +52,37 @@ def test_cases_can_fail(oracle, cid):
         both = (it < max_iter) & (it4 < max_iter)
         assert (it[both] != it4[both]).mean() >= 0.25
     elif group == "small":
-        assert sizes.max() / n <= 0.70 and len(classes) >= 2 and r.N >= 6
+        assert sizes.max() / n <= 0.70 and len(classes) >= 2 and r.N >= 6          # (Julia: N is N_P)
         assert not (np.float32(dc.bailout_of(case)) > np.float32(1.0))             # the lib_log branch
         assert len(classes[classes < max_iter]) >= 2                               # escapes at two different updates
+        want_nq = dc.SMALL_NQ.get((case.view, dc.bailout_of(case)))
+        if want_nq is not None:
+            assert case.path in dc.JULIA_PATHS and r.NQ == want_nq and r.NQ <= 2
+            if case.path == "julia":                                               # samples walk the short Q, or none leaves P
+                walked = r.stats["moved"][0] > 0.0
+                print("share of the samples that leave P for Q", r.stats["moved"][0])
+                assert walked == ((case.view, dc.bailout_of(case)) != ("DENDRITE30", 0.75))
+        if case.path in ("julia_bla", "juliax_bla") and case.view == "RABBIT30" and dc.bailout_of(case) == 0.75:
+            assert r.stats["bla_q"] == 0 and r.stats["bla_p"] > 0                  # Q has no table, P's alone takes steps
     elif group == "short":
         assert r.N == dc.SHORT_N[case.view]
         assert 0.05 <= 1.0 - escaped <= 0.95
         surviving = int((it == max_iter).sum())
-        rb = dc.rebases(case.path == "ship", case.view, max_iter, dc.bailout_of(case), case.W, case.H)
+        rb = dc.rebases_of(case)
         print("rebases", rb, "bar", surviving * max_iter / r.N * 0.9)
         assert rb >= surviving * max_iter / r.N * 0.9
+        if case.path in ("julia_bla", "juliax_bla"):
+            print("BLA steps on P", r.stats["bla_p"], "on Q", r.stats["bla_q"])
+            if r.N <= 2:
+                assert r.stats["bla_p"] == 0                                       # an orbit of one or two updates has no table
+    elif group == "max_iter" and case.path in dc.JULIA_PATHS:
+        # a shallow frame whose centre lies near the escape radius: samples escape at update 0, 1, .. and survive, all in one
+        # frame, so a loop that runs once too often or once too few moves a whole class of iter
+        assert max_iter in (1, 2, 3) and len(classes) >= max_iter + 1
+        assert sizes.min() / n >= 0.05
+        assert list(classes) == list(range(max_iter + 1))                          # updates 0 .. max_iter - 1, and the survivors
+        if r.counts is not None:
+            assert r.counts[0] + r.counts[2] == J.lane_updates(it, max_iter)
     elif group == "max_iter":
         # nothing escapes in three updates of these views: the planes are constant, and what a loop that runs once too
         # often or not at all changes is the step counts of the BLA paths (every sample: max_iter updates, no more)
@@ -90,6 +114,11 @@ def test_cases_can_fail(oracle, cid):
     elif group == "ship_noop":
         assert case.params["stripe_enabled"] and case.params["interior_style"] != 2
         assert 1.0 - escaped >= 0.10 and escaped >= 0.50
+    elif group == "julia_noop":
+        assert case.path == "julia" and any(case.params.get(k) for k in ("interior_style", "orbit_trap_enabled", "stripe_enabled"))
+        assert 1.0 - escaped >= 0.10 and escaped >= 0.50
+        # Julia's shader has no styles: the expected colours are those of the defaults, bit for bit
+        assert np.array_equal(dc.expected_rgb(oracle, case).view(np.uint32), dc.expected_rgb(oracle, case, {}).view(np.uint32))
     else:
         raise AssertionError(group)
 
@@ -97,12 +126,44 @@ def test_cases_can_fail(oracle, cid):
 def test_the_table_holds_what_the_groups_promise():
     assert len(dc.CASES) == sum(len(g) for g in dc.GROUPS.values())
     paths = {g: {c.path for c in cases.values()} for g, cases in dc.GROUPS.items()}
-    assert paths["bailout"] == set(dc.PATHS) and paths["short"] == set(dc.PATHS)
-    assert paths["max_iter"] == {"deep", "deep_bla", "ship", "deepx_bla"}
-    assert paths["colour"] == {"deep", "deepx", "ship"}
-    for path in ("deep", "deepx", "ship"):
-        kinds = [dc.colour_expectation(c) for c in dc.GROUPS["colour"].values() if c.path == path and "palette_mode" in c.params]
-        assert kinds.count("differs") >= 5                                          # every defined palette beside mode 0
+    julia = set(dc.JULIA_PATHS)
+    assert paths["bailout"] == set(dc.PATHS)
+    assert paths["small"] == {"deep", "ship", "ship_bla", "shipx", "shipx_bla", "dex"} | julia
+    assert paths["short"] == {"deep", "deep_bla", "deepx", "deepx_bla", "ship", "ship_bla", "shipx"} | julia
+    assert paths["max_iter"] == {"deep", "deep_bla", "ship", "deepx_bla", "ship_bla", "shipx_bla", "dex_bla", "de"} | julia
+    assert paths["colour"] == {"deep", "deepx", "ship", "julia", "dex_bla", "de"}
+    assert paths["aa"] == {"deep", "ship", "julia", "juliax_bla", "shipx", "dex"}
+    for path in ("deep", "deepx", "ship", "julia", "dex_bla", "de"):
+        for shaded in (False, True):
+            kinds = [dc.colour_expectation(c) for c in dc.GROUPS["colour"].values()
+                     if c.path == path and "palette_mode" in c.params and bool(c.params.get("shade")) == shaded]
+            if kinds:
+                assert kinds.count("differs") >= 5                                  # every defined palette beside mode 0
+    shaded = [c for c in dc.GROUPS["colour"].values() if c.params.get("shade")]
+    assert {c.path for c in shaded} == {"dex_bla", "de"} and all(c.params["edge_px"] == 1.8 for c in shaded)
+    assert all(c.params.get("shade") for c in dc.GROUPS["aa"].values() if c.path == "dex")
+    # the Julia edges, each a case: N_Q of 1 and of 2, N_P of 1, 2 and 3, max_iterations 1 to 3 on all four kernels
+    for path in julia:
+        assert {dc.SMALL_NQ.get((c.view, dc.bailout_of(c))) for c in dc.GROUPS["small"].values() if c.path == path} == {1, 2, None}
+    for path in julia:
+        assert {dc.SHORT_N[c.view] for c in dc.GROUPS["short"].values() if c.path == path} == {1, 2, 3}
+        assert {c.params["max_iterations"] for c in dc.GROUPS["max_iter"].values() if c.path == path} == {1, 2, 3}
+    for c in dc.CASES.values():
+        assert c.view not in ("E", "DENDRITE1000", "TIP1000")
+
+
+def test_every_kernel_of_the_family_runs_in_some_case():
+    """fr_deep.hip.h instantiates sixteen kernels, fourteen deep_kernel<ARGS> and two deepx_de_kernel<ARGS>; a path is one of
+    them (dc.KERNELS: DeepPath<BASE>::name / bla_name of fr_device.hip), and every path has cases"""
+    assert len(dc.PATHS) == 16 and len(set(dc.KERNELS.values())) == 16
+    kernels = {dc.KERNELS[c.path] for c in dc.CASES.values()}
+    assert kernels == set(dc.KERNELS.values())
+    assert sum(k.startswith("deep_kernel<") for k in kernels) == 14 and sum(k.startswith("deepx_de_kernel<") for k in kernels) == 2
+    import os, re
+    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "fractalrenderer_amd", "csrc",
+                            "fr_device.hip")).read()
+    named = set(re.findall(r'"(deepx?_(?:de_)?kernel<\w+>)"', src))
+    assert named == set(dc.KERNELS.values()), named ^ set(dc.KERNELS.values())
 
 
 # ---- 2. the restatements are ground truth across the bailout range ---------------------------------------------------------
@@ -155,6 +216,22 @@ def test_small_bailout_centres_agree_with_exact_iteration(path, view, bailout):
     agreement = float((it[ys, xs] == ex).mean())
     print(path, view, bailout, "agreement", agreement, "classes of the 48 pixels", np.unique(ex))
     assert agreement >= 0.99
+    assert len(np.unique(ex)) >= 2
+
+
+@pytest.mark.parametrize("view,bailout", [("RABBIT30", 0.75), ("DENDRITE30", 0.75), ("DUST30", 0.75), ("RABBIT30", 1.0),
+                                          ("DENDRITE30", 1.0), ("J_N1", 4.0), ("J_N2", 4.0), ("J_N3", 4.0)])
+def test_julia_views_agree_with_exact_iteration(view, bailout):
+    """the Julia views of the small and short cases, fp64 and extended restatement, against the direct iteration in integers
+    on the 48 pixels of a 64 x 48 frame; the bar of the two tests above"""
+    v = dict(dc.VIEWS[view])
+    ys, xs = _pixels()
+    ex = np.array([J.exact_iter(v, int(x), int(y), PW, PH, bailout) for x, y in zip(xs, ys)])
+    it = J.restate(v, PW, PH, 1, bailout)[0][0]
+    itx = J.restate_x(v, PW, PH, 1, bailout)[0][0]
+    agreement = float((it[ys, xs] == ex).mean())
+    print(view, bailout, "agreement", agreement, "classes of the 48 pixels", np.unique(ex))
+    assert agreement >= 0.99 and float((itx[ys, xs] == ex).mean()) >= 0.99
     assert len(np.unique(ex)) >= 2
 
 
@@ -291,7 +368,7 @@ def test_wrong_build_3_mandelbrot_palette_table_for_the_ship(oracle):
 def test_wrong_build_4_lib_log_taken_as_bailout_below_1(oracle):
     """a.lib_log = bailout < 1: at bailout 1 exactly the table log2 runs in place of the library log.  Both compute the same
     function; the table's error is absolute (1e-16), and log2(r2) of the samples that escape on the level curve |z_k| = 1 is
-    1e-10: nu is wrong from the sixth digit.  For the ship both branches give -inf at bailout 1 (log 1 = 0 divides)."""
+    1e-10: nu is wrong from the sixth digit.  For the ship and Julia both branches give -inf at bailout 1 (log 1 = 0 divides)."""
     def fails(cid, case):
         if dc.bailout_of(case) != 1.0:
             return False                                              # the branch taken is the same
@@ -299,13 +376,13 @@ def test_wrong_build_4_lib_log_taken_as_bailout_below_1(oracle):
         want = dc.expected_nu(case)
         got = want.copy()
         e = it < dc.view_of(case)["max_iter"]
-        if case.path == "ship":                                       # lg.log2(lg.log2(r2) * (1 / log2(1)))
+        if dc.formula(case.path) != 0:                                # lg.log2(lg.log2(r2) * (1 / log2(1)))
             got[e] = [(i + 1.0) - math.log2(_log2_tab(float(x)) * math.inf) for i, x in zip(it[e], r2[e])]
         else:
             got[e] = [(i + 1.0) - _log2_tab(0.5 * _log2_tab(float(x))) for i, x in zip(it[e], r2[e])]
         return _nu_fails(got, want)
     bad = _failing(list(dc.CASES), fails)
-    assert bad == ["small/deep-UNIT_M-b1"]
+    assert bad == ["small/deep-UNIT_M-b1", "small/dex-UNIT_M-b1"]
 
 
 def test_wrong_build_5_orbit_cache_key_without_the_bailout():
@@ -323,3 +400,76 @@ def test_wrong_build_5_orbit_cache_key_without_the_bailout():
     print(got)
     assert got["A"] == 0 and got["SHIP_A"] == 0
     assert got["M_N3"] >= 10 and got["S_N3"] >= 10
+
+
+# ---- 4. three wrong builds that the table of the first five paths could not see -----------------------------------------------
+def test_wrong_build_6_log_bailout_left_zero_in_a_non_mandelbrot_block(oracle):
+    """log(bailout) reaches the eight ship and Julia kernels through eight ship_log_bailout overloads, a flagged kernel's from
+    the base block copied into {base block, table} (launch_deep).  A block whose field stays 0: shade<double, 1> and
+    shade<double, 2> read it in the lib_log branch alone, nu = (it + 1) - log(log(r2) / 0) / ln 2 -- NaN for r2 < 1, -inf for
+    r2 > 1, where the right build divides by log(0.75) < 0 and is finite for r2 < 1.  At bailout 1 exactly log(bailout) IS 0:
+    the builds coincide, so the cases that fail are the ship-family and Julia small cases below 1, and no other.  Of the
+    eight paths the old table ran one."""
+    ln2 = np.log(np.float64(2.0))
+
+    def fails(cid, case):
+        if dc.formula(case.path) == 0 or np.float32(dc.bailout_of(case)) > np.float32(1.0):
+            return False                                              # Mandelbrot's shade<double, 0> has no such field; not lib_log
+        it, r2 = dc.restated(case).samples[0]
+        got = dc.expected_nu(case).copy()
+        e = it < dc.view_of(case)["max_iter"]
+        with np.errstate(all="ignore"):
+            got[e] = (it[e].astype(np.float64) + 1.0) - np.log(np.log(r2[e]) / np.float64(0.0)) / ln2
+        return _nu_fails(got, dc.expected_nu(case))
+    bad = _failing(list(dc.CASES), fails)
+    want = [cid for cid in dc.GROUPS_BY_ID["small"] if dc.formula(dc.CASES[cid].path) != 0 and dc.bailout_of(dc.CASES[cid]) < 1.0]
+    assert sorted(bad) == sorted(want)
+    assert {dc.CASES[cid].path for cid in bad} == set(dc.SHIP_PATHS) | set(dc.JULIA_PATHS)
+    assert {dc.CASES[cid].path for cid in bad} & set(dc.OLD_PATHS) == {"ship"}
+
+
+def test_wrong_build_7_julia_tables_swapped():
+    """P's lanes given Q's table (its n1 / K and entries) and Q's lanes P's, on the two flagged Julia kernels: the stepping of
+    deep_julia_bla_ref with the pair of tables swapped.  On RABBIT30 at bailout 0.75 Q has no table, so P's lanes take none of
+    their 24 726 steps: the counts differ.  The old table had no Julia case."""
+    def fails(cid, case):
+        if case.path not in ("julia_bla", "juliax_bla"):
+            return False
+        v, r = dc.view_of(case), dc.restated(case)
+        b = dc.bailout_of(case)
+        try:
+            if case.path == "julia_bla":
+                P, Q = J.reference_orbits(v, b)
+                got, counts = JB.restate_bla(v, case.W, case.H, 1, b, orbits=(P, Q), tabs=JB.bla_tables(P, Q)[::-1])
+            else:
+                Px, Qx = J.reference_orbits_x(v, b)
+                got, counts = JB.restate_x_bla(v, case.W, case.H, 1, b, orbits=(Px, Qx), tabs=JB.bla_tables_x(Px, Qx)[::-1])
+        except IndexError:
+            return True                                               # a lane looked past the end of the other orbit's table
+        by_counts = tuple(int(c) for c in counts) != r.counts
+        print(cid, "counts", tuple(counts), "for", r.counts, "iter differing", int((got[0][0] != r.samples[0][0]).sum()))
+        return by_counts
+    bad = _failing(dc.GROUPS_BY_ID["short"] + dc.GROUPS_BY_ID["small"], fails)
+    # every flagged Julia small case sees it by its counts (at bailout 0.75 P's lanes take no BLA step at all); the short
+    # frames do not: a shallow delta is above every radius of either table, and the counts of both builds are the plain steps
+    assert sorted(bad) == sorted(cid for cid in dc.GROUPS_BY_ID["small"] if dc.CASES[cid].path in ("julia_bla", "juliax_bla"))
+    assert "small/julia_bla-RABBIT30-b0.75" in bad and "small/juliax_bla-RABBIT30-b0.75" in bad
+    assert not {dc.CASES[cid].path for cid in bad} & set(dc.OLD_PATHS)
+
+
+def test_wrong_build_8_the_de_blocks_shade_or_edge_dropped(oracle):
+    """DeepDeArgs / DeepXDeArgs with shade left 0 (rgba is fr_render_deep's), or with edge_px left 0 (de / 0: the smoothstep
+    saturates and nothing is shaded either): every shaded colour case fails.  The old table rendered no DE kernel."""
+    shaded = [cid for cid in dc.GROUPS_BY_ID["colour"] if dc.CASES[cid].params.get("shade")]
+    assert len(shaded) == 32
+
+    def no_shade(cid, case):
+        return _rgb_fails(dc.expected_rgb(oracle, case, dict(case.params, shade=False)), dc.expected_rgb(oracle, case))
+
+    def no_edge(cid, case):
+        with np.errstate(all="ignore"):
+            got = dc.expected_rgb(oracle, case, dict(case.params, edge_px=0.0))
+        return _rgb_fails(got, dc.expected_rgb(oracle, case))
+    assert _failing(shaded, no_shade) == shaded
+    assert _failing(shaded, no_edge) == shaded
+    assert not {dc.CASES[cid].path for cid in shaded} & set(dc.OLD_PATHS)

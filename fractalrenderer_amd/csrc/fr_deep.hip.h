@@ -61,6 +61,12 @@
  *     whatever mode the lane's delta is in, normalised after every update; s = (sm, es) stays in SGPRs.  Five live VGPRs.  Its
  *     two kernels are deepx_de_kernel<ARGS>, a second __global__ template around the one body (deep_kernel_body), so that the
  *     set of deep_kernel instantiations stays what it was.
+ *   - the distance estimate of Julia views (fr_render_deep_julia_de, fr_render_deepx_julia_de; DeepJuliaDeArgs, DeepJuliaDeBlaArgs,
+ *     DeepJuliaXDeArgs, DeepJuliaXDeBlaArgs): the option DE of all four loops for a formula without a dc term (kHasB == false).
+ *     D = dz_n/dz_0 * s starts at s, not at 0; an update is one complex product, D' = 2 z D or D' = A D, and nothing is added (the
+ *     overloads of deep_step_d, deep_step_xd, deep_step_pd and deepx_d_set without s); the extended D is flushed to the zero below
+ *     2^-2^27 as the delta is.  Four and five live VGPRs.  Their kernels are julia_de_kernel<ARGS>, a third __global__ template
+ *     around the one body.
  */
 #pragma once
 #include "fr_kernels.hip.h"
@@ -226,10 +232,47 @@ struct DeepJuliaXBlaArgs {
     JuliaTab<BlaXTable> t;
 };
 
+/* fr_render_deep_julia_de: DeepJuliaArgs with the scaled derivative D = dz_n/dz_0 * s carried next to the delta; the distance
+ * fields are DeepDeArgs's */
+struct DeepJuliaDeArgs {
+    DeepArgs d;
+    double log_bailout;
+    JuliaStart j;
+    double s;
+    double* de;
+    double* deriv;
+    int32_t shade;
+    float edge_px;
+};
+
+struct DeepJuliaDeBlaArgs {
+    DeepJuliaDeArgs e;
+    JuliaTab<BlaTable> t;
+};
+
+/* fr_render_deepx_julia_de: DeepJuliaXArgs with the derivative as an extended complex number; the distance fields are
+ * DeepXDeArgs's */
+struct DeepJuliaXDeArgs {
+    DeepXArgs x;
+    double log_bailout;
+    JuliaStart j;
+    double sm;
+    int32_t es;
+    double* de;
+    double* deriv;
+    int32_t shade;
+    float edge_px;
+};
+
+struct DeepJuliaXDeBlaArgs {
+    DeepJuliaXDeArgs e;
+    JuliaTab<BlaXTable> t;
+};
+
 constexpr int kXZero = FR_DEEPX_ZERO_EXP;
 constexpr int kXThr = -400;              /* extended while the normalised dz.e <= kXThr */
 constexpr int kXBlaExpLim = 1 << 27;     /* an entry whose A.e or B.e leaves [-2^27, 2^27] is void */
-constexpr int kXFlushExp = -(1 << 27);   /* Julia: a normalised dz with e below this becomes the zero (the header's FLUSH) */
+constexpr int kXFlushExp = -(1 << 27);   /* Julia: a normalised dz, or D, with e below this becomes the zero (the header's FLUSH) */
 
 /* ---- extended reals ----------------------------------------------------------------------------------------------------
  * norm(x, y, e) of the header */
@@ -340,6 +383,16 @@ __device__ __forceinline__ void deepx_d_set(XDeriv& D, const double px, const do
     D.y = __builtin_ldexp(py, ep - e);
     D.e = e;
     x_norm(D.x, D.y, D.e);
+    asm volatile("" : "+v"(D.x), "+v"(D.y), "+v"(D.e));
+}
+
+/* ... without q, a formula without a dc term (Julia): D' = norm(p), then the header's FLUSH of D -- below 2^-2^27 it becomes
+ * the zero and stays it (a product with the zero is the zero) */
+__device__ __forceinline__ void deepx_d_set(XDeriv& D, const double px, const double py, const int ep)
+{
+    D.x = px; D.y = py; D.e = ep;
+    x_norm(D.x, D.y, D.e);
+    if (D.e < kXFlushExp) { D.x = 0.0; D.y = 0.0; D.e = kXZero; }
     asm volatile("" : "+v"(D.x), "+v"(D.y), "+v"(D.e));
 }
 
@@ -626,11 +679,29 @@ struct JuliaFormula {
         const double2 a = T.ab[e];
         return make_double2(a.x * dzx - a.y * dzy, a.x * dzy + a.y * dzx);
     }
+    /* bla() with the derivative of the map it applies, from the one load of A: D' = A D, nothing added */
+    static __device__ __forceinline__ double2 bla_d(const BlaTable& T, const uint32_t e, const double dzx, const double dzy,
+                                                    const double, const double, const double, double2& D)
+    {
+        const double2 a = T.ab[e];
+        D = make_double2(a.x * D.x - a.y * D.y, a.x * D.y + a.y * D.x);
+        deep_pin_d(D);
+        return make_double2(a.x * dzx - a.y * dzy, a.x * dzy + a.y * dzx);
+    }
     static __device__ __forceinline__ BlaStepX bla_x(const BlaXTable& T, const uint32_t e, const double qx, const double qy,
                                                      const double, const double)
     {
         const double2 a = T.ab[e];
         return {a.x * qx - a.y * qy, a.x * qy + a.y * qx, 0.0, 0.0, reinterpret_cast<const int32_t*>(T.abe)[e], 0};
+    }
+    /* bla_x() with the derivative of the map it applies, from the one load of the entry: D' = norm(A D, A.e + D.e), flushed */
+    static __device__ __forceinline__ BlaStepX bla_x_d(const BlaXTable& T, const uint32_t e, const double qx, const double qy,
+                                                       const double, const double, const double, const int, XDeriv& D)
+    {
+        const double2 a = T.ab[e];
+        const int ea = reinterpret_cast<const int32_t*>(T.abe)[e];
+        deepx_d_set(D, a.x * D.x - a.y * D.y, a.x * D.y + a.y * D.x, ea + D.e);
+        return {a.x * qx - a.y * qy, a.x * qy + a.y * qx, 0.0, 0.0, ea, 0};
     }
 
     /* the table build: Mandelbrot's, B never read */
@@ -663,6 +734,16 @@ __device__ __forceinline__ void deep_step_d(const double Zx, const double Zy, co
     const double zx = Zx + dzx, zy = Zy + dzy;
     const double wx = zx + zx, wy = zy + zy;
     D = make_double2((wx * D.x - wy * D.y) + s, wx * D.y + wy * D.x);
+    deep_pin_d(D);
+}
+
+/* ... of a formula without a dc term (fr_render_deep_julia_de): D' = (w.x D.x - w.y D.y, w.x D.y + w.y D.x), nothing added (adding
+ * 0.0 would change the sign of a zero) */
+__device__ __forceinline__ void deep_step_d(const double Zx, const double Zy, const double dzx, const double dzy, double2& D)
+{
+    const double zx = Zx + dzx, zy = Zy + dzy;
+    const double wx = zx + zx, wy = zy + zy;
+    D = make_double2(wx * D.x - wy * D.y, wx * D.y + wy * D.x);
     deep_pin_d(D);
 }
 
@@ -707,6 +788,24 @@ __device__ __forceinline__ void deep_step_pd(const double Zx, const double Zy, c
     const double zx = Zx + dzx, zy = Zy + dzy;
     const double wx = zx + zx, wy = zy + zy;
     deepx_d_set(D, wx * D.x - wy * D.y, wx * D.y + wy * D.x, D.e, sm, es);
+}
+
+/* ... and the two of a formula without a dc term (fr_render_deepx_julia_de): D' = norm(b D, eb + 1 + D.e) and D' = norm(w D, D.e),
+ * each flushed */
+__device__ __forceinline__ void deep_step_xd(const double Zx, const double Zy, const int eZ, const double dzx, const double dzy,
+                                             const int ed, XDeriv& D)
+{
+    const int eb = eZ > ed ? eZ : ed;
+    const double bx = __builtin_ldexp(Zx, eZ - eb) + __builtin_ldexp(dzx, ed - eb);
+    const double by = __builtin_ldexp(Zy, eZ - eb) + __builtin_ldexp(dzy, ed - eb);
+    deepx_d_set(D, bx * D.x - by * D.y, bx * D.y + by * D.x, eb + 1 + D.e);
+}
+
+__device__ __forceinline__ void deep_step_pd(const double Zx, const double Zy, const double dzx, const double dzy, XDeriv& D)
+{
+    const double zx = Zx + dzx, zy = Zy + dzy;
+    const double wx = zx + zx, wy = zy + zy;
+    deepx_d_set(D, wx * D.x - wy * D.y, wx * D.y + wy * D.x, D.e);
 }
 
 /* ---- the tables --------------------------------------------------------------------------------------------------------
@@ -1012,11 +1111,13 @@ __device__ __forceinline__ void deep_orbit(const DeepArgs& A, const JuliaStart J
     esc = max_iter;
     er2 = 0.0;
     double2 D = make_double2(0.0, 0.0);                          /* DE: dz/dc * s, through the escaping update */
+    if constexpr (DE && !F::kHasB) D.x = s;                      /* ... without a dc term dz_n/dz_0 * s: (s, +0.0) at the start */
     for (int i = 0; i < max_iter; ++i) {
         if (__builtin_amdgcn_ballot_w64(live) == 0ull) break;
         if (!live) continue;
         const double2 Znn = orbit[base + (m + 2 <= N ? m + 2 : N)];   /* Z_{m+2}, for the next step (m + 1 < N) */
-        if constexpr (DE) deep_step_d(Zx, Zy, dzx, dzy, s, D);
+        if constexpr (DE && F::kHasB) deep_step_d(Zx, Zy, dzx, dzy, s, D);
+        else if constexpr (DE) deep_step_d(Zx, Zy, dzx, dzy, D);
         const double2 n = deep_step<F>(Zx, Zy, dzx, dzy, dcx, dcy);
         const double nx = n.x, ny = n.y;
         ++m;
@@ -1069,6 +1170,7 @@ __device__ __forceinline__ void deep_orbit_bla(const DeepArgs& A, const BlaTable
     er2 = 0.0;
     nplain = 0u; nbla = 0u;
     double2 D = make_double2(0.0, 0.0);                          /* DE: dz/dc * s, through the escaping update */
+    if constexpr (DE && !F::kHasB) D.x = s;                      /* ... without a dc term dz_n/dz_0 * s: (s, +0.0) at the start */
     for (;;) {
         if (__builtin_amdgcn_ballot_w64(live) == 0ull) break;
         if (!live) continue;
@@ -1088,7 +1190,8 @@ __device__ __forceinline__ void deep_orbit_bla(const DeepArgs& A, const BlaTable
             const double2 Zm = orbit[base + m];
             Zmx = Zm.x; Zmy = Zm.y;
         } else {
-            if constexpr (DE) deep_step_d(Zx, Zy, dzx, dzy, s, D);
+            if constexpr (DE && F::kHasB) deep_step_d(Zx, Zy, dzx, dzy, s, D);
+            else if constexpr (DE) deep_step_d(Zx, Zy, dzx, dzy, D);
             n = deep_step<F>(Zx, Zy, dzx, dzy, dcx, dcy);
             step = 1;
             ++nplain;
@@ -1163,6 +1266,7 @@ __device__ __forceinline__ void deep_orbit_x(const DeepXArgs& AA, const JuliaSta
     esc = max_iter;
     er2 = 0.0;
     XDeriv D = {0.0, 0.0, kXZero};                               /* DE: dz/dc * s, through the escaping update */
+    if constexpr (DE && !F::kHasB) { D.x = sm; D.e = es; }       /* ... without a dc term dz_n/dz_0 * s: (sm, +0.0, es) at first */
     for (int i = 0; i < max_iter; ++i) {
         if (__builtin_amdgcn_ballot_w64(live) == 0ull) break;
         if (!live) continue;
@@ -1174,7 +1278,8 @@ __device__ __forceinline__ void deep_orbit_x(const DeepXArgs& AA, const JuliaSta
             const double2 Znn = mant[mn];
             const int eZnn = exp2[mn];
             int en;
-            if constexpr (DE) deep_step_xd(Zx, Zy, eZ, dzx, dzy, ed, sm, es, D);
+            if constexpr (DE && F::kHasB) deep_step_xd(Zx, Zy, eZ, dzx, dzy, ed, sm, es, D);
+            else if constexpr (DE) deep_step_xd(Zx, Zy, eZ, dzx, dzy, ed, D);
             const double2 n = deep_step_x<F>(Zx, Zy, eZ, dzx, dzy, ed, cx, cy, ec, en);
             const double nx = n.x, ny = n.y;
             ++m;
@@ -1208,7 +1313,8 @@ __device__ __forceinline__ void deep_orbit_x(const DeepXArgs& AA, const JuliaSta
             ext = false;
         } else {
             const double2 Znn = orbit[mn];
-            if constexpr (DE) deep_step_pd(Zx, Zy, dzx, dzy, sm, es, D);
+            if constexpr (DE && F::kHasB) deep_step_pd(Zx, Zy, dzx, dzy, sm, es, D);
+            else if constexpr (DE) deep_step_pd(Zx, Zy, dzx, dzy, D);
             const double2 n = deep_step<F>(Zx, Zy, dzx, dzy, cpx, cpy);
             const double nx = n.x, ny = n.y;
             ++m;
@@ -1300,6 +1406,7 @@ __device__ __forceinline__ void deep_orbit_x_bla(const DeepXArgs& AA, const BlaX
     er2 = 0.0;
     nsingle = 0u; nbla = 0u;
     XDeriv D = {0.0, 0.0, kXZero};                               /* DE: dz/dc * s, through the escaping update */
+    if constexpr (DE && !F::kHasB) { D.x = sm; D.e = es; }       /* ... without a dc term dz_n/dz_0 * s: (sm, +0.0, es) at first */
     for (;;) {
         if (__builtin_amdgcn_ballot_w64(live) == 0ull) break;
         if (!live) continue;
@@ -1335,7 +1442,8 @@ __device__ __forceinline__ void deep_orbit_x_bla(const DeepXArgs& AA, const BlaX
             } else {
                 Znn = mant[mn];
                 eZnn = exp2[mn];
-                if constexpr (DE) deep_step_xd(Zx, Zy, eZ, dzx, dzy, ed, sm, es, D);
+                if constexpr (DE && F::kHasB) deep_step_xd(Zx, Zy, eZ, dzx, dzy, ed, sm, es, D);
+                else if constexpr (DE) deep_step_xd(Zx, Zy, eZ, dzx, dzy, ed, D);
                 const double2 n = deep_step_x<F>(Zx, Zy, eZ, dzx, dzy, ed, cx, cy, ec, en);
                 nx = n.x; ny = n.y;
                 ++m;
@@ -1381,7 +1489,8 @@ __device__ __forceinline__ void deep_orbit_x_bla(const DeepXArgs& AA, const BlaX
             }
         } else {
             const double2 Znn = orbit[mn];
-            if constexpr (DE) deep_step_pd(Zx, Zy, dzx, dzy, sm, es, D);
+            if constexpr (DE && F::kHasB) deep_step_pd(Zx, Zy, dzx, dzy, sm, es, D);
+            else if constexpr (DE) deep_step_pd(Zx, Zy, dzx, dzy, D);
             const double2 n = deep_step<F>(Zx, Zy, dzx, dzy, cpx, cpy);
             const double nx = n.x, ny = n.y;
             ++m;
@@ -1459,6 +1568,21 @@ __host__ __device__ __forceinline__ const DeepXArgs& deepx_args(const DeepJuliaX
 __device__ __forceinline__ double ship_log_bailout(const DeepJuliaBlaArgs& A) { return A.j.log_bailout; }
 __device__ __forceinline__ double ship_log_bailout(const DeepJuliaXBlaArgs& A) { return A.j.log_bailout; }
 
+__host__ __device__ __forceinline__ const DeepArgs& deep_args(const DeepJuliaDeArgs& A) { return A.d; }
+__host__ __device__ __forceinline__ const DeepArgs& deep_args(const DeepJuliaDeBlaArgs& A) { return A.e.d; }
+__host__ __device__ __forceinline__ const DeepArgs& deep_args(const DeepJuliaXDeArgs& A) { return A.x.d; }
+__host__ __device__ __forceinline__ const DeepArgs& deep_args(const DeepJuliaXDeBlaArgs& A) { return A.e.x.d; }
+__host__ __device__ __forceinline__ const DeepXArgs& deepx_args(const DeepJuliaXDeArgs& A) { return A.x; }
+__host__ __device__ __forceinline__ const DeepXArgs& deepx_args(const DeepJuliaXDeBlaArgs& A) { return A.e.x; }
+__host__ __device__ __forceinline__ const DeepJuliaDeArgs& de_args(const DeepJuliaDeArgs& A) { return A; }
+__host__ __device__ __forceinline__ const DeepJuliaDeArgs& de_args(const DeepJuliaDeBlaArgs& A) { return A.e; }
+__host__ __device__ __forceinline__ const DeepJuliaXDeArgs& de_args(const DeepJuliaXDeArgs& A) { return A; }
+__host__ __device__ __forceinline__ const DeepJuliaXDeArgs& de_args(const DeepJuliaXDeBlaArgs& A) { return A.e; }
+__device__ __forceinline__ double ship_log_bailout(const DeepJuliaDeArgs& A) { return A.log_bailout; }
+__device__ __forceinline__ double ship_log_bailout(const DeepJuliaDeBlaArgs& A) { return A.e.log_bailout; }
+__device__ __forceinline__ double ship_log_bailout(const DeepJuliaXDeArgs& A) { return A.log_bailout; }
+__device__ __forceinline__ double ship_log_bailout(const DeepJuliaXDeBlaArgs& A) { return A.e.log_bailout; }
+
 template <class T, class... U>
 constexpr bool is_any_of = (std::is_same<T, U>::value || ...);
 
@@ -1466,8 +1590,9 @@ constexpr bool is_any_of = (std::is_same<T, U>::value || ...);
 template <class ARGS>
 __device__ __forceinline__ JuliaStart julia_start(const ARGS& A)
 {
-    if constexpr (is_any_of<ARGS, DeepJuliaArgs, DeepJuliaXArgs>) return A.j;
+    if constexpr (is_any_of<ARGS, DeepJuliaArgs, DeepJuliaXArgs, DeepJuliaDeArgs, DeepJuliaXDeArgs>) return A.j;
     else if constexpr (is_any_of<ARGS, DeepJuliaBlaArgs, DeepJuliaXBlaArgs>) return A.j.j;
+    else if constexpr (is_any_of<ARGS, DeepJuliaDeBlaArgs, DeepJuliaXDeBlaArgs>) return A.e.j;
     else return JuliaStart{0, 0};
 }
 
@@ -1502,19 +1627,21 @@ __device__ __forceinline__ void deep_de_shade(float rgb[3], const double de, con
 }
 
 /* ARGS names the loop: Deep[Ship|Julia][X][Bla]Args = the formula, extended-exponent deltas, BLA (with the step counts);
- * DeepDe[Bla]Args = Deep[Bla]Args, DeepXDe[Bla]Args = DeepX[Bla]Args with the derivative and its two planes.  The body of the
- * two __global__ templates below: deep_kernel for the fourteen blocks without an extended derivative, deepx_de_kernel for the
- * two with one. */
+ * DeepDe[Bla]Args = Deep[Bla]Args, DeepXDe[Bla]Args = DeepX[Bla]Args, DeepJulia[X]De[Bla]Args = DeepJulia[X][Bla]Args with the
+ * derivative and its two planes.  The body of the three __global__ templates below: deep_kernel for the fourteen blocks without
+ * an extended derivative, deepx_de_kernel for the two Mandelbrot blocks with one, julia_de_kernel for Julia's four. */
 template <class ARGS>
 __device__ __forceinline__ void deep_kernel_body(const ARGS& AA)
 {
     constexpr bool BLA = is_any_of<ARGS, DeepBlaArgs, DeepXBlaArgs, DeepShipBlaArgs, DeepShipXBlaArgs, DeepJuliaBlaArgs,
-                                   DeepJuliaXBlaArgs, DeepDeBlaArgs, DeepXDeBlaArgs>;
-    constexpr bool DE = is_any_of<ARGS, DeepDeArgs, DeepDeBlaArgs, DeepXDeArgs, DeepXDeBlaArgs>;
+                                   DeepJuliaXBlaArgs, DeepDeBlaArgs, DeepXDeBlaArgs, DeepJuliaDeBlaArgs, DeepJuliaXDeBlaArgs>;
+    constexpr bool DE = is_any_of<ARGS, DeepDeArgs, DeepDeBlaArgs, DeepXDeArgs, DeepXDeBlaArgs, DeepJuliaDeArgs, DeepJuliaDeBlaArgs,
+                                  DeepJuliaXDeArgs, DeepJuliaXDeBlaArgs>;
     constexpr bool X = is_any_of<ARGS, DeepXArgs, DeepXBlaArgs, DeepShipXArgs, DeepShipXBlaArgs, DeepJuliaXArgs,
-                                 DeepJuliaXBlaArgs, DeepXDeArgs, DeepXDeBlaArgs>;
+                                 DeepJuliaXBlaArgs, DeepXDeArgs, DeepXDeBlaArgs, DeepJuliaXDeArgs, DeepJuliaXDeBlaArgs>;
     constexpr bool SHIP = is_any_of<ARGS, DeepShipArgs, DeepShipBlaArgs, DeepShipXArgs, DeepShipXBlaArgs>;
-    constexpr bool JULIA = is_any_of<ARGS, DeepJuliaArgs, DeepJuliaXArgs, DeepJuliaBlaArgs, DeepJuliaXBlaArgs>;
+    constexpr bool JULIA = is_any_of<ARGS, DeepJuliaArgs, DeepJuliaXArgs, DeepJuliaBlaArgs, DeepJuliaXBlaArgs, DeepJuliaDeArgs,
+                                     DeepJuliaDeBlaArgs, DeepJuliaXDeArgs, DeepJuliaXDeBlaArgs>;
     using F = std::conditional_t<JULIA, JuliaFormula, std::conditional_t<SHIP, ShipFormula, MandelFormula>>;
     constexpr int FRACTAL = F::kFractal;
     const DeepArgs& A = deep_args(AA);
@@ -1576,13 +1703,14 @@ __device__ __forceinline__ void deep_kernel_body(const ARGS& AA)
                 x_norm(cx, cy, ec);
                 XDeriv Dx;
                 if constexpr (BLA)
-                    deep_orbit_x_bla<F, true>(deepx_args(AA), AA.t, julia_start(AA), levels_p, base_p, cx, cy, ec, inside, esc, r2,
-                                              np, nb, de_s, de_es, &Dx);
+                    deep_orbit_x_bla<F, true>(deepx_args(AA), q_table(AA.t), julia_start(AA), levels_p, base_p, cx, cy, ec, inside,
+                                              esc, r2, np, nb, de_s, de_es, &Dx);
                 else deep_orbit_x<F, true>(deepx_args(AA), julia_start(AA), cx, cy, ec, inside, esc, r2, de_s, de_es, &Dx);
                 D = make_double2(Dx.x, Dx.y); eD = Dx.e;
             } else if constexpr (DE) {
                 if constexpr (BLA)
-                    deep_orbit_bla<F, true>(A, AA.t, julia_start(AA), levels_p, base_p, cx, cy, z1, inside, esc, r2, np, nb, de_s, &D);
+                    deep_orbit_bla<F, true>(A, q_table(AA.t), julia_start(AA), levels_p, base_p, cx, cy, z1, inside, esc, r2, np,
+                                            nb, de_s, &D);
                 else deep_orbit<F, true>(A, julia_start(AA), cx, cy, z1, inside, esc, r2, de_s, &D);
             } else if constexpr (X) {
                 int ec = deepx_args(AA).ze;
@@ -1660,6 +1788,15 @@ deep_kernel(const ARGS AA)
 template <class ARGS>
 __global__ void __launch_bounds__(kBlockThreads)
 deepx_de_kernel(const ARGS AA)
+{
+    deep_kernel_body(AA);
+}
+
+/* fr_render_deep_julia_de's and fr_render_deepx_julia_de's four kernels (DeepJuliaDeArgs, DeepJuliaDeBlaArgs, DeepJuliaXDeArgs,
+ * DeepJuliaXDeBlaArgs) */
+template <class ARGS>
+__global__ void __launch_bounds__(kBlockThreads)
+julia_de_kernel(const ARGS AA)
 {
     deep_kernel_body(AA);
 }

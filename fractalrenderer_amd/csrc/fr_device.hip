@@ -75,7 +75,8 @@ struct BlaSlot {
 
 /* What the context keeps for one deep path, a (storage, formula) pair: its most recent reference orbit(s), their BLA table, and
  * the resident workgroups per CU of the deep_kernel instantiations that read them (0 = not asked yet): [0] the path's own pair,
- * [1] fr_render_deep_de's, which shares the fp64 Mandelbrot slot, and fr_render_deepx_de's, which shares the extended one;
+ * [1] the distance entry point's that shares the slot -- fr_render_deep_de's the fp64 Mandelbrot slot, fr_render_deepx_de's the
+ * extended one, fr_render_deep_julia_de's and fr_render_deepx_julia_de's the two Julia slots;
  * [.][0] the unflagged kernel, [.][1] the flagged one */
 struct DeepSlot {
     DeepOrbit o;
@@ -997,6 +998,9 @@ template <> struct DeepPath<DeepShipArgs> : DeepPathOf<kShip, false, DeepShipBla
     static constexpr const char *name = "deep_kernel<DeepShipArgs>", *bla_name = "deep_kernel<DeepShipBlaArgs>"; };
 template <> struct DeepPath<DeepJuliaArgs> : DeepPathOf<kJulia, false, DeepJuliaBlaArgs, FR_FLAG_DEEP_JULIA_BLA> {
     static constexpr const char *name = "deep_kernel<DeepJuliaArgs>", *bla_name = "deep_kernel<DeepJuliaBlaArgs>"; };
+template <> struct DeepPath<DeepJuliaDeArgs> : DeepPathOf<kJulia, false, DeepJuliaDeBlaArgs, FR_FLAG_DEEP_JULIA_BLA, 1> {
+    static constexpr const char *name = "julia_de_kernel<DeepJuliaDeArgs>", *bla_name = "julia_de_kernel<DeepJuliaDeBlaArgs>";
+    template <class ARGS> static auto kernel() -> void (*)(ARGS) { return julia_de_kernel<ARGS>; } };
 template <> struct DeepPath<DeepXArgs> : DeepPathOf<kMandel, true, DeepXBlaArgs, FR_FLAG_DEEPX_BLA> {
     static constexpr const char *name = "deep_kernel<DeepXArgs>", *bla_name = "deep_kernel<DeepXBlaArgs>"; };
 template <> struct DeepPath<DeepXDeArgs> : DeepPathOf<kMandel, true, DeepXDeBlaArgs, FR_FLAG_DEEPX_BLA, 1> {
@@ -1006,6 +1010,9 @@ template <> struct DeepPath<DeepShipXArgs> : DeepPathOf<kShip, true, DeepShipXBl
     static constexpr const char *name = "deep_kernel<DeepShipXArgs>", *bla_name = "deep_kernel<DeepShipXBlaArgs>"; };
 template <> struct DeepPath<DeepJuliaXArgs> : DeepPathOf<kJulia, true, DeepJuliaXBlaArgs, FR_FLAG_DEEPX_JULIA_BLA> {
     static constexpr const char *name = "deep_kernel<DeepJuliaXArgs>", *bla_name = "deep_kernel<DeepJuliaXBlaArgs>"; };
+template <> struct DeepPath<DeepJuliaXDeArgs> : DeepPathOf<kJulia, true, DeepJuliaXDeBlaArgs, FR_FLAG_DEEPX_JULIA_BLA, 1> {
+    static constexpr const char *name = "julia_de_kernel<DeepJuliaXDeArgs>", *bla_name = "julia_de_kernel<DeepJuliaXDeBlaArgs>";
+    template <class ARGS> static auto kernel() -> void (*)(ARGS) { return julia_de_kernel<ARGS>; } };
 
 /* One pass of a deep view, `base` being the argument block of its unflagged kernel: the path's kernel of BASE at the occupancy
  * cached in its slot, or with `bla` the table, then the path's flagged kernel on the same queue plan at its own occupancy, its
@@ -1518,8 +1525,9 @@ static int enqueue_ssaa_staged(fr_ctx* c, const fr_params* p, uint32_t W, uint32
 }
 
 /* ---- render entry points --------------------------------------------------------------------------------------------
- * fr_render_shard, fr_render_phoenix, fr_render_mandelbulb and the eight deep entry points (fr_render_deep, _deep_de,
- * _deep_ship, _deepx, _deepx_de, _deepx_ship, _deep_julia, _deepx_julia; all through deep_entry), each with its _async form:
+ * fr_render_shard, fr_render_phoenix, fr_render_mandelbulb and the ten deep entry points (fr_render_deep, _deep_de,
+ * _deep_ship, _deepx, _deepx_de, _deepx_ship, _deep_julia, _deepx_julia, _deep_julia_de, _deepx_julia_de; all through
+ * deep_entry), each with its _async form:
  * their parameter checks, then render_sync / render_async with the planes beyond fr_output's three (ExtraPlanes;
  * fr_render_deep_de and fr_render_deepx_de alone have any) and the enqueue step as enqueue(shard, rgba, nu, iter, extra planes,
  * stream, out_frame) */
@@ -1901,10 +1909,10 @@ extern "C" int fr_render_mandelbulb(fr_ctx* c, const fr_params* p, const fr_mand
         return enqueue_mandelbulb(c, p, mb, W, H, sh, rgba, nu, iter, s, out_frame); });
 }
 
-/* The sixteen deep entry points: BASE names the path (DeepPath), async_entry the _async form (nullptr: the synchronous one),
+/* The twenty deep entry points: BASE names the path (DeepPath), async_entry the _async form (nullptr: the synchronous one),
  * validate() runs the path's validator once the pointers are known not to be NULL, and the enqueue step is enqueue_deep_view of
- * the view read into a DeepAt.  e: the block of fr_render_deep_de and fr_render_deepx_de, whose two planes travel as extra
- * planes into the derivative's fields; nullptr for every other path. */
+ * the view read into a DeepAt.  e: the block of the four distance entry points (fr_render_deep_de, _deepx_de, _deep_julia_de,
+ * _deepx_julia_de), whose two planes travel as extra planes into the derivative's fields; nullptr for every other path. */
 template <class BASE, class VIEW, class Validate>
 static int deep_entry(const char* async_entry, fr_ctx* c, const fr_params* p, const VIEW* v, const fr_deep_de* e, uint32_t W,
                       uint32_t H, const fr_shard* shard, const fr_output* out, void* hip_stream, Validate&& validate)
@@ -1918,8 +1926,11 @@ static int deep_entry(const char* async_entry, fr_ctx* c, const fr_params* p, co
     ExtraPlanes extra;
     if constexpr (de)
         extra = {2, {{e->deriv, 16}, {e->de, 8}},
-                 DeepPath<BASE>::ext ? "fr_render_deepx_de: neither fr_output nor fr_deep_de has a plane to write"
-                                     : "fr_render_deep_de: neither fr_output nor fr_deep_de has a plane to write"};
+                 DeepPath<BASE>::f == kJulia
+                     ? (DeepPath<BASE>::ext ? "fr_render_deepx_julia_de: neither fr_output nor fr_deep_de has a plane to write"
+                                            : "fr_render_deep_julia_de: neither fr_output nor fr_deep_de has a plane to write")
+                     : (DeepPath<BASE>::ext ? "fr_render_deepx_de: neither fr_output nor fr_deep_de has a plane to write"
+                                            : "fr_render_deep_de: neither fr_output nor fr_deep_de has a plane to write")};
     auto enqueue = [&](auto sh, auto rgba, auto nu, auto iter, void* const* xp, auto s, bool out_frame) {
         DeepAt at = {v->center_x, v->center_y, nullptr, p->zoom, 0, v->frac_bits};
         if constexpr (DeepPath<BASE>::ext) {     /* the zoom is the view's string: resolved here, with the automatic F */
@@ -2059,6 +2070,37 @@ extern "C" int fr_render_deepx_julia(fr_ctx* c, const fr_params* p, const fr_dee
 {
     return deep_entry<DeepJuliaXArgs>(nullptr, c, p, v, nullptr, W, H, shard, out, nullptr,
                                       [&] { return fr_deepx_julia_validate(p, v, W, H); });
+}
+
+/* fr_render_deep_julia_de, fr_render_deepx_julia_de: fr_render_deep_de's five planes on the two Julia paths, whose slots (orbits,
+ * tables, step counts) they share with the plain entry points */
+extern "C" int fr_render_deep_julia_de_async(fr_ctx* c, const fr_params* p, const fr_deep_view* v, const fr_deep_de* e, uint32_t W,
+                                             uint32_t H, const fr_shard* shard, const fr_output* out, void* hip_stream)
+{
+    return deep_entry<DeepJuliaDeArgs>("fr_render_deep_julia_de_async", c, p, v, e, W, H, shard, out, hip_stream,
+                                       [&] { return fr_deep_julia_de_validate(p, v, e, W, H); });
+}
+
+extern "C" int fr_render_deep_julia_de(fr_ctx* c, const fr_params* p, const fr_deep_view* v, const fr_deep_de* e, uint32_t W,
+                                       uint32_t H, const fr_shard* shard, const fr_output* out)
+{
+    return deep_entry<DeepJuliaDeArgs>(nullptr, c, p, v, e, W, H, shard, out, nullptr,
+                                       [&] { return fr_deep_julia_de_validate(p, v, e, W, H); });
+}
+
+extern "C" int fr_render_deepx_julia_de_async(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, const fr_deep_de* e,
+                                              uint32_t W, uint32_t H, const fr_shard* shard, const fr_output* out,
+                                              void* hip_stream)
+{
+    return deep_entry<DeepJuliaXDeArgs>("fr_render_deepx_julia_de_async", c, p, v, e, W, H, shard, out, hip_stream,
+                                        [&] { return fr_deepx_julia_de_validate(p, v, e, W, H); });
+}
+
+extern "C" int fr_render_deepx_julia_de(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, const fr_deep_de* e, uint32_t W,
+                                        uint32_t H, const fr_shard* shard, const fr_output* out)
+{
+    return deep_entry<DeepJuliaXDeArgs>(nullptr, c, p, v, e, W, H, shard, out, nullptr,
+                                        [&] { return fr_deepx_julia_de_validate(p, v, e, W, H); });
 }
 
 /* ---- 8-bit export ------------------------------------------------------------------------------ */

@@ -551,8 +551,8 @@ int fr_ctx_last_deep_steps(fr_ctx* ctx, uint64_t out[3]);
  * <= 0 is FR_ERR_INVALID_ARG.
  * Cost: four live VGPRs and 11 fp64 operations per plain update on top of the step's 18 (README: measured).
  * Extended views below 1e-290, where s underflows and D needs an exponent of its own, are fr_render_deepx_de (below,
- * FR_HAS_DEEPX_DE).  Out of scope: the Burning Ship, which
- * needs a real 2x2 Jacobian; Julia sets; fr_deep_sequence; fr_node and .franim; slope or normal lighting -- deriv is what a
+ * FR_HAS_DEEPX_DE); Julia sets are fr_render_deep_julia_de (FR_HAS_DEEP_JULIA_DE).  Out of scope: the Burning Ship, which
+ * needs a real 2x2 Jacobian; fr_deep_sequence; fr_node and .franim; slope or normal lighting -- deriv is what a
  * caller needs for it. */
 #define FR_HAS_DEEP_DE 1
 
@@ -867,7 +867,8 @@ int fr_ctx_last_deepx_steps(fr_ctx* ctx, uint64_t out[3]);
  * arguments in VGPR lanes: 84 and 87 of them (76 and 78 in fr_render_deepx's kernels; the distance block adds nine scalars),
  * written once in the prologue and read back per sample around the orbit loop, never inside it (checked on the ISA by
  * tests/test_deepx_de_host.py).
- * Out of scope: the Burning Ship, Julia sets, fr_deep_sequence, fr_node and .franim, slope or normal lighting. */
+ * Julia sets are fr_render_deepx_julia_de (below, FR_HAS_DEEPX_JULIA_DE).
+ * Out of scope: the Burning Ship, fr_deep_sequence, fr_node and .franim, slope or normal lighting. */
 #define FR_HAS_DEEPX_DE 1
 
 /* What fr_render_deepx_de checks of its arguments, the view's strings parsed included (no context needed). */
@@ -1243,6 +1244,99 @@ int fr_ctx_last_deepx_julia_steps(fr_ctx* ctx, uint64_t out[3]);
  * int32.  NULL skips a part.  Returns the number of entries the context holds (0: no table, or the orbits have changed since). */
 int64_t fr_deep_julia_bla_table(fr_ctx* ctx, double* r, double* a, int64_t n);
 int64_t fr_deepx_julia_bla_table(fr_ctx* ctx, void* r, double* a, int32_t* a_exp, int64_t n);
+
+/* ---- distance estimates for deep Julia views ------------------------------------------------------------------------------------
+ * fr_render_deep_de and fr_render_deepx_de (above) for the views of fr_render_deep_julia and fr_render_deepx_julia: the same two
+ * planes more, the exterior distance estimate of sample (0,0) in pixel spacings and the scaled derivative.  Dust and dendrite Julia
+ * sets have no interior; at depth their filaments are far thinner than a pixel (48x36 frames of the tests: 63 % of the escaped
+ * pixels of DUST30 and 49 % of RABBIT30 lie less than one pixel spacing from the set) and the smooth count of a frame is noise.
+ * The distance block is fr_deep_de with fr_deep_de_default, unchanged.  Range, view, c, orbits (P and Q), tables, rebasing and
+ * flags are exactly the plain Julia entry points': FR_FLAG_DEEP_JULIA_BLA is read by fr_render_deep_julia_de,
+ * FR_FLAG_DEEPX_JULIA_BLA by fr_render_deepx_julia_de.  Every other entry point is untouched.
+ *
+ * D is dz_n/dz_0 * s: the derivative of the sample's point with respect to ITS OWN starting point (Julia's parameter is the
+ * start, c is fixed), times one pixel spacing s, so that |D| at escape is about 1 / de with de in pixel spacings.  The map is
+ * analytic and has no dc term: an update is one complex product, D' = 2 z D, and nothing is ever added.  Every operation is one
+ * fp64 rounding or an exact scaling, no contraction.
+ *
+ * fp64 (fr_render_deep_julia_de), next to fr_render_deep_julia's step:
+ *   - s = zoom / H, H the height of the WHOLE frame.  D = (s, +0.0) at the start (fr_render_deep_de starts at (0, 0): there the
+ *     parameter is c, here it is z_0, and dz_0/dz_0 = 1).
+ *   - Plain step, formed in every trip from the point before the update on the sample's CURRENT orbit (P at first):
+ *       z = Z_m + dz;   w = z + z;   D' = (w.x D.x - w.y D.y,  w.x D.y + w.y D.x)
+ *     -- nothing is added: adding 0.0 would change the sign of a zero.
+ *   - BLA step with the entry A the sample takes: D' = (A.x D.x - A.y D.y,  A.x D.y + A.y D.x).
+ *   - A rebase, the move from P to Q included, leaves D alone: the point does not move.
+ *   - Escape with r2: fr_render_deep_de's, zl = sqrt(r2); dl = sqrt(D.x D.x + D.y D.y); de = (zl * log(zl)) / dl; a NaN de becomes
+ *     0; an overflowing |D| gives 0 by the division; a ZERO D gives +inf (see the underflow note).
+ *   - Interior samples (iter == max_iterations): de = 0, deriv = (0, 0).
+ *
+ * Extended (fr_render_deepx_julia_de): D is fr_render_deepx_de's extended complex number (D.x, D.y, D.e), normalised after every
+ * update whatever mode the sample's delta is in; notation as there.
+ *   - s = (sm, es) = norm1(zm / (double)H, ze).  D = (sm, +0.0, es) at the start.
+ *   - EXTENDED single step:  eb = max(Z_m.e, dz.e);   b = ldexp(Z_m, Z_m.e - eb) + ldexp(dz, dz.e - eb), per component;
+ *       P = (b.x D.x - b.y D.y,  b.x D.y + b.y D.x) at eP = eb + 1 + D.e;   D' = norm(P.x, P.y, eP)
+ *   - PLAIN single step:  w = (Z_m + dz) + (Z_m + dz) on the plain doubles;   P = w (x) D at eP = D.e;   D' = norm(P)
+ *   - BLA step with the entry A:  P = A (x) D at eP = A.e + D.e;   D' = norm(P)
+ *   - FLUSH of D: after every norm a D with e < -2^27 becomes the zero (0, 0, FR_DEEPX_ZERO_EXP) and stays zero (a product with
+ *     the zero is the zero).  In a superattracting basin (c = 0, c = -1) |2 z| squares itself towards nothing and an int32
+ *     exponent would wrap after about 30 updates.  The other way: |D| <= s (2 bailout + 1)^n with bailout <= 2^16, so D.e stays
+ *     below 18 * 2^24 < 2^29 for every max_iterations the validator accepts.  With both bounds every exponent sum of a step stays
+ *     inside (-2^29, 2^29).
+ *   - A change of mode and a rebase leave D alone.
+ *   - Escape: fr_render_deepx_de's -- de = ldexp(q, -D.e), q = (zl * log(zl)) / dl formed from the mantissas (a NaN quotient
+ *     becoming 0 first);  deriv = (ldexp(D.x, D.e), ldexp(D.y, D.e)), which saturates outside a double's range.  A zero D
+ *     gives de = +inf and deriv = (0, 0).
+ *   - Interior samples: de = 0, deriv = (0, 0).
+ *
+ * D never feeds back: iter, nu, rgba without shading and the three step counts (fr_ctx_last_deep_julia_steps,
+ * fr_ctx_last_deepx_julia_steps, which report these calls too) are the plain Julia entry point's, byte for byte.
+ * Scaling by a power of two is exact, so on a view both entry points accept whose d0 is at least 2^-400, de and deriv of the two
+ * unflagged entry points are bit-identical while no intermediate leaves a double's range.
+ *
+ * Underflow, documented and not worked around: the fp64 D starts near zoom / H and can leave a double's range only downwards,
+ * where an orbit passes close to 0 at great depth (a centre on a depth-12 preimage of 0 at 1e-290: D is exactly 0 on every
+ * pixel of a 48x36 frame, and de = +inf).  The fp64 deltas of fr_render_deep_julia underflow on the same view and every iter
+ * already differs from the exact one: the limit of the fp64 derivative is the limit the fp64 path already has.  Such views
+ * belong to fr_render_deepx_julia_de.
+ *
+ * Accuracy: below de of about 1e-3 pixel spacings the relative error of any fp64 iteration grows like 2^-53 / de -- the orbit
+ * hugs the set for many updates after its delta has reached the size of z.  Above it the tests bound the error against the
+ * derivative iterated directly at F + 64 bits (README: measured).
+ *
+ * Shading (shade == 1): fr_render_deep_de's, on every escaped sub-sample before the aa average and the post chain.
+ * Planes: de->de and de->deriv follow out->memory and out->layout as out->nu does; of the five planes rgba, nu, iter, de, deriv at
+ * least one must be given.  Shards and FR_LAYOUT_FRAME as fr_render_deep_de.
+ * Shared state: the orbit slots, the tables with their keys and the step counts are the plain Julia paths' own -- a call here
+ * after fr_render_deep_julia / fr_render_deepx_julia of the same view computes no orbit and builds no table, and the reverse.
+ * Validation: everything fr_deep_julia_validate / fr_deepx_julia_validate checks; then `de` NULL, shade outside {0, 1}, or
+ * shade == 1 with edge_px not finite or <= 0 is FR_ERR_INVALID_ARG.
+ * Cost: four live VGPRs (five extended) and per plain update 10 fp64 operations on top of the step's 16.  The four kernels use
+ * no scratch and spill no VGPR; the fp64 pair keeps the occupancy of the kernels it extends (5 and 4 waves per SIMD), the
+ * extended pair runs a wave per SIMD below them (4 and 3).  Measured on one MI355X at 4096^2 (profiles/deep_julia_de_time.txt,
+ * interleaved with the plain entry points in one session, device time), without / with the BLA flag: 1.26 / 1.14 of
+ * fr_render_deep_julia on RABBIT30 and on DENDRITE100, 1.33 / 1.38 of fr_render_deepx_julia on the dendrite at 1e-400; in the
+ * same session fr_render_deep_de costs 1.30 / 1.18 of fr_render_deep and fr_render_deepx_de 1.36 / 1.39 of fr_render_deepx.
+ * Out of scope: the Burning Ship (a real 2x2 Jacobian and a choice of norm), sequences, fr_node and .franim, c as a decimal
+ * string, slope or normal lighting -- deriv is what a caller needs for it. */
+#define FR_HAS_DEEP_JULIA_DE 1
+#define FR_HAS_DEEPX_JULIA_DE 1
+
+/* What the two entry points check of their arguments, the view's strings parsed included (no context needed). */
+int fr_deep_julia_de_validate(const fr_params* p, const fr_deep_view* view, const fr_deep_de* de, uint32_t width, uint32_t height);
+int fr_deepx_julia_de_validate(const fr_params* p, const fr_deepx_view* view, const fr_deep_de* de, uint32_t width,
+                               uint32_t height);
+
+/* fr_render_deep_julia / fr_render_deepx_julia with the distance planes; options, timing and the orbit cache as there.  The
+ * asynchronous forms: fr_render_deep_julia_async's contract, de->de and de->deriv device planes like the others. */
+int fr_render_deep_julia_de(fr_ctx* ctx, const fr_params* p, const fr_deep_view* view, const fr_deep_de* de, uint32_t width,
+                            uint32_t height, const fr_shard* shard, const fr_output* out);
+int fr_render_deep_julia_de_async(fr_ctx* ctx, const fr_params* p, const fr_deep_view* view, const fr_deep_de* de, uint32_t width,
+                                  uint32_t height, const fr_shard* shard, const fr_output* out, void* hip_stream);
+int fr_render_deepx_julia_de(fr_ctx* ctx, const fr_params* p, const fr_deepx_view* view, const fr_deep_de* de, uint32_t width,
+                             uint32_t height, const fr_shard* shard, const fr_output* out);
+int fr_render_deepx_julia_de_async(fr_ctx* ctx, const fr_params* p, const fr_deepx_view* view, const fr_deep_de* de, uint32_t width,
+                                   uint32_t height, const fr_shard* shard, const fr_output* out, void* hip_stream);
 
 /* ---- frames over the GPUs of a node (BASELINE.json north_star: "tiled across the 8 GPUs of one node as disjoint row
  * bands with a final RCCL gather over xGMI") -----------------------------------------------------------------------------

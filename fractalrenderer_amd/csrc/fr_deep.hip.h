@@ -46,27 +46,24 @@
  *     offset bla_offset(N - 1, k)), the radius r of every entry in an array of its own -- a double, or an XRad -- and
  *     (A, B) as F::kAbPerEntry double2 per entry (2: complex A, B; 4: the rows of the ship's real matrices; 1: Julia's A), the
  *     extended tables with their two exponents in an int2 (Julia: A's in an int32).
- *   - deep_kernel<ARGS>, one kernel body (deep_kernel_body) for the sixteen argument blocks: a persistent grid of the resident
- *     set pulls runs of 8x8 sub-tiles from the sharded WaveQueue with unlimited stealing (deep views have very uneven
- *     iteration counts); one lane per sample, the aa x aa samples of a pixel one after the other in the lane; dc through the
- *     formula's viewport map, one dispatch on (extended, BLA) to the loop, then the colour stage of the formula's fp64 path:
- *     shade() and post_chain() of fr_kernels.hip.h on (i, r2).
- *   - the distance estimate (fr_render_deep_de; DeepDeArgs, DeepDeBlaArgs): a compile-time option DE of deep_orbit and
- *     deep_orbit_bla for the Mandelbrot formula carries D = dz/dc * s, s = zoom / H one pixel spacing, next to the delta --
- *     D' = 2 z D + s in a plain step, D' = A D + B s in a BLA step, nothing in a rebase -- and feeds nothing back: (i, r2) and
- *     the step counts are those of the loops without it.  Four live VGPRs and, per plain update, 11 fp64 operations.  The
- *     kernel turns (r2, D) of an escaped sample into |z| log|z| / |D| and, on request, the debug shader's distance shading.
- *   - the same below 1e-290 (fr_render_deepx_de; DeepXDeArgs, DeepXDeBlaArgs): the option DE of deep_orbit_x and
- *     deep_orbit_x_bla for the Mandelbrot formula, with D an extended complex number (XDeriv: two mantissas, one int32 exponent)
- *     whatever mode the lane's delta is in, normalised after every update; s = (sm, es) stays in SGPRs.  Five live VGPRs.  Its
- *     two kernels are deepx_de_kernel<ARGS>, a second __global__ template around the one body (deep_kernel_body), so that the
- *     set of deep_kernel instantiations stays what it was.
- *   - the distance estimate of Julia views (fr_render_deep_julia_de, fr_render_deepx_julia_de; DeepJuliaDeArgs, DeepJuliaDeBlaArgs,
- *     DeepJuliaXDeArgs, DeepJuliaXDeBlaArgs): the option DE of all four loops for a formula without a dc term (kHasB == false).
- *     D = dz_n/dz_0 * s starts at s, not at 0; an update is one complex product, D' = 2 z D or D' = A D, and nothing is added (the
- *     overloads of deep_step_d, deep_step_xd, deep_step_pd and deepx_d_set without s); the extended D is flushed to the zero below
- *     2^-2^27 as the delta is.  Four and five live VGPRs.  Their kernels are julia_de_kernel<ARGS>, a third __global__ template
- *     around the one body.
+ *   - deep_kernel<ARGS>, ARGS = DeepBlock<F, X, DE, BLA>: one argument-block template over the four switches -- DeepArgs and
+ *     the parts they turn on -- and one kernel for its twenty instantiations, which reads the switches from the block.  A
+ *     persistent grid of the resident set pulls runs of 8x8 sub-tiles from the sharded WaveQueue with unlimited stealing (deep
+ *     views have very uneven iteration counts); one lane per sample, the aa x aa samples of a pixel one after the other in the
+ *     lane; dc through the formula's viewport map, one dispatch on (X, DE, BLA) to the loop, then the colour stage of the
+ *     formula's fp64 path: shade() and post_chain() of fr_kernels.hip.h on (i, r2).
+ *   - the distance estimate (fr_render_deep_de): a compile-time option DE of deep_orbit and deep_orbit_bla carries
+ *     D = dz/dc * s, s = zoom / H one pixel spacing, next to the delta -- D' = 2 z D + s in a plain step, D' = A D + B s in a
+ *     BLA step, nothing in a rebase -- and feeds nothing back: (i, r2) and the step counts are those of the loops without it.
+ *     Four live VGPRs and, per plain update, 11 fp64 operations.  The kernel turns (r2, D) of an escaped sample into
+ *     |z| log|z| / |D| and, on request, the debug shader's distance shading.
+ *   - the same below 1e-290 (fr_render_deepx_de): the option DE of deep_orbit_x and deep_orbit_x_bla, with D an extended
+ *     complex number (XDeriv: two mantissas, one int32 exponent) whatever mode the lane's delta is in, normalised after every
+ *     update; s = (sm, es) stays in SGPRs.  Five live VGPRs.
+ *   - the distance estimate of Julia views (fr_render_deep_julia_de, fr_render_deepx_julia_de): the option DE for a formula
+ *     without a dc term (kHasB == false).  D = dz_n/dz_0 * s starts at s, not at 0; an update is one complex product,
+ *     D' = 2 z D or D' = A D, and nothing is added (the overloads of deep_step_d, deep_step_xd, deep_step_pd and deepx_d_set
+ *     without s); the extended D is flushed to the zero below 2^-2^27 as the delta is.  Four and five live VGPRs.
  */
 #pragma once
 #include "fr_kernels.hip.h"
@@ -119,101 +116,14 @@ struct BlaXTable {
     unsigned long long* steps;           /* single steps, BLA steps, updates skipped: one atomic add each per wave */
 };
 
-struct DeepBlaArgs {
-    DeepArgs d;
-    BlaTable t;
-};
-
-/* fr_render_deep_de: fr_render_deep with the scaled derivative D = dz/dc * s carried next to the delta */
-struct DeepDeArgs {
-    DeepArgs d;
-    double s;                            /* zoom / H of the whole frame: one pixel spacing */
-    double* de;                          /* distance estimate of sample (0,0), in pixel spacings */
-    double* deriv;                       /* (D.x, D.y) of sample (0,0) at its escaping update: two doubles per pixel, a caller's
-                                          * plane with no more than a double's alignment */
-    int32_t shade;                       /* 1: the debug shader's distance shading on every escaped sub-sample */
-    float edge_px;                       /* ... its smoothstep's upper edge, in pixel spacings */
-};
-
-struct DeepDeBlaArgs {
-    DeepDeArgs e;
-    BlaTable t;
-};
-
-/* fr_render_deep_ship: d.orbit holds the Burning Ship orbit of the centre */
-struct DeepShipArgs {
-    DeepArgs d;
-    double log_bailout;                  /* log(bailout), for shade<double, 2> at bailout <= 1 (LaunchArgs::log_bailout) */
-};
-
-struct DeepShipBlaArgs {
-    DeepShipArgs s;
-    BlaTable t;
-};
-
-/* fr_render_deepx: d.orbit holds the plain doubles P_n, d.zoom is not read */
-struct DeepXArgs {
-    DeepArgs d;
-    const double2* mant;                 /* (mx, my) of Z_0 .. Z_N */
-    const int32_t* exp2;                 /* e of Z_0 .. Z_N */
-    double zm;                           /* zoom = zm 2^ze */
-    int32_t ze;
-};
-
-struct DeepXBlaArgs {
-    DeepXArgs x;
-    BlaXTable t;
-};
-
-/* fr_render_deepx_de: fr_render_deepx with the scaled derivative carried as an extended complex number (D.x, D.y, D.e) */
-struct DeepXDeArgs {
-    DeepXArgs x;
-    double sm;                           /* one pixel spacing zoom / H of the whole frame = sm 2^es, sm in [0.5, 1) */
-    int32_t es;
-    double* de;                          /* as DeepDeArgs */
-    double* deriv;
-    int32_t shade;
-    float edge_px;
-};
-
-struct DeepXDeBlaArgs {
-    DeepXDeArgs e;
-    BlaXTable t;
-};
-
-/* fr_render_deepx_ship: x.d.orbit holds the plain doubles P_n of the ship's orbit, x.mant / x.exp2 its extended storage */
-struct DeepShipXArgs {
-    DeepXArgs x;
-    double log_bailout;                  /* as DeepShipArgs */
-};
-
-struct DeepShipXBlaArgs {
-    DeepShipXArgs s;
-    BlaXTable t;
-};
-
-/* A Julia view's second orbit: d.orbit / d.n_ref (and x.mant, x.exp2) are Q, the critical orbit a rebase lands on, so
+/* A Julia view's second orbit: orbit / n_ref (and mant, exp2) are Q, the critical orbit a rebase lands on, so
  * z1 = Q_1; P, the orbit of the centre every sample starts on, sits p_off points behind Q in the same buffers */
 struct JuliaStart {
     int32_t p_off;
     int32_t n_p;                         /* N_P >= 1 */
 };
 
-/* fr_render_deep_julia */
-struct DeepJuliaArgs {
-    DeepArgs d;
-    double log_bailout;                  /* as DeepShipArgs */
-    JuliaStart j;
-};
-
-/* fr_render_deepx_julia */
-struct DeepJuliaXArgs {
-    DeepXArgs x;
-    double log_bailout;
-    JuliaStart j;
-};
-
-/* A Julia view's tables (FR_FLAG_DEEP_JULIA_BLA, FR_FLAG_DEEPX_JULIA_BLA): q is the table of Q = d.orbit; P's entries start
+/* A Julia view's tables (FR_FLAG_DEEP_JULIA_BLA, FR_FLAG_DEEPX_JULIA_BLA): q is the table of Q = orbit; P's entries start
  * base_p entries behind Q's in the same arrays */
 template <class TAB>
 struct JuliaTab {
@@ -222,52 +132,68 @@ struct JuliaTab {
     uint32_t base_p;                     /* the entries of Q's table */
 };
 
-struct DeepJuliaBlaArgs {
-    DeepJuliaArgs j;
-    JuliaTab<BlaTable> t;
+/* ---- the argument blocks -----------------------------------------------------------------------------------------------
+ * DeepBlock<F, X, DE, BLA> is the argument block of deep_kernel for the formula policy F (below), extended-exponent deltas X,
+ * the distance estimate DE and a BLA table: DeepArgs, then the parts its switches turn on, in this order.  A part that is off
+ * is an empty base and takes no room. */
+struct MandelFormula;
+struct ShipFormula;
+struct JuliaFormula;
+template <int> struct NoPart {};
+
+/* X: the orbit's extended storage; DeepArgs::orbit holds the plain doubles P_n and DeepArgs::zoom is not read */
+struct DeepXOrbit {
+    const double2* mant;                 /* (mx, my) of Z_0 .. Z_N */
+    const int32_t* exp2;                 /* e of Z_0 .. Z_N */
+    double zm;                           /* zoom = zm 2^ze */
+    int32_t ze;
 };
 
-struct DeepJuliaXBlaArgs {
-    DeepJuliaXArgs j;
-    JuliaTab<BlaXTable> t;
+/* what the formula adds: nothing for Mandelbrot */
+template <class F> struct DeepFormulaPart {};
+template <> struct DeepFormulaPart<ShipFormula> {
+    double log_bailout;                  /* log(bailout), for shade<double, 2> at bailout <= 1 (LaunchArgs::log_bailout) */
 };
-
-/* fr_render_deep_julia_de: DeepJuliaArgs with the scaled derivative D = dz_n/dz_0 * s carried next to the delta; the distance
- * fields are DeepDeArgs's */
-struct DeepJuliaDeArgs {
-    DeepArgs d;
+template <> struct DeepFormulaPart<JuliaFormula> {
     double log_bailout;
     JuliaStart j;
-    double s;
-    double* de;
-    double* deriv;
-    int32_t shade;
-    float edge_px;
 };
 
-struct DeepJuliaDeBlaArgs {
-    DeepJuliaDeArgs e;
-    JuliaTab<BlaTable> t;
+/* DE: the scaled derivative D = dz/dc * s (Julia: dz_n/dz_0 * s) carried next to the delta, s = zoom / H of the whole frame, one
+ * pixel spacing: a double, or with X an extended real s = sm 2^es, sm in [0.5, 1), as D is an extended complex number there */
+struct DeepSpacing { double s; };
+struct DeepXSpacing { double sm; int32_t es; };
+template <bool X>
+struct DeepDePart : std::conditional_t<X, DeepXSpacing, DeepSpacing> {
+    double* de;                          /* distance estimate of sample (0,0), in pixel spacings */
+    double* deriv;                       /* (D.x, D.y) of sample (0,0) at its escaping update: two doubles per pixel, a caller's
+                                          * plane with no more than a double's alignment */
+    int32_t shade;                       /* 1: the debug shader's distance shading on every escaped sub-sample */
+    float edge_px;                       /* ... its smoothstep's upper edge, in pixel spacings */
 };
 
-/* fr_render_deepx_julia_de: DeepJuliaXArgs with the derivative as an extended complex number; the distance fields are
- * DeepXDeArgs's */
-struct DeepJuliaXDeArgs {
-    DeepXArgs x;
-    double log_bailout;
-    JuliaStart j;
-    double sm;
-    int32_t es;
-    double* de;
-    double* deriv;
-    int32_t shade;
-    float edge_px;
+template <class F, bool X, bool DE, bool BLA = false>
+struct DeepBlock : DeepArgs, std::conditional_t<X, DeepXOrbit, NoPart<0>>, DeepFormulaPart<F>,
+                   std::conditional_t<DE, DeepDePart<X>, NoPart<1>> {
+    using Formula = F;
+    static constexpr bool kX = X, kDe = DE, kBla = false;
 };
 
-struct DeepJuliaXDeBlaArgs {
-    DeepJuliaXDeArgs e;
-    JuliaTab<BlaXTable> t;
+/* BLA: the block without it, then the table of its storage -- the two tables of a formula with two orbits */
+template <class F, bool X, bool DE>
+struct DeepBlock<F, X, DE, true> : DeepBlock<F, X, DE> {
+    static constexpr bool kBla = true;
+    using Table = std::conditional_t<X, BlaXTable, BlaTable>;
+    std::conditional_t<F::kTwoOrbits, JuliaTab<Table>, Table> t;
 };
+
+/* a block's table: Q's where there are two */
+template <class B>
+__host__ __device__ __forceinline__ auto& bla_table(B& b)
+{
+    if constexpr (B::Formula::kTwoOrbits) return b.t.q;
+    else return b.t;
+}
 
 constexpr int kXZero = FR_DEEPX_ZERO_EXP;
 constexpr int kXThr = -400;              /* extended while the normalised dz.e <= kXThr */
@@ -1228,14 +1154,13 @@ __device__ __forceinline__ void deep_orbit_bla(const DeepArgs& A, const BlaTable
 /* deep_orbit in two modes (the header's EXTENDED and PLAIN steps).  (cx, cy, ec) = dc, normalised.  z = Z_{m+1} (+) n with the
  * signed orbit point; escape, rebase, norm and the mode rule are the same for either formula. */
 template <class F, bool DE = false>
-__device__ __forceinline__ void deep_orbit_x(const DeepXArgs& AA, const JuliaStart J, const double cx, const double cy,
-                                             const int ec, bool live, int& esc, double& er2, const double sm = 0.0,
-                                             const int es = 0, XDeriv* const Dout = nullptr)
+__device__ __forceinline__ void deep_orbit_x(const DeepArgs& A, const DeepXOrbit& AX, const JuliaStart J, const double cx,
+                                             const double cy, const int ec, bool live, int& esc, double& er2,
+                                             const double sm = 0.0, const int es = 0, XDeriv* const Dout = nullptr)
 {
-    const DeepArgs& A = AA.d;
     const double2* __restrict__ orbit = A.orbit;
-    const double2* __restrict__ mant = AA.mant;
-    const int32_t* __restrict__ exp2 = AA.exp2;
+    const double2* __restrict__ mant = AX.mant;
+    const int32_t* __restrict__ exp2 = AX.exp2;
     const int max_iter = A.max_iter;
     int N = A.n_ref;                                             /* of the lane's orbit, which starts at `base` in the arrays */
     int base = 0;
@@ -1362,15 +1287,15 @@ __device__ __forceinline__ void deep_orbit_x(const DeepXArgs& AA, const JuliaSta
  * single-step lanes of a wave take their steps in the same trip.  nsingle / nbla: the steps this sample took.  Two orbits: as
  * deep_orbit_bla, and a BLA step ends with the flush of deep_orbit_x. */
 template <class F, bool DE = false>
-__device__ __forceinline__ void deep_orbit_x_bla(const DeepXArgs& AA, const BlaXTable& T, const JuliaStart J, const int levels_p,
-                                                 const uint32_t base_p, const double cx, const double cy, const int ec,
-                                                 bool live, int& esc, double& er2, uint32_t& nsingle, uint32_t& nbla,
-                                                 const double sm = 0.0, const int es = 0, XDeriv* const Dout = nullptr)
+__device__ __forceinline__ void deep_orbit_x_bla(const DeepArgs& A, const DeepXOrbit& AX, const BlaXTable& T, const JuliaStart J,
+                                                 const int levels_p, const uint32_t base_p, const double cx, const double cy,
+                                                 const int ec, bool live, int& esc, double& er2, uint32_t& nsingle,
+                                                 uint32_t& nbla, const double sm = 0.0, const int es = 0,
+                                                 XDeriv* const Dout = nullptr)
 {
-    const DeepArgs& A = AA.d;
     const double2* __restrict__ orbit = A.orbit;
-    const double2* __restrict__ mant = AA.mant;
-    const int32_t* __restrict__ exp2 = AA.exp2;
+    const double2* __restrict__ mant = AX.mant;
+    const int32_t* __restrict__ exp2 = AX.exp2;
     const XRad* __restrict__ tr = T.r;
     const int max_iter = A.max_iter;
     int N = A.n_ref, K = T.levels;
@@ -1530,81 +1455,7 @@ __device__ __forceinline__ void deep_orbit_x_bla(const DeepXArgs& AA, const BlaX
 }
 
 /* ---- the kernel --------------------------------------------------------------------------------------------------------
- * What an argument block is made of */
-__host__ __device__ __forceinline__ const DeepArgs& deep_args(const DeepArgs& A) { return A; }
-__host__ __device__ __forceinline__ const DeepArgs& deep_args(const DeepXArgs& A) { return A.d; }
-__host__ __device__ __forceinline__ const DeepArgs& deep_args(const DeepBlaArgs& A) { return A.d; }
-__host__ __device__ __forceinline__ const DeepArgs& deep_args(const DeepXBlaArgs& A) { return A.x.d; }
-__host__ __device__ __forceinline__ const DeepArgs& deep_args(const DeepDeArgs& A) { return A.d; }
-__host__ __device__ __forceinline__ const DeepArgs& deep_args(const DeepDeBlaArgs& A) { return A.e.d; }
-__host__ __device__ __forceinline__ const DeepDeArgs& de_args(const DeepDeArgs& A) { return A; }
-__host__ __device__ __forceinline__ const DeepDeArgs& de_args(const DeepDeBlaArgs& A) { return A.e; }
-__host__ __device__ __forceinline__ const DeepArgs& deep_args(const DeepXDeArgs& A) { return A.x.d; }
-__host__ __device__ __forceinline__ const DeepArgs& deep_args(const DeepXDeBlaArgs& A) { return A.e.x.d; }
-__host__ __device__ __forceinline__ const DeepXArgs& deepx_args(const DeepXDeArgs& A) { return A.x; }
-__host__ __device__ __forceinline__ const DeepXArgs& deepx_args(const DeepXDeBlaArgs& A) { return A.e.x; }
-__host__ __device__ __forceinline__ const DeepXDeArgs& de_args(const DeepXDeArgs& A) { return A; }
-__host__ __device__ __forceinline__ const DeepXDeArgs& de_args(const DeepXDeBlaArgs& A) { return A.e; }
-__host__ __device__ __forceinline__ const DeepArgs& deep_args(const DeepShipArgs& A) { return A.d; }
-__host__ __device__ __forceinline__ const DeepArgs& deep_args(const DeepShipBlaArgs& A) { return A.s.d; }
-__host__ __device__ __forceinline__ const DeepArgs& deep_args(const DeepShipXArgs& A) { return A.x.d; }
-__host__ __device__ __forceinline__ const DeepArgs& deep_args(const DeepShipXBlaArgs& A) { return A.s.x.d; }
-__host__ __device__ __forceinline__ const DeepArgs& deep_args(const DeepJuliaArgs& A) { return A.d; }
-__host__ __device__ __forceinline__ const DeepArgs& deep_args(const DeepJuliaXArgs& A) { return A.x.d; }
-__host__ __device__ __forceinline__ const DeepXArgs& deepx_args(const DeepJuliaXArgs& A) { return A.x; }
-__host__ __device__ __forceinline__ const DeepXArgs& deepx_args(const DeepXArgs& A) { return A; }
-__host__ __device__ __forceinline__ const DeepXArgs& deepx_args(const DeepXBlaArgs& A) { return A.x; }
-__host__ __device__ __forceinline__ const DeepXArgs& deepx_args(const DeepShipXArgs& A) { return A.x; }
-__host__ __device__ __forceinline__ const DeepXArgs& deepx_args(const DeepShipXBlaArgs& A) { return A.s.x; }
-__device__ __forceinline__ double ship_log_bailout(const DeepShipArgs& A) { return A.log_bailout; }
-__device__ __forceinline__ double ship_log_bailout(const DeepShipBlaArgs& A) { return A.s.log_bailout; }
-__device__ __forceinline__ double ship_log_bailout(const DeepShipXArgs& A) { return A.log_bailout; }
-__device__ __forceinline__ double ship_log_bailout(const DeepShipXBlaArgs& A) { return A.s.log_bailout; }
-__device__ __forceinline__ double ship_log_bailout(const DeepJuliaArgs& A) { return A.log_bailout; }
-__device__ __forceinline__ double ship_log_bailout(const DeepJuliaXArgs& A) { return A.log_bailout; }
-__host__ __device__ __forceinline__ const DeepArgs& deep_args(const DeepJuliaBlaArgs& A) { return A.j.d; }
-__host__ __device__ __forceinline__ const DeepArgs& deep_args(const DeepJuliaXBlaArgs& A) { return A.j.x.d; }
-__host__ __device__ __forceinline__ const DeepXArgs& deepx_args(const DeepJuliaXBlaArgs& A) { return A.j.x; }
-__device__ __forceinline__ double ship_log_bailout(const DeepJuliaBlaArgs& A) { return A.j.log_bailout; }
-__device__ __forceinline__ double ship_log_bailout(const DeepJuliaXBlaArgs& A) { return A.j.log_bailout; }
-
-__host__ __device__ __forceinline__ const DeepArgs& deep_args(const DeepJuliaDeArgs& A) { return A.d; }
-__host__ __device__ __forceinline__ const DeepArgs& deep_args(const DeepJuliaDeBlaArgs& A) { return A.e.d; }
-__host__ __device__ __forceinline__ const DeepArgs& deep_args(const DeepJuliaXDeArgs& A) { return A.x.d; }
-__host__ __device__ __forceinline__ const DeepArgs& deep_args(const DeepJuliaXDeBlaArgs& A) { return A.e.x.d; }
-__host__ __device__ __forceinline__ const DeepXArgs& deepx_args(const DeepJuliaXDeArgs& A) { return A.x; }
-__host__ __device__ __forceinline__ const DeepXArgs& deepx_args(const DeepJuliaXDeBlaArgs& A) { return A.e.x; }
-__host__ __device__ __forceinline__ const DeepJuliaDeArgs& de_args(const DeepJuliaDeArgs& A) { return A; }
-__host__ __device__ __forceinline__ const DeepJuliaDeArgs& de_args(const DeepJuliaDeBlaArgs& A) { return A.e; }
-__host__ __device__ __forceinline__ const DeepJuliaXDeArgs& de_args(const DeepJuliaXDeArgs& A) { return A; }
-__host__ __device__ __forceinline__ const DeepJuliaXDeArgs& de_args(const DeepJuliaXDeBlaArgs& A) { return A.e; }
-__device__ __forceinline__ double ship_log_bailout(const DeepJuliaDeArgs& A) { return A.log_bailout; }
-__device__ __forceinline__ double ship_log_bailout(const DeepJuliaDeBlaArgs& A) { return A.e.log_bailout; }
-__device__ __forceinline__ double ship_log_bailout(const DeepJuliaXDeArgs& A) { return A.log_bailout; }
-__device__ __forceinline__ double ship_log_bailout(const DeepJuliaXDeBlaArgs& A) { return A.e.log_bailout; }
-
-template <class T, class... U>
-constexpr bool is_any_of = (std::is_same<T, U>::value || ...);
-
-/* where a sample starts: a Julia view's P; nothing for the formulas with one orbit */
-template <class ARGS>
-__device__ __forceinline__ JuliaStart julia_start(const ARGS& A)
-{
-    if constexpr (is_any_of<ARGS, DeepJuliaArgs, DeepJuliaXArgs, DeepJuliaDeArgs, DeepJuliaXDeArgs>) return A.j;
-    else if constexpr (is_any_of<ARGS, DeepJuliaBlaArgs, DeepJuliaXBlaArgs>) return A.j.j;
-    else if constexpr (is_any_of<ARGS, DeepJuliaDeBlaArgs, DeepJuliaXDeBlaArgs>) return A.e.j;
-    else return JuliaStart{0, 0};
-}
-
-/* a table block's table: Q's of a Julia view */
-template <class TAB>
-__host__ __device__ __forceinline__ TAB& q_table(TAB& t) { return t; }
-template <class TAB>
-__host__ __device__ __forceinline__ TAB& q_table(JuliaTab<TAB>& t) { return t.q; }
-template <class TAB>
-__host__ __device__ __forceinline__ const TAB& q_table(const JuliaTab<TAB>& t) { return t.q; }
-
-/* The distance estimate of a sample that escaped with r2 and D (fr_render_deep_de): |z| log|z| / |D|, in pixel spacings since D
+ * The distance estimate of a sample that escaped with r2 and D (fr_render_deep_de): |z| log|z| / |D|, in pixel spacings since D
  * carries s.  |D| overflowing gives 0 by the division; NaN (D not finite, 0 / 0) becomes 0.  A function of its own, once per
  * escaped sample: inlined, the library log's polynomial coefficients are hoisted out of every loop of the kernel into twelve
  * VGPRs that stay live through the orbit loop (107 and 136 VGPRs, a wave per SIMD less in either kernel, against 94 and 123
@@ -1626,30 +1477,23 @@ __device__ __forceinline__ void deep_de_shade(float rgb[3], const double de, con
     for (int c = 0; c < 3; ++c) rgb[c] = rgb[c] * (1.0f - t) + (rgb[c] * 0.7f) * t;
 }
 
-/* ARGS names the loop: Deep[Ship|Julia][X][Bla]Args = the formula, extended-exponent deltas, BLA (with the step counts);
- * DeepDe[Bla]Args = Deep[Bla]Args, DeepXDe[Bla]Args = DeepX[Bla]Args, DeepJulia[X]De[Bla]Args = DeepJulia[X][Bla]Args with the
- * derivative and its two planes.  The body of the three __global__ templates below: deep_kernel for the fourteen blocks without
- * an extended derivative, deepx_de_kernel for the two Mandelbrot blocks with one, julia_de_kernel for Julia's four. */
+/* The block's switches name the loop: its formula, extended-exponent deltas, the distance estimate (the derivative and its two
+ * planes), BLA (with the step counts).  Two things here are as they are for the instruction streams' sake, which are those of
+ * the time when every block was a struct of its own: the body is a function apart from the one __global__ template below (written
+ * into it, all twenty kernels are scheduled differently), and Julia's j is read per sample, where the loops are called (read
+ * once in front of the walk, Julia's eight kernels differ). */
 template <class ARGS>
 __device__ __forceinline__ void deep_kernel_body(const ARGS& AA)
 {
-    constexpr bool BLA = is_any_of<ARGS, DeepBlaArgs, DeepXBlaArgs, DeepShipBlaArgs, DeepShipXBlaArgs, DeepJuliaBlaArgs,
-                                   DeepJuliaXBlaArgs, DeepDeBlaArgs, DeepXDeBlaArgs, DeepJuliaDeBlaArgs, DeepJuliaXDeBlaArgs>;
-    constexpr bool DE = is_any_of<ARGS, DeepDeArgs, DeepDeBlaArgs, DeepXDeArgs, DeepXDeBlaArgs, DeepJuliaDeArgs, DeepJuliaDeBlaArgs,
-                                  DeepJuliaXDeArgs, DeepJuliaXDeBlaArgs>;
-    constexpr bool X = is_any_of<ARGS, DeepXArgs, DeepXBlaArgs, DeepShipXArgs, DeepShipXBlaArgs, DeepJuliaXArgs,
-                                 DeepJuliaXBlaArgs, DeepXDeArgs, DeepXDeBlaArgs, DeepJuliaXDeArgs, DeepJuliaXDeBlaArgs>;
-    constexpr bool SHIP = is_any_of<ARGS, DeepShipArgs, DeepShipBlaArgs, DeepShipXArgs, DeepShipXBlaArgs>;
-    constexpr bool JULIA = is_any_of<ARGS, DeepJuliaArgs, DeepJuliaXArgs, DeepJuliaBlaArgs, DeepJuliaXBlaArgs, DeepJuliaDeArgs,
-                                     DeepJuliaDeBlaArgs, DeepJuliaXDeArgs, DeepJuliaXDeBlaArgs>;
-    using F = std::conditional_t<JULIA, JuliaFormula, std::conditional_t<SHIP, ShipFormula, MandelFormula>>;
+    using F = typename ARGS::Formula;
+    constexpr bool X = ARGS::kX, DE = ARGS::kDe, BLA = ARGS::kBla;
     constexpr int FRACTAL = F::kFractal;
-    const DeepArgs& A = deep_args(AA);
+    const DeepArgs& A = AA;
     __shared__ LdsBlock S;
     __shared__ double2 log2_lds[kLog2Entries];
     if (threadIdx.x == 0) S.pal = A.pal;
     if constexpr (F::kLogBailoutLds) {
-        if (threadIdx.x == 0) S.log_bailout = ship_log_bailout(AA);
+        if (threadIdx.x == 0) S.log_bailout = AA.log_bailout;
     }
     reinterpret_cast<double*>(log2_lds)[threadIdx.x] = reinterpret_cast<const double*>(A.log2_tab)[threadIdx.x];
     __syncthreads();
@@ -1666,7 +1510,7 @@ __device__ __forceinline__ void deep_kernel_body(const ARGS& AA)
     const int aa = A.aa > 1 ? A.aa : 1;
     const double resx = (double)W, resy = (double)H;
     double zs = A.zoom;                                           /* extended: the zoom's mantissa, its exponent goes to dc.e */
-    if constexpr (X) zs = deepx_args(AA).zm;
+    if constexpr (X) zs = AA.zm;
     const double2 z1 = A.orbit[1];
     const bool want_rgb = A.rgba != nullptr;
     const bool want_nu = want_rgb || A.nu != nullptr;
@@ -1674,15 +1518,15 @@ __device__ __forceinline__ void deep_kernel_body(const ARGS& AA)
     int de_es = 0;                                                /* ... and exponent */
     bool de_shade = false;
     if constexpr (DE) {
-        if constexpr (X) { de_s = de_args(AA).sm; de_es = de_args(AA).es; }
-        else de_s = de_args(AA).s;
-        de_shade = want_rgb && de_args(AA).shade != 0;
+        if constexpr (X) { de_s = AA.sm; de_es = AA.es; }
+        else de_s = AA.s;
+        de_shade = want_rgb && AA.shade != 0;
     }
 
     unsigned long long n_plain = 0ull, n_bla = 0ull, n_upd = 0ull;   /* BLA: this lane's steps and updates */
     int levels_p = 0;                                             /* BLA on two orbits: P's table */
     uint32_t base_p = 0u;
-    if constexpr (BLA && JULIA) { levels_p = AA.t.levels_p; base_p = AA.t.base_p; }
+    if constexpr (F::kTwoOrbits && BLA) { levels_p = AA.t.levels_p; base_p = AA.t.base_p; }
     walk_subtiles<3, true>(A.q, A.g, lane, [&](const int px, const int py, const int lrow, const bool inside) {
         float acc[3] = {0.0f, 0.0f, 0.0f};
         double nu0 = 0.0;
@@ -1694,35 +1538,35 @@ __device__ __forceinline__ void deep_kernel_body(const ARGS& AA)
             const double2 dc = F::dc(px, py, s, aa, resx, resy, zs);
             double cx = inside ? dc.x : 0.0, cy = inside ? dc.y : 0.0;
             uint32_t np = 0u, nb = 0u;
+            JuliaStart J = {0, 0};                                /* two orbits: where a sample starts, P */
+            if constexpr (F::kTwoOrbits) J = AA.j;
             double2 D = make_double2(0.0, 0.0);
             /* DE, extended: D = (D.x, D.y) 2^eD.  The loop's XDeriv is unpacked into these two so that the planes and
              * deep_de_of(r2, D) below are one code path with the fp64 derivative's, the exponent applied behind them */
             int eD = 0;
             if constexpr (DE && X) {
-                int ec = deepx_args(AA).ze;
+                int ec = AA.ze;
                 x_norm(cx, cy, ec);
                 XDeriv Dx;
                 if constexpr (BLA)
-                    deep_orbit_x_bla<F, true>(deepx_args(AA), q_table(AA.t), julia_start(AA), levels_p, base_p, cx, cy, ec, inside,
-                                              esc, r2, np, nb, de_s, de_es, &Dx);
-                else deep_orbit_x<F, true>(deepx_args(AA), julia_start(AA), cx, cy, ec, inside, esc, r2, de_s, de_es, &Dx);
+                    deep_orbit_x_bla<F, true>(A, AA, bla_table(AA), J, levels_p, base_p, cx, cy, ec, inside, esc, r2, np, nb,
+                                              de_s, de_es, &Dx);
+                else deep_orbit_x<F, true>(A, AA, J, cx, cy, ec, inside, esc, r2, de_s, de_es, &Dx);
                 D = make_double2(Dx.x, Dx.y); eD = Dx.e;
             } else if constexpr (DE) {
                 if constexpr (BLA)
-                    deep_orbit_bla<F, true>(A, q_table(AA.t), julia_start(AA), levels_p, base_p, cx, cy, z1, inside, esc, r2, np,
-                                            nb, de_s, &D);
-                else deep_orbit<F, true>(A, julia_start(AA), cx, cy, z1, inside, esc, r2, de_s, &D);
+                    deep_orbit_bla<F, true>(A, bla_table(AA), J, levels_p, base_p, cx, cy, z1, inside, esc, r2, np, nb, de_s, &D);
+                else deep_orbit<F, true>(A, J, cx, cy, z1, inside, esc, r2, de_s, &D);
             } else if constexpr (X) {
-                int ec = deepx_args(AA).ze;
+                int ec = AA.ze;
                 x_norm(cx, cy, ec);
                 if constexpr (BLA)
-                    deep_orbit_x_bla<F>(deepx_args(AA), q_table(AA.t), julia_start(AA), levels_p, base_p, cx, cy, ec, inside, esc,
-                                        r2, np, nb);
-                else deep_orbit_x<F>(deepx_args(AA), julia_start(AA), cx, cy, ec, inside, esc, r2);
+                    deep_orbit_x_bla<F>(A, AA, bla_table(AA), J, levels_p, base_p, cx, cy, ec, inside, esc, r2, np, nb);
+                else deep_orbit_x<F>(A, AA, J, cx, cy, ec, inside, esc, r2);
             } else {
                 if constexpr (BLA)
-                    deep_orbit_bla<F>(A, q_table(AA.t), julia_start(AA), levels_p, base_p, cx, cy, z1, inside, esc, r2, np, nb);
-                else deep_orbit<F>(A, julia_start(AA), cx, cy, z1, inside, esc, r2);
+                    deep_orbit_bla<F>(A, bla_table(AA), J, levels_p, base_p, cx, cy, z1, inside, esc, r2, np, nb);
+                else deep_orbit<F>(A, J, cx, cy, z1, inside, esc, r2);
             }
             if (BLA && inside) {
                 n_plain += np; n_bla += nb;
@@ -1734,8 +1578,8 @@ __device__ __forceinline__ void deep_kernel_body(const ARGS& AA)
             if constexpr (DE) {
                 const bool escaped = esc < A.max_iter;            /* interior: 0 and (0, 0) */
                 const bool first = s == 0 && inside;
-                if (first && de_args(AA).deriv) {
-                    double* const dst = de_args(AA).deriv + 2 * plane_index(A.g, px, py, lrow);
+                if (first && AA.deriv) {
+                    double* const dst = AA.deriv + 2 * plane_index(A.g, px, py, lrow);
                     if constexpr (X) {                            /* saturates outside a double's range */
                         dst[0] = escaped ? __builtin_ldexp(D.x, eD) : 0.0; dst[1] = escaped ? __builtin_ldexp(D.y, eD) : 0.0;
                     } else {
@@ -1746,14 +1590,14 @@ __device__ __forceinline__ void deep_kernel_body(const ARGS& AA)
                     de = deep_de_of(r2, D);                       /* extended: of the mantissas, so |D| cannot overflow */
                     if constexpr (X) de = __builtin_ldexp(de, -eD);
                 }
-                if (first && de_args(AA).de) de_args(AA).de[plane_index(A.g, px, py, lrow)] = de;
+                if (first && AA.de) AA.de[plane_index(A.g, px, py, lrow)] = de;
             }
             double nu;
             float rgb[3];
             shade<double, FRACTAL>(A, S, lg, esc, r2, want_nu, want_rgb, nu, rgb);
             if (s == 0) { nu0 = nu; it0 = esc; }
             if constexpr (DE) {
-                if (de_shade && esc < A.max_iter) deep_de_shade(rgb, de, de_args(AA).edge_px);
+                if (de_shade && esc < A.max_iter) deep_de_shade(rgb, de, AA.edge_px);
             }
             acc[0] += rgb[0]; acc[1] += rgb[1]; acc[2] += rgb[2];
         }
@@ -1772,7 +1616,7 @@ __device__ __forceinline__ void deep_kernel_body(const ARGS& AA)
         unsigned long long v[3] = {n_plain, n_bla, n_upd - n_plain};
         for (int c = 0; c < 3; ++c) {
             for (int o = kWave / 2; o > 0; o >>= 1) v[c] += __shfl_xor(v[c], o, kWave);
-            if (lane == 0) atomicAdd(q_table(AA.t).steps + c, v[c]);
+            if (lane == 0) atomicAdd(bla_table(AA).steps + c, v[c]);
         }
     }
 }
@@ -1780,23 +1624,6 @@ __device__ __forceinline__ void deep_kernel_body(const ARGS& AA)
 template <class ARGS>
 __global__ void __launch_bounds__(kBlockThreads)
 deep_kernel(const ARGS AA)
-{
-    deep_kernel_body(AA);
-}
-
-/* fr_render_deepx_de's two kernels (DeepXDeArgs, DeepXDeBlaArgs) */
-template <class ARGS>
-__global__ void __launch_bounds__(kBlockThreads)
-deepx_de_kernel(const ARGS AA)
-{
-    deep_kernel_body(AA);
-}
-
-/* fr_render_deep_julia_de's and fr_render_deepx_julia_de's four kernels (DeepJuliaDeArgs, DeepJuliaDeBlaArgs, DeepJuliaXDeArgs,
- * DeepJuliaXDeBlaArgs) */
-template <class ARGS>
-__global__ void __launch_bounds__(kBlockThreads)
-julia_de_kernel(const ARGS AA)
 {
     deep_kernel_body(AA);
 }

@@ -14,6 +14,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <string>
 
 #include "fr_kernels.hip.h"
 #include "fr_phoenix.hip.h"
@@ -888,7 +889,7 @@ struct JuliaTables { int32_t levels_p; uint32_t base_p; };
  * event: the render may have gone to another stream); growing them frees the old ones, so that waits on the host first.  A
  * Julia slot (jt) holds two tables, Q's entries first and P's behind them, built from the slot's two orbits; no dcmax enters
  * them, so their key is the orbit slot's generation alone and a zoom change rebuilds nothing. */
-static int bla_table_for(fr_ctx* c, DeepSlot& s, int f, const DeepArgs& d, const DeepXArgs* x, hipStream_t stream, int* levels,
+static int bla_table_for(fr_ctx* c, DeepSlot& s, int f, const DeepArgs& d, const DeepXOrbit* x, hipStream_t stream, int* levels,
                          JuliaTables* jt)
 {
     BlaSlot& t = s.t;
@@ -974,45 +975,42 @@ static int bla_table_for(fr_ctx* c, DeepSlot& s, int f, const DeepArgs& d, const
 static void bla_table_args(BlaTable& a, const BlaSlot& t) { a.r = (const double*)t.r; a.ab = t.ab; }
 static void bla_table_args(BlaXTable& a, const BlaSlot& t) { a.r = (const XRad*)t.r; a.ab = t.ab; a.abe = t.abe; }
 
-template <class ARGS>
-static DeepArgs& deep_of(ARGS& a) { return const_cast<DeepArgs&>(deep_args(a)); }
+/* The ten paths, each by the block of its unflagged kernel (the flagged kernel's, with the table: DeepPath::Bla) */
+using DeepMandel = DeepBlock<MandelFormula, false, false>;
+using DeepMandelDe = DeepBlock<MandelFormula, false, true>;
+using DeepMandelX = DeepBlock<MandelFormula, true, false>;
+using DeepMandelXDe = DeepBlock<MandelFormula, true, true>;
+using DeepShip = DeepBlock<ShipFormula, false, false>;
+using DeepShipX = DeepBlock<ShipFormula, true, false>;
+using DeepJulia = DeepBlock<JuliaFormula, false, false>;
+using DeepJuliaDe = DeepBlock<JuliaFormula, false, true>;
+using DeepJuliaX = DeepBlock<JuliaFormula, true, false>;
+using DeepJuliaXDe = DeepBlock<JuliaFormula, true, true>;
 
-/* One record per argument block of an unflagged deep kernel: the path it renders -- formula, storage, de = 1 for the blocks that
- * carry a derivative -- the block of its flagged kernel (Bla = {the base block, the table}), the flag that selects it, the
- * __global__ template of both kernels (deep_kernel unless the record names another) and their names in messages.  launch_deep
- * and enqueue_deep_view read everything that differs between the paths from here. */
-template <int F, bool EXT, class BLA, uint32_t FLAG, int DE = 0>
-struct DeepPathOf {
-    static constexpr int f = F, de = DE;
-    static constexpr bool ext = EXT;
-    static constexpr uint32_t flag = FLAG;
-    using Bla = BLA;
-    template <class ARGS> static auto kernel() -> void (*)(ARGS) { return deep_kernel<ARGS>; }   /* of either block */
+/* What launch_deep and enqueue_deep_view read of a path, BASE being the argument block of its unflagged kernel: the formula, the
+ * storage, de = 1 for the blocks that carry a derivative, the flag that selects the flagged kernel and that kernel's block */
+static constexpr uint32_t kDeepBlaFlag[3][2] = {{FR_FLAG_DEEP_BLA, FR_FLAG_DEEPX_BLA},
+                                                {FR_FLAG_DEEP_SHIP_BLA, FR_FLAG_DEEPX_SHIP_BLA},
+                                                {FR_FLAG_DEEP_JULIA_BLA, FR_FLAG_DEEPX_JULIA_BLA}};
+template <class BASE>
+struct DeepPath {
+    using F = typename BASE::Formula;
+    static constexpr int f = std::is_same<F, ShipFormula>::value ? kShip : std::is_same<F, JuliaFormula>::value ? kJulia : kMandel;
+    static constexpr int de = BASE::kDe;
+    static constexpr bool ext = BASE::kX;
+    static constexpr uint32_t flag = kDeepBlaFlag[f][ext];
+    using Bla = DeepBlock<F, BASE::kX, BASE::kDe, true>;
 };
-template <class BASE> struct DeepPath;
-template <> struct DeepPath<DeepArgs> : DeepPathOf<kMandel, false, DeepBlaArgs, FR_FLAG_DEEP_BLA> {
-    static constexpr const char *name = "deep_kernel<DeepArgs>", *bla_name = "deep_kernel<DeepBlaArgs>"; };
-template <> struct DeepPath<DeepDeArgs> : DeepPathOf<kMandel, false, DeepDeBlaArgs, FR_FLAG_DEEP_BLA, 1> {
-    static constexpr const char *name = "deep_kernel<DeepDeArgs>", *bla_name = "deep_kernel<DeepDeBlaArgs>"; };
-template <> struct DeepPath<DeepShipArgs> : DeepPathOf<kShip, false, DeepShipBlaArgs, FR_FLAG_DEEP_SHIP_BLA> {
-    static constexpr const char *name = "deep_kernel<DeepShipArgs>", *bla_name = "deep_kernel<DeepShipBlaArgs>"; };
-template <> struct DeepPath<DeepJuliaArgs> : DeepPathOf<kJulia, false, DeepJuliaBlaArgs, FR_FLAG_DEEP_JULIA_BLA> {
-    static constexpr const char *name = "deep_kernel<DeepJuliaArgs>", *bla_name = "deep_kernel<DeepJuliaBlaArgs>"; };
-template <> struct DeepPath<DeepJuliaDeArgs> : DeepPathOf<kJulia, false, DeepJuliaDeBlaArgs, FR_FLAG_DEEP_JULIA_BLA, 1> {
-    static constexpr const char *name = "julia_de_kernel<DeepJuliaDeArgs>", *bla_name = "julia_de_kernel<DeepJuliaDeBlaArgs>";
-    template <class ARGS> static auto kernel() -> void (*)(ARGS) { return julia_de_kernel<ARGS>; } };
-template <> struct DeepPath<DeepXArgs> : DeepPathOf<kMandel, true, DeepXBlaArgs, FR_FLAG_DEEPX_BLA> {
-    static constexpr const char *name = "deep_kernel<DeepXArgs>", *bla_name = "deep_kernel<DeepXBlaArgs>"; };
-template <> struct DeepPath<DeepXDeArgs> : DeepPathOf<kMandel, true, DeepXDeBlaArgs, FR_FLAG_DEEPX_BLA, 1> {
-    static constexpr const char *name = "deepx_de_kernel<DeepXDeArgs>", *bla_name = "deepx_de_kernel<DeepXDeBlaArgs>";
-    template <class ARGS> static auto kernel() -> void (*)(ARGS) { return deepx_de_kernel<ARGS>; } };
-template <> struct DeepPath<DeepShipXArgs> : DeepPathOf<kShip, true, DeepShipXBlaArgs, FR_FLAG_DEEPX_SHIP_BLA> {
-    static constexpr const char *name = "deep_kernel<DeepShipXArgs>", *bla_name = "deep_kernel<DeepShipXBlaArgs>"; };
-template <> struct DeepPath<DeepJuliaXArgs> : DeepPathOf<kJulia, true, DeepJuliaXBlaArgs, FR_FLAG_DEEPX_JULIA_BLA> {
-    static constexpr const char *name = "deep_kernel<DeepJuliaXArgs>", *bla_name = "deep_kernel<DeepJuliaXBlaArgs>"; };
-template <> struct DeepPath<DeepJuliaXDeArgs> : DeepPathOf<kJulia, true, DeepJuliaXDeBlaArgs, FR_FLAG_DEEPX_JULIA_BLA, 1> {
-    static constexpr const char *name = "julia_de_kernel<DeepJuliaXDeArgs>", *bla_name = "julia_de_kernel<DeepJuliaXDeBlaArgs>";
-    template <class ARGS> static auto kernel() -> void (*)(ARGS) { return julia_de_kernel<ARGS>; } };
+
+/* a deep kernel's name in messages, from its block's switches: deep_kernel<Julia, X, DE, BLA> */
+template <class ARGS>
+static const char* deep_kernel_name()
+{
+    static const char* const formula[3] = {"Mandel", "Ship", "Julia"};
+    static const std::string name = std::string("deep_kernel<") + formula[DeepPath<ARGS>::f] + (ARGS::kX ? ", X" : "") +
+                                    (ARGS::kDe ? ", DE" : "") + (ARGS::kBla ? ", BLA" : "") + ">";
+    return name.c_str();
+}
 
 /* One pass of a deep view, `base` being the argument block of its unflagged kernel: the path's kernel of BASE at the occupancy
  * cached in its slot, or with `bla` the table, then the path's flagged kernel on the same queue plan at its own occupancy, its
@@ -1024,24 +1022,21 @@ static int launch_deep(fr_ctx* c, hipStream_t stream, BASE& base, bool bla)
     using P = DeepPath<BASE>;
     using BLA = typename P::Bla;
     DeepSlot& s = deep_slot(c, P::ext, P::f);
-    if (!bla) {
-        DeepArgs& d = deep_of(base);
-        return launch_one_pass(c, stream, P::name, P::template kernel<BASE>(), base, d.g, d.q, s.wg_per_cu[P::de][0], false);
-    }
+    if (!bla)
+        return launch_one_pass(c, stream, deep_kernel_name<BASE>(), deep_kernel<BASE>, base, base.g, base.q, s.wg_per_cu[P::de][0],
+                               false);
     BLA a;
     memset(&a, 0, sizeof(a));
-    auto& [b, tabs] = a;
-    b = base;
-    DeepArgs& d = deep_of(a);
-    const DeepXArgs* x = nullptr;
-    if constexpr (P::ext) x = &deepx_args(a);
+    static_cast<BASE&>(a) = base;
+    const DeepXOrbit* x = nullptr;
+    if constexpr (P::ext) x = &a;
     BlaSlot& t = s.t;
     int levels = 0;
     JuliaTables jt = {0, 0u};
-    const int ts = bla_table_for(c, s, P::f, d, x, stream, &levels, &jt);
+    const int ts = bla_table_for(c, s, P::f, a, x, stream, &levels, &jt);
     if (ts != FR_OK) return ts;
-    auto& tab = q_table(tabs);
-    if constexpr (P::f == kJulia) { tabs.levels_p = jt.levels_p; tabs.base_p = jt.base_p; }
+    auto& tab = bla_table(a);
+    if constexpr (P::f == kJulia) { a.t.levels_p = jt.levels_p; a.t.base_p = jt.base_p; }
     bla_table_args(tab, t);
     tab.levels = levels;
     if (!t.steps_dev) {
@@ -1050,7 +1045,7 @@ static int launch_deep(fr_ctx* c, hipStream_t stream, BASE& base, bool bla)
     }
     tab.steps = t.steps_dev;
     FR_HIP_TRY(hipMemsetAsync(t.steps_dev, 0, 3 * sizeof(unsigned long long), stream));
-    const int st = launch_one_pass(c, stream, P::bla_name, P::template kernel<BLA>(), a, d.g, d.q, s.wg_per_cu[P::de][1], false);
+    const int st = launch_one_pass(c, stream, deep_kernel_name<BLA>(), deep_kernel<BLA>, a, a.g, a.q, s.wg_per_cu[P::de][1], false);
     if (st != FR_OK) return st;
     FR_HIP_TRY(hipMemcpyAsync(t.steps_host, t.steps_dev, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
     t.have_steps = true;
@@ -1102,19 +1097,17 @@ static int enqueue_deep_view(fr_ctx* c, const fr_params* p, const DeepAt& at, ui
     const DeepOrbit& o = deep_slot(c, P::ext, P::f).o;
     BASE b;
     memset(&b, 0, sizeof(b));
-    DeepArgs& a = deep_of(b);
-    a.orbit = reinterpret_cast<const double2*>(o.dev); a.n_ref = o.len - 1;
-    if constexpr (P::ext) {                                      /* (d.zoom is not read) */
-        DeepXArgs& x = const_cast<DeepXArgs&>(deepx_args(b));
-        x.mant = a.orbit + o.cap;
-        x.exp2 = reinterpret_cast<const int32_t*>(x.mant + o.cap);
-        x.zm = at.zm;
-        x.ze = at.ze;
+    b.orbit = reinterpret_cast<const double2*>(o.dev); b.n_ref = o.len - 1;
+    if constexpr (P::ext) {                                      /* (zoom is not read) */
+        b.mant = b.orbit + o.cap;
+        b.exp2 = reinterpret_cast<const int32_t*>(b.mant + o.cap);
+        b.zm = at.zm;
+        b.ze = at.ze;
     } else {
-        a.zoom = p->zoom;
+        b.zoom = p->zoom;
     }
     if constexpr (P::f == kJulia) { b.j.p_off = (int32_t)(o.cap / 2); b.j.n_p = o.len_p - 1; }
-    fill_deep_args(a, c, p, tile_geom(W, H, rows_local, &norm, out_frame), rgba, nu, iter);
+    fill_deep_args(b, c, p, tile_geom(W, H, rows_local, &norm, out_frame), rgba, nu, iter);
     if constexpr (P::f != kMandel) b.log_bailout = log((double)p->bailout);
     extra(b);
     return launch_deep(c, stream, b, (p->flags & P::flag) != 0);
@@ -1128,8 +1121,8 @@ static int enqueue_deepx_at(fr_ctx* c, int f, const fr_params* p, const fr_deepx
 {
     const DeepAt at = {v->center_x, v->center_y, v->zoom, zm, ze, bits};
     if (f == kShip)
-        return enqueue_deep_view<DeepShipXArgs>(c, p, at, W, H, shard, rgba, nu, iter, stream, out_frame, [](auto&) {});
-    return enqueue_deep_view<DeepXArgs>(c, p, at, W, H, shard, rgba, nu, iter, stream, out_frame, [](auto&) {});
+        return enqueue_deep_view<DeepShipX>(c, p, at, W, H, shard, rgba, nu, iter, stream, out_frame, [](auto&) {});
+    return enqueue_deep_view<DeepMandelX>(c, p, at, W, H, shard, rgba, nu, iter, stream, out_frame, [](auto&) {});
 }
 
 /* ---- deep zoom sequences (fr_deep_sequence; the rules are in the header, the host planning in fr_deepseq.c) ---------------
@@ -1961,14 +1954,14 @@ static int deep_entry(const char* async_entry, fr_ctx* c, const fr_params* p, co
 extern "C" int fr_render_deep_async(fr_ctx* c, const fr_params* p, const fr_deep_view* v, uint32_t W, uint32_t H,
                                     const fr_shard* shard, const fr_output* out, void* hip_stream)
 {
-    return deep_entry<DeepArgs>("fr_render_deep_async", c, p, v, nullptr, W, H, shard, out, hip_stream,
+    return deep_entry<DeepMandel>("fr_render_deep_async", c, p, v, nullptr, W, H, shard, out, hip_stream,
                                 [&] { return fr_deep_validate(p, v, W, H); });
 }
 
 extern "C" int fr_render_deep(fr_ctx* c, const fr_params* p, const fr_deep_view* v, uint32_t W, uint32_t H,
                               const fr_shard* shard, const fr_output* out)
 {
-    return deep_entry<DeepArgs>(nullptr, c, p, v, nullptr, W, H, shard, out, nullptr,
+    return deep_entry<DeepMandel>(nullptr, c, p, v, nullptr, W, H, shard, out, nullptr,
                                 [&] { return fr_deep_validate(p, v, W, H); });
 }
 
@@ -1976,42 +1969,42 @@ extern "C" int fr_render_deep(fr_ctx* c, const fr_params* p, const fr_deep_view*
 extern "C" int fr_render_deep_de_async(fr_ctx* c, const fr_params* p, const fr_deep_view* v, const fr_deep_de* e, uint32_t W,
                                        uint32_t H, const fr_shard* shard, const fr_output* out, void* hip_stream)
 {
-    return deep_entry<DeepDeArgs>("fr_render_deep_de_async", c, p, v, e, W, H, shard, out, hip_stream,
+    return deep_entry<DeepMandelDe>("fr_render_deep_de_async", c, p, v, e, W, H, shard, out, hip_stream,
                                   [&] { return fr_deep_de_validate(p, v, e, W, H); });
 }
 
 extern "C" int fr_render_deep_de(fr_ctx* c, const fr_params* p, const fr_deep_view* v, const fr_deep_de* e, uint32_t W, uint32_t H,
                                  const fr_shard* shard, const fr_output* out)
 {
-    return deep_entry<DeepDeArgs>(nullptr, c, p, v, e, W, H, shard, out, nullptr,
+    return deep_entry<DeepMandelDe>(nullptr, c, p, v, e, W, H, shard, out, nullptr,
                                   [&] { return fr_deep_de_validate(p, v, e, W, H); });
 }
 
 extern "C" int fr_render_deep_ship_async(fr_ctx* c, const fr_params* p, const fr_deep_view* v, uint32_t W, uint32_t H,
                                          const fr_shard* shard, const fr_output* out, void* hip_stream)
 {
-    return deep_entry<DeepShipArgs>("fr_render_deep_ship_async", c, p, v, nullptr, W, H, shard, out, hip_stream,
+    return deep_entry<DeepShip>("fr_render_deep_ship_async", c, p, v, nullptr, W, H, shard, out, hip_stream,
                                     [&] { return fr_deep_ship_validate(p, v, W, H); });
 }
 
 extern "C" int fr_render_deep_ship(fr_ctx* c, const fr_params* p, const fr_deep_view* v, uint32_t W, uint32_t H,
                                    const fr_shard* shard, const fr_output* out)
 {
-    return deep_entry<DeepShipArgs>(nullptr, c, p, v, nullptr, W, H, shard, out, nullptr,
+    return deep_entry<DeepShip>(nullptr, c, p, v, nullptr, W, H, shard, out, nullptr,
                                     [&] { return fr_deep_ship_validate(p, v, W, H); });
 }
 
 extern "C" int fr_render_deepx_async(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, uint32_t W, uint32_t H,
                                      const fr_shard* shard, const fr_output* out, void* hip_stream)
 {
-    return deep_entry<DeepXArgs>("fr_render_deepx_async", c, p, v, nullptr, W, H, shard, out, hip_stream,
+    return deep_entry<DeepMandelX>("fr_render_deepx_async", c, p, v, nullptr, W, H, shard, out, hip_stream,
                                  [&] { return fr_deepx_validate(p, v, W, H); });
 }
 
 extern "C" int fr_render_deepx(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, uint32_t W, uint32_t H,
                                const fr_shard* shard, const fr_output* out)
 {
-    return deep_entry<DeepXArgs>(nullptr, c, p, v, nullptr, W, H, shard, out, nullptr,
+    return deep_entry<DeepMandelX>(nullptr, c, p, v, nullptr, W, H, shard, out, nullptr,
                                  [&] { return fr_deepx_validate(p, v, W, H); });
 }
 
@@ -2019,56 +2012,56 @@ extern "C" int fr_render_deepx(fr_ctx* c, const fr_params* p, const fr_deepx_vie
 extern "C" int fr_render_deepx_de_async(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, const fr_deep_de* e, uint32_t W,
                                         uint32_t H, const fr_shard* shard, const fr_output* out, void* hip_stream)
 {
-    return deep_entry<DeepXDeArgs>("fr_render_deepx_de_async", c, p, v, e, W, H, shard, out, hip_stream,
+    return deep_entry<DeepMandelXDe>("fr_render_deepx_de_async", c, p, v, e, W, H, shard, out, hip_stream,
                                    [&] { return fr_deepx_de_validate(p, v, e, W, H); });
 }
 
 extern "C" int fr_render_deepx_de(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, const fr_deep_de* e, uint32_t W,
                                   uint32_t H, const fr_shard* shard, const fr_output* out)
 {
-    return deep_entry<DeepXDeArgs>(nullptr, c, p, v, e, W, H, shard, out, nullptr,
+    return deep_entry<DeepMandelXDe>(nullptr, c, p, v, e, W, H, shard, out, nullptr,
                                    [&] { return fr_deepx_de_validate(p, v, e, W, H); });
 }
 
 extern "C" int fr_render_deepx_ship_async(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, uint32_t W, uint32_t H,
                                           const fr_shard* shard, const fr_output* out, void* hip_stream)
 {
-    return deep_entry<DeepShipXArgs>("fr_render_deepx_ship_async", c, p, v, nullptr, W, H, shard, out, hip_stream,
+    return deep_entry<DeepShipX>("fr_render_deepx_ship_async", c, p, v, nullptr, W, H, shard, out, hip_stream,
                                      [&] { return fr_deepx_ship_validate(p, v, W, H); });
 }
 
 extern "C" int fr_render_deepx_ship(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, uint32_t W, uint32_t H,
                                     const fr_shard* shard, const fr_output* out)
 {
-    return deep_entry<DeepShipXArgs>(nullptr, c, p, v, nullptr, W, H, shard, out, nullptr,
+    return deep_entry<DeepShipX>(nullptr, c, p, v, nullptr, W, H, shard, out, nullptr,
                                      [&] { return fr_deepx_ship_validate(p, v, W, H); });
 }
 
 extern "C" int fr_render_deep_julia_async(fr_ctx* c, const fr_params* p, const fr_deep_view* v, uint32_t W, uint32_t H,
                                           const fr_shard* shard, const fr_output* out, void* hip_stream)
 {
-    return deep_entry<DeepJuliaArgs>("fr_render_deep_julia_async", c, p, v, nullptr, W, H, shard, out, hip_stream,
+    return deep_entry<DeepJulia>("fr_render_deep_julia_async", c, p, v, nullptr, W, H, shard, out, hip_stream,
                                      [&] { return fr_deep_julia_validate(p, v, W, H); });
 }
 
 extern "C" int fr_render_deep_julia(fr_ctx* c, const fr_params* p, const fr_deep_view* v, uint32_t W, uint32_t H,
                                     const fr_shard* shard, const fr_output* out)
 {
-    return deep_entry<DeepJuliaArgs>(nullptr, c, p, v, nullptr, W, H, shard, out, nullptr,
+    return deep_entry<DeepJulia>(nullptr, c, p, v, nullptr, W, H, shard, out, nullptr,
                                      [&] { return fr_deep_julia_validate(p, v, W, H); });
 }
 
 extern "C" int fr_render_deepx_julia_async(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, uint32_t W, uint32_t H,
                                            const fr_shard* shard, const fr_output* out, void* hip_stream)
 {
-    return deep_entry<DeepJuliaXArgs>("fr_render_deepx_julia_async", c, p, v, nullptr, W, H, shard, out, hip_stream,
+    return deep_entry<DeepJuliaX>("fr_render_deepx_julia_async", c, p, v, nullptr, W, H, shard, out, hip_stream,
                                       [&] { return fr_deepx_julia_validate(p, v, W, H); });
 }
 
 extern "C" int fr_render_deepx_julia(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, uint32_t W, uint32_t H,
                                      const fr_shard* shard, const fr_output* out)
 {
-    return deep_entry<DeepJuliaXArgs>(nullptr, c, p, v, nullptr, W, H, shard, out, nullptr,
+    return deep_entry<DeepJuliaX>(nullptr, c, p, v, nullptr, W, H, shard, out, nullptr,
                                       [&] { return fr_deepx_julia_validate(p, v, W, H); });
 }
 
@@ -2077,14 +2070,14 @@ extern "C" int fr_render_deepx_julia(fr_ctx* c, const fr_params* p, const fr_dee
 extern "C" int fr_render_deep_julia_de_async(fr_ctx* c, const fr_params* p, const fr_deep_view* v, const fr_deep_de* e, uint32_t W,
                                              uint32_t H, const fr_shard* shard, const fr_output* out, void* hip_stream)
 {
-    return deep_entry<DeepJuliaDeArgs>("fr_render_deep_julia_de_async", c, p, v, e, W, H, shard, out, hip_stream,
+    return deep_entry<DeepJuliaDe>("fr_render_deep_julia_de_async", c, p, v, e, W, H, shard, out, hip_stream,
                                        [&] { return fr_deep_julia_de_validate(p, v, e, W, H); });
 }
 
 extern "C" int fr_render_deep_julia_de(fr_ctx* c, const fr_params* p, const fr_deep_view* v, const fr_deep_de* e, uint32_t W,
                                        uint32_t H, const fr_shard* shard, const fr_output* out)
 {
-    return deep_entry<DeepJuliaDeArgs>(nullptr, c, p, v, e, W, H, shard, out, nullptr,
+    return deep_entry<DeepJuliaDe>(nullptr, c, p, v, e, W, H, shard, out, nullptr,
                                        [&] { return fr_deep_julia_de_validate(p, v, e, W, H); });
 }
 
@@ -2092,14 +2085,14 @@ extern "C" int fr_render_deepx_julia_de_async(fr_ctx* c, const fr_params* p, con
                                               uint32_t W, uint32_t H, const fr_shard* shard, const fr_output* out,
                                               void* hip_stream)
 {
-    return deep_entry<DeepJuliaXDeArgs>("fr_render_deepx_julia_de_async", c, p, v, e, W, H, shard, out, hip_stream,
+    return deep_entry<DeepJuliaXDe>("fr_render_deepx_julia_de_async", c, p, v, e, W, H, shard, out, hip_stream,
                                         [&] { return fr_deepx_julia_de_validate(p, v, e, W, H); });
 }
 
 extern "C" int fr_render_deepx_julia_de(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, const fr_deep_de* e, uint32_t W,
                                         uint32_t H, const fr_shard* shard, const fr_output* out)
 {
-    return deep_entry<DeepJuliaXDeArgs>(nullptr, c, p, v, e, W, H, shard, out, nullptr,
+    return deep_entry<DeepJuliaXDe>(nullptr, c, p, v, e, W, H, shard, out, nullptr,
                                         [&] { return fr_deepx_julia_de_validate(p, v, e, W, H); });
 }
 

@@ -1,11 +1,10 @@
 """The parameter cases of test_deep_cases_gpu.py as data, and the CPU predicates that say what each of them can see.
 
-The deep-view kernels (fr_deep.hip.h: the sixteen instantiations of KERNELS below -- fourteen of deep_kernel<ARGS>, two of
-deepx_de_kernel<ARGS>) are tested elsewhere on many views and always with the FractalState defaults.  Here the views are few
+The deep-view kernels (fr_deep.hip.h: the sixteen instantiations of deep_kernel<ARGS> in KERNELS below) are tested elsewhere on many views and always with the FractalState defaults.  Here the views are few
 and the parameters vary: everything the validators accept (fr_deep_validate, fr_deepx_validate, fr_deep_ship_validate,
 fr_deepx_ship_validate, fr_deep_julia_validate, fr_deepx_julia_validate, fr_deep_de_validate) and the one host path
-(DeepPath<BASE>, enqueue_deep_view, launch_deep in fr_device.hip) turns into a kernel's argument block -- a flagged kernel's
-as {base block, table}.  Every one of the sixteen kernels runs in some case (test_deep_cases_host.py asserts it from PATHS).
+(DeepPath<BASE>, enqueue_deep_view, launch_deep in fr_device.hip) turns into a kernel's argument block, DeepBlock<F, X, DE, BLA>
+-- a flagged kernel's is the base block with the table behind it.  Every one of the sixteen kernels runs in some case (test_deep_cases_host.py asserts it from PATHS).
 
 A case is Case(path, view, params, W, H):
   path    a key of KERNELS: deep | ship | julia | de, an x for the extended arithmetic, _bla for the flagged kernel
@@ -60,15 +59,11 @@ Restated = namedtuple("Restated", "samples counts N D NQ stats", defaults=(None,
 
 W0, H0 = 96, 64
 RAGGED = (100, 37)
-# path -> the kernel instantiation it launches (fr_device.hip, DeepPath<BASE>::name / bla_name)
-KERNELS = {"deep": "deep_kernel<DeepArgs>", "deep_bla": "deep_kernel<DeepBlaArgs>",
-           "deepx": "deep_kernel<DeepXArgs>", "deepx_bla": "deep_kernel<DeepXBlaArgs>",
-           "ship": "deep_kernel<DeepShipArgs>", "ship_bla": "deep_kernel<DeepShipBlaArgs>",
-           "shipx": "deep_kernel<DeepShipXArgs>", "shipx_bla": "deep_kernel<DeepShipXBlaArgs>",
-           "julia": "deep_kernel<DeepJuliaArgs>", "julia_bla": "deep_kernel<DeepJuliaBlaArgs>",
-           "juliax": "deep_kernel<DeepJuliaXArgs>", "juliax_bla": "deep_kernel<DeepJuliaXBlaArgs>",
-           "de": "deep_kernel<DeepDeArgs>", "de_bla": "deep_kernel<DeepDeBlaArgs>",
-           "dex": "deepx_de_kernel<DeepXDeArgs>", "dex_bla": "deepx_de_kernel<DeepXDeBlaArgs>"}
+# path -> the kernel instantiation it launches, as fr_device.hip names it in messages (deep_kernel_name: the switches of the
+# path's DeepBlock<F, X, DE, BLA> that are on)
+_SWITCHES = {"deep": "Mandel", "deepx": "Mandel, X", "ship": "Ship", "shipx": "Ship, X", "julia": "Julia", "juliax": "Julia, X",
+             "de": "Mandel, DE", "dex": "Mandel, X, DE"}
+KERNELS = {p + b: "deep_kernel<%s%s>" % (s, ", BLA" if b else "") for p, s in _SWITCHES.items() for b in ("", "_bla")}
 PATHS = tuple(KERNELS)
 OLD_PATHS = ("deep", "deep_bla", "deepx", "deepx_bla", "ship")     # the paths of the table before the other eleven
 SHIP_PATHS = ("ship", "ship_bla", "shipx", "shipx_bla")

@@ -153,17 +153,23 @@ def test_the_table_holds_what_the_groups_promise():
 
 
 def test_every_kernel_of_the_family_runs_in_some_case():
-    """fr_deep.hip.h instantiates sixteen kernels, fourteen deep_kernel<ARGS> and two deepx_de_kernel<ARGS>; a path is one of
-    them (dc.KERNELS: DeepPath<BASE>::name / bla_name of fr_device.hip), and every path has cases"""
+    """The table's paths are sixteen distinct deep_kernel instantiations, one per path (dc.KERNELS: deep_kernel_name of
+    fr_device.hip), and every path has cases: every block fr_device.hip's entry points name (an alias of DeepBlock<F, X, DE>),
+    without and with its table, but the four of Julia's distance estimate"""
     assert len(dc.PATHS) == 16 and len(set(dc.KERNELS.values())) == 16
     kernels = {dc.KERNELS[c.path] for c in dc.CASES.values()}
     assert kernels == set(dc.KERNELS.values())
-    assert sum(k.startswith("deep_kernel<") for k in kernels) == 14 and sum(k.startswith("deepx_de_kernel<") for k in kernels) == 2
+    assert sum(k.startswith("deep_kernel<") for k in kernels) == 16
     import os, re
     src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "fractalrenderer_amd", "csrc",
                             "fr_device.hip")).read()
-    named = set(re.findall(r'"(deepx?_(?:de_)?kernel<\w+>)"', src))
-    assert named == set(dc.KERNELS.values()), named ^ set(dc.KERNELS.values())
+    alias = {a: (f, x == "true", de == "true")
+             for a, f, x, de in re.findall(r"using (\w+) = DeepBlock<(\w+)Formula, (true|false), (true|false)>;", src)}
+    assert set(re.findall(r"deep_entry<(\w+)>\(", src)) == set(alias) and len(alias) == 10
+    assert '"deep_kernel<"' in src and '", X"' in src and '", DE"' in src and '", BLA"' in src
+    named = {"deep_kernel<%s%s%s%s>" % (f, ", X" if x else "", ", DE" if de else "", ", BLA" if bla else "")
+             for f, x, de in alias.values() for bla in (False, True)}
+    assert len(named) == 20 and named - {k for k in named if k.startswith("deep_kernel<Julia") and ", DE" in k} == set(dc.KERNELS.values())
 
 
 # ---- 2. the restatements are ground truth across the bailout range ---------------------------------------------------------
@@ -458,7 +464,7 @@ def test_wrong_build_7_julia_tables_swapped():
 
 
 def test_wrong_build_8_the_de_blocks_shade_or_edge_dropped(oracle):
-    """DeepDeArgs / DeepXDeArgs with shade left 0 (rgba is fr_render_deep's), or with edge_px left 0 (de / 0: the smoothstep
+    """DeepDePart of a block with shade left 0 (rgba is fr_render_deep's), or with edge_px left 0 (de / 0: the smoothstep
     saturates and nothing is shaded either): every shaded colour case fails.  The old table rendered no DE kernel."""
     shaded = [cid for cid in dc.GROUPS_BY_ID["colour"] if dc.CASES[cid].params.get("shade")]
     assert len(shaded) == 32

@@ -1,4 +1,4 @@
-"""The store footprint of deep_kernel<DeepDeArgs> and deep_kernel<DeepDeBlaArgs> (fr_render_deep_de, plain and with
+"""The store footprint of deep_kernel<Mandel, DE> and deep_kernel<Mandel, DE, BLA> (fr_render_deep_de, plain and with
 FR_FLAG_DEEP_BLA): all five planes inside guard bands (tests/guarded.py) on frames whose edges are no sub-tile multiples and on
 one part of a 3-part sharding written in place -- no byte outside a payload is touched, no in-frame element stays unwritten,
 the rows of other parts stay as they were, and a plane that was not asked for is not written."""

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import deep_bla_ref as BR
+import deep_isa
 import deep_de_ref as D
 import deep_ref as R
 
@@ -261,7 +262,7 @@ def test_shading_restated():
 
 # ---- kernels -------------------------------------------------------------------------------------------------------
 # (VGPRs, SGPRs, scratch bytes per lane, waves per SIMD) of every deep_kernel and level kernel of the parent commit, read from
-# its build with -Rpass-analysis=kernel-resource-usage
+# its build with -Rpass-analysis=kernel-resource-usage, under the blocks' names at the time (deep_isa.OLD_NAMES)
 PARENT = {
     "DeepArgs": (83, 106, 0, 5), "DeepBlaArgs": (113, 106, 0, 4), "DeepXArgs": (96, 106, 0, 5), "DeepXBlaArgs": (127, 106, 0, 4),
     "DeepShipArgs": (89, 106, 0, 5), "DeepShipBlaArgs": (120, 106, 0, 4), "DeepShipXArgs": (101, 106, 0, 4),
@@ -272,30 +273,17 @@ PARENT = {
     "deepx_julia_bla_level_kernel": (42, 32, 0, 8),
 }
 # the new instantiations: at most this many VGPRs, at least this many waves per SIMD -- the occupancy of the kernel each one
-# extends (deep_kernel<DeepArgs> 5, deep_kernel<DeepBlaArgs> 4); measured 94 and 123 VGPRs
+# extends (DeepArgs 5, DeepBlaArgs 4); measured 94 and 123 VGPRs
 BUDGET = {"DeepDeArgs": (96, 5), "DeepDeBlaArgs": (128, 4)}
 
 
 def test_deep_kernels_keep_their_register_budget(fr):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
+    built = deep_isa.by_old_name()
+    if built is None:
         pytest.skip("hipcc not available")
-    csrc = os.path.join(ROOT, "fractalrenderer_amd", "csrc")
-    out = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
-                          "-I" + os.path.join(ROOT, "include"), "-I" + csrc, "-c", os.path.join(csrc, "fr_device.hip"),
-                          "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True)
-    assert out.returncode == 0, out.stderr[-2000:]
-    usage, cur = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            k = re.search(r"deep_kernelINS_\d+(\w+?)EEEvT_$", m.group(1)) or re.search(r"^_ZN2fr\d+(deepx?_\w*?level_kernel)E", m.group(1))
-            cur = usage.setdefault(k.group(1), {}) if k else None
-            continue
-        m = re.search(r"remark:\s+(VGPRs|TotalSGPRs|VGPRs Spill|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]): (\d+)", line)
-        if m and cur is not None:
-            cur[m.group(1)] = int(m.group(2))
-    assert set(usage) == set(PARENT) | set(BUDGET), sorted(set(usage) ^ (set(PARENT) | set(BUDGET)))
+    usage = {name: k.usage for name, k in built.items()}
+    # all twenty deep_kernel instantiations and the six level kernels, and nothing else
+    assert set(deep_isa.kernels()) == set(deep_isa.OLD_NAMES.values()) | deep_isa.LEVEL_KERNELS and len(usage) == 26
     for name, want in PARENT.items():
         u = usage[name]
         got = (u["VGPRs"], u["TotalSGPRs"], u["ScratchSize [bytes/lane]"], u["Occupancy [waves/SIMD]"])

@@ -1,4 +1,4 @@
-"""The store footprint of deep_kernel<DeepJuliaBlaArgs> and deep_kernel<DeepJuliaXBlaArgs> (fr_render_deep_julia with
+"""The store footprint of deep_kernel<Julia, BLA> and deep_kernel<Julia, X, BLA> (fr_render_deep_julia with
 FR_FLAG_DEEP_JULIA_BLA, fr_render_deepx_julia with FR_FLAG_DEEPX_JULIA_BLA) and of the table read-back: guard-banded planes
 (tests/guarded.py) around view PRECRIT60, whose samples step on both tables, at sizes from one pixel to several sub-tile rows
 with edges that are no sub-tile multiples -- (a) no byte outside the planes is touched, (b) no in-frame pixel stays unwritten,

@@ -1,5 +1,5 @@
-"""The store footprint of the four julia_de_kernel instantiations (fr_render_deep_julia_de and fr_render_deepx_julia_de, plain and
-with their BLA flags): all five planes inside guard bands (tests/guarded.py), deriv at no more than a double's alignment, on a
+"""The store footprint of the four deep_kernel<Julia, [X, ]DE[, BLA]> instantiations (fr_render_deep_julia_de and
+fr_render_deepx_julia_de, plain and with their BLA flags): all five planes inside guard bands (tests/guarded.py), deriv at no more than a double's alignment, on a
 frame whose edges are no sub-tile multiples and on one part of a 3-part sharding -- no byte outside a payload is touched, no
 in-frame element stays unwritten, the rows of other parts stay as they were, and a plane that was not asked for is not written."""
 import ctypes as C
@@ -17,7 +17,7 @@ pytestmark = pytest.mark.gpu
 W, H = 21, 13
 VIEW = {False: "DENDRITE30", True: "DENDRITE400"}      # the extended view starts extended and turns plain: both modes store
 KERNELS = [(False, False), (False, True), (True, False), (True, True)]
-IDS = ["DeepJuliaDeArgs", "DeepJuliaDeBlaArgs", "DeepJuliaXDeArgs", "DeepJuliaXDeBlaArgs"]
+IDS = ["DeepJuliaDeArgs", "DeepJuliaDeBlaArgs", "DeepJuliaXDeArgs", "DeepJuliaXDeBlaArgs"]     # the blocks' names at the time
 EACH = pytest.mark.parametrize("ext,bla", KERNELS, ids=IDS)
 
 

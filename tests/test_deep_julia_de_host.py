@@ -13,6 +13,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import deep_isa
 import deep_julia_bla_ref as JB
 import deep_julia_de_ref as JD
 import deep_julia_ref as J
@@ -344,7 +345,8 @@ def test_a_zero_derivative_gives_an_infinite_estimate():
 
 
 # ---- kernels -------------------------------------------------------------------------------------------------------
-# name -> (the kernel it extends, that kernel's VGPRs and waves per SIMD).  A 512-VGPR file in granules of 8 gives 5 waves up to
+# name -> (the kernel it extends, that kernel's VGPRs and waves per SIMD), under the blocks' names when these numbers were
+# recorded (deep_isa.OLD_NAMES).  A 512-VGPR file in granules of 8 gives 5 waves up to
 # 96 VGPRs, 4 up to 128 and 3 up to 168.  Measured: DeepJuliaDeArgs 95 VGPRs and 5 waves, DeepJuliaDeBlaArgs 127 and 4 (both keep
 # their parent's occupancy), DeepJuliaXDeArgs 105 and 4, DeepJuliaXDeBlaArgs 143 and 3 (a wave less, as fr_render_deepx_de's pair).
 # No scratch and no VGPR spill in any of them.
@@ -352,37 +354,11 @@ PARENT = {"DeepJuliaDeArgs": ("DeepJuliaArgs", 87, 5), "DeepJuliaDeBlaArgs": ("D
           "DeepJuliaXDeArgs": ("DeepJuliaXArgs", 93, 5), "DeepJuliaXDeBlaArgs": ("DeepJuliaXBlaArgs", 126, 4)}
 
 
-@functools.lru_cache(maxsize=None)
-def _resource_remarks(tmp):
-    """fr_device.hip compiled for gfx950, device side only: the compiler's resource remarks"""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        return None
-    csrc = os.path.join(ROOT, "fractalrenderer_amd", "csrc")
-    out = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
-                          "-I" + os.path.join(ROOT, "include"), "-I" + csrc, "--cuda-device-only", "-S",
-                          os.path.join(csrc, "fr_device.hip"), "-o", os.path.join(tmp, "fr_device.s"),
-                          "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True)
-    assert out.returncode == 0, out.stderr[-2000:]
-    return out.stderr
-
-
-def test_julia_de_kernels_keep_their_register_budget(fr, tmp_path_factory):
-    remarks = _resource_remarks(str(tmp_path_factory.mktemp("julia_de_isa")))
-    if remarks is None:
+def test_julia_de_kernels_keep_their_register_budget(fr):
+    built = deep_isa.by_old_name()
+    if built is None:
         pytest.skip("hipcc not available")
-    usage, cur = {}, None
-    for line in remarks.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            k = re.search(r"julia_de_kernelINS_\d+(\w+?)EEEvT_$", m.group(1)) or \
-                re.search(r"deep_kernelINS_\d+(DeepJuliaArgs|DeepJuliaBlaArgs|DeepJuliaXArgs|DeepJuliaXBlaArgs)EEEvT_$", m.group(1))
-            cur = usage.setdefault(k.group(1), {}) if k else None
-            continue
-        m = re.search(r"remark:\s+(VGPRs|VGPRs Spill|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]): (\d+)", line)
-        if m and cur is not None:
-            cur[m.group(1)] = int(m.group(2))
-    assert set(usage) == set(PARENT) | {v[0] for v in PARENT.values()}, sorted(usage)
+    usage = {name: k.usage for name, k in built.items()}
     for name, (parent, parent_vgprs, parent_occ) in PARENT.items():
         u, pu = usage[name], usage[parent]
         print(name, u, "extends", parent, pu)

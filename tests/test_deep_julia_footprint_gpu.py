@@ -1,4 +1,4 @@
-"""The store footprint of deep_kernel<DeepJuliaArgs> and deep_kernel<DeepJuliaXArgs> (fr_render_deep_julia,
+"""The store footprint of deep_kernel<Julia> and deep_kernel<Julia, X> (fr_render_deep_julia,
 fr_render_deepx_julia): guard-banded planes (tests/guarded.py) around view DENDRITE30 at sizes from one pixel to several
 sub-tile rows, edges that are no sub-tile multiples included -- (a) no byte outside the planes is touched, (b) no in-frame
 pixel stays unwritten, (c) what is written equals the numpy restatement -- for whole frames, for each plane alone, and for

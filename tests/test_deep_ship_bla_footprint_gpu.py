@@ -1,4 +1,4 @@
-"""The store footprint of deep_kernel<DeepShipBlaArgs> (fr_render_deep_ship with FR_FLAG_DEEP_SHIP_BLA): guard-banded planes
+"""The store footprint of deep_kernel<Ship, BLA> (fr_render_deep_ship with FR_FLAG_DEEP_SHIP_BLA): guard-banded planes
 (tests/guarded.py) around view SHIP_B at sizes from one pixel to several sub-tile rows, edges that are no sub-tile multiples
 included -- (a) no byte outside the planes is touched, (b) no in-frame pixel stays unwritten, (c) what is written equals the
 numpy restatement, the step counts included -- for whole frames and for one part of a 3-part sharding, packed and written in

@@ -1,4 +1,4 @@
-"""The store footprint of deep_kernel<DeepShipArgs> (fr_render_deep_ship): guard-banded planes (tests/guarded.py) around
+"""The store footprint of deep_kernel<Ship> (fr_render_deep_ship): guard-banded planes (tests/guarded.py) around
 view SHIP_A at sizes from one pixel to several sub-tile rows, edges that are no sub-tile multiples included -- (a) no byte
 outside the planes is touched, (b) no in-frame pixel stays unwritten, (c) what is written equals the numpy restatement --
 for whole frames, for each plane alone, and for one part of a 3-part sharding, packed and written in place into whole-frame

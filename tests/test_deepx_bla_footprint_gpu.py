@@ -1,4 +1,4 @@
-"""The store footprint of deep_kernel<DeepXBlaArgs> (fr_render_deepx with FR_FLAG_DEEPX_BLA): guard-banded planes
+"""The store footprint of deep_kernel<Mandel, X, BLA> (fr_render_deepx with FR_FLAG_DEEPX_BLA): guard-banded planes
 (tests/guarded.py) around view T320 at sizes from one pixel to several sub-tile rows -- (a) no byte outside the planes is
 touched, (b) no in-frame pixel stays unwritten, (c) what is written equals the numpy restatement -- for whole frames, and
 for one part of a 3-part sharding written in place into whole-frame planes, whose other rows stay untouched."""

@@ -1,4 +1,4 @@
-"""The store footprint of deepx_de_kernel<DeepXDeArgs> and deepx_de_kernel<DeepXDeBlaArgs> (fr_render_deepx_de, plain and
+"""The store footprint of deep_kernel<Mandel, X, DE> and deep_kernel<Mandel, X, DE, BLA> (fr_render_deepx_de, plain and
 with FR_FLAG_DEEPX_BLA): all five planes inside guard bands (tests/guarded.py), deriv at no more than a double's alignment, on
 frames whose edges are no sub-tile multiples and on one part of a 3-part sharding written in place -- no byte outside a payload
 is touched, no in-frame element stays unwritten, the rows of other parts stay as they were, and a plane that was not asked for

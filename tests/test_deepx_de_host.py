@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import deep_de_ref as D
+import deep_isa
 import deep_ref as R
 import deepx_bla_ref as XB
 import deepx_de_ref as XD
@@ -335,57 +336,27 @@ def test_de_stays_finite_where_deriv_saturates():
 
 
 # ---- kernels -------------------------------------------------------------------------------------------------------
+# The kernels go by their blocks' names at the time (deep_isa.OLD_NAMES: DeepXDeArgs is DeepBlock<MandelFormula, true, true>).
 # name -> (VGPRs at most, waves per SIMD at least, waves per SIMD of the kernel it extends, that kernel, SGPRs spilled at most).
 # A 512-VGPR file in granules of 8 gives 4 waves up to 128 VGPRs and 3 up to 168: one wave less than the kernel each one
-# extends (deep_kernel<DeepXArgs> 96 VGPRs and 5 waves, <DeepXBlaArgs> 127 and 4).  Measured: 106 VGPRs and 4 waves, 144 and 3.
+# extends (DeepXArgs 96 VGPRs and 5 waves, DeepXBlaArgs 127 and 4).  Measured: 106 VGPRs and 4 waves, 144 and 3.
 # No scratch and no VGPR spill.  SGPRs are another matter: every deep kernel sits at the cap of 106 SGPRs and parks kernel
 # arguments of its colour stage in VGPR lanes (v_writelane in the prologue, v_readlane where they are used) -- 76 of them in
-# deep_kernel<DeepXArgs>, 78 in <DeepXBlaArgs>.  The derivative's block adds nine scalars (sm, es, two plane pointers, shade,
+# DeepXArgs, 78 in DeepXBlaArgs.  The derivative's block adds nine scalars (sm, es, two plane pointers, shade,
 # edge_px) and the two new kernels park 84 and 87: that is the bound here, with at most nine more than the kernel each extends.
 # What matters for time is where they are read back: not inside the orbit loop (test below, on the ISA).
 BUDGET = {"DeepXDeArgs": (128, 4, 5, "DeepXArgs", 84), "DeepXDeBlaArgs": (168, 3, 4, "DeepXBlaArgs", 87)}
 SGPR_SPILL_OVER_PARENT = 9
 
 
-@functools.lru_cache(maxsize=None)
-def _device_build(tmp):
-    """fr_device.hip compiled for gfx950, device side only, to assembly: (the compiler's resource remarks, the assembly)"""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        return None
-    csrc = os.path.join(ROOT, "fractalrenderer_amd", "csrc")
-    asm = os.path.join(tmp, "fr_device.s")
-    out = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
-                          "-I" + os.path.join(ROOT, "include"), "-I" + csrc, "--cuda-device-only", "-S",
-                          os.path.join(csrc, "fr_device.hip"), "-o", asm, "-Rpass-analysis=kernel-resource-usage"],
-                         capture_output=True, text=True)
-    assert out.returncode == 0, out.stderr[-2000:]
-    return out.stderr, open(asm).read()
-
-
 @pytest.fixture(scope="module")
-def device_build(tmp_path_factory):
-    b = _device_build(str(tmp_path_factory.mktemp("deepx_de_isa")))
-    if b is None:
-        pytest.skip("hipcc not available")
-    return b
+def device_build():
+    return deep_isa.by_old_name() or pytest.skip("hipcc not available")
 
 
 def test_deepx_de_kernels_keep_their_register_budget(fr, device_build):
-    usage, cur = {}, None
-    for line in device_build[0].splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            k = re.search(r"deepx_de_kernelINS_\d+(\w+?)EEEvT_$", m.group(1)) or \
-                re.search(r"deep_kernelINS_\d+(DeepXArgs|DeepXBlaArgs)EEEvT_$", m.group(1))
-            cur = usage.setdefault(k.group(1), {}) if k else None
-            continue
-        m = re.search(r"remark:\s+(VGPRs|TotalSGPRs|VGPRs Spill|SGPRs Spill|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]): (\d+)", line)
-        if m and cur is not None:
-            cur[m.group(1)] = int(m.group(2))
-    assert set(usage) == set(BUDGET) | {v[3] for v in BUDGET.values()}, sorted(usage)
     for name, (max_vgpr, min_occ, parent_occ, parent, max_sspill) in BUDGET.items():
-        u, pu = usage[name], usage[parent]
+        u, pu = device_build[name].usage, device_build[parent].usage
         print(name, u, "extends", parent, pu)
         assert u["ScratchSize [bytes/lane]"] == 0 and u.get("VGPRs Spill", 0) == 0, (name, u)
         assert u["VGPRs"] <= max_vgpr and u["Occupancy [waves/SIMD]"] >= min_occ, (name, u)
@@ -418,12 +389,8 @@ def test_the_orbit_loop_reads_back_no_spilled_sgpr(device_build):
     both modes' steps and the derivative's -- has no v_readlane, no v_writelane and no scratch access.  The parked SGPRs are
     written once in the prologue and read back per sample, in the colour stage around the loop.  Measured: loops of 822 and
     1030 instructions with 96 and 113 fp64 multiplies, 47 and 60 v_ldexp_f64; 16 and 17 v_readlane per sample outside them."""
-    asm = device_build[1].split("\n")
     for name in BUDGET:
-        start = [i for i, line in enumerate(asm) if re.match(r"^_ZN2fr\d+deepx_de_kernelINS_\d+%sEEEvT_:" % name, line)]
-        assert len(start) == 1, name
-        end = next(i for i in range(start[0], len(asm)) if asm[i].startswith(".Lfunc_end"))
-        ins, loops = _loops(asm[start[0] + 1:end])
+        ins, loops = _loops(device_build[name].asm)
         count = lambda a, b, pat: sum(1 for t in ins[a:b + 1] if re.match(pat, t))
         mul = "v_mul_f64|v_fma_f64"
         most = max(count(a, b, mul) for a, b in loops)

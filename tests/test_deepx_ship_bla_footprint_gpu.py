@@ -1,4 +1,4 @@
-"""The store footprint of deep_kernel<DeepShipXBlaArgs> and of the table build (fr_render_deepx_ship with
+"""The store footprint of deep_kernel<Ship, X, BLA> and of the table build (fr_render_deepx_ship with
 FR_FLAG_DEEPX_SHIP_BLA): guard-banded planes (tests/guarded.py) around view S400 at sizes from one pixel to several sub-tile
 rows -- (a) no byte outside the planes is touched, (b) no in-frame pixel stays unwritten, (c) what is written equals the numpy
 restatement -- for whole frames, and for one part of a 3-part sharding written in place into whole-frame planes, whose other

@@ -1,4 +1,4 @@
-"""The store footprint of deep_kernel<DeepShipXArgs> (fr_render_deepx_ship): guard-banded planes (tests/guarded.py) around
+"""The store footprint of deep_kernel<Ship, X> (fr_render_deepx_ship): guard-banded planes (tests/guarded.py) around
 the tip view at 1e-400 at sizes from one pixel to several sub-tile rows, edges that are no sub-tile multiples included --
 (a) no byte outside the planes is touched, (b) no in-frame pixel stays unwritten, (c) what is written equals the numpy
 restatement -- for whole frames, for every subset of the planes, and for one part of a 3-part sharding, packed and written

@@ -298,6 +298,9 @@ INTERNAL_SIGNATURES = {
     "fr_plan_describe": (C.c_int, [_P(fr_params), C.c_uint32, C.c_uint32, _P(fr_shard), C.c_int, _P(C.c_char_p),
                                    _P(C.c_int64), C.c_int, _P(C.c_int64), C.c_int]),
     "fr_plan_fields": (C.c_char_p, []),
+    "fr_ctx_last_whole_blocks": (C.c_int, [C.c_void_p, _P(C.c_uint64)]),
+    "fr_plan_whole_blocks": (C.c_int, [_P(fr_params), C.c_uint32, C.c_uint32, _P(fr_shard), C.c_int, _P(C.c_char_p),
+                                       _P(C.c_int64), C.c_int, C.c_int]),
     "fr_node_set_tuning": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int64]),
     "fr_node_rccl_usable": (C.c_int, [C.c_void_p]),
     "fr_node_mapped_runtimes": (C.c_int, [C.c_char_p, C.c_size_t]),
@@ -316,7 +319,7 @@ PUBLIC_OPTIONS = ("periodicity", "staging", "shards", "tile_kernel", "timing", "
 TUNING_NAMES = ("workgroups_per_cu", "run_max", "run_min", "shift_bias", "stage_first", "pool_refill_at", "stream_run_max",
                 "stream_run_min", "stream_workgroups_per_cu", "probes", "stream_probes", "regions", "stream_rotate",
                 "tile_pixels", "tile_exit", "tile_exit_from", "prepare", "pool_items_per_wg", "subtile_shape", "debug_region_blocks", "debug_prologue_epoch", "ssaa", "ssaa_band_samples", "stripes",
-                "mandelbulb_split")
+                "mandelbulb_split", "whole_blocks")
 
 
 class FractalRendererError(RuntimeError):
@@ -394,3 +397,12 @@ def plan_describe(params: fr_params, width: int, height: int, shard: "fr_shard |
     check(L.fr_plan_describe(C.byref(params), width, height, C.byref(shard) if shard is not None else None, compute_units,
                              names, values, len(tunings), out, len(fields)))
     return dict(zip(fields, out))
+
+
+def plan_whole_blocks(params: fr_params, width: int, height: int, shard: "fr_shard | None" = None, compute_units: int = 256,
+                      tunings=(), pool_looks: bool = False) -> bool:
+    """Whether this render writes its survivor stream in two classes (fr_tuning.h: fr_plan_whole_blocks).  Needs no GPU."""
+    names = (C.c_char_p * max(len(tunings), 1))(*[n.encode() for n, _ in tunings])
+    values = (C.c_int64 * max(len(tunings), 1))(*[int(v) for _, v in tunings])
+    return bool(check(lib().fr_plan_whole_blocks(C.byref(params), width, height, C.byref(shard) if shard is not None else None,
+                                                 compute_units, names, values, len(tunings), int(pool_looks))))

@@ -28,7 +28,10 @@ using namespace fr;
 
 static constexpr int kMaxStages = 2;            /* tile pass (+ lane-pool pass) */
 static constexpr size_t kStageWords = (size_t)2 * kMaxShards * kShardStrideWords;   /* one stage: its queue heads, then its stream counters */
-static constexpr size_t kCtrlWords = (size_t)kMaxStages * kStageWords;
+/* behind the stages, in their layout: the second class of the survivor stream (WholeRef) -- its queue heads and block counters,
+ * then its two groups of read-out words; zeroed with the stages in front of every render that writes the class */
+static constexpr int kWholeStage = kMaxStages, kWholeStages = 2;
+static constexpr size_t kCtrlWords = (size_t)(kMaxStages + kWholeStages) * kStageWords;
 static constexpr size_t kReadyWord = kCtrlWords + (size_t)(kFeedbackShards + 1) * kShardStrideWords;   /* LaunchArgs::pro_ready */
 static constexpr size_t kFeedbackWord = kCtrlWords;            /* behind the stages: Feedback::dev_flag (kFeedbackShards words, 128 B apart) */
 static constexpr uint32_t kProbeEvery = 16;                     /* frames between two looks of a view that closed nothing */
@@ -105,6 +108,9 @@ struct fr_ctx {
     size_t orbit_cap;           /* capacity in scalars (2 per orbit point) */
     void* stream_buf;           /* survivor stream (tile pass -> lane pool) */
     size_t stream_bytes;
+    void* whole_buf;            /* its second class: whole blocks (WholeRef) */
+    size_t whole_bytes;
+    uint32_t last_whole_cap;    /* the most recent render wrote that class, in regions of this many blocks (0: it did not) */
     Tuning tune;                /* fr_ctx_set_tuning and the scheduling names of fr_ctx_set_option (fr_plan.h) */
     size_t diag_stride;         /* words between the diag regions of consecutive stages */
     int last_stages;
@@ -233,6 +239,7 @@ extern "C" void fr_ctx_destroy(fr_ctx* c)
     if (c->coord_buf) (void)hipFree(c->coord_buf);
     if (c->ssaa_buf) (void)hipFree(c->ssaa_buf);
     if (c->stream_buf) (void)hipFree(c->stream_buf);
+    if (c->whole_buf) (void)hipFree(c->whole_buf);
     if (c->frame_buf) (void)hipFree(c->frame_buf);
     if (c->orbit_host) (void)hipHostFree(c->orbit_host);
     if (c->orbit_dev) (void)hipFree(c->orbit_dev);
@@ -385,7 +392,10 @@ static hipError_t launch_tile(int shape, dim3 grid, hipStream_t s, const LaunchA
 template <typename T, int FRACTAL>
 static hipError_t launch_tile_lean(int np, dim3 grid, hipStream_t s, const LaunchArgs& a)
 {
-    if (np == 2) {
+    if (a.whole.base) {                          /* (staged, no cycle closing in the tile pass: plan_render) */
+        if (np == 2) hipLaunchKernelGGL((tile_lean_kernel<T, FRACTAL, false, 2 + kWholeTrips>), grid, dim3(kBlockThreads), 0, s, a);
+        else hipLaunchKernelGGL((tile_lean_kernel<T, FRACTAL, false, 1 + kWholeTrips>), grid, dim3(kBlockThreads), 0, s, a);
+    } else if (np == 2) {
         if (a.period_window)
             hipLaunchKernelGGL((tile_lean_kernel<T, FRACTAL, true, 2>), grid, dim3(kBlockThreads), 0, s, a);
         else
@@ -428,6 +438,8 @@ static hipError_t launch_stream_pool(dim3 grid, hipStream_t s, const LaunchArgs&
 {
     if (a.period_window)
         hipLaunchKernelGGL((pool_kernel<T, FRACTAL, true>), grid, dim3(kBlockThreads), 0, s, a);
+    else if (a.whole.base)                       /* the stream has two classes (plan_render: never with cycle closing) */
+        hipLaunchKernelGGL((pool_kernel<T, FRACTAL + kWholePool, false>), grid, dim3(kBlockThreads), 0, s, a);
     else
         hipLaunchKernelGGL((pool_kernel<T, FRACTAL, false>), grid, dim3(kBlockThreads), 0, s, a);
     return hipGetLastError();
@@ -525,9 +537,10 @@ static bool pool_wants_cycle_closing(fr_ctx* c, const fr_params* p, uint32_t W, 
 }
 
 /* zero the queue heads and stream counters of the next render (a kernel, not a memset node: see clear_words_kernel) */
-static hipError_t clear_control_block(fr_ctx* c, hipStream_t stream, int nstages)
+/* (whole: the words of the survivor stream's second class too -- they lie behind the last stage) */
+static hipError_t clear_control_block(fr_ctx* c, hipStream_t stream, int nstages, bool whole = false)
 {
-    const uint32_t n = (uint32_t)((size_t)nstages * kStageWords);
+    const uint32_t n = (uint32_t)((size_t)(whole ? kWholeStage + kWholeStages : nstages) * kStageWords);
     hipLaunchKernelGGL(clear_words_kernel, dim3((n + 4 * kBlockThreads - 1) / (4 * kBlockThreads)), dim3(kBlockThreads), 0, stream, c->d_ctrl, n,
                        feedback_of(c));
     return hipGetLastError();
@@ -1338,12 +1351,13 @@ static void fill_geometry(LaunchArgs& a, fr_ctx* c, const fr_params* p, uint32_t
 
 /* In front of the tile pass: the begin event, then a zeroed control block (and, for the lean kernels, their coordinate
  * tables) by one of three means. */
-static int begin_frame(fr_ctx* c, const RenderPlan& plan, int nstages, const fr_params* p, LaunchArgs& a, hipStream_t stream)
+static int begin_frame(fr_ctx* c, const RenderPlan& plan, int nstages, bool whole, const fr_params* p, LaunchArgs& a, hipStream_t stream)
 {
-    const uint32_t ctrl_words = (uint32_t)((size_t)nstages * kStageWords);
+    /* (a render that writes whole blocks clears their words too: they lie behind the last stage) */
+    const uint32_t ctrl_words = (uint32_t)((size_t)(whole ? kWholeStage + kWholeStages : nstages) * kStageWords);
     /* the frame's device time (fr_ctx_last_kernel_ms) includes the small launch that prepares it */
     if (c->timing) FR_HIP_TRY(hipEventRecord(c->ev_begin, stream));
-    if (!plan.lean()) { FR_HIP_TRY(clear_control_block(c, stream, nstages)); return FR_OK; }
+    if (!plan.lean()) { FR_HIP_TRY(clear_control_block(c, stream, nstages, whole)); return FR_OK; }
     a.xs = c->coord_buf;
     a.yds = (uint8_t*)c->coord_buf + (size_t)a.W * (plan.f64 ? sizeof(double) : sizeof(float));
     /* the lean tile pass prepares its own control block and coordinate tables (lean_prologue: its first workgroups, the others
@@ -1393,6 +1407,15 @@ static int launch_tile_pass(fr_ctx* c, const RenderPlan& plan, const fr_params* 
         a.out.region_blocks = plan.region_blocks;
         a.out.rotate = plan.rotate_regions;
         a.out.nregions = plan.nregions;
+    }
+    memset(&a.whole, 0, sizeof(a.whole));
+    c->last_whole_cap = 0;
+    if (plan.whole_blocks_apply(pool_looks)) {                  /* the pool pass reads the same description */
+        a.whole.base = (uint8_t*)c->whole_buf;
+        a.whole.heads = stage_heads(c, kWholeStage);
+        a.whole.n_blocks = stage_counter(c, kWholeStage);
+        a.whole.stats = stage_heads(c, kWholeStage + 1);
+        a.whole.region_blocks = c->last_whole_cap = plan.whole_region_blocks;
     }
     a.diag = c->diag;
     a.period_window = plan.tile_period_window;
@@ -1461,6 +1484,7 @@ static int enqueue_render(fr_ctx* c, const fr_params* p, uint32_t W, uint32_t H,
     a.rgba = reinterpret_cast<float4*>(rgba); a.nu = nu; a.iter = iter;
     c->last_grid = plan.grid; c->last_pool_closing = -1;
     int st = grow_device(&c->stream_buf, &c->stream_bytes, plan.stream_bytes);      /* the context scratch the plan needs */
+    if (st == FR_OK) st = grow_device(&c->whole_buf, &c->whole_bytes, plan.whole_bytes);
     if (st == FR_OK) st = grow_device(&c->coord_buf, &c->coord_bytes, plan.coord_bytes);
     if (st != FR_OK || reserve_only) return st;
 
@@ -1469,7 +1493,7 @@ static int enqueue_render(fr_ctx* c, const fr_params* p, uint32_t W, uint32_t H,
     const bool pool_looks = plan.pool_may_look && pool_wants_cycle_closing(c, p, W, rows_local);
     const int nstages = plan.staged() && !pool_looks ? plan.nstages_all : plan.nstages;   /* (2 either way but for a forced schedule
                                                      with max_iter < 2 b0 of the pool that runs everything: 1, though both passes run) */
-    if ((st = begin_frame(c, plan, nstages, p, a, stream)) != FR_OK) return st;
+    if ((st = begin_frame(c, plan, nstages, plan.whole_blocks_apply(pool_looks), p, a, stream)) != FR_OK) return st;
     if ((st = launch_tile_pass(c, plan, p, a, pool_looks, stream)) != FR_OK) return st;
     if (plan.staged() && (st = launch_pool_pass(c, plan, p, a, pool_looks, stream)) != FR_OK) return st;
     return finish_render(c, stream, nstages);
@@ -1683,40 +1707,78 @@ constexpr int kPlanFieldCount = 44;
 
 extern "C" const char* fr_plan_fields(void) { return kPlanFields; }
 
+/* the automatic choices with n names of fr_ctx_set_tuning / fr_ctx_set_option applied in order */
+static int tunings_from(Tuning& tune, const char* const* names, const int64_t* values, int n)
+{
+    memset(&tune, 0, sizeof(tune));
+    for (int i = 0; i < n; ++i) {
+        int st = tuning_set(tune, names[i], values[i]);
+        if (st == kNotMine) st = option_set(tune, names[i], values[i]);
+        if (st == kNotMine) return fr_set_error(FR_ERR_INVALID_ARG, "unknown tuning name '%s'", names[i]);
+        if (st != FR_OK) return st;
+    }
+    return FR_OK;
+}
+
+/* The plan of the render that runs the kernels of a request: the request's own, or -- staged and banded SSAA -- the sample
+ * grid's (of the first band, the largest), as enqueue_ssaa_staged makes it.  W, H, norm and rows_local become that render's;
+ * *outer receives the request's own plan (route, nbands, band_rows). */
+static int plan_of_kernels(const Tuning& tune, int compute_units, const fr_params* p, uint32_t& W, uint32_t& H, fr_shard& norm,
+                           uint32_t& rows_local, RenderPlan* outer, RenderPlan* r)
+{
+    *r = *outer = plan_render(tune, compute_units, p, W, H, norm, rows_local, 0);
+    if (outer->route != kRouteSsaaStaged && outer->route != kRouteSsaaBanded) return FR_OK;
+    const fr_shard band = {0, outer->nbands, outer->band_rows};
+    if (outer->route == kRouteSsaaBanded) { norm = band; rows_local = fr_shard_rows(&band, H); }
+    const uint32_t aa = (uint32_t)p->antialiasing_samples;
+    const fr_shard grid_shard = {norm.part, norm.nparts, norm.rows_per_strip * aa};
+    fr_params q = *p;
+    q.antialiasing_samples = 1;
+    W *= aa; H *= aa;
+    const int gs = normalise_shard(&grid_shard, H, &norm, &rows_local);
+    if (gs != FR_OK) return gs;
+    *r = plan_render(tune, compute_units, &q, W, H, norm, rows_local, p->antialiasing_samples);
+    if (!r->lean()) return fr_set_error(FR_ERR_INTERNAL, "staged SSAA reached a render the lean tile kernel does not serve");
+    return FR_OK;
+}
+
+/* fr_tuning.h: does the render of this request (of its sample grid, where SSAA is staged) write the survivor stream in two classes? */
+extern "C" int fr_plan_whole_blocks(const fr_params* p, uint32_t W, uint32_t H, const fr_shard* shard, int compute_units,
+                                    const char* const* names, const int64_t* values, int n_tunings, int pool_looks)
+{
+    if (!p || (n_tunings > 0 && (!names || !values))) return fr_set_error(FR_ERR_INVALID_ARG, "fr_plan_whole_blocks: NULL argument");
+    Tuning tune;
+    const int ts = tunings_from(tune, names, values, n_tunings);
+    if (ts != FR_OK) return ts;
+    fr_shard norm;
+    uint32_t rows_local = 0;
+    const int sh = normalise_shard(shard, H, &norm, &rows_local);
+    if (sh != FR_OK || rows_local == 0) return sh;
+    RenderPlan outer, r;
+    const int st = plan_of_kernels(tune, compute_units, p, W, H, norm, rows_local, &outer, &r);
+    if (st != FR_OK) return st;
+    if (outer.route == kRouteDeepZoom) return 0;
+    return r.whole_blocks_apply(r.pool_may_look && pool_looks != 0) ? 1 : 0;
+}
+
 extern "C" int fr_plan_describe(const fr_params* p, uint32_t W, uint32_t H, const fr_shard* shard, int compute_units,
                                 const char* const* names, const int64_t* values, int n_tunings, int64_t* out, int n_out)
 {
     if (!p || !out || (n_tunings > 0 && (!names || !values))) return fr_set_error(FR_ERR_INVALID_ARG, "fr_plan_describe: NULL argument");
     if (n_out != kPlanFieldCount) return fr_set_error(FR_ERR_INVALID_ARG, "fr_plan_describe: the record has %d fields", kPlanFieldCount);
     Tuning tune;
-    memset(&tune, 0, sizeof(tune));
-    for (int i = 0; i < n_tunings; ++i) {
-        int st = tuning_set(tune, names[i], values[i]);
-        if (st == kNotMine) st = option_set(tune, names[i], values[i]);
-        if (st == kNotMine) return fr_set_error(FR_ERR_INVALID_ARG, "unknown tuning name '%s'", names[i]);
-        if (st != FR_OK) return st;
-    }
+    const int ts = tunings_from(tune, names, values, n_tunings);
+    if (ts != FR_OK) return ts;
     memset(out, 0, sizeof(int64_t) * kPlanFieldCount);
     fr_shard norm;
     uint32_t rows_local = 0;
     const int sh = normalise_shard(shard, H, &norm, &rows_local);
     if (sh != FR_OK || rows_local == 0) return sh;
-    RenderPlan r = plan_render(tune, compute_units, p, W, H, norm, rows_local, 0);
-    const int route = r.route;
-    const uint32_t nbands = r.nbands, band_rows = r.band_rows;
-    fr_params q = *p;
-    if (route == kRouteSsaaStaged || route == kRouteSsaaBanded) {
-        const fr_shard band = {0, nbands, band_rows};
-        if (route == kRouteSsaaBanded) { norm = band; rows_local = fr_shard_rows(&band, H); }
-        const uint32_t aa = (uint32_t)p->antialiasing_samples;      /* the sample grid, as enqueue_ssaa_staged makes it */
-        const fr_shard grid_shard = {norm.part, norm.nparts, norm.rows_per_strip * aa};
-        q.antialiasing_samples = 1;
-        W *= aa; H *= aa;
-        const int gs = normalise_shard(&grid_shard, H, &norm, &rows_local);
-        if (gs != FR_OK) return gs;
-        r = plan_render(tune, compute_units, &q, W, H, norm, rows_local, p->antialiasing_samples);
-        if (!r.lean()) return fr_set_error(FR_ERR_INTERNAL, "staged SSAA reached a render the lean tile kernel does not serve");
-    }
+    RenderPlan outer, r;
+    const int st = plan_of_kernels(tune, compute_units, p, W, H, norm, rows_local, &outer, &r);
+    if (st != FR_OK) return st;
+    const int route = outer.route;
+    const uint32_t nbands = outer.nbands, band_rows = outer.band_rows;
     int64_t* o = out;
     *o++ = route; *o++ = nbands; *o++ = band_rows;
     if (route == kRouteDeepZoom) return FR_OK;
@@ -1846,6 +1908,30 @@ extern "C" int fr_ctx_synchronize(fr_ctx* c)
 
 /* fr_tuning.h: 1 / 0 = the lane pool of the most recent render looked / did not look for cycles, -1 = it had no lane pool */
 extern "C" int fr_ctx_last_pool_closing(const fr_ctx* c) { return c ? c->last_pool_closing : -1; }
+
+/* fr_tuning.h: the two classes of the most recent render's survivor stream, read from its control words (waits for it) */
+extern "C" int fr_ctx_last_whole_blocks(fr_ctx* c, uint64_t out[3])
+{
+    if (!c || !out) return fr_set_error(FR_ERR_INVALID_ARG, "ctx/out is NULL");
+    out[0] = out[1] = out[2] = 0;
+    if (!c->have_render || c->last_whole_cap == 0u) return FR_OK;     /* one class: nothing was counted */
+    FR_HIP_TRY(hipSetDevice(c->device));
+    FR_HIP_TRY(hipStreamSynchronize(c->last_stream));
+    const size_t bytes = (size_t)kWholeStages * kStageWords * sizeof(uint32_t);
+    uint32_t* const words = (uint32_t*)malloc(bytes);
+    if (!words) return fr_set_error(FR_ERR_NOMEM, "fr_ctx_last_whole_blocks: out of host memory");
+    const hipError_t e = hipMemcpy(words, stage_heads(c, kWholeStage), bytes, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) { free(words); return fr_set_error(FR_ERR_HIP, "fr_ctx_last_whole_blocks: %s", hipGetErrorString(e)); }
+    const size_t group = (size_t)kMaxShards * kShardStrideWords;
+    for (int r = 0; r < kMaxShards; ++r) {
+        const uint32_t n = words[group + (size_t)r * kShardStrideWords];             /* claims past the cap wrote nothing */
+        out[0] += n < c->last_whole_cap ? n : c->last_whole_cap;
+        out[1] += words[2 * group + (size_t)r * kShardStrideWords];
+        out[2] += words[3 * group + (size_t)r * kShardStrideWords];
+    }
+    free(words);
+    return FR_OK;
+}
 
 extern "C" void* fr_ctx_stream_handle(fr_ctx* c) { return c ? (void*)c->stream : nullptr; }
 extern "C" int fr_ctx_device(const fr_ctx* c) { return c ? c->device : -1; }

@@ -87,6 +87,20 @@ struct StreamRef {
                                   * block are lost and the render is reported as failed, never silently incomplete */
 };
 
+/* The second class of the survivor stream: WHOLE blocks.  A trip of the staged lean tile pass whose samples are all still
+ * running at b0 writes them as blocks of 64 records, lane l's sample in slot l, straight from its registers (no LDS ring);
+ * the lane pool runs such a block in a loop of its own (pool_kernel, "whole blocks").  Same block layout and region count as
+ * the stream it rides beside (StreamRef), its own buffer, counters and queue heads. */
+struct WholeRef {
+    uint8_t* base;               /* nregions regions of region_blocks blocks each; nullptr: this render keeps ONE class */
+    uint32_t* n_blocks;          /* per region, kShardStrideWords apart: blocks claimed by the tile pass (claims past
+                                  * region_blocks wrote nothing: readers cap the count) */
+    uint32_t* heads;             /* per region: the lane pool's queue head */
+    uint32_t* stats;             /* per region: whole blocks the pool found dirty; kMaxShards slots further on: records the
+                                  * tile pass sent through the ring (fr_ctx_last_whole_blocks) */
+    uint32_t region_blocks;      /* a multiple of 2: a trip claims its NP blocks with one atomic */
+};
+
 /* Queue geometry of one launch. */
 struct QueueArgs {
     uint32_t* heads;             /* kShards words, kShardStrideWords apart, zeroed per render */
@@ -171,6 +185,7 @@ struct LaunchArgs {
     uint32_t* pro_fb_flag;
     uint32_t* pro_fb_host;
     fr_palette_table pal;
+    WholeRef whole;              /* (behind everything else: the offsets of the fields above are those of a build without it) */
 };
 
 /* The kernel arguments, re-read where they are used.  Everything a persistent kernel reads from its argument block is
@@ -1960,10 +1975,15 @@ struct LeanWriter {
 /* NP = 1: one 8x8 sub-tile per trip.  NP = 2: two horizontally adjacent ones (a 16x8 patch, lane (lx, ly) holds the
  * pixels (lx, ly) and (lx + 8, ly)); a trip whose second sub-tile does not exist (odd run, end of a row) runs with those
  * samples switched off like lanes outside the frame. */
-template <typename T, int FRACTAL, bool PERIOD, int NP>
+/* TRIP: the sub-tiles of a trip, 1 or 2; kWholeTrips more: the same, and the trips that lost no sample write the survivor
+ * stream's second class (WholeRef).  (One parameter for both, so that the instantiations without the class keep the names
+ * and the code they had before there was one.) */
+constexpr int kWholeTrips = 2;
+template <typename T, int FRACTAL, bool PERIOD, int TRIP>
 __global__ void __launch_bounds__(kBlockThreads)
 tile_lean_kernel(const LaunchArgs A)
 {
+    constexpr int NP = TRIP > kWholeTrips ? TRIP - kWholeTrips : TRIP;
     constexpr int NF = RecFields<FRACTAL>::n;
     constexpr bool ABS = Form<FRACTAL>::abs_step;
     constexpr bool STRIPES = FRACTAL == 3;                    /* Mandelbrot + stripe shading: see shade_stripes */
@@ -2001,6 +2021,10 @@ tile_lean_kernel(const LaunchArgs A)
     writer.init();
     LeanQueue q;
     q.init();
+    constexpr bool WHOLE = TRIP > kWholeTrips;
+    static_assert(!WHOLE || (!PERIOD && !STRIPES), "whole blocks are read by the plain lane pool alone");
+    uint32_t whole_home = writer.home;                       /* region the next whole trip writes to */
+    (void)whole_home;
 
     uint64_t diag_t0 = 0;
     uint32_t diag_items = 0, diag_claims = 0;
@@ -2098,7 +2122,37 @@ tile_lean_kernel(const LaunchArgs A)
                     need_any = need_any || __builtin_amdgcn_ballot_w64(need[p]) != 0ull;
                 }
                 hint_fast = !lost;
-                if (staged) {
+                /* WHOLE BLOCKS.  A full trip that ran to i1 and lost no sample (no bit in any done mask: every sample
+                 * inside the frame, none escaped) hands its NP x 64 records over as NP blocks of the stream's second class,
+                 * lane l's record in slot l: straight from the registers, one atomic for the block indices, no ring.  A
+                 * region of that class that is full sends the trip through the ring like any other. */
+                bool whole_trip = false;
+                if constexpr (WHOLE) {
+                    KArgs K = kargs();
+                    uint64_t any_done = 0ull;
+#pragma unroll
+                    for (int p = 0; p < NP; ++p) any_done |= done[p];
+                    if (staged && K->whole.base != nullptr && np == (uint32_t)NP && i_end == i1 && any_done == 0ull) {
+                        uint32_t v = 0;
+                        if (lane == 0) v = atomicAdd(&K->whole.n_blocks[whole_home * kShardStrideWords], (uint32_t)NP);
+                        const uint32_t blk = __builtin_amdgcn_readfirstlane(v);
+                        if (blk + (uint32_t)NP <= K->whole.region_blocks) {
+                            whole_trip = true;
+#pragma unroll
+                            for (int p = 0; p < NP; ++p) {
+                                uint8_t* b = K->whole.base + ((size_t)whole_home * K->whole.region_blocks + blk + (uint32_t)p) * RingWriter<T, NF>::kBlockBytes;
+                                reinterpret_cast<uint32_t*>(b)[lane] = pixel[p];
+                                reinterpret_cast<uint32_t*>(b)[64 + lane] = (uint32_t)i_end;
+                                T* fields = reinterpret_cast<T*>(b + RingWriter<T, NF>::kHeaderBytes);
+                                const T rec4[4] = {o[p].X, o[p].Yd, o[p].cx, o[p].cyd};
+#pragma unroll
+                                for (int k = 0; k < NF; ++k) fields[k * 64 + lane] = rec4[k];
+                            }
+                        }
+                        if (K->out.rotate) whole_home = (whole_home + 1u) & (K->out.nregions - 1u);
+                    }
+                }
+                if (staged && !whole_trip) {
 #pragma unroll
                     for (int p = 0; p < NP; ++p) {
                         const T rec4[4] = {o[p].X, o[p].Yd, o[p].cx, o[p].cyd};
@@ -2142,6 +2196,11 @@ tile_lean_kernel(const LaunchArgs A)
         }
     }
     if (staged) writer.finish(ring, lane);
+    if constexpr (WHOLE) {               /* read-out (fr_ctx_last_whole_blocks): records this wave sent through the ring */
+        KArgs K = kargs();
+        if (staged && K->whole.base != nullptr && writer.tail != 0u && lane == 0)
+            atomicAdd(&K->whole.stats[((size_t)kMaxShards + writer.home) * kShardStrideWords], writer.tail);
+    }
     {
         KArgs K = kargs();
         if (K->diag && lane == 0) {      /* diagnostics: per-wave timeline (100 MHz ticks) and work counts */
@@ -2231,6 +2290,29 @@ __device__ __forceinline__ void shade_and_store(const LdsBlock& S, const LogTab<
     if (K->iter) K->iter[pix] = it;
 }
 
+/* ... of a sample that never escaped, where that is known for the whole wave (no stripes): what shade_and_store makes of
+ * it = max_iter -- nu = max_iter and the colour `final_rgb` (stage_interior_final) -- without the colour stage around it */
+template <typename T>
+__device__ __forceinline__ void store_interior(const float (&final_rgb)[3], const uint32_t pix, const int max_iter)
+{
+    KArgs K = kargs();
+    if (K->rgba) K->rgba[pix] = make_float4(final_rgb[0], final_rgb[1], final_rgb[2], 1.0f);
+    if (K->nu) reinterpret_cast<T*>(K->nu)[pix] = (T)max_iter;
+    if (K->iter) K->iter[pix] = max_iter;
+}
+/* the colour shade_and_store writes for such a sample: the interior colour (stage_interior), through the post chain if the render
+ * asks for it.  The same for every such sample: thread 0, once per workgroup */
+template <int FR>
+__device__ __forceinline__ void stage_interior_final(const LdsBlock& S, const LaunchArgs& A, float (&final_rgb)[3])
+{
+    if (threadIdx.x == 0) {
+        float rgb[3] = {S.interior_rgb[0], S.interior_rgb[1], S.interior_rgb[2]};
+        if (A.flags & FR_FLAG_POST_CHAIN) post_chain(rgb, S.brightness, S.saturation, S.contrast, FR != 0);
+        final_rgb[0] = rgb[0]; final_rgb[1] = rgb[1]; final_rgb[2] = rgb[2];
+    }
+    __syncthreads();
+}
+
 /* diagnostic build (-DFR_STAMP): the records must have arrived before the clock is read: touch them */
 template <typename T>
 __device__ __forceinline__ void stamp_await_records(const Orbit<T>& o)
@@ -2258,6 +2340,40 @@ __device__ __forceinline__ void watchdog_dump(const LaunchArgs& A, const uint32_
         }
     }
 #endif
+}
+
+/* The queue of the survivor stream's second class (WholeRef): one whole block per claim.  Its shards are the class's regions
+ * (lengths written by the tile pass), probed in WaveQueue's order and under the launch's probe limit, so every region is
+ * somebody's home.  All a wave keeps between claims is `state`: bits 0-7 the shard it is at, bits 8-15 the shards it has found
+ * dry, kWholeDry once it has given up (every wave reaches that: heads only grow). */
+constexpr uint32_t kWholeDry = 0x80000000u;
+constexpr uint32_t kWholeReserve = 0x40000000u;      /* lane pool: the ring's class is dry, the reserve is a block of this class */
+__device__ __forceinline__ bool whole_claim(const uint32_t lane, uint32_t& state, uint32_t& shard, uint32_t& blk)
+{
+    for (;;) {
+        const uint32_t sh = state & 0xFFu;
+        {
+            KArgs K = kargs();
+            uint32_t len = K->whole.n_blocks[sh * kShardStrideWords];
+            len = len < K->whole.region_blocks ? len : K->whole.region_blocks;  /* claims past the capacity wrote nothing */
+            if (len != 0u) {                                                   /* (an empty region costs no atomic) */
+                uint32_t v = 0;
+                if (lane == 0) v = atomicAdd(&K->whole.heads[sh * kShardStrideWords], 1u);
+                const uint32_t b = __builtin_amdgcn_readfirstlane(v);
+                __builtin_amdgcn_s_waitcnt(0x0F70);                            /* (see WaveQueue::next) */
+                if (b < len) { shard = sh; blk = b; return true; }
+            }
+        }
+        /* this shard is dry: the next one, in WaveQueue::advance's order, or none */
+        cold_path();
+        KArgs K = kargs();
+        const uint32_t ns = 1u << K->q.ns_log2;
+        const uint32_t p = (K->q.flags >> kQueueProbeShift) & 0xFu;
+        const uint32_t tried = ((state >> 8) & 0xFFu) + 1u;
+        if (tried >= ((p != 0u && p < ns) ? p : ns)) { state = kWholeDry; return false; }
+        uint32_t nx = ns > (uint32_t)kShards ? sh + (uint32_t)kShards + ((tried & 7u) == 0u ? 1u : 0u) : sh + 1u;
+        state = (nx & (ns - 1u)) | (tried << 8);
+    }
 }
 
 /* what one lane of the pool holds: its sample, and the result it waits to have shaded and stored */
@@ -2297,11 +2413,16 @@ struct PoolLane {
     }
     /* refill: record l of block j of region `shard` of the survivor stream (an empty slot of the block leaves the lane
      * idle).  Returns whether the lane has a sample now */
+    /* (CLASSES: `whole` says that the block is one of the stream's second class, WholeRef -- same layout, its own buffer) */
+    template <bool CLASSES = false>
     __device__ __forceinline__ bool load_record(const LdsBlock& S, const uint32_t shard, const uint32_t j, const uint32_t l,
-                                                const uint32_t wclock, const int max_iter)
+                                                const uint32_t wclock, const int max_iter, const bool whole = false)
     {
         KArgs K = kargs();
         const uint8_t* b = K->in.base + ((size_t)shard * K->in.region_blocks + j) * RingWriter<T, NF>::kBlockBytes;
+        if constexpr (CLASSES) {
+            if (whole) b = K->whole.base + ((size_t)shard * K->whole.region_blocks + j) * RingWriter<T, NF>::kBlockBytes;
+        }
         const T* fields = reinterpret_cast<const T*>(b + RingWriter<T, NF>::kHeaderBytes);
         const uint32_t pix = reinterpret_cast<const uint32_t*>(b)[l];
         if (pix == kInvalidPixel) return false;
@@ -2319,7 +2440,12 @@ struct PoolLane {
 /* Lanes are refilled with survivor records of the tile pass (A.in) and run the remaining iterations [A.i0, max_iter).
  * (A fresh-pixel form of this kernel -- lanes refilled straight from the pixel index, no tile pass -- was the first lane
  * pool; it lost to tile pass + pool on every workload and left the product in round 3: DESIGN.md section 7.) */
-template <typename T, int FRACTAL, bool PERIOD = false>
+/* KIND: the kernel code of the fractal (0 Mandelbrot, 1 Julia, 2 Burning Ship, 3 Mandelbrot with stripe shading); kWholePool
+ * more: the same, for a survivor stream in two classes -- the whole-block loop in front, and a refill that knows of the second
+ * class.  (One parameter for both, as the tile kernel's TRIP: the instantiations for one class keep the names and the code they
+ * had before there was a second.) */
+constexpr int kWholePool = 8;
+template <typename T, int KIND, bool PERIOD = false>
 __global__ void __launch_bounds__(kBlockThreads)
 /* VGPRs are handed out in granules of 16 on gfx950 (measured in round 3: a 68-VGPR fp64 instantiation ran 6 workgroups per
  * CU, not the 7 its count suggests).  Round 3 held the plain fp64 instantiation at 64 (8 waves per SIMD; +-0 to -2 %); with
@@ -2327,6 +2453,7 @@ __global__ void __launch_bounds__(kBlockThreads)
  * the same (profiles/r04_pool_deferred_escapes.txt). */
 pool_kernel(const LaunchArgs A)
 {
+    constexpr int FRACTAL = KIND >= kWholePool ? KIND - kWholePool : KIND;
     constexpr int NF = RecFields<FRACTAL>::n;
     constexpr bool STRIPES = FRACTAL == 3;                /* Mandelbrot + stripe shading (shade_stripes): a finished lane keeps the
                                                            * z of its last update, and no lane runs past its deadline */
@@ -2362,6 +2489,18 @@ pool_kernel(const LaunchArgs A)
     uint32_t diag_items = 0, diag_claims = 0, diag_dry = 0;
     if (A.diag) diag_t0 = __builtin_amdgcn_s_memrealtime();
 
+    /* whole blocks (below): the instantiations that run them, and all that a wave carries for them through the lane pool, in
+     * one word (a VGPR: the lane pool's scalars fill the scalar file) -- bits 0-7 the shard of the class's queue the wave is
+     * at, bits 8-15 the shards it has found dry, bit 31 "the class is dry", bit 30 "the lane pool's reserve comes from it" (q is the
+     * ring class's queue) */
+    constexpr bool WHOLE = KIND >= kWholePool;
+    static_assert(!WHOLE || (!PERIOD && !STRIPES), "whole blocks: the plain lane pool alone");
+    __shared__ float interior_final[3];  /* what a whole block that stays clean stores for its pixels */
+    if constexpr (WHOLE) stage_interior_final<FR>(S, A, interior_final);
+    uint32_t whole_state = kWholeDry;
+    if constexpr (WHOLE) {
+        if (kargs()->whole.base != nullptr) { LeanQueue qw; qw.init(); whole_state = qw.shard; }
+    }
     PoolLane<T, FRACTAL> L;
     L.init();
     Orbit<T>& o = L.o;
@@ -2390,6 +2529,93 @@ pool_kernel(const LaunchArgs A)
     bool dry = false, fast = fast_ok;    /* a dirty stretch costs a ring entry per escaped lane: no reason to start tested */
 
     FR_STAMP_DECL
+    /* ---- WHOLE BLOCKS (the stream's second class, WholeRef) ---------------------------------------------------------------
+     * 64 records that left the tile pass together: the same updates behind them, the same number still to run, and on the
+     * views that matter almost none of them ever escapes (C2: 94 % of the survivors come this way, 99 % of those blocks stay
+     * interior to the end).  Such a block needs nothing of the lane machinery below -- no deadline, no retire / refill round,
+     * no overrun of a stretch past a deadline, no half-empty last generation.  The wave claims a block, runs EXACTLY the updates
+     * it has left in unchecked stretches (lengths by the clean run's streak rule, capped at what is left; the last < 16 as
+     * single steps, tested once behind them) and, if every stretch came out clean, stores the interior result for its 64
+     * pixels -- what shade_and_store makes of a lane that reach_deadline finished -- and claims again.  A DIRTY stretch is the way
+     * back: z goes back to the stretch's start, the 64 samples become running lanes with the deadline the clock gives them, and
+     * the lane pool below takes over, finding the escapes exactly as it always has (it runs that stretch again).  A wave that
+     * finds the class dry enters the lane pool empty and serves the ring's class.  Nobody comes back here: a lane pool whose
+     * ring class has run dry refills from the whole blocks that are left, as the records they are (the refill below) -- so a
+     * view whose whole blocks all turn dirty (a deep view: every sample alive at b0, most escaping later) runs them the lane
+     * pool's way, refilled lane by lane, after one block per wave.
+     * Whole blocks FIRST: they are the coarse items (a block is ~max_iter - b0 updates of a full wave, a C2 wave runs ~7), the
+     * ring's records are the fine ones that level the end of the pass.
+     * Bounded: every loop counts down `left`, or claims from a queue that only shrinks; nothing waits on another wave.
+     * Same operations on the same values in the same order per sample: only where they run changes. */
+    if constexpr (WHOLE) {
+        for (;;) {
+            uint32_t ws = (uint32_t)__builtin_amdgcn_readfirstlane((int)whole_state);
+            if (ws & kWholeDry) break;
+            uint32_t wb, wshard;
+            const bool got = whole_claim(lane, ws, wshard, wb);
+            whole_state = ws;
+            if (!got) break;
+            ++diag_claims;
+            ++diag_items;
+            uint32_t left;
+            {
+                KArgs K = kargs();
+                const uint8_t* b = K->whole.base + ((size_t)wshard * K->whole.region_blocks + wb) * RingWriter<T, NF>::kBlockBytes;
+                const T* fields = reinterpret_cast<const T*>(b + RingWriter<T, NF>::kHeaderBytes);
+                L.pixel = reinterpret_cast<const uint32_t*>(b)[lane];
+                /* (a whole block's records have all run the same updates: lane 0's count is the block's) */
+                left = (uint32_t)K->max_iter - (uint32_t)__builtin_amdgcn_readfirstlane((int)reinterpret_cast<const uint32_t*>(b)[64 + lane]);
+                o.X = fields[lane]; o.Yd = fields[64 + lane];
+                if constexpr (Form<FRACTAL>::per_sample_c) { o.cx = fields[128 + lane]; o.cyd = fields[192 + lane]; }
+                else { o.cx = (T)S.julia_cx; o.cyd = T(2) * (T)S.julia_cy; }
+                o.x2 = o.X * o.X; o.y2d = o.Yd * o.Yd;
+            }
+            /* `left` counts down by clean stretches: 0 = the block ran all its updates and nobody escaped */
+            T sX = o.X, sYd = o.Yd;                                  /* z at the start of the current stretch */
+            if (kargs()->fast_ok != 0) {                             /* (escape not absorbing: every update is tested, below) */
+                uint32_t wstreak = 0;
+                while (left >= (uint32_t)kFastBlock) {
+                    sX = o.X; sYd = o.Yd;
+                    uint32_t reps = wstreak >= 6u ? 4u : (wstreak >= 2u ? 2u : 1u);
+                    if (reps > (left >> 4)) reps = left >> 4;
+                    /* the stretch's blocks two to a trip (most stretches of a long run are four blocks), an odd one in front */
+                    if (reps & 1u) {
+#pragma unroll
+                        for (int k = 0; k < kFastBlock; ++k) orbit_step<T, Form<FRACTAL>::abs_step>(o);
+                    }
+                    for (uint32_t pair = reps >> 1; pair != 0u; --pair) {
+#pragma unroll
+                        for (int k = 0; k < 2 * kFastBlock; ++k) orbit_step<T, Form<FRACTAL>::abs_step>(o);
+                    }
+                    if (__builtin_amdgcn_ballot_w64(!(orbit_r2x4(o) <= B2x4)) != 0ull) break;
+                    ++wstreak;
+                    left -= reps * (uint32_t)kFastBlock;
+                }
+                if (left != 0u && left < (uint32_t)kFastBlock) {
+                    sX = o.X; sYd = o.Yd;
+                    for (uint32_t r = left; r != 0u; --r) orbit_step<T, Form<FRACTAL>::abs_step>(o);
+                    if (__builtin_amdgcn_ballot_w64(!(orbit_r2x4(o) <= B2x4)) == 0ull) left = 0u;
+                }
+            }
+            if (left == 0u) {
+                /* not escaped after exactly max_iter updates: interior, all 64 */
+                store_interior<T>(interior_final, L.pixel, kargs()->max_iter);
+                L.pixel = kInvalidPixel;                             /* the lane is free */
+                o.park();
+                continue;
+            }
+            /* the way back into the lane pool: 64 running lanes at the stretch's start, `left` updates to their deadline */
+            o.X = sX; o.Yd = sYd;
+            o.x2 = o.X * o.X; o.y2d = o.Yd * o.Yd;
+            L.fin = 0u;
+            L.deadline = wclock + left;
+            next_deadline = L.deadline;
+            have_running = true;
+            if (lane == 0)                                           /* read-out: dirty blocks (counted at the wave's shard) */
+                atomicAdd(&kargs()->whole.stats[(size_t)((uint32_t)__builtin_amdgcn_readfirstlane((int)whole_state) & 0xFFu) * kShardStrideWords], 1u);
+            break;
+        }
+    }
     for (;;) {
         /* ---- deferred escapes: 64 queued (or the wave is leaving) -> one tested replay at full occupancy ---- */
         while (dtail - dhead >= 64u || (finishing && dtail != dhead)) {
@@ -2458,7 +2684,22 @@ pool_kernel(const LaunchArgs A)
             const uint64_t freem = __builtin_amdgcn_ballot_w64(L.idle());
             if (freem == 0ull || dry) break;
             if (res_next == res_count * 64u) {
-                if (!FR_STAMP_TIMED(0, q.next<true>(lane, res_begin, res_count, res_shard))) {
+                if constexpr (WHOLE) {
+                    /* once the ring's class is dry, whole blocks that are left (this wave came here with a dirty one, or found
+                     * the class dry only for its own shards' sake) are records like any others: one block per claim */
+                    uint32_t ws = (uint32_t)__builtin_amdgcn_readfirstlane((int)whole_state);
+                    bool got = !(ws & kWholeReserve) && FR_STAMP_TIMED(0, q.next<true>(lane, res_begin, res_count, res_shard));
+                    if (!got) {
+                        got = !(ws & kWholeDry) && whole_claim(lane, ws, res_shard, res_begin);
+                        whole_state = ws | kWholeReserve;
+                        res_count = 1u;
+                    }
+                    if (!got) {
+                        dry = true;
+                        diag_dry = A.diag ? (uint32_t)(__builtin_amdgcn_s_memrealtime() - diag_t0) : 0u;
+                        break;
+                    }
+                } else if (!FR_STAMP_TIMED(0, q.next<true>(lane, res_begin, res_count, res_shard))) {
                     dry = true;
                     /* diagnostics: when this wave found the queue dry, in 100 MHz ticks since its start (bits 32..) */
                     diag_dry = A.diag ? (uint32_t)(__builtin_amdgcn_s_memrealtime() - diag_t0) : 0u;
@@ -2475,7 +2716,9 @@ pool_kernel(const LaunchArgs A)
                 const uint32_t rank = lane_rank(freem);
                 if (rank < n) {
                     const uint32_t t = res_next + rank;
-                    if (L.load_record(S, res_shard, res_begin + (t >> 6), t & 63u, wclock, max_iter)) {
+                    bool from_whole = false;
+                    if constexpr (WHOLE) from_whole = (whole_state & kWholeReserve) != 0u;
+                    if (L.template load_record<WHOLE>(S, res_shard, res_begin + (t >> 6), t & 63u, wclock, max_iter, from_whole)) {
                         if constexpr (PERIOD) { refX = __builtin_nan(""); refYd = refX; cyc = 0u; }
                     }
                 }

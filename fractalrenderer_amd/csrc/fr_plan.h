@@ -46,6 +46,8 @@ struct Tuning {
     uint32_t tile_exit_from;    /* ... and the updates a trip runs before it may leave (0 = automatic) */
     uint32_t prepare;           /* 0 = automatic (the tile pass prepares its own control block and tables, except on a capturing
                                    stream), 1 = prepare_kernel in a launch of its own */
+    uint32_t whole_blocks;      /* survivor stream in two classes (whole blocks beside the ring's records): 0 = automatic (plan_render: large
+                                   fp64 frames), 1 = off, 2 = on wherever whole_blocks_apply */
     uint32_t mandelbulb_split;  /* 0 = automatic (march / shade split), 1 = shade at the hit, inside the march loop */
     uint32_t debug_region_blocks; /* tests only: cap the capacity of a survivor-stream region, to provoke an overflow */
 };
@@ -74,6 +76,7 @@ static const TuningRow kTuningRows[] = {
     {"stripes", &Tuning::stripes, 1, {}, "stripes must be 0 (automatic) or 1 (Mandelbrot effects by the effects variant of the general tile kernel)"},
     {"ssaa_band_samples", &Tuning::ssaa_band, 1ll << 30, {}, "ssaa_band_samples must be 0 (automatic: 2^29) or up to 2^30"},
     {"pool_items_per_wg", &Tuning::pool_items_per_wg, 4096, {}, "pool_items_per_wg must be in [0,4096]"},
+    {"whole_blocks", &Tuning::whole_blocks, 2, {}, "whole_blocks must be 0 (automatic), 1 (off) or 2 (on wherever the lane pool has the loop for them)"},
     {"mandelbulb_split", &Tuning::mandelbulb_split, 1, {}, "mandelbulb_split must be 0 (automatic: march / shade split) or 1 (shade inside the march loop)"},
     {"debug_region_blocks", &Tuning::debug_region_blocks, -1, {}, ""},   /* tests only (overflow reporting); 0 = the real capacity */
 };
@@ -288,6 +291,8 @@ inline int plan_stages(const Tuning& t, const fr_params* p, bool effects, size_t
  * trip runs before it may leave */
 constexpr uint32_t kTileExitCost = 48u, kTileExitFrom = 32u;
 
+constexpr uint32_t kWholeBlocksPerWave = 16u;     /* automatic "whole_blocks": blocks of the frame per lane-pool wave, at least */
+
 enum Route { kRouteDirect = 1, kRouteDeepZoom, kRouteSsaaStaged, kRouteSsaaBanded };
 enum Family { kGeneral, kGeneralEffects, kGeneralSampleLoop, kLean, kLeanStripes };
 
@@ -301,6 +306,12 @@ struct RenderPlan {
     uint32_t wg_per_cu, grid, sgrid;   /* resident workgroups per CU of the tile kernel; workgroups of the tile pass / the lane-pool pass */
     uint32_t nregions, rotate_regions, region_blocks;   /* survivor stream: regions, blocks per region */
     size_t stream_bytes, coord_bytes;   /* the survivor stream; the coordinate tables of the lean kernels */
+    /* the stream's second class (WholeRef, fr_kernels.hip.h): whether this render may write one -- whole_blocks_apply() has the
+     * last word, it knows what the pool does -- and its buffer: every record goes to exactly one class, so the whole blocks
+     * of a frame are at most its pixels / 64; a region that is full sends its trips through the ring, which holds them all */
+    bool whole_may;
+    uint32_t whole_region_blocks;
+    size_t whole_bytes;
     bool f64, bounded, moderate;
     /* b0 and what follows from it, [0] for a pool that runs every survivor to max_iter, [1] for a pool that looks for cycles.
      * Whether it looks is the context's to say (pool_wants_cycle_closing, stateful), and only where pool_may_look. */
@@ -313,6 +324,12 @@ struct RenderPlan {
     bool staged() const { return nstages > 1; }
     bool lean() const { return family == kLean || family == kLeanStripes; }
     bool stripes() const { return family == kLeanStripes; }
+    /* Whole blocks are written and read by the instantiations that hold the clean run -- the staged lean tile pass in front
+     * of a lane pool that neither looks for cycles (pool_looks) nor shades stripes -- and by those alone: the others have no
+     * loop that reads the class.  Row-strip shards and the sample grid of a staged SSAA frame are renders like any other here:
+     * a record carries its pixel's place in the planes, and the conditions of a whole trip (full, inside the frame) are the
+     * trip's own. */
+    bool whole_blocks_apply(bool pool_looks) const { return whole_may && !pool_looks; }
 };
 
 inline RenderPlan plan_render(const Tuning& t, int compute_units, const fr_params* p, uint32_t W, uint32_t H, const fr_shard& norm,
@@ -425,6 +442,18 @@ inline RenderPlan plan_render(const Tuning& t, int compute_units, const fr_param
     r.region_blocks = (worst_blocks * 3u / 2u + r.nregions - 1) / r.nregions + 1u;
     r.stream_bytes = (size_t)r.region_blocks * r.nregions * block_bytes;
     if (t.debug_region_blocks && t.debug_region_blocks < r.region_blocks) r.region_blocks = t.debug_region_blocks;
+    /* Automatic: where it was measured to pay and never to cost (profiles/pool_whole_blocks.txt) -- fp64 frames with at least
+     * kWholeBlocksPerWave blocks of 64 pixels per wave of the pool's grid.  A whole block is a coarse item: its wave runs all the
+     * updates it has left before it claims again, so a frame that gives a wave only a block or two ends on a few waves that
+     * hold one more than the others (1080p at max_iter 1024: 8 blocks of frame per wave, +37 %; 3840 x 2160: 21, -4.5 %;
+     * C2: 42, -2.5 %); fp32 views were measured on the C3 dust alone (+1.9 %) and stay with one class. */
+    const bool whole_auto = f64 && (npx + 63) / 64 >= (size_t)kWholeBlocksPerWave * r.sgrid * 4u;
+    r.whole_may = lean && !stripes && (t.whole_blocks == 2u || (t.whole_blocks == 0u && whole_auto));
+    if (r.whole_may) {
+        r.whole_region_blocks = (((uint32_t)((npx + 63) / 64) + r.nregions - 1) / r.nregions + 3u) & ~1u;   /* even: claims are pairs */
+        r.whole_bytes = (size_t)r.whole_region_blocks * r.nregions * block_bytes;
+        if (t.debug_region_blocks && t.debug_region_blocks < r.whole_region_blocks) r.whole_region_blocks = t.debug_region_blocks & ~1u;
+    }
     if (lean && t.tile_exit != 1u) {
         r.exit_cost = t.tile_exit ? t.tile_exit : kTileExitCost;
         for (int k = 0; k < 2; ++k) {

@@ -36,6 +36,10 @@
  *   "stripes"            the Mandelbrot shader's effects (stripe shading, orbit trap, trap-coloured interior): 0 = automatic (lean tile
  *                        pass + lane pool in their code-3 instantiations), 1 = the effects variant of the general tile kernel (tests
  *                        compare the two bitwise)
+ *   "whole_blocks"       survivor stream in two classes: a full trip of the staged lean tile pass that lost no sample writes its
+ *                        records as whole blocks, which the lane pool runs in a loop of its own (fr_kernels.hip.h, WholeRef).
+ *                        0 = automatic, 1 = off (one class, as before), 2 = on; whatever the value, only where the lane pool neither
+ *                        looks for cycles nor shades stripes (tests compare on and off bitwise)
  *   "mandelbulb_split"   Mandelbulb: 0 = automatic (the wave marches until no lane is marching, then the lanes that hit shade
  *                        together), 1 = each lane shades at its hit, inside the march loop (tests compare the two bitwise)
  *   "ssaa_band_samples"  staged SSAA of a whole frame: sample grids larger than this go through the scratch in bands of whole
@@ -59,6 +63,18 @@ int fr_ctx_set_tuning(fr_ctx* ctx, const char* name, int64_t value);
  * a context whose pools closed nothing skips the looking for a while, fr_device.hip pool_wants_cycle_closing); -1: that
  * render had no lane pool */
 int fr_ctx_last_pool_closing(const fr_ctx* ctx);
+
+/* The two classes of the survivor stream of the context's most recent render (waits for it): out[0] whole blocks the tile
+ * pass wrote, out[1] those of them that a wave's whole-block loop found dirty (some sample escaped: the block went the lane
+ * pool's way from there, and so did every whole block the same wave took afterwards, as plain records, uncounted: at most one
+ * per pool wave), out[2] records that the tile pass sent through the ring.  All zero where the render kept one class. */
+int fr_ctx_last_whole_blocks(fr_ctx* ctx, uint64_t out[3]);
+
+/* 1 / 0: the render of this request -- of its sample grid where SSAA is staged or banded, as fr_plan_describe reports it; not
+ * Deep_Zoom -- writes / does not write its survivor stream in two classes, given whether its lane pool looks for cycles
+ * (pool_looks; the context decides that per render).  Arguments as fr_plan_describe's; no context, no device. */
+int fr_plan_whole_blocks(const fr_params* params, uint32_t width, uint32_t height, const fr_shard* shard, int compute_units,
+                         const char* const* names, const int64_t* values, int n_tunings, int pool_looks);
 
 /* The schedule of a render as a flat record of integers (fr_plan.h: plan_render), decided from the request, a compute-unit
  * count and tunings alone: no context, no device.  names / values: n_tunings fr_ctx_set_tuning names (and the scheduling

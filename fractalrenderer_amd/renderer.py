@@ -170,6 +170,13 @@ class Renderer:
         """internal (fr_tuning.h): 1 / 0 = the lane pool of the most recent render looked / did not look for cycles, -1 = none"""
         return int(self._lib.fr_ctx_last_pool_closing(self._ctx))
 
+    def last_whole_blocks(self) -> tuple[int, int, int]:
+        """internal (fr_tuning.h): of the most recent render's survivor stream (waits for it) -- whole blocks written, whole
+        blocks that turned dirty in the lane pool, records that went through the ring; zeros where it kept one class"""
+        out = (C.c_uint64 * 3)()
+        _capi.check(self._lib.fr_ctx_last_whole_blocks(self._ctx, out))
+        return int(out[0]), int(out[1]), int(out[2])
+
     # -- plane plumbing ------------------------------------------------------------------
     @staticmethod
     def _ptr(x, want_dtype: str, nelem: int, what: str):

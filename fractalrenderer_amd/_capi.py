@@ -215,6 +215,16 @@ SIGNATURES = {
                                            _P(fr_shard), _P(fr_output)]),
     "fr_render_deepx_julia_de_async": (C.c_int, [C.c_void_p, _P(fr_params), _P(fr_deepx_view), _P(fr_deep_de), C.c_uint32,
                                                  C.c_uint32, _P(fr_shard), _P(fr_output), C.c_void_p]),
+    "fr_deep_ship_de_validate": (C.c_int, [_P(fr_params), _P(fr_deep_view), _P(fr_deep_de), C.c_uint32, C.c_uint32]),
+    "fr_deepx_ship_de_validate": (C.c_int, [_P(fr_params), _P(fr_deepx_view), _P(fr_deep_de), C.c_uint32, C.c_uint32]),
+    "fr_render_deep_ship_de": (C.c_int, [C.c_void_p, _P(fr_params), _P(fr_deep_view), _P(fr_deep_de), C.c_uint32, C.c_uint32,
+                                         _P(fr_shard), _P(fr_output)]),
+    "fr_render_deep_ship_de_async": (C.c_int, [C.c_void_p, _P(fr_params), _P(fr_deep_view), _P(fr_deep_de), C.c_uint32,
+                                               C.c_uint32, _P(fr_shard), _P(fr_output), C.c_void_p]),
+    "fr_render_deepx_ship_de": (C.c_int, [C.c_void_p, _P(fr_params), _P(fr_deepx_view), _P(fr_deep_de), C.c_uint32, C.c_uint32,
+                                          _P(fr_shard), _P(fr_output)]),
+    "fr_render_deepx_ship_de_async": (C.c_int, [C.c_void_p, _P(fr_params), _P(fr_deepx_view), _P(fr_deep_de), C.c_uint32,
+                                                C.c_uint32, _P(fr_shard), _P(fr_output), C.c_void_p]),
     "fr_deep_ship_sequence_create": (C.c_int, [C.c_void_p, _P(fr_params), _P(fr_deep_sequence_desc), C.c_uint32, C.c_uint32,
                                                _P(C.c_void_p)]),
     "fr_deep_sequence_plan": (C.c_int, [_P(fr_deep_sequence_desc), C.c_int32, _P(fr_deep_sequence_frame)]),

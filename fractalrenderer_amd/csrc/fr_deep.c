@@ -820,6 +820,20 @@ int fr_deepx_julia_de_validate(const fr_params* p, const fr_deepx_view* v, const
     return st != FR_OK ? st : check_de_block(e);
 }
 
+int fr_deep_ship_de_validate(const fr_params* p, const fr_deep_view* v, const fr_deep_de* e, uint32_t width, uint32_t height)
+{
+    if (!e) return fr_set_error(FR_ERR_INVALID_ARG, "fr_deep_de is NULL");
+    const int st = fr_deep_ship_validate(p, v, width, height);
+    return st != FR_OK ? st : check_de_block(e);
+}
+
+int fr_deepx_ship_de_validate(const fr_params* p, const fr_deepx_view* v, const fr_deep_de* e, uint32_t width, uint32_t height)
+{
+    if (!e) return fr_set_error(FR_ERR_INVALID_ARG, "fr_deep_de is NULL");
+    const int st = fr_deepx_ship_validate(p, v, width, height);
+    return st != FR_OK ? st : check_de_block(e);
+}
+
 /* ---- the reference orbits -----------------------------------------------------------------------------------------------------
  * What the six entry points ask before they iterate, in this order: the out pointers (have_out), max_iter, the zoom (the entry's
  * double; NULL for an extended entry, whose view carries a string), the bailout, Julia's c (julia_c, NULL elsewhere), then

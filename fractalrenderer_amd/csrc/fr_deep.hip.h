@@ -64,6 +64,13 @@
  *     without a dc term (kHasB == false).  D = dz_n/dz_0 * s starts at s, not at 0; an update is one complex product,
  *     D' = 2 z D or D' = A D, and nothing is added (the overloads of deep_step_d, deep_step_xd, deep_step_pd and deepx_d_set
  *     without s); the extended D is flushed to the zero below 2^-2^27 as the delta is.  Four and five live VGPRs.
+ *   - the distance estimate of ship views (fr_render_deep_ship_de, fr_render_deepx_ship_de): the option DE for a formula with
+ *     kRealJacobian.  The ship's map is not conformal, so the derivative is a real 2x2 matrix J = dz/dc * s (Jac; XJac: four
+ *     mantissas, one int32 exponent, norm4 after every update): J' = L J + s I in a single step, L the derivative of
+ *     (|x| + i |y|)^2 at the sample's point (ship_lj), J' = A J + B s in a BLA step, nothing in a rebase.  An escaping lane keeps
+ *     z in its dz registers, and the kernel turns (J, z) into the gradient of |z|, g = J^T z / |z|, which deep_de_of takes as D.
+ *     Eight and nine live VGPRs.  The four kernels are instantiations of deep_ship_de_kernel, a __global__ template of their
+ *     own around the same body.
  */
 #pragma once
 #include "fr_kernels.hip.h"
@@ -167,7 +174,7 @@ template <bool X>
 struct DeepDePart : std::conditional_t<X, DeepXSpacing, DeepSpacing> {
     double* de;                          /* distance estimate of sample (0,0), in pixel spacings */
     double* deriv;                       /* (D.x, D.y) of sample (0,0) at its escaping update: two doubles per pixel, a caller's
-                                          * plane with no more than a double's alignment */
+                                          * plane with no more than a double's alignment; the ship: (J11, J12, J21, J22), four */
     int32_t shade;                       /* 1: the debug shader's distance shading on every escaped sub-sample */
     float edge_px;                       /* ... its smoothstep's upper edge, in pixel spacings */
 };
@@ -322,6 +329,66 @@ __device__ __forceinline__ void deepx_d_set(XDeriv& D, const double px, const do
     asm volatile("" : "+v"(D.x), "+v"(D.y), "+v"(D.e));
 }
 
+/* fr_render_deep_ship_de: the ship's map is not conformal, so its derivative is a real 2x2 matrix,
+ * J = [[dx/dcx, dx/dcy], [dy/dcx, dy/dcy]] * s, carried by rows; z is the sample's point at its escaping update, which the
+ * loops hand back in the escaped lane's dz */
+struct Jac {
+    double2 r1, r2;                      /* (J11, J12), (J21, J22) */
+    double2 z;
+};
+
+/* fr_render_deepx_ship_de: J as four mantissas and one shared int32 exponent, normalised with norm4 after every update */
+struct XJac {
+    double2 r1, r2;
+    int e;
+    double2 z;                           /* plain doubles: |z| > bailout there */
+};
+
+/* deep_pin_d for the four entries of J */
+__device__ __forceinline__ void deep_pin_j(double2& r1, double2& r2)
+{
+    asm volatile("" : "+v"(r1.x), "+v"(r1.y), "+v"(r2.x), "+v"(r2.y));
+}
+
+/* J' = norm4(p (+) q) of the header: the rows p1, p2 at ep the step's linear part applied to J, q1, q2 at eq its dc term applied
+ * to s */
+__device__ __forceinline__ void deepx_j_set(XJac& J, const double2 p1, const double2 p2, const int ep, const double2 q1,
+                                            const double2 q2, const int eq)
+{
+    const int e = ep > eq ? ep : eq;
+    J.r1 = make_double2(__builtin_ldexp(p1.x, ep - e) + __builtin_ldexp(q1.x, eq - e),
+                        __builtin_ldexp(p1.y, ep - e) + __builtin_ldexp(q1.y, eq - e));
+    J.r2 = make_double2(__builtin_ldexp(p2.x, ep - e) + __builtin_ldexp(q2.x, eq - e),
+                        __builtin_ldexp(p2.y, ep - e) + __builtin_ldexp(q2.y, eq - e));
+    J.e = e;
+    x_norm4(J.r1, J.r2, J.e);
+    asm volatile("" : "+v"(J.r1.x), "+v"(J.r1.y), "+v"(J.r2.x), "+v"(J.r2.y), "+v"(J.e));
+}
+
+/* ... with q = (sm I, es), a single step's: nothing is added off the diagonal */
+__device__ __forceinline__ void deepx_j_set(XJac& J, const double2 p1, const double2 p2, const int ep, const double sm,
+                                            const int es)
+{
+    const int e = ep > es ? ep : es;
+    const double q = __builtin_ldexp(sm, es - e);
+    J.r1 = make_double2(__builtin_ldexp(p1.x, ep - e) + q, __builtin_ldexp(p1.y, ep - e));
+    J.r2 = make_double2(__builtin_ldexp(p2.x, ep - e), __builtin_ldexp(p2.y, ep - e) + q);
+    J.e = e;
+    x_norm4(J.r1, J.r2, J.e);
+    asm volatile("" : "+v"(J.r1.x), "+v"(J.r1.y), "+v"(J.r2.x), "+v"(J.r2.y), "+v"(J.e));
+}
+
+/* L J of the ship at the point (x, y), doubling apart: L = [[x, -y], [|y| sgn sx, |x| sgn sy]], sgn v = v >= 0 ? 1 : -1; (sx, sy)
+ * carries the signs of the point's coordinates ((x, y) itself in fp64) */
+__device__ __forceinline__ void ship_lj(const double x, const double y, const double sx, const double sy, const double2 j1,
+                                        const double2 j2, double2& p1, double2& p2)
+{
+    const double l12 = -y;
+    const double l21 = sx >= 0.0 ? fabs(y) : -fabs(y), l22 = sy >= 0.0 ? fabs(x) : -fabs(x);
+    p1 = make_double2(x * j1.x + l12 * j2.x, x * j1.y + l12 * j2.y);
+    p2 = make_double2(l21 * j1.x + l22 * j2.x, l21 * j1.y + l22 * j2.y);
+}
+
 /* ---- the formula policies ------------------------------------------------------------------------------------------------
  * What a policy hands to the shared code, all by value (small structs in registers). */
 struct StepLin { double tx, ty, fx, fy; };          /* the plain step: dz' = t * f + dc, a complex product */
@@ -348,6 +415,7 @@ struct MandelFormula {
     static constexpr bool kLogBailoutLds = false;
     static constexpr bool kTwoOrbits = false;         /* one orbit from 0, a dc term in every step */
     static constexpr bool kHasB = true;
+    static constexpr bool kRealJacobian = false;      /* conformal: the derivative is a complex number */
     static constexpr int kAbPerEntry = 2;             /* complex A, B */
     using Lin = BlaLin<1>;
     using LinX = BlaLinX<1>;
@@ -452,6 +520,7 @@ struct ShipFormula {
     static constexpr bool kLogBailoutLds = true;      /* shade<double, 2> at bailout <= 1 */
     static constexpr bool kTwoOrbits = false;
     static constexpr bool kHasB = true;
+    static constexpr bool kRealJacobian = true;       /* the derivative is a real 2x2 matrix (Jac, XJac) */
     static constexpr int kAbPerEntry = 4;             /* the rows (a11, a12), (a21, a22), (b11, b12), (b21, b22) */
     using Lin = BlaLin<2>;
     using LinX = BlaLinX<2>;
@@ -475,11 +544,35 @@ struct ShipFormula {
         const double2 a1 = T.ab[4 * e], a2 = T.ab[4 * e + 1], b1 = T.ab[4 * e + 2], b2 = T.ab[4 * e + 3];
         return make_double2((a1.x * dzx + a1.y * dzy) + (b1.x * dcx + b1.y * dcy), (a2.x * dzx + a2.y * dzy) + (b2.x * dcx + b2.y * dcy));
     }
+    /* bla() with the derivative of the map it applies, from the one load of (A, B): J' = A J + B s, real 2x2 products */
+    static __device__ __forceinline__ double2 bla_d(const BlaTable& T, const uint32_t e, const double dzx, const double dzy,
+                                                    const double dcx, const double dcy, const double s, Jac& J)
+    {
+        const double2 a1 = T.ab[4 * e], a2 = T.ab[4 * e + 1], b1 = T.ab[4 * e + 2], b2 = T.ab[4 * e + 3];
+        const double2 j1 = J.r1, j2 = J.r2;
+        J.r1 = make_double2((a1.x * j1.x + a1.y * j2.x) + b1.x * s, (a1.x * j1.y + a1.y * j2.y) + b1.y * s);
+        J.r2 = make_double2((a2.x * j1.x + a2.y * j2.x) + b2.x * s, (a2.x * j1.y + a2.y * j2.y) + b2.y * s);
+        deep_pin_j(J.r1, J.r2);
+        return make_double2((a1.x * dzx + a1.y * dzy) + (b1.x * dcx + b1.y * dcy), (a2.x * dzx + a2.y * dzy) + (b2.x * dcx + b2.y * dcy));
+    }
     static __device__ __forceinline__ BlaStepX bla_x(const BlaXTable& T, const uint32_t e, const double qx, const double qy,
                                                      const double cx, const double cy)
     {
         const double2 a1 = T.ab[4 * e], a2 = T.ab[4 * e + 1], b1 = T.ab[4 * e + 2], b2 = T.ab[4 * e + 3];
         const int2 ee = T.abe[e];
+        return {a1.x * qx + a1.y * qy, a2.x * qx + a2.y * qy, b1.x * cx + b1.y * cy, b2.x * cx + b2.y * cy, ee.x, ee.y};
+    }
+    /* bla_x() with the derivative of the map it applies, from the one load of the entry:
+     * J' = norm4((A J, A.e + J.e) (+) (B sm, B.e + es)) */
+    static __device__ __forceinline__ BlaStepX bla_x_d(const BlaXTable& T, const uint32_t e, const double qx, const double qy,
+                                                       const double cx, const double cy, const double sm, const int es, XJac& J)
+    {
+        const double2 a1 = T.ab[4 * e], a2 = T.ab[4 * e + 1], b1 = T.ab[4 * e + 2], b2 = T.ab[4 * e + 3];
+        const int2 ee = T.abe[e];
+        const double2 j1 = J.r1, j2 = J.r2;
+        deepx_j_set(J, make_double2(a1.x * j1.x + a1.y * j2.x, a1.x * j1.y + a1.y * j2.y),
+                    make_double2(a2.x * j1.x + a2.y * j2.x, a2.x * j1.y + a2.y * j2.y), ee.x + J.e,
+                    make_double2(b1.x * sm, b1.y * sm), make_double2(b2.x * sm, b2.y * sm), ee.y + es);
         return {a1.x * qx + a1.y * qy, a2.x * qx + a2.y * qy, b1.x * cx + b1.y * cy, b2.x * cx + b2.y * cy, ee.x, ee.y};
     }
     /* the map of tile_kernel's Burning Ship path, less the centre (burning_ship.comp:337-344: sx outer) */
@@ -579,6 +672,7 @@ struct JuliaFormula {
     static constexpr bool kLogBailoutLds = true;      /* shade<double, 1> at bailout <= 1 */
     static constexpr bool kTwoOrbits = true;
     static constexpr bool kHasB = false;              /* no dc term: an entry is (r, A) */
+    static constexpr bool kRealJacobian = false;
     static constexpr int kAbPerEntry = 1;             /* complex A */
     using Lin = BlaLin<1>;                            /* b stays unused */
     using LinX = BlaLinX<1>;
@@ -673,6 +767,19 @@ __device__ __forceinline__ void deep_step_d(const double Zx, const double Zy, co
     deep_pin_d(D);
 }
 
+/* The ship's (fr_render_deep_ship_de): L = [[w.x, -w.y], [|w.y| sgn x, |w.x| sgn y]] at the same point (x, y) = Z_m + dz, the
+ * derivative of (|x| + i |y|)^2 on the piece the sample's own orbit is on; J' = L J + s I, s added behind each diagonal sum */
+__device__ __forceinline__ void deep_step_d(const double Zx, const double Zy, const double dzx, const double dzy, const double s,
+                                            Jac& J)
+{
+    const double x = Zx + dzx, y = Zy + dzy;
+    double2 p1, p2;
+    ship_lj(x + x, y + y, x, y, J.r1, J.r2, p1, p2);
+    J.r1 = make_double2(p1.x + s, p1.y);
+    J.r2 = make_double2(p2.x, p2.y + s);
+    deep_pin_j(J.r1, J.r2);
+}
+
 /* The extended step (the header's EXTENDED step): dz' = (n.x, n.y, en), not normalised */
 template <class F>
 __device__ __forceinline__ double2 deep_step_x(const double Zx, const double Zy, const int eZ, const double dzx,
@@ -714,6 +821,32 @@ __device__ __forceinline__ void deep_step_pd(const double Zx, const double Zy, c
     const double zx = Zx + dzx, zy = Zy + dzy;
     const double wx = zx + zx, wy = zy + zy;
     deepx_d_set(D, wx * D.x - wy * D.y, wx * D.y + wy * D.x, D.e, sm, es);
+}
+
+/* The ship's two (fr_render_deepx_ship_de): the magnitudes of L from b's mantissas, J' = norm4((L J, eb + 1 + J.e) (+) (sm I, es)).
+ * Its signs cannot come from b: aligned to eb, a coordinate far below the other is 0 there and has lost its sign (the tip of the
+ * needle: Y = 0 exactly and y = dz.y, 2^-1330 below x).  They are those of fold_x's w, the sum taken in the delta's frame, the
+ * same expressions ship_fold_x forms in this trip.  And in the plain mode L from w = 2 (Z_m + dz) on the plain doubles, the
+ * product at J.e */
+__device__ __forceinline__ void deep_step_xd(const double Zx, const double Zy, const int eZ, const double dzx, const double dzy,
+                                             const int ed, const double sm, const int es, XJac& J)
+{
+    const int eb = eZ > ed ? eZ : ed;
+    const double bx = __builtin_ldexp(Zx, eZ - eb) + __builtin_ldexp(dzx, ed - eb);
+    const double by = __builtin_ldexp(Zy, eZ - eb) + __builtin_ldexp(dzy, ed - eb);
+    const double wx = __builtin_ldexp(Zx, eZ - ed) + dzx, wy = __builtin_ldexp(Zy, eZ - ed) + dzy;
+    double2 p1, p2;
+    ship_lj(bx, by, wx, wy, J.r1, J.r2, p1, p2);
+    deepx_j_set(J, p1, p2, eb + 1 + J.e, sm, es);
+}
+
+__device__ __forceinline__ void deep_step_pd(const double Zx, const double Zy, const double dzx, const double dzy, const double sm,
+                                             const int es, XJac& J)
+{
+    const double x = Zx + dzx, y = Zy + dzy;
+    double2 p1, p2;
+    ship_lj(x + x, y + y, x, y, J.r1, J.r2, p1, p2);
+    deepx_j_set(J, p1, p2, J.e, sm, es);
 }
 
 /* ... and the two of a formula without a dc term (fr_render_deepx_julia_de): D' = norm(b D, eb + 1 + D.e) and D' = norm(w D, D.e),
@@ -1010,6 +1143,10 @@ __device__ __forceinline__ BlaHitX bla_probe_x(const XRad* tr, const uint32_t n1
     return h;
 }
 
+/* the derivative a loop carries for a formula: a complex number, or the ship's matrix */
+template <class F> using DeepD = std::conditional_t<F::kRealJacobian, Jac, double2>;
+template <class F> using DeepXD = std::conditional_t<F::kRealJacobian, XJac, XDeriv>;
+
 /* ---- the per-sample loops ----------------------------------------------------------------------------------------------
  * The wave's 64 samples, one per lane.  live = false: a lane without a sample (outside the frame).  esc = the loop index
  * of the escaping update (max_iter if none), r2 = |z|^2 there.  z = Z_{m+1} + dz' with the signed orbit point for either
@@ -1017,7 +1154,7 @@ __device__ __forceinline__ BlaHitX bla_probe_x(const XRad* tr, const uint32_t n1
 template <class F, bool DE = false>
 __device__ __forceinline__ void deep_orbit(const DeepArgs& A, const JuliaStart J, const double dcx, const double dcy,
                                            const double2 z1, bool live, int& esc, double& er2, const double s = 0.0,
-                                           double2* const Dout = nullptr)
+                                           DeepD<F>* const Dout = nullptr)
 {
     const double2* __restrict__ orbit = A.orbit;
     const int max_iter = A.max_iter;
@@ -1036,7 +1173,9 @@ __device__ __forceinline__ void deep_orbit(const DeepArgs& A, const JuliaStart J
     int m = 0;
     esc = max_iter;
     er2 = 0.0;
-    double2 D = make_double2(0.0, 0.0);                          /* DE: dz/dc * s, through the escaping update */
+    DeepD<F> D;                                                  /* DE: dz/dc * s, through the escaping update */
+    if constexpr (F::kRealJacobian) D.r1 = D.r2 = D.z = make_double2(0.0, 0.0);
+    else D = make_double2(0.0, 0.0);
     if constexpr (DE && !F::kHasB) D.x = s;                      /* ... without a dc term dz_n/dz_0 * s: (s, +0.0) at the start */
     for (int i = 0; i < max_iter; ++i) {
         if (__builtin_amdgcn_ballot_w64(live) == 0ull) break;
@@ -1051,6 +1190,7 @@ __device__ __forceinline__ void deep_orbit(const DeepArgs& A, const JuliaStart J
         const double r2 = zx * zx + zy * zy;
         if (r2 > B2) {
             esc = i; er2 = r2; live = false;
+            if constexpr (DE && F::kRealJacobian) { dzx = zx; dzy = zy; }   /* z, for the gradient of |z| */
         } else if (r2 < nx * nx + ny * ny || m == N) {           /* rebase */
             dzx = zx; dzy = zy; m = 0;
             Zx = 0.0; Zy = 0.0; Znx = z1.x; Zny = z1.y;
@@ -1060,6 +1200,7 @@ __device__ __forceinline__ void deep_orbit(const DeepArgs& A, const JuliaStart J
             Zx = Znx; Zy = Zny; Znx = Znn.x; Zny = Znn.y;
         }
     }
+    if constexpr (DE && F::kRealJacobian) D.z = make_double2(dzx, dzy);
     if constexpr (DE) *Dout = D;
 }
 
@@ -1072,7 +1213,7 @@ template <class F, bool DE = false>
 __device__ __forceinline__ void deep_orbit_bla(const DeepArgs& A, const BlaTable& T, const JuliaStart J, const int levels_p,
                                                const uint32_t base_p, const double dcx, const double dcy, const double2 z1,
                                                bool live, int& esc, double& er2, uint32_t& nplain, uint32_t& nbla,
-                                               const double s = 0.0, double2* const Dout = nullptr)
+                                               const double s = 0.0, DeepD<F>* const Dout = nullptr)
 {
     const double2* __restrict__ orbit = A.orbit;
     const double* __restrict__ tr = T.r;
@@ -1095,7 +1236,9 @@ __device__ __forceinline__ void deep_orbit_bla(const DeepArgs& A, const BlaTable
     esc = max_iter;
     er2 = 0.0;
     nplain = 0u; nbla = 0u;
-    double2 D = make_double2(0.0, 0.0);                          /* DE: dz/dc * s, through the escaping update */
+    DeepD<F> D;                                                  /* DE: dz/dc * s, through the escaping update */
+    if constexpr (F::kRealJacobian) D.r1 = D.r2 = D.z = make_double2(0.0, 0.0);
+    else D = make_double2(0.0, 0.0);
     if constexpr (DE && !F::kHasB) D.x = s;                      /* ... without a dc term dz_n/dz_0 * s: (s, +0.0) at the start */
     for (;;) {
         if (__builtin_amdgcn_ballot_w64(live) == 0ull) break;
@@ -1130,6 +1273,7 @@ __device__ __forceinline__ void deep_orbit_bla(const DeepArgs& A, const BlaTable
         const double r2 = zx * zx + zy * zy;
         if (r2 > B2) {
             esc = u - 1; er2 = r2; live = false;                 /* the last update the step covered */
+            if constexpr (DE && F::kRealJacobian) { dzx = zx; dzy = zy; }   /* z, for the gradient of |z| */
         } else if (r2 < nx * nx + ny * ny || m == N) {           /* rebase */
             dzx = zx; dzy = zy; m = 0;
             Zx = 0.0; Zy = 0.0; Znx = z1.x; Zny = z1.y;
@@ -1148,6 +1292,7 @@ __device__ __forceinline__ void deep_orbit_bla(const DeepArgs& A, const BlaTable
         }
         if (u >= max_iter) live = false;                          /* esc stays max_iter */
     }
+    if constexpr (DE && F::kRealJacobian) D.z = make_double2(dzx, dzy);
     if constexpr (DE) *Dout = D;
 }
 
@@ -1156,7 +1301,7 @@ __device__ __forceinline__ void deep_orbit_bla(const DeepArgs& A, const BlaTable
 template <class F, bool DE = false>
 __device__ __forceinline__ void deep_orbit_x(const DeepArgs& A, const DeepXOrbit& AX, const JuliaStart J, const double cx,
                                              const double cy, const int ec, bool live, int& esc, double& er2,
-                                             const double sm = 0.0, const int es = 0, XDeriv* const Dout = nullptr)
+                                             const double sm = 0.0, const int es = 0, DeepXD<F>* const Dout = nullptr)
 {
     const double2* __restrict__ orbit = A.orbit;
     const double2* __restrict__ mant = AX.mant;
@@ -1190,7 +1335,9 @@ __device__ __forceinline__ void deep_orbit_x(const DeepArgs& A, const DeepXOrbit
     int m = 0;
     esc = max_iter;
     er2 = 0.0;
-    XDeriv D = {0.0, 0.0, kXZero};                               /* DE: dz/dc * s, through the escaping update */
+    DeepXD<F> D;                                                 /* DE: dz/dc * s, through the escaping update */
+    if constexpr (F::kRealJacobian) { D.r1 = D.r2 = D.z = make_double2(0.0, 0.0); D.e = kXZero; }
+    else D = XDeriv{0.0, 0.0, kXZero};
     if constexpr (DE && !F::kHasB) { D.x = sm; D.e = es; }       /* ... without a dc term dz_n/dz_0 * s: (sm, +0.0, es) at first */
     for (int i = 0; i < max_iter; ++i) {
         if (__builtin_amdgcn_ballot_w64(live) == 0ull) break;
@@ -1215,6 +1362,7 @@ __device__ __forceinline__ void deep_orbit_x(const DeepArgs& A, const DeepXOrbit
             const double r2d = __builtin_ldexp(r2, 2 * ez);
             if (r2d > B2) {
                 esc = i; er2 = r2d; live = false;
+                if constexpr (DE && F::kRealJacobian) { dzx = __builtin_ldexp(zx, ez); dzy = __builtin_ldexp(zy, ez); }   /* z */
                 continue;
             }
             reb = r2 < __builtin_ldexp(nx * nx + ny * ny, 2 * (en - ez)) || m == N;
@@ -1247,6 +1395,7 @@ __device__ __forceinline__ void deep_orbit_x(const DeepArgs& A, const DeepXOrbit
             const double r2 = zx * zx + zy * zy;
             if (r2 > B2) {
                 esc = i; er2 = r2; live = false;
+                if constexpr (DE && F::kRealJacobian) { dzx = zx; dzy = zy; }   /* z, for the gradient of |z| */
                 continue;
             }
             reb = r2 < nx * nx + ny * ny || m == N;
@@ -1278,6 +1427,7 @@ __device__ __forceinline__ void deep_orbit_x(const DeepArgs& A, const DeepXOrbit
             Zx = a.x; Zy = a.y; Znx = b.x; Zny = b.y;
         }
     }
+    if constexpr (DE && F::kRealJacobian) D.z = make_double2(dzx, dzy);
     if constexpr (DE) *Dout = D;
 }
 
@@ -1291,7 +1441,7 @@ __device__ __forceinline__ void deep_orbit_x_bla(const DeepArgs& A, const DeepXO
                                                  const int levels_p, const uint32_t base_p, const double cx, const double cy,
                                                  const int ec, bool live, int& esc, double& er2, uint32_t& nsingle,
                                                  uint32_t& nbla, const double sm = 0.0, const int es = 0,
-                                                 XDeriv* const Dout = nullptr)
+                                                 DeepXD<F>* const Dout = nullptr)
 {
     const double2* __restrict__ orbit = A.orbit;
     const double2* __restrict__ mant = AX.mant;
@@ -1330,7 +1480,9 @@ __device__ __forceinline__ void deep_orbit_x_bla(const DeepArgs& A, const DeepXO
     esc = max_iter;
     er2 = 0.0;
     nsingle = 0u; nbla = 0u;
-    XDeriv D = {0.0, 0.0, kXZero};                               /* DE: dz/dc * s, through the escaping update */
+    DeepXD<F> D;                                                 /* DE: dz/dc * s, through the escaping update */
+    if constexpr (F::kRealJacobian) { D.r1 = D.r2 = D.z = make_double2(0.0, 0.0); D.e = kXZero; }
+    else D = XDeriv{0.0, 0.0, kXZero};
     if constexpr (DE && !F::kHasB) { D.x = sm; D.e = es; }       /* ... without a dc term dz_n/dz_0 * s: (sm, +0.0, es) at first */
     for (;;) {
         if (__builtin_amdgcn_ballot_w64(live) == 0ull) break;
@@ -1383,6 +1535,7 @@ __device__ __forceinline__ void deep_orbit_x_bla(const DeepArgs& A, const DeepXO
             const double r2d = __builtin_ldexp(r2, 2 * ez);
             if (r2d > B2) {
                 esc = u - 1; er2 = r2d; live = false;             /* the last update the step covered */
+                if constexpr (DE && F::kRealJacobian) { dzx = __builtin_ldexp(zx, ez); dzy = __builtin_ldexp(zy, ez); }   /* z */
                 continue;
             }
             reb = r2 < __builtin_ldexp(nx * nx + ny * ny, 2 * (en - ez)) || m == N;
@@ -1425,6 +1578,7 @@ __device__ __forceinline__ void deep_orbit_x_bla(const DeepArgs& A, const DeepXO
             const double r2 = zx * zx + zy * zy;
             if (r2 > B2) {
                 esc = u - 1; er2 = r2; live = false;
+                if constexpr (DE && F::kRealJacobian) { dzx = zx; dzy = zy; }   /* z, for the gradient of |z| */
                 continue;
             }
             reb = r2 < nx * nx + ny * ny || m == N;
@@ -1451,6 +1605,7 @@ __device__ __forceinline__ void deep_orbit_x_bla(const DeepArgs& A, const DeepXO
         }
         if (u >= max_iter) live = false;                          /* esc stays max_iter */
     }
+    if constexpr (DE && F::kRealJacobian) D.z = make_double2(dzx, dzy);
     if constexpr (DE) *Dout = D;
 }
 
@@ -1544,19 +1699,25 @@ __device__ __forceinline__ void deep_kernel_body(const ARGS& AA)
             /* DE, extended: D = (D.x, D.y) 2^eD.  The loop's XDeriv is unpacked into these two so that the planes and
              * deep_de_of(r2, D) below are one code path with the fp64 derivative's, the exponent applied behind them */
             int eD = 0;
+            Jac Jm;                                               /* ... and the ship's matrix, its mantissas with X */
             if constexpr (DE && X) {
                 int ec = AA.ze;
                 x_norm(cx, cy, ec);
-                XDeriv Dx;
+                DeepXD<F> Dx;
                 if constexpr (BLA)
                     deep_orbit_x_bla<F, true>(A, AA, bla_table(AA), J, levels_p, base_p, cx, cy, ec, inside, esc, r2, np, nb,
                                               de_s, de_es, &Dx);
                 else deep_orbit_x<F, true>(A, AA, J, cx, cy, ec, inside, esc, r2, de_s, de_es, &Dx);
-                D = make_double2(Dx.x, Dx.y); eD = Dx.e;
+                if constexpr (F::kRealJacobian) { Jm.r1 = Dx.r1; Jm.r2 = Dx.r2; Jm.z = Dx.z; }
+                else D = make_double2(Dx.x, Dx.y);
+                eD = Dx.e;
             } else if constexpr (DE) {
+                DeepD<F>* Dp;
+                if constexpr (F::kRealJacobian) Dp = &Jm;
+                else Dp = &D;
                 if constexpr (BLA)
-                    deep_orbit_bla<F, true>(A, bla_table(AA), J, levels_p, base_p, cx, cy, z1, inside, esc, r2, np, nb, de_s, &D);
-                else deep_orbit<F, true>(A, J, cx, cy, z1, inside, esc, r2, de_s, &D);
+                    deep_orbit_bla<F, true>(A, bla_table(AA), J, levels_p, base_p, cx, cy, z1, inside, esc, r2, np, nb, de_s, Dp);
+                else deep_orbit<F, true>(A, J, cx, cy, z1, inside, esc, r2, de_s, Dp);
             } else if constexpr (X) {
                 int ec = AA.ze;
                 x_norm(cx, cy, ec);
@@ -1578,7 +1739,22 @@ __device__ __forceinline__ void deep_kernel_body(const ARGS& AA)
             if constexpr (DE) {
                 const bool escaped = esc < A.max_iter;            /* interior: 0 and (0, 0) */
                 const bool first = s == 0 && inside;
-                if (first && AA.deriv) {
+                if constexpr (F::kRealJacobian) {                 /* four doubles: (J11, J12, J21, J22) */
+                    if (first && AA.deriv) {
+                        double* const dst = AA.deriv + 4 * plane_index(A.g, px, py, lrow);
+                        const double j[4] = {Jm.r1.x, Jm.r1.y, Jm.r2.x, Jm.r2.y};
+                        for (int c = 0; c < 4; ++c) {
+                            if constexpr (X) dst[c] = escaped ? __builtin_ldexp(j[c], eD) : 0.0;
+                            else dst[c] = escaped ? j[c] : 0.0;
+                        }
+                    }
+                    /* the gradient of |z| with respect to c, J^T z / |z|: the D of deep_de_of */
+                    if (escaped && (s == 0 || de_shade)) {
+                        const double zl = sqrt(r2);
+                        const double ux = Jm.z.x / zl, uy = Jm.z.y / zl;
+                        D = make_double2(Jm.r1.x * ux + Jm.r2.x * uy, Jm.r1.y * ux + Jm.r2.y * uy);
+                    }
+                } else if (first && AA.deriv) {
                     double* const dst = AA.deriv + 2 * plane_index(A.g, px, py, lrow);
                     if constexpr (X) {                            /* saturates outside a double's range */
                         dst[0] = escaped ? __builtin_ldexp(D.x, eD) : 0.0; dst[1] = escaped ? __builtin_ldexp(D.y, eD) : 0.0;
@@ -1624,6 +1800,15 @@ __device__ __forceinline__ void deep_kernel_body(const ARGS& AA)
 template <class ARGS>
 __global__ void __launch_bounds__(kBlockThreads)
 deep_kernel(const ARGS AA)
+{
+    deep_kernel_body(AA);
+}
+
+/* The four kernels of the ship's distance estimate, DeepBlock<ShipFormula, X, true, BLA>: the same body under a __global__
+ * template of their own (kShipDe picks it in the launch) */
+template <class ARGS>
+__global__ void __launch_bounds__(kBlockThreads)
+deep_ship_de_kernel(const ARGS AA)
 {
     deep_kernel_body(AA);
 }

@@ -80,7 +80,8 @@ struct BlaSlot {
 /* What the context keeps for one deep path, a (storage, formula) pair: its most recent reference orbit(s), their BLA table, and
  * the resident workgroups per CU of the deep_kernel instantiations that read them (0 = not asked yet): [0] the path's own pair,
  * [1] the distance entry point's that shares the slot -- fr_render_deep_de's the fp64 Mandelbrot slot, fr_render_deepx_de's the
- * extended one, fr_render_deep_julia_de's and fr_render_deepx_julia_de's the two Julia slots;
+ * extended one, fr_render_deep_julia_de's and fr_render_deepx_julia_de's the two Julia slots, fr_render_deep_ship_de's and
+ * fr_render_deepx_ship_de's the two ship slots;
  * [.][0] the unflagged kernel, [.][1] the flagged one */
 struct DeepSlot {
     DeepOrbit o;
@@ -999,6 +1000,8 @@ using DeepJulia = DeepBlock<JuliaFormula, false, false>;
 using DeepJuliaDe = DeepBlock<JuliaFormula, false, true>;
 using DeepJuliaX = DeepBlock<JuliaFormula, true, false>;
 using DeepJuliaXDe = DeepBlock<JuliaFormula, true, true>;
+/* ... and the ship's two distance paths, whose four kernels are deep_ship_de_kernel's */
+template <bool X> using DeepShipDe = DeepBlock<ShipFormula, X, true>;
 
 /* What launch_deep and enqueue_deep_view read of a path, BASE being the argument block of its unflagged kernel: the formula, the
  * storage, de = 1 for the blocks that carry a derivative, the flag that selects the flagged kernel and that kernel's block */
@@ -1015,12 +1018,22 @@ struct DeepPath {
     using Bla = DeepBlock<F, BASE::kX, BASE::kDe, true>;
 };
 
+/* the __global__ template a block's kernel is an instantiation of: deep_ship_de_kernel for the ship's distance estimate */
+template <class ARGS>
+static constexpr bool kShipDe = std::is_same<typename ARGS::Formula, ShipFormula>::value && ARGS::kDe;
+template <class ARGS>
+static constexpr auto deep_kernel_of()
+{
+    if constexpr (kShipDe<ARGS>) return deep_ship_de_kernel<ARGS>;
+    else return deep_kernel<ARGS>;
+}
+
 /* a deep kernel's name in messages, from its block's switches: deep_kernel<Julia, X, DE, BLA> */
 template <class ARGS>
 static const char* deep_kernel_name()
 {
     static const char* const formula[3] = {"Mandel", "Ship", "Julia"};
-    static const std::string name = std::string("deep_kernel<") + formula[DeepPath<ARGS>::f] + (ARGS::kX ? ", X" : "") +
+    static const std::string name = std::string(kShipDe<ARGS> ? "deep_ship_de_kernel<" : "deep_kernel<") + formula[DeepPath<ARGS>::f] + (ARGS::kX ? ", X" : "") +
                                     (ARGS::kDe ? ", DE" : "") + (ARGS::kBla ? ", BLA" : "") + ">";
     return name.c_str();
 }
@@ -1036,7 +1049,7 @@ static int launch_deep(fr_ctx* c, hipStream_t stream, BASE& base, bool bla)
     using BLA = typename P::Bla;
     DeepSlot& s = deep_slot(c, P::ext, P::f);
     if (!bla)
-        return launch_one_pass(c, stream, deep_kernel_name<BASE>(), deep_kernel<BASE>, base, base.g, base.q, s.wg_per_cu[P::de][0],
+        return launch_one_pass(c, stream, deep_kernel_name<BASE>(), deep_kernel_of<BASE>(), base, base.g, base.q, s.wg_per_cu[P::de][0],
                                false);
     BLA a;
     memset(&a, 0, sizeof(a));
@@ -1058,7 +1071,7 @@ static int launch_deep(fr_ctx* c, hipStream_t stream, BASE& base, bool bla)
     }
     tab.steps = t.steps_dev;
     FR_HIP_TRY(hipMemsetAsync(t.steps_dev, 0, 3 * sizeof(unsigned long long), stream));
-    const int st = launch_one_pass(c, stream, deep_kernel_name<BLA>(), deep_kernel<BLA>, a, a.g, a.q, s.wg_per_cu[P::de][1], false);
+    const int st = launch_one_pass(c, stream, deep_kernel_name<BLA>(), deep_kernel_of<BLA>(), a, a.g, a.q, s.wg_per_cu[P::de][1], false);
     if (st != FR_OK) return st;
     FR_HIP_TRY(hipMemcpyAsync(t.steps_host, t.steps_dev, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
     t.have_steps = true;
@@ -1988,10 +2001,10 @@ extern "C" int fr_render_mandelbulb(fr_ctx* c, const fr_params* p, const fr_mand
         return enqueue_mandelbulb(c, p, mb, W, H, sh, rgba, nu, iter, s, out_frame); });
 }
 
-/* The twenty deep entry points: BASE names the path (DeepPath), async_entry the _async form (nullptr: the synchronous one),
+/* The twenty-four deep entry points: BASE names the path (DeepPath), async_entry the _async form (nullptr: the synchronous one),
  * validate() runs the path's validator once the pointers are known not to be NULL, and the enqueue step is enqueue_deep_view of
- * the view read into a DeepAt.  e: the block of the four distance entry points (fr_render_deep_de, _deepx_de, _deep_julia_de,
- * _deepx_julia_de), whose two planes travel as extra planes into the derivative's fields; nullptr for every other path. */
+ * the view read into a DeepAt.  e: the block of the six distance entry points (fr_render_deep_de, _deepx_de, _deep_julia_de,
+ * _deepx_julia_de, _deep_ship_de, _deepx_ship_de), whose two planes travel as extra planes into the derivative's fields; nullptr for every other path. */
 template <class BASE, class VIEW, class Validate>
 static int deep_entry(const char* async_entry, fr_ctx* c, const fr_params* p, const VIEW* v, const fr_deep_de* e, uint32_t W,
                       uint32_t H, const fr_shard* shard, const fr_output* out, void* hip_stream, Validate&& validate)
@@ -2004,8 +2017,11 @@ static int deep_entry(const char* async_entry, fr_ctx* c, const fr_params* p, co
     if (st != FR_OK) return st;
     ExtraPlanes extra;
     if constexpr (de)
-        extra = {2, {{e->deriv, 16}, {e->de, 8}},
-                 DeepPath<BASE>::f == kJulia
+        extra = {2, {{e->deriv, DeepPath<BASE>::f == kShip ? 32u : 16u}, {e->de, 8}},
+                 DeepPath<BASE>::f == kShip
+                     ? (DeepPath<BASE>::ext ? "fr_render_deepx_ship_de: neither fr_output nor fr_deep_de has a plane to write"
+                                            : "fr_render_deep_ship_de: neither fr_output nor fr_deep_de has a plane to write")
+                 : DeepPath<BASE>::f == kJulia
                      ? (DeepPath<BASE>::ext ? "fr_render_deepx_julia_de: neither fr_output nor fr_deep_de has a plane to write"
                                             : "fr_render_deep_julia_de: neither fr_output nor fr_deep_de has a plane to write")
                      : (DeepPath<BASE>::ext ? "fr_render_deepx_de: neither fr_output nor fr_deep_de has a plane to write"
@@ -2149,6 +2165,37 @@ extern "C" int fr_render_deepx_julia(fr_ctx* c, const fr_params* p, const fr_dee
 {
     return deep_entry<DeepJuliaX>(nullptr, c, p, v, nullptr, W, H, shard, out, nullptr,
                                       [&] { return fr_deepx_julia_validate(p, v, W, H); });
+}
+
+/* fr_render_deep_ship_de, fr_render_deepx_ship_de: fr_render_deep_de's five planes on the two ship paths, deriv four doubles per
+ * pixel; the slots (orbit, table, step counts) are those of fr_render_deep_ship and fr_render_deepx_ship */
+extern "C" int fr_render_deep_ship_de_async(fr_ctx* c, const fr_params* p, const fr_deep_view* v, const fr_deep_de* e, uint32_t W,
+                                            uint32_t H, const fr_shard* shard, const fr_output* out, void* hip_stream)
+{
+    return deep_entry<DeepShipDe<false>>("fr_render_deep_ship_de_async", c, p, v, e, W, H, shard, out, hip_stream,
+                                         [&] { return fr_deep_ship_de_validate(p, v, e, W, H); });
+}
+
+extern "C" int fr_render_deep_ship_de(fr_ctx* c, const fr_params* p, const fr_deep_view* v, const fr_deep_de* e, uint32_t W,
+                                      uint32_t H, const fr_shard* shard, const fr_output* out)
+{
+    return deep_entry<DeepShipDe<false>>(nullptr, c, p, v, e, W, H, shard, out, nullptr,
+                                         [&] { return fr_deep_ship_de_validate(p, v, e, W, H); });
+}
+
+extern "C" int fr_render_deepx_ship_de_async(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, const fr_deep_de* e,
+                                             uint32_t W, uint32_t H, const fr_shard* shard, const fr_output* out,
+                                             void* hip_stream)
+{
+    return deep_entry<DeepShipDe<true>>("fr_render_deepx_ship_de_async", c, p, v, e, W, H, shard, out, hip_stream,
+                                        [&] { return fr_deepx_ship_de_validate(p, v, e, W, H); });
+}
+
+extern "C" int fr_render_deepx_ship_de(fr_ctx* c, const fr_params* p, const fr_deepx_view* v, const fr_deep_de* e, uint32_t W,
+                                       uint32_t H, const fr_shard* shard, const fr_output* out)
+{
+    return deep_entry<DeepShipDe<true>>(nullptr, c, p, v, e, W, H, shard, out, nullptr,
+                                        [&] { return fr_deepx_ship_de_validate(p, v, e, W, H); });
 }
 
 /* fr_render_deep_julia_de, fr_render_deepx_julia_de: fr_render_deep_de's five planes on the two Julia paths, whose slots (orbits,

@@ -446,6 +446,39 @@ class Renderer:
                               (C.byref(p), C.byref(v), C.byref(e)), width, height, Precision.F64, rows, rgba, nu, iter, shard,
                               stream, sync, extra=extra)
 
+    def render_deep_ship_de(self, state: FractalState, width: int, height: int, view: Optional[DeepView] = None, *,
+                            post_chain: bool = False, rgba=None, nu=None, iter=None, de=None, deriv=None, shade: bool = False,
+                            edge_px: float = DEEP_DE_EDGE_PX, shard: Optional[Shard] = None, stream: Optional[int] = None,
+                            sync: bool = True, bla: bool = False) -> None:
+        """fr_render_deep_ship_de / fr_render_deepx_ship_de and their _async forms: render_deep_ship() / render_deepx_ship()
+        with the real 2x2 Jacobian of a sample's point with respect to c carried through the perturbation loop, and two planes
+        more.  de: rows*W float64, the exterior distance estimate of sample (0,0) in pixel spacings of the whole frame (0 for
+        interior), |z| log|z| over the length of the gradient of |z|; deriv: rows*W*4 float64, (J11, J12, J21, J22) =
+        dz/dc * (zoom / H) at the escaping update.  Any one of the five planes is enough; all of them are host or all device
+        memory.  shade and edge_px as for render_deep_de().  The view dispatches as in render_deep_julia_de(): with a zoom
+        string it goes to the extended entry point (de stays finite at any depth, deriv saturates outside a double's range),
+        without one to the fp64 entry point.  iter, nu, rgba without shade and the step counts are the plain ship call's, and
+        the context's orbit and table are shared with it.  bla=True sets the flag that fits the view."""
+        p = state.to_params(FractalType.BurningShip, Precision.F64, post_chain)
+        rows = shard.rows(height) if shard else height
+        e = _capi.fr_deep_de(None, None, 1 if shade else 0, float(edge_px))
+        extra = ((e, "de", de, "float64", 1), (e, "deriv", deriv, "float64", 4))
+        # (through the class, as render_deep_de)
+        if view is not None and view.zoom is not None:
+            if bla:
+                p.flags |= _capi.FR_FLAG_DEEPX_SHIP_BLA
+            vx = view.to_cx()
+            Renderer._render_call(self, self._lib.fr_render_deepx_ship_de, self._lib.fr_render_deepx_ship_de_async,
+                                  (C.byref(p), C.byref(vx), C.byref(e)), width, height, Precision.F64, rows, rgba, nu, iter,
+                                  shard, stream, sync, extra=extra)
+            return
+        if bla:
+            p.flags |= _capi.FR_FLAG_DEEP_SHIP_BLA
+        v = (view or DeepView()).to_c()
+        Renderer._render_call(self, self._lib.fr_render_deep_ship_de, self._lib.fr_render_deep_ship_de_async,
+                              (C.byref(p), C.byref(v), C.byref(e)), width, height, Precision.F64, rows, rgba, nu, iter, shard,
+                              stream, sync, extra=extra)
+
     def _render_call(self, fn_sync, fn_async, params: tuple, width: int, height: int, precision: Precision, rows: int,
                      rgba, nu, it, shard: Optional[Shard], stream: Optional[int], sync: bool, extra=()) -> None:
         """the planes, the shard and the sync / async entry of render(), render_phoenix(), render_mandelbulb(), render_deep(),

@@ -551,9 +551,9 @@ int fr_ctx_last_deep_steps(fr_ctx* ctx, uint64_t out[3]);
  * <= 0 is FR_ERR_INVALID_ARG.
  * Cost: four live VGPRs and 11 fp64 operations per plain update on top of the step's 18 (README: measured).
  * Extended views below 1e-290, where s underflows and D needs an exponent of its own, are fr_render_deepx_de (below,
- * FR_HAS_DEEPX_DE); Julia sets are fr_render_deep_julia_de (FR_HAS_DEEP_JULIA_DE).  Out of scope: the Burning Ship, which
- * needs a real 2x2 Jacobian; fr_deep_sequence; fr_node and .franim; slope or normal lighting -- deriv is what a
- * caller needs for it. */
+ * FR_HAS_DEEPX_DE); Julia sets are fr_render_deep_julia_de (FR_HAS_DEEP_JULIA_DE); the Burning Ship, whose derivative is a
+ * real 2x2 Jacobian, is fr_render_deep_ship_de (FR_HAS_DEEP_SHIP_DE).  Out of scope: fr_deep_sequence; fr_node and .franim;
+ * slope or normal lighting -- deriv is what a caller needs for it. */
 #define FR_HAS_DEEP_DE 1
 
 typedef struct fr_deep_de {
@@ -867,8 +867,9 @@ int fr_ctx_last_deepx_steps(fr_ctx* ctx, uint64_t out[3]);
  * arguments in VGPR lanes: 84 and 87 of them (76 and 78 in fr_render_deepx's kernels; the distance block adds nine scalars),
  * written once in the prologue and read back per sample around the orbit loop, never inside it (checked on the ISA by
  * tests/test_deepx_de_host.py).
- * Julia sets are fr_render_deepx_julia_de (below, FR_HAS_DEEPX_JULIA_DE).
- * Out of scope: the Burning Ship, fr_deep_sequence, fr_node and .franim, slope or normal lighting. */
+ * Julia sets are fr_render_deepx_julia_de (below, FR_HAS_DEEPX_JULIA_DE), the Burning Ship is fr_render_deepx_ship_de
+ * (FR_HAS_DEEPX_SHIP_DE).
+ * Out of scope: fr_deep_sequence, fr_node and .franim, slope or normal lighting. */
 #define FR_HAS_DEEPX_DE 1
 
 /* What fr_render_deepx_de checks of its arguments, the view's strings parsed included (no context needed). */
@@ -1317,8 +1318,9 @@ int64_t fr_deepx_julia_bla_table(fr_ctx* ctx, void* r, double* a, int32_t* a_exp
  * interleaved with the plain entry points in one session, device time), without / with the BLA flag: 1.26 / 1.14 of
  * fr_render_deep_julia on RABBIT30 and on DENDRITE100, 1.33 / 1.38 of fr_render_deepx_julia on the dendrite at 1e-400; in the
  * same session fr_render_deep_de costs 1.30 / 1.18 of fr_render_deep and fr_render_deepx_de 1.36 / 1.39 of fr_render_deepx.
- * Out of scope: the Burning Ship (a real 2x2 Jacobian and a choice of norm), sequences, fr_node and .franim, c as a decimal
- * string, slope or normal lighting -- deriv is what a caller needs for it. */
+ * The Burning Ship, with a real 2x2 Jacobian and a fixed norm, is fr_render_deep_ship_de / fr_render_deepx_ship_de (below).
+ * Out of scope: sequences, fr_node and .franim, c as a decimal string, slope or normal lighting -- deriv is what a caller needs
+ * for it. */
 #define FR_HAS_DEEP_JULIA_DE 1
 #define FR_HAS_DEEPX_JULIA_DE 1
 
@@ -1337,6 +1339,78 @@ int fr_render_deepx_julia_de(fr_ctx* ctx, const fr_params* p, const fr_deepx_vie
                              uint32_t height, const fr_shard* shard, const fr_output* out);
 int fr_render_deepx_julia_de_async(fr_ctx* ctx, const fr_params* p, const fr_deepx_view* view, const fr_deep_de* de, uint32_t width,
                                    uint32_t height, const fr_shard* shard, const fr_output* out, void* hip_stream);
+
+/* ---- distance estimates for deep Burning Ship views ----------------------------------------------------------------------
+ * fr_render_deep_ship_de (zoom 1e-290 .. 1e3, plain or FR_FLAG_DEEP_SHIP_BLA) and fr_render_deepx_ship_de (zoom 1e-1000 .. 1e3,
+ * plain or FR_FLAG_DEEPX_SHIP_BLA): fr_render_deep_ship / fr_render_deepx_ship with fr_render_deep_de's two planes and shading.
+ * The ship's map is not conformal, so the derivative of z with respect to c is a real 2x2 matrix
+ *   J = [[dx/dcx, dx/dcy], [dy/dcx, dy/dcy]] * s,   s = zoom / H of the whole frame (never of a shard's rows),
+ * the zero matrix at the start, and the estimate takes the gradient of |z|: de = |z| log|z| / |J^T z / |z||.  For a conformal
+ * J = [[Dx, -Dy], [Dy, Dx]] that norm is |D| and the estimate is fr_render_deep_de's.
+ * fr_deep_de is reused unchanged with one difference: deriv is rows*W*4 doubles, (J11, J12, J21, J22) of sample (0,0) at its
+ * escaping update, zeros for interior pixels.  de, shade and edge_px are as in fr_render_deep_de.
+ *
+ * The arithmetic, fp64 range; every operation is one rounding as written, no contraction.  sgn v = v >= 0 ? 1 : -1.
+ *   plain step, every trip, at the sample's point before the update, (x, y) = Z_m + dz (the sum of fr_render_deep_de's step):
+ *     wx = x + x, wy = y + y;   L = [[wx, -wy], [|wy| sgn x, |wx| sgn y]]
+ *     J11' = (L11 J11 + L12 J21) + s     J12' = L11 J12 + L12 J22
+ *     J21' = L21 J11 + L22 J21           J22' = (L21 J12 + L22 J22) + s
+ *   the derivative of (|x| + i |y|)^2 + c on the piece the sample's own orbit is on.
+ *   BLA step with the entry (A, B) the sample takes, from the one load the step makes: Jij' = (ai1 J1j + ai2 J2j) + bij s.
+ *   a rebase leaves J alone.
+ *   escape at z = (zx, zy) with r2:  zl = sqrt(r2), ux = zx / zl, uy = zy / zl,
+ *     g = (J11 ux + J21 uy, J12 ux + J22 uy),  de = (zl log zl) / sqrt(g.x g.x + g.y g.y), NaN -> 0.
+ *   interior samples: de = 0, deriv = 0.
+ * J never feeds back into the orbit: iter, nu, rgba without shading and the three step counts are the plain ship entry
+ * point's, byte for byte.
+ *
+ * Extended range: J is four double mantissas and one shared int32 exponent J.e, normalised with norm4 (the ship's BLA section)
+ * after every update, in either mode of the lane's delta; the zero has FR_DEEPX_ZERO_EXP.  s = norm1(zm / H, ze) = (sm, es).
+ *   extended step: b = (Z_m, eZ) (+) (dz, ed) at eb = max(eZ, ed); L = [[b.x, -b.y], [|b.y| sgn w.x, |b.x| sgn w.y]] from b's
+ *     mantissas, the doubling in the exponent: J' = norm4((L J, eb + 1 + J.e) (+) (sm I, es)), L J without s as above, (+)
+ *     aligning both to the larger exponent with ldexp and adding; off the diagonal nothing is added.  The signs are those of
+ *     w = (ldexp(Z_m.x, eZ - ed) + dz.x, ldexp(Z_m.y, eZ - ed) + dz.y), fold_x's sum in the delta's frame: aligned to eb a
+ *     coordinate far below the other is 0 and has no sign left (the tip of the needle, where Y = 0 exactly and y = dz.y).
+ *   plain-mode step: L from the plain doubles as in the fp64 range, J' = norm4((L J, J.e) (+) (sm I, es)).
+ *   BLA step: J' = norm4((A J, A.e + J.e) (+) (B sm, B.e + es)).
+ *   no flush: every step adds s.
+ *   escape: z as plain doubles (|z| > bailout there: ldexp of the extended sum's mantissas), g and deep_de_of from J's
+ *     mantissas, de = ldexp(that, -J.e), finite at any depth; deriv = ldexp(Jij, J.e), which saturates outside a double's range
+ *     as in fr_render_deepx_de.
+ * On views both ranges take (1e-30, 1e-100) de and deriv are equal bit for bit.
+ *
+ * Accuracy: as for the other distance estimates the fp64 iteration loses 2^-53 / de below de of about 1e-3 pixel spacings;
+ * above it the tests bound the error against J iterated directly at F + 64 bits (README: measured).
+ * Planes, shards, FR_LAYOUT_FRAME, FR_MEM_HOST: de->de and de->deriv follow out->memory and out->layout as out->nu does, deriv
+ * sized for four doubles per pixel; of the five planes at least one must be given.
+ * Shared state: the orbit slot, the BLA table with its key and fr_ctx_last_deep_ship_steps / fr_ctx_last_deepx_ship_steps are
+ * those of the plain ship entry point of the same range -- a call here after it on the same view computes no orbit and builds no
+ * table, and the reverse.
+ * Validation: everything fr_deep_ship_validate / fr_deepx_ship_validate checks (the other BLA flags are FR_ERR_UNSUPPORTED);
+ * then `de` NULL, shade outside {0, 1}, or shade == 1 with edge_px not finite or <= 0 is FR_ERR_INVALID_ARG.
+ * Cost: eight live VGPRs (nine extended) and per plain update 22 fp64 operations on top of the step's.  The four kernels use no
+ * scratch and spill no VGPR: 109 VGPRs and 4 waves per SIMD (fr_render_deep_ship_de), 153 and 3 (with FR_FLAG_DEEP_SHIP_BLA), 125
+ * and 4 (fr_render_deepx_ship_de), 160 and 3 (with FR_FLAG_DEEPX_SHIP_BLA), against 89 / 5, 120 / 4, 101 / 4 and 130 / 3 in the
+ * kernels they extend: the fp64 pair runs a wave per SIMD below them, the extended pair keeps their occupancy (README: measured).
+ * Out of scope: sequences, fr_node and .franim, slope or normal lighting -- deriv is what a caller needs for it. */
+#define FR_HAS_DEEP_SHIP_DE 1
+#define FR_HAS_DEEPX_SHIP_DE 1
+
+/* What the two entry points check of their arguments, the view's strings parsed included (no context needed). */
+int fr_deep_ship_de_validate(const fr_params* p, const fr_deep_view* view, const fr_deep_de* de, uint32_t width, uint32_t height);
+int fr_deepx_ship_de_validate(const fr_params* p, const fr_deepx_view* view, const fr_deep_de* de, uint32_t width,
+                              uint32_t height);
+
+/* fr_render_deep_ship / fr_render_deepx_ship with the distance planes; options, timing and the orbit cache as there.  The
+ * asynchronous forms: fr_render_deep_ship_async's contract, de->de and de->deriv device planes like the others. */
+int fr_render_deep_ship_de(fr_ctx* ctx, const fr_params* p, const fr_deep_view* view, const fr_deep_de* de, uint32_t width,
+                           uint32_t height, const fr_shard* shard, const fr_output* out);
+int fr_render_deep_ship_de_async(fr_ctx* ctx, const fr_params* p, const fr_deep_view* view, const fr_deep_de* de, uint32_t width,
+                                 uint32_t height, const fr_shard* shard, const fr_output* out, void* hip_stream);
+int fr_render_deepx_ship_de(fr_ctx* ctx, const fr_params* p, const fr_deepx_view* view, const fr_deep_de* de, uint32_t width,
+                            uint32_t height, const fr_shard* shard, const fr_output* out);
+int fr_render_deepx_ship_de_async(fr_ctx* ctx, const fr_params* p, const fr_deepx_view* view, const fr_deep_de* de, uint32_t width,
+                                  uint32_t height, const fr_shard* shard, const fr_output* out, void* hip_stream);
 
 /* ---- frames over the GPUs of a node (BASELINE.json north_star: "tiled across the 8 GPUs of one node as disjoint row
  * bands with a final RCCL gather over xGMI") -----------------------------------------------------------------------------

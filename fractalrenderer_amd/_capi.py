@@ -165,6 +165,13 @@ SIGNATURES = {
                                       _P(fr_output)]),
     "fr_render_deep_ship_async": (C.c_int, [C.c_void_p, _P(fr_params), _P(fr_deep_view), C.c_uint32, C.c_uint32, _P(fr_shard),
                                             _P(fr_output), C.c_void_p]),
+    "fr_deep_phoenix_validate": (C.c_int, [_P(fr_params), _P(fr_phoenix_params), _P(fr_deep_view), C.c_uint32, C.c_uint32]),
+    "fr_deep_phoenix_reference_orbit": (C.c_int, [_P(fr_deep_view), _P(fr_phoenix_params), C.c_double, C.c_int32, C.c_void_p,
+                                                  _P(C.c_int32)]),
+    "fr_render_deep_phoenix": (C.c_int, [C.c_void_p, _P(fr_params), _P(fr_phoenix_params), _P(fr_deep_view), C.c_uint32,
+                                         C.c_uint32, _P(fr_shard), _P(fr_output)]),
+    "fr_render_deep_phoenix_async": (C.c_int, [C.c_void_p, _P(fr_params), _P(fr_phoenix_params), _P(fr_deep_view), C.c_uint32,
+                                               C.c_uint32, _P(fr_shard), _P(fr_output), C.c_void_p]),
     "fr_ctx_last_deep_steps": (C.c_int, [C.c_void_p, _P(C.c_uint64)]),
     "fr_ctx_last_deepx_steps": (C.c_int, [C.c_void_p, _P(C.c_uint64)]),
     "fr_ctx_last_deep_ship_steps": (C.c_int, [C.c_void_p, _P(C.c_uint64)]),
@@ -320,6 +327,7 @@ INTERNAL_SIGNATURES = {
     "fr_deepx_ship_bla_table": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),   # fr_internal.h: tests
     "fr_deep_ship_bla_table": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),   # fr_internal.h: tests
     "fr_deep_bla_builds": (C.c_int64, [C.c_void_p, C.c_int, C.c_int]),                        # fr_internal.h: tests
+    "fr_deep_orbit_generation": (C.c_int64, [C.c_void_p, C.c_int, C.c_int]),                  # fr_internal.h: tests
     "fr_deepx_validate": (C.c_int, [_P(fr_params), _P(fr_deepx_view), C.c_uint32, C.c_uint32]),        # fr_internal.h: tests
     "fr_deepx_ship_validate": (C.c_int, [_P(fr_params), _P(fr_deepx_view), C.c_uint32, C.c_uint32]),   # fr_internal.h: tests
     "fr_deep_ship_validate": (C.c_int, [_P(fr_params), _P(fr_deep_view), C.c_uint32, C.c_uint32]),     # fr_internal.h: tests

@@ -23,6 +23,11 @@
  *
  * The six paths share one host side: what their validators ask is a row of kRules read by validate_params, either view struct
  * goes through resolve_view, and the six reference-orbit entry points start with orbit_request.
+ *
+ * Deep Phoenix views (fr_render_deep_phoenix): a second-order recurrence, Z' = Z^2 + C + r Z_prev + p Z, as one more formula of
+ * the same loop (kOrbitPhoenix: two products more per component and the previous point kept), p and r from floats
+ * (phoenix_terms); its validator stands apart from kRules, since it reads fr_phoenix_params and Phoenix's own field rules
+ * (fr_phoenix_validate), and goes through resolve_view like the others.  |p|, |r| < 2^32 keeps the escaping point below 2^36.
  */
 #include "fr_internal.h"
 
@@ -349,7 +354,24 @@ static void store_extended(const uint64_t* zr, const uint64_t* zi, fx_fmt fmt, d
 
 /* The recurrence: kOrbitMandelbrot Z^2 + C; kOrbitShip (|Zr| + i |Zi|)^2 + C, whose imaginary product is never negative
  * (fr_render_deep_ship). */
-typedef enum { kOrbitMandelbrot = 0, kOrbitShip = 1 } orbit_formula;
+typedef enum { kOrbitMandelbrot = 0, kOrbitShip = 1, kOrbitPhoenix = 2 } orbit_formula;
+
+/* kOrbitPhoenix: Z' = Z^2 + C + r Q + p Z with Q the point before Z (fr_render_deep_phoenix); P = floor(p 2^F), R = floor(r 2^F) */
+typedef struct { uint64_t p[kMaxLimbs], r[kMaxLimbs]; } phoenix_terms;
+
+/* acc += floor(a b / 2^F): a, b and acc signed values of L limbs */
+static void add_mul_floor(uint64_t* acc, const uint64_t* a, const uint64_t* b, fx_fmt fmt)
+{
+    uint64_t ma[kMaxLimbs], mb[kMaxLimbs], pr[2 * kMaxLimbs], t[kMaxLimbs];
+    memcpy(ma, a, sizeof(uint64_t) * (size_t)fmt.L);
+    memcpy(mb, b, sizeof(uint64_t) * (size_t)fmt.L);
+    const int na = is_negative(ma, fmt.L), nb = is_negative(mb, fmt.L);
+    if (na) negate(ma, fmt.L);
+    if (nb) negate(mb, fmt.L);
+    mul_mag(pr, ma, mb, fmt.L);
+    floor_shift(t, pr, fmt.F, na != nb, fmt);
+    add_n(acc, acc, t, fmt.L);
+}
 
 /* T = floor(bailout^2 2^(2F)) in 2L + 1 limbs: |Z|^2 2^(2F) = Zr^2 + Zi^2 is an integer, so "> bailout^2" is "> T" exactly */
 static void bailout_threshold(uint64_t* T, fx_fmt fmt, float bailout)
@@ -367,13 +389,15 @@ static void bailout_threshold(uint64_t* T, fx_fmt fmt, float bailout)
 }
 
 /* out_exp NULL: Z_n as doubles; else the extended storage.  (sr0, si0) the orbit's first point, NULL for 0 (the Julia views'
- * primary orbit starts at the view's centre, fr_render_deep_julia). */
+ * primary orbit starts at the view's centre, fr_render_deep_julia).  ph: kOrbitPhoenix's P and R, NULL for the other formulas. */
 static int orbit_loop(const uint64_t* cr, const uint64_t* ci, const uint64_t* sr0, const uint64_t* si0, fx_fmt fmt,
-                      orbit_formula formula, int32_t max_iter, float bailout, double* out_xy, int32_t* out_exp,
-                      int32_t* out_len)
+                      orbit_formula formula, const phoenix_terms* ph, int32_t max_iter, float bailout, double* out_xy,
+                      int32_t* out_exp, int32_t* out_len)
 {
     const int L = fmt.L, L2 = 2 * fmt.L;
     uint64_t zr[kMaxLimbs], zi[kMaxLimbs], ar[kMaxLimbs], ai[kMaxLimbs], t0[kMaxLimbs], t1[kMaxLimbs];
+    uint64_t qr[kMaxLimbs], qi[kMaxLimbs], wr[kMaxLimbs], wi[kMaxLimbs];   /* Phoenix: Z_{n-1}, and Z_n while Z_{n+1} is formed */
+    memset(qr, 0, sizeof qr); memset(qi, 0, sizeof qi);
     uint64_t sr[2 * kMaxLimbs + 1], si[2 * kMaxLimbs + 1], pr[2 * kMaxLimbs], ssum[2 * kMaxLimbs + 1], T[2 * kMaxLimbs + 1];
     memset(zr, 0, sizeof zr); memset(zi, 0, sizeof zi);
     memset(sr, 0, sizeof sr); memset(si, 0, sizeof si);
@@ -406,6 +430,10 @@ static int orbit_loop(const uint64_t* cr, const uint64_t* ci, const uint64_t* sr
         add_n(ssum, sr, si, L2 + 1);
         if (cmp_n(ssum, T, L2 + 1) > 0) break;                     /* |Z_n|^2 > bailout^2 */
         mul_mag(pr, ar, ai, L);
+        if (formula == kOrbitPhoenix) {
+            memcpy(wr, zr, sizeof(uint64_t) * (size_t)L);
+            memcpy(wi, zi, sizeof(uint64_t) * (size_t)L);
+        }
         /* Re = floor(Zr^2 / 2^F) - floor(Zi^2 / 2^F) + Cr,  Im = floor(2 Zr Zi / 2^F) + Ci (the ship: 2 |Zr| |Zi|) */
         floor_shift(t0, sr, fmt.F, 0, fmt);
         floor_shift(t1, si, fmt.F, 0, fmt);
@@ -413,6 +441,14 @@ static int orbit_loop(const uint64_t* cr, const uint64_t* ci, const uint64_t* sr
         add_n(zr, zr, cr, L);
         floor_shift(t0, pr, fmt.F - 1, formula == kOrbitShip ? 0 : nr != ni, fmt);
         add_n(zi, t0, ci, L);
+        if (formula == kOrbitPhoenix) {     /* ... + floor(R Q / 2^F) + floor(P Z / 2^F) per component, then Q = Z_n */
+            add_mul_floor(zr, ph->r, qr, fmt);
+            add_mul_floor(zr, ph->p, wr, fmt);
+            add_mul_floor(zi, ph->r, qi, fmt);
+            add_mul_floor(zi, ph->p, wi, fmt);
+            memcpy(qr, wr, sizeof(uint64_t) * (size_t)L);
+            memcpy(qi, wi, sizeof(uint64_t) * (size_t)L);
+        }
         if (out_exp) {
             store_extended(zr, zi, fmt, out_xy + 2 * (n + 1), out_exp + n + 1);
         } else {
@@ -857,7 +893,7 @@ int fr_deep_reference_orbit(const fr_deep_view* v, double zoom, int32_t max_iter
     deep_resolved r;
     const int st = orbit_request("fr_deep_reference_orbit", out_xy && out_len, v, NULL, &zoom, max_iter, bailout, NULL, &r);
     if (st != FR_OK) return st;
-    return orbit_loop(r.cr, r.ci, NULL, NULL, r.fmt, kOrbitMandelbrot, max_iter, bailout, out_xy, NULL, out_len);
+    return orbit_loop(r.cr, r.ci, NULL, NULL, r.fmt, kOrbitMandelbrot, NULL, max_iter, bailout, out_xy, NULL, out_len);
 }
 
 int fr_deep_ship_reference_orbit(const fr_deep_view* v, double zoom, int32_t max_iter, float bailout, double* out_xy,
@@ -866,7 +902,7 @@ int fr_deep_ship_reference_orbit(const fr_deep_view* v, double zoom, int32_t max
     deep_resolved r;
     const int st = orbit_request("fr_deep_ship_reference_orbit", out_xy && out_len, v, NULL, &zoom, max_iter, bailout, NULL, &r);
     if (st != FR_OK) return st;
-    return orbit_loop(r.cr, r.ci, NULL, NULL, r.fmt, kOrbitShip, max_iter, bailout, out_xy, NULL, out_len);
+    return orbit_loop(r.cr, r.ci, NULL, NULL, r.fmt, kOrbitShip, NULL, max_iter, bailout, out_xy, NULL, out_len);
 }
 
 int fr_deepx_reference_orbit(const fr_deepx_view* v, int32_t max_iter, float bailout, double* out_mant_xy, int32_t* out_exp2,
@@ -876,7 +912,7 @@ int fr_deepx_reference_orbit(const fr_deepx_view* v, int32_t max_iter, float bai
     const int st = orbit_request("fr_deepx_reference_orbit", out_mant_xy && out_exp2 && out_len, NULL, v, NULL, max_iter, bailout,
                                  NULL, &r);
     if (st != FR_OK) return st;
-    return orbit_loop(r.cr, r.ci, NULL, NULL, r.fmt, kOrbitMandelbrot, max_iter, bailout, out_mant_xy, out_exp2, out_len);
+    return orbit_loop(r.cr, r.ci, NULL, NULL, r.fmt, kOrbitMandelbrot, NULL, max_iter, bailout, out_mant_xy, out_exp2, out_len);
 }
 
 int fr_deepx_ship_reference_orbit(const fr_deepx_view* v, int32_t max_iter, float bailout, double* out_mant_xy,
@@ -886,7 +922,7 @@ int fr_deepx_ship_reference_orbit(const fr_deepx_view* v, int32_t max_iter, floa
     const int st = orbit_request("fr_deepx_ship_reference_orbit", out_mant_xy && out_exp2 && out_len, NULL, v, NULL, max_iter,
                                  bailout, NULL, &r);
     if (st != FR_OK) return st;
-    return orbit_loop(r.cr, r.ci, NULL, NULL, r.fmt, kOrbitShip, max_iter, bailout, out_mant_xy, out_exp2, out_len);
+    return orbit_loop(r.cr, r.ci, NULL, NULL, r.fmt, kOrbitShip, NULL, max_iter, bailout, out_mant_xy, out_exp2, out_len);
 }
 
 /* ---- deep Julia views (fr_render_deep_julia, fr_render_deepx_julia) -----------------------------------------------------------
@@ -919,8 +955,8 @@ static int julia_orbits(const deep_resolved* z, const double* c, int32_t max_ite
     uint64_t cr[kMaxLimbs], ci[kMaxLimbs];
     double_to_fixed(c[0], z->fmt, cr);
     double_to_fixed(c[1], z->fmt, ci);
-    if ((st = orbit_loop(cr, ci, z->cr, z->ci, z->fmt, kOrbitMandelbrot, max_iter, bailout, p_xy, p_exp, p_len)) != FR_OK) return st;
-    return orbit_loop(cr, ci, NULL, NULL, z->fmt, kOrbitMandelbrot, max_iter, bailout, q_xy, q_exp, q_len);
+    if ((st = orbit_loop(cr, ci, z->cr, z->ci, z->fmt, kOrbitMandelbrot, NULL, max_iter, bailout, p_xy, p_exp, p_len)) != FR_OK) return st;
+    return orbit_loop(cr, ci, NULL, NULL, z->fmt, kOrbitMandelbrot, NULL, max_iter, bailout, q_xy, q_exp, q_len);
 }
 
 int fr_deep_julia_reference_orbits(const fr_deep_view* v, double c_re, double c_im, double zoom, int32_t max_iter, float bailout,
@@ -945,4 +981,78 @@ int fr_deepx_julia_reference_orbits(const fr_deepx_view* v, double c_re, double 
                                  max_iter, bailout, c, &r);
     if (st != FR_OK) return st;
     return julia_orbits(&r, c, max_iter, bailout, out_p_mant_xy, out_p_exp2, out_p_len, out_q_mant_xy, out_q_exp2, out_q_len);
+}
+
+/* ---- deep Phoenix views (fr_render_deep_phoenix) ------------------------------------------------------------------------------
+ * p and r are floats: floor(v 2^F) of the float's exact value (an integer already wherever F holds the float's last bit). */
+static void float_to_fixed_floor(float f, fx_fmt fmt, uint64_t* out)
+{
+    memset(out, 0, sizeof(uint64_t) * (size_t)fmt.L);
+    if (f == 0.0f) return;
+    int ex = 0;
+    const double mant = frexp(fabs((double)f), &ex);
+    const uint64_t mi = (uint64_t)ldexp(mant, 53);               /* |f| = mi 2^(ex - 53) */
+    const long s = (long)ex - 53 + fmt.F;
+    int lost = 0;
+    if (s >= 0) {
+        out[0] = mi;
+        shl_bits(out, fmt.L, (int)s);                            /* |f| < 2^32: below 2^(F + 32) */
+    } else if (-s < 64) {
+        out[0] = mi >> -s;
+        lost = (mi & ((1ull << -s) - 1)) != 0;
+    } else {
+        lost = 1;
+    }
+    if (f < 0.0f) {                                              /* floor of a negative value: away from zero */
+        if (lost) add_one(out, fmt.L);
+        negate(out, fmt.L);
+    }
+}
+
+/* the rule both entry points put on p and r beyond fr_phoenix_validate's: inside the fixed point's range, as a centre is */
+static int check_phoenix_terms(const fr_phoenix_params* ph)
+{
+    if (!isfinite(ph->phoenix_p) || !isfinite(ph->phoenix_r) || !(fabsf(ph->phoenix_p) < 4294967296.0f) ||
+        !(fabsf(ph->phoenix_r) < 4294967296.0f))
+        return fr_set_error(FR_ERR_INVALID_ARG, "deep Phoenix views need finite p and r with |p|, |r| < 2^32");
+    return FR_OK;
+}
+
+int fr_deep_phoenix_validate(const fr_params* p, const fr_phoenix_params* ph, const fr_deep_view* v, uint32_t width, uint32_t height)
+{
+    if (!p || !ph || !v) return fr_set_error(FR_ERR_INVALID_ARG, "params/phoenix params/deep view is NULL");
+    if (p->fractal_type != FR_FRACTAL_PHOENIX)
+        return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deep_phoenix renders FR_FRACTAL_PHOENIX only (got %d)", p->fractal_type);
+    if (p->precision != FR_PRECISION_F64)
+        return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deep_phoenix needs FR_PRECISION_F64 (got %d)", p->precision);
+    if (width == 0 || height == 0)
+        return fr_set_error(FR_ERR_INVALID_ARG, "width and height must be > 0 (got %ux%u)", width, height);
+    fr_params q = *p;                                            /* the double centre is not read */
+    q.center_x = 0.0; q.center_y = 0.0;
+    int st = fr_phoenix_validate(&q, ph, width, height);
+    if (st != FR_OK) return st;
+    if ((st = check_phoenix_terms(ph)) != FR_OK) return st;
+    if (ph->use_julia_set)
+        return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deep_phoenix: use_julia_set is not available (a Julia-mode Phoenix frame "
+                            "starts every pixel from z = 0 with the same c, so it is one colour at any depth)");
+    if ((st = check_zoom(p->zoom)) != FR_OK) return st;
+    if (p->flags & (OTHER_FLAGS | JULIA_FLAGS))
+        return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deep_phoenix: the BLA flags are not available (their tables belong to the "
+                            "Mandelbrot, Burning Ship and Julia paths; Phoenix has none)");
+    deep_resolved r;
+    return resolve_view(v, NULL, p->zoom, 1, &r);
+}
+
+int fr_deep_phoenix_reference_orbit(const fr_deep_view* v, const fr_phoenix_params* ph, double zoom, int32_t max_iter, double* out_xy,
+                                    int32_t* out_len)
+{
+    if (!ph) return fr_set_error(FR_ERR_INVALID_ARG, "fr_deep_phoenix_reference_orbit: phoenix params is NULL");
+    deep_resolved r;
+    int st = orbit_request("fr_deep_phoenix_reference_orbit", out_xy && out_len, v, NULL, &zoom, max_iter, 2.0f, NULL, &r);
+    if (st != FR_OK) return st;
+    if ((st = check_phoenix_terms(ph)) != FR_OK) return st;
+    phoenix_terms t;
+    float_to_fixed_floor(ph->phoenix_p, r.fmt, t.p);
+    float_to_fixed_floor(ph->phoenix_r, r.fmt, t.r);
+    return orbit_loop(r.cr, r.ci, NULL, NULL, r.fmt, kOrbitPhoenix, &t, max_iter, 2.0f, out_xy, NULL, out_len);
 }

@@ -20,6 +20,7 @@
 #include "fr_phoenix.hip.h"
 #include "fr_mandelbulb.hip.h"
 #include "fr_deep.hip.h"
+#include "fr_deep_phoenix.hip.h"
 #include "fr_deepseq.hip.h"
 #include "fr_tuning.h"
 #include "fr_plan.h"
@@ -43,11 +44,11 @@ struct OrbitKey {
     char* y;
     int32_t bits, max_iter;
     float bailout;              /* compared by its bits */
-    uint64_t c_bits[2];         /* Julia: the bits of c (0 in the other formulas' slots) */
+    uint64_t c_bits[2];         /* Julia: the bits of c; Phoenix: the bits of its floats p and r (0 in the other formulas' slots) */
 };
 
 /* the formula of a deep view: the index of its cache slots */
-enum { kMandel = 0, kShip = 1, kJulia = 2 };
+enum { kMandel = 0, kShip = 1, kJulia = 2, kPhoenix = 3, kFormulas = 4 };
 
 /* One cache slot of reference orbits of deep views: the buffers and what they hold */
 struct DeepOrbit {
@@ -149,8 +150,9 @@ struct fr_ctx {
      * pinned and one device block of cap points each -- the plain doubles, the mantissa pairs, the exponents, in this order:
      * fr_render_deepx, fr_render_deepx_ship, fr_render_deepx_julia and the sequences, with the tables of FR_FLAG_DEEPX_BLA,
      * FR_FLAG_DEEPX_SHIP_BLA, FR_FLAG_DEEPX_JULIA_BLA.  The six paths share nothing.  A Julia slot holds two orbits: Q in the
-     * first half of every array, P in the second. */
-    DeepSlot deep[2][3];
+     * first half of every array, P in the second.  A seventh slot, deep[0][kPhoenix], is fr_render_deep_phoenix's: plain doubles,
+     * no table; Phoenix has no extended path, so deep[1][kPhoenix] stays empty. */
+    DeepSlot deep[2][kFormulas];
 };
 
 static DeepSlot& deep_slot(fr_ctx* c, bool ext, int f) { return c->deep[ext ? 1 : 0][f]; }
@@ -807,8 +809,8 @@ static int orbit_slot_prepare(fr_ctx* c, DeepOrbit& o, const BlaSlot* t, hipStre
 }
 
 /* what differs per formula on the host: the orbits a slot holds (a Julia slot: Q, then P) and the double2 per table entry */
-static const struct { int orbits; size_t ab_per_entry; } kFormula[3] = {
-    {1, MandelFormula::kAbPerEntry}, {1, ShipFormula::kAbPerEntry}, {2, JuliaFormula::kAbPerEntry}};
+static const struct { int orbits; size_t ab_per_entry; } kFormula[kFormulas] = {
+    {1, MandelFormula::kAbPerEntry}, {1, ShipFormula::kAbPerEntry}, {2, JuliaFormula::kAbPerEntry}, {1, 0 /* Phoenix: no table */}};
 
 /* a view as the enqueue side reads it: the centre strings, the zoom as a pair (an fp64 view: (zoom, 0)) and the fraction bits of
  * its orbit; zoom: the string of an extended view, which the orbit does not depend on (nullptr: an fp64 view) */
@@ -821,8 +823,11 @@ struct DeepAt {
 /* The reference orbit(s) of the view in the path's slot unless the slot holds them already (keyed by the centre strings, the
  * fraction bits, max_iter, the bailout and, in a Julia slot, the bits of c).  One orbit, or Julia's Q at point 0 and P half the
  * capacity behind it (kFormula); ext: the extended storage, whose plain doubles ldexp(mantissa, exponent) are formed here.
- * Per array and orbit, what the host wrote is uploaded and nothing else: no kernel reads a point past an orbit's length. */
-static int deep_slot_fill(fr_ctx* c, int f, bool ext, const fr_params* p, const DeepAt& at, hipStream_t stream)
+ * Per array and orbit, what the host wrote is uploaded and nothing else: no kernel reads a point past an orbit's length.
+ * The Phoenix slot (ph; fp64 only): keyed by the bits of p and r where Julia's has c, and by the shader's fixed bailout 2,
+ * since p->bailout is not read. */
+static int deep_slot_fill(fr_ctx* c, int f, bool ext, const fr_params* p, const DeepAt& at, hipStream_t stream,
+                          const fr_phoenix_params* ph = nullptr)
 {
     DeepSlot& s = deep_slot(c, ext, f);
     DeepOrbit& o = s.o;
@@ -833,7 +838,12 @@ static int deep_slot_fill(fr_ctx* c, int f, bool ext, const fr_params* p, const 
         memcpy(&cb[0], &p->julia_c_real, sizeof(uint64_t));
         memcpy(&cb[1], &p->julia_c_imag, sizeof(uint64_t));
     }
-    if (orbit_key_matches(o.key, at.cx, at.cy, at.bits, max_iter, p->bailout) && o.key.c_bits[0] == cb[0] && o.key.c_bits[1] == cb[1])
+    if (f == kPhoenix) {
+        memcpy(&cb[0], &ph->phoenix_p, sizeof(float));
+        memcpy(&cb[1], &ph->phoenix_r, sizeof(float));
+    }
+    const float bailout = f == kPhoenix ? 2.0f : p->bailout;
+    if (orbit_key_matches(o.key, at.cx, at.cy, at.bits, max_iter, bailout) && o.key.c_bits[0] == cb[0] && o.key.c_bits[1] == cb[1])
         return FR_OK;
     const size_t point_bytes = ext ? 2 * sizeof(double2) + sizeof(int32_t) : sizeof(double2);
     const int ps = orbit_slot_prepare(c, o, &s.t, stream, (size_t)norb * ((size_t)max_iter + 1), point_bytes);
@@ -846,7 +856,9 @@ static int deep_slot_fill(fr_ctx* c, int f, bool ext, const fr_params* p, const 
     const fr_deepx_view x = {at.cx, at.cy, at.zoom, at.bits, 0};
     int32_t len[2] = {0, 0};                                      /* of the orbit at point 0, of Julia's P */
     int st;
-    if (f == kJulia)
+    if (f == kPhoenix)
+        st = fr_deep_phoenix_reference_orbit(&v, ph, p->zoom, max_iter, plain, &len[0]);
+    else if (f == kJulia)
         st = ext ? fr_deepx_julia_reference_orbits(&x, p->julia_c_real, p->julia_c_imag, max_iter, p->bailout, mant + 2 * second,
                                                    exp2 + second, &len[1], mant, exp2, &len[0])
                  : fr_deep_julia_reference_orbits(&v, p->julia_c_real, p->julia_c_imag, p->zoom, max_iter, p->bailout,
@@ -871,7 +883,7 @@ static int deep_slot_fill(fr_ctx* c, int f, bool ext, const fr_params* p, const 
         }
     }
     FR_HIP_TRY(hipStreamSynchronize(stream));     /* a later render of this view may go to another stream */
-    const int ks = orbit_key_store(o.key, at.cx, at.cy, at.bits, max_iter, p->bailout);
+    const int ks = orbit_key_store(o.key, at.cx, at.cy, at.bits, max_iter, bailout);
     if (ks != FR_OK) return ks;
     o.key.c_bits[0] = cb[0]; o.key.c_bits[1] = cb[1];
     o.len = len[0]; o.len_p = len[1];
@@ -1149,6 +1161,37 @@ static int enqueue_deepx_at(fr_ctx* c, int f, const fr_params* p, const fr_deepx
     if (f == kShip)
         return enqueue_deep_view<DeepShipX>(c, p, at, W, H, shard, rgba, nu, iter, stream, out_frame, [](auto&) {});
     return enqueue_deep_view<DeepMandelX>(c, p, at, W, H, shard, rgba, nu, iter, stream, out_frame, [](auto&) {});
+}
+
+/* ---- deep Phoenix views (fr_deep_phoenix.hip.h) ---------------------------------------------------------------------------
+ * enqueue_deep_view's steps for the path that stands apart from DeepBlock: the rows of this part, the orbit in the Phoenix slot
+ * (deep_slot_fill), DeepPhoenixArgs filled as enqueue_phoenix fills PhoenixArgs, then one pass with unlimited stealing at the
+ * occupancy cached in the slot. */
+static int enqueue_deep_phoenix(fr_ctx* c, const fr_params* p, const fr_phoenix_params* ph, const fr_deep_view* v, uint32_t W,
+                                uint32_t H, const fr_shard* shard, float* rgba, void* nu, int32_t* iter, hipStream_t stream,
+                                bool out_frame)
+{
+    fr_shard norm;
+    uint32_t rows_local = 0;
+    const int sh = begin_shard(c, shard, H, &norm, &rows_local);
+    if (sh != FR_OK || rows_local == 0) return sh;
+    const DeepAt at = {v->center_x, v->center_y, nullptr, p->zoom, 0, v->frac_bits ? v->frac_bits : fr_deep_frac_bits(p->zoom)};
+    const int os = deep_slot_fill(c, kPhoenix, false, p, at, stream, ph);
+    if (os != FR_OK) return os;
+
+    DeepSlot& s = deep_slot(c, false, kPhoenix);
+    DeepPhoenixArgs a;
+    memset(&a, 0, sizeof(a));
+    a.orbit = reinterpret_cast<const double2*>(s.o.dev); a.n_ref = s.o.len - 1;
+    a.max_iter = p->max_iterations; a.aa = p->antialiasing_samples;
+    a.zoom = p->zoom;
+    a.p = (double)ph->phoenix_p; a.r = (double)ph->phoenix_r;
+    a.stripe_density = p->stripe_density;
+    a.brightness = p->color_brightness; a.saturation = p->color_saturation; a.contrast = p->color_contrast;
+    a.flags = p->flags;
+    a.g = tile_geom(W, H, rows_local, &norm, out_frame);
+    a.rgba = reinterpret_cast<float4*>(rgba); a.nu = (double*)nu; a.iter = iter;
+    return launch_one_pass(c, stream, "deep_phoenix_kernel", deep_phoenix_kernel, a, a.g, a.q, s.wg_per_cu[0][0], false);
 }
 
 /* ---- deep zoom sequences (fr_deep_sequence; the rules are in the header, the host planning in fr_deepseq.c) ---------------
@@ -1555,7 +1598,7 @@ static int enqueue_ssaa_staged(fr_ctx* c, const fr_params* p, uint32_t W, uint32
 }
 
 /* ---- render entry points --------------------------------------------------------------------------------------------
- * fr_render_shard, fr_render_phoenix, fr_render_mandelbulb and the ten deep entry points (fr_render_deep, _deep_de,
+ * fr_render_shard, fr_render_phoenix, fr_render_mandelbulb, fr_render_deep_phoenix and the ten deep entry points (fr_render_deep, _deep_de,
  * _deep_ship, _deepx, _deepx_de, _deepx_ship, _deep_julia, _deepx_julia, _deep_julia_de, _deepx_julia_de; all through
  * deep_entry), each with its _async form:
  * their parameter checks, then render_sync / render_async with the planes beyond fr_output's three (ExtraPlanes;
@@ -1857,6 +1900,12 @@ extern "C" int fr_ctx_last_deepx_steps(fr_ctx* c, uint64_t out[3])
 extern "C" int fr_ctx_last_deepx_ship_steps(fr_ctx* c, uint64_t out[3])
 {
     return last_bla_steps(c, true, kShip, "fr_render_deepx_ship call with FR_FLAG_DEEPX_SHIP_BLA", out);
+}
+
+extern "C" int64_t fr_deep_orbit_generation(fr_ctx* c, int extended, int formula)
+{
+    if (!c || formula < kMandel || formula >= kFormulas) return fr_set_error(FR_ERR_INVALID_ARG, "ctx is NULL or no such formula");
+    return (int64_t)deep_slot(c, extended != 0, formula).o.gen;
 }
 
 extern "C" int64_t fr_deep_bla_builds(fr_ctx* c, int extended, int formula)
@@ -2165,6 +2214,34 @@ extern "C" int fr_render_deepx_julia(fr_ctx* c, const fr_params* p, const fr_dee
 {
     return deep_entry<DeepJuliaX>(nullptr, c, p, v, nullptr, W, H, shard, out, nullptr,
                                       [&] { return fr_deepx_julia_validate(p, v, W, H); });
+}
+
+/* fr_render_deep_phoenix: fr_render_phoenix's arguments with a deep view; its own validator and enqueue step */
+static int check_deep_phoenix(fr_ctx* c, const fr_params* p, const fr_phoenix_params* ph, const fr_deep_view* v, uint32_t W,
+                              uint32_t H, const fr_output* out)
+{
+    if (!c) return fr_set_error(FR_ERR_INVALID_ARG, "ctx is NULL");
+    if (!p || !ph || !v || !out) return fr_set_error(FR_ERR_INVALID_ARG, "params/phoenix params/deep view/out is NULL");
+    return fr_deep_phoenix_validate(p, ph, v, W, H);
+}
+
+extern "C" int fr_render_deep_phoenix_async(fr_ctx* c, const fr_params* p, const fr_phoenix_params* ph, const fr_deep_view* v,
+                                            uint32_t W, uint32_t H, const fr_shard* shard, const fr_output* out, void* hip_stream)
+{
+    const int st = check_deep_phoenix(c, p, ph, v, W, H, out);
+    if (st != FR_OK) return st;
+    return render_async("fr_render_deep_phoenix_async", c, H, shard, out, {}, hip_stream,
+                        [&](auto sh, auto rgba, auto nu, auto iter, auto, auto s, bool out_frame) {
+                            return enqueue_deep_phoenix(c, p, ph, v, W, H, sh, rgba, nu, iter, s, out_frame); });
+}
+
+extern "C" int fr_render_deep_phoenix(fr_ctx* c, const fr_params* p, const fr_phoenix_params* ph, const fr_deep_view* v, uint32_t W,
+                                      uint32_t H, const fr_shard* shard, const fr_output* out)
+{
+    const int st = check_deep_phoenix(c, p, ph, v, W, H, out);
+    if (st != FR_OK) return st;
+    return render_sync(c, p, W, H, shard, out, {}, [&](auto sh, auto rgba, auto nu, auto iter, auto, auto s, bool out_frame) {
+        return enqueue_deep_phoenix(c, p, ph, v, W, H, sh, rgba, nu, iter, s, out_frame); });
 }
 
 /* fr_render_deep_ship_de, fr_render_deepx_ship_de: fr_render_deep_de's five planes on the two ship paths, deriv four doubles per

@@ -366,6 +366,27 @@ class Renderer:
         self._render_call(self._lib.fr_render_deep_ship, self._lib.fr_render_deep_ship_async, (C.byref(p), C.byref(v)), width,
                           height, Precision.F64, rows, rgba, nu, iter, shard, stream, sync)
 
+    def render_deep_phoenix(self, state: FractalState, width: int, height: int, view: Optional[DeepView] = None,
+                            phoenix: Optional[PhoenixParams] = None, *, post_chain: bool = False, rgba=None, nu=None, iter=None,
+                            shard: Optional[Shard] = None, stream: Optional[int] = None, sync: bool = True) -> None:
+        """fr_render_deep_phoenix / fr_render_deep_phoenix_async: a Phoenix view deeper than double precision, by perturbation
+        around one reference orbit of the second-order recurrence computed on the host.  `view` carries the centre as decimal
+        strings; `phoenix` carries phoenix_p and phoenix_r as for render_phoenix() (use_julia_set must stay off: a Julia-mode
+        Phoenix frame is one colour).  The zoom, in [1e-290, 1e3], and every other field come from `state` (its double centre
+        is not read).  Always fp64: nu is float64.  Planes, shard, stream and sync as for render_deep_ship(); the context keeps
+        the Phoenix orbit in a slot of its own.  A view with a zoom string is a ValueError: there are no extended-exponent
+        deltas, BLA or distance estimates on this path."""
+        if view is not None and view.zoom is not None:
+            raise ValueError("render_deep_phoenix takes the zoom from the state: extended views (a zoom string) are not "
+                             "available for Phoenix")
+        p = state.to_params(FractalType.Phoenix, Precision.F64, post_chain)
+        ph = (phoenix or PhoenixParams()).to_c()
+        v = (view or DeepView()).to_c()
+        rows = shard.rows(height) if shard else height
+        self._render_call(self._lib.fr_render_deep_phoenix, self._lib.fr_render_deep_phoenix_async,
+                          (C.byref(p), C.byref(ph), C.byref(v)), width, height, Precision.F64, rows, rgba, nu, iter, shard, stream,
+                          sync)
+
     def render_deepx_ship(self, state: FractalState, width: int, height: int, view: DeepView, *, post_chain: bool = False,
                           rgba=None, nu=None, iter=None, shard: Optional[Shard] = None, stream: Optional[int] = None,
                           sync: bool = True, bla: bool = False) -> None:
@@ -482,7 +503,7 @@ class Renderer:
     def _render_call(self, fn_sync, fn_async, params: tuple, width: int, height: int, precision: Precision, rows: int,
                      rgba, nu, it, shard: Optional[Shard], stream: Optional[int], sync: bool, extra=()) -> None:
         """the planes, the shard and the sync / async entry of render(), render_phoenix(), render_mandelbulb(), render_deep(),
-        render_deep_de(), render_deep_ship(), render_deepx_ship() and render_deep_julia(); params: the entry's arguments between
+        render_deep_de(), render_deep_ship(), render_deepx_ship(), render_deep_julia() and render_deep_phoenix(); params: the entry's arguments between
         the context and the frame size; extra: the planes it writes beyond rgba, nu and iter (_output)"""
         out = self._output(precision, rows, width, rgba, nu, it, extra)
         sh = shard.to_c() if shard else None

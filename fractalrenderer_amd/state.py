@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import enum
 from dataclasses import dataclass, fields
+from typing import Optional
 
 import numpy as np
 
@@ -231,6 +232,19 @@ def deep_ship_reference_orbit(view: DeepView, zoom: float, max_iterations: int, 
     v = view.to_c()
     _capi.check(_capi.lib().fr_deep_ship_reference_orbit(_capi.C.byref(v), float(zoom), int(max_iterations), _F32(bailout),
                                                          buf.ctypes.data, _capi.C.byref(n)))
+    return buf[:n.value].copy()
+
+
+def deep_phoenix_reference_orbit(view: DeepView, zoom: float, max_iterations: int,
+                                 phoenix: Optional[PhoenixParams] = None) -> np.ndarray:
+    """fr_deep_phoenix_reference_orbit: Z_0 .. Z_N of z' = z^2 + c + r z_prev + p z at the view's centre (the shader's fixed
+    bailout 2), as deep_reference_orbit; `phoenix` carries p and r (default: the reference's initialisers)."""
+    buf = np.empty((int(max_iterations) + 1, 2), np.float64)
+    n = _capi.C.c_int32()
+    v = view.to_c()
+    ph = (phoenix or PhoenixParams()).to_c()
+    _capi.check(_capi.lib().fr_deep_phoenix_reference_orbit(_capi.C.byref(v), _capi.C.byref(ph), float(zoom), int(max_iterations),
+                                                            buf.ctypes.data, _capi.C.byref(n)))
     return buf[:n.value].copy()
 
 

@@ -1412,6 +1412,79 @@ int fr_render_deepx_ship_de(fr_ctx* ctx, const fr_params* p, const fr_deepx_view
 int fr_render_deepx_ship_de_async(fr_ctx* ctx, const fr_params* p, const fr_deepx_view* view, const fr_deep_de* de, uint32_t width,
                                   uint32_t height, const fr_shard* shard, const fr_output* out, void* hip_stream);
 
+/* ---- Phoenix views deeper than double precision --------------------------------------------------------------------------
+ * fr_render_phoenix (above) below the 1e-13 wall of its double centre: perturbation around one reference orbit with rebasing,
+ * for z' = z^2 + c + r z_prev + p z.  The view is a fr_deep_view (p->center_x / p->center_y ignored), p->zoom in [1e-290, 1e3];
+ * deltas are fp64.  The recurrence is second order, and so is everything below: the reference orbit is read at two indices, a
+ * sample carries two deltas, and a rebase restores a pair of values.
+ *
+ * Validation (fr_deep_phoenix_validate), in this order: a NULL argument is FR_ERR_INVALID_ARG; p->fractal_type must be
+ * FR_FRACTAL_PHOENIX and p->precision FR_PRECISION_F64, otherwise FR_ERR_UNSUPPORTED; the frame size and the fields Phoenix
+ * reads, as fr_render_phoenix checks them (phoenix_p and phoenix_r finite, use_julia_set 0 or 1, reserved 0); |p|, |r| < 2^32,
+ * the range of the orbit's fixed point, as for a centre; use_julia_set must be 0 -- a Julia-mode Phoenix frame starts every
+ * pixel from z = 0 with the same c and is one colour (see fr_render_phoenix), so a deep view of it is FR_ERR_UNSUPPORTED; the
+ * zoom in [1e-290, 1e3]; every BLA flag (FR_FLAG_DEEP_BLA .. FR_FLAG_DEEPX_JULIA_BLA) is FR_ERR_UNSUPPORTED, Phoenix has no
+ * table; then the view as fr_render_deep checks it (reserved, frac_bits, the centre strings).  bailout, color_offset,
+ * interior_style, the orbit trap, stripe_enabled and use_perturbation are ignored as fr_render_phoenix ignores them: the
+ * bailout is the shader's fixed 2.  fr_render_deep and the other deep entry points keep rejecting FR_FRACTAL_PHOENIX.
+ *
+ * Reference orbit: fr_render_deep's fixed point (F fraction bits, the centre strings parsed as there).  P = floor(p 2^F) and
+ * R = floor(r 2^F) of the floats' exact values; Z_{-1} = Z_0 = 0; with Q = Z_{n-1}
+ *   Re = floor(Zr Zr / 2^F) - floor(Zi Zi / 2^F) + Cr + floor(R Qr / 2^F) + floor(P Zr / 2^F)
+ *   Im = floor(2 Zr Zi / 2^F) + Ci + floor(R Qi / 2^F) + floor(P Zi / 2^F)
+ * floor being the arithmetic shift of the signed product.  It stops at the first N with |Z_N|^2 > 4, compared exactly, or at
+ * N = max_iterations; Z_0 .. Z_N are stored as doubles, rounded to nearest.  With p = r = 0 it is fr_deep_reference_orbit's
+ * orbit at bailout 2, bit for bit.
+ *
+ * Per sample (x, y) and sub-sample s = 0 .. aa*aa-1 with sx = s / aa (OUTER), sy = s % aa: dc is the Phoenix shader's viewport
+ * map (phoenix.comp:103-110) less the centre, which is fr_render_deep_ship's map above, operation for operation.  The state is
+ * dz, dq (the delta of the previous point) and m, all 0 at the start; Z_{-1} = Z_0 = 0.  For i = 0 .. max_iter-1, with
+ * p and r widened to double:
+ *   t   = (((Z_m.x + Z_m.x) + dz.x) + p,  (Z_m.y + Z_m.y) + dz.y)
+ *   dz' = (((t.x dz.x - t.y dz.y) + r dq.x) + dc.x,  ((t.x dz.y + t.y dz.x) + r dq.y) + dc.y)
+ *   dq' = dz;  m += 1;  z = Z_m + dz';  q = Z_{m-1} + dq';  r2 = z.x z.x + z.y z.y
+ *   r2 > 4:                                                       escaped at i, lastZ = z
+ *   else if r2 + (r r)(q.x q.x + q.y q.y) < (dz'.x dz'.x + dz'.y dz'.y) + (r r)(dq'.x dq'.x + dq'.y dq'.y)  or  m == N:
+ *                                                                 rebase: dz = z, dq = q, m = 0
+ *   else:                                                         dz = dz', dq = dq'
+ * each operation one fp64 rounding as written (no contraction).  Since Z_{-1} = Z_0 = 0, the two deltas after a rebase are the
+ * two whole values and the step at m = 0 is the recurrence itself.
+ *
+ * The rebase rule weighs the previous point by |r|, which is how strongly it feeds the next update.  At r = 0 it is exactly
+ * fr_render_deep's rule.  For r of order 1 it rebases only when the whole PAIR (z, q) is smaller than the pair of deltas, so a
+ * rebase never puts an O(1) term r q next to pixel-dependent terms many orders below it.  This is an empirical rule, not a
+ * theorem: it was checked against the exact fixed-point iteration of every pixel on the views of tests/deep_phoenix_ref.py
+ * (zooms 3 down to 1e-100, r from 0 to -0.5), where the escape index agrees everywhere.
+ *
+ * Planes: iter and nu (double) are sample (0,0)'s i and smooth count, max_iterations for interior samples; rgba is the fp64
+ * Phoenix path's colour stage unchanged -- the smooth count of (i, lastZ), then the colour of (smooth / max_iter, smooth,
+ * lastZ) narrowed to float, flow stripes when stripe_density > 0.01, the aa x aa average -- and FR_FLAG_POST_CHAIN the post
+ * chain with Phoenix's floors.  lastZ of a sample that never escaped is Z_m + dz of its final state, the z of its last update.  Shards, FR_MEM_HOST / FR_MEM_DEVICE, FR_LAYOUT_FRAME, "timing", fr_ctx_last_kernel_ms and
+ * fr_ctx_last_grid as for fr_render_deep_ship.
+ *
+ * The context keeps the most recent Phoenix orbit on the device in a slot of its own, keyed by the centre strings, F,
+ * max_iterations and the bits of p and r: no other deep path evicts it, and it evicts none of theirs.
+ *
+ * Out of scope: extended exponents below 1e-290, BLA, distance estimates, sequences, fr_node, .franim and Julia mode. */
+#define FR_HAS_DEEP_PHOENIX 1
+
+/* What fr_render_deep_phoenix checks of its arguments, the centre strings parsed included (no context needed). */
+int fr_deep_phoenix_validate(const fr_params* p, const fr_phoenix_params* ph, const fr_deep_view* view, uint32_t width,
+                             uint32_t height);
+
+/* Z_0 .. Z_N of the view's centre (host only): out_xy holds (max_iter + 1) pairs, *out_len receives N + 1.  Reads ph's p and r
+ * (finite, below 2^32); zoom, in [1e-290, 1e3], chooses the automatic fraction bits as in fr_deep_reference_orbit. */
+int fr_deep_phoenix_reference_orbit(const fr_deep_view* view, const fr_phoenix_params* ph, double zoom, int32_t max_iter,
+                                    double* out_xy, int32_t* out_len);
+
+/* fr_render_deep_ship's contract (planes, memory kinds, FR_LAYOUT_FRAME, shards, options, fr_ctx_last_kernel_ms / _grid) */
+int fr_render_deep_phoenix(fr_ctx* ctx, const fr_params* p, const fr_phoenix_params* ph, const fr_deep_view* view, uint32_t width,
+                           uint32_t height, const fr_shard* shard, const fr_output* out);
+
+/* fr_render_deep_async's contract: a render of a new view computes its orbit on the host first and is never launch-only */
+int fr_render_deep_phoenix_async(fr_ctx* ctx, const fr_params* p, const fr_phoenix_params* ph, const fr_deep_view* view,
+                                 uint32_t width, uint32_t height, const fr_shard* shard, const fr_output* out, void* hip_stream);
+
 /* ---- frames over the GPUs of a node (BASELINE.json north_star: "tiled across the 8 GPUs of one node as disjoint row
  * bands with a final RCCL gather over xGMI") -----------------------------------------------------------------------------
  * New design, no reference counterpart: the reference renders on the one GPU it picked (src/vk_engine.cpp:608).  What it

@@ -318,6 +318,10 @@ INTERNAL_SIGNATURES = {
     "fr_ctx_last_whole_blocks": (C.c_int, [C.c_void_p, _P(C.c_uint64)]),
     "fr_plan_whole_blocks": (C.c_int, [_P(fr_params), C.c_uint32, C.c_uint32, _P(fr_shard), C.c_int, _P(C.c_char_p),
                                        _P(C.c_int64), C.c_int, C.c_int]),
+    "fr_fold_describe": (C.c_int, [_P(fr_params), C.c_uint32, C.c_uint32, _P(fr_shard), _P(C.c_char_p), _P(C.c_int64), C.c_int,
+                                   _P(C.c_int64)]),
+    "fr_ctx_last_fold": (C.c_int, [C.c_void_p]),
+    "fr_fold_division": (C.c_int, [C.c_uint32, C.c_uint64, _P(C.c_uint32), _P(C.c_uint32)]),
     "fr_node_set_tuning": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int64]),
     "fr_node_rccl_usable": (C.c_int, [C.c_void_p]),
     "fr_node_mapped_runtimes": (C.c_int, [C.c_char_p, C.c_size_t]),
@@ -333,7 +337,7 @@ INTERNAL_SIGNATURES = {
     "fr_deep_ship_validate": (C.c_int, [_P(fr_params), _P(fr_deep_view), C.c_uint32, C.c_uint32]),     # fr_internal.h: tests
     "fr_deepseq_resolve": (C.c_int, [_P(fr_params), _P(fr_deep_sequence_desc), C.c_uint32, C.c_uint32, C.c_void_p]),   # fr_internal.h: tests
 }
-PUBLIC_OPTIONS = ("periodicity", "staging", "shards", "tile_kernel", "timing", "diag_buffer", "diag_stride")
+PUBLIC_OPTIONS = ("periodicity", "staging", "shards", "tile_kernel", "fold", "timing", "diag_buffer", "diag_stride")
 TUNING_NAMES = ("workgroups_per_cu", "run_max", "run_min", "shift_bias", "stage_first", "pool_refill_at", "stream_run_max",
                 "stream_run_min", "stream_workgroups_per_cu", "probes", "stream_probes", "regions", "stream_rotate",
                 "tile_pixels", "tile_exit", "tile_exit_from", "prepare", "pool_items_per_wg", "subtile_shape", "debug_region_blocks", "debug_prologue_epoch", "ssaa", "ssaa_band_samples", "stripes",
@@ -424,3 +428,22 @@ def plan_whole_blocks(params: fr_params, width: int, height: int, shard: "fr_sha
     values = (C.c_int64 * max(len(tunings), 1))(*[int(v) for _, v in tunings])
     return bool(check(lib().fr_plan_whole_blocks(C.byref(params), width, height, C.byref(shard) if shard is not None else None,
                                                  compute_units, names, values, len(tunings), int(pool_looks))))
+
+
+def fold_describe(params: fr_params, width: int, height: int, shard: "fr_shard | None" = None, tunings=()) -> dict:
+    """Whether fr_render_shard would render this request folded about the real axis, and the rows it would render
+    (fr_tuning.h: fr_fold_describe), as {"fold": bool, "rows_rendered": int}.  Needs no GPU.  tunings: as plan_describe's."""
+    names = (C.c_char_p * max(len(tunings), 1))(*[n.encode() for n, _ in tunings])
+    values = (C.c_int64 * max(len(tunings), 1))(*[int(v) for _, v in tunings])
+    out = (C.c_int64 * 2)()
+    check(lib().fr_fold_describe(C.byref(params), width, height, C.byref(shard) if shard is not None else None, names, values,
+                                 len(tunings), out))
+    return {"fold": bool(out[0]), "rows_rendered": int(out[1])}
+
+
+def fold_division(width: int, n_indices: int = 0) -> tuple[int, int, bool]:
+    """(magic, shift, exact): index // width == (index * magic) >> shift, as the folded render's lane pool finds the row of a
+    plane index; exact: the host's check of it over every index below n_indices (fr_tuning.h: fr_fold_division)."""
+    magic, shift = C.c_uint32(), C.c_uint32()
+    ok = check(lib().fr_fold_division(width, n_indices, C.byref(magic), C.byref(shift)))
+    return int(magic.value), int(shift.value), bool(ok)

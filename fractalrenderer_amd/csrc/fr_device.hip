@@ -142,6 +142,8 @@ struct fr_ctx {
     struct DivCheck { bool valid, julia, f64, ok; uint32_t W, H; };
     DivCheck div_cache[8];      /* exact_division_ok() results */
     uint32_t div_next;
+    uint32_t fold_div_w, fold_div_rows;   /* fold_div_ok() held for frames this wide of up to this many rendered rows */
+    uint32_t last_fold;         /* rows the most recent render rendered as a folded render (fr_plan.h: plan_fold); 0: it was not one */
     int phoenix_wg_per_cu[2];   /* resident workgroups per CU of phoenix_kernel<float> / <double> (0 = not asked yet) */
     int mandelbulb_wg_per_cu[2];  /* ... of mandelbulb_kernel<false> / <true> (0 = not asked yet) */
     /* deep views: one slot per path, deep[storage][formula] (deep_slot()).  Storage 0, plain doubles Z_0 .. Z_N in one pinned and
@@ -395,7 +397,19 @@ static hipError_t launch_tile(int shape, dim3 grid, hipStream_t s, const LaunchA
 template <typename T, int FRACTAL>
 static hipError_t launch_tile_lean(int np, dim3 grid, hipStream_t s, const LaunchArgs& a)
 {
-    if (a.whole.base) {                          /* (staged, no cycle closing in the tile pass: plan_render) */
+    if constexpr (FRACTAL == 0) {
+        if (a.fold_rows) {                       /* a folded render (plan_fold): the same kernels with the mirrored stores */
+            const bool w = a.whole.base != nullptr, pw = a.period_window != 0u;
+            if (w && np == 2) hipLaunchKernelGGL((tile_lean_kernel<T, 0, false, 2 + kWholeTrips + kFoldTrips>), grid, dim3(kBlockThreads), 0, s, a);
+            else if (w) hipLaunchKernelGGL((tile_lean_kernel<T, 0, false, 1 + kWholeTrips + kFoldTrips>), grid, dim3(kBlockThreads), 0, s, a);
+            else if (np == 2 && pw) hipLaunchKernelGGL((tile_lean_kernel<T, 0, true, 2 + kFoldTrips>), grid, dim3(kBlockThreads), 0, s, a);
+            else if (np == 2) hipLaunchKernelGGL((tile_lean_kernel<T, 0, false, 2 + kFoldTrips>), grid, dim3(kBlockThreads), 0, s, a);
+            else if (pw) hipLaunchKernelGGL((tile_lean_kernel<T, 0, true, 1 + kFoldTrips>), grid, dim3(kBlockThreads), 0, s, a);
+            else hipLaunchKernelGGL((tile_lean_kernel<T, 0, false, 1 + kFoldTrips>), grid, dim3(kBlockThreads), 0, s, a);
+            return hipGetLastError();
+        }
+    }
+    if (a.whole.base) {                         /* (staged, no cycle closing in the tile pass: plan_render) */
         if (np == 2) hipLaunchKernelGGL((tile_lean_kernel<T, FRACTAL, false, 2 + kWholeTrips>), grid, dim3(kBlockThreads), 0, s, a);
         else hipLaunchKernelGGL((tile_lean_kernel<T, FRACTAL, false, 1 + kWholeTrips>), grid, dim3(kBlockThreads), 0, s, a);
     } else if (np == 2) {
@@ -439,6 +453,14 @@ static hipError_t launch_prepare(hipStream_t s, const LaunchArgs& a, uint32_t* c
 template <typename T, int FRACTAL>
 static hipError_t launch_stream_pool(dim3 grid, hipStream_t s, const LaunchArgs& a)
 {
+    if constexpr (FRACTAL == 0) {
+        if (a.fold_rows) {                       /* a folded render (plan_fold): the same kernels with the mirrored stores */
+            if (a.period_window) hipLaunchKernelGGL((pool_kernel<T, kFoldPool, true>), grid, dim3(kBlockThreads), 0, s, a);
+            else if (a.whole.base) hipLaunchKernelGGL((pool_kernel<T, kWholePool + kFoldPool, false>), grid, dim3(kBlockThreads), 0, s, a);
+            else hipLaunchKernelGGL((pool_kernel<T, kFoldPool, false>), grid, dim3(kBlockThreads), 0, s, a);
+            return hipGetLastError();
+        }
+    }
     if (a.period_window)
         hipLaunchKernelGGL((pool_kernel<T, FRACTAL, true>), grid, dim3(kBlockThreads), 0, s, a);
     else if (a.whole.base)                       /* the stream has two classes (plan_render: never with cycle closing) */
@@ -572,8 +594,9 @@ static int normalise_shard(const fr_shard* shard, uint32_t H, fr_shard* norm, ui
 }
 
 /* behind the last launch of a render: its end event, and where and in how many stages it went */
-static int finish_render(fr_ctx* c, hipStream_t stream, int nstages)
+static int finish_render(fr_ctx* c, hipStream_t stream, int nstages, uint32_t fold = 0u)
 {
+    c->last_fold = fold;                         /* rows a folded render rendered (fr_ctx_last_fold); 0: every row of its own */
     if (c->timing) FR_HIP_TRY(hipEventRecord(c->ev_end, stream));
     c->have_timing = c->timing;
     c->have_render = true;
@@ -1526,7 +1549,21 @@ static int enqueue_render(fr_ctx* c, const fr_params* p, uint32_t W, uint32_t H,
     uint32_t rows_local = 0;
     const int sh = normalise_shard(shard, H, &norm, &rows_local);
     if (sh != FR_OK || rows_local == 0) return sh;           /* (rows_local 0: this part owns no rows) */
+    /* FOLDED RENDER (fr_plan.h: plan_fold): decided before the plan, which is then the plan of the rows that are rendered --
+     * staging, b0, shards, the whole-block rule, grids and scratch sizes all follow them.  (fr_ctx_reserve sizes for the unfolded
+     * render, the larger of the two: "fold" may change between the reserve and the render.) */
+    uint32_t fold = reserve_only ? 0u : plan_fold(c->tune, p, W, H, norm, ssaa_of);
+    FoldDiv fdiv = {0u, 0u};
+    if (fold) {
+        fdiv = fold_div(W);
+        if (c->fold_div_w != W || c->fold_div_rows < fold) {                /* (checked once per geometry) */
+            if (fold_div_ok(W, fdiv, (uint64_t)W * fold)) { c->fold_div_w = W; c->fold_div_rows = fold; }
+            else fold = 0u;                                                  /* (never seen: fold_div's bound covers every legal frame) */
+        }
+    }
+    if (fold) rows_local = fold;
     const RenderPlan plan = plan_render(c->tune, c->compute_units, p, W, H, norm, rows_local, ssaa_of, out_frame);
+    if (fold && plan.family != kLean) return fr_set_error(FR_ERR_INTERNAL, "a folded render reached a kernel family that does not mirror its stores");
     if (plan.route == kRouteDeepZoom)
         return enqueue_deep_zoom(c, p, W, H, &norm, rows_local, rgba, nu, iter, stream, reserve_only, out_frame);
     if (plan.route == kRouteSsaaStaged)
@@ -1538,6 +1575,7 @@ static int enqueue_render(fr_ctx* c, const fr_params* p, uint32_t W, uint32_t H,
     fill_params(a, p);
     fill_geometry(a, c, p, W, H, norm, rows_local, out_frame, ssaa_of, res_w, res_h);
     a.rgba = reinterpret_cast<float4*>(rgba); a.nu = nu; a.iter = iter;
+    a.fold_rows = fold; a.fold_magic = fdiv.magic; a.fold_shift = fdiv.shift;
     c->last_grid = plan.grid; c->last_pool_closing = -1;
     int st = grow_device(&c->stream_buf, &c->stream_bytes, plan.stream_bytes);      /* the context scratch the plan needs */
     if (st == FR_OK) st = grow_device(&c->whole_buf, &c->whole_bytes, plan.whole_bytes);
@@ -1552,7 +1590,7 @@ static int enqueue_render(fr_ctx* c, const fr_params* p, uint32_t W, uint32_t H,
     if ((st = begin_frame(c, plan, nstages, plan.whole_blocks_apply(pool_looks), p, a, stream)) != FR_OK) return st;
     if ((st = launch_tile_pass(c, plan, p, a, pool_looks, stream)) != FR_OK) return st;
     if (plan.staged() && (st = launch_pool_pass(c, plan, p, a, pool_looks, stream)) != FR_OK) return st;
-    return finish_render(c, stream, nstages);
+    return finish_render(c, stream, nstages, fold);
 }
 
 /* staged SSAA: the sample grid as a render of its own into context scratch, then the average */
@@ -1816,6 +1854,37 @@ extern "C" int fr_plan_whole_blocks(const fr_params* p, uint32_t W, uint32_t H, 
     if (outer.route == kRouteDeepZoom) return 0;
     return r.whole_blocks_apply(r.pool_may_look && pool_looks != 0) ? 1 : 0;
 }
+
+/* fr_tuning.h: the fold decision of a request (plan_fold), with no context and no device */
+extern "C" int fr_fold_describe(const fr_params* p, uint32_t W, uint32_t H, const fr_shard* shard, const char* const* names,
+                                const int64_t* values, int n_tunings, int64_t out[2])
+{
+    if (!p || !out || (n_tunings > 0 && (!names || !values))) return fr_set_error(FR_ERR_INVALID_ARG, "fr_fold_describe: NULL argument");
+    Tuning tune;
+    const int ts = tunings_from(tune, names, values, n_tunings);
+    if (ts != FR_OK) return ts;
+    out[0] = out[1] = 0;
+    fr_shard norm;
+    uint32_t rows_local = 0;
+    const int sh = normalise_shard(shard, H, &norm, &rows_local);
+    if (sh != FR_OK || rows_local == 0) return sh;
+    const uint32_t fold = p->fractal_type == FR_FRACTAL_DEEP_ZOOM ? 0u : plan_fold(tune, p, W, H, norm, 0);
+    out[0] = fold != 0u;
+    out[1] = fold ? fold : rows_local;
+    return FR_OK;
+}
+
+/* fr_tuning.h: the folded render's division of a plane index by W; returns whether it is exact for every index below n_indices */
+extern "C" int fr_fold_division(uint32_t W, uint64_t n_indices, uint32_t* magic, uint32_t* shift)
+{
+    if (W == 0u || W > (1u << 31) || !magic || !shift) return fr_set_error(FR_ERR_INVALID_ARG, "fr_fold_division: W in [1, 2^31], magic and shift not NULL");
+    const FoldDiv d = fold_div(W);
+    *magic = d.magic; *shift = d.shift;
+    return fold_div_ok(W, d, n_indices) ? 1 : 0;
+}
+
+/* fr_tuning.h: rows the most recent render rendered as a folded render, 0: it was not one */
+extern "C" int fr_ctx_last_fold(const fr_ctx* c) { return c ? (int)c->last_fold : 0; }
 
 extern "C" int fr_plan_describe(const fr_params* p, uint32_t W, uint32_t H, const fr_shard* shard, int compute_units,
                                 const char* const* names, const int64_t* values, int n_tunings, int64_t* out, int n_out)

@@ -186,6 +186,10 @@ struct LaunchArgs {
     uint32_t* pro_fb_host;
     fr_palette_table pal;
     WholeRef whole;              /* (behind everything else: the offsets of the fields above are those of a build without it) */
+    /* FOLDED RENDER (fr_plan.h: plan_fold).  fold_rows != 0: this render's rows_local are the first fold_rows rows of a frame that
+     * is symmetric about the real axis, and every store of a finished pixel of row r is repeated at row H - r (fold_partner).
+     * fold_magic, fold_shift: row of a plane index, index / W == (index * fold_magic) >> fold_shift (fold_div, verified on the host) */
+    uint32_t fold_rows, fold_magic, fold_shift;
 };
 
 /* The kernel arguments, re-read where they are used.  Everything a persistent kernel reads from its argument block is
@@ -1972,6 +1976,31 @@ struct LeanWriter {
     }
 };
 
+/* FOLDED RENDER (fr_plan.h: plan_fold; the FOLD instantiations of the lean tile kernel and the lane pool).  Where the finished
+ * pixel at plane index `pix` of row `row` is stored a second time: row H - row, same column -- or kInvalidPixel: row 0 has no
+ * partner, and a partner in front of row fold_rows is rendered itself.  (Whole frames only: a plane index is row * W + column in either plane layout; row <
+ * fold_rows <= H - 1, so the partner's index lies inside the planes.) */
+__device__ __forceinline__ uint32_t fold_partner(KArgs K, const uint32_t pix, const uint32_t row)
+{
+    const uint32_t mrow = (uint32_t)K->H - row;
+    return (row != 0u && mrow >= K->fold_rows) ? pix + (mrow - row) * (uint32_t)K->W : kInvalidPixel;
+}
+/* the row of a plane index, for the passes whose records carry nothing else (fold_div: exact below 2^31, verified on the host) */
+__device__ __forceinline__ uint32_t fold_row_of(KArgs K, const uint32_t pix)
+{
+    return (uint32_t)(((uint64_t)pix * K->fold_magic) >> K->fold_shift);
+}
+/* the second store of a finished pixel, all three planes */
+template <typename T>
+__device__ __forceinline__ void fold_store(KArgs K, const uint32_t partner, const float r, const float g, const float b, const T nu, const int it)
+{
+    if (partner != kInvalidPixel) {
+        if (K->rgba) K->rgba[partner] = make_float4(r, g, b, 1.0f);
+        if (K->nu) reinterpret_cast<T*>(K->nu)[partner] = nu;
+        if (K->iter) K->iter[partner] = it;
+    }
+}
+
 /* NP = 1: one 8x8 sub-tile per trip.  NP = 2: two horizontally adjacent ones (a 16x8 patch, lane (lx, ly) holds the
  * pixels (lx, ly) and (lx + 8, ly)); a trip whose second sub-tile does not exist (odd run, end of a row) runs with those
  * samples switched off like lanes outside the frame. */
@@ -1979,11 +2008,19 @@ struct LeanWriter {
  * stream's second class (WholeRef).  (One parameter for both, so that the instantiations without the class keep the names
  * and the code they had before there was one.) */
 constexpr int kWholeTrips = 2;
+/* ... and kFoldTrips more on top of either: the same kernel for a folded render (fr_plan.h: plan_fold), whose stores of finished
+ * pixels are followed by the mirrored ones.  Instantiations of their own, so that no unfolded frame pays for the second store:
+ * as a wave-uniform branch it took tile_lean_kernel<double, 0, false, 2> from 80 to 82 VGPRs and from 6 waves per SIMD to 5
+ * (profiles/fold_mirror.txt). */
+constexpr int kFoldTrips = 4;
 template <typename T, int FRACTAL, bool PERIOD, int TRIP>
 __global__ void __launch_bounds__(kBlockThreads)
 tile_lean_kernel(const LaunchArgs A)
 {
-    constexpr int NP = TRIP > kWholeTrips ? TRIP - kWholeTrips : TRIP;
+    constexpr bool FOLD = TRIP > kFoldTrips;                  /* folded render: a second store per finished pixel (fold_store) */
+    constexpr int TRIP_PLAIN = FOLD ? TRIP - kFoldTrips : TRIP;
+    constexpr int NP = TRIP_PLAIN > kWholeTrips ? TRIP_PLAIN - kWholeTrips : TRIP_PLAIN;
+    static_assert(!FOLD || FRACTAL == 0, "the folded render: the plain Mandelbrot kernels alone");
     constexpr int NF = RecFields<FRACTAL>::n;
     constexpr bool ABS = Form<FRACTAL>::abs_step;
     constexpr bool STRIPES = FRACTAL == 3;                    /* Mandelbrot + stripe shading: see shade_stripes */
@@ -2021,7 +2058,7 @@ tile_lean_kernel(const LaunchArgs A)
     writer.init();
     LeanQueue q;
     q.init();
-    constexpr bool WHOLE = TRIP > kWholeTrips;
+    constexpr bool WHOLE = TRIP_PLAIN > kWholeTrips;
     static_assert(!WHOLE || (!PERIOD && !STRIPES), "whole blocks are read by the plain lane pool alone");
     uint32_t whole_home = writer.home;                       /* region the next whole trip writes to */
     (void)whole_home;
@@ -2188,6 +2225,14 @@ tile_lean_kernel(const LaunchArgs A)
                             if (K->iter) K->iter[pixel[p]] = it[p];
                         }
                     }
+                    if constexpr (FOLD) {                        /* folded render: the same values at row H - row (a whole frame:
+                                                                  * its local rows are the frame's) */
+                        const uint32_t row = sty * 8u + (lane >> 3);
+#pragma unroll
+                        for (int p = 0; p < NP; ++p) {
+                            if (need[p]) fold_store<T>(K, fold_partner(K, pixel[p], row), rgb[p][0], rgb[p][1], rgb[p][2], nu[p], it[p]);
+                        }
+                    }
                 }
                 stx += np;
                 n -= np;
@@ -2273,7 +2318,7 @@ __device__ __forceinline__ uint32_t wave_min_u32(uint32_t v)
 }
 
 /* colour stage of one finished sample and its stores.  eX, eYd: the sample's z after its last update (STRIPES) */
-template <typename T, int FRACTAL>
+template <typename T, int FRACTAL, bool FOLD = false>
 __device__ __forceinline__ void shade_and_store(const LdsBlock& S, const LogTab<T>& lg, const uint32_t pix, const int it, const T r2,
                                                 const T eX, const T eYd, const bool want_nu, const bool want_rgb)
 {
@@ -2288,17 +2333,21 @@ __device__ __forceinline__ void shade_and_store(const LdsBlock& S, const LogTab<
     if (K->rgba) K->rgba[pix] = make_float4(rgb[0], rgb[1], rgb[2], 1.0f);
     if (K->nu) reinterpret_cast<T*>(K->nu)[pix] = nu;
     if (K->iter) K->iter[pix] = it;
+    /* folded render: a record carries its pixel's plane index alone, the row comes from the host-prepared division */
+    if constexpr (FOLD) fold_store<T>(K, fold_partner(K, pix, fold_row_of(K, pix)), rgb[0], rgb[1], rgb[2], nu, it);
 }
 
 /* ... of a sample that never escaped, where that is known for the whole wave (no stripes): what shade_and_store makes of
  * it = max_iter -- nu = max_iter and the colour `final_rgb` (stage_interior_final) -- without the colour stage around it */
-template <typename T>
+template <typename T, bool FOLD = false>
 __device__ __forceinline__ void store_interior(const float (&final_rgb)[3], const uint32_t pix, const int max_iter)
 {
     KArgs K = kargs();
     if (K->rgba) K->rgba[pix] = make_float4(final_rgb[0], final_rgb[1], final_rgb[2], 1.0f);
     if (K->nu) reinterpret_cast<T*>(K->nu)[pix] = (T)max_iter;
     if (K->iter) K->iter[pix] = max_iter;
+    if constexpr (FOLD)
+        fold_store<T>(K, fold_partner(K, pix, fold_row_of(K, pix)), final_rgb[0], final_rgb[1], final_rgb[2], (T)max_iter, max_iter);
 }
 /* the colour shade_and_store writes for such a sample: the interior colour (stage_interior), through the post chain if the render
  * asks for it.  The same for every such sample: thread 0, once per workgroup */
@@ -2445,6 +2494,8 @@ struct PoolLane {
  * class.  (One parameter for both, as the tile kernel's TRIP: the instantiations for one class keep the names and the code they
  * had before there was a second.) */
 constexpr int kWholePool = 8;
+/* ... and kFoldPool more on top of either: the same kernel for a folded render, as the tile kernel's kFoldTrips */
+constexpr int kFoldPool = 16;
 template <typename T, int KIND, bool PERIOD = false>
 __global__ void __launch_bounds__(kBlockThreads)
 /* VGPRs are handed out in granules of 16 on gfx950 (measured in round 3: a 68-VGPR fp64 instantiation ran 6 workgroups per
@@ -2453,7 +2504,10 @@ __global__ void __launch_bounds__(kBlockThreads)
  * the same (profiles/r04_pool_deferred_escapes.txt). */
 pool_kernel(const LaunchArgs A)
 {
-    constexpr int FRACTAL = KIND >= kWholePool ? KIND - kWholePool : KIND;
+    constexpr bool FOLD = KIND >= kFoldPool;              /* folded render: a second store per finished pixel (fold_store) */
+    constexpr int KIND_PLAIN = FOLD ? KIND - kFoldPool : KIND;
+    constexpr int FRACTAL = KIND_PLAIN >= kWholePool ? KIND_PLAIN - kWholePool : KIND_PLAIN;
+    static_assert(!FOLD || FRACTAL == 0, "the folded render: the plain Mandelbrot kernels alone");
     constexpr int NF = RecFields<FRACTAL>::n;
     constexpr bool STRIPES = FRACTAL == 3;                /* Mandelbrot + stripe shading (shade_stripes): a finished lane keeps the
                                                            * z of its last update, and no lane runs past its deadline */
@@ -2493,7 +2547,7 @@ pool_kernel(const LaunchArgs A)
      * one word (a VGPR: the lane pool's scalars fill the scalar file) -- bits 0-7 the shard of the class's queue the wave is
      * at, bits 8-15 the shards it has found dry, bit 31 "the class is dry", bit 30 "the lane pool's reserve comes from it" (q is the
      * ring class's queue) */
-    constexpr bool WHOLE = KIND >= kWholePool;
+    constexpr bool WHOLE = KIND_PLAIN >= kWholePool;
     static_assert(!WHOLE || (!PERIOD && !STRIPES), "whole blocks: the plain lane pool alone");
     __shared__ float interior_final[3];  /* what a whole block that stays clean stores for its pixels */
     if constexpr (WHOLE) stage_interior_final<FR>(S, A, interior_final);
@@ -2599,7 +2653,7 @@ pool_kernel(const LaunchArgs A)
             }
             if (left == 0u) {
                 /* not escaped after exactly max_iter updates: interior, all 64 */
-                store_interior<T>(interior_final, L.pixel, kargs()->max_iter);
+                store_interior<T, FOLD>(interior_final, L.pixel, kargs()->max_iter);
                 L.pixel = kInvalidPixel;                             /* the lane is free */
                 o.park();
                 continue;
@@ -2653,7 +2707,7 @@ pool_kernel(const LaunchArgs A)
                 const int idx = ri0 + (int)ek;
                 const bool esc = !open && idx < max_iter;
                 /* (STRIPES: a stretch never crosses a deadline, so a deferred lane did escape before its max_iter-th update) */
-                shade_and_store<T, FRACTAL>(S, lg, rpix, esc ? idx : max_iter, esc ? T(0.25) * er : T(0), eX, eYd, want_nu, want_rgb);
+                shade_and_store<T, FRACTAL, FOLD>(S, lg, rpix, esc ? idx : max_iter, esc ? T(0.25) * er : T(0), eX, eYd, want_nu, want_rgb);
             }
             dhead += count;
             __builtin_amdgcn_wave_barrier();
@@ -2672,7 +2726,7 @@ pool_kernel(const LaunchArgs A)
                 life_avg = life_avg == 0u ? life : (3u * life_avg + life) >> 2;
             }
             if (L.fin != 0u) {
-                shade_and_store<T, FRACTAL>(S, lg, L.pixel, L.esc_i, L.esc_r2, L.esc_X, L.esc_Yd, want_nu, want_rgb);
+                shade_and_store<T, FRACTAL, FOLD>(S, lg, L.pixel, L.esc_i, L.esc_r2, L.esc_X, L.esc_Yd, want_nu, want_rgb);
                 L.pixel = kInvalidPixel;
                 L.fin = 0u;
             }

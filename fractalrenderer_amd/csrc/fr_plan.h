@@ -49,6 +49,8 @@ struct Tuning {
     uint32_t whole_blocks;      /* survivor stream in two classes (whole blocks beside the ring's records): 0 = automatic (plan_render: large
                                    fp64 frames), 1 = off, 2 = on wherever whole_blocks_apply */
     uint32_t mandelbulb_split;  /* 0 = automatic (march / shade split), 1 = shade at the hit, inside the march loop */
+    uint32_t fold;              /* folded render of a real-axis-symmetric Mandelbrot frame (plan_fold): 0 = automatic (frames of at least
+                                   kFoldAutoPixels pixels), 1 = off, 2 = on wherever the frame qualifies */
     uint32_t debug_region_blocks; /* tests only: cap the capacity of a survivor-stream region, to provoke an overflow */
 };
 
@@ -120,6 +122,9 @@ inline int option_set(Tuning& t, const char* name, int64_t value)
     } else if (!strcmp(name, "tile_kernel")) {
         if (value < 0 || value > 1) return fr_set_error(FR_ERR_INVALID_ARG, "tile_kernel must be 0 (automatic: lean where it applies) or 1 (general)");
         t.tile_kernel = (uint32_t)value;
+    } else if (!strcmp(name, "fold")) {
+        if (value < 0 || value > 2) return fr_set_error(FR_ERR_INVALID_ARG, "fold must be 0 (automatic), 1 (off) or 2 (on wherever the frame qualifies)");
+        t.fold = (uint32_t)value;
     } else {
         return kNotMine;
     }
@@ -156,6 +161,62 @@ inline bool needs_effects(const fr_params* p)
 inline bool lean_applies(const Tuning& t, const fr_shard& shard, uint32_t row_multiple)
 {
     return t.tile_kernel != 1u && (t.shape == 0u || t.shape == 3u) && (shard.nparts == 1 || (shard.rows_per_strip * row_multiple) % 8u == 0u);
+}
+
+/* ---- folded render ------------------------------------------------------------------------------------
+ * The Mandelbrot viewport map is cy(py) = center_y + ((py - 0.5 H) / H) zoom (write_coordinate_tables, MAP == 0): with
+ * center_y == 0 rows r and H - r get exactly negated cy, for even and odd H, in either precision.  The update negates Yd and
+ * changes nothing else -- products and round-to-nearest are sign-symmetric; x2, y2d and 4|z|^2 are even in Yd -- so the two
+ * orbits are conjugates bit for bit: same escape index, same |z|^2, and the plain colour stage is a function of those two
+ * alone.  Such a frame renders rows [0, R) and every store of a pixel in row r also stores the same values at row H - r.
+ * R = floor(H / 2) + 1 rounded up to whole sub-tile rows; the mirrored store happens iff r >= 1 and H - r >= R, so a mirror
+ * never lands on a row that is rendered itself (row 0 has no partner, row H / 2 is its own).
+ * Qualifies: Mandelbrot by the lean family without effects (stripes read the sign of z), one sample per pixel (the SSAA
+ * sample offsets are anchored top-left and do not mirror), a whole frame (no shard, not a sample grid), (T)center_y == 0 in
+ * the kernels' precision, R < H.  "fold" = 2 never overrides any of these; automatic folds frames of at least
+ * kFoldAutoPixels pixels (below that the frame is one pass and ramp-bound: halving its rows buys little). */
+constexpr size_t kFoldAutoPixels = (size_t)1 << 20;
+
+inline uint32_t fold_rows(uint32_t H) { return (uint32_t)(((uint64_t)H / 2u + 1u + 7u) & ~(uint64_t)7u); }
+
+/* rows the folded render of this request renders, or 0: not folded */
+inline uint32_t plan_fold(const Tuning& t, const fr_params* p, uint32_t W, uint32_t H, const fr_shard& norm, int ssaa_of)
+{
+    if (t.fold == 1u || p->fractal_type != FR_FRACTAL_MANDELBROT) return 0u;
+    if (needs_effects(p) || p->antialiasing_samples > 1 || ssaa_of > 1) return 0u;
+    if (norm.nparts != 1u || !lean_applies(t, norm, 1)) return 0u;
+    const bool zero = p->precision == FR_PRECISION_F64 ? (double)p->center_y == 0.0 : (float)p->center_y == 0.0f;
+    if (!zero) return 0u;
+    const uint32_t R = fold_rows(H);
+    if (R >= H) return 0u;
+    if (t.fold == 0u && (size_t)W * H < kFoldAutoPixels) return 0u;
+    return R;
+}
+
+/* The lane pool's records carry a pixel's index in the planes and nothing else: its row is index / W, as one multiplication
+ * and one shift.  With l = ceil(log2 W), s = 31 + l and m = floor(2^s / W) + 1 (< 2^32):  index m / 2^s = index / W + index e / 2^s
+ * with 0 < e <= 1, and index e / 2^s < 2^31 / 2^s = 2^-l <= 1 / W for every index < 2^31 -- less than what the fraction of
+ * index / W lacks to the next integer -- so floor(index m / 2^s) == floor(index / W) for every index a legal frame has.
+ * fold_div_ok evaluates the kernel's expression at both ends of every row of the frame (the expression is monotonic in the
+ * index): the same kind of check exact_division_ok makes for the viewport map. */
+struct FoldDiv { uint32_t magic, shift; };
+inline FoldDiv fold_div(uint32_t W)
+{
+    FoldDiv d;
+    d.shift = 31u + ceil_log2(W);
+    d.magic = (uint32_t)((((uint64_t)1 << d.shift) / W) + 1u);
+    return d;
+}
+inline uint32_t fold_div_apply(const FoldDiv& d, uint32_t index) { return (uint32_t)(((uint64_t)index * d.magic) >> d.shift); }
+/* exact for every index in [0, n)?  (n <= 2^31) */
+inline bool fold_div_ok(uint32_t W, const FoldDiv& d, uint64_t n)
+{
+    if (W == 0u || n > ((uint64_t)1 << 31)) return false;
+    for (uint64_t first = 0, row = 0; first < n; first += W, ++row) {
+        const uint64_t last = first + W - 1u < n - 1u ? first + W - 1u : n - 1u;
+        if (fold_div_apply(d, (uint32_t)first) != row || fold_div_apply(d, (uint32_t)last) != row) return false;
+    }
+    return true;
 }
 
 /* ---- geometry of the tile pass ----------------------------------------------------------------------

@@ -76,6 +76,23 @@ int fr_ctx_last_whole_blocks(fr_ctx* ctx, uint64_t out[3]);
 int fr_plan_whole_blocks(const fr_params* params, uint32_t width, uint32_t height, const fr_shard* shard, int compute_units,
                          const char* const* names, const int64_t* values, int n_tunings, int pool_looks);
 
+/* FOLDED RENDER (fr_plan.h: plan_fold).  A Mandelbrot frame with center_y == 0 is symmetric about the real axis bit for bit:
+ * it renders its first R = floor(H / 2) + 1 rows (rounded up to whole sub-tile rows) and stores every finished pixel of row r at
+ * row H - r as well.  fr_ctx_set_option "fold": 0 = automatic (frames of at least 2^20 pixels), 1 = off, 2 = on wherever the
+ * frame qualifies -- Mandelbrot by the lean kernels without effects, one sample per pixel, a whole frame (no shard),
+ * center_y == 0 in the render's precision, R < H; no value overrides these.  Like every option it cannot change a pixel
+ * (tests compare on and off bitwise).
+ * fr_fold_describe: the decision for a request, no context, no device -- out[0] = 1 / 0 folded or not, out[1] = the rows the
+ * render renders (R, or the rows the part owns).  names / values: as fr_plan_describe's.
+ * fr_ctx_last_fold: R of the context's most recent render if it was folded, else 0.
+ * fr_fold_division: the multiplier and shift with which the lane pool finds the row of a plane index,
+ * index / W == (index * magic) >> shift in 64 bits; returns 1 / 0: the host's check (both ends of every row) finds it exact
+ * for every index below n_indices (<= 2^31) / it does not. */
+int fr_fold_describe(const fr_params* params, uint32_t width, uint32_t height, const fr_shard* shard, const char* const* names,
+                     const int64_t* values, int n_tunings, int64_t out[2]);
+int fr_ctx_last_fold(const fr_ctx* ctx);
+int fr_fold_division(uint32_t width, uint64_t n_indices, uint32_t* magic, uint32_t* shift);
+
 /* The schedule of a render as a flat record of integers (fr_plan.h: plan_render), decided from the request, a compute-unit
  * count and tunings alone: no context, no device.  names / values: n_tunings fr_ctx_set_tuning names (and the scheduling
  * names of fr_ctx_set_option: "periodicity", "staging", "shards", "tile_kernel") applied in order to the automatic

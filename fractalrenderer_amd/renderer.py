@@ -177,6 +177,11 @@ class Renderer:
         _capi.check(self._lib.fr_ctx_last_whole_blocks(self._ctx, out))
         return int(out[0]), int(out[1]), int(out[2])
 
+    def last_fold(self) -> int:
+        """internal (fr_tuning.h): rows the most recent render rendered as a folded render (a Mandelbrot frame with
+        center_y == 0: the rows below the real axis are mirrored stores), 0 where it rendered every row itself"""
+        return int(self._lib.fr_ctx_last_fold(self._ctx))
+
     # -- plane plumbing ------------------------------------------------------------------
     @staticmethod
     def _ptr(x, want_dtype: str, nelem: int, what: str):

@@ -278,6 +278,10 @@ float fr_ctx_last_kernel_ms(fr_ctx* ctx);
  *                   first workgroups -- by a small launch in front of it on capturing streams --, two 8x8 sub-tiles per wave
  *                   and trip) for every one-sample render (the Burning Ship's trap / stripe effects excepted) whose row
  *                   strips, if sharded, are whole sub-tile rows.
+ *   "fold"          a Mandelbrot frame with center_y == 0 is symmetric about the real axis bit for bit: 0 = automatic (such a
+ *                   frame of at least 2^20 pixels renders its upper floor(H / 2) + 1 rows, rounded up to 8, and stores every
+ *                   finished pixel of row r at row H - r as well), 1 = off, 2 = on wherever the frame qualifies (one sample per
+ *                   pixel, no stripes / orbit trap / interior style 2, a whole frame by the lean tile kernel).
  *   "timing"        1 = record a HIP event pair around every render (fr_ctx_last_kernel_ms, fr_node_last_kernel_ms); 0 = off, the
  *                   default since 1.1.
  *   "diag_buffer"   device pointer to 4 x uint64 per wave (t_start, t_end in 100 MHz ticks, items processed, dequeues);

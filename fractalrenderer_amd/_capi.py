@@ -172,6 +172,13 @@ SIGNATURES = {
                                          C.c_uint32, _P(fr_shard), _P(fr_output)]),
     "fr_render_deep_phoenix_async": (C.c_int, [C.c_void_p, _P(fr_params), _P(fr_phoenix_params), _P(fr_deep_view), C.c_uint32,
                                                C.c_uint32, _P(fr_shard), _P(fr_output), C.c_void_p]),
+    "fr_deepx_phoenix_validate": (C.c_int, [_P(fr_params), _P(fr_phoenix_params), _P(fr_deepx_view), C.c_uint32, C.c_uint32]),
+    "fr_deepx_phoenix_reference_orbit": (C.c_int, [_P(fr_deepx_view), _P(fr_phoenix_params), C.c_int32, C.c_void_p, C.c_void_p,
+                                                   _P(C.c_int32)]),
+    "fr_render_deepx_phoenix": (C.c_int, [C.c_void_p, _P(fr_params), _P(fr_phoenix_params), _P(fr_deepx_view), C.c_uint32,
+                                          C.c_uint32, _P(fr_shard), _P(fr_output)]),
+    "fr_render_deepx_phoenix_async": (C.c_int, [C.c_void_p, _P(fr_params), _P(fr_phoenix_params), _P(fr_deepx_view), C.c_uint32,
+                                                C.c_uint32, _P(fr_shard), _P(fr_output), C.c_void_p]),
     "fr_ctx_last_deep_steps": (C.c_int, [C.c_void_p, _P(C.c_uint64)]),
     "fr_ctx_last_deepx_steps": (C.c_int, [C.c_void_p, _P(C.c_uint64)]),
     "fr_ctx_last_deep_ship_steps": (C.c_int, [C.c_void_p, _P(C.c_uint64)]),

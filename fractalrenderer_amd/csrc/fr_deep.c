@@ -1056,3 +1056,46 @@ int fr_deep_phoenix_reference_orbit(const fr_deep_view* v, const fr_phoenix_para
     float_to_fixed_floor(ph->phoenix_r, r.fmt, t.r);
     return orbit_loop(r.cr, r.ci, NULL, NULL, r.fmt, kOrbitPhoenix, &t, max_iter, 2.0f, out_xy, NULL, out_len);
 }
+
+/* ---- deep Phoenix views below 1e-290 (fr_render_deepx_phoenix) ------------------------------------------------------------------
+ * fr_deep_phoenix_validate's rules in its order with the zoom in the view's string: p->zoom is not read, and the view is checked
+ * as fr_deepx_validate checks its own (resolve_view: reserved, frac_bits, the centre strings, the zoom string and its range). */
+int fr_deepx_phoenix_validate(const fr_params* p, const fr_phoenix_params* ph, const fr_deepx_view* v, uint32_t width, uint32_t height)
+{
+    if (!p || !ph || !v) return fr_set_error(FR_ERR_INVALID_ARG, "params/phoenix params/deep view is NULL");
+    if (p->fractal_type != FR_FRACTAL_PHOENIX)
+        return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deepx_phoenix renders FR_FRACTAL_PHOENIX only (got %d)", p->fractal_type);
+    if (p->precision != FR_PRECISION_F64)
+        return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deepx_phoenix needs FR_PRECISION_F64 (got %d)", p->precision);
+    if (width == 0 || height == 0)
+        return fr_set_error(FR_ERR_INVALID_ARG, "width and height must be > 0 (got %ux%u)", width, height);
+    fr_params q = *p;                                            /* the double centre and the double zoom are not read */
+    q.center_x = 0.0; q.center_y = 0.0;
+    q.zoom = 1.0;
+    int st = fr_phoenix_validate(&q, ph, width, height);
+    if (st != FR_OK) return st;
+    if ((st = check_phoenix_terms(ph)) != FR_OK) return st;
+    if (ph->use_julia_set)
+        return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deepx_phoenix: use_julia_set is not available (a Julia-mode Phoenix frame "
+                            "starts every pixel from z = 0 with the same c, so it is one colour at any depth)");
+    if (p->flags & (OTHER_FLAGS | JULIA_FLAGS))
+        return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deepx_phoenix: the BLA flags are not available (their tables belong to the "
+                            "Mandelbrot, Burning Ship and Julia paths; Phoenix has none)");
+    deep_resolved r;
+    return resolve_view(NULL, v, 0.0, 1, &r);
+}
+
+int fr_deepx_phoenix_reference_orbit(const fr_deepx_view* v, const fr_phoenix_params* ph, int32_t max_iter, double* out_mant_xy,
+                                     int32_t* out_exp2, int32_t* out_len)
+{
+    if (!ph) return fr_set_error(FR_ERR_INVALID_ARG, "fr_deepx_phoenix_reference_orbit: phoenix params is NULL");
+    deep_resolved r;
+    int st = orbit_request("fr_deepx_phoenix_reference_orbit", out_mant_xy && out_exp2 && out_len, NULL, v, NULL, max_iter, 2.0f,
+                           NULL, &r);
+    if (st != FR_OK) return st;
+    if ((st = check_phoenix_terms(ph)) != FR_OK) return st;
+    phoenix_terms t;
+    float_to_fixed_floor(ph->phoenix_p, r.fmt, t.p);
+    float_to_fixed_floor(ph->phoenix_r, r.fmt, t.r);
+    return orbit_loop(r.cr, r.ci, NULL, NULL, r.fmt, kOrbitPhoenix, &t, max_iter, 2.0f, out_mant_xy, out_exp2, out_len);
+}

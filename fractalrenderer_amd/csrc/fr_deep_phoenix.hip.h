@@ -1,6 +1,7 @@
 /*
- * fr_deep_phoenix.hip.h -- Phoenix views deeper than double precision on gfx950 (fr_render_deep_phoenix): perturbation around
- * one reference orbit with rebasing, for the second-order recurrence of shaders/phoenix.comp,
+ * fr_deep_phoenix.hip.h -- Phoenix views deeper than double precision on gfx950 (fr_render_deep_phoenix, and below 1e-290
+ * fr_render_deepx_phoenix: the second half of the file): perturbation around one reference orbit with rebasing, for the
+ * second-order recurrence of shaders/phoenix.comp,
  *
  *   z' = z^2 + c + r z_prev + p z,   z = z_prev = 0 at the start, update then test |z|^2 > 4.
  *
@@ -134,6 +135,219 @@ deep_phoenix_kernel(const DeepPhoenixArgs A)
             int esc;
             double ezx, ezy;
             deep_phoenix_orbit(A, cx, cy, z1, inside, esc, ezx, ezy);
+            const PhoenixShade sh = deep_phoenix_shade(esc, ezx, ezy, max_iter, A.stripe_density, A.rgba != nullptr);
+            if (s == 0) { nu0 = sh.smooth; it0 = esc; }
+            if (A.rgba) { acc[0] = acc[0] + sh.r; acc[1] = acc[1] + sh.g; acc[2] = acc[2] + sh.b; }
+        }
+        if (!inside) return;
+        const size_t o = plane_index(A.g, px, py, lrow);
+        if (A.rgba) {
+            const float n = (float)(aa * aa);
+            float rgb[3] = {acc[0] / n, acc[1] / n, acc[2] / n};
+            if (A.flags & FR_FLAG_POST_CHAIN) post_chain(rgb, A.brightness, A.saturation, A.contrast, true);
+            A.rgba[o] = make_float4(rgb[0], rgb[1], rgb[2], 1.0f);
+        }
+        if (A.nu) A.nu[o] = nu0;
+        if (A.iter) A.iter[o] = it0;
+    });
+}
+
+/* ---- below 1e-290: extended-exponent deltas (fr_render_deepx_phoenix) ---------------------------------------------------------
+ * deep_phoenix_orbit in the two modes of deep_orbit_x (fr_deep.hip.h; norm, (+), ldexp and the storage are the header's).  The
+ * orbit is in the extended storage: mantissa pairs and int32 exponents for the extended mode, the plain doubles for the plain
+ * one.  dc = norm(fx zm, fy zm, ze) as in deep_kernel, dcp = x_plain(dc).  A lane starts EXTENDED with dz = dq = the zero, m = 0.
+ *
+ * EXTENDED step.  Z_m = (X, Y, eZ), Z_{m+1} = (Xn, Yn, eZn), dz = (a, b, ed) normalised, dq = (c, d, eq) with |c|, |d| <= 2 (not
+ * normalised: it is a copy of an earlier dz, or a q), dc = (cx, cy, ec).  pe = 0, or FR_DEEPX_ZERO_EXP when p == 0; the exponent of
+ * the r dq term is er = eq, or FR_DEEPX_ZERO_EXP when r == 0: a term that is exactly zero never raises a common exponent.
+ *   eu = max(eZ + 1, ed);   u = (ldexp(X, eZ + 1 - eu) + ldexp(a, ed - eu),  ldexp(Y, eZ + 1 - eu) + ldexp(b, ed - eu))
+ *   et = max(eu, pe);       t = (ldexp(u.x, eu - et) + ldexp(p, pe - et),  ldexp(u.y, eu - et))
+ *   P = (t.x a - t.y b,  t.x b + t.y a) at eP = et + ed
+ *   e1 = max(eP, er);       s = (ldexp(P.x, eP - e1) + ldexp(r c, er - e1),  ldexp(P.y, eP - e1) + ldexp(r d, er - e1))
+ *   en = max(e1, ec);       n = (ldexp(s.x, e1 - en) + ldexp(cx, ec - en),  ldexp(s.y, e1 - en) + ldexp(cy, ec - en))
+ *   m += 1
+ *   ez = max(eZn, en);      z = (ldexp(Xn, eZn - ez) + ldexp(n.x, en - ez),  ldexp(Yn, eZn - ez) + ldexp(n.y, en - ez))
+ *   eq' = max(eZ, ed);      q = (ldexp(X, eZ - eq') + ldexp(a, ed - eq'),  ldexp(Y, eZ - eq') + ldexp(b, ed - eq'))
+ *   r2 = z.x z.x + z.y z.y;   escaped at i if ldexp(r2, 2 ez) > 4, lastZ = (ldexp(z.x, ez), ldexp(z.y, ez))
+ *   rebase if  r2 + ldexp((r r)(q.x q.x + q.y q.y), 2 (eq' - ez))  <  ldexp(n.x n.x + n.y n.y, 2 (en - ez)) + ldexp((r r)(a a + b b), 2 (ed - ez))
+ *           or m == N:   dz = norm(z, ez), dq = (q, eq') with FR_DEEPX_ZERO_EXP for q = 0, m = 0
+ *   else:                dz = norm(n, en), dq = (a, b, ed) -- a copy, no rounding and no second normalisation
+ *   dz.e > -400: the lane turns PLAIN with dz = ldexp(dz, dz.e), dq = ldexp(dq, dq.e) (which may flush).
+ * On operands a double holds every ldexp is exact, so the step performs the roundings of the PLAIN step in its order; from
+ * dz = dq = 0 it gives n = dc exactly.
+ *
+ * PLAIN step: deep_phoenix_orbit's step and rule, operation for operation, on the plain doubles of the orbit and dcp.  If
+ * afterwards max(|dz.x|, |dz.y|) < 2^-400 the lane turns EXTENDED with dz = norm(dz, 0), dq = norm(dq, 0).
+ *
+ * The mode depends on the new dz alone.  In the plain mode |dz| >= 2^-400, so t dz is at least 2^-800 unless t itself is down at
+ * its rounding error; an r dq or a dc that a double cannot hold (below 2^-1074) is then more than 2^200 below the sum it enters.
+ * lastZ of a lane that never escaped is Z_m (+) dz of its final state as a double.
+ *
+ * Registers across a step as in deep_phoenix_orbit: Z_{m+2} is loaded one step ahead, Z_1 is kept for the rebase, q comes from
+ * the register that held Z_m; a lane that changes mode reloads Z_m and Z_{m+1} from the new mode's arrays. */
+struct DeepPhoenixXArgs : DeepPhoenixArgs {   /* orbit: the plain doubles; zoom is not read */
+    const double2* mant;                 /* (mx, my) of Z_0 .. Z_N */
+    const int32_t* exp2;                 /* e of Z_0 .. Z_N */
+    double zm;                           /* zoom = zm 2^ze */
+    int32_t ze;
+};
+
+__device__ __forceinline__ void deep_phoenix_orbit_x(const DeepPhoenixXArgs& A, const double cx, const double cy, const int ec,
+                                                     bool live, int& esc, double& ezx, double& ezy)
+{
+    const double2* __restrict__ orbit = A.orbit;
+    const double2* __restrict__ mant = A.mant;
+    const int32_t* __restrict__ exp2 = A.exp2;
+    const int max_iter = A.max_iter, N = A.n_ref;
+    const double p = A.p, r = A.r;
+    const double rr = r * r;
+    const int pe = p == 0.0 ? kXZero : 0;
+    const bool rzero = r == 0.0;
+    const double cpx = x_plain(cx, ec), cpy = x_plain(cy, ec);   /* the plain mode's dc */
+    double dzx = 0.0, dzy = 0.0, dqx = 0.0, dqy = 0.0;           /* plain: dz, dq; extended: their mantissas */
+    int ed = kXZero, eq = kXZero;
+    bool ext = true;
+    double Zx = 0.0, Zy = 0.0;                                   /* Z_m, in the lane's mode */
+    int eZ = kXZero;
+    const double2 z1 = mant[1];
+    const int ez1 = exp2[1];
+    double Znx = z1.x, Zny = z1.y;                               /* Z_{m+1} */
+    int eZn = ez1;
+    int m = 0;
+    esc = max_iter;
+    ezx = 0.0; ezy = 0.0;
+    for (int i = 0; i < max_iter; ++i) {
+        if (__builtin_amdgcn_ballot_w64(live) == 0ull) break;
+        if (!live) continue;
+        const int mn = m + 2 <= N ? m + 2 : N;                   /* Z_{m+2}, for the next step (m + 1 < N) */
+        if (ext) {
+            const double2 Znn = mant[mn];
+            const int eZnn = exp2[mn];
+            const int eu = eZ + 1 > ed ? eZ + 1 : ed;
+            const double ux = __builtin_ldexp(Zx, eZ + 1 - eu) + __builtin_ldexp(dzx, ed - eu);
+            const double uy = __builtin_ldexp(Zy, eZ + 1 - eu) + __builtin_ldexp(dzy, ed - eu);
+            const int et = eu > pe ? eu : pe;
+            const double tx = __builtin_ldexp(ux, eu - et) + __builtin_ldexp(p, pe - et);
+            const double ty = __builtin_ldexp(uy, eu - et);
+            const double px = tx * dzx - ty * dzy;
+            const double py = tx * dzy + ty * dzx;
+            const int ep = et + ed;
+            const int er = rzero ? kXZero : eq;
+            const int e1 = ep > er ? ep : er;
+            const double sx = __builtin_ldexp(px, ep - e1) + __builtin_ldexp(r * dqx, er - e1);
+            const double sy = __builtin_ldexp(py, ep - e1) + __builtin_ldexp(r * dqy, er - e1);
+            const int en = e1 > ec ? e1 : ec;
+            const double nx = __builtin_ldexp(sx, e1 - en) + __builtin_ldexp(cx, ec - en);
+            const double ny = __builtin_ldexp(sy, e1 - en) + __builtin_ldexp(cy, ec - en);
+            ++m;                                                 /* (Zx, Zy, eZ) is Z_{m-1} from here, (dzx, dzy, ed) is dq' */
+            const int ez = eZn > en ? eZn : en;
+            const double zx = __builtin_ldexp(Znx, eZn - ez) + __builtin_ldexp(nx, en - ez);
+            const double zy = __builtin_ldexp(Zny, eZn - ez) + __builtin_ldexp(ny, en - ez);
+            const int eqq = eZ > ed ? eZ : ed;
+            const double qx = __builtin_ldexp(Zx, eZ - eqq) + __builtin_ldexp(dzx, ed - eqq);
+            const double qy = __builtin_ldexp(Zy, eZ - eqq) + __builtin_ldexp(dzy, ed - eqq);
+            const double r2 = zx * zx + zy * zy;
+            if (__builtin_ldexp(r2, 2 * ez) > 4.0) {
+                esc = i; ezx = __builtin_ldexp(zx, ez); ezy = __builtin_ldexp(zy, ez); live = false;
+                continue;
+            }
+            const double lhs = r2 + __builtin_ldexp(rr * (qx * qx + qy * qy), 2 * (eqq - ez));
+            const double rhs = __builtin_ldexp(nx * nx + ny * ny, 2 * (en - ez)) +
+                               __builtin_ldexp(rr * (dzx * dzx + dzy * dzy), 2 * (ed - ez));
+            const bool reb = lhs < rhs || m == N;
+            double ax = reb ? zx : nx, ay = reb ? zy : ny;
+            int ea = reb ? ez : en;
+            x_norm(ax, ay, ea);
+            dqx = reb ? qx : dzx; dqy = reb ? qy : dzy;
+            eq = reb ? ((qx == 0.0 && qy == 0.0) ? kXZero : eqq) : ed;
+            if (reb) m = 0;
+            if (ea <= kXThr) {                                    /* stays extended */
+                dzx = ax; dzy = ay; ed = ea;
+                if (reb) {
+                    Zx = 0.0; Zy = 0.0; eZ = kXZero; Znx = z1.x; Zny = z1.y; eZn = ez1;
+                } else {
+                    Zx = Znx; Zy = Zny; eZ = eZn; Znx = Znn.x; Zny = Znn.y; eZn = eZnn;
+                }
+                continue;
+            }
+            dzx = __builtin_ldexp(ax, ea); dzy = __builtin_ldexp(ay, ea);
+            dqx = __builtin_ldexp(dqx, eq); dqy = __builtin_ldexp(dqy, eq);
+            ext = false;
+        } else {
+            const double2 Znn = orbit[mn];
+            const double tx = ((Zx + Zx) + dzx) + p, ty = (Zy + Zy) + dzy;
+            const double nx = ((tx * dzx - ty * dzy) + r * dqx) + cpx;
+            const double ny = ((tx * dzy + ty * dzx) + r * dqy) + cpy;
+            ++m;
+            const double zx = Znx + nx, zy = Zny + ny;
+            const double qx = Zx + dzx, qy = Zy + dzy;
+            const double r2 = zx * zx + zy * zy;
+            if (r2 > 4.0) {
+                esc = i; ezx = zx; ezy = zy; live = false;
+                continue;
+            }
+            const bool reb = r2 + rr * (qx * qx + qy * qy) < (nx * nx + ny * ny) + rr * (dzx * dzx + dzy * dzy) || m == N;
+            double ax = reb ? zx : nx, ay = reb ? zy : ny;
+            dqx = reb ? qx : dzx; dqy = reb ? qy : dzy;
+            if (reb) m = 0;
+            if (!(fmax(fabs(ax), fabs(ay)) < 0x1p-400)) {         /* stays plain */
+                dzx = ax; dzy = ay;
+                if (reb) {
+                    const double2 p1 = orbit[1];
+                    Zx = 0.0; Zy = 0.0; Znx = p1.x; Zny = p1.y;
+                } else {
+                    Zx = Znx; Zy = Zny; Znx = Znn.x; Zny = Znn.y;
+                }
+                continue;
+            }
+            int ea = 0;
+            x_norm(ax, ay, ea);
+            dzx = ax; dzy = ay; ed = ea;
+            eq = 0;
+            x_norm(dqx, dqy, eq);
+            ext = true;
+        }
+        /* the lane changed its mode: Z_m and Z_{m+1} (m < N here) from the new mode's arrays */
+        if (ext) {
+            const double2 a = mant[m], b = mant[m + 1];
+            Zx = a.x; Zy = a.y; eZ = exp2[m]; Znx = b.x; Zny = b.y; eZn = exp2[m + 1];
+        } else {
+            const double2 a = orbit[m], b = orbit[m + 1];
+            Zx = a.x; Zy = a.y; Znx = b.x; Zny = b.y;
+        }
+    }
+    if (live) {                                                  /* lastZ of a sample that never escaped */
+        if (ext) {
+            const int ez = eZ > ed ? eZ : ed;
+            ezx = __builtin_ldexp(__builtin_ldexp(Zx, eZ - ez) + __builtin_ldexp(dzx, ed - ez), ez);
+            ezy = __builtin_ldexp(__builtin_ldexp(Zy, eZ - ez) + __builtin_ldexp(dzy, ed - ez), ez);
+        } else {
+            ezx = Zx + dzx; ezy = Zy + dzy;
+        }
+    }
+}
+
+__global__ void __launch_bounds__(kBlockThreads)
+deep_phoenix_x_kernel(const DeepPhoenixXArgs A)
+{
+    const uint32_t lane = threadIdx.x & (kWave - 1);
+    const int W = A.g.W, H = A.g.H, max_iter = A.max_iter;
+    const int aa = A.aa > 1 ? A.aa : 1;
+    const double resx = (double)W, resy = (double)H;
+
+    walk_subtiles<3, true>(A.q, A.g, lane, [&](const int px, const int py, const int lrow, const bool inside) {
+        float acc[3] = {0.0f, 0.0f, 0.0f};
+        double nu0 = 0.0;
+        int it0 = 0;
+        const int nsamp = aa * aa;
+        for (int s = 0; s < nsamp; ++s) {
+            const double2 dc = ShipFormula::dc(px, py, s, aa, resx, resy, A.zm);   /* on the zoom's mantissa; its exponent is dc.e */
+            double cx = inside ? dc.x : 0.0, cy = inside ? dc.y : 0.0;
+            int ec = A.ze;
+            x_norm(cx, cy, ec);
+            int esc;
+            double ezx, ezy;
+            deep_phoenix_orbit_x(A, cx, cy, ec, inside, esc, ezx, ezy);
             const PhoenixShade sh = deep_phoenix_shade(esc, ezx, ezy, max_iter, A.stripe_density, A.rgba != nullptr);
             if (s == 0) { nu0 = sh.smooth; it0 = esc; }
             if (A.rgba) { acc[0] = acc[0] + sh.r; acc[1] = acc[1] + sh.g; acc[2] = acc[2] + sh.b; }

@@ -153,7 +153,7 @@ struct fr_ctx {
      * fr_render_deepx, fr_render_deepx_ship, fr_render_deepx_julia and the sequences, with the tables of FR_FLAG_DEEPX_BLA,
      * FR_FLAG_DEEPX_SHIP_BLA, FR_FLAG_DEEPX_JULIA_BLA.  The six paths share nothing.  A Julia slot holds two orbits: Q in the
      * first half of every array, P in the second.  A seventh slot, deep[0][kPhoenix], is fr_render_deep_phoenix's: plain doubles,
-     * no table; Phoenix has no extended path, so deep[1][kPhoenix] stays empty. */
+     * no table; an eighth, deep[1][kPhoenix], is fr_render_deepx_phoenix's: the extended storage, no table either. */
     DeepSlot deep[2][kFormulas];
 };
 
@@ -847,8 +847,8 @@ struct DeepAt {
  * fraction bits, max_iter, the bailout and, in a Julia slot, the bits of c).  One orbit, or Julia's Q at point 0 and P half the
  * capacity behind it (kFormula); ext: the extended storage, whose plain doubles ldexp(mantissa, exponent) are formed here.
  * Per array and orbit, what the host wrote is uploaded and nothing else: no kernel reads a point past an orbit's length.
- * The Phoenix slot (ph; fp64 only): keyed by the bits of p and r where Julia's has c, and by the shader's fixed bailout 2,
- * since p->bailout is not read. */
+ * The two Phoenix slots (ph): keyed by the bits of p and r where Julia's has c, and by the shader's fixed bailout 2, since
+ * p->bailout is not read. */
 static int deep_slot_fill(fr_ctx* c, int f, bool ext, const fr_params* p, const DeepAt& at, hipStream_t stream,
                           const fr_phoenix_params* ph = nullptr)
 {
@@ -880,7 +880,8 @@ static int deep_slot_fill(fr_ctx* c, int f, bool ext, const fr_params* p, const 
     int32_t len[2] = {0, 0};                                      /* of the orbit at point 0, of Julia's P */
     int st;
     if (f == kPhoenix)
-        st = fr_deep_phoenix_reference_orbit(&v, ph, p->zoom, max_iter, plain, &len[0]);
+        st = ext ? fr_deepx_phoenix_reference_orbit(&x, ph, max_iter, mant, exp2, &len[0])
+                 : fr_deep_phoenix_reference_orbit(&v, ph, p->zoom, max_iter, plain, &len[0]);
     else if (f == kJulia)
         st = ext ? fr_deepx_julia_reference_orbits(&x, p->julia_c_real, p->julia_c_imag, max_iter, p->bailout, mant + 2 * second,
                                                    exp2 + second, &len[1], mant, exp2, &len[0])
@@ -1215,6 +1216,39 @@ static int enqueue_deep_phoenix(fr_ctx* c, const fr_params* p, const fr_phoenix_
     a.g = tile_geom(W, H, rows_local, &norm, out_frame);
     a.rgba = reinterpret_cast<float4*>(rgba); a.nu = (double*)nu; a.iter = iter;
     return launch_one_pass(c, stream, "deep_phoenix_kernel", deep_phoenix_kernel, a, a.g, a.q, s.wg_per_cu[0][0], false);
+}
+
+/* ... and below 1e-290 (fr_render_deepx_phoenix): the same steps around the extended slot, deep[1][kPhoenix], and
+ * deep_phoenix_x_kernel; the view's zoom string resolved as deep_entry resolves an extended view's */
+static int enqueue_deepx_phoenix(fr_ctx* c, const fr_params* p, const fr_phoenix_params* ph, const fr_deepx_view* v, uint32_t W,
+                                 uint32_t H, const fr_shard* shard, float* rgba, void* nu, int32_t* iter, hipStream_t stream,
+                                 bool out_frame)
+{
+    fr_shard norm;
+    uint32_t rows_local = 0;
+    const int sh = begin_shard(c, shard, H, &norm, &rows_local);
+    if (sh != FR_OK || rows_local == 0) return sh;
+    DeepAt at = {v->center_x, v->center_y, v->zoom, 0.0, 0, v->frac_bits};
+    const int rs = fr_deepx_resolve(v, &at.zm, &at.ze, &at.bits);
+    if (rs != FR_OK) return rs;
+    const int os = deep_slot_fill(c, kPhoenix, true, p, at, stream, ph);
+    if (os != FR_OK) return os;
+
+    DeepSlot& s = deep_slot(c, true, kPhoenix);
+    DeepPhoenixXArgs a;
+    memset(&a, 0, sizeof(a));
+    a.orbit = reinterpret_cast<const double2*>(s.o.dev); a.n_ref = s.o.len - 1;
+    a.mant = a.orbit + s.o.cap;
+    a.exp2 = reinterpret_cast<const int32_t*>(a.mant + s.o.cap);
+    a.zm = at.zm; a.ze = at.ze;                                  /* (zoom is not read) */
+    a.max_iter = p->max_iterations; a.aa = p->antialiasing_samples;
+    a.p = (double)ph->phoenix_p; a.r = (double)ph->phoenix_r;
+    a.stripe_density = p->stripe_density;
+    a.brightness = p->color_brightness; a.saturation = p->color_saturation; a.contrast = p->color_contrast;
+    a.flags = p->flags;
+    a.g = tile_geom(W, H, rows_local, &norm, out_frame);
+    a.rgba = reinterpret_cast<float4*>(rgba); a.nu = (double*)nu; a.iter = iter;
+    return launch_one_pass(c, stream, "deep_phoenix_x_kernel", deep_phoenix_x_kernel, a, a.g, a.q, s.wg_per_cu[0][0], false);
 }
 
 /* ---- deep zoom sequences (fr_deep_sequence; the rules are in the header, the host planning in fr_deepseq.c) ---------------
@@ -2311,6 +2345,34 @@ extern "C" int fr_render_deep_phoenix(fr_ctx* c, const fr_params* p, const fr_ph
     if (st != FR_OK) return st;
     return render_sync(c, p, W, H, shard, out, {}, [&](auto sh, auto rgba, auto nu, auto iter, auto, auto s, bool out_frame) {
         return enqueue_deep_phoenix(c, p, ph, v, W, H, sh, rgba, nu, iter, s, out_frame); });
+}
+
+/* fr_render_deepx_phoenix: the same with an extended view */
+static int check_deepx_phoenix(fr_ctx* c, const fr_params* p, const fr_phoenix_params* ph, const fr_deepx_view* v, uint32_t W,
+                               uint32_t H, const fr_output* out)
+{
+    if (!c) return fr_set_error(FR_ERR_INVALID_ARG, "ctx is NULL");
+    if (!p || !ph || !v || !out) return fr_set_error(FR_ERR_INVALID_ARG, "params/phoenix params/deep view/out is NULL");
+    return fr_deepx_phoenix_validate(p, ph, v, W, H);
+}
+
+extern "C" int fr_render_deepx_phoenix_async(fr_ctx* c, const fr_params* p, const fr_phoenix_params* ph, const fr_deepx_view* v,
+                                             uint32_t W, uint32_t H, const fr_shard* shard, const fr_output* out, void* hip_stream)
+{
+    const int st = check_deepx_phoenix(c, p, ph, v, W, H, out);
+    if (st != FR_OK) return st;
+    return render_async("fr_render_deepx_phoenix_async", c, H, shard, out, {}, hip_stream,
+                        [&](auto sh, auto rgba, auto nu, auto iter, auto, auto s, bool out_frame) {
+                            return enqueue_deepx_phoenix(c, p, ph, v, W, H, sh, rgba, nu, iter, s, out_frame); });
+}
+
+extern "C" int fr_render_deepx_phoenix(fr_ctx* c, const fr_params* p, const fr_phoenix_params* ph, const fr_deepx_view* v, uint32_t W,
+                                       uint32_t H, const fr_shard* shard, const fr_output* out)
+{
+    const int st = check_deepx_phoenix(c, p, ph, v, W, H, out);
+    if (st != FR_OK) return st;
+    return render_sync(c, p, W, H, shard, out, {}, [&](auto sh, auto rgba, auto nu, auto iter, auto, auto s, bool out_frame) {
+        return enqueue_deepx_phoenix(c, p, ph, v, W, H, sh, rgba, nu, iter, s, out_frame); });
 }
 
 /* fr_render_deep_ship_de, fr_render_deepx_ship_de: fr_render_deep_de's five planes on the two ship paths, deriv four doubles per

@@ -77,7 +77,7 @@ int64_t fr_deepx_ship_bla_table(fr_ctx* ctx, void* r, double* ab, int32_t* ab_ex
  * (a cached table serves a render without a build) */
 int64_t fr_deep_bla_builds(fr_ctx* ctx, int extended, int formula);
 /* tests: how often the orbit slot of a path has received another orbit (a render of the view it holds leaves it unchanged):
- * extended 0 / 1, formula as above and 3 Phoenix (fr_render_deep_phoenix, fp64 storage only) */
+ * extended 0 / 1, formula as above and 3 Phoenix (fr_render_deep_phoenix, fr_render_deepx_phoenix) */
 int64_t fr_deep_orbit_generation(fr_ctx* ctx, int extended, int formula);
 
 /* the context's own stream (hipStream_t) and device ordinal: fr_node.cpp orders RCCL transfers behind the renders */

@@ -379,17 +379,36 @@ class Renderer:
         strings; `phoenix` carries phoenix_p and phoenix_r as for render_phoenix() (use_julia_set must stay off: a Julia-mode
         Phoenix frame is one colour).  The zoom, in [1e-290, 1e3], and every other field come from `state` (its double centre
         is not read).  Always fp64: nu is float64.  Planes, shard, stream and sync as for render_deep_ship(); the context keeps
-        the Phoenix orbit in a slot of its own.  A view with a zoom string is a ValueError: there are no extended-exponent
-        deltas, BLA or distance estimates on this path."""
+        the Phoenix orbit in a slot of its own.  A view with a zoom string is a ValueError (render_deepx_phoenix() takes
+        those); there is no BLA and no distance estimate on this path."""
         if view is not None and view.zoom is not None:
-            raise ValueError("render_deep_phoenix takes the zoom from the state: extended views (a zoom string) are not "
-                             "available for Phoenix")
+            raise ValueError("render_deep_phoenix takes the zoom from the state: render_deepx_phoenix renders views with a zoom "
+                             "string")
         p = state.to_params(FractalType.Phoenix, Precision.F64, post_chain)
         ph = (phoenix or PhoenixParams()).to_c()
         v = (view or DeepView()).to_c()
         rows = shard.rows(height) if shard else height
         self._render_call(self._lib.fr_render_deep_phoenix, self._lib.fr_render_deep_phoenix_async,
                           (C.byref(p), C.byref(ph), C.byref(v)), width, height, Precision.F64, rows, rgba, nu, iter, shard, stream,
+                          sync)
+
+    def render_deepx_phoenix(self, state: FractalState, width: int, height: int, view: DeepView,
+                             phoenix: Optional[PhoenixParams] = None, *, post_chain: bool = False, rgba=None, nu=None, iter=None,
+                             shard: Optional[Shard] = None, stream: Optional[int] = None, sync: bool = True) -> None:
+        """fr_render_deepx_phoenix / fr_render_deepx_phoenix_async: a Phoenix view with extended-exponent deltas, zooms down to
+        1e-1000.  `view` carries the centre and the zoom as decimal strings (DeepView(..., zoom="1e-400")); a view without a
+        zoom string is a ValueError (render_deep_phoenix() takes those).  state.zoom and its double centre are not read;
+        `phoenix` and every other argument as for render_deep_phoenix().  The context keeps this path's orbit in a slot of its
+        own."""
+        if view is None or view.zoom is None:
+            raise ValueError("render_deepx_phoenix needs a view with a zoom string (DeepView(..., zoom=\"1e-400\")); "
+                             "render_deep_phoenix renders views without one")
+        p = state.to_params(FractalType.Phoenix, Precision.F64, post_chain)
+        ph = (phoenix or PhoenixParams()).to_c()
+        vx = view.to_cx()
+        rows = shard.rows(height) if shard else height
+        self._render_call(self._lib.fr_render_deepx_phoenix, self._lib.fr_render_deepx_phoenix_async,
+                          (C.byref(p), C.byref(ph), C.byref(vx)), width, height, Precision.F64, rows, rgba, nu, iter, shard, stream,
                           sync)
 
     def render_deepx_ship(self, state: FractalState, width: int, height: int, view: DeepView, *, post_chain: bool = False,

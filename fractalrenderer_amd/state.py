@@ -285,6 +285,19 @@ def deepx_ship_reference_orbit(view: DeepView, max_iterations: int, bailout: flo
     return mant[:n.value].copy(), exp2[:n.value].copy()
 
 
+def deepx_phoenix_reference_orbit(view: DeepView, max_iterations: int, phoenix: Optional[PhoenixParams] = None) -> tuple:
+    """fr_deepx_phoenix_reference_orbit: deep_phoenix_reference_orbit's orbit of a view with a zoom string, in the extended
+    storage: (mant, exp2) as deepx_reference_orbit returns them."""
+    mant = np.empty((int(max_iterations) + 1, 2), np.float64)
+    exp2 = np.empty(int(max_iterations) + 1, np.int32)
+    n = _capi.C.c_int32()
+    v = view.to_cx()
+    ph = (phoenix or PhoenixParams()).to_c()
+    _capi.check(_capi.lib().fr_deepx_phoenix_reference_orbit(_capi.C.byref(v), _capi.C.byref(ph), int(max_iterations),
+                                                             mant.ctypes.data, exp2.ctypes.data, _capi.C.byref(n)))
+    return mant[:n.value].copy(), exp2[:n.value].copy()
+
+
 def deep_julia_reference_orbits(view: DeepView, c, max_iterations: int, bailout: float = 4.0, zoom: float = 1.0) -> tuple:
     """fr_deep_julia_reference_orbits / fr_deepx_julia_reference_orbits: the two orbits of a deep Julia view (host only).
     c = (c_re, c_im), doubles.  P starts at the view's centre, Q at 0.  A view without a zoom string gives

@@ -1469,7 +1469,7 @@ int fr_render_deepx_ship_de_async(fr_ctx* ctx, const fr_params* p, const fr_deep
  * The context keeps the most recent Phoenix orbit on the device in a slot of its own, keyed by the centre strings, F,
  * max_iterations and the bits of p and r: no other deep path evicts it, and it evicts none of theirs.
  *
- * Out of scope: extended exponents below 1e-290, BLA, distance estimates, sequences, fr_node, .franim and Julia mode. */
+ * Out of scope: BLA, distance estimates, sequences, fr_node, .franim and Julia mode; below 1e-290: fr_render_deepx_phoenix. */
 #define FR_HAS_DEEP_PHOENIX 1
 
 /* What fr_render_deep_phoenix checks of its arguments, the centre strings parsed included (no context needed). */
@@ -1488,6 +1488,76 @@ int fr_render_deep_phoenix(fr_ctx* ctx, const fr_params* p, const fr_phoenix_par
 /* fr_render_deep_async's contract: a render of a new view computes its orbit on the host first and is never launch-only */
 int fr_render_deep_phoenix_async(fr_ctx* ctx, const fr_params* p, const fr_phoenix_params* ph, const fr_deep_view* view,
                                  uint32_t width, uint32_t height, const fr_shard* shard, const fr_output* out, void* hip_stream);
+
+/* ---- Phoenix views below 1e-290: extended-exponent deltas ------------------------------------------------------------------
+ * fr_render_deep_phoenix stops at 1e-290, where a double can no longer hold the zoom, dc or its two deltas.  These entry points
+ * take fr_render_deep_phoenix's arguments with a fr_deepx_view -- centre AND zoom as decimal strings, 1e-1000 <= zoom <= 1e3 as for
+ * fr_render_deepx -- and carry dz and dq each as two double mantissas and one int32 exponent while they are small.  p->zoom,
+ * p->center_x and p->center_y are not read.  Nothing about fr_render_deep_phoenix changes (it still refuses a zoom below 1e-290).
+ *
+ * Validation (fr_deepx_phoenix_validate): fr_deep_phoenix_validate's rules in its order -- NULL arguments; FR_FRACTAL_PHOENIX and
+ * FR_PRECISION_F64, otherwise FR_ERR_UNSUPPORTED; the frame size and the fields Phoenix reads; |p|, |r| < 2^32; use_julia_set is
+ * FR_ERR_UNSUPPORTED for the reason given there; every BLA flag is FR_ERR_UNSUPPORTED -- then the view as fr_deepx_validate
+ * checks its own: reserved, frac_bits, the centre strings, the zoom string and its range (FR_ERR_INVALID_ARG).
+ *
+ * Reference orbit (fr_deepx_phoenix_reference_orbit): fr_deep_phoenix_reference_orbit's recurrence at F = frac_bits or
+ * fr_deepx_frac_bits(zoom), in the extended storage of fr_deepx_reference_orbit (signed mantissas, int32 exponents,
+ * FR_DEEPX_ZERO_EXP for the zero).  Where both entry points accept a view the points are equal bit for bit.
+ *
+ * Per sample: dc = norm(fx zm, fy zm, ze) with fr_render_deep_phoenix's map on the zoom's mantissa, dcp = dc as plain doubles
+ * (a component below 2^-1022 is 0); dz = dq = the zero, m = 0, mode EXTENDED.  Notation (norm, (+), ldexp, extended numbers) as for
+ * fr_render_deepx.  For i = 0 .. max_iter-1 one step in the sample's mode, p and r widened to double.
+ *   EXTENDED: Z_m = (X, Y, eZ), Z_{m+1} = (Xn, Yn, eZn), dz = (a, b, ed) normalised, dq = (c, d, eq), |c|, |d| <= 2.  pe = 0, or
+ *   FR_DEEPX_ZERO_EXP when p == 0; er = eq, or FR_DEEPX_ZERO_EXP when r == 0 (an exact zero never raises a common exponent).
+ *     eu = max(eZ + 1, ed);   u = (ldexp(X, eZ + 1 - eu) + ldexp(a, ed - eu),  ldexp(Y, eZ + 1 - eu) + ldexp(b, ed - eu))
+ *     et = max(eu, pe);       t = (ldexp(u.x, eu - et) + ldexp(p, pe - et),  ldexp(u.y, eu - et))
+ *     P = (t.x a - t.y b,  t.x b + t.y a) at eP = et + ed
+ *     e1 = max(eP, er);       s = (ldexp(P.x, eP - e1) + ldexp(r c, er - e1),  ldexp(P.y, eP - e1) + ldexp(r d, er - e1))
+ *     en = max(e1, ec);       n = (ldexp(s.x, e1 - en) + ldexp(dc.x, ec - en),  ldexp(s.y, e1 - en) + ldexp(dc.y, ec - en))
+ *     m += 1
+ *     ez = max(eZn, en);      z = (ldexp(Xn, eZn - ez) + ldexp(n.x, en - ez),  ldexp(Yn, eZn - ez) + ldexp(n.y, en - ez))
+ *     eq' = max(eZ, ed);      q = (ldexp(X, eZ - eq') + ldexp(a, ed - eq'),  ldexp(Y, eZ - eq') + ldexp(b, ed - eq'))
+ *     r2 = z.x z.x + z.y z.y;   escaped at i if ldexp(r2, 2 ez) > 4, lastZ = (ldexp(z.x, ez), ldexp(z.y, ez))
+ *     else rebase if
+ *       r2 + ldexp((r r)(q.x q.x + q.y q.y), 2 (eq' - ez)) < ldexp(n.x n.x + n.y n.y, 2 (en - ez)) + ldexp((r r)(a a + b b), 2 (ed - ez))
+ *       or m == N:      dz = norm(z, ez), dq = (q, eq') with FR_DEEPX_ZERO_EXP for q = 0, m = 0
+ *     else:             dz = norm(n, en), dq = (a, b, ed): a copy, no rounding, no second normalisation
+ *     If now dz.e > -400 the sample turns PLAIN with dz = ldexp(dz, dz.e), dq = ldexp(dq, dq.e), which may flush.
+ *   PLAIN: the step and the rule of fr_render_deep_phoenix, operation for operation, on the plain doubles of the orbit and dcp.
+ *     If afterwards max(|dz.x|, |dz.y|) < 2^-400 the sample turns EXTENDED with dz = norm(dz, 0), dq = norm(dq, 0).
+ * The mode is decided by the new dz alone.  In the plain mode |dz| >= 2^-400, so t dz is at least 2^-800 unless t is down at its
+ * own rounding error, and an r dq or a dc that a double cannot hold is more than 2^200 below the sum it enters.  On operands a double
+ * holds every ldexp is exact and the extended step performs the plain step's roundings, so on every view fr_render_deep_phoenix
+ * accepts (the zoom string naming its double) iter, nu and rgba are its bytes.  lastZ of a sample that never escaped is
+ * Z_m (+) dz of its final state as a double.  Planes, shards, memory kinds, options and the asynchronous form as there.
+ *
+ * The pair rebase rule stays empirical: below 1e-290 it was checked against the exact iteration of every pixel on the views of
+ * tests/deepx_phoenix_ref.py (1e-310 and 1e-400 with r = -0.5 and -0.375; 1e-1000 with p = r = 0).  No view with r != 0 was
+ * checked below 1e-400.  Near Z_m = -p/2 the sum 2 Z_m + p cancels and the stored orbit point limits it to about 2^-53 |p|
+ * absolute accuracy, exactly as in fr_render_deep_phoenix.
+ *
+ * The context keeps the most recent extended Phoenix orbit in a slot of its own, keyed by the centre strings, F,
+ * max_iterations and the bits of p and r: it evicts no other slot and none evicts it.
+ *
+ * Out of scope: BLA, distance estimates, sequences, fr_node, .franim and Julia mode. */
+#define FR_HAS_DEEPX_PHOENIX 1
+
+/* What fr_render_deepx_phoenix checks of its arguments, the view's strings parsed included (no context needed). */
+int fr_deepx_phoenix_validate(const fr_params* p, const fr_phoenix_params* ph, const fr_deepx_view* view, uint32_t width,
+                              uint32_t height);
+
+/* Z_0 .. Z_N of the view's centre in the extended storage (host only): out_mant_xy holds 2 (max_iter + 1) doubles, out_exp2
+ * max_iter + 1 exponents, *out_len receives N + 1.  Reads ph's p and r (finite, below 2^32). */
+int fr_deepx_phoenix_reference_orbit(const fr_deepx_view* view, const fr_phoenix_params* ph, int32_t max_iter, double* out_mant_xy,
+                                     int32_t* out_exp2, int32_t* out_len);
+
+/* fr_render_deep_phoenix's contract for an extended view */
+int fr_render_deepx_phoenix(fr_ctx* ctx, const fr_params* p, const fr_phoenix_params* ph, const fr_deepx_view* view, uint32_t width,
+                            uint32_t height, const fr_shard* shard, const fr_output* out);
+
+/* fr_render_deep_async's contract: a render of a new view computes its orbit on the host first and is never launch-only */
+int fr_render_deepx_phoenix_async(fr_ctx* ctx, const fr_params* p, const fr_phoenix_params* ph, const fr_deepx_view* view,
+                                  uint32_t width, uint32_t height, const fr_shard* shard, const fr_output* out, void* hip_stream);
 
 /* ---- frames over the GPUs of a node (BASELINE.json north_star: "tiled across the 8 GPUs of one node as disjoint row
  * bands with a final RCCL gather over xGMI") -----------------------------------------------------------------------------

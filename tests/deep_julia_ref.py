@@ -267,7 +267,7 @@ def perturb_x(Px, Qx, d0, max_iter: int, bailout: float = 4.0, stats=None):
     m = np.zeros(n, np.int64)
     base = np.full(n, poff, np.int64)
     N = np.full(n, NP, np.int64)
-    n_ext = n_plain = n_reb = n_flush = 0
+    n_ext = n_plain = n_reb = n_flush = to_plain = to_ext = 0
     with np.errstate(all="ignore"):
         for i in range(max_iter):
             if idx.size == 0:
@@ -303,6 +303,7 @@ def perturb_x(Px, Qx, d0, max_iter: int, bailout: float = 4.0, stats=None):
                 n_flush += int((fl & (ea != X.X_ZERO) & ~es).sum())
                 ax, ay, ea = np.where(fl, 0.0, ax), np.where(fl, 0.0, ay), np.where(fl, X.X_ZERO, ea)
                 stay = ea <= X.X_THR
+                to_plain += int((~stay & ~es).sum())
                 dx[E] = np.where(stay, ax, _ld(ax, np.where(stay, 0, ea)))
                 dy[E] = np.where(stay, ay, _ld(ay, np.where(stay, 0, ea)))
                 ed[E] = ea
@@ -331,6 +332,7 @@ def perturb_x(Px, Qx, d0, max_iter: int, bailout: float = 4.0, stats=None):
                 ax = np.where(reb, zx, nx)
                 ay = np.where(reb, zy, ny)
                 small = np.maximum(np.abs(ax), np.abs(ay)) < X._THR
+                to_ext += int((small & ~es).sum())
                 bx, by, be = _norm(ax, ay, np.zeros(P.size, np.int64))
                 dx[P] = np.where(small, bx, ax)
                 dy[P] = np.where(small, by, ay)
@@ -347,7 +349,8 @@ def perturb_x(Px, Qx, d0, max_iter: int, bailout: float = 4.0, stats=None):
                 k = ~esc
                 idx, dx, dy, ed, ext, m, base, N = idx[k], dx[k], dy[k], ed[k], ext[k], m[k], base[k], N[k]
     if stats is not None:
-        for key, val in (("ext_steps", n_ext), ("plain_steps", n_plain), ("rebases", n_reb), ("flushes", n_flush)):
+        for key, val in (("ext_steps", n_ext), ("plain_steps", n_plain), ("rebases", n_reb), ("flushes", n_flush),
+                         ("to_plain", to_plain), ("to_ext", to_ext)):
             stats[key] = stats.get(key, 0) + val
     return it, r2out
 

@@ -53,7 +53,13 @@ PX310 = dict(cx=_round_decimals(PX400A["cx"], 322), cy=_round_decimals(PX400A["c
 # escapes at index 0 by a margin of 1e-1000, which no 53-bit z = Z_1 + dz can show (|z|^2 rounds to 4); moved right, every pixel has
 # Re c > -2, row H/2 is the antenna itself (interior), and the exact iteration shows 8 escape indices, 1660 .. 1667.
 TIP1000 = dict(cx="-1." + "9" * 1000 + "328", cy="0", zoom="1e-1000", max_iter=2400, p=0.0, r=0.0)
-NEW_VIEWS = {"PX310": PX310, "PX400A": PX400A, "PX400B": PX400B, "TIP1000": TIP1000}
+# PXRET: PX400A's centre at a zoom at which most lanes of a 24x18 frame turn plain and fall back to the extended mode at least
+# once (367 of 432 in the restatement): the plain-to-extended block of the Phoenix loop with r != 0, dq normalised with dz.
+# The strings are rounded to 342 decimals as PX310's are to 322: PX400A's centre lies within 1e-400 of the boundary, the
+# sample with dc = 0 is the centre itself, and the orbit (F = 1280 bits) and the exact iteration (F + 64) round a longer
+# string to two numbers on either side of that boundary (escape at 2825 against none: measured).
+PXRET = dict(PX400A, cx=_round_decimals(PX400A["cx"], 342), cy=_round_decimals(PX400A["cy"], 342), zoom="7e-330")
+NEW_VIEWS = {"PX310": PX310, "PX400A": PX400A, "PX400B": PX400B, "TIP1000": TIP1000, "PXRET": PXRET}
 
 
 def as_x_view(v: dict) -> dict:

@@ -84,7 +84,7 @@ def test_planes_on_a_ragged_frame_with_aa_3(fr, renderer):
     _check_planes("PX400A", _render(fr, renderer, VIEWS["PX400A"], 3, True, 10.0, w=w, h=h), w, h, 3, True, 10.0)
 
 
-@pytest.mark.parametrize("name", ["PX310", "PX400A", "TIP1000"])
+@pytest.mark.parametrize("name", ["PX310", "PX400A", "TIP1000", "PXRET"])
 def test_iter_is_the_exact_iteration(fr, renderer, name):
     w, h = SMALL
     _, _, it = _render(fr, renderer, VIEWS[name], w=w, h=h)

@@ -1037,8 +1037,9 @@ int fr_deep_phoenix_validate(const fr_params* p, const fr_phoenix_params* ph, co
                             "starts every pixel from z = 0 with the same c, so it is one colour at any depth)");
     if ((st = check_zoom(p->zoom)) != FR_OK) return st;
     if (p->flags & (OTHER_FLAGS | JULIA_FLAGS))
-        return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deep_phoenix: the BLA flags are not available (their tables belong to the "
-                            "Mandelbrot, Burning Ship and Julia paths; Phoenix has none)");
+        return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deep_phoenix: the BLA flags of the other paths are not available (their "
+                            "tables belong to the Mandelbrot, Burning Ship and Julia paths): the flag of this entry point is "
+                            "FR_FLAG_DEEP_PHOENIX_BLA");
     deep_resolved r;
     return resolve_view(v, NULL, p->zoom, 1, &r);
 }
@@ -1080,7 +1081,10 @@ int fr_deepx_phoenix_validate(const fr_params* p, const fr_phoenix_params* ph, c
                             "starts every pixel from z = 0 with the same c, so it is one colour at any depth)");
     if (p->flags & (OTHER_FLAGS | JULIA_FLAGS))
         return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deepx_phoenix: the BLA flags are not available (their tables belong to the "
-                            "Mandelbrot, Burning Ship and Julia paths; Phoenix has none)");
+                            "Mandelbrot, Burning Ship and Julia paths; extended Phoenix views have none)");
+    if (p->flags & FR_FLAG_DEEP_PHOENIX_BLA)
+        return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deepx_phoenix: FR_FLAG_DEEP_PHOENIX_BLA is not available (its BLA table is "
+                            "fp64, fr_render_deep_phoenix's; extended Phoenix views have none)");
     deep_resolved r;
     return resolve_view(NULL, v, 0.0, 1, &r);
 }

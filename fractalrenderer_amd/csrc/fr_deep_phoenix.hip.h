@@ -33,6 +33,8 @@
  *   - the colour stage is phoenix_kernel<double>'s: phoenix_smooth on (i, lastZ) in double, phoenix_colour on
  *     (smooth / max_iter, smooth, lastZ) narrowed to float, the aa x aa average, post_chain with Phoenix's floors.  lastZ of a
  *     sample that never escaped is Z_m + dz of its final state, the z of its last update.
+ * Behind the kernel: iteration skipping for this path (FR_FLAG_DEEP_PHOENIX_BLA) -- the table's level kernel, the flagged loop
+ * and its kernel; then the extended half.
  */
 #pragma once
 #include "fr_deep.hip.h"
@@ -150,6 +152,232 @@ deep_phoenix_kernel(const DeepPhoenixArgs A)
         if (A.nu) A.nu[o] = nu0;
         if (A.iter) A.iter[o] = it0;
     });
+}
+
+/* ---- iteration skipping (FR_FLAG_DEEP_PHOENIX_BLA; the header's section is the contract) ----------------------------------------
+ * The linear part of the step acts on the PAIR (dz, dq): an entry of the table is a complex 2 x 2 matrix M = (M11, M12, M21, M22),
+ * a complex 2-vector B = (B1, B2) and a radius that bounds |dz|^2 + |dq|^2.  Levels, coverage and entry count are those of the
+ * other fp64 tables (bla_offset, bla_top_level of fr_deep.hip.h); the storage is BlaTable's, r in an array of its own and six
+ * double2 per entry in ab: M's four, then B's two. */
+constexpr int kPhoenixMbPerEntry = 6;
+
+struct PhoenixLin {
+    double2 m[4];                        /* M11, M12, M21, M22 */
+    double2 b[2];                        /* B1, B2 */
+    double r;
+};
+
+__device__ __forceinline__ double2 pc_mul(const double2 a, const double2 b)
+{
+    return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
+}
+__device__ __forceinline__ double2 pc_add(const double2 a, const double2 b) { return make_double2(a.x + b.x, a.y + b.y); }
+__device__ __forceinline__ double pc_n2(const double2 c) { return c.x * c.x + c.y * c.y; }
+
+/* the single step at Z_m, 1 <= m <= N - 1: dz' = (2 Z_m + p) dz + r dq + dc, dq' = dz, valid while the dropped dz^2 stays below
+ * one rounding of a dz */
+__device__ __forceinline__ PhoenixLin phoenix_single(const double2 Z, const double p, const double r)
+{
+    PhoenixLin s;
+    const double ax = (Z.x + Z.x) + p, ay = Z.y + Z.y;
+    s.m[0] = make_double2(ax, ay); s.m[1] = make_double2(r, 0.0);
+    s.m[2] = make_double2(1.0, 0.0); s.m[3] = make_double2(0.0, 0.0);
+    s.b[0] = make_double2(1.0, 0.0); s.b[1] = make_double2(0.0, 0.0);
+    s.r = 0x1p-54 * bla_abs(ax, ay);
+    return s;
+}
+
+/* Level k of the table, as bla_level builds the others': entry j merges x (level k - 1, entry 2j) and y (entry 2j + 1), level 0
+ * being the single steps from the orbit.  M = M_y M_x, B = M_y B_x + B_y,
+ * r = min(r_x, max(0, (r_y - |B_x| dcmax) / |M_x|)) with the Frobenius norm of M_x, 0 when an element is not finite. */
+__global__ void __launch_bounds__(kBlockThreads)
+phoenix_bla_level_kernel(const double2* __restrict__ orbit, const int32_t n_ref, const int32_t k, const double dcmax,
+                              const double p, const double r, double* __restrict__ rad, double2* __restrict__ mb)
+{
+    constexpr int S = kPhoenixMbPerEntry;
+    const uint32_t n1 = (uint32_t)(n_ref - 1);
+    const uint32_t cnt = n1 >> k;
+    const uint32_t off = bla_offset(n1, k);
+    const uint32_t offp = k > 1 ? bla_offset(n1, k - 1) : 0u;
+    for (uint32_t j = blockIdx.x * kBlockThreads + threadIdx.x; j < cnt; j += gridDim.x * kBlockThreads) {
+        PhoenixLin x, y;
+        if (k == 1) {
+            x = phoenix_single(orbit[1 + 2 * j], p, r);
+            y = phoenix_single(orbit[2 + 2 * j], p, r);
+        } else {
+            const uint32_t ex = offp + 2 * j, ey = ex + 1;
+            for (int i = 0; i < 4; ++i) { x.m[i] = mb[S * ex + i]; y.m[i] = mb[S * ey + i]; }
+            for (int i = 0; i < 2; ++i) { x.b[i] = mb[S * ex + 4 + i]; y.b[i] = mb[S * ey + 4 + i]; }
+            x.r = rad[ex]; y.r = rad[ey];
+        }
+        double2 m[4], b[2];
+        bool finite = true;
+        for (int i = 0; i < 2; ++i) {
+            for (int c = 0; c < 2; ++c) m[2 * i + c] = pc_add(pc_mul(y.m[2 * i], x.m[c]), pc_mul(y.m[2 * i + 1], x.m[2 + c]));
+            b[i] = pc_add(pc_add(pc_mul(y.m[2 * i], x.b[0]), pc_mul(y.m[2 * i + 1], x.b[1])), y.b[i]);
+        }
+        for (int i = 0; i < 4; ++i) finite = finite && __builtin_isfinite(m[i].x) && __builtin_isfinite(m[i].y);
+        for (int i = 0; i < 2; ++i) finite = finite && __builtin_isfinite(b[i].x) && __builtin_isfinite(b[i].y);
+        const double nm = sqrt((pc_n2(x.m[0]) + pc_n2(x.m[1])) + (pc_n2(x.m[2]) + pc_n2(x.m[3])));
+        const double nb = sqrt(pc_n2(x.b[0]) + pc_n2(x.b[1]));
+        const double t = (y.r - nb * dcmax) / nm;
+        double rr = t > 0.0 ? t : 0.0;                           /* NaN: 0 */
+        rr = rr < x.r ? rr : x.r;
+        if (!finite) rr = 0.0;
+        const uint32_t e = off + j;
+        rad[e] = rr;
+        for (int i = 0; i < 4; ++i) mb[S * e + i] = m[i];
+        for (int i = 0; i < 2; ++i) mb[S * e + 4 + i] = b[i];
+    }
+}
+
+/* Kernel argument block of deep_phoenix_bla_kernel */
+struct DeepPhoenixBlaArgs : DeepPhoenixArgs {
+    BlaTable t;
+};
+
+/* deep_phoenix_orbit with BLA: u replaces the loop index.  A lane at m >= 1 probes the levels top down from bla_top_level (radii
+ * are monotone in k) and takes the first whose radius admits the pair, else the plain step, operation for operation
+ * deep_phoenix_orbit's; BLA and plain lanes of a wave take their steps in the same trip.  No level's radius exceeds the single
+ * step's 2^-54 |2 Z_m + p| <= 2^-54 (4 + |p|), so a lane whose pair has |dz|^2 + |dq|^2 >= 2^-104 (4 + |p|)^2 (a bound sixteen
+ * times above, with room for every rounding, and one compare against a wave-uniform constant) cannot pass a probe and gathers
+ * nothing.  A BLA lane loads Z_m and Z_{m-1} at its new m, and Z_{m+1} if it goes on from there (the Z_{m+2} prefetch is for the
+ * plain step).  nplain / nbla: the steps this sample took. */
+__device__ __forceinline__ void deep_phoenix_orbit_bla(const DeepPhoenixArgs& A, const BlaTable& T, const double dcx,
+                                                       const double dcy, const double2 z1, bool live, int& esc, double& ezx,
+                                                       double& ezy, uint32_t& nplain, uint32_t& nbla)
+{
+    const double2* __restrict__ orbit = A.orbit;
+    const double* __restrict__ tr = T.r;
+    const double2* __restrict__ tmb = T.ab;
+    const int max_iter = A.max_iter, N = A.n_ref, K = T.levels;
+    const uint32_t n1 = (uint32_t)(N - 1);
+    const double p = A.p, r = A.r;
+    const double rr = r * r;
+    double dzx = 0.0, dzy = 0.0, dqx = 0.0, dqy = 0.0;
+    double Zx = 0.0, Zy = 0.0;                                   /* Z_m */
+    double Znx = z1.x, Zny = z1.y;                               /* Z_{m+1} */
+    /* |dz|^2 + |dq|^2 of a lane at m >= 1, (dz.x dz.x + dz.y dz.y) + (dq.x dq.x + dq.y dq.y): the two sums are those of the
+     * rebase test that let the lane go on from its last step, so the probe's operand costs one addition.  (A rebased lane is at
+     * m = 0 and probes nothing before its next step.) */
+    double v2 = 0.0;
+    const double amax = 4.0 + fabs(p);                           /* |2 Z_m + p| <= 4 + |p| for m < N, where |Z_m| <= 2 */
+    const double vmax = 0x1p-104 * (amax * amax);
+    int m = 0, u = 0;
+    esc = max_iter;
+    ezx = 0.0; ezy = 0.0;
+    nplain = 0u; nbla = 0u;
+    for (;;) {
+        if (__builtin_amdgcn_ballot_w64(live) == 0ull) break;
+        if (!live) continue;
+        const double2 Znn = orbit[m + 2 <= N ? m + 2 : N];       /* Z_{m+2}, for a plain step */
+        int k = 0;
+        uint32_t e = 0u;
+        if (m >= 1 && v2 < vmax) {
+            const uint32_t mm = (uint32_t)(m - 1);
+            for (int kk = bla_top_level(mm, K, N, m, max_iter, u); kk >= 1; --kk) {
+                const uint32_t ek = bla_offset(n1, kk) + (mm >> kk);
+                const double rad = tr[ek];
+                if (v2 < rad * rad) { k = kk; e = ek; break; }
+            }
+        }
+        double nx, ny, nqx, nqy;                                 /* dz', dq' */
+        double Zmx, Zmy, Zpx, Zpy;                               /* Z_m and Z_{m-1} behind the step */
+        if (k > 0) {
+            const double2* __restrict__ E = tmb + (size_t)kPhoenixMbPerEntry * e;
+            const double2 dz = make_double2(dzx, dzy), dq = make_double2(dqx, dqy), dc = make_double2(dcx, dcy);
+            const double2 nz = pc_add(pc_add(pc_mul(E[0], dz), pc_mul(E[1], dq)), pc_mul(E[4], dc));
+            const double2 nq = pc_add(pc_add(pc_mul(E[2], dz), pc_mul(E[3], dq)), pc_mul(E[5], dc));
+            nx = nz.x; ny = nz.y; nqx = nq.x; nqy = nq.y;
+            m += 1 << k;
+            u += 1 << k;
+            ++nbla;
+            const double2 Zm = orbit[m], Zp = orbit[m - 1];
+            Zmx = Zm.x; Zmy = Zm.y; Zpx = Zp.x; Zpy = Zp.y;
+        } else {
+            const double tx = ((Zx + Zx) + dzx) + p, ty = (Zy + Zy) + dzy;
+            nx = ((tx * dzx - ty * dzy) + r * dqx) + dcx;
+            ny = ((tx * dzy + ty * dzx) + r * dqy) + dcy;
+            nqx = dzx; nqy = dzy;
+            ++m;
+            ++u;
+            ++nplain;
+            Zmx = Znx; Zmy = Zny; Zpx = Zx; Zpy = Zy;
+        }
+        const double zx = Zmx + nx, zy = Zmy + ny;
+        const double qx = Zpx + nqx, qy = Zpy + nqy;
+        const double r2 = zx * zx + zy * zy;
+        const double n2 = nx * nx + ny * ny, nq2 = nqx * nqx + nqy * nqy;
+        if (r2 > 4.0) {
+            esc = u - 1; ezx = zx; ezy = zy; live = false;       /* the last update the step covered */
+        } else if (r2 + rr * (qx * qx + qy * qy) < n2 + rr * nq2 || m == N) {   /* rebase */
+            dzx = zx; dzy = zy; dqx = qx; dqy = qy; m = 0;
+            Zx = 0.0; Zy = 0.0; Znx = z1.x; Zny = z1.y;
+        } else {
+            dzx = nx; dzy = ny; dqx = nqx; dqy = nqy;
+            v2 = n2 + nq2;
+            Zx = Zmx; Zy = Zmy;
+            if (k > 0) {                                          /* m < N here */
+                const double2 Zn = orbit[m + 1];
+                Znx = Zn.x; Zny = Zn.y;
+            } else {
+                Znx = Znn.x; Zny = Znn.y;
+            }
+        }
+        if (u >= max_iter) live = false;                          /* esc stays max_iter */
+    }
+    if (esc == max_iter) { ezx = Zx + dzx; ezy = Zy + dzy; }     /* lastZ of a sample that never escaped */
+}
+
+/* deep_phoenix_kernel around deep_phoenix_orbit_bla, with the step counts: a kernel of its own, so that the unflagged kernel
+ * stays the instruction stream it was.  Each lane sums its samples' steps and updates; a wave adds its three totals to the
+ * table's counters with one atomic each (updates skipped = updates - plain steps). */
+__global__ void __launch_bounds__(kBlockThreads)
+deep_phoenix_bla_kernel(const DeepPhoenixBlaArgs A)
+{
+    const uint32_t lane = threadIdx.x & (kWave - 1);
+    const int W = A.g.W, H = A.g.H, max_iter = A.max_iter;
+    const int aa = A.aa > 1 ? A.aa : 1;
+    const double resx = (double)W, resy = (double)H;
+    const double2 z1 = A.orbit[1];
+    unsigned long long n_plain = 0ull, n_bla = 0ull, n_upd = 0ull;
+
+    walk_subtiles<3, true>(A.q, A.g, lane, [&](const int px, const int py, const int lrow, const bool inside) {
+        float acc[3] = {0.0f, 0.0f, 0.0f};
+        double nu0 = 0.0;
+        int it0 = 0;
+        const int nsamp = aa * aa;
+        for (int s = 0; s < nsamp; ++s) {
+            const double2 dc = ShipFormula::dc(px, py, s, aa, resx, resy, A.zoom);
+            const double cx = inside ? dc.x : 0.0, cy = inside ? dc.y : 0.0;
+            int esc;
+            double ezx, ezy;
+            uint32_t np, nb;
+            deep_phoenix_orbit_bla(A, A.t, cx, cy, z1, inside, esc, ezx, ezy, np, nb);
+            if (inside) {
+                n_plain += np; n_bla += nb;
+                n_upd += (unsigned long long)(esc < max_iter ? esc + 1 : max_iter);
+            }
+            const PhoenixShade sh = deep_phoenix_shade(esc, ezx, ezy, max_iter, A.stripe_density, A.rgba != nullptr);
+            if (s == 0) { nu0 = sh.smooth; it0 = esc; }
+            if (A.rgba) { acc[0] = acc[0] + sh.r; acc[1] = acc[1] + sh.g; acc[2] = acc[2] + sh.b; }
+        }
+        if (!inside) return;
+        const size_t o = plane_index(A.g, px, py, lrow);
+        if (A.rgba) {
+            const float n = (float)(aa * aa);
+            float rgb[3] = {acc[0] / n, acc[1] / n, acc[2] / n};
+            if (A.flags & FR_FLAG_POST_CHAIN) post_chain(rgb, A.brightness, A.saturation, A.contrast, true);
+            A.rgba[o] = make_float4(rgb[0], rgb[1], rgb[2], 1.0f);
+        }
+        if (A.nu) A.nu[o] = nu0;
+        if (A.iter) A.iter[o] = it0;
+    });
+    unsigned long long v[3] = {n_plain, n_bla, n_upd - n_plain};
+    for (int c = 0; c < 3; ++c) {
+        for (int o = kWave / 2; o > 0; o >>= 1) v[c] += __shfl_xor(v[c], o, kWave);
+        if (lane == 0) atomicAdd(A.t.steps + c, v[c]);
+    }
 }
 
 /* ---- below 1e-290: extended-exponent deltas (fr_render_deepx_phoenix) ---------------------------------------------------------

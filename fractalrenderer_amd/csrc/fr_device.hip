@@ -153,7 +153,8 @@ struct fr_ctx {
      * fr_render_deepx, fr_render_deepx_ship, fr_render_deepx_julia and the sequences, with the tables of FR_FLAG_DEEPX_BLA,
      * FR_FLAG_DEEPX_SHIP_BLA, FR_FLAG_DEEPX_JULIA_BLA.  The six paths share nothing.  A Julia slot holds two orbits: Q in the
      * first half of every array, P in the second.  A seventh slot, deep[0][kPhoenix], is fr_render_deep_phoenix's: plain doubles,
-     * no table; an eighth, deep[1][kPhoenix], is fr_render_deepx_phoenix's: the extended storage, no table either. */
+     * with the table of FR_FLAG_DEEP_PHOENIX_BLA; an eighth, deep[1][kPhoenix], is fr_render_deepx_phoenix's: the extended
+     * storage, no table. */
     DeepSlot deep[2][kFormulas];
 };
 
@@ -833,7 +834,7 @@ static int orbit_slot_prepare(fr_ctx* c, DeepOrbit& o, const BlaSlot* t, hipStre
 
 /* what differs per formula on the host: the orbits a slot holds (a Julia slot: Q, then P) and the double2 per table entry */
 static const struct { int orbits; size_t ab_per_entry; } kFormula[kFormulas] = {
-    {1, MandelFormula::kAbPerEntry}, {1, ShipFormula::kAbPerEntry}, {2, JuliaFormula::kAbPerEntry}, {1, 0 /* Phoenix: no table */}};
+    {1, MandelFormula::kAbPerEntry}, {1, ShipFormula::kAbPerEntry}, {2, JuliaFormula::kAbPerEntry}, {1, kPhoenixMbPerEntry}};
 
 /* a view as the enqueue side reads it: the centre strings, the zoom as a pair (an fp64 view: (zoom, 0)) and the fraction bits of
  * its orbit; zoom: the string of an extended view, which the orbit does not depend on (nullptr: an fp64 view) */
@@ -934,12 +935,21 @@ static size_t bla_entries(int32_t N)             /* sum over k >= 1 of (N - 1) >
 
 struct JuliaTables { int32_t levels_p; uint32_t base_p; };
 
+/* what a table build reads of the render it is for: the orbit's plain doubles, the zoom (an extended view: not read), the whole
+ * frame's size, and Phoenix's p and r widened (the other formulas: not read) */
+struct BlaFrame {
+    const double2* orbit;
+    double zoom;
+    int32_t W, H;
+    double p, r;
+};
+
 /* BLA: the table of the slot's cached orbit -- the extended one with x, the view's extended block -- for this frame's dcmax,
  * built on `stream` unless the slot holds it.  A rebuild overwrites the buffers in place behind the slot's last BLA render (its
  * event: the render may have gone to another stream); growing them frees the old ones, so that waits on the host first.  A
  * Julia slot (jt) holds two tables, Q's entries first and P's behind them, built from the slot's two orbits; no dcmax enters
  * them, so their key is the orbit slot's generation alone and a zoom change rebuilds nothing. */
-static int bla_table_for(fr_ctx* c, DeepSlot& s, int f, const DeepArgs& d, const DeepXOrbit* x, hipStream_t stream, int* levels,
+static int bla_table_for(fr_ctx* c, DeepSlot& s, int f, const BlaFrame& d, const DeepXOrbit* x, hipStream_t stream, int* levels,
                          JuliaTables* jt)
 {
     BlaSlot& t = s.t;
@@ -959,7 +969,7 @@ static int bla_table_for(fr_ctx* c, DeepSlot& s, int f, const DeepArgs& d, const
     double dcv = 0.0;
     int32_t dce = 0;
     if (f != kJulia) {
-        dcv = bla_dcmax(f, x ? x->zm : d.zoom, (double)d.g.W, (double)d.g.H);
+        dcv = bla_dcmax(f, x ? x->zm : d.zoom, (double)d.W, (double)d.H);
         if (x) {                                 /* as an extended real with the zoom pair, normalised: dcv in [0.5, 1) */
             int de = 0;
             dcv = frexp(dcv, &de);
@@ -995,6 +1005,9 @@ static int bla_table_for(fr_ctx* c, DeepSlot& s, int f, const DeepArgs& d, const
         else if (f == kJulia)
             hipLaunchKernelGGL(deep_julia_bla_level_kernel, grid, block, 0, stream, d.orbit + po, N, k, (double*)t.r + eo,
                                t.ab + eo * nab);
+        else if (f == kPhoenix)
+            hipLaunchKernelGGL(phoenix_bla_level_kernel, grid, block, 0, stream, d.orbit, N, k, dcv, d.p, d.r, (double*)t.r,
+                               t.ab);
         else if (x)
             hipLaunchKernelGGL(f == kShip ? deepx_ship_bla_level_kernel : deepx_bla_level_kernel, grid, block, 0, stream, x->mant,
                                x->exp2, N, k, dcv, dce, (XRad*)t.r, t.ab, t.abe);
@@ -1012,7 +1025,7 @@ static int bla_table_for(fr_ctx* c, DeepSlot& s, int f, const DeepArgs& d, const
             const hipError_t e = hipGetLastError();
             if (e != hipSuccess)
                 return fr_set_error(FR_ERR_HIP, "%s%sBLA table launch failed: %s", x ? "extended " : "",
-                                    f == kShip ? "ship " : f == kJulia ? "Julia " : "", hipGetErrorString(e));
+                                    f == kShip ? "ship " : f == kJulia ? "Julia " : f == kPhoenix ? "Phoenix " : "", hipGetErrorString(e));
         }
     ++t.builds;
     t.key_gen = o.gen;
@@ -1024,6 +1037,33 @@ static int bla_table_for(fr_ctx* c, DeepSlot& s, int f, const DeepArgs& d, const
 
 static void bla_table_args(BlaTable& a, const BlaSlot& t) { a.r = (const double*)t.r; a.ab = t.ab; }
 static void bla_table_args(BlaXTable& a, const BlaSlot& t) { a.r = (const XRad*)t.r; a.ab = t.ab; a.abe = t.abe; }
+
+/* Around a flagged kernel's launch.  In front of it: the slot's three counters, allocated on first use and cleared on the stream.
+ * Behind it: their copy to pinned memory, and the slot's event unless the stream is capturing. */
+static int bla_steps_begin(BlaSlot& t, hipStream_t stream, unsigned long long** steps)
+{
+    if (!t.steps_dev) {
+        FR_HIP_TRY(hipMalloc((void**)&t.steps_dev, 3 * sizeof(unsigned long long)));
+        FR_HIP_TRY(hipHostMalloc((void**)&t.steps_host, 3 * sizeof(unsigned long long)));
+    }
+    *steps = t.steps_dev;
+    FR_HIP_TRY(hipMemsetAsync(t.steps_dev, 0, 3 * sizeof(unsigned long long), stream));
+    return FR_OK;
+}
+
+static int bla_steps_end(BlaSlot& t, hipStream_t stream)
+{
+    FR_HIP_TRY(hipMemcpyAsync(t.steps_host, t.steps_dev, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+    t.have_steps = true;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusActive; }
+    t.ev_valid = false;
+    if (cap == hipStreamCaptureStatusNone) {
+        FR_HIP_TRY(hipEventRecord(t.ev, stream));
+        t.ev_valid = true;
+    }
+    return FR_OK;
+}
 
 /* The ten paths, each by the block of its unflagged kernel (the flagged kernel's, with the table: DeepPath::Bla) */
 using DeepMandel = DeepBlock<MandelFormula, false, false>;
@@ -1095,30 +1135,18 @@ static int launch_deep(fr_ctx* c, hipStream_t stream, BASE& base, bool bla)
     BlaSlot& t = s.t;
     int levels = 0;
     JuliaTables jt = {0, 0u};
-    const int ts = bla_table_for(c, s, P::f, a, x, stream, &levels, &jt);
+    const BlaFrame fr = {a.orbit, a.zoom, a.g.W, a.g.H, 0.0, 0.0};
+    const int ts = bla_table_for(c, s, P::f, fr, x, stream, &levels, &jt);
     if (ts != FR_OK) return ts;
     auto& tab = bla_table(a);
     if constexpr (P::f == kJulia) { a.t.levels_p = jt.levels_p; a.t.base_p = jt.base_p; }
     bla_table_args(tab, t);
     tab.levels = levels;
-    if (!t.steps_dev) {
-        FR_HIP_TRY(hipMalloc((void**)&t.steps_dev, 3 * sizeof(unsigned long long)));
-        FR_HIP_TRY(hipHostMalloc((void**)&t.steps_host, 3 * sizeof(unsigned long long)));
-    }
-    tab.steps = t.steps_dev;
-    FR_HIP_TRY(hipMemsetAsync(t.steps_dev, 0, 3 * sizeof(unsigned long long), stream));
+    const int bs = bla_steps_begin(t, stream, &tab.steps);
+    if (bs != FR_OK) return bs;
     const int st = launch_one_pass(c, stream, deep_kernel_name<BLA>(), deep_kernel_of<BLA>(), a, a.g, a.q, s.wg_per_cu[P::de][1], false);
     if (st != FR_OK) return st;
-    FR_HIP_TRY(hipMemcpyAsync(t.steps_host, t.steps_dev, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
-    t.have_steps = true;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(stream, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusActive; }
-    t.ev_valid = false;
-    if (cap == hipStreamCaptureStatusNone) {
-        FR_HIP_TRY(hipEventRecord(t.ev, stream));
-        t.ev_valid = true;
-    }
-    return FR_OK;
+    return bla_steps_end(t, stream);
 }
 
 /* everything of DeepArgs that does not depend on the path: the zoom and the orbit stay with enqueue_deep_view */
@@ -1215,7 +1243,24 @@ static int enqueue_deep_phoenix(fr_ctx* c, const fr_params* p, const fr_phoenix_
     a.flags = p->flags;
     a.g = tile_geom(W, H, rows_local, &norm, out_frame);
     a.rgba = reinterpret_cast<float4*>(rgba); a.nu = (double*)nu; a.iter = iter;
-    return launch_one_pass(c, stream, "deep_phoenix_kernel", deep_phoenix_kernel, a, a.g, a.q, s.wg_per_cu[0][0], false);
+    if (!(p->flags & FR_FLAG_DEEP_PHOENIX_BLA))
+        return launch_one_pass(c, stream, "deep_phoenix_kernel", deep_phoenix_kernel, a, a.g, a.q, s.wg_per_cu[0][0], false);
+    /* the slot's table for this frame's dcmax (the whole frame's W and H), then the flagged kernel between its counters' clearing
+     * and their copy, as launch_deep does it */
+    DeepPhoenixBlaArgs b;
+    memset(&b, 0, sizeof(b));
+    static_cast<DeepPhoenixArgs&>(b) = a;
+    const BlaFrame fr = {a.orbit, a.zoom, a.g.W, a.g.H, a.p, a.r};
+    int levels = 0;
+    const int ts = bla_table_for(c, s, kPhoenix, fr, nullptr, stream, &levels, nullptr);
+    if (ts != FR_OK) return ts;
+    bla_table_args(b.t, s.t);
+    b.t.levels = levels;
+    const int bs = bla_steps_begin(s.t, stream, &b.t.steps);
+    if (bs != FR_OK) return bs;
+    const int st = launch_one_pass(c, stream, "deep_phoenix_bla_kernel", deep_phoenix_bla_kernel, b, b.g, b.q, s.wg_per_cu[0][1], false);
+    if (st != FR_OK) return st;
+    return bla_steps_end(s.t, stream);
 }
 
 /* ... and below 1e-290 (fr_render_deepx_phoenix): the same steps around the extended slot, deep[1][kPhoenix], and
@@ -1995,6 +2040,11 @@ extern "C" int fr_ctx_last_deep_ship_steps(fr_ctx* c, uint64_t out[3])
     return last_bla_steps(c, false, kShip, "fr_render_deep_ship call with FR_FLAG_DEEP_SHIP_BLA", out);
 }
 
+extern "C" int fr_ctx_last_deep_phoenix_steps(fr_ctx* c, uint64_t out[3])
+{
+    return last_bla_steps(c, false, kPhoenix, "fr_render_deep_phoenix call with FR_FLAG_DEEP_PHOENIX_BLA", out);
+}
+
 extern "C" int fr_ctx_last_deepx_steps(fr_ctx* c, uint64_t out[3])
 {
     return last_bla_steps(c, true, kMandel, "fr_render_deepx call with FR_FLAG_DEEPX_BLA", out);
@@ -2013,7 +2063,7 @@ extern "C" int64_t fr_deep_orbit_generation(fr_ctx* c, int extended, int formula
 
 extern "C" int64_t fr_deep_bla_builds(fr_ctx* c, int extended, int formula)
 {
-    if (!c || formula < kMandel || formula > kJulia) return fr_set_error(FR_ERR_INVALID_ARG, "ctx is NULL or no such formula");
+    if (!c || formula < kMandel || formula >= kFormulas) return fr_set_error(FR_ERR_INVALID_ARG, "ctx is NULL or no such formula");
     return (int64_t)deep_slot(c, extended != 0, formula).t.builds;
 }
 
@@ -2045,6 +2095,11 @@ extern "C" int64_t fr_deep_bla_table(fr_ctx* c, double* r, double* ab, int64_t n
 extern "C" int64_t fr_deep_ship_bla_table(fr_ctx* c, double* r, double* ab, int64_t n)
 {
     return read_bla_table(c, false, kShip, r, ab, nullptr, n);
+}
+
+extern "C" int64_t fr_deep_phoenix_bla_table(fr_ctx* c, double* r, double* mb, int64_t n)
+{
+    return read_bla_table(c, false, kPhoenix, r, mb, nullptr, n);
 }
 
 extern "C" int64_t fr_deepx_bla_table(fr_ctx* c, void* r, double* ab, int32_t* ab_exp, int64_t n)

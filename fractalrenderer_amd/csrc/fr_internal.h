@@ -69,12 +69,15 @@ int64_t fr_deepx_bla_table(fr_ctx* ctx, void* r, double* ab, int32_t* ab_exp, in
 /* tests: the ship's BLA table of the context (FR_FLAG_DEEP_SHIP_BLA), as fr_deep_bla_table: r[0 .. n) and ab[0 .. 8n)
  * (a11, a12, a21, a22, b11, b12, b21, b22 per entry), level after level.  Returns the entries it holds, 0 for none. */
 int64_t fr_deep_ship_bla_table(fr_ctx* ctx, double* r, double* ab, int64_t n);
+/* tests: the Phoenix BLA table of the context (FR_FLAG_DEEP_PHOENIX_BLA), as fr_deep_bla_table: r[0 .. n) and mb[0 .. 12n)
+ * (M11, M12, M21, M22, B1, B2 per entry, each as x, y), level after level.  Returns the entries it holds, 0 for none. */
+int64_t fr_deep_phoenix_bla_table(fr_ctx* ctx, double* r, double* mb, int64_t n);
 /* tests: the extended ship BLA table of the context (FR_FLAG_DEEPX_SHIP_BLA), as fr_deepx_bla_table: r receives n entries of 8
  * bytes, ab 8 n doubles (the mantissas a11, a12, a21, a22, b11, b12, b21, b22 per entry), ab_exp 2 n int32 (A.e, B.e);
  * NULL skips a part.  Returns the number of entries the table has (0: none). */
 int64_t fr_deepx_ship_bla_table(fr_ctx* ctx, void* r, double* ab, int32_t* ab_exp, int64_t n);
-/* tests: how often the context has built the BLA table of a path: extended 0 / 1, formula 0 Mandelbrot, 1 Burning Ship, 2 Julia
- * (a cached table serves a render without a build) */
+/* tests: how often the context has built the BLA table of a path: extended 0 / 1, formula 0 Mandelbrot, 1 Burning Ship, 2 Julia,
+ * 3 Phoenix (its fp64 path alone has a table; a cached table serves a render without a build) */
 int64_t fr_deep_bla_builds(fr_ctx* ctx, int extended, int formula);
 /* tests: how often the orbit slot of a path has received another orbit (a render of the view it holds leaves it unchanged):
  * extended 0 / 1, formula as above and 3 Phoenix (fr_render_deep_phoenix, fr_render_deepx_phoenix) */

@@ -148,6 +148,11 @@ class Renderer:
         render_deep_ship(bla=True) on this context, as last_deep_steps()."""
         return self._last_steps("fr_ctx_last_deep_ship_steps")
 
+    def last_deep_phoenix_steps(self) -> DeepSteps:
+        """fr_ctx_last_deep_phoenix_steps: (plain steps, BLA steps, updates skipped) of the most recent
+        render_deep_phoenix(bla=True) on this context, as last_deep_steps()."""
+        return self._last_steps("fr_ctx_last_deep_phoenix_steps")
+
     def last_deepx_ship_steps(self) -> DeepSteps:
         """fr_ctx_last_deepx_ship_steps: (single steps of both modes, BLA steps, updates skipped) of the most recent
         render_deepx_ship(bla=True) or ship-sequence render with bla=True on this context, as last_deep_steps()."""
@@ -373,18 +378,23 @@ class Renderer:
 
     def render_deep_phoenix(self, state: FractalState, width: int, height: int, view: Optional[DeepView] = None,
                             phoenix: Optional[PhoenixParams] = None, *, post_chain: bool = False, rgba=None, nu=None, iter=None,
-                            shard: Optional[Shard] = None, stream: Optional[int] = None, sync: bool = True) -> None:
+                            shard: Optional[Shard] = None, stream: Optional[int] = None, sync: bool = True,
+                            bla: bool = False) -> None:
         """fr_render_deep_phoenix / fr_render_deep_phoenix_async: a Phoenix view deeper than double precision, by perturbation
         around one reference orbit of the second-order recurrence computed on the host.  `view` carries the centre as decimal
         strings; `phoenix` carries phoenix_p and phoenix_r as for render_phoenix() (use_julia_set must stay off: a Julia-mode
         Phoenix frame is one colour).  The zoom, in [1e-290, 1e3], and every other field come from `state` (its double centre
         is not read).  Always fp64: nu is float64.  Planes, shard, stream and sync as for render_deep_ship(); the context keeps
         the Phoenix orbit in a slot of its own.  A view with a zoom string is a ValueError (render_deepx_phoenix() takes
-        those); there is no BLA and no distance estimate on this path."""
+        those); there is no distance estimate on this path.
+        bla=True sets FR_FLAG_DEEP_PHOENIX_BLA: iteration skipping by bilinear approximation on the pair of deltas, with complex
+        2x2 maps (the header's rules; last_deep_phoenix_steps() reports what it skipped)."""
         if view is not None and view.zoom is not None:
             raise ValueError("render_deep_phoenix takes the zoom from the state: render_deepx_phoenix renders views with a zoom "
                              "string")
         p = state.to_params(FractalType.Phoenix, Precision.F64, post_chain)
+        if bla:
+            p.flags |= _capi.FR_FLAG_DEEP_PHOENIX_BLA
         ph = (phoenix or PhoenixParams()).to_c()
         v = (view or DeepView()).to_c()
         rows = shard.rows(height) if shard else height

@@ -81,6 +81,8 @@ typedef enum fr_precision {
                                       there); the other deep entry points answer FR_ERR_UNSUPPORTED */
 #define FR_FLAG_DEEPX_JULIA_BLA 0x40u /* fr_render_deepx_julia and its _async form only: the same for extended Julia views (see
                                       there); the other deep entry points answer FR_ERR_UNSUPPORTED */
+#define FR_FLAG_DEEP_PHOENIX_BLA 0x80u /* fr_render_deep_phoenix and its _async form only: the same for deep Phoenix views (see
+                                      there); fr_deepx_phoenix_validate answers FR_ERR_UNSUPPORTED, nobody else reads it */
 
 /*
  * fr_params -- the hot-path fields of FractalState (src/fractal_state.h:16-91),
@@ -1427,8 +1429,8 @@ int fr_render_deepx_ship_de_async(fr_ctx* ctx, const fr_params* p, const fr_deep
  * reads, as fr_render_phoenix checks them (phoenix_p and phoenix_r finite, use_julia_set 0 or 1, reserved 0); |p|, |r| < 2^32,
  * the range of the orbit's fixed point, as for a centre; use_julia_set must be 0 -- a Julia-mode Phoenix frame starts every
  * pixel from z = 0 with the same c and is one colour (see fr_render_phoenix), so a deep view of it is FR_ERR_UNSUPPORTED; the
- * zoom in [1e-290, 1e3]; every BLA flag (FR_FLAG_DEEP_BLA .. FR_FLAG_DEEPX_JULIA_BLA) is FR_ERR_UNSUPPORTED, Phoenix has no
- * table; then the view as fr_render_deep checks it (reserved, frac_bits, the centre strings).  bailout, color_offset,
+ * zoom in [1e-290, 1e3]; every BLA flag of another path (FR_FLAG_DEEP_BLA .. FR_FLAG_DEEPX_JULIA_BLA) is FR_ERR_UNSUPPORTED,
+ * alone or next to the path's own FR_FLAG_DEEP_PHOENIX_BLA (below), which is accepted; then the view as fr_render_deep checks it (reserved, frac_bits, the centre strings).  bailout, color_offset,
  * interior_style, the orbit trap, stripe_enabled and use_perturbation are ignored as fr_render_phoenix ignores them: the
  * bailout is the shader's fixed 2.  fr_render_deep and the other deep entry points keep rejecting FR_FRACTAL_PHOENIX.
  *
@@ -1469,8 +1471,10 @@ int fr_render_deepx_ship_de_async(fr_ctx* ctx, const fr_params* p, const fr_deep
  * The context keeps the most recent Phoenix orbit on the device in a slot of its own, keyed by the centre strings, F,
  * max_iterations and the bits of p and r: no other deep path evicts it, and it evicts none of theirs.
  *
- * Out of scope: BLA, distance estimates, sequences, fr_node, .franim and Julia mode; below 1e-290: fr_render_deepx_phoenix. */
+ * Out of scope: distance estimates, sequences, fr_node, .franim and Julia mode; below 1e-290: fr_render_deepx_phoenix.
+ * Iteration skipping is FR_FLAG_DEEP_PHOENIX_BLA (below fr_render_deep_phoenix_async, FR_HAS_DEEP_PHOENIX_BLA). */
 #define FR_HAS_DEEP_PHOENIX 1
+#define FR_HAS_DEEP_PHOENIX_BLA 1 /* FR_FLAG_DEEP_PHOENIX_BLA and fr_ctx_last_deep_phoenix_steps (below fr_render_deep_phoenix_async) */
 
 /* What fr_render_deep_phoenix checks of its arguments, the centre strings parsed included (no context needed). */
 int fr_deep_phoenix_validate(const fr_params* p, const fr_phoenix_params* ph, const fr_deep_view* view, uint32_t width,
@@ -1489,6 +1493,62 @@ int fr_render_deep_phoenix(fr_ctx* ctx, const fr_params* p, const fr_phoenix_par
 int fr_render_deep_phoenix_async(fr_ctx* ctx, const fr_params* p, const fr_phoenix_params* ph, const fr_deep_view* view,
                                  uint32_t width, uint32_t height, const fr_shard* shard, const fr_output* out, void* hip_stream);
 
+/* Bilinear approximation for Phoenix, opt-in per call with FR_FLAG_DEEP_PHOENIX_BLA in p->flags.  Only fr_render_deep_phoenix,
+ * fr_render_deep_phoenix_async and fr_deep_phoenix_validate read the flag; without it every byte they write is as above.
+ * fr_deepx_phoenix_validate answers FR_ERR_UNSUPPORTED for it: the extended path has no table.  The recurrence is second order,
+ * so the step less its dz^2 term, dz' = (2 Z_m + p) dz + r dq + dc, dq' = dz, is a linear map of the PAIR (dz, dq): an entry of
+ * the table is a complex 2x2 matrix M, a complex 2-vector B and a radius that bounds the pair.  The dropped term is below one
+ * rounding of (2 Z_m + p) dz while |dz| < 2^-54 |2 Z_m + p|.
+ *
+ * Notation: every operation is one fp64 rounding as written (no contraction); sqrt is correctly rounded; a complex product a*b
+ * is (a.x b.x - a.y b.y, a.x b.y + a.y b.x); sums of complex numbers are componentwise; |c|^2 = c.x c.x + c.y c.y; p and r are
+ * the floats widened to double; Z_m is the cached Phoenix orbit, N its last index; M = (M11, M12, M21, M22), B = (B1, B2).
+ *   - Constants: eps = 2^-53; dcmax is FR_FLAG_DEEP_SHIP_BLA's, operation for operation (Phoenix uses the ship's viewport map),
+ *     from the WHOLE frame's W, H and zoom, never from a shard's rows.
+ *   - Single step at 1 <= m <= N-1 (never stored):
+ *       a = ((Z_m.x + Z_m.x) + p, Z_m.y + Z_m.y);  M = (a, (r, 0), (1, 0), (0, 0));  B = ((1, 0), (0, 0));
+ *       rad = (0.5 * eps) * sqrt(a.x a.x + a.y a.y)
+ *   - Table: the levels K = floor(log2(N-1)), the entry coverage (entry j of level k starts at m = 1 + j 2^k and exists iff
+ *     m + 2^k <= N) and the entry count (N - 1) - popcount(N - 1) of FR_FLAG_DEEP_BLA; no table for N <= 2.  An entry merges x
+ *     (level k-1 at m) and y (level k-1 at m + 2^(k-1)):
+ *       Mij = (y.Mi1 * x.M1j) + (y.Mi2 * x.M2j);   Bi = ((y.Mi1 * x.B1) + (y.Mi2 * x.B2)) + y.Bi;
+ *       |M_x| = sqrt((|M11|^2 + |M12|^2) + (|M21|^2 + |M22|^2)) of x, the Frobenius norm, an upper bound of the operator norm;
+ *       |B_x| = sqrt(|B1|^2 + |B2|^2) of x;
+ *       t = (rad_y - |B_x| * dcmax) / |M_x|,  rad = (t > 0 ? t : 0) (NaN: 0),  rad = (rad < rad_x ? rad : rad_x),
+ *       and rad = 0 if any of the 12 doubles of M, B is not finite.
+ *     The radius bounds the pair: if |dz|^2 + |dq|^2 < rad_x^2 then x is valid, and the pair behind x has norm at most
+ *     |M_x| |(dz, dq)| + |B_x| dcmax, which the rule keeps below rad_y.
+ *   - Stepping: u is the update index and replaces the loop index.  At a trip with m >= 1 take the largest k >= 1 with
+ *     (m-1) mod 2^k == 0, m + 2^k <= N, u + 2^k <= max_iterations and
+ *     (dz.x dz.x + dz.y dz.y) + (dq.x dq.x + dq.y dq.y) < rad*rad; then
+ *       dz' = ((M11*dz) + (M12*dq)) + (B1*dc),  dq' = ((M21*dz) + (M22*dq)) + (B2*dc),
+ *       m += 2^k, u += 2^k, z = Z_m + dz', q = Z_{m-1} + dq', r2 = z.x z.x + z.y z.y;
+ *     r2 > 4: escaped at u - 1 with lastZ = z; else the plain step's pair rebase rule on (r2, q, dz', dq'), or m == N: rebase;
+ *     else dz = dz', dq = dq'.  If no k qualifies, or m == 0, the plain step above, operation for operation: it escapes at u
+ *     and then u += 1.  The planes follow from (escape index, lastZ) exactly as without the flag.  Radii are monotone in k, and
+ *     no level's exceeds (0.5 eps) |2 Z_m + p|.
+ * Escapes between the first and the last update of a BLA step are not looked for.
+ *
+ * What it skips (the numpy restatement tests/deep_phoenix_bla_ref.py, 48 x 36, aa 1, the views of tests/deep_phoenix_ref.py):
+ * 37.2 % of the updates at 1e-30 with N = 244 (PA30), 43.1 % with N = 391 (PB30); 79.5 % at 1e-100 with N = 758 (PA), 76.5 % with
+ * N = 1330 (PB); iter equal to the unflagged path's, and to the exact fixed-point iteration's at 24 x 18, on every pixel of the
+ * four.  Shallow views (|dc| far above every radius) take no BLA step.  Measured on one MI355X at 4096^2, aa 1
+ * (profiles/deep_phoenix_bla_time.txt, flagged and unflagged interleaved in one session): 7.87 ms against 23.38 ms on PA (2.97x),
+ * 15.50 ms against 40.51 ms on PB (2.61x), 8.30 ms against 8.33 ms on PA30 (1.00x: 1.56x fewer loop trips, each costing 1.56
+ * plain ones -- the level probe, the 96-byte gather, 4 waves per SIMD for 5), and 2.77 ms against 1.81 ms on the shallow view
+ * (0.65x), where the flag can only cost time; iter equal to the unflagged render's on every pixel of all four.
+ *
+ * Cost: 104 bytes per entry (rad 8, M 64, B 32), on the device, per context, in buffers of the Phoenix path's own, grown like
+ * the orbit buffer and keyed by the Phoenix orbit (whose key holds p and r) and the bits of dcmax: a zoom change at a fixed
+ * centre rebuilds the table (K small launches on the render's stream, no host work), a new view computes its orbit first.  A
+ * rebuild, and the upload of a new Phoenix orbit, are ordered behind the context's previous render with the flag, whatever
+ * stream it went to.  The other paths' orbits, tables and counts are untouched by Phoenix renders, and the reverse. */
+
+/* fr_ctx_last_deep_ship_steps' contract for the context's most recent fr_render_deep_phoenix / fr_render_deep_phoenix_async call
+ * made with FR_FLAG_DEEP_PHOENIX_BLA: out[0] plain steps, out[1] BLA steps, out[2] updates skipped.  FR_ERR_UNSUPPORTED if there
+ * is no such call. */
+int fr_ctx_last_deep_phoenix_steps(fr_ctx* ctx, uint64_t out[3]);
+
 /* ---- Phoenix views below 1e-290: extended-exponent deltas ------------------------------------------------------------------
  * fr_render_deep_phoenix stops at 1e-290, where a double can no longer hold the zoom, dc or its two deltas.  These entry points
  * take fr_render_deep_phoenix's arguments with a fr_deepx_view -- centre AND zoom as decimal strings, 1e-1000 <= zoom <= 1e3 as for
@@ -1497,7 +1557,8 @@ int fr_render_deep_phoenix_async(fr_ctx* ctx, const fr_params* p, const fr_phoen
  *
  * Validation (fr_deepx_phoenix_validate): fr_deep_phoenix_validate's rules in its order -- NULL arguments; FR_FRACTAL_PHOENIX and
  * FR_PRECISION_F64, otherwise FR_ERR_UNSUPPORTED; the frame size and the fields Phoenix reads; |p|, |r| < 2^32; use_julia_set is
- * FR_ERR_UNSUPPORTED for the reason given there; every BLA flag is FR_ERR_UNSUPPORTED -- then the view as fr_deepx_validate
+ * FR_ERR_UNSUPPORTED for the reason given there; every BLA flag, FR_FLAG_DEEP_PHOENIX_BLA included, is FR_ERR_UNSUPPORTED (the
+ * extended path has no table) -- then the view as fr_deepx_validate
  * checks its own: reserved, frac_bits, the centre strings, the zoom string and its range (FR_ERR_INVALID_ARG).
  *
  * Reference orbit (fr_deepx_phoenix_reference_orbit): fr_deep_phoenix_reference_orbit's recurrence at F = frac_bits or
@@ -1539,7 +1600,8 @@ int fr_render_deep_phoenix_async(fr_ctx* ctx, const fr_params* p, const fr_phoen
  * The context keeps the most recent extended Phoenix orbit in a slot of its own, keyed by the centre strings, F,
  * max_iterations and the bits of p and r: it evicts no other slot and none evicts it.
  *
- * Out of scope: BLA, distance estimates, sequences, fr_node, .franim and Julia mode. */
+ * Out of scope: BLA for extended Phoenix views (FR_FLAG_DEEP_PHOENIX_BLA is fr_render_deep_phoenix's alone), distance
+ * estimates, sequences, fr_node, .franim and Julia mode. */
 #define FR_HAS_DEEPX_PHOENIX 1
 
 /* What fr_render_deepx_phoenix checks of its arguments, the view's strings parsed included (no context needed). */

@@ -44,6 +44,7 @@ FR_FLAG_DEEPX_SHIP_BLA = 0x10
 FR_FLAG_DEEP_JULIA_BLA = 0x20
 FR_FLAG_DEEPX_JULIA_BLA = 0x40
 FR_FLAG_DEEP_PHOENIX_BLA = 0x80
+FR_FLAG_DEEPX_PHOENIX_BLA = 0x100
 
 
 class fr_params(C.Structure):
@@ -185,6 +186,7 @@ SIGNATURES = {
     "fr_ctx_last_deep_ship_steps": (C.c_int, [C.c_void_p, _P(C.c_uint64)]),
     "fr_ctx_last_deep_phoenix_steps": (C.c_int, [C.c_void_p, _P(C.c_uint64)]),
     "fr_ctx_last_deepx_ship_steps": (C.c_int, [C.c_void_p, _P(C.c_uint64)]),
+    "fr_ctx_last_deepx_phoenix_steps": (C.c_int, [C.c_void_p, _P(C.c_uint64)]),
     "fr_ctx_last_deep_julia_steps": (C.c_int, [C.c_void_p, _P(C.c_uint64)]),
     "fr_ctx_last_deepx_julia_steps": (C.c_int, [C.c_void_p, _P(C.c_uint64)]),
     "fr_deep_julia_bla_table": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
@@ -340,6 +342,7 @@ INTERNAL_SIGNATURES = {
     "fr_deepx_ship_bla_table": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),   # fr_internal.h: tests
     "fr_deep_ship_bla_table": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),   # fr_internal.h: tests
     "fr_deep_phoenix_bla_table": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),   # fr_internal.h: tests
+    "fr_deepx_phoenix_bla_table": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),   # fr_internal.h: tests
     "fr_deep_bla_builds": (C.c_int64, [C.c_void_p, C.c_int, C.c_int]),                        # fr_internal.h: tests
     "fr_deep_orbit_generation": (C.c_int64, [C.c_void_p, C.c_int, C.c_int]),                  # fr_internal.h: tests
     "fr_deepx_validate": (C.c_int, [_P(fr_params), _P(fr_deepx_view), C.c_uint32, C.c_uint32]),        # fr_internal.h: tests

@@ -677,6 +677,8 @@ typedef struct {
 #define OTHER_FLAGS (FR_FLAG_DEEP_BLA | FR_FLAG_DEEPX_BLA | FR_FLAG_DEEP_SHIP_BLA | FR_FLAG_DEEPX_SHIP_BLA)
 #define OTHER_FLAGS_MSG "the BLA flags are not available (their tables belong to the Mandelbrot and Burning Ship paths)"
 
+#define XPHOENIX_FLAG_MSG "FR_FLAG_DEEPX_PHOENIX_BLA is not available (its BLA table belongs to fr_render_deepx_phoenix)"
+
 enum { kDeep, kDeepX, kDeepShip, kDeepXShip, kDeepJulia, kDeepXJulia };
 
 static const deep_rules kRules[6] = {
@@ -730,6 +732,7 @@ static int validate_params(const deep_rules* k, const fr_params* p, uint32_t wid
                             "whole orbit and are not available", k->who);
     for (int i = 0; i < 2; ++i)
         if (p->flags & k->foreign[i].mask) return fr_set_error(FR_ERR_UNSUPPORTED, "%s: %s", k->who, k->foreign[i].msg);
+    if (p->flags & FR_FLAG_DEEPX_PHOENIX_BLA) return fr_set_error(FR_ERR_UNSUPPORTED, "%s: %s", k->who, XPHOENIX_FLAG_MSG);
     return FR_OK;
 }
 
@@ -1040,6 +1043,9 @@ int fr_deep_phoenix_validate(const fr_params* p, const fr_phoenix_params* ph, co
         return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deep_phoenix: the BLA flags of the other paths are not available (their "
                             "tables belong to the Mandelbrot, Burning Ship and Julia paths): the flag of this entry point is "
                             "FR_FLAG_DEEP_PHOENIX_BLA");
+    if (p->flags & FR_FLAG_DEEPX_PHOENIX_BLA)
+        return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deep_phoenix: FR_FLAG_DEEPX_PHOENIX_BLA is not available (its BLA table is "
+                            "extended, fr_render_deepx_phoenix's): the flag of this entry point is FR_FLAG_DEEP_PHOENIX_BLA");
     deep_resolved r;
     return resolve_view(v, NULL, p->zoom, 1, &r);
 }
@@ -1080,11 +1086,12 @@ int fr_deepx_phoenix_validate(const fr_params* p, const fr_phoenix_params* ph, c
         return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deepx_phoenix: use_julia_set is not available (a Julia-mode Phoenix frame "
                             "starts every pixel from z = 0 with the same c, so it is one colour at any depth)");
     if (p->flags & (OTHER_FLAGS | JULIA_FLAGS))
-        return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deepx_phoenix: the BLA flags are not available (their tables belong to the "
-                            "Mandelbrot, Burning Ship and Julia paths; extended Phoenix views have none)");
+        return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deepx_phoenix: the BLA flags of the other paths are not available (their "
+                            "tables belong to the Mandelbrot, Burning Ship and Julia paths): the flag of this entry point is "
+                            "FR_FLAG_DEEPX_PHOENIX_BLA");
     if (p->flags & FR_FLAG_DEEP_PHOENIX_BLA)
         return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deepx_phoenix: FR_FLAG_DEEP_PHOENIX_BLA is not available (its BLA table is "
-                            "fp64, fr_render_deep_phoenix's; extended Phoenix views have none)");
+                            "fp64, fr_render_deep_phoenix's): the flag of this entry point is FR_FLAG_DEEPX_PHOENIX_BLA");
     deep_resolved r;
     return resolve_view(NULL, v, 0.0, 1, &r);
 }

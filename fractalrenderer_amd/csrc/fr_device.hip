@@ -154,7 +154,7 @@ struct fr_ctx {
      * FR_FLAG_DEEPX_SHIP_BLA, FR_FLAG_DEEPX_JULIA_BLA.  The six paths share nothing.  A Julia slot holds two orbits: Q in the
      * first half of every array, P in the second.  A seventh slot, deep[0][kPhoenix], is fr_render_deep_phoenix's: plain doubles,
      * with the table of FR_FLAG_DEEP_PHOENIX_BLA; an eighth, deep[1][kPhoenix], is fr_render_deepx_phoenix's: the extended
-     * storage, no table. */
+     * storage, with the table of FR_FLAG_DEEPX_PHOENIX_BLA. */
     DeepSlot deep[2][kFormulas];
 };
 
@@ -1005,6 +1005,9 @@ static int bla_table_for(fr_ctx* c, DeepSlot& s, int f, const BlaFrame& d, const
         else if (f == kJulia)
             hipLaunchKernelGGL(deep_julia_bla_level_kernel, grid, block, 0, stream, d.orbit + po, N, k, (double*)t.r + eo,
                                t.ab + eo * nab);
+        else if (f == kPhoenix && x)
+            hipLaunchKernelGGL(phoenix_x_bla_level_kernel, grid, block, 0, stream, x->mant, x->exp2, N, k, dcv, dce, d.p, d.r,
+                               (XRad*)t.r, t.ab, t.abe);
         else if (f == kPhoenix)
             hipLaunchKernelGGL(phoenix_bla_level_kernel, grid, block, 0, stream, d.orbit, N, k, dcv, d.p, d.r, (double*)t.r,
                                t.ab);
@@ -1293,7 +1296,26 @@ static int enqueue_deepx_phoenix(fr_ctx* c, const fr_params* p, const fr_phoenix
     a.flags = p->flags;
     a.g = tile_geom(W, H, rows_local, &norm, out_frame);
     a.rgba = reinterpret_cast<float4*>(rgba); a.nu = (double*)nu; a.iter = iter;
-    return launch_one_pass(c, stream, "deep_phoenix_x_kernel", deep_phoenix_x_kernel, a, a.g, a.q, s.wg_per_cu[0][0], false);
+    if (!(p->flags & FR_FLAG_DEEPX_PHOENIX_BLA))
+        return launch_one_pass(c, stream, "deep_phoenix_x_kernel", deep_phoenix_x_kernel, a, a.g, a.q, s.wg_per_cu[0][0], false);
+    /* as enqueue_deep_phoenix: the slot's extended table for this frame's dcmax (the whole frame's W and H, the zoom pair), then
+     * the flagged kernel between its counters' clearing and their copy */
+    DeepPhoenixXBlaArgs b;
+    memset(&b, 0, sizeof(b));
+    static_cast<DeepPhoenixXArgs&>(b) = a;
+    DeepXOrbit x;
+    x.mant = a.mant; x.exp2 = a.exp2; x.zm = a.zm; x.ze = a.ze;
+    const BlaFrame fr = {a.orbit, 0.0, a.g.W, a.g.H, a.p, a.r};
+    int levels = 0;
+    const int ts = bla_table_for(c, s, kPhoenix, fr, &x, stream, &levels, nullptr);
+    if (ts != FR_OK) return ts;
+    bla_table_args(b.t, s.t);
+    b.t.levels = levels;
+    const int bs = bla_steps_begin(s.t, stream, &b.t.steps);
+    if (bs != FR_OK) return bs;
+    const int st = launch_one_pass(c, stream, "deep_phoenix_x_bla_kernel", deep_phoenix_x_bla_kernel, b, b.g, b.q, s.wg_per_cu[0][1], false);
+    if (st != FR_OK) return st;
+    return bla_steps_end(s.t, stream);
 }
 
 /* ---- deep zoom sequences (fr_deep_sequence; the rules are in the header, the host planning in fr_deepseq.c) ---------------
@@ -2045,6 +2067,11 @@ extern "C" int fr_ctx_last_deep_phoenix_steps(fr_ctx* c, uint64_t out[3])
     return last_bla_steps(c, false, kPhoenix, "fr_render_deep_phoenix call with FR_FLAG_DEEP_PHOENIX_BLA", out);
 }
 
+extern "C" int fr_ctx_last_deepx_phoenix_steps(fr_ctx* c, uint64_t out[3])
+{
+    return last_bla_steps(c, true, kPhoenix, "fr_render_deepx_phoenix call with FR_FLAG_DEEPX_PHOENIX_BLA", out);
+}
+
 extern "C" int fr_ctx_last_deepx_steps(fr_ctx* c, uint64_t out[3])
 {
     return last_bla_steps(c, true, kMandel, "fr_render_deepx call with FR_FLAG_DEEPX_BLA", out);
@@ -2100,6 +2127,11 @@ extern "C" int64_t fr_deep_ship_bla_table(fr_ctx* c, double* r, double* ab, int6
 extern "C" int64_t fr_deep_phoenix_bla_table(fr_ctx* c, double* r, double* mb, int64_t n)
 {
     return read_bla_table(c, false, kPhoenix, r, mb, nullptr, n);
+}
+
+extern "C" int64_t fr_deepx_phoenix_bla_table(fr_ctx* c, void* r, double* mb, int32_t* mb_exp, int64_t n)
+{
+    return read_bla_table(c, true, kPhoenix, r, mb, mb_exp, n);
 }
 
 extern "C" int64_t fr_deepx_bla_table(fr_ctx* c, void* r, double* ab, int32_t* ab_exp, int64_t n)

@@ -76,8 +76,13 @@ int64_t fr_deep_phoenix_bla_table(fr_ctx* ctx, double* r, double* mb, int64_t n)
  * bytes, ab 8 n doubles (the mantissas a11, a12, a21, a22, b11, b12, b21, b22 per entry), ab_exp 2 n int32 (A.e, B.e);
  * NULL skips a part.  Returns the number of entries the table has (0: none). */
 int64_t fr_deepx_ship_bla_table(fr_ctx* ctx, void* r, double* ab, int32_t* ab_exp, int64_t n);
+/* tests: the extended Phoenix BLA table of the context (FR_FLAG_DEEPX_PHOENIX_BLA), as fr_deepx_ship_bla_table: r receives n
+ * entries of 8 bytes, mb 12 n doubles (the mantissas of M11, M12, M21, M22, B1, B2 per entry, each as x, y), mb_exp 2 n int32
+ * (M.e, B.e); NULL skips a part.  Returns the number of entries the table has (0: none). */
+int64_t fr_deepx_phoenix_bla_table(fr_ctx* ctx, void* r, double* mb, int32_t* mb_exp, int64_t n);
 /* tests: how often the context has built the BLA table of a path: extended 0 / 1, formula 0 Mandelbrot, 1 Burning Ship, 2 Julia,
- * 3 Phoenix (its fp64 path alone has a table; a cached table serves a render without a build) */
+ * 3 Phoenix (fp64: FR_FLAG_DEEP_PHOENIX_BLA's table, extended: FR_FLAG_DEEPX_PHOENIX_BLA's; a cached table serves a render
+ * without a build) */
 int64_t fr_deep_bla_builds(fr_ctx* ctx, int extended, int formula);
 /* tests: how often the orbit slot of a path has received another orbit (a render of the view it holds leaves it unchanged):
  * extended 0 / 1, formula as above and 3 Phoenix (fr_render_deep_phoenix, fr_render_deepx_phoenix) */

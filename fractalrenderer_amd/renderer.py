@@ -153,6 +153,11 @@ class Renderer:
         render_deep_phoenix(bla=True) on this context, as last_deep_steps()."""
         return self._last_steps("fr_ctx_last_deep_phoenix_steps")
 
+    def last_deepx_phoenix_steps(self) -> DeepSteps:
+        """fr_ctx_last_deepx_phoenix_steps: (single steps of both modes, BLA steps, updates skipped) of the most recent
+        render_deepx_phoenix(xbla=True) on this context, as last_deep_steps()."""
+        return self._last_steps("fr_ctx_last_deepx_phoenix_steps")
+
     def last_deepx_ship_steps(self) -> DeepSteps:
         """fr_ctx_last_deepx_ship_steps: (single steps of both modes, BLA steps, updates skipped) of the most recent
         render_deepx_ship(bla=True) or ship-sequence render with bla=True on this context, as last_deep_steps()."""
@@ -404,16 +409,21 @@ class Renderer:
 
     def render_deepx_phoenix(self, state: FractalState, width: int, height: int, view: DeepView,
                              phoenix: Optional[PhoenixParams] = None, *, post_chain: bool = False, rgba=None, nu=None, iter=None,
-                             shard: Optional[Shard] = None, stream: Optional[int] = None, sync: bool = True) -> None:
+                             shard: Optional[Shard] = None, stream: Optional[int] = None, sync: bool = True,
+                             xbla: bool = False) -> None:
         """fr_render_deepx_phoenix / fr_render_deepx_phoenix_async: a Phoenix view with extended-exponent deltas, zooms down to
         1e-1000.  `view` carries the centre and the zoom as decimal strings (DeepView(..., zoom="1e-400")); a view without a
         zoom string is a ValueError (render_deep_phoenix() takes those).  state.zoom and its double centre are not read;
         `phoenix` and every other argument as for render_deep_phoenix().  The context keeps this path's orbit in a slot of its
-        own."""
+        own.  xbla=True sets FR_FLAG_DEEPX_PHOENIX_BLA (the keyword of render_deep()'s extended flag): iteration skipping on the
+        pair of deltas with complex 2x2 maps in extended arithmetic (the header's rules; last_deepx_phoenix_steps() reports what
+        it skipped)."""
         if view is None or view.zoom is None:
             raise ValueError("render_deepx_phoenix needs a view with a zoom string (DeepView(..., zoom=\"1e-400\")); "
                              "render_deep_phoenix renders views without one")
         p = state.to_params(FractalType.Phoenix, Precision.F64, post_chain)
+        if xbla:
+            p.flags |= _capi.FR_FLAG_DEEPX_PHOENIX_BLA
         ph = (phoenix or PhoenixParams()).to_c()
         vx = view.to_cx()
         rows = shard.rows(height) if shard else height

@@ -83,6 +83,8 @@ typedef enum fr_precision {
                                       there); the other deep entry points answer FR_ERR_UNSUPPORTED */
 #define FR_FLAG_DEEP_PHOENIX_BLA 0x80u /* fr_render_deep_phoenix and its _async form only: the same for deep Phoenix views (see
                                       there); fr_deepx_phoenix_validate answers FR_ERR_UNSUPPORTED, nobody else reads it */
+#define FR_FLAG_DEEPX_PHOENIX_BLA 0x100u /* fr_render_deepx_phoenix and its _async form only: the same for Phoenix views below
+                                      1e-290 (see there); every other deep validator answers FR_ERR_UNSUPPORTED */
 
 /*
  * fr_params -- the hot-path fields of FractalState (src/fractal_state.h:16-91),
@@ -1430,7 +1432,7 @@ int fr_render_deepx_ship_de_async(fr_ctx* ctx, const fr_params* p, const fr_deep
  * the range of the orbit's fixed point, as for a centre; use_julia_set must be 0 -- a Julia-mode Phoenix frame starts every
  * pixel from z = 0 with the same c and is one colour (see fr_render_phoenix), so a deep view of it is FR_ERR_UNSUPPORTED; the
  * zoom in [1e-290, 1e3]; every BLA flag of another path (FR_FLAG_DEEP_BLA .. FR_FLAG_DEEPX_JULIA_BLA) is FR_ERR_UNSUPPORTED,
- * alone or next to the path's own FR_FLAG_DEEP_PHOENIX_BLA (below), which is accepted; then the view as fr_render_deep checks it (reserved, frac_bits, the centre strings).  bailout, color_offset,
+ * and so is FR_FLAG_DEEPX_PHOENIX_BLA, alone or next to the path's own FR_FLAG_DEEP_PHOENIX_BLA (below), which is accepted; then the view as fr_render_deep checks it (reserved, frac_bits, the centre strings).  bailout, color_offset,
  * interior_style, the orbit trap, stripe_enabled and use_perturbation are ignored as fr_render_phoenix ignores them: the
  * bailout is the shader's fixed 2.  fr_render_deep and the other deep entry points keep rejecting FR_FRACTAL_PHOENIX.
  *
@@ -1495,7 +1497,8 @@ int fr_render_deep_phoenix_async(fr_ctx* ctx, const fr_params* p, const fr_phoen
 
 /* Bilinear approximation for Phoenix, opt-in per call with FR_FLAG_DEEP_PHOENIX_BLA in p->flags.  Only fr_render_deep_phoenix,
  * fr_render_deep_phoenix_async and fr_deep_phoenix_validate read the flag; without it every byte they write is as above.
- * fr_deepx_phoenix_validate answers FR_ERR_UNSUPPORTED for it: the extended path has no table.  The recurrence is second order,
+ * fr_deepx_phoenix_validate answers FR_ERR_UNSUPPORTED for it: the extended path's table is FR_FLAG_DEEPX_PHOENIX_BLA's, in
+ * another arithmetic (below fr_render_deepx_phoenix_async).  The recurrence is second order,
  * so the step less its dz^2 term, dz' = (2 Z_m + p) dz + r dq + dc, dq' = dz, is a linear map of the PAIR (dz, dq): an entry of
  * the table is a complex 2x2 matrix M, a complex 2-vector B and a radius that bounds the pair.  The dropped term is below one
  * rounding of (2 Z_m + p) dz while |dz| < 2^-54 |2 Z_m + p|.
@@ -1557,8 +1560,9 @@ int fr_ctx_last_deep_phoenix_steps(fr_ctx* ctx, uint64_t out[3]);
  *
  * Validation (fr_deepx_phoenix_validate): fr_deep_phoenix_validate's rules in its order -- NULL arguments; FR_FRACTAL_PHOENIX and
  * FR_PRECISION_F64, otherwise FR_ERR_UNSUPPORTED; the frame size and the fields Phoenix reads; |p|, |r| < 2^32; use_julia_set is
- * FR_ERR_UNSUPPORTED for the reason given there; every BLA flag, FR_FLAG_DEEP_PHOENIX_BLA included, is FR_ERR_UNSUPPORTED (the
- * extended path has no table) -- then the view as fr_deepx_validate
+ * FR_ERR_UNSUPPORTED for the reason given there; every BLA flag of another path, FR_FLAG_DEEP_PHOENIX_BLA included, is
+ * FR_ERR_UNSUPPORTED, alone or next to the path's own FR_FLAG_DEEPX_PHOENIX_BLA (below), which is accepted -- then the view as
+ * fr_deepx_validate
  * checks its own: reserved, frac_bits, the centre strings, the zoom string and its range (FR_ERR_INVALID_ARG).
  *
  * Reference orbit (fr_deepx_phoenix_reference_orbit): fr_deep_phoenix_reference_orbit's recurrence at F = frac_bits or
@@ -1600,9 +1604,10 @@ int fr_ctx_last_deep_phoenix_steps(fr_ctx* ctx, uint64_t out[3]);
  * The context keeps the most recent extended Phoenix orbit in a slot of its own, keyed by the centre strings, F,
  * max_iterations and the bits of p and r: it evicts no other slot and none evicts it.
  *
- * Out of scope: BLA for extended Phoenix views (FR_FLAG_DEEP_PHOENIX_BLA is fr_render_deep_phoenix's alone), distance
- * estimates, sequences, fr_node, .franim and Julia mode. */
+ * Out of scope: distance estimates, sequences, fr_node, .franim and Julia mode.  Iteration skipping is
+ * FR_FLAG_DEEPX_PHOENIX_BLA (below fr_render_deepx_phoenix_async, FR_HAS_DEEPX_PHOENIX_BLA). */
 #define FR_HAS_DEEPX_PHOENIX 1
+#define FR_HAS_DEEPX_PHOENIX_BLA 1 /* FR_FLAG_DEEPX_PHOENIX_BLA and fr_ctx_last_deepx_phoenix_steps (below fr_render_deepx_phoenix_async) */
 
 /* What fr_render_deepx_phoenix checks of its arguments, the view's strings parsed included (no context needed). */
 int fr_deepx_phoenix_validate(const fr_params* p, const fr_phoenix_params* ph, const fr_deepx_view* view, uint32_t width,
@@ -1620,6 +1625,92 @@ int fr_render_deepx_phoenix(fr_ctx* ctx, const fr_params* p, const fr_phoenix_pa
 /* fr_render_deep_async's contract: a render of a new view computes its orbit on the host first and is never launch-only */
 int fr_render_deepx_phoenix_async(fr_ctx* ctx, const fr_params* p, const fr_phoenix_params* ph, const fr_deepx_view* view,
                                   uint32_t width, uint32_t height, const fr_shard* shard, const fr_output* out, void* hip_stream);
+
+/* Bilinear approximation for Phoenix views below 1e-290, opt-in per call with FR_FLAG_DEEPX_PHOENIX_BLA in p->flags.  Only
+ * fr_render_deepx_phoenix, its _async form and fr_deepx_phoenix_validate read the flag; without it every byte they write is as
+ * above, from the same orbit slot and the same kernel.  Every other deep validator answers FR_ERR_UNSUPPORTED for it.  It is
+ * FR_FLAG_DEEP_PHOENIX_BLA's scheme -- complex 2x2 maps M and 2-vectors B of the PAIR (dz, dq), a radius on the pair -- with the
+ * table and the BLA step carried in FR_FLAG_DEEPX_BLA's extended arithmetic, taken by samples in either mode.
+ *
+ * Notation: FR_FLAG_DEEP_PHOENIX_BLA's (complex products a*b, componentwise sums, |c|^2, M = (M11, M12, M21, M22), B = (B1, B2),
+ * one fp64 rounding per operation as written, sqrt correctly rounded) and FR_FLAG_DEEPX_BLA's: ldexp, FR_DEEPX_ZERO_EXP, the -400
+ * mode rule, normalised extended reals (v, e) with v in [0.5, 1), and for mantissas sharing an exponent e
+ *   norm(c_1, .., c_n, e) = (ldexp(c_i, -k), e + k), k the frexp exponent of the largest |component| of all the c_i;
+ *                           e = FR_DEEPX_ZERO_EXP when all are zero.
+ * (P, eP) (+) (Q, eQ) = (ldexp(P, eP - e) + ldexp(Q, eQ - e), e) per component at e = max(eP, eQ), one addition per component.
+ * M is its four complex mantissas (8 doubles) with one int32 exponent M.e, B its two (4 doubles) with B.e, both normalised.
+ *   - Constants: eps = 2^-53.  dcmax is FR_FLAG_DEEPX_SHIP_BLA's extended real (dcv, dce), operation for operation (Phoenix uses
+ *     the ship's viewport map), from the WHOLE frame's W, H and zoom pair, never from a shard's rows.
+ *   - Single step at 1 <= m <= N-1 (never stored), from the extended storage Z_m = (X, Y, eZ); pe = 0, or FR_DEEPX_ZERO_EXP
+ *     when p == 0, as in the extended step:
+ *       ea = max(eZ + 1, pe);   a = (ldexp(X, eZ + 1 - ea) + ldexp(p, pe - ea),  ldexp(Y, eZ + 1 - ea))    (the doubling goes
+ *                               to the exponent)
+ *       em = max(ea, 0);        M = norm(ldexp(a, ea - em), (ldexp(r, -em), 0), (ldexp(1, -em), 0), (0, 0), em)
+ *       B = norm((1, 0), (0, 0), 0) = ((0.5, 0), (0, 0)) with B.e = 1
+ *       n = norm(a, ea);  rad = (sqrt(n.x n.x + n.y n.y), n.e) normalised, then rad.e -= 54 unless rad is zero: (0.5 eps) |a|
+ *       with the factor in the exponent.  Neither a nor rad is formed from the slot's plain doubles: an orbit point below 2^-1074
+ *       is 0 there, and 2^-54 |a| underflows a double for |a| < 2^-968.
+ *   - Table: levels, entry coverage, the existence rule and the entry count (N - 1) - popcount(N - 1) of FR_FLAG_DEEP_BLA; no
+ *     table for N <= 2.  Merging x then y, products on mantissas in FR_FLAG_DEEP_PHOENIX_BLA's element order:
+ *       M = norm(Mij = (y.Mi1 * x.M1j) + (y.Mi2 * x.M2j), y.M.e + x.M.e)
+ *       Qi = (y.Mi1 * x.B1) + (y.Mi2 * x.B2) at e1 = y.M.e + x.B.e;   eB = max(e1, y.B.e);
+ *       B = norm(Bi = ldexp(Qi, e1 - eB) + ldexp(y.Bi, y.B.e - eB) per component, eB)
+ *       |M_x| = (sqrt((|M11|^2 + |M12|^2) + (|M21|^2 + |M22|^2)) of x's mantissas, x.M.e) normalised (the Frobenius norm);
+ *       |B_x| = (sqrt(|B1|^2 + |B2|^2) of x's mantissas, x.B.e) normalised;
+ *       t = (rad_y (-) |B_x| dcmax) (/) |M_x|, the > 0 and finite rule, rad = rad_x unless rad < rad_x, the void rule (an M.e
+ *       or B.e outside [-2^27, 2^27] zeroes the whole entry) and the 24-bit cut of the STORED radius, all exactly as
+ *       FR_FLAG_DEEPX_BLA writes them for (A, B) -- with ONE addition, which that flag's formulas never meet: M may be the zero
+ *       matrix.  At r = 0 the single step is M = (a, 0, 1, 0), and an a more than 2^1074 below the 1 of M21 (an orbit that
+ *       returns below 2^-1075) has no mantissa left under the shared exponent, so the merge behind it is all zero: the map
+ *       dz' = B1 dc, dq' = B2 dc, off by less than 2^-1074 |dz|.  The zero matrix (M.e = FR_DEEPX_ZERO_EXP) is NOT void, and
+ *       where |M_x| is zero and rad_y (-) |B_x| dcmax > 0 (t would be +inf) rad = rad_x.  Without this a period-201 nucleus at
+ *       1e-1000 takes 40 176 loop trips for a 24 x 18 frame instead of 3 456.
+ *     An entry is 112 bytes: radius 8 (a float and an int32), mantissas 96, exponents 8.
+ *   - Stepping: u replaces the loop index.  At m >= 1, in either mode, the sample's pair as two normalised extended numbers
+ *     dz = (a, b, ed), dq = (c, d, eq) -- a PLAIN sample forms norm(dz, 0) and norm(dq, 0) -- is probed on
+ *       ev = max(ed, eq);   v2 = (A A + B B) + (C C + D D),  A = ldexp(a, ed - ev), B = ldexp(b, ed - ev), C = ldexp(c, eq - ev),
+ *       D = ldexp(d, eq - ev);   the probe passes if v2 < ldexp(rad.v rad.v, 2 (rad.e - ev)).
+ *     Take the largest k >= 1 with (m-1) mod 2^k == 0, m + 2^k <= N, u + 2^k <= max_iterations and a passing probe.  The step
+ *     is always extended, on the extended dc = (dc, ec).  A term is a product of mantissas at the sum of the exponents; a term
+ *     that is exactly zero has FR_DEEPX_ZERO_EXP and raises no common exponent (M12 = M22 = 0 at r = 0, next to a dq that may
+ *     lie 2^1300 above dz):
+ *       dz' = ((M11*dz, M.e + ed) (+) (M12*dq, M.e + eq)) (+) (B1*dc, B.e + ec)    at en
+ *       dq' = ((M21*dz, M.e + ed) (+) (M22*dq, M.e + eq)) (+) (B2*dc, B.e + ec)    at enq
+ *       m += 2^k, u += 2^k;   z = Z_m (+) dz' at ez,   q = Z_{m-1} (+) dq' at eq', both orbit points from the extended storage;
+ *     then the EXTENDED step's tail with (n, en) = dz' and dq' in the place of its (a, b, ed): escaped at u - 1 if
+ *     ldexp(r2, 2 ez) > 4; else the pair rebase rule with its four terms at z's exponent, or m == N: dz = norm(z, ez),
+ *     dq = norm(q, eq'), m = 0; else dz = norm(dz', en), dq = norm(dq', enq).  dq' is computed, not copied, so this is where it
+ *     is normalised: a BLA step stores both deltas normalised (the zero with FR_DEEPX_ZERO_EXP), and at m >= 1 an extended
+ *     sample's dq is always normalised -- a copy of a normalised dz, or this.  Then the mode rule on the new dz alone.
+ *     If no level qualifies, or m == 0, the sample's own step of fr_render_deepx_phoenix in its mode, operation for operation:
+ *     it escapes at u, then u += 1.  Escapes inside a BLA step are not looked for.  Radii are monotone in k, and none exceeds
+ *     2^-54 (4 + |p|).
+ *
+ * What it skips (the numpy restatement tests/deepx_phoenix_bla_ref.py, 24 x 18, aa 1, the views of tests/deepx_phoenix_ref.py):
+ * 79.5 % of the updates on PX310 (N = 2258; 4.9x fewer loop trips), 83.0 % on PX400A (2826; 5.8x), 86.6 % on PX400B (4656;
+ * 7.4x), 75.4 % on PXRET (2408; 4.0x), 96.0 % on TIP1000 (2400; 23x), 99.9 % on NUC201X (the period-201 nucleus at 1e-1000,
+ * 2412; 302x).  iter equals the unflagged restatement's and the exact fixed-point iteration's on every pixel of PX310, PX400A,
+ * PX400B, PXRET and TIP1000 (0 of 432 differ on each; on TIP1000, whose escapes hang on margins of 1e-1000, the unflagged
+ * restatement agrees with exact everywhere too); NUC201X is interior on every pixel.
+ * Measured on one MI355X at 4096^2, aa 1 (profiles/deepx_phoenix_bla_time.txt, flagged and unflagged interleaved in one session,
+ * the unflagged render being the parent's kernel unchanged): PX310 34.19 ms against 142.41 ms (4.17x; 4.55x fewer loop trips),
+ * PX400A 32.78 ms against 184.02 ms (5.61x; 6.03x), PX400B 46.77 ms against 301.70 ms (6.45x; 7.17x), TIP1000 3.28 ms against
+ * 107.80 ms (32.9x; 48.9x), NUC201X 1.50 ms against 164.74 ms (110x; 302x), and PA (1e-100) passed as an extended view 11.22 ms
+ * against 30.44 ms (2.71x; 4.74x); iter equal to the unflagged render's on every pixel of all six.  A flagged trip costs 1.07 to
+ * 1.11 unflagged ones on the 1e-310 / 1e-400 views, 1.5 to 2.7 where most trips are BLA steps, 1.74 on PA, whose lanes are
+ * plain; the table build is 0.16 to 0.72 ms.  On the shallow view (zoom 3, passed as an extended view; a session of its own) the
+ * flag can only cost: 3.56 ms against 2.43 ms (0.68x), no lane passes the pre-filter, the cost is the 3 waves per SIMD for 4
+ * and the longer loop body.
+ *
+ * Cost: 112 bytes per entry on the device, per context, in buffers of the extended Phoenix slot's own, keyed by that slot's
+ * orbit generation (the orbit key holds p and r) and the bits of dcmax (mantissa and exponent): a zoom change at a fixed centre
+ * and fixed fraction bits rebuilds the table (K small launches on the render's stream) and not the orbit; a second flagged render
+ * builds nothing; unflagged renders, and every other path's slots, tables and counters, are untouched. */
+
+/* fr_ctx_last_deepx_ship_steps' contract for the context's most recent fr_render_deepx_phoenix / fr_render_deepx_phoenix_async call
+ * made with FR_FLAG_DEEPX_PHOENIX_BLA: out[0] single steps (plain and extended), out[1] BLA steps, out[2] updates skipped.
+ * FR_ERR_UNSUPPORTED if there is no such call.  The seven other counters do not report these calls, and the reverse. */
+int fr_ctx_last_deepx_phoenix_steps(fr_ctx* ctx, uint64_t out[3]);
 
 /* ---- frames over the GPUs of a node (BASELINE.json north_star: "tiled across the 8 GPUs of one node as disjoint row
  * bands with a final RCCL gather over xGMI") -----------------------------------------------------------------------------

@@ -1021,33 +1021,59 @@ static int check_phoenix_terms(const fr_phoenix_params* ph)
     return FR_OK;
 }
 
-int fr_deep_phoenix_validate(const fr_params* p, const fr_phoenix_params* ph, const fr_deep_view* v, uint32_t width, uint32_t height)
+/* The rules of the two entry points, in one order: `entry` with the fp64 view v checks p->zoom and resolves with it; with the
+ * extended view x the zoom is the view's string, p->zoom is not read, and the view is checked as fr_deepx_validate checks its own
+ * (resolve_view: reserved, frac_bits, the centre strings, the zoom string and its range).  flag: the entry's own BLA flag; other /
+ * other_flag / other_table: the other Phoenix entry's, its name and what its table is. */
+static int phoenix_view_validate(const char* entry, const char* flag, uint32_t other, const char* other_flag, const char* other_table,
+                                 const fr_params* p, const fr_phoenix_params* ph, const fr_deep_view* v, const fr_deepx_view* x,
+                                 uint32_t width, uint32_t height)
 {
-    if (!p || !ph || !v) return fr_set_error(FR_ERR_INVALID_ARG, "params/phoenix params/deep view is NULL");
+    if (!p || !ph || (!v && !x)) return fr_set_error(FR_ERR_INVALID_ARG, "params/phoenix params/deep view is NULL");
     if (p->fractal_type != FR_FRACTAL_PHOENIX)
-        return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deep_phoenix renders FR_FRACTAL_PHOENIX only (got %d)", p->fractal_type);
+        return fr_set_error(FR_ERR_UNSUPPORTED, "%s renders FR_FRACTAL_PHOENIX only (got %d)", entry, p->fractal_type);
     if (p->precision != FR_PRECISION_F64)
-        return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deep_phoenix needs FR_PRECISION_F64 (got %d)", p->precision);
+        return fr_set_error(FR_ERR_UNSUPPORTED, "%s needs FR_PRECISION_F64 (got %d)", entry, p->precision);
     if (width == 0 || height == 0)
         return fr_set_error(FR_ERR_INVALID_ARG, "width and height must be > 0 (got %ux%u)", width, height);
-    fr_params q = *p;                                            /* the double centre is not read */
+    fr_params q = *p;                                            /* the double centre is not read, nor an extended view's double zoom */
     q.center_x = 0.0; q.center_y = 0.0;
+    if (x) q.zoom = 1.0;
     int st = fr_phoenix_validate(&q, ph, width, height);
     if (st != FR_OK) return st;
     if ((st = check_phoenix_terms(ph)) != FR_OK) return st;
     if (ph->use_julia_set)
-        return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deep_phoenix: use_julia_set is not available (a Julia-mode Phoenix frame "
-                            "starts every pixel from z = 0 with the same c, so it is one colour at any depth)");
-    if ((st = check_zoom(p->zoom)) != FR_OK) return st;
+        return fr_set_error(FR_ERR_UNSUPPORTED, "%s: use_julia_set is not available (a Julia-mode Phoenix frame "
+                            "starts every pixel from z = 0 with the same c, so it is one colour at any depth)", entry);
+    if (v && (st = check_zoom(p->zoom)) != FR_OK) return st;
     if (p->flags & (OTHER_FLAGS | JULIA_FLAGS))
-        return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deep_phoenix: the BLA flags of the other paths are not available (their "
+        return fr_set_error(FR_ERR_UNSUPPORTED, "%s: the BLA flags of the other paths are not available (their "
                             "tables belong to the Mandelbrot, Burning Ship and Julia paths): the flag of this entry point is "
-                            "FR_FLAG_DEEP_PHOENIX_BLA");
-    if (p->flags & FR_FLAG_DEEPX_PHOENIX_BLA)
-        return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deep_phoenix: FR_FLAG_DEEPX_PHOENIX_BLA is not available (its BLA table is "
-                            "extended, fr_render_deepx_phoenix's): the flag of this entry point is FR_FLAG_DEEP_PHOENIX_BLA");
+                            "%s", entry, flag);
+    if (p->flags & other)
+        return fr_set_error(FR_ERR_UNSUPPORTED, "%s: %s is not available (its BLA table is %s): the flag of this entry point is %s",
+                            entry, other_flag, other_table, flag);
     deep_resolved r;
-    return resolve_view(v, NULL, p->zoom, 1, &r);
+    return resolve_view(v, x, v ? p->zoom : 0.0, 1, &r);
+}
+
+int fr_deep_phoenix_validate(const fr_params* p, const fr_phoenix_params* ph, const fr_deep_view* v, uint32_t width, uint32_t height)
+{
+    return phoenix_view_validate("fr_render_deep_phoenix", "FR_FLAG_DEEP_PHOENIX_BLA", FR_FLAG_DEEPX_PHOENIX_BLA,
+                                 "FR_FLAG_DEEPX_PHOENIX_BLA", "extended, fr_render_deepx_phoenix's", p, ph, v, NULL, width, height);
+}
+
+/* the shared tail of the two reference orbits: p and r in the resolved view's fixed point, then the Phoenix recurrence; out_exp2
+ * with the extended storage */
+static int phoenix_orbit_tail(const deep_resolved* r, const fr_phoenix_params* ph, int32_t max_iter, double* out_xy, int32_t* out_exp2,
+                              int32_t* out_len)
+{
+    const int st = check_phoenix_terms(ph);
+    if (st != FR_OK) return st;
+    phoenix_terms t;
+    float_to_fixed_floor(ph->phoenix_p, r->fmt, t.p);
+    float_to_fixed_floor(ph->phoenix_r, r->fmt, t.r);
+    return orbit_loop(r->cr, r->ci, NULL, NULL, r->fmt, kOrbitPhoenix, &t, max_iter, 2.0f, out_xy, out_exp2, out_len);
 }
 
 int fr_deep_phoenix_reference_orbit(const fr_deep_view* v, const fr_phoenix_params* ph, double zoom, int32_t max_iter, double* out_xy,
@@ -1057,43 +1083,15 @@ int fr_deep_phoenix_reference_orbit(const fr_deep_view* v, const fr_phoenix_para
     deep_resolved r;
     int st = orbit_request("fr_deep_phoenix_reference_orbit", out_xy && out_len, v, NULL, &zoom, max_iter, 2.0f, NULL, &r);
     if (st != FR_OK) return st;
-    if ((st = check_phoenix_terms(ph)) != FR_OK) return st;
-    phoenix_terms t;
-    float_to_fixed_floor(ph->phoenix_p, r.fmt, t.p);
-    float_to_fixed_floor(ph->phoenix_r, r.fmt, t.r);
-    return orbit_loop(r.cr, r.ci, NULL, NULL, r.fmt, kOrbitPhoenix, &t, max_iter, 2.0f, out_xy, NULL, out_len);
+    return phoenix_orbit_tail(&r, ph, max_iter, out_xy, NULL, out_len);
 }
 
-/* ---- deep Phoenix views below 1e-290 (fr_render_deepx_phoenix) ------------------------------------------------------------------
- * fr_deep_phoenix_validate's rules in its order with the zoom in the view's string: p->zoom is not read, and the view is checked
- * as fr_deepx_validate checks its own (resolve_view: reserved, frac_bits, the centre strings, the zoom string and its range). */
+/* ---- deep Phoenix views below 1e-290 (fr_render_deepx_phoenix): fr_deep_phoenix_validate's rules with the zoom in the view's
+ * string ---------------------------------------------------------------------------------------------------------------------- */
 int fr_deepx_phoenix_validate(const fr_params* p, const fr_phoenix_params* ph, const fr_deepx_view* v, uint32_t width, uint32_t height)
 {
-    if (!p || !ph || !v) return fr_set_error(FR_ERR_INVALID_ARG, "params/phoenix params/deep view is NULL");
-    if (p->fractal_type != FR_FRACTAL_PHOENIX)
-        return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deepx_phoenix renders FR_FRACTAL_PHOENIX only (got %d)", p->fractal_type);
-    if (p->precision != FR_PRECISION_F64)
-        return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deepx_phoenix needs FR_PRECISION_F64 (got %d)", p->precision);
-    if (width == 0 || height == 0)
-        return fr_set_error(FR_ERR_INVALID_ARG, "width and height must be > 0 (got %ux%u)", width, height);
-    fr_params q = *p;                                            /* the double centre and the double zoom are not read */
-    q.center_x = 0.0; q.center_y = 0.0;
-    q.zoom = 1.0;
-    int st = fr_phoenix_validate(&q, ph, width, height);
-    if (st != FR_OK) return st;
-    if ((st = check_phoenix_terms(ph)) != FR_OK) return st;
-    if (ph->use_julia_set)
-        return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deepx_phoenix: use_julia_set is not available (a Julia-mode Phoenix frame "
-                            "starts every pixel from z = 0 with the same c, so it is one colour at any depth)");
-    if (p->flags & (OTHER_FLAGS | JULIA_FLAGS))
-        return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deepx_phoenix: the BLA flags of the other paths are not available (their "
-                            "tables belong to the Mandelbrot, Burning Ship and Julia paths): the flag of this entry point is "
-                            "FR_FLAG_DEEPX_PHOENIX_BLA");
-    if (p->flags & FR_FLAG_DEEP_PHOENIX_BLA)
-        return fr_set_error(FR_ERR_UNSUPPORTED, "fr_render_deepx_phoenix: FR_FLAG_DEEP_PHOENIX_BLA is not available (its BLA table is "
-                            "fp64, fr_render_deep_phoenix's): the flag of this entry point is FR_FLAG_DEEPX_PHOENIX_BLA");
-    deep_resolved r;
-    return resolve_view(NULL, v, 0.0, 1, &r);
+    return phoenix_view_validate("fr_render_deepx_phoenix", "FR_FLAG_DEEPX_PHOENIX_BLA", FR_FLAG_DEEP_PHOENIX_BLA,
+                                 "FR_FLAG_DEEP_PHOENIX_BLA", "fp64, fr_render_deep_phoenix's", p, ph, NULL, v, width, height);
 }
 
 int fr_deepx_phoenix_reference_orbit(const fr_deepx_view* v, const fr_phoenix_params* ph, int32_t max_iter, double* out_mant_xy,
@@ -1104,9 +1102,5 @@ int fr_deepx_phoenix_reference_orbit(const fr_deepx_view* v, const fr_phoenix_pa
     int st = orbit_request("fr_deepx_phoenix_reference_orbit", out_mant_xy && out_exp2 && out_len, NULL, v, NULL, max_iter, 2.0f,
                            NULL, &r);
     if (st != FR_OK) return st;
-    if ((st = check_phoenix_terms(ph)) != FR_OK) return st;
-    phoenix_terms t;
-    float_to_fixed_floor(ph->phoenix_p, r.fmt, t.p);
-    float_to_fixed_floor(ph->phoenix_r, r.fmt, t.r);
-    return orbit_loop(r.cr, r.ci, NULL, NULL, r.fmt, kOrbitPhoenix, &t, max_iter, 2.0f, out_mant_xy, out_exp2, out_len);
+    return phoenix_orbit_tail(&r, ph, max_iter, out_mant_xy, out_exp2, out_len);
 }

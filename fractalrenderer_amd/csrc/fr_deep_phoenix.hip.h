@@ -22,8 +22,10 @@
  * O(1) term r q next to pixel-dependent terms many orders below it.  The rule is empirical (the header says on which views it
  * was checked against the exact iteration), not a theorem.
  *
- * A kernel and a loop of its own rather than a fourth policy of deep_orbit<F>: the state is two deltas, the orbit is read at
- * two indices, and the rebase is another rule.  How it runs is deep_kernel's way:
+ * Loops and a kernel body of their own rather than a fourth policy of deep_orbit<F>: the state is two deltas, the orbit is read
+ * at two indices, and the rebase is another rule.  There are four loops -- fp64 or extended-exponent deltas, each plain or with
+ * iteration skipping -- and one body around them, deep_phoenix_kernel_body<DeepPhoenixBlock<X, BLA>> at the end of the file: the
+ * block's two switches pick how dc is formed, which loop runs and whether the step counts exist.  How it runs is deep_kernel's way:
  *   - a persistent grid of the resident set pulls runs of 8x8 sub-tiles from the sharded WaveQueue with unlimited stealing; one
  *     lane per sample, the aa x aa samples of a pixel one after the other in the lane (sx outer: the ship's viewport map, which
  *     is Phoenix's less the centre); the wave leaves a sample's loop when no lane is live;
@@ -33,8 +35,8 @@
  *   - the colour stage is phoenix_kernel<double>'s: phoenix_smooth on (i, lastZ) in double, phoenix_colour on
  *     (smooth / max_iter, smooth, lastZ) narrowed to float, the aa x aa average, post_chain with Phoenix's floors.  lastZ of a
  *     sample that never escaped is Z_m + dz of its final state, the z of its last update.
- * Behind the kernel: iteration skipping for this path (FR_FLAG_DEEP_PHOENIX_BLA) -- the table's level kernel, the flagged loop
- * and its kernel; then the extended half, and its iteration skipping (FR_FLAG_DEEPX_PHOENIX_BLA) at the end.
+ * Behind the fp64 loop and the colour stage: iteration skipping for this path (FR_FLAG_DEEP_PHOENIX_BLA) -- the table's level
+ * kernel and the flagged loop; then the extended half, its iteration skipping (FR_FLAG_DEEPX_PHOENIX_BLA), and the kernels.
  */
 #pragma once
 #include "fr_deep.hip.h"
@@ -42,7 +44,7 @@
 
 namespace fr {
 
-/* Kernel argument block of deep_phoenix_kernel */
+/* What every deep Phoenix kernel reads: the whole argument block of deep_phoenix_kernel */
 struct DeepPhoenixArgs {
     const double2* orbit;                /* Z_0 .. Z_N */
     int32_t n_ref;                       /* N >= 1 */
@@ -57,6 +59,20 @@ struct DeepPhoenixArgs {
     double* nu;
     int32_t* iter;
     QueueArgs q;
+};
+
+/* The argument block of the four kernels, composed as DeepBlock is (fr_deep.hip.h): DeepPhoenixArgs, then with X the orbit's
+ * extended storage (orbit holds the plain doubles and zoom is not read), then with BLA the table of that storage.  A part that is
+ * off is an empty base and takes no room. */
+template <bool X, bool BLA = false>
+struct DeepPhoenixBlock : DeepPhoenixArgs, std::conditional_t<X, DeepXOrbit, NoPart<0>> {
+    static constexpr bool kX = X, kBla = false;
+};
+
+template <bool X>
+struct DeepPhoenixBlock<X, true> : DeepPhoenixBlock<X> {
+    static constexpr bool kBla = true;
+    std::conditional_t<X, BlaXTable, BlaTable> t;
 };
 
 /* The wave's 64 samples, one per lane.  live = false: a lane without a sample (outside the frame).  esc = the loop index of
@@ -115,43 +131,6 @@ __device__ __attribute__((noinline)) PhoenixShade deep_phoenix_shade(const int e
     if (want_rgb) phoenix_colour((float)(o.smooth / (double)max_iter), (float)o.smooth, (float)ezx, (float)ezy, density, rgb);
     o.r = rgb[0]; o.g = rgb[1]; o.b = rgb[2];
     return o;
-}
-
-__global__ void __launch_bounds__(kBlockThreads)
-deep_phoenix_kernel(const DeepPhoenixArgs A)
-{
-    const uint32_t lane = threadIdx.x & (kWave - 1);
-    const int W = A.g.W, H = A.g.H, max_iter = A.max_iter;
-    const int aa = A.aa > 1 ? A.aa : 1;
-    const double resx = (double)W, resy = (double)H;
-    const double2 z1 = A.orbit[1];
-
-    walk_subtiles<3, true>(A.q, A.g, lane, [&](const int px, const int py, const int lrow, const bool inside) {
-        float acc[3] = {0.0f, 0.0f, 0.0f};
-        double nu0 = 0.0;
-        int it0 = 0;
-        const int nsamp = aa * aa;
-        for (int s = 0; s < nsamp; ++s) {
-            const double2 dc = ShipFormula::dc(px, py, s, aa, resx, resy, A.zoom);
-            const double cx = inside ? dc.x : 0.0, cy = inside ? dc.y : 0.0;
-            int esc;
-            double ezx, ezy;
-            deep_phoenix_orbit(A, cx, cy, z1, inside, esc, ezx, ezy);
-            const PhoenixShade sh = deep_phoenix_shade(esc, ezx, ezy, max_iter, A.stripe_density, A.rgba != nullptr);
-            if (s == 0) { nu0 = sh.smooth; it0 = esc; }
-            if (A.rgba) { acc[0] = acc[0] + sh.r; acc[1] = acc[1] + sh.g; acc[2] = acc[2] + sh.b; }
-        }
-        if (!inside) return;
-        const size_t o = plane_index(A.g, px, py, lrow);
-        if (A.rgba) {
-            const float n = (float)(aa * aa);
-            float rgb[3] = {acc[0] / n, acc[1] / n, acc[2] / n};
-            if (A.flags & FR_FLAG_POST_CHAIN) post_chain(rgb, A.brightness, A.saturation, A.contrast, true);
-            A.rgba[o] = make_float4(rgb[0], rgb[1], rgb[2], 1.0f);
-        }
-        if (A.nu) A.nu[o] = nu0;
-        if (A.iter) A.iter[o] = it0;
-    });
 }
 
 /* ---- iteration skipping (FR_FLAG_DEEP_PHOENIX_BLA; the header's section is the contract) ----------------------------------------
@@ -230,11 +209,6 @@ phoenix_bla_level_kernel(const double2* __restrict__ orbit, const int32_t n_ref,
         for (int i = 0; i < 2; ++i) mb[S * e + 4 + i] = b[i];
     }
 }
-
-/* Kernel argument block of deep_phoenix_bla_kernel */
-struct DeepPhoenixBlaArgs : DeepPhoenixArgs {
-    BlaTable t;
-};
 
 /* deep_phoenix_orbit with BLA: u replaces the loop index.  A lane at m >= 1 probes the levels top down from bla_top_level (radii
  * are monotone in k) and takes the first whose radius admits the pair, else the plain step, operation for operation
@@ -329,57 +303,6 @@ __device__ __forceinline__ void deep_phoenix_orbit_bla(const DeepPhoenixArgs& A,
     if (esc == max_iter) { ezx = Zx + dzx; ezy = Zy + dzy; }     /* lastZ of a sample that never escaped */
 }
 
-/* deep_phoenix_kernel around deep_phoenix_orbit_bla, with the step counts: a kernel of its own, so that the unflagged kernel
- * stays the instruction stream it was.  Each lane sums its samples' steps and updates; a wave adds its three totals to the
- * table's counters with one atomic each (updates skipped = updates - plain steps). */
-__global__ void __launch_bounds__(kBlockThreads)
-deep_phoenix_bla_kernel(const DeepPhoenixBlaArgs A)
-{
-    const uint32_t lane = threadIdx.x & (kWave - 1);
-    const int W = A.g.W, H = A.g.H, max_iter = A.max_iter;
-    const int aa = A.aa > 1 ? A.aa : 1;
-    const double resx = (double)W, resy = (double)H;
-    const double2 z1 = A.orbit[1];
-    unsigned long long n_plain = 0ull, n_bla = 0ull, n_upd = 0ull;
-
-    walk_subtiles<3, true>(A.q, A.g, lane, [&](const int px, const int py, const int lrow, const bool inside) {
-        float acc[3] = {0.0f, 0.0f, 0.0f};
-        double nu0 = 0.0;
-        int it0 = 0;
-        const int nsamp = aa * aa;
-        for (int s = 0; s < nsamp; ++s) {
-            const double2 dc = ShipFormula::dc(px, py, s, aa, resx, resy, A.zoom);
-            const double cx = inside ? dc.x : 0.0, cy = inside ? dc.y : 0.0;
-            int esc;
-            double ezx, ezy;
-            uint32_t np, nb;
-            deep_phoenix_orbit_bla(A, A.t, cx, cy, z1, inside, esc, ezx, ezy, np, nb);
-            if (inside) {
-                n_plain += np; n_bla += nb;
-                n_upd += (unsigned long long)(esc < max_iter ? esc + 1 : max_iter);
-            }
-            const PhoenixShade sh = deep_phoenix_shade(esc, ezx, ezy, max_iter, A.stripe_density, A.rgba != nullptr);
-            if (s == 0) { nu0 = sh.smooth; it0 = esc; }
-            if (A.rgba) { acc[0] = acc[0] + sh.r; acc[1] = acc[1] + sh.g; acc[2] = acc[2] + sh.b; }
-        }
-        if (!inside) return;
-        const size_t o = plane_index(A.g, px, py, lrow);
-        if (A.rgba) {
-            const float n = (float)(aa * aa);
-            float rgb[3] = {acc[0] / n, acc[1] / n, acc[2] / n};
-            if (A.flags & FR_FLAG_POST_CHAIN) post_chain(rgb, A.brightness, A.saturation, A.contrast, true);
-            A.rgba[o] = make_float4(rgb[0], rgb[1], rgb[2], 1.0f);
-        }
-        if (A.nu) A.nu[o] = nu0;
-        if (A.iter) A.iter[o] = it0;
-    });
-    unsigned long long v[3] = {n_plain, n_bla, n_upd - n_plain};
-    for (int c = 0; c < 3; ++c) {
-        for (int o = kWave / 2; o > 0; o >>= 1) v[c] += __shfl_xor(v[c], o, kWave);
-        if (lane == 0) atomicAdd(A.t.steps + c, v[c]);
-    }
-}
-
 /* ---- below 1e-290: extended-exponent deltas (fr_render_deepx_phoenix) ---------------------------------------------------------
  * deep_phoenix_orbit in the two modes of deep_orbit_x (fr_deep.hip.h; norm, (+), ldexp and the storage are the header's).  The
  * orbit is in the extended storage: mantissa pairs and int32 exponents for the extended mode, the plain doubles for the plain
@@ -413,14 +336,7 @@ deep_phoenix_bla_kernel(const DeepPhoenixBlaArgs A)
  *
  * Registers across a step as in deep_phoenix_orbit: Z_{m+2} is loaded one step ahead, Z_1 is kept for the rebase, q comes from
  * the register that held Z_m; a lane that changes mode reloads Z_m and Z_{m+1} from the new mode's arrays. */
-struct DeepPhoenixXArgs : DeepPhoenixArgs {   /* orbit: the plain doubles; zoom is not read */
-    const double2* mant;                 /* (mx, my) of Z_0 .. Z_N */
-    const int32_t* exp2;                 /* e of Z_0 .. Z_N */
-    double zm;                           /* zoom = zm 2^ze */
-    int32_t ze;
-};
-
-__device__ __forceinline__ void deep_phoenix_orbit_x(const DeepPhoenixXArgs& A, const double cx, const double cy, const int ec,
+__device__ __forceinline__ void deep_phoenix_orbit_x(const DeepPhoenixBlock<true>& A, const double cx, const double cy, const int ec,
                                                      bool live, int& esc, double& ezx, double& ezy)
 {
     const double2* __restrict__ orbit = A.orbit;
@@ -555,44 +471,6 @@ __device__ __forceinline__ void deep_phoenix_orbit_x(const DeepPhoenixXArgs& A, 
     }
 }
 
-__global__ void __launch_bounds__(kBlockThreads)
-deep_phoenix_x_kernel(const DeepPhoenixXArgs A)
-{
-    const uint32_t lane = threadIdx.x & (kWave - 1);
-    const int W = A.g.W, H = A.g.H, max_iter = A.max_iter;
-    const int aa = A.aa > 1 ? A.aa : 1;
-    const double resx = (double)W, resy = (double)H;
-
-    walk_subtiles<3, true>(A.q, A.g, lane, [&](const int px, const int py, const int lrow, const bool inside) {
-        float acc[3] = {0.0f, 0.0f, 0.0f};
-        double nu0 = 0.0;
-        int it0 = 0;
-        const int nsamp = aa * aa;
-        for (int s = 0; s < nsamp; ++s) {
-            const double2 dc = ShipFormula::dc(px, py, s, aa, resx, resy, A.zm);   /* on the zoom's mantissa; its exponent is dc.e */
-            double cx = inside ? dc.x : 0.0, cy = inside ? dc.y : 0.0;
-            int ec = A.ze;
-            x_norm(cx, cy, ec);
-            int esc;
-            double ezx, ezy;
-            deep_phoenix_orbit_x(A, cx, cy, ec, inside, esc, ezx, ezy);
-            const PhoenixShade sh = deep_phoenix_shade(esc, ezx, ezy, max_iter, A.stripe_density, A.rgba != nullptr);
-            if (s == 0) { nu0 = sh.smooth; it0 = esc; }
-            if (A.rgba) { acc[0] = acc[0] + sh.r; acc[1] = acc[1] + sh.g; acc[2] = acc[2] + sh.b; }
-        }
-        if (!inside) return;
-        const size_t o = plane_index(A.g, px, py, lrow);
-        if (A.rgba) {
-            const float n = (float)(aa * aa);
-            float rgb[3] = {acc[0] / n, acc[1] / n, acc[2] / n};
-            if (A.flags & FR_FLAG_POST_CHAIN) post_chain(rgb, A.brightness, A.saturation, A.contrast, true);
-            A.rgba[o] = make_float4(rgb[0], rgb[1], rgb[2], 1.0f);
-        }
-        if (A.nu) A.nu[o] = nu0;
-        if (A.iter) A.iter[o] = it0;
-    });
-}
-
 /* ---- iteration skipping below 1e-290 (FR_FLAG_DEEPX_PHOENIX_BLA; the header's section is the contract) ---------------------------
  * FR_FLAG_DEEP_PHOENIX_BLA's maps of the pair (dz, dq) in the extended arithmetic of BlaXTable: M's eight mantissas share one
  * int32 exponent, B's four another, the radius is an XRad.  The storage is the extended tables': r in an array of its own, six
@@ -718,11 +596,6 @@ phoenix_x_bla_level_kernel(const double2* __restrict__ mant, const int32_t* __re
     }
 }
 
-/* Kernel argument block of deep_phoenix_x_bla_kernel */
-struct DeepPhoenixXBlaArgs : DeepPhoenixXArgs {
-    BlaXTable t;
-};
-
 /* a term of a BLA step, a product of mantissas at the exponent e: exactly zero, it has FR_DEEPX_ZERO_EXP and raises no common
  * exponent (M12 = M22 = 0 at r = 0 must not shift M11 dz out of a double next to a dq 2^1100 above dz) */
 __device__ __forceinline__ int px_term_exp(const double2 t, const int e) { return (t.x == 0.0 && t.y == 0.0) ? kXZero : e; }
@@ -746,7 +619,7 @@ __device__ __forceinline__ double2 px_add(const double2 a, const int ea, const d
  * |dz|^2 + |dq|^2 >= 2^-104 (4 + |p|)^2 (deep_phoenix_orbit_bla's compare; no underflow, |dz| >= 2^-400), cannot pass a probe and
  * gathers nothing.  A BLA lane loads Z_m and Z_{m-1} at its new m from the extended storage, and Z_{m+1} from the arrays of the
  * mode it goes on in.  nsingle / nbla: the steps this sample took. */
-__device__ __forceinline__ void deep_phoenix_orbit_x_bla(const DeepPhoenixXArgs& A, const BlaXTable& T, const double cx,
+__device__ __forceinline__ void deep_phoenix_orbit_x_bla(const DeepPhoenixBlock<true>& A, const BlaXTable& T, const double cx,
                                                          const double cy, const int ec, bool live, int& esc, double& ezx,
                                                          double& ezy, uint32_t& nsingle, uint32_t& nbla)
 {
@@ -953,16 +826,23 @@ __device__ __forceinline__ void deep_phoenix_orbit_x_bla(const DeepPhoenixXArgs&
     }
 }
 
-/* deep_phoenix_x_kernel around deep_phoenix_orbit_x_bla, with the step counts of deep_phoenix_bla_kernel: a kernel of its own, so
- * that the unflagged kernel stays the instruction stream it was */
-__global__ void __launch_bounds__(kBlockThreads)
-deep_phoenix_x_bla_kernel(const DeepPhoenixXBlaArgs A)
+/* ---- the kernels ---------------------------------------------------------------------------------------------------------------
+ * One body for the four, ARGS = DeepPhoenixBlock<X, BLA>.  X: dc is formed on the zoom's mantissa and normalised with the zoom's
+ * exponent, and the loops are the extended ones.  BLA: the flagged loop, and the step counts -- each lane sums its samples' steps
+ * and updates; a wave adds its three totals to the table's counters with one atomic each (updates skipped = updates - plain or
+ * single steps).  The four named __global__ wrappers below are the kernels.  The block comes by value for the instruction
+ * streams' sake, which are those of the time when each kernel had this body written into it: taken by reference, all four kernels
+ * are scheduled differently. */
+template <class ARGS>
+__device__ __forceinline__ void deep_phoenix_kernel_body(const ARGS A)
 {
+    constexpr bool X = ARGS::kX, BLA = ARGS::kBla;
     const uint32_t lane = threadIdx.x & (kWave - 1);
     const int W = A.g.W, H = A.g.H, max_iter = A.max_iter;
     const int aa = A.aa > 1 ? A.aa : 1;
     const double resx = (double)W, resy = (double)H;
-    unsigned long long n_single = 0ull, n_bla = 0ull, n_upd = 0ull;
+    const double2 z1 = X ? make_double2(0.0, 0.0) : A.orbit[1];  /* fp64: Z_1 for the rebase; the extended loops load their own */
+    unsigned long long n_plain = 0ull, n_bla = 0ull, n_upd = 0ull;   /* BLA: this lane's steps and updates */
 
     walk_subtiles<3, true>(A.q, A.g, lane, [&](const int px, const int py, const int lrow, const bool inside) {
         float acc[3] = {0.0f, 0.0f, 0.0f};
@@ -970,17 +850,28 @@ deep_phoenix_x_bla_kernel(const DeepPhoenixXBlaArgs A)
         int it0 = 0;
         const int nsamp = aa * aa;
         for (int s = 0; s < nsamp; ++s) {
-            const double2 dc = ShipFormula::dc(px, py, s, aa, resx, resy, A.zm);   /* on the zoom's mantissa; its exponent is dc.e */
+            double zs;                                           /* extended: the zoom's mantissa; its exponent is dc.e */
+            if constexpr (X) zs = A.zm;
+            else zs = A.zoom;
+            const double2 dc = ShipFormula::dc(px, py, s, aa, resx, resy, zs);
             double cx = inside ? dc.x : 0.0, cy = inside ? dc.y : 0.0;
-            int ec = A.ze;
-            x_norm(cx, cy, ec);
+            int ec = 0;
+            if constexpr (X) { ec = A.ze; x_norm(cx, cy, ec); }
             int esc;
             double ezx, ezy;
-            uint32_t ns, nb;
-            deep_phoenix_orbit_x_bla(A, A.t, cx, cy, ec, inside, esc, ezx, ezy, ns, nb);
-            if (inside) {
-                n_single += ns; n_bla += nb;
-                n_upd += (unsigned long long)(esc < max_iter ? esc + 1 : max_iter);
+            uint32_t np, nb;
+            if constexpr (X) {
+                if constexpr (BLA) deep_phoenix_orbit_x_bla(A, A.t, cx, cy, ec, inside, esc, ezx, ezy, np, nb);
+                else deep_phoenix_orbit_x(A, cx, cy, ec, inside, esc, ezx, ezy);
+            } else {
+                if constexpr (BLA) deep_phoenix_orbit_bla(A, A.t, cx, cy, z1, inside, esc, ezx, ezy, np, nb);
+                else deep_phoenix_orbit(A, cx, cy, z1, inside, esc, ezx, ezy);
+            }
+            if constexpr (BLA) {
+                if (inside) {
+                    n_plain += np; n_bla += nb;
+                    n_upd += (unsigned long long)(esc < max_iter ? esc + 1 : max_iter);
+                }
             }
             const PhoenixShade sh = deep_phoenix_shade(esc, ezx, ezy, max_iter, A.stripe_density, A.rgba != nullptr);
             if (s == 0) { nu0 = sh.smooth; it0 = esc; }
@@ -997,11 +888,22 @@ deep_phoenix_x_bla_kernel(const DeepPhoenixXBlaArgs A)
         if (A.nu) A.nu[o] = nu0;
         if (A.iter) A.iter[o] = it0;
     });
-    unsigned long long v[3] = {n_single, n_bla, n_upd - n_single};
-    for (int c = 0; c < 3; ++c) {
-        for (int o = kWave / 2; o > 0; o >>= 1) v[c] += __shfl_xor(v[c], o, kWave);
-        if (lane == 0) atomicAdd(A.t.steps + c, v[c]);
+    if constexpr (BLA) {
+        unsigned long long v[3] = {n_plain, n_bla, n_upd - n_plain};
+        for (int c = 0; c < 3; ++c) {
+            for (int o = kWave / 2; o > 0; o >>= 1) v[c] += __shfl_xor(v[c], o, kWave);
+            if (lane == 0) atomicAdd(A.t.steps + c, v[c]);
+        }
     }
 }
+
+__global__ void __launch_bounds__(kBlockThreads)
+deep_phoenix_kernel(const DeepPhoenixBlock<false> A) { deep_phoenix_kernel_body(A); }
+__global__ void __launch_bounds__(kBlockThreads)
+deep_phoenix_bla_kernel(const DeepPhoenixBlock<false, true> A) { deep_phoenix_kernel_body(A); }
+__global__ void __launch_bounds__(kBlockThreads)
+deep_phoenix_x_kernel(const DeepPhoenixBlock<true> A) { deep_phoenix_kernel_body(A); }
+__global__ void __launch_bounds__(kBlockThreads)
+deep_phoenix_x_bla_kernel(const DeepPhoenixBlock<true, true> A) { deep_phoenix_kernel_body(A); }
 
 }  // namespace fr

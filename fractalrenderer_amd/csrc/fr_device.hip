@@ -844,6 +844,20 @@ struct DeepAt {
     int32_t ze, bits;
 };
 
+/* ... of an entry point's view, validated: an fp64 view with the automatic F where frac_bits is 0; an extended view's zoom is its
+ * string, resolved here with its F */
+static int deep_at_of(const fr_params* p, const fr_deep_view* v, DeepAt* at)
+{
+    *at = {v->center_x, v->center_y, nullptr, p->zoom, 0, v->frac_bits ? v->frac_bits : fr_deep_frac_bits(p->zoom)};
+    return FR_OK;
+}
+
+static int deep_at_of(const fr_params*, const fr_deepx_view* v, DeepAt* at)
+{
+    *at = {v->center_x, v->center_y, v->zoom, 0.0, 0, v->frac_bits};
+    return fr_deepx_resolve(v, &at->zm, &at->ze, &at->bits);
+}
+
 /* The reference orbit(s) of the view in the path's slot unless the slot holds them already (keyed by the centre strings, the
  * fraction bits, max_iter, the bailout and, in a Julia slot, the bits of c).  One orbit, or Julia's Q at point 0 and P half the
  * capacity behind it (kFormula); ext: the extended storage, whose plain doubles ldexp(mantissa, exponent) are formed here.
@@ -1068,7 +1082,26 @@ static int bla_steps_end(BlaSlot& t, hipStream_t stream)
     return FR_OK;
 }
 
-/* The ten paths, each by the block of its unflagged kernel (the flagged kernel's, with the table: DeepPath::Bla) */
+/* A flagged kernel's launch, for every path: the slot's table of formula f for the frame fr (bla_table_for: x with the extended
+ * storage, jt for Julia's two), its pointers and level count into `tab`, the table inside the kernel's argument block, then
+ * launch() -- the kernel on that block -- between the counters' clearing and their copy. */
+template <class TAB, class Launch>
+static int launch_with_bla(fr_ctx* c, hipStream_t stream, DeepSlot& s, int f, const BlaFrame& fr, const DeepXOrbit* x, TAB& tab,
+                           JuliaTables* jt, Launch&& launch)
+{
+    int levels = 0;
+    const int ts = bla_table_for(c, s, f, fr, x, stream, &levels, jt);
+    if (ts != FR_OK) return ts;
+    bla_table_args(tab, s.t);
+    tab.levels = levels;
+    const int bs = bla_steps_begin(s.t, stream, &tab.steps);
+    if (bs != FR_OK) return bs;
+    const int st = launch();
+    if (st != FR_OK) return st;
+    return bla_steps_end(s.t, stream);
+}
+
+/* The ten paths of DeepBlock, each by the block of its unflagged kernel (the flagged kernel's, with the table: DeepPath::Bla) */
 using DeepMandel = DeepBlock<MandelFormula, false, false>;
 using DeepMandelDe = DeepBlock<MandelFormula, false, true>;
 using DeepMandelX = DeepBlock<MandelFormula, true, false>;
@@ -1135,21 +1168,12 @@ static int launch_deep(fr_ctx* c, hipStream_t stream, BASE& base, bool bla)
     static_cast<BASE&>(a) = base;
     const DeepXOrbit* x = nullptr;
     if constexpr (P::ext) x = &a;
-    BlaSlot& t = s.t;
-    int levels = 0;
     JuliaTables jt = {0, 0u};
     const BlaFrame fr = {a.orbit, a.zoom, a.g.W, a.g.H, 0.0, 0.0};
-    const int ts = bla_table_for(c, s, P::f, fr, x, stream, &levels, &jt);
-    if (ts != FR_OK) return ts;
-    auto& tab = bla_table(a);
-    if constexpr (P::f == kJulia) { a.t.levels_p = jt.levels_p; a.t.base_p = jt.base_p; }
-    bla_table_args(tab, t);
-    tab.levels = levels;
-    const int bs = bla_steps_begin(t, stream, &tab.steps);
-    if (bs != FR_OK) return bs;
-    const int st = launch_one_pass(c, stream, deep_kernel_name<BLA>(), deep_kernel_of<BLA>(), a, a.g, a.q, s.wg_per_cu[P::de][1], false);
-    if (st != FR_OK) return st;
-    return bla_steps_end(t, stream);
+    return launch_with_bla(c, stream, s, P::f, fr, x, bla_table(a), &jt, [&] {
+        if constexpr (P::f == kJulia) { a.t.levels_p = jt.levels_p; a.t.base_p = jt.base_p; }
+        return launch_one_pass(c, stream, deep_kernel_name<BLA>(), deep_kernel_of<BLA>(), a, a.g, a.q, s.wg_per_cu[P::de][1], false);
+    });
 }
 
 /* everything of DeepArgs that does not depend on the path: the zoom and the orbit stay with enqueue_deep_view */
@@ -1218,11 +1242,24 @@ static int enqueue_deepx_at(fr_ctx* c, int f, const fr_params* p, const fr_deepx
     return enqueue_deep_view<DeepMandelX>(c, p, at, W, H, shard, rgba, nu, iter, stream, out_frame, [](auto&) {});
 }
 
-/* ---- deep Phoenix views (fr_deep_phoenix.hip.h) ---------------------------------------------------------------------------
- * enqueue_deep_view's steps for the path that stands apart from DeepBlock: the rows of this part, the orbit in the Phoenix slot
- * (deep_slot_fill), DeepPhoenixArgs filled as enqueue_phoenix fills PhoenixArgs, then one pass with unlimited stealing at the
- * occupancy cached in the slot. */
-static int enqueue_deep_phoenix(fr_ctx* c, const fr_params* p, const fr_phoenix_params* ph, const fr_deep_view* v, uint32_t W,
+/* ---- deep Phoenix views (fr_deep_phoenix.hip.h) --------------------------------------------------------------------------- */
+/* the kernel of DeepPhoenixBlock<X, BLA> */
+template <bool X, bool BLA>
+static constexpr auto deep_phoenix_kernel_of()
+{
+    if constexpr (X && BLA) return deep_phoenix_x_bla_kernel;
+    else if constexpr (X) return deep_phoenix_x_kernel;
+    else if constexpr (BLA) return deep_phoenix_bla_kernel;
+    else return deep_phoenix_kernel;
+}
+
+/* enqueue_deep_view's steps for the two paths that stand apart from DeepBlock, fr_render_deep_phoenix and with X
+ * fr_render_deepx_phoenix: the rows of this part, the orbit in the Phoenix slot of the storage (deep_slot_fill), the flagged
+ * kernel's block filled as enqueue_phoenix fills PhoenixArgs -- with X the extended storage and the zoom pair, else the zoom --
+ * then one pass with unlimited stealing at the occupancy cached in the slot: the unflagged kernel on the block less its table, or
+ * with the entry's flag the table for this frame's dcmax (the whole frame's W and H) and the flagged kernel (launch_with_bla). */
+template <bool X>
+static int enqueue_deep_phoenix(fr_ctx* c, const fr_params* p, const fr_phoenix_params* ph, const DeepAt& at, uint32_t W,
                                 uint32_t H, const fr_shard* shard, float* rgba, void* nu, int32_t* iter, hipStream_t stream,
                                 bool out_frame)
 {
@@ -1230,92 +1267,39 @@ static int enqueue_deep_phoenix(fr_ctx* c, const fr_params* p, const fr_phoenix_
     uint32_t rows_local = 0;
     const int sh = begin_shard(c, shard, H, &norm, &rows_local);
     if (sh != FR_OK || rows_local == 0) return sh;
-    const DeepAt at = {v->center_x, v->center_y, nullptr, p->zoom, 0, v->frac_bits ? v->frac_bits : fr_deep_frac_bits(p->zoom)};
-    const int os = deep_slot_fill(c, kPhoenix, false, p, at, stream, ph);
+    const int os = deep_slot_fill(c, kPhoenix, X, p, at, stream, ph);
     if (os != FR_OK) return os;
 
-    DeepSlot& s = deep_slot(c, false, kPhoenix);
-    DeepPhoenixArgs a;
-    memset(&a, 0, sizeof(a));
-    a.orbit = reinterpret_cast<const double2*>(s.o.dev); a.n_ref = s.o.len - 1;
-    a.max_iter = p->max_iterations; a.aa = p->antialiasing_samples;
-    a.zoom = p->zoom;
-    a.p = (double)ph->phoenix_p; a.r = (double)ph->phoenix_r;
-    a.stripe_density = p->stripe_density;
-    a.brightness = p->color_brightness; a.saturation = p->color_saturation; a.contrast = p->color_contrast;
-    a.flags = p->flags;
-    a.g = tile_geom(W, H, rows_local, &norm, out_frame);
-    a.rgba = reinterpret_cast<float4*>(rgba); a.nu = (double*)nu; a.iter = iter;
-    if (!(p->flags & FR_FLAG_DEEP_PHOENIX_BLA))
-        return launch_one_pass(c, stream, "deep_phoenix_kernel", deep_phoenix_kernel, a, a.g, a.q, s.wg_per_cu[0][0], false);
-    /* the slot's table for this frame's dcmax (the whole frame's W and H), then the flagged kernel between its counters' clearing
-     * and their copy, as launch_deep does it */
-    DeepPhoenixBlaArgs b;
+    DeepSlot& s = deep_slot(c, X, kPhoenix);
+    DeepPhoenixBlock<X, true> b;
     memset(&b, 0, sizeof(b));
-    static_cast<DeepPhoenixArgs&>(b) = a;
-    const BlaFrame fr = {a.orbit, a.zoom, a.g.W, a.g.H, a.p, a.r};
-    int levels = 0;
-    const int ts = bla_table_for(c, s, kPhoenix, fr, nullptr, stream, &levels, nullptr);
-    if (ts != FR_OK) return ts;
-    bla_table_args(b.t, s.t);
-    b.t.levels = levels;
-    const int bs = bla_steps_begin(s.t, stream, &b.t.steps);
-    if (bs != FR_OK) return bs;
-    const int st = launch_one_pass(c, stream, "deep_phoenix_bla_kernel", deep_phoenix_bla_kernel, b, b.g, b.q, s.wg_per_cu[0][1], false);
-    if (st != FR_OK) return st;
-    return bla_steps_end(s.t, stream);
-}
-
-/* ... and below 1e-290 (fr_render_deepx_phoenix): the same steps around the extended slot, deep[1][kPhoenix], and
- * deep_phoenix_x_kernel; the view's zoom string resolved as deep_entry resolves an extended view's */
-static int enqueue_deepx_phoenix(fr_ctx* c, const fr_params* p, const fr_phoenix_params* ph, const fr_deepx_view* v, uint32_t W,
-                                 uint32_t H, const fr_shard* shard, float* rgba, void* nu, int32_t* iter, hipStream_t stream,
-                                 bool out_frame)
-{
-    fr_shard norm;
-    uint32_t rows_local = 0;
-    const int sh = begin_shard(c, shard, H, &norm, &rows_local);
-    if (sh != FR_OK || rows_local == 0) return sh;
-    DeepAt at = {v->center_x, v->center_y, v->zoom, 0.0, 0, v->frac_bits};
-    const int rs = fr_deepx_resolve(v, &at.zm, &at.ze, &at.bits);
-    if (rs != FR_OK) return rs;
-    const int os = deep_slot_fill(c, kPhoenix, true, p, at, stream, ph);
-    if (os != FR_OK) return os;
-
-    DeepSlot& s = deep_slot(c, true, kPhoenix);
-    DeepPhoenixXArgs a;
-    memset(&a, 0, sizeof(a));
-    a.orbit = reinterpret_cast<const double2*>(s.o.dev); a.n_ref = s.o.len - 1;
-    a.mant = a.orbit + s.o.cap;
-    a.exp2 = reinterpret_cast<const int32_t*>(a.mant + s.o.cap);
-    a.zm = at.zm; a.ze = at.ze;                                  /* (zoom is not read) */
-    a.max_iter = p->max_iterations; a.aa = p->antialiasing_samples;
-    a.p = (double)ph->phoenix_p; a.r = (double)ph->phoenix_r;
-    a.stripe_density = p->stripe_density;
-    a.brightness = p->color_brightness; a.saturation = p->color_saturation; a.contrast = p->color_contrast;
-    a.flags = p->flags;
-    a.g = tile_geom(W, H, rows_local, &norm, out_frame);
-    a.rgba = reinterpret_cast<float4*>(rgba); a.nu = (double*)nu; a.iter = iter;
-    if (!(p->flags & FR_FLAG_DEEPX_PHOENIX_BLA))
-        return launch_one_pass(c, stream, "deep_phoenix_x_kernel", deep_phoenix_x_kernel, a, a.g, a.q, s.wg_per_cu[0][0], false);
-    /* as enqueue_deep_phoenix: the slot's extended table for this frame's dcmax (the whole frame's W and H, the zoom pair), then
-     * the flagged kernel between its counters' clearing and their copy */
-    DeepPhoenixXBlaArgs b;
-    memset(&b, 0, sizeof(b));
-    static_cast<DeepPhoenixXArgs&>(b) = a;
-    DeepXOrbit x;
-    x.mant = a.mant; x.exp2 = a.exp2; x.zm = a.zm; x.ze = a.ze;
-    const BlaFrame fr = {a.orbit, 0.0, a.g.W, a.g.H, a.p, a.r};
-    int levels = 0;
-    const int ts = bla_table_for(c, s, kPhoenix, fr, &x, stream, &levels, nullptr);
-    if (ts != FR_OK) return ts;
-    bla_table_args(b.t, s.t);
-    b.t.levels = levels;
-    const int bs = bla_steps_begin(s.t, stream, &b.t.steps);
-    if (bs != FR_OK) return bs;
-    const int st = launch_one_pass(c, stream, "deep_phoenix_x_bla_kernel", deep_phoenix_x_bla_kernel, b, b.g, b.q, s.wg_per_cu[0][1], false);
-    if (st != FR_OK) return st;
-    return bla_steps_end(s.t, stream);
+    b.orbit = reinterpret_cast<const double2*>(s.o.dev); b.n_ref = s.o.len - 1;
+    const DeepXOrbit* x = nullptr;
+    if constexpr (X) {                                           /* (zoom is not read) */
+        b.mant = b.orbit + s.o.cap;
+        b.exp2 = reinterpret_cast<const int32_t*>(b.mant + s.o.cap);
+        b.zm = at.zm; b.ze = at.ze;
+        x = &b;
+    } else {
+        b.zoom = p->zoom;
+    }
+    b.max_iter = p->max_iterations; b.aa = p->antialiasing_samples;
+    b.p = (double)ph->phoenix_p; b.r = (double)ph->phoenix_r;
+    b.stripe_density = p->stripe_density;
+    b.brightness = p->color_brightness; b.saturation = p->color_saturation; b.contrast = p->color_contrast;
+    b.flags = p->flags;
+    b.g = tile_geom(W, H, rows_local, &norm, out_frame);
+    b.rgba = reinterpret_cast<float4*>(rgba); b.nu = (double*)nu; b.iter = iter;
+    if (!(p->flags & (X ? FR_FLAG_DEEPX_PHOENIX_BLA : FR_FLAG_DEEP_PHOENIX_BLA))) {
+        DeepPhoenixBlock<X>& a = b;
+        return launch_one_pass(c, stream, X ? "deep_phoenix_x_kernel" : "deep_phoenix_kernel", deep_phoenix_kernel_of<X, false>(), a,
+                               a.g, a.q, s.wg_per_cu[0][0], false);
+    }
+    const BlaFrame fr = {b.orbit, b.zoom, b.g.W, b.g.H, b.p, b.r};
+    return launch_with_bla(c, stream, s, kPhoenix, fr, x, b.t, nullptr, [&] {
+        return launch_one_pass(c, stream, X ? "deep_phoenix_x_bla_kernel" : "deep_phoenix_bla_kernel", deep_phoenix_kernel_of<X, true>(),
+                               b, b.g, b.q, s.wg_per_cu[0][1], false);
+    });
 }
 
 /* ---- deep zoom sequences (fr_deep_sequence; the rules are in the header, the host planning in fr_deepseq.c) ---------------
@@ -1737,12 +1721,12 @@ static int enqueue_ssaa_staged(fr_ctx* c, const fr_params* p, uint32_t W, uint32
 }
 
 /* ---- render entry points --------------------------------------------------------------------------------------------
- * fr_render_shard, fr_render_phoenix, fr_render_mandelbulb, fr_render_deep_phoenix and the ten deep entry points (fr_render_deep, _deep_de,
- * _deep_ship, _deepx, _deepx_de, _deepx_ship, _deep_julia, _deepx_julia, _deep_julia_de, _deepx_julia_de; all through
- * deep_entry), each with its _async form:
- * their parameter checks, then render_sync / render_async with the planes beyond fr_output's three (ExtraPlanes;
- * fr_render_deep_de and fr_render_deepx_de alone have any) and the enqueue step as enqueue(shard, rgba, nu, iter, extra planes,
- * stream, out_frame) */
+ * fr_render_shard, fr_render_phoenix, fr_render_mandelbulb, the twelve deep entry points of DeepBlock's paths (fr_render_deep,
+ * _deep_de, _deep_ship, _deep_ship_de, _deepx, _deepx_de, _deepx_ship, _deepx_ship_de, _deep_julia, _deepx_julia, _deep_julia_de,
+ * _deepx_julia_de; all through deep_entry) and the two of deep Phoenix (fr_render_deep_phoenix, _deepx_phoenix; through
+ * deep_phoenix_entry), each with its _async form:
+ * their parameter checks, then render_sync / render_async with the planes beyond fr_output's three (ExtraPlanes; the six
+ * distance entry points alone have any) and the enqueue step as enqueue(shard, rgba, nu, iter, extra planes, stream, out_frame) */
 static int check_common(fr_ctx* c, const fr_params* p, uint32_t W, uint32_t H, const fr_output* out)
 {
     if (!c) return fr_set_error(FR_ERR_INVALID_ARG, "ctx is NULL");
@@ -2240,9 +2224,9 @@ extern "C" int fr_render_mandelbulb(fr_ctx* c, const fr_params* p, const fr_mand
         return enqueue_mandelbulb(c, p, mb, W, H, sh, rgba, nu, iter, s, out_frame); });
 }
 
-/* The twenty-four deep entry points: BASE names the path (DeepPath), async_entry the _async form (nullptr: the synchronous one),
- * validate() runs the path's validator once the pointers are known not to be NULL, and the enqueue step is enqueue_deep_view of
- * the view read into a DeepAt.  e: the block of the six distance entry points (fr_render_deep_de, _deepx_de, _deep_julia_de,
+/* The twenty-four deep entry points of DeepBlock's paths (deep Phoenix has four more, deep_phoenix_entry below): BASE names the
+ * path (DeepPath), async_entry the _async form (nullptr: the synchronous one), validate() runs the path's validator once the
+ * pointers are known not to be NULL, and the enqueue step is enqueue_deep_view of the view read into a DeepAt (deep_at_of).  e: the block of the six distance entry points (fr_render_deep_de, _deepx_de, _deep_julia_de,
  * _deepx_julia_de, _deep_ship_de, _deepx_ship_de), whose two planes travel as extra planes into the derivative's fields; nullptr for every other path. */
 template <class BASE, class VIEW, class Validate>
 static int deep_entry(const char* async_entry, fr_ctx* c, const fr_params* p, const VIEW* v, const fr_deep_de* e, uint32_t W,
@@ -2266,14 +2250,9 @@ static int deep_entry(const char* async_entry, fr_ctx* c, const fr_params* p, co
                      : (DeepPath<BASE>::ext ? "fr_render_deepx_de: neither fr_output nor fr_deep_de has a plane to write"
                                             : "fr_render_deep_de: neither fr_output nor fr_deep_de has a plane to write")};
     auto enqueue = [&](auto sh, auto rgba, auto nu, auto iter, void* const* xp, auto s, bool out_frame) {
-        DeepAt at = {v->center_x, v->center_y, nullptr, p->zoom, 0, v->frac_bits};
-        if constexpr (DeepPath<BASE>::ext) {     /* the zoom is the view's string: resolved here, with the automatic F */
-            at.zoom = v->zoom;
-            const int rs = fr_deepx_resolve(v, &at.zm, &at.ze, &at.bits);
-            if (rs != FR_OK) return rs;
-        } else if (!at.bits) {
-            at.bits = fr_deep_frac_bits(p->zoom);
-        }
+        DeepAt at;
+        const int rs = deep_at_of(p, v, &at);
+        if (rs != FR_OK) return rs;
         return enqueue_deep_view<BASE>(c, p, at, W, H, sh, rgba, nu, iter, s, out_frame, [&](BASE& a) {
             if constexpr (de) {                  /* s = zoom / H of the whole frame, whatever rows this part owns */
                 if constexpr (DeepPath<BASE>::ext) {     /* norm1(zm / H, ze) */
@@ -2406,60 +2385,53 @@ extern "C" int fr_render_deepx_julia(fr_ctx* c, const fr_params* p, const fr_dee
                                       [&] { return fr_deepx_julia_validate(p, v, W, H); });
 }
 
-/* fr_render_deep_phoenix: fr_render_phoenix's arguments with a deep view; its own validator and enqueue step */
-static int check_deep_phoenix(fr_ctx* c, const fr_params* p, const fr_phoenix_params* ph, const fr_deep_view* v, uint32_t W,
-                              uint32_t H, const fr_output* out)
+/* fr_render_deep_phoenix, fr_render_deepx_phoenix: fr_render_phoenix's arguments with a deep view.  deep_entry's steps with
+ * the Phoenix parameters: X names the storage, validate() runs the entry's validator, the enqueue step is enqueue_deep_phoenix. */
+template <bool X, class VIEW, class Validate>
+static int deep_phoenix_entry(const char* async_entry, fr_ctx* c, const fr_params* p, const fr_phoenix_params* ph, const VIEW* v,
+                              uint32_t W, uint32_t H, const fr_shard* shard, const fr_output* out, void* hip_stream,
+                              Validate&& validate)
 {
     if (!c) return fr_set_error(FR_ERR_INVALID_ARG, "ctx is NULL");
     if (!p || !ph || !v || !out) return fr_set_error(FR_ERR_INVALID_ARG, "params/phoenix params/deep view/out is NULL");
-    return fr_deep_phoenix_validate(p, ph, v, W, H);
+    const int st = validate();
+    if (st != FR_OK) return st;
+    auto enqueue = [&](auto sh, auto rgba, auto nu, auto iter, auto, auto s, bool out_frame) {
+        DeepAt at;
+        const int rs = deep_at_of(p, v, &at);
+        if (rs != FR_OK) return rs;
+        return enqueue_deep_phoenix<X>(c, p, ph, at, W, H, sh, rgba, nu, iter, s, out_frame);
+    };
+    return async_entry ? render_async(async_entry, c, H, shard, out, {}, hip_stream, enqueue)
+                       : render_sync(c, p, W, H, shard, out, {}, enqueue);
 }
 
 extern "C" int fr_render_deep_phoenix_async(fr_ctx* c, const fr_params* p, const fr_phoenix_params* ph, const fr_deep_view* v,
                                             uint32_t W, uint32_t H, const fr_shard* shard, const fr_output* out, void* hip_stream)
 {
-    const int st = check_deep_phoenix(c, p, ph, v, W, H, out);
-    if (st != FR_OK) return st;
-    return render_async("fr_render_deep_phoenix_async", c, H, shard, out, {}, hip_stream,
-                        [&](auto sh, auto rgba, auto nu, auto iter, auto, auto s, bool out_frame) {
-                            return enqueue_deep_phoenix(c, p, ph, v, W, H, sh, rgba, nu, iter, s, out_frame); });
+    return deep_phoenix_entry<false>("fr_render_deep_phoenix_async", c, p, ph, v, W, H, shard, out, hip_stream,
+                                     [&] { return fr_deep_phoenix_validate(p, ph, v, W, H); });
 }
 
 extern "C" int fr_render_deep_phoenix(fr_ctx* c, const fr_params* p, const fr_phoenix_params* ph, const fr_deep_view* v, uint32_t W,
                                       uint32_t H, const fr_shard* shard, const fr_output* out)
 {
-    const int st = check_deep_phoenix(c, p, ph, v, W, H, out);
-    if (st != FR_OK) return st;
-    return render_sync(c, p, W, H, shard, out, {}, [&](auto sh, auto rgba, auto nu, auto iter, auto, auto s, bool out_frame) {
-        return enqueue_deep_phoenix(c, p, ph, v, W, H, sh, rgba, nu, iter, s, out_frame); });
-}
-
-/* fr_render_deepx_phoenix: the same with an extended view */
-static int check_deepx_phoenix(fr_ctx* c, const fr_params* p, const fr_phoenix_params* ph, const fr_deepx_view* v, uint32_t W,
-                               uint32_t H, const fr_output* out)
-{
-    if (!c) return fr_set_error(FR_ERR_INVALID_ARG, "ctx is NULL");
-    if (!p || !ph || !v || !out) return fr_set_error(FR_ERR_INVALID_ARG, "params/phoenix params/deep view/out is NULL");
-    return fr_deepx_phoenix_validate(p, ph, v, W, H);
+    return deep_phoenix_entry<false>(nullptr, c, p, ph, v, W, H, shard, out, nullptr,
+                                     [&] { return fr_deep_phoenix_validate(p, ph, v, W, H); });
 }
 
 extern "C" int fr_render_deepx_phoenix_async(fr_ctx* c, const fr_params* p, const fr_phoenix_params* ph, const fr_deepx_view* v,
                                              uint32_t W, uint32_t H, const fr_shard* shard, const fr_output* out, void* hip_stream)
 {
-    const int st = check_deepx_phoenix(c, p, ph, v, W, H, out);
-    if (st != FR_OK) return st;
-    return render_async("fr_render_deepx_phoenix_async", c, H, shard, out, {}, hip_stream,
-                        [&](auto sh, auto rgba, auto nu, auto iter, auto, auto s, bool out_frame) {
-                            return enqueue_deepx_phoenix(c, p, ph, v, W, H, sh, rgba, nu, iter, s, out_frame); });
+    return deep_phoenix_entry<true>("fr_render_deepx_phoenix_async", c, p, ph, v, W, H, shard, out, hip_stream,
+                                    [&] { return fr_deepx_phoenix_validate(p, ph, v, W, H); });
 }
 
 extern "C" int fr_render_deepx_phoenix(fr_ctx* c, const fr_params* p, const fr_phoenix_params* ph, const fr_deepx_view* v, uint32_t W,
                                        uint32_t H, const fr_shard* shard, const fr_output* out)
 {
-    const int st = check_deepx_phoenix(c, p, ph, v, W, H, out);
-    if (st != FR_OK) return st;
-    return render_sync(c, p, W, H, shard, out, {}, [&](auto sh, auto rgba, auto nu, auto iter, auto, auto s, bool out_frame) {
-        return enqueue_deepx_phoenix(c, p, ph, v, W, H, sh, rgba, nu, iter, s, out_frame); });
+    return deep_phoenix_entry<true>(nullptr, c, p, ph, v, W, H, shard, out, nullptr,
+                                    [&] { return fr_deepx_phoenix_validate(p, ph, v, W, H); });
 }
 
 /* fr_render_deep_ship_de, fr_render_deepx_ship_de: fr_render_deep_de's five planes on the two ship paths, deriv four doubles per
